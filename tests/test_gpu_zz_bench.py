@@ -1,7 +1,8 @@
 """-m gpu: bench.py as the driver runs it.  (1) `python bench.py --gpus 2` launches ITSELF under torch.distributed.run (one process per GPU) and
 prints one JSON line from rank 0; on the one-GPU test box BENCH_SAME_GPU=1 puts both ranks on GPU 0 over gloo, which exercises the whole N>1
 branch -- sharded data generation, the one-time weight broadcast (no silent fallback), barrier / max-over-ranks timing -- with the HIP kernels
-doing the arithmetic.  (2) the default N=1 line carries the AlexNet / NiN conv-ops legs under `conv_ops`."""
+doing the arithmetic.  (2) the --full N=1 line carries the AlexNet / NiN conv-ops legs under `conv_ops`.  (3) a plain N=1 run does the headline only, and
+--dump-outputs writes what its last timed step computed."""
 import json
 import os
 import subprocess
@@ -75,7 +76,7 @@ def test_world_size_mismatch_is_an_error():
 
 
 def test_default_line_carries_conv_ops():
-    r, lines = _bench(["--steps", "2", "--warmup", "1", "--settle-ms", "100"])
+    r, lines = _bench(["--full", "--steps", "2", "--warmup", "1", "--settle-ms", "100"])
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1
     out = json.loads(lines[0])
@@ -95,3 +96,35 @@ def test_default_line_carries_conv_ops():
         ind, ch = cf[f"config5_{nm}_b64_bf16_nhwc_independent"], cf[f"config5_{nm}_b64_bf16_nhwc"]
         assert "no edges" in ind["launch"] and "chain" in ch["launch"] and ind["ms_per_step"] < 1.15 * ch["ms_per_step"]
     assert all("error" not in v and v["value"] > 0 and 0 < v["roofline"]["frac"] <= 1 for v in cf.values()), cf
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the headline line only (nothing that takes runs of its own), K timed steps; --dump-outputs writes
+    every op's output of the last step -- whole where small, a fixed sample where large -- and both are the oracle's products of the same inputs."""
+    import numpy as np
+    import bench
+    from oracle import boda_oracle as bo
+    d = tmp_path / "dump"
+    r, lines = _bench(["--steps", "3", "--warmup", "1", "--settle-ms", "0", "--dump-outputs", str(d)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["unit"] == "TFLOP/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert not {"conv_ops", "configs", "cpu_baseline", "compile", "ref_style_gpu", "summary"} & set(out) and out["roofline"]["kernel"] is None
+    ops = bench.sgemm_full_ops()
+    files = sorted(os.listdir(d))
+    assert files == [f"op{i:02d}_c.npy" for i in range(len(ops))]
+    assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+    cap = bench.DUMP_BUDGET_ELEMS // len(ops)
+    for i, op in enumerate(ops):
+        n = op.sgemm_geom()["M"]
+        if n > 1024:
+            continue
+        got = np.load(d / f"op{i:02d}_c.npy")
+        assert got.dtype == np.float32
+        want = bo.sgemm(bo.gen_sgemm_a(n, n), bo.gen_sgemm_b(n, n))
+        if n * n <= cap:
+            assert np.array_equal(got, want), n
+        else:
+            idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n * n, cap, replace=False))
+            assert got.shape == (cap,) and np.array_equal(got, want.reshape(-1)[idx]), n
