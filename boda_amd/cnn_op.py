@@ -156,6 +156,30 @@ def add_codegen_annotations(op: Op, tune: OpTune, tile_wisdom=None) -> Op:
     return a
 
 
+BCONV_FUNCS = ("hip_bconv_in", "hip_bconv_biases", "hip_bconv_filts")   # the order of the reference's three calls (src/rtc_fwd.cc:398-400)
+
+
+def add_bck_conv_annotations(op: Op, tune: OpTune) -> tuple:
+    """-> (in_op, biases_op, filts_op): the three annotated function ops of a BckConv, in the order src/rtc_fwd.cc:398-400 calls them -- the data gradient
+    (hip_bconv_in), the bias gradient (hip_bconv_biases), the filter gradient (hip_bconv_filts).  fp32 and reference layouts only (bf16 / channels-last gradients
+    are not provided); a tile in the tune travels with the data and filter gradient functions."""
+    if op.get_type() != "BckConv":
+        raise RtErr(f"add_bck_conv_annotations: op type {op.get_type()!r} is not BckConv")
+    op.bck_conv_geom()
+    if tune.use_be not in ("", "hip") or tune.use_culibs or tune.k1conv or tune.tconv or tune.ipconv:
+        raise UnsupErr(f"BckConv variants of op_tune={tune.to_str()} are generated by the reference's CUCL code generator; be=hip provides hip_bconv_*")
+    if tune.hip_dtype not in ("", "f32") or tune.hip_layout or tune.hip_algo or tune.hip_out:
+        raise UnsupErr("BckConv: fp32 gradients in reference layout only (no bf16, channels-last or Winograd variant)")
+    outs = []
+    for fn in BCONV_FUNCS:
+        a = op.copy()
+        a.set_func_name(fn)
+        if tune.hip_tile and fn != "hip_bconv_biases":
+            a.str_vals["hip_tile"] = tune.hip_tile
+        outs.append(a)
+    return tuple(outs)
+
+
 # arg tables of the native side-door functions (the stubs test/rtc/cublas_sgemm.cucl:1-4, cudnn_conv.cucl:1-7)
 NATIVE_ARGS: Dict[str, tuple] = {
     "hip_sgemm": (("a", "IN"), ("b", "IN"), ("c", "OUT")),
@@ -167,7 +191,11 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_conv_winograd": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),
     "hip_conv_nhwc": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),
     "hip_conv_k1_chain": (("filts", "IN"), ("biases", "IN"), ("filts2", "IN"), ("biases2", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),
-    "hip_conv_filts_kmajor": (("filts", "IN"), ("filts_km", "OUT")),   # filts as [K + 128][out_chan padded to 4]: what hip_conv's optional filts_km arg takes
+    "hip_conv_filts_kmajor": (("filts", "IN"), ("filts_km", "OUT")),
+    # BckConv's gradients: the reference templates' arg lists (test/rtc/BckConv_in_grad_loss.cucl, BckConv_filts_grad_loss.cucl, BckConv_biases_grad_loss.cucl)
+    "hip_bconv_in": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),
+    "hip_bconv_filts": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT")),
+    "hip_bconv_biases": (("out_grad_loss", "IN"), ("biases_grad_loss", "OUT")),   # filts as [K + 128][out_chan padded to 4]: what hip_conv's optional filts_km arg takes
 }
 
 

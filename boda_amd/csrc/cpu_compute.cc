@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <omp.h>
 
@@ -139,12 +140,13 @@ struct cpu_compute_t : public rtc_compute_t {
   // ---- functions: the native side door only
   static bool is_sgemm(string const &fn) { return fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "cpu_sgemm"; }
   static bool is_conv(string const &fn) { return fn == "hip_conv" || fn == "cudnn_conv" || fn == "cpu_conv_fwd"; }
+  static bool is_bck(string const &fn) { return fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases"; }
   void compile(vect_rtc_func_info_t const &func_infos, rtc_compile_opts_t const &) override {
     assert_st(init_done);
     for (auto const &fi : func_infos) {
       if (funcs.count(fi.func_name)) rt_err("compile: function '" + fi.func_name + "' already exists");
       string const fn = fi.op.has_func_name() ? fi.op.get_func_name() : string();
-      if (!is_sgemm(fn) && !is_conv(fn)) unsup_err("be=cpu runs the native sgemm / Convolution functions only (hip_sgemm, hip_conv and their aliases); '" +
+      if (!is_sgemm(fn) && !is_conv(fn) && !is_bck(fn)) unsup_err("be=cpu runs the native sgemm / Convolution / BckConv functions only (hip_sgemm, hip_conv and their aliases, hip_bconv_*); '" +
                                                     (fn.empty() ? fi.func_name : fn) + "' is generated CUCL source, which needs a GPU backend");
       if (is_conv(fn)) (void)fi.op.get_u32("conv_has_relu");
       funcs.emplace(fi.func_name, cpu_func_t{fi});
@@ -205,6 +207,86 @@ struct cpu_compute_t : public rtc_compute_t {
         } });
   }
 
+  // BckConv's gradients: the reference templates' loops, one fmaf chain per output in exactly their order (test/rtc/BckConv_in_grad_loss.cucl,
+  // BckConv_filts_grad_loss.cucl, BckConv_biases_grad_loss.cucl), parallel over outputs.  g is the forward convolution's geometry.
+  static void bconv_in(float const *filts, float const *ogl, float *igl, conv_geom_c const &g) {
+#pragma omp parallel for collapse(2) schedule(static)
+    for (long img = 0; img < g.B; ++img)
+      for (long c = 0; c < g.C; ++c)
+        for (long y = 0; y < g.H; ++y)
+          for (long x = 0; x < g.W; ++x) {
+            long const oxb = std::max<long>(0, x + g.PX - g.KW + g.SX) / g.SX, oxe = std::min<long>((x + g.PX) / g.SX + 1, g.OW);
+            long const oyb = std::max<long>(0, y + g.PY - g.KH + g.SY) / g.SY, oye = std::min<long>((y + g.PY) / g.SY + 1, g.OH);
+            float v = 0.f;
+            for (long oc = 0; oc < g.OC; ++oc) {
+              long fx = x + g.PX - oxb * g.SX;   // out_x ascending (outer), filter taps descending
+              for (long ox = oxb; ox < oxe; ++ox, fx -= g.SX) {
+                long fy = y + g.PY - oyb * g.SY;
+                for (long oy = oyb; oy < oye; ++oy, fy -= g.SY)
+                  v = fmaf(ogl[((img * g.OC + oc) * g.OH + oy) * g.OW + ox], filts[((oc * g.C + c) * g.KH + fy) * g.KW + fx], v);
+              }
+            }
+            igl[((img * g.C + c) * g.H + y) * g.W + x] = v;
+          }
+  }
+  static void bconv_filts(float const *in, float const *ogl, float *fgl, conv_geom_c const &g) {
+#pragma omp parallel for collapse(2) schedule(static)
+    for (long oc = 0; oc < g.OC; ++oc)
+      for (long c = 0; c < g.C; ++c)
+        for (long fy = 0; fy < g.KH; ++fy)
+          for (long fx = 0; fx < g.KW; ++fx) {
+            long oyb = 0, iyb = fy - g.PY; while (iyb < 0) { iyb += g.SY; ++oyb; }
+            long oxb = 0, ixb = fx - g.PX; while (ixb < 0) { ixb += g.SX; ++oxb; }
+            float v = 0.f;
+            for (long img = 0; img < g.B; ++img) {
+              float const *ip = in + (img * g.C + c) * g.H * g.W, *op = ogl + (img * g.OC + oc) * g.OH * g.OW;
+              long oy = oyb;
+              for (long iy = iyb; iy < g.H && oy < g.OH; iy += g.SY, ++oy) {
+                long ox = oxb;
+                for (long ix = ixb; ix < g.W && ox < g.OW; ix += g.SX, ++ox) v = fmaf(ip[iy * g.W + ix], op[oy * g.OW + ox], v);
+              }
+            }
+            fgl[((oc * g.C + c) * g.KH + fy) * g.KW + fx] = v;
+          }
+  }
+  static void bconv_biases(float const *ogl, float *bgl, conv_geom_c const &g) {
+#pragma omp parallel for schedule(static)
+    for (long oc = 0; oc < g.OC; ++oc) {
+      float v = 0.f;
+      for (long img = 0; img < g.B; ++img)
+        for (long e = 0; e < g.OH * g.OW; ++e) v += ogl[(img * g.OC + oc) * g.OH * g.OW + e];
+      bgl[oc] = v;
+    }
+  }
+  void run_bck(string const &fn, map_str_rtc_arg_t const &am) {
+    string const ognm = var_of(am, "out_grad_loss");
+    dims_t const og = get_var_dims(ognm); need_float(og, "out_grad_loss");
+    if (og.sz() != 4) rt_err(fn + ": out_grad_loss must be img:chan:y:x");
+    conv_geom_c g; memset(&g, 0, sizeof(g));
+    g.B = og.dsz("img"); g.OC = og.dsz("chan"); g.OH = og.dsz("y"); g.OW = og.dsz("x");
+    if (fn == "hip_bconv_biases") {
+      string const bnm = var_of(am, "biases_grad_loss"); dims_t const b = get_var_dims(bnm); need_float(b, "biases_grad_loss");
+      if (b.dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
+      bconv_biases((float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, bnm).buf.get(), g);
+      return;
+    }
+    bool const din = fn == "hip_bconv_in";
+    string const fnm = var_of(am, din ? "filts" : "filts_grad_loss"), inm = var_of(am, din ? "in_grad_loss" : "in");
+    dims_t const f = get_var_dims(fnm), in = get_var_dims(inm);
+    need_float(f, "filts"); need_float(in, "in");
+    auto si = am.find("stride"), pi = am.find("in_pad");
+    if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
+    dims_t const stride = si->second.get_dims(*this), in_pad = pi->second.get_dims(*this);
+    if (f.sz() != 4 || in.sz() != 4 || stride.sz() != 2 || in_pad.sz() != 2) rt_err(fn + ": filts out_chan:in_chan:y:x, in img:chan:y:x, stride / in_pad y:x");
+    g.C = in.dsz("chan"); g.H = in.dsz("y"); g.W = in.dsz("x"); g.KH = f.dsz("y"); g.KW = f.dsz("x");
+    g.SY = stride.dsz("y"); g.SX = stride.dsz("x"); g.PY = in_pad.dsz("y"); g.PX = in_pad.dsz("x");
+    if (!g.SY || !g.SX) rt_err(fn + ": zero stride");
+    if (f.dsz("out_chan") != (uint32_t)g.OC || f.dsz("in_chan") != (uint32_t)g.C || in.dsz("img") != (uint32_t)g.B) rt_err(fn + ": inconsistent filts / in / out_grad_loss dims");
+    if ((g.H + 2 * g.PY - g.KH) / g.SY + 1 != g.OH || (g.W + 2 * g.PX - g.KW) / g.SX + 1 != g.OW) rt_err(fn + ": out_grad_loss dims do not match in / filts / stride / in_pad");
+    if (din) bconv_in((float const *)must_find(vis, fnm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, inm).buf.get(), g);
+    else bconv_filts((float const *)must_find(vis, inm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, fnm).buf.get(), g);
+  }
+
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
     auto fit = funcs.find(rfc.rtc_func_name);
@@ -213,7 +295,8 @@ struct cpu_compute_t : public rtc_compute_t {
     string const &fn = fi.op.get_func_name();
     map_str_rtc_arg_t const &am = rfc.arg_map;
     double const tb = now_ms();
-    if (is_sgemm(fn)) {
+    if (is_bck(fn)) run_bck(fn, am);
+    else if (is_sgemm(fn)) {
       string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");
       dims_t const a = get_var_dims(an), b = get_var_dims(bn), c = get_var_dims(cn);
       need_float(a, "a"); need_float(b, "b"); need_float(c, "c");

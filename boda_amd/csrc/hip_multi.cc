@@ -30,6 +30,7 @@
 
 #include <hip/hip_runtime.h>
 #include <sstream>
+#include <set>
 
 namespace bodahip {
 
@@ -121,6 +122,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
   std::vector<p_rtc_compute_t> subs;
   std::map<string, multi_var_t> vis;
   std::map<string, bool> func_native;
+  std::set<string> func_img_sum;   // native functions that reduce over the images (BckConv filter / bias gradients): refused on a sharded run
   std::map<string, gen_func_t> func_gen;       // generated functions: their index declaration
   std::vector<hipEvent_t> peer_evs;            // per device: marks the end of its last peer copy out of device 0
   static constexpr uint32_t kNoCall = 0xffffffffu;   // per-device call id of a call that launched nothing there (an empty shard)
@@ -335,16 +337,20 @@ struct hip_multi_compute_t : public rtc_compute_t {
     for (auto const &fi : func_infos) {
       bool const nat = native_kernels_t::is_native_func_name(fi.op.has_func_name() ? fi.op.get_func_name() : string());
       func_native[fi.func_name] = nat;
+      // BckConv's filter / bias gradients sum over the images: on img shards every device would hold a partial sum, and no cross-device reduction exists here
+      if (nat && n() > 1 && (fi.op.get_func_name() == "hip_bconv_filts" || fi.op.get_func_name() == "hip_bconv_biases")) func_img_sum.insert(fi.func_name);
       if (!nat) func_gen[fi.func_name] = scan_gen_func(all_src, fi.func_name);
     }
   }
-  void release_func(string const &fn) override { must_find(func_native, fn); for (auto &s : subs) s->release_func(fn); func_native.erase(fn); func_gen.erase(fn); }
-  void release_all_funcs() override { for (auto &s : subs) s->release_all_funcs(); func_native.clear(); func_gen.clear(); }
+  void release_func(string const &fn) override { must_find(func_native, fn); for (auto &s : subs) s->release_func(fn); func_native.erase(fn); func_gen.erase(fn); func_img_sum.erase(fn); }
+  void release_all_funcs() override { for (auto &s : subs) s->release_all_funcs(); func_native.clear(); func_gen.clear(); func_img_sum.clear(); }
 
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
     auto fit = func_native.find(rfc.rtc_func_name);
     if (fit == func_native.end()) rt_err("run: unknown function '" + rfc.rtc_func_name + "' (not compiled, or released)");
+    if (func_img_sum.count(rfc.rtc_func_name)) unsup_err("multi-device backend: '" + rfc.rtc_func_name + "' (a BckConv filter / bias gradient) sums over the images, which would need a "
+                                                        "cross-device reduction; only the data gradient (hip_bconv_in) runs on img shards");
     if (!fit->second) {
       bool sharded = false;
       for (auto const &kv : rfc.arg_map) if (kv.second.is_valid() && kv.second.is_var() && must_find(vis, kv.second.n).shard_dim >= 0) sharded = true;

@@ -46,7 +46,15 @@ struct native_kernels_t::impl_t {
 };
 
 
-struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false; int rows = 0, cg = 0; };
+struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false, bconv_in = false, bconv_filts = false; int rows = 0, cg = 0; };
+
+struct bconv_args_t { // must match kernels/bconv_in_f32.hip, kernels/bconv_filts_f32.hip
+  float const *a; float const *b; float *d;
+  float *ws; long ws_slab;
+  int B, C, H, W, OC, OH, OW;
+  int tiles_i, tiles_j, ksl, kt_per;
+  unsigned a_bytes, b_bytes, d_bytes;
+};
 
 struct rows_args_t { // must match kernels/conv_nhwc_rows_bf16.hip
   void const *filts; void const *in; void *out; float const *bias;
@@ -72,6 +80,10 @@ bool rows_auto(conv_geom_t const &g, int num_cus, string const &tile);
 bool apply_post_ops(op_base_t const &op, conv_geom_t &g, post_ops_t &post, char const *what);
 bool plan_ipconv_dma(conv_geom_t const &g, int num_cus, plan_t &p);
 plan_t plan_conv(conv_geom_t const &g, int num_cus, string const &tile, bool bf16 = false, string const &k1s = string(), bool allow_splitk = true, bool exact = true);
+plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile);       // BckConv data gradient (kernels/bconv_in_f32.hip)
+plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile);    // BckConv filter gradient, in-launch K slices (kernels/bconv_filts_f32.hip)
+plan_t plan_bconv_biases();                                                          // BckConv bias gradient (kernels/bconv_filts_f32.hip -DBIAS_ONLY)
+long bconv_in_tiles(conv_geom_t const &g, int BJ);                                   // pel tiles over all SY x SX phases (the kernel's walk)
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log);
 void ensure_ws(native_kernels_t::impl_t *impl, native_host_t *host, size_t need);
 void call_ws_make_room(native_kernels_t::impl_t *impl, native_host_t *host, size_t need);

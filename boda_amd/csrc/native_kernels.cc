@@ -43,6 +43,10 @@ void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
   if (fn == "hip_conv" || fn == "cudnn_conv" || fn == "hip_conv_bf16" || fn == "hip_conv_winograd" || fn == "hip_conv_nhwc" || fn == "hip_conv_nhwc_grp" || fn == "hip_conv_nhwc_multi" || fn == "hip_conv_nhwc_set") { (void)fi.op.get_u32("conv_has_relu"); return; } // required, as src/culibs-wrap.cc:198
   if (fn == "hip_conv_k1_chain") { (void)fi.op.get_u32("conv_has_relu"); (void)fi.op.get_u32("conv_has_relu2"); return; }
   if (fn == "hip_conv_filts_kmajor") return;
+  if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases") {   // BckConv's gradients: the op must carry the geometry
+    for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
+    return;
+  }
   rt_err("unknown/unhandled native hip function: " + fn);
 }
 void native_kernels_t::set_tune(string const &key, string const &val) {
@@ -62,7 +66,7 @@ void launch(native_host_t *host, kernel_t &k, gemm_args_t &a, tile_cfg_t const &
 
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log) {
   vect_string opts = p.defs; opts.push_back("-DKNAME=" + p.kname);
-  return hiprtc_compile(p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
+  return hiprtc_compile(p.bconv_in ? k_src_bconv_in_f32 : p.bconv_filts ? k_src_bconv_filts_f32 : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
 }
 
 // grow-only scratch shared by the split-K slabs and the Winograd-domain tensors (like the reference's cudnn scratch var)
@@ -688,6 +692,74 @@ kernel_t &get_kernel(native_kernels_t::impl_t *impl, native_host_t *host, plan_t
   hip_err_chk(hipModuleLoadData(&k.mod, code.data()), "hipModuleLoadData(native)");
   hip_err_chk(hipModuleGetFunction(&k.func, k.mod, p.kname.c_str()), "hipModuleGetFunction(native)");
   return impl->kernels.emplace(key, k).first->second;
+}
+
+
+
+// ---- BckConv: data, filter and bias gradients (kernels/bconv_in_f32.hip, kernels/bconv_filts_f32.hip).  g is the FORWARD convolution's geometry; the tile comes from
+// the "conv_tile" tune (BODAHIP_CONV_TILE, or a function's hip_tile).
+static bconv_args_t bconv_args(conv_geom_t const &g) {
+  bconv_args_t a; memset(&a, 0, sizeof(a));
+  a.B = g.B; a.C = g.C; a.H = g.H; a.W = g.W; a.OC = g.OC; a.OH = g.OH; a.OW = g.OW;
+  return a;
+}
+void native_kernels_t::bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g) {
+  plan_t const p = plan_bconv_in(g, host->nh_num_cus(), tune_of(impl, "conv_tile"));
+  kernel_t &k = get_kernel(impl, host, p);
+  bconv_args_t a = bconv_args(g);
+  a.a = filts; a.b = out_grad; a.d = in_grad;
+  a.a_bytes = (unsigned)(4ull * g.OC * g.C * g.KH * g.KW); a.b_bytes = (unsigned)(4ull * g.B * g.OC * g.OH * g.OW); a.d_bytes = (unsigned)(4ull * g.B * g.C * g.H * g.W);
+  a.tiles_i = (g.C + p.cfg.BI - 1) / p.cfg.BI; a.tiles_j = (int)bconv_in_tiles(g, p.cfg.BJ); a.ksl = 1;
+  uint32_t const grid = (uint32_t)a.tiles_i * (uint32_t)a.tiles_j;
+  void *params[] = {&a};
+  if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, (uint32_t)p.cfg.threads(), params), "hipModuleLaunchKernel(bconv_in)");
+  int const TY = (g.KH + g.SY - 1) / g.SY, TX = (g.KW + g.SX - 1) / g.SX;
+  last_launch.kernel = p.kname; last_launch.cfg = p.cfg; last_launch.grid = grid; last_launch.block = p.cfg.threads();
+  last_launch.flops = 2.0 * g.B * g.H * g.W * g.C * ((double)g.OC * TY * TX);   // (the phase GEMMs as run: M = img x pels, N = in_chan, K = out_chan x taps)
+  last_launch.algo_bytes = (double)a.a_bytes + a.b_bytes + a.d_bytes;
+}
+void native_kernels_t::bconv_filts(float const *in, float const *out_grad, float *filts_grad, conv_geom_t const &g) {
+  plan_t const p = plan_bconv_filts(g, host->nh_num_cus(), tune_of(impl, "conv_tile"));
+  kernel_t &k = get_kernel(impl, host, p);
+  bconv_args_t a = bconv_args(g);
+  a.a = out_grad; a.b = in; a.d = filts_grad;
+  a.a_bytes = (unsigned)(4ull * g.B * g.OC * g.OH * g.OW); a.b_bytes = (unsigned)(4ull * g.B * g.C * g.H * g.W); a.d_bytes = (unsigned)(4ull * g.OC * g.C * g.KH * g.KW);
+  long const NJ = (long)g.C * g.KH * g.KW, K = (long)g.B * g.OH * g.OW, nkt = (K + p.cfg.BK - 1) / p.cfg.BK;
+  a.tiles_i = (g.OC + p.cfg.BI - 1) / p.cfg.BI; a.tiles_j = (int)((NJ + p.cfg.BJ - 1) / p.cfg.BJ);
+  a.ksl = p.cfg.SPLITK; a.kt_per = (int)((nkt + a.ksl - 1) / a.ksl);
+  long const tiles = (long)a.tiles_i * a.tiles_j;
+  if (a.ksl > 1) {   // the call's K-slice workspace: tickets (zero between launches), then KSL slabs per tile (see setup_ksl)
+    size_t const tick_b = ((size_t)tiles * 4 + 255) & ~size_t(255), slab_b = (size_t)p.cfg.BI * p.cfg.BJ * 4;
+    size_t const total = tick_b + (size_t)tiles * a.ksl * slab_b;
+    if ((size_t)a.ksl * slab_b >= 0x7ffffff0ull || total >= (size_t(1) << 32)) unsup_err("hip_bconv_filts: K-slice workspace too large");
+    string const key = "ksl:bconv:" + std::to_string((uintptr_t)in) + ":" + std::to_string((uintptr_t)out_grad) + ":" + std::to_string((uintptr_t)filts_grad) + ":" +
+                       std::to_string(total) + ":" + p.cfg.str();
+    auto it = impl->ktabs.find(key);
+    if (it == impl->ktabs.end()) {
+      if (host->nh_capturing()) rt_err("graph capture: the K-slice workspace of this call is not allocated yet -- run the call list once before capturing it");
+      void *dev = nullptr;
+      call_ws_make_room(impl, host, total);
+      hip_err_chk(hipMalloc(&dev, total), "hipMalloc(K-slice workspace)"); impl->call_ws_bytes += total;
+      hip_err_chk(hipMemsetAsync(dev, 0, tick_b, host->nh_stream()), "hipMemsetAsync(K-slice tickets)");
+      it = impl->ktabs.emplace(key, dev).first;
+    }
+    a.ws = (float *)it->second; a.ws_slab = (long)(tick_b / 4);
+  }
+  uint32_t const grid = (uint32_t)(tiles * a.ksl);
+  void *params[] = {&a};
+  if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, (uint32_t)p.cfg.threads(), params), "hipModuleLaunchKernel(bconv_filts)");
+  last_launch.kernel = p.kname; last_launch.cfg = p.cfg; last_launch.grid = grid; last_launch.block = p.cfg.threads();
+  last_launch.flops = 2.0 * g.OC * (double)NJ * K;
+  last_launch.algo_bytes = (double)a.a_bytes + a.b_bytes + a.d_bytes;
+}
+void native_kernels_t::bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g) {
+  kernel_t &k = get_kernel(impl, host, plan_bconv_biases());
+  bconv_args_t a = bconv_args(g);
+  a.a = out_grad; a.d = biases_grad;
+  void *params[] = {&a};
+  hip_err_chk(host->nh_launch(k.func, (uint32_t)g.OC, 1, 256, params), "hipModuleLaunchKernel(bconv_biases)");
+  last_launch.kernel = "bodahip_bconv_biases"; last_launch.cfg = tile_cfg_t(); last_launch.grid = (uint32_t)g.OC; last_launch.block = 256;
+  last_launch.flops = (double)g.B * g.OC * g.OH * g.OW; last_launch.algo_bytes = 4.0 * ((double)g.B * g.OC * g.OH * g.OW + g.OC);
 }
 
 

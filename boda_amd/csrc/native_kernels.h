@@ -15,6 +15,8 @@
 //                                       small members handed to the hardware dispatcher together, longest first (kernels/conv_nhwc_multi_bf16.hip)
 //     hip_conv_nhwc_set                 up to 16 independent hip_conv_nhwc convolutions, each on ITS OWN specialised kernel code, as one launch: an inception module's
 //                                       3x3 / 5x5 / pool-projection convolutions (the kernel sources instantiated per member inside one wrapper kernel, built at run time)
+//     hip_bconv_in / _filts / _biases   BckConv's three gradients (fp32, NCHW / OIHW): args filts out_grad_loss stride(REF) in_pad(REF) in_grad_loss |
+//                                       in out_grad_loss stride(REF) in_pad(REF) filts_grad_loss | out_grad_loss biases_grad_loss  (test/rtc/BckConv_*.cucl)
 //     hip_conv_winograd                 same contract as hip_conv; 3x3 / stride-1 layers through F(2x2,3x3) Winograd (mrd <= ~2e-3)
 // and lands them on kernels/gemm_conv_f32.hip (and, for short-K 1x1 convs with a long pel axis, kernels/k1_stream_f32.hip),
 // specialised with hiprtc per shape class at first use.
@@ -99,6 +101,11 @@ struct native_kernels_t {
   // convolution's geometry, mid (optional) also receives its output
   void conv_k1_chain(float const *filts, float const *biases, float const *filts2, float const *biases2, float const *in, float *out, float *mid, conv_geom_t const &g, int oc2,
                      bool relu2, int out_ctot, int out_coff);
+  // BckConv gradients (fp32, reference layouts; g = the forward convolution's geometry, out_grad_loss has g.OH x g.OW planes): kernels/bconv_in_f32.hip (data gradient,
+  // bit-identical to the reference's chain), kernels/bconv_filts_f32.hip (filter gradient with deterministic in-launch K slices; bias gradient)
+  void bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g);
+  void bconv_filts(float const *in, float const *out_grad, float *filts_grad, conv_geom_t const &g);
+  void bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g);
   void conv_winograd(float const *filts, float const *biases, float const *in, float *out, conv_geom_t const &g, int out_ctot, int out_coff);
 
   // tuning overrides ("" clears): key "sgemm_tile" / "conv_tile" -> "BIxBJxBKxWIxWJ[xMINW[xSPLITK[xMT]]]"; key "k1_stream" -> "off" | "WIxWJxOCBxCB[xMINW]";

@@ -1131,4 +1131,75 @@ std::vector<sgemm_part_t> plan_sgemm_parts(uint32_t M, uint32_t N, uint32_t K, i
 }
 
 
+
+// ---- BckConv (kernels/bconv_in_f32.hip, kernels/bconv_filts_f32.hip).  Tile strings "BIxBJxBKxWIxWJ[xMINW[xKSL]]"; a tile of fewer than seven fields leaves the
+// K-slice count of the filter gradient to the planner.  Both kernels run WI x WJ waves of 32 x 32 MFMA blocks; every thread stages one column and whole rows.
+static void check_bconv_cfg(tile_cfg_t const &c, bool filts) {
+  int const nt = c.WI * c.WJ * 64;
+  bool ok = c.BI > 0 && c.BJ > 0 && c.BK > 0 && c.WI > 0 && c.WJ > 0 && nt <= 1024 && c.MT == 32 && c.BI % (c.WI * 32) == 0 && c.BJ % (c.WJ * 32) == 0 && c.BK % 2 == 0 &&
+            nt % c.BJ == 0 && (c.BK * c.BI) % nt == 0 && (c.BK * c.BJ) % nt == 0 && (filts ? (nt % c.BK == 0) : (nt % c.BI == 0)) && c.MINW >= 1 && c.MINW <= 8 &&
+            c.SPLITK >= 1 && c.SPLITK <= 32 && (filts || c.SPLITK == 1) && c.PF == 1 && c.SW == 0 && c.KHO == 0;
+  int const accs = (c.BI / (c.WI * 32)) * (c.BJ / (c.WJ * 32));
+  ok = ok && accs * 16 <= 128 && 2ull * c.BK * (c.BI + 4 + c.BJ + 4) * 4 <= 160 * 1024;
+  if (!ok) unsup_err(string(filts ? "hip_bconv_filts" : "hip_bconv_in") + ": unsupported tile configuration " + c.str());
+}
+static tile_cfg_t bconv_default_cfg(int ni, int BK) {   // i-extent (channels) picks the i tile; 4 waves
+  tile_cfg_t c; c.BJ = 128; c.BK = BK; c.MINW = 2; c.SPLITK = 1;
+  if (ni <= 32) { c.BI = 32; c.WI = 1; c.WJ = 4; } else if (ni <= 64) { c.BI = 64; c.WI = 2; c.WJ = 2; } else { c.BI = 128; c.WI = 2; c.WJ = 2; }
+  return c;
+}
+static vect_string bconv_geom_defs(conv_geom_t const &g, tile_cfg_t const &c) {
+  return {"-DBI=" + std::to_string(c.BI), "-DBJ=" + std::to_string(c.BJ), "-DBK=" + std::to_string(c.BK), "-DWI=" + std::to_string(c.WI), "-DWJ=" + std::to_string(c.WJ),
+          "-DMINW=" + std::to_string(c.MINW), "-DKH=" + std::to_string(g.KH), "-DKW=" + std::to_string(g.KW), "-DSY=" + std::to_string(g.SY), "-DSX=" + std::to_string(g.SX),
+          "-DPY=" + std::to_string(g.PY), "-DPX=" + std::to_string(g.PX)};
+}
+static void bconv_check_geom(conv_geom_t const &g, char const *what) {
+  if (g.B < 1 || g.C < 1 || g.H < 1 || g.W < 1 || g.OC < 1 || g.KH < 1 || g.KW < 1 || g.SY < 1 || g.SX < 1 || g.PY < 0 || g.PX < 0 || g.OH < 1 || g.OW < 1 ||
+      g.SY > 16 || g.SX > 16 || g.KH > 64 || g.KW > 64) unsup_err(string(what) + ": unsupported geometry");
+  if ((g.H + 2 * g.PY - g.KH) / g.SY + 1 != g.OH || (g.W + 2 * g.PX - g.KW) / g.SX + 1 != g.OW) rt_err(string(what) + ": out_grad_loss dims do not match in / filts / stride / in_pad");
+  uint64_t const in_b = 4ull * g.B * g.C * g.H * g.W, out_b = 4ull * g.B * g.OC * g.OH * g.OW, f_b = 4ull * g.OC * g.C * g.KH * g.KW;
+  if (in_b >= 0x7ffffff0ull || out_b >= 0x7ffffff0ull || f_b >= 0x7ffffff0ull) unsup_err(string(what) + ": tensors of 2 GiB or more (32-bit buffer offsets)");
+}
+long bconv_in_tiles(conv_geom_t const &g, int BJ) {
+  long n = 0;
+  for (int ry = 0; ry < g.SY; ++ry)
+    for (int rx = 0; rx < g.SX; ++rx) {
+      long const ny = (ry < g.H) ? (g.H - ry + g.SY - 1) / g.SY : 0, nx = (rx < g.W) ? (g.W - rx + g.SX - 1) / g.SX : 0;
+      n += ((long)g.B * ny * nx + BJ - 1) / BJ;
+    }
+  return n;
+}
+plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile) {
+  bconv_check_geom(g, "hip_bconv_in");
+  plan_t p; p.bconv_in = true; p.kname = "bodahip_bconv_in";
+  if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_in: bad tile '" + tile + "'"); }
+  else {
+    p.cfg = bconv_default_cfg(g.C, 16);
+    // fewer tiles than CUs: halve the pel tile (the i tile already follows the channels)
+    if ((long)((g.C + p.cfg.BI - 1) / p.cfg.BI) * bconv_in_tiles(g, 128) < num_cus) { p.cfg.BJ = 64; if (p.cfg.WJ == 4) p.cfg.WJ = 2; }
+  }
+  check_bconv_cfg(p.cfg, false);
+  p.defs = bconv_geom_defs(g, p.cfg);
+  return p;
+}
+plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile) {
+  bconv_check_geom(g, "hip_bconv_filts");
+  plan_t p; p.bconv_filts = true; p.kname = "bodahip_bconv_filts";
+  bool ksl_given = false;
+  if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_filts: bad tile '" + tile + "'"); ksl_given = std::count(tile.begin(), tile.end(), 'x') >= 6; }
+  else p.cfg = bconv_default_cfg(g.OC, 32);
+  if (!ksl_given) {   // K slices until the tiles x slices cover about two workgroups per CU, each slice at least 8 K steps long
+    long const tiles = (long)((g.OC + p.cfg.BI - 1) / p.cfg.BI) * (((long)g.C * g.KH * g.KW + p.cfg.BJ - 1) / p.cfg.BJ);
+    long const nkt = ((long)g.B * g.OH * g.OW + p.cfg.BK - 1) / p.cfg.BK;
+    long ksl = (2L * num_cus + tiles - 1) / tiles;
+    ksl = std::min<long>(ksl, std::max<long>(1, nkt / 8));
+    p.cfg.SPLITK = (int)std::max<long>(1, std::min<long>(32, ksl));
+  }
+  check_bconv_cfg(p.cfg, true);
+  p.defs = bconv_geom_defs(g, p.cfg); p.defs.push_back("-DKSL=" + std::to_string(p.cfg.SPLITK));
+  return p;
+}
+plan_t plan_bconv_biases() { plan_t p; p.bconv_filts = true; p.kname = "bodahip_bconv_biases"; p.defs = {"-DBIAS_ONLY=1"}; return p; }
+
+
 } // namespace bodahip

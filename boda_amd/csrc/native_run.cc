@@ -37,6 +37,14 @@ static bool apply_f32_pool(op_base_t const &op, conv_geom_t &g, char const *what
 
 // AOT: compile (into the on-disk code-object cache) the specialisation that run() would pick for `op`.  No device needed.
 // With arch == "" nothing is compiled and *plan_out receives "<kernel> <tile> <-D options>": the planner's decision (host-logic tests).
+// BckConv: the forward convolution's geometry from the op's in / filts / out_grad_loss / stride / in_pad (OP_INFO["BckConv"], boda_amd/op.py)
+static conv_geom_t bck_geom_of_op(op_base_t const &op) {
+  conv_geom_t g = geom_from_dims(op.get_dims("filts"), op.get_dims("in"), op.get_dims("out_grad_loss"), op.get_dims("stride"), op.get_dims("in_pad"), false);
+  if (op.get_dims("filts").dsz("in_chan") != (uint32_t)g.C || op.get_dims("out_grad_loss").dsz("chan") != (uint32_t)g.OC || op.get_dims("out_grad_loss").dsz("img") != (uint32_t)g.B)
+    rt_err("BckConv: in / filts / out_grad_loss dims are inconsistent");
+  return g;
+}
+
 size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int num_cus, string const &tile_arg, string *plan_out) {
   string const &t = op.get_type();
   // a tile that travels with the function (str_val hip_tile: per-op tuned tiles, see tile_override_t) is what run() would use
@@ -139,6 +147,23 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
         p = plan_sgemm((uint32_t)g.OC, (uint32_t)(std::min<long>(Bc, g.B) * tpi), (uint32_t)g.C, num_cus, string(), false, 16);
       } else { char const *k1e = getenv("BODAHIP_K1_STREAM"); p = plan_conv(g, num_cus, tile, bf16, k1e ? string(k1e) : string(), true, exact); }   // (the env var a backend instance reads its k1_stream tune from)
     }
+  } else if (t == "BckConv") {   // the three gradient functions (or, for the bare op, all three: the calls of src/rtc_fwd.cc:398-400)
+    conv_geom_t const g = bck_geom_of_op(op);
+    string const fn = op.has_func_name() ? op.get_func_name() : string();
+    if (!fn.empty() && fn != "hip_bconv_in" && fn != "hip_bconv_filts" && fn != "hip_bconv_biases") rt_err("prebuild: BckConv function '" + fn + "' has no native kernel");
+    std::vector<plan_t> ps;
+    if (fn.empty() || fn == "hip_bconv_in") ps.push_back(plan_bconv_in(g, num_cus, tile));
+    if (fn.empty() || fn == "hip_bconv_biases") ps.push_back(plan_bconv_biases());
+    if (fn.empty() || fn == "hip_bconv_filts") ps.push_back(plan_bconv_filts(g, num_cus, tile));
+    string desc; size_t bytes = 0;
+    for (plan_t const &q : ps) {
+      desc += (desc.empty() ? "" : " | ") + q.kname + (q.defs.size() > 1 ? " " + q.cfg.str() : string());
+      if (q.bconv_in) desc += " grid=" + std::to_string((long)((g.C + q.cfg.BI - 1) / q.cfg.BI) * bconv_in_tiles(g, q.cfg.BJ));
+      if (q.kname == "bodahip_bconv_filts") desc += " ksl=" + std::to_string(q.cfg.SPLITK);
+      if (!arch.empty()) bytes += compile_plan(q, arch, &log).size();
+    }
+    if (plan_out) *plan_out = desc;
+    return bytes;
   } else rt_err("prebuild: op type '" + t + "' has no native kernel");
   if (plan_out) { *plan_out = s2d + p.kname + " " + p.cfg.str(); for (auto const &d : p.defs) *plan_out += " " + d;
     if (p.split_pels > 0) *plan_out += " pels<" + std::to_string(p.split_pels) + "+rest:" + p.tail_cfg.str(); }
@@ -467,6 +492,46 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     tile_override_t const tov(impl, "conv_tile", fi.op);
     conv((float const *)host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), (float const *)host->nh_var_ptr(inm), (float *)host->nh_var_ptr(onm), g, bf16, out_ctot, out_coff,
          (fn == "hip_conv_winograd") ? "winograd_all" : nullptr, km); // hip_conv_winograd: the F(2x2,3x3) path for this function (3x3 / stride 1; others: direct)
+    return;
+  }
+  if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases") {
+    // every var must have the dims the op gives its arg -- except the number of images, which only has to agree between the vars (a multi-device backend
+    // runs the data gradient on img shards: csrc/hip_multi.cc)
+    conv_geom_t g = bck_geom_of_op(fi.op);
+    long n_img = -1;
+    auto var_dims = [&](char const *an) {
+      string const vn = var_of(am, an); dims_t const d = host->nh_var_dims(vn); need_float(d, an);
+      dims_t want = fi.op.get_dims(an);
+      if (want.sz() == 4 && want.names(0) == "img" && d.sz() == 4) {
+        if (n_img < 0) n_img = d.dims(0);
+        if ((long)d.dims(0) != n_img) rt_err(fn + ": arg '" + an + "' has " + std::to_string(d.dims(0)) + " images, another arg " + std::to_string(n_img));
+        want[0].sz = d.dims(0);
+      }
+      if (!(d == want)) rt_err(fn + ": arg '" + an + "' has dims " + d.pretty_str() + ", the op says " + fi.op.get_dims(an).pretty_str());
+      return vn;
+    };
+    if (fn != "hip_bconv_biases") {
+      auto si = am.find("stride"), pi = am.find("in_pad");
+      if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
+      dims_t const stride = si->second.get_dims(host->nh_rtc()), in_pad = pi->second.get_dims(host->nh_rtc());
+      if (!(stride == fi.op.get_dims("stride")) || !(in_pad == fi.op.get_dims("in_pad"))) rt_err(fn + ": stride / in_pad args disagree with the op");
+    }
+    string const ogl = var_dims("out_grad_loss");
+    g.B = (int)n_img;
+    tile_override_t const tov(impl, "conv_tile", fi.op);
+    if (fn == "hip_bconv_in") {
+      string const f = var_dims("filts"), igl = var_dims("in_grad_loss");
+      if (!(fi.op.get_dims("in_grad_loss") == fi.op.get_dims("in"))) rt_err(fn + ": in_grad_loss must have the dims of in");
+      bconv_in((float const *)host->nh_var_ptr(f), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(igl), g);
+    } else if (fn == "hip_bconv_filts") {
+      string const in = var_dims("in"), fgl = var_dims("filts_grad_loss");
+      if (!(fi.op.get_dims("filts_grad_loss") == fi.op.get_dims("filts"))) rt_err(fn + ": filts_grad_loss must have the dims of filts");
+      bconv_filts((float const *)host->nh_var_ptr(in), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(fgl), g);
+    } else {
+      string const bgl = var_dims("biases_grad_loss");
+      if (fi.op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
+      bconv_biases((float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(bgl), g);
+    }
     return;
   }
   if (fn == "hip_conv_filts_kmajor") {   // filts (out_chan:in_chan:y:x) -> filts_km ([K + 128][out_chan padded to 4], zeros in the padding): see filts_km above

@@ -14,7 +14,8 @@ from .op import Dims, Op
 from .rtc import RtcArg, RtcFuncCall, RtcFuncInfo
 
 HASH_CONSTS = {("sgemm", "a"): 12738732, ("sgemm", "b"): 12738732, ("Convolution", "in"): 234234567,
-               ("Convolution", "filts"): 8753985, ("Convolution", "biases"): 39475612}
+               ("Convolution", "filts"): 8753985, ("Convolution", "biases"): 39475612,
+               ("BckConv", "in"): 234234567, ("BckConv", "filts"): 8753985, ("BckConv", "biases"): 39475612, ("BckConv", "out_grad_loss"): 61734523}
 
 _UTIL = """
 CUCL_DEVICE float det_hash_rand( uint32_t const rv ) {
@@ -111,7 +112,8 @@ def func_infos() -> List[RtcFuncInfo]:
 def gen_call(op_type: str, arg: str, vn: str, dims: Dims, mode: int, vi: float, shard_off: int = 0, shard_glob: int = 0) -> RtcFuncCall:
     """The call that fills var `vn` (dims `dims`) with the reference's test pattern for (op_type, arg).
     Batch-axis shards: for sgemm `a`, shard_off/shard_glob = first global column m and global M; for Convolution `in`,
-    shard_off = first global image (the var then holds the matching slice of the global tensor's pattern)."""
+    shard_off = first global image (the var then holds the matching slice of the global tensor's pattern).  BckConv's in / filts / biases get the Convolution
+    patterns, its out_grad_loss one of its own."""
     n = dims.dims_prod()
     u32 = lambda v: RtcArg.scalar(v, "uint32_t")
     base = {"mode": u32(mode), "vi": RtcArg.scalar(vi, "float")}
@@ -121,12 +123,12 @@ def gen_call(op_type: str, arg: str, vn: str, dims: Dims, mode: int, vi: float, 
         if arg == "a":
             am["m_off"] = u32(shard_off); am["M_glob"] = u32(shard_glob or dims.dsz("M"))
         fn = "gen_data_sgemm_" + arg + ("_half" if dims.tn == "half" else "")
-    elif op_type == "Convolution" and arg in ("in", "filts"):
+    elif (op_type, arg) in HASH_CONSTS and arg != "biases":
         am = {"t": RtcArg.var(vn), **base, "sz": u32(n), "Y": u32(dims.dsz("y")), "X": u32(dims.dsz("x")),
               "hc": u32(HASH_CONSTS[(op_type, arg)]),
-              "ix_off": u32((shard_off * (n // dims.dsz("img"))) if arg == "in" else 0)}
+              "ix_off": u32((shard_off * (n // dims.dsz("img"))) if arg in ("in", "out_grad_loss") else 0)}
         fn = "gen_data_Convolution_4d"
-    elif op_type == "Convolution" and arg == "biases":
+    elif (op_type, arg) in HASH_CONSTS:
         am = {"biases": RtcArg.var(vn), **base, "sz": u32(n)}
         fn = "gen_data_Convolution_biases"
     else:

@@ -227,6 +227,8 @@ def parse_nda(l: Lexp) -> Nda:
 OP_INFO = {
     "Convolution": (("in", "filts", "biases"), ("out",), ("kern_sz", "stride", "in_pad", "out_chans")),
     "sgemm": (("a", "b"), ("c",), ()),
+    # { in, filts, biases, out_grad_loss } -> { in_grad_loss, filts_grad_loss, biases_grad_loss }: each output has its matching input's dims (src/conv_util.cc:65-66,411-416)
+    "BckConv": (("in", "filts", "biases", "out_grad_loss"), ("in_grad_loss", "filts_grad_loss", "biases_grad_loss"), ("kern_sz", "stride", "in_pad", "out_chans")),
 }
 
 
@@ -325,6 +327,19 @@ class Op:
                 raise RtErr(f"conv: out {oo}={g[oo]} != ({hw}+2*{p}-{k})/{s}+1")
         return g
 
+    def bck_conv_geom(self) -> dict:
+        """Geometry of a BckConv: the forward Convolution's (in, filts, stride, in_pad; out_grad_loss in the place of out), validated like conv_geom, and every
+        gradient with its matching input's dims."""
+        fwd = Op(dict(self.str_vals), {k: v for k, v in self.nda_vals.items() if k not in ("out", "hip_pool")})
+        fwd.nda_vals["out"] = self.get("out_grad_loss")
+        g = fwd.conv_geom()
+        for src, dst in (("in", "in_grad_loss"), ("filts", "filts_grad_loss"), ("biases", "biases_grad_loss")):
+            if self.get_dims(dst) != self.get_dims(src):
+                raise RtErr(f"BckConv: {dst} dims {self.get_dims(dst).pretty()} != {src} dims {self.get_dims(src).pretty()}")
+        if self.get_dims("biases").dims_prod() != g["OC"]:
+            raise RtErr("BckConv: biases must hold out_chan values")
+        return g
+
     def sgemm_geom(self) -> dict:
         a, b, c = self.get_dims("a"), self.get_dims("b"), self.get_dims("c")
         g = dict(M=a.dsz("M"), K=a.dsz("K"), N=b.dsz("N"))
@@ -337,6 +352,9 @@ class Op:
         if self.get_type() == "sgemm":
             g = self.sgemm_geom()
             return 2 * g["M"] * g["N"] * g["K"]
+        if self.get_type() == "BckConv":   # two GEMMs of the forward size: the data and the filter gradient
+            g = self.bck_conv_geom()
+            return 4 * (g["B"] * g["OH"] * g["OW"]) * g["OC"] * (g["C"] * g["KH"] * g["KW"])
         g = self.conv_geom()
         return 2 * (g["B"] * g["OH"] * g["OW"]) * g["OC"] * (g["C"] * g["KH"] * g["KW"])
 
@@ -381,6 +399,8 @@ def parse_op(line: str) -> Op:
                 raise RtErr(f"op: {t} is missing required field {an!r}")
         if t == "Convolution":
             op.conv_geom()
+        elif t == "BckConv":
+            op.bck_conv_geom()
         else:
             op.sgemm_geom()
     return op
