@@ -8,7 +8,11 @@
 // reduced INSIDE the launch, the pattern of conv_nhwc_bf16.hip -DKSL: workgroup (tile, s) accumulates K steps [s*kt_per, (s+1)*kt_per) as one exact MFMA
 // chain, writes its raw accumulators write-through to slab s of the tile, drains, and takes ONE relaxed agent-scope ticket; the workgroup that draws the
 // tile's last ticket resets it and sums the KSL slabs in slice order.  No float atomics, no workgroup waits on another: run-to-run deterministic, and the
-// same bits for every tile shape with the same slice count.  Not bit-identical to the reference's single sequential chain (a different association).
+// same bits for every tile shape that cuts K at the same places -- the same slice count AND the same slice length kt_per * BK, with nkt = ceil(K / BK) and
+// kt_per = ceil(nkt / KSL) (K = 300, KSL = 3: slices of 128 at BK = 32, of 112 at BK = 16 -- different bits; BI, BJ and the waves never matter).  KSL = 1 is the
+// reference template's single sequential chain bit for bit (the skipped border terms are fma(g, 0, acc) on finite data); KSL > 1 is a different association:
+// result = slab[0] + slab[1] + ... + slab[KSL-1], slab s = the chain from +0 over slice s, an empty slice (kt0 == kt1) a slab of +0.  Both are held to the CPU
+// emulation of exactly this (oracle/bck_chain.py) by tests/test_gpu_bck_chain.py.
 //
 // -DBIAS_ONLY=1: biases_grad_loss[oc] = sum over img, y, x of out_grad_loss -- one workgroup per out_chan, a fixed-order chain per thread (ascending flat
 // index, stride 256) and a fixed LDS tree: deterministic.
