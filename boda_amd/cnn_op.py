@@ -13,7 +13,7 @@ from __future__ import annotations
 from dataclasses import dataclass, fields
 from typing import Dict
 
-from .op import Op, RtErr, UnsupErr, parse_lexp
+from .op import Nda, Op, RtErr, UnsupErr, parse_lexp
 
 
 @dataclass
@@ -180,6 +180,56 @@ def add_bck_conv_annotations(op: Op, tune: OpTune) -> tuple:
     return tuple(outs)
 
 
+# the native functions of the non-conv backward ops, in the reference's call order (src/rtc_fwd.cc:345-404), and of the two forward ops whose side outputs the
+# backward pass reads: the max-pooling argmax out_in_yx (test/rtc/pool.cucl, emit_out_in_yx) and the LRN out_scale_base (test/rtc/lrn.cucl, emit_out_scale_base)
+BCK_OP_FUNCS: Dict[str, tuple] = {
+    "Spreading": ("hip_spreading",),
+    "BckLRN": ("hip_bck_lrn",),
+    "ZeroIfNonPos": ("hip_zero_if_non_pos",),
+    "SoftmaxWithLoss": ("hip_softmax", "hip_sm_grad_and_loss", "hip_sum_loss_over_imgs"),
+    "Pooling": ("hip_pool_yx",),
+    "LRN": ("hip_lrn_sb",),
+}
+
+
+def add_bck_op_annotations(op: Op, tune: OpTune) -> tuple:
+    """-> the annotated native function ops of one non-conv op of the gradient pipe, in the order the reference calls them: Spreading -> (hip_spreading,), BckLRN ->
+    (hip_bck_lrn,), ZeroIfNonPos -> (hip_zero_if_non_pos,), SoftmaxWithLoss -> (hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs) with the intermediate vars
+    prob (in's dims) and loss_per_pel (label's dims) added to the op under the reference's names.  A Pooling with emit_out_in_yx=1 gives (hip_pool_yx,) and an LRN with
+    emit_out_scale_base=1 (hip_lrn_sb,): the forward functions that also write what Spreading / BckLRN read (out_in_yx / out_scale_base, added to the op with out's
+    dims).  Without the emit flag those two ops belong to the forward pipe (conv_pipe.ConvPipeFwd) and are refused here.  fp32, reference layouts only."""
+    t = op.get_type()
+    if t not in BCK_OP_FUNCS:
+        raise RtErr(f"add_bck_op_annotations: op type {t!r} is none of {sorted(BCK_OP_FUNCS)}")
+    if tune.use_be not in ("", "hip") or tune.use_culibs:
+        raise UnsupErr(f"{t} variants of op_tune={tune.to_str()} are generated by the reference's CUCL code generator; be=hip provides {' / '.join(BCK_OP_FUNCS[t])}")
+    if tune.hip_dtype not in ("", "f32") or tune.hip_layout or tune.hip_algo or tune.hip_out:
+        raise UnsupErr(f"{t}: fp32 in reference layout only (no bf16, channels-last or Winograd variant)")
+    a = op.copy()
+    if t in ("Pooling", "Spreading"):
+        g = a.pool_geom()
+        if t == "Pooling" and not g["emit"]:
+            raise UnsupErr("Pooling with emit_out_in_yx=0 is the forward pipe's (conv_pipe.ConvPipeFwd, POOL_TEMPLATE); hip_pool_yx is the pooling that also writes out_in_yx")
+        a.nda_vals["out_in_yx"] = Nda(dims=a.get_dims("out"), tn="float")
+    elif t in ("LRN", "BckLRN"):
+        g = a.lrn_geom()
+        if t == "LRN" and not g["emit"]:
+            raise UnsupErr("LRN with emit_out_scale_base=0 is the forward pipe's (conv_pipe.ConvPipeFwd, LRN_TEMPLATE); hip_lrn_sb is the LRN that also writes out_scale_base")
+        a.nda_vals["out_scale_base"] = Nda(dims=a.get_dims("out"), tn="float")
+    elif t == "ZeroIfNonPos":
+        a.zinp_geom()
+    else:
+        a.softmax_geom()
+        a.nda_vals["prob"] = Nda(dims=a.get_dims("in"), tn="float")
+        a.nda_vals["loss_per_pel"] = Nda(dims=a.get_dims("label"), tn="float")
+    outs = []
+    for fn in BCK_OP_FUNCS[t]:
+        f = a.copy()
+        f.set_func_name(fn)
+        outs.append(f)
+    return tuple(outs)
+
+
 # arg tables of the native side-door functions (the stubs test/rtc/cublas_sgemm.cucl:1-4, cudnn_conv.cucl:1-7)
 NATIVE_ARGS: Dict[str, tuple] = {
     "hip_sgemm": (("a", "IN"), ("b", "IN"), ("c", "OUT")),
@@ -196,6 +246,16 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_bconv_in": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),
     "hip_bconv_filts": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT")),
     "hip_bconv_biases": (("out_grad_loss", "IN"), ("biases_grad_loss", "OUT")),   # filts as [K + 128][out_chan padded to 4]: what hip_conv's optional filts_km arg takes
+    # the non-conv backward ops, in their reference templates' arg order (test/rtc/pool.cucl, lrn.cucl, spreading.cucl, bck_lrn.cucl, ZeroIfNonPos.cucl, softmax.cucl,
+    # sm_grad_and_loss.cucl, sum_loss_over_imgs.cucl); the by-value scalars of those templates (avg_pool, alpha, ...) ride in the op
+    "hip_pool_yx": (("in", "IN"), ("kern_sz", "REF"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT"), ("out_in_yx", "OUT")),
+    "hip_lrn_sb": (("in", "IN"), ("out", "OUT"), ("out_scale_base", "OUT")),
+    "hip_spreading": (("out", "IN"), ("out_grad_loss", "IN"), ("out_in_yx", "IN"), ("kern_sz", "REF"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),
+    "hip_bck_lrn": (("in", "IN"), ("out", "IN"), ("out_grad_loss", "IN"), ("out_scale_base", "IN"), ("in_grad_loss", "OUT")),
+    "hip_zero_if_non_pos": (("in", "IN"), ("cond", "IN"), ("out", "OUT")),
+    "hip_softmax": (("in", "IN"), ("prob", "OUT")),
+    "hip_sm_grad_and_loss": (("prob", "IN"), ("label", "IN"), ("in_grad_loss", "OUT"), ("loss_per_pel", "OUT")),
+    "hip_sum_loss_over_imgs": (("loss_per_pel", "IN"), ("loss", "OUT")),
 }
 
 

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstring>
 #include <omp.h>
+#include <vector>
 
 namespace bodahip {
 
@@ -82,6 +83,131 @@ void tiled_contract(micro_t micro, float const *at, long lda, long Mi, long Nj, 
 }
 
 struct conv_geom_c { long B, C, H, W, OC, KH, KW, SY, SX, PY, PX, OH, OW; bool relu; };
+
+// ---- the non-conv ops of the gradient pipe: plain loops in exactly the reference templates' order (test/rtc/pool.cucl, spreading.cucl, lrn.cucl, bck_lrn.cucl,
+// ZeroIfNonPos.cucl, softmax.cucl, sm_grad_and_loss.cucl, sum_loss_over_imgs.cucl), parallel over outputs.  They are the bit-exact checker of the HIP kernels
+// (kernels/bck_ops_f32.hip states the semantics and the quirks), so nothing here may be fused or regrouped: this file builds with -ffp-contract=fast for the fmaf
+// chains above, and these functions switch contraction off again.
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+struct pool_geom_c { long B, C, H, W, OH, OW, KH, KW, SY, SX, PY, PX; bool avg; };
+void pool_yx(float const *in, float *out, float *out_in_yx, pool_geom_c const &g) {
+#pragma omp parallel for schedule(static)
+  for (long pl = 0; pl < g.B * g.C; ++pl)
+    for (long oy = 0; oy < g.OH; ++oy)
+      for (long ox = 0; ox < g.OW; ++ox) {
+        float best = -3.402823466e+38f; long oyx = -1;
+        for (long kx = 0; kx < g.KW; ++kx)
+          for (long ky = 0; ky < g.KH; ++ky) {
+            long const iy = oy * g.SY + ky - g.PY, ix = ox * g.SX + kx - g.PX;
+            if (iy < 0 || ix < 0 || ix >= g.W || iy >= g.H) continue;
+            float const v = in[(pl * g.H + iy) * g.W + ix];
+            if (v > best) { best = v; oyx = iy * g.W + ix; }
+          }
+        out[(pl * g.OH + oy) * g.OW + ox] = best;
+        out_in_yx[(pl * g.OH + oy) * g.OW + ox] = (float)oyx;
+      }
+}
+void spreading(float const *ogl, float const *out_in_yx, float *igl, pool_geom_c const &g) {
+  float const spread_sz = (float)(g.KW * g.KH);   // the full window area, also where a border clips the window (the reference's own FIXME)
+#pragma omp parallel for schedule(static)
+  for (long pl = 0; pl < g.B * g.C; ++pl)
+    for (long y = 0; y < g.H; ++y)
+      for (long x = 0; x < g.W; ++x) {
+        long const oxb = std::max<long>(0, x + g.PX - g.KW + g.SX) / g.SX, oxe = std::min<long>((x + g.PX) / g.SX + 1, g.OW);
+        long const oyb = std::max<long>(0, y + g.PY - g.KH + g.SY) / g.SY, oye = std::min<long>((y + g.PY) / g.SY + 1, g.OH);
+        float const in_yx = (float)(y * g.W + x);
+        float v = 0.0f;
+        for (long ox = oxb; ox < oxe; ++ox)
+          for (long oy = oyb; oy < oye; ++oy) {
+            long const oix = (pl * g.OH + oy) * g.OW + ox;
+            if (g.avg) v = v + ogl[oix] / spread_sz;
+            else if (in_yx == out_in_yx[oix]) v = v + ogl[oix];
+          }
+        igl[(pl * g.H + y) * g.W + x] = v;
+      }
+}
+struct lrn_geom_c { long B, C, HW, LS; float alpha, beta, k; };
+void lrn_sb(float const *in, float *out, float *sb, lrn_geom_c const &g) {
+  long const hls = g.LS / 2;
+  float const alpha_over_ls = g.alpha / (float)g.LS;
+#pragma omp parallel for schedule(static)
+  for (long pix = 0; pix < g.B * g.HW; ++pix) {
+    long const base = (pix / g.HW) * g.C * g.HW + pix % g.HW;
+    std::vector<float> ls_buf((size_t)g.LS, 0.0f);
+    float ls_sum = 0.0f;
+    for (long c = 0; c < g.C + hls; ++c) {
+      long const slot = c % g.LS;
+      float const ls_old = ls_buf[slot];
+      ls_buf[slot] = (c < g.C) ? in[base + c * g.HW] : 0.0f;
+      ls_sum = ls_sum + ls_buf[slot] * ls_buf[slot];
+      ls_sum = ls_sum - ls_old * ls_old;
+      if (c >= hls) {
+        long const oc = c - hls;
+        float const scale_base = g.k + ls_sum * alpha_over_ls;
+        sb[base + oc * g.HW] = scale_base;
+        out[base + oc * g.HW] = ls_buf[(slot + g.LS - hls) % g.LS] * powf(scale_base, -g.beta);
+      }
+    }
+  }
+}
+void bck_lrn(float const *in, float const *out, float const *ogl, float const *sb, float *igl, lrn_geom_c const &g) {
+  long const hls = g.LS / 2;
+  float const coef = ((2.0f * -g.beta) * g.alpha) / (float)g.LS;
+#pragma omp parallel for schedule(static)
+  for (long pix = 0; pix < g.B * g.HW; ++pix) {
+    long const base = (pix / g.HW) * g.C * g.HW + pix % g.HW;
+    std::vector<float> ls_buf((size_t)g.LS, 0.0f);
+    for (long c = 0; c < g.C + hls; ++c) {
+      long const ix = base + c * g.HW;
+      ls_buf[c % g.LS] = (c < g.C) ? (ogl[ix] * out[ix] / sb[ix]) : 0.0f;
+      if (c >= hls) {
+        long const ox = base + (c - hls) * g.HW;
+        float ls_sum = 0.0f;
+        for (long i = 0; i < g.LS; ++i) ls_sum = ls_sum + ls_buf[i];   // slot order, recomputed: not carried
+        float const a = ogl[ox] * powf(sb[ox], -g.beta);
+        float const b = in[ox] * ls_sum * coef;
+        igl[ox] = a + b;
+      }
+    }
+  }
+}
+void zero_if_non_pos(float const *in, float const *cond, float *out, long n) {
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < n; ++i) out[i] = (cond[i] > 0.0f) ? in[i] : 0.0f;
+}
+void softmax(float const *in, float *prob, long B, long C) {   // 1 x 1 planes; the reference's sequential sum
+#pragma omp parallel for schedule(static)
+  for (long img = 0; img < B; ++img) {
+    float const *x = in + img * C; float *pr = prob + img * C;
+    float pel_sum = 0.0f, pel_max = 0.0f;   // pel_max starts at 0, not at the first value
+    for (long c = 0; c < C; ++c) pel_max = (x[c] > pel_max) ? x[c] : pel_max;
+    for (long c = 0; c < C; ++c) { float const v = expf(x[c] - pel_max); pr[c] = v; pel_sum = pel_sum + v; }
+    for (long c = 0; c < C; ++c) pr[c] = pr[c] / pel_sum;
+  }
+}
+void sm_grad_and_loss(float const *prob, float const *label, float *igl, float *loss_per_pel, long B, long C) {
+#pragma omp parallel for schedule(static)
+  for (long img = 0; img < B; ++img) {
+    float const lf = label[img];
+    bool const valid = lf >= 0.0f && lf < (float)C;   // a label outside [0, chan) matches no channel and reads no memory
+    long const lab = valid ? (long)lf : -1;
+    float const pl = valid ? prob[img * C + lab] : 0.0f;
+    loss_per_pel[img] = -logf(pl > 1.175494351e-38f ? pl : 1.175494351e-38f);
+    for (long c = 0; c < C; ++c) {
+      float v = prob[img * C + c];
+      if (c == lab) v = v - 1.0f;
+      v = v / (float)B;
+      igl[img * C + c] = v;
+    }
+  }
+}
+void sum_loss_over_imgs(float const *loss_per_pel, float *loss, long B) {
+  float v = 0.0f;
+  for (long i = 0; i < B; ++i) v = v + loss_per_pel[i];
+  loss[0] = v / (float)B;
+}
+#pragma GCC pop_options
 } // namespace
 
 struct cpu_var_t { std::shared_ptr<void> buf; dims_t dims; };
@@ -141,14 +267,37 @@ struct cpu_compute_t : public rtc_compute_t {
   static bool is_sgemm(string const &fn) { return fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "cpu_sgemm"; }
   static bool is_conv(string const &fn) { return fn == "hip_conv" || fn == "cudnn_conv" || fn == "cpu_conv_fwd"; }
   static bool is_bck(string const &fn) { return fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases"; }
+  // the gradient pipe's non-conv functions and their var args in arg order (inputs | outputs); `refs`: kern_sz / stride / in_pad REF args
+  struct bck_op_fn_t { char const *fn; char const *type; std::vector<char const *> ins, outs; bool refs; };
+  static bck_op_fn_t const *find_bck_op(string const &fn) {
+    static bck_op_fn_t const tab[] = {
+      {"hip_pool_yx", "Pooling", {"in"}, {"out", "out_in_yx"}, true},
+      {"hip_spreading", "Spreading", {"out", "out_grad_loss", "out_in_yx"}, {"in_grad_loss"}, true},
+      {"hip_lrn_sb", "LRN", {"in"}, {"out", "out_scale_base"}, false},
+      {"hip_bck_lrn", "BckLRN", {"in", "out", "out_grad_loss", "out_scale_base"}, {"in_grad_loss"}, false},
+      {"hip_zero_if_non_pos", "ZeroIfNonPos", {"in", "cond"}, {"out"}, false},
+      {"hip_softmax", "SoftmaxWithLoss", {"in"}, {"prob"}, false},
+      {"hip_sm_grad_and_loss", "SoftmaxWithLoss", {"prob", "label"}, {"in_grad_loss", "loss_per_pel"}, false},
+      {"hip_sum_loss_over_imgs", "SoftmaxWithLoss", {"loss_per_pel"}, {"loss"}, false},
+    };
+    for (auto const &d : tab) if (fn == d.fn) return &d;
+    return nullptr;
+  }
   void compile(vect_rtc_func_info_t const &func_infos, rtc_compile_opts_t const &) override {
     assert_st(init_done);
     for (auto const &fi : func_infos) {
       if (funcs.count(fi.func_name)) rt_err("compile: function '" + fi.func_name + "' already exists");
       string const fn = fi.op.has_func_name() ? fi.op.get_func_name() : string();
-      if (!is_sgemm(fn) && !is_conv(fn) && !is_bck(fn)) unsup_err("be=cpu runs the native sgemm / Convolution / BckConv functions only (hip_sgemm, hip_conv and their aliases, hip_bconv_*); '" +
+      if (!is_sgemm(fn) && !is_conv(fn) && !is_bck(fn) && !find_bck_op(fn))
+        unsup_err("be=cpu runs the native sgemm / Convolution / BckConv functions and the gradient pipe's non-conv functions only (hip_sgemm, hip_conv and their aliases, hip_bconv_*, "
+                  "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs); '" +
                                                     (fn.empty() ? fi.func_name : fn) + "' is generated CUCL source, which needs a GPU backend");
       if (is_conv(fn)) (void)fi.op.get_u32("conv_has_relu");
+      if (bck_op_fn_t const *d = find_bck_op(fn)) {
+        if (fi.op.get_type() != d->type) rt_err(fn + ": a function of op type " + d->type + ", not " + fi.op.get_type());
+        for (char const *an : d->ins) (void)fi.op.get_dims(an);
+        for (char const *an : d->outs) (void)fi.op.get_dims(an);
+      }
       funcs.emplace(fi.func_name, cpu_func_t{fi});
     }
   }
@@ -287,6 +436,69 @@ struct cpu_compute_t : public rtc_compute_t {
     else bconv_filts((float const *)must_find(vis, inm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, fnm).buf.get(), g);
   }
 
+  static float op_f32(op_base_t const &op, string const &an) {
+    p_nda_t const &n = op.get(an);
+    if (n->dims.tn != "float" || n->dims.sz() != 0 || !n->rp) rt_err("op: '" + an + "' is not a float scalar");
+    return *static_cast<float const *>(n->rp);
+  }
+  // the gradient pipe's non-conv functions: every var must have the dims the op gives its arg (the image count only has to agree between the vars, as on be=hip)
+  void run_bck_op(bck_op_fn_t const &d, op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = d.fn;
+    long n_img = -1;
+    auto var_ptr = [&](char const *an) -> float * {
+      string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn); need_float(vd, an);
+      dims_t want = op.get_dims(an);
+      if (want.sz() >= 1 && want.names(0) == "img" && vd.sz() == want.sz()) {
+        if (n_img < 0) n_img = vd.dims(0);
+        if ((long)vd.dims(0) != n_img) rt_err(fn + ": arg '" + an + "' has " + std::to_string(vd.dims(0)) + " images, another arg " + std::to_string(n_img));
+        want[0].sz = vd.dims(0); want.calc_strides();
+      }
+      if (!(vd == want)) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + op.get_dims(an).pretty_str());
+      return (float *)must_find(vis, vn).buf.get();
+    };
+    if (d.refs) for (char const *an : {"kern_sz", "stride", "in_pad"}) {
+      auto ri = am.find(an);
+      if (ri == am.end()) rt_err(fn + ": the REF arg '" + an + "' is required");
+      if (!(ri->second.get_dims(*this) == op.get_dims(an))) rt_err(fn + ": arg '" + an + "' disagrees with the op");
+    }
+    float *in[4] = {nullptr, nullptr, nullptr, nullptr}, *out[2] = {nullptr, nullptr};
+    for (size_t i = 0; i < d.ins.size(); ++i) in[i] = var_ptr(d.ins[i]);
+    for (size_t i = 0; i < d.outs.size(); ++i) out[i] = var_ptr(d.outs[i]);
+    if (d.refs) {
+      dims_t const &i4 = op.get_dims("in"), &o4 = op.get_dims("out"), &ks = op.get_dims("kern_sz"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
+      if (i4.sz() != 4 || o4.sz() != 4) rt_err(fn + ": in / out must be img:chan:y:x");
+      pool_geom_c g{n_img, (long)i4.dsz("chan"), (long)i4.dsz("y"), (long)i4.dsz("x"), (long)o4.dsz("y"), (long)o4.dsz("x"), (long)ks.dsz("y"), (long)ks.dsz("x"),
+                    (long)st.dsz("y"), (long)st.dsz("x"), (long)pad.dsz("y"), (long)pad.dsz("x"), op.get_u32("avg_pool") != 0};
+      if (g.KH < 1 || g.KW < 1 || g.SY < 1 || g.SX < 1) rt_err(fn + ": zero kern_sz / stride");
+      bool const small = g.H + 2 * g.PY < g.KH || g.W + 2 * g.PX < g.KW;   // either padded dim below the window: a 1 x 1 output
+      auto osz = [&](long in_sz, long k, long s, long pd) { return small ? 1 : (in_sz + 2 * pd - k + s - 1) / s + 1; };
+      if (osz(g.H, g.KH, g.SY, g.PY) != g.OH || osz(g.W, g.KW, g.SX, g.PX) != g.OW) rt_err(fn + ": out plane does not follow from in / kern_sz / stride / in_pad");
+      if (fn == "hip_pool_yx") {
+        if (!op.get_u32("emit_out_in_yx")) unsup_err(fn + ": a Pooling with emit_out_in_yx=0 belongs to the forward pipe");
+        if (g.avg) unsup_err(fn + ": out_in_yx is the argmax of a MAX pooling (avg_pool must be 0)");
+        pool_yx(in[0], out[0], out[1], g);
+      } else spreading(in[1], in[2], out[0], g);
+    } else if (fn == "hip_lrn_sb" || fn == "hip_bck_lrn") {
+      dims_t const &i4 = op.get_dims("in");
+      if (i4.sz() != 4) rt_err(fn + ": in must be img:chan:y:x");
+      lrn_geom_c g{n_img, (long)i4.dsz("chan"), (long)i4.dsz("y") * i4.dsz("x"), (long)op.get_u32("local_size"), op_f32(op, "alpha"), op_f32(op, "beta"), op_f32(op, "k")};
+      if (g.LS < 1 || g.LS % 2 == 0) unsup_err(fn + ": local_size=" + std::to_string(g.LS) + ": only odd windows (an even local_size has no centre channel)");
+      if (fn == "hip_lrn_sb") {
+        if (!op.get_u32("emit_out_scale_base")) unsup_err(fn + ": an LRN with emit_out_scale_base=0 belongs to the forward pipe");
+        lrn_sb(in[0], out[0], out[1], g);
+      } else bck_lrn(in[0], in[1], in[2], in[3], out[0], g);
+    } else if (fn == "hip_zero_if_non_pos") {
+      zero_if_non_pos(in[0], in[1], out[0], (long)get_var_dims(var_of(am, "in")).dims_prod());
+    } else {
+      dims_t const &i4 = op.get_dims("in");
+      if (i4.sz() != 4 || i4.dims(2) != 1 || i4.dims(3) != 1) unsup_err(fn + ": only 1 x 1 planes (in img:chan:1:1, label img:1:1): the reference reads label by image");
+      long const C = i4.dsz("chan");
+      if (fn == "hip_softmax") softmax(in[0], out[0], n_img, C);
+      else if (fn == "hip_sm_grad_and_loss") sm_grad_and_loss(in[0], in[1], out[0], out[1], n_img, C);
+      else sum_loss_over_imgs(in[0], out[0], n_img);
+    }
+  }
+
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
     auto fit = funcs.find(rfc.rtc_func_name);
@@ -295,7 +507,8 @@ struct cpu_compute_t : public rtc_compute_t {
     string const &fn = fi.op.get_func_name();
     map_str_rtc_arg_t const &am = rfc.arg_map;
     double const tb = now_ms();
-    if (is_bck(fn)) run_bck(fn, am);
+    if (bck_op_fn_t const *bd = find_bck_op(fn)) run_bck_op(*bd, fi.op, am);
+    else if (is_bck(fn)) run_bck(fn, am);
     else if (is_sgemm(fn)) {
       string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");
       dims_t const a = get_var_dims(an), b = get_var_dims(bn), c = get_var_dims(cn);

@@ -30,7 +30,6 @@
 
 #include <hip/hip_runtime.h>
 #include <sstream>
-#include <set>
 
 namespace bodahip {
 
@@ -122,7 +121,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
   std::vector<p_rtc_compute_t> subs;
   std::map<string, multi_var_t> vis;
   std::map<string, bool> func_native;
-  std::set<string> func_img_sum;   // native functions that reduce over the images (BckConv filter / bias gradients): refused on a sharded run
+  std::map<string, string> func_img_sum;   // native functions that reduce over the images (BckConv filter / bias gradients, the softmax loss): refused on a sharded run, with this message
   std::map<string, gen_func_t> func_gen;       // generated functions: their index declaration
   std::vector<hipEvent_t> peer_evs;            // per device: marks the end of its last peer copy out of device 0
   static constexpr uint32_t kNoCall = 0xffffffffu;   // per-device call id of a call that launched nothing there (an empty shard)
@@ -338,7 +337,12 @@ struct hip_multi_compute_t : public rtc_compute_t {
       bool const nat = native_kernels_t::is_native_func_name(fi.op.has_func_name() ? fi.op.get_func_name() : string());
       func_native[fi.func_name] = nat;
       // BckConv's filter / bias gradients sum over the images: on img shards every device would hold a partial sum, and no cross-device reduction exists here
-      if (nat && n() > 1 && (fi.op.get_func_name() == "hip_bconv_filts" || fi.op.get_func_name() == "hip_bconv_biases")) func_img_sum.insert(fi.func_name);
+      if (nat && n() > 1 && (fi.op.get_func_name() == "hip_bconv_filts" || fi.op.get_func_name() == "hip_bconv_biases"))
+        func_img_sum[fi.func_name] = "(a BckConv filter / bias gradient) sums over the images, which would need a cross-device reduction; only the data gradient (hip_bconv_in) runs on img shards";
+      // the softmax loss: hip_sm_grad_and_loss divides by the GLOBAL image count and hip_sum_loss_over_imgs sums over all images; the gradient pipe's other six
+      // non-conv functions (hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax) are independent per image and run on img shards
+      if (nat && n() > 1 && fi.op.get_func_name() == "hip_sm_grad_and_loss") func_img_sum[fi.func_name] = "(the softmax loss gradient) divides by the GLOBAL image count, which an img shard does not know; hip_softmax runs on img shards";
+      if (nat && n() > 1 && fi.op.get_func_name() == "hip_sum_loss_over_imgs") func_img_sum[fi.func_name] = "(the softmax loss) sums loss_per_pel over ALL images, which would need a cross-device reduction; hip_softmax runs on img shards";
       if (!nat) func_gen[fi.func_name] = scan_gen_func(all_src, fi.func_name);
     }
   }
@@ -349,8 +353,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
     assert_st(init_done);
     auto fit = func_native.find(rfc.rtc_func_name);
     if (fit == func_native.end()) rt_err("run: unknown function '" + rfc.rtc_func_name + "' (not compiled, or released)");
-    if (func_img_sum.count(rfc.rtc_func_name)) unsup_err("multi-device backend: '" + rfc.rtc_func_name + "' (a BckConv filter / bias gradient) sums over the images, which would need a "
-                                                        "cross-device reduction; only the data gradient (hip_bconv_in) runs on img shards");
+    { auto is = func_img_sum.find(rfc.rtc_func_name); if (is != func_img_sum.end()) unsup_err("multi-device backend: '" + rfc.rtc_func_name + "' " + is->second); }
     if (!fit->second) {
       bool sharded = false;
       for (auto const &kv : rfc.arg_map) if (kv.second.is_valid() && kv.second.is_var() && must_find(vis, kv.second.n).shard_dim >= 0) sharded = true;

@@ -123,6 +123,32 @@ op_base_t parse_op_lexp(string const &s_in) {
   return op;
 }
 
+// a float scalar as the Python side prints it (boda_amd/op.py _fmt_val): integer-valued -> the integer; else the shortest decimal that reads back as the same float,
+// written the way Python's repr() writes a number (plain notation for exponents -4 .. 15, d.ddde-XX otherwise)
+static string f32_to_str(float v) {
+  if (v != v) return "nan";
+  if (v - v != 0.0f) return v > 0 ? "inf" : "-inf";
+  char buf[64];
+  if (v == (float)(long long)v && (v < 1e15f && v > -1e15f)) { snprintf(buf, sizeof(buf), "%lld", (long long)v); return buf; }
+  int p = 1;
+  for (; p < 9; ++p) { snprintf(buf, sizeof(buf), "%.*e", p - 1, (double)v); if (strtof(buf, nullptr) == v) break; }
+  snprintf(buf, sizeof(buf), "%.*e", p - 1, (double)v);
+  string s = buf; string sign; if (s[0] == '-') { sign = "-"; s = s.substr(1); }
+  size_t const epos = s.find('e');
+  int const e = atoi(s.c_str() + epos + 1);
+  string digits; for (size_t i = 0; i < epos; ++i) if (s[i] != '.') digits.push_back(s[i]);
+  while (digits.size() > 1 && digits.back() == '0') digits.pop_back();
+  string r;
+  if (e >= -4 && e < 16) {
+    if (e >= 0) { while ((int)digits.size() < e + 1) digits.push_back('0'); r = digits.substr(0, e + 1) + "." + ((int)digits.size() > e + 1 ? digits.substr(e + 1) : string("0")); }
+    else r = "0." + string((size_t)(-e - 1), '0') + digits;
+  } else {
+    r = digits.substr(0, 1) + (digits.size() > 1 ? "." + digits.substr(1) : string());
+    snprintf(buf, sizeof(buf), "e%c%02d", e < 0 ? '-' : '+', e < 0 ? -e : e); r += buf;
+  }
+  return sign + r;
+}
+
 string op_to_str(op_base_t const &op) {
   string r = "(str_vals=(";
   bool first = true;
@@ -147,7 +173,7 @@ string op_to_str(op_base_t const &op) {
         if (i) r += ":";
         if (n.dims.tn == "uint32_t") r += std::to_string(static_cast<uint32_t const *>(n.rp)[i]);
         else if (n.dims.tn == "int32_t") r += std::to_string(static_cast<int32_t const *>(n.rp)[i]);
-        else if (n.dims.tn == "float") r += std::to_string(static_cast<float const *>(n.rp)[i]);
+        else if (n.dims.tn == "float") r += f32_to_str(static_cast<float const *>(n.rp)[i]);
         else r += "?";
       }
     }

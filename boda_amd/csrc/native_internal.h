@@ -46,7 +46,7 @@ struct native_kernels_t::impl_t {
 };
 
 
-struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false, bconv_in = false, bconv_filts = false; int rows = 0, cg = 0; };
+struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false, bconv_in = false, bconv_filts = false, bck_ops = false; int rows = 0, cg = 0; };
 
 struct bconv_args_t { // must match kernels/bconv_in_f32.hip, kernels/bconv_filts_f32.hip
   float const *a; float const *b; float *d;
@@ -55,6 +55,20 @@ struct bconv_args_t { // must match kernels/bconv_in_f32.hip, kernels/bconv_filt
   int tiles_i, tiles_j, ksl, kt_per;
   unsigned a_bytes, b_bytes, d_bytes;
 };
+
+struct bck_ops_args_t { // must match kernels/bck_ops_f32.hip
+  float const *p0; float const *p1; float const *p2; float const *p3;
+  float *o0; float *o1;
+  long n;
+  int B, C, HW, n4;
+  float f0, f1, f2, f3;
+};
+// a native function of the gradient pipe's non-conv ops: its kernel, and its var args in the function's arg order
+struct bck_op_desc_t { char const *fn; int op; char const *kname; char const *type_a; std::vector<char const *> ins, outs; bool refs; };
+bck_op_desc_t const *find_bck_op(string const &fn);                 // null: not one of them
+std::vector<bck_op_desc_t const *> bck_ops_of_type(string const &t);   // the functions of a bare op, in the reference's call order (empty: not such an op)
+struct bck_plan_t { plan_t p; long threads = 0; uint32_t grid = 0, block = 256; int CB = 0; double algo_bytes = 0; };
+bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus);
 
 struct rows_args_t { // must match kernels/conv_nhwc_rows_bf16.hip
   void const *filts; void const *in; void *out; float const *bias;

@@ -47,6 +47,12 @@ void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     return;
   }
+  if (bck_op_desc_t const *d = find_bck_op(fn)) {   // the gradient pipe's non-conv ops: the (annotated) op must carry every arg's dims
+    for (char const *an : d->ins) (void)fi.op.get_dims(an);
+    for (char const *an : d->outs) (void)fi.op.get_dims(an);
+    if (d->refs) for (char const *an : {"kern_sz", "stride", "in_pad"}) (void)fi.op.get_dims(an);
+    return;
+  }
   rt_err("unknown/unhandled native hip function: " + fn);
 }
 void native_kernels_t::set_tune(string const &key, string const &val) {
@@ -66,7 +72,7 @@ void launch(native_host_t *host, kernel_t &k, gemm_args_t &a, tile_cfg_t const &
 
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log) {
   vect_string opts = p.defs; opts.push_back("-DKNAME=" + p.kname);
-  return hiprtc_compile(p.bconv_in ? k_src_bconv_in_f32 : p.bconv_filts ? k_src_bconv_filts_f32 : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
+  return hiprtc_compile(p.bck_ops ? k_src_bck_ops_f32 : p.bconv_in ? k_src_bconv_in_f32 : p.bconv_filts ? k_src_bconv_filts_f32 : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
 }
 
 // grow-only scratch shared by the split-K slabs and the Winograd-domain tensors (like the reference's cudnn scratch var)
@@ -762,5 +768,25 @@ void native_kernels_t::bconv_biases(float const *out_grad, float *biases_grad, c
   last_launch.flops = (double)g.B * g.OC * g.OH * g.OW; last_launch.algo_bytes = 4.0 * ((double)g.B * g.OC * g.OH * g.OW + g.OC);
 }
 
+
+
+// ---- the non-conv ops of the gradient pipe (kernels/bck_ops_f32.hip): one launch, one thread per written element (softmax: one wave per image)
+void native_kernels_t::bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs) {
+  bck_plan_t const bp = plan_bck_op(g, host->nh_num_cus());
+  kernel_t &k = get_kernel(impl, host, bp.p);
+  bck_ops_args_t a; memset(&a, 0, sizeof(a));
+  a.p0 = ins[0]; a.p1 = ins[1]; a.p2 = ins[2]; a.p3 = ins[3]; a.o0 = outs[0]; a.o1 = outs[1];
+  a.n = bp.threads; a.B = (int)g.B; a.C = g.C; a.HW = g.H * g.W;
+  if (g.op == 3 || g.op == 4) { a.f0 = g.alpha / (float)g.LS; a.f1 = g.beta; a.f2 = g.k; a.f3 = ((2.0f * -g.beta) * g.alpha) / (float)g.LS; }
+  if (g.op == 5) {   // float4 over whole quads when the three buffers are 16-byte aligned, scalars over the rest
+    bool const al = (((uintptr_t)ins[0] | (uintptr_t)ins[1] | (uintptr_t)outs[0]) & 15) == 0;
+    a.n4 = al ? (int)(g.n / 4) : 0; a.n = (long)a.n4 + (g.n - 4L * a.n4);
+  }
+  uint32_t const grid = (g.op == 5) ? (uint32_t)((a.n + 255) / 256) : bp.grid;
+  void *params[] = {&a};
+  if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, bp.block, params), "hipModuleLaunchKernel(bck_op)");
+  last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = grid; last_launch.block = bp.block;
+  last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
+}
 
 } // namespace bodahip

@@ -17,6 +17,16 @@
 //                                       3x3 / 5x5 / pool-projection convolutions (the kernel sources instantiated per member inside one wrapper kernel, built at run time)
 //     hip_bconv_in / _filts / _biases   BckConv's three gradients (fp32, NCHW / OIHW): args filts out_grad_loss stride(REF) in_pad(REF) in_grad_loss |
 //                                       in out_grad_loss stride(REF) in_pad(REF) filts_grad_loss | out_grad_loss biases_grad_loss  (test/rtc/BckConv_*.cucl)
+//     the non-conv ops of the gradient pipe (fp32, img:chan:y:x; kernels/bck_ops_f32.hip), each with its reference template's arg list -- the templates' by-value
+//     scalars (avg_pool, emit_*, alpha, beta, k, local_size) ride in the op:
+//       hip_pool_yx             in kern_sz(REF) stride(REF) in_pad(REF) out out_in_yx                              test/rtc/pool.cucl (max, emit_out_in_yx=1)
+//       hip_lrn_sb              in out out_scale_base                                                              test/rtc/lrn.cucl (emit_out_scale_base=1)
+//       hip_spreading           out out_grad_loss out_in_yx kern_sz(REF) stride(REF) in_pad(REF) in_grad_loss      test/rtc/spreading.cucl
+//       hip_bck_lrn             in out out_grad_loss out_scale_base in_grad_loss                                   test/rtc/bck_lrn.cucl
+//       hip_zero_if_non_pos     in cond out                                                                        test/rtc/ZeroIfNonPos.cucl
+//       hip_softmax             in prob                                                                            test/rtc/softmax.cucl
+//       hip_sm_grad_and_loss    prob label in_grad_loss loss_per_pel                                               test/rtc/sm_grad_and_loss.cucl
+//       hip_sum_loss_over_imgs  loss_per_pel loss                                                                  test/rtc/sum_loss_over_imgs.cucl
 //     hip_conv_winograd                 same contract as hip_conv; 3x3 / stride-1 layers through F(2x2,3x3) Winograd (mrd <= ~2e-3)
 // and lands them on kernels/gemm_conv_f32.hip (and, for short-K 1x1 convs with a long pel axis, kernels/k1_stream_f32.hip),
 // specialised with hiprtc per shape class at first use.
@@ -70,6 +80,10 @@ struct conv_geom_t { int B, C, H, W, OC, KH, KW, SY, SX, PY, PX, OH, OW; bool re
 // window, stride, padding; POH x POW = the pooled planes, the tensor the launch writes) and an across-channel LRN of the pooled values (LRN_N > 0: local size, alpha, beta, k)
 struct post_ops_t { int PKH = 0, PKW = 0, PSY = 1, PSX = 1, PPY = 0, PPX = 0, POH = 0, POW = 0, LRN_N = 0; float alpha = 0.f, beta = 0.f, k = 0.f; bool pooled() const { return PKH > 0; } };
 
+// one call of a non-conv gradient-pipe kernel (kernels/bck_ops_f32.hip): op = 1 pool_yx, 2 spreading, 3 lrn_sb, 4 bck_lrn, 5 zero_if_non_pos, 6 softmax, 7 sm_grad_and_loss,
+// 8 sum_loss_over_imgs.  B images of C channels; H x W = the pooling's INPUT plane (LRN: the plane), OH x OW its output plane; n = elements (zero_if_non_pos)
+struct bck_op_geom_t { int op = 0; long B = 0; int C = 0, H = 1, W = 1, OH = 1, OW = 1, KH = 1, KW = 1, SY = 1, SX = 1, PY = 0, PX = 0, avg = 0, LS = 1; float alpha = 0.f, beta = 0.f, k = 0.f; long n = 0; };
+
 struct launch_info_t { string kernel; tile_cfg_t cfg; uint32_t grid = 0, block = 0; double flops = 0, algo_bytes = 0; };
 
 struct native_kernels_t {
@@ -106,6 +120,8 @@ struct native_kernels_t {
   void bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g);
   void bconv_filts(float const *in, float const *out_grad, float *filts_grad, conv_geom_t const &g);
   void bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g);
+  // the non-conv ops of the gradient pipe: ins / outs in the function's arg order (up to four / two raw device pointers)
+  void bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs);
   void conv_winograd(float const *filts, float const *biases, float const *in, float *out, conv_geom_t const &g, int out_ctot, int out_coff);
 
   // tuning overrides ("" clears): key "sgemm_tile" / "conv_tile" -> "BIxBJxBKxWIxWJ[xMINW[xSPLITK[xMT]]]"; key "k1_stream" -> "off" | "WIxWJxOCBxCB[xMINW]";

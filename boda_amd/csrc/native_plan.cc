@@ -1202,4 +1202,77 @@ plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile) {
 plan_t plan_bconv_biases() { plan_t p; p.bconv_filts = true; p.kname = "bodahip_bconv_biases"; p.defs = {"-DBIAS_ONLY=1"}; return p; }
 
 
+
+// ---- the non-conv ops of the gradient pipe (kernels/bck_ops_f32.hip).  Bandwidth kernels: no tile to choose, only the geometry to fold into the code (pooling
+// window / planes; LRN window and channel block) and the grid.
+static bck_op_desc_t const kBckOps[] = {
+  {"hip_pool_yx", 1, "bodahip_pool_yx", "Pooling", {"in"}, {"out", "out_in_yx"}, true},
+  {"hip_spreading", 2, "bodahip_spreading", "Spreading", {"out", "out_grad_loss", "out_in_yx"}, {"in_grad_loss"}, true},
+  {"hip_lrn_sb", 3, "bodahip_lrn_sb", "LRN", {"in"}, {"out", "out_scale_base"}, false},
+  {"hip_bck_lrn", 4, "bodahip_bck_lrn", "BckLRN", {"in", "out", "out_grad_loss", "out_scale_base"}, {"in_grad_loss"}, false},
+  {"hip_zero_if_non_pos", 5, "bodahip_zero_if_non_pos", "ZeroIfNonPos", {"in", "cond"}, {"out"}, false},
+  {"hip_softmax", 6, "bodahip_softmax", "SoftmaxWithLoss", {"in"}, {"prob"}, false},
+  {"hip_sm_grad_and_loss", 7, "bodahip_sm_grad_and_loss", "SoftmaxWithLoss", {"prob", "label"}, {"in_grad_loss", "loss_per_pel"}, false},
+  {"hip_sum_loss_over_imgs", 8, "bodahip_sum_loss_over_imgs", "SoftmaxWithLoss", {"loss_per_pel"}, {"loss"}, false},
+};
+bck_op_desc_t const *find_bck_op(string const &fn) { for (auto const &d : kBckOps) if (fn == d.fn) return &d; return nullptr; }
+std::vector<bck_op_desc_t const *> bck_ops_of_type(string const &t) {
+  std::vector<bck_op_desc_t const *> r;
+  for (auto const &d : kBckOps) if (t == d.type_a) r.push_back(&d);   // (the table lists SoftmaxWithLoss's three calls in the order of src/rtc_fwd.cc:384-386)
+  return r;
+}
+bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
+  bck_op_desc_t const *d = nullptr;
+  for (auto const &e : kBckOps) if (e.op == g.op) d = &e;
+  if (!d) rt_err("plan_bck_op: unknown op " + std::to_string(g.op));
+  string const what = d->fn;
+  bck_plan_t r; r.p.bck_ops = true; r.p.kname = d->kname; r.p.defs = {"-DOP=" + std::to_string(g.op)};
+  auto D = [&](char const *n, long v) { r.p.defs.push_back(string("-D") + n + "=" + std::to_string(v)); };
+  auto lim = [&](double elems) { if (4.0 * elems >= 2147483648.0) unsup_err(what + ": tensors of 2 GiB or more (32-bit element offsets)"); };
+  if (g.B < 0 || g.C < 0) rt_err(what + ": negative dims");
+  double const in_e = (double)g.B * g.C * g.H * g.W, out_e = (double)g.B * g.C * g.OH * g.OW;
+  if (g.op == 1 || g.op == 2) {
+    if (g.KH < 1 || g.KW < 1 || g.SY < 1 || g.SX < 1 || g.PY < 0 || g.PX < 0 || g.H < 1 || g.W < 1 || g.OH < 1 || g.OW < 1) rt_err(what + ": zero kern_sz / stride / plane");
+    if (g.KH > 64 || g.KW > 64) unsup_err(what + ": pooling windows of at most 64 x 64");
+    bool const small = g.H + 2 * g.PY < g.KH || g.W + 2 * g.PX < g.KW;   // either padded dim below the window: a 1 x 1 output (src/conv_util.cc:198-204)
+    auto osz = [&](int in, int k, int s, int pd) { return small ? 1 : (in + 2 * pd - k + s - 1) / s + 1; };
+    if (osz(g.H, g.KH, g.SY, g.PY) != g.OH || osz(g.W, g.KW, g.SX, g.PX) != g.OW) rt_err(what + ": out plane does not follow from in / kern_sz / stride / in_pad (the pooling rule: a partial last window counts)");
+    if (g.op == 1 && g.avg) unsup_err(what + ": out_in_yx is the argmax of a MAX pooling (avg_pool must be 0)");
+    lim(in_e); lim(out_e);
+    D("H", g.H); D("W", g.W); D("OH", g.OH); D("OW", g.OW); D("KH", g.KH); D("KW", g.KW); D("SY", g.SY); D("SX", g.SX); D("PY", g.PY); D("PX", g.PX);
+    if (g.op == 2) D("AVG", g.avg ? 1 : 0);
+    r.threads = (long)((g.op == 1) ? out_e : in_e);
+    r.algo_bytes = 4.0 * ((g.op == 1) ? (in_e + 2 * out_e) : (in_e + out_e * (g.avg ? 1 : 2)));
+  } else if (g.op == 3 || g.op == 4) {
+    if (g.LS < 1 || g.LS % 2 == 0) unsup_err(what + ": local_size=" + std::to_string(g.LS) + ": only odd windows (an even local_size has no centre channel)");
+    if (g.LS > 15) unsup_err(what + ": local_size of at most 15 (the window lives in registers)");
+    lim(in_e);
+    // channel blocks: enough threads for ~8 (lrn_sb: ~4, its blocks re-walk the channels below them) waves per SIMD even on small planes (13 x 13 at 256 images),
+    // at least 8 channels per thread
+    long const pels = std::max<long>(1, g.B * (long)g.H * g.W), target = (long)num_cus * ((g.op == 3) ? 1024 : 2048);
+    long const ncb = std::max<long>(1, std::min<long>((target + pels - 1) / pels, (g.C + 7) / 8));
+    r.CB = (int)std::max<long>(1, (g.C + ncb - 1) / ncb);
+    if (g.op == 4) r.CB = std::min(r.CB, 32);   // (its walk is fully unrolled)
+    D("LS", g.LS); D("CB", r.CB);
+    r.threads = g.B * (long)g.H * g.W * ((g.C + r.CB - 1) / r.CB);
+    r.algo_bytes = 4.0 * in_e * ((g.op == 3) ? 3 : 5);
+  } else if (g.op == 5) {
+    if (g.n < 0) rt_err(what + ": negative size");
+    lim((double)g.n);
+    r.threads = g.n; r.algo_bytes = 12.0 * g.n;
+  } else if (g.op == 6 || g.op == 7) {
+    if (g.C < 1) rt_err(what + ": no channels");
+    lim((double)g.B * g.C);
+    r.threads = (g.op == 6) ? g.B * 64 : g.B * (long)g.C;
+    r.algo_bytes = (g.op == 6) ? 8.0 * g.B * g.C : 4.0 * (2.0 * g.B * g.C + 2.0 * g.B);
+  } else {
+    lim((double)g.B);
+    r.threads = g.B > 0 ? 1 : 0; r.block = 64; r.algo_bytes = 4.0 * (g.B + 1);
+  }
+  long const blocks = (r.threads + r.block - 1) / r.block;
+  if (blocks >= (1L << 31)) unsup_err(what + ": too many workgroups");
+  r.grid = (uint32_t)blocks;
+  return r;
+}
+
 } // namespace bodahip

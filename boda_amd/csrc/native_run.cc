@@ -45,6 +45,50 @@ static conv_geom_t bck_geom_of_op(op_base_t const &op) {
   return g;
 }
 
+// The non-conv ops of the gradient pipe: a kernel's geometry from the op (OP_INFO of boda_amd/op.py: Pooling / Spreading carry in, out, kern_sz, stride, in_pad,
+// avg_pool, emit_out_in_yx; LRN / BckLRN in, alpha, beta, k, local_size, emit_out_scale_base; ZeroIfNonPos in; SoftmaxWithLoss in, label).  The image count is the
+// op's; run() replaces it with the vars'.
+static float op_f32(op_base_t const &op, string const &an) {
+  p_nda_t const &n = op.get(an);
+  if (n->dims.tn != "float" || n->dims.sz() != 0 || !n->rp) rt_err("op: '" + an + "' is not a float scalar");
+  return *static_cast<float const *>(n->rp);
+}
+static void need_nchw(dims_t const &d, string const &what) {
+  if (!(d.sz() == 4 && d.names(0) == "img" && d.names(1) == "chan" && d.names(2) == "y" && d.names(3) == "x")) rt_err(what + " must be img:chan:y:x, got " + d.pretty_str());
+}
+static bck_op_geom_t bck_op_geom_of_op(op_base_t const &op, bck_op_desc_t const &d) {
+  string const &t = op.get_type(); string const fn = d.fn;
+  if (t != d.type_a) rt_err(fn + ": a function of op type " + d.type_a + ", not " + t);
+  bck_op_geom_t g; g.op = d.op;
+  if (d.op == 1 || d.op == 2) {
+    dims_t const &in = op.get_dims("in"), &out = op.get_dims("out"), &ks = op.get_dims("kern_sz"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
+    need_nchw(in, fn + ": in"); need_nchw(out, fn + ": out");
+    if (out.dims(0) != in.dims(0) || out.dims(1) != in.dims(1)) rt_err(fn + ": out img / chan differ from in");
+    g.B = in.dims(0); g.C = (int)in.dims(1); g.H = (int)in.dims(2); g.W = (int)in.dims(3); g.OH = (int)out.dims(2); g.OW = (int)out.dims(3);
+    g.KH = (int)ks.dsz("y"); g.KW = (int)ks.dsz("x"); g.SY = (int)st.dsz("y"); g.SX = (int)st.dsz("x"); g.PY = (int)pad.dsz("y"); g.PX = (int)pad.dsz("x");
+    g.avg = op.get_u32("avg_pool") ? 1 : 0;
+    if (d.op == 1 && !op.get_u32("emit_out_in_yx")) unsup_err(fn + ": a Pooling with emit_out_in_yx=0 belongs to the forward pipe; hip_pool_yx is the pooling that also writes out_in_yx");
+  } else if (d.op == 3 || d.op == 4) {
+    dims_t const &in = op.get_dims("in"); need_nchw(in, fn + ": in");
+    g.B = in.dims(0); g.C = (int)in.dims(1); g.H = (int)in.dims(2); g.W = (int)in.dims(3);
+    g.LS = (int)op.get_u32("local_size"); g.alpha = op_f32(op, "alpha"); g.beta = op_f32(op, "beta"); g.k = op_f32(op, "k");
+    if (d.op == 3 && !op.get_u32("emit_out_scale_base")) unsup_err(fn + ": an LRN with emit_out_scale_base=0 belongs to the forward pipe; hip_lrn_sb is the LRN that also writes out_scale_base");
+  } else if (d.op == 5) {
+    g.n = (long)op.get_dims("in").dims_prod();
+  } else {
+    dims_t const &in = op.get_dims("in"), &lab = op.get_dims("label"); need_nchw(in, fn + ": in");
+    if (in.dims(2) != 1 || in.dims(3) != 1 || lab.sz() != 3 || lab.names(0) != "img" || lab.dims(1) != 1 || lab.dims(2) != 1 || lab.dims(0) != in.dims(0))
+      unsup_err(fn + ": only 1 x 1 planes (in img:chan:1:1, label img:1:1): the reference reads label by image");
+    g.B = in.dims(0); g.C = (int)in.dims(1);
+  }
+  return g;
+}
+static string bck_plan_desc(bck_plan_t const &bp) {
+  string s = bp.p.kname + " grid=" + std::to_string(bp.grid) + " block=" + std::to_string(bp.block);
+  for (size_t i = 1; i < bp.p.defs.size(); ++i) s += " " + bp.p.defs[i];
+  return s;
+}
+
 size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int num_cus, string const &tile_arg, string *plan_out) {
   string const &t = op.get_type();
   // a tile that travels with the function (str_val hip_tile: per-op tuned tiles, see tile_override_t) is what run() would use
@@ -161,6 +205,21 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
       if (q.bconv_in) desc += " grid=" + std::to_string((long)((g.C + q.cfg.BI - 1) / q.cfg.BI) * bconv_in_tiles(g, q.cfg.BJ));
       if (q.kname == "bodahip_bconv_filts") desc += " ksl=" + std::to_string(q.cfg.SPLITK);
       if (!arch.empty()) bytes += compile_plan(q, arch, &log).size();
+    }
+    if (plan_out) *plan_out = desc;
+    return bytes;
+  } else if (!bck_ops_of_type(t).empty()) {   // a non-conv op of the gradient pipe: its annotated function, or (the bare op) all its functions in call order
+    std::vector<bck_op_desc_t const *> ds;
+    if (op.has_func_name()) {
+      bck_op_desc_t const *d = find_bck_op(op.get_func_name());
+      if (!d) rt_err("prebuild: " + t + " function '" + op.get_func_name() + "' has no native kernel");
+      ds.push_back(d);
+    } else ds = bck_ops_of_type(t);
+    string desc; size_t bytes = 0;
+    for (bck_op_desc_t const *d : ds) {
+      bck_plan_t const bp = plan_bck_op(bck_op_geom_of_op(op, *d), num_cus);
+      desc += (desc.empty() ? "" : " | ") + bck_plan_desc(bp);
+      if (!arch.empty()) bytes += compile_plan(bp.p, arch, &log).size();
     }
     if (plan_out) *plan_out = desc;
     return bytes;
@@ -532,6 +591,35 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
       if (fi.op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
       bconv_biases((float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(bgl), g);
     }
+    return;
+  }
+  if (bck_op_desc_t const *d = find_bck_op(fn)) {
+    // every var must have the dims the op gives its arg -- except the number of images, which only has to agree between the vars (a multi-device backend runs these
+    // functions on img shards: csrc/hip_multi.cc); the REF args must be the op's
+    bck_op_geom_t g = bck_op_geom_of_op(fi.op, *d);
+    long n_img = -1;
+    auto var_ptr = [&](char const *an) -> void * {
+      string const vn = var_of(am, an); dims_t const vd = host->nh_var_dims(vn); need_float(vd, an);
+      dims_t want = fi.op.get_dims(an);
+      if (want.sz() >= 1 && want.names(0) == "img" && vd.sz() == want.sz()) {
+        if (n_img < 0) n_img = vd.dims(0);
+        if ((long)vd.dims(0) != n_img) rt_err(fn + ": arg '" + an + "' has " + std::to_string(vd.dims(0)) + " images, another arg " + std::to_string(n_img));
+        want[0].sz = vd.dims(0); want.calc_strides();
+      }
+      if (!(vd == want)) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + fi.op.get_dims(an).pretty_str());
+      return host->nh_var_ptr(vn);
+    };
+    if (d->refs) for (char const *an : {"kern_sz", "stride", "in_pad"}) {
+      auto ri = am.find(an);
+      if (ri == am.end()) rt_err(fn + ": the REF arg '" + an + "' is required");
+      if (!(ri->second.get_dims(host->nh_rtc()) == fi.op.get_dims(an))) rt_err(fn + ": arg '" + an + "' disagrees with the op");
+    }
+    float const *ins[4] = {nullptr, nullptr, nullptr, nullptr}; float *outs[2] = {nullptr, nullptr};
+    for (size_t i = 0; i < d->ins.size(); ++i) ins[i] = (float const *)var_ptr(d->ins[i]);
+    for (size_t i = 0; i < d->outs.size(); ++i) outs[i] = (float *)var_ptr(d->outs[i]);
+    if (g.op == 5) g.n = (long)host->nh_var_dims(var_of(am, "in")).dims_prod();
+    else if (n_img >= 0) g.B = n_img;
+    bck_op(g, ins, outs);
     return;
   }
   if (fn == "hip_conv_filts_kmajor") {   // filts (out_chan:in_chan:y:x) -> filts_km ([K + 128][out_chan padded to 4], zeros in the padding): see filts_km above

@@ -6,6 +6,7 @@ Restates (behaviour only) the reference's
   * op_base_t {str_vals, nda_vals}    src/op_base.H:9-43, ordering src/op_base.cc:16-23
   * legacy '(type=T,dims_vals=(...))' form still used by test/sgemm-ops-{micro,tiny,small,full}.txt
   * Convolution / sgemm arg tables    src/conv_util.cc:25-35
+  * the non-conv forward / backward op tables (Pooling, LRN, Spreading, BckLRN, ZeroIfNonPos, SoftmaxWithLoss)   src/conv_util.cc:33-64
 """
 from __future__ import annotations
 from dataclasses import dataclass, field
@@ -180,8 +181,27 @@ class Nda:
         return "(" + ",".join(parts) + ")"
 
 
+def _f32_shortest(x: float) -> float:
+    """The shortest decimal that reads back as the same fp32 value (what the backend's op printer writes, csrc/lexp.cc)."""
+    import struct
+    rt = lambda v: struct.unpack("f", struct.pack("f", v))[0]
+    try:
+        want = rt(x)
+    except OverflowError:
+        return x
+    for p in range(1, 10):
+        s = float("%.*e" % (p - 1, want))
+        if rt(s) == want:
+            return s
+    return want
+
+
 def _fmt_val(x, tn: str) -> str:
+    if tn == "float" and float(x) == float(x) and abs(float(x)) != float("inf"):
+        x = _f32_shortest(float(x))
     if tn in ("float", "double", "half"):
+        if tn == "float" and abs(float(x)) >= 1e15:   # (the backend's printer writes such values in exponent form)
+            return repr(float(x))
         return repr(float(x)) if float(x) != int(float(x)) else str(int(float(x)))
     return str(int(x))
 
@@ -224,12 +244,25 @@ def parse_nda(l: Lexp) -> Nda:
 # op_base_t
 # ------------------------------------------------------------------------------------------------
 # (type) -> (bottom/input arg names, top/output arg names, required non-tensor fields); src/conv_util.cc:25-35
+_POOL_PARAMS = ("kern_sz", "stride", "in_pad", "avg_pool", "emit_out_in_yx")
+_LRN_PARAMS = ("alpha", "beta", "k", "local_size", "emit_out_scale_base")
 OP_INFO = {
     "Convolution": (("in", "filts", "biases"), ("out",), ("kern_sz", "stride", "in_pad", "out_chans")),
     "sgemm": (("a", "b"), ("c",), ()),
     # { in, filts, biases, out_grad_loss } -> { in_grad_loss, filts_grad_loss, biases_grad_loss }: each output has its matching input's dims (src/conv_util.cc:65-66,411-416)
     "BckConv": (("in", "filts", "biases", "out_grad_loss"), ("in_grad_loss", "filts_grad_loss", "biases_grad_loss"), ("kern_sz", "stride", "in_pad", "out_chans")),
+    # the non-conv ops of the gradient pipe, with the reference's arg names (src/conv_util.cc:33-64).  Scalars (uint32 / float ndas) and kern_sz / stride / in_pad ride in the op.
+    # Spreading is the pooling gradient and BckLRN the LRN gradient: each carries its forward op's parameters; ZeroIfNonPos is the ReLU gradient.
+    "Pooling": (("in",), ("out",), _POOL_PARAMS),
+    "LRN": (("in",), ("out",), _LRN_PARAMS),
+    "Spreading": (("out", "out_grad_loss", "in"), ("in_grad_loss",), _POOL_PARAMS),
+    "BckLRN": (("in", "out", "out_grad_loss"), ("in_grad_loss",), _LRN_PARAMS),
+    "ZeroIfNonPos": (("in", "cond"), ("out",), ()),
+    "SoftmaxWithLoss": (("in", "label"), ("in_grad_loss", "loss"), ()),
 }
+
+
+_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss")
 
 
 @dataclass
@@ -340,6 +373,83 @@ class Op:
             raise RtErr("BckConv: biases must hold out_chan values")
         return g
 
+    def get_f32(self, an: str) -> float:
+        n = self.get(an)
+        if n.dims is not None or n.tn != "float":
+            raise RtErr(f"op: {an!r} is not a float scalar")
+        return float(n.scalar())
+
+    def pool_geom(self) -> dict:
+        """Geometry of a Pooling or a Spreading (the pooling gradient, which carries the pooling's parameters): in (the pooling's input) img:chan:y:x, window, stride,
+        padding, and an output plane that follows the pooling rule -- a partial last window makes an output of its own, and an input smaller than the window gives
+        1 x 1 (src/conv_util.cc:198-204; what conv_pipe computes for its Pooling ops).  Spreading: out_grad_loss has out's dims, in_grad_loss has in's."""
+        t = self.get_type()
+        i, o = self.get_dims("in"), self.get_dims("out")
+        ks, st, pad = self.get_dims("kern_sz"), self.get_dims("stride"), self.get_dims("in_pad")
+        g = dict(B=i.dsz("img"), C=i.dsz("chan"), H=i.dsz("y"), W=i.dsz("x"), KH=ks.dsz("y"), KW=ks.dsz("x"), SY=st.dsz("y"), SX=st.dsz("x"),
+                 PY=pad.dsz("y"), PX=pad.dsz("x"), OH=o.dsz("y"), OW=o.dsz("x"), avg_pool=self.get_u32("avg_pool"), emit=self.get_u32("emit_out_in_yx"))
+        if i.names != ("img", "chan", "y", "x") or o.names != i.names or i.tn != "float" or o.tn != "float":
+            raise RtErr(f"{t}: in / out must be float img:chan:y:x")
+        if min(g["KH"], g["KW"], g["SY"], g["SX"]) < 1:
+            raise RtErr(f"{t}: zero kern_sz / stride")
+        if o.dsz("img") != g["B"] or o.dsz("chan") != g["C"]:
+            raise RtErr(f"{t}: out img / chan differ from in")
+        small = g["H"] + 2 * g["PY"] < g["KH"] or g["W"] + 2 * g["PX"] < g["KW"]   # EITHER padded dim below the window: 1 x 1 (pad_in_sz.both_dims_ge)
+        for hw, k, s, p, oo in (("H", "KH", "SY", "PY", "OH"), ("W", "KW", "SX", "PX", "OW")):
+            want = 1 if small else -(-(g[hw] + 2 * g[p] - g[k]) // g[s]) + 1
+            if want != g[oo]:
+                raise RtErr(f"{t}: out {oo}={g[oo]} != ceil(({hw}+2*{p}-{k})/{s})+1 = {want}")
+        if g["avg_pool"] not in (0, 1) or g["emit"] not in (0, 1):
+            raise RtErr(f"{t}: avg_pool / emit_out_in_yx must be 0 | 1")
+        if t == "Pooling" and g["emit"] and g["avg_pool"]:
+            raise UnsupErr("Pooling: emit_out_in_yx needs avg_pool=0 (an average has no argmax; test/rtc/pool.cucl says so)")
+        if t == "Spreading":
+            if self.get_dims("out_grad_loss") != o or self.get_dims("in_grad_loss") != i:
+                raise RtErr("Spreading: out_grad_loss must have out's dims and in_grad_loss in's")
+        return g
+
+    def lrn_geom(self) -> dict:
+        """An LRN or a BckLRN (which carries the LRN's parameters): every tensor float img:chan:y:x with equal dims; an odd local_size."""
+        t = self.get_type()
+        i = self.get_dims("in")
+        if i.names != ("img", "chan", "y", "x") or i.tn != "float":
+            raise RtErr(f"{t}: in must be float img:chan:y:x")
+        for an in OP_INFO[t][0] + OP_INFO[t][1]:
+            if self.get_dims(an) != i:
+                raise RtErr(f"{t}: {an} dims {self.get_dims(an).pretty()} != in dims {i.pretty()}")
+        g = dict(B=i.dsz("img"), C=i.dsz("chan"), H=i.dsz("y"), W=i.dsz("x"), local_size=self.get_u32("local_size"), emit=self.get_u32("emit_out_scale_base"),
+                 alpha=self.get_f32("alpha"), beta=self.get_f32("beta"), k=self.get_f32("k"))
+        if g["local_size"] < 1 or g["local_size"] % 2 == 0:
+            raise UnsupErr(f"{t}: local_size={g['local_size']}: only odd windows (a centred window over the channels)")
+        if g["emit"] not in (0, 1):
+            raise RtErr(f"{t}: emit_out_scale_base must be 0 | 1")
+        return g
+
+    def zinp_geom(self) -> dict:
+        i = self.get_dims("in")
+        if i.tn != "float" or self.get_dims("cond") != i or self.get_dims("out") != i:
+            raise RtErr("ZeroIfNonPos: in, cond and out must be float tensors of equal dims")
+        return dict(N=i.dims_prod())
+
+    def softmax_geom(self) -> dict:
+        """SoftmaxWithLoss: in / in_grad_loss img:chan:1:1, label img:1:1, loss 1:1.  Larger planes are refused on purpose: the reference template reads `label` by image only
+        (test/rtc/sm_grad_and_loss.cucl), which is wrong for them, and every net here ends in a 1 x 1 plane."""
+        i, l = self.get_dims("in"), self.get_dims("label")
+        if i.names != ("img", "chan", "y", "x") or l.names != ("img", "y", "x") or i.tn != "float" or l.tn != "float":
+            raise UnsupErr("SoftmaxWithLoss: in must be float img:chan:y:x and label float img:y:x")
+        if (i.dsz("y"), i.dsz("x")) != (1, 1) or (l.dsz("y"), l.dsz("x")) != (1, 1):
+            raise UnsupErr("SoftmaxWithLoss: only 1 x 1 planes (in img:chan:1:1, label img:1:1): the reference reads label by image")
+        if l.dsz("img") != i.dsz("img"):
+            raise RtErr("SoftmaxWithLoss: label img != in img")
+        if self.get_dims("in_grad_loss") != i:
+            raise RtErr("SoftmaxWithLoss: in_grad_loss must have in's dims")
+        lo = self.get_dims("loss")
+        if lo.names != ("y", "x") or lo.sizes != (1, 1) or lo.tn != "float":
+            raise RtErr("SoftmaxWithLoss: loss must be float y=1:x=1")
+        if i.dsz("img") < 1 or i.dsz("chan") < 1:
+            raise RtErr("SoftmaxWithLoss: empty in")
+        return dict(B=i.dsz("img"), C=i.dsz("chan"))
+
     def sgemm_geom(self) -> dict:
         a, b, c = self.get_dims("a"), self.get_dims("b"), self.get_dims("c")
         g = dict(M=a.dsz("M"), K=a.dsz("K"), N=b.dsz("N"))
@@ -352,6 +462,8 @@ class Op:
         if self.get_type() == "sgemm":
             g = self.sgemm_geom()
             return 2 * g["M"] * g["N"] * g["K"]
+        if self.get_type() in _NON_GEMM_TYPES:   # bandwidth ops: no multiply-accumulate work is accounted
+            return 0
         if self.get_type() == "BckConv":   # two GEMMs of the forward size: the data and the filter gradient
             g = self.bck_conv_geom()
             return 4 * (g["B"] * g["OH"] * g["OW"]) * g["OC"] * (g["C"] * g["KH"] * g["KW"])
@@ -401,6 +513,14 @@ def parse_op(line: str) -> Op:
             op.conv_geom()
         elif t == "BckConv":
             op.bck_conv_geom()
+        elif t in ("Pooling", "Spreading"):
+            op.pool_geom()
+        elif t in ("LRN", "BckLRN"):
+            op.lrn_geom()
+        elif t == "ZeroIfNonPos":
+            op.zinp_geom()
+        elif t == "SoftmaxWithLoss":
+            op.softmax_geom()
         else:
             op.sgemm_geom()
     return op
