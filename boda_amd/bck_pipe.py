@@ -1,0 +1,434 @@
+"""Full-net gradient pipe: the graph reversal `add_bck_ops` and the training-form driver `ConvPipeBck`.
+
+Restates the behaviour of the reference's add_bck_ops=1 path (not its code):
+  * conv_pipe_t::add_bck_ops / add_bck_ops_rec / add_bck_ops_op / get_grad_loss_onn     src/conv_util.cc:729-879
+      every forward top is capped with a SoftmaxWithLoss (which itself writes <in>_grad_loss); every other forward op gets its gradient op -- Pooling -> Spreading,
+      LRN -> BckLRN, ReLU -> ZeroIfNonPos, Dropout -> BckDropout, Convolution -> BckConv, Concat -> Split; a node read by more than one op gets one partial gradient
+      per reader and a Reduce that sums them.  The list is built by a topological walk from the sources and appended REVERSED.
+  * conv_pipe_fwd_t::gen_op, the gradient half                                          src/rtc_fwd.cc:263-405
+      one call per function, vars kept on the device, the side vars <out>_in_yx / <out>_scale_base / <tag>_prob / <loss>_per_pel under those names, dropout's
+      det_drop_seed a by-value argument of the call that is rewritten per step.
+Every function is a native one (boda_amd/cnn_op.py: hip_conv, BCONV_FUNCS, BCK_OP_FUNCS, PIPE_OP_FUNCS), so the same pipe runs on be=hip and on be=cpu, the bit-exact
+checker.  Unfused, fp32, reference layouts, one device; ConvPipe / ConvPipeFwd (the inference pipe) are not touched.
+
+Where this departs from the reference, on purpose:
+  * an AVERAGE pooling keeps emit_out_in_yx=0 (an average has no argmax; the op layer refuses avg_pool=1 with emit_out_in_yx=1): hip_pool_yx then writes the average and
+    an <out>_in_yx of -1s, which is what the reference's template leaves there
+  * the forward ops run in the ConvPipe's definition order, which is a topological order like the reference's walk
+"""
+from __future__ import annotations
+import zlib
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .cnn_op import (NATIVE_ARGS, OpTune, add_bck_conv_annotations, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, pipe_func_args)
+from .conv_pipe import ConvPipe, PipeOp
+from .op import Dims, Nda, Op, RtErr, UnsupErr
+from .rtc import RtcArg, RtcFuncCall, RtcFuncInfo
+
+IN_PLACE_TYPES = ("ReLU", "Dropout", "BckDropout")   # and a ZeroIfNonPos whose out is its in (src/conv_util.cc:273-279)
+DROPOUT_RATIO = 0.5   # Dropout_coi's default (src/conv_util.cc:39); the ConvPipe records carry no ratio
+
+
+@dataclass
+class GradOp:
+    """One op of the pipe with gradient ops: the reference's conv_op_t reduced to tag / type / bots / tops.  `src` is the forward PipeOp whose parameters it carries."""
+    tag: str
+    type: str
+    bots: List[str]
+    tops: List[str]
+    src: Optional[PipeOp] = None
+
+    @property
+    def in_place(self) -> bool:
+        return self.type in IN_PLACE_TYPES or (self.type == "ZeroIfNonPos" and self.tops[0] == self.bots[0])
+
+
+@dataclass
+class _Node:
+    top_for: List[str] = field(default_factory=list)
+    bot_for: List[str] = field(default_factory=list)
+    in_place_ops: List[GradOp] = field(default_factory=list)
+
+
+@dataclass
+class BckPipe:
+    """What add_bck_ops returns: the forward ops, the loss ops and the gradient ops in run order, and every node's dims."""
+    cp: ConvPipe
+    ops: List[GradOp]
+    nodes: Dict[str, Dims]
+    label_node: str
+    n_fwd: int                                  # ops[:n_fwd] are the forward ops and the SoftmaxWithLoss caps
+    loss_nodes: List[str] = field(default_factory=list)
+
+    def fwd_ops(self) -> List[GradOp]:
+        return self.ops[:self.n_fwd]
+
+    def bck_ops(self) -> List[GradOp]:
+        return self.ops[self.n_fwd:]
+
+
+def _fwd_grad_op(cp: ConvPipe, o: PipeOp) -> GradOp:
+    if o.type == "Convolution":
+        return GradOp(o.tag, o.type, [o.bot, o.tag + "_filts", o.tag + "_biases"], [o.top], o)
+    if o.type == "Concat":
+        return GradOp(o.tag, o.type, list(o.bots), [o.top], o)
+    return GradOp(o.tag, o.type, [o.bot], [o.top], o)
+
+
+def add_bck_ops(cp: ConvPipe, label_node: str = "label", loss_tops: Optional[Sequence[str]] = None) -> BckPipe:
+    """The pipe of `cp` with gradient ops.  `loss_tops`: the forward nodes to cap with a SoftmaxWithLoss (default: the pipe's out node; GoogLeNet's auxiliary heads are
+    named here).  One cap is tagged `loss` and writes the node `loss`; several are tagged loss1, loss2, ... in the order given.  All of them read `label_node`."""
+    loss_tops = list(loss_tops) if loss_tops else [cp.out_node()]
+    fwd = [_fwd_grad_op(cp, o) for o in cp.ops]
+    nodes: Dict[str, Dims] = dict(cp.nodes); nodes.update(cp.params)
+    if label_node in nodes:
+        raise RtErr(f"add_bck_ops: the pipe already has a node {label_node!r}")
+    loss_nodes = []
+    for i, t in enumerate(loss_tops):
+        if t not in cp.nodes:
+            raise RtErr(f"add_bck_ops: loss top {t!r} is no node of the pipe")
+        tag = "loss" if len(loss_tops) == 1 else f"loss{i + 1}"
+        if tag in nodes or t + "_grad_loss" in nodes:
+            raise RtErr(f"add_bck_ops: node {tag!r} / {t + '_grad_loss'!r} already exists")
+        fwd.append(GradOp(tag, "SoftmaxWithLoss", [t, label_node], [t + "_grad_loss", tag]))
+        nodes[t + "_grad_loss"] = cp.nodes[t]
+        nodes[tag] = Dims.make("float", y=1, x=1)
+        nodes[label_node] = Dims.make("float", img=cp.nodes[t].dsz("img"), y=1, x=1)
+        loss_nodes.append(tag)
+
+    # the graph as the reference holds it: in-place ops hang off their node and are in nobody's bot_for / top_for (src/conv_util.cc:273-292)
+    g: Dict[str, _Node] = {}
+    by_tag: Dict[str, GradOp] = {}
+    for o in fwd:
+        if o.tag in by_tag:
+            raise RtErr(f"add_bck_ops: op tag {o.tag!r} used twice")
+        by_tag[o.tag] = o
+        if o.in_place:
+            g.setdefault(o.bots[0], _Node()).in_place_ops.append(o)
+            continue
+        for t in o.tops:
+            g.setdefault(t, _Node()).top_for.append(o.tag)
+        for b in o.bots:
+            g.setdefault(b, _Node()).bot_for.append(o.tag)
+
+    def grad_loss_onn(cop: GradOp, inn: str) -> str:
+        """The node that takes cop's contribution to inn's gradient: inn_grad_loss, or -- inn read by several ops and cop not in place -- the partial
+        inn_<producer or last in-place op>_0_split_<reader index>_grad_loss (get_grad_loss_onn)."""
+        n = g[inn]
+        if len(n.bot_for) == 1 or cop.in_place:
+            return inn + "_grad_loss"
+        wopn = "_" + inn   # data / label ...
+        if n.top_for:
+            wopn = "_" + (n.in_place_ops[-1].tag if n.in_place_ops else n.top_for[0])
+        return f"{inn}{wopn}_0_split_{n.bot_for.index(cop.tag)}_grad_loss"
+
+    def bck_of(cop: GradOp) -> Optional[GradOp]:
+        t, tag = cop.type, cop.tag + "_bck"
+        if t == "SoftmaxWithLoss":
+            assert cop.bots[0] + "_grad_loss" == cop.tops[0]
+            return None
+        if t == "Pooling":    # { out, out_grad_loss, in } -> in_grad_loss
+            return GradOp(tag, "Spreading", [cop.tops[0], cop.tops[0] + "_grad_loss", cop.bots[0]], [grad_loss_onn(cop, cop.bots[0])], cop.src)
+        if t == "ReLU":       # { in = X_grad_loss, cond = X } -> X_grad_loss
+            return GradOp(tag, "ZeroIfNonPos", [cop.tops[0] + "_grad_loss", cop.bots[0]], [grad_loss_onn(cop, cop.bots[0])], cop.src)
+        if t == "Dropout":
+            return GradOp(tag, "BckDropout", [cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, cop.bots[0])], cop.src)
+        if t == "Convolution":   # { in, filts, biases, out_grad_loss } -> the three gradients
+            return GradOp(tag, "BckConv", cop.bots + [cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, b) for b in cop.bots], cop.src)
+        if t == "Concat":
+            return GradOp(tag, "Split", [cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, b) for b in cop.bots], cop.src)
+        if t == "LRN":        # { in, out, out_grad_loss } -> in_grad_loss
+            return GradOp(tag, "BckLRN", [cop.bots[0], cop.tops[0], cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, cop.bots[0])], cop.src)
+        raise RtErr(f"FIXME: add_bck_ops: unhandled cop->type={t}")
+
+    seen: Dict[str, int] = {}
+    walk: List[GradOp] = []
+
+    def rec(nn: str) -> None:
+        n = g[nn]
+        if not n.bot_for:   # a sink: must be what a SoftmaxWithLoss wrote
+            if len(n.top_for) != 1 or by_tag[n.top_for[0]].type != "SoftmaxWithLoss":
+                raise RtErr(f"add_bck_ops: unhandled: top node {nn} not produced by SoftmaxWithLoss op")
+        for ip in reversed(n.in_place_ops):
+            b = bck_of(ip)
+            if b:
+                walk.append(b)
+        if len(n.bot_for) > 1:
+            walk.append(GradOp("reduce_" + nn + "_grad_loss", "Reduce", [grad_loss_onn(by_tag[r], nn) for r in n.bot_for], [nn + "_grad_loss"]))
+        for r in n.bot_for:
+            cop = by_tag[r]
+            seen[r] = seen.get(r, 0) + 1
+            if seen[r] != len(cop.bots):   # wait until all its bottoms were seen
+                continue
+            b = bck_of(cop)
+            if b:
+                walk.append(b)
+            for t in cop.tops:
+                rec(t)
+
+    for src in sorted(nn for nn, n in g.items() if not n.top_for):   # the reference's `bots`, a sorted set of names
+        rec(src)
+
+    # appended in reverse; a Reduce is kept only if nobody wrote its output yet and its first input exists (src/conv_util.cc:866-877): `label` has none
+    out = list(fwd)
+    for b in reversed(walk):
+        if b.type == "Reduce" and not (b.tops[0] not in nodes and b.bots[0] in nodes):
+            continue
+        for i in b.bots:
+            if i not in nodes:
+                raise RtErr(f"add_bck_ops: gradient op {b.tag} reads {i!r}, which no earlier op writes")
+        if b.type == "BckConv":
+            for t, s in zip(b.tops, b.bots[:3]):
+                nodes[t] = nodes[s]
+        elif b.type == "Split":
+            for t, s in zip(b.tops, b.src.bots):
+                nodes[t] = nodes[s]
+        elif b.type in ("Spreading", "BckLRN"):
+            nodes[b.tops[0]] = nodes[b.src.bot]
+        elif b.type == "Reduce":
+            if not 2 <= len(b.bots) <= 8:
+                raise UnsupErr(f"add_bck_ops: {b.tag} sums {len(b.bots)} partial gradients; hip_reduce takes 2 to 8")
+            nodes[b.tops[0]] = nodes[b.bots[0]]
+        else:                 # ZeroIfNonPos, BckDropout: in place on the gradient
+            nodes[b.tops[0]] = nodes[b.bots[0]]
+        out.append(b)
+    return BckPipe(cp, out, nodes, label_node, len(fwd), loss_nodes)
+
+
+# ------------------------------------------------------------------------------------------------
+# ops of the pipe as op_base_t lines
+# ------------------------------------------------------------------------------------------------
+_none = lambda y, x: Nda(Dims(("y", "x"), (y, x), "none"), "none")
+_u32 = lambda v: Nda(None, "uint32_t", (int(v),))
+_f32 = lambda v: Nda(None, "float", (float(np.float32(v)),))
+
+
+def grad_op_to_op(bp: BckPipe, o: GradOp) -> Op:
+    """The op_base_t of one op of the pipe, with the reference's arg names (boda_amd/op.py OP_INFO)."""
+    nd = lambda n: Nda(bp.nodes[n])
+    s, t = o.src, o.type
+    if t in ("Convolution", "BckConv"):
+        v = {"in": nd(o.bots[0]), "filts": nd(o.bots[1]), "biases": nd(o.bots[2]), "kern_sz": _none(*s.kern_sz), "stride": _none(*s.stride), "in_pad": _none(*s.in_pad),
+             "out_chans": _u32(s.out_chans)}
+        if t == "Convolution":
+            v["out"] = nd(o.tops[0])
+        else:
+            v.update({"out_grad_loss": nd(o.bots[3]), "in_grad_loss": Nda(bp.nodes[o.bots[0]]), "filts_grad_loss": nd(o.tops[1]), "biases_grad_loss": nd(o.tops[2])})
+        return Op({"type": t}, v)
+    if t in ("Pooling", "Spreading"):
+        v = {"kern_sz": _none(*s.kern_sz), "stride": _none(*s.stride), "in_pad": _none(*s.in_pad), "avg_pool": _u32(s.avg_pool), "emit_out_in_yx": _u32(0 if s.avg_pool else 1)}
+        if t == "Pooling":
+            v.update({"in": nd(o.bots[0]), "out": nd(o.tops[0])})
+        else:
+            v.update({"out": nd(o.bots[0]), "out_grad_loss": nd(o.bots[1]), "in": nd(o.bots[2]), "in_grad_loss": nd(o.tops[0])})
+        return Op({"type": t}, v)
+    if t in ("LRN", "BckLRN"):
+        ls, alpha, beta, k = s.lrn
+        v = {"local_size": _u32(ls), "alpha": _f32(alpha), "beta": _f32(beta), "k": _f32(k), "emit_out_scale_base": _u32(1)}
+        if t == "LRN":
+            v.update({"in": nd(o.bots[0]), "out": nd(o.tops[0])})
+        else:
+            v.update({"in": nd(o.bots[0]), "out": nd(o.bots[1]), "out_grad_loss": nd(o.bots[2]), "in_grad_loss": nd(o.tops[0])})
+        return Op({"type": t}, v)
+    if t == "ZeroIfNonPos":
+        return Op({"type": t}, {"in": nd(o.bots[0]), "cond": nd(o.bots[1]), "out": nd(o.tops[0])})
+    if t == "ReLU":
+        return Op({"type": t}, {"in": nd(o.bots[0]), "out": nd(o.tops[0])})
+    if t in ("Dropout", "BckDropout"):
+        return Op({"type": t}, {"in": nd(o.bots[0]), "out": nd(o.tops[0]), "dropout_ratio": _f32(getattr(s, "dropout_ratio", DROPOUT_RATIO))})
+    if t == "SoftmaxWithLoss":
+        return Op({"type": t}, {"in": nd(o.bots[0]), "label": nd(o.bots[1]), "in_grad_loss": nd(o.tops[0]), "loss": nd(o.tops[1])})
+    if t in ("Reduce", "Concat"):
+        v = {f"ins_{i}": nd(b) for i, b in enumerate(o.bots)}
+        v.update({"ins_num": _u32(len(o.bots)), "out": nd(o.tops[0])})
+        return Op({"type": t}, v)
+    if t == "Split":
+        v = {f"outs_{i}": nd(b) for i, b in enumerate(o.tops)}
+        v.update({"outs_num": _u32(len(o.tops)), "in": nd(o.bots[0])})
+        return Op({"type": t}, v)
+    raise UnsupErr(f"bck_pipe: op type {t!r} (op {o.tag}) has no native function")
+
+
+# ------------------------------------------------------------------------------------------------
+# driver
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class BckCall:
+    tag: str
+    fop: Op                      # the annotated function op
+    args: Dict[str, str]         # arg name -> var name (var args only; REF / by-value args follow from the function op)
+    rfc: RtcFuncCall
+    call_id: int = -1
+
+
+def host_params(bp: BckPipe, seed: int = 0) -> Dict[str, np.ndarray]:
+    """Deterministic host-made params for a pipe without trained weights: filts ~ N(0, 2 / fan_in) (so activations neither die nor blow up through the ReLUs), biases
+    ~ U(-0.1, 0.1), each seeded by its name.  (ConvPipeFwd's device generator is generated CUCL source, which be=cpu cannot run.)"""
+    out = {}
+    for n, d in bp.cp.params.items():
+        rng = np.random.default_rng([zlib.crc32(n.encode()), seed])
+        if n.endswith("_filts"):
+            fan_in = d.dsz("in_chan") * d.dsz("y") * d.dsz("x")
+            out[n] = (rng.standard_normal(d.sizes) * np.sqrt(2.0 / fan_in)).astype(np.float32)
+        else:
+            out[n] = rng.uniform(-0.1, 0.1, d.sizes).astype(np.float32)
+    return out
+
+
+class ConvPipeBck:
+    """The training-form step of a pipe with gradient ops over one backend (be=hip or be=cpu): forward, loss and every gradient, one call per native function."""
+
+    def __init__(self, rtc, op_tune: Optional[OpTune] = None):
+        self.rtc = rtc
+        self.op_tune = op_tune or OpTune()
+        self.bck_calls: List[BckCall] = []
+        self.vars: List[str] = []
+        self.funcs: List[str] = []
+        self.per_call_ms: List[Tuple[str, str, float]] = []
+        self.compute_dur_ms = 0.0
+
+    def _var(self, vn: str, dims: Dims) -> None:
+        if vn not in self.vars:
+            self.rtc.create_var_with_dims(vn, dims); self.vars.append(vn)
+
+    def init(self, bp: BckPipe, op_params: Optional[Dict[str, np.ndarray]] = None, gen_mode: int = 5) -> None:
+        """Create every var, annotate every op, compile, upload the params once.  Without op_params the params are host_params(bp, gen_mode)."""
+        if not isinstance(bp, BckPipe):
+            raise RtErr("ConvPipeBck.init: pass the pipe add_bck_ops returned")
+        self.bp = bp
+        rtc, tune = self.rtc, self.op_tune
+        for n, d in bp.nodes.items():
+            self._var(n, d)
+        fused = set()   # ReLUs taken into their convolution (src/rtc_fwd.cc:486-493): no forward call, their ZeroIfNonPos still runs
+        relu_of: Dict[str, bool] = {}
+        ops = bp.ops
+        for i, o in enumerate(ops[:bp.n_fwd]):
+            if o.type == "Convolution":
+                first_ip = next((q for q in ops[i + 1:bp.n_fwd] if q.in_place and q.bots[0] == o.tops[0]), None)
+                relu_of[o.tag] = bool(first_ip and first_ip.type == "ReLU")
+                if relu_of[o.tag]:
+                    fused.add(first_ip.tag)
+        infos: List[RtcFuncInfo] = []
+        for o in ops:
+            if o.tag in fused:
+                continue
+            op = grad_op_to_op(bp, o)
+            t = o.type
+            calls: List[Tuple[Op, Dict[str, str]]] = []
+            if t == "Convolution":
+                a = add_codegen_annotations(op, tune)
+                a.nda_vals["conv_has_relu"] = _u32(1 if relu_of[o.tag] else 0)
+                calls.append((a, {"filts": o.bots[1], "biases": o.bots[2], "in": o.bots[0], "out": o.tops[0]}))
+            elif t == "ReLU":    # one that follows no convolution: out = in > 0 ? in : +0 is hip_zero_if_non_pos with the node as its own condition
+                z = Op({"type": "ZeroIfNonPos"}, {"in": op_nd(bp, o.bots[0]), "cond": op_nd(bp, o.bots[0]), "out": op_nd(bp, o.bots[0])})
+                calls.append((add_bck_op_annotations(z, tune)[0], {"in": o.bots[0], "cond": o.bots[0], "out": o.bots[0]}))
+            elif t == "BckConv":
+                fi, fb, ff = add_bck_conv_annotations(op, tune)
+                calls.append((fi, {"filts": o.bots[1], "out_grad_loss": o.bots[3], "in_grad_loss": o.tops[0]}))
+                calls.append((fb, {"out_grad_loss": o.bots[3], "biases_grad_loss": o.tops[2]}))
+                calls.append((ff, {"in": o.bots[0], "out_grad_loss": o.bots[3], "filts_grad_loss": o.tops[1]}))
+            elif t == "Pooling":
+                self._var(o.tops[0] + "_in_yx", bp.nodes[o.tops[0]])
+                calls.append((add_bck_op_annotations(op, tune)[0], {"in": o.bots[0], "out": o.tops[0], "out_in_yx": o.tops[0] + "_in_yx"}))
+            elif t == "Spreading":
+                calls.append((add_bck_op_annotations(op, tune)[0], {"out": o.bots[0], "out_grad_loss": o.bots[1], "out_in_yx": o.bots[0] + "_in_yx", "in_grad_loss": o.tops[0]}))
+            elif t == "LRN":
+                self._var(o.tops[0] + "_scale_base", bp.nodes[o.tops[0]])
+                calls.append((add_bck_op_annotations(op, tune)[0], {"in": o.bots[0], "out": o.tops[0], "out_scale_base": o.tops[0] + "_scale_base"}))
+            elif t == "BckLRN":
+                calls.append((add_bck_op_annotations(op, tune)[0], {"in": o.bots[0], "out": o.bots[1], "out_grad_loss": o.bots[2], "out_scale_base": o.bots[1] + "_scale_base",
+                                                                    "in_grad_loss": o.tops[0]}))
+            elif t == "ZeroIfNonPos":
+                calls.append((add_bck_op_annotations(op, tune)[0], {"in": o.bots[0], "cond": o.bots[1], "out": o.tops[0]}))
+            elif t == "SoftmaxWithLoss":
+                prob, lpp = o.tag + "_prob", o.tops[1] + "_per_pel"
+                self._var(prob, bp.nodes[o.bots[0]]); self._var(lpp, bp.nodes[o.bots[1]])
+                fs, fg, fl = add_bck_op_annotations(op, tune)
+                calls.append((fs, {"in": o.bots[0], "prob": prob}))
+                calls.append((fg, {"prob": prob, "label": o.bots[1], "in_grad_loss": o.tops[0], "loss_per_pel": lpp}))
+                calls.append((fl, {"loss_per_pel": lpp, "loss": o.tops[1]}))
+            elif t in ("Dropout", "BckDropout"):
+                calls.append((add_pipe_op_annotations(op, tune)[0], {"inout": o.tops[0]}))
+            elif t == "Reduce":
+                calls.append((add_pipe_op_annotations(op, tune)[0], dict({f"ins_{i}": b for i, b in enumerate(o.bots)}, out=o.tops[0])))
+            elif t == "Concat":
+                for f, b in zip(add_pipe_op_annotations(op, tune), o.bots):
+                    calls.append((f, {"in": b, "out": o.tops[0]}))
+            elif t == "Split":
+                for f, tp in zip(add_pipe_op_annotations(op, tune), o.tops):
+                    calls.append((f, {"in": o.bots[0], "out": tp}))
+            else:
+                raise UnsupErr(f"ConvPipeBck: op type {t!r} (op {o.tag}) has no native function")
+            for fop, args in calls:
+                fname = f"bck_{len(self.bck_calls)}_{fop.get_func_name()}"
+                spec = pipe_func_args(fop)
+                am: Dict[str, RtcArg] = {}
+                for an, io in spec:
+                    if io == "REF":
+                        am[an] = RtcArg.ref(fop.get_dims(an))
+                    elif io == "VAL":
+                        am[an] = RtcArg.scalar(0, "uint32_t")
+                    else:
+                        am[an] = RtcArg.var(args[an])
+                infos.append(RtcFuncInfo(fname, "", [an for an, _ in spec], fop))
+                self.bck_calls.append(BckCall(o.tag, fop, dict(args), RtcFuncCall(fname, am)))
+                self.funcs.append(fname)
+        rtc.compile(infos)
+        params = op_params if op_params is not None else host_params(bp, gen_mode)
+        for n, d in bp.cp.params.items():
+            if n not in params:
+                raise RtErr(f"ConvPipeBck.init: no value for param {n!r}")
+            rtc.copy_nda_to_var(n, np.ascontiguousarray(params[n], np.float32).reshape(d.sizes))
+        self.set_det_drop_seed(0)
+
+    def set_det_drop_seed(self, seed: int) -> None:
+        """Rewrite the by-value det_drop_seed of every dropout call.  The forward and the backward call of one layer get the same seed (the gradient must drop what
+        the forward pass dropped); layers differ by their position among the pipe's Dropout ops."""
+        layer: Dict[str, int] = {}
+        for c in self.bck_calls:
+            if c.fop.get_func_name() != "hip_dropout":
+                continue
+            tag = c.tag[:-4] if c.tag.endswith("_bck") else c.tag
+            k = layer.setdefault(tag, len(layer))
+            c.rfc.arg_map["det_drop_seed"] = RtcArg.scalar((int(seed) + k * 0x9E3779B1) & 0xFFFFFFFF, "uint32_t")
+            c.rfc.invalidate()
+
+    def calls(self) -> List[Tuple[str, Op, Dict[str, RtcArg]]]:
+        """The ordered (tag, function op, arg map) list of the step."""
+        return [(c.tag, c.fop, dict(c.rfc.arg_map)) for c in self.bck_calls]
+
+    def run_bck(self, to_set_vns: Sequence[str], fwd: Dict[str, np.ndarray], to_get_vns: Sequence[str]) -> None:
+        """Set inputs (data, label) -> run all calls -> get outputs into `fwd`: ConvPipeFwd.run_fwd's contract."""
+        rtc = self.rtc
+        for v in to_set_vns:
+            rtc.copy_nda_to_var(v, fwd[v])
+        rtc.finish_and_sync()
+        self.run_device_only()
+        for v in to_get_vns:
+            fwd[v] = rtc.copy_var_to_nda(v)
+
+    def run_device_only(self) -> float:
+        """Run all calls once with the inputs already resident; -> ms first-call-start to last-call-end.  per_call_ms: (tag, function, ms) per call."""
+        rtc = self.rtc
+        for c in self.bck_calls:
+            c.call_id = rtc.run(c.rfc)
+        rtc.finish_and_sync()
+        ids = [c.call_id for c in self.bck_calls]
+        self.compute_dur_ms = rtc.get_dur(ids[0], ids[-1]) if ids else 0.0
+        self.per_call_ms = [(c.tag, c.fop.get_func_name(), rtc.get_dur(i, i)) for c, i in zip(self.bck_calls, ids)]
+        rtc.release_per_call_id_data()
+        return self.compute_dur_ms
+
+    def release(self) -> None:
+        for f in self.funcs:
+            self.rtc.release_func(f)
+        for v in self.vars:
+            self.rtc.release_var(v)
+        self.funcs, self.vars, self.bck_calls = [], [], []
+
+
+def op_nd(bp: BckPipe, node: str) -> Nda:
+    return Nda(bp.nodes[node])

@@ -208,7 +208,7 @@ def add_bck_op_annotations(op: Op, tune: OpTune) -> tuple:
     a = op.copy()
     if t in ("Pooling", "Spreading"):
         g = a.pool_geom()
-        if t == "Pooling" and not g["emit"]:
+        if t == "Pooling" and not g["emit"] and not g["avg_pool"]:   # (an average has no argmax: the gradient pipe's average poolings keep emit_out_in_yx=0, hip_pool_yx writes -1)
             raise UnsupErr("Pooling with emit_out_in_yx=0 is the forward pipe's (conv_pipe.ConvPipeFwd, POOL_TEMPLATE); hip_pool_yx is the pooling that also writes out_in_yx")
         a.nda_vals["out_in_yx"] = Nda(dims=a.get_dims("out"), tn="float")
     elif t in ("LRN", "BckLRN"):
@@ -228,6 +228,53 @@ def add_bck_op_annotations(op: Op, tune: OpTune) -> tuple:
         f.set_func_name(fn)
         outs.append(f)
     return tuple(outs)
+
+
+# the plumbing ops of the full-net gradient pipe (boda_amd/bck_pipe.py), kept apart from BCK_OP_FUNCS: Reduce sums a fan-out's partial gradients, Dropout / BckDropout are
+# the same in-place function, Concat / Split are one copy call per narrow tensor (src/rtc_fwd.cc:267-294,348-364,402-403)
+PIPE_OP_FUNCS: Dict[str, tuple] = {
+    "Reduce": ("hip_reduce",),
+    "Dropout": ("hip_dropout",),
+    "BckDropout": ("hip_dropout",),
+    "Concat": ("hip_concat",),
+    "Split": ("hip_split",),
+}
+
+
+def add_pipe_op_annotations(op: Op, tune: OpTune) -> tuple:
+    """-> the annotated native function ops of one plumbing op of the gradient pipe, in call order: Reduce -> (hip_reduce,) with args ins_0 .. ins_{n-1}, out; Dropout /
+    BckDropout -> (hip_dropout,) with the in-place arg `inout` (the reference's name) and the by-value det_drop_seed of the CALL; Concat -> one hip_concat per input,
+    each carrying that input as `in` and its first output channel as ocix; Split -> one hip_split per output (`out`, icix).  fp32, reference layouts only."""
+    t = op.get_type()
+    if t not in PIPE_OP_FUNCS:
+        raise RtErr(f"add_pipe_op_annotations: op type {t!r} is none of {sorted(PIPE_OP_FUNCS)}")
+    if tune.use_be not in ("", "hip") or tune.use_culibs:
+        raise UnsupErr(f"{t} variants of op_tune={tune.to_str()} are generated by the reference's CUCL code generator; be=hip provides {PIPE_OP_FUNCS[t][0]}")
+    if tune.hip_dtype not in ("", "f32") or tune.hip_layout or tune.hip_algo or tune.hip_out:
+        raise UnsupErr(f"{t}: fp32 in reference layout only (no bf16, channels-last or Winograd variant)")
+    fn = PIPE_OP_FUNCS[t][0]
+    outs = []
+    if t == "Reduce":
+        op.reduce_geom()
+        a = op.copy(); a.set_func_name(fn); outs.append(a)
+    elif t in ("Dropout", "BckDropout"):
+        op.dropout_geom()
+        a = op.copy(); a.nda_vals["inout"] = Nda(dims=a.get_dims("in"), tn="float"); a.set_func_name(fn); outs.append(a)
+    else:
+        g = op.concat_geom()
+        narrow, ix = ("in", "ocix") if t == "Concat" else ("out", "icix")
+        for an, c0, _ in g["chans"]:
+            a = Op(dict(op.str_vals), {narrow: op.get(an), ("out" if t == "Concat" else "in"): op.get("out" if t == "Concat" else "in")})
+            a.set_u32(ix, c0); a.set_func_name(fn); outs.append(a)
+    return tuple(outs)
+
+
+def pipe_func_args(fop: Op) -> tuple:
+    """The (arg, IN | OUT | REF | VAL) list of an annotated function op: NATIVE_ARGS, and for hip_reduce its ins_0 .. ins_{n-1} followed by out."""
+    fn = fop.get_func_name()
+    if fn == "hip_reduce":
+        return tuple((an, "IN") for an in fop.multi_names("ins")) + (("out", "OUT"),)
+    return NATIVE_ARGS[fn]
 
 
 # arg tables of the native side-door functions (the stubs test/rtc/cublas_sgemm.cucl:1-4, cudnn_conv.cucl:1-7)
@@ -256,6 +303,11 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_softmax": (("in", "IN"), ("prob", "OUT")),
     "hip_sm_grad_and_loss": (("prob", "IN"), ("label", "IN"), ("in_grad_loss", "OUT"), ("loss_per_pel", "OUT")),
     "hip_sum_loss_over_imgs": (("loss_per_pel", "IN"), ("loss", "OUT")),
+    # the gradient pipe's plumbing (test/rtc/dropout.cucl; the copy calls of src/rtc_fwd.cc:267-294).  VAL: a by-value scalar of the CALL (uint32 det_drop_seed).
+    # hip_reduce's list depends on the op (ins_0 .. ins_{n-1}, out): pipe_func_args
+    "hip_dropout": (("inout", "OUT"), ("det_drop_seed", "VAL")),
+    "hip_concat": (("in", "IN"), ("out", "OUT")),
+    "hip_split": (("in", "IN"), ("out", "OUT")),
 }
 
 

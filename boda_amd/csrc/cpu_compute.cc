@@ -96,14 +96,16 @@ void pool_yx(float const *in, float *out, float *out_in_yx, pool_geom_c const &g
   for (long pl = 0; pl < g.B * g.C; ++pl)
     for (long oy = 0; oy < g.OH; ++oy)
       for (long ox = 0; ox < g.OW; ++ox) {
-        float best = -3.402823466e+38f; long oyx = -1;
+        float best = g.avg ? 0.0f : -3.402823466e+38f, cnt = 0.0f; long oyx = -1;
         for (long kx = 0; kx < g.KW; ++kx)
           for (long ky = 0; ky < g.KH; ++ky) {
             long const iy = oy * g.SY + ky - g.PY, ix = ox * g.SX + kx - g.PX;
             if (iy < 0 || ix < 0 || ix >= g.W || iy >= g.H) continue;
             float const v = in[(pl * g.H + iy) * g.W + ix];
-            if (v > best) { best = v; oyx = iy * g.W + ix; }
+            if (g.avg) { best = best + v; cnt = cnt + 1.0f; }   // an average: the taps inside the plane, divided by their number; out_in_yx stays -1
+            else if (v > best) { best = v; oyx = iy * g.W + ix; }
           }
+        if (g.avg) best = best / cnt;
         out[(pl * g.OH + oy) * g.OW + ox] = best;
         out_in_yx[(pl * g.OH + oy) * g.OW + ox] = (float)oyx;
       }
@@ -175,6 +177,32 @@ void bck_lrn(float const *in, float const *out, float const *ogl, float const *s
 void zero_if_non_pos(float const *in, float const *cond, float *out, long n) {
 #pragma omp parallel for schedule(static)
   for (long i = 0; i < n; ++i) out[i] = (cond[i] > 0.0f) ? in[i] : 0.0f;
+}
+void reduce(float const *const *ins, int nin, float *out, long n) {   // a sequential chain from +0 in input order
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < n; ++i) {
+    float v = 0.0f;
+    for (int k = 0; k < nin; ++k) v = v + ins[k][i];
+    out[i] = v;
+  }
+}
+void dropout(float *inout, long n, float ratio, uint32_t seed) {
+  float const scale = (float)(1.0 / (1.0 - (double)ratio));
+  uint32_t const thresh = (uint32_t)((float)0xffffffffu * ratio);
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < n; ++i) {
+    uint32_t h = (uint32_t)i + seed;
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    inout[i] = (h > thresh) ? inout[i] * scale : 0.0f;
+  }
+}
+// concat (to_wide) / split: B images of `run` floats each <-> the floats [off, off + run) of every image of the wide tensor
+void copy_chan_range(float const *in, float *out, long B, long run, long wide, long off, bool to_wide) {
+#pragma omp parallel for schedule(static)
+  for (long img = 0; img < B; ++img) {
+    if (to_wide) memcpy(out + img * wide + off, in + img * run, sizeof(float) * run);
+    else memcpy(out + img * run, in + img * wide + off, sizeof(float) * run);
+  }
 }
 void softmax(float const *in, float *prob, long B, long C) {   // 1 x 1 planes; the reference's sequential sum
 #pragma omp parallel for schedule(static)
@@ -279,10 +307,24 @@ struct cpu_compute_t : public rtc_compute_t {
       {"hip_softmax", "SoftmaxWithLoss", {"in"}, {"prob"}, false},
       {"hip_sm_grad_and_loss", "SoftmaxWithLoss", {"prob", "label"}, {"in_grad_loss", "loss_per_pel"}, false},
       {"hip_sum_loss_over_imgs", "SoftmaxWithLoss", {"loss_per_pel"}, {"loss"}, false},
+      {"hip_reduce", "Reduce", {}, {"out"}, false},        // (inputs: ins_0 .. ins_{ins_num-1})
+      {"hip_dropout", "Dropout", {}, {"inout"}, false},    // (also BckDropout's)
+      {"hip_concat", "Concat", {"in"}, {"out"}, false},
+      {"hip_split", "Split", {"in"}, {"out"}, false},
     };
     for (auto const &d : tab) if (fn == d.fn) return &d;
     return nullptr;
   }
+  static std::vector<string> bck_op_ins(bck_op_fn_t const &d, op_base_t const &op) {
+    std::vector<string> r(d.ins.begin(), d.ins.end());
+    if (string(d.fn) == "hip_reduce") {
+      uint32_t const n = op.get_u32("ins_num");
+      if (n < 2 || n > 8) unsup_err("hip_reduce: ins_num=" + std::to_string(n) + ": 2 to 8 inputs");
+      for (uint32_t i = 0; i < n; ++i) r.push_back("ins_" + std::to_string(i));
+    }
+    return r;
+  }
+  static bool type_ok(bck_op_fn_t const &d, string const &t) { return t == d.type || (string(d.fn) == "hip_dropout" && t == "BckDropout"); }
   void compile(vect_rtc_func_info_t const &func_infos, rtc_compile_opts_t const &) override {
     assert_st(init_done);
     for (auto const &fi : func_infos) {
@@ -290,12 +332,12 @@ struct cpu_compute_t : public rtc_compute_t {
       string const fn = fi.op.has_func_name() ? fi.op.get_func_name() : string();
       if (!is_sgemm(fn) && !is_conv(fn) && !is_bck(fn) && !find_bck_op(fn))
         unsup_err("be=cpu runs the native sgemm / Convolution / BckConv functions and the gradient pipe's non-conv functions only (hip_sgemm, hip_conv and their aliases, hip_bconv_*, "
-                  "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs); '" +
+                  "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs, hip_reduce, hip_dropout, hip_concat, hip_split); '" +
                                                     (fn.empty() ? fi.func_name : fn) + "' is generated CUCL source, which needs a GPU backend");
       if (is_conv(fn)) (void)fi.op.get_u32("conv_has_relu");
       if (bck_op_fn_t const *d = find_bck_op(fn)) {
-        if (fi.op.get_type() != d->type) rt_err(fn + ": a function of op type " + d->type + ", not " + fi.op.get_type());
-        for (char const *an : d->ins) (void)fi.op.get_dims(an);
+        if (!type_ok(*d, fi.op.get_type())) rt_err(fn + ": a function of op type " + d->type + ", not " + fi.op.get_type());
+        for (string const &an : bck_op_ins(*d, fi.op)) (void)fi.op.get_dims(an);
         for (char const *an : d->outs) (void)fi.op.get_dims(an);
       }
       funcs.emplace(fi.func_name, cpu_func_t{fi});
@@ -461,8 +503,9 @@ struct cpu_compute_t : public rtc_compute_t {
       if (ri == am.end()) rt_err(fn + ": the REF arg '" + an + "' is required");
       if (!(ri->second.get_dims(*this) == op.get_dims(an))) rt_err(fn + ": arg '" + an + "' disagrees with the op");
     }
-    float *in[4] = {nullptr, nullptr, nullptr, nullptr}, *out[2] = {nullptr, nullptr};
-    for (size_t i = 0; i < d.ins.size(); ++i) in[i] = var_ptr(d.ins[i]);
+    float *in[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, *out[2] = {nullptr, nullptr};
+    std::vector<string> const in_ans = bck_op_ins(d, op);
+    for (size_t i = 0; i < in_ans.size(); ++i) in[i] = var_ptr(in_ans[i].c_str());
     for (size_t i = 0; i < d.outs.size(); ++i) out[i] = var_ptr(d.outs[i]);
     if (d.refs) {
       dims_t const &i4 = op.get_dims("in"), &o4 = op.get_dims("out"), &ks = op.get_dims("kern_sz"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
@@ -474,8 +517,7 @@ struct cpu_compute_t : public rtc_compute_t {
       auto osz = [&](long in_sz, long k, long s, long pd) { return small ? 1 : (in_sz + 2 * pd - k + s - 1) / s + 1; };
       if (osz(g.H, g.KH, g.SY, g.PY) != g.OH || osz(g.W, g.KW, g.SX, g.PX) != g.OW) rt_err(fn + ": out plane does not follow from in / kern_sz / stride / in_pad");
       if (fn == "hip_pool_yx") {
-        if (!op.get_u32("emit_out_in_yx")) unsup_err(fn + ": a Pooling with emit_out_in_yx=0 belongs to the forward pipe");
-        if (g.avg) unsup_err(fn + ": out_in_yx is the argmax of a MAX pooling (avg_pool must be 0)");
+        if (!op.get_u32("emit_out_in_yx") && !g.avg) unsup_err(fn + ": a Pooling with emit_out_in_yx=0 belongs to the forward pipe");
         pool_yx(in[0], out[0], out[1], g);
       } else spreading(in[1], in[2], out[0], g);
     } else if (fn == "hip_lrn_sb" || fn == "hip_bck_lrn") {
@@ -489,6 +531,26 @@ struct cpu_compute_t : public rtc_compute_t {
       } else bck_lrn(in[0], in[1], in[2], in[3], out[0], g);
     } else if (fn == "hip_zero_if_non_pos") {
       zero_if_non_pos(in[0], in[1], out[0], (long)get_var_dims(var_of(am, "in")).dims_prod());
+    } else if (fn == "hip_reduce") {
+      dims_t const &od = op.get_dims("out");
+      for (string const &an : in_ans) if (!(op.get_dims(an) == od)) rt_err(fn + ": " + an + " dims " + op.get_dims(an).pretty_str() + " differ from out's " + od.pretty_str());
+      reduce(in, (int)in_ans.size(), out[0], (long)get_var_dims(var_of(am, "out")).dims_prod());
+    } else if (fn == "hip_dropout") {
+      float const ratio = op_f32(op, "dropout_ratio");
+      if (!(ratio > 0.0f && ratio < 1.0f)) rt_err(fn + ": dropout_ratio=" + std::to_string(ratio) + " must lie inside (0, 1)");
+      auto si = am.find("det_drop_seed");
+      if (si == am.end() || !si->second.is_valid() || si->second.is_var() || !si->second.v->rp_elems() || si->second.v->dims.tn != "uint32_t" || si->second.v->dims.sz() != 0)
+        rt_err(fn + ": 'det_drop_seed' must be a by-value uint32_t scalar of the call");
+      dropout(out[0], (long)get_var_dims(var_of(am, "inout")).dims_prod(), ratio, *(uint32_t const *)si->second.v->rp_elems());
+    } else if (fn == "hip_concat" || fn == "hip_split") {
+      bool const cat = fn == "hip_concat";
+      dims_t const &i4 = op.get_dims("in"), &o4 = op.get_dims("out");
+      if (i4.sz() != 4 || o4.sz() != 4) rt_err(fn + ": in / out must be img:chan:y:x");
+      dims_t const &nar = cat ? i4 : o4, &wid = cat ? o4 : i4;
+      if (nar.dims(0) != wid.dims(0) || nar.dims(2) != wid.dims(2) || nar.dims(3) != wid.dims(3)) rt_err(fn + ": in " + i4.pretty_str() + " and out " + o4.pretty_str() + " differ in img / y / x");
+      long const hw = (long)nar.dims(2) * nar.dims(3), cix = op.get_u32(cat ? "ocix" : "icix");
+      if (cix + (long)nar.dims(1) > (long)wid.dims(1)) rt_err(fn + ": channels [" + std::to_string(cix) + ", " + std::to_string(cix + (long)nar.dims(1)) + ") do not fit the wide tensor's " + std::to_string(wid.dims(1)));
+      copy_chan_range(in[0], out[0], n_img, (long)nar.dims(1) * hw, (long)wid.dims(1) * hw, cix * hw, cat);
     } else {
       dims_t const &i4 = op.get_dims("in");
       if (i4.sz() != 4 || i4.dims(2) != 1 || i4.dims(3) != 1) unsup_err(fn + ": only 1 x 1 planes (in img:chan:1:1, label img:1:1): the reference reads label by image");

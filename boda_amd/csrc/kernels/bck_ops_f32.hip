@@ -5,7 +5,9 @@
 // The semantics are the reference templates', quirks included (parity is the contract); every kernel keeps the WRITTEN order of its fp32 operations: the
 // file is compiled with contraction and reassociation off, so a*b + c stays two roundings, and it calls the real powf / expf / logf.
 //
-// OP 1  bodahip_pool_yx  (test/rtc/pool.cucl with emit_out_in_yx=1, max pooling)   in -> out, out_in_yx
+// OP 1  bodahip_pool_yx  (test/rtc/pool.cucl with emit_out_in_yx=1)   in -> out, out_in_yx
+//   * AVG=1 (an average pooling of the gradient pipe): the taps inside the plane are summed from +0 in the same order and divided by their NUMBER (the window
+//     clipped by the border); out_in_yx is -1 everywhere, what the template leaves for an average.  The rest describes AVG=0
 //   * padding pels never take part; taps are visited kx OUTER, ky inner
 //   * the maximum starts at -FLT_MAX and is replaced on strict `>`: the FIRST maximal tap in that order wins a tie (and a NaN never wins)
 //   * out_in_yx is a FLOAT holding in_y*W + in_x of the winning tap, or -1 when no tap won (a window of -FLT_MAX / NaN only, or one wholly in the padding)
@@ -35,8 +37,19 @@
 //   * label is a FLOAT holding the class index, read by image; in_grad_loss = (prob - [chan == label]) / img_count: an fp32 subtract, then an fp32 divide
 //   * loss_per_pel = -logf(max(prob[label], FLT_MIN)); a label outside [0, chan) matches no channel and reads no memory: its loss is -logf(FLT_MIN)
 // OP 8  bodahip_sum_loss_over_imgs  (test/rtc/sum_loss_over_imgs.cucl)   loss = (sequential fp32 sum of loss_per_pel over the images from +0) / img_count: one thread
+// OP 9  bodahip_reduce  (test/rtc/reduce.cucl, the sum of a fan-out's partial gradients)   ins_0 .. ins_{NIN-1} -> out
+//   * out[i] = (((+0 + ins_0[i]) + ins_1[i]) + ...): a sequential fp32 chain from +0 in the op's input order, so two -0 inputs give +0
+// OP 10 bodahip_dropout  (test/rtc/dropout.cucl; the gradient of dropout is the same dropout)   inout, in place
+//   * h = (uint32)flat index + seed (wraps), then h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16
+//   * inout = h > thresh ? inout * scale : +0;  thresh = (uint32)((float)0xffffffff * ratio) and scale = (float)(1 / (1 - (double)ratio)) come from the host;
+//     the seed is a run-time argument: a new seed is no new specialisation
+// OP 11 bodahip_concat / OP 12 bodahip_split  (the reference's copy calls, src/rtc_fwd.cc:267-294)   in -> out: an img:chan:y:x tensor copied into (11) / out of (12)
+//   the channel range [cix, cix + chan) of a wider one.  Per image that range is one run of `run` = chan * y * x consecutive floats, `wide` = the wider tensor's
+//   floats per image, `off` = cix * y * x
+// OP 9 .. 12 take float4 over the first n4 quads and scalars over the tail, like OP 5; the host sets n4 = 0 unless every pointer (11, 12: every per-image run) is
+// 16-byte aligned.  Quads never straddle a run: 11 / 12 use them only when run, wide and off are multiples of 4.
 //
-// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX (2: AVG) | 3, 4: LS CB.  Host side: plan_bck_op (native_plan.cc), native_kernels.cc.
+// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN.  Host side: plan_bck_op (native_plan.cc), native_kernels.cc.
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -49,7 +62,10 @@ struct bck_ops_args_t {   // must match native_internal.h
   float *o0; float *o1;                                                 // outputs, in the function's arg order
   long n;                                                               // threads that have work
   int B, C, HW, n4;                                                     // images, channels, pels of a plane; OP 5: float4 quads
-  float f0, f1, f2, f3;                                                 // LRN: alpha / local_size, beta, k, ((2 * -beta) * alpha) / local_size
+  float f0, f1, f2, f3;                                                 // LRN: alpha / local_size, beta, k, ((2 * -beta) * alpha) / local_size; OP 10: f0 = scale
+  float const *p4; float const *p5; float const *p6; float const *p7;   // OP 9: inputs 4 .. 7
+  unsigned seed, thresh;                                                // OP 10
+  int run, wide, off;                                                   // OP 11, 12: floats of one image's channel range, of one image of the wider tensor, offset of the range
 };
 
 constexpr float kFltMax = 3.402823466e+38f, kFltMin = 1.175494351e-38f;
@@ -61,7 +77,11 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
   int const ox = (int)(id % OW), oy = (int)((id / OW) % OH);
   long const plane = id / (OW * OH);
   float const *const in = p.p0 + plane * (H * W);
+#if AVG
+  float best = 0.0f, cnt = 0.0f; int const oyx = -1;
+#else
   float best = -kFltMax; int oyx = -1;
+#endif
 #pragma unroll
   for (int kx = 0; kx < KW; ++kx) {
 #pragma unroll
@@ -69,10 +89,17 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
       int const iy = oy * SY + ky - PY, ix = ox * SX + kx - PX;
       if (iy >= 0 && ix >= 0 && ix < W && iy < H) {
         float const v = in[iy * W + ix];
+#if AVG
+        best = best + v; cnt = cnt + 1.0f;
+#else
         if (v > best) { best = v; oyx = iy * W + ix; }
+#endif
       }
     }
   }
+#if AVG
+  best = best / cnt;
+#endif
   p.o0[id] = best;
   p.o1[id] = (float)oyx;
 }
@@ -241,6 +268,61 @@ extern "C" __global__ __launch_bounds__(64) void KNAME(bck_ops_args_t const p) {
   p.o0[0] = v / (float)p.B;
 }
 
+#elif OP == 9
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+#define RED_INS(T, ix) \
+  T v = (T)0.0f + ((T const *)p.p0)[ix]; v = v + ((T const *)p.p1)[ix]; \
+  if (NIN > 2) v = v + ((T const *)p.p2)[ix]; if (NIN > 3) v = v + ((T const *)p.p3)[ix]; if (NIN > 4) v = v + ((T const *)p.p4)[ix]; \
+  if (NIN > 5) v = v + ((T const *)p.p5)[ix]; if (NIN > 6) v = v + ((T const *)p.p6)[ix]; if (NIN > 7) v = v + ((T const *)p.p7)[ix];
+extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) {
+  long const id = (long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= p.n) return;
+  if (id < p.n4) {
+    RED_INS(f32x4, id)
+    ((f32x4 *)p.o0)[id] = v;
+  } else {
+    long const e = 4L * p.n4 + (id - p.n4);
+    RED_INS(float, e)
+    p.o0[e] = v;
+  }
+}
+
+#elif OP == 10
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float drop1(float x, unsigned ix, bck_ops_args_t const &p) {
+  unsigned h = ix + p.seed;
+  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  return h > p.thresh ? x * p.f0 : 0.0f;
+}
+extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) {
+  long const id = (long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= p.n) return;
+  if (id < p.n4) {
+    f32x4 v = ((f32x4 const *)p.o0)[id];
+    unsigned const e = 4u * (unsigned)id;
+    v.x = drop1(v.x, e, p); v.y = drop1(v.y, e + 1u, p); v.z = drop1(v.z, e + 2u, p); v.w = drop1(v.w, e + 3u, p);
+    ((f32x4 *)p.o0)[id] = v;
+  } else {
+    long const e = 4L * p.n4 + (id - p.n4);
+    p.o0[e] = drop1(p.o0[e], (unsigned)e, p);
+  }
+}
+
+#elif OP == 11 || OP == 12
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) {
+  long const id = (long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= p.n) return;
+  long const e = (id < p.n4) ? 4L * id : 4L * p.n4 + (id - p.n4);   // first element, counted in the narrow tensor
+  long const img = e / p.run;
+  long const w = img * p.wide + p.off + (e - img * p.run);          // the same element in the wide tensor
+#if OP == 11
+  if (id < p.n4) *(f32x4 *)(p.o0 + w) = *(f32x4 const *)(p.p0 + e); else p.o0[w] = p.p0[e];
 #else
-#error "bck_ops_f32.hip: -DOP=1..8"
+  if (id < p.n4) *(f32x4 *)(p.o0 + e) = *(f32x4 const *)(p.p0 + w); else p.o0[e] = p.p0[w];
+#endif
+}
+
+#else
+#error "bck_ops_f32.hip: -DOP=1..12"
 #endif

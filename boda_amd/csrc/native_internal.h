@@ -62,10 +62,15 @@ struct bck_ops_args_t { // must match kernels/bck_ops_f32.hip
   long n;
   int B, C, HW, n4;
   float f0, f1, f2, f3;
+  float const *p4; float const *p5; float const *p6; float const *p7;
+  unsigned seed, thresh;
+  int run, wide, off;
 };
-// a native function of the gradient pipe's non-conv ops: its kernel, and its var args in the function's arg order
+// a native function of the gradient pipe's non-conv ops: its kernel, and its var args in the function's arg order (hip_reduce: ins_0 .. ins_{ins_num-1}, see
+// bck_op_ins; hip_dropout also takes the by-value uint32 det_drop_seed)
 struct bck_op_desc_t { char const *fn; int op; char const *kname; char const *type_a; std::vector<char const *> ins, outs; bool refs; };
 bck_op_desc_t const *find_bck_op(string const &fn);                 // null: not one of them
+std::vector<string> bck_op_ins(bck_op_desc_t const &d, op_base_t const &op);   // the input var args of d for this op
 std::vector<bck_op_desc_t const *> bck_ops_of_type(string const &t);   // the functions of a bare op, in the reference's call order (empty: not such an op)
 struct bck_plan_t { plan_t p; long threads = 0; uint32_t grid = 0, block = 256; int CB = 0; double algo_bytes = 0; };
 bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus);

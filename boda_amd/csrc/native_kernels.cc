@@ -48,8 +48,10 @@ void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
     return;
   }
   if (bck_op_desc_t const *d = find_bck_op(fn)) {   // the gradient pipe's non-conv ops: the (annotated) op must carry every arg's dims
-    for (char const *an : d->ins) (void)fi.op.get_dims(an);
+    for (string const &an : bck_op_ins(*d, fi.op)) (void)fi.op.get_dims(an);
     for (char const *an : d->outs) (void)fi.op.get_dims(an);
+    if (d->op == 10) (void)fi.op.get("dropout_ratio");
+    if (d->op == 11 || d->op == 12) (void)fi.op.get_u32(d->op == 11 ? "ocix" : "icix");
     if (d->refs) for (char const *an : {"kern_sz", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     return;
   }
@@ -778,11 +780,23 @@ void native_kernels_t::bck_op(bck_op_geom_t const &g, float const *const *ins, f
   a.p0 = ins[0]; a.p1 = ins[1]; a.p2 = ins[2]; a.p3 = ins[3]; a.o0 = outs[0]; a.o1 = outs[1];
   a.n = bp.threads; a.B = (int)g.B; a.C = g.C; a.HW = g.H * g.W;
   if (g.op == 3 || g.op == 4) { a.f0 = g.alpha / (float)g.LS; a.f1 = g.beta; a.f2 = g.k; a.f3 = ((2.0f * -g.beta) * g.alpha) / (float)g.LS; }
-  if (g.op == 5) {   // float4 over whole quads when the three buffers are 16-byte aligned, scalars over the rest
-    bool const al = (((uintptr_t)ins[0] | (uintptr_t)ins[1] | (uintptr_t)outs[0]) & 15) == 0;
-    a.n4 = al ? (int)(g.n / 4) : 0; a.n = (long)a.n4 + (g.n - 4L * a.n4);
+  bool const quads = g.op == 5 || (g.op >= 9 && g.op <= 12);
+  if (quads) {   // float4 over whole quads when every buffer is 16-byte aligned, scalars over the rest
+    long n = g.n;
+    uintptr_t al = (uintptr_t)outs[0];
+    for (int i = 0; i < 8; ++i) al |= (uintptr_t)ins[i];   // (unused slots are null)
+    if (g.op == 9) { a.p4 = ins[4]; a.p5 = ins[5]; a.p6 = ins[6]; a.p7 = ins[7]; }
+    if (g.op == 10) {   // the template's own arithmetic: a float product truncated to uint32, a double quotient rounded to float
+      a.seed = g.seed; a.thresh = (uint32_t)((float)0xffffffffu * g.ratio); a.f0 = (float)(1.0 / (1.0 - (double)g.ratio));
+    }
+    if (g.op == 11 || g.op == 12) {   // every per-image run must start on a quad in both tensors, and be whole quads
+      n = bp.threads;
+      a.run = g.C * g.H * g.W; a.wide = g.CT * g.H * g.W; a.off = g.cix * g.H * g.W;
+      al |= (uintptr_t)(((a.run | a.wide | a.off) & 3) ? 1 : 0);
+    }
+    a.n4 = (al & 15) == 0 ? (int)(n / 4) : 0; a.n = (long)a.n4 + (n - 4L * a.n4);
   }
-  uint32_t const grid = (g.op == 5) ? (uint32_t)((a.n + 255) / 256) : bp.grid;
+  uint32_t const grid = quads ? (uint32_t)((a.n + 255) / 256) : bp.grid;
   void *params[] = {&a};
   if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, bp.block, params), "hipModuleLaunchKernel(bck_op)");
   last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = grid; last_launch.block = bp.block;

@@ -27,6 +27,9 @@
 //       hip_softmax             in prob                                                                            test/rtc/softmax.cucl
 //       hip_sm_grad_and_loss    prob label in_grad_loss loss_per_pel                                               test/rtc/sm_grad_and_loss.cucl
 //       hip_sum_loss_over_imgs  loss_per_pel loss                                                                  test/rtc/sum_loss_over_imgs.cucl
+//       hip_reduce              ins_0 .. ins_{ins_num-1} out                  (2 .. 8 inputs)                      test/rtc/reduce.cucl
+//       hip_dropout             inout det_drop_seed(by-value uint32)          (Dropout and BckDropout)             test/rtc/dropout.cucl
+//       hip_concat / hip_split  in out   (ocix / icix in the op: one call per input / output)                      src/rtc_fwd.cc:267-294
 //     hip_conv_winograd                 same contract as hip_conv; 3x3 / stride-1 layers through F(2x2,3x3) Winograd (mrd <= ~2e-3)
 // and lands them on kernels/gemm_conv_f32.hip (and, for short-K 1x1 convs with a long pel axis, kernels/k1_stream_f32.hip),
 // specialised with hiprtc per shape class at first use.
@@ -81,8 +84,11 @@ struct conv_geom_t { int B, C, H, W, OC, KH, KW, SY, SX, PY, PX, OH, OW; bool re
 struct post_ops_t { int PKH = 0, PKW = 0, PSY = 1, PSX = 1, PPY = 0, PPX = 0, POH = 0, POW = 0, LRN_N = 0; float alpha = 0.f, beta = 0.f, k = 0.f; bool pooled() const { return PKH > 0; } };
 
 // one call of a non-conv gradient-pipe kernel (kernels/bck_ops_f32.hip): op = 1 pool_yx, 2 spreading, 3 lrn_sb, 4 bck_lrn, 5 zero_if_non_pos, 6 softmax, 7 sm_grad_and_loss,
-// 8 sum_loss_over_imgs.  B images of C channels; H x W = the pooling's INPUT plane (LRN: the plane), OH x OW its output plane; n = elements (zero_if_non_pos)
-struct bck_op_geom_t { int op = 0; long B = 0; int C = 0, H = 1, W = 1, OH = 1, OW = 1, KH = 1, KW = 1, SY = 1, SX = 1, PY = 0, PX = 0, avg = 0, LS = 1; float alpha = 0.f, beta = 0.f, k = 0.f; long n = 0; };
+// 8 sum_loss_over_imgs, 9 reduce, 10 dropout, 11 concat, 12 split.  B images of C channels; H x W = the pooling's INPUT plane (LRN: the plane), OH x OW its output
+// plane; n = elements (zero_if_non_pos, reduce, dropout).  reduce: nin inputs.  dropout: ratio from the op, seed from the
+// call.  concat / split: B images of the narrow tensor's C channels (planes H x W) at channels [cix, cix + C) of the wide tensor's CT
+struct bck_op_geom_t { int op = 0; long B = 0; int C = 0, H = 1, W = 1, OH = 1, OW = 1, KH = 1, KW = 1, SY = 1, SX = 1, PY = 0, PX = 0, avg = 0, LS = 1; float alpha = 0.f, beta = 0.f, k = 0.f; long n = 0;
+  int nin = 0; float ratio = 0.f; uint32_t seed = 0; int CT = 0, cix = 0; };
 
 struct launch_info_t { string kernel; tile_cfg_t cfg; uint32_t grid = 0, block = 0; double flops = 0, algo_bytes = 0; };
 
@@ -120,7 +126,7 @@ struct native_kernels_t {
   void bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g);
   void bconv_filts(float const *in, float const *out_grad, float *filts_grad, conv_geom_t const &g);
   void bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g);
-  // the non-conv ops of the gradient pipe: ins / outs in the function's arg order (up to four / two raw device pointers)
+  // the non-conv ops of the gradient pipe: ins / outs in the function's arg order (up to eight / two raw device pointers)
   void bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs);
   void conv_winograd(float const *filts, float const *biases, float const *in, float *out, conv_geom_t const &g, int out_ctot, int out_coff);
 

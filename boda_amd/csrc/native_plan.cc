@@ -1214,11 +1214,24 @@ static bck_op_desc_t const kBckOps[] = {
   {"hip_softmax", 6, "bodahip_softmax", "SoftmaxWithLoss", {"in"}, {"prob"}, false},
   {"hip_sm_grad_and_loss", 7, "bodahip_sm_grad_and_loss", "SoftmaxWithLoss", {"prob", "label"}, {"in_grad_loss", "loss_per_pel"}, false},
   {"hip_sum_loss_over_imgs", 8, "bodahip_sum_loss_over_imgs", "SoftmaxWithLoss", {"loss_per_pel"}, {"loss"}, false},
+  {"hip_reduce", 9, "bodahip_reduce", "Reduce", {}, {"out"}, false},       // (its inputs: bck_op_ins)
+  {"hip_dropout", 10, "bodahip_dropout", "Dropout", {}, {"inout"}, false}, // (also the function of a BckDropout: the gradient of dropout is dropout)
+  {"hip_concat", 11, "bodahip_concat", "Concat", {"in"}, {"out"}, false},
+  {"hip_split", 12, "bodahip_split", "Split", {"in"}, {"out"}, false},
 };
+std::vector<string> bck_op_ins(bck_op_desc_t const &d, op_base_t const &op) {
+  std::vector<string> r(d.ins.begin(), d.ins.end());
+  if (d.op == 9) {   // the reference's flattened names of the multi arg `ins`
+    uint32_t const n = op.get_u32("ins_num");
+    if (n < 2 || n > 8) unsup_err("hip_reduce: ins_num=" + std::to_string(n) + ": 2 to 8 inputs");
+    for (uint32_t i = 0; i < n; ++i) r.push_back("ins_" + std::to_string(i));
+  }
+  return r;
+}
 bck_op_desc_t const *find_bck_op(string const &fn) { for (auto const &d : kBckOps) if (fn == d.fn) return &d; return nullptr; }
 std::vector<bck_op_desc_t const *> bck_ops_of_type(string const &t) {
   std::vector<bck_op_desc_t const *> r;
-  for (auto const &d : kBckOps) if (t == d.type_a) r.push_back(&d);   // (the table lists SoftmaxWithLoss's three calls in the order of src/rtc_fwd.cc:384-386)
+  for (auto const &d : kBckOps) if (t == d.type_a || (d.op == 10 && t == "BckDropout")) r.push_back(&d);   // (the table lists SoftmaxWithLoss's three calls in the order of src/rtc_fwd.cc:384-386)
   return r;
 }
 bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
@@ -1237,10 +1250,9 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
     bool const small = g.H + 2 * g.PY < g.KH || g.W + 2 * g.PX < g.KW;   // either padded dim below the window: a 1 x 1 output (src/conv_util.cc:198-204)
     auto osz = [&](int in, int k, int s, int pd) { return small ? 1 : (in + 2 * pd - k + s - 1) / s + 1; };
     if (osz(g.H, g.KH, g.SY, g.PY) != g.OH || osz(g.W, g.KW, g.SX, g.PX) != g.OW) rt_err(what + ": out plane does not follow from in / kern_sz / stride / in_pad (the pooling rule: a partial last window counts)");
-    if (g.op == 1 && g.avg) unsup_err(what + ": out_in_yx is the argmax of a MAX pooling (avg_pool must be 0)");
     lim(in_e); lim(out_e);
     D("H", g.H); D("W", g.W); D("OH", g.OH); D("OW", g.OW); D("KH", g.KH); D("KW", g.KW); D("SY", g.SY); D("SX", g.SX); D("PY", g.PY); D("PX", g.PX);
-    if (g.op == 2) D("AVG", g.avg ? 1 : 0);
+    if (g.op == 2 || g.avg) D("AVG", g.avg ? 1 : 0);   // (hip_pool_yx: AVG=1 is the average pooling of the gradient pipe, out_in_yx all -1)
     r.threads = (long)((g.op == 1) ? out_e : in_e);
     r.algo_bytes = 4.0 * ((g.op == 1) ? (in_e + 2 * out_e) : (in_e + out_e * (g.avg ? 1 : 2)));
   } else if (g.op == 3 || g.op == 4) {
@@ -1260,6 +1272,23 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
     if (g.n < 0) rt_err(what + ": negative size");
     lim((double)g.n);
     r.threads = g.n; r.algo_bytes = 12.0 * g.n;
+  } else if (g.op == 9) {
+    if (g.nin < 2 || g.nin > 8) unsup_err(what + ": ins_num=" + std::to_string(g.nin) + ": 2 to 8 inputs");
+    if (g.n < 0) rt_err(what + ": negative size");
+    lim((double)g.n);
+    D("NIN", g.nin);
+    r.threads = g.n; r.algo_bytes = 4.0 * (g.nin + 1) * g.n;
+  } else if (g.op == 10) {
+    if (!(g.ratio > 0.0f && g.ratio < 1.0f)) rt_err(what + ": dropout_ratio=" + std::to_string(g.ratio) + " must lie inside (0, 1)");
+    if (g.n < 0) rt_err(what + ": negative size");
+    lim((double)g.n);
+    r.threads = g.n; r.algo_bytes = 8.0 * g.n;
+  } else if (g.op == 11 || g.op == 12) {
+    char const *const ix = (g.op == 11) ? "ocix" : "icix";
+    if (g.C < 1 || g.CT < 1 || g.H < 1 || g.W < 1) rt_err(what + ": empty tensor");
+    if (g.cix < 0 || (long)g.cix + g.C > g.CT) rt_err(what + ": channels [" + std::to_string(g.cix) + ", " + std::to_string((long)g.cix + g.C) + ") (" + ix + " + chan) do not fit the wide tensor's " + std::to_string(g.CT));
+    lim((double)g.B * g.CT * g.H * g.W);
+    r.threads = g.B * (long)g.C * g.H * g.W; r.algo_bytes = 8.0 * (double)r.threads;
   } else if (g.op == 6 || g.op == 7) {
     if (g.C < 1) rt_err(what + ": no channels");
     lim((double)g.B * g.C);

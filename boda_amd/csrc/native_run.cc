@@ -58,7 +58,7 @@ static void need_nchw(dims_t const &d, string const &what) {
 }
 static bck_op_geom_t bck_op_geom_of_op(op_base_t const &op, bck_op_desc_t const &d) {
   string const &t = op.get_type(); string const fn = d.fn;
-  if (t != d.type_a) rt_err(fn + ": a function of op type " + d.type_a + ", not " + t);
+  if (t != d.type_a && !(d.op == 10 && t == "BckDropout")) rt_err(fn + ": a function of op type " + d.type_a + ", not " + t);
   bck_op_geom_t g; g.op = d.op;
   if (d.op == 1 || d.op == 2) {
     dims_t const &in = op.get_dims("in"), &out = op.get_dims("out"), &ks = op.get_dims("kern_sz"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
@@ -67,7 +67,7 @@ static bck_op_geom_t bck_op_geom_of_op(op_base_t const &op, bck_op_desc_t const 
     g.B = in.dims(0); g.C = (int)in.dims(1); g.H = (int)in.dims(2); g.W = (int)in.dims(3); g.OH = (int)out.dims(2); g.OW = (int)out.dims(3);
     g.KH = (int)ks.dsz("y"); g.KW = (int)ks.dsz("x"); g.SY = (int)st.dsz("y"); g.SX = (int)st.dsz("x"); g.PY = (int)pad.dsz("y"); g.PX = (int)pad.dsz("x");
     g.avg = op.get_u32("avg_pool") ? 1 : 0;
-    if (d.op == 1 && !op.get_u32("emit_out_in_yx")) unsup_err(fn + ": a Pooling with emit_out_in_yx=0 belongs to the forward pipe; hip_pool_yx is the pooling that also writes out_in_yx");
+    if (d.op == 1 && !op.get_u32("emit_out_in_yx") && !g.avg) unsup_err(fn + ": a Pooling with emit_out_in_yx=0 belongs to the forward pipe; hip_pool_yx is the pooling that also writes out_in_yx");
   } else if (d.op == 3 || d.op == 4) {
     dims_t const &in = op.get_dims("in"); need_nchw(in, fn + ": in");
     g.B = in.dims(0); g.C = (int)in.dims(1); g.H = (int)in.dims(2); g.W = (int)in.dims(3);
@@ -75,6 +75,17 @@ static bck_op_geom_t bck_op_geom_of_op(op_base_t const &op, bck_op_desc_t const 
     if (d.op == 3 && !op.get_u32("emit_out_scale_base")) unsup_err(fn + ": an LRN with emit_out_scale_base=0 belongs to the forward pipe; hip_lrn_sb is the LRN that also writes out_scale_base");
   } else if (d.op == 5) {
     g.n = (long)op.get_dims("in").dims_prod();
+  } else if (d.op == 9) {
+    dims_t const &out = op.get_dims("out");
+    g.nin = (int)op.get_u32("ins_num"); g.n = (long)out.dims_prod();
+    for (string const &an : bck_op_ins(d, op)) if (!(op.get_dims(an) == out)) rt_err(fn + ": " + an + " dims " + op.get_dims(an).pretty_str() + " differ from out's " + out.pretty_str());
+  } else if (d.op == 10) {
+    g.ratio = op_f32(op, "dropout_ratio"); g.n = (long)op.get_dims(op.has("inout") ? "inout" : "in").dims_prod();   // (the bare op carries in / out, its function the in-place arg inout)
+  } else if (d.op == 11 || d.op == 12) {
+    dims_t const &in = op.get_dims("in"), &out = op.get_dims("out"); need_nchw(in, fn + ": in"); need_nchw(out, fn + ": out");
+    dims_t const &nar = (d.op == 11) ? in : out, &wid = (d.op == 11) ? out : in;
+    if (nar.dims(0) != wid.dims(0) || nar.dims(2) != wid.dims(2) || nar.dims(3) != wid.dims(3)) rt_err(fn + ": in " + in.pretty_str() + " and out " + out.pretty_str() + " differ in img / y / x");
+    g.B = nar.dims(0); g.C = (int)nar.dims(1); g.H = (int)nar.dims(2); g.W = (int)nar.dims(3); g.CT = (int)wid.dims(1); g.cix = (int)op.get_u32((d.op == 11) ? "ocix" : "icix");
   } else {
     dims_t const &in = op.get_dims("in"), &lab = op.get_dims("label"); need_nchw(in, fn + ": in");
     if (in.dims(2) != 1 || in.dims(3) != 1 || lab.sz() != 3 || lab.names(0) != "img" || lab.dims(1) != 1 || lab.dims(2) != 1 || lab.dims(0) != in.dims(0))
@@ -216,6 +227,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
       ds.push_back(d);
     } else ds = bck_ops_of_type(t);
     string desc; size_t bytes = 0;
+    if (!op.has_func_name() && (t == "Concat" || t == "Split")) unsup_err("prebuild: a bare " + t + " is one call per " + (t == "Concat" ? "input" : "output") + ": annotate it (cnn_op.add_pipe_op_annotations) and pass the function ops");
     for (bck_op_desc_t const *d : ds) {
       bck_plan_t const bp = plan_bck_op(bck_op_geom_of_op(op, *d), num_cus);
       desc += (desc.empty() ? "" : " | ") + bck_plan_desc(bp);
@@ -614,10 +626,18 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
       if (ri == am.end()) rt_err(fn + ": the REF arg '" + an + "' is required");
       if (!(ri->second.get_dims(host->nh_rtc()) == fi.op.get_dims(an))) rt_err(fn + ": arg '" + an + "' disagrees with the op");
     }
-    float const *ins[4] = {nullptr, nullptr, nullptr, nullptr}; float *outs[2] = {nullptr, nullptr};
-    for (size_t i = 0; i < d->ins.size(); ++i) ins[i] = (float const *)var_ptr(d->ins[i]);
+    float const *ins[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float *outs[2] = {nullptr, nullptr};
+    std::vector<string> const in_ans = bck_op_ins(*d, fi.op);
+    for (size_t i = 0; i < in_ans.size(); ++i) ins[i] = (float const *)var_ptr(in_ans[i].c_str());
     for (size_t i = 0; i < d->outs.size(); ++i) outs[i] = (float *)var_ptr(d->outs[i]);
+    if (g.op == 10) {   // the seed is a by-value uint32 of the CALL: a new seed is no new function
+      auto si = am.find("det_drop_seed");
+      if (si == am.end() || !si->second.is_valid() || si->second.is_var() || !si->second.v->rp_elems() || si->second.v->dims.tn != "uint32_t" || si->second.v->dims.sz() != 0)
+        rt_err(fn + ": 'det_drop_seed' must be a by-value uint32_t scalar of the call");
+      g.seed = *(uint32_t const *)si->second.v->rp_elems();
+    }
     if (g.op == 5) g.n = (long)host->nh_var_dims(var_of(am, "in")).dims_prod();
+    else if (g.op == 9 || g.op == 10) g.n = (long)host->nh_var_dims(var_of(am, d->outs[0])).dims_prod();
     else if (n_img >= 0) g.B = n_img;
     bck_op(g, ins, outs);
     return;

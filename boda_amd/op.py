@@ -6,7 +6,7 @@ Restates (behaviour only) the reference's
   * op_base_t {str_vals, nda_vals}    src/op_base.H:9-43, ordering src/op_base.cc:16-23
   * legacy '(type=T,dims_vals=(...))' form still used by test/sgemm-ops-{micro,tiny,small,full}.txt
   * Convolution / sgemm arg tables    src/conv_util.cc:25-35
-  * the non-conv forward / backward op tables (Pooling, LRN, Spreading, BckLRN, ZeroIfNonPos, SoftmaxWithLoss)   src/conv_util.cc:33-64
+  * the non-conv forward / backward op tables (Pooling, LRN, Spreading, BckLRN, ZeroIfNonPos, SoftmaxWithLoss, Reduce, Concat, Split, Dropout, BckDropout)   src/conv_util.cc:33-64
 """
 from __future__ import annotations
 from dataclasses import dataclass, field
@@ -259,10 +259,17 @@ OP_INFO = {
     "BckLRN": (("in", "out", "out_grad_loss"), ("in_grad_loss",), _LRN_PARAMS),
     "ZeroIfNonPos": (("in", "cond"), ("out",), ()),
     "SoftmaxWithLoss": (("in", "label"), ("in_grad_loss", "loss"), ()),
+    # the plumbing ops of the gradient pipe (src/conv_util.cc:39-40,55-58).  Reduce and Concat read the MULTI arg `ins`, Split writes the multi arg `outs`: such an arg is
+    # carried under the reference's flattened names ins_0 .. ins_{ins_num-1} / outs_0 .. outs_{outs_num-1} (Op.multi_names); the tuples here list the fixed args only
+    "Reduce": ((), ("out",), ("ins_num",)),
+    "Concat": ((), ("out",), ("ins_num",)),
+    "Split": (("in",), (), ("outs_num",)),
+    "Dropout": (("in",), ("out",), ("dropout_ratio",)),
+    "BckDropout": (("in",), ("out",), ("dropout_ratio",)),
 }
 
 
-_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss")
+_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout")
 
 
 @dataclass
@@ -450,6 +457,52 @@ class Op:
             raise RtErr("SoftmaxWithLoss: empty in")
         return dict(B=i.dsz("img"), C=i.dsz("chan"))
 
+    def multi_names(self, an: str) -> tuple:
+        """The flattened names of a multi arg: `ins` -> ins_0 .. ins_{ins_num-1} (likewise `outs`), each of which must be in the op."""
+        names = tuple(f"{an}_{i}" for i in range(self.get_u32(an + "_num")))
+        for n in names:
+            self.get_dims(n)
+        return names
+
+    def reduce_geom(self) -> dict:
+        """Reduce: out = the sum of 2 to 8 float tensors of out's dims (GoogLeNet's widest fan-out needs 4)."""
+        o = self.get_dims("out")
+        n = self.get_u32("ins_num")
+        if n < 2 or n > 8:
+            raise UnsupErr(f"Reduce: ins_num={n}: 2 to 8 inputs")
+        for an in self.multi_names("ins"):
+            if self.get_dims(an) != o or o.tn != "float":
+                raise RtErr(f"Reduce: {an} dims {self.get_dims(an).pretty()} != out dims {o.pretty()} (float tensors of equal dims)")
+        return dict(N=o.dims_prod(), n=n)
+
+    def dropout_geom(self) -> dict:
+        """Dropout / BckDropout: in place (in and out of equal dims), a ratio strictly inside (0, 1) as the reference asserts (src/rtc_fwd.cc:353-355)."""
+        t = self.get_type()
+        i = self.get_dims("in")
+        if self.get_dims("out") != i or i.tn != "float":
+            raise RtErr(f"{t}: in and out must be float tensors of equal dims")
+        r = self.get_f32("dropout_ratio")
+        if not (0.0 < r < 1.0):
+            raise RtErr(f"{t}: dropout_ratio={r} must lie inside (0, 1)")
+        return dict(N=i.dims_prod(), ratio=r)
+
+    def concat_geom(self) -> dict:
+        """Concat (ins_i -> out) / Split (in -> outs_i): float img:chan:y:x tensors of equal img / y / x whose channels add up to the wide tensor's.  -> B, H, W, CT and
+        chans: per narrow tensor (arg name, first channel in the wide tensor, channels)."""
+        t = self.get_type()
+        wide, names = (self.get_dims("out"), self.multi_names("ins")) if t == "Concat" else (self.get_dims("in"), self.multi_names("outs"))
+        if wide.names != ("img", "chan", "y", "x") or wide.tn != "float" or not names:
+            raise RtErr(f"{t}: tensors must be float img:chan:y:x, and at least one narrow tensor")
+        chans, c0 = [], 0
+        for an in names:
+            d = self.get_dims(an)
+            if d.names != wide.names or d.tn != "float" or (d.dsz("img"), d.dsz("y"), d.dsz("x")) != (wide.dsz("img"), wide.dsz("y"), wide.dsz("x")):
+                raise RtErr(f"{t}: {an} dims {d.pretty()} differ from the wide tensor's {wide.pretty()} in img / y / x")
+            chans.append((an, c0, d.dsz("chan"))); c0 += d.dsz("chan")
+        if c0 != wide.dsz("chan"):
+            raise RtErr(f"{t}: the narrow tensors hold {c0} channels, the wide one {wide.dsz('chan')}")
+        return dict(B=wide.dsz("img"), CT=wide.dsz("chan"), H=wide.dsz("y"), W=wide.dsz("x"), chans=chans)
+
     def sgemm_geom(self) -> dict:
         a, b, c = self.get_dims("a"), self.get_dims("b"), self.get_dims("c")
         g = dict(M=a.dsz("M"), K=a.dsz("K"), N=b.dsz("N"))
@@ -473,7 +526,8 @@ class Op:
     def algo_bytes(self) -> int:
         """4*(in+out+filts+biases) resp. 4*(a+b+c) (src/latex-util.H:119,133)."""
         ins, outs, _ = OP_INFO[self.get_type()]
-        return sum(self.get_dims(a).bytes_sz() for a in ins + outs)
+        multi = {"Reduce": ("ins",), "Concat": ("ins",), "Split": ("outs",)}.get(self.get_type(), ())
+        return sum(self.get_dims(a).bytes_sz() for a in ins + outs + tuple(n for m in multi for n in self.multi_names(m)))
 
 
 def parse_op(line: str) -> Op:
@@ -521,6 +575,12 @@ def parse_op(line: str) -> Op:
             op.zinp_geom()
         elif t == "SoftmaxWithLoss":
             op.softmax_geom()
+        elif t == "Reduce":
+            op.reduce_geom()
+        elif t in ("Concat", "Split"):
+            op.concat_geom()
+        elif t in ("Dropout", "BckDropout"):
+            op.dropout_geom()
         else:
             op.sgemm_geom()
     return op

@@ -1,0 +1,77 @@
+"""Times the full-net gradient step (boda_amd/bck_pipe.py: forward, softmax loss and every gradient, one call per native function, unfused) on be=hip: NiN and
+AlexNet at 256 images, the batch of tools/bck_conv_bench.py.  Per net one JSON line with the whole-step time (median of --runs steps after --warmup), images/s
+and the share of the step each native function takes (sums of the backend's per-call durations).  No target is set: the first record is the baseline.
+
+    python tools/bck_pipe_bench.py [--nets nin,alexnet] [--batch 256] [--runs 5] [--warmup 2] [--out profiles/r09_bck_pipe_bench.txt]
+
+Every net runs in a child process of its own under a time limit (--limit seconds); the first one that fails ends the run.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def one_net(net, batch, runs, warmup):
+    import numpy as np
+    from boda_amd import conv_pipe
+    from boda_amd.bck_pipe import ConvPipeBck, add_bck_ops
+    from boda_amd.rtc import make_rtc
+    cp = {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv}[net](batch)
+    bp = add_bck_ops(cp)
+    rtc = make_rtc("(be=hip)", 0)
+    rtc.init()
+    drv = ConvPipeBck(rtc)
+    drv.init(bp)
+    rng = np.random.default_rng(0)
+    rtc.copy_nda_to_var("data", rng.uniform(-1, 1, cp.nodes["data"].sizes).astype(np.float32))
+    rtc.copy_nda_to_var("label", rng.integers(0, 1000, (batch, 1, 1)).astype(np.float32))
+    ms, share = [], {}
+    for i in range(warmup + runs):
+        drv.set_det_drop_seed(i)
+        t = drv.run_device_only()
+        if i >= warmup:
+            ms.append(t)
+            for _, fn, d in drv.per_call_ms:
+                share[fn] = share.get(fn, 0.0) + d
+    loss = float(rtc.copy_var_to_nda("loss").item())
+    tot = sum(share.values())
+    step = statistics.median(ms)
+    print(json.dumps({"net": net, "batch": batch, "calls": len(drv.calls()), "step_ms": round(step, 3), "imgs_per_s": round(batch / (step * 1e-3), 1), "loss": round(loss, 4),
+                      "share": {k: round(v / tot, 4) for k, v in sorted(share.items(), key=lambda kv: -kv[1])}}), flush=True)
+    drv.release(); rtc.close()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nets", default="nin,alexnet")
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--limit", type=int, default=240, help="seconds per net")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09_bck_pipe_bench.txt"))
+    ap.add_argument("--child", default="")
+    a = ap.parse_args(argv)
+    if a.child:
+        return one_net(a.child, a.batch, a.runs, a.warmup)
+    lines = []
+    for net in a.nets.split(","):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", net, "--batch", str(a.batch), "--runs", str(a.runs), "--warmup", str(a.warmup)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:   # nothing more is started on the GPU after a failure
+            print(f"{net}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
+            return r.returncode
+        lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
+        print(lines[-1], flush=True)
+    with open(a.out, "w") as f:
+        f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}\n" + "\n".join(lines) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main() or 0)
