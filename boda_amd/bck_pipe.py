@@ -23,7 +23,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .cnn_op import (NATIVE_ARGS, OpTune, add_bck_conv_annotations, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, pipe_func_args)
+from .cnn_op import (NATIVE_ARGS, OpTune, add_bck_conv_annotations, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos,
+                     pipe_func_args)
 from .conv_pipe import ConvPipe, PipeOp
 from .op import Dims, Nda, Op, RtErr, UnsupErr
 from .rtc import RtcArg, RtcFuncCall, RtcFuncInfo
@@ -278,12 +279,52 @@ def host_params(bp: BckPipe, seed: int = 0) -> Dict[str, np.ndarray]:
     return out
 
 
-class ConvPipeBck:
-    """The training-form step of a pipe with gradient ops over one backend (be=hip or be=cpu): forward, loss and every gradient, one call per native function."""
+RELU_GRAD_PRODUCERS = {"BckConv": 0, "Spreading": 2, "BckLRN": 0}   # gradient op type -> index among its bots of the forward op's `in`
 
-    def __init__(self, rtc, op_tune: Optional[OpTune] = None):
+
+def plan_relu_grad_folds(bp: BckPipe) -> Tuple[Dict[str, str], Dict[str, str]]:
+    """Which ReLU gradients can be taken into the call before them -> ({ZeroIfNonPos tag: tag of the gradient op that takes it}, {ZeroIfNonPos tag: why not}).
+    A ZeroIfNonPos folds exactly when it is in place on X_grad_loss, the gradient op immediately before it is a BckConv / Spreading / BckLRN whose in_grad_loss node
+    is that X_grad_loss, and that op's forward `in` node is the ZeroIfNonPos's cond X: the producer then applies the mask on its own store (zero_if_in_non_pos=1)."""
+    bck = bp.bck_ops()
+    folds: Dict[str, str] = {}
+    why: Dict[str, str] = {}
+    for i, o in enumerate(bck):
+        if o.type != "ZeroIfNonPos":
+            continue
+        gl, x = o.bots
+        prev = bck[i - 1] if i else None
+        if o.tops[0] != gl:
+            why[o.tag] = f"not in place: reads {gl}, writes {o.tops[0]}"
+        elif any(q.type == "BckDropout" and q.tops[0] == gl for q in bck):
+            # (a Dropout rewrites X in place behind the ReLU, so X is no longer the ReLU's output alone.  The reference's walk puts that BckDropout AFTER this op, right
+            # behind the producer's call; the pair is left as it is all the same: fusing across a BckDropout is a change of its own)
+            why[o.tag] = f"a BckDropout works in place on {gl} as well: {x} is rewritten by a Dropout behind the ReLU"
+        elif prev is None:
+            why[o.tag] = f"{gl} is written by a SoftmaxWithLoss, no gradient op runs before it"
+        elif prev.type not in RELU_GRAD_PRODUCERS:
+            why[o.tag] = f"the op before it is {prev.tag}, a {prev.type}" + (f": {gl} sums the partial gradients of {x}'s readers" if prev.type == "Reduce" else
+                                                                             f" between {gl}'s producer and the ReLU gradient" if prev.type == "BckDropout" else "")
+        elif prev.tops[0] != gl:
+            why[o.tag] = f"the op before it, {prev.tag}, writes {prev.tops[0]}, not {gl}"
+        elif prev.bots[RELU_GRAD_PRODUCERS[prev.type]] != x:
+            why[o.tag] = f"the op before it, {prev.tag}, has the forward input {prev.bots[RELU_GRAD_PRODUCERS[prev.type]]}, not {x}"
+        else:
+            folds[o.tag] = prev.tag
+    return folds, why
+
+
+class ConvPipeBck:
+    """The training-form step of a pipe with gradient ops over one backend (be=hip or be=cpu): forward, loss and every gradient, one call per native function.
+    fuse_relu_grad=True (opt-in): every ReLU gradient that plan_relu_grad_folds allows emits no call; the BckConv data gradient / Spreading / BckLRN before it runs with
+    zero_if_in_non_pos=1 and writes the masked gradient itself.  Every node holds the same values after a step either way.  `fused_relu_grads` says what init did:
+    {"folded": [ZeroIfNonPos tags], "unfolded": {ZeroIfNonPos tag: reason}}."""
+
+    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False):
         self.rtc = rtc
         self.op_tune = op_tune or OpTune()
+        self.fuse_relu_grad = bool(fuse_relu_grad)
+        self.fused_relu_grads: Dict[str, object] = {"folded": [], "unfolded": {}}
         self.bck_calls: List[BckCall] = []
         self.vars: List[str] = []
         self.funcs: List[str] = []
@@ -311,9 +352,13 @@ class ConvPipeBck:
                 relu_of[o.tag] = bool(first_ip and first_ip.type == "ReLU")
                 if relu_of[o.tag]:
                     fused.add(first_ip.tag)
+        folds, why = plan_relu_grad_folds(bp) if self.fuse_relu_grad else ({}, {o.tag: "fuse_relu_grad is off" for o in bp.bck_ops() if o.type == "ZeroIfNonPos"})
+        self.fused_relu_grads = {"folded": list(folds), "unfolded": why}
+        takes_relu = set(folds.values())   # the gradient ops that apply the mask of the ZeroIfNonPos behind them
+        zinp = lambda o, f: fuse_zero_if_in_non_pos(f) if o.tag in takes_relu else f
         infos: List[RtcFuncInfo] = []
         for o in ops:
-            if o.tag in fused:
+            if o.tag in fused or o.tag in folds:
                 continue
             op = grad_op_to_op(bp, o)
             t = o.type
@@ -327,20 +372,21 @@ class ConvPipeBck:
                 calls.append((add_bck_op_annotations(z, tune)[0], {"in": o.bots[0], "cond": o.bots[0], "out": o.bots[0]}))
             elif t == "BckConv":
                 fi, fb, ff = add_bck_conv_annotations(op, tune)
-                calls.append((fi, {"filts": o.bots[1], "out_grad_loss": o.bots[3], "in_grad_loss": o.tops[0]}))
+                calls.append((zinp(o, fi), dict({"filts": o.bots[1], "out_grad_loss": o.bots[3], "in_grad_loss": o.tops[0]}, **({"in": o.bots[0]} if o.tag in takes_relu else {}))))
                 calls.append((fb, {"out_grad_loss": o.bots[3], "biases_grad_loss": o.tops[2]}))
                 calls.append((ff, {"in": o.bots[0], "out_grad_loss": o.bots[3], "filts_grad_loss": o.tops[1]}))
             elif t == "Pooling":
                 self._var(o.tops[0] + "_in_yx", bp.nodes[o.tops[0]])
                 calls.append((add_bck_op_annotations(op, tune)[0], {"in": o.bots[0], "out": o.tops[0], "out_in_yx": o.tops[0] + "_in_yx"}))
             elif t == "Spreading":
-                calls.append((add_bck_op_annotations(op, tune)[0], {"out": o.bots[0], "out_grad_loss": o.bots[1], "out_in_yx": o.bots[0] + "_in_yx", "in_grad_loss": o.tops[0]}))
+                calls.append((zinp(o, add_bck_op_annotations(op, tune)[0]), dict({"out": o.bots[0], "out_grad_loss": o.bots[1], "out_in_yx": o.bots[0] + "_in_yx", "in_grad_loss": o.tops[0]},
+                                                                                 **({"in": o.bots[2]} if o.tag in takes_relu else {}))))
             elif t == "LRN":
                 self._var(o.tops[0] + "_scale_base", bp.nodes[o.tops[0]])
                 calls.append((add_bck_op_annotations(op, tune)[0], {"in": o.bots[0], "out": o.tops[0], "out_scale_base": o.tops[0] + "_scale_base"}))
             elif t == "BckLRN":
-                calls.append((add_bck_op_annotations(op, tune)[0], {"in": o.bots[0], "out": o.bots[1], "out_grad_loss": o.bots[2], "out_scale_base": o.bots[1] + "_scale_base",
-                                                                    "in_grad_loss": o.tops[0]}))
+                calls.append((zinp(o, add_bck_op_annotations(op, tune)[0]), {"in": o.bots[0], "out": o.bots[1], "out_grad_loss": o.bots[2], "out_scale_base": o.bots[1] + "_scale_base",
+                                                                             "in_grad_loss": o.tops[0]}))
             elif t == "ZeroIfNonPos":
                 calls.append((add_bck_op_annotations(op, tune)[0], {"in": o.bots[0], "cond": o.bots[1], "out": o.tops[0]}))
             elif t == "SoftmaxWithLoss":

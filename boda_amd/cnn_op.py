@@ -269,11 +269,36 @@ def add_pipe_op_annotations(op: Op, tune: OpTune) -> tuple:
     return tuple(outs)
 
 
+ZINP_FLAG = "zero_if_in_non_pos"   # uint32 of a function op: in_grad_loss[e] = in[e] > 0 ? g[e] : +0, hip_zero_if_non_pos's rule applied on the producer's store
+ZINP_FUNCS = ("hip_bconv_in", "hip_spreading", "hip_bck_lrn")   # the functions that write an in_grad_loss with the dims of their op's forward input `in`
+
+
+def has_zinp_flag(fop: Op) -> bool:
+    return fop.has(ZINP_FLAG) and fop.get_u32(ZINP_FLAG) != 0
+
+
+def fuse_zero_if_in_non_pos(fop: Op) -> Op:
+    """-> a copy of an annotated hip_bconv_in / hip_spreading / hip_bck_lrn function op with zero_if_in_non_pos=1: the function then writes
+    in_grad_loss[e] = in[e] > 0 ? g[e] : +0, g being what the unflagged function writes and `in` the op's forward input -- the ReLU gradient (hip_zero_if_non_pos
+    with cond = in) folded into the store.  hip_bconv_in and hip_spreading take `in` as one more var arg (pipe_func_args); hip_bck_lrn reads it already."""
+    fn = fop.get_func_name() if fop.has_func_name() else ""
+    if fn not in ZINP_FUNCS:
+        raise RtErr(f"fuse_zero_if_in_non_pos: {fn or fop.get_type()!r} is none of {', '.join(ZINP_FUNCS)} (the functions whose in_grad_loss has the dims of their forward input)")
+    if fop.get_dims("in") != fop.get_dims("in_grad_loss"):
+        raise RtErr(f"fuse_zero_if_in_non_pos: {fn}: in and in_grad_loss dims differ")
+    a = fop.copy()
+    a.nda_vals[ZINP_FLAG] = Nda(None, "uint32_t", (1,))
+    return a
+
+
 def pipe_func_args(fop: Op) -> tuple:
-    """The (arg, IN | OUT | REF | VAL) list of an annotated function op: NATIVE_ARGS, and for hip_reduce its ins_0 .. ins_{n-1} followed by out."""
+    """The (arg, IN | OUT | REF | VAL) list of an annotated function op: NATIVE_ARGS; for hip_reduce its ins_0 .. ins_{n-1} followed by out; for a hip_bconv_in /
+    hip_spreading with zero_if_in_non_pos=1 the var arg `in` in front of in_grad_loss."""
     fn = fop.get_func_name()
     if fn == "hip_reduce":
         return tuple((an, "IN") for an in fop.multi_names("ins")) + (("out", "OUT"),)
+    if fn in ("hip_bconv_in", "hip_spreading") and has_zinp_flag(fop):
+        return NATIVE_ARGS[fn][:-1] + (("in", "IN"),) + NATIVE_ARGS[fn][-1:]
     return NATIVE_ARGS[fn]
 
 

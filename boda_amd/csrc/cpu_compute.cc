@@ -110,7 +110,9 @@ void pool_yx(float const *in, float *out, float *out_in_yx, pool_geom_c const &g
         out_in_yx[(pl * g.OH + oy) * g.OW + ox] = (float)oyx;
       }
 }
-void spreading(float const *ogl, float const *out_in_yx, float *igl, pool_geom_c const &g) {
+// zin (spreading, bck_lrn, bconv_in; the function op's zero_if_in_non_pos=1): the forward input.  The loop is the template's; the value it forms is replaced by +0
+// where !(zin > 0) just before the store -- hip_zero_if_non_pos's select with cond = in
+void spreading(float const *ogl, float const *out_in_yx, float *igl, pool_geom_c const &g, float const *zin = nullptr) {
   float const spread_sz = (float)(g.KW * g.KH);   // the full window area, also where a border clips the window (the reference's own FIXME)
 #pragma omp parallel for schedule(static)
   for (long pl = 0; pl < g.B * g.C; ++pl)
@@ -126,7 +128,8 @@ void spreading(float const *ogl, float const *out_in_yx, float *igl, pool_geom_c
             if (g.avg) v = v + ogl[oix] / spread_sz;
             else if (in_yx == out_in_yx[oix]) v = v + ogl[oix];
           }
-        igl[(pl * g.H + y) * g.W + x] = v;
+        long const ix = (pl * g.H + y) * g.W + x;
+        igl[ix] = (zin && !(zin[ix] > 0.0f)) ? 0.0f : v;
       }
 }
 struct lrn_geom_c { long B, C, HW, LS; float alpha, beta, k; };
@@ -153,7 +156,7 @@ void lrn_sb(float const *in, float *out, float *sb, lrn_geom_c const &g) {
     }
   }
 }
-void bck_lrn(float const *in, float const *out, float const *ogl, float const *sb, float *igl, lrn_geom_c const &g) {
+void bck_lrn(float const *in, float const *out, float const *ogl, float const *sb, float *igl, lrn_geom_c const &g, bool zinp = false) {
   long const hls = g.LS / 2;
   float const coef = ((2.0f * -g.beta) * g.alpha) / (float)g.LS;
 #pragma omp parallel for schedule(static)
@@ -169,7 +172,7 @@ void bck_lrn(float const *in, float const *out, float const *ogl, float const *s
         for (long i = 0; i < g.LS; ++i) ls_sum = ls_sum + ls_buf[i];   // slot order, recomputed: not carried
         float const a = ogl[ox] * powf(sb[ox], -g.beta);
         float const b = in[ox] * ls_sum * coef;
-        igl[ox] = a + b;
+        igl[ox] = (zinp && !(in[ox] > 0.0f)) ? 0.0f : a + b;
       }
     }
   }
@@ -335,6 +338,7 @@ struct cpu_compute_t : public rtc_compute_t {
                   "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs, hip_reduce, hip_dropout, hip_concat, hip_split); '" +
                                                     (fn.empty() ? fi.func_name : fn) + "' is generated CUCL source, which needs a GPU backend");
       if (is_conv(fn)) (void)fi.op.get_u32("conv_has_relu");
+      (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
       if (bck_op_fn_t const *d = find_bck_op(fn)) {
         if (!type_ok(*d, fi.op.get_type())) rt_err(fn + ": a function of op type " + d->type + ", not " + fi.op.get_type());
         for (string const &an : bck_op_ins(*d, fi.op)) (void)fi.op.get_dims(an);
@@ -400,7 +404,7 @@ struct cpu_compute_t : public rtc_compute_t {
 
   // BckConv's gradients: the reference templates' loops, one fmaf chain per output in exactly their order (test/rtc/BckConv_in_grad_loss.cucl,
   // BckConv_filts_grad_loss.cucl, BckConv_biases_grad_loss.cucl), parallel over outputs.  g is the forward convolution's geometry.
-  static void bconv_in(float const *filts, float const *ogl, float *igl, conv_geom_c const &g) {
+  static void bconv_in(float const *filts, float const *ogl, float *igl, conv_geom_c const &g, float const *zin = nullptr) {
 #pragma omp parallel for collapse(2) schedule(static)
     for (long img = 0; img < g.B; ++img)
       for (long c = 0; c < g.C; ++c)
@@ -417,7 +421,8 @@ struct cpu_compute_t : public rtc_compute_t {
                   v = fmaf(ogl[((img * g.OC + oc) * g.OH + oy) * g.OW + ox], filts[((oc * g.C + c) * g.KH + fy) * g.KW + fx], v);
               }
             }
-            igl[((img * g.C + c) * g.H + y) * g.W + x] = v;
+            long const ix = ((img * g.C + c) * g.H + y) * g.W + x;
+            igl[ix] = (zin && !(zin[ix] > 0.0f)) ? 0.0f : v;
           }
   }
   static void bconv_filts(float const *in, float const *ogl, float *fgl, conv_geom_c const &g) {
@@ -449,7 +454,7 @@ struct cpu_compute_t : public rtc_compute_t {
       bgl[oc] = v;
     }
   }
-  void run_bck(string const &fn, map_str_rtc_arg_t const &am) {
+  void run_bck(string const &fn, op_base_t const &op, map_str_rtc_arg_t const &am) {
     string const ognm = var_of(am, "out_grad_loss");
     dims_t const og = get_var_dims(ognm); need_float(og, "out_grad_loss");
     if (og.sz() != 4) rt_err(fn + ": out_grad_loss must be img:chan:y:x");
@@ -474,7 +479,16 @@ struct cpu_compute_t : public rtc_compute_t {
     if (!g.SY || !g.SX) rt_err(fn + ": zero stride");
     if (f.dsz("out_chan") != (uint32_t)g.OC || f.dsz("in_chan") != (uint32_t)g.C || in.dsz("img") != (uint32_t)g.B) rt_err(fn + ": inconsistent filts / in / out_grad_loss dims");
     if ((g.H + 2 * g.PY - g.KH) / g.SY + 1 != g.OH || (g.W + 2 * g.PX - g.KW) / g.SX + 1 != g.OW) rt_err(fn + ": out_grad_loss dims do not match in / filts / stride / in_pad");
-    if (din) bconv_in((float const *)must_find(vis, fnm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, inm).buf.get(), g);
+    float const *zin = nullptr;
+    if (din && op_zinp_flag(op)) {   // the forward input: the op's in dims (the image count the other vars'), and not the var this call writes
+      string const znm = var_of(am, "in"); dims_t const zd = get_var_dims(znm); need_float(zd, "in");
+      dims_t want = op.get_dims("in");
+      if (want.sz() == 4 && zd.sz() == 4) { want[0].sz = (uint32_t)g.B; want.calc_strides(); }
+      if (!(zd == want) || !(zd == in)) rt_err(fn + ": arg 'in' has dims " + zd.pretty_str() + ", the op says " + op.get_dims("in").pretty_str());
+      if (znm == inm) rt_err(fn + ": zero_if_in_non_pos=1: 'in' and 'in_grad_loss' are the same var '" + znm + "'");
+      zin = (float const *)must_find(vis, znm).buf.get();
+    }
+    if (din) bconv_in((float const *)must_find(vis, fnm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, inm).buf.get(), g, zin);
     else bconv_filts((float const *)must_find(vis, inm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, fnm).buf.get(), g);
   }
 
@@ -507,6 +521,12 @@ struct cpu_compute_t : public rtc_compute_t {
     std::vector<string> const in_ans = bck_op_ins(d, op);
     for (size_t i = 0; i < in_ans.size(); ++i) in[i] = var_ptr(in_ans[i].c_str());
     for (size_t i = 0; i < d.outs.size(); ++i) out[i] = var_ptr(d.outs[i]);
+    bool const zinp = op_zinp_flag(op);
+    float const *zin = nullptr;
+    if (zinp) {   // the condition is the forward input `in` (hip_bck_lrn's first arg; one more var arg of hip_spreading), never the var the call writes
+      zin = var_ptr("in");
+      if (var_of(am, "in") == var_of(am, "in_grad_loss")) rt_err(fn + ": zero_if_in_non_pos=1: 'in' and 'in_grad_loss' are the same var '" + var_of(am, "in") + "'");
+    }
     if (d.refs) {
       dims_t const &i4 = op.get_dims("in"), &o4 = op.get_dims("out"), &ks = op.get_dims("kern_sz"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
       if (i4.sz() != 4 || o4.sz() != 4) rt_err(fn + ": in / out must be img:chan:y:x");
@@ -519,7 +539,7 @@ struct cpu_compute_t : public rtc_compute_t {
       if (fn == "hip_pool_yx") {
         if (!op.get_u32("emit_out_in_yx") && !g.avg) unsup_err(fn + ": a Pooling with emit_out_in_yx=0 belongs to the forward pipe");
         pool_yx(in[0], out[0], out[1], g);
-      } else spreading(in[1], in[2], out[0], g);
+      } else spreading(in[1], in[2], out[0], g, zin);
     } else if (fn == "hip_lrn_sb" || fn == "hip_bck_lrn") {
       dims_t const &i4 = op.get_dims("in");
       if (i4.sz() != 4) rt_err(fn + ": in must be img:chan:y:x");
@@ -528,7 +548,7 @@ struct cpu_compute_t : public rtc_compute_t {
       if (fn == "hip_lrn_sb") {
         if (!op.get_u32("emit_out_scale_base")) unsup_err(fn + ": an LRN with emit_out_scale_base=0 belongs to the forward pipe");
         lrn_sb(in[0], out[0], out[1], g);
-      } else bck_lrn(in[0], in[1], in[2], in[3], out[0], g);
+      } else bck_lrn(in[0], in[1], in[2], in[3], out[0], g, zinp);
     } else if (fn == "hip_zero_if_non_pos") {
       zero_if_non_pos(in[0], in[1], out[0], (long)get_var_dims(var_of(am, "in")).dims_prod());
     } else if (fn == "hip_reduce") {
@@ -570,7 +590,7 @@ struct cpu_compute_t : public rtc_compute_t {
     map_str_rtc_arg_t const &am = rfc.arg_map;
     double const tb = now_ms();
     if (bck_op_fn_t const *bd = find_bck_op(fn)) run_bck_op(*bd, fi.op, am);
-    else if (is_bck(fn)) run_bck(fn, am);
+    else if (is_bck(fn)) run_bck(fn, fi.op, am);
     else if (is_sgemm(fn)) {
       string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");
       dims_t const a = get_var_dims(an), b = get_var_dims(bn), c = get_var_dims(cn);

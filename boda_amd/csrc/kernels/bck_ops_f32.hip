@@ -16,6 +16,8 @@
 //   * out_x OUTER, out_y inner, a sequential fp32 sum from +0 (a pel no window holds is exactly +0)
 //   * max (AVG=0): add out_grad_loss where out_in_yx == y*W + x (compared as floats);  average (AVG=1): add out_grad_loss / (KH*KW) -- the FULL window area
 //     even where the window is clipped by a border, as the reference does (its own FIXME says so); a division per term, not a multiplication by 1/area
+//   * ZINP=1 (the function op's zero_if_in_non_pos): the ReLU gradient that follows this call in a gradient pipe, folded into the store -- in_grad_loss = in > 0 ? v : +0
+//     with `in` (p3) the pooling's forward input at the written pel: OP 5's rule with cond = in, a select on the finished sum (a +0, -0 or NaN condition gives +0)
 // OP 3  bodahip_lrn_sb  (test/rtc/lrn.cucl, the caffe-matching path, emit_out_scale_base=1)   in -> out, out_scale_base
 //   * scale_base = k + ls_sum * (alpha / local_size), the quotient formed once in fp32 on the host
 //   * ls_sum is CARRIED along the channels of a pel as (ls_sum + new*new) - old*old, in that order; its bits depend on the whole history from channel 0, so a
@@ -26,6 +28,7 @@
 //   * ls_sum is RECOMPUTED for every channel from +0 over the ring in SLOT order i = 0 .. local_size-1 (not in channel order, and not carried)
 //   * in_grad_loss = out_grad_loss * powf(scale_base, -beta) + in * ls_sum * coef,  coef = ((2 * -beta) * alpha) / local_size formed once in fp32 on the host
 //   * a thread owns CB channels of a pel; its walk starts at a multiple of local_size at or below c0 - local_size/2, so every ring slot is a compile-time index
+//   * ZINP=1: in_grad_loss = in > 0 ? (the value above) : +0 -- the same fold as OP 2's, on the `in` value the formula has loaded already
 // OP 5  bodahip_zero_if_non_pos  (test/rtc/ZeroIfNonPos.cucl)   out = cond > 0 ? in : 0.0f -- the code's `>` (the reference's comment says >=); +0, -0 and NaN
 //   conditions give +0.  float4 over the first n4 quads, scalars over the tail.
 // OP 6  bodahip_softmax  (test/rtc/softmax.cucl, 1 x 1 planes)   in -> prob
@@ -49,13 +52,16 @@
 // OP 9 .. 12 take float4 over the first n4 quads and scalars over the tail, like OP 5; the host sets n4 = 0 unless every pointer (11, 12: every per-image run) is
 // 16-byte aligned.  Quads never straddle a run: 11 / 12 use them only when run, wide and off are multiples of 4.
 //
-// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN.  Host side: plan_bck_op (native_plan.cc), native_kernels.cc.
+// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN | 2, 4: [ZINP].  Host side: plan_bck_op (native_plan.cc), native_kernels.cc.
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
 
 #pragma clang fp contract(off) reassociate(off)
+#ifndef ZINP
+#define ZINP 0
+#endif
 
 struct bck_ops_args_t {   // must match native_internal.h
   float const *p0; float const *p1; float const *p2; float const *p3;   // inputs, in the function's arg order
@@ -118,6 +124,9 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
   int const oxe = ((x + PX) / SX + 1 < OW) ? (x + PX) / SX + 1 : OW, oye = ((y + PY) / SY + 1 < OH) ? (y + PY) / SY + 1 : OH;
   float const spread_sz = (float)(KW * KH);
   float const in_yx = (float)(y * W + x);
+#if ZINP
+  float const zc = p.p3[id];   // (loaded ahead of the gather; this thread owns the pel)
+#endif
   float v = 0.0f;
 #pragma unroll
   for (int i = 0; i < kMaxX; ++i) {
@@ -135,6 +144,9 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
       }
     }
   }
+#if ZINP
+  v = zc > 0.0f ? v : 0.0f;
+#endif
   p.o0[id] = v;
 }
 
@@ -200,9 +212,14 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
 #pragma unroll
       for (int i = 0; i < LS; ++i) ls_sum = ls_sum + ring[i];
       long const ox = base + (long)c_out * p.HW;
+      float const in_v = p.p0[ox];
       float const a = p.p2[ox] * powf(p.p3[ox], -p.f1);
-      float const b = p.p0[ox] * ls_sum * p.f3;
+      float const b = in_v * ls_sum * p.f3;
+#if ZINP
+      p.o0[ox] = in_v > 0.0f ? a + b : 0.0f;
+#else
       p.o0[ox] = a + b;
+#endif
     }
   }
 }

@@ -37,6 +37,7 @@ struct bconv_args_t {   // must match native_internal.h
   int B, C, H, W, OC, OH, OW;
   int tiles_i, tiles_j, ksl, kt_per;
   unsigned a_bytes, b_bytes, d_bytes;
+  float const *zin;                           // (the data gradient's: kernels/bconv_in_f32.hip -DZINP=1)
 };
 
 #if BIAS_ONLY

@@ -14,10 +14,18 @@
 // (borders, taps outside the kernel) are fma(0, w, acc) or fma(g, 0, acc), which equal acc for FINITE data: the accumulator starts at +0 and never becomes -0.
 // An inf / nan in filts or out_grad_loss would poison padded terms the reference never forms (the same caveat as the forward kernels' K tail).
 //
-// -D parameters: KNAME BI BJ BK WI WJ MINW KH KW SY SX PY PX.  Host side: plan_bconv_in (native_plan.cc), native_kernels_t::bconv_in (native_kernels.cc).
+// -DZINP=1 (the function op's zero_if_in_non_pos): the ReLU gradient that follows this launch in a gradient pipe, folded into the store --
+//   in_grad_loss[e] = in[e] > 0 ? g[e] : +0,   g[e] the value above, `in` (p.zin) the convolution's forward input, which has in_grad_loss's dims:
+// hip_zero_if_non_pos's rule (kernels/bck_ops_f32.hip OP 5) with cond = in.  A select on the finished chain, never a product: a +0, -0 or NaN condition gives +0
+// whatever g is.  The MFMA chains are the same; positions no term reaches (1x1 at stride 2) are written +0 either way.
+//
+// -D parameters: KNAME BI BJ BK WI WJ MINW KH KW SY SX PY PX [ZINP].  Host side: plan_bconv_in (native_plan.cc), native_kernels_t::bconv_in (native_kernels.cc).
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#endif
+#ifndef ZINP
+#define ZINP 0
 #endif
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -32,6 +40,7 @@ struct bconv_args_t {   // must match native_internal.h
   int B, C, H, W, OC, OH, OW;
   int tiles_i, tiles_j, ksl, kt_per;
   unsigned a_bytes, b_bytes, d_bytes;
+  float const *zin;   // ZINP: the forward input (in_grad_loss's dims)
 };
 
 constexpr int kTY = (KH + SY - 1) / SY, kTX = (KW + SX - 1) / SX, kTT = kTY * kTX;
@@ -137,12 +146,32 @@ extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(bconv_arg
     if (j >= P) continue;
     int const img = j / nyx, rem = j - img * nyx, ty = rem / nx, tx = rem - ty * nx;
     long const obase = ((long)img * p.C * p.H + (ry + SY * ty)) * p.W + (rx + SX * tx);
+#if ZINP
+    // the condition values of this column of blocks, all loaded before its first store (a load issued between stores waits for every earlier store): the same
+    // elements the stores below write, so the same bounds and the same coalescing.  A channel past the tensor reads the last channel instead (never stored): an
+    // unconditional load, so the loads issue back to back -- a load under its own branch is waited for before the next one is issued
+    float zc[kTI][16];
 #pragma unroll
     for (int a = 0; a < kTI; ++a)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int const c = i0 + wi * (kTI * 32) + a * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+        zc[a][r] = p.zin[obase + (long)(c < p.C ? c : p.C - 1) * p.H * p.W];
+      }
+    // vmcnt(0) (gfx9 encoding; expcnt / lgkmcnt left at their maxima): every condition value has arrived before the first store.  Left to the compiler, the wait for each
+    // value sits in front of its own store, and a vmcnt wait between stores waits for the earlier stores as well
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+#endif
+#pragma unroll
+    for (int a = 0; a < kTI; ++a)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int const c = i0 + wi * (kTI * 32) + a * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+#if ZINP
+        if (c < p.C) p.d[obase + (long)c * p.H * p.W] = zc[a][r] > 0.0f ? acc[a][b][r] : 0.0f;
+#else
         if (c < p.C) p.d[obase + (long)c * p.H * p.W] = acc[a][b][r];
+#endif
       }
   }
 }

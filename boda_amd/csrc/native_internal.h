@@ -54,6 +54,7 @@ struct bconv_args_t { // must match kernels/bconv_in_f32.hip, kernels/bconv_filt
   int B, C, H, W, OC, OH, OW;
   int tiles_i, tiles_j, ksl, kt_per;
   unsigned a_bytes, b_bytes, d_bytes;
+  float const *zin;   // bconv_in -DZINP=1: the forward input, the condition of the select on the store
 };
 
 struct bck_ops_args_t { // must match kernels/bck_ops_f32.hip
@@ -99,7 +100,7 @@ bool rows_auto(conv_geom_t const &g, int num_cus, string const &tile);
 bool apply_post_ops(op_base_t const &op, conv_geom_t &g, post_ops_t &post, char const *what);
 bool plan_ipconv_dma(conv_geom_t const &g, int num_cus, plan_t &p);
 plan_t plan_conv(conv_geom_t const &g, int num_cus, string const &tile, bool bf16 = false, string const &k1s = string(), bool allow_splitk = true, bool exact = true);
-plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile);       // BckConv data gradient (kernels/bconv_in_f32.hip)
+plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile, bool zinp = false);   // (zinp: -DZINP=1) BckConv data gradient (kernels/bconv_in_f32.hip)
 plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile);    // BckConv filter gradient, in-launch K slices (kernels/bconv_filts_f32.hip)
 plan_t plan_bconv_biases();                                                          // BckConv bias gradient (kernels/bconv_filts_f32.hip -DBIAS_ONLY)
 long bconv_in_tiles(conv_geom_t const &g, int BJ);                                   // pel tiles over all SY x SX phases (the kernel's walk)

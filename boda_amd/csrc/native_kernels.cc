@@ -43,6 +43,7 @@ void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
   if (fn == "hip_conv" || fn == "cudnn_conv" || fn == "hip_conv_bf16" || fn == "hip_conv_winograd" || fn == "hip_conv_nhwc" || fn == "hip_conv_nhwc_grp" || fn == "hip_conv_nhwc_multi" || fn == "hip_conv_nhwc_set") { (void)fi.op.get_u32("conv_has_relu"); return; } // required, as src/culibs-wrap.cc:198
   if (fn == "hip_conv_k1_chain") { (void)fi.op.get_u32("conv_has_relu"); (void)fi.op.get_u32("conv_has_relu2"); return; }
   if (fn == "hip_conv_filts_kmajor") return;
+  (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
   if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases") {   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     return;
@@ -711,11 +712,11 @@ static bconv_args_t bconv_args(conv_geom_t const &g) {
   a.B = g.B; a.C = g.C; a.H = g.H; a.W = g.W; a.OC = g.OC; a.OH = g.OH; a.OW = g.OW;
   return a;
 }
-void native_kernels_t::bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g) {
-  plan_t const p = plan_bconv_in(g, host->nh_num_cus(), tune_of(impl, "conv_tile"));
+void native_kernels_t::bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g, float const *zin) {
+  plan_t const p = plan_bconv_in(g, host->nh_num_cus(), tune_of(impl, "conv_tile"), zin != nullptr);
   kernel_t &k = get_kernel(impl, host, p);
   bconv_args_t a = bconv_args(g);
-  a.a = filts; a.b = out_grad; a.d = in_grad;
+  a.a = filts; a.b = out_grad; a.d = in_grad; a.zin = zin;
   a.a_bytes = (unsigned)(4ull * g.OC * g.C * g.KH * g.KW); a.b_bytes = (unsigned)(4ull * g.B * g.OC * g.OH * g.OW); a.d_bytes = (unsigned)(4ull * g.B * g.C * g.H * g.W);
   a.tiles_i = (g.C + p.cfg.BI - 1) / p.cfg.BI; a.tiles_j = (int)bconv_in_tiles(g, p.cfg.BJ); a.ksl = 1;
   uint32_t const grid = (uint32_t)a.tiles_i * (uint32_t)a.tiles_j;
@@ -724,7 +725,7 @@ void native_kernels_t::bconv_in(float const *filts, float const *out_grad, float
   int const TY = (g.KH + g.SY - 1) / g.SY, TX = (g.KW + g.SX - 1) / g.SX;
   last_launch.kernel = p.kname; last_launch.cfg = p.cfg; last_launch.grid = grid; last_launch.block = p.cfg.threads();
   last_launch.flops = 2.0 * g.B * g.H * g.W * g.C * ((double)g.OC * TY * TX);   // (the phase GEMMs as run: M = img x pels, N = in_chan, K = out_chan x taps)
-  last_launch.algo_bytes = (double)a.a_bytes + a.b_bytes + a.d_bytes;
+  last_launch.algo_bytes = (double)a.a_bytes + a.b_bytes + a.d_bytes * (zin ? 2.0 : 1.0);
 }
 void native_kernels_t::bconv_filts(float const *in, float const *out_grad, float *filts_grad, conv_geom_t const &g) {
   plan_t const p = plan_bconv_filts(g, host->nh_num_cus(), tune_of(impl, "conv_tile"));

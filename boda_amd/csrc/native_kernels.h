@@ -88,7 +88,8 @@ struct post_ops_t { int PKH = 0, PKW = 0, PSY = 1, PSX = 1, PPY = 0, PPX = 0, PO
 // plane; n = elements (zero_if_non_pos, reduce, dropout).  reduce: nin inputs.  dropout: ratio from the op, seed from the
 // call.  concat / split: B images of the narrow tensor's C channels (planes H x W) at channels [cix, cix + C) of the wide tensor's CT
 struct bck_op_geom_t { int op = 0; long B = 0; int C = 0, H = 1, W = 1, OH = 1, OW = 1, KH = 1, KW = 1, SY = 1, SX = 1, PY = 0, PX = 0, avg = 0, LS = 1; float alpha = 0.f, beta = 0.f, k = 0.f; long n = 0;
-  int nin = 0; float ratio = 0.f; uint32_t seed = 0; int CT = 0, cix = 0; };
+  int nin = 0; float ratio = 0.f; uint32_t seed = 0; int CT = 0, cix = 0;
+  int zinp = 0; };   // spreading, bck_lrn: 1 = in_grad_loss = in > 0 ? value : +0 (the op's zero_if_in_non_pos; spreading then takes `in` as its fourth input)
 
 struct launch_info_t { string kernel; tile_cfg_t cfg; uint32_t grid = 0, block = 0; double flops = 0, algo_bytes = 0; };
 
@@ -123,7 +124,8 @@ struct native_kernels_t {
                      bool relu2, int out_ctot, int out_coff);
   // BckConv gradients (fp32, reference layouts; g = the forward convolution's geometry, out_grad_loss has g.OH x g.OW planes): kernels/bconv_in_f32.hip (data gradient,
   // bit-identical to the reference's chain), kernels/bconv_filts_f32.hip (filter gradient with deterministic in-launch K slices; bias gradient)
-  void bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g);
+  // zin (the op's zero_if_in_non_pos=1): the forward input; in_grad = zin > 0 ? gradient : +0
+  void bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g, float const *zin = nullptr);
   void bconv_filts(float const *in, float const *out_grad, float *filts_grad, conv_geom_t const &g);
   void bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g);
   // the non-conv ops of the gradient pipe: ins / outs in the function's arg order (up to eight / two raw device pointers)

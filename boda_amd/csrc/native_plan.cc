@@ -1169,7 +1169,7 @@ long bconv_in_tiles(conv_geom_t const &g, int BJ) {
     }
   return n;
 }
-plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile) {
+plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile, bool zinp) {
   bconv_check_geom(g, "hip_bconv_in");
   plan_t p; p.bconv_in = true; p.kname = "bodahip_bconv_in";
   if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_in: bad tile '" + tile + "'"); }
@@ -1180,6 +1180,7 @@ plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile) {
   }
   check_bconv_cfg(p.cfg, false);
   p.defs = bconv_geom_defs(g, p.cfg);
+  if (zinp) p.defs.push_back("-DZINP=1");   // (the tile does not depend on it: the flagged launch is the unflagged one with a select on its stores)
   return p;
 }
 plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile) {
@@ -1243,6 +1244,7 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
   auto D = [&](char const *n, long v) { r.p.defs.push_back(string("-D") + n + "=" + std::to_string(v)); };
   auto lim = [&](double elems) { if (4.0 * elems >= 2147483648.0) unsup_err(what + ": tensors of 2 GiB or more (32-bit element offsets)"); };
   if (g.B < 0 || g.C < 0) rt_err(what + ": negative dims");
+  if (g.zinp && g.op != 2 && g.op != 4) rt_err(what + ": zero_if_in_non_pos=1 is taken by hip_spreading and hip_bck_lrn only");
   double const in_e = (double)g.B * g.C * g.H * g.W, out_e = (double)g.B * g.C * g.OH * g.OW;
   if (g.op == 1 || g.op == 2) {
     if (g.KH < 1 || g.KW < 1 || g.SY < 1 || g.SX < 1 || g.PY < 0 || g.PX < 0 || g.H < 1 || g.W < 1 || g.OH < 1 || g.OW < 1) rt_err(what + ": zero kern_sz / stride / plane");
@@ -1253,8 +1255,9 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
     lim(in_e); lim(out_e);
     D("H", g.H); D("W", g.W); D("OH", g.OH); D("OW", g.OW); D("KH", g.KH); D("KW", g.KW); D("SY", g.SY); D("SX", g.SX); D("PY", g.PY); D("PX", g.PX);
     if (g.op == 2 || g.avg) D("AVG", g.avg ? 1 : 0);   // (hip_pool_yx: AVG=1 is the average pooling of the gradient pipe, out_in_yx all -1)
+    if (g.zinp) D("ZINP", 1);
     r.threads = (long)((g.op == 1) ? out_e : in_e);
-    r.algo_bytes = 4.0 * ((g.op == 1) ? (in_e + 2 * out_e) : (in_e + out_e * (g.avg ? 1 : 2)));
+    r.algo_bytes = 4.0 * ((g.op == 1) ? (in_e + 2 * out_e) : (in_e * (g.zinp ? 2 : 1) + out_e * (g.avg ? 1 : 2)));
   } else if (g.op == 3 || g.op == 4) {
     if (g.LS < 1 || g.LS % 2 == 0) unsup_err(what + ": local_size=" + std::to_string(g.LS) + ": only odd windows (an even local_size has no centre channel)");
     if (g.LS > 15) unsup_err(what + ": local_size of at most 15 (the window lives in registers)");
@@ -1266,6 +1269,7 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
     r.CB = (int)std::max<long>(1, (g.C + ncb - 1) / ncb);
     if (g.op == 4) r.CB = std::min(r.CB, 32);   // (its walk is fully unrolled)
     D("LS", g.LS); D("CB", r.CB);
+    if (g.zinp) D("ZINP", 1);
     r.threads = g.B * (long)g.H * g.W * ((g.C + r.CB - 1) / r.CB);
     r.algo_bytes = 4.0 * in_e * ((g.op == 3) ? 3 : 5);
   } else if (g.op == 5) {

@@ -106,6 +106,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
   auto const ht = op.str_vals.find("hip_tile");
   string const tile = (tile_arg.empty() && ht != op.str_vals.end()) ? ht->second : tile_arg;
   plan_t p; string log, s2d;
+  (void)op_zinp_flag(op);   // (refuses the flag on a function that cannot take it)
   bool const bf16 = op.has_func_name() && (op.get_func_name() == "hip_sgemm_bf16" || op.get_func_name() == "hip_conv_bf16");
   if (t == "sgemm") {
     dims_t const &a = op.get_dims("a"), &b = op.get_dims("b");
@@ -207,13 +208,13 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     string const fn = op.has_func_name() ? op.get_func_name() : string();
     if (!fn.empty() && fn != "hip_bconv_in" && fn != "hip_bconv_filts" && fn != "hip_bconv_biases") rt_err("prebuild: BckConv function '" + fn + "' has no native kernel");
     std::vector<plan_t> ps;
-    if (fn.empty() || fn == "hip_bconv_in") ps.push_back(plan_bconv_in(g, num_cus, tile));
+    if (fn.empty() || fn == "hip_bconv_in") ps.push_back(plan_bconv_in(g, num_cus, tile, op_zinp_flag(op)));
     if (fn.empty() || fn == "hip_bconv_biases") ps.push_back(plan_bconv_biases());
     if (fn.empty() || fn == "hip_bconv_filts") ps.push_back(plan_bconv_filts(g, num_cus, tile));
     string desc; size_t bytes = 0;
     for (plan_t const &q : ps) {
       desc += (desc.empty() ? "" : " | ") + q.kname + (q.defs.size() > 1 ? " " + q.cfg.str() : string());
-      if (q.bconv_in) desc += " grid=" + std::to_string((long)((g.C + q.cfg.BI - 1) / q.cfg.BI) * bconv_in_tiles(g, q.cfg.BJ));
+      if (q.bconv_in) desc += " grid=" + std::to_string((long)((g.C + q.cfg.BI - 1) / q.cfg.BI) * bconv_in_tiles(g, q.cfg.BJ)) + (q.defs.back() == "-DZINP=1" ? " -DZINP=1" : "");
       if (q.kname == "bodahip_bconv_filts") desc += " ksl=" + std::to_string(q.cfg.SPLITK);
       if (!arch.empty()) bytes += compile_plan(q, arch, &log).size();
     }
@@ -229,7 +230,8 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     string desc; size_t bytes = 0;
     if (!op.has_func_name() && (t == "Concat" || t == "Split")) unsup_err("prebuild: a bare " + t + " is one call per " + (t == "Concat" ? "input" : "output") + ": annotate it (cnn_op.add_pipe_op_annotations) and pass the function ops");
     for (bck_op_desc_t const *d : ds) {
-      bck_plan_t const bp = plan_bck_op(bck_op_geom_of_op(op, *d), num_cus);
+      bck_op_geom_t bg = bck_op_geom_of_op(op, *d); bg.zinp = op_zinp_flag(op) ? 1 : 0;
+      bck_plan_t const bp = plan_bck_op(bg, num_cus);
       desc += (desc.empty() ? "" : " | ") + bck_plan_desc(bp);
       if (!arch.empty()) bytes += compile_plan(bp.p, arch, &log).size();
     }
@@ -298,6 +300,7 @@ struct exact_override_t {
 void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &am) {
   string const &fn = fi.op.get_func_name();
   exact_override_t const xov(impl, fi.op);
+  bool const zinp = op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
   bool const bf16 = (fn == "hip_sgemm_bf16" || fn == "hip_conv_bf16");
   if (fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "hip_sgemm_bf16") {
     string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");
@@ -593,7 +596,13 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     if (fn == "hip_bconv_in") {
       string const f = var_dims("filts"), igl = var_dims("in_grad_loss");
       if (!(fi.op.get_dims("in_grad_loss") == fi.op.get_dims("in"))) rt_err(fn + ": in_grad_loss must have the dims of in");
-      bconv_in((float const *)host->nh_var_ptr(f), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(igl), g);
+      float const *zin = nullptr;
+      if (zinp) {   // the forward input: the op's in dims (the image count the other vars'), and not the var this call writes
+        string const in = var_dims("in");
+        if (in == igl) rt_err(fn + ": zero_if_in_non_pos=1: 'in' and 'in_grad_loss' are the same var '" + in + "'");
+        zin = (float const *)host->nh_var_ptr(in);
+      }
+      bconv_in((float const *)host->nh_var_ptr(f), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(igl), g, zin);
     } else if (fn == "hip_bconv_filts") {
       string const in = var_dims("in"), fgl = var_dims("filts_grad_loss");
       if (!(fi.op.get_dims("filts_grad_loss") == fi.op.get_dims("filts"))) rt_err(fn + ": filts_grad_loss must have the dims of filts");
@@ -630,6 +639,11 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     std::vector<string> const in_ans = bck_op_ins(*d, fi.op);
     for (size_t i = 0; i < in_ans.size(); ++i) ins[i] = (float const *)var_ptr(in_ans[i].c_str());
     for (size_t i = 0; i < d->outs.size(); ++i) outs[i] = (float *)var_ptr(d->outs[i]);
+    if (zinp) {   // the condition is the forward input `in`: hip_bck_lrn's first arg; hip_spreading takes it as a fourth input.  Never the var the call writes
+      if (g.op == 2) ins[3] = (float const *)var_ptr("in");
+      if (var_of(am, "in") == var_of(am, "in_grad_loss")) rt_err(fn + ": zero_if_in_non_pos=1: 'in' and 'in_grad_loss' are the same var '" + var_of(am, "in") + "'");
+      g.zinp = 1;
+    }
     if (g.op == 10) {   // the seed is a by-value uint32 of the CALL: a new seed is no new function
       auto si = am.find("det_drop_seed");
       if (si == am.end() || !si->second.is_valid() || si->second.is_var() || !si->second.v->rp_elems() || si->second.v->dims.tn != "uint32_t" || si->second.v->dims.sz() != 0)

@@ -127,6 +127,17 @@ struct op_base_t {
   void set_func_name(string const &f) { must_insert(str_vals, "func_name", f); }
 };
 typedef std::shared_ptr<op_base_t> p_op_base_t;
+// zero_if_in_non_pos, a uint32 of a function op (absent: 0).  1: the function writes in_grad_loss[e] = in[e] > 0 ? g[e] : +0, g what it writes without the flag and `in` the
+// op's forward input -- hip_zero_if_non_pos's rule on the producer's store.  Only the three functions whose in_grad_loss has the dims of `in` take it; hip_bconv_in and
+// hip_spreading then take `in` as one more var arg, hip_bck_lrn reads it already
+inline bool op_zinp_flag(op_base_t const &op) {
+  if (!op.has("zero_if_in_non_pos") || !op.get_u32("zero_if_in_non_pos")) return false;
+  string const fn = op.has_func_name() ? op.get_func_name() : string();
+  if (fn != "hip_bconv_in" && fn != "hip_spreading" && fn != "hip_bck_lrn")
+    rt_err("zero_if_in_non_pos=1 on '" + (fn.empty() ? op.get_type() : fn) + "': only hip_bconv_in, hip_spreading and hip_bck_lrn write an in_grad_loss with the dims of their forward input in");
+  if (!(op.get_dims("in") == op.get_dims("in_grad_loss"))) rt_err(fn + ": zero_if_in_non_pos=1 needs in and in_grad_loss of the same dims");
+  return true;
+}
 
 // ---- rtc layer ----------------------------------------------------------------------------------------------------
 struct rtc_compile_opts_t {

@@ -3,6 +3,12 @@ AlexNet at 256 images, the batch of tools/bck_conv_bench.py.  Per net one JSON l
 and the share of the step each native function takes (sums of the backend's per-call durations).  No target is set: the first record is the baseline.
 
     python tools/bck_pipe_bench.py [--nets nin,alexnet] [--batch 256] [--runs 5] [--warmup 2] [--out profiles/r09_bck_pipe_bench.txt]
+    python tools/bck_pipe_bench.py --fuse-relu-grad [--repeats 3] [--out profiles/r09_bck_fuse_ab.txt]
+
+--fuse-relu-grad: the same step both ways in ONE process -- ConvPipeBck() and ConvPipeBck(fuse_relu_grad=True), each on a backend instance of its own with the same
+params and inputs -- after the usual warm-up, in --repeats alternating blocks of --runs steps.  Per net two JSON lines ("way": "unfused" / "fused": step ms as the median
+over all blocks, the medians of the single blocks (their spread is the run-to-run spread a difference has to beat), images/s, the call count, the per-function share)
+and a third with the launches removed and the fused / unfused ratio.  The comparison is between the two ways of one run, never against a recorded figure.
 
 Every net runs in a child process of its own under a time limit (--limit seconds); the first one that fails ends the run.
 """
@@ -15,6 +21,52 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def fuse_ab(net, batch, runs, warmup, repeats):
+    import numpy as np
+    from boda_amd import conv_pipe
+    from boda_amd.bck_pipe import ConvPipeBck, add_bck_ops, host_params
+    from boda_amd.rtc import make_rtc
+    cp = {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv}[net](batch)
+    bp = add_bck_ops(cp)
+    params = host_params(bp, 5)
+    rng = np.random.default_rng(0)
+    data = rng.uniform(-1, 1, cp.nodes["data"].sizes).astype(np.float32)
+    label = rng.integers(0, 1000, (batch, 1, 1)).astype(np.float32)
+    ways = {}
+    for way, fuse in (("unfused", False), ("fused", True)):
+        rtc = make_rtc("(be=hip)", 0)
+        rtc.init()
+        drv = ConvPipeBck(rtc, fuse_relu_grad=fuse)
+        drv.init(bp, params)
+        rtc.copy_nda_to_var("data", data); rtc.copy_nda_to_var("label", label)
+        ways[way] = {"rtc": rtc, "drv": drv, "blocks": [], "ms": [], "share": {}}
+    for w in ways.values():
+        for i in range(warmup):
+            w["drv"].set_det_drop_seed(i); w["drv"].run_device_only()
+    for rep in range(repeats):
+        for w in ways.values():
+            ms = []
+            for i in range(runs):
+                w["drv"].set_det_drop_seed(warmup + rep * runs + i)
+                ms.append(w["drv"].run_device_only())
+                for _, fn, d in w["drv"].per_call_ms:
+                    w["share"][fn] = w["share"].get(fn, 0.0) + d
+            w["ms"] += ms; w["blocks"].append(round(statistics.median(ms), 3))
+    loss = {k: float(w["rtc"].copy_var_to_nda("loss").item()) for k, w in ways.items()}
+    for way, w in ways.items():
+        tot = sum(w["share"].values()); step = statistics.median(w["ms"])
+        print(json.dumps({"net": net, "batch": batch, "way": way, "calls": len(w["drv"].calls()), "step_ms": round(step, 3), "block_medians_ms": w["blocks"],
+                          "imgs_per_s": round(batch / (step * 1e-3), 1), "loss": round(loss[way], 4),
+                          "share": {k: round(v / tot, 4) for k, v in sorted(w["share"].items(), key=lambda kv: -kv[1])},
+                          "ms_per_step": {k: round(v / len(w["ms"]), 3) for k, v in sorted(w["share"].items(), key=lambda kv: -kv[1])}}), flush=True)
+    u, f = ways["unfused"], ways["fused"]
+    print(json.dumps({"net": net, "launches_removed": len(u["drv"].calls()) - len(f["drv"].calls()), "folded": f["drv"].fused_relu_grads["folded"],
+                      "unfolded": sorted(f["drv"].fused_relu_grads["unfolded"]), "fused_over_unfused": round(statistics.median(f["ms"]) / statistics.median(u["ms"]), 4),
+                      "same_loss_bits": loss["unfused"] == loss["fused"]}), flush=True)
+    for w in ways.values():
+        w["drv"].release(); w["rtc"].close()
 
 
 def one_net(net, batch, runs, warmup):
@@ -54,22 +106,27 @@ def main(argv=None):
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--limit", type=int, default=240, help="seconds per net")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09_bck_pipe_bench.txt"))
+    ap.add_argument("--out", default="")
+    ap.add_argument("--fuse-relu-grad", action="store_true", help="A/B: the step with and without the ReLU gradients folded into their producers, in one process")
+    ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad: alternating blocks of --runs steps per way")
     ap.add_argument("--child", default="")
     a = ap.parse_args(argv)
+    a.out = a.out or os.path.join(ROOT, "profiles", "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r09_bck_pipe_bench.txt")
     if a.child:
-        return one_net(a.child, a.batch, a.runs, a.warmup)
+        return fuse_ab(a.child, a.batch, a.runs, a.warmup, a.repeats) if a.fuse_relu_grad else one_net(a.child, a.batch, a.runs, a.warmup)
     lines = []
     for net in a.nets.split(","):
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", net, "--batch", str(a.batch), "--runs", str(a.runs), "--warmup", str(a.warmup)]
+        cmd += ["--fuse-relu-grad", "--repeats", str(a.repeats)] if a.fuse_relu_grad else []
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:   # nothing more is started on the GPU after a failure
             print(f"{net}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
             return r.returncode
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
-        print(lines[-1], flush=True)
+        print("\n".join(lines[-3:] if a.fuse_relu_grad else lines[-1:]), flush=True)
     with open(a.out, "w") as f:
-        f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}\n" + "\n".join(lines) + "\n")
+        extra = f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else ""
+        f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 
 
