@@ -46,6 +46,8 @@ def pool_yx_f32(x, kern, stride, pad):
     x = np.asarray(x, f32); B, C, H, W = x.shape
     (KH, KW), (SY, SX), (PY, PX) = kern, stride, pad
     OH, OW = pool_out_sz(H, KH, SY, PY), pool_out_sz(W, KW, SX, PX)
+    if H + 2 * PY < KH or W + 2 * PX < KW:   # either padded dim below the window: the op's out plane is 1 x 1
+        OH = OW = 1
     out = np.full((B, C, OH, OW), -FLT_MAX, f32); yx = np.full((B, C, OH, OW), -1.0, f32)
     for oy in range(OH):
         for ox in range(OW):
