@@ -24,13 +24,15 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .cnn_op import (NATIVE_ARGS, OpTune, add_bck_conv_annotations, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos,
-                     pipe_func_args)
+                     pipe_func_args, seed_from_var, SEED_VAR_ARG)
 from .conv_pipe import ConvPipe, PipeOp
 from .op import Dims, Nda, Op, RtErr, UnsupErr
 from .rtc import RtcArg, RtcFuncCall, RtcFuncInfo
 
 IN_PLACE_TYPES = ("ReLU", "Dropout", "BckDropout")   # and a ZeroIfNonPos whose out is its in (src/conv_util.cc:273-279)
 DROPOUT_RATIO = 0.5   # Dropout_coi's default (src/conv_util.cc:39); the ConvPipe records carry no ratio
+SEED_VAR = "det_drop_seed"   # ConvPipeBck(seed_in_var=True): the one-word uint32 var every dropout call reads its seed from
+DROP_LAYER_STEP = 0x9E3779B1   # the k-th Dropout layer of a pipe hashes with seed + k * this (mod 2^32)
 
 
 @dataclass
@@ -318,12 +320,21 @@ class ConvPipeBck:
     """The training-form step of a pipe with gradient ops over one backend (be=hip or be=cpu): forward, loss and every gradient, one call per native function.
     fuse_relu_grad=True (opt-in): every ReLU gradient that plan_relu_grad_folds allows emits no call; the BckConv data gradient / Spreading / BckLRN before it runs with
     zero_if_in_non_pos=1 and writes the masked gradient itself.  Every node holds the same values after a step either way.  `fused_relu_grads` says what init did:
-    {"folded": [ZeroIfNonPos tags], "unfolded": {ZeroIfNonPos tag: reason}}."""
+    {"folded": [ZeroIfNonPos tags], "unfolded": {ZeroIfNonPos tag: reason}}.
+    seed_in_var=True (opt-in): the dropout seed lives in the one-word uint32 var `det_drop_seed`.  Every dropout call runs with seed_from_var=1, reads that var and
+    carries only its layer's fixed offset by value; set_det_drop_seed uploads four bytes and touches no call.  Every node holds the same bits as under the default driver
+    given the same seed.  This is what lets a step with dropout be captured: capture_graph / run_graph / run_bck(graph=True) replay the whole call list as one
+    hipGraph (be=hip, one device), serially or -- parallel=True -- with the calls' true dependencies (_call_deps), and leave the same bits in every var as the eager
+    step."""
 
-    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False):
+    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False):
         self.rtc = rtc
         self.op_tune = op_tune or OpTune()
         self.fuse_relu_grad = bool(fuse_relu_grad)
+        self.seed_in_var = bool(seed_in_var)
+        self._graph: Optional[int] = None
+        self._stepped = False      # an ordinary step has run since init: every workspace and lazily built kernel exists
+        self.call_deps: List[List[int]] = []
         self.fused_relu_grads: Dict[str, object] = {"folded": [], "unfolded": {}}
         self.bck_calls: List[BckCall] = []
         self.vars: List[str] = []
@@ -341,8 +352,13 @@ class ConvPipeBck:
             raise RtErr("ConvPipeBck.init: pass the pipe add_bck_ops returned")
         self.bp = bp
         rtc, tune = self.rtc, self.op_tune
+        self._stepped = False
+        if self.seed_in_var and SEED_VAR in bp.nodes:
+            raise RtErr(f"ConvPipeBck.init: seed_in_var=True needs the var name {SEED_VAR!r}, which is a node of the pipe")
         for n, d in bp.nodes.items():
             self._var(n, d)
+        if self.seed_in_var:
+            self._var(SEED_VAR, Dims(("v",), (1,), "uint32_t"))
         fused = set()   # ReLUs taken into their convolution (src/rtc_fwd.cc:486-493): no forward call, their ZeroIfNonPos still runs
         relu_of: Dict[str, bool] = {}
         ops = bp.ops
@@ -397,7 +413,8 @@ class ConvPipeBck:
                 calls.append((fg, {"prob": prob, "label": o.bots[1], "in_grad_loss": o.tops[0], "loss_per_pel": lpp}))
                 calls.append((fl, {"loss_per_pel": lpp, "loss": o.tops[1]}))
             elif t in ("Dropout", "BckDropout"):
-                calls.append((add_pipe_op_annotations(op, tune)[0], {"inout": o.tops[0]}))
+                fd = add_pipe_op_annotations(op, tune)[0]
+                calls.append((seed_from_var(fd), {"inout": o.tops[0], SEED_VAR_ARG: SEED_VAR}) if self.seed_in_var else (fd, {"inout": o.tops[0]}))
             elif t == "Reduce":
                 calls.append((add_pipe_op_annotations(op, tune)[0], dict({f"ins_{i}": b for i, b in enumerate(o.bots)}, out=o.tops[0])))
             elif t == "Concat":
@@ -428,31 +445,49 @@ class ConvPipeBck:
             if n not in params:
                 raise RtErr(f"ConvPipeBck.init: no value for param {n!r}")
             rtc.copy_nda_to_var(n, np.ascontiguousarray(params[n], np.float32).reshape(d.sizes))
+        if self.seed_in_var:   # each layer's fixed offset, by value, once: from here on a new seed is four bytes into the var
+            for c, k in self._dropout_calls():
+                c.rfc.arg_map["det_drop_seed"] = RtcArg.scalar((k * DROP_LAYER_STEP) & 0xFFFFFFFF, "uint32_t")
         self.set_det_drop_seed(0)
+
+    def _dropout_calls(self) -> List[Tuple[BckCall, int]]:
+        """The dropout calls of the step with their layer's index among the pipe's Dropout ops (a layer's forward and backward call share it)."""
+        layer: Dict[str, int] = {}
+        out = []
+        for c in self.bck_calls:
+            if c.fop.get_func_name() == "hip_dropout":
+                tag = c.tag[:-4] if c.tag.endswith("_bck") else c.tag
+                out.append((c, layer.setdefault(tag, len(layer))))
+        return out
 
     def set_det_drop_seed(self, seed: int) -> None:
         """Rewrite the by-value det_drop_seed of every dropout call.  The forward and the backward call of one layer get the same seed (the gradient must drop what
-        the forward pass dropped); layers differ by their position among the pipe's Dropout ops."""
-        layer: Dict[str, int] = {}
-        for c in self.bck_calls:
-            if c.fop.get_func_name() != "hip_dropout":
-                continue
-            tag = c.tag[:-4] if c.tag.endswith("_bck") else c.tag
-            k = layer.setdefault(tag, len(layer))
-            c.rfc.arg_map["det_drop_seed"] = RtcArg.scalar((int(seed) + k * 0x9E3779B1) & 0xFFFFFFFF, "uint32_t")
+        the forward pass dropped); layers differ by their position among the pipe's Dropout ops.  With seed_in_var the calls stay as they are -- they carry their layer's
+        offset -- and the seed is uploaded into the var they all read."""
+        if self.seed_in_var:
+            self.rtc.copy_nda_to_var(SEED_VAR, np.array([int(seed) & 0xFFFFFFFF], np.uint32))
+            return
+        for c, k in self._dropout_calls():
+            c.rfc.arg_map["det_drop_seed"] = RtcArg.scalar((int(seed) + k * DROP_LAYER_STEP) & 0xFFFFFFFF, "uint32_t")
             c.rfc.invalidate()
 
     def calls(self) -> List[Tuple[str, Op, Dict[str, RtcArg]]]:
         """The ordered (tag, function op, arg map) list of the step."""
         return [(c.tag, c.fop, dict(c.rfc.arg_map)) for c in self.bck_calls]
 
-    def run_bck(self, to_set_vns: Sequence[str], fwd: Dict[str, np.ndarray], to_get_vns: Sequence[str]) -> None:
-        """Set inputs (data, label) -> run all calls -> get outputs into `fwd`: ConvPipeFwd.run_fwd's contract."""
+    def run_bck(self, to_set_vns: Sequence[str], fwd: Dict[str, np.ndarray], to_get_vns: Sequence[str], graph: bool = False) -> None:
+        """Set inputs (data, label) -> run all calls -> get outputs into `fwd`: ConvPipeFwd.run_fwd's contract.  graph=True: the calls run as one replay of the
+        graph capture_graph made."""
         rtc = self.rtc
+        if graph and self._graph is None:
+            raise RtErr("ConvPipeBck.run_bck(graph=True): no captured graph -- call capture_graph() first")
         for v in to_set_vns:
             rtc.copy_nda_to_var(v, fwd[v])
         rtc.finish_and_sync()
-        self.run_device_only()
+        if graph:
+            self.run_graph()
+        else:
+            self.run_device_only()
         for v in to_get_vns:
             fwd[v] = rtc.copy_var_to_nda(v)
 
@@ -466,14 +501,87 @@ class ConvPipeBck:
         self.compute_dur_ms = rtc.get_dur(ids[0], ids[-1]) if ids else 0.0
         self.per_call_ms = [(c.tag, c.fop.get_func_name(), rtc.get_dur(i, i)) for c, i in zip(self.bck_calls, ids)]
         rtc.release_per_call_id_data()
+        self._stepped = True
+        return self.compute_dur_ms
+
+    # -- hipGraph form of run_device_only: the call list captured once, replayed with one host call per step
+    def capture_graph(self, parallel: bool = False) -> int:
+        """Capture the step's call list into a hipGraph; -> number of captured calls.  If no ordinary step has run since init, one runs first on whatever the vars
+        hold: the K-slice workspaces and lazily built kernels must exist before a capture.  parallel=True: the graph gets the calls' true dependencies (_call_deps)
+        instead of the launch order, so that independent calls -- the three gradients of one BckConv, the branches of a fan-out -- may overlap.  A second capture
+        destroys the first.  Not provided on a multi-device backend (devices=...), where the step does not run either."""
+        rtc = self.rtc
+        drops = [c.tag for c, _ in self._dropout_calls()]
+        if drops and not self.seed_in_var:
+            raise RtErr(f"ConvPipeBck.capture_graph: the pipe has dropout calls ({', '.join(drops)}) whose det_drop_seed is a by-value argument: a captured launch freezes "
+                        "it, and every replay would drop the same elements.  Build the driver with seed_in_var=True: the seed then lives in a var the replay reads")
+        if isinstance(getattr(rtc, "devices", None), list):
+            raise UnsupErr("ConvPipeBck.capture_graph: not provided on a multi-device backend (devices=...)")
+        deps = self._call_deps() if parallel else None   # (before the capture opens: a host-side error here leaves none behind)
+        if self._graph is not None:
+            rtc.graph_destroy(self._graph); self._graph = None
+        if not self._stepped:
+            self.run_device_only()
+        rtc.finish_and_sync()
+        rtc.graph_begin()
+        for c in self.bck_calls:   # (a call that raises inside a capture: the backend drops the capture before it rethrows)
+            rtc.run(c.rfc)
+        if parallel:
+            self.call_deps = deps
+            self._graph = rtc.graph_end_deps(deps); n = len(self.bck_calls)
+        else:
+            self._graph, n = rtc.graph_end()
+        return n
+
+    def _call_deps(self) -> List[List[int]]:
+        """deps[i] = the earlier calls that call i must run after, from the IN / OUT kinds of each call's pipe_func_args on WHOLE vars: a call runs after the last
+        writer of every var it reads or writes (read-after-write, write-after-write) and after every reader since of a var it writes (write-after-read).  The in-place
+        arg `inout` is read and written; a var bound to an IN and an OUT arg of one call (an in-place hip_zero_if_non_pos) likewise.  The `in` of a zero_if_in_non_pos
+        call is an IN like any other.  The params and det_drop_seed are only read inside a step and order nothing.  The hip_concat calls of one op fill disjoint
+        channel ranges of one var; as whole-var writers they simply stay in list order among themselves, and a reader of the var follows the last of them."""
+        writer: Dict[str, int] = {}
+        readers: Dict[str, List[int]] = {}
+        deps: List[List[int]] = []
+        for i, c in enumerate(self.bck_calls):
+            am = c.rfc.arg_map
+            rd, wr = set(), set()
+            for an, io in pipe_func_args(c.fop):
+                if io == "IN" or an == "inout":
+                    rd.add(am[an].n)
+                if io == "OUT":
+                    wr.add(am[an].n)
+            d = {writer[v] for v in rd | wr if v in writer}
+            for v in wr:
+                d.update(readers.get(v, ()))
+            d.discard(i)
+            for v in rd:
+                readers.setdefault(v, []).append(i)
+            for v in wr:
+                writer[v] = i; readers[v] = []
+            deps.append(sorted(d))
+        return deps
+
+    def run_graph(self) -> float:
+        """One step as one graph launch; -> ms of the whole replay.  A replay has no per-call times: per_call_ms is []."""
+        rtc = self.rtc
+        if self._graph is None:
+            raise RtErr("ConvPipeBck.run_graph: no captured graph -- call capture_graph() first")
+        cid = rtc.graph_launch(self._graph)
+        rtc.finish_and_sync()
+        self.compute_dur_ms = rtc.get_dur(cid, cid)
+        self.per_call_ms = []
+        rtc.release_per_call_id_data()
         return self.compute_dur_ms
 
     def release(self) -> None:
+        if self._graph is not None:   # (before the funcs and vars its kernel nodes point into)
+            self.rtc.graph_destroy(self._graph); self._graph = None
         for f in self.funcs:
             self.rtc.release_func(f)
         for v in self.vars:
             self.rtc.release_var(v)
         self.funcs, self.vars, self.bck_calls = [], [], []
+        self._stepped = False
 
 
 def op_nd(bp: BckPipe, node: str) -> Nda:

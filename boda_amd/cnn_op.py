@@ -291,10 +291,35 @@ def fuse_zero_if_in_non_pos(fop: Op) -> Op:
     return a
 
 
+SEED_VAR_FLAG = "seed_from_var"   # uint32 of a hip_dropout function op: the hash seed is the word of the var arg det_drop_seed_var + the by-value det_drop_seed (wraps)
+SEED_VAR_ARG = "det_drop_seed_var"
+
+
+def has_seed_var_flag(fop: Op) -> bool:
+    return fop.has(SEED_VAR_FLAG) and fop.get_u32(SEED_VAR_FLAG) != 0
+
+
+def seed_from_var(fop: Op) -> Op:
+    """-> a copy of an annotated hip_dropout function op (a Dropout's or a BckDropout's) with seed_from_var=1: the call takes one more var arg behind inout,
+    det_drop_seed_var (uint32_t, dims v=1, added to the op), and hashes with seed = that word + the by-value det_drop_seed, a uint32 add that wraps.  A flagged call
+    with word w and by-value o writes the bits of the unflagged call with by-value (w + o) mod 2^32.  The seed then lives in device memory: a launch captured into a
+    hipGraph freezes the by-value argument, not the word."""
+    fn = fop.get_func_name() if fop.has_func_name() else ""
+    if fn != "hip_dropout":
+        raise RtErr(f"seed_from_var: {fn or fop.get_type()!r} is not hip_dropout (the only function that takes a seed)")
+    from .op import Dims
+    a = fop.copy()
+    a.nda_vals[SEED_VAR_FLAG] = Nda(None, "uint32_t", (1,))
+    a.nda_vals[SEED_VAR_ARG] = Nda(dims=Dims(("v",), (1,), "uint32_t"), tn="uint32_t")
+    return a
+
+
 def pipe_func_args(fop: Op) -> tuple:
     """The (arg, IN | OUT | REF | VAL) list of an annotated function op: NATIVE_ARGS; for hip_reduce its ins_0 .. ins_{n-1} followed by out; for a hip_bconv_in /
-    hip_spreading with zero_if_in_non_pos=1 the var arg `in` in front of in_grad_loss."""
+    hip_spreading with zero_if_in_non_pos=1 the var arg `in` in front of in_grad_loss; for a hip_dropout with seed_from_var=1 the var arg det_drop_seed_var behind inout."""
     fn = fop.get_func_name()
+    if fn == "hip_dropout" and has_seed_var_flag(fop):
+        return NATIVE_ARGS[fn][:1] + ((SEED_VAR_ARG, "IN"),) + NATIVE_ARGS[fn][1:]
     if fn == "hip_reduce":
         return tuple((an, "IN") for an in fop.multi_names("ins")) + (("out", "OUT"),)
     if fn in ("hip_bconv_in", "hip_spreading") and has_zinp_flag(fop):
@@ -329,7 +354,7 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_sm_grad_and_loss": (("prob", "IN"), ("label", "IN"), ("in_grad_loss", "OUT"), ("loss_per_pel", "OUT")),
     "hip_sum_loss_over_imgs": (("loss_per_pel", "IN"), ("loss", "OUT")),
     # the gradient pipe's plumbing (test/rtc/dropout.cucl; the copy calls of src/rtc_fwd.cc:267-294).  VAL: a by-value scalar of the CALL (uint32 det_drop_seed).
-    # hip_reduce's list depends on the op (ins_0 .. ins_{n-1}, out): pipe_func_args
+    # hip_reduce's list depends on the op (ins_0 .. ins_{n-1}, out), hip_dropout's on seed_from_var (inout, det_drop_seed_var, det_drop_seed): pipe_func_args
     "hip_dropout": (("inout", "OUT"), ("det_drop_seed", "VAL")),
     "hip_concat": (("in", "IN"), ("out", "OUT")),
     "hip_split": (("in", "IN"), ("out", "OUT")),

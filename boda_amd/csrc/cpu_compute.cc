@@ -339,6 +339,7 @@ struct cpu_compute_t : public rtc_compute_t {
                                                     (fn.empty() ? fi.func_name : fn) + "' is generated CUCL source, which needs a GPU backend");
       if (is_conv(fn)) (void)fi.op.get_u32("conv_has_relu");
       (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
+      (void)op_seed_var_flag(fi.op);   // (likewise)
       if (bck_op_fn_t const *d = find_bck_op(fn)) {
         if (!type_ok(*d, fi.op.get_type())) rt_err(fn + ": a function of op type " + d->type + ", not " + fi.op.get_type());
         for (string const &an : bck_op_ins(*d, fi.op)) (void)fi.op.get_dims(an);
@@ -561,7 +562,14 @@ struct cpu_compute_t : public rtc_compute_t {
       auto si = am.find("det_drop_seed");
       if (si == am.end() || !si->second.is_valid() || si->second.is_var() || !si->second.v->rp_elems() || si->second.v->dims.tn != "uint32_t" || si->second.v->dims.sz() != 0)
         rt_err(fn + ": 'det_drop_seed' must be a by-value uint32_t scalar of the call");
-      dropout(out[0], (long)get_var_dims(var_of(am, "inout")).dims_prod(), ratio, *(uint32_t const *)si->second.v->rp_elems());
+      uint32_t seed = *(uint32_t const *)si->second.v->rp_elems();
+      if (op_seed_var_flag(op)) {   // the hash seed is the var's word + the by-value seed, a uint32 add that wraps
+        auto wi = am.find("det_drop_seed_var");
+        if (wi == am.end() || !wi->second.is_valid() || !wi->second.is_var()) rt_err(fn + ": seed_from_var=1: the var arg 'det_drop_seed_var' is required");
+        check_seed_var(fn, wi->second.n, get_var_dims(wi->second.n), var_of(am, "inout"));
+        seed += *(uint32_t const *)must_find(vis, wi->second.n).buf.get();
+      }
+      dropout(out[0], (long)get_var_dims(var_of(am, "inout")).dims_prod(), ratio, seed);
     } else if (fn == "hip_concat" || fn == "hip_split") {
       bool const cat = fn == "hip_concat";
       dims_t const &i4 = op.get_dims("in"), &o4 = op.get_dims("out");
@@ -588,6 +596,7 @@ struct cpu_compute_t : public rtc_compute_t {
     rtc_func_info_t const &fi = fit->second.info;
     string const &fn = fi.op.get_func_name();
     map_str_rtc_arg_t const &am = rfc.arg_map;
+    (void)op_seed_var_flag(fi.op);   // (refuses the flag on a function that cannot take it)
     double const tb = now_ms();
     if (bck_op_fn_t const *bd = find_bck_op(fn)) run_bck_op(*bd, fi.op, am);
     else if (is_bck(fn)) run_bck(fn, fi.op, am);

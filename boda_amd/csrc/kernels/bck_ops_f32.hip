@@ -46,13 +46,16 @@
 //   * h = (uint32)flat index + seed (wraps), then h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16
 //   * inout = h > thresh ? inout * scale : +0;  thresh = (uint32)((float)0xffffffff * ratio) and scale = (float)(1 / (1 - (double)ratio)) come from the host;
 //     the seed is a run-time argument: a new seed is no new specialisation
+//   * SEEDVAR=1 (the function op's seed_from_var): seed = *p4 + p.seed (a uint32 wrap-around add), p4 one uint32 word in device memory that every thread
+//     loads from the same address -- a captured launch (hipGraph) freezes p.seed but not the word, so every replay can drop other elements.  With word w and
+//     by-value o the bits are those of the plain kernel under the seed (w + o) mod 2^32; without the define the kernel is the plain one
 // OP 11 bodahip_concat / OP 12 bodahip_split  (the reference's copy calls, src/rtc_fwd.cc:267-294)   in -> out: an img:chan:y:x tensor copied into (11) / out of (12)
 //   the channel range [cix, cix + chan) of a wider one.  Per image that range is one run of `run` = chan * y * x consecutive floats, `wide` = the wider tensor's
 //   floats per image, `off` = cix * y * x
 // OP 9 .. 12 take float4 over the first n4 quads and scalars over the tail, like OP 5; the host sets n4 = 0 unless every pointer (11, 12: every per-image run) is
 // 16-byte aligned.  Quads never straddle a run: 11 / 12 use them only when run, wide and off are multiples of 4.
 //
-// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN | 2, 4: [ZINP].  Host side: plan_bck_op (native_plan.cc), native_kernels.cc.
+// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN | 2, 4: [ZINP] | 10: [SEEDVAR].  Host side: plan_bck_op (native_plan.cc), native_kernels.cc.
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -62,6 +65,9 @@
 #ifndef ZINP
 #define ZINP 0
 #endif
+#ifndef SEEDVAR
+#define SEEDVAR 0
+#endif
 
 struct bck_ops_args_t {   // must match native_internal.h
   float const *p0; float const *p1; float const *p2; float const *p3;   // inputs, in the function's arg order
@@ -69,7 +75,7 @@ struct bck_ops_args_t {   // must match native_internal.h
   long n;                                                               // threads that have work
   int B, C, HW, n4;                                                     // images, channels, pels of a plane; OP 5: float4 quads
   float f0, f1, f2, f3;                                                 // LRN: alpha / local_size, beta, k, ((2 * -beta) * alpha) / local_size; OP 10: f0 = scale
-  float const *p4; float const *p5; float const *p6; float const *p7;   // OP 9: inputs 4 .. 7
+  float const *p4; float const *p5; float const *p6; float const *p7;   // OP 9: inputs 4 .. 7; OP 10 with SEEDVAR: p4 = the uint32 word added to seed
   unsigned seed, thresh;                                                // OP 10
   int run, wide, off;                                                   // OP 11, 12: floats of one image's channel range, of one image of the wider tensor, offset of the range
 };
@@ -306,22 +312,27 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
 
 #elif OP == 10
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float drop1(float x, unsigned ix, bck_ops_args_t const &p) {
-  unsigned h = ix + p.seed;
+__device__ __forceinline__ float drop1(float x, unsigned ix, unsigned seed, bck_ops_args_t const &p) {
+  unsigned h = ix + seed;
   h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
   return h > p.thresh ? x * p.f0 : 0.0f;
 }
 extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) {
   long const id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= p.n) return;
+#if SEEDVAR
+  unsigned const seed = *(unsigned const *)p.p4 + p.seed;   // (one address for the whole launch)
+#else
+  unsigned const seed = p.seed;
+#endif
   if (id < p.n4) {
     f32x4 v = ((f32x4 const *)p.o0)[id];
     unsigned const e = 4u * (unsigned)id;
-    v.x = drop1(v.x, e, p); v.y = drop1(v.y, e + 1u, p); v.z = drop1(v.z, e + 2u, p); v.w = drop1(v.w, e + 3u, p);
+    v.x = drop1(v.x, e, seed, p); v.y = drop1(v.y, e + 1u, seed, p); v.z = drop1(v.z, e + 2u, seed, p); v.w = drop1(v.w, e + 3u, seed, p);
     ((f32x4 *)p.o0)[id] = v;
   } else {
     long const e = 4L * p.n4 + (id - p.n4);
-    p.o0[e] = drop1(p.o0[e], (unsigned)e, p);
+    p.o0[e] = drop1(p.o0[e], (unsigned)e, seed, p);
   }
 }
 

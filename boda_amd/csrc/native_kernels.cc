@@ -44,6 +44,7 @@ void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
   if (fn == "hip_conv_k1_chain") { (void)fi.op.get_u32("conv_has_relu"); (void)fi.op.get_u32("conv_has_relu2"); return; }
   if (fn == "hip_conv_filts_kmajor") return;
   (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
+  (void)op_seed_var_flag(fi.op);   // (likewise)
   if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases") {   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     return;
@@ -774,7 +775,7 @@ void native_kernels_t::bconv_biases(float const *out_grad, float *biases_grad, c
 
 
 // ---- the non-conv ops of the gradient pipe (kernels/bck_ops_f32.hip): one launch, one thread per written element (softmax: one wave per image)
-void native_kernels_t::bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs) {
+void native_kernels_t::bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs, uint32_t const *seed_word) {
   bck_plan_t const bp = plan_bck_op(g, host->nh_num_cus());
   kernel_t &k = get_kernel(impl, host, bp.p);
   bck_ops_args_t a; memset(&a, 0, sizeof(a));
@@ -789,6 +790,7 @@ void native_kernels_t::bck_op(bck_op_geom_t const &g, float const *const *ins, f
     if (g.op == 9) { a.p4 = ins[4]; a.p5 = ins[5]; a.p6 = ins[6]; a.p7 = ins[7]; }
     if (g.op == 10) {   // the template's own arithmetic: a float product truncated to uint32, a double quotient rounded to float
       a.seed = g.seed; a.thresh = (uint32_t)((float)0xffffffffu * g.ratio); a.f0 = (float)(1.0 / (1.0 - (double)g.ratio));
+      if (g.seedvar) { if (!seed_word) rt_err("hip_dropout: seed_from_var=1 without a seed word"); a.p4 = (float const *)seed_word; }   // (-DSEEDVAR=1 reads it as one uint32)
     }
     if (g.op == 11 || g.op == 12) {   // every per-image run must start on a quad in both tensors, and be whole quads
       n = bp.threads;

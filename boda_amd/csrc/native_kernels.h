@@ -29,6 +29,7 @@
 //       hip_sum_loss_over_imgs  loss_per_pel loss                                                                  test/rtc/sum_loss_over_imgs.cucl
 //       hip_reduce              ins_0 .. ins_{ins_num-1} out                  (2 .. 8 inputs)                      test/rtc/reduce.cucl
 //       hip_dropout             inout det_drop_seed(by-value uint32)          (Dropout and BckDropout)             test/rtc/dropout.cucl
+//                               with seed_from_var=1 in the op: inout det_drop_seed_var(uint32_t var, one element) det_drop_seed -- the hash seed is word + by-value
 //       hip_concat / hip_split  in out   (ocix / icix in the op: one call per input / output)                      src/rtc_fwd.cc:267-294
 //     hip_conv_winograd                 same contract as hip_conv; 3x3 / stride-1 layers through F(2x2,3x3) Winograd (mrd <= ~2e-3)
 // and lands them on kernels/gemm_conv_f32.hip (and, for short-K 1x1 convs with a long pel axis, kernels/k1_stream_f32.hip),
@@ -89,7 +90,8 @@ struct post_ops_t { int PKH = 0, PKW = 0, PSY = 1, PSX = 1, PPY = 0, PPX = 0, PO
 // call.  concat / split: B images of the narrow tensor's C channels (planes H x W) at channels [cix, cix + C) of the wide tensor's CT
 struct bck_op_geom_t { int op = 0; long B = 0; int C = 0, H = 1, W = 1, OH = 1, OW = 1, KH = 1, KW = 1, SY = 1, SX = 1, PY = 0, PX = 0, avg = 0, LS = 1; float alpha = 0.f, beta = 0.f, k = 0.f; long n = 0;
   int nin = 0; float ratio = 0.f; uint32_t seed = 0; int CT = 0, cix = 0;
-  int zinp = 0; };   // spreading, bck_lrn: 1 = in_grad_loss = in > 0 ? value : +0 (the op's zero_if_in_non_pos; spreading then takes `in` as its fourth input)
+  int zinp = 0;      // spreading, bck_lrn: 1 = in_grad_loss = in > 0 ? value : +0 (the op's zero_if_in_non_pos; spreading then takes `in` as its fourth input)
+  int seedvar = 0; };   // dropout: 1 = the hash seed is the word of the call's det_drop_seed_var + seed (the op's seed_from_var)
 
 struct launch_info_t { string kernel; tile_cfg_t cfg; uint32_t grid = 0, block = 0; double flops = 0, algo_bytes = 0; };
 
@@ -129,7 +131,8 @@ struct native_kernels_t {
   void bconv_filts(float const *in, float const *out_grad, float *filts_grad, conv_geom_t const &g);
   void bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g);
   // the non-conv ops of the gradient pipe: ins / outs in the function's arg order (up to eight / two raw device pointers)
-  void bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs);
+  // seed_word (dropout with g.seedvar): the device word added to g.seed
+  void bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs, uint32_t const *seed_word = nullptr);
   void conv_winograd(float const *filts, float const *biases, float const *in, float *out, conv_geom_t const &g, int out_ctot, int out_coff);
 
   // tuning overrides ("" clears): key "sgemm_tile" / "conv_tile" -> "BIxBJxBKxWIxWJ[xMINW[xSPLITK[xMT]]]"; key "k1_stream" -> "off" | "WIxWJxOCBxCB[xMINW]";

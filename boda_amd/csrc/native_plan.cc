@@ -1245,6 +1245,7 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
   auto lim = [&](double elems) { if (4.0 * elems >= 2147483648.0) unsup_err(what + ": tensors of 2 GiB or more (32-bit element offsets)"); };
   if (g.B < 0 || g.C < 0) rt_err(what + ": negative dims");
   if (g.zinp && g.op != 2 && g.op != 4) rt_err(what + ": zero_if_in_non_pos=1 is taken by hip_spreading and hip_bck_lrn only");
+  if (g.seedvar && g.op != 10) rt_err(what + ": seed_from_var=1 is taken by hip_dropout only");
   double const in_e = (double)g.B * g.C * g.H * g.W, out_e = (double)g.B * g.C * g.OH * g.OW;
   if (g.op == 1 || g.op == 2) {
     if (g.KH < 1 || g.KW < 1 || g.SY < 1 || g.SX < 1 || g.PY < 0 || g.PX < 0 || g.H < 1 || g.W < 1 || g.OH < 1 || g.OW < 1) rt_err(what + ": zero kern_sz / stride / plane");
@@ -1286,6 +1287,7 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
     if (!(g.ratio > 0.0f && g.ratio < 1.0f)) rt_err(what + ": dropout_ratio=" + std::to_string(g.ratio) + " must lie inside (0, 1)");
     if (g.n < 0) rt_err(what + ": negative size");
     lim((double)g.n);
+    if (g.seedvar) D("SEEDVAR", 1);
     r.threads = g.n; r.algo_bytes = 8.0 * g.n;
   } else if (g.op == 11 || g.op == 12) {
     char const *const ix = (g.op == 11) ? "ocix" : "icix";

@@ -107,6 +107,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
   string const tile = (tile_arg.empty() && ht != op.str_vals.end()) ? ht->second : tile_arg;
   plan_t p; string log, s2d;
   (void)op_zinp_flag(op);   // (refuses the flag on a function that cannot take it)
+  (void)op_seed_var_flag(op);   // (likewise)
   bool const bf16 = op.has_func_name() && (op.get_func_name() == "hip_sgemm_bf16" || op.get_func_name() == "hip_conv_bf16");
   if (t == "sgemm") {
     dims_t const &a = op.get_dims("a"), &b = op.get_dims("b");
@@ -230,7 +231,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     string desc; size_t bytes = 0;
     if (!op.has_func_name() && (t == "Concat" || t == "Split")) unsup_err("prebuild: a bare " + t + " is one call per " + (t == "Concat" ? "input" : "output") + ": annotate it (cnn_op.add_pipe_op_annotations) and pass the function ops");
     for (bck_op_desc_t const *d : ds) {
-      bck_op_geom_t bg = bck_op_geom_of_op(op, *d); bg.zinp = op_zinp_flag(op) ? 1 : 0;
+      bck_op_geom_t bg = bck_op_geom_of_op(op, *d); bg.zinp = op_zinp_flag(op) ? 1 : 0; bg.seedvar = op_seed_var_flag(op) ? 1 : 0;
       bck_plan_t const bp = plan_bck_op(bg, num_cus);
       desc += (desc.empty() ? "" : " | ") + bck_plan_desc(bp);
       if (!arch.empty()) bytes += compile_plan(bp.p, arch, &log).size();
@@ -301,6 +302,7 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
   string const &fn = fi.op.get_func_name();
   exact_override_t const xov(impl, fi.op);
   bool const zinp = op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
+  bool const seedvar = op_seed_var_flag(fi.op);   // (likewise)
   bool const bf16 = (fn == "hip_sgemm_bf16" || fn == "hip_conv_bf16");
   if (fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "hip_sgemm_bf16") {
     string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");
@@ -650,10 +652,17 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
         rt_err(fn + ": 'det_drop_seed' must be a by-value uint32_t scalar of the call");
       g.seed = *(uint32_t const *)si->second.v->rp_elems();
     }
+    uint32_t const *seed_word = nullptr;
+    if (seedvar) {   // the word the kernel adds to the by-value seed: one uint32 in device memory, never the tensor the call rewrites
+      auto wi = am.find("det_drop_seed_var");
+      if (wi == am.end() || !wi->second.is_valid() || !wi->second.is_var()) rt_err(fn + ": seed_from_var=1: the var arg 'det_drop_seed_var' is required");
+      check_seed_var(fn, wi->second.n, host->nh_var_dims(wi->second.n), var_of(am, "inout"));
+      seed_word = (uint32_t const *)host->nh_var_ptr(wi->second.n); g.seedvar = 1;
+    }
     if (g.op == 5) g.n = (long)host->nh_var_dims(var_of(am, "in")).dims_prod();
     else if (g.op == 9 || g.op == 10) g.n = (long)host->nh_var_dims(var_of(am, d->outs[0])).dims_prod();
     else if (n_img >= 0) g.B = n_img;
-    bck_op(g, ins, outs);
+    bck_op(g, ins, outs, seed_word);
     return;
   }
   if (fn == "hip_conv_filts_kmajor") {   // filts (out_chan:in_chan:y:x) -> filts_km ([K + 128][out_chan padded to 4], zeros in the padding): see filts_km above

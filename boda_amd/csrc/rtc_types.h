@@ -138,6 +138,20 @@ inline bool op_zinp_flag(op_base_t const &op) {
   if (!(op.get_dims("in") == op.get_dims("in_grad_loss"))) rt_err(fn + ": zero_if_in_non_pos=1 needs in and in_grad_loss of the same dims");
   return true;
 }
+// seed_from_var, a uint32 of a hip_dropout function op (absent: 0).  1: the call takes one more var arg, det_drop_seed_var (uint32_t, one element), and hashes with
+// seed = that word + the by-value det_drop_seed (wraps): the seed then lives in device memory, where a captured launch reads it anew at every replay
+inline bool op_seed_var_flag(op_base_t const &op) {
+  if (!op.has("seed_from_var") || !op.get_u32("seed_from_var")) return false;
+  string const fn = op.has_func_name() ? op.get_func_name() : string();
+  bool const bare_dropout = fn.empty() && op.has_type() && (op.get_type() == "Dropout" || op.get_type() == "BckDropout");
+  if (fn != "hip_dropout" && !bare_dropout) rt_err("seed_from_var=1 on '" + (fn.empty() ? (op.has_type() ? op.get_type() : string("?")) : fn) + "': only hip_dropout takes a seed, and only it can read one from a var");
+  return true;
+}
+// the var bound to det_drop_seed_var: uint32_t, exactly one element, and not the tensor the call rewrites
+inline void check_seed_var(string const &fn, string const &vn, dims_t const &d, string const &inout_vn) {
+  if (vn == inout_vn) rt_err(fn + ": seed_from_var=1: 'det_drop_seed_var' and 'inout' are the same var '" + vn + "'");
+  if (d.tn != "uint32_t" || d.dims_prod() != 1) rt_err(fn + ": seed_from_var=1: 'det_drop_seed_var' must be a uint32_t var with exactly one element, got '" + vn + "' " + d.tn + " " + d.pretty_str());
+}
 
 // ---- rtc layer ----------------------------------------------------------------------------------------------------
 struct rtc_compile_opts_t {

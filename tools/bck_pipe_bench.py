@@ -4,11 +4,18 @@ and the share of the step each native function takes (sums of the backend's per-
 
     python tools/bck_pipe_bench.py [--nets nin,alexnet] [--batch 256] [--runs 5] [--warmup 2] [--out profiles/r09_bck_pipe_bench.txt]
     python tools/bck_pipe_bench.py --fuse-relu-grad [--repeats 3] [--out profiles/r09_bck_fuse_ab.txt]
+    python tools/bck_pipe_bench.py --graph [--repeats 3] [--out profiles/r10_bck_graph_ab.txt]
 
 --fuse-relu-grad: the same step both ways in ONE process -- ConvPipeBck() and ConvPipeBck(fuse_relu_grad=True), each on a backend instance of its own with the same
 params and inputs -- after the usual warm-up, in --repeats alternating blocks of --runs steps.  Per net two JSON lines ("way": "unfused" / "fused": step ms as the median
 over all blocks, the medians of the single blocks (their spread is the run-to-run spread a difference has to beat), images/s, the call count, the per-function share)
 and a third with the launches removed and the fused / unfused ratio.  The comparison is between the two ways of one run, never against a recorded figure.
+
+--graph: the same construction for the step as one hipGraph replay.  Three ways in ONE process, each a ConvPipeBck(seed_in_var=True) on a backend instance of its own
+with the same params and inputs: "eager" (run_device_only), "graph" (capture_graph(), run_graph) and "graph_parallel" (capture_graph(parallel=True): the calls' true
+dependencies instead of the launch order).  The seed advances per step in all three (four bytes into the det_drop_seed var).  Per net one JSON line per way (step ms as
+the median over all blocks, the block medians, images/s, the captured call count) and one with the two ratios against the eager step of the same run and whether all
+three ended with the same loss bits.  No ratio is required: the spread of the block medians is what a difference has to beat.
 
 Every net runs in a child process of its own under a time limit (--limit seconds); the first one that fails ends the run.
 """
@@ -69,6 +76,51 @@ def fuse_ab(net, batch, runs, warmup, repeats):
         w["drv"].release(); w["rtc"].close()
 
 
+def graph_ab(net, batch, runs, warmup, repeats):
+    import numpy as np
+    from boda_amd import conv_pipe
+    from boda_amd.bck_pipe import ConvPipeBck, add_bck_ops, host_params
+    from boda_amd.rtc import make_rtc
+    cp = {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv}[net](batch)
+    bp = add_bck_ops(cp)
+    params = host_params(bp, 5)
+    rng = np.random.default_rng(0)
+    data = rng.uniform(-1, 1, cp.nodes["data"].sizes).astype(np.float32)
+    label = rng.integers(0, 1000, (batch, 1, 1)).astype(np.float32)
+    ways = {}
+    for way in ("eager", "graph", "graph_parallel"):
+        rtc = make_rtc("(be=hip)", 0)
+        rtc.init()
+        drv = ConvPipeBck(rtc, seed_in_var=True)
+        drv.init(bp, params)
+        rtc.copy_nda_to_var("data", data); rtc.copy_nda_to_var("label", label)
+        drv.set_det_drop_seed(0); drv.run_device_only()   # (every way's first step is an eager one: kernels and workspaces)
+        captured = drv.capture_graph(parallel=(way == "graph_parallel")) if way != "eager" else 0
+        ways[way] = {"rtc": rtc, "drv": drv, "blocks": [], "ms": [], "captured": captured, "run": drv.run_device_only if way == "eager" else drv.run_graph}
+    for w in ways.values():
+        for i in range(warmup):
+            w["drv"].set_det_drop_seed(i); w["run"]()
+    for rep in range(repeats):
+        for w in ways.values():
+            ms = []
+            for i in range(runs):
+                w["drv"].set_det_drop_seed(warmup + rep * runs + i)
+                ms.append(w["run"]())
+            w["ms"] += ms; w["blocks"].append(round(statistics.median(ms), 3))
+    loss = {k: w["rtc"].copy_var_to_nda("loss").tobytes() for k, w in ways.items()}
+    for way, w in ways.items():
+        step = statistics.median(w["ms"])
+        print(json.dumps({"net": net, "batch": batch, "way": way, "calls": len(w["drv"].calls()), "captured_calls": w["captured"], "step_ms": round(step, 3),
+                          "block_medians_ms": w["blocks"], "imgs_per_s": round(batch / (step * 1e-3), 1),
+                          "loss": round(float(np.frombuffer(loss[way], np.float32)[0]), 4)}), flush=True)
+    e = statistics.median(ways["eager"]["ms"])
+    print(json.dumps({"net": net, "graph_over_eager": round(statistics.median(ways["graph"]["ms"]) / e, 4),
+                      "graph_parallel_over_eager": round(statistics.median(ways["graph_parallel"]["ms"]) / e, 4),
+                      "same_loss_bits": loss["eager"] == loss["graph"] == loss["graph_parallel"]}), flush=True)
+    for w in ways.values():
+        w["drv"].release(); w["rtc"].close()
+
+
 def one_net(net, batch, runs, warmup):
     import numpy as np
     from boda_amd import conv_pipe
@@ -108,24 +160,30 @@ def main(argv=None):
     ap.add_argument("--limit", type=int, default=240, help="seconds per net")
     ap.add_argument("--out", default="")
     ap.add_argument("--fuse-relu-grad", action="store_true", help="A/B: the step with and without the ReLU gradients folded into their producers, in one process")
-    ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad: alternating blocks of --runs steps per way")
+    ap.add_argument("--graph", action="store_true", help="A/B: the eager step, the step as one hipGraph replay, and the replay with the calls' true dependencies, in one process")
+    ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad / --graph: alternating blocks of --runs steps per way")
     ap.add_argument("--child", default="")
     a = ap.parse_args(argv)
-    a.out = a.out or os.path.join(ROOT, "profiles", "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r09_bck_pipe_bench.txt")
+    if a.graph and a.fuse_relu_grad:
+        ap.error("--graph and --fuse-relu-grad are two comparisons: run them one at a time")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r09_bck_pipe_bench.txt")
     if a.child:
+        if a.graph:
+            return graph_ab(a.child, a.batch, a.runs, a.warmup, a.repeats)
         return fuse_ab(a.child, a.batch, a.runs, a.warmup, a.repeats) if a.fuse_relu_grad else one_net(a.child, a.batch, a.runs, a.warmup)
     lines = []
     for net in a.nets.split(","):
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", net, "--batch", str(a.batch), "--runs", str(a.runs), "--warmup", str(a.warmup)]
         cmd += ["--fuse-relu-grad", "--repeats", str(a.repeats)] if a.fuse_relu_grad else []
+        cmd += ["--graph", "--repeats", str(a.repeats)] if a.graph else []
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:   # nothing more is started on the GPU after a failure
             print(f"{net}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
             return r.returncode
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
-        print("\n".join(lines[-3:] if a.fuse_relu_grad else lines[-1:]), flush=True)
+        print("\n".join(lines[-4:] if a.graph else lines[-3:] if a.fuse_relu_grad else lines[-1:]), flush=True)
     with open(a.out, "w") as f:
-        extra = f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else ""
+        extra = f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else ""
         f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 
