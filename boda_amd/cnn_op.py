@@ -269,6 +269,21 @@ def add_pipe_op_annotations(op: Op, tune: OpTune) -> tuple:
     return tuple(outs)
 
 
+CHAN_AFFINE_FUNC = "hip_chan_affine"
+
+
+def chan_affine_func_op(dims, relu: int) -> Op:
+    """-> the annotated function op of hip_chan_affine on a float img:chan:y:x tensor `dims`: out = in * a[chan] + b[chan] (a multiply, then an add), with relu=1
+    followed by x > 0 ? x : +0.  Args in, a, b, out; in and out may be one var.  What ConvPipeFwd runs for a BatchNorm / Scale run of an fp32 net."""
+    from .op import Dims
+    ch = Dims(("chan",), (dims.dsz("chan"),), "float")
+    a = Op({"type": "ChanAffine"}, {"in": Nda(dims=dims, tn="float"), "out": Nda(dims=dims, tn="float"), "a": Nda(dims=ch, tn="float"), "b": Nda(dims=ch, tn="float"),
+                                    "relu": Nda(None, "uint32_t", (int(relu),))})
+    a.chan_affine_geom()
+    a.set_func_name(CHAN_AFFINE_FUNC)
+    return a
+
+
 ZINP_FLAG = "zero_if_in_non_pos"   # uint32 of a function op: in_grad_loss[e] = in[e] > 0 ? g[e] : +0, hip_zero_if_non_pos's rule applied on the producer's store
 ZINP_FUNCS = ("hip_bconv_in", "hip_spreading", "hip_bck_lrn")   # the functions that write an in_grad_loss with the dims of their op's forward input `in`
 
@@ -316,7 +331,8 @@ def seed_from_var(fop: Op) -> Op:
 
 def pipe_func_args(fop: Op) -> tuple:
     """The (arg, IN | OUT | REF | VAL) list of an annotated function op: NATIVE_ARGS; for hip_reduce its ins_0 .. ins_{n-1} followed by out; for a hip_bconv_in /
-    hip_spreading with zero_if_in_non_pos=1 the var arg `in` in front of in_grad_loss; for a hip_dropout with seed_from_var=1 the var arg det_drop_seed_var behind inout."""
+    hip_spreading with zero_if_in_non_pos=1 the var arg `in` in front of in_grad_loss; for a hip_dropout with seed_from_var=1 the var arg det_drop_seed_var behind inout;
+    for a hip_conv_nhwc with nhwc_residual=1 the var arg `res` in front of out."""
     fn = fop.get_func_name()
     if fn == "hip_dropout" and has_seed_var_flag(fop):
         return NATIVE_ARGS[fn][:1] + ((SEED_VAR_ARG, "IN"),) + NATIVE_ARGS[fn][1:]
@@ -324,6 +340,8 @@ def pipe_func_args(fop: Op) -> tuple:
         return tuple((an, "IN") for an in fop.multi_names("ins")) + (("out", "OUT"),)
     if fn in ("hip_bconv_in", "hip_spreading") and has_zinp_flag(fop):
         return NATIVE_ARGS[fn][:-1] + (("in", "IN"),) + NATIVE_ARGS[fn][-1:]
+    if fn == "hip_conv_nhwc" and fop.has("nhwc_residual") and fop.get_u32("nhwc_residual"):     # (nhwc.fuse_residual: the shortcut, in front of out)
+        return NATIVE_ARGS[fn][:-1] + (("res", "IN"),) + NATIVE_ARGS[fn][-1:]
     return NATIVE_ARGS[fn]
 
 
@@ -358,6 +376,8 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_dropout": (("inout", "OUT"), ("det_drop_seed", "VAL")),
     "hip_concat": (("in", "IN"), ("out", "OUT")),
     "hip_split": (("in", "IN"), ("out", "OUT")),
+    # the forward pipe's BatchNorm / Scale runs (this backend's own; relu rides in the op)
+    "hip_chan_affine": (("in", "IN"), ("a", "IN"), ("b", "IN"), ("out", "OUT")),
 }
 
 

@@ -9,6 +9,8 @@ Restates the behaviour of the reference's net-level path (not its code):
       conv in place is FUSED into it (conv_has_relu=1, the ReLU emits no call, :486-493,266); one call per remaining op in
       topological order; params are uploaded once; run_fwd = set inputs -> run all calls -> get outputs; the duration
       is get_dur(first call, last call); an optional per-call profile (python assignments, :560-572)
+  * BatchNorm / Scale / Eltwise (ResNet)  the reference names the types (src/conv_util.cc:37-38,56) and ships nets/resnet-50, its rtc_fwd.cc never ran them:
+      their inference semantics here are this backend's own -- fold_affine() and the native function hip_chan_affine state them
 Convolutions run on the native side door (hip_conv); pooling / LRN / un-fused ReLU are this project's own CUCL-dialect
 sources (semantics of test/rtc/{pool,lrn,relu}.cucl) and go through the backend's generic hiprtc path.
 The reference ships no trained weights (nets/ holds prototxts only), so params default to its deterministic
@@ -23,7 +25,7 @@ import os
 import numpy as np
 
 from . import gen_data as gd
-from .cnn_op import FILTS_KMAJOR_FUNC, K1_CHAIN_FUNC, NATIVE_ARGS, OpTune, add_codegen_annotations, annotate_k1_chain, f32_pool_fusable, fuse_f32_pool, k1_chain_applies
+from .cnn_op import CHAN_AFFINE_FUNC, FILTS_KMAJOR_FUNC, K1_CHAIN_FUNC, NATIVE_ARGS, OpTune, chan_affine_func_op, pipe_func_args, add_codegen_annotations, annotate_k1_chain, f32_pool_fusable, fuse_f32_pool, k1_chain_applies
 from .cucl_template import instantiate, parse_template
 from .op import Dims, Nda, Op, RtErr, UnsupErr
 from .rtc import HipCompute, RtcArg, RtcCompileOpts, RtcFuncCall, RtcFuncInfo
@@ -35,7 +37,7 @@ from .rtc import HipCompute, RtcArg, RtcCompileOpts, RtcFuncCall, RtcFuncInfo
 @dataclass
 class PipeOp:
     tag: str
-    type: str                      # Convolution | Pooling | ReLU | LRN | Dropout | Concat
+    type: str                      # Convolution | Pooling | ReLU | LRN | Dropout | Concat | BatchNorm | Scale | Eltwise
     bot: str
     top: str
     out_chans: int = 0
@@ -44,7 +46,8 @@ class PipeOp:
     in_pad: Tuple[int, int] = (0, 0)
     avg_pool: int = 0
     lrn: Tuple[int, float, float, float] = (5, 1.0, 0.75, 1.0)  # local_size, alpha, beta, k (src/conv_util.cc:42-48)
-    bots: Tuple[str, ...] = ()     # Concat: all inputs in channel order (bot == bots[0])
+    bots: Tuple[str, ...] = ()     # Concat: all inputs in channel order (bot == bots[0]); Eltwise: the 2 to 8 nodes that are summed, in that order
+    eps: float = 1e-5              # BatchNorm: added to the variance
 
     @property
     def in_place(self) -> bool:
@@ -97,6 +100,25 @@ class ConvPipe:
             if any((x.dsz("img"), x.dsz("y"), x.dsz("x")) != (B, H, W) for x in ds):
                 raise RtErr(f"pipe: concat {op.tag} of mismatched sizes")
             out = Dims.make("float", img=B, chan=sum(x.dsz("chan") for x in ds), y=H, x=W)
+        elif op.type in AFFINE_TYPES:      # inference BatchNorm (global stats) / Scale: one multiply-add per channel, in place (fold_affine)
+            if not op.in_place:
+                raise UnsupErr(f"pipe: {op.type} {op.tag} must work in place (top == bottom), as every such layer of the nets here does")
+            out = d
+            for sfx in AFFINE_TYPES[op.type]:
+                self.params[op.tag + sfx] = Dims.make("float", chan=C)
+        elif op.type == "Eltwise":         # SUM of 2 to 8 nodes of identical dims into a new node
+            if not 2 <= len(op.bots) <= 8:
+                raise UnsupErr(f"pipe: eltwise {op.tag} sums {len(op.bots)} nodes; 2 to 8 are summed")
+            if op.bot != op.bots[0]:
+                raise RtErr(f"pipe: eltwise {op.tag}: bot must be bots[0]")
+            for b in op.bots:
+                if b not in self.nodes:
+                    raise RtErr(f"pipe: eltwise {op.tag} reads unknown node {b!r}")
+                if self.nodes[b] != d:
+                    raise RtErr(f"pipe: eltwise {op.tag} of mismatched sizes")
+            if op.in_place or op.top in op.bots:
+                raise RtErr(f"pipe: eltwise {op.tag} must write a new node")
+            out = d
         else:
             raise UnsupErr(f"pipe: op type {op.type!r} has no forward kernel in this backend")
         if op.top in self.nodes and not op.in_place:
@@ -119,6 +141,66 @@ class ConvPipe:
 
     def out_node(self) -> str:
         return self.ops[-1].top
+
+
+# the per-channel params of the affine op types, already in the form the formula reads: BatchNorm's mean / var are divided by Caffe's scale factor
+AFFINE_TYPES = {"BatchNorm": ("_mean", "_var"), "Scale": ("_scale", "_bias")}
+
+
+def fold_affine(steps) -> Tuple[np.ndarray, np.ndarray]:
+    """A run of in-place BatchNorm / Scale ops on one node as ONE per-channel pair (a, b): node' = node * a + b.  `steps`, in op order: ("BatchNorm", mean, var, eps)
+    or ("Scale", scale, bias).  All arithmetic is fp32 numpy, every operation rounded: from (1, 0), each step (a2, b2) gives a' = a2 * a and b' = a2 * b + b2
+    (a multiply, then an add); BatchNorm is a2 = 1 / sqrt(var + eps), b2 = -(mean * a2), Scale is (scale, bias).  The ONE definition of the fold: hip_chan_affine
+    takes (a, b) on fp32 nets, the channels-last bf16 nets take them into the convolution in front."""
+    f32 = np.float32
+    a = b = None
+    for st in steps:
+        if st[0] == "BatchNorm":
+            mean, var = np.asarray(st[1], f32), np.asarray(st[2], f32)
+            a2 = f32(1.0) / np.sqrt(var + f32(st[3]), dtype=f32)
+            b2 = -(mean * a2)
+        elif st[0] == "Scale":
+            a2, b2 = np.asarray(st[1], f32), np.asarray(st[2], f32)
+        else:
+            raise RtErr(f"fold_affine: {st[0]!r} is neither BatchNorm nor Scale")
+        if a is None:
+            a, b = np.ones(a2.shape, f32), np.zeros(a2.shape, f32)
+        if a2.shape != a.shape or b2.shape != a.shape or a2.ndim != 1:
+            raise RtErr("fold_affine: every param holds one value per channel")
+        a, b = a2 * a, a2 * b + b2
+    if a is None:
+        raise RtErr("fold_affine: no steps")
+    return a.astype(f32), b.astype(f32)
+
+
+def default_affine_param(pn: str, n: int) -> np.ndarray:
+    """What an affine param holds when the caller passes none (the reference ships no trained weights): a fixed pattern near the identity -- mean in
+    [-0.03, 0.03], var in [1, 1.2], scale in [0.96, 1], bias in [-0.02, 0.02]."""
+    c = np.arange(n, dtype=np.float32)
+    if pn.endswith("_mean"):
+        return ((c % 7) - 3) * np.float32(0.01)
+    if pn.endswith("_var"):
+        return 1 + (c % 5) * np.float32(0.05)
+    if pn.endswith("_scale"):
+        return 1 - (c % 3) * np.float32(0.02)
+    return ((c % 5) - 2) * np.float32(0.01)
+
+
+def affine_runs(cp: "ConvPipe") -> List[dict]:
+    """The maximal runs of consecutive in-place BatchNorm / Scale ops on one node, in op order: {"ops": the run, "relu": the in-place ReLU directly behind it or
+    None, "conv": the Convolution directly in front that writes the node, or None}."""
+    runs, i, ops = [], 0, cp.ops
+    while i < len(ops):
+        if ops[i].type not in AFFINE_TYPES:
+            i += 1; continue
+        j = i
+        while j < len(ops) and ops[j].type in AFFINE_TYPES and ops[j].bot == ops[i].bot:
+            j += 1
+        relu = ops[j] if (j < len(ops) and ops[j].type == "ReLU" and ops[j].in_place and ops[j].bot == ops[i].bot) else None
+        conv = ops[i - 1] if (i > 0 and ops[i - 1].type == "Convolution" and ops[i - 1].top == ops[i].bot) else None
+        runs.append({"ops": ops[i:j], "relu": relu, "conv": conv})
+        i = j
+    return runs
 
 
 class DryRtc:
@@ -206,6 +288,36 @@ def alexnet_ng_conv(batch: int, in_hw: int = 227) -> ConvPipe:
     n = _conv(p, "fc6", "pool5", 4096, 6); p.add(PipeOp("drop6", "Dropout", n, n))
     n = _conv(p, "fc7", n, 4096, 1); p.add(PipeOp("drop7", "Dropout", n, n))
     p.add(PipeOp("fc8", "Convolution", n, "fc8", out_chans=1000, kern_sz=(1, 1)))
+    return p
+
+
+def resnet50(batch: int, in_hw: int = 224) -> ConvPipe:
+    """nets/resnet-50/train_val.prototxt (TEST phase), Caffe's node and layer names: conv1 7x7/2 (+ bn_conv1, scale_conv1, ReLU), pool1 max 3x3/2, stages 2 .. 5 of
+    [3, 4, 6, 3] bottleneck blocks, pool5 (global average), fc1000.  A block: branch2a 1x1 -> branch2b 3x3 -> branch2c 1x1 (x4 channels), every convolution followed
+    by BatchNorm + Scale, 2a and 2b by a ReLU as well; res<s><b> = ReLU(shortcut + branch2c), the shortcut being the block's input or, in a stage's first block, the
+    projection branch1 (1x1; strided, like branch2a, from stage 3 on).  Every convolution keeps a _biases param (zero where the prototxt says bias_term: false)."""
+    p = ConvPipe("resnet50", "data", Dims.make("float", img=batch, chan=3, y=in_hw, x=in_hw))
+    def cbs(tag, bn, bot, oc, k, s=1, pad=0, relu=True):
+        p.add(PipeOp(tag, "Convolution", bot, tag, out_chans=oc, kern_sz=(k, k), stride=(s, s), in_pad=(pad, pad)))
+        p.add(PipeOp("bn" + bn, "BatchNorm", tag, tag)); p.add(PipeOp("scale" + bn, "Scale", tag, tag))
+        if relu:
+            p.add(PipeOp(tag + "_relu", "ReLU", tag, tag))
+        return tag
+    cbs("conv1", "_conv1", "data", 64, 7, 2, 3)
+    p.add(PipeOp("pool1", "Pooling", "conv1", "pool1", kern_sz=(3, 3), stride=(2, 2)))
+    n = "pool1"
+    for stage, blocks in zip((2, 3, 4, 5), (3, 4, 6, 3)):
+        mid = 64 << (stage - 2)
+        for bi in range(blocks):
+            blk = f"{stage}{'abcdef'[bi]}"; s = 2 if (bi == 0 and stage > 2) else 1
+            short = cbs(f"res{blk}_branch1", f"{blk}_branch1", n, 4 * mid, 1, s, relu=False) if bi == 0 else n
+            t = cbs(f"res{blk}_branch2a", f"{blk}_branch2a", n, mid, 1, s)
+            t = cbs(f"res{blk}_branch2b", f"{blk}_branch2b", t, mid, 3, 1, 1)
+            t = cbs(f"res{blk}_branch2c", f"{blk}_branch2c", t, 4 * mid, 1, relu=False)
+            n = f"res{blk}"
+            p.add(PipeOp(n, "Eltwise", short, n, bots=(short, t))); p.add(PipeOp(n + "_relu", "ReLU", n, n))
+    p.add(PipeOp("pool5", "Pooling", n, "pool5", kern_sz=None, avg_pool=1))
+    p.add(PipeOp("fc1000", "Convolution", "pool5", "fc1000", out_chans=1000, kern_sz=(0, 0)))
     return p
 
 
@@ -405,8 +517,14 @@ class ConvPipeFwd:
     mode = "rtc"
 
     def __init__(self, rtc: HipCompute, op_tune: Optional[OpTune] = None, per_call_fn: str = "", enable_double_run: bool = False, fuse_siblings: bool = True, fuse_levels: bool = True, fuse_pools: bool = True, sets_take_groups: bool = True,
-                 spec_fwd: bool = True, fuse_pool_lrn="pool_first", fuse_k1_chains: bool = True, fuse_f32_pools: Optional[bool] = None, fuse_post: bool = True, filts_kmajor_once: bool = True):
+                 spec_fwd: bool = True, fuse_pool_lrn="pool_first", fuse_k1_chains: bool = True, fuse_f32_pools: Optional[bool] = None, fuse_post: bool = True, filts_kmajor_once: bool = True,
+                 fuse_residual: bool = True):
         self.rtc, self.op_tune = rtc, op_tune or OpTune()
+        # channels-last bf16 nets: an Eltwise of two nodes (a ResNet block's res = ReLU(shortcut + branch2c)) is taken into the epilogue of the convolution that writes its
+        # later-defined bottom (nhwc.fuse_residual, kernels/conv_nhwc_bf16.hip -DRES=1): the shortcut is read once, the convolution's own output is never written or read
+        # again, the Eltwise and its ReLU emit no call.  False: every Eltwise runs as nhwc_eltwise.  No net without an Eltwise is touched either way
+        self.fuse_residual = fuse_residual
+        self.fused_residuals: Dict[str, object] = {"folded": [], "unfolded": {}}     # tags of the Eltwise ops taken into a convolution | tag -> why not
         # fp32 nets (round 6): a convolution whose plan reads its filters k-major gets that copy made once per set of weights (hip_conv_filts_kmajor, refresh_group_params())
         # instead of in front of every call -- seven launches less per NiN pass.  Bit-identical (the same transposition kernel, the same bytes); BODAHIP_FILTS_KM_ONCE=off: per call
         self.filts_kmajor_once = filts_kmajor_once and os.environ.get("BODAHIP_FILTS_KM_ONCE") != "off"
@@ -486,6 +604,40 @@ class ConvPipeFwd:
                 has_relu[op.tag] = hr
                 if hr:
                     fused.add(nxt.tag)
+        # BatchNorm / Scale runs (fp32 nets): ONE hip_chan_affine call at the run's first op, with the in-place ReLU behind the run taken into it; the run's other ops
+        # and that ReLU emit no call.  A convolution in front of a run keeps its own ReLU flag at 0 (its successor is the BatchNorm), so the conv's bits and the
+        # affine's bits are each those of their written formula -- nothing is folded into the filters on this path
+        self._runs = affine_runs(cp)
+        run_of: Dict[str, dict] = {r["ops"][0].tag: r for r in self._runs}
+        # Channels-last bf16 nets: every run is FOLDED into the convolution directly in front of it (filts' = filts * a per out_chan in fp32, then the usual layout
+        # pass and bf16 rounding; biases' = biases * a + b: refresh_group_params()), the ReLU behind the run fuses into that convolution as a conv's own ReLU does; no op of
+        # the run emits a call.  There is no channels-last affine kernel: a run with no convolution in front is refused
+        conv_fold: Dict[str, dict] = {}       # convolution tag -> the run folded into it
+        elt_relu: Dict[str, PipeOp] = {}      # Eltwise tag -> the in-place ReLU directly behind it (taken into whatever forms the sum)
+        if self.nhwc:
+            for r in self._runs:
+                if r["conv"] is None:
+                    raise UnsupErr(f"channels-last bf16 nets: {r['ops'][0].type} {r['ops'][0].tag} does not directly follow a convolution: there is nothing to fold it into (fp32 nets run it as hip_chan_affine)")
+                conv_fold[r["conv"].tag] = r
+                fused.update(o.tag for o in r["ops"])
+                if r["relu"] is not None:
+                    has_relu[r["conv"].tag] = 1; fused.add(r["relu"].tag)
+            for i, o in enumerate(cp.ops):
+                if o.type != "Eltwise":
+                    continue
+                if len(o.bots) != 2:
+                    raise UnsupErr(f"channels-last bf16 nets: Eltwise {o.tag} sums {len(o.bots)} nodes; nhwc_eltwise and the residual epilogue take two")
+                nxt = cp.ops[i + 1] if i + 1 < len(cp.ops) else None
+                if nxt is not None and nxt.type == "ReLU" and nxt.in_place and nxt.bot == o.top:
+                    elt_relu[o.tag] = nxt; fused.add(nxt.tag)
+        else:
+            for r in self._runs:
+                fused.update(o.tag for o in r["ops"][1:])
+                if r["relu"] is not None:
+                    fused.add(r["relu"].tag)
+        self._conv_folds: List[Tuple[str, list]] = [(t, [(o.type, o.tag, o.eps) for o in r["ops"]]) for t, r in conv_fold.items()]
+        elt_tops = {o.top for o in cp.ops if o.type == "Eltwise"}
+        self._affine_params: List[Tuple[str, str, list]] = []     # (var of a, var of b, [(type, tag, eps)] of the run): refresh_group_params() folds the params into them
         # Concat elimination: a Concat input that is produced by a convolution and read by nothing but the Concat is never
         # materialised -- the conv writes its channel range of the Concat output directly (hip_conv's out_chan_off), which removes
         # the channel-offset copy the reference makes per input (src/rtc_fwd.cc:267-280) and one tensor round trip through HBM
@@ -529,6 +681,53 @@ class ConvPipeFwd:
                 s2d_ok = self.nhwc and len(in_readers) == 1 and in_readers[0] is o
                 annos[o.tag] = add_codegen_annotations(cp.conv_op(o), dataclasses.replace(self.op_tune, hip_s2d=int(s2d_ok)) if self.nhwc else self.op_tune)
         in_anno = annos[in_readers[0].tag] if (self.nhwc and len(in_readers) == 1 and in_readers[0].type == "Convolution") else None
+        # residual folds (channels-last bf16 nets; see fuse_residual): decided per Eltwise, in op order.  The convolution `q` that writes the LATER-defined bottom takes the
+        # sum when it is a plain implicit-GEMM call without a ReLU of its own, the Eltwise alone reads its output, the other bottom (`res`) is final where q runs -- q's call
+        # is emitted at q's own position and reads res there -- and the planner accepts the flagged function.  q then writes the Eltwise's top; q's own node does not exist
+        res_fold: Dict[str, Tuple[PipeOp, str]] = {}     # convolution tag -> (the Eltwise, the node that is res)
+        self._res_nodes: Dict[str, str] = {}             # node of a flagged convolution (never materialised) -> the Eltwise top it is part of
+        if self.nhwc:
+            from .rtc import explain_plan
+            pos = {o.tag: i for i, o in enumerate(cp.ops)}
+            producer: Dict[str, PipeOp] = {o.top: o for o in cp.ops if not o.in_place}
+            for e in cp.ops:
+                if e.type != "Eltwise":
+                    continue
+                why, q, other, fa = None, None, None, None
+                if not self.fuse_residual:
+                    why = "fuse_residual is off"
+                elif e.bots[0] == e.bots[1]:
+                    why = f"both bottoms are the node {e.bots[0]}"
+                else:
+                    later = max(e.bots, key=lambda b: pos[producer[b].tag] if b in producer else -1)
+                    other = e.bots[1] if later == e.bots[0] else e.bots[0]
+                    q = producer.get(later)
+                    rd = [o for o in cp.ops if o.tag not in fused and later in (o.bots or (o.bot,))]
+                    if q is None or q.type != "Convolution":
+                        why = f"its later-defined bottom {later} is " + ("the net's input" if q is None else f"written by {q.tag}, a {q.type}")
+                    elif has_relu[q.tag]:
+                        why = f"{q.tag} has a ReLU of its own in front of the sum"
+                    elif rd != [e]:
+                        why = f"{later} is also read by {', '.join(o.tag for o in rd if o is not e)}"
+                    elif later in self.slices or q.tag in res_fold:
+                        why = f"{q.tag} writes a channel range of a Concat output"
+                    elif any(o.tag not in fused and o.top == other for o in cp.ops[pos[q.tag]:pos[e.tag]]):
+                        why = f"{other} is rewritten between {q.tag} and the sum"
+                    elif cp.nodes[e.top].dsz("chan") % 8:
+                        why = f"{cp.nodes[e.top].dsz('chan')} channels are no multiple of 8: the stored row is wider than what {q.tag} writes (an output channel slice)"
+                    else:
+                        try:
+                            fa = annos[q.tag].copy(); fa.nda_vals["conv_has_relu"].v = (int(e.tag in elt_relu),)
+                            _nhwc.fuse_residual(fa)
+                            explain_plan(fa, getattr(self, "_num_cus", 256))
+                        except (UnsupErr, RtErr) as ex:
+                            why = str(ex)
+                if why is not None:
+                    self.fused_residuals["unfolded"][e.tag] = why
+                    continue
+                annos[q.tag] = fa; res_fold[q.tag] = (e, other); has_relu[q.tag] = int(e.tag in elt_relu); self._res_nodes[q.top] = e.top
+                self.fused_residuals["folded"].append(e.tag)
+        elt_folded = {e.tag for e, _ in res_fold.values()}
         # 1x1 -> 1x1 chains (fp32 nets; see fuse_k1_chains): first conv's output (after its fused ReLU) read by the second conv and nothing else, both plain hip_conv
         # functions without a tile of their own, the pair covered by the chain kernel, and a layer the streaming kernels are measured ahead on (long pel axis)
         chain_first: Dict[str, PipeOp] = {}    # tag of the second conv -> the first conv
@@ -688,7 +887,7 @@ class ConvPipeFwd:
         if self.nhwc and self.fuse_siblings:
             by_key: Dict[tuple, List[PipeOp]] = {}
             for o in cp.ops:
-                if o.type == "Convolution" and not annos[o.tag].has("nhwc_s2d") and not annos[o.tag].get_dims("filts").has("in_grp"):
+                if o.type == "Convolution" and not annos[o.tag].has("nhwc_s2d") and not annos[o.tag].get_dims("filts").has("in_grp") and o.tag not in res_fold:
                     by_key.setdefault((o.bot, tuple(o.kern_sz), tuple(o.stride), tuple(o.in_pad), has_relu[o.tag]), []).append(o)
             for members0 in by_key.values():
                 for members in sibling_runs(cp.ops, members0, fused):
@@ -725,7 +924,13 @@ class ConvPipeFwd:
                 if not op.in_place:
                     alias[op.top] = vn(op.bot)
                 continue
-            if not op.in_place and op.top not in made and op.top not in self.slices:
+            if op.tag in elt_folded:           # the sum is formed by the convolution that wrote its later-defined bottom: no call
+                continue
+            if op.tag in res_fold:             # a flagged convolution writes the Eltwise's top; its own node is never materialised
+                etop = res_fold[op.tag][0].top
+                if etop not in made:
+                    rtc.create_var_with_dims(etop, vd(etop)); self._vars.append(etop); made.add(etop)
+            elif not op.in_place and op.top not in made and op.top not in self.slices:
                 rtc.create_var_with_dims(op.top, vd(op.top)); self._vars.append(op.top); made.add(op.top)
             if op.type == "Convolution" and op.tag in group_of:
                 grp = group_of[op.tag]
@@ -760,9 +965,15 @@ class ConvPipeFwd:
                 anno = annos[op.tag]
                 anno.nda_vals["conv_has_relu"].v = (has_relu[op.tag],)
                 fn = anno.get_func_name(); gen_fn = f"{fn}__{cp.name}_{op.tag}"
-                rtc.compile([RtcFuncInfo(gen_fn, "", [a for a, _ in NATIVE_ARGS[fn]], anno)]); self._funcs.append(gen_fn)
+                rtc.compile([RtcFuncInfo(gen_fn, "", [a for a, _ in pipe_func_args(anno)], anno)]); self._funcs.append(gen_fn)
                 am = {"filts": RtcArg.var(op.tag + "_filts"), "biases": RtcArg.var(op.tag + "_biases"), "in": RtcArg.var(vn(conv_in.get(op.tag, op.bot))),
                       "stride": RtcArg.ref(anno.get_dims("stride")), "in_pad": RtcArg.ref(anno.get_dims("in_pad")), "out": RtcArg.var(op.top)}
+                if op.tag in res_fold:           # conv + shortcut [+ ReLU] as one call: res is the Eltwise's other bottom, out the Eltwise's top
+                    e, other = res_fold[op.tag]
+                    am["res"] = RtcArg.var(vn(other)); am["out"] = RtcArg.var(e.top)
+                    ftag = "+".join([op.tag, e.tag] + ([elt_relu[e.tag].tag] if e.tag in elt_relu else [])); annos[ftag] = anno
+                    self.fwd_calls.append(FwdCall(ftag, RtcFuncCall(gen_fn, am), fn, cop.flops()))
+                    continue
                 if op.top in self.slices:
                     cat, c_off, _ = self.slices[op.top]
                     am["out"] = RtcArg.var(cat); am["out_chan_off"] = _u32(c_off)
@@ -807,6 +1018,34 @@ class ConvPipeFwd:
                     self._km_params.append(RtcFuncCall(xfn, {"filts": am["filts"], "filts_km": RtcArg.var(kmv)}))
                     am["filts_km"] = RtcArg.var(kmv)
                 self.fwd_calls.append(FwdCall(op.tag, RtcFuncCall(gen_fn, am), fn, cop.flops()))
+            elif op.type in AFFINE_TYPES:      # the first op of a BatchNorm / Scale run: the whole run (and the ReLU behind it) as one native call, in place
+                r = run_of[op.tag]
+                fop = chan_affine_func_op(cp.nodes[op.top], int(r["relu"] is not None))
+                gen_fn = f"{CHAN_AFFINE_FUNC}__{cp.name}_{op.tag}"
+                rtc.compile([RtcFuncInfo(gen_fn, "", [a for a, _ in NATIVE_ARGS[CHAN_AFFINE_FUNC]], fop)]); self._funcs.append(gen_fn)
+                av, bv = op.tag + "_affine_a", op.tag + "_affine_b"
+                rtc.create_var_with_dims(av, fop.get_dims("a")); rtc.create_var_with_dims(bv, fop.get_dims("b")); self._vars += [av, bv]
+                self._affine_params.append((av, bv, [(o.type, o.tag, o.eps) for o in r["ops"]]))
+                am = {"in": RtcArg.var(vn(op.bot)), "a": RtcArg.var(av), "b": RtcArg.var(bv), "out": RtcArg.var(vn(op.top))}
+                self.fwd_calls.append(FwdCall("+".join(o.tag for o in r["ops"] + ([r["relu"]] if r["relu"] is not None else [])), RtcFuncCall(gen_fn, am), CHAN_AFFINE_FUNC))
+            elif self.nhwc and op.type == "Eltwise":     # one that no convolution took: the generic channels-last kernel, with the ReLU behind it
+                self.fwd_calls.append(FwdCall("+".join([op.tag] + ([elt_relu[op.tag].tag] if op.tag in elt_relu else [])),
+                                              _nhwc.eltwise_call(vn(op.bots[0]), vn(op.bots[1]), op.top, vd(op.top), int(op.tag in elt_relu)), "nhwc_eltwise"))
+            elif op.type == "Eltwise":         # the gradient pipe's hip_reduce: a sequential fp32 chain from +0 in the order of bots
+                d = cp.nodes[op.top]
+                rop = Op({"type": "Reduce", "func_name": "hip_reduce"}, dict({f"ins_{i}": Nda(d) for i in range(len(op.bots))}, out=Nda(d), ins_num=Nda(None, "uint32_t", (len(op.bots),))))
+                rop.reduce_geom()
+                gen_fn = f"hip_reduce__{cp.name}_{op.tag}"
+                rtc.compile([RtcFuncInfo(gen_fn, "", [a for a, _ in pipe_func_args(rop)], rop)]); self._funcs.append(gen_fn)
+                am = dict({f"ins_{i}": RtcArg.var(vn(b)) for i, b in enumerate(op.bots)}, out=RtcArg.var(op.top))
+                self.fwd_calls.append(FwdCall(op.tag, RtcFuncCall(gen_fn, am), "hip_reduce"))
+            elif (not self.nhwc) and op.type == "ReLU" and op.bot in elt_tops:     # out = in > 0 ? in : +0 is hip_zero_if_non_pos with the node as its own condition
+                d = cp.nodes[op.top]
+                zop = Op({"type": "ZeroIfNonPos", "func_name": "hip_zero_if_non_pos"}, {"in": Nda(d), "cond": Nda(d), "out": Nda(d)})
+                gen_fn = f"hip_zero_if_non_pos__{cp.name}_{op.tag}"
+                rtc.compile([RtcFuncInfo(gen_fn, "", [a for a, _ in NATIVE_ARGS["hip_zero_if_non_pos"]], zop)]); self._funcs.append(gen_fn)
+                v = RtcArg.var(vn(op.bot))
+                self.fwd_calls.append(FwdCall(op.tag, RtcFuncCall(gen_fn, {"in": v, "cond": v, "out": v}), "hip_zero_if_non_pos"))
             elif self.nhwc and op.tag in post_of:                   # taken into its convolution's launch (fuse_post): the pooling's node on demand (from the convolution's, on demand too); the LRN's is what that launch writes
                 if op.type == "Pooling":
                     self._lazy[op.top] = FwdCall(op.tag, _nhwc.pool_call(vn(op.bot), op.top, vd(op.bot), vd(op.top), op.kern_sz, op.stride, op.in_pad, int(op.avg_pool), rtc if self.spec_fwd else None), "nhwc_pool")
@@ -904,8 +1143,22 @@ class ConvPipeFwd:
         if self.nhwc and self.fuse_levels:
             self._fuse_level_sets(cp)
         # params: given arrays (copy_ndas_to_vars, src/rtc_fwd.cc:524) or the deterministic on-device pattern
+        aff_params = {o.tag + sfx for o in cp.ops if o.type in AFFINE_TYPES for sfx in AFFINE_TYPES[o.type]}
         for pn in self.op_param_names:
             dst = pn
+            if self.nhwc and (pn.endswith("_filts") or pn.endswith("_biases")) and pn[:pn.rfind("_")] in conv_fold:
+                # a convolution that takes a BatchNorm / Scale run: the params as given are kept (fp32, reference layout) in <param>_raw; what the call reads is folded from
+                # them in refresh_group_params() -- a caller who overwrites such a convolution's params later writes the _raw vars
+                dst = pn + "_raw"; rtc.create_var_with_dims(dst, cp.params[pn]); self._vars.append(dst)
+                if op_params is not None and pn in op_params:
+                    rtc.copy_nda_to_var(dst, op_params[pn])
+                else:
+                    rtc.run(gd.gen_call("Convolution", "filts" if pn.endswith("_filts") else "biases", dst, cp.params[pn], gen_mode, 0.0))
+                continue
+            if pn in aff_params:      # one float per channel, as given or the fixed near-identity pattern; folded into the calls' (a, b) below
+                n = cp.params[pn].dims_prod()
+                rtc.copy_nda_to_var(pn, np.ascontiguousarray(op_params[pn], np.float32).reshape(n) if (op_params is not None and pn in op_params) else default_affine_param(pn, n))
+                continue
             if self.nhwc and pn.endswith("_filts"):   # filters: uploaded / generated in the reference layout, transposed once (src/rtc_fwd.cc:229-243 does the same at init)
                 dst = pn + "_ref"; rtc.create_var_with_dims(dst, cp.params[pn])
             if op_params is not None and pn in op_params:
@@ -916,6 +1169,7 @@ class ConvPipeFwd:
             if dst != pn:
                 rtc.run(_nhwc.xpose_call("filts", dst, pn, cp.params[pn], pdims(pn), annos[pn[:-len("_filts")]])); rtc.finish_and_sync(); rtc.release_var(dst)
         rtc.finish_and_sync()
+        self._pdims = pdims
         self.refresh_group_params()
         rtc.release_per_call_id_data()
 
@@ -974,6 +1228,24 @@ class ConvPipeFwd:
         """Stacked filters / biases of the fused sibling convolutions, from the members' own (already transposed) params: init time only (and again after a
         caller overwrote params, e.g. a weight broadcast)."""
         rtc = self.rtc
+        for av, bv, steps in getattr(self, "_affine_params", []):     # the (a, b) of every BatchNorm / Scale run, from the run's params as they are on the device
+            sfx = lambda t, tag: [np.asarray(rtc.copy_var_to_nda(tag + x), np.float32).reshape(-1) for x in AFFINE_TYPES[t]]
+            a, b = fold_affine([(t, *sfx(t, tag), eps) if t == "BatchNorm" else (t, *sfx(t, tag)) for t, tag, eps in steps])
+            rtc.copy_nda_to_var(av, a); rtc.copy_nda_to_var(bv, b)
+        if self.nhwc and getattr(self, "_conv_folds", None):     # channels-last nets: the runs folded into their convolutions, from the _raw params (before the sibling groups stack them)
+            from . import nhwc as _nhwc
+            cp = self.cp
+            get = lambda vn_: np.asarray(rtc.copy_var_to_nda(vn_), np.float32)
+            for tag, steps in self._conv_folds:
+                prm = lambda t, tg: [get(tg + x).reshape(-1) for x in AFFINE_TYPES[t]]
+                a, b = fold_affine([(t, *prm(t, tg), eps) if t == "BatchNorm" else (t, *prm(t, tg)) for t, tg, eps in steps])
+                fn_, bn_ = tag + "_filts", tag + "_biases"
+                F = get(fn_ + "_raw").reshape(cp.params[fn_].sizes) * a[:, None, None, None]      # fp32, rounded once; the layout pass then rounds to bf16
+                Bv = get(bn_ + "_raw").reshape(-1) * a + b
+                tmp = fn_ + "_ref"
+                rtc.create_var_with_dims(tmp, cp.params[fn_]); rtc.copy_nda_to_var(tmp, np.ascontiguousarray(F, np.float32))
+                rtc.run(_nhwc.xpose_call("filts", tmp, fn_, cp.params[fn_], self._pdims(fn_), self._annos[tag])); rtc.finish_and_sync(); rtc.release_var(tmp)
+                rtc.copy_nda_to_var(bn_, np.ascontiguousarray(Bv, np.float32))
         for call in getattr(self, "_km_params", []):     # k-major filter copies of the staging-wave convolutions (filts_kmajor_once)
             rtc.run(call)
         for fv, bv, grp, tags in getattr(self, "_grp_params", []):
@@ -1012,6 +1284,8 @@ class ConvPipeFwd:
             c.call_id = rtc.run(c.rfc)
         rtc.finish_and_sync()
         for v in to_get_vns:
+            if v in getattr(self, "_res_nodes", {}):
+                raise RtErr(f"node {v!r} is never written: its convolution adds the shortcut in its epilogue and writes {self._res_nodes[v]!r} (ConvPipeFwd(fuse_residual=False) keeps it)")
             if v in self._lazy:      # (a fused pooling's output: no call of the pass writes it)
                 self._materialise(v)
             if v in self.slices:     # a conv output that only exists as a channel range of its Concat output
@@ -1095,7 +1369,7 @@ class ConvPipeFwd:
         deps: List[List[int]] = []
         for i, c in enumerate(self.fwd_calls):
             am = c.rfc.arg_map
-            rd = [am[a].n for a in am if (a in ("in", "inout") or (a.startswith("in_") and a[3:].isdigit())) and am[a].is_var()]   # (in_<m>: the members of a set)
+            rd = [am[a].n for a in am if (a in ("in", "inout", "cond", "res") or (a[:3] == "in_" and a[3:].isdigit()) or (a[:4] == "ins_" and a[4:].isdigit())) and am[a].is_var()]   # (in_<m>: the members of a set, nhwc_eltwise's two inputs; ins_<i>: hip_reduce's inputs; res: a flagged convolution's shortcut)
             outs = [a for a in am if (a in ("out", "inout") or (a.startswith("out_") and not a.startswith("out_chan_off"))) and am[a].is_var()]
             wr = [am[a].n for a in outs]
             if c.func == "nhwc_xpose_in":     # (the layout pass of the net's input: reads <in>_ref, writes <in>)
@@ -1142,6 +1416,7 @@ class ConvPipeFwd:
         for v in self._vars:
             rtc.release_var(v)
         self._funcs, self._vars, self.fwd_calls, self._grp_params, self.groups = [], [], [], [], []
-        self._km_params = []
+        self._km_params, self._affine_params, self._conv_folds, self._res_nodes = [], [], [], {}
+        self.fused_residuals = {"folded": [], "unfolded": {}}
         self.fused_post, self._lazy_pre = {}, {}
         self.k1_chains, self._lazy, self.fused_pools, self.fused_pool_lrn, self.level_sets, self.lds_pool_lrn = [], {}, {}, {}, [], set()   # (a second init() starts from a clean slate)

@@ -189,6 +189,18 @@ void reduce(float const *const *ins, int nin, float *out, long n) {   // a seque
     out[i] = v;
   }
 }
+// the forward pipe's BatchNorm / Scale runs: a multiply, then an add (two roundings: contraction is off here); relu: x > 0 ? x : +0.  in == out is fine
+void chan_affine(float const *in, float const *a, float const *b, float *out, long B, long C, long HW, bool relu) {
+#pragma omp parallel for schedule(static)
+  for (long pl = 0; pl < B * C; ++pl) {
+    float const av = a[pl % C], bv = b[pl % C];
+    for (long i = pl * HW; i < (pl + 1) * HW; ++i) {
+      float v = in[i] * av;
+      v = v + bv;
+      out[i] = (relu && !(v > 0.0f)) ? 0.0f : v;
+    }
+  }
+}
 void dropout(float *inout, long n, float ratio, uint32_t seed) {
   float const scale = (float)(1.0 / (1.0 - (double)ratio));
   uint32_t const thresh = (uint32_t)((float)0xffffffffu * ratio);
@@ -314,6 +326,7 @@ struct cpu_compute_t : public rtc_compute_t {
       {"hip_dropout", "Dropout", {}, {"inout"}, false},    // (also BckDropout's)
       {"hip_concat", "Concat", {"in"}, {"out"}, false},
       {"hip_split", "Split", {"in"}, {"out"}, false},
+      {"hip_chan_affine", "ChanAffine", {"in", "a", "b"}, {"out"}, false},
     };
     for (auto const &d : tab) if (fn == d.fn) return &d;
     return nullptr;
@@ -335,7 +348,7 @@ struct cpu_compute_t : public rtc_compute_t {
       string const fn = fi.op.has_func_name() ? fi.op.get_func_name() : string();
       if (!is_sgemm(fn) && !is_conv(fn) && !is_bck(fn) && !find_bck_op(fn))
         unsup_err("be=cpu runs the native sgemm / Convolution / BckConv functions and the gradient pipe's non-conv functions only (hip_sgemm, hip_conv and their aliases, hip_bconv_*, "
-                  "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs, hip_reduce, hip_dropout, hip_concat, hip_split); '" +
+                  "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs, hip_reduce, hip_dropout, hip_concat, hip_split, hip_chan_affine); '" +
                                                     (fn.empty() ? fi.func_name : fn) + "' is generated CUCL source, which needs a GPU backend");
       if (is_conv(fn)) (void)fi.op.get_u32("conv_has_relu");
       (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
@@ -570,6 +583,13 @@ struct cpu_compute_t : public rtc_compute_t {
         seed += *(uint32_t const *)must_find(vis, wi->second.n).buf.get();
       }
       dropout(out[0], (long)get_var_dims(var_of(am, "inout")).dims_prod(), ratio, seed);
+    } else if (fn == "hip_chan_affine") {
+      dims_t const &i4 = op.get_dims("in");
+      if (i4.sz() != 4 || !(op.get_dims("out") == i4)) rt_err(fn + ": in and out must be img:chan:y:x tensors of equal dims");
+      for (char const *an : {"a", "b"}) if (op.get_dims(an).sz() != 1 || op.get_dims(an).dims(0) != i4.dims(1)) rt_err(fn + ": " + an + " dims " + op.get_dims(an).pretty_str() + ": one float per channel of in " + i4.pretty_str());
+      uint32_t const relu = op.get_u32("relu");
+      if (relu > 1) rt_err(fn + ": relu must be 0 | 1");
+      chan_affine(in[0], in[1], in[2], out[0], n_img, (long)i4.dsz("chan"), (long)i4.dsz("y") * i4.dsz("x"), relu != 0);
     } else if (fn == "hip_concat" || fn == "hip_split") {
       bool const cat = fn == "hip_concat";
       dims_t const &i4 = op.get_dims("in"), &o4 = op.get_dims("out");

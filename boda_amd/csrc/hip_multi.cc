@@ -343,7 +343,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
       // non-conv functions (hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax) are independent per image and run on img shards
       if (nat && n() > 1 && fi.op.get_func_name() == "hip_sm_grad_and_loss") func_img_sum[fi.func_name] = "(the softmax loss gradient) divides by the GLOBAL image count, which an img shard does not know; hip_softmax runs on img shards";
       if (nat && n() > 1 && fi.op.get_func_name() == "hip_sum_loss_over_imgs") func_img_sum[fi.func_name] = "(the softmax loss) sums loss_per_pel over ALL images, which would need a cross-device reduction; hip_softmax runs on img shards";
-      // hip_reduce / hip_concat / hip_split are independent per image and run on img shards; hip_dropout hashes the element's index in the WHOLE tensor
+      // hip_reduce / hip_concat / hip_split / hip_chan_affine are independent per image and run on img shards (a and b, one value per channel, are whole on every device); hip_dropout hashes the element's index in the WHOLE tensor
       if (nat && n() > 1 && fi.op.get_func_name() == "hip_dropout") func_img_sum[fi.func_name] = "(dropout) hashes every element's GLOBAL flat index, which an img shard does not know; hip_reduce / hip_concat / hip_split run on img shards";
       if (!nat) func_gen[fi.func_name] = scan_gen_func(all_src, fi.func_name);
     }

@@ -52,10 +52,14 @@
 // OP 11 bodahip_concat / OP 12 bodahip_split  (the reference's copy calls, src/rtc_fwd.cc:267-294)   in -> out: an img:chan:y:x tensor copied into (11) / out of (12)
 //   the channel range [cix, cix + chan) of a wider one.  Per image that range is one run of `run` = chan * y * x consecutive floats, `wide` = the wider tensor's
 //   floats per image, `off` = cix * y * x
+// OP 13 bodahip_chan_affine  (this backend's own: an inference BatchNorm / Scale run of the forward pipe, conv_pipe.fold_affine)   in, a, b -> out
+//   * out[i,c,y,x] = in[i,c,y,x] * a[c] + b[c]: an fp32 multiply, then an fp32 add, two roundings; RELU=1 (the op's relu): x > 0 ? x : +0 on that sum, so -0 and a NaN give +0
+//   * a thread owns one quad or one tail element of one plane, loads before it stores and touches nothing else: in and out may be the same buffer
+//   * n4 counts the float4 quads of ONE plane here (0 unless both pointers are 16-byte aligned and HW is a multiple of 4), the elements behind them are scalars
 // OP 9 .. 12 take float4 over the first n4 quads and scalars over the tail, like OP 5; the host sets n4 = 0 unless every pointer (11, 12: every per-image run) is
 // 16-byte aligned.  Quads never straddle a run: 11 / 12 use them only when run, wide and off are multiples of 4.
 //
-// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN | 2, 4: [ZINP] | 10: [SEEDVAR].  Host side: plan_bck_op (native_plan.cc), native_kernels.cc.
+// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN | 2, 4: [ZINP] | 10: [SEEDVAR] | 13: RELU.  Host side: plan_bck_op (native_plan.cc), native_kernels.cc.
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -351,6 +355,35 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
 #endif
 }
 
+#elif OP == 13
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float affine1(float x, float a, float b) {
+  float v = x * a;
+  v = v + b;
+#if RELU
+  v = v > 0.0f ? v : 0.0f;
+#endif
+  return v;
+}
+extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) {
+  long const id = (long)blockIdx.x * 256 + threadIdx.x;   // (plane, unit of the plane): n4 quads, then HW - 4 n4 single elements
+  if (id >= p.n) return;
+  int const units = p.n4 + (p.HW - 4 * p.n4);
+  long const plane = id / units;
+  int const u = (int)(id - plane * units);
+  int const c = (int)(plane % p.C);
+  float const a = p.p1[c], b = p.p2[c];
+  long const base = plane * p.HW;
+  if (u < p.n4) {
+    f32x4 v = ((f32x4 const *)(p.p0 + base))[u];
+    v.x = affine1(v.x, a, b); v.y = affine1(v.y, a, b); v.z = affine1(v.z, a, b); v.w = affine1(v.w, a, b);
+    ((f32x4 *)(p.o0 + base))[u] = v;
+  } else {
+    long const e = base + 4L * p.n4 + (u - p.n4);
+    p.o0[e] = affine1(p.p0[e], a, b);
+  }
+}
+
 #else
-#error "bck_ops_f32.hip: -DOP=1..12"
+#error "bck_ops_f32.hip: -DOP=1..13"
 #endif

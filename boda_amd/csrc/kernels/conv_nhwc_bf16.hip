@@ -29,7 +29,7 @@
 // Numerics: bf16 products are exact in fp32; the MFMA sums 16 of them per instruction in an order of its own, so results are NOT
 // bit-comparable with a CPU loop; parity is stated against the oracle fed the same bf16 operands (tests), unpinned by construction.
 //
-// -D parameters: KNAME BI BJ BK(32|64; f32: 16|32) WI WJ MINW CIN KH KW SY SX PY PX CH CW COH COW RELU OUT_F32 NBUF(2..8) [IN_F32 SPLITK KSL]
+// -D parameters: KNAME BI BJ BK(32|64; f32: 16|32) WI WJ MINW CIN KH KW SY SX PY PX CH CW COH COW RELU OUT_F32 NBUF(2..8) [IN_F32 SPLITK KSL RES]
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -40,6 +40,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef GROUP_I
 #define GROUP_I 8
@@ -69,6 +70,16 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                  // LAST ticket of its tile acquires, sums the KSL slabs in slice order -- the same order whoever arrives last: run-to-run deterministic --, resets the
                  // ticket for the next launch / graph replay, and runs the ordinary epilogue.  One kernel, no second launch, no shared scratch: legal for members of a
                  // hip_conv_nhwc_set and for calls that overlap in an edge-free graph.  For tile-starved layers with a long K (7x7 / 14x14 maps at 64 images).
+#ifndef RES
+#define RES 0    // 1: RESIDUAL EPILOGUE (a ResNet block's res = ReLU(shortcut + branch2c), the function op's nhwc_residual=1).  The kernel takes a second argument `res`, a
+#endif           // tensor of exactly out's dims and element type (bf16, or float with OUT_F32), and writes  out = cvt( relu( (acc + bias) + float(res) ) ): the fp32 sum is
+                 // formed in the accumulator layout BEFORE the one rounding to the output type -- the convolution's own result is never rounded on its way into the
+                 // sum -- and the ReLU (RELU) applies to the sum.  A lane's register quad is 4 consecutive out_chans of one pel, so its part of `res` is ONE 8-byte
+                 // (bf16) / 16-byte (float) buffer load.  The loads of a column of the tile are issued together in front of that column's first store (a load issued
+                 // between stores would wait for every earlier store) and they are unconditional: a lane outside the tensor (ragged pel / out_chan tiles) loads from
+                 // an offset past the descriptor and gets zero, it stores nothing anyway.  Row pitches that are no multiple of 4 channels take element loads, a
+                 // workgroup-uniform choice.  With KSL > 1 the workgroup that arrives last runs this epilogue on the summed slabs like any other.  `res` is read, never
+                 // written, and must not be the tensor the launch writes (the host refuses): a tile's loads then depend on nothing another workgroup stores.
 #ifndef ABLATE
 #define ABLATE 0   // measurement only (wrong results): 1 = no operand loads, 2 = no fragment reads / MFMAs, 3 = fragment reads but no MFMAs,
                    // 4 = no K loop at all (prologue + epilogue), 5 = return at once (launch floor), 6 = K loop but no epilogue
@@ -191,6 +202,9 @@ __device__ __forceinline__ rsrc_t make_rsrc(void const *p, unsigned bytes) { ret
 __device__ __forceinline__ constexpr int swz(int row) { return (row / kRP) & (kCPR - 1); }
 } // namespace
 
+#if RES && (defined(BODAHIP_AS_MEMBER) || GROUPS)
+#error "conv_nhwc_bf16.hip: the residual epilogue (RES) belongs to a plain launch, not to a set member or a sibling group"
+#endif
 #ifdef BODAHIP_AS_MEMBER
 static_assert(!SPLITK && !IN_F32, "a member of a set: one kernel (K slices only in their in-launch form, KSL)");
 constexpr int member_smem_bytes = kSmem, member_threads = WI * WJ * 64, member_minw = MINW;
@@ -198,6 +212,10 @@ __device__ __forceinline__ void KNAME(gemm_args_t const &p, grp_args_t const &q,
 #elif GROUPS
 static_assert(!SPLITK && !IN_F32, "fused convolutions: bf16 tensors, K slices only in their in-launch form (KSL)");
 extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(gemm_args_t const p, grp_args_t const q) {
+  __shared__ __attribute__((aligned(1024))) char smem[kSmem];
+#elif RES
+static_assert(!SPLITK && !IN_F32, "residual epilogue: bf16 operands, K slices only in their in-launch form (KSL)");
+extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(gemm_args_t const p, void const *const res) {
   __shared__ __attribute__((aligned(1024))) char smem[kSmem];
 #else
 extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(gemm_args_t const p) {
@@ -486,12 +504,38 @@ extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(gemm_args
         for (int e = 0; e < 4; ++e) bv[ta][g][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rB, (oc + e < e_Mi) ? (oc + e) * 4 : kOOB, 0, 0));
       }
     }
+#if RES
+  rsrc_t const rR = make_rsrc(res, p.D_bytes);               // (out's dims and element type)
+  bool const r_vec = ((o_ctot | o_coff) & 3) == 0;           // every quad of 4 consecutive out_chans is one aligned load (workgroup-uniform)
+#endif
 #if OUT_F32 || SPLITK
   // fp32 output (tests / the last layer of a net; the partial tiles of a K slice): 16-byte stores of 4 consecutive out_chans straight from the accumulator layout
 #pragma unroll
   for (int tb = 0; tb < kTJ; ++tb) {
     int const pel = j0 + wj * (kTJ * 32) + tb * 32 + (lane & 31);
     unsigned const rowoff = ((unsigned)pel * (unsigned)o_ctot + (unsigned)o_coff) * 4u;
+#if RES
+    float rv[kTI][4][4];   // this column's part of res: every load in front of the column's first store, one run of loads for the whole column
+    if (r_vec) {
+#pragma unroll
+      for (int ta = 0; ta < kTI; ++ta)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          int const oc = e_i0 + wi * (kTI * 32) + ta * 32 + 8 * g + 4 * h;
+          f32x4 const q4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rR, (pel < p.Nj && oc + 4 <= e_Mi) ? (int)(rowoff + (unsigned)oc * 4u) : kOOB, 0, 0));
+          rv[ta][g][0] = q4[0]; rv[ta][g][1] = q4[1]; rv[ta][g][2] = q4[2]; rv[ta][g][3] = q4[3];
+        }
+    } else {
+#pragma unroll
+      for (int ta = 0; ta < kTI; ++ta)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          int const oc = e_i0 + wi * (kTI * 32) + ta * 32 + 8 * g + 4 * h;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) rv[ta][g][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rR, (pel < p.Nj && oc + e < e_Mi) ? (int)(rowoff + (unsigned)(oc + e) * 4u) : kOOB, 0, 0));
+        }
+    }
+#endif
 #pragma unroll
     for (int ta = 0; ta < kTI; ++ta)
 #pragma unroll
@@ -499,7 +543,13 @@ extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(gemm_args
         int const oc = e_i0 + wi * (kTI * 32) + ta * 32 + 8 * g + 4 * h;
         float x[4];   // (scalars, not elements of a vector: this hipcc mis-compiles element-wise bit-casts of a vector's lanes -- DESIGN.md section 3.1)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { x[e] = acc[ta][tb][4 * g + e] + bv[ta][g][e]; if (kRelu) x[e] = (x[e] > 0.f) ? x[e] : 0.f; }
+        for (int e = 0; e < 4; ++e) {
+          x[e] = acc[ta][tb][4 * g + e] + bv[ta][g][e];
+#if RES
+          x[e] = x[e] + rv[ta][g][e];
+#endif
+          if (kRelu) x[e] = (x[e] > 0.f) ? x[e] : 0.f;
+        }
         if (pel < p.Nj) {
           if (oc + 4 <= e_Mi && ((o_ctot | o_coff) & 3) == 0) {
             f32x4 v; v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
@@ -517,13 +567,58 @@ extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(gemm_args
 #pragma unroll
     for (int tb = 0; tb < kTJ; ++tb) {
       int const prow = wj * (kTJ * 32) + tb * 32 + (lane & 31);
+#if RES
+      // this column's part of res, widened to fp32 (a bf16 is the upper half of its float): no global store of this workgroup has been issued yet
+      unsigned rw[kTI][4][2];   // (two bf16 per word, as they lie in memory)
+      {
+        int const pel = j0 + prow;
+        unsigned const rowoff = ((unsigned)pel * (unsigned)o_ctot + (unsigned)o_coff) * 2u;
+        if (r_vec) {   // one run of 8-byte loads for the whole column
+#pragma unroll
+          for (int ta = 0; ta < kTI; ++ta)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              int const oc = e_i0 + wi * (kTI * 32) + ta * 32 + 8 * g + 4 * h;
+              u32x2 const q2 = __builtin_amdgcn_raw_buffer_load_b64(rR, (pel < p.Nj && oc + 4 <= e_Mi) ? (int)(rowoff + (unsigned)oc * 2u) : kOOB, 0, 0);
+              unsigned const w0 = q2[0], w1 = q2[1];
+              rw[ta][g][0] = w0; rw[ta][g][1] = w1;
+            }
+        } else {
+#pragma unroll
+          for (int ta = 0; ta < kTI; ++ta)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              int const oc = e_i0 + wi * (kTI * 32) + ta * 32 + 8 * g + 4 * h;
+              unsigned w[4];
+#pragma unroll
+              for (int e = 0; e < 4; ++e) w[e] = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rR, (pel < p.Nj && oc + e < e_Mi) ? (int)(rowoff + (unsigned)(oc + e) * 2u) : kOOB, 0, 0);
+              rw[ta][g][0] = w[0] | (w[1] << 16); rw[ta][g][1] = w[2] | (w[3] << 16);
+            }
+        }
+      }
+      float rv[kTI][4][4];
+#pragma unroll
+      for (int ta = 0; ta < kTI; ++ta)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          rv[ta][g][0] = __builtin_bit_cast(float, rw[ta][g][0] << 16); rv[ta][g][1] = __builtin_bit_cast(float, rw[ta][g][0] & 0xffff0000u);
+          rv[ta][g][2] = __builtin_bit_cast(float, rw[ta][g][1] << 16); rv[ta][g][3] = __builtin_bit_cast(float, rw[ta][g][1] & 0xffff0000u);
+        }
+#endif
 #pragma unroll
       for (int ta = 0; ta < kTI; ++ta)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           bf16x4 v;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) { float x = acc[ta][tb][4 * g + e] + bv[ta][g][e]; if (kRelu) x = (x > 0.f) ? x : 0.f; v[e] = (__bf16)x; }
+          for (int e = 0; e < 4; ++e) {
+            float x = acc[ta][tb][4 * g + e] + bv[ta][g][e];
+#if RES
+            x = x + rv[ta][g][e];
+#endif
+            if (kRelu) x = (x > 0.f) ? x : 0.f;
+            v[e] = (__bf16)x;
+          }
           *reinterpret_cast<bf16x4 *>(E + prow * kEPitch + (wi * (kTI * 32) + ta * 32 + 8 * g + 4 * h) * 2) = v;
         }
     }

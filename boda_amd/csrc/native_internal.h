@@ -93,7 +93,7 @@ bool parse_tile(string const &s, tile_cfg_t &c);
 void launch(native_host_t *host, kernel_t &k, gemm_args_t &a, tile_cfg_t const &c);
 plan_t plan_sgemm(uint32_t M, uint32_t N, uint32_t K, int num_cus, string const &tile, bool bf16 = false, int batch = 1, bool allow_big = true);
 bool plan_patch_bf16(conv_geom_t const &g, int num_cus, plan_t &p);
-plan_t plan_conv_nhwc(conv_geom_t const &g, int num_cus, string const &tile, bool out_f32, int grp_pad = 0, bool allow_split = true);
+plan_t plan_conv_nhwc(conv_geom_t const &g, int num_cus, string const &tile, bool out_f32, int grp_pad = 0, bool allow_split = true, bool res = false);   // res: -DRES=1, the residual epilogue
 plan_t plan_conv_nhwc_patch(conv_geom_t const &g, int num_cus, string const &tile_arg, bool out_f32, bool pool = false);
 bool plan_conv_nhwc_rows(conv_geom_t const &g, post_ops_t const &post, int num_cus, plan_t &p, string *why = nullptr);
 bool rows_auto(conv_geom_t const &g, int num_cus, string const &tile);

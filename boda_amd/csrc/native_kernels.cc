@@ -40,6 +40,7 @@ bool native_kernels_t::is_native_func_name(string const &fn) {
 void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
   string const &fn = fi.op.get_func_name();
   if (fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "hip_sgemm_bf16") return;
+  (void)op_nhwc_residual_flag(fi.op);   // (refuses the flag on every function but a plain hip_conv_nhwc)
   if (fn == "hip_conv" || fn == "cudnn_conv" || fn == "hip_conv_bf16" || fn == "hip_conv_winograd" || fn == "hip_conv_nhwc" || fn == "hip_conv_nhwc_grp" || fn == "hip_conv_nhwc_multi" || fn == "hip_conv_nhwc_set") { (void)fi.op.get_u32("conv_has_relu"); return; } // required, as src/culibs-wrap.cc:198
   if (fn == "hip_conv_k1_chain") { (void)fi.op.get_u32("conv_has_relu"); (void)fi.op.get_u32("conv_has_relu2"); return; }
   if (fn == "hip_conv_filts_kmajor") return;
@@ -54,6 +55,7 @@ void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
     for (char const *an : d->outs) (void)fi.op.get_dims(an);
     if (d->op == 10) (void)fi.op.get("dropout_ratio");
     if (d->op == 11 || d->op == 12) (void)fi.op.get_u32(d->op == 11 ? "ocix" : "icix");
+    if (d->op == 13) (void)fi.op.get_u32("relu");
     if (d->refs) for (char const *an : {"kern_sz", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     return;
   }
@@ -799,7 +801,12 @@ void native_kernels_t::bck_op(bck_op_geom_t const &g, float const *const *ins, f
     }
     a.n4 = (al & 15) == 0 ? (int)(n / 4) : 0; a.n = (long)a.n4 + (n - 4L * a.n4);
   }
-  uint32_t const grid = quads ? (uint32_t)((a.n + 255) / 256) : bp.grid;
+  if (g.op == 13) {   // quads of a plane: both tensors 16-byte aligned and planes of whole quads, so that every plane starts on a quad
+    uintptr_t const al = (uintptr_t)ins[0] | (uintptr_t)outs[0];
+    a.n4 = ((al & 15) == 0 && (a.HW & 3) == 0) ? a.HW / 4 : 0;
+    a.n = g.B * (long)g.C * (a.n4 + (a.HW - 4 * a.n4));
+  }
+  uint32_t const grid = (quads || g.op == 13) ? (uint32_t)((a.n + 255) / 256) : bp.grid;
   void *params[] = {&a};
   if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, bp.block, params), "hipModuleLaunchKernel(bck_op)");
   last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = grid; last_launch.block = bp.block;

@@ -31,6 +31,7 @@
 //       hip_dropout             inout det_drop_seed(by-value uint32)          (Dropout and BckDropout)             test/rtc/dropout.cucl
 //                               with seed_from_var=1 in the op: inout det_drop_seed_var(uint32_t var, one element) det_drop_seed -- the hash seed is word + by-value
 //       hip_concat / hip_split  in out   (ocix / icix in the op: one call per input / output)                      src/rtc_fwd.cc:267-294
+//       hip_chan_affine         in a b out   (relu in the op; in and out may be one var)   out = in * a[chan] + b[chan], two roundings: the forward pipe's BatchNorm / Scale runs
 //     hip_conv_winograd                 same contract as hip_conv; 3x3 / stride-1 layers through F(2x2,3x3) Winograd (mrd <= ~2e-3)
 // and lands them on kernels/gemm_conv_f32.hip (and, for short-K 1x1 convs with a long pel axis, kernels/k1_stream_f32.hip),
 // specialised with hiprtc per shape class at first use.
@@ -85,13 +86,14 @@ struct conv_geom_t { int B, C, H, W, OC, KH, KW, SY, SX, PY, PX, OH, OW; bool re
 struct post_ops_t { int PKH = 0, PKW = 0, PSY = 1, PSX = 1, PPY = 0, PPX = 0, POH = 0, POW = 0, LRN_N = 0; float alpha = 0.f, beta = 0.f, k = 0.f; bool pooled() const { return PKH > 0; } };
 
 // one call of a non-conv gradient-pipe kernel (kernels/bck_ops_f32.hip): op = 1 pool_yx, 2 spreading, 3 lrn_sb, 4 bck_lrn, 5 zero_if_non_pos, 6 softmax, 7 sm_grad_and_loss,
-// 8 sum_loss_over_imgs, 9 reduce, 10 dropout, 11 concat, 12 split.  B images of C channels; H x W = the pooling's INPUT plane (LRN: the plane), OH x OW its output
+// 8 sum_loss_over_imgs, 9 reduce, 10 dropout, 11 concat, 12 split, 13 chan_affine (the forward pipe's; relu from the op).  B images of C channels; H x W = the pooling's INPUT plane (LRN: the plane), OH x OW its output
 // plane; n = elements (zero_if_non_pos, reduce, dropout).  reduce: nin inputs.  dropout: ratio from the op, seed from the
 // call.  concat / split: B images of the narrow tensor's C channels (planes H x W) at channels [cix, cix + C) of the wide tensor's CT
 struct bck_op_geom_t { int op = 0; long B = 0; int C = 0, H = 1, W = 1, OH = 1, OW = 1, KH = 1, KW = 1, SY = 1, SX = 1, PY = 0, PX = 0, avg = 0, LS = 1; float alpha = 0.f, beta = 0.f, k = 0.f; long n = 0;
   int nin = 0; float ratio = 0.f; uint32_t seed = 0; int CT = 0, cix = 0;
   int zinp = 0;      // spreading, bck_lrn: 1 = in_grad_loss = in > 0 ? value : +0 (the op's zero_if_in_non_pos; spreading then takes `in` as its fourth input)
-  int seedvar = 0; };   // dropout: 1 = the hash seed is the word of the call's det_drop_seed_var + seed (the op's seed_from_var)
+  int seedvar = 0;   // dropout: 1 = the hash seed is the word of the call's det_drop_seed_var + seed (the op's seed_from_var)
+  int relu = 0; };   // chan_affine: 1 = x > 0 ? x : +0 on the finished sum (the op's relu)
 
 struct launch_info_t { string kernel; tile_cfg_t cfg; uint32_t grid = 0, block = 0; double flops = 0, algo_bytes = 0; };
 
@@ -109,7 +111,7 @@ struct native_kernels_t {
 
   // channels-last bf16 tensors (kernels/conv_nhwc_bf16.hip): filts out_chan:y:x:in_chan, in / out img:y:x:chan; g.C = stored channels (multiple of 8)
   void conv_nhwc_rows(void const *filts, float const *biases, void const *in, void *out, conv_geom_t const &g, post_ops_t const &post, int out_ctot = 0, int out_coff = 0);   // F' filts; g.OH x g.OW = the convolution's own output planes
-  void conv_nhwc(void const *filts, float const *biases, void const *in, void *out, conv_geom_t const &g, bool out_f32, int out_ctot = 0, int out_coff = 0, bool patch_filts = false, bool pool = false);   // pool: g.KH x g.KW / g.PY, g.PX are a max-pooling window fused in front of 1x1 filters (patch form); patch_filts: filts are F'[in_grp][ky][kx][out_chan][8] -> the LDS input-patch kernel
+  void conv_nhwc(void const *filts, float const *biases, void const *in, void *out, conv_geom_t const &g, bool out_f32, int out_ctot = 0, int out_coff = 0, bool patch_filts = false, bool pool = false, void const *res = nullptr);   // res: the function op's nhwc_residual=1 -- a tensor of out's dims and type added in the epilogue before the one rounding (-DRES=1; implicit-GEMM kernel only); pool: g.KH x g.KW / g.PY, g.PX are a max-pooling window fused in front of 1x1 filters (patch form); patch_filts: filts are F'[in_grp][ky][kx][out_chan][8] -> the LDS input-patch kernel
   // horizontally fused channels-last convolutions (same `in`, same kernel geometry; filts / biases stacked along out_chan, members padded to `pad` rows)
   void conv_nhwc_grp(void const *filts, float const *biases, void const *in, conv_geom_t const &g, bool out_f32, int n, int const *noc, void *const *outs,
                      int const *ctot, int const *coff, int pad);

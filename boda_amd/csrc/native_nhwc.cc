@@ -353,14 +353,20 @@ void native_kernels_t::conv_nhwc_grp(void const *filts, float const *biases, voi
   last_launch.algo_bytes = 2.0 * ((double)g.B * g.C * g.H * g.W + real_oc * Kt) + (out_f32 ? 4.0 : 2.0) * (double)Nj * real_oc + 4.0 * real_oc;
 }
 
-void native_kernels_t::conv_nhwc(void const *filts, float const *biases, void const *in, void *out, conv_geom_t const &g, bool out_f32, int out_ctot, int out_coff, bool patch_filts, bool pool) {
+void native_kernels_t::conv_nhwc(void const *filts, float const *biases, void const *in, void *out, conv_geom_t const &g, bool out_f32, int out_ctot, int out_coff, bool patch_filts, bool pool, void const *res) {
   if (out_ctot <= 0) { out_ctot = g.OC; out_coff = 0; }
   if (pool && !patch_filts) rt_err("hip_conv_nhwc: fused pooling needs the patch form of filts");
+  if (res) {   // the residual epilogue exists in the implicit-GEMM kernel of a plain call, on a whole tensor
+    if (pool) unsup_err("hip_conv_nhwc: nhwc_residual=1 with a max pooling fused in front (POOL): that form runs on the input-patch kernel, which has no residual epilogue");
+    if (patch_filts) unsup_err("hip_conv_nhwc: nhwc_residual=1 with the in_grp:y:x:out_chan:in_chan8 form of filts: the input-patch and rolling-rows kernels have no residual epilogue");
+    if (out_ctot != g.OC || out_coff != 0) unsup_err("hip_conv_nhwc: nhwc_residual=1 on an output channel slice (out holds " + std::to_string(out_ctot) + " channels, the convolution writes " + std::to_string(g.OC) + "): res has out's dims, the sum is defined on whole tensors");
+    if (res == out) rt_err("hip_conv_nhwc: nhwc_residual=1: res and out are the same buffer");
+  }
   long const Nj = (long)g.B * g.OH * g.OW, Kt = pool ? (long)g.C : (long)g.C * g.KH * g.KW;
   if (!Nj || !g.OC) return;
   if (Nj > 0x7fffffffl || Kt > 0x7fffffffl) unsup_err("hip_conv_nhwc: dims exceed int32");
   if (patch_filts && !pool && !out_f32 && rows_auto(g, host->nh_num_cus(), tune_of(impl, "conv_tile"))) { conv_nhwc_rows(filts, biases, in, out, g, post_ops_t(), out_ctot, out_coff); return; }   // (output-bound stems)
-  plan_t const p = patch_filts ? plan_conv_nhwc_patch(g, host->nh_num_cus(), tune_of(impl, "conv_tile"), out_f32, pool) : plan_conv_nhwc(g, host->nh_num_cus(), tune_of(impl, "conv_tile"), out_f32);
+  plan_t const p = patch_filts ? plan_conv_nhwc_patch(g, host->nh_num_cus(), tune_of(impl, "conv_tile"), out_f32, pool) : plan_conv_nhwc(g, host->nh_num_cus(), tune_of(impl, "conv_tile"), out_f32, 0, true, res != nullptr);
   tile_cfg_t const &cfg = p.cfg;
   kernel_t &k = get_kernel(impl, host, p);
   gemm_args_t ga; memset(&ga, 0, sizeof(ga));
@@ -381,7 +387,7 @@ void native_kernels_t::conv_nhwc(void const *filts, float const *biases, void co
     ensure_ws(impl, host, slab * (size_t)cfg.SPLITK * sizeof(float));
     ga.splitk = cfg.SPLITK; ga.kt_per = (int)((nk + cfg.SPLITK - 1) / cfg.SPLITK); ga.ws = (float *)impl->ws; ga.ws_slab = (long)slab;
   }
-  void *params[] = {&ga};
+  void *params[] = {&ga, &res};   // (the plain kernel declares one argument and reads only that)
   hip_err_chk(host->nh_launch(k.func, (uint32_t)(ga.tiles_i * ga.tiles_j * ga.splitk), 1, (uint32_t)cfg.threads(), params), "hipModuleLaunchKernel(conv_nhwc_bf16)");
   if (cfg.SPLITK > 1 && !p.ksl) {
     plan_t rp; rp.nhwc = true; rp.bf16 = true; rp.kname = "bodahip_nhwc_splitk_reduce";
@@ -393,7 +399,7 @@ void native_kernels_t::conv_nhwc(void const *filts, float const *biases, void co
   }
   last_launch.kernel = p.kname; last_launch.cfg = cfg; last_launch.grid = (uint32_t)(ga.tiles_i * ga.tiles_j * ga.splitk); last_launch.block = cfg.threads();
   last_launch.flops = 2.0 * Nj * g.OC * Kt;   // (as stored: zero pad channels of a conv1-type layer count as work done, not as credit -- bench.py credits the op's own 2MNK)
-  last_launch.algo_bytes = 2.0 * ((double)g.B * g.C * g.H * g.W + (double)g.OC * Kt) + (out_f32 ? 4.0 : 2.0) * (double)Nj * g.OC + 4.0 * g.OC;
+  last_launch.algo_bytes = 2.0 * ((double)g.B * g.C * g.H * g.W + (double)g.OC * Kt) + (out_f32 ? 4.0 : 2.0) * (double)Nj * g.OC * (res ? 2.0 : 1.0) + 4.0 * g.OC;
 }
 
 

@@ -318,7 +318,8 @@ static int ksl_normalise(int want, long nk) {
   while (s > 1) { long const per = (nk + s - 1) / s; if ((nk + per - 1) / per == s) break; --s; }
   return s;
 }
-plan_t plan_conv_nhwc(conv_geom_t const &g, int num_cus, string const &tile, bool out_f32, int grp_pad, bool allow_split) {
+plan_t plan_conv_nhwc(conv_geom_t const &g, int num_cus, string const &tile, bool out_f32, int grp_pad, bool allow_split, bool res) {
+  if (res && grp_pad) unsup_err("hip_conv_nhwc: nhwc_residual=1 on a sibling group (GROUPS): the residual epilogue belongs to a plain call");
   if (g.C % 8) unsup_err("hip_conv_nhwc: in_chan of a channels-last bf16 tensor must be a multiple of 8 (the layout pass pads)");
   if (g.H >= 32768 || g.W >= 32768) unsup_err("hip_conv_nhwc: planes of 32768 rows / columns or more are not supported");
   long const Nj = (long)g.B * g.OH * g.OW;
@@ -406,10 +407,14 @@ plan_t plan_conv_nhwc(conv_geom_t const &g, int num_cus, string const &tile, boo
             string("-DRELU=") + (g.relu ? "1" : "0"), string("-DOUT_F32=") + (out_f32 ? "1" : "0"), "-DNBUF=" + std::to_string(nbuf)};
   if (c.SPLITK > 1) {   // K slices: reduced inside the launch (KSL, round 5) unless the two-kernel form is asked for (BODAHIP_NHWC_SPLITK2=1: slabs in the shared scratch + bodahip_nhwc_splitk_reduce)
     long const nk2 = ((long)kc + c.BK / 8 - 1) / (c.BK / 8);
-    if (getenv("BODAHIP_NHWC_SPLITK2") && !grp_pad) p.defs.push_back("-DSPLITK=1");
+    if (getenv("BODAHIP_NHWC_SPLITK2") && !grp_pad) {
+      if (res) unsup_err("hip_conv_nhwc: nhwc_residual=1 with the two-kernel form of the K slices (BODAHIP_NHWC_SPLITK2): the reduce pass has no residual epilogue; the in-launch slices (KSL) do");
+      p.defs.push_back("-DSPLITK=1");
+    }
     else { c.SPLITK = ksl_normalise(c.SPLITK, nk2); p.cfg = c; if (c.SPLITK > 1) { p.defs.push_back("-DKSL=" + std::to_string(c.SPLITK)); p.ksl = true; } }
   }
   if (grp_pad) p.defs.push_back("-DGROUPS=1");
+  if (res) p.defs.push_back("-DRES=1");   // (the tile does not depend on it: the flagged launch is the unflagged one with one more operand in its epilogue)
   if (char const *e = getenv("BODAHIP_EXTRA_DEFS")) { std::istringstream is(e); string tok; while (is >> tok) p.defs.push_back(tok); }
   return p;
 }
@@ -1219,6 +1224,7 @@ static bck_op_desc_t const kBckOps[] = {
   {"hip_dropout", 10, "bodahip_dropout", "Dropout", {}, {"inout"}, false}, // (also the function of a BckDropout: the gradient of dropout is dropout)
   {"hip_concat", 11, "bodahip_concat", "Concat", {"in"}, {"out"}, false},
   {"hip_split", 12, "bodahip_split", "Split", {"in"}, {"out"}, false},
+  {"hip_chan_affine", 13, "bodahip_chan_affine", "ChanAffine", {"in", "a", "b"}, {"out"}, false},   // (the forward pipe's BatchNorm / Scale runs; `in` and `out` may be one var)
 };
 std::vector<string> bck_op_ins(bck_op_desc_t const &d, op_base_t const &op) {
   std::vector<string> r(d.ins.begin(), d.ins.end());
@@ -1295,6 +1301,12 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
     if (g.cix < 0 || (long)g.cix + g.C > g.CT) rt_err(what + ": channels [" + std::to_string(g.cix) + ", " + std::to_string((long)g.cix + g.C) + ") (" + ix + " + chan) do not fit the wide tensor's " + std::to_string(g.CT));
     lim((double)g.B * g.CT * g.H * g.W);
     r.threads = g.B * (long)g.C * g.H * g.W; r.algo_bytes = 8.0 * (double)r.threads;
+  } else if (g.op == 13) {
+    if (g.C < 1 || g.H < 1 || g.W < 1) rt_err(what + ": empty tensor");
+    if (g.relu != 0 && g.relu != 1) rt_err(what + ": relu must be 0 | 1");
+    lim(in_e);
+    D("RELU", g.relu);
+    r.threads = (long)in_e; r.algo_bytes = 8.0 * in_e + 8.0 * g.C;   // (one thread per element at most: the launch counts quads where it may use them)
   } else if (g.op == 6 || g.op == 7) {
     if (g.C < 1) rt_err(what + ": no channels");
     lim((double)g.B * g.C);

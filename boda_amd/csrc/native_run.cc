@@ -79,6 +79,15 @@ static bck_op_geom_t bck_op_geom_of_op(op_base_t const &op, bck_op_desc_t const 
     dims_t const &out = op.get_dims("out");
     g.nin = (int)op.get_u32("ins_num"); g.n = (long)out.dims_prod();
     for (string const &an : bck_op_ins(d, op)) if (!(op.get_dims(an) == out)) rt_err(fn + ": " + an + " dims " + op.get_dims(an).pretty_str() + " differ from out's " + out.pretty_str());
+  } else if (d.op == 13) {
+    dims_t const &in = op.get_dims("in"), &out = op.get_dims("out"); need_nchw(in, fn + ": in");
+    if (!(out == in)) rt_err(fn + ": out dims " + out.pretty_str() + " differ from in's " + in.pretty_str());
+    for (char const *an : {"a", "b"}) {
+      dims_t const &d1 = op.get_dims(an);
+      if (d1.sz() != 1 || d1.dims(0) != in.dims(1) || d1.tn != "float") rt_err(fn + ": " + an + " dims " + d1.pretty_str() + ": one float per channel of in " + in.pretty_str());
+    }
+    g.B = in.dims(0); g.C = (int)in.dims(1); g.H = (int)in.dims(2); g.W = (int)in.dims(3); g.relu = (int)op.get_u32("relu");
+    if (g.relu != 0 && g.relu != 1) rt_err(fn + ": relu must be 0 | 1");
   } else if (d.op == 10) {
     g.ratio = op_f32(op, "dropout_ratio"); g.n = (long)op.get_dims(op.has("inout") ? "inout" : "in").dims_prod();   // (the bare op carries in / out, its function the in-place arg inout)
   } else if (d.op == 11 || d.op == 12) {
@@ -108,6 +117,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
   plan_t p; string log, s2d;
   (void)op_zinp_flag(op);   // (refuses the flag on a function that cannot take it)
   (void)op_seed_var_flag(op);   // (likewise)
+  bool const nhwc_res = op_nhwc_residual_flag(op);   // (likewise: a plain hip_conv_nhwc only)
   bool const bf16 = op.has_func_name() && (op.get_func_name() == "hip_sgemm_bf16" || op.get_func_name() == "hip_conv_bf16");
   if (t == "sgemm") {
     dims_t const &a = op.get_dims("a"), &b = op.get_dims("b");
@@ -171,6 +181,8 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
       p = plan_conv_nhwc_multi(gs, tile, op.get_dims("out_0").tn == "float");
     }
     else if (op.has_func_name() && op.get_func_name() == "hip_conv_nhwc" && op.get_dims("filts").sz() == 5) {
+      if (nhwc_res) unsup_err(string("hip_conv_nhwc: nhwc_residual=1 with ") + ((op.has("nhwc_pool") && op.get_u32("nhwc_pool")) ? "a max pooling fused in front (POOL): that form runs on the input-patch kernel, which has no residual epilogue" :
+                              "the in_grp:y:x:out_chan:in_chan8 form of filts: the input-patch and rolling-rows kernels have no residual epilogue"));
       conv_geom_t gp = g; bool pool = false;
       if (op.has("nhwc_pool") && op.get_u32("nhwc_pool")) {   // (filts are in_grp:1:1:out_chan:8: geom_from_dims read in_grp / 1 as out_chan / y -- rebuild from the logical dims)
         dims_t const &f5 = op.get_dims("filts");
@@ -186,7 +198,13 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     else if (op.has_func_name() && op.get_func_name() == "hip_conv_k1_chain") {
       if (!plan_k1_chain(g, (int)op.get_dims("filts2").dsz("out_chan"), op.get_u32("conv_has_relu2") != 0, p)) unsup_err("prebuild: hip_conv_k1_chain does not cover this pair of convolutions");
     }
-    else if (op.has_func_name() && op.get_func_name() == "hip_conv_nhwc") p = plan_conv_nhwc(g, num_cus, tile, op.get_dims("out").tn == "float");
+    else if (op.has_func_name() && op.get_func_name() == "hip_conv_nhwc") {
+      if (nhwc_res) {   // res: exactly out's dims and element type; the sum is defined on whole tensors
+        if (!op.has("res")) rt_err("hip_conv_nhwc: nhwc_residual=1 without the arg 'res'");
+        if (!(op.get_dims("res") == op.get_dims("out")) || op.get_dims("res").tn != op.get_dims("out").tn) rt_err("hip_conv_nhwc: nhwc_residual=1: res dims " + op.get_dims("res").pretty_str() + " (" + op.get_dims("res").tn + ") differ from out's " + op.get_dims("out").pretty_str() + " (" + op.get_dims("out").tn + ")");
+      }
+      p = plan_conv_nhwc(g, num_cus, tile, op.get_dims("out").tn == "float", 0, true, nhwc_res);
+    }
     else if (op.has_func_name() && op.get_func_name() == "hip_conv_nhwc_grp") { dims_t const &grp = op.get_dims("grp"); p = plan_conv_nhwc(g, num_cus, tile, op.get_dims("out_0").tn == "float", (int)grp.dims(grp.sz() - 1)); }
     else if (bf16 && tile.empty() && s2d_geom(g, g2, pry, prx) && plan_patch_bf16(g2, num_cus, p)) { // conv1-type layers: space-to-depth front end (see conv())
       s2d = "s2d(" + std::to_string(g2.C) + "x" + std::to_string(g2.H) + "x" + std::to_string(g2.W) + ",k" + std::to_string(g2.KH) + "x" + std::to_string(g2.KW) + ")+";
@@ -484,13 +502,24 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     if (bi.dsz("out_chan") != (uint32_t)g.OC || (!out_ctot && out.dsz("chan") != (uint32_t)g.OC) || out.dsz("img") != (uint32_t)g.B) rt_err("hip_conv_nhwc: inconsistent biases/out dims");
     if (!g.SY || !g.SX) rt_err("hip_conv_nhwc: zero stride");
     if ((g.H + 2 * g.PY - g.KH) / g.SY + 1 != g.OH || (g.W + 2 * g.PX - g.KW) / g.SX + 1 != g.OW) rt_err("hip_conv_nhwc: out dims do not match in/filts/stride/in_pad");
+    void const *res = nullptr;
+    if (op_nhwc_residual_flag(fi.op)) {   // one more var arg: a tensor of exactly out's dims and element type, and not the tensor the call writes
+      auto ri = am.find("res");
+      if (ri == am.end() || !ri->second.is_valid() || !ri->second.is_var()) rt_err("hip_conv_nhwc: nhwc_residual=1: the var arg 'res' is required");
+      dims_t const rd = host->nh_var_dims(ri->second.n);
+      if (rd.tn != out.tn) rt_err("hip_conv_nhwc: nhwc_residual=1: res has type " + rd.tn + ", out " + out.tn + " (res must have out's element type)");
+      if (!(rd == out)) rt_err("hip_conv_nhwc: nhwc_residual=1: res dims " + rd.pretty_str() + " differ from out's " + out.pretty_str());
+      if (ri->second.n == onm) rt_err("hip_conv_nhwc: nhwc_residual=1: 'res' and 'out' are the same var '" + onm + "'");
+      if (has_post) unsup_err("hip_conv_nhwc: nhwc_residual=1 with a pooling fused behind the convolution: the rolling-rows kernel has no residual epilogue");
+      res = host->nh_var_ptr(ri->second.n);
+    }
     if (has_post) {
       if ((int)out.dsz("y") != post.POH || (int)out.dsz("x") != post.POW) rt_err("hip_conv_nhwc: out dims do not match the fused pooling");
       conv_nhwc_rows(host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), host->nh_var_ptr(inm), host->nh_var_ptr(onm), g, post, out_ctot, out_coff);
       return;
     }
     tile_override_t const tov(impl, "conv_tile", fi.op);
-    conv_nhwc(host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), host->nh_var_ptr(inm), host->nh_var_ptr(onm), g, out.tn == "float", out_ctot, out_coff, patch_filts, pool);
+    conv_nhwc(host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), host->nh_var_ptr(inm), host->nh_var_ptr(onm), g, out.tn == "float", out_ctot, out_coff, patch_filts, pool, res);
     return;
   }
   if (fn == "hip_conv_k1_chain") {

@@ -138,6 +138,15 @@ inline bool op_zinp_flag(op_base_t const &op) {
   if (!(op.get_dims("in") == op.get_dims("in_grad_loss"))) rt_err(fn + ": zero_if_in_non_pos=1 needs in and in_grad_loss of the same dims");
   return true;
 }
+// nhwc_residual, a uint32 of a plain hip_conv_nhwc function op (absent: 0).  1: the call takes one more var arg `res` (in front of out), a tensor of exactly out's dims
+// and element type, and writes out = cvt( relu( (conv + bias) + float(res) ) ): a ResNet block's shortcut added in the convolution's epilogue, one rounding
+// (kernels/conv_nhwc_bf16.hip -DRES=1).  Only the implicit-GEMM kernel of a plain call has that epilogue
+inline bool op_nhwc_residual_flag(op_base_t const &op) {
+  if (!op.has("nhwc_residual") || !op.get_u32("nhwc_residual")) return false;
+  string const fn = op.has_func_name() ? op.get_func_name() : string();
+  if (fn != "hip_conv_nhwc") unsup_err("nhwc_residual=1 on '" + (fn.empty() ? (op.has_type() ? op.get_type() : string("?")) : fn) + "': only a plain hip_conv_nhwc call has the residual epilogue (not a sibling group, a set or a multi-problem launch)");
+  return true;
+}
 // seed_from_var, a uint32 of a hip_dropout function op (absent: 0).  1: the call takes one more var arg, det_drop_seed_var (uint32_t, one element), and hashes with
 // seed = that word + the by-value det_drop_seed (wraps): the seed then lives in device memory, where a captured launch reads it anew at every replay
 inline bool op_seed_var_flag(op_base_t const &op) {

@@ -20,8 +20,9 @@ for net in ("googlenet_conv", "resnet-50"):
     with open(os.path.join(HERE, "nets", f"{net}-conv-bottoms.txt"), "w") as f:
         f.write("".join(f"{n} {b}\n" for n, b in cb))
 
-# full-net op records (TEST phase) for the nets whose every layer type has a forward kernel here (GoogLeNet: conv, ReLU, max/avg
-# pool, LRN, Concat, Dropout) -- read back by boda_amd.conv_pipe.pipe_from_spec
+# full-net op records (TEST phase) for the nets that are read back from a spec by boda_amd.conv_pipe.pipe_from_spec (GoogLeNet: conv, ReLU, max/avg
+# pool, LRN, Concat, Dropout).  ResNet-50's layer types (BatchNorm, Scale, Eltwise as well) all have a forward kernel too, but that net is built in code
+# (boda_amd.conv_pipe.resnet50, like nin_imagenet / alexnet_ng_conv) and needs no spec file: only its convolution list and bottoms above are data
 os.makedirs(os.path.join(HERE, "nets"), exist_ok=True)
 for net in ("googlenet_conv",):
     spec = pipe_spec(open(os.path.join(REF, "nets", net, "train_val.prototxt")).read())

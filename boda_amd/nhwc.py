@@ -188,6 +188,35 @@ def fuse_post(a: Op, pool_out: Dims, kern, stride, pad, lrn=None) -> None:
             a.nda_vals[n] = Nda(None, "float", (float(v),))
 
 
+RES_FLAG = "nhwc_residual"   # uint32 of a plain hip_conv_nhwc function op: out = cvt( relu( (conv + bias) + float(res) ) ), `res` one more var arg in front of out
+
+
+def has_residual(a: Op) -> bool:
+    return a.has(RES_FLAG) and a.get_u32(RES_FLAG) != 0
+
+
+def fuse_residual(a: Op) -> None:
+    """In place: an annotated plain hip_conv_nhwc function takes a residual add into its epilogue (a ResNet block's res = ReLU(shortcut + branch2c)).  It sets
+    nhwc_residual=1; the call then takes one more var arg `res` in front of `out` (cnn_op.pipe_func_args), a tensor of exactly out's dims and element type (added to the
+    op), and writes out = cvt( relu( (conv + bias) + float(res) ) ): the sum is formed in fp32 before the ONE rounding to the output type, and the function's
+    conv_has_relu applies to the sum (kernels/conv_nhwc_bf16.hip -DRES=1).  Only the implicit-GEMM kernel has that epilogue: the input-patch form of filts (which also
+    binds the rolling-rows kernel), a pooling fused in front or behind are refused here, sibling groups / sets / multi-problem launches refuse a flagged member, the
+    planner refuses the two-kernel form of the K slices, the call an output channel slice."""
+    if not a.has_func_name() or a.get_func_name() != FUNC:
+        raise UnsupErr(f"fuse_residual: {a.get_func_name() if a.has_func_name() else a.get_type()!r} is not a plain {FUNC} function")
+    if a.has("nhwc_pool"):
+        raise UnsupErr("fuse_residual: a max pooling is fused in front of this convolution (POOL): the input-patch kernel has no residual epilogue")
+    if a.has("nhwc_post_pool"):
+        raise UnsupErr("fuse_residual: a pooling is fused behind this convolution: the rolling-rows kernel has no residual epilogue")
+    if a.get_dims("filts").has("in_grp"):
+        raise UnsupErr("fuse_residual: filts are in the input-patch form (in_grp:y:x:out_chan:in_chan8): the input-patch and rolling-rows kernels have no residual epilogue")
+    if has_residual(a):
+        raise UnsupErr("fuse_residual: the function takes a residual already")
+    a.set_u32(RES_FLAG, 1)
+    o = a.get_dims("out")
+    a.nda_vals["res"] = Nda(dims=o, tn=o.tn)
+
+
 GRP_FUNC = "hip_conv_nhwc_grp"
 
 
@@ -210,6 +239,8 @@ def annotate_group(annos: List[Op]) -> Op:
     for a in annos:
         if a.get_func_name() != FUNC or a.has("nhwc_s2d") or a.get_dims("filts").has("in_grp"):
             raise UnsupErr("hip_conv_nhwc_grp: members must be plain hip_conv_nhwc functions")
+        if has_residual(a):
+            raise UnsupErr("hip_conv_nhwc_grp: a member with nhwc_residual=1 (the residual epilogue belongs to a plain call)")
         for an in ("in", "stride", "in_pad", "kern_sz"):
             if a.get_dims(an) != a0.get_dims(an):
                 raise UnsupErr(f"hip_conv_nhwc_grp: members differ in {an}")
@@ -234,7 +265,7 @@ _MULTI_MEMBER_ARGS = ("filts", "biases", "in", "stride", "in_pad", "out")
 def multi_eligible(anno: Op) -> bool:
     """A member of a multi-problem launch: a plain hip_conv_nhwc function on the implicit-GEMM kernel (filts out_chan:y:x:in_chan) -- not the input-patch form, not
     space-to-depth (both bind other kernels with another summation order)."""
-    return anno.get_func_name() == FUNC and not anno.has("nhwc_s2d") and not anno.get_dims("filts").has("in_grp") and not anno.has("nhwc_pool") and not anno.has("nhwc_post_pool")
+    return anno.get_func_name() == FUNC and not anno.has("nhwc_s2d") and not anno.get_dims("filts").has("in_grp") and not anno.has("nhwc_pool") and not anno.has("nhwc_post_pool") and not has_residual(anno)
 
 
 def annotate_multi(annos: List[Op]) -> Op:
@@ -247,6 +278,8 @@ def annotate_multi(annos: List[Op]) -> Op:
     nv = {"multi": Nda(dims=Dims(("n",), (len(annos),), "none"), tn="none")}
     relu = [a.get_u32("conv_has_relu") for a in annos]
     for m, a in enumerate(annos):
+        if a.has_func_name() and a.get_func_name() == FUNC and has_residual(a):
+            raise UnsupErr("hip_conv_nhwc_multi: a member with nhwc_residual=1 (the residual epilogue belongs to a plain call)")
         if not multi_eligible(a):
             raise UnsupErr("hip_conv_nhwc_multi: members must be plain hip_conv_nhwc functions (out_chan:y:x:in_chan filters)")
         if a.get_dims("out").tn != annos[0].get_dims("out").tn:
@@ -267,7 +300,7 @@ SET_FUNC = "hip_conv_nhwc_set"
 def set_eligible(anno: Op) -> bool:
     """A member of a set: any hip_conv_nhwc function -- implicit-GEMM or input-patch form of filts (the member keeps its own specialised kernel code); not the
     space-to-depth conv1 form, whose input layout belongs to the net's first layout pass."""
-    return anno.get_func_name() == FUNC and not anno.has("nhwc_s2d") and not anno.has("nhwc_post_pool")     # (nor a convolution with a pooling taken into its launch: the rolling-rows kernel)
+    return anno.get_func_name() == FUNC and not anno.has("nhwc_s2d") and not anno.has("nhwc_post_pool") and not has_residual(anno)     # (nor a flagged residual convolution, nor a convolution with a pooling taken into its launch: the rolling-rows kernel)
 
 
 def annotate_set(annos: List[Op]) -> Op:
@@ -289,6 +322,8 @@ def annotate_set(annos: List[Op]) -> Op:
                 if an != "conv_has_relu":
                     nv[f"{an}_{m}"] = v
             continue
+        if a.get_func_name() == FUNC and has_residual(a):
+            raise UnsupErr("hip_conv_nhwc_set: a member with nhwc_residual=1 (the residual epilogue belongs to a plain call)")
         if not set_eligible(a):
             raise UnsupErr("hip_conv_nhwc_set: members must be hip_conv_nhwc / hip_conv_nhwc_grp functions (not the space-to-depth form)")
         for an in _MULTI_MEMBER_ARGS + ("kern_sz",):
@@ -558,6 +593,17 @@ CUCL_GLOBAL_KERNEL void nhwc_relu( GASQ __bf16 * const inout, uint32_t const n )
   uint32_t const i = GLOB_ID_1D;
   if( i < n ) { if( (float)inout[i] <= 0.0f ) { inout[i] = (__bf16)0.0f; } }
 }
+// Eltwise SUM of two tensors of equal dims that was not taken into a convolution's epilogue: the fp32 sum of the two bf16 values, an optional ReLU on it, ONE rounding.
+// One thread per 16-byte chunk; out may be neither input's var (the pipe gives an Eltwise a node of its own)
+CUCL_GLOBAL_KERNEL void nhwc_eltwise( GASQ bf16x8_t const * const in_0, GASQ bf16x8_t const * const in_1, GASQ bf16x8_t * const out, uint32_t const n, uint32_t const relu ) {
+  // CUCL IX GLOB_ID_1D out n=n
+  uint32_t const i = GLOB_ID_1D;
+  if( i >= n ) { return; }
+  bf16x8_t const a = in_0[i], b = in_1[i];
+  bf16x8_t r;
+  for( int32_t e = 0; e != 8; ++e ) { float x = (float)a[e] + (float)b[e]; if( relu && !( x > 0.0f ) ) { x = 0.0f; } r[e] = (__bf16)x; }
+  out[i] = r;
+}
 // Concat: copy one input (C8_in chunks per position) into its channel range of the output (src/rtc_fwd.cc:267-280)
 CUCL_GLOBAL_KERNEL void nhwc_copy( GASQ bf16x8_t const * const in, GASQ bf16x8_t * const out, uint32_t const n, uint32_t const C8_in, uint32_t const C8_out,
                                    uint32_t const off8 ) {
@@ -572,6 +618,7 @@ FWD_FUNCS: Dict[str, List[str]] = {
     "nhwc_pool": ["in", "out", "n", "C8", "H", "W", "OH", "OW", "KH", "KW", "SY", "SX", "PY", "PX", "avg_pool"],
     "nhwc_lrn": ["in", "out", "n", "C8", "local_size", "alpha", "beta", "k"],
     "nhwc_relu": ["inout", "n"],
+    "nhwc_eltwise": ["in_0", "in_1", "out", "n", "relu"],
     "nhwc_copy": ["in", "out", "n", "C8_in", "C8_out", "off8"],
 }
 _f32 = lambda v: RtcArg.scalar(float(v), "float")
@@ -926,6 +973,12 @@ def lrn_call(in_vn: str, out_vn: str, d: Dims, local_size: int, alpha: float, be
 def relu_call(vn: str, d: Dims) -> RtcFuncCall:
     n = d.dims_prod()
     return RtcFuncCall("nhwc_relu", {"inout": RtcArg.var(vn), "n": _u32(n)}, tpb=_TPB, blks=(n + _TPB - 1) // _TPB)
+
+
+def eltwise_call(in0_vn: str, in1_vn: str, out_vn: str, d: Dims, relu: int) -> RtcFuncCall:
+    n = d.dims_prod() // 8
+    am = {"in_0": RtcArg.var(in0_vn), "in_1": RtcArg.var(in1_vn), "out": RtcArg.var(out_vn), "n": _u32(n), "relu": _u32(int(relu))}
+    return RtcFuncCall("nhwc_eltwise", am, tpb=_TPB, blks=(n + _TPB - 1) // _TPB)
 
 
 def copy_call(in_vn: str, out_vn: str, i: Dims, o: Dims, chan_off: int) -> RtcFuncCall:

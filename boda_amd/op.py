@@ -266,10 +266,12 @@ OP_INFO = {
     "Split": (("in",), (), ("outs_num",)),
     "Dropout": (("in",), ("out",), ("dropout_ratio",)),
     "BckDropout": (("in",), ("out",), ("dropout_ratio",)),
+    # this backend's own (the forward pipe's BatchNorm / Scale runs at inference, conv_pipe.fold_affine): out = in * a[chan] + b[chan], then a ReLU if relu=1
+    "ChanAffine": (("in", "a", "b"), ("out",), ("relu",)),
 }
 
 
-_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout")
+_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine")
 
 
 @dataclass
@@ -486,6 +488,19 @@ class Op:
             raise RtErr(f"{t}: dropout_ratio={r} must lie inside (0, 1)")
         return dict(N=i.dims_prod(), ratio=r)
 
+    def chan_affine_geom(self) -> dict:
+        """ChanAffine: in and out float img:chan:y:x of equal dims, a and b one float per channel, relu 0 | 1."""
+        i = self.get_dims("in")
+        if i.names != ("img", "chan", "y", "x") or i.tn != "float" or self.get_dims("out") != i:
+            raise RtErr("ChanAffine: in and out must be float img:chan:y:x tensors of equal dims")
+        for an in ("a", "b"):
+            d = self.get_dims(an)
+            if d.names != ("chan",) or d.sizes != (i.dsz("chan"),) or d.tn != "float":
+                raise RtErr(f"ChanAffine: {an} dims {d.pretty()}: one float per channel of in {i.pretty()}")
+        if self.get_u32("relu") not in (0, 1):
+            raise RtErr("ChanAffine: relu must be 0 | 1")
+        return dict(B=i.dsz("img"), C=i.dsz("chan"), H=i.dsz("y"), W=i.dsz("x"), relu=self.get_u32("relu"))
+
     def concat_geom(self) -> dict:
         """Concat (ins_i -> out) / Split (in -> outs_i): float img:chan:y:x tensors of equal img / y / x whose channels add up to the wide tensor's.  -> B, H, W, CT and
         chans: per narrow tensor (arg name, first channel in the wide tensor, channels)."""
@@ -581,6 +596,8 @@ def parse_op(line: str) -> Op:
             op.concat_geom()
         elif t in ("Dropout", "BckDropout"):
             op.dropout_geom()
+        elif t == "ChanAffine":
+            op.chan_affine_geom()
         else:
             op.sgemm_geom()
     return op

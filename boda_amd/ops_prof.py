@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from . import gen_data as gd
-from .cnn_op import NATIVE_ARGS, OpTune, add_codegen_annotations
+from .cnn_op import NATIVE_ARGS, OpTune, add_codegen_annotations, pipe_func_args
 from .digest import Digest, KNOWN_SEEDS, OpRun, OpTuneWisdom, OpWisdom, SsdsDiff, read_wisdoms, write_wisdoms
 from .op import Dims, Op, RtErr, UnsupErr, parse_lexp, read_ops
 from .rtc import HipCompute, RtcArg, RtcCompileOpts, RtcFuncCall, RtcFuncInfo
@@ -61,7 +61,7 @@ class OpsBackend:
             raise UnsupErr(f"no template for function {fn!r} in this backend")
         gen_fn = f"{fn}__{self._fn_ix}"
         self._fn_ix += 1
-        args = [a for a, _ in NATIVE_ARGS[fn]]
+        args = [a for a, _ in pipe_func_args(anno_op)]
         stub = f"CUCL_GLOBAL_KERNEL void {gen_fn}( void ) {{ }}\n"  # never launched: the backend binds by op.func_name
         self.rtc.compile([RtcFuncInfo(gen_fn, stub, args, anno_op)], self.compile_opts)
         self._gen_fns[key] = gen_fn
@@ -74,9 +74,12 @@ class OpsBackend:
 
 
 def profile_rcg_call(be: OpsBackend, anno_op: Op, gen_mode: Optional[int], gen_vi: float = 0.0, run_iter: int = 1,
-                     want_outs: bool = True, include_ins: bool = False, tile: str = "") -> Tuple[Dict[str, np.ndarray], PrcRet]:
+                     want_outs: bool = True, include_ins: bool = False, tile: str = "", ins: Optional[Dict[str, np.ndarray]] = None) -> Tuple[Dict[str, np.ndarray], PrcRet]:
+    """`ins`: host arrays for IN args that are not generated -- each in its var's OWN dims and element type (bfloat16 as its uint16 bit patterns), uploaded as they
+    are: how a test hands a flagged hip_conv_nhwc its `res` (cnn_op.pipe_func_args: the function's args, flag-dependent ones included)."""
     rtc = be.rtc
     fn = anno_op.get_func_name()
+    spec = pipe_func_args(anno_op)
     gen_fn = be.gen_func(anno_op)
     arg_map: Dict[str, RtcArg] = {}
     created: List[str] = []
@@ -87,7 +90,7 @@ def profile_rcg_call(be: OpsBackend, anno_op: Op, gen_mode: Optional[int], gen_v
     def ref_dims_of(an):
         return anno_op.get_dims(an + "_ref") if anno_op.has(an + "_ref") else anno_op.get_dims(an)
     try:
-        for an, io in NATIVE_ARGS[fn]:
+        for an, io in spec:
             if io == "REF":
                 arg_map[an] = RtcArg.ref(anno_op.get_dims(an))
                 continue
@@ -97,12 +100,16 @@ def profile_rcg_call(be: OpsBackend, anno_op: Op, gen_mode: Optional[int], gen_v
             arg_map[an] = RtcArg.var(an)
             if ref_dims_of(an) != dims:
                 rtc.create_var_with_dims(an + "_ref", ref_dims_of(an)); created.append(an + "_ref")
-        if any(anno_op.has(an + "_ref") for an, _ in NATIVE_ARGS[fn]):
+        for an, arr in (ins or {}).items():
+            rtc.copy_nda_to_var(an, arr)
+            if include_ins and want_outs:
+                outs[an] = arr
+        if any(anno_op.has(an + "_ref") for an, _ in spec):
             from . import nhwc
             nhwc.ensure_compiled(rtc)
         if gen_mode is not None:
-            for an, io in NATIVE_ARGS[fn]:
-                if io != "IN":
+            for an, io in spec:
+                if io != "IN" or (ins is not None and an in ins):
                     continue
                 dims, rdims = anno_op.get_dims(an), ref_dims_of(an)
                 gen_vn = an if rdims == dims else an + "_ref"
@@ -116,7 +123,7 @@ def profile_rcg_call(be: OpsBackend, anno_op: Op, gen_mode: Optional[int], gen_v
         ids = [rtc.run(rfc) for _ in range(run_iter)]
         launch = rtc.last_launch()
         if want_outs:
-            for an, io in NATIVE_ARGS[fn]:
+            for an, io in spec:
                 if io == "OUT":
                     dims, rdims = anno_op.get_dims(an), ref_dims_of(an)
                     if rdims != dims:
