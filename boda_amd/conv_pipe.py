@@ -1360,22 +1360,29 @@ class ConvPipeFwd:
             self._graph, n = rtc.graph_end()
         return n
 
+    def _call_rw(self, i: int) -> Tuple[List[str], List[str], Dict[str, bool]]:
+        """What `_call_deps` takes call i to read and to write: (vars read, vars written, written var -> True when the call writes a channel range of it that the
+        var's other writers stay clear of).  A call reads its `in` / `inout` vars and writes its `out` / `inout` vars (convs also read filts / biases, which nothing
+        writes during a forward pass)."""
+        c = self.fwd_calls[i]
+        am = c.rfc.arg_map
+        rd = [am[a].n for a in am if (a in ("in", "inout", "cond", "res") or (a[:3] == "in_" and a[3:].isdigit()) or (a[:4] == "ins_" and a[4:].isdigit())) and am[a].is_var()]   # (in_<m>: the members of a set, nhwc_eltwise's two inputs; ins_<i>: hip_reduce's inputs; res: a flagged convolution's shortcut)
+        outs = [a for a in am if (a in ("out", "inout") or (a.startswith("out_") and not a.startswith("out_chan_off"))) and am[a].is_var()]
+        wr = [am[a].n for a in outs]
+        if c.func == "nhwc_xpose_in":     # (the layout pass of the net's input: reads <in>_ref, writes <in>)
+            rd, wr = [am["in_ref"].n], [am["in"].n]
+        slice_outs = {t for t, _, _ in getattr(self, "slices", {}).values()}   # (Concat outputs that convs write channel ranges of)
+        part_of = {v: (c.func in ("fwd_copy", "nhwc_copy") or v in slice_outs) for v in wr}   # writers of disjoint channel ranges of one var: unordered among themselves
+        return rd, wr, part_of
+
     def _call_deps(self) -> List[List[int]]:
-        """deps[i] = the earlier calls that call i must run after.  A call reads its `in` / `inout` vars and writes its `out` /
-        `inout` vars (convs also read filts / biases, which nothing writes during a forward pass); Concat copies fill disjoint
-        channel ranges of one var and are not ordered among themselves."""
+        """deps[i] = the earlier calls that call i must run after: read-after-write, write-after-read and write-after-write hazards between what the calls read and
+        write (`_call_rw`); Concat copies fill disjoint channel ranges of one var and are not ordered among themselves."""
         writers: Dict[str, List[int]] = {}   # var -> the call(s) that produced its current contents
         readers: Dict[str, List[int]] = {}   # var -> calls that read it since
         deps: List[List[int]] = []
-        for i, c in enumerate(self.fwd_calls):
-            am = c.rfc.arg_map
-            rd = [am[a].n for a in am if (a in ("in", "inout", "cond", "res") or (a[:3] == "in_" and a[3:].isdigit()) or (a[:4] == "ins_" and a[4:].isdigit())) and am[a].is_var()]   # (in_<m>: the members of a set, nhwc_eltwise's two inputs; ins_<i>: hip_reduce's inputs; res: a flagged convolution's shortcut)
-            outs = [a for a in am if (a in ("out", "inout") or (a.startswith("out_") and not a.startswith("out_chan_off"))) and am[a].is_var()]
-            wr = [am[a].n for a in outs]
-            if c.func == "nhwc_xpose_in":     # (the layout pass of the net's input: reads <in>_ref, writes <in>)
-                rd, wr = [am["in_ref"].n], [am["in"].n]
-            slice_outs = {t for t, _, _ in getattr(self, "slices", {}).values()}   # (Concat outputs that convs write channel ranges of)
-            part_of = {am[a].n: (c.func in ("fwd_copy", "nhwc_copy") or am[a].n in slice_outs) for a in outs}   # writers of disjoint channel ranges of one var: unordered among themselves
+        for i in range(len(self.fwd_calls)):
+            rd, wr, part_of = self._call_rw(i)
             d = set()
             for v in rd:
                 d.update(writers.get(v, []))

@@ -16,6 +16,7 @@ uint32_t hip_any_graph_num_calls(rtc_compute_t *rtc, uint32_t id);
 void hip_any_graph_destroy(rtc_compute_t *rtc, uint32_t id);
 uint32_t hip_any_graph_end_deps(rtc_compute_t *rtc, uint32_t n, uint32_t const *ptr, uint32_t const *idx);
 native_kernels_t *hip_compute_native(rtc_compute_t *rtc);
+uint32_t hip_compute_last_call_kernels(rtc_compute_t *rtc);
 void hip_compute_compile_code_object(rtc_compute_t *rtc, void const *code, size_t code_sz, vect_rtc_func_info_t const &fis);
 p_rtc_compute_t make_hip_multi_compute(std::vector<int> const &device_ordinals);
 rtc_compute_t *hip_multi_sub(rtc_compute_t *rtc, uint32_t i);
@@ -176,6 +177,12 @@ int bodahip_last_launch(bodahip_ctx *ctx, char *kbuf, size_t kn, char *cbuf, siz
   launch_info_t const &li = hip_compute_native(hip_multi_sub(&R(ctx), 0))->last_launch;   // (a multi-device backend: device 0's)
   put_str(kbuf, kn, li.kernel, "kernel"); put_str(cbuf, cn, li.cfg.str(), "cfg");
   if (grid) *grid = li.grid; if (block) *block = li.block; if (flops) *flops = li.flops; if (algo_bytes) *algo_bytes = li.algo_bytes;
+  ABI_CATCH }
+int bodahip_last_call(bodahip_ctx *ctx, uint32_t *kernels, uint32_t *uses_scratch) {
+  ABI_TRY
+  rtc_compute_t *sub = hip_multi_sub(&R(ctx), 0);   // (a multi-device backend: device 0's)
+  if (kernels) *kernels = hip_compute_last_call_kernels(sub);
+  if (uses_scratch) *uses_scratch = hip_compute_native(sub)->last_call_uses_ws ? 1u : 0u;
   ABI_CATCH }
 int bodahip_compile_offline(const char *src_or_opts, const char *native_template, const char *arch, int add_prelude, int use_cache, size_t *code_size_out, char *log_buf, size_t log_n) {
   ABI_TRY

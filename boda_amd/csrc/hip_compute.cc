@@ -359,11 +359,14 @@ struct hip_compute_t : public rtc_compute_t, public native_host_t {
     return ms;
   }
 
+  uint32_t call_kernels = 0;   // kernels launched by the last run() (eager or captured)
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done); use_dev();
+    call_kernels = 0;
     auto fit = funcs.find(rfc.rtc_func_name);
     if (fit == funcs.end()) rt_err("run: unknown function '" + rfc.rtc_func_name + "' (not compiled, or released)");
     hip_func_t &hf = fit->second;
+    if (!hf.native && native) native->last_call_uses_ws = false;   // (a generated function has its arguments and nothing else)
     if (hf.native) {
       if (capturing) { try { native->run(hf.info, rfc.arg_map); } catch (...) { graph_abort(); throw; } note_captured_call(); return kCapturedCallId; }
       uint32_t const call_id = new_call_events();
@@ -406,6 +409,7 @@ struct hip_compute_t : public rtc_compute_t, public native_host_t {
     rtc_launch_check_blks_and_tpb(rfc.rtc_func_name, blks, rfc.tpb);
     if (rfc.tpb > (uint32_t)props.maxThreadsPerBlock) unsup_err("hip backend: tpb=" + std::to_string(rfc.tpb) + " exceeds device limit for '" + rfc.rtc_func_name + "'");
     if (capturing) {
+      ++call_kernels;
       hipError_t const err = hipModuleLaunchKernel(hf.func, blks, 1, 1, rfc.tpb, 1, 1, 0, stream, kargs.empty() ? nullptr : kargs.data(), nullptr);
       if (err != hipSuccess) { graph_abort(); hip_err_chk(err, ("hipModuleLaunchKernel(" + rfc.rtc_func_name + ") [capture]").c_str()); }
       note_captured_call(); return kCapturedCallId;
@@ -424,6 +428,7 @@ struct hip_compute_t : public rtc_compute_t, public native_host_t {
   // ---- native_host_t: what the native kernels need from the backend
   hipStream_t nh_stream() override { return stream; }
   hipError_t launch_kernel(hipFunction_t f, uint32_t gx, uint32_t gy, uint32_t block, void **params) {
+    ++call_kernels;
     if (timing_kernel && cur_call >= 0 && !capturing && (uint64_t)gx * block <= 0xffffffffull) {
       ev_pair_t &ce = call_evs[cur_call];
       hipError_t const e = hipExtModuleLaunchKernel(f, gx * block, gy, 1, block, 1, 1, 0, stream, params, nullptr, cur_first ? ce.b : nullptr, ce.e, 0);
@@ -592,6 +597,7 @@ uint32_t hip_compute_graph_launch(rtc_compute_t *rtc, uint32_t id) { return as_h
 uint32_t hip_compute_graph_num_calls(rtc_compute_t *rtc, uint32_t id) { return as_hip(rtc).graph_num_calls(id); }
 void hip_compute_graph_destroy(rtc_compute_t *rtc, uint32_t id) { as_hip(rtc).graph_destroy(id); }
 uint32_t hip_compute_graph_end_deps(rtc_compute_t *rtc, uint32_t n, uint32_t const *ptr, uint32_t const *idx) { return as_hip(rtc).graph_end_deps(n, ptr, idx); }
+uint32_t hip_compute_last_call_kernels(rtc_compute_t *rtc) { return as_hip(rtc).call_kernels; }
 void hip_compute_compile_code_object(rtc_compute_t *rtc, void const *code, size_t code_sz, vect_rtc_func_info_t const &fis) { as_hip(rtc).compile_code_object(code, code_sz, fis); }
 void hip_compute_set_shard_aware(rtc_compute_t *rtc) { as_hip(rtc).shard_aware = true; }
 uint32_t hip_compute_run_shard(rtc_compute_t *rtc, rtc_func_call_t const &rfc, uint32_t blks, uint32_t gid_off, uint32_t gid_last, std::map<string, int64_t> const &var_bias) {

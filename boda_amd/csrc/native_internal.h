@@ -37,6 +37,7 @@ struct native_kernels_t::impl_t {
   std::map<string, kernel_t> kernels; // key = option string
   std::map<string, string> tune;
   void *ws = nullptr; size_t ws_bytes = 0; // split-K partial-sum slabs (grow-only scratch, like the reference's cudnn scratch var)
+  bool ws_used = false;                    // ensure_ws was called since run() began: the call works in the shared scratch (native_kernels_t::last_call_uses_ws)
   std::vector<void *> ws_retired;          // outgrown scratch buffers that captured graphs may still point into (freed with the backend)
   std::map<string, void *> ktabs;           // im2col gather tables, one per (C,H,W,KH,KW) (device memory)
   int call_ws_hold = 0;                       // > 0: a launch is collecting several of them (hip_conv_nhwc_set): none may be dropped

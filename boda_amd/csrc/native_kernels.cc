@@ -83,6 +83,7 @@ std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log)
 
 // grow-only scratch shared by the split-K slabs and the Winograd-domain tensors (like the reference's cudnn scratch var)
 void ensure_ws(native_kernels_t::impl_t *impl, native_host_t *host, size_t need) {
+  impl->ws_used = true;   // (whoever asks for the shared scratch works in it)
   if (impl->ws_bytes >= need) return;
   if (host->nh_capturing()) rt_err("graph capture: kernel workspace not allocated yet -- run the call list once before capturing it");
   if (impl->ws) {
@@ -331,7 +332,7 @@ static void launch_patch16(native_kernels_t::impl_t *impl, native_host_t *host, 
   int const taps = g.KH * g.KW, ncg = (g.C + 7) / 8;
   size_t const fbytes = (size_t)ncg * taps * g.OC * 16;
   if (fbytes >= 0x7ffffff0ull) unsup_err("hip_conv_bf16: re-laid-out filters of 2 GiB or more");
-  if (impl->ws_bytes < ws_off + fbytes) ensure_ws(impl, host, ws_off + fbytes);
+  ensure_ws(impl, host, ws_off + fbytes);
   plan_t fp; fp.patch16 = true; fp.bf16 = true; fp.kname = "bodahip_filt_bf16"; fp.defs = {"-DFILT_ONLY=1"};
   kernel_t &fk = get_kernel(impl, host, fp);
   gemm_args_t fa; memset(&fa, 0, sizeof(fa));

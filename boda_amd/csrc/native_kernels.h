@@ -144,6 +144,7 @@ struct native_kernels_t {
   void set_tune(string const &key, string const &val);
   static size_t prebuild(op_base_t const &op, string const &arch, int num_cus, string const &tile, string *plan_out = nullptr);
   launch_info_t last_launch;
+  bool last_call_uses_ws = false;   // the last run(): its plan works in the backend's one shared scratch (ensure_ws was called for it)
   uint32_t num_specialisations() const;
   struct impl_t;
 

@@ -318,6 +318,8 @@ struct exact_override_t {
 
 void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &am) {
   string const &fn = fi.op.get_func_name();
+  impl->ws_used = false;   // set by ensure_ws: does this call's plan work in the shared scratch?  (what graph_end_deps' launch-order rule is about)
+  struct ws_note_t { native_kernels_t *nk; impl_t *im; ~ws_note_t() { nk->last_call_uses_ws = im->ws_used; } } const ws_note{this, impl};
   exact_override_t const xov(impl, fi.op);
   bool const zinp = op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
   bool const seedvar = op_seed_var_flag(fi.op);   // (likewise)

@@ -88,6 +88,7 @@ ABI = {  # symbol -> (restype, argtypes); every symbol include/bodahip.h declare
     "bodahip_set_tune": (C.c_int, [_ctxp, C.c_char_p, C.c_char_p]),
     "bodahip_last_launch": (C.c_int, [_ctxp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "bodahip_last_call": (C.c_int, [_ctxp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "bodahip_compile_offline": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
     "bodahip_parse_op": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
     "bodahip_prebuild": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t)]),
@@ -382,7 +383,10 @@ class HipCompute:
     def last_launch(self) -> dict:
         k = C.create_string_buffer(128); c = C.create_string_buffer(128); g = C.c_uint32(); b = C.c_uint32(); fl = C.c_double(); by = C.c_double()
         _chk(_lib.bodahip_last_launch(self._ctx, k, 128, c, 128, C.byref(g), C.byref(b), C.byref(fl), C.byref(by)))
-        return {"kernel": k.value.decode(), "cfg": c.value.decode(), "grid": g.value, "block": b.value, "flops": fl.value, "algo_bytes": by.value}
+        nk = C.c_uint32(); ws = C.c_uint32()
+        _chk(_lib.bodahip_last_call(self._ctx, C.byref(nk), C.byref(ws)))      # (of the last run(): kernels launched, and does its plan work in the shared scratch?)
+        return {"kernel": k.value.decode(), "cfg": c.value.decode(), "grid": g.value, "block": b.value, "flops": fl.value, "algo_bytes": by.value,
+                "kernels": int(nk.value), "uses_scratch": bool(ws.value)}
 
     def torch_view(self, vn: str):
         """Zero-copy torch tensor over a var's device memory (for torch.distributed / RCCL collectives on weights).  bf16 storage is viewed as bytes (last dim x 2):

@@ -133,6 +133,9 @@ int bodahip_get_device_info(bodahip_ctx *ctx, char *arch_buf, size_t arch_buf_sz
 int bodahip_set_tune(bodahip_ctx *ctx, const char *key, const char *value);
 int bodahip_last_launch(bodahip_ctx *ctx, char *kernel_buf, size_t kernel_buf_sz, char *cfg_buf, size_t cfg_buf_sz, uint32_t *grid, uint32_t *block,
                         double *flops, double *algo_bytes);
+/* the last run() (eager or captured; a multi-device backend: device 0's): how many kernels it launched, and whether its plan works in the backend's one shared
+ * scratch buffer (1) -- the calls a dependency-wired graph keeps in launch order among themselves (bodahip_graph_end_deps) */
+int bodahip_last_call(bodahip_ctx *ctx, uint32_t *kernels_out, uint32_t *uses_scratch_out);
 /* device-less hiprtc compile of CUCL-dialect source (prelude prepended iff add_prelude) or of a named native kernel
  * template ("gemm_conv_f32"; src = "-D..." option string); returns code-object size.  Works without a GPU. */
 int bodahip_compile_offline(const char *src_or_opts, const char *native_template_or_null, const char *arch, int add_prelude, int use_cache,
