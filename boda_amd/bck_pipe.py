@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .cnn_op import (NATIVE_ARGS, OpTune, add_bck_conv_annotations, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos,
+from .cnn_op import (NATIVE_ARGS, OpTune, add_bck_conv_annotations, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
                      pipe_func_args, seed_from_var, SEED_VAR_ARG)
 from .conv_pipe import ConvPipe, PipeOp
 from .op import Dims, Nda, Op, RtErr, UnsupErr
@@ -325,7 +325,10 @@ class ConvPipeBck:
     carries only its layer's fixed offset by value; set_det_drop_seed uploads four bytes and touches no call.  Every node holds the same bits as under the default driver
     given the same seed.  This is what lets a step with dropout be captured: capture_graph / run_graph / run_bck(graph=True) replay the whole call list as one
     hipGraph (be=hip, one device), serially or -- parallel=True -- with the calls' true dependencies (_call_deps), and leave the same bits in every var as the eager
-    step."""
+    step.
+    On a multi-device backend (`(be=hip,devices=0:1:...)`, vars sharded on img) init flags the five functions that are not independent per image with img_shards=1
+    (cnn_op.on_img_shards); run_bck, set_det_drop_seed, seed_in_var, fuse_relu_grad and calls() work as on one device.  Every img-leading node and every loss then
+    hold the bits of the one-device step, every filter / bias gradient the per-shard gradients added in device order."""
 
     def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False):
         self.rtc = rtc
@@ -372,6 +375,7 @@ class ConvPipeBck:
         self.fused_relu_grads = {"folded": list(folds), "unfolded": why}
         takes_relu = set(folds.values())   # the gradient ops that apply the mask of the ZeroIfNonPos behind them
         zinp = lambda o, f: fuse_zero_if_in_non_pos(f) if o.tag in takes_relu else f
+        multi_dev = isinstance(getattr(rtc, "devices", None), list) and len(rtc.devices) > 1
         infos: List[RtcFuncInfo] = []
         for o in ops:
             if o.tag in fused or o.tag in folds:
@@ -426,6 +430,8 @@ class ConvPipeBck:
             else:
                 raise UnsupErr(f"ConvPipeBck: op type {t!r} (op {o.tag}) has no native function")
             for fop, args in calls:
+                if multi_dev and fop.get_func_name() in IMG_SHARDS_FUNCS:   # (the only way these five run on img shards)
+                    fop = on_img_shards(fop)
                 fname = f"bck_{len(self.bck_calls)}_{fop.get_func_name()}"
                 spec = pipe_func_args(fop)
                 am: Dict[str, RtcArg] = {}
@@ -509,7 +515,7 @@ class ConvPipeBck:
         """Capture the step's call list into a hipGraph; -> number of captured calls.  If no ordinary step has run since init, one runs first on whatever the vars
         hold: the K-slice workspaces and lazily built kernels must exist before a capture.  parallel=True: the graph gets the calls' true dependencies (_call_deps)
         instead of the launch order, so that independent calls -- the three gradients of one BckConv, the branches of a fan-out -- may overlap.  A second capture
-        destroys the first.  Not provided on a multi-device backend (devices=...), where the step does not run either."""
+        destroys the first.  Not provided on a multi-device backend (devices=...): the step runs there eagerly, its cross-device sums are no part of a device's capture."""
         rtc = self.rtc
         drops = [c.tag for c, _ in self._dropout_calls()]
         if drops and not self.seed_in_var:

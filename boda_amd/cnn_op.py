@@ -329,6 +329,28 @@ def seed_from_var(fop: Op) -> Op:
     return a
 
 
+IMG_SHARDS_FLAG = "img_shards"   # uint32 of a function op: the call's img-leading vars may be shards of a batch, and the call leaves the bits of the whole batch's call
+IMG_SHARDS_FUNCS = ("hip_bconv_filts", "hip_bconv_biases", "hip_sm_grad_and_loss", "hip_sum_loss_over_imgs", "hip_dropout")   # the functions that are not independent per image
+
+
+def has_img_shards_flag(fop: Op) -> bool:
+    return fop.has(IMG_SHARDS_FLAG) and fop.get_u32(IMG_SHARDS_FLAG) != 0
+
+
+def on_img_shards(fop: Op) -> Op:
+    """-> a copy of an annotated hip_bconv_filts / hip_bconv_biases / hip_sm_grad_and_loss / hip_sum_loss_over_imgs / hip_dropout function op with img_shards=1: the
+    five functions a multi-device backend (`(be=hip,devices=...)`, vars sharded on img) refuses, because they are not independent per image.  A flagged call runs there
+    and leaves, for the whole batch, the bits DESIGN.md section 3.13 writes down: dropout, the loss gradient, loss_per_pel and loss those of the one-device call; a
+    filter / bias gradient the per-shard gradients of the unflagged function added in device order, plain fp32 adds from the first shard's.  No new var args
+    (pipe_func_args is unchanged).  be=cpu and a single be=hip device accept the flag and run the unflagged function: one shard, a chain of one term."""
+    fn = fop.get_func_name() if fop.has_func_name() else ""
+    if fn not in IMG_SHARDS_FUNCS:
+        raise RtErr(f"on_img_shards: {fn or fop.get_type()!r} is none of {', '.join(IMG_SHARDS_FUNCS)} (every other function is independent per image and runs on img shards as it is)")
+    a = fop.copy()
+    a.nda_vals[IMG_SHARDS_FLAG] = Nda(None, "uint32_t", (1,))
+    return a
+
+
 def pipe_func_args(fop: Op) -> tuple:
     """The (arg, IN | OUT | REF | VAL) list of an annotated function op: NATIVE_ARGS; for hip_reduce its ins_0 .. ins_{n-1} followed by out; for a hip_bconv_in /
     hip_spreading with zero_if_in_non_pos=1 the var arg `in` in front of in_grad_loss; for a hip_dropout with seed_from_var=1 the var arg det_drop_seed_var behind inout;

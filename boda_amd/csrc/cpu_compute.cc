@@ -353,6 +353,7 @@ struct cpu_compute_t : public rtc_compute_t {
       if (is_conv(fn)) (void)fi.op.get_u32("conv_has_relu");
       (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
       (void)op_seed_var_flag(fi.op);   // (likewise)
+      (void)op_img_shards_flag(fi.op);   // (likewise; here there is one shard: a flagged call is the unflagged one)
       if (bck_op_fn_t const *d = find_bck_op(fn)) {
         if (!type_ok(*d, fi.op.get_type())) rt_err(fn + ": a function of op type " + d->type + ", not " + fi.op.get_type());
         for (string const &an : bck_op_ins(*d, fi.op)) (void)fi.op.get_dims(an);
@@ -617,6 +618,7 @@ struct cpu_compute_t : public rtc_compute_t {
     string const &fn = fi.op.get_func_name();
     map_str_rtc_arg_t const &am = rfc.arg_map;
     (void)op_seed_var_flag(fi.op);   // (refuses the flag on a function that cannot take it)
+    (void)op_img_shards_flag(fi.op);   // (likewise)
     double const tb = now_ms();
     if (bck_op_fn_t const *bd = find_bck_op(fn)) run_bck_op(*bd, fi.op, am);
     else if (is_bck(fn)) run_bck(fn, fi.op, am);

@@ -21,6 +21,11 @@
 //     sizes stay those of the whole tensor -- each thread computes exactly what it computes on one device (incl. the flat-index hash of
 //     gen_data), on memory its device owns.  Functions that use the workgroup (LOC_ID_1D, GRP_ID_1D, LOCSHAR_MEM, BARRIER_SYNC), that declare
 //     no GLOB_ID_1D index, or that take a var sharded along its second dim (sgemm `a`) are refused with unsup_err on sharded vars;
+//   * the five native functions that are NOT independent per image -- hip_bconv_filts / hip_bconv_biases (a sum over the images), hip_sm_grad_and_loss (divides by the
+//     image count), hip_sum_loss_over_imgs (one chain over the images), hip_dropout (hashes the flat index in the whole tensor) -- are refused on more than one device,
+//     unless their op carries img_shards=1 (rtc_types.h: op_img_shards_flag).  A flagged call leaves the bits defined in run_on_img_shards below: dropout and the
+//     loss gradient by host arithmetic on a by-value argument, the loss by gathering loss_per_pel to device 0, the two gradients by summing the per-device partials
+//     on device 0 in device order (kernels/bck_ops_f32.hip OP 14) and copying the sum back to every device.  Ordered by events, no host synchronisation;
 //   * get_dur(b, e) = the longest of the devices' durations; finish_and_sync() waits for all.
 // The per-GPU process model of bench.py / boda_amd/shard.py (torch.distributed, RCCL weight broadcast) stays: this class is for callers that
 // want one process -- an unmodified Boda with --rtc='(be=hip,devices=...)'.  Devices may repeat (e.g. {0, 0}): the same GPU then holds several
@@ -43,6 +48,7 @@ uint32_t hip_compute_graph_num_calls(rtc_compute_t *rtc, uint32_t id);
 void hip_compute_graph_destroy(rtc_compute_t *rtc, uint32_t id);
 uint32_t hip_compute_graph_end_deps(rtc_compute_t *rtc, uint32_t n, uint32_t const *ptr, uint32_t const *idx);
 void hip_compute_set_shard_aware(rtc_compute_t *rtc);
+native_kernels_t *hip_compute_native(rtc_compute_t *rtc);
 uint32_t hip_compute_run_shard(rtc_compute_t *rtc, rtc_func_call_t const &rfc, uint32_t blks, uint32_t gid_off, uint32_t gid_last, std::map<string, int64_t> const &var_bias);
 
 struct multi_var_t { dims_t dims; int shard_dim = -1; };   // logical dims; index of the sharded dim (-1: replicated)
@@ -123,6 +129,11 @@ struct hip_multi_compute_t : public rtc_compute_t {
   std::map<string, bool> func_native;
   std::map<string, string> func_img_sum;   // native functions that reduce over the images (BckConv filter / bias gradients, the softmax loss): refused on a sharded run, with this message
   std::map<string, gen_func_t> func_gen;       // generated functions: their index declaration
+  std::map<string, string> func_shards;    // native functions compiled with img_shards=1 (n() > 1): func name -> the op's function, run by run_on_img_shards
+  std::vector<hipEvent_t> shard_in_evs;        // per device i > 0: recorded on stream i behind what a flagged call enqueued there; stream 0 waits for it before it gathers
+  hipEvent_t shard_out_ev = nullptr;           // recorded on stream 0 behind a flagged call's fan-out; every other stream waits for it before it goes on
+  float *shard_ws = nullptr; size_t shard_ws_bytes = 0;   // device 0: the slabs of the per-device partials (the gathered loss_per_pel).  Grow-only, reused by every flagged call
+  bool force_peer = false;
   std::vector<hipEvent_t> peer_evs;            // per device: marks the end of its last peer copy out of device 0
   static constexpr uint32_t kNoCall = 0xffffffffu;   // per-device call id of a call that launched nothing there (an empty shard)
   std::vector<std::vector<uint32_t>> calls;   // multi call id -> per-device call ids
@@ -183,14 +194,20 @@ struct hip_multi_compute_t : public rtc_compute_t {
     if (devs.empty()) rt_err("hip multi-device backend: empty device list");
     for (int d : devs) subs.push_back(make_hip_compute(d));
   }
-  ~hip_multi_compute_t() override { for (hipEvent_t e : peer_evs) if (e) (void)hipEventDestroy(e); }
+  ~hip_multi_compute_t() override {
+    for (hipEvent_t e : peer_evs) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : shard_in_evs) if (e) (void)hipEventDestroy(e);
+    if (shard_out_ev) (void)hipEventDestroy(shard_out_ev);
+    if (shard_ws) { (void)hipSetDevice(devs[0]); (void)hipFree(shard_ws); }   // (hipFree waits for the device: nothing on stream 0 still works in it)
+  }
   size_t n() const { return subs.size(); }
 
   void init() override {
     assert_st(!init_done);
     for (auto &s : subs) { s->gen_src = gen_src; s->gen_src_output_dir = gen_src_output_dir; s->init(); hip_compute_set_shard_aware(s.get()); }
     peer_ok.assign(n(), 0); peer_evs.assign(n(), nullptr);
-    bool const force_peer = getenv("BODAHIP_FORCE_PEER") != nullptr;   // (tests: take the device-to-device fan-out between shards of ONE GPU too)
+    shard_in_evs.assign(n(), nullptr);
+    force_peer = getenv("BODAHIP_FORCE_PEER") != nullptr;   // (tests: take the device-to-device fan-out between shards of ONE GPU too)
     for (size_t i = 1; i < n(); ++i) {
       if (devs[i] == devs[0]) { peer_ok[i] = force_peer ? 1 : 0; continue; }
       int can = 0;
@@ -336,6 +353,8 @@ struct hip_multi_compute_t : public rtc_compute_t {
     for (auto const &fi : func_infos) {
       bool const nat = native_kernels_t::is_native_func_name(fi.op.has_func_name() ? fi.op.get_func_name() : string());
       func_native[fi.func_name] = nat;
+      bool const shards = nat && op_img_shards_flag(fi.op);   // (on any other function the devices' own compile has refused the flag already)
+      if (shards && n() > 1) { func_shards[fi.func_name] = fi.op.get_func_name(); continue; }
       // BckConv's filter / bias gradients sum over the images: on img shards every device would hold a partial sum, and no cross-device reduction exists here
       if (nat && n() > 1 && (fi.op.get_func_name() == "hip_bconv_filts" || fi.op.get_func_name() == "hip_bconv_biases"))
         func_img_sum[fi.func_name] = "(a BckConv filter / bias gradient) sums over the images, which would need a cross-device reduction; only the data gradient (hip_bconv_in) runs on img shards";
@@ -348,14 +367,15 @@ struct hip_multi_compute_t : public rtc_compute_t {
       if (!nat) func_gen[fi.func_name] = scan_gen_func(all_src, fi.func_name);
     }
   }
-  void release_func(string const &fn) override { must_find(func_native, fn); for (auto &s : subs) s->release_func(fn); func_native.erase(fn); func_gen.erase(fn); func_img_sum.erase(fn); }
-  void release_all_funcs() override { for (auto &s : subs) s->release_all_funcs(); func_native.clear(); func_gen.clear(); func_img_sum.clear(); }
+  void release_func(string const &fn) override { must_find(func_native, fn); for (auto &s : subs) s->release_func(fn); func_native.erase(fn); func_gen.erase(fn); func_img_sum.erase(fn); func_shards.erase(fn); }
+  void release_all_funcs() override { for (auto &s : subs) s->release_all_funcs(); func_native.clear(); func_gen.clear(); func_img_sum.clear(); func_shards.clear(); }
 
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
     auto fit = func_native.find(rfc.rtc_func_name);
     if (fit == func_native.end()) rt_err("run: unknown function '" + rfc.rtc_func_name + "' (not compiled, or released)");
     { auto is = func_img_sum.find(rfc.rtc_func_name); if (is != func_img_sum.end()) unsup_err("multi-device backend: '" + rfc.rtc_func_name + "' " + is->second); }
+    { auto sh = func_shards.find(rfc.rtc_func_name); if (sh != func_shards.end()) return run_on_img_shards(rfc, sh->second); }
     if (!fit->second) {
       bool sharded = false;
       for (auto const &kv : rfc.arg_map) if (kv.second.is_valid() && kv.second.is_var() && must_find(vis, kv.second.n).shard_dim >= 0) sharded = true;
@@ -366,6 +386,123 @@ struct hip_multi_compute_t : public rtc_compute_t {
     if (capturing) return kCapturedCallId;             // (recorded into every device's graph: no call id of its own)
     calls.push_back(ids);
     return (uint32_t)calls.size() - 1;
+  }
+  // ---- the five functions with img_shards=1.  T = the image count of the logical (sharded) var, device i holds images [chunk_begin(T, i), chunk_begin(T, i + 1)); a device
+  // without images launches nothing and contributes no term to any sum.
+  //   hip_dropout            device i runs the plain call with the by-value seed + chunk_begin(T, i) * (elements per image), mod 2^32: the kernel hashes flat index +
+  //                          seed in wrapping uint32, so every element gets the hash of its index in the whole tensor (with seed_from_var=1 the by-value part is the offset
+  //                          and is moved the same way).  Host arithmetic only.
+  //   hip_sm_grad_and_loss   device i runs the call with one more by-value uint32, img_total = T: the divisor (native_run.cc).  Host arithmetic only.
+  //   hip_sum_loss_over_imgs the loss_per_pel shards are copied, in image order, into the workspace on device 0; the one chain of OP 8 (from +0, then / T) runs there once;
+  //                          `loss` is copied to every other device.
+  //   hip_bconv_filts / hip_bconv_biases   every device with images runs the plain call on its shard into ITS copy of the (replicated) gradient var: the partial p_i, by
+  //                          whatever plan the planner picks for the shard's dims.  The partials are copied into slabs of the workspace on device 0 and summed there in
+  //                          device order, (p_0 + p_1) + p_2 + ..., plain fp32 adds that start from the first partial (one partial: no add).  The sum is written into
+  //                          device 0's copy and copied from there into every other device's.
+  // Ordering, by events alone (the host never waits): (1) every stream i > 0 records shard_in_evs[i] behind what the call enqueued there, and stream 0 waits for all of
+  // them -- so the gather reads finished partials, and nothing enqueued earlier on stream i still reads the var the fan-out will overwrite; (2) gather, sum and fan-out
+  // are all enqueued on stream 0, whose in-order execution puts the fan-out copy into device i's var behind the gather copy out of it, and keeps the workspace -- which
+  // only stream 0 ever touches -- free of a second call's slabs until the first call's sum has read them; (3) stream 0 records shard_out_ev behind the fan-out and
+  // every stream i > 0 waits for it, so nothing later on device i reads or rewrites the var before the sum has arrived.  Copies: hipMemcpyPeerAsync, or a plain
+  // device-to-device copy between shards of one physical device (BODAHIP_FORCE_PEER: the peer copy there too); no kernel reads another device's memory.
+  hipStream_t sub_stream(size_t i) { return (hipStream_t)hip_compute_stream(subs[i].get()); }
+  char *sub_ptr(size_t i, string const &vn) { return (char *)subs[i]->get_var_raw_native_pointer(vn)->rp_elems(); }
+  void copy_on_stream0(void *dst, size_t di, void const *src, size_t si, size_t bytes) {   // (the device is devs[0] throughout a flagged call's stream-0 work)
+    if (!bytes) return;
+    if (devs[di] == devs[si] && !force_peer) hip_err_chk(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, sub_stream(0)), "hipMemcpyAsync(D2D)");
+    else hip_err_chk(hipMemcpyPeerAsync(dst, devs[di], src, devs[si], bytes, sub_stream(0)), "hipMemcpyPeerAsync");
+  }
+  void shards_gather_begin() {   // step (1)
+    for (size_t i = 1; i < n(); ++i) {
+      hip_err_chk(hipSetDevice(devs[i]), "hipSetDevice");
+      if (!shard_in_evs[i]) hip_err_chk(hipEventCreateWithFlags(&shard_in_evs[i], hipEventDisableTiming), "hipEventCreateWithFlags");
+      hip_err_chk(hipEventRecord(shard_in_evs[i], sub_stream(i)), "hipEventRecord(shard partial)");
+    }
+    hip_err_chk(hipSetDevice(devs[0]), "hipSetDevice");
+    for (size_t i = 1; i < n(); ++i) hip_err_chk(hipStreamWaitEvent(sub_stream(0), shard_in_evs[i], 0), "hipStreamWaitEvent(shard partial)");
+  }
+  void shards_fan_out_end() {    // step (3)
+    if (!shard_out_ev) hip_err_chk(hipEventCreateWithFlags(&shard_out_ev, hipEventDisableTiming), "hipEventCreateWithFlags");
+    hip_err_chk(hipEventRecord(shard_out_ev, sub_stream(0)), "hipEventRecord(shard sum)");
+    for (size_t i = 1; i < n(); ++i) { hip_err_chk(hipSetDevice(devs[i]), "hipSetDevice"); hip_err_chk(hipStreamWaitEvent(sub_stream(i), shard_out_ev, 0), "hipStreamWaitEvent(shard sum)"); }
+    hip_err_chk(hipSetDevice(devs[0]), "hipSetDevice");
+  }
+  float *shards_ws(size_t bytes) {   // grow-only; growing frees the old buffer, and hipFree waits for the device -- the first call of a size only, never a steady-state step
+    if (bytes > shard_ws_bytes) {
+      hip_err_chk(hipSetDevice(devs[0]), "hipSetDevice");
+      if (shard_ws) { hip_err_chk(hipFree(shard_ws), "hipFree(shard workspace)"); shard_ws = nullptr; shard_ws_bytes = 0; }
+      size_t const want = (bytes + 4095) & ~size_t(4095);
+      hip_err_chk(hipMalloc((void **)&shard_ws, want), "hipMalloc(shard workspace)"); shard_ws_bytes = want;
+    }
+    return shard_ws;
+  }
+  // the var bound to arg `an`, which must be sharded along img (want_sharded) or replicated
+  multi_var_t const &shards_arg(rtc_func_call_t const &rfc, string const &fn, char const *an, bool want_sharded, string &vn) {
+    auto ai = rfc.arg_map.find(an);
+    if (ai == rfc.arg_map.end() || !ai->second.is_valid() || !ai->second.is_var()) rt_err(fn + ": img_shards=1: arg '" + an + "' must be a var");
+    vn = ai->second.n;
+    multi_var_t const &v = must_find(vis, vn);
+    if (want_sharded ? (v.shard_dim != 0 || v.dims.names(0) != "img") : (v.shard_dim >= 0)) rt_err(fn + ": img_shards=1: arg '" + an + "' (var '" + vn + "' " + v.dims.pretty_str() + ") must be " + (want_sharded ? "sharded along its leading img dim" : "a replicated var"));
+    return v;
+  }
+  uint32_t run_on_img_shards(rtc_func_call_t const &rfc, string const &fn) {
+    if (capturing) { capturing = false; for (auto &s : subs) hip_compute_graph_abort(s.get()); unsup_err("multi-device backend: '" + rfc.rtc_func_name + "' (" + fn + " with img_shards=1) cannot be captured into a graph: its cross-device work is not part of any one device's capture"); }
+    bool const sum = fn == "hip_bconv_filts" || fn == "hip_bconv_biases";
+    string svn, rvn;
+    multi_var_t const &sv = shards_arg(rfc, fn, sum ? "out_grad_loss" : fn == "hip_dropout" ? "inout" : fn == "hip_sm_grad_and_loss" ? "prob" : "loss_per_pel", true, svn);
+    uint32_t const T = sv.dims.dims(0);
+    std::vector<uint32_t> ids(n(), kNoCall);
+    auto done = [&]() { calls.push_back(ids); return (uint32_t)calls.size() - 1; };
+    if (!T) return done();   // (an empty batch: nothing to run anywhere)
+    auto has_imgs = [&](size_t i) { return chunk_begin(T, i + 1) > chunk_begin(T, i); };
+    if (fn == "hip_dropout" || fn == "hip_sm_grad_and_loss") {
+      bool const drop = fn == "hip_dropout";
+      uint32_t seed = 0;
+      if (drop) {
+        auto si = rfc.arg_map.find("det_drop_seed");
+        if (si == rfc.arg_map.end() || !si->second.is_valid() || si->second.is_var() || !si->second.v->rp_elems() || si->second.v->dims.tn != "uint32_t" || si->second.v->dims.sz() != 0)
+          rt_err(fn + ": 'det_drop_seed' must be a by-value uint32_t scalar of the call");
+        seed = *(uint32_t const *)si->second.v->rp_elems();
+      }
+      uint64_t const per_img = sv.dims.dims_prod() / T;
+      for (size_t i = 0; i < n(); ++i) {
+        if (!has_imgs(i)) continue;
+        rtc_func_call_t sub = rfc;   // (a fresh by-value nda: the caller's is shared)
+        if (drop) sub.arg_map["det_drop_seed"] = rtc_arg_t(make_scalar_nda<uint32_t>((uint32_t)(seed + (uint64_t)chunk_begin(T, i) * per_img)));
+        else sub.arg_map["img_total"] = rtc_arg_t(make_scalar_nda<uint32_t>(T));
+        ids[i] = subs[i]->run(sub);
+      }
+      return done();
+    }
+    if (fn == "hip_sum_loss_over_imgs") {
+      multi_var_t const &lv = shards_arg(rfc, fn, "loss", false, rvn);
+      if (sv.dims.tn != "float" || lv.dims.tn != "float" || sv.dims.dims_prod() != T || lv.dims.dims_prod() != 1) rt_err(fn + ": img_shards=1: loss_per_pel must hold one float per image and loss one float");
+      float *const ws = shards_ws((size_t)T * 4);
+      shards_gather_begin();
+      for (size_t i = 0; i < n(); ++i) if (has_imgs(i)) copy_on_stream0(ws + chunk_begin(T, i), 0, sub_ptr(i, svn), i, (size_t)(chunk_begin(T, i + 1) - chunk_begin(T, i)) * 4);
+      bck_op_geom_t g; g.op = 8; g.B = T;
+      float const *ins[8] = {ws, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float *outs[2] = {(float *)sub_ptr(0, rvn), nullptr};
+      hip_compute_native(subs[0].get())->bck_op(g, ins, outs);
+      for (size_t i = 1; i < n(); ++i) copy_on_stream0(sub_ptr(i, rvn), i, sub_ptr(0, rvn), 0, 4);
+      shards_fan_out_end();
+      return done();
+    }
+    // the filter / bias gradient
+    multi_var_t const &gv = shards_arg(rfc, fn, fn == "hip_bconv_filts" ? "filts_grad_loss" : "biases_grad_loss", false, rvn);
+    if (gv.dims.tn != "float") rt_err(fn + ": img_shards=1: the gradient var must be float");
+    uint64_t const elems = gv.dims.dims_prod(), stride = (elems + 3) & ~uint64_t(3);   // (slabs start on 16 bytes: the sum walks quads)
+    size_t const bytes = (size_t)elems * 4;
+    std::vector<size_t> live;
+    for (size_t i = 0; i < n(); ++i) if (has_imgs(i)) { ids[i] = subs[i]->run(rfc); live.push_back(i); }
+    float *const ws = live.size() > 1 ? shards_ws((size_t)stride * live.size() * 4) : nullptr;
+    shards_gather_begin();
+    if (live.size() > 1) {
+      for (size_t k = 0; k < live.size(); ++k) copy_on_stream0(ws + k * stride, 0, sub_ptr(live[k], rvn), live[k], bytes);
+      hip_compute_native(subs[0].get())->shard_sum(ws, (float *)sub_ptr(0, rvn), (int)live.size(), (long)stride, (long)elems);
+    } else if (live[0] != 0) copy_on_stream0(sub_ptr(0, rvn), 0, sub_ptr(live[0], rvn), live[0], bytes);   // (one partial: it IS the sum)
+    for (size_t i = 1; i < n(); ++i) if (!(live.size() == 1 && live[0] == i)) copy_on_stream0(sub_ptr(i, rvn), i, sub_ptr(0, rvn), 0, bytes);
+    shards_fan_out_end();
+    return done();
   }
   // a per-element generated function over vars sharded along their leading dim: see the header of this file
   uint32_t run_generated_on_shards(rtc_func_call_t const &rfc) {

@@ -39,6 +39,8 @@
 // OP 7  bodahip_sm_grad_and_loss  (test/rtc/sm_grad_and_loss.cucl)   prob, label -> in_grad_loss, loss_per_pel
 //   * label is a FLOAT holding the class index, read by image; in_grad_loss = (prob - [chan == label]) / img_count: an fp32 subtract, then an fp32 divide
 //   * loss_per_pel = -logf(max(prob[label], FLT_MIN)); a label outside [0, chan) matches no channel and reads no memory: its loss is -logf(FLT_MIN)
+//   * B is read only as that divisor, the threads are counted by n: on an img shard of a batch (the function op's img_shards=1 on a multi-device backend) the host
+//     passes the WHOLE batch's image count as B and the shard's elements as n -- the same kernel, the one-device bits
 // OP 8  bodahip_sum_loss_over_imgs  (test/rtc/sum_loss_over_imgs.cucl)   loss = (sequential fp32 sum of loss_per_pel over the images from +0) / img_count: one thread
 // OP 9  bodahip_reduce  (test/rtc/reduce.cucl, the sum of a fan-out's partial gradients)   ins_0 .. ins_{NIN-1} -> out
 //   * out[i] = (((+0 + ins_0[i]) + ins_1[i]) + ...): a sequential fp32 chain from +0 in the op's input order, so two -0 inputs give +0
@@ -56,10 +58,15 @@
 //   * out[i,c,y,x] = in[i,c,y,x] * a[c] + b[c]: an fp32 multiply, then an fp32 add, two roundings; RELU=1 (the op's relu): x > 0 ? x : +0 on that sum, so -0 and a NaN give +0
 //   * a thread owns one quad or one tail element of one plane, loads before it stores and touches nothing else: in and out may be the same buffer
 //   * n4 counts the float4 quads of ONE plane here (0 unless both pointers are 16-byte aligned and HW is a multiple of 4), the elements behind them are scalars
+// OP 14 bodahip_shard_sum  (this backend's own: the sum of the per-shard partial gradients of a multi-device backend, csrc/hip_multi.cc)   B slabs -> out
+//   * slab d holds n floats at p0 + d * wide (wide: the slab stride in floats); out[e] = ((slab_0[e] + slab_1[e]) + slab_2[e]) + ...: plain fp32 adds in slab order that
+//     START FROM slab 0's value -- no +0 in front, so one slab is a copy and keeps a -0
+//   * the slab count is a loop bound: one specialisation for every device count.  A thread owns one quad or one tail element, reads it from every slab and then
+//     stores: out may be slab 0.  n4 = 0 unless p0, out and the stride are all 16-byte aligned
 // OP 9 .. 12 take float4 over the first n4 quads and scalars over the tail, like OP 5; the host sets n4 = 0 unless every pointer (11, 12: every per-image run) is
 // 16-byte aligned.  Quads never straddle a run: 11 / 12 use them only when run, wide and off are multiples of 4.
 //
-// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN | 2, 4: [ZINP] | 10: [SEEDVAR] | 13: RELU.  Host side: plan_bck_op (native_plan.cc), native_kernels.cc.
+// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN | 2, 4: [ZINP] | 10: [SEEDVAR] | 13: RELU | 14: none.  Host side: plan_bck_op / plan_shard_sum (native_plan.cc), native_kernels.cc.
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -81,7 +88,7 @@ struct bck_ops_args_t {   // must match native_internal.h
   float f0, f1, f2, f3;                                                 // LRN: alpha / local_size, beta, k, ((2 * -beta) * alpha) / local_size; OP 10: f0 = scale
   float const *p4; float const *p5; float const *p6; float const *p7;   // OP 9: inputs 4 .. 7; OP 10 with SEEDVAR: p4 = the uint32 word added to seed
   unsigned seed, thresh;                                                // OP 10
-  int run, wide, off;                                                   // OP 11, 12: floats of one image's channel range, of one image of the wider tensor, offset of the range
+  int run, wide, off;                                                   // OP 11, 12: floats of one image's channel range, of one image of the wider tensor, offset of the range; OP 14: wide = the slab stride, B = the slabs
 };
 
 constexpr float kFltMax = 3.402823466e+38f, kFltMin = 1.175494351e-38f;
@@ -384,6 +391,24 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
   }
 }
 
+#elif OP == 14
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+#define SUM_SLABS(T, ix) \
+  T v = ((T const *)p.p0)[ix]; \
+  for (int d = 1; d < p.B; ++d) v = v + ((T const *)(p.p0 + (long)d * p.wide))[ix];
+extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) {
+  long const id = (long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= p.n) return;
+  if (id < p.n4) {
+    SUM_SLABS(f32x4, id)
+    ((f32x4 *)p.o0)[id] = v;
+  } else {
+    long const e = 4L * p.n4 + (id - p.n4);
+    SUM_SLABS(float, e)
+    p.o0[e] = v;
+  }
+}
+
 #else
-#error "bck_ops_f32.hip: -DOP=1..13"
+#error "bck_ops_f32.hip: -DOP=1..14"
 #endif

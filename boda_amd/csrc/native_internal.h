@@ -76,6 +76,7 @@ std::vector<string> bck_op_ins(bck_op_desc_t const &d, op_base_t const &op);   /
 std::vector<bck_op_desc_t const *> bck_ops_of_type(string const &t);   // the functions of a bare op, in the reference's call order (empty: not such an op)
 struct bck_plan_t { plan_t p; long threads = 0; uint32_t grid = 0, block = 256; int CB = 0; double algo_bytes = 0; };
 bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus);
+bck_plan_t plan_shard_sum(int nslabs, long stride, long n);   // OP 14 of the same file: no function of its own, the multi-device backend's sum of per-shard partials
 
 struct rows_args_t { // must match kernels/conv_nhwc_rows_bf16.hip
   void const *filts; void const *in; void *out; float const *bias;

@@ -39,6 +39,7 @@ bool native_kernels_t::is_native_func_name(string const &fn) {
 }
 void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
   string const &fn = fi.op.get_func_name();
+  (void)op_img_shards_flag(fi.op);   // (refuses the flag on every function but the five that are not independent per image)
   if (fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "hip_sgemm_bf16") return;
   (void)op_nhwc_residual_flag(fi.op);   // (refuses the flag on every function but a plain hip_conv_nhwc)
   if (fn == "hip_conv" || fn == "cudnn_conv" || fn == "hip_conv_bf16" || fn == "hip_conv_winograd" || fn == "hip_conv_nhwc" || fn == "hip_conv_nhwc_grp" || fn == "hip_conv_nhwc_multi" || fn == "hip_conv_nhwc_set") { (void)fi.op.get_u32("conv_has_relu"); return; } // required, as src/culibs-wrap.cc:198
@@ -784,6 +785,7 @@ void native_kernels_t::bck_op(bck_op_geom_t const &g, float const *const *ins, f
   bck_ops_args_t a; memset(&a, 0, sizeof(a));
   a.p0 = ins[0]; a.p1 = ins[1]; a.p2 = ins[2]; a.p3 = ins[3]; a.o0 = outs[0]; a.o1 = outs[1];
   a.n = bp.threads; a.B = (int)g.B; a.C = g.C; a.HW = g.H * g.W;
+  if (g.op == 7 && g.img_total) a.B = (int)g.img_total;   // (OP 7 reads B only as its divisor; its threads are counted by n)
   if (g.op == 3 || g.op == 4) { a.f0 = g.alpha / (float)g.LS; a.f1 = g.beta; a.f2 = g.k; a.f3 = ((2.0f * -g.beta) * g.alpha) / (float)g.LS; }
   bool const quads = g.op == 5 || (g.op >= 9 && g.op <= 12);
   if (quads) {   // float4 over whole quads when every buffer is 16-byte aligned, scalars over the rest
@@ -810,6 +812,20 @@ void native_kernels_t::bck_op(bck_op_geom_t const &g, float const *const *ins, f
   uint32_t const grid = (quads || g.op == 13) ? (uint32_t)((a.n + 255) / 256) : bp.grid;
   void *params[] = {&a};
   if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, bp.block, params), "hipModuleLaunchKernel(bck_op)");
+  last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = grid; last_launch.block = bp.block;
+  last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
+}
+void native_kernels_t::shard_sum(float const *slabs, float *out, int nslabs, long stride, long n) {
+  bck_plan_t const bp = plan_shard_sum(nslabs, stride, n);
+  kernel_t &k = get_kernel(impl, host, bp.p);
+  bck_ops_args_t a; memset(&a, 0, sizeof(a));
+  a.p0 = slabs; a.o0 = out; a.B = nslabs; a.wide = (int)stride;
+  // float4 over whole quads when every slab and out start on 16 bytes, scalars over the tail
+  bool const al = (((uintptr_t)slabs | (uintptr_t)out) & 15) == 0 && (stride & 3) == 0;
+  a.n4 = al ? (int)(n / 4) : 0; a.n = (long)a.n4 + (n - 4L * a.n4);
+  uint32_t const grid = (uint32_t)((a.n + 255) / 256);
+  void *params[] = {&a};
+  if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, bp.block, params), "hipModuleLaunchKernel(shard_sum)");
   last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = grid; last_launch.block = bp.block;
   last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
 }

@@ -30,6 +30,9 @@
 //       hip_reduce              ins_0 .. ins_{ins_num-1} out                  (2 .. 8 inputs)                      test/rtc/reduce.cucl
 //       hip_dropout             inout det_drop_seed(by-value uint32)          (Dropout and BckDropout)             test/rtc/dropout.cucl
 //                               with seed_from_var=1 in the op: inout det_drop_seed_var(uint32_t var, one element) det_drop_seed -- the hash seed is word + by-value
+//                               the five functions that are not independent per image -- hip_bconv_filts / hip_bconv_biases, hip_sm_grad_and_loss, hip_sum_loss_over_imgs,
+//                               hip_dropout -- take img_shards=1 in the op (rtc_types.h): no new var args; what a multi-device backend then does is in hip_multi.cc.
+//                               hip_sm_grad_and_loss then reads an optional by-value uint32 img_total of the call: the divisor
 //       hip_concat / hip_split  in out   (ocix / icix in the op: one call per input / output)                      src/rtc_fwd.cc:267-294
 //       hip_chan_affine         in a b out   (relu in the op; in and out may be one var)   out = in * a[chan] + b[chan], two roundings: the forward pipe's BatchNorm / Scale runs
 //     hip_conv_winograd                 same contract as hip_conv; 3x3 / stride-1 layers through F(2x2,3x3) Winograd (mrd <= ~2e-3)
@@ -93,6 +96,7 @@ struct bck_op_geom_t { int op = 0; long B = 0; int C = 0, H = 1, W = 1, OH = 1, 
   int nin = 0; float ratio = 0.f; uint32_t seed = 0; int CT = 0, cix = 0;
   int zinp = 0;      // spreading, bck_lrn: 1 = in_grad_loss = in > 0 ? value : +0 (the op's zero_if_in_non_pos; spreading then takes `in` as its fourth input)
   int seedvar = 0;   // dropout: 1 = the hash seed is the word of the call's det_drop_seed_var + seed (the op's seed_from_var)
+  long img_total = 0;   // sm_grad_and_loss on an img shard (the op's img_shards=1): the image count of the WHOLE batch, the divisor (0: B)
   int relu = 0; };   // chan_affine: 1 = x > 0 ? x : +0 on the finished sum (the op's relu)
 
 struct launch_info_t { string kernel; tile_cfg_t cfg; uint32_t grid = 0, block = 0; double flops = 0, algo_bytes = 0; };
@@ -135,6 +139,9 @@ struct native_kernels_t {
   // the non-conv ops of the gradient pipe: ins / outs in the function's arg order (up to eight / two raw device pointers)
   // seed_word (dropout with g.seedvar): the device word added to g.seed
   void bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs, uint32_t const *seed_word = nullptr);
+  // the cross-device sum of a multi-device backend (kernels/bck_ops_f32.hip OP 14): nslabs slabs of n floats at slabs + d * stride (stride in floats) -> out[e] =
+  // ((slab_0[e] + slab_1[e]) + slab_2[e]) + ..., plain fp32 adds in slab order starting FROM slab 0; out may be slab 0.  Launched on this backend's stream
+  void shard_sum(float const *slabs, float *out, int nslabs, long stride, long n);
   void conv_winograd(float const *filts, float const *biases, float const *in, float *out, conv_geom_t const &g, int out_ctot, int out_coff);
 
   // tuning overrides ("" clears): key "sgemm_tile" / "conv_tile" -> "BIxBJxBKxWIxWJ[xMINW[xSPLITK[xMT]]]"; key "k1_stream" -> "off" | "WIxWJxOCBxCB[xMINW]";

@@ -1321,5 +1321,15 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
   r.grid = (uint32_t)blocks;
   return r;
 }
+// the sum of per-shard partial gradients (csrc/hip_multi.cc): one specialisation for every slab count, which is a loop bound
+bck_plan_t plan_shard_sum(int nslabs, long stride, long n) {
+  string const what = "bodahip_shard_sum";
+  if (nslabs < 1 || n < 0 || stride < n) rt_err(what + ": " + std::to_string(nslabs) + " slabs of " + std::to_string(n) + " floats at a stride of " + std::to_string(stride));
+  if (4.0 * (double)stride * nslabs >= 2147483648.0) unsup_err(what + ": slabs of 2 GiB or more (32-bit strides)");
+  bck_plan_t r; r.p.bck_ops = true; r.p.kname = what; r.p.defs = {"-DOP=14"};
+  r.threads = n; r.algo_bytes = 4.0 * (nslabs + 1) * (double)n;
+  r.grid = (uint32_t)((n + r.block - 1) / r.block);
+  return r;
+}
 
 } // namespace bodahip

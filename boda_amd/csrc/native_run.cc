@@ -117,6 +117,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
   plan_t p; string log, s2d;
   (void)op_zinp_flag(op);   // (refuses the flag on a function that cannot take it)
   (void)op_seed_var_flag(op);   // (likewise)
+  (void)op_img_shards_flag(op);   // (likewise.  A flagged function plans as the unflagged one: the flag adds no define)
   bool const nhwc_res = op_nhwc_residual_flag(op);   // (likewise: a plain hip_conv_nhwc only)
   bool const bf16 = op.has_func_name() && (op.get_func_name() == "hip_sgemm_bf16" || op.get_func_name() == "hip_conv_bf16");
   if (t == "sgemm") {
@@ -237,6 +238,11 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
       if (q.kname == "bodahip_bconv_filts") desc += " ksl=" + std::to_string(q.cfg.SPLITK);
       if (!arch.empty()) bytes += compile_plan(q, arch, &log).size();
     }
+    if (op_img_shards_flag(op)) {   // a flagged filter / bias gradient on several devices also runs the sum of the per-device partials (csrc/hip_multi.cc): one kernel for every device count
+      bck_plan_t const sp = plan_shard_sum(2, 4, 4);
+      desc += " | " + sp.p.kname + " " + sp.p.defs[0];
+      if (!arch.empty()) bytes += compile_plan(sp.p, arch, &log).size();
+    }
     if (plan_out) *plan_out = desc;
     return bytes;
   } else if (!bck_ops_of_type(t).empty()) {   // a non-conv op of the gradient pipe: its annotated function, or (the bare op) all its functions in call order
@@ -323,6 +329,7 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
   exact_override_t const xov(impl, fi.op);
   bool const zinp = op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
   bool const seedvar = op_seed_var_flag(fi.op);   // (likewise)
+  bool const img_shards = op_img_shards_flag(fi.op);   // (likewise)
   bool const bf16 = (fn == "hip_sgemm_bf16" || fn == "hip_conv_bf16");
   if (fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "hip_sgemm_bf16") {
     string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");
@@ -693,6 +700,14 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     if (g.op == 5) g.n = (long)host->nh_var_dims(var_of(am, "in")).dims_prod();
     else if (g.op == 9 || g.op == 10) g.n = (long)host->nh_var_dims(var_of(am, d->outs[0])).dims_prod();
     else if (n_img >= 0) g.B = n_img;
+    if (g.op == 7 && img_shards) {   // an img shard of a batch: the divisor is the WHOLE batch's image count, which a multi-device backend adds to the call by value
+      auto ti = am.find("img_total");
+      if (ti != am.end()) {
+        if (!ti->second.is_valid() || ti->second.is_var() || !ti->second.v->rp_elems() || ti->second.v->dims.tn != "uint32_t" || ti->second.v->dims.sz() != 0) rt_err(fn + ": img_shards=1: 'img_total' must be a by-value uint32_t scalar of the call");
+        g.img_total = (long)*(uint32_t const *)ti->second.v->rp_elems();
+        if (g.img_total < g.B) rt_err(fn + ": img_shards=1: img_total=" + std::to_string(g.img_total) + " is less than the " + std::to_string(g.B) + " images of this shard");
+      }
+    }
     bck_op(g, ins, outs, seed_word);
     return;
   }

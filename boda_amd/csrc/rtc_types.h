@@ -156,6 +156,17 @@ inline bool op_seed_var_flag(op_base_t const &op) {
   if (fn != "hip_dropout" && !bare_dropout) rt_err("seed_from_var=1 on '" + (fn.empty() ? (op.has_type() ? op.get_type() : string("?")) : fn) + "': only hip_dropout takes a seed, and only it can read one from a var");
   return true;
 }
+// img_shards, a uint32 of a function op (absent: 0).  1: the call's img-leading vars may be shards of a batch, and the call leaves the bits of the WHOLE batch's call --
+// the five functions that are not independent per image: hip_bconv_filts / hip_bconv_biases (a sum over the images), hip_sm_grad_and_loss (divides by the image
+// count), hip_sum_loss_over_imgs (one chain over the images), hip_dropout (hashes the flat index in the whole tensor).  On one device (be=cpu, be=hip) there is one shard
+// and the flagged call is the unflagged one; a multi-device backend runs it as csrc/hip_multi.cc describes.  No new var args
+inline bool op_img_shards_flag(op_base_t const &op) {
+  if (!op.has("img_shards") || !op.get_u32("img_shards")) return false;
+  string const fn = op.has_func_name() ? op.get_func_name() : string();
+  if (fn != "hip_bconv_filts" && fn != "hip_bconv_biases" && fn != "hip_sm_grad_and_loss" && fn != "hip_sum_loss_over_imgs" && fn != "hip_dropout")
+    rt_err("img_shards=1 on '" + (fn.empty() ? (op.has_type() ? op.get_type() : string("?")) : fn) + "': only hip_bconv_filts, hip_bconv_biases, hip_sm_grad_and_loss, hip_sum_loss_over_imgs and hip_dropout take it (every other function is independent per image and runs on img shards as it is)");
+  return true;
+}
 // the var bound to det_drop_seed_var: uint32_t, exactly one element, and not the tensor the call rewrites
 inline void check_seed_var(string const &fn, string const &vn, dims_t const &d, string const &inout_vn) {
   if (vn == inout_vn) rt_err(fn + ": seed_from_var=1: 'det_drop_seed_var' and 'inout' are the same var '" + vn + "'");

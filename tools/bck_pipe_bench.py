@@ -5,6 +5,7 @@ and the share of the step each native function takes (sums of the backend's per-
     python tools/bck_pipe_bench.py [--nets nin,alexnet] [--batch 256] [--runs 5] [--warmup 2] [--out profiles/r09_bck_pipe_bench.txt]
     python tools/bck_pipe_bench.py --fuse-relu-grad [--repeats 3] [--out profiles/r09_bck_fuse_ab.txt]
     python tools/bck_pipe_bench.py --graph [--repeats 3] [--out profiles/r10_bck_graph_ab.txt]
+    python tools/bck_pipe_bench.py --devices 0:1:2:3 [--out profiles/bck_pipe_devices.txt]
 
 --fuse-relu-grad: the same step both ways in ONE process -- ConvPipeBck() and ConvPipeBck(fuse_relu_grad=True), each on a backend instance of its own with the same
 params and inputs -- after the usual warm-up, in --repeats alternating blocks of --runs steps.  Per net two JSON lines ("way": "unfused" / "fused": step ms as the median
@@ -16,6 +17,10 @@ with the same params and inputs: "eager" (run_device_only), "graph" (capture_gra
 dependencies instead of the launch order).  The seed advances per step in all three (four bytes into the det_drop_seed var).  Per net one JSON line per way (step ms as
 the median over all blocks, the block medians, images/s, the captured call count) and one with the two ratios against the eager step of the same run and whether all
 three ended with the same loss bits.  No ratio is required: the spread of the block medians is what a difference has to beat.
+
+--devices d0:d1:...: the plain step on the multi-device backend `(be=hip,devices=...)`: the batch sharded on img, the five functions that are not independent per image
+run with img_shards=1.  Step ms is the longest of the devices' times; a call's share counts the time its device-side launches took, not the
+cross-device copies behind them.  No figure for more than one physical GPU is recorded yet.
 
 Every net runs in a child process of its own under a time limit (--limit seconds); the first one that fails ends the run.
 """
@@ -121,14 +126,14 @@ def graph_ab(net, batch, runs, warmup, repeats):
         w["drv"].release(); w["rtc"].close()
 
 
-def one_net(net, batch, runs, warmup):
+def one_net(net, batch, runs, warmup, devices=""):
     import numpy as np
     from boda_amd import conv_pipe
     from boda_amd.bck_pipe import ConvPipeBck, add_bck_ops
     from boda_amd.rtc import make_rtc
     cp = {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv}[net](batch)
     bp = add_bck_ops(cp)
-    rtc = make_rtc("(be=hip)", 0)
+    rtc = make_rtc(f"(be=hip,devices={devices})" if devices else "(be=hip)", 0)   # (several devices: the driver flags the five functions that are not independent per image)
     rtc.init()
     drv = ConvPipeBck(rtc)
     drv.init(bp)
@@ -146,7 +151,7 @@ def one_net(net, batch, runs, warmup):
     loss = float(rtc.copy_var_to_nda("loss").item())
     tot = sum(share.values())
     step = statistics.median(ms)
-    print(json.dumps({"net": net, "batch": batch, "calls": len(drv.calls()), "step_ms": round(step, 3), "imgs_per_s": round(batch / (step * 1e-3), 1), "loss": round(loss, 4),
+    print(json.dumps({"net": net, "batch": batch, **({"devices": devices} if devices else {}), "calls": len(drv.calls()), "step_ms": round(step, 3), "imgs_per_s": round(batch / (step * 1e-3), 1), "loss": round(loss, 4),
                       "share": {k: round(v / tot, 4) for k, v in sorted(share.items(), key=lambda kv: -kv[1])}}), flush=True)
     drv.release(); rtc.close()
 
@@ -162,20 +167,24 @@ def main(argv=None):
     ap.add_argument("--fuse-relu-grad", action="store_true", help="A/B: the step with and without the ReLU gradients folded into their producers, in one process")
     ap.add_argument("--graph", action="store_true", help="A/B: the eager step, the step as one hipGraph replay, and the replay with the calls' true dependencies, in one process")
     ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad / --graph: alternating blocks of --runs steps per way")
+    ap.add_argument("--devices", default="", help="e.g. 0:1:2:3: the plain step on the multi-device backend (be=hip,devices=...), batch sharded on img")
     ap.add_argument("--child", default="")
     a = ap.parse_args(argv)
+    if a.devices and (a.graph or a.fuse_relu_grad):
+        ap.error("--devices times the plain step: graph capture is not provided on several devices, and the fused A/B runs on one")
     if a.graph and a.fuse_relu_grad:
         ap.error("--graph and --fuse-relu-grad are two comparisons: run them one at a time")
-    a.out = a.out or os.path.join(ROOT, "profiles", "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r09_bck_pipe_bench.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "bck_pipe_devices.txt" if a.devices else "r09_bck_pipe_bench.txt")
     if a.child:
         if a.graph:
             return graph_ab(a.child, a.batch, a.runs, a.warmup, a.repeats)
-        return fuse_ab(a.child, a.batch, a.runs, a.warmup, a.repeats) if a.fuse_relu_grad else one_net(a.child, a.batch, a.runs, a.warmup)
+        return fuse_ab(a.child, a.batch, a.runs, a.warmup, a.repeats) if a.fuse_relu_grad else one_net(a.child, a.batch, a.runs, a.warmup, a.devices)
     lines = []
     for net in a.nets.split(","):
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", net, "--batch", str(a.batch), "--runs", str(a.runs), "--warmup", str(a.warmup)]
         cmd += ["--fuse-relu-grad", "--repeats", str(a.repeats)] if a.fuse_relu_grad else []
         cmd += ["--graph", "--repeats", str(a.repeats)] if a.graph else []
+        cmd += ["--devices", a.devices] if a.devices else []
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:   # nothing more is started on the GPU after a failure
             print(f"{net}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
@@ -183,7 +192,7 @@ def main(argv=None):
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
         print("\n".join(lines[-4:] if a.graph else lines[-3:] if a.fuse_relu_grad else lines[-1:]), flush=True)
     with open(a.out, "w") as f:
-        extra = f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else ""
+        extra = f" --devices {a.devices}" if a.devices else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else ""
         f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 
