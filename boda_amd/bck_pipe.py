@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .cnn_op import (NATIVE_ARGS, OpTune, add_bck_conv_annotations, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
+from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, sgd_update_func_op, add_bck_conv_annotations, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
                      pipe_func_args, seed_from_var, SEED_VAR_ARG)
 from .conv_pipe import ConvPipe, PipeOp
 from .op import Dims, Nda, Op, RtErr, UnsupErr
@@ -33,6 +33,32 @@ IN_PLACE_TYPES = ("ReLU", "Dropout", "BckDropout")   # and a ZeroIfNonPos whose 
 DROPOUT_RATIO = 0.5   # Dropout_coi's default (src/conv_util.cc:39); the ConvPipe records carry no ratio
 SEED_VAR = "det_drop_seed"   # ConvPipeBck(seed_in_var=True): the one-word uint32 var every dropout call reads its seed from
 DROP_LAYER_STEP = 0x9E3779B1   # the k-th Dropout layer of a pipe hashes with seed + k * this (mod 2^32)
+SGD_HYPER_VAR = "sgd_hyper"    # ConvPipeBck(solver=...): float v=4 = [lr, momentum, weight_decay, unused], read by every update call
+SGD_HIST_SFX = "_sgd_hist"     # <param>_sgd_hist: the param's momentum history
+
+
+@dataclass
+class SgdSolver:
+    """SGD with momentum and weight decay for ConvPipeBck(solver=...), Caffe's order (regularise, history, update) with the gradient left unmodified.  Per element of
+    param tensor i, every operation one fp32 rounding (hip_sgd_update, cnn_op.sgd_update_func_op):
+        g1 = g + (weight_decay * decay_mult_i) * w;   h' = momentum * h + (lr * lr_mult_i) * g1;   w' = w - h'
+    lr_mult / decay_mult: dicts keyed by param name (`conv1_filts`) or by the suffix `filts` / `biases`; a name wins over a suffix, the default is 1.
+    tensors_per_call (1 .. 32): params per hip_sgd_update call, packed in the order of the pipe's params."""
+    lr: float
+    momentum: float = 0.9
+    weight_decay: float = 5e-4
+    lr_mult: Optional[Dict[str, float]] = None
+    decay_mult: Optional[Dict[str, float]] = None
+    tensors_per_call: int = 32
+
+    def mult_of(self, which: Optional[Dict[str, float]], param: str) -> float:
+        d = which or {}
+        if param in d:
+            return float(d[param])
+        return float(d.get(param.rsplit("_", 1)[-1], 1.0))
+
+    def hyper(self) -> np.ndarray:
+        return np.array([self.lr, self.momentum, self.weight_decay, 0.0], np.float32)
 
 
 @dataclass
@@ -328,10 +354,18 @@ class ConvPipeBck:
     step.
     On a multi-device backend (`(be=hip,devices=0:1:...)`, vars sharded on img) init flags the five functions that are not independent per image with img_shards=1
     (cnn_op.on_img_shards); run_bck, set_det_drop_seed, seed_in_var, fuse_relu_grad and calls() work as on one device.  Every img-leading node and every loss then
-    hold the bits of the one-device step, every filter / bias gradient the per-shard gradients added in device order."""
+    hold the bits of the one-device step, every filter / bias gradient the per-shard gradients added in device order.
+    solver=SgdSolver(...) (opt-in; None leaves the vars, calls(), _call_deps() and every bit of a step as they are): the step also UPDATES the params on the device.
+    init creates one zero-filled history var <param>_sgd_hist per param and the var sgd_hyper, and appends the hip_sgd_update calls, tagged sgd_update_0 ..., at the
+    END of the call list, behind every gradient op: tensors_per_call params per call in the order of the pipe's params, g_i bound to <param>_grad_loss.
+    set_sgd_hyper uploads 16 bytes and touches no call (valid between graph replays: a learning-rate schedule needs no new capture); zero_sgd_history clears the
+    history.  capture_graph captures the update calls with the rest and leaves params and history as they were.  On a multi-device backend the update runs on every
+    device's replicas, which hold the same summed gradients and so stay equal."""
 
-    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False):
+    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[SgdSolver] = None):
         self.rtc = rtc
+        self.solver = solver
+        self.n_sgd_calls = 0       # the update calls, the last n_sgd_calls of bck_calls
         self.op_tune = op_tune or OpTune()
         self.fuse_relu_grad = bool(fuse_relu_grad)
         self.seed_in_var = bool(seed_in_var)
@@ -358,6 +392,15 @@ class ConvPipeBck:
         self._stepped = False
         if self.seed_in_var and SEED_VAR in bp.nodes:
             raise RtErr(f"ConvPipeBck.init: seed_in_var=True needs the var name {SEED_VAR!r}, which is a node of the pipe")
+        if self.solver is not None:   # (refused before anything is created)
+            if not 1 <= int(self.solver.tensors_per_call) <= SGD_MAX_TENS:
+                raise RtErr(f"ConvPipeBck.init: SgdSolver.tensors_per_call={self.solver.tensors_per_call}: 1 to {SGD_MAX_TENS}")
+            for vn in [pn + SGD_HIST_SFX for pn in bp.cp.params] + [SGD_HYPER_VAR]:
+                if vn in bp.nodes:
+                    raise RtErr(f"ConvPipeBck.init: the solver needs the var name {vn!r}, which is a node of the pipe")
+            for pn in bp.cp.params:
+                if pn + "_grad_loss" not in bp.nodes:
+                    raise RtErr(f"ConvPipeBck.init: the solver: no gradient op writes {pn + '_grad_loss'!r}")
         for n, d in bp.nodes.items():
             self._var(n, d)
         if self.seed_in_var:
@@ -377,6 +420,24 @@ class ConvPipeBck:
         zinp = lambda o, f: fuse_zero_if_in_non_pos(f) if o.tag in takes_relu else f
         multi_dev = isinstance(getattr(rtc, "devices", None), list) and len(rtc.devices) > 1
         infos: List[RtcFuncInfo] = []
+
+        def emit(tag: str, fop: Op, args: Dict[str, str]) -> None:
+            if multi_dev and fop.get_func_name() in IMG_SHARDS_FUNCS:   # (the only way these five run on img shards)
+                fop = on_img_shards(fop)
+            fname = f"bck_{len(self.bck_calls)}_{fop.get_func_name()}"
+            spec = pipe_func_args(fop)
+            am: Dict[str, RtcArg] = {}
+            for an, io in spec:
+                if io == "REF":
+                    am[an] = RtcArg.ref(fop.get_dims(an))
+                elif io == "VAL":
+                    am[an] = RtcArg.scalar(0, "uint32_t")
+                else:
+                    am[an] = RtcArg.var(args[an])
+            infos.append(RtcFuncInfo(fname, "", [an for an, _ in spec], fop))
+            self.bck_calls.append(BckCall(tag, fop, dict(args), RtcFuncCall(fname, am)))
+            self.funcs.append(fname)
+
         for o in ops:
             if o.tag in fused or o.tag in folds:
                 continue
@@ -430,21 +491,23 @@ class ConvPipeBck:
             else:
                 raise UnsupErr(f"ConvPipeBck: op type {t!r} (op {o.tag}) has no native function")
             for fop, args in calls:
-                if multi_dev and fop.get_func_name() in IMG_SHARDS_FUNCS:   # (the only way these five run on img shards)
-                    fop = on_img_shards(fop)
-                fname = f"bck_{len(self.bck_calls)}_{fop.get_func_name()}"
-                spec = pipe_func_args(fop)
-                am: Dict[str, RtcArg] = {}
-                for an, io in spec:
-                    if io == "REF":
-                        am[an] = RtcArg.ref(fop.get_dims(an))
-                    elif io == "VAL":
-                        am[an] = RtcArg.scalar(0, "uint32_t")
-                    else:
-                        am[an] = RtcArg.var(args[an])
-                infos.append(RtcFuncInfo(fname, "", [an for an, _ in spec], fop))
-                self.bck_calls.append(BckCall(o.tag, fop, dict(args), RtcFuncCall(fname, am)))
-                self.funcs.append(fname)
+                emit(o.tag, fop, args)
+        self.n_sgd_calls = 0
+        if self.solver is not None:   # the update calls, behind every gradient op
+            sv = self.solver
+            pnames = list(bp.cp.params)
+            for pn in pnames:
+                self._var(pn + SGD_HIST_SFX, bp.cp.params[pn])
+            self._var(SGD_HYPER_VAR, Dims(("v",), (4,), "float"))
+            per = int(sv.tensors_per_call)
+            for k in range(0, len(pnames), per):
+                grp = pnames[k:k + per]
+                fop = sgd_update_func_op([bp.cp.params[pn] for pn in grp], [sv.mult_of(sv.lr_mult, pn) for pn in grp], [sv.mult_of(sv.decay_mult, pn) for pn in grp])
+                args = {"hyper": SGD_HYPER_VAR}
+                for i, pn in enumerate(grp):
+                    args.update({f"w_{i}": pn, f"g_{i}": pn + "_grad_loss", f"h_{i}": pn + SGD_HIST_SFX})
+                emit(f"sgd_update_{self.n_sgd_calls}", fop, args)
+                self.n_sgd_calls += 1
         rtc.compile(infos)
         params = op_params if op_params is not None else host_params(bp, gen_mode)
         for n, d in bp.cp.params.items():
@@ -455,6 +518,26 @@ class ConvPipeBck:
             for c, k in self._dropout_calls():
                 c.rfc.arg_map["det_drop_seed"] = RtcArg.scalar((k * DROP_LAYER_STEP) & 0xFFFFFFFF, "uint32_t")
         self.set_det_drop_seed(0)
+        if self.solver is not None:
+            self._sgd_hyper = self.solver.hyper()
+            self.zero_sgd_history()
+            self.set_sgd_hyper()
+
+    def set_sgd_hyper(self, lr: Optional[float] = None, momentum: Optional[float] = None, weight_decay: Optional[float] = None) -> None:
+        """Upload the 16 bytes of sgd_hyper with the values given replaced (None: kept).  Touches no call: the next step -- eager or a graph replay -- reads them."""
+        if self.solver is None:
+            raise RtErr("ConvPipeBck.set_sgd_hyper: the driver was built without a solver")
+        for i, v in enumerate((lr, momentum, weight_decay)):
+            if v is not None:
+                self._sgd_hyper[i] = np.float32(v)
+        self.rtc.copy_nda_to_var(SGD_HYPER_VAR, self._sgd_hyper)
+
+    def zero_sgd_history(self) -> None:
+        """Clear every <param>_sgd_hist."""
+        if self.solver is None:
+            raise RtErr("ConvPipeBck.zero_sgd_history: the driver was built without a solver")
+        for pn, d in self.bp.cp.params.items():
+            self.rtc.copy_nda_to_var(pn + SGD_HIST_SFX, np.zeros(d.sizes, np.float32))
 
     def _dropout_calls(self) -> List[Tuple[BckCall, int]]:
         """The dropout calls of the step with their layer's index among the pipe's Dropout ops (a layer's forward and backward call share it)."""
@@ -497,15 +580,17 @@ class ConvPipeBck:
         for v in to_get_vns:
             fwd[v] = rtc.copy_var_to_nda(v)
 
-    def run_device_only(self) -> float:
-        """Run all calls once with the inputs already resident; -> ms first-call-start to last-call-end.  per_call_ms: (tag, function, ms) per call."""
+    def run_device_only(self, skip_sgd: bool = False) -> float:
+        """Run all calls once with the inputs already resident; -> ms first-call-start to last-call-end.  per_call_ms: (tag, function, ms) per call.
+        skip_sgd: leave the solver's update calls out (what capture_graph's preparing step does: params and history stay as they are)."""
         rtc = self.rtc
-        for c in self.bck_calls:
+        todo = self.bck_calls[:len(self.bck_calls) - self.n_sgd_calls] if skip_sgd else self.bck_calls
+        for c in todo:
             c.call_id = rtc.run(c.rfc)
         rtc.finish_and_sync()
-        ids = [c.call_id for c in self.bck_calls]
+        ids = [c.call_id for c in todo]
         self.compute_dur_ms = rtc.get_dur(ids[0], ids[-1]) if ids else 0.0
-        self.per_call_ms = [(c.tag, c.fop.get_func_name(), rtc.get_dur(i, i)) for c, i in zip(self.bck_calls, ids)]
+        self.per_call_ms = [(c.tag, c.fop.get_func_name(), rtc.get_dur(i, i)) for c, i in zip(todo, ids)]
         rtc.release_per_call_id_data()
         self._stepped = True
         return self.compute_dur_ms
@@ -526,8 +611,8 @@ class ConvPipeBck:
         deps = self._call_deps() if parallel else None   # (before the capture opens: a host-side error here leaves none behind)
         if self._graph is not None:
             rtc.graph_destroy(self._graph); self._graph = None
-        if not self._stepped:
-            self.run_device_only()
+        if not self._stepped:   # (without the update calls: a capture leaves params and history as they were; their kernel was built when they were compiled)
+            self.run_device_only(skip_sgd=True)
         rtc.finish_and_sync()
         rtc.graph_begin()
         for c in self.bck_calls:   # (a call that raises inside a capture: the backend drops the capture before it rethrows)
@@ -543,7 +628,9 @@ class ConvPipeBck:
         """deps[i] = the earlier calls that call i must run after, from the IN / OUT kinds of each call's pipe_func_args on WHOLE vars: a call runs after the last
         writer of every var it reads or writes (read-after-write, write-after-write) and after every reader since of a var it writes (write-after-read).  The in-place
         arg `inout` is read and written; a var bound to an IN and an OUT arg of one call (an in-place hip_zero_if_non_pos) likewise.  The `in` of a zero_if_in_non_pos
-        call is an IN like any other.  The params and det_drop_seed are only read inside a step and order nothing.  The hip_concat calls of one op fill disjoint
+        call is an IN like any other.  The params and det_drop_seed are only read inside a step and order nothing -- unless the
+        driver has a solver: an arg of kind INOUT (w_i, h_i of hip_sgd_update) is read and written, so an update call follows every forward and backward reader of
+        its params (write after read) and the writers of its gradients.  The hip_concat calls of one op fill disjoint
         channel ranges of one var; as whole-var writers they simply stay in list order among themselves, and a reader of the var follows the last of them."""
         writer: Dict[str, int] = {}
         readers: Dict[str, List[int]] = {}
@@ -552,9 +639,9 @@ class ConvPipeBck:
             am = c.rfc.arg_map
             rd, wr = set(), set()
             for an, io in pipe_func_args(c.fop):
-                if io == "IN" or an == "inout":
+                if io in ("IN", "INOUT") or an == "inout":
                     rd.add(am[an].n)
-                if io == "OUT":
+                if io in ("OUT", "INOUT"):
                     wr.add(am[an].n)
             d = {writer[v] for v in rd | wr if v in writer}
             for v in wr:
@@ -587,6 +674,7 @@ class ConvPipeBck:
         for v in self.vars:
             self.rtc.release_var(v)
         self.funcs, self.vars, self.bck_calls = [], [], []
+        self.n_sgd_calls = 0
         self._stepped = False
 
 

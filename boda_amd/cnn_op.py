@@ -284,6 +284,36 @@ def chan_affine_func_op(dims, relu: int) -> Op:
     return a
 
 
+SGD_UPDATE_FUNC = "hip_sgd_update"
+SGD_MAX_TENS = 32
+# the solver's function, in a table of its own (PIPE_OP_FUNCS is the gradient pipe's plumbing): no op of a pipe maps to it, ConvPipeBck appends its calls behind the gradient ops
+SGD_OP_FUNCS: Dict[str, tuple] = {"SgdUpdate": (SGD_UPDATE_FUNC,)}
+
+
+def sgd_update_func_op(dims_list, lr_mults=None, decay_mults=None) -> Op:
+    """-> the annotated function op of hip_sgd_update over the float tensors `dims_list` (1 to 32, any dims): per tensor i the var args w_i (param), g_i (gradient),
+    h_i (momentum history), all of dims_list[i], and the floats lr_mult_i / decay_mult_i (default 1); one var arg hyper, float v=4 = [lr, momentum, weight_decay, unused].
+    Per element, every operation one fp32 rounding:  g1 = g + (weight_decay * decay_mult_i) * w;  h' = momentum * h + (lr * lr_mult_i) * g1;  w' = w - h'.
+    w_i and h_i are rewritten in place, g_i and hyper only read.  This backend's own: the reference has no solver."""
+    from .op import Dims
+    dims_list = list(dims_list)
+    n = len(dims_list)
+    lr_mults = [1.0] * n if lr_mults is None else list(lr_mults)
+    decay_mults = [1.0] * n if decay_mults is None else list(decay_mults)
+    if len(lr_mults) != n or len(decay_mults) != n:
+        raise RtErr(f"sgd_update_func_op: {n} tensors, {len(lr_mults)} lr_mults, {len(decay_mults)} decay_mults")
+    v = {"tens_num": Nda(None, "uint32_t", (n,)), "hyper": Nda(dims=Dims(("v",), (4,), "float"), tn="float")}
+    for i, d in enumerate(dims_list):
+        for b in ("w", "g", "h"):
+            v[f"{b}_{i}"] = Nda(dims=d, tn=d.tn)
+        v[f"lr_mult_{i}"] = Nda(None, "float", (float(lr_mults[i]),))
+        v[f"decay_mult_{i}"] = Nda(None, "float", (float(decay_mults[i]),))
+    a = Op({"type": "SgdUpdate"}, v)
+    a.sgd_geom()
+    a.set_func_name(SGD_UPDATE_FUNC)
+    return a
+
+
 ZINP_FLAG = "zero_if_in_non_pos"   # uint32 of a function op: in_grad_loss[e] = in[e] > 0 ? g[e] : +0, hip_zero_if_non_pos's rule applied on the producer's store
 ZINP_FUNCS = ("hip_bconv_in", "hip_spreading", "hip_bck_lrn")   # the functions that write an in_grad_loss with the dims of their op's forward input `in`
 
@@ -354,8 +384,12 @@ def on_img_shards(fop: Op) -> Op:
 def pipe_func_args(fop: Op) -> tuple:
     """The (arg, IN | OUT | REF | VAL) list of an annotated function op: NATIVE_ARGS; for hip_reduce its ins_0 .. ins_{n-1} followed by out; for a hip_bconv_in /
     hip_spreading with zero_if_in_non_pos=1 the var arg `in` in front of in_grad_loss; for a hip_dropout with seed_from_var=1 the var arg det_drop_seed_var behind inout;
-    for a hip_conv_nhwc with nhwc_residual=1 the var arg `res` in front of out."""
+    for a hip_conv_nhwc with nhwc_residual=1 the var arg `res` in front of out; for hip_sgd_update w_0 g_0 h_0 .. w_{n-1} g_{n-1} h_{n-1} hyper, with the kind INOUT
+    (read and written in place) for w_i and h_i."""
     fn = fop.get_func_name()
+    if fn == SGD_UPDATE_FUNC:
+        per = tuple(x for i in range(fop.get_u32("tens_num")) for x in ((f"w_{i}", "INOUT"), (f"g_{i}", "IN"), (f"h_{i}", "INOUT")))
+        return per + NATIVE_ARGS[fn]
     if fn == "hip_dropout" and has_seed_var_flag(fop):
         return NATIVE_ARGS[fn][:1] + ((SEED_VAR_ARG, "IN"),) + NATIVE_ARGS[fn][1:]
     if fn == "hip_reduce":
@@ -400,6 +434,8 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_split": (("in", "IN"), ("out", "OUT")),
     # the forward pipe's BatchNorm / Scale runs (this backend's own; relu rides in the op)
     "hip_chan_affine": (("in", "IN"), ("a", "IN"), ("b", "IN"), ("out", "OUT")),
+    # the solver's update (this backend's own).  The list depends on the op: w_i (INOUT) g_i (IN) h_i (INOUT) per tensor in front of hyper (pipe_func_args)
+    "hip_sgd_update": (("hyper", "IN"),),
 }
 
 

@@ -250,6 +250,19 @@ void sum_loss_over_imgs(float const *loss_per_pel, float *loss, long B) {
   for (long i = 0; i < B; ++i) v = v + loss_per_pel[i];
   loss[0] = v / (float)B;
 }
+// hip_sgd_update (kernels/sgd_update_f32.hip states the formula): the same chain, every operation its own fp32 rounding, g only read
+void sgd_update(float *w, float const *g, float *h, long n, float lr_i, float wd_i, float mom) {
+#pragma omp parallel for schedule(static)
+  for (long e = 0; e < n; ++e) {
+    float const reg = wd_i * w[e];
+    float const g1 = g[e] + reg;
+    float const a = mom * h[e];
+    float const b = lr_i * g1;
+    float const h2 = a + b;
+    h[e] = h2;
+    w[e] = w[e] - h2;
+  }
+}
 #pragma GCC pop_options
 } // namespace
 
@@ -346,14 +359,15 @@ struct cpu_compute_t : public rtc_compute_t {
     for (auto const &fi : func_infos) {
       if (funcs.count(fi.func_name)) rt_err("compile: function '" + fi.func_name + "' already exists");
       string const fn = fi.op.has_func_name() ? fi.op.get_func_name() : string();
-      if (!is_sgemm(fn) && !is_conv(fn) && !is_bck(fn) && !find_bck_op(fn))
+      if (!is_sgemm(fn) && !is_conv(fn) && !is_bck(fn) && !find_bck_op(fn) && fn != "hip_sgd_update")
         unsup_err("be=cpu runs the native sgemm / Convolution / BckConv functions and the gradient pipe's non-conv functions only (hip_sgemm, hip_conv and their aliases, hip_bconv_*, "
-                  "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs, hip_reduce, hip_dropout, hip_concat, hip_split, hip_chan_affine); '" +
+                  "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs, hip_reduce, hip_dropout, hip_concat, hip_split, hip_chan_affine, hip_sgd_update); '" +
                                                     (fn.empty() ? fi.func_name : fn) + "' is generated CUCL source, which needs a GPU backend");
       if (is_conv(fn)) (void)fi.op.get_u32("conv_has_relu");
       (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
       (void)op_seed_var_flag(fi.op);   // (likewise)
       (void)op_img_shards_flag(fi.op);   // (likewise; here there is one shard: a flagged call is the unflagged one)
+      if (fn == "hip_sgd_update") (void)sgd_op_of_op(fi.op);   // (the op must be whole)
       if (bck_op_fn_t const *d = find_bck_op(fn)) {
         if (!type_ok(*d, fi.op.get_type())) rt_err(fn + ": a function of op type " + d->type + ", not " + fi.op.get_type());
         for (string const &an : bck_op_ins(*d, fi.op)) (void)fi.op.get_dims(an);
@@ -610,6 +624,30 @@ struct cpu_compute_t : public rtc_compute_t {
     }
   }
 
+  // hip_sgd_update: the checks of be=hip (csrc/native_run.cc), then the loop per tensor with lr_i / wd_i formed once
+  void run_sgd_update(op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = "hip_sgd_update";
+    sgd_op_t const so = sgd_op_of_op(op);
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    auto var_ptr = [&](string const &an) -> float * {
+      string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn);
+      if (vd.tn != "float") rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ": the update is fp32 only");
+      if (!(vd == op.get_dims(an))) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + op.get_dims(an).pretty_str());
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      return (float *)must_find(vis, vn).buf.get();
+    };
+    size_t const n = so.elems.size();
+    std::vector<float *> w(n), h(n); std::vector<float const *> g(n);
+    for (size_t i = 0; i < n; ++i) { string const sx = "_" + std::to_string(i); w[i] = var_ptr("w" + sx); g[i] = var_ptr("g" + sx); h[i] = var_ptr("h" + sx); }
+    float const *hy = var_ptr("hyper");
+    float const lr = hy[0], mom = hy[1], wd = hy[2];
+    for (size_t i = 0; i < n; ++i) {
+      float const lr_i = lr * so.lr_mult[i], wd_i = wd * so.decay_mult[i];   // (one fp32 multiply each)
+      sgd_update(w[i], g[i], h[i], so.elems[i], lr_i, wd_i, mom);
+    }
+  }
+
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
     auto fit = funcs.find(rfc.rtc_func_name);
@@ -620,7 +658,8 @@ struct cpu_compute_t : public rtc_compute_t {
     (void)op_seed_var_flag(fi.op);   // (refuses the flag on a function that cannot take it)
     (void)op_img_shards_flag(fi.op);   // (likewise)
     double const tb = now_ms();
-    if (bck_op_fn_t const *bd = find_bck_op(fn)) run_bck_op(*bd, fi.op, am);
+    if (fn == "hip_sgd_update") run_sgd_update(fi.op, am);
+    else if (bck_op_fn_t const *bd = find_bck_op(fn)) run_bck_op(*bd, fi.op, am);
     else if (is_bck(fn)) run_bck(fn, fi.op, am);
     else if (is_sgemm(fn)) {
       string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");

@@ -127,6 +127,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
   std::vector<p_rtc_compute_t> subs;
   std::map<string, multi_var_t> vis;
   std::map<string, bool> func_native;
+  std::map<string, string> funcs_op_fn;      // function -> its op's func_name ("": none)
   std::map<string, string> func_img_sum;   // native functions that reduce over the images (BckConv filter / bias gradients, the softmax loss): refused on a sharded run, with this message
   std::map<string, gen_func_t> func_gen;       // generated functions: their index declaration
   std::map<string, string> func_shards;    // native functions compiled with img_shards=1 (n() > 1): func name -> the op's function, run by run_on_img_shards
@@ -353,6 +354,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
     for (auto const &fi : func_infos) {
       bool const nat = native_kernels_t::is_native_func_name(fi.op.has_func_name() ? fi.op.get_func_name() : string());
       func_native[fi.func_name] = nat;
+      funcs_op_fn[fi.func_name] = fi.op.has_func_name() ? fi.op.get_func_name() : string();
       bool const shards = nat && op_img_shards_flag(fi.op);   // (on any other function the devices' own compile has refused the flag already)
       if (shards && n() > 1) { func_shards[fi.func_name] = fi.op.get_func_name(); continue; }
       // BckConv's filter / bias gradients sum over the images: on img shards every device would hold a partial sum, and no cross-device reduction exists here
@@ -367,8 +369,8 @@ struct hip_multi_compute_t : public rtc_compute_t {
       if (!nat) func_gen[fi.func_name] = scan_gen_func(all_src, fi.func_name);
     }
   }
-  void release_func(string const &fn) override { must_find(func_native, fn); for (auto &s : subs) s->release_func(fn); func_native.erase(fn); func_gen.erase(fn); func_img_sum.erase(fn); func_shards.erase(fn); }
-  void release_all_funcs() override { for (auto &s : subs) s->release_all_funcs(); func_native.clear(); func_gen.clear(); func_img_sum.clear(); func_shards.clear(); }
+  void release_func(string const &fn) override { must_find(func_native, fn); for (auto &s : subs) s->release_func(fn); func_native.erase(fn); funcs_op_fn.erase(fn); func_gen.erase(fn); func_img_sum.erase(fn); func_shards.erase(fn); }
+  void release_all_funcs() override { for (auto &s : subs) s->release_all_funcs(); func_native.clear(); funcs_op_fn.clear(); func_gen.clear(); func_img_sum.clear(); func_shards.clear(); }
 
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
@@ -376,6 +378,12 @@ struct hip_multi_compute_t : public rtc_compute_t {
     if (fit == func_native.end()) rt_err("run: unknown function '" + rfc.rtc_func_name + "' (not compiled, or released)");
     { auto is = func_img_sum.find(rfc.rtc_func_name); if (is != func_img_sum.end()) unsup_err("multi-device backend: '" + rfc.rtc_func_name + "' " + is->second); }
     { auto sh = func_shards.find(rfc.rtc_func_name); if (sh != func_shards.end()) return run_on_img_shards(rfc, sh->second); }
+    // hip_sgd_update: params, gradients and momentum history are REPLICATED vars, and an unflagged native call on replicated vars runs on every device (below).  The
+    // replicas stay equal by construction: every device holds the same summed gradient after run_on_img_shards' fan-out, the same hyper, the same history, and runs the
+    // same kernel -- no cross-device work of its own.  A sharded var (a leading img / M dim) would give every device another piece: refused
+    if (fit->second && must_find(funcs_op_fn, rfc.rtc_func_name) == "hip_sgd_update")
+      for (auto const &kv : rfc.arg_map) if (kv.second.is_valid() && kv.second.is_var() && must_find(vis, kv.second.n).shard_dim >= 0)
+        rt_err("multi-device backend: hip_sgd_update: arg '" + kv.first + "' (var '" + kv.second.n + "' " + must_find(vis, kv.second.n).dims.pretty_str() + ") is sharded over the devices; the update runs on replicated vars only");
     if (!fit->second) {
       bool sharded = false;
       for (auto const &kv : rfc.arg_map) if (kv.second.is_valid() && kv.second.is_var() && must_find(vis, kv.second.n).shard_dim >= 0) sharded = true;

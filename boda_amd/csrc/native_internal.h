@@ -47,7 +47,7 @@ struct native_kernels_t::impl_t {
 };
 
 
-struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false, bconv_in = false, bconv_filts = false, bck_ops = false; int rows = 0, cg = 0; };
+struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false, bconv_in = false, bconv_filts = false, bck_ops = false, sgd = false; int rows = 0, cg = 0; };
 
 struct bconv_args_t { // must match kernels/bconv_in_f32.hip, kernels/bconv_filts_f32.hip
   float const *a; float const *b; float *d;
@@ -77,6 +77,24 @@ std::vector<bck_op_desc_t const *> bck_ops_of_type(string const &t);   // the fu
 struct bck_plan_t { plan_t p; long threads = 0; uint32_t grid = 0, block = 256; int CB = 0; double algo_bytes = 0; };
 bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus);
 bck_plan_t plan_shard_sum(int nslabs, long stride, long n);   // OP 14 of the same file: no function of its own, the multi-device backend's sum of per-shard partials
+
+// hip_sgd_update (kernels/sgd_update_f32.hip): the table of up to 32 tensors rides by value in the kernel arguments
+constexpr int kSgdMaxTens = kSgdUpdateMaxTens;
+constexpr long kSgdChunk = 4096;   // floats of one tensor a workgroup owns
+struct sgd_tensor_t { // must match kernels/sgd_update_f32.hip
+  float *w; float const *g; float *h;
+  unsigned n, blk0;
+  float lr_mult, decay_mult;
+  unsigned quads, pad;
+};
+struct sgd_update_args_t { // must match kernels/sgd_update_f32.hip
+  float const *hyper;
+  unsigned tens_num, pad;
+  sgd_tensor_t t[kSgdMaxTens];
+};
+static_assert(sizeof(sgd_tensor_t) == 48 && sizeof(sgd_update_args_t) == 16 + 48 * kSgdMaxTens, "sgd_update_args_t is declared with this layout by kernels/sgd_update_f32.hip");
+struct sgd_plan_t { plan_t p; uint32_t grid = 0, block = 256; std::vector<uint32_t> blk0; double algo_bytes = 0; };
+sgd_plan_t plan_sgd_update(std::vector<long> const &elems);
 
 struct rows_args_t { // must match kernels/conv_nhwc_rows_bf16.hip
   void const *filts; void const *in; void *out; float const *bias;

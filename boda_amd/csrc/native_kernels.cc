@@ -35,7 +35,7 @@ uint32_t native_kernels_t::num_specialisations() const { return (uint32_t)impl->
 
 bool native_kernels_t::is_native_func_name(string const &fn) {
   if (fn.find("_xpose_") != string::npos) return false; // (layout passes are generated CUCL functions, as the reference's <func>_xpose_<arg>)
-  return fn == "hip_sgemm" || fn == "hip_conv" || fn == "cublas_sgemm" || fn == "cudnn_conv" || startswith(fn, "hip_");
+  return fn == "hip_sgemm" || fn == "hip_conv" || fn == "cublas_sgemm" || fn == "cudnn_conv" || fn == "hip_sgd_update" || startswith(fn, "hip_");
 }
 void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
   string const &fn = fi.op.get_func_name();
@@ -47,6 +47,11 @@ void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
   if (fn == "hip_conv_filts_kmajor") return;
   (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
   (void)op_seed_var_flag(fi.op);   // (likewise)
+  if (fn == "hip_sgd_update") {   // the op must be whole; the code object is built NOW: a first run inside a graph capture (ConvPipeBck.capture_graph never runs the update eagerly) finds it
+    sgd_op_t const so = sgd_op_of_op(fi.op);
+    (void)get_kernel(impl, host, plan_sgd_update(so.elems).p);
+    return;
+  }
   if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases") {   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     return;
@@ -79,7 +84,7 @@ void launch(native_host_t *host, kernel_t &k, gemm_args_t &a, tile_cfg_t const &
 
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log) {
   vect_string opts = p.defs; opts.push_back("-DKNAME=" + p.kname);
-  return hiprtc_compile(p.bck_ops ? k_src_bck_ops_f32 : p.bconv_in ? k_src_bconv_in_f32 : p.bconv_filts ? k_src_bconv_filts_f32 : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
+  return hiprtc_compile(p.sgd ? k_src_sgd_update_f32 : p.bck_ops ? k_src_bck_ops_f32 : p.bconv_in ? k_src_bconv_in_f32 : p.bconv_filts ? k_src_bconv_filts_f32 : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
 }
 
 // grow-only scratch shared by the split-K slabs and the Winograd-domain tensors (like the reference's cudnn scratch var)
@@ -814,6 +819,24 @@ void native_kernels_t::bck_op(bck_op_geom_t const &g, float const *const *ins, f
   if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, bp.block, params), "hipModuleLaunchKernel(bck_op)");
   last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = grid; last_launch.block = bp.block;
   last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
+}
+// ---- hip_sgd_update (kernels/sgd_update_f32.hip): one launch over all the call's tensors, the table by value in the kernel arguments
+void native_kernels_t::sgd_update(int n, sgd_member_t const *m, float const *hyper) {
+  std::vector<long> elems; for (int i = 0; i < n; ++i) elems.push_back(m[i].n);
+  sgd_plan_t const sp = plan_sgd_update(elems);
+  kernel_t &k = get_kernel(impl, host, sp.p);
+  sgd_update_args_t a; memset(&a, 0, sizeof(a));
+  a.hyper = hyper; a.tens_num = (unsigned)n;
+  for (int i = 0; i < n; ++i) {
+    sgd_tensor_t &t = a.t[i];
+    t.w = m[i].w; t.g = m[i].g; t.h = m[i].h; t.n = (unsigned)m[i].n; t.blk0 = sp.blk0[(size_t)i]; t.lr_mult = m[i].lr_mult; t.decay_mult = m[i].decay_mult;
+    t.quads = ((((uintptr_t)m[i].w | (uintptr_t)m[i].g | (uintptr_t)m[i].h) & 15) == 0) ? 1u : 0u;   // float4 where all three are 16-byte aligned (a chunk starts on a quad)
+  }
+  for (int i = n; i < kSgdMaxTens; ++i) a.t[i].blk0 = 0xffffffffu;   // (never reached: the kernel's scan stops at tens_num)
+  void *params[] = {&a};
+  if (sp.grid) hip_err_chk(host->nh_launch(k.func, sp.grid, 1, sp.block, params), "hipModuleLaunchKernel(sgd_update)");
+  last_launch.kernel = sp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = sp.grid; last_launch.block = sp.block;
+  last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
 }
 void native_kernels_t::shard_sum(float const *slabs, float *out, int nslabs, long stride, long n) {
   bck_plan_t const bp = plan_shard_sum(nslabs, stride, n);

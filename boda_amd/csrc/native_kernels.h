@@ -35,6 +35,10 @@
 //                               hip_sm_grad_and_loss then reads an optional by-value uint32 img_total of the call: the divisor
 //       hip_concat / hip_split  in out   (ocix / icix in the op: one call per input / output)                      src/rtc_fwd.cc:267-294
 //       hip_chan_affine         in a b out   (relu in the op; in and out may be one var)   out = in * a[chan] + b[chan], two roundings: the forward pipe's BatchNorm / Scale runs
+//     hip_sgd_update                    op type SgdUpdate, this backend's own (the reference has no solver): w_0 g_0 h_0 .. w_{n-1} g_{n-1} h_{n-1} hyper, n = tens_num (1 .. 32) and the
+//                                       floats lr_mult_i / decay_mult_i in the op; w_i (param) and h_i (momentum history) read and written, g_i (gradient) and hyper (float v=4:
+//                                       lr, momentum, weight_decay, unused) read.  g1 = g + (wd * decay_mult_i) * w; h' = momentum * h + (lr * lr_mult_i) * g1; w' = w - h', every
+//                                       operation one fp32 rounding.  One launch for all tensors (kernels/sgd_update_f32.hip); the code object is built when the function is compiled
 //     hip_conv_winograd                 same contract as hip_conv; 3x3 / stride-1 layers through F(2x2,3x3) Winograd (mrd <= ~2e-3)
 // and lands them on kernels/gemm_conv_f32.hip (and, for short-K 1x1 convs with a long pel axis, kernels/k1_stream_f32.hip),
 // specialised with hiprtc per shape class at first use.
@@ -141,6 +145,9 @@ struct native_kernels_t {
   void bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs, uint32_t const *seed_word = nullptr);
   // the cross-device sum of a multi-device backend (kernels/bck_ops_f32.hip OP 14): nslabs slabs of n floats at slabs + d * stride (stride in floats) -> out[e] =
   // ((slab_0[e] + slab_1[e]) + slab_2[e]) + ..., plain fp32 adds in slab order starting FROM slab 0; out may be slab 0.  Launched on this backend's stream
+  // hip_sgd_update on raw device pointers: n (1 .. 32) tensors of m[i].n floats, hyper = {lr, momentum, weight_decay, unused} in device memory
+  struct sgd_member_t { float *w; float const *g; float *h; long n; float lr_mult, decay_mult; };
+  void sgd_update(int n, sgd_member_t const *m, float const *hyper);
   void shard_sum(float const *slabs, float *out, int nslabs, long stride, long n);
   void conv_winograd(float const *filts, float const *biases, float const *in, float *out, conv_geom_t const &g, int out_ctot, int out_coff);
 

@@ -1332,4 +1332,22 @@ bck_plan_t plan_shard_sum(int nslabs, long stride, long n) {
   return r;
 }
 
+// ---- hip_sgd_update (kernels/sgd_update_f32.hip): one workgroup per chunk of kSgdChunk floats of one tensor; the grid is the sum of the tensors' chunks, blk0 its
+// prefix sums.  20 bytes move per element: w, g, h read, h and w written.
+sgd_plan_t plan_sgd_update(std::vector<long> const &elems) {
+  string const what = "hip_sgd_update";
+  if (elems.empty() || (int)elems.size() > kSgdMaxTens) rt_err(what + ": tens_num=" + std::to_string(elems.size()) + ": 1 to " + std::to_string(kSgdMaxTens) + " tensors");
+  sgd_plan_t r; r.p.sgd = true; r.p.kname = "bodahip_sgd_update";
+  uint64_t blocks = 0; double tot = 0;
+  for (long n : elems) {
+    if (n < 0) rt_err(what + ": negative size");
+    if (4.0 * (double)n >= 2147483648.0) unsup_err(what + ": tensors of 2 GiB or more (32-bit element offsets)");
+    r.blk0.push_back((uint32_t)blocks);
+    blocks += (uint64_t)((n + kSgdChunk - 1) / kSgdChunk); tot += (double)n;
+  }
+  if (blocks >= (1ull << 31)) unsup_err(what + ": too many workgroups");
+  r.grid = (uint32_t)blocks; r.algo_bytes = 20.0 * tot;
+  return r;
+}
+
 } // namespace bodahip

@@ -245,6 +245,10 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     }
     if (plan_out) *plan_out = desc;
     return bytes;
+  } else if (t == "SgdUpdate") {   // (hip_sgd_update: one kernel, no specialisation by shape; the grid is the sum of the tensors' chunks)
+    sgd_plan_t const sp = plan_sgd_update(sgd_op_of_op(op).elems);
+    if (plan_out) *plan_out = sp.p.kname + " grid=" + std::to_string(sp.grid) + " block=" + std::to_string(sp.block) + " tens=" + std::to_string(sp.blk0.size()) + " chunk=" + std::to_string(kSgdChunk);
+    return arch.empty() ? 0 : compile_plan(sp.p, arch, &log).size();
   } else if (!bck_ops_of_type(t).empty()) {   // a non-conv op of the gradient pipe: its annotated function, or (the bare op) all its functions in call order
     std::vector<bck_op_desc_t const *> ds;
     if (op.has_func_name()) {
@@ -652,6 +656,30 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
       if (fi.op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
       bconv_biases((float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(bgl), g);
     }
+    return;
+  }
+  if (fn == "hip_sgd_update") {
+    // every var must have exactly the dims the op gives its arg (params are no img shards), and the 3n + 1 vars must all be different: w_i and h_i are rewritten in place
+    sgd_op_t const so = sgd_op_of_op(fi.op);
+    int const n = (int)so.elems.size();
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    auto var_ptr = [&](string const &an) -> void * {
+      string const vn = var_of(am, an); dims_t const vd = host->nh_var_dims(vn);
+      if (vd.tn != "float") rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ": the update is fp32 only");
+      if (!(vd == fi.op.get_dims(an))) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + fi.op.get_dims(an).pretty_str());
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      return host->nh_var_ptr(vn);
+    };
+    std::vector<sgd_member_t> ms((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      string const sx = "_" + std::to_string(i);
+      sgd_member_t &m = ms[(size_t)i];
+      m.w = (float *)var_ptr("w" + sx); m.g = (float const *)var_ptr("g" + sx); m.h = (float *)var_ptr("h" + sx);
+      m.n = so.elems[(size_t)i]; m.lr_mult = so.lr_mult[(size_t)i]; m.decay_mult = so.decay_mult[(size_t)i];
+    }
+    float const *hyper = (float const *)var_ptr("hyper");
+    sgd_update(n, ms.data(), hyper);
     return;
   }
   if (bck_op_desc_t const *d = find_bck_op(fn)) {

@@ -173,6 +173,38 @@ inline void check_seed_var(string const &fn, string const &vn, dims_t const &d, 
   if (d.tn != "uint32_t" || d.dims_prod() != 1) rt_err(fn + ": seed_from_var=1: 'det_drop_seed_var' must be a uint32_t var with exactly one element, got '" + vn + "' " + d.tn + " " + d.pretty_str());
 }
 
+// ---- hip_sgd_update (op type SgdUpdate; this backend's own -- the reference has no solver): what both backends read from the function's op, and every refusal that needs
+// the op alone
+constexpr int kSgdUpdateMaxTens = 32;
+struct sgd_op_t { std::vector<long> elems; std::vector<float> lr_mult, decay_mult; };   // per tensor: element count and the two multipliers
+// hip_sgd_update: the op carries tens_num, per tensor the dims of w_i / g_i / h_i (float, identical) and the floats lr_mult_i / decay_mult_i, and hyper (float v=4)
+inline sgd_op_t sgd_op_of_op(op_base_t const &op) {
+  string const fn = "hip_sgd_update";
+  if (op.get_type() != "SgdUpdate") rt_err(fn + ": a function of op type SgdUpdate, not " + op.get_type());
+  for (char const *fl : {"img_shards", "seed_from_var", "zero_if_in_non_pos"}) if (op.has(fl) && op.get_u32(fl)) rt_err(string(fl) + "=1 on '" + fn + "': the update takes no flag");
+  if (!op.has("tens_num")) rt_err(fn + ": the op has no 'tens_num'");
+  uint32_t const n = op.get_u32("tens_num");
+  if (n < 1 || n > (uint32_t)kSgdUpdateMaxTens) rt_err(fn + ": tens_num=" + std::to_string(n) + ": 1 to " + std::to_string(kSgdUpdateMaxTens) + " tensors");
+  auto need = [&](string const &an) { if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'"); };
+  need("hyper");
+  dims_t const &hy = op.get_dims("hyper");
+  if (hy.tn != "float" || hy.sz() != 1 || hy.names(0) != "v" || hy.dims(0) != 4) rt_err(fn + ": hyper must be float v=4 (lr, momentum, weight_decay, unused), got " + hy.tn + " " + hy.pretty_str());
+  auto f32 = [&](string const &an) { p_nda_t const &v = op.get(an); if (v->dims.tn != "float" || v->dims.sz() != 0 || !v->rp) rt_err(fn + ": '" + an + "' is not a float scalar"); return *static_cast<float const *>(v->rp); };
+  sgd_op_t r;
+  for (uint32_t i = 0; i < n; ++i) {
+    string const sx = "_" + std::to_string(i);
+    for (char const *b : {"w", "g", "h", "lr_mult", "decay_mult"}) need(b + sx);
+    dims_t const &w = op.get_dims("w" + sx);
+    for (char const *b : {"w", "g", "h"}) {
+      dims_t const &d = op.get_dims(b + sx);
+      if (d.tn != "float") rt_err(fn + ": " + b + sx + " has type " + d.tn + ": the update is fp32 only");
+      if (!(d == w)) rt_err(fn + ": " + b + sx + " dims " + d.pretty_str() + " differ from w" + sx + "'s " + w.pretty_str());
+    }
+    r.elems.push_back((long)w.dims_prod()); r.lr_mult.push_back(f32("lr_mult" + sx)); r.decay_mult.push_back(f32("decay_mult" + sx));
+  }
+  return r;
+}
+
 // ---- rtc layer ----------------------------------------------------------------------------------------------------
 struct rtc_compile_opts_t {
   uint32_t show_compile_log = 0, enable_lineinfo = 0, show_func_attrs = 0, show_rtc_calls = 0;

@@ -268,10 +268,13 @@ OP_INFO = {
     "BckDropout": (("in",), ("out",), ("dropout_ratio",)),
     # this backend's own (the forward pipe's BatchNorm / Scale runs at inference, conv_pipe.fold_affine): out = in * a[chan] + b[chan], then a ReLU if relu=1
     "ChanAffine": (("in", "a", "b"), ("out",), ("relu",)),
+    # this backend's own (the reference has no solver): the SGD update of up to 32 tensors.  The multi args w / g / h ride flattened as w_0 .. w_{tens_num-1} etc., with the
+    # floats lr_mult_i / decay_mult_i beside them; w and h are read and written, g and hyper (float v=4: lr, momentum, weight_decay, unused) read
+    "SgdUpdate": (("hyper",), (), ("tens_num",)),
 }
 
 
-_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine")
+_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate")
 
 
 @dataclass
@@ -501,6 +504,27 @@ class Op:
             raise RtErr("ChanAffine: relu must be 0 | 1")
         return dict(B=i.dsz("img"), C=i.dsz("chan"), H=i.dsz("y"), W=i.dsz("x"), relu=self.get_u32("relu"))
 
+    def sgd_geom(self) -> dict:
+        """SgdUpdate: 1 to 32 tensors, w_i / g_i / h_i float of identical dims, the float scalars lr_mult_i / decay_mult_i, hyper float v=4."""
+        n = self.get_u32("tens_num")
+        if n < 1 or n > 32:
+            raise RtErr(f"SgdUpdate: tens_num={n}: 1 to 32 tensors")
+        hy = self.get_dims("hyper")
+        if hy.names != ("v",) or hy.sizes != (4,) or hy.tn != "float":
+            raise RtErr(f"SgdUpdate: hyper must be float v=4 (lr, momentum, weight_decay, unused), got {hy.tn} {hy.pretty()}")
+        elems = []
+        for i in range(n):
+            w = self.get_dims(f"w_{i}")
+            for b in ("w", "g", "h"):
+                d = self.get_dims(f"{b}_{i}")
+                if d.tn != "float":
+                    raise RtErr(f"SgdUpdate: {b}_{i} has type {d.tn}: the update is fp32 only")
+                if d != w:
+                    raise RtErr(f"SgdUpdate: {b}_{i} dims {d.pretty()} differ from w_{i}'s {w.pretty()}")
+            self.get_f32(f"lr_mult_{i}"); self.get_f32(f"decay_mult_{i}")
+            elems.append(w.dims_prod())
+        return dict(n=n, elems=elems)
+
     def concat_geom(self) -> dict:
         """Concat (ins_i -> out) / Split (in -> outs_i): float img:chan:y:x tensors of equal img / y / x whose channels add up to the wide tensor's.  -> B, H, W, CT and
         chans: per narrow tensor (arg name, first channel in the wide tensor, channels)."""
@@ -540,6 +564,8 @@ class Op:
 
     def algo_bytes(self) -> int:
         """4*(in+out+filts+biases) resp. 4*(a+b+c) (src/latex-util.H:119,133)."""
+        if self.get_type() == "SgdUpdate":   # w, g, h read, h and w written
+            return 20 * sum(self.sgd_geom()["elems"])
         ins, outs, _ = OP_INFO[self.get_type()]
         multi = {"Reduce": ("ins",), "Concat": ("ins",), "Split": ("outs",)}.get(self.get_type(), ())
         return sum(self.get_dims(a).bytes_sz() for a in ins + outs + tuple(n for m in multi for n in self.multi_names(m)))
@@ -598,6 +624,8 @@ def parse_op(line: str) -> Op:
             op.dropout_geom()
         elif t == "ChanAffine":
             op.chan_affine_geom()
+        elif t == "SgdUpdate":
+            op.sgd_geom()
         else:
             op.sgemm_geom()
     return op

@@ -6,6 +6,7 @@ and the share of the step each native function takes (sums of the backend's per-
     python tools/bck_pipe_bench.py --fuse-relu-grad [--repeats 3] [--out profiles/r09_bck_fuse_ab.txt]
     python tools/bck_pipe_bench.py --graph [--repeats 3] [--out profiles/r10_bck_graph_ab.txt]
     python tools/bck_pipe_bench.py --devices 0:1:2:3 [--out profiles/bck_pipe_devices.txt]
+    python tools/bck_pipe_bench.py --sgd [--repeats 3] [--out profiles/r13_sgd_update.txt]
 
 --fuse-relu-grad: the same step both ways in ONE process -- ConvPipeBck() and ConvPipeBck(fuse_relu_grad=True), each on a backend instance of its own with the same
 params and inputs -- after the usual warm-up, in --repeats alternating blocks of --runs steps.  Per net two JSON lines ("way": "unfused" / "fused": step ms as the median
@@ -17,6 +18,13 @@ with the same params and inputs: "eager" (run_device_only), "graph" (capture_gra
 dependencies instead of the launch order).  The seed advances per step in all three (four bytes into the det_drop_seed var).  Per net one JSON line per way (step ms as
 the median over all blocks, the block medians, images/s, the captured call count) and one with the two ratios against the eager step of the same run and whether all
 three ended with the same loss bits.  No ratio is required: the spread of the block medians is what a difference has to beat.
+
+--sgd: the same construction for the step that also updates its params (ConvPipeBck(solver=SgdSolver(...)), hip_sgd_update).  Three ways in ONE process, each on a backend
+instance of its own with the same params and inputs: "no_solver" (the step as it was), "sgd_packed" (the update as multi-tensor calls, tensors_per_call=32) and
+"sgd_per_tensor" (tensors_per_call=1: one launch per param tensor).  Per net one JSON line per way (step ms as the median over all blocks, the block medians, images/s,
+the call count; for the two solver ways the update calls alone: how many, their summed microseconds per step, and GB/s = algo_bytes / that time, algo_bytes = 20 bytes
+per param element) and one with the ratios of the same run.  The copy rate profiles/ records for this device is 6.29 TB/s.  The comparison that decides the default of
+tensors_per_call is sgd_packed against sgd_per_tensor in the same run; no figure is required.
 
 --devices d0:d1:...: the plain step on the multi-device backend `(be=hip,devices=...)`: the batch sharded on img, the five functions that are not independent per image
 run with img_shards=1.  Step ms is the longest of the devices' times; a call's share counts the time its device-side launches took, not the
@@ -126,6 +134,55 @@ def graph_ab(net, batch, runs, warmup, repeats):
         w["drv"].release(); w["rtc"].close()
 
 
+def sgd_ab(net, batch, runs, warmup, repeats):
+    import numpy as np
+    from boda_amd import conv_pipe
+    from boda_amd.bck_pipe import ConvPipeBck, SgdSolver, add_bck_ops, host_params
+    from boda_amd.rtc import make_rtc
+    cp = {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv}[net](batch)
+    bp = add_bck_ops(cp)
+    params = host_params(bp, 5)
+    rng = np.random.default_rng(0)
+    data = rng.uniform(-1, 1, cp.nodes["data"].sizes).astype(np.float32)
+    label = rng.integers(0, 1000, (batch, 1, 1)).astype(np.float32)
+    algo_bytes = 20.0 * sum(d.dims_prod() for d in cp.params.values())
+    ways = {}
+    for way, per in (("no_solver", 0), ("sgd_packed", 32), ("sgd_per_tensor", 1)):
+        rtc = make_rtc("(be=hip)", 0)
+        rtc.init()
+        solver = SgdSolver(lr=1e-5, momentum=0.9, weight_decay=5e-4, lr_mult={"biases": 2.0}, decay_mult={"biases": 0.0}, tensors_per_call=per) if per else None   # (a rate at which random labels keep every value finite)
+        drv = ConvPipeBck(rtc, solver=solver)
+        drv.init(bp, params)
+        rtc.copy_nda_to_var("data", data); rtc.copy_nda_to_var("label", label)
+        ways[way] = {"rtc": rtc, "drv": drv, "blocks": [], "ms": [], "upd_ms": []}
+    for w in ways.values():
+        for i in range(warmup):
+            w["drv"].set_det_drop_seed(i); w["drv"].run_device_only()
+    for rep in range(repeats):
+        for w in ways.values():
+            ms = []
+            for i in range(runs):
+                w["drv"].set_det_drop_seed(warmup + rep * runs + i)
+                ms.append(w["drv"].run_device_only())
+                w["upd_ms"].append(sum(d for _, fn, d in w["drv"].per_call_ms if fn == "hip_sgd_update"))
+            w["ms"] += ms; w["blocks"].append(round(statistics.median(ms), 3))
+    for way, w in ways.items():
+        step = statistics.median(w["ms"]); upd = statistics.median(w["upd_ms"])
+        rec = {"net": net, "batch": batch, "way": way, "calls": len(w["drv"].calls()), "step_ms": round(step, 3), "block_medians_ms": w["blocks"],
+               "imgs_per_s": round(batch / (step * 1e-3), 1), "loss": round(float(w["rtc"].copy_var_to_nda("loss").item()), 4)}
+        if w["drv"].n_sgd_calls:
+            rec.update({"update_calls": w["drv"].n_sgd_calls, "param_tensors": len(cp.params), "update_us": round(upd * 1e3, 1), "update_algo_bytes": algo_bytes,
+                        "update_GBps": round(algo_bytes / (upd * 1e-3) / 1e9, 1), "copy_rate_GBps_recorded": 6290.0})
+        print(json.dumps(rec), flush=True)
+    med = lambda k, f: statistics.median(ways[k][f])
+    print(json.dumps({"net": net, "sgd_packed_over_no_solver": round(med("sgd_packed", "ms") / med("no_solver", "ms"), 4),
+                      "sgd_per_tensor_over_no_solver": round(med("sgd_per_tensor", "ms") / med("no_solver", "ms"), 4),
+                      "packed_over_per_tensor_step": round(med("sgd_packed", "ms") / med("sgd_per_tensor", "ms"), 4),
+                      "packed_over_per_tensor_update": round(med("sgd_packed", "upd_ms") / med("sgd_per_tensor", "upd_ms"), 4)}), flush=True)
+    for w in ways.values():
+        w["drv"].release(); w["rtc"].close()
+
+
 def one_net(net, batch, runs, warmup, devices=""):
     import numpy as np
     from boda_amd import conv_pipe
@@ -166,16 +223,19 @@ def main(argv=None):
     ap.add_argument("--out", default="")
     ap.add_argument("--fuse-relu-grad", action="store_true", help="A/B: the step with and without the ReLU gradients folded into their producers, in one process")
     ap.add_argument("--graph", action="store_true", help="A/B: the eager step, the step as one hipGraph replay, and the replay with the calls' true dependencies, in one process")
-    ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad / --graph: alternating blocks of --runs steps per way")
+    ap.add_argument("--sgd", action="store_true", help="A/B: the step without a solver, with the SGD update as multi-tensor calls, and with one update call per tensor, in one process")
+    ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad / --graph / --sgd: alternating blocks of --runs steps per way")
     ap.add_argument("--devices", default="", help="e.g. 0:1:2:3: the plain step on the multi-device backend (be=hip,devices=...), batch sharded on img")
     ap.add_argument("--child", default="")
     a = ap.parse_args(argv)
-    if a.devices and (a.graph or a.fuse_relu_grad):
-        ap.error("--devices times the plain step: graph capture is not provided on several devices, and the fused A/B runs on one")
-    if a.graph and a.fuse_relu_grad:
-        ap.error("--graph and --fuse-relu-grad are two comparisons: run them one at a time")
-    a.out = a.out or os.path.join(ROOT, "profiles", "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "bck_pipe_devices.txt" if a.devices else "r09_bck_pipe_bench.txt")
+    if a.devices and (a.graph or a.fuse_relu_grad or a.sgd):
+        ap.error("--devices times the plain step: graph capture is not provided on several devices, and the fused and the solver A/B run on one")
+    if a.graph + a.fuse_relu_grad + a.sgd > 1:
+        ap.error("--graph, --fuse-relu-grad and --sgd are three comparisons: run them one at a time")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "bck_pipe_devices.txt" if a.devices else "r09_bck_pipe_bench.txt")
     if a.child:
+        if a.sgd:
+            return sgd_ab(a.child, a.batch, a.runs, a.warmup, a.repeats)
         if a.graph:
             return graph_ab(a.child, a.batch, a.runs, a.warmup, a.repeats)
         return fuse_ab(a.child, a.batch, a.runs, a.warmup, a.repeats) if a.fuse_relu_grad else one_net(a.child, a.batch, a.runs, a.warmup, a.devices)
@@ -184,15 +244,16 @@ def main(argv=None):
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", net, "--batch", str(a.batch), "--runs", str(a.runs), "--warmup", str(a.warmup)]
         cmd += ["--fuse-relu-grad", "--repeats", str(a.repeats)] if a.fuse_relu_grad else []
         cmd += ["--graph", "--repeats", str(a.repeats)] if a.graph else []
+        cmd += ["--sgd", "--repeats", str(a.repeats)] if a.sgd else []
         cmd += ["--devices", a.devices] if a.devices else []
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:   # nothing more is started on the GPU after a failure
             print(f"{net}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
             return r.returncode
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
-        print("\n".join(lines[-4:] if a.graph else lines[-3:] if a.fuse_relu_grad else lines[-1:]), flush=True)
+        print("\n".join(lines[-4:] if (a.graph or a.sgd) else lines[-3:] if a.fuse_relu_grad else lines[-1:]), flush=True)
     with open(a.out, "w") as f:
-        extra = f" --devices {a.devices}" if a.devices else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else ""
+        extra = f" --devices {a.devices}" if a.devices else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else ""
         f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 
