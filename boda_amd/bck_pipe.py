@@ -23,13 +23,17 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, sgd_update_func_op, add_bck_conv_annotations, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
+from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, fan_out_func_op, sgd_update_func_op, add_bck_conv_annotations, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
                      pipe_func_args, seed_from_var, SEED_VAR_ARG)
 from .conv_pipe import ConvPipe, PipeOp
 from .op import Dims, Nda, Op, RtErr, UnsupErr
 from .rtc import RtcArg, RtcFuncCall, RtcFuncInfo
 
 IN_PLACE_TYPES = ("ReLU", "Dropout", "BckDropout")   # and a ZeroIfNonPos whose out is its in (src/conv_util.cc:273-279)
+AFFINE_IN_PLACE_TYPES = ("BatchNorm", "Scale")       # ResNet's: in place on the node a convolution wrote, like a ReLU; their gradient ops must run in TRUE reverse order
+BN_IN_SFX = "_bn_in"                # <X>_bn_in: what the convolution in front of a BatchNorm wrote (X itself holds the normalised, scaled, rectified values)
+BN_MEAN_SFX, BN_ISTD_SFX = "_batch_mean", "_batch_inv_std"   # <bn-tag>_batch_mean / _batch_inv_std: the statistics of the step's batch
+BN_STAT_SFXS = ("_mean", "_var")    # a BatchNorm's params: running statistics, rewritten by the forward pass and never by a solver
 DROPOUT_RATIO = 0.5   # Dropout_coi's default (src/conv_util.cc:39); the ConvPipe records carry no ratio
 SEED_VAR = "det_drop_seed"   # ConvPipeBck(seed_in_var=True): the one-word uint32 var every dropout call reads its seed from
 DROP_LAYER_STEP = 0x9E3779B1   # the k-th Dropout layer of a pipe hashes with seed + k * this (mod 2^32)
@@ -42,7 +46,8 @@ class SgdSolver:
     """SGD with momentum and weight decay for ConvPipeBck(solver=...), Caffe's order (regularise, history, update) with the gradient left unmodified.  Per element of
     param tensor i, every operation one fp32 rounding (hip_sgd_update, cnn_op.sgd_update_func_op):
         g1 = g + (weight_decay * decay_mult_i) * w;   h' = momentum * h + (lr * lr_mult_i) * g1;   w' = w - h'
-    lr_mult / decay_mult: dicts keyed by param name (`conv1_filts`) or by the suffix `filts` / `biases`; a name wins over a suffix, the default is 1.
+    lr_mult / decay_mult: dicts keyed by param name (`conv1_filts`) or by the suffix `filts` / `biases` / `scale` / `bias`; a name wins over a suffix, the default is 1.
+    A BatchNorm's params (<tag>_mean / <tag>_var, the running statistics) are not updated: the forward pass rewrites them.
     tensors_per_call (1 .. 32): params per hip_sgd_update call, packed in the order of the pipe's params."""
     lr: float
     momentum: float = 0.9
@@ -72,7 +77,7 @@ class GradOp:
 
     @property
     def in_place(self) -> bool:
-        return self.type in IN_PLACE_TYPES or (self.type == "ZeroIfNonPos" and self.tops[0] == self.bots[0])
+        return self.type in IN_PLACE_TYPES or self.type in AFFINE_IN_PLACE_TYPES or (self.type == "ZeroIfNonPos" and self.tops[0] == self.bots[0])
 
 
 @dataclass
@@ -102,8 +107,12 @@ class BckPipe:
 def _fwd_grad_op(cp: ConvPipe, o: PipeOp) -> GradOp:
     if o.type == "Convolution":
         return GradOp(o.tag, o.type, [o.bot, o.tag + "_filts", o.tag + "_biases"], [o.top], o)
-    if o.type == "Concat":
+    if o.type in ("Concat", "Eltwise"):
         return GradOp(o.tag, o.type, list(o.bots), [o.top], o)
+    if o.type == "BatchNorm":   # in place; the running statistics are params it reads AND rewrites
+        return GradOp(o.tag, o.type, [o.bot, o.tag + "_mean", o.tag + "_var"], [o.top], o)
+    if o.type == "Scale":
+        return GradOp(o.tag, o.type, [o.bot, o.tag + "_scale", o.tag + "_bias"], [o.top], o)
     return GradOp(o.tag, o.type, [o.bot], [o.top], o)
 
 
@@ -171,6 +180,13 @@ def add_bck_ops(cp: ConvPipe, label_node: str = "label", loss_tops: Optional[Seq
             return GradOp(tag, "Split", [cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, b) for b in cop.bots], cop.src)
         if t == "LRN":        # { in, out, out_grad_loss } -> in_grad_loss
             return GradOp(tag, "BckLRN", [cop.bots[0], cop.tops[0], cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, cop.bots[0])], cop.src)
+        if t == "Scale":      # { X_grad_loss, X, scale } -> X_grad_loss in place, and the two param gradients
+            gl = grad_loss_onn(cop, cop.bots[0])
+            return GradOp(tag, "BckScale", [cop.tops[0] + "_grad_loss", cop.bots[0], cop.bots[1]], [gl, cop.bots[1] + "_grad_loss", cop.bots[2] + "_grad_loss"], cop.src)
+        if t == "BatchNorm":  # { X_grad_loss, X } -> X_grad_loss in place; _mean / _var get no gradient node
+            return GradOp(tag, "BckBatchNorm", [cop.tops[0] + "_grad_loss", cop.bots[0]], [grad_loss_onn(cop, cop.bots[0])], cop.src)
+        if t == "Eltwise":    # { top_grad_loss } -> one gradient node per bottom (a SUM hands its gradient to every term)
+            return GradOp(tag, "BckEltwise", [cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, b) for b in cop.bots], cop.src)
         raise RtErr(f"FIXME: add_bck_ops: unhandled cop->type={t}")
 
     seen: Dict[str, int] = {}
@@ -181,7 +197,11 @@ def add_bck_ops(cp: ConvPipe, label_node: str = "label", loss_tops: Optional[Seq
         if not n.bot_for:   # a sink: must be what a SoftmaxWithLoss wrote
             if len(n.top_for) != 1 or by_tag[n.top_for[0]].type != "SoftmaxWithLoss":
                 raise RtErr(f"add_bck_ops: unhandled: top node {nn} not produced by SoftmaxWithLoss op")
-        for ip in reversed(n.in_place_ops):
+        # the walk appends a node's in-place gradient ops reversed and the whole list is reversed again below: they RUN in forward order, which is harmless for ReLU /
+        # Dropout (they commute; the reference does the same and existing lists pin it) and wrong for [BatchNorm, Scale, ReLU].  A node with a BatchNorm or a Scale
+        # among its in-place ops gets them in true reverse: ZeroIfNonPos, BckScale, BckBatchNorm
+        affine = any(ip.type in AFFINE_IN_PLACE_TYPES for ip in n.in_place_ops)
+        for ip in (n.in_place_ops if affine else reversed(n.in_place_ops)):
             b = bck_of(ip)
             if b:
                 walk.append(b)
@@ -212,9 +232,14 @@ def add_bck_ops(cp: ConvPipe, label_node: str = "label", loss_tops: Optional[Seq
         if b.type == "BckConv":
             for t, s in zip(b.tops, b.bots[:3]):
                 nodes[t] = nodes[s]
-        elif b.type == "Split":
+        elif b.type in ("Split", "BckEltwise"):
+            if b.type == "BckEltwise" and len(set(b.tops)) != len(b.tops):
+                raise UnsupErr(f"add_bck_ops: {b.tag}: the Eltwise sums one node twice")
             for t, s in zip(b.tops, b.src.bots):
                 nodes[t] = nodes[s]
+        elif b.type == "BckScale":
+            nodes[b.tops[0]] = nodes[b.bots[0]]
+            nodes[b.tops[1]] = cp.params[b.src.tag + "_scale"]; nodes[b.tops[2]] = cp.params[b.src.tag + "_bias"]
         elif b.type in ("Spreading", "BckLRN"):
             nodes[b.tops[0]] = nodes[b.src.bot]
         elif b.type == "Reduce":
@@ -270,10 +295,10 @@ def grad_op_to_op(bp: BckPipe, o: GradOp) -> Op:
         return Op({"type": t}, {"in": nd(o.bots[0]), "out": nd(o.tops[0]), "dropout_ratio": _f32(getattr(s, "dropout_ratio", DROPOUT_RATIO))})
     if t == "SoftmaxWithLoss":
         return Op({"type": t}, {"in": nd(o.bots[0]), "label": nd(o.bots[1]), "in_grad_loss": nd(o.tops[0]), "loss": nd(o.tops[1])})
-    if t in ("Reduce", "Concat"):
+    if t in ("Reduce", "Concat", "Eltwise"):   # (an Eltwise SUM runs as a Reduce: a sequential fp32 chain from +0 in the order of its bottoms)
         v = {f"ins_{i}": nd(b) for i, b in enumerate(o.bots)}
         v.update({"ins_num": _u32(len(o.bots)), "out": nd(o.tops[0])})
-        return Op({"type": t}, v)
+        return Op({"type": "Reduce" if t == "Eltwise" else t}, v)
     if t == "Split":
         v = {f"outs_{i}": nd(b) for i, b in enumerate(o.tops)}
         v.update({"outs_num": _u32(len(o.tops)), "in": nd(o.bots[0])})
@@ -293,15 +318,28 @@ class BckCall:
     call_id: int = -1
 
 
+def bn_stat_params(cp: ConvPipe) -> List[str]:
+    """The running-statistics params of the pipe's BatchNorm ops (<tag>_mean, <tag>_var): rewritten by the forward pass, without a gradient, never updated by a solver."""
+    return [o.tag + sfx for o in cp.ops if o.type == "BatchNorm" for sfx in BN_STAT_SFXS]
+
+
 def host_params(bp: BckPipe, seed: int = 0) -> Dict[str, np.ndarray]:
     """Deterministic host-made params for a pipe without trained weights: filts ~ N(0, 2 / fan_in) (so activations neither die nor blow up through the ReLUs), biases
-    ~ U(-0.1, 0.1), each seeded by its name.  (ConvPipeFwd's device generator is generated CUCL source, which be=cpu cannot run.)"""
+    ~ U(-0.1, 0.1), a BatchNorm's _mean 0 and _var 1, a Scale's _scale ~ U(0.9, 1.1) and _bias ~ U(-0.05, 0.05), each seeded by its name.  (ConvPipeFwd's device generator is generated CUCL source, which be=cpu cannot run.)"""
     out = {}
+    stats = bn_stat_params(bp.cp)
+    scales = {o.tag + "_scale" for o in bp.cp.ops if o.type == "Scale"}; sbias = {o.tag + "_bias" for o in bp.cp.ops if o.type == "Scale"}
     for n, d in bp.cp.params.items():
         rng = np.random.default_rng([zlib.crc32(n.encode()), seed])
         if n.endswith("_filts"):
             fan_in = d.dsz("in_chan") * d.dsz("y") * d.dsz("x")
             out[n] = (rng.standard_normal(d.sizes) * np.sqrt(2.0 / fan_in)).astype(np.float32)
+        elif n in stats:         # a BatchNorm's running pair starts at (0, 1)
+            out[n] = (np.zeros if n.endswith("_mean") else np.ones)(d.sizes, np.float32)
+        elif n in scales:
+            out[n] = rng.uniform(0.9, 1.1, d.sizes).astype(np.float32)
+        elif n in sbias:
+            out[n] = rng.uniform(-0.05, 0.05, d.sizes).astype(np.float32)
         else:
             out[n] = rng.uniform(-0.1, 0.1, d.sizes).astype(np.float32)
     return out
@@ -360,11 +398,18 @@ class ConvPipeBck:
     END of the call list, behind every gradient op: tensors_per_call params per call in the order of the pipe's params, g_i bound to <param>_grad_loss.
     set_sgd_hyper uploads 16 bytes and touches no call (valid between graph replays: a learning-rate schedule needs no new capture); zero_sgd_history clears the
     history.  capture_graph captures the update calls with the rest and leaves params and history as they were.  On a multi-device backend the update runs on every
-    device's replicas, which hold the same summed gradients and so stay equal."""
+    device's replicas, which hold the same summed gradients and so stay equal.
+    BatchNorm / Scale: exactly the run [BatchNorm, Scale] plus an optional in-place ReLU behind it, on a node X a Convolution produces, is
+    supported -- all ResNet-50 has.  It runs as a TRAINING BatchNorm: the convolution (conv_has_relu=0) writes the side var <X>_bn_in; hip_bn_stats reads it and writes
+    <bn-tag>_batch_mean / _batch_inv_std and moves the running pair <bn-tag>_mean / _var by bn_maf; hip_bn_fwd writes X, ReLU included.  Backward, BckScale is
+    hip_bn_bck_sums (-> <scale-tag>_scale_grad_loss / _bias_grad_loss) and BckBatchNorm hip_bn_bck_in, in place on X_grad_loss, both recomputing the normalised value
+    from <X>_bn_in.  An Eltwise runs as hip_reduce, its gradient as one hip_fan_out.  A solver leaves <bn-tag>_mean / _var alone.  Not on a multi-device backend: init refuses a pipe with a BatchNorm or an Eltwise there before creating anything."""
 
-    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[SgdSolver] = None):
+    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[SgdSolver] = None, bn_maf: float = 0.999):
         self.rtc = rtc
         self.solver = solver
+        self.bn_maf = float(bn_maf)   # a training BatchNorm's moving-average fraction: run' = maf * run + (1 - maf) * batch
+        self.sgd_params: List[str] = []   # the params the solver updates: all of them but the BatchNorm running statistics
         self.n_sgd_calls = 0       # the update calls, the last n_sgd_calls of bck_calls
         self.op_tune = op_tune or OpTune()
         self.fuse_relu_grad = bool(fuse_relu_grad)
@@ -392,17 +437,35 @@ class ConvPipeBck:
         self._stepped = False
         if self.seed_in_var and SEED_VAR in bp.nodes:
             raise RtErr(f"ConvPipeBck.init: seed_in_var=True needs the var name {SEED_VAR!r}, which is a node of the pipe")
+        multi_dev = isinstance(getattr(rtc, "devices", None), list) and len(rtc.devices) > 1
+        bn_runs = self._plan_bn_runs(bp)   # node X -> (BatchNorm op, Scale op, the ReLU behind them or None); every other shape of BatchNorm / Scale is refused here
+        if bn_runs and multi_dev:
+            raise UnsupErr("ConvPipeBck.init: the pipe has a BatchNorm, whose batch statistics sum over the images of the WHOLE batch: not provided on a multi-device backend "
+                           "(devices=...); statistics summed across img shards are out of scope")
+        if multi_dev and any(o.type == "BckEltwise" for o in bp.bck_ops()):
+            raise UnsupErr("ConvPipeBck.init: the pipe has an Eltwise, whose gradient (hip_fan_out) takes vars of exactly its op's dims, not img shards: not provided on a "
+                           "multi-device backend (devices=...)")
+        stats = set(bn_stat_params(bp.cp))
+        self.sgd_params = [pn for pn in bp.cp.params if pn not in stats]
         if self.solver is not None:   # (refused before anything is created)
             if not 1 <= int(self.solver.tensors_per_call) <= SGD_MAX_TENS:
                 raise RtErr(f"ConvPipeBck.init: SgdSolver.tensors_per_call={self.solver.tensors_per_call}: 1 to {SGD_MAX_TENS}")
-            for vn in [pn + SGD_HIST_SFX for pn in bp.cp.params] + [SGD_HYPER_VAR]:
+            for vn in [pn + SGD_HIST_SFX for pn in self.sgd_params] + [SGD_HYPER_VAR]:
                 if vn in bp.nodes:
                     raise RtErr(f"ConvPipeBck.init: the solver needs the var name {vn!r}, which is a node of the pipe")
-            for pn in bp.cp.params:
+            for pn in self.sgd_params:
                 if pn + "_grad_loss" not in bp.nodes:
                     raise RtErr(f"ConvPipeBck.init: the solver: no gradient op writes {pn + '_grad_loss'!r}")
+        for x, (bn, sc, _) in bn_runs.items():
+            for vn in (x + BN_IN_SFX, bn.tag + BN_MEAN_SFX, bn.tag + BN_ISTD_SFX):
+                if vn in bp.nodes:
+                    raise RtErr(f"ConvPipeBck.init: the BatchNorm on {x} needs the var name {vn!r}, which is a node of the pipe")
         for n, d in bp.nodes.items():
             self._var(n, d)
+        for x, (bn, sc, _) in bn_runs.items():
+            self._var(x + BN_IN_SFX, bp.nodes[x])
+            for sfx in (BN_MEAN_SFX, BN_ISTD_SFX):
+                self._var(bn.tag + sfx, bp.cp.params[bn.tag + "_mean"])
         if self.seed_in_var:
             self._var(SEED_VAR, Dims(("v",), (1,), "uint32_t"))
         fused = set()   # ReLUs taken into their convolution (src/rtc_fwd.cc:486-493): no forward call, their ZeroIfNonPos still runs
@@ -414,11 +477,14 @@ class ConvPipeBck:
                 relu_of[o.tag] = bool(first_ip and first_ip.type == "ReLU")
                 if relu_of[o.tag]:
                     fused.add(first_ip.tag)
+        for x, (bn, sc, relu) in bn_runs.items():   # the ReLU behind a [BatchNorm, Scale] run is hip_bn_fwd's
+            if relu is not None:
+                fused.add(relu.tag)
+        bn_of_tag = {q.tag: (x, run) for x, run in bn_runs.items() for q in run[:2]}
         folds, why = plan_relu_grad_folds(bp) if self.fuse_relu_grad else ({}, {o.tag: "fuse_relu_grad is off" for o in bp.bck_ops() if o.type == "ZeroIfNonPos"})
         self.fused_relu_grads = {"folded": list(folds), "unfolded": why}
         takes_relu = set(folds.values())   # the gradient ops that apply the mask of the ZeroIfNonPos behind them
         zinp = lambda o, f: fuse_zero_if_in_non_pos(f) if o.tag in takes_relu else f
-        multi_dev = isinstance(getattr(rtc, "devices", None), list) and len(rtc.devices) > 1
         infos: List[RtcFuncInfo] = []
 
         def emit(tag: str, fop: Op, args: Dict[str, str]) -> None:
@@ -441,13 +507,35 @@ class ConvPipeBck:
         for o in ops:
             if o.tag in fused or o.tag in folds:
                 continue
-            op = grad_op_to_op(bp, o)
             t = o.type
             calls: List[Tuple[Op, Dict[str, str]]] = []
+            if t in ("BatchNorm", "Scale", "BckScale", "BckBatchNorm"):
+                # a [BatchNorm, Scale (, ReLU)] run on X: statistics at the BatchNorm, normalise + scale + bias + ReLU at the Scale; backward the two sums at BckScale and
+                # the data gradient at BckBatchNorm, in place on X_grad_loss.  The normalised value is recomputed from <X>_bn_in everywhere: nothing is saved twice
+                x, (bn, sc, relu) = bn_of_tag[o.src.tag]
+                xd = bp.nodes[x]
+                common = {"in": x + BN_IN_SFX, "mean": bn.tag + BN_MEAN_SFX, "inv_std": bn.tag + BN_ISTD_SFX}
+                if t == "BatchNorm":
+                    calls.append((bn_stats_func_op(xd, bn.eps, self.bn_maf), dict(common, run_mean=bn.tag + "_mean", run_var=bn.tag + "_var")))
+                elif t == "Scale":
+                    calls.append((bn_fwd_func_op(xd, 1 if relu is not None else 0), dict(common, scale=sc.tag + "_scale", bias=sc.tag + "_bias", out=x)))
+                elif t == "BckScale":
+                    calls.append((bn_bck_sums_func_op(xd), dict(common, out_grad_loss=o.bots[0], scale_grad_loss=o.tops[1], bias_grad_loss=o.tops[2])))
+                else:
+                    calls.append((bn_bck_in_func_op(xd), dict(common, scale=sc.tag + "_scale", scale_grad_loss=sc.tag + "_scale_grad_loss", bias_grad_loss=sc.tag + "_bias_grad_loss",
+                                                              out_grad_loss=o.bots[0], in_grad_loss=o.tops[0])))
+                for fop, args in calls:
+                    emit(o.tag, fop, args)
+                continue
+            if t == "BckEltwise":
+                emit(o.tag, fan_out_func_op(bp.nodes[o.bots[0]], len(o.tops)), dict({f"outs_{i}": tp for i, tp in enumerate(o.tops)}, **{"in": o.bots[0]}))
+                continue
+            op = grad_op_to_op(bp, o)
             if t == "Convolution":
                 a = add_codegen_annotations(op, tune)
                 a.nda_vals["conv_has_relu"] = _u32(1 if relu_of[o.tag] else 0)
-                calls.append((a, {"filts": o.bots[1], "biases": o.bots[2], "in": o.bots[0], "out": o.tops[0]}))
+                # (in front of a BatchNorm the convolution writes the side var <X>_bn_in: X itself is written by hip_bn_fwd)
+                calls.append((a, {"filts": o.bots[1], "biases": o.bots[2], "in": o.bots[0], "out": o.tops[0] + BN_IN_SFX if o.tops[0] in bn_runs else o.tops[0]}))
             elif t == "ReLU":    # one that follows no convolution: out = in > 0 ? in : +0 is hip_zero_if_non_pos with the node as its own condition
                 z = Op({"type": "ZeroIfNonPos"}, {"in": op_nd(bp, o.bots[0]), "cond": op_nd(bp, o.bots[0]), "out": op_nd(bp, o.bots[0])})
                 calls.append((add_bck_op_annotations(z, tune)[0], {"in": o.bots[0], "cond": o.bots[0], "out": o.bots[0]}))
@@ -480,7 +568,7 @@ class ConvPipeBck:
             elif t in ("Dropout", "BckDropout"):
                 fd = add_pipe_op_annotations(op, tune)[0]
                 calls.append((seed_from_var(fd), {"inout": o.tops[0], SEED_VAR_ARG: SEED_VAR}) if self.seed_in_var else (fd, {"inout": o.tops[0]}))
-            elif t == "Reduce":
+            elif t in ("Reduce", "Eltwise"):
                 calls.append((add_pipe_op_annotations(op, tune)[0], dict({f"ins_{i}": b for i, b in enumerate(o.bots)}, out=o.tops[0])))
             elif t == "Concat":
                 for f, b in zip(add_pipe_op_annotations(op, tune), o.bots):
@@ -495,7 +583,7 @@ class ConvPipeBck:
         self.n_sgd_calls = 0
         if self.solver is not None:   # the update calls, behind every gradient op
             sv = self.solver
-            pnames = list(bp.cp.params)
+            pnames = list(self.sgd_params)
             for pn in pnames:
                 self._var(pn + SGD_HIST_SFX, bp.cp.params[pn])
             self._var(SGD_HYPER_VAR, Dims(("v",), (4,), "float"))
@@ -523,6 +611,26 @@ class ConvPipeBck:
             self.zero_sgd_history()
             self.set_sgd_hyper()
 
+    @staticmethod
+    def _plan_bn_runs(bp: BckPipe) -> Dict[str, tuple]:
+        """node X -> (BatchNorm op, Scale op, the in-place ReLU behind them or None) for every BatchNorm / Scale of the pipe; raises UnsupErr for every shape but
+        [BatchNorm, Scale] (+ ReLU) on a node a Convolution produces."""
+        fwd = [o.src for o in bp.fwd_ops() if o.src is not None]
+        runs: Dict[str, tuple] = {}
+        producer = {o.top: o for o in fwd if not o.in_place}
+        for x in dict.fromkeys(o.bot for o in fwd if o.type in AFFINE_IN_PLACE_TYPES):
+            ips = [o for o in fwd if o.in_place and o.bot == x]
+            kinds = [o.type for o in ips]
+            what = f"the in-place ops on {x} are {' '.join(kinds)}"
+            if x not in producer or producer[x].type != "Convolution":
+                raise UnsupErr(f"ConvPipeBck: a BatchNorm / Scale on {x}, which {'a ' + producer[x].type if x in producer else 'no op'} produces; only [BatchNorm, Scale] (+ ReLU) behind a Convolution is supported")
+            if kinds[:2] != ["BatchNorm", "Scale"]:
+                raise UnsupErr(f"ConvPipeBck: {what}; only the run [BatchNorm, Scale] (+ ReLU) is supported (a training BatchNorm and its Scale run as one function)")
+            if kinds[2:] not in ([], ["ReLU"]):
+                raise UnsupErr(f"ConvPipeBck: {what}; behind [BatchNorm, Scale] only one in-place ReLU is supported")
+            runs[x] = (ips[0], ips[1], ips[2] if len(ips) > 2 else None)
+        return runs
+
     def set_sgd_hyper(self, lr: Optional[float] = None, momentum: Optional[float] = None, weight_decay: Optional[float] = None) -> None:
         """Upload the 16 bytes of sgd_hyper with the values given replaced (None: kept).  Touches no call: the next step -- eager or a graph replay -- reads them."""
         if self.solver is None:
@@ -536,8 +644,8 @@ class ConvPipeBck:
         """Clear every <param>_sgd_hist."""
         if self.solver is None:
             raise RtErr("ConvPipeBck.zero_sgd_history: the driver was built without a solver")
-        for pn, d in self.bp.cp.params.items():
-            self.rtc.copy_nda_to_var(pn + SGD_HIST_SFX, np.zeros(d.sizes, np.float32))
+        for pn in self.sgd_params:
+            self.rtc.copy_nda_to_var(pn + SGD_HIST_SFX, np.zeros(self.bp.cp.params[pn].sizes, np.float32))
 
     def _dropout_calls(self) -> List[Tuple[BckCall, int]]:
         """The dropout calls of the step with their layer's index among the pipe's Dropout ops (a layer's forward and backward call share it)."""
@@ -612,7 +720,10 @@ class ConvPipeBck:
         if self._graph is not None:
             rtc.graph_destroy(self._graph); self._graph = None
         if not self._stepped:   # (without the update calls: a capture leaves params and history as they were; their kernel was built when they were compiled)
+            stats = {vn: rtc.copy_var_to_nda(vn) for vn in bn_stat_params(self.bp.cp)}   # (a forward pass moves a BatchNorm's running pair: put back below)
             self.run_device_only(skip_sgd=True)
+            for vn, a in stats.items():
+                rtc.copy_nda_to_var(vn, a)
         rtc.finish_and_sync()
         rtc.graph_begin()
         for c in self.bck_calls:   # (a call that raises inside a capture: the backend drops the capture before it rethrows)

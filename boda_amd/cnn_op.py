@@ -314,6 +314,77 @@ def sgd_update_func_op(dims_list, lr_mults=None, decay_mults=None) -> Op:
     return a
 
 
+# the training BatchNorm of the gradient pipe and the Eltwise-SUM gradient, in a table of their own (PIPE_OP_FUNCS is pinned): what bck_pipe.ConvPipeBck runs for a
+# BatchNorm + Scale (+ ReLU) run and its gradient, and for a BckEltwise.  This backend's own arithmetic: csrc/kernels/bn_f32.hip and DESIGN.md section 3.15 state it
+BN_OP_FUNCS: Dict[str, tuple] = {
+    "BnStats": ("hip_bn_stats",),
+    "BnFwd": ("hip_bn_fwd",),
+    "BnBckSums": ("hip_bn_bck_sums",),
+    "BnBckIn": ("hip_bn_bck_in",),
+    "FanOut": ("hip_fan_out",),
+}
+BN_FUNCS = tuple(v[0] for v in BN_OP_FUNCS.values())
+
+
+def _as_f32(v: float) -> float:
+    """The value a float scalar of an op holds: rounded to fp32 once, here."""
+    import struct
+    return struct.unpack("f", struct.pack("f", float(v)))[0]
+
+
+def _bn_func_op(t: str, dims, tens, chans, **scalars) -> Op:
+    from .op import Dims
+    if dims.names != ("img", "chan", "y", "x") or dims.tn != "float":
+        raise RtErr(f"{t}: in must be float img:chan:y:x, got {dims.tn} {dims.pretty()}")
+    ch = Dims(("chan",), (dims.dsz("chan"),), "float")
+    v = {an: Nda(dims=dims, tn="float") for an in tens}
+    v.update({an: Nda(dims=ch, tn="float") for an in chans})
+    for k, (tn, val) in scalars.items():
+        v[k] = Nda(None, tn, (_as_f32(val) if tn == "float" else val,))
+    a = Op({"type": t}, v)
+    a.bn_geom()
+    a.set_func_name(BN_OP_FUNCS[t][0])
+    return a
+
+
+def bn_stats_func_op(dims, eps: float, maf: float, slab: int = 0) -> Op:
+    """-> the annotated function op of hip_bn_stats on a float img:chan:y:x tensor `dims`: args in (IN), mean, inv_std (OUT), run_mean, run_var (INOUT), the per-channel
+    ones float chan=C.  mean = S1 / N, var = S2 / N (two passes, biased), inv_std = 1 / sqrtf(var + eps), run' = maf * run + (1 - maf) * (mean | var * N / (N - 1)).
+    slab > 0 (a multiple of 4) forces the slab length of the sums' chain; 0: the planner's."""
+    return _bn_func_op("BnStats", dims, ("in",), ("mean", "inv_std", "run_mean", "run_var"), eps=("float", float(eps)), maf=("float", float(maf)), slab=("uint32_t", int(slab)))
+
+
+def bn_fwd_func_op(dims, relu: int) -> Op:
+    """-> hip_bn_fwd: out = ((in - mean[c]) * inv_std[c]) * scale[c] + bias[c], with relu=1 followed by y > 0 ? y : +0.  Args in, mean, inv_std, scale, bias (IN), out
+    (OUT); in and out may be one var."""
+    return _bn_func_op("BnFwd", dims, ("in", "out"), ("mean", "inv_std", "scale", "bias"), relu=("uint32_t", int(relu)))
+
+
+def bn_bck_sums_func_op(dims, slab: int = 0) -> Op:
+    """-> hip_bn_bck_sums: scale_grad_loss = SUM dy * xh, bias_grad_loss = SUM dy per channel, xh recomputed from in, mean, inv_std.  Args in, mean, inv_std,
+    out_grad_loss (IN), scale_grad_loss, bias_grad_loss (OUT)."""
+    return _bn_func_op("BnBckSums", dims, ("in", "out_grad_loss"), ("mean", "inv_std", "scale_grad_loss", "bias_grad_loss"), slab=("uint32_t", int(slab)))
+
+
+def bn_bck_in_func_op(dims) -> Op:
+    """-> hip_bn_bck_in: dx = (scale * inv_std) * ((dy - bias_grad_loss / N) - xh * (scale_grad_loss / N)).  Args in, mean, inv_std, scale, scale_grad_loss,
+    bias_grad_loss, out_grad_loss (IN), in_grad_loss (OUT, may be out_grad_loss's var)."""
+    return _bn_func_op("BnBckIn", dims, ("in", "out_grad_loss", "in_grad_loss"), ("mean", "inv_std", "scale", "scale_grad_loss", "bias_grad_loss"))
+
+
+def fan_out_func_op(dims, n: int) -> Op:
+    """-> hip_fan_out, the gradient of an Eltwise SUM: args in (IN), outs_0 .. outs_{n-1} (OUT), 2 <= n <= 8, float tensors of equal dims; every outs_i = in bit for bit."""
+    if dims.tn != "float":
+        raise RtErr(f"FanOut: in has type {dims.tn}: fp32 only")
+    v = {"in": Nda(dims=dims, tn="float"), "outs_num": Nda(None, "uint32_t", (int(n),))}
+    for i in range(int(n)):
+        v[f"outs_{i}"] = Nda(dims=dims, tn="float")
+    a = Op({"type": "FanOut"}, v)
+    a.bn_geom()
+    a.set_func_name("hip_fan_out")
+    return a
+
+
 ZINP_FLAG = "zero_if_in_non_pos"   # uint32 of a function op: in_grad_loss[e] = in[e] > 0 ? g[e] : +0, hip_zero_if_non_pos's rule applied on the producer's store
 ZINP_FUNCS = ("hip_bconv_in", "hip_spreading", "hip_bck_lrn")   # the functions that write an in_grad_loss with the dims of their op's forward input `in`
 
@@ -390,6 +461,8 @@ def pipe_func_args(fop: Op) -> tuple:
     if fn == SGD_UPDATE_FUNC:
         per = tuple(x for i in range(fop.get_u32("tens_num")) for x in ((f"w_{i}", "INOUT"), (f"g_{i}", "IN"), (f"h_{i}", "INOUT")))
         return per + NATIVE_ARGS[fn]
+    if fn == "hip_fan_out":
+        return NATIVE_ARGS[fn] + tuple((an, "OUT") for an in fop.multi_names("outs"))
     if fn == "hip_dropout" and has_seed_var_flag(fop):
         return NATIVE_ARGS[fn][:1] + ((SEED_VAR_ARG, "IN"),) + NATIVE_ARGS[fn][1:]
     if fn == "hip_reduce":
@@ -436,6 +509,13 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_chan_affine": (("in", "IN"), ("a", "IN"), ("b", "IN"), ("out", "OUT")),
     # the solver's update (this backend's own).  The list depends on the op: w_i (INOUT) g_i (IN) h_i (INOUT) per tensor in front of hyper (pipe_func_args)
     "hip_sgd_update": (("hyper", "IN"),),
+    # the training BatchNorm and the Eltwise-SUM gradient (this backend's own; eps / maf / slab / relu ride in the op).  hip_fan_out's list depends on the op: in,
+    # then outs_0 .. outs_{n-1} (pipe_func_args)
+    "hip_bn_stats": (("in", "IN"), ("mean", "OUT"), ("inv_std", "OUT"), ("run_mean", "INOUT"), ("run_var", "INOUT")),
+    "hip_bn_fwd": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("scale", "IN"), ("bias", "IN"), ("out", "OUT")),
+    "hip_bn_bck_sums": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("out_grad_loss", "IN"), ("scale_grad_loss", "OUT"), ("bias_grad_loss", "OUT")),
+    "hip_bn_bck_in": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("scale", "IN"), ("scale_grad_loss", "IN"), ("bias_grad_loss", "IN"), ("out_grad_loss", "IN"), ("in_grad_loss", "OUT")),
+    "hip_fan_out": (("in", "IN"),),
 }
 
 

@@ -263,6 +263,88 @@ void sgd_update(float *w, float const *g, float *h, long n, float lr_i, float wd
     w[e] = w[e] - h2;
   }
 }
+// ---- the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip states the formulas and the chain of the sums): the same operations in the same order.
+// One slab of one channel: 256 chains, chain t owning the elements with (r / 4) mod 256 == t in ascending r, then the fixed tree.  term(e, acc0, acc1) adds element e's terms
+template <typename TermF> void bn_slab_sums(long e0, long len, TermF term, float &P0, float &P1) {
+  float a0[256], a1[256];
+  for (int t = 0; t < 256; ++t) { a0[t] = 0.0f; a1[t] = 0.0f; }
+  for (long r = 0; r < len; ++r) { int const t = (int)((r >> 2) & 255); term(e0 + r, a0[t], a1[t]); }
+  for (int h = 128; h > 0; h >>= 1) for (int t = 0; t < h; ++t) { a0[t] = a0[t] + a0[t + h]; a1[t] = a1[t] + a1[t + h]; }
+  P0 = a0[0]; P1 = a1[0];
+}
+// the sums of every channel: slab partials in slab order starting from P_0 -> S0[c], S1[c]
+template <typename TermOfChanF> void bn_chan_sums(bn_op_t const &b, TermOfChanF term_of, float *S0, float *S1) {
+  std::vector<float> P0((size_t)(b.C * b.nslabs)), P1((size_t)(b.C * b.nslabs));
+#pragma omp parallel for schedule(static)
+  for (long cs = 0; cs < b.C * b.nslabs; ++cs) {
+    long const c = cs / b.nslabs, s = cs - c * b.nslabs, e0 = s * b.slab, len = std::min(b.slab, b.N - e0);
+    bn_slab_sums(e0, len, term_of(c), P0[(size_t)cs], P1[(size_t)cs]);
+  }
+  for (long c = 0; c < b.C; ++c) {
+    float A = P0[(size_t)(c * b.nslabs)], B = P1[(size_t)(c * b.nslabs)];
+    for (long i = 1; i < b.nslabs; ++i) { A = A + P0[(size_t)(c * b.nslabs + i)]; B = B + P1[(size_t)(c * b.nslabs + i)]; }
+    S0[c] = A; S1[c] = B;
+  }
+}
+inline long bn_off(bn_op_t const &b, long c, long e) { long const img = e / b.HW; return (img * b.C + c) * b.HW + (e - img * b.HW); }
+void bn_stats(bn_op_t const &b, float const *in, float *mean, float *inv_std, float *run_mean, float *run_var) {
+  std::vector<float> S1((size_t)b.C), S2((size_t)b.C), dummy((size_t)b.C), mu((size_t)b.C);
+  float const fN = (float)b.N, omm = 1.0f - b.maf, unb = b.N > 1 ? (float)b.N / (float)(b.N - 1) : 1.0f;
+  bn_chan_sums(b, [&](long c) { return [&b, in, c](long e, float &a0, float &) { a0 = a0 + in[bn_off(b, c, e)]; }; }, S1.data(), dummy.data());
+  for (long c = 0; c < b.C; ++c) mu[(size_t)c] = S1[(size_t)c] / fN;
+  bn_chan_sums(b, [&](long c) { float const m = mu[(size_t)c]; return [&b, in, c, m](long e, float &a0, float &) { float const df = in[bn_off(b, c, e)] - m; float const sq = df * df; a0 = a0 + sq; }; }, S2.data(), dummy.data());
+  for (long c = 0; c < b.C; ++c) {
+    float const m = mu[(size_t)c];
+    float const var = S2[(size_t)c] / fN;
+    float const ve = var + b.eps;
+    float const sd = sqrtf(ve);
+    float const istd = 1.0f / sd;
+    float const m1 = b.maf * run_mean[c];
+    float const m2 = omm * m;
+    float const uv = (b.N == 1) ? var : var * unb;
+    float const v1 = b.maf * run_var[c];
+    float const v2 = omm * uv;
+    mean[c] = m; inv_std[c] = istd; run_mean[c] = m1 + m2; run_var[c] = v1 + v2;
+  }
+}
+void bn_fwd(bn_op_t const &b, float const *in, float *out, float const *mean, float const *inv_std, float const *scale, float const *bias) {
+#pragma omp parallel for schedule(static)
+  for (long pl = 0; pl < b.B * b.C; ++pl) {
+    long const c = pl % b.C;
+    float const m = mean[c], is = inv_std[c], sc = scale[c], bi = bias[c];
+    for (long e = pl * b.HW; e < (pl + 1) * b.HW; ++e) {
+      float const df = in[e] - m;
+      float const xh = df * is;
+      float v = xh * sc;
+      v = v + bi;
+      if (b.relu) v = v > 0.0f ? v : 0.0f;
+      out[e] = v;
+    }
+  }
+}
+void bn_bck_sums(bn_op_t const &b, float const *in, float const *dy, float const *mean, float const *inv_std, float *sg, float *bg) {
+  bn_chan_sums(b, [&](long c) { float const m = mean[c], is = inv_std[c]; return [&b, in, dy, c, m, is](long e, float &a0, float &a1) {
+    long const o = bn_off(b, c, e); float const df = in[o] - m; float const xh = df * is; float const tm = dy[o] * xh; a0 = a0 + tm; a1 = a1 + dy[o]; }; }, sg, bg);
+}
+void bn_bck_in(bn_op_t const &b, float const *in, float const *dy, float *dx, float const *mean, float const *inv_std, float const *scale, float const *sg, float const *bg) {
+  float const fN = (float)b.N;
+#pragma omp parallel for schedule(static)
+  for (long pl = 0; pl < b.B * b.C; ++pl) {
+    long const c = pl % b.C;
+    float const m = mean[c], is = inv_std[c];
+    float const k = scale[c] * is;
+    float const mg = sg[c] / fN;
+    float const mb = bg[c] / fN;
+    for (long e = pl * b.HW; e < (pl + 1) * b.HW; ++e) {
+      float const df = in[e] - m;
+      float const xh = df * is;
+      float const t1 = dy[e] - mb;
+      float const t2 = xh * mg;
+      float const t3 = t1 - t2;
+      dx[e] = k * t3;
+    }
+  }
+}
 #pragma GCC pop_options
 } // namespace
 
@@ -359,15 +441,16 @@ struct cpu_compute_t : public rtc_compute_t {
     for (auto const &fi : func_infos) {
       if (funcs.count(fi.func_name)) rt_err("compile: function '" + fi.func_name + "' already exists");
       string const fn = fi.op.has_func_name() ? fi.op.get_func_name() : string();
-      if (!is_sgemm(fn) && !is_conv(fn) && !is_bck(fn) && !find_bck_op(fn) && fn != "hip_sgd_update")
+      if (!is_sgemm(fn) && !is_conv(fn) && !is_bck(fn) && !find_bck_op(fn) && fn != "hip_sgd_update" && !is_bn_func_name(fn))
         unsup_err("be=cpu runs the native sgemm / Convolution / BckConv functions and the gradient pipe's non-conv functions only (hip_sgemm, hip_conv and their aliases, hip_bconv_*, "
-                  "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs, hip_reduce, hip_dropout, hip_concat, hip_split, hip_chan_affine, hip_sgd_update); '" +
+                  "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs, hip_reduce, hip_dropout, hip_concat, hip_split, hip_chan_affine, hip_sgd_update, hip_bn_stats, hip_bn_fwd, hip_bn_bck_sums, hip_bn_bck_in, hip_fan_out); '" +
                                                     (fn.empty() ? fi.func_name : fn) + "' is generated CUCL source, which needs a GPU backend");
       if (is_conv(fn)) (void)fi.op.get_u32("conv_has_relu");
       (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
       (void)op_seed_var_flag(fi.op);   // (likewise)
       (void)op_img_shards_flag(fi.op);   // (likewise; here there is one shard: a flagged call is the unflagged one)
       if (fn == "hip_sgd_update") (void)sgd_op_of_op(fi.op);   // (the op must be whole)
+      if (is_bn_func_name(fn)) (void)bn_op_of_op(fi.op);   // (likewise)
       if (bck_op_fn_t const *d = find_bck_op(fn)) {
         if (!type_ok(*d, fi.op.get_type())) rt_err(fn + ": a function of op type " + d->type + ", not " + fi.op.get_type());
         for (string const &an : bck_op_ins(*d, fi.op)) (void)fi.op.get_dims(an);
@@ -648,6 +731,30 @@ struct cpu_compute_t : public rtc_compute_t {
     }
   }
 
+  // the training BatchNorm functions and hip_fan_out: the checks of be=hip (csrc/native_run.cc), then the twins above
+  void run_bn(op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = op.get_func_name();
+    bn_op_t const b = bn_op_of_op(op);
+    vect_string vars; std::vector<float *> T, Cv;
+    auto var_ptr = [&](string const &an) -> float * {
+      string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn);
+      if (vd.tn != "float") rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ": fp32 only");
+      if (!(vd == op.get_dims(an))) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + op.get_dims(an).pretty_str());
+      vars.push_back(vn);
+      return (float *)must_find(vis, vn).buf.get();
+    };
+    for (string const &an : b.tens) T.push_back(var_ptr(an));
+    for (string const &an : b.chans) Cv.push_back(var_ptr(an));
+    bn_check_aliases(fn, b, vars);
+    switch (b.kind) {
+    case 1: bn_stats(b, T[0], Cv[0], Cv[1], Cv[2], Cv[3]); break;
+    case 2: bn_fwd(b, T[0], T[1], Cv[0], Cv[1], Cv[2], Cv[3]); break;
+    case 3: bn_bck_sums(b, T[0], T[1], Cv[0], Cv[1], Cv[2], Cv[3]); break;
+    case 4: bn_bck_in(b, T[0], T[1], T[2], Cv[0], Cv[1], Cv[2], Cv[3], Cv[4]); break;
+    default: for (int i = 0; i < b.nout; ++i) memcpy(T[(size_t)(1 + i)], T[0], sizeof(float) * (size_t)b.elems);
+    }
+  }
+
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
     auto fit = funcs.find(rfc.rtc_func_name);
@@ -659,6 +766,7 @@ struct cpu_compute_t : public rtc_compute_t {
     (void)op_img_shards_flag(fi.op);   // (likewise)
     double const tb = now_ms();
     if (fn == "hip_sgd_update") run_sgd_update(fi.op, am);
+    else if (is_bn_func_name(fn)) run_bn(fi.op, am);
     else if (bck_op_fn_t const *bd = find_bck_op(fn)) run_bck_op(*bd, fi.op, am);
     else if (is_bck(fn)) run_bck(fn, fi.op, am);
     else if (is_sgemm(fn)) {

@@ -366,6 +366,14 @@ struct hip_multi_compute_t : public rtc_compute_t {
       if (nat && n() > 1 && fi.op.get_func_name() == "hip_sum_loss_over_imgs") func_img_sum[fi.func_name] = "(the softmax loss) sums loss_per_pel over ALL images, which would need a cross-device reduction; hip_softmax runs on img shards";
       // hip_reduce / hip_concat / hip_split / hip_chan_affine are independent per image and run on img shards (a and b, one value per channel, are whole on every device); hip_dropout hashes the element's index in the WHOLE tensor
       if (nat && n() > 1 && fi.op.get_func_name() == "hip_dropout") func_img_sum[fi.func_name] = "(dropout) hashes every element's GLOBAL flat index, which an img shard does not know; hip_reduce / hip_concat / hip_split run on img shards";
+      // the training BatchNorm: hip_bn_stats and hip_bn_bck_sums sum over img x y x x of the WHOLE batch, hip_bn_bck_in divides by that count.  hip_bn_fwd and
+      // hip_fan_out are independent per image, but their calls demand vars of exactly the op's dims (csrc/native_run.cc), which an img shard does not have: they are
+      // refused here by name, with a message of their own, not left to fail on dims
+      if (nat && n() > 1 && (fi.op.get_func_name() == "hip_bn_stats" || fi.op.get_func_name() == "hip_bn_bck_sums"))
+        func_img_sum[fi.func_name] = "(a training BatchNorm's per-channel sums) sums over the images of the WHOLE batch, which would need a cross-device reduction; statistics summed across img shards are out of scope";
+      if (nat && n() > 1 && fi.op.get_func_name() == "hip_bn_bck_in") func_img_sum[fi.func_name] = "(a training BatchNorm's data gradient) divides by the element count of the WHOLE batch, which an img shard does not know";
+      if (nat && n() > 1 && (fi.op.get_func_name() == "hip_bn_fwd" || fi.op.get_func_name() == "hip_fan_out"))
+        func_img_sum[fi.func_name] = "(" + fi.op.get_func_name() + ") takes vars of exactly its op's dims, not img shards: the training BatchNorm functions and the Eltwise gradient run on one device";
       if (!nat) func_gen[fi.func_name] = scan_gen_func(all_src, fi.func_name);
     }
   }

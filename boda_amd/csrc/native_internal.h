@@ -47,7 +47,7 @@ struct native_kernels_t::impl_t {
 };
 
 
-struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false, bconv_in = false, bconv_filts = false, bck_ops = false, sgd = false; int rows = 0, cg = 0; };
+struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false, bconv_in = false, bconv_filts = false, bck_ops = false, sgd = false, bn = false; int rows = 0, cg = 0; };
 
 struct bconv_args_t { // must match kernels/bconv_in_f32.hip, kernels/bconv_filts_f32.hip
   float const *a; float const *b; float *d;
@@ -95,6 +95,28 @@ struct sgd_update_args_t { // must match kernels/sgd_update_f32.hip
 static_assert(sizeof(sgd_tensor_t) == 48 && sizeof(sgd_update_args_t) == 16 + 48 * kSgdMaxTens, "sgd_update_args_t is declared with this layout by kernels/sgd_update_f32.hip");
 struct sgd_plan_t { plan_t p; uint32_t grid = 0, block = 256; std::vector<uint32_t> blk0; double algo_bytes = 0; };
 sgd_plan_t plan_sgd_update(std::vector<long> const &elems);
+
+// the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip)
+struct bn_args_t { // must match kernels/bn_f32.hip
+  float const *in; float const *dy;
+  float const *c0; float const *c1; float const *c2; float const *c3; float const *c4;
+  float *out;
+  float *w0; float *w1; float *w2; float *w3;
+  float *ws;
+  float *outs[8];
+  long n;
+  int B, C, HW, N;
+  int slab, nslabs;
+  int quads;
+  int step_img, step_pel;
+  float fN, eps, maf, omm, unb;
+};
+static_assert(sizeof(bn_args_t) == 13 * 8 + 8 * 8 + 8 + 9 * 4 + 5 * 4, "bn_args_t is declared with this layout by kernels/bn_f32.hip");
+// the kernels of one call in launch order: op 1 (a sum over slabs; mode 0 S1, 1 S2, 2 the bck_sums pair), 2 (the finalising step; fin 1 stats, 2 bck_sums), 3 fwd, 4 bck_in, 5 fan_out
+struct bn_launch_t { plan_t p; int op = 0; };
+struct bn_plan_t { std::vector<bn_launch_t> ls; double algo_bytes = 0; size_t ws_bytes = 0; };
+bn_plan_t plan_bn(bn_op_t const &b);
+string bn_plan_desc(bn_op_t const &b, bn_plan_t const &bp);
 
 struct rows_args_t { // must match kernels/conv_nhwc_rows_bf16.hip
   void const *filts; void const *in; void *out; float const *bias;

@@ -52,6 +52,10 @@ void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
     (void)get_kernel(impl, host, plan_sgd_update(so.elems).p);
     return;
   }
+  if (is_bn_func_name(fn)) {   // the op must be whole; the code objects of all the call's launches are built NOW, so that a first run inside a graph capture finds them
+    for (bn_launch_t const &l : plan_bn(bn_op_of_op(fi.op)).ls) (void)get_kernel(impl, host, l.p);
+    return;
+  }
   if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases") {   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     return;
@@ -84,7 +88,7 @@ void launch(native_host_t *host, kernel_t &k, gemm_args_t &a, tile_cfg_t const &
 
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log) {
   vect_string opts = p.defs; opts.push_back("-DKNAME=" + p.kname);
-  return hiprtc_compile(p.sgd ? k_src_sgd_update_f32 : p.bck_ops ? k_src_bck_ops_f32 : p.bconv_in ? k_src_bconv_in_f32 : p.bconv_filts ? k_src_bconv_filts_f32 : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
+  return hiprtc_compile(p.bn ? k_src_bn_f32 : p.sgd ? k_src_sgd_update_f32 : p.bck_ops ? k_src_bck_ops_f32 : p.bconv_in ? k_src_bconv_in_f32 : p.bconv_filts ? k_src_bconv_filts_f32 : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
 }
 
 // grow-only scratch shared by the split-K slabs and the Winograd-domain tensors (like the reference's cudnn scratch var)
@@ -837,6 +841,62 @@ void native_kernels_t::sgd_update(int n, sgd_member_t const *m, float const *hyp
   if (sp.grid) hip_err_chk(host->nh_launch(k.func, sp.grid, 1, sp.block, params), "hipModuleLaunchKernel(sgd_update)");
   last_launch.kernel = sp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = sp.grid; last_launch.block = sp.block;
   last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
+}
+// ---- the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip): one to three launches per call, in plan_bn's order.  The slab partials of the two
+// reducing functions live in a workspace of the CALL (keyed by its pointers, like the K-slice workspaces: calls of a parallel graph run at the same time), allocated on
+// the call's first run; one launch writes it, the next launch of the same call reads it
+void native_kernels_t::bn_call(bn_op_t const &b, float *const *tens, float *const *chans) {
+  bn_plan_t const bp = plan_bn(b);
+  bn_args_t a; memset(&a, 0, sizeof(a));
+  a.B = (int)b.B; a.C = (int)b.C; a.HW = (int)b.HW; a.N = (int)b.N; a.slab = (int)b.slab; a.nslabs = (int)b.nslabs;
+  a.fN = (float)b.N; a.eps = b.eps; a.maf = b.maf; a.omm = 1.0f - b.maf; a.unb = b.N > 1 ? (float)b.N / (float)(b.N - 1) : 1.0f;
+  uintptr_t al = 0;
+  for (size_t i = 0; i < b.tens.size(); ++i) al |= (uintptr_t)tens[i];
+  bool const aligned = (al & 15) == 0;
+  switch (b.kind) {
+  case 1: a.in = tens[0]; a.w0 = chans[0]; a.w1 = chans[1]; a.w2 = chans[2]; a.w3 = chans[3]; break;
+  case 2: a.in = tens[0]; a.out = tens[1]; a.c0 = chans[0]; a.c1 = chans[1]; a.c2 = chans[2]; a.c3 = chans[3]; break;
+  case 3: a.in = tens[0]; a.dy = tens[1]; a.c0 = chans[0]; a.c1 = chans[1]; a.w0 = chans[2]; a.w1 = chans[3]; break;
+  case 4: a.in = tens[0]; a.dy = tens[1]; a.out = tens[2]; a.c0 = chans[0]; a.c1 = chans[1]; a.c2 = chans[2]; a.c3 = chans[3]; a.c4 = chans[4]; break;
+  default: a.in = tens[0]; for (int i = 0; i < b.nout; ++i) a.outs[i] = tens[1 + i];
+  }
+  if (bp.ws_bytes) {
+    string const key = "ksl:bn:" + std::to_string(b.kind) + ":" + std::to_string((uintptr_t)tens[0]) + ":" + std::to_string((uintptr_t)chans[2]) + ":" + std::to_string(bp.ws_bytes);
+    auto it = impl->ktabs.find(key);
+    if (it == impl->ktabs.end()) {
+      if (host->nh_capturing()) rt_err("graph capture: the slab workspace of this call is not allocated yet -- run the call list once before capturing it");
+      void *dev = nullptr;
+      call_ws_make_room(impl, host, bp.ws_bytes);
+      hip_err_chk(hipMalloc(&dev, bp.ws_bytes), "hipMalloc(BatchNorm slab workspace)"); impl->call_ws_bytes += bp.ws_bytes;
+      it = impl->ktabs.emplace(key, dev).first;
+    }
+    a.ws = (float *)it->second;
+  }
+  uint32_t grid0 = 0;
+  for (bn_launch_t const &l : bp.ls) {
+    kernel_t &k = get_kernel(impl, host, l.p);
+    uint32_t grid = 0;
+    if (l.op == 1) {
+      a.quads = (aligned && (b.HW & 3) == 0) ? 1 : 0;
+      a.step_img = (int)(kBnSlabUnit / b.HW); a.step_pel = (int)(kBnSlabUnit % b.HW);
+      grid = (uint32_t)(b.C * b.nslabs);
+    } else if (l.op == 2) {
+      grid = (uint32_t)((b.C + 255) / 256);
+    } else if (l.op == 3 || l.op == 4) {   // quads of a plane: every tensor 16-byte aligned and planes of whole quads, so that every plane starts on a quad
+      a.quads = (aligned && (b.HW & 3) == 0) ? (int)(b.HW / 4) : 0;
+      a.n = b.B * b.C * (a.quads + (b.HW - 4L * a.quads));
+      grid = (uint32_t)((a.n + 255) / 256);
+    } else {
+      a.quads = aligned ? (int)(b.elems / 4) : 0;
+      a.n = (long)a.quads + (b.elems - 4L * a.quads);
+      grid = (uint32_t)((a.n + 255) / 256);
+    }
+    void *params[] = {&a};
+    if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, 256, params), "hipModuleLaunchKernel(bn)");
+    if (!grid0) grid0 = grid;
+  }
+  last_launch.kernel = bp.ls[0].p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = grid0; last_launch.block = 256;
+  last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
 }
 void native_kernels_t::shard_sum(float const *slabs, float *out, int nslabs, long stride, long n) {
   bck_plan_t const bp = plan_shard_sum(nslabs, stride, n);

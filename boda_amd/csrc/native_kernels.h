@@ -39,6 +39,9 @@
 //                                       floats lr_mult_i / decay_mult_i in the op; w_i (param) and h_i (momentum history) read and written, g_i (gradient) and hyper (float v=4:
 //                                       lr, momentum, weight_decay, unused) read.  g1 = g + (wd * decay_mult_i) * w; h' = momentum * h + (lr * lr_mult_i) * g1; w' = w - h', every
 //                                       operation one fp32 rounding.  One launch for all tensors (kernels/sgd_update_f32.hip); the code object is built when the function is compiled
+//     hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out    op types BnStats / BnFwd / BnBckSums / BnBckIn / FanOut, this backend's own: the training
+//                                       BatchNorm of the gradient pipe (batch statistics, running pair, normalise + scale + bias + ReLU, the two gradients) and the
+//                                       gradient of an Eltwise SUM.  kernels/bn_f32.hip states the arithmetic and the order of the per-channel sums
 //     hip_conv_winograd                 same contract as hip_conv; 3x3 / stride-1 layers through F(2x2,3x3) Winograd (mrd <= ~2e-3)
 // and lands them on kernels/gemm_conv_f32.hip (and, for short-K 1x1 convs with a long pel axis, kernels/k1_stream_f32.hip),
 // specialised with hiprtc per shape class at first use.
@@ -149,6 +152,8 @@ struct native_kernels_t {
   struct sgd_member_t { float *w; float const *g; float *h; long n; float lr_mult, decay_mult; };
   void sgd_update(int n, sgd_member_t const *m, float const *hyper);
   void shard_sum(float const *slabs, float *out, int nslabs, long stride, long n);
+  // hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out on raw device pointers (kernels/bn_f32.hip): tens / chans in bn_op_t's arg order
+  void bn_call(bn_op_t const &b, float *const *tens, float *const *chans);
   void conv_winograd(float const *filts, float const *biases, float const *in, float *out, conv_geom_t const &g, int out_ctot, int out_coff);
 
   // tuning overrides ("" clears): key "sgemm_tile" / "conv_tile" -> "BIxBJxBKxWIxWJ[xMINW[xSPLITK[xMT]]]"; key "k1_stream" -> "off" | "WIxWJxOCBxCB[xMINW]";

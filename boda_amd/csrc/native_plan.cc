@@ -1350,4 +1350,37 @@ sgd_plan_t plan_sgd_update(std::vector<long> const &elems) {
   return r;
 }
 
+// ---- the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip): the kernels of one call in launch order.  The slab plan itself is bn_slab_plan's
+// (rtc_types.h), shared with be=cpu; nothing here depends on the device.  algo_bytes counts every tensor of the call once
+bn_plan_t plan_bn(bn_op_t const &b) {
+  bn_plan_t r;
+  auto add = [&](int op, char const *kname, vect_string const &defs) {
+    bn_launch_t l; l.op = op; l.p.bn = true; l.p.kname = kname; l.p.defs = {"-DOP=" + std::to_string(op)};
+    for (string const &d : defs) l.p.defs.push_back(d);
+    r.ls.push_back(l);
+  };
+  double const T = 4.0 * (double)b.elems, Cb = 4.0 * (double)b.C;
+  switch (b.kind) {
+  case 1: add(1, "bodahip_bn_sum", {"-DMODE=0"}); add(1, "bodahip_bn_sum", {"-DMODE=1"}); add(2, "bodahip_bn_fin", {"-DFIN=1"}); r.algo_bytes = T + 4 * Cb; break;
+  case 2: add(3, "bodahip_bn_fwd", {"-DRELU=" + std::to_string(b.relu)}); r.algo_bytes = 2 * T + 4 * Cb; break;
+  case 3: add(1, "bodahip_bn_sum", {"-DMODE=2"}); add(2, "bodahip_bn_fin", {"-DFIN=2"}); r.algo_bytes = 2 * T + 4 * Cb; break;
+  case 4: add(4, "bodahip_bn_bck_in", {}); r.algo_bytes = 3 * T + 5 * Cb; break;
+  case 5: add(5, "bodahip_fan_out", {"-DNOUT=" + std::to_string(b.nout)}); r.algo_bytes = (1.0 + b.nout) * T; break;
+  default: rt_err("plan_bn: unknown kind");
+  }
+  if (b.kind == 1 || b.kind == 3) r.ws_bytes = (size_t)(2 * b.C * b.nslabs) * sizeof(float);
+  return r;
+}
+string bn_plan_desc(bn_op_t const &b, bn_plan_t const &bp) {
+  string s;
+  for (bn_launch_t const &l : bp.ls) {
+    long const grid = l.op == 1 ? b.C * b.nslabs : l.op == 2 ? (b.C + 255) / 256 : 0;
+    s += (s.empty() ? "" : " | ") + l.p.kname;
+    if (grid) s += " grid=" + std::to_string(grid) + " block=256";
+    for (size_t i = 1; i < l.p.defs.size(); ++i) s += " " + l.p.defs[i];
+  }
+  if (b.kind == 1 || b.kind == 3) s += " | slab=" + std::to_string(b.slab) + " slabs=" + std::to_string(b.nslabs);
+  return s;
+}
+
 } // namespace bodahip

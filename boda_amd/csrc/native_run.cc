@@ -249,6 +249,13 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     sgd_plan_t const sp = plan_sgd_update(sgd_op_of_op(op).elems);
     if (plan_out) *plan_out = sp.p.kname + " grid=" + std::to_string(sp.grid) + " block=" + std::to_string(sp.block) + " tens=" + std::to_string(sp.blk0.size()) + " chunk=" + std::to_string(kSgdChunk);
     return arch.empty() ? 0 : compile_plan(sp.p, arch, &log).size();
+  } else if (t == "BnStats" || t == "BnFwd" || t == "BnBckSums" || t == "BnBckIn" || t == "FanOut") {   // (kernels/bn_f32.hip: every launch of the call, and the slab plan)
+    bn_op_t const b = bn_op_of_op(op);
+    bn_plan_t const bp = plan_bn(b);
+    if (plan_out) *plan_out = bn_plan_desc(b, bp);
+    size_t bytes = 0;
+    if (!arch.empty()) for (bn_launch_t const &l : bp.ls) bytes += compile_plan(l.p, arch, &log).size();
+    return bytes;
   } else if (!bck_ops_of_type(t).empty()) {   // a non-conv op of the gradient pipe: its annotated function, or (the bare op) all its functions in call order
     std::vector<bck_op_desc_t const *> ds;
     if (op.has_func_name()) {
@@ -680,6 +687,25 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     }
     float const *hyper = (float const *)var_ptr("hyper");
     sgd_update(n, ms.data(), hyper);
+    return;
+  }
+  if (is_bn_func_name(fn)) {
+    // every var must have exactly the dims the op gives its arg (the sums run over the whole batch: no img shards), and no two args may be one var except where
+    // kernels/bn_f32.hip allows in-place use
+    bn_op_t const b = bn_op_of_op(fi.op);
+    vect_string vars; std::vector<float *> tens, chans;
+    auto var_ptr = [&](string const &an) -> float * {
+      string const vn = var_of(am, an); dims_t const vd = host->nh_var_dims(vn);
+      if (vd.tn != "float") rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ": fp32 only");
+      if (!(vd == fi.op.get_dims(an))) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + fi.op.get_dims(an).pretty_str());
+      vars.push_back(vn);
+      return (float *)host->nh_var_ptr(vn);
+    };
+    for (string const &an : b.tens) tens.push_back(var_ptr(an));
+    for (string const &an : b.chans) chans.push_back(var_ptr(an));
+    bn_check_aliases(fn, b, vars);
+    while (chans.size() < 5) chans.push_back(nullptr);
+    bn_call(b, tens.data(), chans.data());
     return;
   }
   if (bck_op_desc_t const *d = find_bck_op(fn)) {

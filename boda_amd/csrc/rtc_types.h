@@ -10,6 +10,7 @@
 //   rt_err / unsup_err        src/boda_base.H:98,105               (fatal vs. "unsupported, caller may record")
 // Written from the interface's behaviour; this is not a copy of those headers (no NESI, no boost).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <map>
@@ -203,6 +204,91 @@ inline sgd_op_t sgd_op_of_op(op_base_t const &op) {
     r.elems.push_back((long)w.dims_prod()); r.lr_mult.push_back(f32("lr_mult" + sx)); r.decay_mult.push_back(f32("decay_mult" + sx));
   }
   return r;
+}
+
+// ---- the training BatchNorm functions and the Eltwise gradient (this backend's own; kernels/bn_f32.hip states the arithmetic): hip_bn_stats (op type BnStats),
+// hip_bn_fwd (BnFwd), hip_bn_bck_sums (BnBckSums), hip_bn_bck_in (BnBckIn), hip_fan_out (FanOut).  What both backends read from the function's op, every refusal that
+// needs the op alone, and the SLAB PLAN of the three per-channel sums: a function of the op alone, so that be=cpu and be=hip always cut at the same places
+constexpr long kBnSlabUnit = 1024;     // a planned slab is a multiple of this (256 threads x one quad)
+constexpr long kBnMinSlab = 4096;      // ... and never shorter than this: a short channel keeps one slab
+constexpr long kBnTargetWgs = 512;     // two workgroups per CU on a fixed 256 CUs (not the device's count: the plan must not depend on the device)
+constexpr long kBnMaxSlabs = 4096;     // per channel (only a forced slab length can ask for more)
+constexpr int kFanOutMax = 8;
+inline bool is_bn_func_name(string const &fn) { return fn == "hip_bn_stats" || fn == "hip_bn_fwd" || fn == "hip_bn_bck_sums" || fn == "hip_bn_bck_in" || fn == "hip_fan_out"; }
+struct bn_op_t {
+  int kind = 0;                  // 1 stats, 2 fwd, 3 bck_sums, 4 bck_in, 5 fan_out
+  long B = 0, C = 0, HW = 0, N = 0;   // N = B * HW: the elements of one channel
+  long elems = 0;                // of the whole tensor
+  long slab = 0, nslabs = 0;     // kinds 1, 3: elements of a slab of a channel's flat (img, pel) range, slabs per channel
+  float eps = 0.f, maf = 0.f; uint32_t relu = 0; int nout = 0;
+  vect_string tens, chans;       // the tensor args (dims of `in`) and the per-channel args (float chan=C), in the function's arg order
+};
+inline void bn_slab_plan(string const &fn, long C, long N, uint32_t forced, long &slab, long &nslabs) {
+  if (forced) {
+    if (forced % 4) rt_err(fn + ": slab=" + std::to_string(forced) + ": a forced slab length is a multiple of 4");
+    slab = (long)forced;
+  } else {
+    long const want = std::max<long>(1, (kBnTargetWgs + C - 1) / C);
+    slab = (N + want - 1) / want;
+    slab = (slab + kBnSlabUnit - 1) / kBnSlabUnit * kBnSlabUnit;
+    slab = std::max(slab, kBnMinSlab);
+  }
+  nslabs = std::max<long>(1, (N + slab - 1) / slab);
+  if (nslabs > kBnMaxSlabs) unsup_err(fn + ": slab=" + std::to_string(slab) + " cuts a channel of " + std::to_string(N) + " elements into " + std::to_string(nslabs) + " slabs, more than " + std::to_string(kBnMaxSlabs));
+}
+inline bn_op_t bn_op_of_op(op_base_t const &op) {
+  string const fn = op.has_func_name() ? op.get_func_name() : string();
+  static char const *const types[] = {"", "BnStats", "BnFwd", "BnBckSums", "BnBckIn", "FanOut"};
+  bn_op_t r;
+  r.kind = fn == "hip_bn_stats" ? 1 : fn == "hip_bn_fwd" ? 2 : fn == "hip_bn_bck_sums" ? 3 : fn == "hip_bn_bck_in" ? 4 : fn == "hip_fan_out" ? 5 : 0;
+  if (!r.kind) rt_err("'" + fn + "' is none of hip_bn_stats, hip_bn_fwd, hip_bn_bck_sums, hip_bn_bck_in, hip_fan_out");
+  if (!op.has_type() || op.get_type() != types[r.kind]) rt_err(fn + ": a function of op type " + types[r.kind] + ", not " + (op.has_type() ? op.get_type() : string("?")));
+  for (char const *fl : {"img_shards", "seed_from_var", "zero_if_in_non_pos"}) if (op.has(fl) && op.get_u32(fl)) rt_err(string(fl) + "=1 on '" + fn + "': the function takes no flag");
+  auto f32 = [&](string const &an) { if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'"); p_nda_t const &v = op.get(an); if (v->dims.tn != "float" || v->dims.sz() != 0 || !v->rp) rt_err(fn + ": '" + an + "' is not a float scalar"); return *static_cast<float const *>(v->rp); };
+  auto u32 = [&](string const &an) { if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'"); return op.get_u32(an); };
+  switch (r.kind) {
+  case 1: r.tens = {"in"}; r.chans = {"mean", "inv_std", "run_mean", "run_var"}; break;
+  case 2: r.tens = {"in", "out"}; r.chans = {"mean", "inv_std", "scale", "bias"}; break;
+  case 3: r.tens = {"in", "out_grad_loss"}; r.chans = {"mean", "inv_std", "scale_grad_loss", "bias_grad_loss"}; break;
+  case 4: r.tens = {"in", "out_grad_loss", "in_grad_loss"}; r.chans = {"mean", "inv_std", "scale", "scale_grad_loss", "bias_grad_loss"}; break;
+  default: {
+    uint32_t const n = u32("outs_num");
+    if (n < 2 || n > (uint32_t)kFanOutMax) unsup_err(fn + ": outs_num=" + std::to_string(n) + ": 2 to " + std::to_string(kFanOutMax) + " outputs");
+    r.nout = (int)n; r.tens = {"in"};
+    for (uint32_t i = 0; i < n; ++i) r.tens.push_back("outs_" + std::to_string(i));
+  } }
+  for (string const &an : r.tens) if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'");
+  for (string const &an : r.chans) if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'");
+  dims_t const &in = op.get_dims("in");
+  if (in.tn != "float") rt_err(fn + ": in has type " + in.tn + ": fp32 only");
+  if (r.kind != 5 && !(in.sz() == 4 && in.names(0) == "img" && in.names(1) == "chan" && in.names(2) == "y" && in.names(3) == "x")) rt_err(fn + ": in must be img:chan:y:x, got " + in.pretty_str());
+  for (string const &an : r.tens) if (!(op.get_dims(an) == in)) rt_err(fn + ": " + an + " dims " + op.get_dims(an).tn + " " + op.get_dims(an).pretty_str() + " differ from in's float " + in.pretty_str());
+  r.elems = (long)in.dims_prod();
+  if (r.elems < 1) rt_err(fn + ": empty in");
+  if (4.0 * (double)in.dims_prod() >= 2147483648.0) unsup_err(fn + ": tensors of 2 GiB or more (32-bit element offsets)");
+  if (r.kind == 5) return r;
+  r.B = in.dims(0); r.C = in.dims(1); r.HW = (long)in.dims(2) * in.dims(3); r.N = r.B * r.HW;
+  for (string const &an : r.chans) {
+    dims_t const &d = op.get_dims(an);
+    if (d.tn != "float" || d.sz() != 1 || d.names(0) != "chan" || (long)d.dims(0) != r.C) rt_err(fn + ": " + an + " dims " + d.tn + " " + d.pretty_str() + ": one float per channel of in " + in.pretty_str());
+  }
+  if (r.kind == 1) { r.eps = f32("eps"); r.maf = f32("maf"); if (!(r.eps >= 0.0f)) rt_err(fn + ": eps must not be negative"); }
+  if (r.kind == 2) { r.relu = u32("relu"); if (r.relu > 1) rt_err(fn + ": relu must be 0 | 1"); }
+  if (r.kind == 1 || r.kind == 3) bn_slab_plan(fn, r.C, r.N, u32("slab"), r.slab, r.nslabs);
+  return r;
+}
+// the var-level refusals of a call, the same text on both backends: `vars` = the var bound to every tensor arg followed by every per-channel arg (bn_op_t's order)
+inline void bn_check_aliases(string const &fn, bn_op_t const &b, vect_string const &vars) {
+  vect_string args = b.tens; args.insert(args.end(), b.chans.begin(), b.chans.end());
+  assert_st(args.size() == vars.size());
+  auto same = [&](size_t i, size_t j) { return vars[i] == vars[j]; };
+  for (size_t i = 0; i < args.size(); ++i) for (size_t j = i + 1; j < args.size(); ++j) {
+    if (!same(i, j)) continue;
+    bool ok = false;
+    if (b.kind == 2 && i == 0 && j == 1) ok = true;                       // hip_bn_fwd: in and out may be one var
+    if (b.kind == 4 && i == 1 && j == 2) ok = true;                       // hip_bn_bck_in: in_grad_loss may be out_grad_loss's var
+    if (!ok) rt_err(fn + ": args '" + args[i] + "' and '" + args[j] + "' are the same var '" + vars[i] + "'");
+  }
 }
 
 // ---- rtc layer ----------------------------------------------------------------------------------------------------

@@ -271,10 +271,18 @@ OP_INFO = {
     # this backend's own (the reference has no solver): the SGD update of up to 32 tensors.  The multi args w / g / h ride flattened as w_0 .. w_{tens_num-1} etc., with the
     # floats lr_mult_i / decay_mult_i beside them; w and h are read and written, g and hyper (float v=4: lr, momentum, weight_decay, unused) read
     "SgdUpdate": (("hyper",), (), ("tens_num",)),
+    # this backend's own: the training BatchNorm of the gradient pipe and the gradient of an Eltwise SUM (csrc/kernels/bn_f32.hip states the arithmetic).  The per-channel
+    # args are float chan=C; run_mean / run_var are read and written; slab (0: the planner's) forces the slab length of the per-channel sums; FanOut writes the multi arg outs
+    "BnStats": (("in",), ("mean", "inv_std", "run_mean", "run_var"), ("eps", "maf", "slab")),
+    "BnFwd": (("in", "mean", "inv_std", "scale", "bias"), ("out",), ("relu",)),
+    "BnBckSums": (("in", "mean", "inv_std", "out_grad_loss"), ("scale_grad_loss", "bias_grad_loss"), ("slab",)),
+    "BnBckIn": (("in", "mean", "inv_std", "scale", "scale_grad_loss", "bias_grad_loss", "out_grad_loss"), ("in_grad_loss",), ()),
+    "FanOut": (("in",), (), ("outs_num",)),
 }
+BN_TYPES = ("BnStats", "BnFwd", "BnBckSums", "BnBckIn", "FanOut")
 
 
-_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate")
+_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES
 
 
 @dataclass
@@ -525,6 +533,38 @@ class Op:
             elems.append(w.dims_prod())
         return dict(n=n, elems=elems)
 
+    def bn_geom(self) -> dict:
+        """BnStats / BnFwd / BnBckSums / BnBckIn: float img:chan:y:x tensors of equal dims, the per-channel args float chan=C; FanOut: in and 2 to 8 outs of equal float dims."""
+        t = self.get_type()
+        i = self.get_dims("in")
+        if i.tn != "float":
+            raise RtErr(f"{t}: in has type {i.tn}: fp32 only")
+        ins, outs, _ = OP_INFO[t]
+        if t == "FanOut":
+            n = self.get_u32("outs_num")
+            if n < 2 or n > 8:
+                raise UnsupErr(f"FanOut: outs_num={n}: 2 to 8 outputs")
+            for an in self.multi_names("outs"):
+                if self.get_dims(an) != i:
+                    raise RtErr(f"FanOut: {an} dims {self.get_dims(an).pretty()} differ from in's {i.pretty()}")
+            return dict(N=i.dims_prod(), n=n)
+        if i.names != ("img", "chan", "y", "x"):
+            raise RtErr(f"{t}: in must be img:chan:y:x, got {i.pretty()}")
+        for an in ins + outs:
+            d = self.get_dims(an)
+            if an in ("in", "out", "out_grad_loss", "in_grad_loss"):
+                if d != i:
+                    raise RtErr(f"{t}: {an} dims {d.pretty()} differ from in's {i.pretty()}")
+            elif d.names != ("chan",) or d.sizes != (i.dsz("chan"),) or d.tn != "float":
+                raise RtErr(f"{t}: {an} dims {d.pretty()}: one float per channel of in {i.pretty()}")
+        if t == "BnStats":
+            self.get_f32("eps"); self.get_f32("maf")
+        if t in ("BnStats", "BnBckSums") and self.get_u32("slab") % 4:
+            raise RtErr(f"{t}: slab={self.get_u32('slab')}: a forced slab length is a multiple of 4")
+        if t == "BnFwd" and self.get_u32("relu") not in (0, 1):
+            raise RtErr("BnFwd: relu must be 0 | 1")
+        return dict(B=i.dsz("img"), C=i.dsz("chan"), H=i.dsz("y"), W=i.dsz("x"))
+
     def concat_geom(self) -> dict:
         """Concat (ins_i -> out) / Split (in -> outs_i): float img:chan:y:x tensors of equal img / y / x whose channels add up to the wide tensor's.  -> B, H, W, CT and
         chans: per narrow tensor (arg name, first channel in the wide tensor, channels)."""
@@ -567,7 +607,7 @@ class Op:
         if self.get_type() == "SgdUpdate":   # w, g, h read, h and w written
             return 20 * sum(self.sgd_geom()["elems"])
         ins, outs, _ = OP_INFO[self.get_type()]
-        multi = {"Reduce": ("ins",), "Concat": ("ins",), "Split": ("outs",)}.get(self.get_type(), ())
+        multi = {"Reduce": ("ins",), "Concat": ("ins",), "Split": ("outs",), "FanOut": ("outs",)}.get(self.get_type(), ())
         return sum(self.get_dims(a).bytes_sz() for a in ins + outs + tuple(n for m in multi for n in self.multi_names(m)))
 
 
@@ -626,6 +666,8 @@ def parse_op(line: str) -> Op:
             op.chan_affine_geom()
         elif t == "SgdUpdate":
             op.sgd_geom()
+        elif t in BN_TYPES:
+            op.bn_geom()
         else:
             op.sgemm_geom()
     return op

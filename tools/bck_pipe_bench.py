@@ -7,6 +7,7 @@ and the share of the step each native function takes (sums of the backend's per-
     python tools/bck_pipe_bench.py --graph [--repeats 3] [--out profiles/r10_bck_graph_ab.txt]
     python tools/bck_pipe_bench.py --devices 0:1:2:3 [--out profiles/bck_pipe_devices.txt]
     python tools/bck_pipe_bench.py --sgd [--repeats 3] [--out profiles/r13_sgd_update.txt]
+    python tools/bck_pipe_bench.py --nets resnet50 --batch 32 [--limit 900] [--out profiles/r14_resnet50_step.txt]
 
 --fuse-relu-grad: the same step both ways in ONE process -- ConvPipeBck() and ConvPipeBck(fuse_relu_grad=True), each on a backend instance of its own with the same
 params and inputs -- after the usual warm-up, in --repeats alternating blocks of --runs steps.  Per net two JSON lines ("way": "unfused" / "fused": step ms as the median
@@ -30,6 +31,9 @@ tensors_per_call is sgd_packed against sgd_per_tensor in the same run; no figure
 run with img_shards=1.  Step ms is the longest of the devices' times; a call's share counts the time its device-side launches took, not the
 cross-device copies behind them.  No figure for more than one physical GPU is recorded yet.
 
+--nets resnet50: the fourth net, with its 53 BatchNorm + Scale runs as training BatchNorms (hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in) and its 16 Eltwise
+gradients as hip_fan_out.  The step must end with a finite loss (the child fails otherwise).  Its first step compiles some 150 specialisations: give it --limit 900.
+
 Every net runs in a child process of its own under a time limit (--limit seconds); the first one that fails ends the run.
 """
 import argparse
@@ -43,12 +47,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def _pipe(net, batch):
+    """nin | alexnet | resnet50 (BatchNorm / Scale as a training BatchNorm) at `batch` images."""
+    from boda_amd import conv_pipe
+    return {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv, "resnet50": conv_pipe.resnet50}[net](batch)
+
+
 def fuse_ab(net, batch, runs, warmup, repeats):
     import numpy as np
     from boda_amd import conv_pipe
     from boda_amd.bck_pipe import ConvPipeBck, add_bck_ops, host_params
     from boda_amd.rtc import make_rtc
-    cp = {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv}[net](batch)
+    cp = _pipe(net, batch)
     bp = add_bck_ops(cp)
     params = host_params(bp, 5)
     rng = np.random.default_rng(0)
@@ -94,7 +104,7 @@ def graph_ab(net, batch, runs, warmup, repeats):
     from boda_amd import conv_pipe
     from boda_amd.bck_pipe import ConvPipeBck, add_bck_ops, host_params
     from boda_amd.rtc import make_rtc
-    cp = {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv}[net](batch)
+    cp = _pipe(net, batch)
     bp = add_bck_ops(cp)
     params = host_params(bp, 5)
     rng = np.random.default_rng(0)
@@ -139,7 +149,7 @@ def sgd_ab(net, batch, runs, warmup, repeats):
     from boda_amd import conv_pipe
     from boda_amd.bck_pipe import ConvPipeBck, SgdSolver, add_bck_ops, host_params
     from boda_amd.rtc import make_rtc
-    cp = {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv}[net](batch)
+    cp = _pipe(net, batch)
     bp = add_bck_ops(cp)
     params = host_params(bp, 5)
     rng = np.random.default_rng(0)
@@ -188,7 +198,7 @@ def one_net(net, batch, runs, warmup, devices=""):
     from boda_amd import conv_pipe
     from boda_amd.bck_pipe import ConvPipeBck, add_bck_ops
     from boda_amd.rtc import make_rtc
-    cp = {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv}[net](batch)
+    cp = _pipe(net, batch)
     bp = add_bck_ops(cp)
     rtc = make_rtc(f"(be=hip,devices={devices})" if devices else "(be=hip)", 0)   # (several devices: the driver flags the five functions that are not independent per image)
     rtc.init()
@@ -206,6 +216,8 @@ def one_net(net, batch, runs, warmup, devices=""):
             for _, fn, d in drv.per_call_ms:
                 share[fn] = share.get(fn, 0.0) + d
     loss = float(rtc.copy_var_to_nda("loss").item())
+    if not np.isfinite(loss):
+        raise SystemExit(f"{net}: the step ended with the loss {loss}")
     tot = sum(share.values())
     step = statistics.median(ms)
     print(json.dumps({"net": net, "batch": batch, **({"devices": devices} if devices else {}), "calls": len(drv.calls()), "step_ms": round(step, 3), "imgs_per_s": round(batch / (step * 1e-3), 1), "loss": round(loss, 4),
@@ -232,7 +244,7 @@ def main(argv=None):
         ap.error("--devices times the plain step: graph capture is not provided on several devices, and the fused and the solver A/B run on one")
     if a.graph + a.fuse_relu_grad + a.sgd > 1:
         ap.error("--graph, --fuse-relu-grad and --sgd are three comparisons: run them one at a time")
-    a.out = a.out or os.path.join(ROOT, "profiles", "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "bck_pipe_devices.txt" if a.devices else "r09_bck_pipe_bench.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
     if a.child:
         if a.sgd:
             return sgd_ab(a.child, a.batch, a.runs, a.warmup, a.repeats)
