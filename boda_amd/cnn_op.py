@@ -180,6 +180,28 @@ def add_bck_conv_annotations(op: Op, tune: OpTune) -> tuple:
     return tuple(outs)
 
 
+BCONV_FB_FUNC = "hip_bconv_filts_biases"   # the filter and bias gradients in one call (kernels/bconv_fb_f32.hip); opt-in: ConvPipeBck(fuse_filts_biases=True)
+
+
+def bconv_filts_biases_func_op(op: Op, tune: OpTune) -> Op:
+    """-> the annotated hip_bconv_filts_biases function op of a BckConv: ONE call in place of the hip_bconv_biases + hip_bconv_filts pair of add_bck_conv_annotations
+    (which stays as it is), writing filts_grad_loss and biases_grad_loss.  On be=hip both operands are staged k-major and K is cut into up to 1024 slices summed in
+    slice order; on be=cpu the call is the two single chains.  The same refusals as add_bck_conv_annotations; a tile in the tune travels
+    with the function."""
+    if op.get_type() != "BckConv":
+        raise RtErr(f"bconv_filts_biases_func_op: op type {op.get_type()!r} is not BckConv")
+    op.bck_conv_geom()
+    if tune.use_be not in ("", "hip") or tune.use_culibs or tune.k1conv or tune.tconv or tune.ipconv:
+        raise UnsupErr(f"BckConv variants of op_tune={tune.to_str()} are generated by the reference's CUCL code generator; be=hip provides hip_bconv_*")
+    if tune.hip_dtype not in ("", "f32") or tune.hip_layout or tune.hip_algo or tune.hip_out:
+        raise UnsupErr("BckConv: fp32 gradients in reference layout only (no bf16, channels-last or Winograd variant)")
+    a = op.copy()
+    a.set_func_name(BCONV_FB_FUNC)
+    if tune.hip_tile:
+        a.str_vals["hip_tile"] = tune.hip_tile
+    return a
+
+
 # the native functions of the non-conv backward ops, in the reference's call order (src/rtc_fwd.cc:345-404), and of the two forward ops whose side outputs the
 # backward pass reads: the max-pooling argmax out_in_yx (test/rtc/pool.cucl, emit_out_in_yx) and the LRN out_scale_base (test/rtc/lrn.cucl, emit_out_scale_base)
 BCK_OP_FUNCS: Dict[str, tuple] = {
@@ -489,6 +511,7 @@ NATIVE_ARGS: Dict[str, tuple] = {
     # BckConv's gradients: the reference templates' arg lists (test/rtc/BckConv_in_grad_loss.cucl, BckConv_filts_grad_loss.cucl, BckConv_biases_grad_loss.cucl)
     "hip_bconv_in": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),
     "hip_bconv_filts": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT")),
+    "hip_bconv_filts_biases": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT"), ("biases_grad_loss", "OUT")),
     "hip_bconv_biases": (("out_grad_loss", "IN"), ("biases_grad_loss", "OUT")),   # filts as [K + 128][out_chan padded to 4]: what hip_conv's optional filts_km arg takes
     # the non-conv backward ops, in their reference templates' arg order (test/rtc/pool.cucl, lrn.cucl, spreading.cucl, bck_lrn.cucl, ZeroIfNonPos.cucl, softmax.cucl,
     # sm_grad_and_loss.cucl, sum_loss_over_imgs.cucl); the by-value scalars of those templates (avg_pool, alpha, ...) ride in the op

@@ -404,7 +404,7 @@ struct cpu_compute_t : public rtc_compute_t {
   // ---- functions: the native side door only
   static bool is_sgemm(string const &fn) { return fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "cpu_sgemm"; }
   static bool is_conv(string const &fn) { return fn == "hip_conv" || fn == "cudnn_conv" || fn == "cpu_conv_fwd"; }
-  static bool is_bck(string const &fn) { return fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases"; }
+  static bool is_bck(string const &fn) { return fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases" || fn == "hip_bconv_filts_biases"; }
   // the gradient pipe's non-conv functions and their var args in arg order (inputs | outputs); `refs`: kern_sz / stride / in_pad REF args
   struct bck_op_fn_t { char const *fn; char const *type; std::vector<char const *> ins, outs; bool refs; };
   static bck_op_fn_t const *find_bck_op(string const &fn) {
@@ -599,6 +599,13 @@ struct cpu_compute_t : public rtc_compute_t {
       if (!(zd == want) || !(zd == in)) rt_err(fn + ": arg 'in' has dims " + zd.pretty_str() + ", the op says " + op.get_dims("in").pretty_str());
       if (znm == inm) rt_err(fn + ": zero_if_in_non_pos=1: 'in' and 'in_grad_loss' are the same var '" + znm + "'");
       zin = (float const *)must_find(vis, znm).buf.get();
+    }
+    if (fn == "hip_bconv_filts_biases") {   // the two loops of hip_bconv_biases and hip_bconv_filts, one call: the bits of the two calls
+      string const bnm = var_of(am, "biases_grad_loss"); dims_t const b = get_var_dims(bnm); need_float(b, "biases_grad_loss");
+      if (b.dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
+      for (string const *o : {&fnm, &bnm}) if (*o == inm || *o == ognm) rt_err(fn + ": the output var '" + *o + "' is also an input of the call");
+      if (fnm == bnm) rt_err(fn + ": filts_grad_loss and biases_grad_loss are the same var '" + fnm + "'");
+      bconv_biases((float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, bnm).buf.get(), g);
     }
     if (din) bconv_in((float const *)must_find(vis, fnm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, inm).buf.get(), g, zin);
     else bconv_filts((float const *)must_find(vis, inm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, fnm).buf.get(), g);

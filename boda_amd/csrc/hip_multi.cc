@@ -360,6 +360,9 @@ struct hip_multi_compute_t : public rtc_compute_t {
       // BckConv's filter / bias gradients sum over the images: on img shards every device would hold a partial sum, and no cross-device reduction exists here
       if (nat && n() > 1 && (fi.op.get_func_name() == "hip_bconv_filts" || fi.op.get_func_name() == "hip_bconv_biases"))
         func_img_sum[fi.func_name] = "(a BckConv filter / bias gradient) sums over the images, which would need a cross-device reduction; only the data gradient (hip_bconv_in) runs on img shards";
+      // the fused filter + bias gradient writes TWO sums over the images; summing two outputs over the shards is not provided (and img_shards=1 on it is an RtErr)
+      if (nat && n() > 1 && fi.op.get_func_name() == "hip_bconv_filts_biases")
+        func_img_sum[fi.func_name] = "(hip_bconv_filts_biases, a BckConv's fused filter and bias gradient) sums over the images into two outputs, which would need a cross-device reduction of both; on several devices use hip_bconv_filts and hip_bconv_biases with img_shards=1";
       // the softmax loss: hip_sm_grad_and_loss divides by the GLOBAL image count and hip_sum_loss_over_imgs sums over all images; the gradient pipe's other six
       // non-conv functions (hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax) are independent per image and run on img shards
       if (nat && n() > 1 && fi.op.get_func_name() == "hip_sm_grad_and_loss") func_img_sum[fi.func_name] = "(the softmax loss gradient) divides by the GLOBAL image count, which an img shard does not know; hip_softmax runs on img shards";

@@ -47,7 +47,7 @@ struct native_kernels_t::impl_t {
 };
 
 
-struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false, bconv_in = false, bconv_filts = false, bck_ops = false, sgd = false, bn = false; int rows = 0, cg = 0; };
+struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false, bconv_in = false, bconv_filts = false, bconv_fb = false, bck_ops = false, sgd = false, bn = false; int rows = 0, cg = 0; };
 
 struct bconv_args_t { // must match kernels/bconv_in_f32.hip, kernels/bconv_filts_f32.hip
   float const *a; float const *b; float *d;
@@ -56,6 +56,14 @@ struct bconv_args_t { // must match kernels/bconv_in_f32.hip, kernels/bconv_filt
   int tiles_i, tiles_j, ksl, kt_per;
   unsigned a_bytes, b_bytes, d_bytes;
   float const *zin;   // bconv_in -DZINP=1: the forward input, the condition of the select on the store
+};
+
+struct bconv_fb_args_t { // must match kernels/bconv_fb_f32.hip
+  float const *g; float const *x; float *df; float *db;
+  float *ws; long slab_elems;
+  int B, C, H, W, OC, OH, OW;
+  int tiles_i, tiles_j, ksl, kt_per;
+  unsigned g_bytes, x_bytes;
 };
 
 struct bck_ops_args_t { // must match kernels/bck_ops_f32.hip
@@ -144,6 +152,8 @@ bool plan_ipconv_dma(conv_geom_t const &g, int num_cus, plan_t &p);
 plan_t plan_conv(conv_geom_t const &g, int num_cus, string const &tile, bool bf16 = false, string const &k1s = string(), bool allow_splitk = true, bool exact = true);
 plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile, bool zinp = false);   // (zinp: -DZINP=1) BckConv data gradient (kernels/bconv_in_f32.hip)
 plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile);    // BckConv filter gradient, in-launch K slices (kernels/bconv_filts_f32.hip)
+plan_t plan_bconv_filts_biases(conv_geom_t const &g, int num_cus, string const &tile);   // the fused filter + bias gradient, k-major staging, slab slices (kernels/bconv_fb_f32.hip)
+plan_t plan_bconv_slab_sum();                                                        // its second launch: the slabs added in slice order (kernels/bconv_fb_f32.hip -DSLAB_SUM)
 plan_t plan_bconv_biases();                                                          // BckConv bias gradient (kernels/bconv_filts_f32.hip -DBIAS_ONLY)
 long bconv_in_tiles(conv_geom_t const &g, int BJ);                                   // pel tiles over all SY x SX phases (the kernel's walk)
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log);

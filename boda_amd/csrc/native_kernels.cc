@@ -56,7 +56,7 @@ void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
     for (bn_launch_t const &l : plan_bn(bn_op_of_op(fi.op)).ls) (void)get_kernel(impl, host, l.p);
     return;
   }
-  if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases") {   // BckConv's gradients: the op must carry the geometry
+  if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases" || fn == "hip_bconv_filts_biases") {   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     return;
   }
@@ -88,7 +88,7 @@ void launch(native_host_t *host, kernel_t &k, gemm_args_t &a, tile_cfg_t const &
 
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log) {
   vect_string opts = p.defs; opts.push_back("-DKNAME=" + p.kname);
-  return hiprtc_compile(p.bn ? k_src_bn_f32 : p.sgd ? k_src_sgd_update_f32 : p.bck_ops ? k_src_bck_ops_f32 : p.bconv_in ? k_src_bconv_in_f32 : p.bconv_filts ? k_src_bconv_filts_f32 : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
+  return hiprtc_compile(p.bn ? k_src_bn_f32 : p.sgd ? k_src_sgd_update_f32 : p.bck_ops ? k_src_bck_ops_f32 : p.bconv_in ? k_src_bconv_in_f32 : p.bconv_filts ? k_src_bconv_filts_f32 : p.bconv_fb ? k_src_bconv_fb_f32 : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
 }
 
 // grow-only scratch shared by the split-K slabs and the Winograd-domain tensors (like the reference's cudnn scratch var)
@@ -783,6 +783,46 @@ void native_kernels_t::bconv_biases(float const *out_grad, float *biases_grad, c
   hip_err_chk(host->nh_launch(k.func, (uint32_t)g.OC, 1, 256, params), "hipModuleLaunchKernel(bconv_biases)");
   last_launch.kernel = "bodahip_bconv_biases"; last_launch.cfg = tile_cfg_t(); last_launch.grid = (uint32_t)g.OC; last_launch.block = 256;
   last_launch.flops = (double)g.B * g.OC * g.OH * g.OW; last_launch.algo_bytes = 4.0 * ((double)g.B * g.OC * g.OH * g.OW + g.OC);
+}
+// hip_bconv_filts_biases: both gradients from one main launch (kernels/bconv_fb_f32.hip); with K slices the main launch fills the call's slabs and a second launch in
+// the same stream adds them in slice order.  The slab workspace belongs to the call like a K-slice workspace (key: operands and plan) but holds no tickets: nothing to zero
+void native_kernels_t::bconv_filts_biases(float const *in, float const *out_grad, float *filts_grad, float *biases_grad, conv_geom_t const &g) {
+  plan_t const p = plan_bconv_filts_biases(g, host->nh_num_cus(), tune_of(impl, "conv_tile"));
+  kernel_t &k = get_kernel(impl, host, p);
+  bconv_fb_args_t a; memset(&a, 0, sizeof(a));
+  a.B = g.B; a.C = g.C; a.H = g.H; a.W = g.W; a.OC = g.OC; a.OH = g.OH; a.OW = g.OW;
+  a.g = out_grad; a.x = in; a.df = filts_grad; a.db = biases_grad;
+  a.g_bytes = (unsigned)(4ull * g.B * g.OC * g.OH * g.OW); a.x_bytes = (unsigned)(4ull * g.B * g.C * g.H * g.W);
+  long const NJ = (long)g.C * g.KH * g.KW, K = (long)g.B * g.OH * g.OW, nkt = (K + p.cfg.BK - 1) / p.cfg.BK;
+  a.tiles_i = (g.OC + p.cfg.BI - 1) / p.cfg.BI; a.tiles_j = (int)((NJ + p.cfg.BJ - 1) / p.cfg.BJ);
+  a.ksl = p.cfg.SPLITK; a.kt_per = (int)((nkt + a.ksl - 1) / a.ksl);
+  a.slab_elems = (long)g.OC * NJ + g.OC;
+  long const tiles = (long)a.tiles_i * a.tiles_j;
+  if (tiles * a.ksl >= (1L << 31)) unsup_err("hip_bconv_filts_biases: K-slice workspace too large");
+  kernel_t *ks = nullptr;
+  if (a.ksl > 1) {
+    ks = &get_kernel(impl, host, plan_bconv_slab_sum());
+    size_t const total = (size_t)a.ksl * (size_t)a.slab_elems * 4;
+    if (total >= (size_t(1) << 32)) unsup_err("hip_bconv_filts_biases: K-slice workspace too large");
+    string const key = "ksl:bconv_fb:" + std::to_string((uintptr_t)in) + ":" + std::to_string((uintptr_t)out_grad) + ":" + std::to_string((uintptr_t)filts_grad) + ":" +
+                       std::to_string((uintptr_t)biases_grad) + ":" + std::to_string(total);
+    auto it = impl->ktabs.find(key);
+    if (it == impl->ktabs.end()) {
+      if (host->nh_capturing()) rt_err("graph capture: the K-slice workspace of this call is not allocated yet -- run the call list once before capturing it");
+      void *dev = nullptr;
+      call_ws_make_room(impl, host, total);
+      hip_err_chk(hipMalloc(&dev, total), "hipMalloc(K-slice workspace)"); impl->call_ws_bytes += total;
+      it = impl->ktabs.emplace(key, dev).first;
+    }
+    a.ws = (float *)it->second;
+  }
+  uint32_t const grid = (uint32_t)(tiles * a.ksl);
+  void *params[] = {&a};
+  hip_err_chk(host->nh_launch(k.func, grid, 1, (uint32_t)p.cfg.threads(), params), "hipModuleLaunchKernel(bconv_filts_biases)");
+  if (ks) hip_err_chk(host->nh_launch(ks->func, (uint32_t)((a.slab_elems + 255) / 256), 1, 256, params), "hipModuleLaunchKernel(bconv_slab_sum)");
+  last_launch.kernel = p.kname; last_launch.cfg = p.cfg; last_launch.grid = grid; last_launch.block = p.cfg.threads();
+  last_launch.flops = 2.0 * g.OC * (double)NJ * K + (double)g.OC * K;
+  last_launch.algo_bytes = (double)a.g_bytes + a.x_bytes + 4.0 * ((double)g.OC * NJ + g.OC);
 }
 
 

@@ -17,6 +17,8 @@
 //                                       3x3 / 5x5 / pool-projection convolutions (the kernel sources instantiated per member inside one wrapper kernel, built at run time)
 //     hip_bconv_in / _filts / _biases   BckConv's three gradients (fp32, NCHW / OIHW): args filts out_grad_loss stride(REF) in_pad(REF) in_grad_loss |
 //                                       in out_grad_loss stride(REF) in_pad(REF) filts_grad_loss | out_grad_loss biases_grad_loss  (test/rtc/BckConv_*.cucl)
+//     hip_bconv_filts_biases            the filter and bias gradients in one call (kernels/bconv_fb_f32.hip): args in out_grad_loss stride(REF) in_pad(REF)
+//                                       filts_grad_loss biases_grad_loss
 //     the non-conv ops of the gradient pipe (fp32, img:chan:y:x; kernels/bck_ops_f32.hip), each with its reference template's arg list -- the templates' by-value
 //     scalars (avg_pool, emit_*, alpha, beta, k, local_size) ride in the op:
 //       hip_pool_yx             in kern_sz(REF) stride(REF) in_pad(REF) out out_in_yx                              test/rtc/pool.cucl (max, emit_out_in_yx=1)
@@ -143,6 +145,8 @@ struct native_kernels_t {
   void bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g, float const *zin = nullptr);
   void bconv_filts(float const *in, float const *out_grad, float *filts_grad, conv_geom_t const &g);
   void bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g);
+  // both at once, k-major staging, up to 1024 K slices in slabs summed by a second launch (kernels/bconv_fb_f32.hip); opt-in: ConvPipeBck(fuse_filts_biases=True)
+  void bconv_filts_biases(float const *in, float const *out_grad, float *filts_grad, float *biases_grad, conv_geom_t const &g);
   // the non-conv ops of the gradient pipe: ins / outs in the function's arg order (up to eight / two raw device pointers)
   // seed_word (dropout with g.seedvar): the device word added to g.seed
   void bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs, uint32_t const *seed_word = nullptr);

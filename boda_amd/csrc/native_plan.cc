@@ -1207,6 +1207,36 @@ plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile) {
 }
 plan_t plan_bconv_biases() { plan_t p; p.bconv_filts = true; p.kname = "bodahip_bconv_biases"; p.defs = {"-DBIAS_ONLY=1"}; return p; }
 
+// hip_bconv_filts_biases (kernels/bconv_fb_f32.hip): the same tile strings; both operands are staged k-major, so every thread owns one k offset (threads % BK == 0) and
+// whole rows AND columns ((threads / BK) divides BI and BJ); the LDS images are transposed with pitch BK + 1; K slices go to slabs summed by a second launch: 1..1024
+static void check_bconv_fb_cfg(tile_cfg_t const &c) {
+  int const nt = c.WI * c.WJ * 64;
+  bool ok = c.BI > 0 && c.BJ > 0 && c.BK > 0 && c.WI > 0 && c.WJ > 0 && nt <= 1024 && c.MT == 32 && c.BI % (c.WI * 32) == 0 && c.BJ % (c.WJ * 32) == 0 && c.BK % 2 == 0 &&
+            nt % c.BK == 0 && c.BI <= nt && c.MINW >= 1 && c.MINW <= 8 && c.SPLITK >= 1 && c.SPLITK <= 1024 && c.PF == 1 && c.SW == 0 && c.KHO == 0;
+  ok = ok && c.BI % (nt / c.BK) == 0 && c.BJ % (nt / c.BK) == 0;
+  int const accs = (c.BI / (c.WI * 32)) * (c.BJ / (c.WJ * 32));
+  ok = ok && accs * 16 <= 128 && 2ull * (c.BI + c.BJ) * (c.BK + 1) * 4 <= 160 * 1024;
+  if (!ok) unsup_err("hip_bconv_filts_biases: unsupported tile configuration " + c.str());
+}
+plan_t plan_bconv_filts_biases(conv_geom_t const &g, int num_cus, string const &tile) {
+  bconv_check_geom(g, "hip_bconv_filts_biases");
+  plan_t p; p.bconv_fb = true; p.kname = "bodahip_bconv_filts_biases";
+  bool ksl_given = false;
+  if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_filts_biases: bad tile '" + tile + "'"); ksl_given = std::count(tile.begin(), tile.end(), 'x') >= 6; }
+  else p.cfg = bconv_default_cfg(g.OC, 32);
+  if (!ksl_given) {   // plan_bconv_filts's rule -- about two workgroups per CU, every slice at least 8 K steps long -- with the cap of this kernel's slab sum
+    long const tiles = (long)((g.OC + p.cfg.BI - 1) / p.cfg.BI) * (((long)g.C * g.KH * g.KW + p.cfg.BJ - 1) / p.cfg.BJ);
+    long const nkt = ((long)g.B * g.OH * g.OW + p.cfg.BK - 1) / p.cfg.BK;
+    long ksl = (2L * num_cus + tiles - 1) / tiles;
+    ksl = std::min<long>(ksl, std::max<long>(1, nkt / 8));
+    p.cfg.SPLITK = (int)std::max<long>(1, std::min<long>(1024, ksl));
+  }
+  check_bconv_fb_cfg(p.cfg);
+  p.defs = bconv_geom_defs(g, p.cfg); p.defs.push_back(string("-DSLICED=") + (p.cfg.SPLITK > 1 ? "1" : "0"));
+  return p;
+}
+plan_t plan_bconv_slab_sum() { plan_t p; p.bconv_fb = true; p.kname = "bodahip_bconv_slab_sum"; p.defs = {"-DSLAB_SUM=1"}; return p; }
+
 
 
 // ---- the non-conv ops of the gradient pipe (kernels/bck_ops_f32.hip).  Bandwidth kernels: no tile to choose, only the geometry to fold into the code (pooling

@@ -226,16 +226,20 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
   } else if (t == "BckConv") {   // the three gradient functions (or, for the bare op, all three: the calls of src/rtc_fwd.cc:398-400)
     conv_geom_t const g = bck_geom_of_op(op);
     string const fn = op.has_func_name() ? op.get_func_name() : string();
-    if (!fn.empty() && fn != "hip_bconv_in" && fn != "hip_bconv_filts" && fn != "hip_bconv_biases") rt_err("prebuild: BckConv function '" + fn + "' has no native kernel");
+    if (!fn.empty() && fn != "hip_bconv_in" && fn != "hip_bconv_filts" && fn != "hip_bconv_biases" && fn != "hip_bconv_filts_biases") rt_err("prebuild: BckConv function '" + fn + "' has no native kernel");
     std::vector<plan_t> ps;
     if (fn.empty() || fn == "hip_bconv_in") ps.push_back(plan_bconv_in(g, num_cus, tile, op_zinp_flag(op)));
     if (fn.empty() || fn == "hip_bconv_biases") ps.push_back(plan_bconv_biases());
     if (fn.empty() || fn == "hip_bconv_filts") ps.push_back(plan_bconv_filts(g, num_cus, tile));
+    if (fn == "hip_bconv_filts_biases") {   // (opt-in: never part of the bare op's three calls) the main kernel and, with K slices, the slab sum behind it
+      ps.push_back(plan_bconv_filts_biases(g, num_cus, tile));
+      if (ps.back().cfg.SPLITK > 1) ps.push_back(plan_bconv_slab_sum());
+    }
     string desc; size_t bytes = 0;
     for (plan_t const &q : ps) {
       desc += (desc.empty() ? "" : " | ") + q.kname + (q.defs.size() > 1 ? " " + q.cfg.str() : string());
       if (q.bconv_in) desc += " grid=" + std::to_string((long)((g.C + q.cfg.BI - 1) / q.cfg.BI) * bconv_in_tiles(g, q.cfg.BJ)) + (q.defs.back() == "-DZINP=1" ? " -DZINP=1" : "");
-      if (q.kname == "bodahip_bconv_filts") desc += " ksl=" + std::to_string(q.cfg.SPLITK);
+      if (q.kname == "bodahip_bconv_filts" || q.kname == "bodahip_bconv_filts_biases") desc += " ksl=" + std::to_string(q.cfg.SPLITK);
       if (!arch.empty()) bytes += compile_plan(q, arch, &log).size();
     }
     if (op_img_shards_flag(op)) {   // a flagged filter / bias gradient on several devices also runs the sum of the per-device partials (csrc/hip_multi.cc): one kernel for every device count
@@ -619,7 +623,7 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
          (fn == "hip_conv_winograd") ? "winograd_all" : nullptr, km); // hip_conv_winograd: the F(2x2,3x3) path for this function (3x3 / stride 1; others: direct)
     return;
   }
-  if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases") {
+  if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases" || fn == "hip_bconv_filts_biases") {
     // every var must have the dims the op gives its arg -- except the number of images, which only has to agree between the vars (a multi-device backend
     // runs the data gradient on img shards: csrc/hip_multi.cc)
     conv_geom_t g = bck_geom_of_op(fi.op);
@@ -658,6 +662,13 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
       string const in = var_dims("in"), fgl = var_dims("filts_grad_loss");
       if (!(fi.op.get_dims("filts_grad_loss") == fi.op.get_dims("filts"))) rt_err(fn + ": filts_grad_loss must have the dims of filts");
       bconv_filts((float const *)host->nh_var_ptr(in), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(fgl), g);
+    } else if (fn == "hip_bconv_filts_biases") {
+      string const in = var_dims("in"), fgl = var_dims("filts_grad_loss"), bgl = var_dims("biases_grad_loss");
+      if (!(fi.op.get_dims("filts_grad_loss") == fi.op.get_dims("filts"))) rt_err(fn + ": filts_grad_loss must have the dims of filts");
+      if (fi.op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
+      for (string const *o : {&fgl, &bgl}) if (*o == in || *o == ogl) rt_err(fn + ": the output var '" + *o + "' is also an input of the call");
+      if (fgl == bgl) rt_err(fn + ": filts_grad_loss and biases_grad_loss are the same var '" + fgl + "'");
+      bconv_filts_biases((float const *)host->nh_var_ptr(in), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(fgl), (float *)host->nh_var_ptr(bgl), g);
     } else {
       string const bgl = var_dims("biases_grad_loss");
       if (fi.op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");

@@ -4,6 +4,7 @@ and the share of the step each native function takes (sums of the backend's per-
 
     python tools/bck_pipe_bench.py [--nets nin,alexnet] [--batch 256] [--runs 5] [--warmup 2] [--out profiles/r09_bck_pipe_bench.txt]
     python tools/bck_pipe_bench.py --fuse-relu-grad [--repeats 3] [--out profiles/r09_bck_fuse_ab.txt]
+    python tools/bck_pipe_bench.py --fuse-filts-biases --nets resnet50 --batch 32 [--repeats 3] [--limit 900] [--out profiles/r15_resnet50_step_fb.txt]
     python tools/bck_pipe_bench.py --graph [--repeats 3] [--out profiles/r10_bck_graph_ab.txt]
     python tools/bck_pipe_bench.py --devices 0:1:2:3 [--out profiles/bck_pipe_devices.txt]
     python tools/bck_pipe_bench.py --sgd [--repeats 3] [--out profiles/r13_sgd_update.txt]
@@ -13,6 +14,9 @@ and the share of the step each native function takes (sums of the backend's per-
 params and inputs -- after the usual warm-up, in --repeats alternating blocks of --runs steps.  Per net two JSON lines ("way": "unfused" / "fused": step ms as the median
 over all blocks, the medians of the single blocks (their spread is the run-to-run spread a difference has to beat), images/s, the call count, the per-function share)
 and a third with the launches removed and the fused / unfused ratio.  The comparison is between the two ways of one run, never against a recorded figure.
+
+--fuse-filts-biases: the same A/B for ConvPipeBck(fuse_filts_biases=True): every BckConv's hip_bconv_biases + hip_bconv_filts pair as one hip_bconv_filts_biases call
+(DESIGN.md section 3.11).  The losses need not have the same bits: nothing the loss depends on changes, and they do; the gradients follow other chains.
 
 --graph: the same construction for the step as one hipGraph replay.  Three ways in ONE process, each a ConvPipeBck(seed_in_var=True) on a backend instance of its own
 with the same params and inputs: "eager" (run_device_only), "graph" (capture_graph(), run_graph) and "graph_parallel" (capture_graph(parallel=True): the calls' true
@@ -53,7 +57,7 @@ def _pipe(net, batch):
     return {"nin": conv_pipe.nin_imagenet, "alexnet": conv_pipe.alexnet_ng_conv, "resnet50": conv_pipe.resnet50}[net](batch)
 
 
-def fuse_ab(net, batch, runs, warmup, repeats):
+def fuse_ab(net, batch, runs, warmup, repeats, option="fuse_relu_grad"):
     import numpy as np
     from boda_amd import conv_pipe
     from boda_amd.bck_pipe import ConvPipeBck, add_bck_ops, host_params
@@ -68,7 +72,7 @@ def fuse_ab(net, batch, runs, warmup, repeats):
     for way, fuse in (("unfused", False), ("fused", True)):
         rtc = make_rtc("(be=hip)", 0)
         rtc.init()
-        drv = ConvPipeBck(rtc, fuse_relu_grad=fuse)
+        drv = ConvPipeBck(rtc, **{option: fuse})
         drv.init(bp, params)
         rtc.copy_nda_to_var("data", data); rtc.copy_nda_to_var("label", label)
         ways[way] = {"rtc": rtc, "drv": drv, "blocks": [], "ms": [], "share": {}}
@@ -234,27 +238,31 @@ def main(argv=None):
     ap.add_argument("--limit", type=int, default=240, help="seconds per net")
     ap.add_argument("--out", default="")
     ap.add_argument("--fuse-relu-grad", action="store_true", help="A/B: the step with and without the ReLU gradients folded into their producers, in one process")
+    ap.add_argument("--fuse-filts-biases", action="store_true", help="A/B: the step with every BckConv's bias + filter gradient pair, and with the one fused hip_bconv_filts_biases call, in one process")
     ap.add_argument("--graph", action="store_true", help="A/B: the eager step, the step as one hipGraph replay, and the replay with the calls' true dependencies, in one process")
     ap.add_argument("--sgd", action="store_true", help="A/B: the step without a solver, with the SGD update as multi-tensor calls, and with one update call per tensor, in one process")
     ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad / --graph / --sgd: alternating blocks of --runs steps per way")
     ap.add_argument("--devices", default="", help="e.g. 0:1:2:3: the plain step on the multi-device backend (be=hip,devices=...), batch sharded on img")
     ap.add_argument("--child", default="")
     a = ap.parse_args(argv)
-    if a.devices and (a.graph or a.fuse_relu_grad or a.sgd):
+    if a.devices and (a.graph or a.fuse_relu_grad or a.sgd or a.fuse_filts_biases):
         ap.error("--devices times the plain step: graph capture is not provided on several devices, and the fused and the solver A/B run on one")
-    if a.graph + a.fuse_relu_grad + a.sgd > 1:
-        ap.error("--graph, --fuse-relu-grad and --sgd are three comparisons: run them one at a time")
-    a.out = a.out or os.path.join(ROOT, "profiles", "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
+    if a.graph + a.fuse_relu_grad + a.sgd + a.fuse_filts_biases > 1:
+        ap.error("--graph, --fuse-relu-grad, --fuse-filts-biases and --sgd are four comparisons: run them one at a time")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
     if a.child:
         if a.sgd:
             return sgd_ab(a.child, a.batch, a.runs, a.warmup, a.repeats)
         if a.graph:
             return graph_ab(a.child, a.batch, a.runs, a.warmup, a.repeats)
+        if a.fuse_filts_biases:
+            return fuse_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, "fuse_filts_biases")
         return fuse_ab(a.child, a.batch, a.runs, a.warmup, a.repeats) if a.fuse_relu_grad else one_net(a.child, a.batch, a.runs, a.warmup, a.devices)
     lines = []
     for net in a.nets.split(","):
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", net, "--batch", str(a.batch), "--runs", str(a.runs), "--warmup", str(a.warmup)]
         cmd += ["--fuse-relu-grad", "--repeats", str(a.repeats)] if a.fuse_relu_grad else []
+        cmd += ["--fuse-filts-biases", "--repeats", str(a.repeats)] if a.fuse_filts_biases else []
         cmd += ["--graph", "--repeats", str(a.repeats)] if a.graph else []
         cmd += ["--sgd", "--repeats", str(a.repeats)] if a.sgd else []
         cmd += ["--devices", a.devices] if a.devices else []
@@ -263,9 +271,9 @@ def main(argv=None):
             print(f"{net}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
             return r.returncode
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
-        print("\n".join(lines[-4:] if (a.graph or a.sgd) else lines[-3:] if a.fuse_relu_grad else lines[-1:]), flush=True)
+        print("\n".join(lines[-4:] if (a.graph or a.sgd) else lines[-3:] if (a.fuse_relu_grad or a.fuse_filts_biases) else lines[-1:]), flush=True)
     with open(a.out, "w") as f:
-        extra = f" --devices {a.devices}" if a.devices else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else ""
+        extra = f" --devices {a.devices}" if a.devices else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
         f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 
