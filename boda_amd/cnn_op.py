@@ -488,7 +488,7 @@ def pipe_func_args(fop: Op) -> tuple:
     if fn == "hip_dropout" and has_seed_var_flag(fop):
         return NATIVE_ARGS[fn][:1] + ((SEED_VAR_ARG, "IN"),) + NATIVE_ARGS[fn][1:]
     if fn == "hip_reduce":
-        return tuple((an, "IN") for an in fop.multi_names("ins")) + (("out", "OUT"),)
+        return tuple((an, "IN") for an in fop.multi_names("ins")) + NATIVE_ARGS[fn]
     if fn in ("hip_bconv_in", "hip_spreading") and has_zinp_flag(fop):
         return NATIVE_ARGS[fn][:-1] + (("in", "IN"),) + NATIVE_ARGS[fn][-1:]
     if fn == "hip_conv_nhwc" and fop.has("nhwc_residual") and fop.get_u32("nhwc_residual"):     # (nhwc.fuse_residual: the shortcut, in front of out)
@@ -496,7 +496,8 @@ def pipe_func_args(fop: Op) -> tuple:
     return NATIVE_ARGS[fn]
 
 
-# arg tables of the native side-door functions (the stubs test/rtc/cublas_sgemm.cucl:1-4, cudnn_conv.cucl:1-7)
+# arg tables of the native side-door functions (the stubs test/rtc/cublas_sgemm.cucl:1-4, cudnn_conv.cucl:1-7).  The backend keeps the same facts in one table of its own,
+# csrc/native_funcs.h; tests/test_native_funcs_cpu.py holds this table, pipe_func_args and the *_FUNCS tuples of this file to it
 NATIVE_ARGS: Dict[str, tuple] = {
     "hip_sgemm": (("a", "IN"), ("b", "IN"), ("c", "OUT")),
     "cublas_sgemm": (("a", "IN"), ("b", "IN"), ("c", "OUT")),
@@ -525,6 +526,7 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_sum_loss_over_imgs": (("loss_per_pel", "IN"), ("loss", "OUT")),
     # the gradient pipe's plumbing (test/rtc/dropout.cucl; the copy calls of src/rtc_fwd.cc:267-294).  VAL: a by-value scalar of the CALL (uint32 det_drop_seed).
     # hip_reduce's list depends on the op (ins_0 .. ins_{n-1}, out), hip_dropout's on seed_from_var (inout, det_drop_seed_var, det_drop_seed): pipe_func_args
+    "hip_reduce": (("out", "OUT"),),
     "hip_dropout": (("inout", "OUT"), ("det_drop_seed", "VAL")),
     "hip_concat": (("in", "IN"), ("out", "OUT")),
     "hip_split": (("in", "IN"), ("out", "OUT")),

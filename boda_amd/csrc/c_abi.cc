@@ -211,6 +211,28 @@ int bodahip_explain_plan(const char *op_lexp, int num_cus, const char *tile, cha
   native_kernels_t::prebuild(parse_op_lexp(S(op_lexp, "op")), "", num_cus > 0 ? num_cus : 256, tile ? tile : "", &plan);
   put_str(plan_buf, plan_buf_sz, plan, "plan");
   ABI_CATCH }
+int bodahip_native_funcs(char *buf, size_t buf_sz) {
+  ABI_TRY
+  static char const *const modes[] = {"on_shards", "replicated_only", "needs_flag", "refused"};
+  string s;
+  for (native_func_t const &f : kNativeFuncs) {
+    string flags; for (auto const &fl : kOpFlagNames) if (f.flags & fl.flag) flags += string(flags.empty() ? "" : ",") + fl.name;
+    s += string(f.name) + " family=" + kFamilyNames[f.family] + " member=" + std::to_string(f.member) + " types=" + f.types[0] + (f.types[1] ? string(",") + f.types[1] : string()) +
+         " flags=" + (flags.empty() ? "-" : flags) + " be=" + ((f.backends & kBeHip) ? ((f.backends & kBeCpu) ? "hip,cpu" : "hip") : "cpu") + " multi_dev=" + modes[f.multi_dev.mode] +
+         " opt=" + (f.opt_arg.name ? string(f.opt_arg.name) + ":" + kArgKindNames[f.opt_arg.kind] : string("-")) + " why=" + f.multi_dev.why + "\n";
+  }
+  put_str(buf, buf_sz, s, "native funcs");
+  ABI_CATCH }
+int bodahip_func_args(const char *op_lexp, char *buf, size_t buf_sz) {
+  ABI_TRY
+  op_base_t const op = parse_op_lexp(S(op_lexp, "op"));
+  native_func_t const *f = op.has_func_name() ? find_native_func(op.get_func_name()) : nullptr;
+  if (!f) rt_err("func_args: the op names no native function");
+  (void)op_zinp_flag(op); (void)op_seed_var_flag(op); (void)op_img_shards_flag(op); (void)op_nhwc_residual_flag(op);   // (refuse a flag the function does not take)
+  string s;
+  for (auto const &a : native_func_args(*f, op)) s += string(s.empty() ? "" : " ") + a.first + ":" + kArgKindNames[a.second];
+  put_str(buf, buf_sz, s, "func args");
+  ABI_CATCH }
 int bodahip_compile_stats(uint64_t *cache_hits_out, uint64_t *compiled_out, double *compile_ms_out) {
   ABI_TRY
   hiprtc_compile_stats(cache_hits_out, compiled_out, compile_ms_out);

@@ -349,7 +349,7 @@ void bn_bck_in(bn_op_t const &b, float const *in, float const *dy, float *dx, fl
 } // namespace
 
 struct cpu_var_t { std::shared_ptr<void> buf; dims_t dims; };
-struct cpu_func_t { rtc_func_info_t info; };
+struct cpu_func_t { rtc_func_info_t info; native_func_t const *row; };   // row: the function's row of native_funcs.h, looked up when it is compiled
 
 struct cpu_compute_t : public rtc_compute_t {
   bool init_done = false;
@@ -402,61 +402,29 @@ struct cpu_compute_t : public rtc_compute_t {
   p_nda_t get_var_raw_native_pointer(string const &vn) override { cpu_var_t const &v = must_find(vis, vn); return std::make_shared<nda_t>(v.dims, v.buf.get()); }
 
   // ---- functions: the native side door only
-  static bool is_sgemm(string const &fn) { return fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "cpu_sgemm"; }
-  static bool is_conv(string const &fn) { return fn == "hip_conv" || fn == "cudnn_conv" || fn == "cpu_conv_fwd"; }
-  static bool is_bck(string const &fn) { return fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases" || fn == "hip_bconv_filts_biases"; }
-  // the gradient pipe's non-conv functions and their var args in arg order (inputs | outputs); `refs`: kern_sz / stride / in_pad REF args
-  struct bck_op_fn_t { char const *fn; char const *type; std::vector<char const *> ins, outs; bool refs; };
-  static bck_op_fn_t const *find_bck_op(string const &fn) {
-    static bck_op_fn_t const tab[] = {
-      {"hip_pool_yx", "Pooling", {"in"}, {"out", "out_in_yx"}, true},
-      {"hip_spreading", "Spreading", {"out", "out_grad_loss", "out_in_yx"}, {"in_grad_loss"}, true},
-      {"hip_lrn_sb", "LRN", {"in"}, {"out", "out_scale_base"}, false},
-      {"hip_bck_lrn", "BckLRN", {"in", "out", "out_grad_loss", "out_scale_base"}, {"in_grad_loss"}, false},
-      {"hip_zero_if_non_pos", "ZeroIfNonPos", {"in", "cond"}, {"out"}, false},
-      {"hip_softmax", "SoftmaxWithLoss", {"in"}, {"prob"}, false},
-      {"hip_sm_grad_and_loss", "SoftmaxWithLoss", {"prob", "label"}, {"in_grad_loss", "loss_per_pel"}, false},
-      {"hip_sum_loss_over_imgs", "SoftmaxWithLoss", {"loss_per_pel"}, {"loss"}, false},
-      {"hip_reduce", "Reduce", {}, {"out"}, false},        // (inputs: ins_0 .. ins_{ins_num-1})
-      {"hip_dropout", "Dropout", {}, {"inout"}, false},    // (also BckDropout's)
-      {"hip_concat", "Concat", {"in"}, {"out"}, false},
-      {"hip_split", "Split", {"in"}, {"out"}, false},
-      {"hip_chan_affine", "ChanAffine", {"in", "a", "b"}, {"out"}, false},
-    };
-    for (auto const &d : tab) if (fn == d.fn) return &d;
-    return nullptr;
-  }
-  static std::vector<string> bck_op_ins(bck_op_fn_t const &d, op_base_t const &op) {
-    std::vector<string> r(d.ins.begin(), d.ins.end());
-    if (string(d.fn) == "hip_reduce") {
-      uint32_t const n = op.get_u32("ins_num");
-      if (n < 2 || n > 8) unsup_err("hip_reduce: ins_num=" + std::to_string(n) + ": 2 to 8 inputs");
-      for (uint32_t i = 0; i < n; ++i) r.push_back("ins_" + std::to_string(i));
-    }
-    return r;
-  }
-  static bool type_ok(bck_op_fn_t const &d, string const &t) { return t == d.type || (string(d.fn) == "hip_dropout" && t == "BckDropout"); }
   void compile(vect_rtc_func_info_t const &func_infos, rtc_compile_opts_t const &) override {
     assert_st(init_done);
     for (auto const &fi : func_infos) {
       if (funcs.count(fi.func_name)) rt_err("compile: function '" + fi.func_name + "' already exists");
       string const fn = fi.op.has_func_name() ? fi.op.get_func_name() : string();
-      if (!is_sgemm(fn) && !is_conv(fn) && !is_bck(fn) && !find_bck_op(fn) && fn != "hip_sgd_update" && !is_bn_func_name(fn))
-        unsup_err("be=cpu runs the native sgemm / Convolution / BckConv functions and the gradient pipe's non-conv functions only (hip_sgemm, hip_conv and their aliases, hip_bconv_*, "
-                  "hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax, hip_sm_grad_and_loss, hip_sum_loss_over_imgs, hip_reduce, hip_dropout, hip_concat, hip_split, hip_chan_affine, hip_sgd_update, hip_bn_stats, hip_bn_fwd, hip_bn_bck_sums, hip_bn_bck_in, hip_fan_out); '" +
+      native_func_t const *f = find_native_func(fn);   // (the table of native_funcs.h says which functions be=cpu runs)
+      if (!f || !(f->backends & kBeCpu))
+        unsup_err("be=cpu runs the native sgemm / Convolution / BckConv functions and the gradient pipe's non-conv functions only (hip_sgemm, hip_conv and their aliases, hip_bconv_*, " +
+                  native_func_names([](native_func_t const &r) { return (r.backends & kBeCpu) && r.family >= kFamBckOp; }, ", ") + "); '" +
                                                     (fn.empty() ? fi.func_name : fn) + "' is generated CUCL source, which needs a GPU backend");
-      if (is_conv(fn)) (void)fi.op.get_u32("conv_has_relu");
+      if (f->family == kFamConv) (void)fi.op.get_u32("conv_has_relu");
       (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
       (void)op_seed_var_flag(fi.op);   // (likewise)
       (void)op_img_shards_flag(fi.op);   // (likewise; here there is one shard: a flagged call is the unflagged one)
-      if (fn == "hip_sgd_update") (void)sgd_op_of_op(fi.op);   // (the op must be whole)
-      if (is_bn_func_name(fn)) (void)bn_op_of_op(fi.op);   // (likewise)
-      if (bck_op_fn_t const *d = find_bck_op(fn)) {
-        if (!type_ok(*d, fi.op.get_type())) rt_err(fn + ": a function of op type " + d->type + ", not " + fi.op.get_type());
-        for (string const &an : bck_op_ins(*d, fi.op)) (void)fi.op.get_dims(an);
-        for (char const *an : d->outs) (void)fi.op.get_dims(an);
+      if (f->family == kFamSgd) (void)sgd_op_of_op(fi.op);   // (the op must be whole)
+      if (f->family == kFamBn) (void)bn_op_of_op(fi.op);   // (likewise)
+      if (f->family == kFamBckOp) {
+        if (!f->of_type(fi.op.get_type())) rt_err(fn + ": a function of op type " + f->types[0] + ", not " + fi.op.get_type());
+        bck_op_args_t const a = bck_op_args(*f, fi.op);
+        for (string const &an : a.ins) (void)fi.op.get_dims(an);
+        for (string const &an : a.outs) (void)fi.op.get_dims(an);
       }
-      funcs.emplace(fi.func_name, cpu_func_t{fi});
+      funcs.emplace(fi.func_name, cpu_func_t{fi, f});
     }
   }
   void release_func(string const &func_name) override { must_erase(funcs, func_name); }
@@ -566,30 +534,31 @@ struct cpu_compute_t : public rtc_compute_t {
       bgl[oc] = v;
     }
   }
-  void run_bck(string const &fn, op_base_t const &op, map_str_rtc_arg_t const &am) {
+  void run_bck(native_func_t const &f, op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = f.name;
     string const ognm = var_of(am, "out_grad_loss");
     dims_t const og = get_var_dims(ognm); need_float(og, "out_grad_loss");
     if (og.sz() != 4) rt_err(fn + ": out_grad_loss must be img:chan:y:x");
     conv_geom_c g; memset(&g, 0, sizeof(g));
     g.B = og.dsz("img"); g.OC = og.dsz("chan"); g.OH = og.dsz("y"); g.OW = og.dsz("x");
-    if (fn == "hip_bconv_biases") {
+    if (f.member == kBconvBiases) {
       string const bnm = var_of(am, "biases_grad_loss"); dims_t const b = get_var_dims(bnm); need_float(b, "biases_grad_loss");
       if (b.dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
       bconv_biases((float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, bnm).buf.get(), g);
       return;
     }
-    bool const din = fn == "hip_bconv_in";
+    bool const din = f.member == kBconvIn;
     string const fnm = var_of(am, din ? "filts" : "filts_grad_loss"), inm = var_of(am, din ? "in_grad_loss" : "in");
-    dims_t const f = get_var_dims(fnm), in = get_var_dims(inm);
-    need_float(f, "filts"); need_float(in, "in");
+    dims_t const fd = get_var_dims(fnm), in = get_var_dims(inm);
+    need_float(fd, "filts"); need_float(in, "in");
     auto si = am.find("stride"), pi = am.find("in_pad");
     if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
     dims_t const stride = si->second.get_dims(*this), in_pad = pi->second.get_dims(*this);
-    if (f.sz() != 4 || in.sz() != 4 || stride.sz() != 2 || in_pad.sz() != 2) rt_err(fn + ": filts out_chan:in_chan:y:x, in img:chan:y:x, stride / in_pad y:x");
-    g.C = in.dsz("chan"); g.H = in.dsz("y"); g.W = in.dsz("x"); g.KH = f.dsz("y"); g.KW = f.dsz("x");
+    if (fd.sz() != 4 || in.sz() != 4 || stride.sz() != 2 || in_pad.sz() != 2) rt_err(fn + ": filts out_chan:in_chan:y:x, in img:chan:y:x, stride / in_pad y:x");
+    g.C = in.dsz("chan"); g.H = in.dsz("y"); g.W = in.dsz("x"); g.KH = fd.dsz("y"); g.KW = fd.dsz("x");
     g.SY = stride.dsz("y"); g.SX = stride.dsz("x"); g.PY = in_pad.dsz("y"); g.PX = in_pad.dsz("x");
     if (!g.SY || !g.SX) rt_err(fn + ": zero stride");
-    if (f.dsz("out_chan") != (uint32_t)g.OC || f.dsz("in_chan") != (uint32_t)g.C || in.dsz("img") != (uint32_t)g.B) rt_err(fn + ": inconsistent filts / in / out_grad_loss dims");
+    if (fd.dsz("out_chan") != (uint32_t)g.OC || fd.dsz("in_chan") != (uint32_t)g.C || in.dsz("img") != (uint32_t)g.B) rt_err(fn + ": inconsistent filts / in / out_grad_loss dims");
     if ((g.H + 2 * g.PY - g.KH) / g.SY + 1 != g.OH || (g.W + 2 * g.PX - g.KW) / g.SX + 1 != g.OW) rt_err(fn + ": out_grad_loss dims do not match in / filts / stride / in_pad");
     float const *zin = nullptr;
     if (din && op_zinp_flag(op)) {   // the forward input: the op's in dims (the image count the other vars'), and not the var this call writes
@@ -600,7 +569,7 @@ struct cpu_compute_t : public rtc_compute_t {
       if (znm == inm) rt_err(fn + ": zero_if_in_non_pos=1: 'in' and 'in_grad_loss' are the same var '" + znm + "'");
       zin = (float const *)must_find(vis, znm).buf.get();
     }
-    if (fn == "hip_bconv_filts_biases") {   // the two loops of hip_bconv_biases and hip_bconv_filts, one call: the bits of the two calls
+    if (f.member == kBconvFiltsBiases) {   // the two loops of hip_bconv_biases and hip_bconv_filts, one call: the bits of the two calls
       string const bnm = var_of(am, "biases_grad_loss"); dims_t const b = get_var_dims(bnm); need_float(b, "biases_grad_loss");
       if (b.dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
       for (string const *o : {&fnm, &bnm}) if (*o == inm || *o == ognm) rt_err(fn + ": the output var '" + *o + "' is also an input of the call");
@@ -617,11 +586,11 @@ struct cpu_compute_t : public rtc_compute_t {
     return *static_cast<float const *>(n->rp);
   }
   // the gradient pipe's non-conv functions: every var must have the dims the op gives its arg (the image count only has to agree between the vars, as on be=hip)
-  void run_bck_op(bck_op_fn_t const &d, op_base_t const &op, map_str_rtc_arg_t const &am) {
-    string const fn = d.fn;
+  void run_bck_op(native_func_t const &f, op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = f.name; bck_op_args_t const d = bck_op_args(f, op);
     long n_img = -1;
-    auto var_ptr = [&](char const *an) -> float * {
-      string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn); need_float(vd, an);
+    auto var_ptr = [&](string const &an) -> float * {
+      string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn); need_float(vd, an.c_str());
       dims_t want = op.get_dims(an);
       if (want.sz() >= 1 && want.names(0) == "img" && vd.sz() == want.sz()) {
         if (n_img < 0) n_img = vd.dims(0);
@@ -637,8 +606,8 @@ struct cpu_compute_t : public rtc_compute_t {
       if (!(ri->second.get_dims(*this) == op.get_dims(an))) rt_err(fn + ": arg '" + an + "' disagrees with the op");
     }
     float *in[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, *out[2] = {nullptr, nullptr};
-    std::vector<string> const in_ans = bck_op_ins(d, op);
-    for (size_t i = 0; i < in_ans.size(); ++i) in[i] = var_ptr(in_ans[i].c_str());
+    std::vector<string> const &in_ans = d.ins;   // (hip_reduce: ins_0 .. ins_{ins_num-1})
+    for (size_t i = 0; i < in_ans.size(); ++i) in[i] = var_ptr(in_ans[i]);
     for (size_t i = 0; i < d.outs.size(); ++i) out[i] = var_ptr(d.outs[i]);
     bool const zinp = op_zinp_flag(op);
     float const *zin = nullptr;
@@ -655,26 +624,26 @@ struct cpu_compute_t : public rtc_compute_t {
       bool const small = g.H + 2 * g.PY < g.KH || g.W + 2 * g.PX < g.KW;   // either padded dim below the window: a 1 x 1 output
       auto osz = [&](long in_sz, long k, long s, long pd) { return small ? 1 : (in_sz + 2 * pd - k + s - 1) / s + 1; };
       if (osz(g.H, g.KH, g.SY, g.PY) != g.OH || osz(g.W, g.KW, g.SX, g.PX) != g.OW) rt_err(fn + ": out plane does not follow from in / kern_sz / stride / in_pad");
-      if (fn == "hip_pool_yx") {
+      if (f.member == kOpPoolYx) {
         if (!op.get_u32("emit_out_in_yx") && !g.avg) unsup_err(fn + ": a Pooling with emit_out_in_yx=0 belongs to the forward pipe");
         pool_yx(in[0], out[0], out[1], g);
       } else spreading(in[1], in[2], out[0], g, zin);
-    } else if (fn == "hip_lrn_sb" || fn == "hip_bck_lrn") {
+    } else if (f.member == kOpLrnSb || f.member == kOpBckLrn) {
       dims_t const &i4 = op.get_dims("in");
       if (i4.sz() != 4) rt_err(fn + ": in must be img:chan:y:x");
       lrn_geom_c g{n_img, (long)i4.dsz("chan"), (long)i4.dsz("y") * i4.dsz("x"), (long)op.get_u32("local_size"), op_f32(op, "alpha"), op_f32(op, "beta"), op_f32(op, "k")};
       if (g.LS < 1 || g.LS % 2 == 0) unsup_err(fn + ": local_size=" + std::to_string(g.LS) + ": only odd windows (an even local_size has no centre channel)");
-      if (fn == "hip_lrn_sb") {
+      if (f.member == kOpLrnSb) {
         if (!op.get_u32("emit_out_scale_base")) unsup_err(fn + ": an LRN with emit_out_scale_base=0 belongs to the forward pipe");
         lrn_sb(in[0], out[0], out[1], g);
       } else bck_lrn(in[0], in[1], in[2], in[3], out[0], g, zinp);
-    } else if (fn == "hip_zero_if_non_pos") {
+    } else if (f.member == kOpZeroIfNonPos) {
       zero_if_non_pos(in[0], in[1], out[0], (long)get_var_dims(var_of(am, "in")).dims_prod());
-    } else if (fn == "hip_reduce") {
+    } else if (f.member == kOpReduce) {
       dims_t const &od = op.get_dims("out");
       for (string const &an : in_ans) if (!(op.get_dims(an) == od)) rt_err(fn + ": " + an + " dims " + op.get_dims(an).pretty_str() + " differ from out's " + od.pretty_str());
       reduce(in, (int)in_ans.size(), out[0], (long)get_var_dims(var_of(am, "out")).dims_prod());
-    } else if (fn == "hip_dropout") {
+    } else if (f.member == kOpDropout) {
       float const ratio = op_f32(op, "dropout_ratio");
       if (!(ratio > 0.0f && ratio < 1.0f)) rt_err(fn + ": dropout_ratio=" + std::to_string(ratio) + " must lie inside (0, 1)");
       auto si = am.find("det_drop_seed");
@@ -688,15 +657,15 @@ struct cpu_compute_t : public rtc_compute_t {
         seed += *(uint32_t const *)must_find(vis, wi->second.n).buf.get();
       }
       dropout(out[0], (long)get_var_dims(var_of(am, "inout")).dims_prod(), ratio, seed);
-    } else if (fn == "hip_chan_affine") {
+    } else if (f.member == kOpChanAffine) {
       dims_t const &i4 = op.get_dims("in");
       if (i4.sz() != 4 || !(op.get_dims("out") == i4)) rt_err(fn + ": in and out must be img:chan:y:x tensors of equal dims");
       for (char const *an : {"a", "b"}) if (op.get_dims(an).sz() != 1 || op.get_dims(an).dims(0) != i4.dims(1)) rt_err(fn + ": " + an + " dims " + op.get_dims(an).pretty_str() + ": one float per channel of in " + i4.pretty_str());
       uint32_t const relu = op.get_u32("relu");
       if (relu > 1) rt_err(fn + ": relu must be 0 | 1");
       chan_affine(in[0], in[1], in[2], out[0], n_img, (long)i4.dsz("chan"), (long)i4.dsz("y") * i4.dsz("x"), relu != 0);
-    } else if (fn == "hip_concat" || fn == "hip_split") {
-      bool const cat = fn == "hip_concat";
+    } else if (f.member == kOpConcat || f.member == kOpSplit) {
+      bool const cat = f.member == kOpConcat;
       dims_t const &i4 = op.get_dims("in"), &o4 = op.get_dims("out");
       if (i4.sz() != 4 || o4.sz() != 4) rt_err(fn + ": in / out must be img:chan:y:x");
       dims_t const &nar = cat ? i4 : o4, &wid = cat ? o4 : i4;
@@ -708,15 +677,15 @@ struct cpu_compute_t : public rtc_compute_t {
       dims_t const &i4 = op.get_dims("in");
       if (i4.sz() != 4 || i4.dims(2) != 1 || i4.dims(3) != 1) unsup_err(fn + ": only 1 x 1 planes (in img:chan:1:1, label img:1:1): the reference reads label by image");
       long const C = i4.dsz("chan");
-      if (fn == "hip_softmax") softmax(in[0], out[0], n_img, C);
-      else if (fn == "hip_sm_grad_and_loss") sm_grad_and_loss(in[0], in[1], out[0], out[1], n_img, C);
+      if (f.member == kOpSoftmax) softmax(in[0], out[0], n_img, C);
+      else if (f.member == kOpSmGradAndLoss) sm_grad_and_loss(in[0], in[1], out[0], out[1], n_img, C);
       else sum_loss_over_imgs(in[0], out[0], n_img);
     }
   }
 
   // hip_sgd_update: the checks of be=hip (csrc/native_run.cc), then the loop per tensor with lr_i / wd_i formed once
   void run_sgd_update(op_base_t const &op, map_str_rtc_arg_t const &am) {
-    string const fn = "hip_sgd_update";
+    string const fn = op.get_func_name();
     sgd_op_t const so = sgd_op_of_op(op);
     std::map<string, string> seen;   // var -> the arg it is bound to
     auto var_ptr = [&](string const &an) -> float * {
@@ -767,16 +736,16 @@ struct cpu_compute_t : public rtc_compute_t {
     auto fit = funcs.find(rfc.rtc_func_name);
     if (fit == funcs.end()) rt_err("run: unknown function '" + rfc.rtc_func_name + "' (not compiled, or released)");
     rtc_func_info_t const &fi = fit->second.info;
-    string const &fn = fi.op.get_func_name();
+    native_func_t const &f = *fit->second.row;
     map_str_rtc_arg_t const &am = rfc.arg_map;
     (void)op_seed_var_flag(fi.op);   // (refuses the flag on a function that cannot take it)
     (void)op_img_shards_flag(fi.op);   // (likewise)
     double const tb = now_ms();
-    if (fn == "hip_sgd_update") run_sgd_update(fi.op, am);
-    else if (is_bn_func_name(fn)) run_bn(fi.op, am);
-    else if (bck_op_fn_t const *bd = find_bck_op(fn)) run_bck_op(*bd, fi.op, am);
-    else if (is_bck(fn)) run_bck(fn, fi.op, am);
-    else if (is_sgemm(fn)) {
+    if (f.family == kFamSgd) run_sgd_update(fi.op, am);
+    else if (f.family == kFamBn) run_bn(fi.op, am);
+    else if (f.family == kFamBckOp) run_bck_op(f, fi.op, am);
+    else if (f.family == kFamBconv) run_bck(f, fi.op, am);
+    else if (f.family == kFamSgemm) {
       string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");
       dims_t const a = get_var_dims(an), b = get_var_dims(bn), c = get_var_dims(cn);
       need_float(a, "a"); need_float(b, "b"); need_float(c, "c");

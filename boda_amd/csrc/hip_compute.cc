@@ -169,7 +169,7 @@ struct hip_func_t {
   std::shared_ptr<hipModule_t> mod; // one module per compile() call, shared by its functions
   struct gid_t { hipDeviceptr_t p = nullptr; uint32_t off = 0, last = 0xffffffffu; bool known = true; uint64_t epoch = 0; };   // known (and epoch == the backend's gid_epoch): off / last are what the device global holds NOW
   std::shared_ptr<gid_t> gid;       // shard-aware backends: the module's bodahip_gid global and the values last written to it
-  bool native = false;              // native side door (no module of its own: kernels are specialised at run())
+  native_func_t const *native = nullptr;   // native side door: the function's row of native_funcs.h (no module of its own: kernels are specialised at run())
 };
 struct ev_pair_t { hipEvent_t b = nullptr, e = nullptr; };
 
@@ -277,8 +277,8 @@ struct hip_compute_t : public rtc_compute_t, public native_host_t {
       if (funcs.count(fi.func_name)) rt_err("compile: function '" + fi.func_name + "' already exists");
       string const op_fn = fi.op.has_func_name() ? fi.op.get_func_name() : string();
       if (native_kernels_t::is_native_func_name(op_fn)) {
-        hip_func_t hf; hf.info = fi; hf.native = true;
-        native->check_compile_time(hf.info); // unknown native name / malformed op -> error now, not at run()
+        hip_func_t hf; hf.info = fi;
+        hf.native = native->check_compile_time(hf.info); // unknown native name / malformed op -> error now, not at run()
         funcs.emplace(fi.func_name, std::move(hf));
       } else { to_rtc.push_back(fi); }
     }
@@ -368,10 +368,10 @@ struct hip_compute_t : public rtc_compute_t, public native_host_t {
     hip_func_t &hf = fit->second;
     if (!hf.native && native) native->last_call_uses_ws = false;   // (a generated function has its arguments and nothing else)
     if (hf.native) {
-      if (capturing) { try { native->run(hf.info, rfc.arg_map); } catch (...) { graph_abort(); throw; } note_captured_call(); return kCapturedCallId; }
+      if (capturing) { try { native->run(*hf.native, hf.info, rfc.arg_map); } catch (...) { graph_abort(); throw; } note_captured_call(); return kCapturedCallId; }
       uint32_t const call_id = new_call_events();
       call_begin(call_id);
-      try { native->run(hf.info, rfc.arg_map); } catch (...) { cur_call = -1; throw; }
+      try { native->run(*hf.native, hf.info, rfc.arg_map); } catch (...) { cur_call = -1; throw; }
       call_end(call_id);
       return call_id;
     }

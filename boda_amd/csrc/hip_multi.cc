@@ -127,10 +127,10 @@ struct hip_multi_compute_t : public rtc_compute_t {
   std::vector<p_rtc_compute_t> subs;
   std::map<string, multi_var_t> vis;
   std::map<string, bool> func_native;
-  std::map<string, string> funcs_op_fn;      // function -> its op's func_name ("": none)
+  std::map<string, native_func_t const *> func_row;   // function -> its row of native_funcs.h (null: a generated function)
   std::map<string, string> func_img_sum;   // native functions that reduce over the images (BckConv filter / bias gradients, the softmax loss): refused on a sharded run, with this message
   std::map<string, gen_func_t> func_gen;       // generated functions: their index declaration
-  std::map<string, string> func_shards;    // native functions compiled with img_shards=1 (n() > 1): func name -> the op's function, run by run_on_img_shards
+  std::map<string, native_func_t const *> func_shards;    // native functions compiled with img_shards=1 (n() > 1): func name -> the op's function, run by run_on_img_shards
   std::vector<hipEvent_t> shard_in_evs;        // per device i > 0: recorded on stream i behind what a flagged call enqueued there; stream 0 waits for it before it gathers
   hipEvent_t shard_out_ev = nullptr;           // recorded on stream 0 behind a flagged call's fan-out; every other stream waits for it before it goes on
   float *shard_ws = nullptr; size_t shard_ws_bytes = 0;   // device 0: the slabs of the per-device partials (the gathered loss_per_pel).  Grow-only, reused by every flagged call
@@ -354,47 +354,32 @@ struct hip_multi_compute_t : public rtc_compute_t {
     for (auto const &fi : func_infos) {
       bool const nat = native_kernels_t::is_native_func_name(fi.op.has_func_name() ? fi.op.get_func_name() : string());
       func_native[fi.func_name] = nat;
-      funcs_op_fn[fi.func_name] = fi.op.has_func_name() ? fi.op.get_func_name() : string();
+      native_func_t const *row = nat ? find_native_func(fi.op.get_func_name()) : nullptr;   // (never null for a native function: the devices' own compile has refused an unknown name)
+      func_row[fi.func_name] = row;
       bool const shards = nat && op_img_shards_flag(fi.op);   // (on any other function the devices' own compile has refused the flag already)
-      if (shards && n() > 1) { func_shards[fi.func_name] = fi.op.get_func_name(); continue; }
-      // BckConv's filter / bias gradients sum over the images: on img shards every device would hold a partial sum, and no cross-device reduction exists here
-      if (nat && n() > 1 && (fi.op.get_func_name() == "hip_bconv_filts" || fi.op.get_func_name() == "hip_bconv_biases"))
-        func_img_sum[fi.func_name] = "(a BckConv filter / bias gradient) sums over the images, which would need a cross-device reduction; only the data gradient (hip_bconv_in) runs on img shards";
-      // the fused filter + bias gradient writes TWO sums over the images; summing two outputs over the shards is not provided (and img_shards=1 on it is an RtErr)
-      if (nat && n() > 1 && fi.op.get_func_name() == "hip_bconv_filts_biases")
-        func_img_sum[fi.func_name] = "(hip_bconv_filts_biases, a BckConv's fused filter and bias gradient) sums over the images into two outputs, which would need a cross-device reduction of both; on several devices use hip_bconv_filts and hip_bconv_biases with img_shards=1";
-      // the softmax loss: hip_sm_grad_and_loss divides by the GLOBAL image count and hip_sum_loss_over_imgs sums over all images; the gradient pipe's other six
-      // non-conv functions (hip_pool_yx, hip_lrn_sb, hip_spreading, hip_bck_lrn, hip_zero_if_non_pos, hip_softmax) are independent per image and run on img shards
-      if (nat && n() > 1 && fi.op.get_func_name() == "hip_sm_grad_and_loss") func_img_sum[fi.func_name] = "(the softmax loss gradient) divides by the GLOBAL image count, which an img shard does not know; hip_softmax runs on img shards";
-      if (nat && n() > 1 && fi.op.get_func_name() == "hip_sum_loss_over_imgs") func_img_sum[fi.func_name] = "(the softmax loss) sums loss_per_pel over ALL images, which would need a cross-device reduction; hip_softmax runs on img shards";
-      // hip_reduce / hip_concat / hip_split / hip_chan_affine are independent per image and run on img shards (a and b, one value per channel, are whole on every device); hip_dropout hashes the element's index in the WHOLE tensor
-      if (nat && n() > 1 && fi.op.get_func_name() == "hip_dropout") func_img_sum[fi.func_name] = "(dropout) hashes every element's GLOBAL flat index, which an img shard does not know; hip_reduce / hip_concat / hip_split run on img shards";
-      // the training BatchNorm: hip_bn_stats and hip_bn_bck_sums sum over img x y x x of the WHOLE batch, hip_bn_bck_in divides by that count.  hip_bn_fwd and
-      // hip_fan_out are independent per image, but their calls demand vars of exactly the op's dims (csrc/native_run.cc), which an img shard does not have: they are
-      // refused here by name, with a message of their own, not left to fail on dims
-      if (nat && n() > 1 && (fi.op.get_func_name() == "hip_bn_stats" || fi.op.get_func_name() == "hip_bn_bck_sums"))
-        func_img_sum[fi.func_name] = "(a training BatchNorm's per-channel sums) sums over the images of the WHOLE batch, which would need a cross-device reduction; statistics summed across img shards are out of scope";
-      if (nat && n() > 1 && fi.op.get_func_name() == "hip_bn_bck_in") func_img_sum[fi.func_name] = "(a training BatchNorm's data gradient) divides by the element count of the WHOLE batch, which an img shard does not know";
-      if (nat && n() > 1 && (fi.op.get_func_name() == "hip_bn_fwd" || fi.op.get_func_name() == "hip_fan_out"))
-        func_img_sum[fi.func_name] = "(" + fi.op.get_func_name() + ") takes vars of exactly its op's dims, not img shards: the training BatchNorm functions and the Eltwise gradient run on one device";
+      if (shards && n() > 1) { func_shards[fi.func_name] = row; continue; }
+      // what a call on img shards does is the row's multi-device policy (native_funcs.h), where every function has to state one.  A function that is not independent per
+      // image is refused with the row's sentence; one that sums over the images only without img_shards=1, which has taken the `continue` above
+      if (row && n() > 1 && (row->multi_dev.mode == multi_dev_t::needs_flag || row->multi_dev.mode == multi_dev_t::refused)) func_img_sum[fi.func_name] = row->multi_dev.why;
       if (!nat) func_gen[fi.func_name] = scan_gen_func(all_src, fi.func_name);
     }
   }
-  void release_func(string const &fn) override { must_find(func_native, fn); for (auto &s : subs) s->release_func(fn); func_native.erase(fn); funcs_op_fn.erase(fn); func_gen.erase(fn); func_img_sum.erase(fn); func_shards.erase(fn); }
-  void release_all_funcs() override { for (auto &s : subs) s->release_all_funcs(); func_native.clear(); funcs_op_fn.clear(); func_gen.clear(); func_img_sum.clear(); func_shards.clear(); }
+  void release_func(string const &fn) override { must_find(func_native, fn); for (auto &s : subs) s->release_func(fn); func_native.erase(fn); func_row.erase(fn); func_gen.erase(fn); func_img_sum.erase(fn); func_shards.erase(fn); }
+  void release_all_funcs() override { for (auto &s : subs) s->release_all_funcs(); func_native.clear(); func_row.clear(); func_gen.clear(); func_img_sum.clear(); func_shards.clear(); }
 
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
     auto fit = func_native.find(rfc.rtc_func_name);
     if (fit == func_native.end()) rt_err("run: unknown function '" + rfc.rtc_func_name + "' (not compiled, or released)");
     { auto is = func_img_sum.find(rfc.rtc_func_name); if (is != func_img_sum.end()) unsup_err("multi-device backend: '" + rfc.rtc_func_name + "' " + is->second); }
-    { auto sh = func_shards.find(rfc.rtc_func_name); if (sh != func_shards.end()) return run_on_img_shards(rfc, sh->second); }
+    { auto sh = func_shards.find(rfc.rtc_func_name); if (sh != func_shards.end()) return run_on_img_shards(rfc, *sh->second); }
     // hip_sgd_update: params, gradients and momentum history are REPLICATED vars, and an unflagged native call on replicated vars runs on every device (below).  The
     // replicas stay equal by construction: every device holds the same summed gradient after run_on_img_shards' fan-out, the same hyper, the same history, and runs the
     // same kernel -- no cross-device work of its own.  A sharded var (a leading img / M dim) would give every device another piece: refused
-    if (fit->second && must_find(funcs_op_fn, rfc.rtc_func_name) == "hip_sgd_update")
+    native_func_t const *row = fit->second ? must_find(func_row, rfc.rtc_func_name) : nullptr;
+    if (row && row->multi_dev.mode == multi_dev_t::replicated_only)
       for (auto const &kv : rfc.arg_map) if (kv.second.is_valid() && kv.second.is_var() && must_find(vis, kv.second.n).shard_dim >= 0)
-        rt_err("multi-device backend: hip_sgd_update: arg '" + kv.first + "' (var '" + kv.second.n + "' " + must_find(vis, kv.second.n).dims.pretty_str() + ") is sharded over the devices; the update runs on replicated vars only");
+        rt_err("multi-device backend: " + string(row->name) + ": arg '" + kv.first + "' (var '" + kv.second.n + "' " + must_find(vis, kv.second.n).dims.pretty_str() + ") is sharded over the devices; the update runs on replicated vars only");
     if (!fit->second) {
       bool sharded = false;
       for (auto const &kv : rfc.arg_map) if (kv.second.is_valid() && kv.second.is_var() && must_find(vis, kv.second.n).shard_dim >= 0) sharded = true;
@@ -464,18 +449,19 @@ struct hip_multi_compute_t : public rtc_compute_t {
     if (want_sharded ? (v.shard_dim != 0 || v.dims.names(0) != "img") : (v.shard_dim >= 0)) rt_err(fn + ": img_shards=1: arg '" + an + "' (var '" + vn + "' " + v.dims.pretty_str() + ") must be " + (want_sharded ? "sharded along its leading img dim" : "a replicated var"));
     return v;
   }
-  uint32_t run_on_img_shards(rtc_func_call_t const &rfc, string const &fn) {
+  uint32_t run_on_img_shards(rtc_func_call_t const &rfc, native_func_t const &row) {
+    string const fn = row.name;
     if (capturing) { capturing = false; for (auto &s : subs) hip_compute_graph_abort(s.get()); unsup_err("multi-device backend: '" + rfc.rtc_func_name + "' (" + fn + " with img_shards=1) cannot be captured into a graph: its cross-device work is not part of any one device's capture"); }
-    bool const sum = fn == "hip_bconv_filts" || fn == "hip_bconv_biases";
+    bool const sum = row.family == kFamBconv;   // (hip_bconv_filts / hip_bconv_biases; the other three are kFamBckOp members)
     string svn, rvn;
-    multi_var_t const &sv = shards_arg(rfc, fn, sum ? "out_grad_loss" : fn == "hip_dropout" ? "inout" : fn == "hip_sm_grad_and_loss" ? "prob" : "loss_per_pel", true, svn);
+    multi_var_t const &sv = shards_arg(rfc, fn, sum ? "out_grad_loss" : row.member == kOpDropout ? "inout" : row.member == kOpSmGradAndLoss ? "prob" : "loss_per_pel", true, svn);
     uint32_t const T = sv.dims.dims(0);
     std::vector<uint32_t> ids(n(), kNoCall);
     auto done = [&]() { calls.push_back(ids); return (uint32_t)calls.size() - 1; };
     if (!T) return done();   // (an empty batch: nothing to run anywhere)
     auto has_imgs = [&](size_t i) { return chunk_begin(T, i + 1) > chunk_begin(T, i); };
-    if (fn == "hip_dropout" || fn == "hip_sm_grad_and_loss") {
-      bool const drop = fn == "hip_dropout";
+    if (!sum && (row.member == kOpDropout || row.member == kOpSmGradAndLoss)) {
+      bool const drop = row.member == kOpDropout;
       uint32_t seed = 0;
       if (drop) {
         auto si = rfc.arg_map.find("det_drop_seed");
@@ -493,7 +479,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
       }
       return done();
     }
-    if (fn == "hip_sum_loss_over_imgs") {
+    if (!sum) {   // hip_sum_loss_over_imgs
       multi_var_t const &lv = shards_arg(rfc, fn, "loss", false, rvn);
       if (sv.dims.tn != "float" || lv.dims.tn != "float" || sv.dims.dims_prod() != T || lv.dims.dims_prod() != 1) rt_err(fn + ": img_shards=1: loss_per_pel must hold one float per image and loss one float");
       float *const ws = shards_ws((size_t)T * 4);
@@ -507,7 +493,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
       return done();
     }
     // the filter / bias gradient
-    multi_var_t const &gv = shards_arg(rfc, fn, fn == "hip_bconv_filts" ? "filts_grad_loss" : "biases_grad_loss", false, rvn);
+    multi_var_t const &gv = shards_arg(rfc, fn, row.member == kBconvFilts ? "filts_grad_loss" : "biases_grad_loss", false, rvn);
     if (gv.dims.tn != "float") rt_err(fn + ": img_shards=1: the gradient var must be float");
     uint64_t const elems = gv.dims.dims_prod(), stride = (elems + 3) & ~uint64_t(3);   // (slabs start on 16 bytes: the sum walks quads)
     size_t const bytes = (size_t)elems * 4;

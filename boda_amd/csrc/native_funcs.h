@@ -1,0 +1,172 @@
+// native_funcs.h -- the one table of the native side door: which function names exist, their family and member, the op types they belong to, their args in call order,
+// the op flags they take, which backends run them and what a multi-device backend does with them.  Host-only (nothing of HIP): be=cpu reads it too.  Every other file
+// asks this table; boda_amd/cnn_op.py keeps tables of its own (it imports no library) and tests/test_native_funcs_cpu.py holds them to this one.
+//
+// Row order: the order the refusal messages list the names in (rtc_types.h's flag messages, be=cpu's refusal).  A bare op's calls are its type's rows in ascending
+// member: the reference's call order (src/rtc_fwd.cc:384-386 for SoftmaxWithLoss's three, :398-400 for BckConv's in / biases / filts).
+#pragma once
+#include "rtc_types.h"
+
+namespace bodahip {
+
+// the family (func_family_t of rtc_types.h) selects the handler (native_run.cc, native_kernels.cc: check_compile_time); handlers switch on the member, never on the name
+inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn"};
+// members.  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn: the kind of bn_op_t
+enum { kConvF32 = 0, kConvAlias = 1, kConvBf16 = 2, kConvWinograd = 3 };            // (the alias: hip_conv's contract without its fused pooling and filts_km)
+enum { kBconvIn = 1, kBconvBiases = 2, kBconvFilts = 3, kBconvFiltsBiases = 4 };   // (4 is opt-in: never one of the bare op's three calls)
+enum { kOpPoolYx = 1, kOpSpreading = 2, kOpLrnSb = 3, kOpBckLrn = 4, kOpZeroIfNonPos = 5, kOpSoftmax = 6, kOpSmGradAndLoss = 7, kOpSumLossOverImgs = 8, kOpReduce = 9,
+       kOpDropout = 10, kOpConcat = 11, kOpSplit = 12, kOpChanAffine = 13 };
+
+enum arg_kind_t { kIn, kOut, kInOut, kRef, kVal };   // kVal: a by-value scalar of the CALL
+inline constexpr char const *kArgKindNames[] = {"IN", "OUT", "INOUT", "REF", "VAL"};
+struct func_arg_t { char const *name; arg_kind_t kind; };
+// the part of the arg list that depends on the op, as a rule: ins_0 .. ins_{ins_num-1} (IN, 2 to 8) in front of the last fixed arg | outs_0 .. outs_{outs_num-1} (OUT, 2 to 8)
+// behind the fixed args | w_i (INOUT) g_i (IN) h_i (INOUT), i < tens_num (1 to 32), in front of the fixed args | member lists, which their handlers describe
+enum var_args_t { kVarNone, kVarInsBeforeLast, kVarOutsBehind, kVarWghInFront, kVarMembers };
+// a flag that adds a var arg (IN): which flag, the arg, and where -- at >= 0: in front of fixed arg `at`; at < 0: in front of the last fixed arg.  flag 0: none
+struct flag_arg_t { unsigned flag; char const *name; int at; };
+enum : unsigned { kBeHip = 1, kBeCpu = 2 };
+
+// what a multi-device backend (hip_multi.cc) does with a call on vars sharded along img.  No default: a row that does not state it does not compile
+struct multi_dev_t {
+  enum mode_t { on_shards,         // independent per image: runs on every device's shard as it is
+                replicated_only,   // runs on every device, and refuses a sharded var
+                needs_flag,        // not independent per image: refused (`why`) unless the op carries img_shards=1
+                refused };         // refused (`why`) on several devices
+  mode_t mode; char const *why;
+  constexpr multi_dev_t(mode_t mode_, char const *why_) : mode(mode_), why(why_) {}
+};
+constexpr multi_dev_t kOnShards{multi_dev_t::on_shards, ""}, kReplicatedOnly{multi_dev_t::replicated_only, ""};
+constexpr multi_dev_t needs_img_shards_flag(char const *why) { return multi_dev_t(multi_dev_t::needs_flag, why); }
+constexpr multi_dev_t refused_on_devices(char const *why) { return multi_dev_t(multi_dev_t::refused, why); }
+
+struct native_func_t {
+  char const *name; func_family_t family; int member;
+  char const *kname;        // kFamBckOp: the kernel's name
+  char const *types[2];     // the op types it is a function of
+  func_arg_t args[9];       // the fixed args in call order (null name: end)
+  func_arg_t opt_arg;       // one more var arg a call may bind (null name: none)
+  var_args_t var;
+  unsigned flags;           // the op flags it takes (kFlag* of rtc_types.h)
+  flag_arg_t flag_arg;
+  unsigned backends;
+  multi_dev_t multi_dev;
+  bool of_type(string const &t) const { return t == types[0] || (types[1] && t == types[1]); }
+  // the vars of a call have the op's dims -- for a function that runs on img shards except the image count, which then only has to agree between the vars.  (All four
+  // BckConv gradients read the image count from their vars: the fused one, refused on several devices, has always done so on one)
+  bool img_count_free() const { return multi_dev.mode == multi_dev_t::on_shards || multi_dev.mode == multi_dev_t::needs_flag || family == kFamBconv; }
+};
+
+#define BODAHIP_CONV_ARGS {"filts", kIn}, {"biases", kIn}, {"in", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"out", kOut}
+inline constexpr char kWhyBconvSum[] = "(a BckConv filter / bias gradient) sums over the images, which would need a cross-device reduction; only the data gradient (hip_bconv_in) runs on img shards";
+inline constexpr char kWhyBnSums[] = "(a training BatchNorm's per-channel sums) sums over the images of the WHOLE batch, which would need a cross-device reduction; statistics summed across img shards are out of scope";
+inline constexpr native_func_t kNativeFuncs[] = {
+  // sgemm, a:K:M b:K:N c:M:N (test/rtc/cublas_sgemm.cucl:1-4); Convolution in reference layout (test/rtc/cudnn_conv.cucl:1-7)
+  {"hip_sgemm", kFamSgemm, 0, nullptr, {"sgemm"}, {{"a", kIn}, {"b", kIn}, {"c", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"cublas_sgemm", kFamSgemm, 0, nullptr, {"sgemm"}, {{"a", kIn}, {"b", kIn}, {"c", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"cpu_sgemm", kFamSgemm, 0, nullptr, {"sgemm"}, {{"a", kIn}, {"b", kIn}, {"c", kOut}}, {}, kVarNone, 0, {}, kBeCpu, kOnShards},
+  {"hip_sgemm_bf16", kFamSgemm, 1, nullptr, {"sgemm"}, {{"a", kIn}, {"b", kIn}, {"c", kOut}}, {}, kVarNone, 0, {}, kBeHip, kOnShards},
+  {"hip_conv", kFamConv, kConvF32, nullptr, {"Convolution"}, {BODAHIP_CONV_ARGS}, {"filts_km", kIn}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"cudnn_conv", kFamConv, kConvAlias, nullptr, {"Convolution"}, {BODAHIP_CONV_ARGS}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"cpu_conv_fwd", kFamConv, kConvF32, nullptr, {"Convolution"}, {BODAHIP_CONV_ARGS}, {}, kVarNone, 0, {}, kBeCpu, kOnShards},
+  {"hip_conv_bf16", kFamConv, kConvBf16, nullptr, {"Convolution"}, {BODAHIP_CONV_ARGS}, {}, kVarNone, 0, {}, kBeHip, kOnShards},
+  {"hip_conv_winograd", kFamConv, kConvWinograd, nullptr, {"Convolution"}, {BODAHIP_CONV_ARGS}, {}, kVarNone, 0, {}, kBeHip, kOnShards},
+  // channels-last bf16 tensors; the sibling group, the multi-problem launch and the level set take member lists
+  {"hip_conv_nhwc", kFamConvNhwc, 0, nullptr, {"Convolution"}, {BODAHIP_CONV_ARGS}, {}, kVarNone, kFlagNhwcResidual, {kFlagNhwcResidual, "res", -1}, kBeHip, kOnShards},
+  {"hip_conv_nhwc_grp", kFamNhwcGrp, 0, nullptr, {"Convolution"}, {}, {}, kVarMembers, 0, {}, kBeHip, kOnShards},
+  {"hip_conv_nhwc_multi", kFamNhwcMulti, 0, nullptr, {"Convolution"}, {}, {}, kVarMembers, 0, {}, kBeHip, kOnShards},
+  {"hip_conv_nhwc_set", kFamNhwcMulti, 1, nullptr, {"Convolution"}, {}, {}, kVarMembers, 0, {}, kBeHip, kOnShards},
+  {"hip_conv_k1_chain", kFamK1Chain, 0, nullptr, {"Convolution"}, {{"filts", kIn}, {"biases", kIn}, {"filts2", kIn}, {"biases2", kIn}, {"in", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip, kOnShards},
+  {"hip_conv_filts_kmajor", kFamFiltsKmajor, 0, nullptr, {"Convolution"}, {{"filts", kIn}, {"filts_km", kOut}}, {}, kVarNone, 0, {}, kBeHip, kOnShards},
+  // BckConv's gradients: the reference templates' arg lists (test/rtc/BckConv_in_grad_loss.cucl, BckConv_filts_grad_loss.cucl, BckConv_biases_grad_loss.cucl)
+  {"hip_bconv_in", kFamBconv, kBconvIn, nullptr, {"BckConv"}, {{"filts", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"in_grad_loss", kOut}}, {}, kVarNone, kFlagZinp, {kFlagZinp, "in", -1}, kBeHip | kBeCpu, kOnShards},
+  {"hip_bconv_filts", kFamBconv, kBconvFilts, nullptr, {"BckConv"}, {{"in", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"filts_grad_loss", kOut}}, {}, kVarNone, kFlagImgShards, {}, kBeHip | kBeCpu, needs_img_shards_flag(kWhyBconvSum)},
+  {"hip_bconv_biases", kFamBconv, kBconvBiases, nullptr, {"BckConv"}, {{"out_grad_loss", kIn}, {"biases_grad_loss", kOut}}, {}, kVarNone, kFlagImgShards, {}, kBeHip | kBeCpu, needs_img_shards_flag(kWhyBconvSum)},
+  {"hip_bconv_filts_biases", kFamBconv, kBconvFiltsBiases, nullptr, {"BckConv"}, {{"in", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"filts_grad_loss", kOut}, {"biases_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu,
+   refused_on_devices("(hip_bconv_filts_biases, a BckConv's fused filter and bias gradient) sums over the images into two outputs, which would need a cross-device reduction of both; on several devices use hip_bconv_filts and hip_bconv_biases with img_shards=1")},
+  // the non-conv ops of the gradient pipe (kernels/bck_ops_f32.hip), in their reference templates' arg order (test/rtc/pool.cucl, lrn.cucl, spreading.cucl, bck_lrn.cucl,
+  // ZeroIfNonPos.cucl, softmax.cucl, sm_grad_and_loss.cucl, sum_loss_over_imgs.cucl, reduce.cucl, dropout.cucl; the copy calls of src/rtc_fwd.cc:267-294); the templates'
+  // by-value scalars ride in the op.  hip_dropout rewrites inout in place (the reference declares it OUT); it is also the function of a BckDropout
+  {"hip_pool_yx", kFamBckOp, kOpPoolYx, "bodahip_pool_yx", {"Pooling"}, {{"in", kIn}, {"kern_sz", kRef}, {"stride", kRef}, {"in_pad", kRef}, {"out", kOut}, {"out_in_yx", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_lrn_sb", kFamBckOp, kOpLrnSb, "bodahip_lrn_sb", {"LRN"}, {{"in", kIn}, {"out", kOut}, {"out_scale_base", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_spreading", kFamBckOp, kOpSpreading, "bodahip_spreading", {"Spreading"}, {{"out", kIn}, {"out_grad_loss", kIn}, {"out_in_yx", kIn}, {"kern_sz", kRef}, {"stride", kRef}, {"in_pad", kRef}, {"in_grad_loss", kOut}}, {}, kVarNone, kFlagZinp, {kFlagZinp, "in", -1}, kBeHip | kBeCpu, kOnShards},
+  {"hip_bck_lrn", kFamBckOp, kOpBckLrn, "bodahip_bck_lrn", {"BckLRN"}, {{"in", kIn}, {"out", kIn}, {"out_grad_loss", kIn}, {"out_scale_base", kIn}, {"in_grad_loss", kOut}}, {}, kVarNone, kFlagZinp, {}, kBeHip | kBeCpu, kOnShards},   // (reads `in` already)
+  {"hip_zero_if_non_pos", kFamBckOp, kOpZeroIfNonPos, "bodahip_zero_if_non_pos", {"ZeroIfNonPos"}, {{"in", kIn}, {"cond", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_softmax", kFamBckOp, kOpSoftmax, "bodahip_softmax", {"SoftmaxWithLoss"}, {{"in", kIn}, {"prob", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_sm_grad_and_loss", kFamBckOp, kOpSmGradAndLoss, "bodahip_sm_grad_and_loss", {"SoftmaxWithLoss"}, {{"prob", kIn}, {"label", kIn}, {"in_grad_loss", kOut}, {"loss_per_pel", kOut}}, {}, kVarNone, kFlagImgShards, {}, kBeHip | kBeCpu,
+   needs_img_shards_flag("(the softmax loss gradient) divides by the GLOBAL image count, which an img shard does not know; hip_softmax runs on img shards")},
+  {"hip_sum_loss_over_imgs", kFamBckOp, kOpSumLossOverImgs, "bodahip_sum_loss_over_imgs", {"SoftmaxWithLoss"}, {{"loss_per_pel", kIn}, {"loss", kOut}}, {}, kVarNone, kFlagImgShards, {}, kBeHip | kBeCpu,
+   needs_img_shards_flag("(the softmax loss) sums loss_per_pel over ALL images, which would need a cross-device reduction; hip_softmax runs on img shards")},
+  {"hip_reduce", kFamBckOp, kOpReduce, "bodahip_reduce", {"Reduce"}, {{"out", kOut}}, {}, kVarInsBeforeLast, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_dropout", kFamBckOp, kOpDropout, "bodahip_dropout", {"Dropout", "BckDropout"}, {{"inout", kOut}, {"det_drop_seed", kVal}}, {}, kVarNone, kFlagSeedVar | kFlagImgShards, {kFlagSeedVar, "det_drop_seed_var", 1}, kBeHip | kBeCpu,
+   needs_img_shards_flag("(dropout) hashes every element's GLOBAL flat index, which an img shard does not know; hip_reduce / hip_concat / hip_split run on img shards")},
+  {"hip_concat", kFamBckOp, kOpConcat, "bodahip_concat", {"Concat"}, {{"in", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_split", kFamBckOp, kOpSplit, "bodahip_split", {"Split"}, {{"in", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_chan_affine", kFamBckOp, kOpChanAffine, "bodahip_chan_affine", {"ChanAffine"}, {{"in", kIn}, {"a", kIn}, {"b", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},   // (a and b, one value per channel, are whole on every device)
+  // the solver's update (this backend's own): params, gradients and momentum history are replicated vars
+  {"hip_sgd_update", kFamSgd, 0, nullptr, {"SgdUpdate"}, {{"hyper", kIn}}, {}, kVarWghInFront, 0, {}, kBeHip | kBeCpu, kReplicatedOnly},
+  // the training BatchNorm and the Eltwise-SUM gradient (this backend's own; kernels/bn_f32.hip).  hip_bn_fwd and hip_fan_out are independent per image, but their calls
+  // demand vars of exactly the op's dims, which an img shard does not have: refused with a message of their own, not left to fail on dims
+  {"hip_bn_stats", kFamBn, 1, nullptr, {"BnStats"}, {{"in", kIn}, {"mean", kOut}, {"inv_std", kOut}, {"run_mean", kInOut}, {"run_var", kInOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, refused_on_devices(kWhyBnSums)},
+  {"hip_bn_fwd", kFamBn, 2, nullptr, {"BnFwd"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"scale", kIn}, {"bias", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu,
+   refused_on_devices("(hip_bn_fwd) takes vars of exactly its op's dims, not img shards: the training BatchNorm functions and the Eltwise gradient run on one device")},
+  {"hip_bn_bck_sums", kFamBn, 3, nullptr, {"BnBckSums"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"out_grad_loss", kIn}, {"scale_grad_loss", kOut}, {"bias_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, refused_on_devices(kWhyBnSums)},
+  {"hip_bn_bck_in", kFamBn, 4, nullptr, {"BnBckIn"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"scale", kIn}, {"scale_grad_loss", kIn}, {"bias_grad_loss", kIn}, {"out_grad_loss", kIn}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu,
+   refused_on_devices("(a training BatchNorm's data gradient) divides by the element count of the WHOLE batch, which an img shard does not know")},
+  {"hip_fan_out", kFamBn, 5, nullptr, {"FanOut"}, {{"in", kIn}}, {}, kVarOutsBehind, 0, {}, kBeHip | kBeCpu,
+   refused_on_devices("(hip_fan_out) takes vars of exactly its op's dims, not img shards: the training BatchNorm functions and the Eltwise gradient run on one device")},
+};
+#undef BODAHIP_CONV_ARGS
+
+inline native_func_t const *find_native_func(string const &fn) { for (auto const &f : kNativeFuncs) if (fn == f.name) return &f; return nullptr; }
+inline native_func_t const *find_native_func(func_family_t family, int member) { for (auto const &f : kNativeFuncs) if (f.family == family && f.member == member) return &f; return nullptr; }
+// the functions of a bare op of type t, in call order (empty: no such op).  kBconvFiltsBiases is nobody's default call
+inline std::vector<native_func_t const *> native_funcs_of_type(string const &t, unsigned backend = kBeHip) {
+  std::vector<native_func_t const *> r;
+  for (auto const &f : kNativeFuncs) if (f.of_type(t) && (f.backends & backend) && !(f.family == kFamBconv && f.member == kBconvFiltsBiases)) r.push_back(&f);
+  std::stable_sort(r.begin(), r.end(), [](native_func_t const *a, native_func_t const *b) { return a->member < b->member; });
+  return r;
+}
+// "a, b and c" (last_sep " and ") or "a, b, c" (last_sep ", "): the rows `pick` accepts, in table order
+template <typename F> inline string native_func_names(F const &pick, char const *last_sep) {
+  std::vector<char const *> ns; for (auto const &f : kNativeFuncs) if (pick(f)) ns.push_back(f.name);
+  string r; for (size_t i = 0; i < ns.size(); ++i) r += string(i ? (i + 1 == ns.size() ? last_sep : ", ") : "") + ns[i];
+  return r;
+}
+inline bool native_func_takes_flag(string const &fn, unsigned flag) { native_func_t const *f = find_native_func(fn); return f && (f->flags & flag); }
+inline bool native_type_takes_flag(string const &t, unsigned flag) { for (auto const &f : kNativeFuncs) if ((f.flags & flag) && f.of_type(t)) return true; return false; }
+inline string native_funcs_taking_flag(unsigned flag) { return native_func_names([&](native_func_t const &f) { return (f.flags & flag) != 0; }, " and "); }
+inline int native_func_member(string const &fn, func_family_t family) { native_func_t const *f = find_native_func(fn); return (f && f->family == family) ? f->member : 0; }
+inline char const *native_func_type(func_family_t family, int member) { native_func_t const *f = find_native_func(family, member); return f ? f->types[0] : ""; }
+inline string native_family_names(func_family_t family) { return native_func_names([&](native_func_t const &f) { return f.family == family; }, ", "); }
+
+// the (arg, kind) list of an annotated function op: the fixed args with the variable part and the flag's arg applied (what boda_amd/cnn_op.py calls pipe_func_args)
+inline std::vector<func_arg_t> fixed_args(native_func_t const &f) { std::vector<func_arg_t> r; for (auto const &a : f.args) { if (!a.name) break; r.push_back(a); } return r; }
+typedef std::vector<std::pair<string, arg_kind_t>> vect_func_arg_t;
+inline vect_func_arg_t native_func_args(native_func_t const &f, op_base_t const &op) {
+  string const fn = f.name;
+  vect_func_arg_t r; for (func_arg_t const &a : fixed_args(f)) r.emplace_back(a.name, a.kind);
+  auto count = [&](char const *an, uint32_t lo, uint32_t hi, char const *what) {
+    uint32_t const n = op.get_u32(an);
+    if (n < lo || n > hi) unsup_err(fn + ": " + an + "=" + std::to_string(n) + ": " + std::to_string(lo) + " to " + std::to_string(hi) + " " + what);
+    return n; };
+  if (f.var == kVarMembers) unsup_err(fn + ": the arg list is a list of members, which the function's handler describes");
+  if (f.var == kVarInsBeforeLast) { uint32_t const n = count("ins_num", 2, 8, "inputs"); for (uint32_t i = 0; i < n; ++i) r.emplace(r.end() - 1, "ins_" + std::to_string(i), kIn); }   // the reference's flattened names of the multi arg `ins`
+  if (f.var == kVarOutsBehind) { uint32_t const n = count("outs_num", 2, kFanOutMax, "outputs"); for (uint32_t i = 0; i < n; ++i) r.emplace_back("outs_" + std::to_string(i), kOut); }
+  if (f.var == kVarWghInFront) {
+    uint32_t const n = count("tens_num", 1, kSgdUpdateMaxTens, "tensors"); vect_func_arg_t per;
+    for (uint32_t i = 0; i < n; ++i) { string const sx = "_" + std::to_string(i); per.emplace_back("w" + sx, kInOut); per.emplace_back("g" + sx, kIn); per.emplace_back("h" + sx, kInOut); }
+    r.insert(r.begin(), per.begin(), per.end());
+  }
+  if (f.flag_arg.flag && op_flag_set(op, f.flag_arg.flag)) r.emplace(f.flag_arg.at >= 0 ? r.begin() + f.flag_arg.at : r.end() - 1, f.flag_arg.name, kIn);
+  return r;
+}
+// the IN / OUT var args of a kFamBckOp function in call order, without the flag's arg (which its handler binds by name); refs: does it take kern_sz / stride / in_pad
+struct bck_op_args_t { std::vector<string> ins, outs; bool refs = false; };
+inline bck_op_args_t bck_op_args(native_func_t const &f, op_base_t const &op) {
+  bck_op_args_t r; native_func_t plain = f; plain.flag_arg = flag_arg_t{};
+  for (auto const &a : native_func_args(plain, op)) { if (a.second == kIn) r.ins.push_back(a.first); else if (a.second == kOut) r.outs.push_back(a.first); else if (a.second == kRef) r.refs = true; }
+  return r;
+}
+
+} // namespace bodahip

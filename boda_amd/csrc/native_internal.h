@@ -76,12 +76,7 @@ struct bck_ops_args_t { // must match kernels/bck_ops_f32.hip
   unsigned seed, thresh;
   int run, wide, off;
 };
-// a native function of the gradient pipe's non-conv ops: its kernel, and its var args in the function's arg order (hip_reduce: ins_0 .. ins_{ins_num-1}, see
-// bck_op_ins; hip_dropout also takes the by-value uint32 det_drop_seed and, with seed_from_var=1, the uint32 var det_drop_seed_var)
-struct bck_op_desc_t { char const *fn; int op; char const *kname; char const *type_a; std::vector<char const *> ins, outs; bool refs; };
-bck_op_desc_t const *find_bck_op(string const &fn);                 // null: not one of them
-std::vector<string> bck_op_ins(bck_op_desc_t const &d, op_base_t const &op);   // the input var args of d for this op
-std::vector<bck_op_desc_t const *> bck_ops_of_type(string const &t);   // the functions of a bare op, in the reference's call order (empty: not such an op)
+// (the functions of the gradient pipe's non-conv ops, their kernels and their args: the kFamBckOp rows of native_funcs.h)
 struct bck_plan_t { plan_t p; long threads = 0; uint32_t grid = 0, block = 256; int CB = 0; double algo_bytes = 0; };
 bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus);
 bck_plan_t plan_shard_sum(int nslabs, long stride, long n);   // OP 14 of the same file: no function of its own, the multi-device backend's sum of per-shard partials

@@ -35,41 +35,45 @@ uint32_t native_kernels_t::num_specialisations() const { return (uint32_t)impl->
 
 bool native_kernels_t::is_native_func_name(string const &fn) {
   if (fn.find("_xpose_") != string::npos) return false; // (layout passes are generated CUCL functions, as the reference's <func>_xpose_<arg>)
-  return fn == "hip_sgemm" || fn == "hip_conv" || fn == "cublas_sgemm" || fn == "cudnn_conv" || fn == "hip_sgd_update" || startswith(fn, "hip_");
+  native_func_t const *f = find_native_func(fn);
+  return (f && (f->backends & kBeHip)) || startswith(fn, "hip_");   // (any other hip_ name is an error of check_compile_time, not CUCL source)
 }
-void native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
+native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const &fi) {
   string const &fn = fi.op.get_func_name();
+  native_func_t const *f = find_native_func(fn);
+  if (!f || !(f->backends & kBeHip)) rt_err("unknown/unhandled native hip function: " + fn);
   (void)op_img_shards_flag(fi.op);   // (refuses the flag on every function but the five that are not independent per image)
-  if (fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "hip_sgemm_bf16") return;
+  if (f->family == kFamSgemm) return f;
   (void)op_nhwc_residual_flag(fi.op);   // (refuses the flag on every function but a plain hip_conv_nhwc)
-  if (fn == "hip_conv" || fn == "cudnn_conv" || fn == "hip_conv_bf16" || fn == "hip_conv_winograd" || fn == "hip_conv_nhwc" || fn == "hip_conv_nhwc_grp" || fn == "hip_conv_nhwc_multi" || fn == "hip_conv_nhwc_set") { (void)fi.op.get_u32("conv_has_relu"); return; } // required, as src/culibs-wrap.cc:198
-  if (fn == "hip_conv_k1_chain") { (void)fi.op.get_u32("conv_has_relu"); (void)fi.op.get_u32("conv_has_relu2"); return; }
-  if (fn == "hip_conv_filts_kmajor") return;
+  switch (f->family) {
+  case kFamConv: case kFamConvNhwc: case kFamNhwcGrp: case kFamNhwcMulti: (void)fi.op.get_u32("conv_has_relu"); return f; // required, as src/culibs-wrap.cc:198
+  case kFamK1Chain: (void)fi.op.get_u32("conv_has_relu"); (void)fi.op.get_u32("conv_has_relu2"); return f;
+  case kFamFiltsKmajor: return f;
+  default: break;
+  }
   (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
   (void)op_seed_var_flag(fi.op);   // (likewise)
-  if (fn == "hip_sgd_update") {   // the op must be whole; the code object is built NOW: a first run inside a graph capture (ConvPipeBck.capture_graph never runs the update eagerly) finds it
+  switch (f->family) {
+  case kFamSgd: {   // the op must be whole; the code object is built NOW: a first run inside a graph capture (ConvPipeBck.capture_graph never runs the update eagerly) finds it
     sgd_op_t const so = sgd_op_of_op(fi.op);
     (void)get_kernel(impl, host, plan_sgd_update(so.elems).p);
-    return;
-  }
-  if (is_bn_func_name(fn)) {   // the op must be whole; the code objects of all the call's launches are built NOW, so that a first run inside a graph capture finds them
+  } break;
+  case kFamBn:   // the op must be whole; the code objects of all the call's launches are built NOW, so that a first run inside a graph capture finds them
     for (bn_launch_t const &l : plan_bn(bn_op_of_op(fi.op)).ls) (void)get_kernel(impl, host, l.p);
-    return;
-  }
-  if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases" || fn == "hip_bconv_filts_biases") {   // BckConv's gradients: the op must carry the geometry
+    break;
+  case kFamBconv:   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
-    return;
-  }
-  if (bck_op_desc_t const *d = find_bck_op(fn)) {   // the gradient pipe's non-conv ops: the (annotated) op must carry every arg's dims
-    for (string const &an : bck_op_ins(*d, fi.op)) (void)fi.op.get_dims(an);
-    for (char const *an : d->outs) (void)fi.op.get_dims(an);
-    if (d->op == 10) (void)fi.op.get("dropout_ratio");
-    if (d->op == 11 || d->op == 12) (void)fi.op.get_u32(d->op == 11 ? "ocix" : "icix");
-    if (d->op == 13) (void)fi.op.get_u32("relu");
-    if (d->refs) for (char const *an : {"kern_sz", "stride", "in_pad"}) (void)fi.op.get_dims(an);
-    return;
-  }
-  rt_err("unknown/unhandled native hip function: " + fn);
+    break;
+  default: {   // kFamBckOp, the gradient pipe's non-conv ops: the (annotated) op must carry every arg's dims
+    bck_op_args_t const a = bck_op_args(*f, fi.op);
+    for (string const &an : a.ins) (void)fi.op.get_dims(an);
+    for (string const &an : a.outs) (void)fi.op.get_dims(an);
+    if (f->member == kOpDropout) (void)fi.op.get("dropout_ratio");
+    if (f->member == kOpConcat || f->member == kOpSplit) (void)fi.op.get_u32(f->member == kOpConcat ? "ocix" : "icix");
+    if (f->member == kOpChanAffine) (void)fi.op.get_u32("relu");
+    if (a.refs) for (char const *an : {"kern_sz", "stride", "in_pad"}) (void)fi.op.get_dims(an);
+  } }
+  return f;
 }
 void native_kernels_t::set_tune(string const &key, string const &val) {
   if (key != "sgemm_tile" && key != "conv_tile" && key != "k1_stream" && key != "conv_algo" && key != "exact") rt_err("set_tune: unknown key '" + key + "'");

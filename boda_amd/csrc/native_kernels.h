@@ -2,10 +2,11 @@
 //
 // Precedent in the reference: nvrtc_compute_t::run() routes functions whose op.func_name starts with cublas_ / cudnn_
 // to a vendor library (src/nvrtc_util.cc:369-372, src/culibs-wrap.cc:66-247) while every tensor stays in reference
-// layout (src/cnn_op.cc:47-48,142,339-340).  This backend does the same for
-//     hip_sgemm  (alias cublas_sgemm)   args a:K:M  b:K:N  c:M:N                      test/rtc/cublas_sgemm.cucl:1-4
-//     hip_conv   (alias cudnn_conv)     args filts biases in stride(REF) in_pad(REF) out   test/rtc/cudnn_conv.cucl:1-7
-//     hip_sgemm_bf16 / hip_conv_bf16    same contracts; bf16 operands (converted while staging), fp32 accumulate (config 5)
+// layout (src/cnn_op.cc:47-48,142,339-340).  This backend does the same for the functions of native_funcs.h: that table lists every name with its op types, its args in
+// call order, the op flags it takes, the backends that run it and what a multi-device backend does with it.  What the table cannot say:
+//     hip_sgemm / hip_conv (aliases cublas_sgemm / cudnn_conv) keep the contracts of test/rtc/cublas_sgemm.cucl:1-4 and cudnn_conv.cucl:1-7; hip_sgemm_bf16 / hip_conv_bf16
+//                                       take bf16 operands (converted while staging) and accumulate in fp32 (config 5); hip_conv_winograd runs 3x3 / stride-1 layers through
+//                                       F(2x2,3x3) Winograd (mrd <= ~2e-3)
 //     hip_conv_nhwc                     Convolution on channels-last bf16 tensors (filts out_chan:y:x:in_chan, in / out img:y:x:chan, type bfloat16;
 //                                       out may be float): the layout the bf16 matrix cores want -- reached through xpose functions like the
 //                                       reference's k1conv / tconv (src/rtc_prof.cc:92-121)
@@ -15,36 +16,19 @@
 //                                       small members handed to the hardware dispatcher together, longest first (kernels/conv_nhwc_multi_bf16.hip)
 //     hip_conv_nhwc_set                 up to 16 independent hip_conv_nhwc convolutions, each on ITS OWN specialised kernel code, as one launch: an inception module's
 //                                       3x3 / 5x5 / pool-projection convolutions (the kernel sources instantiated per member inside one wrapper kernel, built at run time)
-//     hip_bconv_in / _filts / _biases   BckConv's three gradients (fp32, NCHW / OIHW): args filts out_grad_loss stride(REF) in_pad(REF) in_grad_loss |
-//                                       in out_grad_loss stride(REF) in_pad(REF) filts_grad_loss | out_grad_loss biases_grad_loss  (test/rtc/BckConv_*.cucl)
-//     hip_bconv_filts_biases            the filter and bias gradients in one call (kernels/bconv_fb_f32.hip): args in out_grad_loss stride(REF) in_pad(REF)
-//                                       filts_grad_loss biases_grad_loss
-//     the non-conv ops of the gradient pipe (fp32, img:chan:y:x; kernels/bck_ops_f32.hip), each with its reference template's arg list -- the templates' by-value
-//     scalars (avg_pool, emit_*, alpha, beta, k, local_size) ride in the op:
-//       hip_pool_yx             in kern_sz(REF) stride(REF) in_pad(REF) out out_in_yx                              test/rtc/pool.cucl (max, emit_out_in_yx=1)
-//       hip_lrn_sb              in out out_scale_base                                                              test/rtc/lrn.cucl (emit_out_scale_base=1)
-//       hip_spreading           out out_grad_loss out_in_yx kern_sz(REF) stride(REF) in_pad(REF) in_grad_loss      test/rtc/spreading.cucl
-//       hip_bck_lrn             in out out_grad_loss out_scale_base in_grad_loss                                   test/rtc/bck_lrn.cucl
-//       hip_zero_if_non_pos     in cond out                                                                        test/rtc/ZeroIfNonPos.cucl
-//       hip_softmax             in prob                                                                            test/rtc/softmax.cucl
-//       hip_sm_grad_and_loss    prob label in_grad_loss loss_per_pel                                               test/rtc/sm_grad_and_loss.cucl
-//       hip_sum_loss_over_imgs  loss_per_pel loss                                                                  test/rtc/sum_loss_over_imgs.cucl
-//       hip_reduce              ins_0 .. ins_{ins_num-1} out                  (2 .. 8 inputs)                      test/rtc/reduce.cucl
-//       hip_dropout             inout det_drop_seed(by-value uint32)          (Dropout and BckDropout)             test/rtc/dropout.cucl
-//                               with seed_from_var=1 in the op: inout det_drop_seed_var(uint32_t var, one element) det_drop_seed -- the hash seed is word + by-value
-//                               the five functions that are not independent per image -- hip_bconv_filts / hip_bconv_biases, hip_sm_grad_and_loss, hip_sum_loss_over_imgs,
-//                               hip_dropout -- take img_shards=1 in the op (rtc_types.h): no new var args; what a multi-device backend then does is in hip_multi.cc.
-//                               hip_sm_grad_and_loss then reads an optional by-value uint32 img_total of the call: the divisor
-//       hip_concat / hip_split  in out   (ocix / icix in the op: one call per input / output)                      src/rtc_fwd.cc:267-294
-//       hip_chan_affine         in a b out   (relu in the op; in and out may be one var)   out = in * a[chan] + b[chan], two roundings: the forward pipe's BatchNorm / Scale runs
-//     hip_sgd_update                    op type SgdUpdate, this backend's own (the reference has no solver): w_0 g_0 h_0 .. w_{n-1} g_{n-1} h_{n-1} hyper, n = tens_num (1 .. 32) and the
-//                                       floats lr_mult_i / decay_mult_i in the op; w_i (param) and h_i (momentum history) read and written, g_i (gradient) and hyper (float v=4:
-//                                       lr, momentum, weight_decay, unused) read.  g1 = g + (wd * decay_mult_i) * w; h' = momentum * h + (lr * lr_mult_i) * g1; w' = w - h', every
+//     the non-conv ops of the gradient pipe (fp32, img:chan:y:x; kernels/bck_ops_f32.hip) take their reference templates' arg lists (test/rtc/pool.cucl with
+//                                       emit_out_in_yx=1, lrn.cucl with emit_out_scale_base=1, spreading.cucl, bck_lrn.cucl, ZeroIfNonPos.cucl, softmax.cucl, sm_grad_and_loss.cucl,
+//                                       sum_loss_over_imgs.cucl, reduce.cucl, dropout.cucl; hip_concat / hip_split: src/rtc_fwd.cc:267-294, one call per input / output, ocix / icix
+//                                       in the op); the templates' by-value scalars (avg_pool, emit_*, alpha, beta, k, local_size) ride in the op.  hip_dropout with seed_from_var=1:
+//                                       the hash seed is the word of det_drop_seed_var + the by-value det_drop_seed.  hip_sm_grad_and_loss with img_shards=1 reads an optional
+//                                       by-value uint32 img_total of the call: the divisor.  hip_chan_affine: out = in * a[chan] + b[chan], two roundings (relu in the op; in and
+//                                       out may be one var): the forward pipe's BatchNorm / Scale runs
+//     hip_sgd_update                    this backend's own (the reference has no solver): n = tens_num and the floats lr_mult_i / decay_mult_i in the op; hyper is float v=4: lr,
+//                                       momentum, weight_decay, unused.  g1 = g + (wd * decay_mult_i) * w; h' = momentum * h + (lr * lr_mult_i) * g1; w' = w - h', every
 //                                       operation one fp32 rounding.  One launch for all tensors (kernels/sgd_update_f32.hip); the code object is built when the function is compiled
-//     hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out    op types BnStats / BnFwd / BnBckSums / BnBckIn / FanOut, this backend's own: the training
-//                                       BatchNorm of the gradient pipe (batch statistics, running pair, normalise + scale + bias + ReLU, the two gradients) and the
-//                                       gradient of an Eltwise SUM.  kernels/bn_f32.hip states the arithmetic and the order of the per-channel sums
-//     hip_conv_winograd                 same contract as hip_conv; 3x3 / stride-1 layers through F(2x2,3x3) Winograd (mrd <= ~2e-3)
+//     hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out    this backend's own: the training BatchNorm of the gradient pipe (batch statistics, running
+//                                       pair, normalise + scale + bias + ReLU, the two gradients) and the gradient of an Eltwise SUM.  kernels/bn_f32.hip states the arithmetic and
+//                                       the order of the per-channel sums
 // and lands them on kernels/gemm_conv_f32.hip (and, for short-K 1x1 convs with a long pel axis, kernels/k1_stream_f32.hip),
 // specialised with hiprtc per shape class at first use.
 #pragma once
@@ -114,8 +98,8 @@ struct native_kernels_t {
   explicit native_kernels_t(native_host_t *host_);
   ~native_kernels_t();
   static bool is_native_func_name(string const &fn);
-  void check_compile_time(rtc_func_info_t const &fi);
-  void run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &arg_map);
+  native_func_t const *check_compile_time(rtc_func_info_t const &fi);   // -> the function's row of native_funcs.h: looked up once, kept with the compiled function
+  void run(native_func_t const &f, rtc_func_info_t const &fi, map_str_rtc_arg_t const &arg_map);
 
   // direct entry points on raw device pointers (used by run() and by the C ABI's fast paths)
   void sgemm(float const *a, float const *b, float *c, uint32_t M, uint32_t N, uint32_t K, bool bf16 = false, bool half = false);   // half: 2-byte IEEE half elements, fp32 math
@@ -170,6 +154,7 @@ struct native_kernels_t {
   bool last_call_uses_ws = false;   // the last run(): its plan works in the backend's one shared scratch (ensure_ws was called for it)
   uint32_t num_specialisations() const;
   struct impl_t;
+  struct call_t;   // one run(): the family handlers (native_run.cc)
 
  private:
   impl_t *impl;

@@ -1241,41 +1241,10 @@ plan_t plan_bconv_slab_sum() { plan_t p; p.bconv_fb = true; p.kname = "bodahip_b
 
 // ---- the non-conv ops of the gradient pipe (kernels/bck_ops_f32.hip).  Bandwidth kernels: no tile to choose, only the geometry to fold into the code (pooling
 // window / planes; LRN window and channel block) and the grid.
-static bck_op_desc_t const kBckOps[] = {
-  {"hip_pool_yx", 1, "bodahip_pool_yx", "Pooling", {"in"}, {"out", "out_in_yx"}, true},
-  {"hip_spreading", 2, "bodahip_spreading", "Spreading", {"out", "out_grad_loss", "out_in_yx"}, {"in_grad_loss"}, true},
-  {"hip_lrn_sb", 3, "bodahip_lrn_sb", "LRN", {"in"}, {"out", "out_scale_base"}, false},
-  {"hip_bck_lrn", 4, "bodahip_bck_lrn", "BckLRN", {"in", "out", "out_grad_loss", "out_scale_base"}, {"in_grad_loss"}, false},
-  {"hip_zero_if_non_pos", 5, "bodahip_zero_if_non_pos", "ZeroIfNonPos", {"in", "cond"}, {"out"}, false},
-  {"hip_softmax", 6, "bodahip_softmax", "SoftmaxWithLoss", {"in"}, {"prob"}, false},
-  {"hip_sm_grad_and_loss", 7, "bodahip_sm_grad_and_loss", "SoftmaxWithLoss", {"prob", "label"}, {"in_grad_loss", "loss_per_pel"}, false},
-  {"hip_sum_loss_over_imgs", 8, "bodahip_sum_loss_over_imgs", "SoftmaxWithLoss", {"loss_per_pel"}, {"loss"}, false},
-  {"hip_reduce", 9, "bodahip_reduce", "Reduce", {}, {"out"}, false},       // (its inputs: bck_op_ins)
-  {"hip_dropout", 10, "bodahip_dropout", "Dropout", {}, {"inout"}, false}, // (also the function of a BckDropout: the gradient of dropout is dropout)
-  {"hip_concat", 11, "bodahip_concat", "Concat", {"in"}, {"out"}, false},
-  {"hip_split", 12, "bodahip_split", "Split", {"in"}, {"out"}, false},
-  {"hip_chan_affine", 13, "bodahip_chan_affine", "ChanAffine", {"in", "a", "b"}, {"out"}, false},   // (the forward pipe's BatchNorm / Scale runs; `in` and `out` may be one var)
-};
-std::vector<string> bck_op_ins(bck_op_desc_t const &d, op_base_t const &op) {
-  std::vector<string> r(d.ins.begin(), d.ins.end());
-  if (d.op == 9) {   // the reference's flattened names of the multi arg `ins`
-    uint32_t const n = op.get_u32("ins_num");
-    if (n < 2 || n > 8) unsup_err("hip_reduce: ins_num=" + std::to_string(n) + ": 2 to 8 inputs");
-    for (uint32_t i = 0; i < n; ++i) r.push_back("ins_" + std::to_string(i));
-  }
-  return r;
-}
-bck_op_desc_t const *find_bck_op(string const &fn) { for (auto const &d : kBckOps) if (fn == d.fn) return &d; return nullptr; }
-std::vector<bck_op_desc_t const *> bck_ops_of_type(string const &t) {
-  std::vector<bck_op_desc_t const *> r;
-  for (auto const &d : kBckOps) if (t == d.type_a || (d.op == 10 && t == "BckDropout")) r.push_back(&d);   // (the table lists SoftmaxWithLoss's three calls in the order of src/rtc_fwd.cc:384-386)
-  return r;
-}
 bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
-  bck_op_desc_t const *d = nullptr;
-  for (auto const &e : kBckOps) if (e.op == g.op) d = &e;
+  native_func_t const *d = find_native_func(kFamBckOp, g.op);
   if (!d) rt_err("plan_bck_op: unknown op " + std::to_string(g.op));
-  string const what = d->fn;
+  string const what = d->name;
   bck_plan_t r; r.p.bck_ops = true; r.p.kname = d->kname; r.p.defs = {"-DOP=" + std::to_string(g.op)};
   auto D = [&](char const *n, long v) { r.p.defs.push_back(string("-D") + n + "=" + std::to_string(v)); };
   auto lim = [&](double elems) { if (4.0 * elems >= 2147483648.0) unsup_err(what + ": tensors of 2 GiB or more (32-bit element offsets)"); };

@@ -56,30 +56,30 @@ static float op_f32(op_base_t const &op, string const &an) {
 static void need_nchw(dims_t const &d, string const &what) {
   if (!(d.sz() == 4 && d.names(0) == "img" && d.names(1) == "chan" && d.names(2) == "y" && d.names(3) == "x")) rt_err(what + " must be img:chan:y:x, got " + d.pretty_str());
 }
-static bck_op_geom_t bck_op_geom_of_op(op_base_t const &op, bck_op_desc_t const &d) {
-  string const &t = op.get_type(); string const fn = d.fn;
-  if (t != d.type_a && !(d.op == 10 && t == "BckDropout")) rt_err(fn + ": a function of op type " + d.type_a + ", not " + t);
-  bck_op_geom_t g; g.op = d.op;
-  if (d.op == 1 || d.op == 2) {
+static bck_op_geom_t bck_op_geom_of_op(op_base_t const &op, native_func_t const &f) {
+  string const &t = op.get_type(); string const fn = f.name;
+  if (!f.of_type(t)) rt_err(fn + ": a function of op type " + f.types[0] + ", not " + t);
+  bck_op_geom_t g; g.op = f.member;
+  if (g.op == 1 || g.op == 2) {
     dims_t const &in = op.get_dims("in"), &out = op.get_dims("out"), &ks = op.get_dims("kern_sz"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
     need_nchw(in, fn + ": in"); need_nchw(out, fn + ": out");
     if (out.dims(0) != in.dims(0) || out.dims(1) != in.dims(1)) rt_err(fn + ": out img / chan differ from in");
     g.B = in.dims(0); g.C = (int)in.dims(1); g.H = (int)in.dims(2); g.W = (int)in.dims(3); g.OH = (int)out.dims(2); g.OW = (int)out.dims(3);
     g.KH = (int)ks.dsz("y"); g.KW = (int)ks.dsz("x"); g.SY = (int)st.dsz("y"); g.SX = (int)st.dsz("x"); g.PY = (int)pad.dsz("y"); g.PX = (int)pad.dsz("x");
     g.avg = op.get_u32("avg_pool") ? 1 : 0;
-    if (d.op == 1 && !op.get_u32("emit_out_in_yx") && !g.avg) unsup_err(fn + ": a Pooling with emit_out_in_yx=0 belongs to the forward pipe; hip_pool_yx is the pooling that also writes out_in_yx");
-  } else if (d.op == 3 || d.op == 4) {
+    if (g.op == 1 && !op.get_u32("emit_out_in_yx") && !g.avg) unsup_err(fn + ": a Pooling with emit_out_in_yx=0 belongs to the forward pipe; hip_pool_yx is the pooling that also writes out_in_yx");
+  } else if (g.op == 3 || g.op == 4) {
     dims_t const &in = op.get_dims("in"); need_nchw(in, fn + ": in");
     g.B = in.dims(0); g.C = (int)in.dims(1); g.H = (int)in.dims(2); g.W = (int)in.dims(3);
     g.LS = (int)op.get_u32("local_size"); g.alpha = op_f32(op, "alpha"); g.beta = op_f32(op, "beta"); g.k = op_f32(op, "k");
-    if (d.op == 3 && !op.get_u32("emit_out_scale_base")) unsup_err(fn + ": an LRN with emit_out_scale_base=0 belongs to the forward pipe; hip_lrn_sb is the LRN that also writes out_scale_base");
-  } else if (d.op == 5) {
+    if (g.op == 3 && !op.get_u32("emit_out_scale_base")) unsup_err(fn + ": an LRN with emit_out_scale_base=0 belongs to the forward pipe; hip_lrn_sb is the LRN that also writes out_scale_base");
+  } else if (g.op == 5) {
     g.n = (long)op.get_dims("in").dims_prod();
-  } else if (d.op == 9) {
+  } else if (g.op == 9) {
     dims_t const &out = op.get_dims("out");
     g.nin = (int)op.get_u32("ins_num"); g.n = (long)out.dims_prod();
-    for (string const &an : bck_op_ins(d, op)) if (!(op.get_dims(an) == out)) rt_err(fn + ": " + an + " dims " + op.get_dims(an).pretty_str() + " differ from out's " + out.pretty_str());
-  } else if (d.op == 13) {
+    for (string const &an : bck_op_args(f, op).ins) if (!(op.get_dims(an) == out)) rt_err(fn + ": " + an + " dims " + op.get_dims(an).pretty_str() + " differ from out's " + out.pretty_str());
+  } else if (g.op == 13) {
     dims_t const &in = op.get_dims("in"), &out = op.get_dims("out"); need_nchw(in, fn + ": in");
     if (!(out == in)) rt_err(fn + ": out dims " + out.pretty_str() + " differ from in's " + in.pretty_str());
     for (char const *an : {"a", "b"}) {
@@ -88,13 +88,13 @@ static bck_op_geom_t bck_op_geom_of_op(op_base_t const &op, bck_op_desc_t const 
     }
     g.B = in.dims(0); g.C = (int)in.dims(1); g.H = (int)in.dims(2); g.W = (int)in.dims(3); g.relu = (int)op.get_u32("relu");
     if (g.relu != 0 && g.relu != 1) rt_err(fn + ": relu must be 0 | 1");
-  } else if (d.op == 10) {
+  } else if (g.op == 10) {
     g.ratio = op_f32(op, "dropout_ratio"); g.n = (long)op.get_dims(op.has("inout") ? "inout" : "in").dims_prod();   // (the bare op carries in / out, its function the in-place arg inout)
-  } else if (d.op == 11 || d.op == 12) {
+  } else if (g.op == 11 || g.op == 12) {
     dims_t const &in = op.get_dims("in"), &out = op.get_dims("out"); need_nchw(in, fn + ": in"); need_nchw(out, fn + ": out");
-    dims_t const &nar = (d.op == 11) ? in : out, &wid = (d.op == 11) ? out : in;
+    dims_t const &nar = (g.op == 11) ? in : out, &wid = (g.op == 11) ? out : in;
     if (nar.dims(0) != wid.dims(0) || nar.dims(2) != wid.dims(2) || nar.dims(3) != wid.dims(3)) rt_err(fn + ": in " + in.pretty_str() + " and out " + out.pretty_str() + " differ in img / y / x");
-    g.B = nar.dims(0); g.C = (int)nar.dims(1); g.H = (int)nar.dims(2); g.W = (int)nar.dims(3); g.CT = (int)wid.dims(1); g.cix = (int)op.get_u32((d.op == 11) ? "ocix" : "icix");
+    g.B = nar.dims(0); g.C = (int)nar.dims(1); g.H = (int)nar.dims(2); g.W = (int)nar.dims(3); g.CT = (int)wid.dims(1); g.cix = (int)op.get_u32((g.op == 11) ? "ocix" : "icix");
   } else {
     dims_t const &in = op.get_dims("in"), &lab = op.get_dims("label"); need_nchw(in, fn + ": in");
     if (in.dims(2) != 1 || in.dims(3) != 1 || lab.sz() != 3 || lab.names(0) != "img" || lab.dims(1) != 1 || lab.dims(2) != 1 || lab.dims(0) != in.dims(0))
@@ -119,8 +119,15 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
   (void)op_seed_var_flag(op);   // (likewise)
   (void)op_img_shards_flag(op);   // (likewise.  A flagged function plans as the unflagged one: the flag adds no define)
   bool const nhwc_res = op_nhwc_residual_flag(op);   // (likewise: a plain hip_conv_nhwc only)
-  bool const bf16 = op.has_func_name() && (op.get_func_name() == "hip_sgemm_bf16" || op.get_func_name() == "hip_conv_bf16");
-  if (t == "sgemm") {
+  // the family: the function's row (native_funcs.h) where the op names one of its type's functions, else -- a bare op -- the family of the type's functions
+  native_func_t const *f = op.has_func_name() ? find_native_func(op.get_func_name()) : nullptr;
+  if (f && !f->of_type(t)) f = nullptr;
+  std::vector<native_func_t const *> const of_t = native_funcs_of_type(t);
+  if (!f && of_t.empty()) rt_err("prebuild: op type '" + t + "' has no native kernel");
+  func_family_t const fam = f ? f->family : of_t[0]->family;
+  int const member = f ? f->member : 0;   // (0: the bare op, or the family's plain form)
+  bool const bf16 = (fam == kFamSgemm && member == 1) || (fam == kFamConv && member == kConvBf16);
+  if (fam == kFamSgemm) {
     dims_t const &a = op.get_dims("a"), &b = op.get_dims("b");
     string const wide = (!bf16 && tile.empty() && a.tn != "half") ? sgemm_wide_tile(a.dsz("M"), b.dsz("N"), a.dsz("K"), num_cus) : string();
     sgemm_split_t sp; if (!bf16 && tile.empty() && a.tn != "half" && wide.empty()) sp = plan_sgemm_split(a.dsz("M"), b.dsz("N"), a.dsz("K"), num_cus);
@@ -143,10 +150,10 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     } else p = plan_sgemm(a.dsz("M"), b.dsz("N"), a.dsz("K"), num_cus, tile, bf16);
     if (a.tn == "half") { s2d.clear(); p = plan_sgemm(a.dsz("M"), b.dsz("N"), a.dsz("K"), num_cus, tile, false, 1, false); p.kname = "bodahip_sgemm_f16s"; p.defs.push_back("-DHALF=1"); }
   }
-  else if (t == "Convolution") {
+  else if (fam <= kFamFiltsKmajor) {   // op type Convolution
     bool const relu = op.has("conv_has_relu") ? (op.get_u32("conv_has_relu") != 0) : true;
-    bool const multi = op.has_func_name() && op.get_func_name() == "hip_conv_nhwc_multi";
-    if (op.has_func_name() && op.get_func_name() == "hip_conv_nhwc_set") {   // the wrapper kernel of the members' specialisations (and the kernels of members that stay alone)
+    bool const multi = fam == kFamNhwcMulti && member == 0;
+    if (fam == kFamNhwcMulti && member == 1) {   // the wrapper kernel of the members' specialisations (and the kernels of members that stay alone)
       int const n = (int)op.get_dims("multi").dsz("n"); bool const out_f32 = op.get_dims(op.has("out_0") ? "out_0" : "out_0_0").tn == "float";
       std::vector<plan_t> plans; std::vector<double> costs; size_t bytes = 0; string desc;
       for (int m = 0; m < n; ++m) { string const sfx = "_" + std::to_string(m);
@@ -181,7 +188,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
         gs.push_back(geom_from_dims(op.get_dims("filts" + sfx), op.get_dims("in" + sfx), op.get_dims("out" + sfx), op.get_dims("stride" + sfx), op.get_dims("in_pad" + sfx), relu)); }
       p = plan_conv_nhwc_multi(gs, tile, op.get_dims("out_0").tn == "float");
     }
-    else if (op.has_func_name() && op.get_func_name() == "hip_conv_nhwc" && op.get_dims("filts").sz() == 5) {
+    else if (fam == kFamConvNhwc && op.get_dims("filts").sz() == 5) {
       if (nhwc_res) unsup_err(string("hip_conv_nhwc: nhwc_residual=1 with ") + ((op.has("nhwc_pool") && op.get_u32("nhwc_pool")) ? "a max pooling fused in front (POOL): that form runs on the input-patch kernel, which has no residual epilogue" :
                               "the in_grp:y:x:out_chan:in_chan8 form of filts: the input-patch and rolling-rows kernels have no residual epilogue"));
       conv_geom_t gp = g; bool pool = false;
@@ -196,17 +203,17 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
       else if (!pool && op.get_dims("out").tn != "float" && rows_auto(gp, num_cus, tile)) plan_conv_nhwc_rows(gp, post_ops_t(), num_cus, p);
       else p = plan_conv_nhwc_patch(gp, num_cus, tile, op.get_dims("out").tn == "float", pool);
     }
-    else if (op.has_func_name() && op.get_func_name() == "hip_conv_k1_chain") {
+    else if (fam == kFamK1Chain) {
       if (!plan_k1_chain(g, (int)op.get_dims("filts2").dsz("out_chan"), op.get_u32("conv_has_relu2") != 0, p)) unsup_err("prebuild: hip_conv_k1_chain does not cover this pair of convolutions");
     }
-    else if (op.has_func_name() && op.get_func_name() == "hip_conv_nhwc") {
+    else if (fam == kFamConvNhwc) {
       if (nhwc_res) {   // res: exactly out's dims and element type; the sum is defined on whole tensors
         if (!op.has("res")) rt_err("hip_conv_nhwc: nhwc_residual=1 without the arg 'res'");
         if (!(op.get_dims("res") == op.get_dims("out")) || op.get_dims("res").tn != op.get_dims("out").tn) rt_err("hip_conv_nhwc: nhwc_residual=1: res dims " + op.get_dims("res").pretty_str() + " (" + op.get_dims("res").tn + ") differ from out's " + op.get_dims("out").pretty_str() + " (" + op.get_dims("out").tn + ")");
       }
       p = plan_conv_nhwc(g, num_cus, tile, op.get_dims("out").tn == "float", 0, true, nhwc_res);
     }
-    else if (op.has_func_name() && op.get_func_name() == "hip_conv_nhwc_grp") { dims_t const &grp = op.get_dims("grp"); p = plan_conv_nhwc(g, num_cus, tile, op.get_dims("out_0").tn == "float", (int)grp.dims(grp.sz() - 1)); }
+    else if (fam == kFamNhwcGrp) { dims_t const &grp = op.get_dims("grp"); p = plan_conv_nhwc(g, num_cus, tile, op.get_dims("out_0").tn == "float", (int)grp.dims(grp.sz() - 1)); }
     else if (bf16 && tile.empty() && s2d_geom(g, g2, pry, prx) && plan_patch_bf16(g2, num_cus, p)) { // conv1-type layers: space-to-depth front end (see conv())
       s2d = "s2d(" + std::to_string(g2.C) + "x" + std::to_string(g2.H) + "x" + std::to_string(g2.W) + ",k" + std::to_string(g2.KH) + "x" + std::to_string(g2.KW) + ")+";
       if (!arch.empty()) { plan_t sp; sp.patch16 = true; sp.bf16 = true; sp.kname = "bodahip_s2d"; sp.defs = {"-DS2D_ONLY=1"}; compile_plan(sp, arch, &log); }
@@ -223,15 +230,15 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
         p = plan_sgemm((uint32_t)g.OC, (uint32_t)(std::min<long>(Bc, g.B) * tpi), (uint32_t)g.C, num_cus, string(), false, 16);
       } else { char const *k1e = getenv("BODAHIP_K1_STREAM"); p = plan_conv(g, num_cus, tile, bf16, k1e ? string(k1e) : string(), true, exact); }   // (the env var a backend instance reads its k1_stream tune from)
     }
-  } else if (t == "BckConv") {   // the three gradient functions (or, for the bare op, all three: the calls of src/rtc_fwd.cc:398-400)
+  } else if (fam == kFamBconv) {   // the three gradient functions (or, for the bare op, all three: the calls of src/rtc_fwd.cc:398-400)
     conv_geom_t const g = bck_geom_of_op(op);
     string const fn = op.has_func_name() ? op.get_func_name() : string();
-    if (!fn.empty() && fn != "hip_bconv_in" && fn != "hip_bconv_filts" && fn != "hip_bconv_biases" && fn != "hip_bconv_filts_biases") rt_err("prebuild: BckConv function '" + fn + "' has no native kernel");
+    if (!fn.empty() && !f) rt_err("prebuild: BckConv function '" + fn + "' has no native kernel");
     std::vector<plan_t> ps;
-    if (fn.empty() || fn == "hip_bconv_in") ps.push_back(plan_bconv_in(g, num_cus, tile, op_zinp_flag(op)));
-    if (fn.empty() || fn == "hip_bconv_biases") ps.push_back(plan_bconv_biases());
-    if (fn.empty() || fn == "hip_bconv_filts") ps.push_back(plan_bconv_filts(g, num_cus, tile));
-    if (fn == "hip_bconv_filts_biases") {   // (opt-in: never part of the bare op's three calls) the main kernel and, with K slices, the slab sum behind it
+    if (!member || member == kBconvIn) ps.push_back(plan_bconv_in(g, num_cus, tile, op_zinp_flag(op)));
+    if (!member || member == kBconvBiases) ps.push_back(plan_bconv_biases());
+    if (!member || member == kBconvFilts) ps.push_back(plan_bconv_filts(g, num_cus, tile));
+    if (member == kBconvFiltsBiases) {   // (opt-in: never part of the bare op's three calls) the main kernel and, with K slices, the slab sum behind it
       ps.push_back(plan_bconv_filts_biases(g, num_cus, tile));
       if (ps.back().cfg.SPLITK > 1) ps.push_back(plan_bconv_slab_sum());
     }
@@ -249,27 +256,23 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     }
     if (plan_out) *plan_out = desc;
     return bytes;
-  } else if (t == "SgdUpdate") {   // (hip_sgd_update: one kernel, no specialisation by shape; the grid is the sum of the tensors' chunks)
+  } else if (fam == kFamSgd) {   // (hip_sgd_update: one kernel, no specialisation by shape; the grid is the sum of the tensors' chunks)
     sgd_plan_t const sp = plan_sgd_update(sgd_op_of_op(op).elems);
     if (plan_out) *plan_out = sp.p.kname + " grid=" + std::to_string(sp.grid) + " block=" + std::to_string(sp.block) + " tens=" + std::to_string(sp.blk0.size()) + " chunk=" + std::to_string(kSgdChunk);
     return arch.empty() ? 0 : compile_plan(sp.p, arch, &log).size();
-  } else if (t == "BnStats" || t == "BnFwd" || t == "BnBckSums" || t == "BnBckIn" || t == "FanOut") {   // (kernels/bn_f32.hip: every launch of the call, and the slab plan)
+  } else if (fam == kFamBn) {   // (kernels/bn_f32.hip: every launch of the call, and the slab plan)
     bn_op_t const b = bn_op_of_op(op);
     bn_plan_t const bp = plan_bn(b);
     if (plan_out) *plan_out = bn_plan_desc(b, bp);
     size_t bytes = 0;
     if (!arch.empty()) for (bn_launch_t const &l : bp.ls) bytes += compile_plan(l.p, arch, &log).size();
     return bytes;
-  } else if (!bck_ops_of_type(t).empty()) {   // a non-conv op of the gradient pipe: its annotated function, or (the bare op) all its functions in call order
-    std::vector<bck_op_desc_t const *> ds;
-    if (op.has_func_name()) {
-      bck_op_desc_t const *d = find_bck_op(op.get_func_name());
-      if (!d) rt_err("prebuild: " + t + " function '" + op.get_func_name() + "' has no native kernel");
-      ds.push_back(d);
-    } else ds = bck_ops_of_type(t);
+  } else {   // kFamBckOp, a non-conv op of the gradient pipe: its annotated function, or (the bare op) all its functions in call order
+    if (op.has_func_name() && !f) rt_err("prebuild: " + t + " function '" + op.get_func_name() + "' has no native kernel");
+    std::vector<native_func_t const *> const ds = f ? std::vector<native_func_t const *>{f} : of_t;
     string desc; size_t bytes = 0;
     if (!op.has_func_name() && (t == "Concat" || t == "Split")) unsup_err("prebuild: a bare " + t + " is one call per " + (t == "Concat" ? "input" : "output") + ": annotate it (cnn_op.add_pipe_op_annotations) and pass the function ops");
-    for (bck_op_desc_t const *d : ds) {
+    for (native_func_t const *d : ds) {
       bck_op_geom_t bg = bck_op_geom_of_op(op, *d); bg.zinp = op_zinp_flag(op) ? 1 : 0; bg.seedvar = op_seed_var_flag(op) ? 1 : 0;
       bck_plan_t const bp = plan_bck_op(bg, num_cus);
       desc += (desc.empty() ? "" : " | ") + bck_plan_desc(bp);
@@ -277,7 +280,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     }
     if (plan_out) *plan_out = desc;
     return bytes;
-  } else rt_err("prebuild: op type '" + t + "' has no native kernel");
+  }
   if (plan_out) { *plan_out = s2d + p.kname + " " + p.cfg.str(); for (auto const &d : p.defs) *plan_out += " " + d;
     if (p.split_pels > 0) *plan_out += " pels<" + std::to_string(p.split_pels) + "+rest:" + p.tail_cfg.str(); }
   if (arch.empty()) return 0;
@@ -337,16 +340,29 @@ struct exact_override_t {
   ~exact_override_t() { if (!active) return; if (had) impl->tune["exact"] = old; else impl->tune.erase("exact"); }
 };
 
-void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &am) {
-  string const &fn = fi.op.get_func_name();
-  impl->ws_used = false;   // set by ensure_ws: does this call's plan work in the shared scratch?  (what graph_end_deps' launch-order rule is about)
-  struct ws_note_t { native_kernels_t *nk; impl_t *im; ~ws_note_t() { nk->last_call_uses_ws = im->ws_used; } } const ws_note{this, impl};
-  exact_override_t const xov(impl, fi.op);
-  bool const zinp = op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
-  bool const seedvar = op_seed_var_flag(fi.op);   // (likewise)
-  bool const img_shards = op_img_shards_flag(fi.op);   // (likewise)
-  bool const bf16 = (fn == "hip_sgemm_bf16" || fn == "hip_conv_bf16");
-  if (fn == "hip_sgemm" || fn == "cublas_sgemm" || fn == "hip_sgemm_bf16") {
+// one run(): what every family's handler reads, the check of a var against the op's dims, and the handlers.  They switch on the row's member, never on the name
+struct native_kernels_t::call_t {
+  native_kernels_t &nk; impl_t *impl; native_host_t *host;
+  native_func_t const &row; rtc_func_info_t const &fi; map_str_rtc_arg_t const &am; string const &fn;
+  bool zinp, seedvar, img_shards;
+  long n_img = -1;   // of the call's img-leading vars, where the function leaves the image count free
+  // the var bound to arg `an`, which must be float (fp32_only: the words of a function's own refusal) and have the dims the op gives the arg -- except, for a function that
+  // runs on img shards (csrc/hip_multi.cc), the number of images, which only has to agree between the call's vars
+  string var_of_op_dims(string const &an, char const *fp32_only = nullptr) {
+    string const vn = var_of(am, an); dims_t const vd = host->nh_var_dims(vn);
+    if (!fp32_only) need_float(vd, an.c_str());
+    else if (vd.tn != "float") rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ": " + fp32_only);
+    dims_t want = fi.op.get_dims(an);
+    if (row.img_count_free() && want.sz() >= 1 && want.names(0) == "img" && vd.sz() == want.sz()) {
+      if (n_img < 0) n_img = vd.dims(0);
+      if ((long)vd.dims(0) != n_img) rt_err(fn + ": arg '" + an + "' has " + std::to_string(vd.dims(0)) + " images, another arg " + std::to_string(n_img));
+      want[0].sz = vd.dims(0); want.calc_strides();
+    }
+    if (!(vd == want)) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + fi.op.get_dims(an).pretty_str());
+    return vn;
+  }
+  void run_sgemm() {
+    bool const bf16 = row.member == 1;
     string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");
     dims_t const a = host->nh_var_dims(an), b = host->nh_var_dims(bn), c = host->nh_var_dims(cn);
     // storage type: float, or all three `half` (16-bit storage, fp32 math: the reference's sgemm with __tn__=half dims, test/sgemm-ops-debug-half.txt)
@@ -358,10 +374,9 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     assert_st(a.names(0) == "K" && a.names(1) == "M" && b.names(0) == "K" && b.names(1) == "N" && c.names(0) == "M" && c.names(1) == "N");
     assert_st(b.dsz("K") == K); assert_st(c.dsz("M") == M); assert_st(c.dsz("N") == N);
     tile_override_t const tov(impl, "sgemm_tile", fi.op);
-    sgemm((float const *)host->nh_var_ptr(an), (float const *)host->nh_var_ptr(bn), (float *)host->nh_var_ptr(cn), M, N, K, bf16, half);
-    return;
+    nk.sgemm((float const *)host->nh_var_ptr(an), (float const *)host->nh_var_ptr(bn), (float *)host->nh_var_ptr(cn), M, N, K, bf16, half);
   }
-  if (fn == "hip_conv_nhwc_grp") {
+  void run_nhwc_grp() {
     // horizontally fused channels-last convolutions: filts / biases stacked and padded (REF `grp`: dims m0..m{n-1} = the members' out_chans, pad = padding granularity),
     // outputs out_0 .. out_{n-1} (vars), optional by-value out_chan_off_<m> (member m writes a channel slice of a wider tensor)
     string const fnm = var_of(am, "filts"), bnm = var_of(am, "biases"), inm = var_of(am, "in");
@@ -396,11 +411,10 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     if (!g.SY || !g.SX) rt_err("hip_conv_nhwc_grp: zero stride");
     if ((g.H + 2 * g.PY - g.KH) / g.SY + 1 != g.OH || (g.W + 2 * g.PX - g.KW) / g.SX + 1 != g.OW || out0.dsz("img") != (uint32_t)g.B) rt_err("hip_conv_nhwc_grp: out dims do not match in/filts/stride/in_pad");
     tile_override_t const tov(impl, "conv_tile", fi.op);
-    conv_nhwc_grp(host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), host->nh_var_ptr(inm), g, out_f32, n, noc, outs, ctot, coff, (int)grp.dims(n));
-    return;
+    nk.conv_nhwc_grp(host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), host->nh_var_ptr(inm), g, out_f32, n, noc, outs, ctot, coff, (int)grp.dims(n));
   }
-  if (fn == "hip_conv_nhwc_multi" || fn == "hip_conv_nhwc_set") {
-    bool const is_set = (fn == "hip_conv_nhwc_set");   // (a set's members keep their own specialised kernels -- implicit-GEMM or input-patch form, by the dims of their filts)
+  void run_nhwc_multi() {
+    bool const is_set = row.member == 1;   // (a set's members keep their own specialised kernels -- implicit-GEMM or input-patch form, by the dims of their filts)
     // n independent channels-last convolutions (REF `multi`: dims n = the member count), member m: vars filts_<m> (out_chan:y:x:in_chan) biases_<m> in_<m> out_<m>,
     // REFs stride_<m> in_pad_<m>, optional by-value out_chan_off_<m>; ReLU: conv_has_relu for all, or bit m of the optional uint32 relu_mask
     auto mi = am.find("multi");
@@ -482,14 +496,13 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     if (is_set) {
       std::vector<char> pf(patch_f); bool pfb[16]; if (n > 16) unsup_err("hip_conv_nhwc_set: 1..16 members");
       for (int m = 0; m < n; ++m) pfb[m] = pf[(size_t)m] != 0;
-      conv_nhwc_set(n, ms.data(), pfb, out_tn == "float");
+      nk.conv_nhwc_set(n, ms.data(), pfb, out_tn == "float");
       return;
     }
     tile_override_t const tov(impl, "conv_tile", fi.op);
-    conv_nhwc_multi(n, ms.data(), out_tn == "float");
-    return;
+    nk.conv_nhwc_multi(n, ms.data(), out_tn == "float");
   }
-  if (fn == "hip_conv_nhwc") {
+  void run_conv_nhwc() {
     // channels-last bf16 tensors: filts out_chan:y:x:in_chan, in / out img:y:x:chan (out bf16 or float), biases float
     string const fnm = var_of(am, "filts"), bnm = var_of(am, "biases"), inm = var_of(am, "in"), onm = var_of(am, "out");
     dims_t f = host->nh_var_dims(fnm); dims_t const bi = host->nh_var_dims(bnm), in = host->nh_var_dims(inm), out = host->nh_var_dims(onm);
@@ -539,14 +552,13 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     }
     if (has_post) {
       if ((int)out.dsz("y") != post.POH || (int)out.dsz("x") != post.POW) rt_err("hip_conv_nhwc: out dims do not match the fused pooling");
-      conv_nhwc_rows(host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), host->nh_var_ptr(inm), host->nh_var_ptr(onm), g, post, out_ctot, out_coff);
+      nk.conv_nhwc_rows(host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), host->nh_var_ptr(inm), host->nh_var_ptr(onm), g, post, out_ctot, out_coff);
       return;
     }
     tile_override_t const tov(impl, "conv_tile", fi.op);
-    conv_nhwc(host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), host->nh_var_ptr(inm), host->nh_var_ptr(onm), g, out.tn == "float", out_ctot, out_coff, patch_filts, pool, res);
-    return;
+    nk.conv_nhwc(host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), host->nh_var_ptr(inm), host->nh_var_ptr(onm), g, out.tn == "float", out_ctot, out_coff, patch_filts, pool, res);
   }
-  if (fn == "hip_conv_k1_chain") {
+  void run_k1_chain() {
     // two chained 1x1 convolutions (see conv_k1_chain): vars filts / biases (first conv), filts2 / biases2 (second), in, out, optionally mid (the first conv's output,
     // written as well); REFs stride / in_pad (of both: 1x1 / stride 1 / no padding); uint32 conv_has_relu / conv_has_relu2; optional by-value out_chan_off
     string const fnm = var_of(am, "filts"), bnm = var_of(am, "biases"), f2nm = var_of(am, "filts2"), b2nm = var_of(am, "biases2"), inm = var_of(am, "in"), onm = var_of(am, "out");
@@ -578,11 +590,11 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
       if (md.sz() != 4 || md.dsz("img") != (uint32_t)g.B || md.dsz("chan") != (uint32_t)g.OC || md.dsz("y") != (uint32_t)g.OH || md.dsz("x") != (uint32_t)g.OW) rt_err("hip_conv_k1_chain: mid must be img:chan:y:x of the first convolution's output");
       mid = (float *)host->nh_var_ptr(mnm);
     }
-    conv_k1_chain((float const *)host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), (float const *)host->nh_var_ptr(f2nm), (float const *)host->nh_var_ptr(b2nm),
+    nk.conv_k1_chain((float const *)host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), (float const *)host->nh_var_ptr(f2nm), (float const *)host->nh_var_ptr(b2nm),
                   (float const *)host->nh_var_ptr(inm), (float *)host->nh_var_ptr(onm), mid, g, oc2, relu2, out_ctot, out_coff);
-    return;
   }
-  if (fn == "hip_conv" || fn == "cudnn_conv" || fn == "hip_conv_bf16" || fn == "hip_conv_winograd") {
+  void run_conv() {
+    bool const bf16 = row.member == kConvBf16;
     string const fnm = var_of(am, "filts"), bnm = var_of(am, "biases"), inm = var_of(am, "in"), onm = var_of(am, "out");
     dims_t const f = host->nh_var_dims(fnm), bi = host->nh_var_dims(bnm), in = host->nh_var_dims(inm), out = host->nh_var_dims(onm);
     need_float(f, "filts"); need_float(bi, "biases"); need_float(in, "in"); need_float(out, "out");
@@ -593,7 +605,7 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     assert_st(f.sz() == 4 && in.sz() == 4 && out.sz() == 4 && bi.sz() == 1);
     conv_geom_t g = geom_from_dims(f, in, out, stride, in_pad, fi.op.get_u32("conv_has_relu") != 0);
     if (f.dsz("in_chan") != (uint32_t)g.C) rt_err("hip_conv: filts.in_chan != in.chan");
-    if (apply_f32_pool(fi.op, g, "hip_conv") && (fn != "hip_conv" || bf16)) unsup_err("fused pooling (hip_pool): the fp32 hip_conv function only");
+    if (apply_f32_pool(fi.op, g, "hip_conv") && row.member != kConvF32) unsup_err("fused pooling (hip_pool): the fp32 hip_conv function only");
     // optional by-value arg out_chan_off: `out` is then a wider tensor (an inception module's Concat output) and this conv writes
     // channels [out_chan_off, out_chan_off + out_chan) of it -- the channel-offset copy of src/rtc_fwd.cc:267-280 folded into the store
     int out_ctot = 0, out_coff = 0;
@@ -611,7 +623,7 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     // reads its filters k-major (the staging-wave kernel) then skips the transposition it would run in front of every call; every other plan ignores it
     float const *km = nullptr;
     auto ki = am.find("filts_km");
-    if (ki != am.end() && fn == "hip_conv") {
+    if (ki != am.end() && row.member == kConvF32) {
       if (!ki->second.is_var()) rt_err("hip_conv: filts_km must be a var");
       dims_t const kd = host->nh_var_dims(ki->second.n); need_float(kd, "filts_km");
       long const Ktot = (long)g.C * g.KH * g.KW, mi4 = ((long)g.OC + 3) / 4 * 4;
@@ -619,72 +631,54 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
       km = (float const *)host->nh_var_ptr(ki->second.n);
     }
     tile_override_t const tov(impl, "conv_tile", fi.op);
-    conv((float const *)host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), (float const *)host->nh_var_ptr(inm), (float *)host->nh_var_ptr(onm), g, bf16, out_ctot, out_coff,
-         (fn == "hip_conv_winograd") ? "winograd_all" : nullptr, km); // hip_conv_winograd: the F(2x2,3x3) path for this function (3x3 / stride 1; others: direct)
-    return;
+    nk.conv((float const *)host->nh_var_ptr(fnm), (float const *)host->nh_var_ptr(bnm), (float const *)host->nh_var_ptr(inm), (float *)host->nh_var_ptr(onm), g, bf16, out_ctot, out_coff,
+         (row.member == kConvWinograd) ? "winograd_all" : nullptr, km); // hip_conv_winograd: the F(2x2,3x3) path for this function (3x3 / stride 1; others: direct)
   }
-  if (fn == "hip_bconv_in" || fn == "hip_bconv_filts" || fn == "hip_bconv_biases" || fn == "hip_bconv_filts_biases") {
-    // every var must have the dims the op gives its arg -- except the number of images, which only has to agree between the vars (a multi-device backend
-    // runs the data gradient on img shards: csrc/hip_multi.cc)
+  void run_bconv() {
     conv_geom_t g = bck_geom_of_op(fi.op);
-    long n_img = -1;
-    auto var_dims = [&](char const *an) {
-      string const vn = var_of(am, an); dims_t const d = host->nh_var_dims(vn); need_float(d, an);
-      dims_t want = fi.op.get_dims(an);
-      if (want.sz() == 4 && want.names(0) == "img" && d.sz() == 4) {
-        if (n_img < 0) n_img = d.dims(0);
-        if ((long)d.dims(0) != n_img) rt_err(fn + ": arg '" + an + "' has " + std::to_string(d.dims(0)) + " images, another arg " + std::to_string(n_img));
-        want[0].sz = d.dims(0);
-      }
-      if (!(d == want)) rt_err(fn + ": arg '" + an + "' has dims " + d.pretty_str() + ", the op says " + fi.op.get_dims(an).pretty_str());
-      return vn;
-    };
-    if (fn != "hip_bconv_biases") {
+    if (row.member != kBconvBiases) {
       auto si = am.find("stride"), pi = am.find("in_pad");
       if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
       dims_t const stride = si->second.get_dims(host->nh_rtc()), in_pad = pi->second.get_dims(host->nh_rtc());
       if (!(stride == fi.op.get_dims("stride")) || !(in_pad == fi.op.get_dims("in_pad"))) rt_err(fn + ": stride / in_pad args disagree with the op");
     }
-    string const ogl = var_dims("out_grad_loss");
+    string const ogl = var_of_op_dims("out_grad_loss");
     g.B = (int)n_img;
     tile_override_t const tov(impl, "conv_tile", fi.op);
-    if (fn == "hip_bconv_in") {
-      string const f = var_dims("filts"), igl = var_dims("in_grad_loss");
+    if (row.member == kBconvIn) {
+      string const f = var_of_op_dims("filts"), igl = var_of_op_dims("in_grad_loss");
       if (!(fi.op.get_dims("in_grad_loss") == fi.op.get_dims("in"))) rt_err(fn + ": in_grad_loss must have the dims of in");
       float const *zin = nullptr;
       if (zinp) {   // the forward input: the op's in dims (the image count the other vars'), and not the var this call writes
-        string const in = var_dims("in");
+        string const in = var_of_op_dims("in");
         if (in == igl) rt_err(fn + ": zero_if_in_non_pos=1: 'in' and 'in_grad_loss' are the same var '" + in + "'");
         zin = (float const *)host->nh_var_ptr(in);
       }
-      bconv_in((float const *)host->nh_var_ptr(f), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(igl), g, zin);
-    } else if (fn == "hip_bconv_filts") {
-      string const in = var_dims("in"), fgl = var_dims("filts_grad_loss");
+      nk.bconv_in((float const *)host->nh_var_ptr(f), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(igl), g, zin);
+    } else if (row.member == kBconvFilts) {
+      string const in = var_of_op_dims("in"), fgl = var_of_op_dims("filts_grad_loss");
       if (!(fi.op.get_dims("filts_grad_loss") == fi.op.get_dims("filts"))) rt_err(fn + ": filts_grad_loss must have the dims of filts");
-      bconv_filts((float const *)host->nh_var_ptr(in), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(fgl), g);
-    } else if (fn == "hip_bconv_filts_biases") {
-      string const in = var_dims("in"), fgl = var_dims("filts_grad_loss"), bgl = var_dims("biases_grad_loss");
+      nk.bconv_filts((float const *)host->nh_var_ptr(in), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(fgl), g);
+    } else if (row.member == kBconvFiltsBiases) {
+      string const in = var_of_op_dims("in"), fgl = var_of_op_dims("filts_grad_loss"), bgl = var_of_op_dims("biases_grad_loss");
       if (!(fi.op.get_dims("filts_grad_loss") == fi.op.get_dims("filts"))) rt_err(fn + ": filts_grad_loss must have the dims of filts");
       if (fi.op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
       for (string const *o : {&fgl, &bgl}) if (*o == in || *o == ogl) rt_err(fn + ": the output var '" + *o + "' is also an input of the call");
       if (fgl == bgl) rt_err(fn + ": filts_grad_loss and biases_grad_loss are the same var '" + fgl + "'");
-      bconv_filts_biases((float const *)host->nh_var_ptr(in), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(fgl), (float *)host->nh_var_ptr(bgl), g);
+      nk.bconv_filts_biases((float const *)host->nh_var_ptr(in), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(fgl), (float *)host->nh_var_ptr(bgl), g);
     } else {
-      string const bgl = var_dims("biases_grad_loss");
+      string const bgl = var_of_op_dims("biases_grad_loss");
       if (fi.op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
-      bconv_biases((float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(bgl), g);
+      nk.bconv_biases((float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(bgl), g);
     }
-    return;
   }
-  if (fn == "hip_sgd_update") {
+  void run_sgd() {
     // every var must have exactly the dims the op gives its arg (params are no img shards), and the 3n + 1 vars must all be different: w_i and h_i are rewritten in place
     sgd_op_t const so = sgd_op_of_op(fi.op);
     int const n = (int)so.elems.size();
     std::map<string, string> seen;   // var -> the arg it is bound to
     auto var_ptr = [&](string const &an) -> void * {
-      string const vn = var_of(am, an); dims_t const vd = host->nh_var_dims(vn);
-      if (vd.tn != "float") rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ": the update is fp32 only");
-      if (!(vd == fi.op.get_dims(an))) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + fi.op.get_dims(an).pretty_str());
+      string const vn = var_of_op_dims(an, "the update is fp32 only");
       auto ins = seen.emplace(vn, an);
       if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
       return host->nh_var_ptr(vn);
@@ -697,18 +691,15 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
       m.n = so.elems[(size_t)i]; m.lr_mult = so.lr_mult[(size_t)i]; m.decay_mult = so.decay_mult[(size_t)i];
     }
     float const *hyper = (float const *)var_ptr("hyper");
-    sgd_update(n, ms.data(), hyper);
-    return;
+    nk.sgd_update(n, ms.data(), hyper);
   }
-  if (is_bn_func_name(fn)) {
+  void run_bn() {
     // every var must have exactly the dims the op gives its arg (the sums run over the whole batch: no img shards), and no two args may be one var except where
     // kernels/bn_f32.hip allows in-place use
     bn_op_t const b = bn_op_of_op(fi.op);
     vect_string vars; std::vector<float *> tens, chans;
     auto var_ptr = [&](string const &an) -> float * {
-      string const vn = var_of(am, an); dims_t const vd = host->nh_var_dims(vn);
-      if (vd.tn != "float") rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ": fp32 only");
-      if (!(vd == fi.op.get_dims(an))) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + fi.op.get_dims(an).pretty_str());
+      string const vn = var_of_op_dims(an, "fp32 only");
       vars.push_back(vn);
       return (float *)host->nh_var_ptr(vn);
     };
@@ -716,34 +707,22 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     for (string const &an : b.chans) chans.push_back(var_ptr(an));
     bn_check_aliases(fn, b, vars);
     while (chans.size() < 5) chans.push_back(nullptr);
-    bn_call(b, tens.data(), chans.data());
-    return;
+    nk.bn_call(b, tens.data(), chans.data());
   }
-  if (bck_op_desc_t const *d = find_bck_op(fn)) {
+  void run_bck_op() {
     // every var must have the dims the op gives its arg -- except the number of images, which only has to agree between the vars (a multi-device backend runs these
     // functions on img shards: csrc/hip_multi.cc); the REF args must be the op's
-    bck_op_geom_t g = bck_op_geom_of_op(fi.op, *d);
-    long n_img = -1;
-    auto var_ptr = [&](char const *an) -> void * {
-      string const vn = var_of(am, an); dims_t const vd = host->nh_var_dims(vn); need_float(vd, an);
-      dims_t want = fi.op.get_dims(an);
-      if (want.sz() >= 1 && want.names(0) == "img" && vd.sz() == want.sz()) {
-        if (n_img < 0) n_img = vd.dims(0);
-        if ((long)vd.dims(0) != n_img) rt_err(fn + ": arg '" + an + "' has " + std::to_string(vd.dims(0)) + " images, another arg " + std::to_string(n_img));
-        want[0].sz = vd.dims(0); want.calc_strides();
-      }
-      if (!(vd == want)) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + fi.op.get_dims(an).pretty_str());
-      return host->nh_var_ptr(vn);
-    };
-    if (d->refs) for (char const *an : {"kern_sz", "stride", "in_pad"}) {
+    bck_op_geom_t g = bck_op_geom_of_op(fi.op, row);
+    bck_op_args_t const a = bck_op_args(row, fi.op);
+    auto var_ptr = [&](string const &an) { return host->nh_var_ptr(var_of_op_dims(an)); };
+    if (a.refs) for (char const *an : {"kern_sz", "stride", "in_pad"}) {
       auto ri = am.find(an);
       if (ri == am.end()) rt_err(fn + ": the REF arg '" + an + "' is required");
       if (!(ri->second.get_dims(host->nh_rtc()) == fi.op.get_dims(an))) rt_err(fn + ": arg '" + an + "' disagrees with the op");
     }
     float const *ins[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float *outs[2] = {nullptr, nullptr};
-    std::vector<string> const in_ans = bck_op_ins(*d, fi.op);
-    for (size_t i = 0; i < in_ans.size(); ++i) ins[i] = (float const *)var_ptr(in_ans[i].c_str());
-    for (size_t i = 0; i < d->outs.size(); ++i) outs[i] = (float *)var_ptr(d->outs[i]);
+    for (size_t i = 0; i < a.ins.size(); ++i) ins[i] = (float const *)var_ptr(a.ins[i]);
+    for (size_t i = 0; i < a.outs.size(); ++i) outs[i] = (float *)var_ptr(a.outs[i]);
     if (zinp) {   // the condition is the forward input `in`: hip_bck_lrn's first arg; hip_spreading takes it as a fourth input.  Never the var the call writes
       if (g.op == 2) ins[3] = (float const *)var_ptr("in");
       if (var_of(am, "in") == var_of(am, "in_grad_loss")) rt_err(fn + ": zero_if_in_non_pos=1: 'in' and 'in_grad_loss' are the same var '" + var_of(am, "in") + "'");
@@ -763,7 +742,7 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
       seed_word = (uint32_t const *)host->nh_var_ptr(wi->second.n); g.seedvar = 1;
     }
     if (g.op == 5) g.n = (long)host->nh_var_dims(var_of(am, "in")).dims_prod();
-    else if (g.op == 9 || g.op == 10) g.n = (long)host->nh_var_dims(var_of(am, d->outs[0])).dims_prod();
+    else if (g.op == 9 || g.op == 10) g.n = (long)host->nh_var_dims(var_of(am, a.outs[0])).dims_prod();
     else if (n_img >= 0) g.B = n_img;
     if (g.op == 7 && img_shards) {   // an img shard of a batch: the divisor is the WHOLE batch's image count, which a multi-device backend adds to the call by value
       auto ti = am.find("img_total");
@@ -773,10 +752,9 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
         if (g.img_total < g.B) rt_err(fn + ": img_shards=1: img_total=" + std::to_string(g.img_total) + " is less than the " + std::to_string(g.B) + " images of this shard");
       }
     }
-    bck_op(g, ins, outs, seed_word);
-    return;
+    nk.bck_op(g, ins, outs, seed_word);
   }
-  if (fn == "hip_conv_filts_kmajor") {   // filts (out_chan:in_chan:y:x) -> filts_km ([K + 128][out_chan padded to 4], zeros in the padding): see filts_km above
+  void run_filts_kmajor() {   // filts (out_chan:in_chan:y:x) -> filts_km ([K + 128][out_chan padded to 4], zeros in the padding): see filts_km above
     string const fnm = var_of(am, "filts"), knm = var_of(am, "filts_km");
     dims_t const f = host->nh_var_dims(fnm), kd = host->nh_var_dims(knm);
     need_float(f, "filts"); need_float(kd, "filts_km"); assert_st(f.sz() == 4);
@@ -788,10 +766,32 @@ void native_kernels_t::run(rtc_func_info_t const &fi, map_str_rtc_arg_t const &a
     float const *src = (float const *)host->nh_var_ptr(fnm); float *dst = (float *)host->nh_var_ptr(knm); int Mi = (int)OC, Mi4 = (int)mi4, Kk = (int)Ktot, Kp = (int)kp;
     void *xparams[] = {&src, &dst, &Mi, &Mi4, &Kk, &Kp};
     hip_err_chk(host->nh_launch(xk.func, (uint32_t)((kp + 31) / 32), (uint32_t)((mi4 + 31) / 32), 256, xparams), "hipModuleLaunchKernel(conv_big_xpose)");
-    last_launch.kernel = "bodahip_conv_big_xpose"; last_launch.grid = (uint32_t)(((kp + 31) / 32) * ((mi4 + 31) / 32)); last_launch.block = 256; last_launch.flops = 0; last_launch.algo_bytes = 8.0 * OC * Ktot;
-    return;
+    nk.last_launch.kernel = "bodahip_conv_big_xpose"; nk.last_launch.grid = (uint32_t)(((kp + 31) / 32) * ((mi4 + 31) / 32)); nk.last_launch.block = 256; nk.last_launch.flops = 0; nk.last_launch.algo_bytes = 8.0 * OC * Ktot;
   }
-  rt_err("unknown/unhandled native hip function: " + fn);
+};
+
+void native_kernels_t::run(native_func_t const &f, rtc_func_info_t const &fi, map_str_rtc_arg_t const &am) {
+  string const &fn = fi.op.get_func_name();
+  impl->ws_used = false;   // set by ensure_ws: does this call's plan work in the shared scratch?  (what graph_end_deps' launch-order rule is about)
+  struct ws_note_t { native_kernels_t *nk; impl_t *im; ~ws_note_t() { nk->last_call_uses_ws = im->ws_used; } } const ws_note{this, impl};
+  exact_override_t const xov(impl, fi.op);
+  bool const zinp = op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
+  bool const seedvar = op_seed_var_flag(fi.op);   // (likewise)
+  bool const img_shards = op_img_shards_flag(fi.op);   // (likewise)
+  call_t c{*this, impl, host, f, fi, am, fn, zinp, seedvar, img_shards};
+  switch (f.family) {
+  case kFamSgemm: c.run_sgemm(); break;
+  case kFamConv: c.run_conv(); break;
+  case kFamConvNhwc: c.run_conv_nhwc(); break;
+  case kFamNhwcGrp: c.run_nhwc_grp(); break;
+  case kFamNhwcMulti: c.run_nhwc_multi(); break;
+  case kFamK1Chain: c.run_k1_chain(); break;
+  case kFamFiltsKmajor: c.run_filts_kmajor(); break;
+  case kFamBconv: c.run_bconv(); break;
+  case kFamBckOp: c.run_bck_op(); break;
+  case kFamSgd: c.run_sgd(); break;
+  case kFamBn: c.run_bn(); break;
+  }
 }
 
 } // namespace bodahip

@@ -128,14 +128,30 @@ struct op_base_t {
   void set_func_name(string const &f) { must_insert(str_vals, "func_name", f); }
 };
 typedef std::shared_ptr<op_base_t> p_op_base_t;
+// ---- the op flags of a native function.  Which function takes which flag is a column of the one table, native_funcs.h (included at the end of this file), which defines:
+enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn };   // selects the handler
+enum : unsigned { kFlagZinp = 1, kFlagSeedVar = 2, kFlagImgShards = 4, kFlagNhwcResidual = 8 };
+struct op_flag_name_t { char const *name; unsigned flag; };
+constexpr op_flag_name_t kOpFlagNames[] = {{"img_shards", kFlagImgShards}, {"seed_from_var", kFlagSeedVar}, {"zero_if_in_non_pos", kFlagZinp}, {"nhwc_residual", kFlagNhwcResidual}};
+inline bool native_func_takes_flag(string const &fn, unsigned flag);   // (false for a name that is no row)
+inline bool native_type_takes_flag(string const &t, unsigned flag);    // does a function of op type t take it
+inline string native_funcs_taking_flag(unsigned flag);                 // "a, b and c", in table order
+inline int native_func_member(string const &fn, func_family_t family);           // 0: no row of that family
+inline char const *native_func_type(func_family_t family, int member);           // the row's (first) op type
+inline string native_family_names(func_family_t family);                         // "a, b, c", in table order
+inline bool op_flag_set(op_base_t const &op, unsigned flag) { for (auto const &f : kOpFlagNames) if (f.flag == flag) return op.has(f.name) && op.get_u32(f.name); return false; }
+// every flag but nhwc_residual that the op carries and its function `fn` does not take is refused: "<flag>=1 on '<fn>': <what> takes no flag"
+inline void refuse_flags_not_taken(op_base_t const &op, string const &fn, char const *what) {
+  for (auto const &f : kOpFlagNames) if (f.flag != kFlagNhwcResidual && op_flag_set(op, f.flag) && !native_func_takes_flag(fn, f.flag)) rt_err(string(f.name) + "=1 on '" + fn + "': " + what + " takes no flag");
+}
 // zero_if_in_non_pos, a uint32 of a function op (absent: 0).  1: the function writes in_grad_loss[e] = in[e] > 0 ? g[e] : +0, g what it writes without the flag and `in` the
 // op's forward input -- hip_zero_if_non_pos's rule on the producer's store.  Only the three functions whose in_grad_loss has the dims of `in` take it; hip_bconv_in and
 // hip_spreading then take `in` as one more var arg, hip_bck_lrn reads it already
 inline bool op_zinp_flag(op_base_t const &op) {
-  if (!op.has("zero_if_in_non_pos") || !op.get_u32("zero_if_in_non_pos")) return false;
+  if (!op_flag_set(op, kFlagZinp)) return false;
   string const fn = op.has_func_name() ? op.get_func_name() : string();
-  if (fn != "hip_bconv_in" && fn != "hip_spreading" && fn != "hip_bck_lrn")
-    rt_err("zero_if_in_non_pos=1 on '" + (fn.empty() ? op.get_type() : fn) + "': only hip_bconv_in, hip_spreading and hip_bck_lrn write an in_grad_loss with the dims of their forward input in");
+  if (!native_func_takes_flag(fn, kFlagZinp))
+    rt_err("zero_if_in_non_pos=1 on '" + (fn.empty() ? op.get_type() : fn) + "': only " + native_funcs_taking_flag(kFlagZinp) + " write an in_grad_loss with the dims of their forward input in");
   if (!(op.get_dims("in") == op.get_dims("in_grad_loss"))) rt_err(fn + ": zero_if_in_non_pos=1 needs in and in_grad_loss of the same dims");
   return true;
 }
@@ -143,18 +159,18 @@ inline bool op_zinp_flag(op_base_t const &op) {
 // and element type, and writes out = cvt( relu( (conv + bias) + float(res) ) ): a ResNet block's shortcut added in the convolution's epilogue, one rounding
 // (kernels/conv_nhwc_bf16.hip -DRES=1).  Only the implicit-GEMM kernel of a plain call has that epilogue
 inline bool op_nhwc_residual_flag(op_base_t const &op) {
-  if (!op.has("nhwc_residual") || !op.get_u32("nhwc_residual")) return false;
+  if (!op_flag_set(op, kFlagNhwcResidual)) return false;
   string const fn = op.has_func_name() ? op.get_func_name() : string();
-  if (fn != "hip_conv_nhwc") unsup_err("nhwc_residual=1 on '" + (fn.empty() ? (op.has_type() ? op.get_type() : string("?")) : fn) + "': only a plain hip_conv_nhwc call has the residual epilogue (not a sibling group, a set or a multi-problem launch)");
+  if (!native_func_takes_flag(fn, kFlagNhwcResidual)) unsup_err("nhwc_residual=1 on '" + (fn.empty() ? (op.has_type() ? op.get_type() : string("?")) : fn) + "': only a plain " + native_funcs_taking_flag(kFlagNhwcResidual) + " call has the residual epilogue (not a sibling group, a set or a multi-problem launch)");
   return true;
 }
 // seed_from_var, a uint32 of a hip_dropout function op (absent: 0).  1: the call takes one more var arg, det_drop_seed_var (uint32_t, one element), and hashes with
 // seed = that word + the by-value det_drop_seed (wraps): the seed then lives in device memory, where a captured launch reads it anew at every replay
 inline bool op_seed_var_flag(op_base_t const &op) {
-  if (!op.has("seed_from_var") || !op.get_u32("seed_from_var")) return false;
+  if (!op_flag_set(op, kFlagSeedVar)) return false;
   string const fn = op.has_func_name() ? op.get_func_name() : string();
-  bool const bare_dropout = fn.empty() && op.has_type() && (op.get_type() == "Dropout" || op.get_type() == "BckDropout");
-  if (fn != "hip_dropout" && !bare_dropout) rt_err("seed_from_var=1 on '" + (fn.empty() ? (op.has_type() ? op.get_type() : string("?")) : fn) + "': only hip_dropout takes a seed, and only it can read one from a var");
+  bool const bare_dropout = fn.empty() && op.has_type() && native_type_takes_flag(op.get_type(), kFlagSeedVar);   // (a bare Dropout / BckDropout)
+  if (!native_func_takes_flag(fn, kFlagSeedVar) && !bare_dropout) rt_err("seed_from_var=1 on '" + (fn.empty() ? (op.has_type() ? op.get_type() : string("?")) : fn) + "': only " + native_funcs_taking_flag(kFlagSeedVar) + " takes a seed, and only it can read one from a var");
   return true;
 }
 // img_shards, a uint32 of a function op (absent: 0).  1: the call's img-leading vars may be shards of a batch, and the call leaves the bits of the WHOLE batch's call --
@@ -162,10 +178,10 @@ inline bool op_seed_var_flag(op_base_t const &op) {
 // count), hip_sum_loss_over_imgs (one chain over the images), hip_dropout (hashes the flat index in the whole tensor).  On one device (be=cpu, be=hip) there is one shard
 // and the flagged call is the unflagged one; a multi-device backend runs it as csrc/hip_multi.cc describes.  No new var args
 inline bool op_img_shards_flag(op_base_t const &op) {
-  if (!op.has("img_shards") || !op.get_u32("img_shards")) return false;
+  if (!op_flag_set(op, kFlagImgShards)) return false;
   string const fn = op.has_func_name() ? op.get_func_name() : string();
-  if (fn != "hip_bconv_filts" && fn != "hip_bconv_biases" && fn != "hip_sm_grad_and_loss" && fn != "hip_sum_loss_over_imgs" && fn != "hip_dropout")
-    rt_err("img_shards=1 on '" + (fn.empty() ? (op.has_type() ? op.get_type() : string("?")) : fn) + "': only hip_bconv_filts, hip_bconv_biases, hip_sm_grad_and_loss, hip_sum_loss_over_imgs and hip_dropout take it (every other function is independent per image and runs on img shards as it is)");
+  if (!native_func_takes_flag(fn, kFlagImgShards))
+    rt_err("img_shards=1 on '" + (fn.empty() ? (op.has_type() ? op.get_type() : string("?")) : fn) + "': only " + native_funcs_taking_flag(kFlagImgShards) + " take it (every other function is independent per image and runs on img shards as it is)");
   return true;
 }
 // the var bound to det_drop_seed_var: uint32_t, exactly one element, and not the tensor the call rewrites
@@ -182,7 +198,7 @@ struct sgd_op_t { std::vector<long> elems; std::vector<float> lr_mult, decay_mul
 inline sgd_op_t sgd_op_of_op(op_base_t const &op) {
   string const fn = "hip_sgd_update";
   if (op.get_type() != "SgdUpdate") rt_err(fn + ": a function of op type SgdUpdate, not " + op.get_type());
-  for (char const *fl : {"img_shards", "seed_from_var", "zero_if_in_non_pos"}) if (op.has(fl) && op.get_u32(fl)) rt_err(string(fl) + "=1 on '" + fn + "': the update takes no flag");
+  refuse_flags_not_taken(op, fn, "the update");
   if (!op.has("tens_num")) rt_err(fn + ": the op has no 'tens_num'");
   uint32_t const n = op.get_u32("tens_num");
   if (n < 1 || n > (uint32_t)kSgdUpdateMaxTens) rt_err(fn + ": tens_num=" + std::to_string(n) + ": 1 to " + std::to_string(kSgdUpdateMaxTens) + " tensors");
@@ -214,7 +230,6 @@ constexpr long kBnMinSlab = 4096;      // ... and never shorter than this: a sho
 constexpr long kBnTargetWgs = 512;     // two workgroups per CU on a fixed 256 CUs (not the device's count: the plan must not depend on the device)
 constexpr long kBnMaxSlabs = 4096;     // per channel (only a forced slab length can ask for more)
 constexpr int kFanOutMax = 8;
-inline bool is_bn_func_name(string const &fn) { return fn == "hip_bn_stats" || fn == "hip_bn_fwd" || fn == "hip_bn_bck_sums" || fn == "hip_bn_bck_in" || fn == "hip_fan_out"; }
 struct bn_op_t {
   int kind = 0;                  // 1 stats, 2 fwd, 3 bck_sums, 4 bck_in, 5 fan_out
   long B = 0, C = 0, HW = 0, N = 0;   // N = B * HW: the elements of one channel
@@ -238,12 +253,12 @@ inline void bn_slab_plan(string const &fn, long C, long N, uint32_t forced, long
 }
 inline bn_op_t bn_op_of_op(op_base_t const &op) {
   string const fn = op.has_func_name() ? op.get_func_name() : string();
-  static char const *const types[] = {"", "BnStats", "BnFwd", "BnBckSums", "BnBckIn", "FanOut"};
   bn_op_t r;
-  r.kind = fn == "hip_bn_stats" ? 1 : fn == "hip_bn_fwd" ? 2 : fn == "hip_bn_bck_sums" ? 3 : fn == "hip_bn_bck_in" ? 4 : fn == "hip_fan_out" ? 5 : 0;
-  if (!r.kind) rt_err("'" + fn + "' is none of hip_bn_stats, hip_bn_fwd, hip_bn_bck_sums, hip_bn_bck_in, hip_fan_out");
-  if (!op.has_type() || op.get_type() != types[r.kind]) rt_err(fn + ": a function of op type " + types[r.kind] + ", not " + (op.has_type() ? op.get_type() : string("?")));
-  for (char const *fl : {"img_shards", "seed_from_var", "zero_if_in_non_pos"}) if (op.has(fl) && op.get_u32(fl)) rt_err(string(fl) + "=1 on '" + fn + "': the function takes no flag");
+  r.kind = native_func_member(fn, kFamBn);
+  if (!r.kind) rt_err("'" + fn + "' is none of " + native_family_names(kFamBn));
+  string const type = native_func_type(kFamBn, r.kind);
+  if (!op.has_type() || op.get_type() != type) rt_err(fn + ": a function of op type " + type + ", not " + (op.has_type() ? op.get_type() : string("?")));
+  refuse_flags_not_taken(op, fn, "the function");
   auto f32 = [&](string const &an) { if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'"); p_nda_t const &v = op.get(an); if (v->dims.tn != "float" || v->dims.sz() != 0 || !v->rp) rt_err(fn + ": '" + an + "' is not a float scalar"); return *static_cast<float const *>(v->rp); };
   auto u32 = [&](string const &an) { if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'"); return op.get_u32(an); };
   switch (r.kind) {
@@ -391,3 +406,4 @@ p_rtc_compute_t make_hip_compute(int device_ordinal);
 p_rtc_compute_t make_cpu_compute();
 
 } // namespace bodahip
+#include "native_funcs.h"   // (the definitions of the native_func_* functions declared above)

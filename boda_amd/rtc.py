@@ -93,6 +93,8 @@ ABI = {  # symbol -> (restype, argtypes); every symbol include/bodahip.h declare
     "bodahip_parse_op": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
     "bodahip_prebuild": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t)]),
     "bodahip_explain_plan": (C.c_int, [C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t]),
+    "bodahip_native_funcs": (C.c_int, [C.c_char_p, C.c_size_t]),
+    "bodahip_func_args": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
 }
 for _n, (_r, _a) in ABI.items():
     _f = getattr(_lib, _n)  # AttributeError here == library does not export what the header declares
@@ -429,6 +431,29 @@ def compile_stats() -> dict:
     h = C.c_uint64(); m = C.c_uint64(); ms = C.c_double()
     _chk(_lib.bodahip_compile_stats(C.byref(h), C.byref(m), C.byref(ms)))
     return {"cache_hits": int(h.value), "compiled": int(m.value), "compile_ms": float(ms.value)}
+
+
+def native_funcs() -> dict:
+    """The backend's table of native functions (csrc/native_funcs.h): name -> {family, member, types, flags, be, multi_dev, opt, why}, in table order.  Host-only."""
+    buf = C.create_string_buffer(1 << 16)
+    _chk(_lib.bodahip_native_funcs(buf, 1 << 16))
+    out = {}
+    for line in buf.value.decode().splitlines():
+        head, why = line.split(" why=", 1)
+        name, *kv = head.split(" ")
+        if name in out:
+            raise RtErr(f"native_funcs: {name!r} has two rows")
+        row = dict(x.split("=", 1) for x in kv)
+        out[name] = {"family": row["family"], "member": int(row["member"]), "types": tuple(row["types"].split(",")), "flags": () if row["flags"] == "-" else tuple(row["flags"].split(",")),
+                     "be": tuple(row["be"].split(",")), "multi_dev": row["multi_dev"], "opt": () if row["opt"] == "-" else tuple(row["opt"].split(":")), "why": why}
+    return out
+
+
+def func_args(fop: Op) -> tuple:
+    """The (arg, kind) list of an annotated function op as the backend's table gives it: what cnn_op.pipe_func_args states in Python.  Host-only."""
+    buf = C.create_string_buffer(1 << 14)
+    _chk(_lib.bodahip_func_args(fop.to_str().encode(), buf, 1 << 14))
+    return tuple(tuple(x.split(":")) for x in buf.value.decode().split())
 
 
 def parse_op_native(line: str) -> str:

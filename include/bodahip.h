@@ -156,6 +156,13 @@ int bodahip_prebuild(const char *op_lexp, const char *arch, int num_cus, const c
 /* the planner's decision for an annotated op, without compiling or touching a device: "<kernel> <tile> <-D options ...>"
  * (variant / blocking selection is host logic: the counterpart of add_codegen_annotations' choice, src/cnn_op.cc:16-378) */
 int bodahip_explain_plan(const char *op_lexp, int num_cus, const char *tile, char *plan_buf, size_t plan_buf_sz);
+/* the table of native functions (csrc/native_funcs.h), one line per function name:
+ *   "<name> family=<family> member=<n> types=<T[,T]> flags=<flag[,flag] | -> be=<hip[,cpu]> multi_dev=<on_shards | replicated_only | needs_flag | refused> opt=<arg:KIND | -> why=<sentence>"
+ * (why: what a multi-device backend answers an unflagged / any call of a needs_flag / refused function; it runs to the end of the line).  Host-only, no context. */
+int bodahip_native_funcs(char *buf, size_t buf_sz);
+/* the args of an annotated function op in call order, "arg:KIND arg:KIND ..." with KIND one of IN OUT INOUT REF VAL: the table's fixed args with the part that depends
+ * on the op (ins_<i>, outs_<i>, w_<i> g_<i> h_<i>) and the arg an op flag adds.  Host-only, no context. */
+int bodahip_func_args(const char *op_lexp, char *buf, size_t buf_sz);
 /* what run-time compilation cost this process so far (the reference publishes it per run: doc/ops-prof-and-wis-ana-usage-notes.txt:9-10, INSTALL.md:283; its compile is
  * nvrtc_compute_t::compile, src/nvrtc_util.cc:216-238): code objects served from the on-disk cache, code objects hiprtc had to compile, milliseconds spent compiling */
 int bodahip_compile_stats(uint64_t *cache_hits_out, uint64_t *compiled_out, double *compile_ms_out);
