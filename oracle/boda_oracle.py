@@ -128,10 +128,14 @@ def lrn_fwd(inp, local_size=5, alpha=1.0, beta=0.75, k=1.0) -> np.ndarray:
 
 
 def to_bf16(x: np.ndarray) -> np.ndarray:
-    """fp32 -> bf16 (round-to-nearest-even) -> fp32: what v_cvt_pk_bf16_f32 does to the operands of the bf16 kernels."""
+    """fp32 -> bf16 (round-to-nearest-even) -> fp32: what v_cvt_pk_bf16_f32 does to the operands of the bf16 kernels.
+    A NaN stays a NaN: the quiet NaN of the same sign and the same top 7 mantissa bits (the rounding add would carry 0x7FFFFFFF into -0 and 0x7F800001 into +Inf).
+    Everything else rounds to nearest even; a finite value at or above the largest bf16's upper half-ulp becomes Inf, as RNE says."""
     u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
     r = ((u >> 16) & 1) + 0x7FFF
-    return ((u + r) & 0xFFFF0000).astype(np.uint32).view(np.float32).reshape(x.shape)
+    rne = (u + r) & 0xFFFF0000
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    return np.where(nan, (u & 0xFFFF0000) | 0x00400000, rne).astype(np.uint32).view(np.float32).reshape(np.shape(x))
 
 
 def mrd(o1: np.ndarray, o2: np.ndarray) -> float:
