@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, fan_out_func_op, sgd_update_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
-                     pipe_func_args, seed_from_var, SEED_VAR_ARG)
+                     pipe_func_args, seed_from_var, SEED_VAR_ARG, bf16_operands)
 from .conv_pipe import ConvPipe, PipeOp
 from .op import Dims, Nda, Op, RtErr, UnsupErr
 from .rtc import RtcArg, RtcFuncCall, RtcFuncInfo
@@ -402,15 +402,24 @@ class ConvPipeBck:
     fuse_filts_biases=True (opt-in; False leaves the calls, their names and every bit as they are): every BckConv emits hip_bconv_in followed by ONE
     hip_bconv_filts_biases in place of the hip_bconv_biases + hip_bconv_filts pair.  Every other node holds the same bits; the filter and
     bias gradients follow that function's written chains (on be=cpu: the single chains, the same bits as the pair).  Not on a multi-device backend: init raises UnsupErr.
+    grad_operands="bf16" (opt-in; "" leaves everything as it is): every BckConv emits hip_bconv_in and hip_bconv_filts_biases with hip_operands=bf16
+    (cnn_op.bf16_operands) -- the option therefore IMPLIES fuse_filts_biases=True.  Tensors stay fp32; the operands of the two convolution
+    gradients are rounded to bf16 on the way into the matrix pipe and summed in fp32; the bias gradients, the forward pass, the loss and every non-conv gradient are
+    untouched.  The two conv gradients are then held to a bound, not to bits, and are the same bits run to run and from graph replay to eager.  Composes with
+    fuse_relu_grad, seed_in_var, solver= and capture_graph.  Any other string is an RtErr; on a multi-device backend init raises UnsupErr before creating anything.
     BatchNorm / Scale: exactly the run [BatchNorm, Scale] plus an optional in-place ReLU behind it, on a node X a Convolution produces, is
     supported -- all ResNet-50 has.  It runs as a TRAINING BatchNorm: the convolution (conv_has_relu=0) writes the side var <X>_bn_in; hip_bn_stats reads it and writes
     <bn-tag>_batch_mean / _batch_inv_std and moves the running pair <bn-tag>_mean / _var by bn_maf; hip_bn_fwd writes X, ReLU included.  Backward, BckScale is
     hip_bn_bck_sums (-> <scale-tag>_scale_grad_loss / _bias_grad_loss) and BckBatchNorm hip_bn_bck_in, in place on X_grad_loss, both recomputing the normalised value
     from <X>_bn_in.  An Eltwise runs as hip_reduce, its gradient as one hip_fan_out.  A solver leaves <bn-tag>_mean / _var alone.  Not on a multi-device backend: init refuses a pipe with a BatchNorm or an Eltwise there before creating anything."""
 
-    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[SgdSolver] = None, bn_maf: float = 0.999, fuse_filts_biases: bool = False):
+    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[SgdSolver] = None, bn_maf: float = 0.999, fuse_filts_biases: bool = False,
+                 grad_operands: str = ""):
         self.rtc = rtc
-        self.fuse_filts_biases = bool(fuse_filts_biases)
+        if grad_operands not in ("", "bf16"):
+            raise RtErr(f"ConvPipeBck: grad_operands must be '' | 'bf16', got {grad_operands!r}")
+        self.grad_operands = grad_operands
+        self.fuse_filts_biases = bool(fuse_filts_biases) or self.grad_operands == "bf16"   # (the filter and bias gradients have their bf16 form as the fused call only)
         self.solver = solver
         self.bn_maf = float(bn_maf)   # a training BatchNorm's moving-average fraction: run' = maf * run + (1 - maf) * batch
         self.sgd_params: List[str] = []   # the params the solver updates: all of them but the BatchNorm running statistics
@@ -442,6 +451,9 @@ class ConvPipeBck:
         if self.seed_in_var and SEED_VAR in bp.nodes:
             raise RtErr(f"ConvPipeBck.init: seed_in_var=True needs the var name {SEED_VAR!r}, which is a node of the pipe")
         multi_dev = isinstance(getattr(rtc, "devices", None), list) and len(rtc.devices) > 1
+        if self.grad_operands and multi_dev:
+            raise UnsupErr("ConvPipeBck.init: grad_operands='bf16': the filter and bias gradients have their bf16-operand form as hip_bconv_filts_biases only, which sums over "
+                           "the images into two outputs and is not provided on a multi-device backend (devices=...); leave the option off there")
         if self.fuse_filts_biases and multi_dev:
             raise UnsupErr("ConvPipeBck.init: fuse_filts_biases=True: hip_bconv_filts_biases sums over the images into two outputs and is not provided on a multi-device "
                            "backend (devices=...); leave the option off there")
@@ -548,9 +560,10 @@ class ConvPipeBck:
                 calls.append((add_bck_op_annotations(z, tune)[0], {"in": o.bots[0], "cond": o.bots[0], "out": o.bots[0]}))
             elif t == "BckConv":
                 fi, fb, ff = add_bck_conv_annotations(op, tune)
-                calls.append((zinp(o, fi), dict({"filts": o.bots[1], "out_grad_loss": o.bots[3], "in_grad_loss": o.tops[0]}, **({"in": o.bots[0]} if o.tag in takes_relu else {}))))
+                b16 = bf16_operands if self.grad_operands else (lambda f: f)
+                calls.append((b16(zinp(o, fi)), dict({"filts": o.bots[1], "out_grad_loss": o.bots[3], "in_grad_loss": o.tops[0]}, **({"in": o.bots[0]} if o.tag in takes_relu else {}))))
                 if self.fuse_filts_biases:   # one call writes both gradients
-                    calls.append((bconv_filts_biases_func_op(op, tune), {"in": o.bots[0], "out_grad_loss": o.bots[3], "filts_grad_loss": o.tops[1], "biases_grad_loss": o.tops[2]}))
+                    calls.append((b16(bconv_filts_biases_func_op(op, tune)), {"in": o.bots[0], "out_grad_loss": o.bots[3], "filts_grad_loss": o.tops[1], "biases_grad_loss": o.tops[2]}))
                 else:
                     calls.append((fb, {"out_grad_loss": o.bots[3], "biases_grad_loss": o.tops[2]}))
                     calls.append((ff, {"in": o.bots[0], "out_grad_loss": o.bots[3], "filts_grad_loss": o.tops[1]}))

@@ -429,6 +429,31 @@ def fuse_zero_if_in_non_pos(fop: Op) -> Op:
     return a
 
 
+OPERANDS_VAL = "hip_operands"   # str_val of a function op, travels with it like hip_tile: "" / "f32" the function as it is | "bf16" bf16 operands, fp32 sums
+BF16_OPERAND_FUNCS = ("hip_bconv_in", BCONV_FB_FUNC)   # the functions that have a bf16-operand form (kernels/bconv_in_bf16.hip, kernels/bconv_fb_bf16.hip)
+
+
+def has_bf16_operands(fop: Op) -> bool:
+    return fop.str_vals.get(OPERANDS_VAL, "") == "bf16"
+
+
+def bf16_operands(fop: Op) -> Op:
+    """-> a copy of an annotated hip_bconv_in / hip_bconv_filts_biases function op with hip_operands=bf16: tensors and arg list stay as they are (fp32, reference
+    layouts); the operands of the products are rounded to bf16 (round-to-nearest-even) while they are staged and the sums stay fp32 -- v_mfma_f32_32x32x16_bf16 on
+    be=hip, the template loops on rounded copies on be=cpu.  The bias gradient of the fused call is summed from the unrounded out_grad_loss, bit for bit the fp32 call's
+    chain; zero_if_in_non_pos=1 composes (the condition is read unrounded).  The data and filter gradients are held to a bound, not to bits.
+    hip_bconv_filts and hip_bconv_biases have no bf16 form of their own: UnsupErr, as on the backends."""
+    fn = fop.get_func_name() if fop.has_func_name() else ""
+    if fn in ("hip_bconv_filts", "hip_bconv_biases"):
+        raise UnsupErr(f"{fn}: hip_operands=bf16: the filter and bias gradients have their bf16-operand form as ONE call, {BCONV_FB_FUNC} "
+                       f"(cnn_op.bconv_filts_biases_func_op); hip_bconv_filts and hip_bconv_biases are fp32 only")
+    if fn not in BF16_OPERAND_FUNCS:
+        raise RtErr(f"bf16_operands: {fn or fop.get_type()!r} is none of {', '.join(BF16_OPERAND_FUNCS)} (the functions that have a bf16-operand form)")
+    a = fop.copy()
+    a.str_vals[OPERANDS_VAL] = "bf16"
+    return a
+
+
 SEED_VAR_FLAG = "seed_from_var"   # uint32 of a hip_dropout function op: the hash seed is the word of the var arg det_drop_seed_var + the by-value det_drop_seed (wraps)
 SEED_VAR_ARG = "det_drop_seed_var"
 

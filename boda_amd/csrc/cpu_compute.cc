@@ -416,6 +416,7 @@ struct cpu_compute_t : public rtc_compute_t {
       (void)op_zinp_flag(fi.op);   // (refuses the flag on a function that cannot take it)
       (void)op_seed_var_flag(fi.op);   // (likewise)
       (void)op_img_shards_flag(fi.op);   // (likewise; here there is one shard: a flagged call is the unflagged one)
+      (void)op_bf16_operands(fi.op);   // (str_val hip_operands: refused where the function has no bf16-operand form)
       if (f->family == kFamSgd) (void)sgd_op_of_op(fi.op);   // (the op must be whole)
       if (f->family == kFamBn) (void)bn_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamBckOp) {
@@ -534,8 +535,24 @@ struct cpu_compute_t : public rtc_compute_t {
       bgl[oc] = v;
     }
   }
+  // hip_operands=bf16: fp32 -> bf16 -> fp32, round to nearest even (what v_cvt_pk_bf16_f32 does).  Inf stays inf; a NaN stays a NaN (quiet, same sign, same top seven
+  // mantissa bits); a finite value at or above the largest bf16's upper half ulp becomes inf
+  static float rne_bf16(float v) {
+    uint32_t u; memcpy(&u, &v, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) u = (u & 0xffff0000u) | 0x00400000u;
+    else u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
+    float r; memcpy(&r, &u, 4);
+    return r;
+  }
+  static std::vector<float> rounded_bf16(float const *p, size_t n) {
+    std::vector<float> r(n);
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < (long)n; ++i) r[(size_t)i] = rne_bf16(p[i]);
+    return r;
+  }
   void run_bck(native_func_t const &f, op_base_t const &op, map_str_rtc_arg_t const &am) {
     string const fn = f.name;
+    (void)op_bf16_operands(op);   // (refuses hip_operands=bf16 on hip_bconv_filts / hip_bconv_biases)
     string const ognm = var_of(am, "out_grad_loss");
     dims_t const og = get_var_dims(ognm); need_float(og, "out_grad_loss");
     if (og.sz() != 4) rt_err(fn + ": out_grad_loss must be img:chan:y:x");
@@ -575,6 +592,13 @@ struct cpu_compute_t : public rtc_compute_t {
       for (string const *o : {&fnm, &bnm}) if (*o == inm || *o == ognm) rt_err(fn + ": the output var '" + *o + "' is also an input of the call");
       if (fnm == bnm) rt_err(fn + ": filts_grad_loss and biases_grad_loss are the same var '" + fnm + "'");
       bconv_biases((float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, bnm).buf.get(), g);
+    }
+    if (op_bf16_operands(op)) {   // the operands of the products rounded to bf16 (copies), then the same template loops; biases (above) and the condition zin stay unrounded
+      size_t const n_f = (size_t)g.OC * g.C * g.KH * g.KW, n_in = (size_t)g.B * g.C * g.H * g.W, n_og = (size_t)g.B * g.OC * g.OH * g.OW;
+      std::vector<float> const og = rounded_bf16((float const *)must_find(vis, ognm).buf.get(), n_og);
+      if (din) { std::vector<float> const fr = rounded_bf16((float const *)must_find(vis, fnm).buf.get(), n_f); bconv_in(fr.data(), og.data(), (float *)must_find(vis, inm).buf.get(), g, zin); }
+      else { std::vector<float> const ir = rounded_bf16((float const *)must_find(vis, inm).buf.get(), n_in); bconv_filts(ir.data(), og.data(), (float *)must_find(vis, fnm).buf.get(), g); }
+      return;
     }
     if (din) bconv_in((float const *)must_find(vis, fnm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, inm).buf.get(), g, zin);
     else bconv_filts((float const *)must_find(vis, inm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, fnm).buf.get(), g);

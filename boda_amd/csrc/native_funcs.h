@@ -140,6 +140,22 @@ inline int native_func_member(string const &fn, func_family_t family) { native_f
 inline char const *native_func_type(func_family_t family, int member) { native_func_t const *f = find_native_func(family, member); return f ? f->types[0] : ""; }
 inline string native_family_names(func_family_t family) { return native_func_names([&](native_func_t const &f) { return f.family == family; }, ", "); }
 
+// hip_operands, a str_val of a function op that travels with it like hip_tile and hip_exact (no kFlag*: it adds no arg and changes no row).  Absent, empty or "f32": the
+// function as it is.  "bf16" on hip_bconv_in / hip_bconv_filts_biases: the operands of the products are rounded to bf16 (round-to-nearest-even) and the sums stay fp32
+// (kernels/bconv_in_bf16.hip, kernels/bconv_fb_bf16.hip; be=cpu rounds and runs its template loops); the bias gradient is summed from the unrounded values.  Only the
+// bconv family looks at the value
+inline constexpr char kWhyNoBf16Pair[] = "hip_operands=bf16: the filter and bias gradients have their bf16-operand form as ONE call, hip_bconv_filts_biases (cnn_op.bconv_filts_biases_func_op); hip_bconv_filts and hip_bconv_biases are fp32 only";
+inline bool op_bf16_operands(op_base_t const &op) {
+  auto const it = op.str_vals.find("hip_operands");
+  if (it == op.str_vals.end() || !op.has_func_name()) return false;
+  native_func_t const *f = find_native_func(op.get_func_name());
+  if (!f || f->family != kFamBconv) return false;
+  if (it->second.empty() || it->second == "f32") return false;
+  if (it->second != "bf16") rt_err(string(f->name) + ": hip_operands must be f32 | bf16, got '" + it->second + "'");
+  if (f->member != kBconvIn && f->member != kBconvFiltsBiases) unsup_err(string(f->name) + ": " + kWhyNoBf16Pair);
+  return true;
+}
+
 // the (arg, kind) list of an annotated function op: the fixed args with the variable part and the flag's arg applied (what boda_amd/cnn_op.py calls pipe_func_args)
 inline std::vector<func_arg_t> fixed_args(native_func_t const &f) { std::vector<func_arg_t> r; for (auto const &a : f.args) { if (!a.name) break; r.push_back(a); } return r; }
 typedef std::vector<std::pair<string, arg_kind_t>> vect_func_arg_t;

@@ -148,6 +148,8 @@ plan_t plan_conv(conv_geom_t const &g, int num_cus, string const &tile, bool bf1
 plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile, bool zinp = false);   // (zinp: -DZINP=1) BckConv data gradient (kernels/bconv_in_f32.hip)
 plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile);    // BckConv filter gradient, in-launch K slices (kernels/bconv_filts_f32.hip)
 plan_t plan_bconv_filts_biases(conv_geom_t const &g, int num_cus, string const &tile);   // the fused filter + bias gradient, k-major staging, slab slices (kernels/bconv_fb_f32.hip)
+plan_t plan_bconv_in_bf16(conv_geom_t const &g, int num_cus, string const &tile, bool zinp = false);   // hip_operands=bf16: kernels/bconv_in_bf16.hip (plan_t::bf16 is set)
+plan_t plan_bconv_fb_bf16(conv_geom_t const &g, int num_cus, string const &tile);                     // hip_operands=bf16: kernels/bconv_fb_bf16.hip; its second launch is plan_bconv_slab_sum's
 plan_t plan_bconv_slab_sum();                                                        // its second launch: the slabs added in slice order (kernels/bconv_fb_f32.hip -DSLAB_SUM)
 plan_t plan_bconv_biases();                                                          // BckConv bias gradient (kernels/bconv_filts_f32.hip -DBIAS_ONLY)
 long bconv_in_tiles(conv_geom_t const &g, int BJ);                                   // pel tiles over all SY x SX phases (the kernel's walk)

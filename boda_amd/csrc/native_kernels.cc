@@ -63,6 +63,7 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
     break;
   case kFamBconv:   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
+    (void)op_bf16_operands(fi.op);   // (str_val hip_operands: refused at compile where the function has no bf16-operand form)
     break;
   default: {   // kFamBckOp, the gradient pipe's non-conv ops: the (annotated) op must carry every arg's dims
     bck_op_args_t const a = bck_op_args(*f, fi.op);
@@ -92,7 +93,7 @@ void launch(native_host_t *host, kernel_t &k, gemm_args_t &a, tile_cfg_t const &
 
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log) {
   vect_string opts = p.defs; opts.push_back("-DKNAME=" + p.kname);
-  return hiprtc_compile(p.bn ? k_src_bn_f32 : p.sgd ? k_src_sgd_update_f32 : p.bck_ops ? k_src_bck_ops_f32 : p.bconv_in ? k_src_bconv_in_f32 : p.bconv_filts ? k_src_bconv_filts_f32 : p.bconv_fb ? k_src_bconv_fb_f32 : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
+  return hiprtc_compile(p.bn ? k_src_bn_f32 : p.sgd ? k_src_sgd_update_f32 : p.bck_ops ? k_src_bck_ops_f32 : p.bconv_in ? (p.bf16 ? k_src_bconv_in_bf16 : k_src_bconv_in_f32) : p.bconv_filts ? k_src_bconv_filts_f32 : p.bconv_fb ? (p.bf16 ? k_src_bconv_fb_bf16 : k_src_bconv_fb_f32) : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
 }
 
 // grow-only scratch shared by the split-K slabs and the Winograd-domain tensors (like the reference's cudnn scratch var)
@@ -730,8 +731,8 @@ static bconv_args_t bconv_args(conv_geom_t const &g) {
   a.B = g.B; a.C = g.C; a.H = g.H; a.W = g.W; a.OC = g.OC; a.OH = g.OH; a.OW = g.OW;
   return a;
 }
-void native_kernels_t::bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g, float const *zin) {
-  plan_t const p = plan_bconv_in(g, host->nh_num_cus(), tune_of(impl, "conv_tile"), zin != nullptr);
+void native_kernels_t::bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g, float const *zin, bool bf16) {
+  plan_t const p = bf16 ? plan_bconv_in_bf16(g, host->nh_num_cus(), tune_of(impl, "conv_tile"), zin != nullptr) : plan_bconv_in(g, host->nh_num_cus(), tune_of(impl, "conv_tile"), zin != nullptr);
   kernel_t &k = get_kernel(impl, host, p);
   bconv_args_t a = bconv_args(g);
   a.a = filts; a.b = out_grad; a.d = in_grad; a.zin = zin;
@@ -790,8 +791,8 @@ void native_kernels_t::bconv_biases(float const *out_grad, float *biases_grad, c
 }
 // hip_bconv_filts_biases: both gradients from one main launch (kernels/bconv_fb_f32.hip); with K slices the main launch fills the call's slabs and a second launch in
 // the same stream adds them in slice order.  The slab workspace belongs to the call like a K-slice workspace (key: operands and plan) but holds no tickets: nothing to zero
-void native_kernels_t::bconv_filts_biases(float const *in, float const *out_grad, float *filts_grad, float *biases_grad, conv_geom_t const &g) {
-  plan_t const p = plan_bconv_filts_biases(g, host->nh_num_cus(), tune_of(impl, "conv_tile"));
+void native_kernels_t::bconv_filts_biases(float const *in, float const *out_grad, float *filts_grad, float *biases_grad, conv_geom_t const &g, bool bf16) {
+  plan_t const p = bf16 ? plan_bconv_fb_bf16(g, host->nh_num_cus(), tune_of(impl, "conv_tile")) : plan_bconv_filts_biases(g, host->nh_num_cus(), tune_of(impl, "conv_tile"));
   kernel_t &k = get_kernel(impl, host, p);
   bconv_fb_args_t a; memset(&a, 0, sizeof(a));
   a.B = g.B; a.C = g.C; a.H = g.H; a.W = g.W; a.OC = g.OC; a.OH = g.OH; a.OW = g.OW;

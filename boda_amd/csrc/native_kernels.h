@@ -126,11 +126,11 @@ struct native_kernels_t {
   // BckConv gradients (fp32, reference layouts; g = the forward convolution's geometry, out_grad_loss has g.OH x g.OW planes): kernels/bconv_in_f32.hip (data gradient,
   // bit-identical to the reference's chain), kernels/bconv_filts_f32.hip (filter gradient with deterministic in-launch K slices; bias gradient)
   // zin (the op's zero_if_in_non_pos=1): the forward input; in_grad = zin > 0 ? gradient : +0
-  void bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g, float const *zin = nullptr);
+  void bconv_in(float const *filts, float const *out_grad, float *in_grad, conv_geom_t const &g, float const *zin = nullptr, bool bf16 = false);   // bf16 (the op's hip_operands=bf16): kernels/bconv_in_bf16.hip
   void bconv_filts(float const *in, float const *out_grad, float *filts_grad, conv_geom_t const &g);
   void bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g);
   // both at once, k-major staging, up to 1024 K slices in slabs summed by a second launch (kernels/bconv_fb_f32.hip); opt-in: ConvPipeBck(fuse_filts_biases=True)
-  void bconv_filts_biases(float const *in, float const *out_grad, float *filts_grad, float *biases_grad, conv_geom_t const &g);
+  void bconv_filts_biases(float const *in, float const *out_grad, float *filts_grad, float *biases_grad, conv_geom_t const &g, bool bf16 = false);   // bf16: kernels/bconv_fb_bf16.hip, the same slabs and slab sum
   // the non-conv ops of the gradient pipe: ins / outs in the function's arg order (up to eight / two raw device pointers)
   // seed_word (dropout with g.seedvar): the device word added to g.seed
   void bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs, uint32_t const *seed_word = nullptr);

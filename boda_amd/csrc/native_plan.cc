@@ -1237,6 +1237,64 @@ plan_t plan_bconv_filts_biases(conv_geom_t const &g, int num_cus, string const &
 }
 plan_t plan_bconv_slab_sum() { plan_t p; p.bconv_fb = true; p.kname = "bodahip_bconv_slab_sum"; p.defs = {"-DSLAB_SUM=1"}; return p; }
 
+// ---- hip_operands=bf16 (kernels/bconv_in_bf16.hip, kernels/bconv_fb_bf16.hip): the fp32 functions' tile strings, 16-deep MFMA steps (BK % 16 == 0), LDS images of
+// [row][BK + 8] bf16, double-buffered.  The static_asserts of the two kernels, checked on the host
+static void check_bconv_in_bf16_cfg(tile_cfg_t const &c) {
+  int const nt = c.WI * c.WJ * 64;
+  bool ok = c.BI > 0 && c.BJ > 0 && c.BK > 0 && c.WI > 0 && c.WJ > 0 && nt <= 1024 && c.MT == 32 && c.BI % (c.WI * 32) == 0 && c.BJ % (c.WJ * 32) == 0 && c.BK % 16 == 0 &&
+            nt % c.BI == 0 && nt % c.BJ == 0 && c.MINW >= 1 && c.MINW <= 8 && c.SPLITK == 1 && c.PF == 1 && c.SW == 0 && c.KHO == 0;
+  if (ok) {   // a thread owns whole 8-k chunks of one column: whole chunks per thread, or fewer chunks than threads
+    long const chi = (long)c.BI * c.BK / 8, chj = (long)c.BJ * c.BK / 8;
+    ok = (chi % nt == 0 || chi < nt) && (chj % nt == 0 || chj < nt);
+    int const accs = (c.BI / (c.WI * 32)) * (c.BJ / (c.WJ * 32));
+    ok = ok && accs * 16 <= 128 && ((chi + nt - 1) / nt + (chj + nt - 1) / nt) * 8 <= 128 && 2ull * (c.BI + c.BJ) * (c.BK + 8) * 2 <= 160 * 1024;
+  }
+  if (!ok) unsup_err("hip_bconv_in (hip_operands=bf16): unsupported tile configuration " + c.str() + " (BK a multiple of 16, no K slices, LDS 2 * (BI + BJ) * (BK + 8) * 2 bytes of at most 160 KiB)");
+}
+plan_t plan_bconv_in_bf16(conv_geom_t const &g, int num_cus, string const &tile, bool zinp) {
+  bconv_check_geom(g, "hip_bconv_in");
+  plan_t p; p.bconv_in = true; p.bf16 = true; p.kname = "bodahip_bconv_in_bf16";
+  if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_in: bad tile '" + tile + "'"); }
+  else {
+    p.cfg = bconv_default_cfg(g.C, 32);
+    // plan_bconv_in's rule -- fewer tiles than CUs: halve the pel tile
+    if ((long)((g.C + p.cfg.BI - 1) / p.cfg.BI) * bconv_in_tiles(g, 128) < num_cus) { p.cfg.BJ = 64; if (p.cfg.WJ == 4) p.cfg.WJ = 2; }
+  }
+  check_bconv_in_bf16_cfg(p.cfg);
+  p.defs = bconv_geom_defs(g, p.cfg);
+  if (zinp) p.defs.push_back("-DZINP=1");
+  return p;
+}
+static void check_bconv_fb_bf16_cfg(tile_cfg_t const &c) {
+  int const nt = c.WI * c.WJ * 64;
+  bool ok = c.BI > 0 && c.BJ > 0 && c.BK > 0 && c.WI > 0 && c.WJ > 0 && nt <= 1024 && c.MT == 32 && c.BI % (c.WI * 32) == 0 && c.BJ % (c.WJ * 32) == 0 && c.BK % 16 == 0 &&
+            nt % (c.BK / 2) == 0 && c.BI <= nt && c.MINW >= 1 && c.MINW <= 8 && c.SPLITK >= 1 && c.SPLITK <= 1024 && c.PF == 1 && c.SW == 0 && c.KHO == 0;
+  if (ok) {   // a thread owns one k pair and whole rows AND columns
+    int const kg = nt / (c.BK / 2);
+    ok = c.BI % kg == 0 && c.BJ % kg == 0;
+    int const accs = (c.BI / (c.WI * 32)) * (c.BJ / (c.WJ * 32));
+    ok = ok && accs * 16 <= 128 && 2ull * (c.BI + c.BJ) * (c.BK + 8) * 2 <= 160 * 1024;
+  }
+  if (!ok) unsup_err("hip_bconv_filts_biases (hip_operands=bf16): unsupported tile configuration " + c.str() + " (BK a multiple of 16, KSL 1..1024, LDS 2 * (BI + BJ) * (BK + 8) * 2 bytes of at most 160 KiB)");
+}
+plan_t plan_bconv_fb_bf16(conv_geom_t const &g, int num_cus, string const &tile) {
+  bconv_check_geom(g, "hip_bconv_filts_biases");
+  plan_t p; p.bconv_fb = true; p.bf16 = true; p.kname = "bodahip_bconv_filts_biases_bf16";
+  bool ksl_given = false;
+  if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_filts_biases: bad tile '" + tile + "'"); ksl_given = std::count(tile.begin(), tile.end(), 'x') >= 6; }
+  else p.cfg = bconv_default_cfg(g.OC, 32);
+  if (!ksl_given && p.cfg.BI > 0 && p.cfg.BJ > 0 && p.cfg.BK > 0) {   // the fp32 fused call's rule: about two workgroups per CU, every slice at least 8 K steps long
+    long const tiles = (long)((g.OC + p.cfg.BI - 1) / p.cfg.BI) * (((long)g.C * g.KH * g.KW + p.cfg.BJ - 1) / p.cfg.BJ);
+    long const nkt = ((long)g.B * g.OH * g.OW + p.cfg.BK - 1) / p.cfg.BK;
+    long ksl = (2L * num_cus + tiles - 1) / tiles;
+    ksl = std::min<long>(ksl, std::max<long>(1, nkt / 8));
+    p.cfg.SPLITK = (int)std::max<long>(1, std::min<long>(1024, ksl));
+  }
+  check_bconv_fb_bf16_cfg(p.cfg);
+  p.defs = bconv_geom_defs(g, p.cfg); p.defs.push_back(string("-DSLICED=") + (p.cfg.SPLITK > 1 ? "1" : "0"));
+  return p;
+}
+
 
 
 // ---- the non-conv ops of the gradient pipe (kernels/bck_ops_f32.hip).  Bandwidth kernels: no tile to choose, only the geometry to fold into the code (pooling

@@ -235,18 +235,19 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     string const fn = op.has_func_name() ? op.get_func_name() : string();
     if (!fn.empty() && !f) rt_err("prebuild: BckConv function '" + fn + "' has no native kernel");
     std::vector<plan_t> ps;
-    if (!member || member == kBconvIn) ps.push_back(plan_bconv_in(g, num_cus, tile, op_zinp_flag(op)));
+    bool const b16 = op_bf16_operands(op);   // (refuses bf16 on hip_bconv_filts / hip_bconv_biases)
+    if (!member || member == kBconvIn) ps.push_back(b16 ? plan_bconv_in_bf16(g, num_cus, tile, op_zinp_flag(op)) : plan_bconv_in(g, num_cus, tile, op_zinp_flag(op)));
     if (!member || member == kBconvBiases) ps.push_back(plan_bconv_biases());
     if (!member || member == kBconvFilts) ps.push_back(plan_bconv_filts(g, num_cus, tile));
     if (member == kBconvFiltsBiases) {   // (opt-in: never part of the bare op's three calls) the main kernel and, with K slices, the slab sum behind it
-      ps.push_back(plan_bconv_filts_biases(g, num_cus, tile));
+      ps.push_back(b16 ? plan_bconv_fb_bf16(g, num_cus, tile) : plan_bconv_filts_biases(g, num_cus, tile));
       if (ps.back().cfg.SPLITK > 1) ps.push_back(plan_bconv_slab_sum());
     }
     string desc; size_t bytes = 0;
     for (plan_t const &q : ps) {
       desc += (desc.empty() ? "" : " | ") + q.kname + (q.defs.size() > 1 ? " " + q.cfg.str() : string());
       if (q.bconv_in) desc += " grid=" + std::to_string((long)((g.C + q.cfg.BI - 1) / q.cfg.BI) * bconv_in_tiles(g, q.cfg.BJ)) + (q.defs.back() == "-DZINP=1" ? " -DZINP=1" : "");
-      if (q.kname == "bodahip_bconv_filts" || q.kname == "bodahip_bconv_filts_biases") desc += " ksl=" + std::to_string(q.cfg.SPLITK);
+      if (q.kname == "bodahip_bconv_filts" || q.kname == "bodahip_bconv_filts_biases" || q.kname == "bodahip_bconv_filts_biases_bf16") desc += " ksl=" + std::to_string(q.cfg.SPLITK);
       if (!arch.empty()) bytes += compile_plan(q, arch, &log).size();
     }
     if (op_img_shards_flag(op)) {   // a flagged filter / bias gradient on several devices also runs the sum of the per-device partials (csrc/hip_multi.cc): one kernel for every device count
@@ -645,6 +646,7 @@ struct native_kernels_t::call_t {
     string const ogl = var_of_op_dims("out_grad_loss");
     g.B = (int)n_img;
     tile_override_t const tov(impl, "conv_tile", fi.op);
+    bool const bf16 = op_bf16_operands(fi.op);   // (str_val hip_operands: refuses a value that is neither f32 nor bf16, and bf16 on hip_bconv_filts / hip_bconv_biases)
     if (row.member == kBconvIn) {
       string const f = var_of_op_dims("filts"), igl = var_of_op_dims("in_grad_loss");
       if (!(fi.op.get_dims("in_grad_loss") == fi.op.get_dims("in"))) rt_err(fn + ": in_grad_loss must have the dims of in");
@@ -654,7 +656,7 @@ struct native_kernels_t::call_t {
         if (in == igl) rt_err(fn + ": zero_if_in_non_pos=1: 'in' and 'in_grad_loss' are the same var '" + in + "'");
         zin = (float const *)host->nh_var_ptr(in);
       }
-      nk.bconv_in((float const *)host->nh_var_ptr(f), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(igl), g, zin);
+      nk.bconv_in((float const *)host->nh_var_ptr(f), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(igl), g, zin, bf16);
     } else if (row.member == kBconvFilts) {
       string const in = var_of_op_dims("in"), fgl = var_of_op_dims("filts_grad_loss");
       if (!(fi.op.get_dims("filts_grad_loss") == fi.op.get_dims("filts"))) rt_err(fn + ": filts_grad_loss must have the dims of filts");
@@ -665,7 +667,7 @@ struct native_kernels_t::call_t {
       if (fi.op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
       for (string const *o : {&fgl, &bgl}) if (*o == in || *o == ogl) rt_err(fn + ": the output var '" + *o + "' is also an input of the call");
       if (fgl == bgl) rt_err(fn + ": filts_grad_loss and biases_grad_loss are the same var '" + fgl + "'");
-      nk.bconv_filts_biases((float const *)host->nh_var_ptr(in), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(fgl), (float *)host->nh_var_ptr(bgl), g);
+      nk.bconv_filts_biases((float const *)host->nh_var_ptr(in), (float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(fgl), (float *)host->nh_var_ptr(bgl), g, bf16);
     } else {
       string const bgl = var_of_op_dims("biases_grad_loss");
       if (fi.op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");

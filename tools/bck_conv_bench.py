@@ -8,6 +8,11 @@ fp32 MFMA roof.
 --fb: per layer (layers of one geometry once, with their count), the default pipe's pair hip_bconv_biases + hip_bconv_filts beside the one fused call
 hip_bconv_filts_biases, in ONE process on the same vars, in --blocks alternating blocks of --runs calls each (pair, fused, pair, fused, ...): the median of the pair's
 summed times, the median of the fused call's time (both its launches), their ratio, and both plans.
+
+--bf16: per layer (layers of one geometry once, with their count), the fp32 call beside the same call with hip_operands=bf16 (cnn_op.bf16_operands), in ONE process
+on the same vars, in --blocks alternating blocks of --runs calls each (fp32, bf16, fp32, bf16, ...): hip_bconv_in, and with --fb also hip_bconv_filts_biases.  Per call
+one JSON line: the medians in us, their quotient bf16 / fp32, and the GB/s of the call's algorithmic bytes (fp32 tensors either way) beside the recorded 6.29 TB/s copy
+rate.  The yardstick is the fp32 call of the same run; no figure is fixed in advance.
 """
 import argparse
 import json
@@ -20,7 +25,7 @@ sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402
 from boda_amd import gen_data as gd  # noqa: E402
-from boda_amd.cnn_op import NATIVE_ARGS, OpTune, add_bck_conv_annotations, bconv_filts_biases_func_op  # noqa: E402
+from boda_amd.cnn_op import NATIVE_ARGS, OpTune, add_bck_conv_annotations, bconv_filts_biases_func_op, bf16_operands  # noqa: E402
 from boda_amd.op import parse_op  # noqa: E402
 from boda_amd.ops_prof import OpsBackend, profile_rcg_call  # noqa: E402
 from boda_amd.rtc import RtcArg, RtcFuncCall, RtcFuncInfo, make_rtc  # noqa: E402
@@ -89,6 +94,78 @@ def time_pair_and_fused(rtc, op, runs, warmup, blocks):
         rtc.release_per_call_id_data()
 
 
+COPY_GBS = 6290.0   # the recorded device-to-device copy rate
+
+
+def time_f32_and_bf16(rtc, f32_fop, runs, warmup, blocks):
+    """-> (median us of the fp32 call, median us of the same call with hip_operands=bf16, the two launches) on device-generated inputs, alternating blocks."""
+    fn = f32_fop.get_func_name()
+    fops = {"f32": f32_fop, "bf16": bf16_operands(f32_fop)}
+    made, funcs, calls = [], [], {}
+    try:
+        for an, io in NATIVE_ARGS[fn]:
+            if io != "REF":
+                rtc.create_var_with_dims("ob_" + an, f32_fop.get_dims(an)); made.append("ob_" + an)
+                if io == "IN":
+                    rtc.run(gd.gen_call("BckConv", an, "ob_" + an, f32_fop.get_dims(an), 5, 0.0))
+        for mode, f in fops.items():
+            rtc.compile([RtcFuncInfo(f"ob_{mode}", "", [a for a, _ in NATIVE_ARGS[fn]], f)]); funcs.append(f"ob_{mode}")
+            calls[mode] = RtcFuncCall(f"ob_{mode}", {an: (RtcArg.ref(f.get_dims(an)) if io == "REF" else RtcArg.var("ob_" + an)) for an, io in NATIVE_ARGS[fn]})
+        launches = {}
+        for mode in fops:
+            for _ in range(max(1, warmup)):
+                rtc.run(calls[mode])
+            launches[mode] = rtc.last_launch()
+        secs = {"f32": [], "bf16": []}
+        for _ in range(blocks):
+            ids = {mode: [rtc.run(calls[mode]) for _ in range(runs)] for mode in ("f32", "bf16")}
+            rtc.finish_and_sync()
+            for mode in ids:
+                secs[mode] += [rtc.get_dur(i, i) for i in ids[mode]]
+            rtc.release_per_call_id_data()
+        return statistics.median(secs["f32"]) * 1e3, statistics.median(secs["bf16"]) * 1e3, launches
+    finally:
+        rtc.finish_and_sync()
+        for vn in made:
+            rtc.release_var(vn)
+        for f in funcs:
+            rtc.release_func(f)
+        rtc.release_per_call_id_data()
+
+
+def unique_layers(a):
+    seen, layers = {}, []
+    for net, name, conv in nets(a.nets.split(","), a.batch):
+        key = (net, bck_of(conv).to_str())
+        if key in seen:
+            seen[key]["count"] += 1; continue
+        seen[key] = {"net": net, "layer": name, "op": bck_of(conv), "count": 1}
+        layers.append(seen[key])
+    return layers
+
+
+def main_bf16(a):
+    rtc = make_rtc("(be=hip)", 0)
+    rtc.init()
+    OpsBackend(rtc)   # (compiles the input generators)
+    per_net = {}
+    for L in unique_layers(a):
+        per_net[L["net"]] = per_net.get(L["net"], 0) + 1
+        if a.layers and per_net[L["net"]] > a.layers:
+            continue
+        op = L["op"]; g = op.bck_conv_geom()
+        fops = [("data", add_bck_conv_annotations(op, OpTune())[0])] + ([("filts_biases", bconv_filts_biases_func_op(op, OpTune()))] if a.fb else [])
+        for grad, f in fops:
+            f32_us, bf16_us, lch = time_f32_and_bf16(rtc, f, a.runs, a.warmup, a.blocks)
+            by = lch["bf16"]["algo_bytes"]
+            print(json.dumps({"net": L["net"], "layer": L["layer"], "count": L["count"], "grad": grad, "B": g["B"], "C": g["C"], "HW": g["H"], "OC": g["OC"], "k": g["KH"], "s": g["SY"],
+                              "f32_us": round(f32_us, 2), "bf16_us": round(bf16_us, 2), "bf16_over_f32": round(bf16_us / f32_us, 3),
+                              "f32_gbs": round(by / (f32_us * 1e-6) / 1e9, 1), "bf16_gbs": round(by / (bf16_us * 1e-6) / 1e9, 1), "copy_gbs": COPY_GBS,
+                              "bf16_tflops": round(lch["bf16"]["flops"] / (bf16_us * 1e-6) / 1e12, 2),
+                              "f32_cfg": str(lch["f32"].get("cfg", "")), "bf16_cfg": str(lch["bf16"].get("cfg", "")), "bf16_kernel": lch["bf16"]["kernel"]}), flush=True)
+    rtc.close()
+
+
 def main_fb(a):
     rtc = make_rtc("(be=hip)", 0)
     rtc.init()
@@ -121,8 +198,11 @@ def main(argv=None):
     ap.add_argument("--layers", type=int, default=0, help="at most this many layers per net (0: all)")
     ap.add_argument("--batch", type=int, default=0, help="images per layer (0: the layer tables' own batches)")
     ap.add_argument("--fb", action="store_true", help="the pair hip_bconv_biases + hip_bconv_filts beside hip_bconv_filts_biases, in alternating blocks")
-    ap.add_argument("--blocks", type=int, default=4, help="--fb: alternating blocks of --runs calls each")
+    ap.add_argument("--blocks", type=int, default=4, help="--fb / --bf16: alternating blocks of --runs calls each")
+    ap.add_argument("--bf16", action="store_true", help="the fp32 call beside the hip_operands=bf16 call, in alternating blocks: hip_bconv_in, and with --fb hip_bconv_filts_biases")
     a = ap.parse_args(argv)
+    if a.bf16:
+        return main_bf16(a)
     if a.fb:
         return main_fb(a)
     rtc = make_rtc("(be=hip)", 0)

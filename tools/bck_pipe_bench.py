@@ -9,6 +9,7 @@ and the share of the step each native function takes (sums of the backend's per-
     python tools/bck_pipe_bench.py --devices 0:1:2:3 [--out profiles/bck_pipe_devices.txt]
     python tools/bck_pipe_bench.py --sgd [--repeats 3] [--out profiles/r13_sgd_update.txt]
     python tools/bck_pipe_bench.py --nets resnet50 --batch 32 [--limit 900] [--out profiles/r14_resnet50_step.txt]
+    python tools/bck_pipe_bench.py --grad-operands bf16 --nets resnet50 --batch 32 [--repeats 3] [--limit 900] [--out profiles/r16_step_bf16.txt]
 
 --fuse-relu-grad: the same step both ways in ONE process -- ConvPipeBck() and ConvPipeBck(fuse_relu_grad=True), each on a backend instance of its own with the same
 params and inputs -- after the usual warm-up, in --repeats alternating blocks of --runs steps.  Per net two JSON lines ("way": "unfused" / "fused": step ms as the median
@@ -17,6 +18,11 @@ and a third with the launches removed and the fused / unfused ratio.  The compar
 
 --fuse-filts-biases: the same A/B for ConvPipeBck(fuse_filts_biases=True): every BckConv's hip_bconv_biases + hip_bconv_filts pair as one hip_bconv_filts_biases call
 (DESIGN.md section 3.11).  The losses need not have the same bits: nothing the loss depends on changes, and they do; the gradients follow other chains.
+
+--grad-operands bf16: the same construction for ConvPipeBck(grad_operands="bf16").  Three ways in ONE process, each on a backend instance of
+its own with the same params and inputs, in alternating blocks: "f32" (the default step), "f32_fused" (fuse_filts_biases=True: the fp32 step with the same call list as
+the bf16 one) and "bf16".  Per net one JSON line per way, with the loss of each, and one with the two quotients of the same run.  The losses agree in every bit (nothing
+the loss depends on changes); no quotient is required.
 
 --graph: the same construction for the step as one hipGraph replay.  Three ways in ONE process, each a ConvPipeBck(seed_in_var=True) on a backend instance of its own
 with the same params and inputs: "eager" (run_device_only), "graph" (capture_graph(), run_graph) and "graph_parallel" (capture_graph(parallel=True): the calls' true
@@ -99,6 +105,53 @@ def fuse_ab(net, batch, runs, warmup, repeats, option="fuse_relu_grad"):
     print(json.dumps({"net": net, "launches_removed": len(u["drv"].calls()) - len(f["drv"].calls()), "folded": f["drv"].fused_relu_grads["folded"],
                       "unfolded": sorted(f["drv"].fused_relu_grads["unfolded"]), "fused_over_unfused": round(statistics.median(f["ms"]) / statistics.median(u["ms"]), 4),
                       "same_loss_bits": loss["unfused"] == loss["fused"]}), flush=True)
+    for w in ways.values():
+        w["drv"].release(); w["rtc"].close()
+
+
+def operands_ab(net, batch, runs, warmup, repeats, mode):
+    import numpy as np
+    from boda_amd.bck_pipe import ConvPipeBck, add_bck_ops, host_params
+    from boda_amd.rtc import make_rtc
+    cp = _pipe(net, batch)
+    bp = add_bck_ops(cp)
+    params = host_params(bp, 5)
+    rng = np.random.default_rng(0)
+    data = rng.uniform(-1, 1, cp.nodes["data"].sizes).astype(np.float32)
+    label = rng.integers(0, 1000, (batch, 1, 1)).astype(np.float32)
+    ways = {}
+    for way, kw in (("f32", {}), ("f32_fused", {"fuse_filts_biases": True}), (mode, {"grad_operands": mode})):
+        rtc = make_rtc("(be=hip)", 0)
+        rtc.init()
+        drv = ConvPipeBck(rtc, **kw)
+        drv.init(bp, params)
+        rtc.copy_nda_to_var("data", data); rtc.copy_nda_to_var("label", label)
+        ways[way] = {"rtc": rtc, "drv": drv, "blocks": [], "ms": [], "share": {}}
+    for w in ways.values():
+        for i in range(warmup):
+            w["drv"].set_det_drop_seed(i); w["drv"].run_device_only()
+    for rep in range(repeats):
+        for w in ways.values():
+            ms = []
+            for i in range(runs):
+                w["drv"].set_det_drop_seed(warmup + rep * runs + i)
+                ms.append(w["drv"].run_device_only())
+                for _, fn, d in w["drv"].per_call_ms:
+                    w["share"][fn] = w["share"].get(fn, 0.0) + d
+            w["ms"] += ms; w["blocks"].append(round(statistics.median(ms), 3))
+    loss = {k: w["rtc"].copy_var_to_nda("loss").tobytes() for k, w in ways.items()}
+    for way, w in ways.items():
+        tot = sum(w["share"].values()); step = statistics.median(w["ms"])
+        lv = float(np.frombuffer(loss[way], np.float32)[0])
+        if not np.isfinite(lv):
+            raise SystemExit(f"{net} {way}: the step ended with the loss {lv}")
+        print(json.dumps({"net": net, "batch": batch, "way": way, "calls": len(w["drv"].calls()), "step_ms": round(step, 3), "block_medians_ms": w["blocks"],
+                          "imgs_per_s": round(batch / (step * 1e-3), 1), "loss": round(lv, 4),
+                          "share": {k: round(v / tot, 4) for k, v in sorted(w["share"].items(), key=lambda kv: -kv[1])},
+                          "ms_per_step": {k: round(v / len(w["ms"]), 3) for k, v in sorted(w["share"].items(), key=lambda kv: -kv[1])}}), flush=True)
+    med = lambda k: statistics.median(ways[k]["ms"])
+    print(json.dumps({"net": net, f"{mode}_over_f32": round(med(mode) / med("f32"), 4), f"{mode}_over_f32_fused": round(med(mode) / med("f32_fused"), 4),
+                      "same_loss_bits": loss["f32"] == loss["f32_fused"] == loss[mode]}), flush=True)
     for w in ways.values():
         w["drv"].release(); w["rtc"].close()
 
@@ -241,16 +294,19 @@ def main(argv=None):
     ap.add_argument("--fuse-filts-biases", action="store_true", help="A/B: the step with every BckConv's bias + filter gradient pair, and with the one fused hip_bconv_filts_biases call, in one process")
     ap.add_argument("--graph", action="store_true", help="A/B: the eager step, the step as one hipGraph replay, and the replay with the calls' true dependencies, in one process")
     ap.add_argument("--sgd", action="store_true", help="A/B: the step without a solver, with the SGD update as multi-tensor calls, and with one update call per tensor, in one process")
+    ap.add_argument("--grad-operands", default="", choices=["", "bf16"], help="A/B: the fp32 step, the fp32 step with the fused filter + bias call, and the step with bf16 gradient operands, in one process")
     ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad / --graph / --sgd: alternating blocks of --runs steps per way")
     ap.add_argument("--devices", default="", help="e.g. 0:1:2:3: the plain step on the multi-device backend (be=hip,devices=...), batch sharded on img")
     ap.add_argument("--child", default="")
     a = ap.parse_args(argv)
-    if a.devices and (a.graph or a.fuse_relu_grad or a.sgd or a.fuse_filts_biases):
+    if a.devices and (a.graph or a.fuse_relu_grad or a.sgd or a.fuse_filts_biases or a.grad_operands):
         ap.error("--devices times the plain step: graph capture is not provided on several devices, and the fused and the solver A/B run on one")
-    if a.graph + a.fuse_relu_grad + a.sgd + a.fuse_filts_biases > 1:
-        ap.error("--graph, --fuse-relu-grad, --fuse-filts-biases and --sgd are four comparisons: run them one at a time")
-    a.out = a.out or os.path.join(ROOT, "profiles", "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
+    if a.graph + a.fuse_relu_grad + a.sgd + a.fuse_filts_biases + bool(a.grad_operands) > 1:
+        ap.error("--graph, --fuse-relu-grad, --fuse-filts-biases, --grad-operands and --sgd are five comparisons: run them one at a time")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r16_step_bf16.txt" if a.grad_operands else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
     if a.child:
+        if a.grad_operands:
+            return operands_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, a.grad_operands)
         if a.sgd:
             return sgd_ab(a.child, a.batch, a.runs, a.warmup, a.repeats)
         if a.graph:
@@ -263,6 +319,7 @@ def main(argv=None):
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", net, "--batch", str(a.batch), "--runs", str(a.runs), "--warmup", str(a.warmup)]
         cmd += ["--fuse-relu-grad", "--repeats", str(a.repeats)] if a.fuse_relu_grad else []
         cmd += ["--fuse-filts-biases", "--repeats", str(a.repeats)] if a.fuse_filts_biases else []
+        cmd += ["--grad-operands", a.grad_operands, "--repeats", str(a.repeats)] if a.grad_operands else []
         cmd += ["--graph", "--repeats", str(a.repeats)] if a.graph else []
         cmd += ["--sgd", "--repeats", str(a.repeats)] if a.sgd else []
         cmd += ["--devices", a.devices] if a.devices else []
@@ -271,9 +328,9 @@ def main(argv=None):
             print(f"{net}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
             return r.returncode
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
-        print("\n".join(lines[-4:] if (a.graph or a.sgd) else lines[-3:] if (a.fuse_relu_grad or a.fuse_filts_biases) else lines[-1:]), flush=True)
+        print("\n".join(lines[-4:] if (a.graph or a.sgd or a.grad_operands) else lines[-3:] if (a.fuse_relu_grad or a.fuse_filts_biases) else lines[-1:]), flush=True)
     with open(a.out, "w") as f:
-        extra = f" --devices {a.devices}" if a.devices else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
+        extra = f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
         f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 
