@@ -19,6 +19,9 @@
 // Round 6: FOUR multiplying waves as well (WI x WJ = 2 x 2 | 1 x 4 | 4 x 1; 512 threads) and wave tiles of one row block -- 128 x 128 (64 x 64 per wave), 64 x 128,
 // 128 x 64, 64 x 64: the tiles of the sizes that give 256 CUs less than a 128 x 128 tile each (1024^3) or whose last round is ragged (the rest launch of the two-level
 // tiling).  Several such workgroups share a CU (MINW = waves per SIMD the register budget is set for).
+// Round 7: TWELVE multiplying waves (WI x WJ = 4 x 3 | 3 x 4 of 64 x 64; 1024 threads) on a 256 x 192 | 192 x 256 tile: three multiplying waves and ONE staging wave per SIMD in
+// one barrier domain, one workgroup per CU.  BKS 16 (192 / 4 = 48 float4 units per k row: 16 rows give every staging thread three); the loop, the barriers, the LDS
+// images and the epilogue are those of the 256 x 128 form.
 // Compile-time parameters (-D): KNAME BKS (k per step: 16) PF (K tiles in flight in registers per staging thread: 2 | 4) GROUP_I [TBI TBJ WI WJ MINW]
 
 #ifndef __HIPCC_RTC__
@@ -58,6 +61,9 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #ifndef STGPRIO
 #define STGPRIO 0
 #endif
+#ifndef STGRING
+#define STGRING 1 // round 7: the staging loop's steps in pinned order, K-tail tests in the last round only (0: the loop as the compiler schedules it, every load tested) -- interleaved
+#endif            // A/B on one device (tools/sgemm_plan_ab.py; TF/s): 12288^3 146.4 -> 152.3, 8192^3 146.1 -> 152.5, 7168^3 140.2 -> 149.3, 6144^3 138.6 -> 143.4; the 12288^3 launch MFMA-busy 94.2 -> 98.4 %
 #ifndef NSTG
 #define NSTG 4 // LDS stages: tile t lives in stage t % NSTG and is written during step t - (NSTG - 1).  4: a tile is complete one barrier before its step, so the
 #endif         // multiplying waves fetch its first operands BEFORE the barrier that ends the previous step (nothing but the barrier itself between two steps)
@@ -79,7 +85,7 @@ struct gemm_args_t { // same layout as gemm_conv_f32.hip (one host-side struct s
 
 namespace {
 constexpr int kNMW = WI * WJ;                 // multiplying waves
-static_assert(kNMW == 8 || kNMW == 4, "eight (or four) multiplying waves");
+static_assert(kNMW == 12 || kNMW == 8 || kNMW == 4, "twelve, eight or four multiplying waves");
 constexpr int kTI = TBI / (WI * 32), kTJ = TBJ / (WJ * 32);   // 32 x 32 blocks per wave
 static_assert(TBI % (WI * 32) == 0 && TBJ % (WJ * 32) == 0 && (kTI == 4 || kTI == 2 || kTI == 1) && (kTJ == 2 || kTJ == 1), "wave tile: 4 | 2 | 1 row blocks x 2 | 1 column blocks");
 constexpr int kLDI = TBI + 4, kLDJ = TBJ + 4; // floats per k row of the a / b image
@@ -95,6 +101,7 @@ static_assert(BKS % 4 == 0 && (PF == 2 || PF == 4), "BKS % 4 == 0, PF: 2 | 4");
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ rsrc_t make_rsrc(float const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
 __device__ __forceinline__ f32x4 bload4(rsrc_t r, int voff, int soff) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0)); }
+template <bool B> struct bool_c { static constexpr bool value = B; };
 } // namespace
 
 #if (TBI / (WI * 32)) == 4
@@ -176,6 +183,37 @@ extern "C" __global__ __launch_bounds__((kNMW + 4) * 64, MINW) void KNAME(gemm_a
       for (int n = 0; n < kNLJ; ++n) { lstoreJ(n, t, ringJ[t % PF][n]); ringJ[t % PF][n] = gloadJ(n, t + PF); }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n s_barrier" ::: "memory");
+#if STGRING
+    // Round 7: a step is "every slot's ds_write, then every slot's reload, then the barrier", pinned in that order (scheduling fences): left to itself the compiler hoists a
+    // step's loads over the stores of their own slots -- into spare registers, copied back behind an s_waitcnt vmcnt that drains the ring (the 256 x 128 form: one load per
+    // step a single step ahead instead of PF; the 1024-thread forms: spills) -- and over the barriers.  And only a round that reaches the last K tile (or the padded steps
+    // behind it) tests rows against K: in the rounds before it every row is inside, the offsets are the loop-invariant column offsets and the scalar offset is not clamped.
+    int const nfull = p.K / BKS;   // K tiles that are whole
+    auto step = [&](auto tail, int u, int kb) __attribute__((always_inline)) {
+      int const slot = (u + kD) % PF, stage = (u + kD) % NSTG, kt = kb + u + kD + PF;
+#pragma unroll
+      for (int n = 0; n < kNLI; ++n) lstoreI(n, stage, ringI[slot][n]);
+#pragma unroll
+      for (int n = 0; n < kNLJ; ++n) lstoreJ(n, stage, ringJ[slot][n]);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int n = 0; n < kNLI; ++n) ringI[slot][n] = decltype(tail)::value ? gloadI(n, kt) : bload4(rI, goffI[n], kt * (BKS * 4) * p.ldI);
+#pragma unroll
+      for (int n = 0; n < kNLJ; ++n) ringJ[slot][n] = decltype(tail)::value ? gloadJ(n, kt) : bload4(rJ, goffJ[n], kt * (BKS * 4) * p.ldJ);
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(%0)\n s_barrier" :: "n"(kNLI + kNLJ) : "memory");
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    int kb = 0;
+    for (; kb + kU + kD + PF <= nfull; kb += kU) {   // (the round's last load is of tile kb + kU - 1 + kD + PF)
+#pragma unroll
+      for (int u = 0; u < kU; ++u) step(bool_c<false>(), u, kb);
+    }
+    for (; kb < nkt_pad; kb += kU) {
+#pragma unroll
+      for (int u = 0; u < kU; ++u) step(bool_c<true>(), u, kb);
+    }
+#else
     for (int kb = 0; kb < nkt_pad; kb += kU) {
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
@@ -186,6 +224,7 @@ extern "C" __global__ __launch_bounds__((kNMW + 4) * 64, MINW) void KNAME(gemm_a
         asm volatile("s_waitcnt lgkmcnt(%0)\n s_barrier" :: "n"(kNLI + kNLJ) : "memory");
       }
     }
+#endif
     return;
   }
 

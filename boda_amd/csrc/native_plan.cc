@@ -3,7 +3,7 @@
 
 namespace bodahip {
 
-// "BIxBJxBKxWIxWJ[xMINW[xSPLITK[xMT[xPF[xSW[xKHO]]]]]]"
+// "BIxBJxBKxWIxWJ[xMINW[xSPLITK[xMT[xPF[xSW[xKHO]]]]]]"   (SW 3, the staging-wave sgemm kernel: the eleventh field is its LDS stage count)
 bool parse_tile(string const &s, tile_cfg_t &c) {
   int v[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; int n = 0; string cur;
   for (size_t i = 0; i <= s.size(); ++i) {
@@ -217,12 +217,17 @@ plan_t plan_sgemm(uint32_t M, uint32_t N, uint32_t K, int num_cus, string const 
   if (!tile.empty() && p.cfg.SW == 3) {   // round 6: the staging-wave kernel with WI x WJ = 8 | 4 multiplying waves spelled out ("64x128x16x2x2x4x1x32x2x3"): its small forms
     tile_cfg_t const &c = p.cfg;
     int const nmw = c.WI * c.WJ, ti = (c.WI > 0 && c.BI % (c.WI * 32) == 0) ? c.BI / (c.WI * 32) : 0, tj = (c.WJ > 0 && c.BJ % (c.WJ * 32) == 0) ? c.BJ / (c.WJ * 32) : 0;
-    bool const ok = (nmw == 8 || nmw == 4) && (ti == 4 || ti == 2 || ti == 1) && (tj == 2 || tj == 1) && c.BK >= 4 && c.BK <= 32 && c.BK % 4 == 0 && (c.BK * (c.BI / 4)) % 256 == 0 &&
-                    (c.BK * (c.BJ / 4)) % 256 == 0 && (c.PF == 2 || c.PF == 4) && c.MT == 32 && c.SPLITK == 1 && c.MINW >= 1 && c.MINW <= 8 && 4l * 4 * c.BK * (c.BI + c.BJ + 8) <= 160 * 1024;
-    if (!ok || batch != 1 || M % 4 || N % 4 || !allow_big) unsup_err("hip_sgemm: unsupported staging-wave tile " + c.str() + " (8 | 4 multiplying waves of 4 | 2 | 1 x 2 | 1 blocks, whole float4 units per staging thread, M and N multiples of 4)");
-    p.big = true; p.kname = "bodahip_sgemm_big_f32"; p.cfg.KHO = 0;
+    // round 7: twelve multiplying waves as 4 x 3 | 3 x 4 of 64 x 64 ("256x192x16x4x3x4x1x32x2x3": 1024 threads, one workgroup per CU, a register budget of four waves per SIMD)
+    int const nstg = c.KHO ? c.KHO : 4;   // (an eleventh field, 3 | 4: the LDS stages -- the kernel's NSTG; absent: its default, and the option list of the ten-field strings)
+    bool const w12 = (nmw == 12) && ((c.WI == 4 && c.WJ == 3) || (c.WI == 3 && c.WJ == 4)) && ti == 2 && tj == 2 && c.MINW <= 4;
+    bool const ok = (nmw == 8 || nmw == 4 || w12) && (ti == 4 || ti == 2 || ti == 1) && (tj == 2 || tj == 1) && c.BK >= 4 && c.BK <= 32 && c.BK % 4 == 0 && (c.BK * (c.BI / 4)) % 256 == 0 &&
+                    (c.BK * (c.BJ / 4)) % 256 == 0 && (c.PF == 2 || c.PF == 4) && c.MT == 32 && c.SPLITK == 1 && c.MINW >= 1 && c.MINW <= 8 && (nstg == 3 || nstg == 4) && 4l * nstg * c.BK * (c.BI + c.BJ + 8) <= 160 * 1024;
+    if (!ok || batch != 1 || M % 4 || N % 4 || !allow_big) unsup_err("hip_sgemm: unsupported staging-wave tile " + c.str() + " (8 | 4 multiplying waves of 4 | 2 | 1 x 2 | 1 blocks or 4 x 3 | 3 x 4 of 2 x 2, whole float4 units per staging thread, M and N multiples of 4)");
+    p.big = true; p.kname = "bodahip_sgemm_big_f32";
     p.defs = {"-DBKS=" + std::to_string(c.BK), "-DPF=" + std::to_string(c.PF), "-DTBI=" + std::to_string(c.BI), "-DTBJ=" + std::to_string(c.BJ), "-DWI=" + std::to_string(c.WI),
               "-DWJ=" + std::to_string(c.WJ), "-DMINW=" + std::to_string(c.MINW)};
+    if (c.KHO) p.defs.push_back("-DNSTG=" + std::to_string(nstg));
+    p.cfg.KHO = 0;
     if (char const *x = getenv("BODAHIP_EXTRA_DEFS")) { std::istringstream is(x); string tok; while (is >> tok) p.defs.push_back(tok); }
     return p;
   }
@@ -1037,15 +1042,6 @@ sgemm_split_t plan_sgemm_split(uint32_t M, uint32_t N, uint32_t K, int num_cus) 
   return sp;
 }
 
-// the 256 x 128 form of the staging-wave kernel where its tiles deal out in (nearly) whole rounds -- see sgemm(); "" = not here
-string sgemm_wide_tile(uint32_t M, uint32_t N, uint32_t K, long cus) {
-  if (M % 4 || N % 4 || K < 512 || getenv("BODAHIP_NO_SGEMM_256X128")) return string();
-  if (char const *e = getenv("BODAHIP_SGEMM_BIG")) { if (string(e) == "off") return string(); }   // (the x3x4 tile is a form of the staging-wave kernel only: with the kernel switched off the general kernel's own choice stands)
-  long const t256 = (long)((M + 255) / 256) * ((N + 255) / 256), t128 = (long)((M + 255) / 256) * ((N + 127) / 128);
-  double const eff = (double)t128 / (double)(((t128 + cus - 1) / cus) * cus);
-  return (t256 >= cus && eff >= 0.95) ? string("256x128x8x3x4x1") : string();
-}
-
 // Round 6: the two-level tiling generalised to guillotine cuts -- a list of rectangles [m0, m0 + rows) x [n0, n0 + cols) of c, each ONE launch of one tile form (operands
 // and output addressed through pointer offsets: a and b are k-major, a sub-rectangle is a column range of both).  Every output still belongs to exactly one launch and is
 // one ascending-k chain: bit-identical to the single launch.  10240^3: 3200 tiles of 256 x 128 = 12.5 rounds of 256 CUs -> rows < 8192 (10 rounds) + the last 2048 rows'
@@ -1074,6 +1070,12 @@ bool parse_parts_env(uint32_t M, uint32_t N, uint32_t K, std::vector<sgemm_part_
 // is >= 2 % ahead of the single launch / the row split above.  10240^3 140.4 -> 146.0 TF/s, 5120^3 135.2 -> 139.5 in the list (tools/sgemm_parts_ab.sh).
 struct sgemm_form_t { char const *tile; int bi, bj, s; double r, lone; };   // s workgroups per CU, relative rate r, efficiency of ONE workgroup alone on a CU against its share of a full CU
 static sgemm_form_t const kFormQ = {"256x256x16x2x4x1x1x32x2", 256, 256, 1, 1.0, 1.0}, kFormW = {"256x128x8x3x4x1", 256, 128, 2, 1.0127, 0.82}, kFormS = {kStg64, 64, 64, 4, 0.913, 0.5};
+// Round 7, the 256 x 192 form of twelve multiplying waves (three multiplying waves and one staging wave per SIMD, one workgroup per CU).  Probed beside the other two with
+// the round-7 staging loop (tools/sgemm_rounds_probe.py, K = 6144, 768 tiles each, profiles/r07_probe_sgemm_rounds.txt): 1.046 ms per round of 256 tiles against 1.343 of
+// the 256 x 256 form -- r = 0.75 x 1.343 / 1.046 = 0.963 -- and 2 x 0.676 of the 256 x 128 form at six rounds (r = 0.993).  Where both deal out in whole rounds the
+// 256 x 128 form stays ahead in the model, and the interleaved A/B agrees (12288^3: 152.8 against 152.3 TF/s, inside the arms' spread): the form is taken by tile string
+// (6144^3 = three whole rounds: 152.1 against 143.4 TF/s on the two-level split, profiles/r07_probe_sgemm_w12_ab.txt).  BODAHIP_SGEMM_RW12 = another r (experiments).
+static sgemm_form_t const kFormT = {"256x192x16x4x3x4x1x32x2x3", 256, 192, 1, getenv("BODAHIP_SGEMM_RW12") ? atof(getenv("BODAHIP_SGEMM_RW12")) : 0.963, 1.0};
 static double form_cost(sgemm_form_t const &f, uint32_t rows, uint32_t cols, int cus) {
   long const n = (long)((rows + f.bi - 1) / f.bi) * ((cols + f.bj - 1) / f.bj), per = (long)cus * f.s;
   double const a = (double)f.bi * f.bj / 65536.0, round = f.s * a / f.r;
@@ -1082,6 +1084,20 @@ static double form_cost(sgemm_form_t const &f, uint32_t rows, uint32_t cols, int
   if (f.s >= 4) return (double)n / (double)per * round;    // four staggered workgroups per CU: no rounds to speak of -- 5120^3's rest launch of 2560 tiles (2.5 x 1024) took 2.5 x a 1024-tile launch
   return (double)((n + per - 1) / per) * round;
 }
+// the 256 x 128 form of the staging-wave kernel where its tiles deal out in (nearly) whole rounds -- see sgemm(); "" = not here.  Round 7: where that form is the plan and
+// the 256 x 192 form of twelve multiplying waves (one workgroup per CU) deals out in rounds as full, the form whose probed round time makes the launch shorter.
+string sgemm_wide_tile(uint32_t M, uint32_t N, uint32_t K, long cus) {
+  if (M % 4 || N % 4 || K < 512 || getenv("BODAHIP_NO_SGEMM_256X128")) return string();
+  if (char const *e = getenv("BODAHIP_SGEMM_BIG")) { if (string(e) == "off") return string(); }   // (the x3x4 tile is a form of the staging-wave kernel only: with the kernel switched off the general kernel's own choice stands)
+  long const t256 = (long)((M + 255) / 256) * ((N + 255) / 256), t128 = (long)((M + 255) / 256) * ((N + 127) / 128);
+  double const eff = (double)t128 / (double)(((t128 + cus - 1) / cus) * cus);
+  if (!(t256 >= cus && eff >= 0.95)) return string();
+  long const t192 = (long)((M + 255) / 256) * ((N + 191) / 192);
+  double const eff192 = (double)t192 / (double)(((t192 + cus - 1) / cus) * cus);
+  if (!getenv("BODAHIP_NO_SGEMM_W12") && eff192 >= 0.95 && form_cost(kFormT, M, N, (int)cus) < form_cost(kFormW, M, N, (int)cus)) return string(kFormT.tile);
+  return string(kFormW.tile);
+}
+
 struct sgemm_parts_plan_t { std::vector<sgemm_part_t> parts; double t = 1e30; };
 static sgemm_parts_plan_t plan_parts_rec(uint32_t m0, uint32_t rows, uint32_t n0, uint32_t cols, int cus, double ovh, int depth) {
   sgemm_parts_plan_t best;

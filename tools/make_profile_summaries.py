@@ -18,8 +18,11 @@ def q(db, sql):
 cal = q(os.path.join(src, "calib", "c_results.db"), "select avg(value) from counters_collection where counter_name='FETCH_SIZE' and kernel_name like 'calib_stream_read%'")[0][0]
 known = 1 << 30
 factor = known / (cal * 1024.0)
-res = {"_fetch_size_calibration": {"known_bytes": known, "FETCH_SIZE_KB": cal, "bytes_per_reported_byte": round(factor, 4),
-                                   "note": "16 B/lane coalesced stream; FETCH_SIZE under-reports by this factor on gfx950 (guide: exactly 2)"}}
+res = {}
+if os.path.exists(os.path.join(out, "pmc_summary.json")):   # a partial collection (ONLY=<key>) refreshes its own entries: the others stay as they are on record
+    res = json.load(open(os.path.join(out, "pmc_summary.json")))
+res["_fetch_size_calibration"] = {"known_bytes": known, "FETCH_SIZE_KB": cal, "bytes_per_reported_byte": round(factor, 4),
+                                   "note": "16 B/lane coalesced stream; FETCH_SIZE under-reports by this factor on gfx950 (guide: exactly 2)"}
 hash_fn = os.path.join(src, "kernel_src_hash.txt")
 khash = open(hash_fn).read().strip() if os.path.exists(hash_fn) else ""
 WORK = {"sgemm-ops-full": ("--workload sgemm-ops-full", "bodahip_sgemm%f32"), "alexnet": ("--workload alexnet", "bodahip_%f32"), "nin": ("--workload nin", "bodahip_%f32"),   # (LIKE patterns: sgemm_f32 + sgemm_big_f32; conv_f32 + fc_f32 + k1_quad_f32)
