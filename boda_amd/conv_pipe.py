@@ -443,7 +443,7 @@ CUCL_GLOBAL_KERNEL void %(rtc_func_name)( GASQ float const * const in, // CUCL I
 #endif
   int32_t const n_y = ( ty_hi > ty_lo ) ? ty_hi - ty_lo : 0;
   int32_t const n_x = ( tx_hi > tx_lo ) ? tx_hi - tx_lo : 0;
-  if( %(avg_pool) ) { acc /= (float)( n_y*n_x ); }
+  if( %(avg_pool) ) { acc /= (float)( n_y*n_x ); } else { POOL_MAX_FIX( acc ); }      // (see boda_amd/nhwc.py POOL_MAX_FIX: what fast-math does to a maximum of NaNs or -Inf)
   out[GLOB_ID_1D] = acc;
 }
 """
@@ -1094,7 +1094,8 @@ class ConvPipeFwd:
                 cache = rtc.__dict__.setdefault("_pool_funcs", {})      # one generated function per distinct signature (rtc_func_sigs_map_t)
                 if sig not in cache:
                     inst = instantiate(_POOL_T, pop, f"fwd_pool__{len(cache)}")
-                    inst.src = f"#define BODAHIP_POOL_UNCOND {uncond}\n" + inst.src
+                    from .nhwc import POOL_MAX_FIX
+                    inst.src = POOL_MAX_FIX + f"#define BODAHIP_POOL_UNCOND {uncond}\n" + inst.src
                     rtc.compile([RtcFuncInfo(inst.func_name, inst.src, inst.arg_names, pop)])
                     cache[sig] = inst
                 inst = cache[sig]

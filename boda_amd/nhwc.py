@@ -528,7 +528,15 @@ def xpose_call(arg: str, ref_vn: str, vn: str, ref_dims: Dims, dims: Dims, anno:
 # non-conv forward kernels on channels-last bf16 tensors (full-net driver, boda_amd/conv_pipe.py): semantics of test/rtc/{pool,lrn,relu,
 # copy}.cucl, 8 channels (one 16-byte chunk) per thread.  Arithmetic in fp32, results rounded to bf16 once (RNE) when stored.
 # ------------------------------------------------------------------------------------------------
-FWD_SRC = """
+# The generated sources build with fast-math, which lets the compiler assume that no value is a NaN or an Inf: it drops the -FLT_MAX a maximum starts from (v_max of the
+# taps alone), so a window that holds nothing but NaNs came out as NaN, and one whose largest value is -Inf as -Inf, where the `v > acc` of test/rtc/pool.cucl -- and the
+# oracle -- keeps -FLT_MAX (a NaN beside a number is dropped by v_max itself).  POOL_MAX_FIX puts that back on the BITS of the finished maximum, as an integer between two
+# empty asm statements: the optimiser then sees an integer of unknown origin (a test on the bits of a float it believes finite is folded away: seen with the -Inf half)
+POOL_MAX_FIX = """
+#define POOL_MAX_FIX( A ) { uint32_t pmf_b = __builtin_bit_cast( uint32_t, A ); asm volatile( "" : "+v"( pmf_b ) ); \\
+  if( ( ( pmf_b & 0x7fffffffu ) > 0x7f800000u ) || ( pmf_b == 0xff800000u ) ) { pmf_b = 0xff7fffffu; } asm volatile( "" : "+v"( pmf_b ) ); A = __builtin_bit_cast( float, pmf_b ); }
+"""
+FWD_SRC = POOL_MAX_FIX + """
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 // pooling: one thread per (img, oy, ox, 8 channels); the window is clipped to the plane (padding never takes part; an average divides by
 // the clipped area), taps column by column as the reference sums an average (test/rtc/pool.cucl)
@@ -552,10 +560,12 @@ CUCL_GLOBAL_KERNEL void nhwc_pool( GASQ bf16x8_t const * const in, GASQ bf16x8_t
   }
   float const area = (float)( ( ( yb > ya ) ? yb - ya : 0 ) * ( ( xb > xa ) ? xb - xa : 0 ) );
   bf16x8_t r;
+  if( !avg_pool ) { for( int32_t e = 0; e != 8; ++e ) { POOL_MAX_FIX( acc[e] ); } }
   for( int32_t e = 0; e != 8; ++e ) { r[e] = (__bf16)( avg_pool ? acc[e] / area : acc[e] ); }
   out[i] = r;
 }
-// across-channel LRN (test/rtc/lrn.cucl): out[c] = in[c] * ( k + alpha/local_size * sum_{|d| <= local_size/2} in[c+d]^2 ) ^ -beta.  One thread per
+// across-channel LRN (test/rtc/lrn.cucl): out[c] = in[c] * ( k + alpha/local_size * sum_{-lo <= d <= half} in[c+d]^2 ) ^ -beta with half = local_size/2 and
+// lo = local_size - 1 - half: the last local_size channels entered once channel c + half has (lo == half for an odd size; {c-1 .. c+2} for 4).  One thread per
 // 16-byte chunk (8 channels) of one position; consecutive lanes hold consecutive chunks, so the halo -- the last `half` channels of the chunk
 // below and the first `half` of the chunk above (half = local_size/2 <= 8) -- comes from the neighbouring LANES (wave shuffles of the squares)
 // instead of from memory: every element is loaded once.  Lanes at a position's first / last chunk, and at the wave's edges, take zero / reload.
@@ -564,7 +574,7 @@ CUCL_GLOBAL_KERNEL void nhwc_lrn( GASQ bf16x8_t const * const in, GASQ bf16x8_t 
   // CUCL IX GLOB_ID_1D out n=n wave_local
   uint32_t const i = GLOB_ID_1D;
   bool const live = i < n;
-  int32_t const q = live ? (int32_t)( i % C8 ) : 0, half = local_size / 2, lane = LOC_ID_1D & 63;
+  int32_t const q = live ? (int32_t)( i % C8 ) : 0, half = local_size / 2, lo = (int32_t)local_size - 1 - half, lane = LOC_ID_1D & 63;
   float v[8], sq[24];
   bf16x8_t const mid = live ? in[i] : (bf16x8_t)0;
   for( int32_t e = 0; e != 8; ++e ) { v[e] = (float)mid[e]; sq[8 + e] = v[e]*v[e]; }
@@ -582,7 +592,7 @@ CUCL_GLOBAL_KERNEL void nhwc_lrn( GASQ bf16x8_t const * const in, GASQ bf16x8_t 
   bf16x8_t r;
   for( int32_t e = 0; e != 8; ++e ) {
     float sumsq = 0.0f;
-    for( int32_t d = -8; d <= 8; ++d ) { if( d >= -half && d <= half ) { sumsq += sq[8 + e + d]; } }
+    for( int32_t d = -8; d <= 8; ++d ) { if( d >= -lo && d <= half ) { sumsq += sq[8 + e + d]; } }
     r[e] = (__bf16)( v[e] * powf( k + sumsq * per_elem, -beta ) );
   }
   out[i] = r;
@@ -639,7 +649,7 @@ def ensure_fwd_compiled(rtc) -> None:
 # an average adds it as zero), index arithmetic is multiply-shift, LRN shuffles only the `half` squares it needs from each neighbour lane and takes
 # x^-beta as exp2(-beta * log2 x) (v_log_f32 / v_exp_f32, relative error ~3e-7 against a result stored with 8 bits of mantissa).  Same values as the
 # generic kernels for max pooling (exact) and the same order of additions for averages; LRN within one bf16 rounding (tests/test_gpu_fullnet.py).
-POOL_SPEC_SRC = """
+POOL_SPEC_SRC = POOL_MAX_FIX + """
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 // one thread: XT consecutive outputs along x of one (img, oy, 8 channels); the (XT-1)*SX + KW input columns they touch are loaded once ( x KH rows)
 CUCL_GLOBAL_KERNEL void @NAME@( GASQ bf16x8_t const * const in, GASQ bf16x8_t * const out, uint32_t const n ) {
@@ -681,6 +691,7 @@ CUCL_GLOBAL_KERNEL void @NAME@( GASQ bf16x8_t const * const in, GASQ bf16x8_t * 
     }
     float const area = (float)( ( yb - ya ) * ( xb - xa ) );
     bf16x8_t r;
+    if( !@AVG@ ) { for( int32_t e = 0; e != 8; ++e ) { POOL_MAX_FIX( acc[e] ); } }
     for( int32_t e = 0; e != 8; ++e ) { r[e] = (__bf16)( @AVG@ ? acc[e] / area : acc[e] ); }
     if( ( @OW@ % @XT@ == 0 ) || ( ox < @OW@u ) ) { out[( ( img*@OH@u + oy )*@OW@u + ox )*@C8@u + c] = r; }
   }
@@ -724,7 +735,7 @@ CUCL_GLOBAL_KERNEL void @NAME@( GASQ bf16x8_t const * const in, GASQ bf16x8_t * 
 # reaches HALF channels into each: L1 hits, the neighbouring threads load them as their own).  @LRN_FIRST@ = 1: LRN of every window position (rounded to bf16 as the LRN
 # kernel stores it), then the maximum; 0: maximum of the 8 + 2 HALF channels (rounded to bf16 as the pooling kernel stores it), then LRN.  Same expressions, same order of
 # additions, same roundings as the two kernels run apart: bit-identical output.  Window positions outside the plane are clamped onto it (maximum: duplicates are harmless).
-POOL_LRN_SPEC_SRC = """
+POOL_LRN_SPEC_SRC = POOL_MAX_FIX + """
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 CUCL_GLOBAL_KERNEL __launch_bounds__(256) void @NAME@( GASQ bf16x8_t const * const in, GASQ bf16x8_t * const out, uint32_t const n, float const alpha, float const beta, float const k ) {
   // CUCL IX GLOB_ID_1D out n=n
@@ -779,6 +790,7 @@ CUCL_GLOBAL_KERNEL __launch_bounds__(256) void @NAME@( GASQ bf16x8_t const * con
   for( int32_t t = 0; t != @XT@; ++t ) {
     uint32_t const ox = xg*@XT@u + t;
     bf16x8_t r;
+    for( int32_t e = ( @LRN_FIRST@ ? @HALF@ : 0 ); e != ( @LRN_FIRST@ ? @HALF@ + 8 : 8 + 2*@HALF@ ); ++e ) { POOL_MAX_FIX( acc[t][e] ); }
 #if @LRN_FIRST@
     for( int32_t e = 0; e != 8; ++e ) { r[e] = (__bf16)acc[t][@HALF@ + e]; }
 #else
@@ -806,7 +818,7 @@ CUCL_GLOBAL_KERNEL __launch_bounds__(256) void @NAME@( GASQ bf16x8_t const * con
 # 1 + (KH - SY) / (TY SY) of the LRN kernel's arithmetic (1.5 for the TY = 1 the planner takes: see lrn_pool_lds_rows), one read of the input, one write of the pooled output.  Same expressions, same order, same
 # bf16 rounding between the two ops as the two kernels run apart: bit-identical.  A workgroup kernel: single-device backends only (the multi-device backend shards
 # per-element functions), ConvPipeFwd keeps the pair apart elsewhere.
-LRN_POOL_LDS_SRC = """
+LRN_POOL_LDS_SRC = POOL_MAX_FIX + """
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 CUCL_GLOBAL_KERNEL __launch_bounds__(@TPB@) void @NAME@( GASQ bf16x8_t const * const in, GASQ bf16x8_t * const out, uint32_t const n, float const alpha, float const beta, float const k ) {
   // CUCL IX GRP_ID_1D in n=n
@@ -867,7 +879,7 @@ CUCL_GLOBAL_KERNEL __launch_bounds__(@TPB@) void @NAME@( GASQ bf16x8_t const * c
       }
     }
     bf16x8_t r;
-    for( int32_t e = 0; e != 8; ++e ) { r[e] = (__bf16)acc[e]; }
+    for( int32_t e = 0; e != 8; ++e ) { POOL_MAX_FIX( acc[e] ); r[e] = (__bf16)acc[e]; }
     out[( ( img*@OH@u + oy )*@OW@u + ox )*@C8@u + c] = r;
   }
 }

@@ -5,49 +5,9 @@ MODE=exact (default) | bf16 (hip_conv_bf16 incl. the LDS-patch kernel; mrd < 1e-
      winograd (conv_algo=winograd_all; mrd < 2e-3, the reference's Winograd bound) | k1s (1x1 stride-1 shapes through random k1_stream
      specs; bit-exact)"""
 import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
-
-
-def cases(n, seed, big=False):
-    rng = np.random.default_rng(seed)
-    out = []
-    while len(out) < n:
-        k = int(rng.choice([1, 1, 2, 3, 3, 3, 4, 5, 5, 7, 11]))
-        kh, kw = (k, k) if rng.random() < 0.85 else (k, int(rng.choice([1, 2, 3, 5])))
-        s = int(rng.choice([1, 1, 1, 2, 2, 3, 4]))
-        p = int(rng.integers(0, max(kh, kw) // 2 + 2))
-        h = int(rng.integers(max(kh - 2 * p, 1), 40)); w = int(rng.integers(max(kw - 2 * p, 1), 40))
-        if h + 2 * p < kh or w + 2 * p < kw:
-            continue
-        if big:   # enough tiles for the 128x128 / 64x256 / 96x256 / 128x256 workgroup shapes
-            b = int(rng.choice([16, 33, 64])); h = int(rng.integers(max(kh - 2 * p, 6), 60)); w = int(rng.integers(max(kw - 2 * p, 6), 60))
-        else:
-            b = int(rng.choice([1, 2, 3, 5, 8, 17]))
-        c = int(rng.choice([1, 2, 3, 4, 7, 8, 16, 19, 32, 48, 64])); oc = int(rng.choice([1, 3, 8, 16, 24, 33, 64, 96, 100, 128, 160]))
-        if 2.0 * b * ((h + 2 * p - kh) // s + 1) * ((w + 2 * p - kw) // s + 1) * oc * c * kh * kw > (4e10 if big else 3e9):
-            continue
-        out.append((b, c, h, w, oc, kh, kw, s, p))
-    return out
-
-
-def cases_mode(n, seed, big, mode):
-    """shape filter per MODE: channel counts the bf16 patch kernel takes (multiples of 8) mixed with others; 3x3/s1 only for winograd; 1x1/s1/p0 for k1s"""
-    rng = np.random.default_rng(seed + 7)
-    out = []
-    for sh in cases(40 * n, seed, big):
-        b, c, h, w, oc, kh, kw, s, p = sh
-        if mode == "winograd":
-            sh = (b, c, h, w, oc, 3, 3, 1, min(p, 2))
-            if h + 2 * sh[8] < 3 or w + 2 * sh[8] < 3: continue
-        elif mode == "k1s":
-            sh = (b, c, h, w, oc, 1, 1, 1, 0)
-        elif mode == "bf16" and rng.random() < 0.6:
-            sh = (b, int(rng.choice([16, 24, 32, 40, 64, 96])), h, w, oc, kh, kw, 1 if rng.random() < 0.7 else s, p)
-            if (h + 2 * p - kh) < 0 or (w + 2 * p - kw) < 0: continue
-        out.append(sh)
-        if len(out) == n: break
-    return out
+from fuzz_fwd import conv_cases as cases, conv_mode_cases as cases_mode, k1s_specs   # the generators (tools/fuzz_fwd.py; tests/test_fwd_fuzz_cpu.py checks them)
 
 
 def main():
@@ -64,21 +24,13 @@ def main():
     bad = 0; modes = {}
     mode = os.environ.get("MODE", "exact")
     from boda_amd.digest import SsdsDiff
-    rng = np.random.default_rng(seed + 13)
     worst = 0.0
-    for sh in (cases(n, seed, big) if mode == "exact" else cases_mode(n, seed, big, mode)):
+    shapes = cases(n, seed, big) if mode == "exact" else cases_mode(n, seed, big, mode)
+    specs = k1s_specs(shapes, seed) if mode == "k1s" else [""] * len(shapes)
+    for sh, spec in zip(shapes, specs):
         op = _conv_op(*sh)
-        spec = ""
         if mode == "winograd": rtc.set_tune("conv_algo", "winograd_all")
         if mode == "k1s":
-            wi, wj = [(1, 4), (2, 2), (4, 1), (1, 8), (8, 1), (1, 1), (3, 1), (2, 4)][int(rng.integers(0, 8))]
-            ocb = int(rng.integers(1, 5)); cb = int(rng.integers(1, 3))
-            if (sh[1] + 1) // 2 * cb + 32 * ocb * cb + 30 > 256: cb = 1
-            if (sh[1] + 1) // 2 * cb + 32 * ocb * cb + 30 > 256: ocb = 1
-            spec = f"{wi}x{wj}x{ocb}x{cb}"
-            if rng.random() < 0.5:   # the 16-bytes-per-lane kernel (k1_quad_f32.hip): qWJxOCBxRING, RING a divisor of the K step count; planes of >= 4 pels
-                ks = (sh[1] + 1) // 2; divs = [d for d in range(1, 17) if ks % d == 0]
-                spec = f"q{int(rng.choice([1, 2, 4, 8]))}x{int(rng.integers(1, 4))}x{int(rng.choice(divs))}" + (f"x{int(rng.integers(1, 3))}" if rng.random() < 0.5 else "")
             rtc.set_tune("k1_stream", spec)
         try:
             outs, prc = _run(be, op, 5, tune=OpTune(hip_tile=tile, hip_dtype="bf16" if mode == "bf16" else ""), include_ins=True)

@@ -2,8 +2,9 @@
 """Random LRN -> max-pooling pairs through ConvPipeFwd's default mode (the pair as ONE workgroup kernel through LDS, boda_amd/nhwc.py LRN_POOL_LDS_SRC) against the two kernels
 run apart, bit for bit, and the pairs' pooled outputs against the oracle's pooling of the device's LRN output.   usage: fuzz_lrn_pool_lds.py [n_pipes] [seed]   (GPU box)"""
 import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
+from fuzz_fwd import lrn_pool_pipes   # the generator (tools/fuzz_fwd.py)
 from boda_amd.cnn_op import OpTune
 from boda_amd.conv_pipe import ConvPipe, ConvPipeFwd, PipeOp
 from boda_amd.op import Dims, RtErr
@@ -12,24 +13,16 @@ from oracle import boda_oracle as bo
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-rng = np.random.default_rng(seed)
 rtc = make_rtc("(be=hip)", 0); rtc.init()
 bad = n_pairs = n_lds = 0
-for it in range(n):
-    B = int(rng.choice([1, 2, 3, 5])); C = int(rng.choice([8, 16, 24, 40, 64, 96, 192, 256])); H = int(rng.integers(3, 40)); W = int(rng.integers(3, 40))
+for it, (B, C, H, W, ops) in enumerate(lrn_pool_pipes(n, seed)):
     def pipe():
-        r = np.random.default_rng(seed * 1000 + it)
-        p = ConvPipe("fz", "data", Dims.make("float", img=B, chan=C, y=H, x=W)); k = 0
-        for _ in range(8):
-            kh = int(r.choice([2, 3, 3, 3, 4, 5])); kw = kh if r.random() < 0.8 else int(r.choice([1, 2, 3, 5]))
-            s = int(r.choice([1, 2, 2, 2, 3])); pd = int(r.integers(0, max(1, min(kh, kw)))) if r.random() < 0.4 else 0
-            if kh > H + 2 * pd or kw > W + 2 * pd: continue
-            ls = int(r.choice([3, 5, 5, 7, 9]))
-            try:
-                p.add(PipeOp(f"l{k}", "LRN", "data", f"l{k}", lrn=(ls, float(r.choice([1e-4, 2e-2, 0.5])), float(r.choice([0.75, 0.5])), float(r.choice([1.0, 2.0])))))
-                p.add(PipeOp(f"p{k}", "Pooling", f"l{k}", f"p{k}", kern_sz=(kh, kw), stride=(s, s), in_pad=(pd, pd))); k += 1
-            except RtErr:
-                pass
+        p = ConvPipe("fz", "data", Dims.make("float", img=B, chan=C, y=H, x=W))
+        for o in ops:
+            if o[0] == "Pooling":
+                p.add(PipeOp(o[1], "Pooling", o[2], o[1], kern_sz=o[3], stride=o[4], in_pad=o[5]))
+            else:
+                p.add(PipeOp(o[1], "LRN", o[2], o[1], lrn=o[3]))
         return p
     data = (bo.gen_conv_in(B, C, H, W) * np.float32(3.0)).astype(np.float32)
     res = {}

@@ -2,8 +2,9 @@
 """Random pool / LRN geometries through ConvPipeFwd: the geometry-specialised kernels (channels-last bf16 and the fp32 template's unconditional-taps form) against the
 generic ones and the oracle.   usage: fuzz_pool_lrn.py [n_pipes] [seed]   (GPU box)"""
 import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
+from fuzz_fwd import pool_lrn_pipes   # the generator (tools/fuzz_fwd.py)
 
 
 def main():
@@ -14,24 +15,16 @@ def main():
     from boda_amd.op import Dims, RtErr, UnsupErr
     from boda_amd.rtc import make_rtc
     from oracle import boda_oracle as bo
-    rng = np.random.default_rng(seed)
     rtc = make_rtc("(be=hip)", 0); rtc.init()
     bad = 0; n_ops = 0
-    for it in range(n):
-        B = int(rng.choice([1, 2, 5])); C = int(rng.choice([8, 24, 40, 64, 16, 32])); H = int(rng.integers(3, 30)); W = int(rng.integers(3, 30))
+    for B, C, H, W, ops in pool_lrn_pipes(n, seed):
         def pipe():
-            r = np.random.default_rng(seed * 1000 + it)
-            p = ConvPipe("fz", "data", Dims.make("float", img=B, chan=C, y=H, x=W)); k = 0
-            for _ in range(10):
-                kh = int(r.choice([1, 2, 3, 3, 4, 5, 7])); kw = kh if r.random() < 0.8 else int(r.choice([1, 2, 3, 5]))
-                s = int(r.choice([1, 1, 2, 2, 3])); pd = int(r.integers(0, max(1, min(kh, kw))))
-                if kh > H + 2 * pd or kw > W + 2 * pd: continue
-                try:
-                    p.add(PipeOp(f"p{k}", "Pooling", "data", f"p{k}", kern_sz=(kh, kw), stride=(s, s), in_pad=(pd, pd), avg_pool=int(r.random() < 0.4))); k += 1
-                except RtErr:
-                    pass
-            for j, ls in enumerate((3, 5, 7)):
-                p.add(PipeOp(f"l{j}", "LRN", "data", f"l{j}", lrn=(ls, float(r.choice([1e-4, 2e-2, 0.5])), 0.75, float(r.choice([1.0, 2.0])))))
+            p = ConvPipe("fz", "data", Dims.make("float", img=B, chan=C, y=H, x=W))
+            for o in ops:
+                if o[0] == "Pooling":
+                    p.add(PipeOp(o[1], "Pooling", o[2], o[1], kern_sz=o[3], stride=o[4], in_pad=o[5], avg_pool=o[6]))
+                else:
+                    p.add(PipeOp(o[1], "LRN", o[2], o[1], lrn=o[3]))
             return p
         data = (bo.gen_conv_in(B, C, H, W) * np.float32(3.0)).astype(np.float32)
         for mode in ("nhwc", "f32"):
