@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, fan_out_func_op, sgd_update_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
+from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, bnc_bck_in_func_op, bnc_bck_sums_func_op, bnc_fwd_func_op, bnc_stats_func_op, BNC_MAX_CHUNKS, fan_out_func_op, sgd_update_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
                      pipe_func_args, seed_from_var, SEED_VAR_ARG, bf16_operands)
 from .conv_pipe import ConvPipe, PipeOp
 from .op import Dims, Nda, Op, RtErr, UnsupErr
@@ -411,11 +411,22 @@ class ConvPipeBck:
     supported -- all ResNet-50 has.  It runs as a TRAINING BatchNorm: the convolution (conv_has_relu=0) writes the side var <X>_bn_in; hip_bn_stats reads it and writes
     <bn-tag>_batch_mean / _batch_inv_std and moves the running pair <bn-tag>_mean / _var by bn_maf; hip_bn_fwd writes X, ReLU included.  Backward, BckScale is
     hip_bn_bck_sums (-> <scale-tag>_scale_grad_loss / _bias_grad_loss) and BckBatchNorm hip_bn_bck_in, in place on X_grad_loss, both recomputing the normalised value
-    from <X>_bn_in.  An Eltwise runs as hip_reduce, its gradient as one hip_fan_out.  A solver leaves <bn-tag>_mean / _var alone.  Not on a multi-device backend: init refuses a pipe with a BatchNorm or an Eltwise there before creating anything."""
+    from <X>_bn_in.  An Eltwise runs as hip_reduce, its gradient as one hip_fan_out.  A solver leaves <bn-tag>_mean / _var alone.  Not on a multi-device backend: init refuses a pipe with a BatchNorm or an Eltwise there before creating anything
+    -- unless img_chunks is set.
+    img_chunks=n >= 1 (opt-in; 0 leaves everything as it is, both refusals included): every [BatchNorm, Scale (, ReLU)] run uses the four hip_bnc_*
+    functions with chunks=n -- the per-channel sums in the chunked chain, the batch cut into n img chunks as a multi-device backend cuts it -- and every BckEltwise runs
+    as one hip_split call per output (icix=0, out of in's dims: a bit-for-bit copy by a function that runs on img shards).  Var names, side vars, call tags and order
+    are unchanged.  On one device and on be=cpu any n is allowed, and n=1 leaves today's bits in every node; on `(be=hip,devices=...)` n must be the device count (RtErr
+    before anything is created) and the pipe then runs there: every node but the convolutions' filter / bias gradients (summed per shard, section 3.13) holds the bits of
+    the one-device step with the same n.  fuse_relu_grad, seed_in_var, solver= and, on one device, capture_graph work as before; fuse_filts_biases and grad_operands
+    stay refused on a multi-device backend."""
 
     def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[SgdSolver] = None, bn_maf: float = 0.999, fuse_filts_biases: bool = False,
-                 grad_operands: str = ""):
+                 grad_operands: str = "", img_chunks: int = 0):
         self.rtc = rtc
+        if not isinstance(img_chunks, int) or isinstance(img_chunks, bool) or not 0 <= img_chunks <= BNC_MAX_CHUNKS:
+            raise RtErr(f"ConvPipeBck: img_chunks must be an int, 0 (off) or 1 to {BNC_MAX_CHUNKS}, got {img_chunks!r}")
+        self.img_chunks = img_chunks   # > 0: the training BatchNorm's sums in the chunked chain over this many img chunks, an Eltwise gradient as hip_split copies
         if grad_operands not in ("", "bf16"):
             raise RtErr(f"ConvPipeBck: grad_operands must be '' | 'bf16', got {grad_operands!r}")
         self.grad_operands = grad_operands
@@ -457,11 +468,14 @@ class ConvPipeBck:
         if self.fuse_filts_biases and multi_dev:
             raise UnsupErr("ConvPipeBck.init: fuse_filts_biases=True: hip_bconv_filts_biases sums over the images into two outputs and is not provided on a multi-device "
                            "backend (devices=...); leave the option off there")
+        if self.img_chunks and multi_dev and self.img_chunks != len(rtc.devices):
+            raise RtErr(f"ConvPipeBck.init: img_chunks={self.img_chunks} on {len(rtc.devices)} devices: chunk i of a BatchNorm's sums is device i's img shard, so img_chunks must "
+                        "be the device count")
         bn_runs = self._plan_bn_runs(bp)   # node X -> (BatchNorm op, Scale op, the ReLU behind them or None); every other shape of BatchNorm / Scale is refused here
-        if bn_runs and multi_dev:
+        if bn_runs and multi_dev and not self.img_chunks:
             raise UnsupErr("ConvPipeBck.init: the pipe has a BatchNorm, whose batch statistics sum over the images of the WHOLE batch: not provided on a multi-device backend "
                            "(devices=...); statistics summed across img shards are out of scope")
-        if multi_dev and any(o.type == "BckEltwise" for o in bp.bck_ops()):
+        if multi_dev and not self.img_chunks and any(o.type == "BckEltwise" for o in bp.bck_ops()):
             raise UnsupErr("ConvPipeBck.init: the pipe has an Eltwise, whose gradient (hip_fan_out) takes vars of exactly its op's dims, not img shards: not provided on a "
                            "multi-device backend (devices=...)")
         stats = set(bn_stat_params(bp.cp))
@@ -534,17 +548,27 @@ class ConvPipeBck:
                 x, (bn, sc, relu) = bn_of_tag[o.src.tag]
                 xd = bp.nodes[x]
                 common = {"in": x + BN_IN_SFX, "mean": bn.tag + BN_MEAN_SFX, "inv_std": bn.tag + BN_ISTD_SFX}
+                nc = self.img_chunks
+                stats_op = (lambda d, eps, maf: bnc_stats_func_op(d, eps, maf, nc)) if nc else bn_stats_func_op
+                fwd_op = bnc_fwd_func_op if nc else bn_fwd_func_op
+                sums_op = (lambda d: bnc_bck_sums_func_op(d, nc)) if nc else bn_bck_sums_func_op
+                in_op = bnc_bck_in_func_op if nc else bn_bck_in_func_op
                 if t == "BatchNorm":
-                    calls.append((bn_stats_func_op(xd, bn.eps, self.bn_maf), dict(common, run_mean=bn.tag + "_mean", run_var=bn.tag + "_var")))
+                    calls.append((stats_op(xd, bn.eps, self.bn_maf), dict(common, run_mean=bn.tag + "_mean", run_var=bn.tag + "_var")))
                 elif t == "Scale":
-                    calls.append((bn_fwd_func_op(xd, 1 if relu is not None else 0), dict(common, scale=sc.tag + "_scale", bias=sc.tag + "_bias", out=x)))
+                    calls.append((fwd_op(xd, 1 if relu is not None else 0), dict(common, scale=sc.tag + "_scale", bias=sc.tag + "_bias", out=x)))
                 elif t == "BckScale":
-                    calls.append((bn_bck_sums_func_op(xd), dict(common, out_grad_loss=o.bots[0], scale_grad_loss=o.tops[1], bias_grad_loss=o.tops[2])))
+                    calls.append((sums_op(xd), dict(common, out_grad_loss=o.bots[0], scale_grad_loss=o.tops[1], bias_grad_loss=o.tops[2])))
                 else:
-                    calls.append((bn_bck_in_func_op(xd), dict(common, scale=sc.tag + "_scale", scale_grad_loss=sc.tag + "_scale_grad_loss", bias_grad_loss=sc.tag + "_bias_grad_loss",
+                    calls.append((in_op(xd), dict(common, scale=sc.tag + "_scale", scale_grad_loss=sc.tag + "_scale_grad_loss", bias_grad_loss=sc.tag + "_bias_grad_loss",
                                                               out_grad_loss=o.bots[0], in_grad_loss=o.tops[0])))
                 for fop, args in calls:
                     emit(o.tag, fop, args)
+                continue
+            if t == "BckEltwise" and self.img_chunks:   # one copy per output by a function that runs on img shards: hip_split of ALL of in's channels
+                d = bp.nodes[o.bots[0]]
+                for tp in o.tops:
+                    emit(o.tag, add_pipe_op_annotations(Op({"type": "Split"}, {"in": Nda(d), "outs_0": Nda(d), "outs_num": _u32(1)}), tune)[0], {"in": o.bots[0], "out": tp})
                 continue
             if t == "BckEltwise":
                 emit(o.tag, fan_out_func_op(bp.nodes[o.bots[0]], len(o.tops)), dict({f"outs_{i}": tp for i, tp in enumerate(o.tops)}, **{"in": o.bots[0]}))

@@ -407,6 +407,55 @@ def fan_out_func_op(dims, n: int) -> Op:
     return a
 
 
+# the training BatchNorm over img CHUNKS, a table of its own again (BN_OP_FUNCS is pinned): the hip_bn_* functions' args and formulas, with the
+# three per-channel sums in the chunked chain -- the batch cut into `chunks` pieces as a multi-device backend cuts it over its devices, every chunk's total by the plan of
+# the chunk's own dims, the totals added in chunk order.  The same bits on be=cpu, on one device and on `chunks` devices; chunks=1 is the hip_bn_* chain
+BNC_OP_FUNCS: Dict[str, tuple] = {
+    "BncStats": ("hip_bnc_stats",),
+    "BncFwd": ("hip_bnc_fwd",),
+    "BncBckSums": ("hip_bnc_bck_sums",),
+    "BncBckIn": ("hip_bnc_bck_in",),
+}
+BNC_FUNCS = tuple(v[0] for v in BNC_OP_FUNCS.values())
+BNC_MAX_CHUNKS = 64
+
+
+def _bnc_func_op(twin: Op, t: str, **u32s) -> Op:
+    """The hip_bn_* function op `twin` (checked by its constructor) as the hip_bnc_* function op of type t, with the uint32 scalars given added."""
+    a = Op(dict(twin.str_vals, type=t, func_name=BNC_OP_FUNCS[t][0]), dict(twin.nda_vals))
+    for k, val in u32s.items():
+        a.nda_vals[k] = Nda(None, "uint32_t", (int(val),))
+    return a
+
+
+def _bnc_chunks(t: str, chunks: int) -> int:
+    if not 1 <= int(chunks) <= BNC_MAX_CHUNKS:
+        raise UnsupErr(f"{t}: chunks={chunks}: 1 to {BNC_MAX_CHUNKS} img chunks")
+    return int(chunks)
+
+
+def bnc_stats_func_op(dims, eps: float, maf: float, chunks: int, slab: int = 0) -> Op:
+    """-> hip_bnc_stats: hip_bn_stats' args and formulas on the WHOLE batch's `dims`, S1 and S2 in the chunked chain over `chunks` img chunks (chunk i = images
+    [T * i / chunks, T * (i + 1) / chunks); an empty chunk adds no term); fN, the unbiasing factor and S2's mean are the whole batch's.  slab > 0 forces the slab length of
+    every chunk's plan.  On `(be=hip,devices=...)` chunks must be the device count."""
+    return _bnc_func_op(bn_stats_func_op(dims, eps, maf, slab), "BncStats", chunks=_bnc_chunks("BncStats", chunks))
+
+
+def bnc_fwd_func_op(dims, relu: int) -> Op:
+    """-> hip_bnc_fwd: hip_bn_fwd, whose vars may hold fewer images than `dims` (an img shard): independent per image."""
+    return _bnc_func_op(bn_fwd_func_op(dims, relu), "BncFwd")
+
+
+def bnc_bck_sums_func_op(dims, chunks: int, slab: int = 0) -> Op:
+    """-> hip_bnc_bck_sums: hip_bn_bck_sums with both sums in the chunked chain over `chunks` img chunks (bnc_stats_func_op)."""
+    return _bnc_func_op(bn_bck_sums_func_op(dims, slab), "BncBckSums", chunks=_bnc_chunks("BncBckSums", chunks))
+
+
+def bnc_bck_in_func_op(dims) -> Op:
+    """-> hip_bnc_bck_in: hip_bn_bck_in dividing by the element count of the WHOLE batch, which `dims` gives; its vars may hold fewer images (an img shard)."""
+    return _bnc_func_op(bn_bck_in_func_op(dims), "BncBckIn")
+
+
 ZINP_FLAG = "zero_if_in_non_pos"   # uint32 of a function op: in_grad_loss[e] = in[e] > 0 ? g[e] : +0, hip_zero_if_non_pos's rule applied on the producer's store
 ZINP_FUNCS = ("hip_bconv_in", "hip_spreading", "hip_bck_lrn")   # the functions that write an in_grad_loss with the dims of their op's forward input `in`
 
@@ -566,6 +615,11 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_bn_bck_sums": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("out_grad_loss", "IN"), ("scale_grad_loss", "OUT"), ("bias_grad_loss", "OUT")),
     "hip_bn_bck_in": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("scale", "IN"), ("scale_grad_loss", "IN"), ("bias_grad_loss", "IN"), ("out_grad_loss", "IN"), ("in_grad_loss", "OUT")),
     "hip_fan_out": (("in", "IN"),),
+    # the training BatchNorm over img chunks: the args of their hip_bn_* twins (chunks rides in the op)
+    "hip_bnc_stats": (("in", "IN"), ("mean", "OUT"), ("inv_std", "OUT"), ("run_mean", "INOUT"), ("run_var", "INOUT")),
+    "hip_bnc_fwd": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("scale", "IN"), ("bias", "IN"), ("out", "OUT")),
+    "hip_bnc_bck_sums": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("out_grad_loss", "IN"), ("scale_grad_loss", "OUT"), ("bias_grad_loss", "OUT")),
+    "hip_bnc_bck_in": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("scale", "IN"), ("scale_grad_loss", "IN"), ("bias_grad_loss", "IN"), ("out_grad_loss", "IN"), ("in_grad_loss", "OUT")),
 }
 
 

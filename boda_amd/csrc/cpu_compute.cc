@@ -287,12 +287,28 @@ template <typename TermOfChanF> void bn_chan_sums(bn_op_t const &b, TermOfChanF 
   }
 }
 inline long bn_off(bn_op_t const &b, long c, long e) { long const img = e / b.HW; return (img * b.C + c) * b.HW + (e - img * b.HW); }
+// the chunked chain (hip_bnc_stats / hip_bnc_bck_sums; one chunk, and every hip_bn_* call: bn_chan_sums itself): every non-empty chunk's totals by the plan of the chunk's
+// own dims, its elements numbered from its first image, then ((D_a + D_b) + D_c) + ... in ascending chunk order starting FROM the first.  term_of(cb, off, c): the terms
+// of channel c of the chunk whose first element in the tensors is off
+template <typename TermOfChunkChanF> void bn_chunked_sums(bn_op_t const &b, TermOfChunkChanF term_of, float *S0, float *S1) {
+  if (!(b.bnc && b.chunks > 1)) { bn_chan_sums(b, [&](long c) { return term_of(b, 0L, c); }, S0, S1); return; }
+  std::vector<float> D0((size_t)b.C), D1((size_t)b.C);
+  bool first = true;
+  for (uint32_t i = 0; i < b.chunks; ++i) {
+    bn_op_t const cb = bnc_chunk_op(b.kind == 1 ? "hip_bnc_stats" : "hip_bnc_bck_sums", b, i);
+    if (!cb.B) continue;
+    long const off = bnc_chunk_begin(b.B, b.chunks, i) * b.C * b.HW;
+    bn_chan_sums(cb, [&](long c) { return term_of(cb, off, c); }, first ? S0 : D0.data(), first ? S1 : D1.data());
+    if (!first) for (long c = 0; c < b.C; ++c) { S0[c] = S0[c] + D0[(size_t)c]; S1[c] = S1[c] + D1[(size_t)c]; }
+    first = false;
+  }
+}
 void bn_stats(bn_op_t const &b, float const *in, float *mean, float *inv_std, float *run_mean, float *run_var) {
   std::vector<float> S1((size_t)b.C), S2((size_t)b.C), dummy((size_t)b.C), mu((size_t)b.C);
   float const fN = (float)b.N, omm = 1.0f - b.maf, unb = b.N > 1 ? (float)b.N / (float)(b.N - 1) : 1.0f;
-  bn_chan_sums(b, [&](long c) { return [&b, in, c](long e, float &a0, float &) { a0 = a0 + in[bn_off(b, c, e)]; }; }, S1.data(), dummy.data());
+  bn_chunked_sums(b, [&](bn_op_t const &cb, long off, long c) { return [&cb, in, off, c](long e, float &a0, float &) { a0 = a0 + in[off + bn_off(cb, c, e)]; }; }, S1.data(), dummy.data());
   for (long c = 0; c < b.C; ++c) mu[(size_t)c] = S1[(size_t)c] / fN;
-  bn_chan_sums(b, [&](long c) { float const m = mu[(size_t)c]; return [&b, in, c, m](long e, float &a0, float &) { float const df = in[bn_off(b, c, e)] - m; float const sq = df * df; a0 = a0 + sq; }; }, S2.data(), dummy.data());
+  bn_chunked_sums(b, [&](bn_op_t const &cb, long off, long c) { float const m = mu[(size_t)c]; return [&cb, in, off, c, m](long e, float &a0, float &) { float const df = in[off + bn_off(cb, c, e)] - m; float const sq = df * df; a0 = a0 + sq; }; }, S2.data(), dummy.data());
   for (long c = 0; c < b.C; ++c) {
     float const m = mu[(size_t)c];
     float const var = S2[(size_t)c] / fN;
@@ -323,11 +339,11 @@ void bn_fwd(bn_op_t const &b, float const *in, float *out, float const *mean, fl
   }
 }
 void bn_bck_sums(bn_op_t const &b, float const *in, float const *dy, float const *mean, float const *inv_std, float *sg, float *bg) {
-  bn_chan_sums(b, [&](long c) { float const m = mean[c], is = inv_std[c]; return [&b, in, dy, c, m, is](long e, float &a0, float &a1) {
-    long const o = bn_off(b, c, e); float const df = in[o] - m; float const xh = df * is; float const tm = dy[o] * xh; a0 = a0 + tm; a1 = a1 + dy[o]; }; }, sg, bg);
+  bn_chunked_sums(b, [&](bn_op_t const &cb, long off, long c) { float const m = mean[c], is = inv_std[c]; return [&cb, in, dy, off, c, m, is](long e, float &a0, float &a1) {
+    long const o = off + bn_off(cb, c, e); float const df = in[o] - m; float const xh = df * is; float const tm = dy[o] * xh; a0 = a0 + tm; a1 = a1 + dy[o]; }; }, sg, bg);
 }
 void bn_bck_in(bn_op_t const &b, float const *in, float const *dy, float *dx, float const *mean, float const *inv_std, float const *scale, float const *sg, float const *bg) {
-  float const fN = (float)b.N;
+  float const fN = (float)b.n_glob();   // (the whole batch's, also where the vars hold an img shard of it)
 #pragma omp parallel for schedule(static)
   for (long pl = 0; pl < b.B * b.C; ++pl) {
     long const c = pl % b.C;
@@ -418,7 +434,7 @@ struct cpu_compute_t : public rtc_compute_t {
       (void)op_img_shards_flag(fi.op);   // (likewise; here there is one shard: a flagged call is the unflagged one)
       (void)op_bf16_operands(fi.op);   // (str_val hip_operands: refused where the function has no bf16-operand form)
       if (f->family == kFamSgd) (void)sgd_op_of_op(fi.op);   // (the op must be whole)
-      if (f->family == kFamBn) (void)bn_op_of_op(fi.op);   // (likewise)
+      if (f->family == kFamBn || f->family == kFamBnc) (void)bn_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamBckOp) {
         if (!f->of_type(fi.op.get_type())) rt_err(fn + ": a function of op type " + f->types[0] + ", not " + fi.op.get_type());
         bck_op_args_t const a = bck_op_args(*f, fi.op);
@@ -734,18 +750,27 @@ struct cpu_compute_t : public rtc_compute_t {
   // the training BatchNorm functions and hip_fan_out: the checks of be=hip (csrc/native_run.cc), then the twins above
   void run_bn(op_base_t const &op, map_str_rtc_arg_t const &am) {
     string const fn = op.get_func_name();
-    bn_op_t const b = bn_op_of_op(op);
+    bn_op_t b = bn_op_of_op(op);
     vect_string vars; std::vector<float *> T, Cv;
+    long n_img = -1;   // of the tensor vars of a hip_bnc_* call, which leaves the image count free as on be=hip (it only has to agree between the vars)
     auto var_ptr = [&](string const &an) -> float * {
       string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn);
       if (vd.tn != "float") rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ": fp32 only");
-      if (!(vd == op.get_dims(an))) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + op.get_dims(an).pretty_str());
+      dims_t want = op.get_dims(an);
+      if (b.bnc && want.sz() == 4 && vd.sz() == 4) {
+        if (n_img < 0) n_img = vd.dims(0);
+        if ((long)vd.dims(0) != n_img) rt_err(fn + ": arg '" + an + "' has " + std::to_string(vd.dims(0)) + " images, another arg " + std::to_string(n_img));
+        want[0].sz = vd.dims(0); want.calc_strides();
+      }
+      if (!(vd == want)) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + op.get_dims(an).pretty_str());
       vars.push_back(vn);
       return (float *)must_find(vis, vn).buf.get();
     };
     for (string const &an : b.tens) T.push_back(var_ptr(an));
     for (string const &an : b.chans) Cv.push_back(var_ptr(an));
     bn_check_aliases(fn, b, vars);
+    if (b.bnc && (b.kind == 2 || b.kind == 4)) b = bn_op_on_imgs(b, n_img);
+    else if (b.bnc && n_img != b.B) rt_err(fn + ": the call's vars hold " + std::to_string(n_img) + " images, the op says " + std::to_string(b.B) + ": the sums run over the whole batch (a multi-device backend runs them per shard)");
     switch (b.kind) {
     case 1: bn_stats(b, T[0], Cv[0], Cv[1], Cv[2], Cv[3]); break;
     case 2: bn_fwd(b, T[0], T[1], Cv[0], Cv[1], Cv[2], Cv[3]); break;
@@ -766,7 +791,7 @@ struct cpu_compute_t : public rtc_compute_t {
     (void)op_img_shards_flag(fi.op);   // (likewise)
     double const tb = now_ms();
     if (f.family == kFamSgd) run_sgd_update(fi.op, am);
-    else if (f.family == kFamBn) run_bn(fi.op, am);
+    else if (f.family == kFamBn || f.family == kFamBnc) run_bn(fi.op, am);
     else if (f.family == kFamBckOp) run_bck_op(f, fi.op, am);
     else if (f.family == kFamBconv) run_bck(f, fi.op, am);
     else if (f.family == kFamSgemm) {

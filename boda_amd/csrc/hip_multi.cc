@@ -26,6 +26,9 @@
 //     unless their op carries img_shards=1 (rtc_types.h: op_img_shards_flag).  A flagged call leaves the bits defined in run_on_img_shards below: dropout and the
 //     loss gradient by host arithmetic on a by-value argument, the loss by gathering loss_per_pel to device 0, the two gradients by summing the per-device partials
 //     on device 0 in device order (kernels/bck_ops_f32.hip OP 14) and copying the sum back to every device.  Ordered by events, no host synchronisation;
+//   * hip_bnc_stats / hip_bnc_bck_sums, the training BatchNorm's per-channel sums over img CHUNKS (kernels/bn_f32.hip; their op's chunks must be the device count): chunk
+//     i is device i's shard; the chunk totals are gathered to device 0, added and finalised there and the per-channel results fanned out (run_bnc_on_shards below), with
+//     the same events and helpers as the flagged calls.  hip_bnc_fwd / hip_bnc_bck_in are independent per image (fN is their op's) and run on every shard as they are;
 //   * get_dur(b, e) = the longest of the devices' durations; finish_and_sync() waits for all.
 // The per-GPU process model of bench.py / boda_amd/shard.py (torch.distributed, RCCL weight broadcast) stays: this class is for callers that
 // want one process -- an unmodified Boda with --rtc='(be=hip,devices=...)'.  Devices may repeat (e.g. {0, 0}): the same GPU then holds several
@@ -131,6 +134,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
   std::map<string, string> func_img_sum;   // native functions that reduce over the images (BckConv filter / bias gradients, the softmax loss): refused on a sharded run, with this message
   std::map<string, gen_func_t> func_gen;       // generated functions: their index declaration
   std::map<string, native_func_t const *> func_shards;    // native functions compiled with img_shards=1 (n() > 1): func name -> the op's function, run by run_on_img_shards
+  std::map<string, bn_op_t> func_bnc;          // hip_bnc_stats / hip_bnc_bck_sums (n() > 1): func name -> the op as both backends read it, run by run_bnc_on_shards
   std::vector<hipEvent_t> shard_in_evs;        // per device i > 0: recorded on stream i behind what a flagged call enqueued there; stream 0 waits for it before it gathers
   hipEvent_t shard_out_ev = nullptr;           // recorded on stream 0 behind a flagged call's fan-out; every other stream waits for it before it goes on
   float *shard_ws = nullptr; size_t shard_ws_bytes = 0;   // device 0: the slabs of the per-device partials (the gathered loss_per_pel).  Grow-only, reused by every flagged call
@@ -349,7 +353,16 @@ struct hip_multi_compute_t : public rtc_compute_t {
   void compile(vect_rtc_func_info_t const &func_infos, rtc_compile_opts_t const &opts) override {
     assert_st(init_done);
     for (auto const &fi : func_infos) if (func_native.count(fi.func_name)) rt_err("compile: function '" + fi.func_name + "' already exists");
+    std::map<string, bn_op_t> bnc;   // the chunked sums: chunk i is device i's shard, so the op's chunks must be the device count -- refused before any device compiles anything
+    for (auto const &fi : func_infos) {
+      native_func_t const *row = fi.op.has_func_name() ? find_native_func(fi.op.get_func_name()) : nullptr;
+      if (!row || row->family != kFamBnc || (row->member != 1 && row->member != 3) || n() < 2) continue;
+      bn_op_t const b = bn_op_of_op(fi.op);
+      if (b.chunks != n()) rt_err("multi-device backend: '" + fi.func_name + "' (" + row->name + "): chunks=" + std::to_string(b.chunks) + " on " + std::to_string(n()) + " devices: chunk i of the sums is device i's img shard, so chunks must be the device count");
+      bnc.emplace(fi.func_name, b);
+    }
     for (auto &s : subs) s->compile(func_infos, opts);
+    func_bnc.insert(bnc.begin(), bnc.end());
     string all_src; for (auto const &fi : func_infos) all_src += fi.func_src;
     for (auto const &fi : func_infos) {
       bool const nat = native_kernels_t::is_native_func_name(fi.op.has_func_name() ? fi.op.get_func_name() : string());
@@ -364,8 +377,8 @@ struct hip_multi_compute_t : public rtc_compute_t {
       if (!nat) func_gen[fi.func_name] = scan_gen_func(all_src, fi.func_name);
     }
   }
-  void release_func(string const &fn) override { must_find(func_native, fn); for (auto &s : subs) s->release_func(fn); func_native.erase(fn); func_row.erase(fn); func_gen.erase(fn); func_img_sum.erase(fn); func_shards.erase(fn); }
-  void release_all_funcs() override { for (auto &s : subs) s->release_all_funcs(); func_native.clear(); func_row.clear(); func_gen.clear(); func_img_sum.clear(); func_shards.clear(); }
+  void release_func(string const &fn) override { must_find(func_native, fn); for (auto &s : subs) s->release_func(fn); func_native.erase(fn); func_row.erase(fn); func_gen.erase(fn); func_img_sum.erase(fn); func_shards.erase(fn); func_bnc.erase(fn); }
+  void release_all_funcs() override { for (auto &s : subs) s->release_all_funcs(); func_native.clear(); func_row.clear(); func_gen.clear(); func_img_sum.clear(); func_shards.clear(); func_bnc.clear(); }
 
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
@@ -373,6 +386,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
     if (fit == func_native.end()) rt_err("run: unknown function '" + rfc.rtc_func_name + "' (not compiled, or released)");
     { auto is = func_img_sum.find(rfc.rtc_func_name); if (is != func_img_sum.end()) unsup_err("multi-device backend: '" + rfc.rtc_func_name + "' " + is->second); }
     { auto sh = func_shards.find(rfc.rtc_func_name); if (sh != func_shards.end()) return run_on_img_shards(rfc, *sh->second); }
+    { auto bc = func_bnc.find(rfc.rtc_func_name); if (bc != func_bnc.end()) return run_bnc_on_shards(rfc, bc->second); }
     // hip_sgd_update: params, gradients and momentum history are REPLICATED vars, and an unflagged native call on replicated vars runs on every device (below).  The
     // replicas stay equal by construction: every device holds the same summed gradient after run_on_img_shards' fan-out, the same hyper, the same history, and runs the
     // same kernel -- no cross-device work of its own.  A sharded var (a leading img / M dim) would give every device another piece: refused
@@ -508,6 +522,57 @@ struct hip_multi_compute_t : public rtc_compute_t {
     for (size_t i = 1; i < n(); ++i) if (!(live.size() == 1 && live[0] == i)) copy_on_stream0(sub_ptr(i, rvn), i, sub_ptr(0, rvn), 0, bytes);
     shards_fan_out_end();
     return done();
+  }
+  // ---- hip_bnc_stats / hip_bnc_bck_sums: the chunked chain of kernels/bn_f32.hip with chunk i = device i's shard (compile has checked chunks == n()).  Every device
+  // with images runs the call's chunk piece on its shard, on its own stream -- the slab partials and the chunk's totals D_i ([2][C]) stay in the call's workspace on THAT
+  // device (native_run.cc: bnc_stage / bnc_slot, two by-value args added here).  The totals are copied, in chunk order, into the call's workspace on device 0, where
+  // the cross-chunk step adds them, finalises and writes device 0's replicas of the per-channel vars; those are copied into every other device's.  hip_bnc_stats does
+  // this twice: S1 -> mean, fanned out so that every device's S2 pass reads the whole batch's mean, then S2 -> mean, inv_std and the running pair.  hip_bnc_bck_sums once,
+  // for the pair.  Ordering: run_on_img_shards' three steps and helpers, once per exchange; the workspace on device 0 is touched by stream 0 alone.  No host wait, no
+  // kernel that reads another device's memory.  The call id of device i is that of its first piece
+  uint32_t run_bnc_on_shards(rtc_func_call_t const &rfc, bn_op_t const &b) {
+    string const fn = b.kind == 1 ? "hip_bnc_stats" : "hip_bnc_bck_sums";
+    if (capturing) { capturing = false; for (auto &s : subs) hip_compute_graph_abort(s.get()); unsup_err("multi-device backend: '" + rfc.rtc_func_name + "' (" + fn + ") cannot be captured into a graph: the exchange of its chunk totals between the devices is not part of any one device's capture"); }
+    string svn;
+    multi_var_t const &sv = shards_arg(rfc, fn, "in", true, svn);
+    if ((long)sv.dims.dims(0) != b.B) rt_err(fn + ": the var bound to 'in' holds " + std::to_string(sv.dims.dims(0)) + " images, the op says " + std::to_string(b.B));
+    std::vector<string> cvn(b.chans.size());
+    for (size_t k = 0; k < b.chans.size(); ++k) (void)shards_arg(rfc, fn, b.chans[k].c_str(), false, cvn[k]);
+    uint32_t const T = (uint32_t)b.B;
+    size_t const C = (size_t)b.C;
+    std::vector<uint32_t> ids(n(), kNoCall);
+    std::vector<size_t> live;
+    for (size_t i = 0; i < n(); ++i) if (chunk_begin(T, i + 1) > chunk_begin(T, i)) live.push_back(i);
+    auto piece = [&](size_t i, uint32_t stage, uint32_t slot) {
+      rtc_func_call_t sub = rfc;
+      sub.arg_map["bnc_stage"] = rtc_arg_t(make_scalar_nda<uint32_t>(stage)); sub.arg_map["bnc_slot"] = rtc_arg_t(make_scalar_nda<uint32_t>(slot));
+      uint32_t const id = subs[i]->run(sub);
+      if (ids[i] == kNoCall) ids[i] = id;
+    };
+    auto tots_of = [&](size_t i) {   // the call's totals on device i (the workspace is keyed by the device's own replicas of two per-channel vars)
+      hip_err_chk(hipSetDevice(devs[i]), "hipSetDevice");
+      float *t = nullptr; (void)hip_compute_native(subs[i].get())->bnc_ws(b, sub_ptr(i, cvn[0]), sub_ptr(i, cvn[2]), &t);
+      return t;
+    };
+    std::vector<float *> tots(n(), nullptr);
+    for (size_t i : live) tots[i] = tots_of(i);
+    if (!tots[0]) tots[0] = tots_of(0);
+    // one exchange: the chunk pieces, the gather of `half` (0: the first sum's totals, 1: the second's, 2: both), the cross-chunk step, the fan-out of chans[c0 .. c1)
+    auto exchange = [&](uint32_t chunk_stage, int half, uint32_t cross_stage, size_t c0, size_t c1) {
+      for (size_t k = 0; k < live.size(); ++k) piece(live[k], chunk_stage, (uint32_t)k);
+      shards_gather_begin();
+      for (size_t k = 0; k < live.size(); ++k) if (live[k] != 0) {
+        size_t const off = k * 2 * C + (half == 1 ? C : 0);
+        copy_on_stream0(tots[0] + off, 0, tots[live[k]] + off, live[k], (half == 2 ? 2 * C : C) * 4);
+      }
+      piece(0, cross_stage, (uint32_t)live.size());
+      for (size_t c = c0; c < c1; ++c) for (size_t i = 1; i < n(); ++i) copy_on_stream0(sub_ptr(i, cvn[c]), i, sub_ptr(0, cvn[c]), 0, C * 4);
+      shards_fan_out_end();
+    };
+    if (b.kind == 1) { exchange(1, 0, 4, 0, 1); exchange(2, 1, 5, 0, 4); }
+    else exchange(3, 2, 6, 2, 4);
+    calls.push_back(ids);
+    return (uint32_t)calls.size() - 1;
   }
   // a per-element generated function over vars sharded along their leading dim: see the header of this file
   uint32_t run_generated_on_shards(rtc_func_call_t const &rfc) {

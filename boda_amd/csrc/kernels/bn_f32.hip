@@ -34,7 +34,15 @@
 // 16-byte load, up to four such loads per tensor are issued before the first use.  Otherwise the element path: the same ownership, scalar loads, four in flight.
 // The element-wise kernels follow bodahip_chan_affine: a thread owns one quad of a plane or one element, loads everything before it stores, writes nothing else.
 //
-// -D parameters: KNAME OP, then  1: MODE (0 S1, 1 S2, 2 the bck_sums pair) | 2: FIN (1 stats, 2 bck_sums) | 3: RELU | 5: NOUT.
+// THE CHUNKED CHAIN (hip_bnc_stats, hip_bnc_bck_sums): the batch is cut into img chunks, chunk i = images [T * i / n, T * (i + 1) / n).  Inside a
+// chunk the elements are numbered from the chunk's first image, the slab plan is the plan of the chunk's own dims, and the rules above give the chunk total D_i; the
+// channel's sum is ((D_a + D_b) + D_c) + ... over the non-empty chunks in ascending order STARTING FROM the first.  fN, unb, the N == 1 case and the mean of S2's terms
+// are the whole batch's.  One chunk is the chain above.  Its forms: MODE=3, the S2 partials with mean[c] read from memory (the mean of the WHOLE batch, which the cross-
+// chunk step of S1 wrote); FIN=4, a chunk total (one sum's slab partials in slab order -> one value per channel); XCH=1, the cross-chunk step: the totals [chunk][2][C]
+// added in chunk order, then FIN=3 (mean = S1 / fN alone), FIN=1 (the finalising arithmetic below, verbatim) or FIN=2 (the raw pair).  On several devices chunk i is
+// device i's shard; the totals are copied between the launches, no kernel reads another device's memory.
+//
+// -D parameters: KNAME OP, then  1: MODE (0 S1, 1 S2, 2 the bck_sums pair, 3 S2 with mean from memory) | 2: FIN (1 stats, 2 bck_sums, 3 mean alone, 4 one raw sum), XCH | 3: RELU | 5: NOUT.
 // Host side: bn_slab_plan / bn_op_of_op (rtc_types.h), plan_bn (native_plan.cc), native_kernels_t::bn_call (native_kernels.cc), the argument checks in native_run.cc.
 
 #ifndef __HIPCC_RTC__
@@ -68,7 +76,7 @@ struct bn_args_t {   // must match native_internal.h
 #endif
 #if MODE == 0
 #define TERM(x, d) { a0 = a0 + (x); }
-#elif MODE == 1
+#elif MODE == 1 || MODE == 3
 #define TERM(x, d) { float const df = (x) - mean; float const sq = df * df; a0 = a0 + sq; }
 #else
 #define TERM(x, d) { float const df = (x) - mean; float const xh = df * istd; float const tm = (d) * xh; a0 = a0 + tm; a1 = a1 + (d); }
@@ -88,6 +96,8 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
   float const mean = S1 / p.fN;
 #elif MODE == 2
   float const mean = p.c0[c], istd = p.c1[c];
+#elif MODE == 3
+  float const mean = p.c0[c];
 #endif
   int img, pel;
   { int const e = e0 + 4 * tid; img = e / p.HW; pel = e - img * p.HW; }   // (this chain's first element; may lie behind the slab: then q < nq fails below)
@@ -186,13 +196,33 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
 }
 
 #elif OP == 2
+#ifndef XCH
+#define XCH 0
+#endif
 extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
   int const c = (int)(blockIdx.x * 256 + threadIdx.x);   // one owner per channel
   if (c >= p.C) return;
+#if XCH   // the cross-chunk step: p.ws holds the totals [chunk][2][C] of the nslabs non-empty chunks, in chunk order
+  float const *const pa = p.ws + c;
+  long const st = 2L * p.C;
+#if FIN == 3
+  float A = pa[0];
+  for (int i = 1; i < p.nslabs; ++i) A = A + pa[i * st];
+#else
+  float const *const pb = pa + p.C;
+  float A = pa[0], Bv = pb[0];
+  for (int i = 1; i < p.nslabs; ++i) { A = A + pa[i * st]; Bv = Bv + pb[i * st]; }
+#endif
+#elif FIN == 4   // a chunk total: one sum's slab partials
+  float const *const pa = p.ws + (long)c * p.nslabs;
+  float A = pa[0];
+  for (int i = 1; i < p.nslabs; ++i) A = A + pa[i];
+#else
   float const *const pa = p.ws + (long)c * p.nslabs;
   float const *const pb = pa + (long)p.C * p.nslabs;
   float A = pa[0], Bv = pb[0];
   for (int i = 1; i < p.nslabs; ++i) { A = A + pa[i]; Bv = Bv + pb[i]; }
+#endif
 #if FIN == 1
   float const mean = A / p.fN;
   float const var = Bv / p.fN;
@@ -207,6 +237,10 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
   float const v2 = p.omm * uv;
   p.w0[c] = mean; p.w1[c] = istd;
   p.w2[c] = m1 + m2; p.w3[c] = v1 + v2;
+#elif FIN == 3
+  p.w0[c] = A / p.fN;
+#elif FIN == 4
+  p.w0[c] = A;
 #else
   p.w0[c] = A; p.w1[c] = Bv;
 #endif

@@ -10,8 +10,8 @@
 namespace bodahip {
 
 // the family (func_family_t of rtc_types.h) selects the handler (native_run.cc, native_kernels.cc: check_compile_time); handlers switch on the member, never on the name
-inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn"};
-// members.  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn: the kind of bn_op_t
+inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc"};
+// members.  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc: the kind of bn_op_t
 enum { kConvF32 = 0, kConvAlias = 1, kConvBf16 = 2, kConvWinograd = 3 };            // (the alias: hip_conv's contract without its fused pooling and filts_km)
 enum { kBconvIn = 1, kBconvBiases = 2, kBconvFilts = 3, kBconvFiltsBiases = 4 };   // (4 is opt-in: never one of the bare op's three calls)
 enum { kOpPoolYx = 1, kOpSpreading = 2, kOpLrnSb = 3, kOpBckLrn = 4, kOpZeroIfNonPos = 5, kOpSoftmax = 6, kOpSmGradAndLoss = 7, kOpSumLossOverImgs = 8, kOpReduce = 9,
@@ -115,6 +115,13 @@ inline constexpr native_func_t kNativeFuncs[] = {
    refused_on_devices("(a training BatchNorm's data gradient) divides by the element count of the WHOLE batch, which an img shard does not know")},
   {"hip_fan_out", kFamBn, 5, nullptr, {"FanOut"}, {{"in", kIn}}, {}, kVarOutsBehind, 0, {}, kBeHip | kBeCpu,
    refused_on_devices("(hip_fan_out) takes vars of exactly its op's dims, not img shards: the training BatchNorm functions and the Eltwise gradient run on one device")},
+  // the training BatchNorm over img CHUNKS (a family of its own; the args of the hip_bn_* twins).  hip_bnc_stats / hip_bnc_bck_sums carry `chunks` and sum in the chunked
+  // chain (kernels/bn_f32.hip); on several devices chunk i is device i's shard and the chunk totals cross the devices (csrc/hip_multi.cc: run_bnc_on_shards, a dispatch
+  // on this family).  hip_bnc_fwd / hip_bnc_bck_in are independent per image once fN is the whole batch's, which their op's dims give: they run on shards as they are
+  {"hip_bnc_stats", kFamBnc, 1, nullptr, {"BncStats"}, {{"in", kIn}, {"mean", kOut}, {"inv_std", kOut}, {"run_mean", kInOut}, {"run_var", kInOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_bnc_fwd", kFamBnc, 2, nullptr, {"BncFwd"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"scale", kIn}, {"bias", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_bnc_bck_sums", kFamBnc, 3, nullptr, {"BncBckSums"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"out_grad_loss", kIn}, {"scale_grad_loss", kOut}, {"bias_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_bnc_bck_in", kFamBnc, 4, nullptr, {"BncBckIn"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"scale", kIn}, {"scale_grad_loss", kIn}, {"bias_grad_loss", kIn}, {"out_grad_loss", kIn}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
 };
 #undef BODAHIP_CONV_ARGS
 

@@ -117,8 +117,9 @@ struct bn_args_t { // must match kernels/bn_f32.hip
 static_assert(sizeof(bn_args_t) == 13 * 8 + 8 * 8 + 8 + 9 * 4 + 5 * 4, "bn_args_t is declared with this layout by kernels/bn_f32.hip");
 // the kernels of one call in launch order: op 1 (a sum over slabs; mode 0 S1, 1 S2, 2 the bck_sums pair), 2 (the finalising step; fin 1 stats, 2 bck_sums), 3 fwd, 4 bck_in, 5 fan_out
 struct bn_launch_t { plan_t p; int op = 0; };
-struct bn_plan_t { std::vector<bn_launch_t> ls; double algo_bytes = 0; size_t ws_bytes = 0; };
+struct bn_plan_t { std::vector<bn_launch_t> ls; double algo_bytes = 0; size_t ws_bytes = 0, ws_part = 0; };   // ws_part (the chunked chain): floats of slab partials in front of the totals
 bn_plan_t plan_bn(bn_op_t const &b);
+plan_t bn_kernel_plan(int op, char const *kname, vect_string const &defs);   // one specialisation of kernels/bn_f32.hip (plan_bn's entries are these)
 string bn_plan_desc(bn_op_t const &b, bn_plan_t const &bp);
 
 struct rows_args_t { // must match kernels/conv_nhwc_rows_bf16.hip

@@ -58,7 +58,7 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
     sgd_op_t const so = sgd_op_of_op(fi.op);
     (void)get_kernel(impl, host, plan_sgd_update(so.elems).p);
   } break;
-  case kFamBn:   // the op must be whole; the code objects of all the call's launches are built NOW, so that a first run inside a graph capture finds them
+  case kFamBn: case kFamBnc:   // the op must be whole; the code objects of all the call's launches are built NOW, so that a first run inside a graph capture finds them
     for (bn_launch_t const &l : plan_bn(bn_op_of_op(fi.op)).ls) (void)get_kernel(impl, host, l.p);
     break;
   case kFamBconv:   // BckConv's gradients: the op must carry the geometry
@@ -890,11 +890,18 @@ void native_kernels_t::sgd_update(int n, sgd_member_t const *m, float const *hyp
 // ---- the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip): one to three launches per call, in plan_bn's order.  The slab partials of the two
 // reducing functions live in a workspace of the CALL (keyed by its pointers, like the K-slice workspaces: calls of a parallel graph run at the same time), allocated on
 // the call's first run; one launch writes it, the next launch of the same call reads it
-void native_kernels_t::bn_call(bn_op_t const &b, float *const *tens, float *const *chans) {
-  bn_plan_t const bp = plan_bn(b);
+// what every launch of a call shares.  fN, unb (and, where a kernel asks, N == 1) are the WHOLE batch's even where b is a chunk's or an img shard's op
+static bn_args_t bn_args_of(bn_op_t const &b) {
   bn_args_t a; memset(&a, 0, sizeof(a));
+  long const Ng = b.n_glob();
   a.B = (int)b.B; a.C = (int)b.C; a.HW = (int)b.HW; a.N = (int)b.N; a.slab = (int)b.slab; a.nslabs = (int)b.nslabs;
-  a.fN = (float)b.N; a.eps = b.eps; a.maf = b.maf; a.omm = 1.0f - b.maf; a.unb = b.N > 1 ? (float)b.N / (float)(b.N - 1) : 1.0f;
+  a.fN = (float)Ng; a.eps = b.eps; a.maf = b.maf; a.omm = 1.0f - b.maf; a.unb = Ng > 1 ? (float)Ng / (float)(Ng - 1) : 1.0f;
+  return a;
+}
+void native_kernels_t::bn_call(bn_op_t const &b, float *const *tens, float *const *chans) {
+  if (b.bnc && b.chunks > 1) { bnc_call(b, tens, chans); return; }
+  bn_plan_t const bp = plan_bn(b);
+  bn_args_t a = bn_args_of(b);
   uintptr_t al = 0;
   for (size_t i = 0; i < b.tens.size(); ++i) al |= (uintptr_t)tens[i];
   bool const aligned = (al & 15) == 0;
@@ -942,6 +949,60 @@ void native_kernels_t::bn_call(bn_op_t const &b, float *const *tens, float *cons
   }
   last_launch.kernel = bp.ls[0].p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = grid0; last_launch.block = 256;
   last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
+}
+// ---- the chunked chain of hip_bnc_stats / hip_bnc_bck_sums (kernels/bn_f32.hip).  The call's workspace -- keyed and allocated like bn_call's --
+// holds the slab partials of ONE chunk at a time (the launches of a call are ordered among themselves) and behind them the totals [chunk][2][C].  bnc_call is the whole
+// call on one device; bnc_chunk / bnc_cross are its two pieces, which a multi-device backend runs on the devices' shards and on device 0 (csrc/hip_multi.cc)
+float *native_kernels_t::bnc_ws(bn_op_t const &b, void const *key_in, void const *key_chan, float **tots) {
+  bn_plan_t const bp = plan_bn(b);
+  string const key = "ksl:bnc:" + std::to_string(b.kind) + ":" + std::to_string((uintptr_t)key_in) + ":" + std::to_string((uintptr_t)key_chan) + ":" + std::to_string(bp.ws_bytes);
+  auto it = impl->ktabs.find(key);
+  if (it == impl->ktabs.end()) {
+    if (host->nh_capturing()) rt_err("graph capture: the chunk workspace of this call is not allocated yet -- run the call list once before capturing it");
+    void *dev = nullptr;
+    call_ws_make_room(impl, host, bp.ws_bytes);
+    hip_err_chk(hipMalloc(&dev, bp.ws_bytes), "hipMalloc(BatchNorm chunk workspace)"); impl->call_ws_bytes += bp.ws_bytes;
+    it = impl->ktabs.emplace(key, dev).first;
+  }
+  *tots = (float *)it->second + bp.ws_part;
+  return (float *)it->second;
+}
+// one chunk: cb its op (bnc_chunk_op), mode 0 S1 | 3 S2 around mean[c] read from c0 | 2 the bck_sums pair (c0 mean, c1 inv_std); in / dy the chunk's first image.  The
+// slab partials go to `part`, the chunk's totals to tot[0 .. C) (S1, or the first of the pair) or tot[C .. 2C) (S2, or the second of the pair)
+void native_kernels_t::bnc_chunk(bn_op_t const &cb, int mode, float const *in, float const *dy, float const *c0, float const *c1, float *part, float *tot) {
+  if (!cb.B) return;
+  bn_args_t a = bn_args_of(cb);
+  a.in = in; a.dy = dy; a.c0 = c0; a.c1 = c1; a.ws = part;
+  a.quads = ((((uintptr_t)in | (uintptr_t)dy) & 15) == 0 && (cb.HW & 3) == 0) ? 1 : 0;
+  a.step_img = (int)(kBnSlabUnit / cb.HW); a.step_pel = (int)(kBnSlabUnit % cb.HW);
+  void *params[] = {&a};
+  uint32_t const grid = (uint32_t)(cb.C * cb.nslabs);
+  hip_err_chk(host->nh_launch(get_kernel(impl, host, bn_kernel_plan(1, "bodahip_bn_sum", {"-DMODE=" + std::to_string(mode)})).func, grid, 1, 256, params), "hipModuleLaunchKernel(bn chunk sum)");
+  if (mode == 2) { a.w0 = tot; a.w1 = tot + cb.C; } else a.w0 = tot + (mode == 3 ? cb.C : 0);
+  hip_err_chk(host->nh_launch(get_kernel(impl, host, bn_kernel_plan(2, "bodahip_bn_fin", {mode == 2 ? "-DFIN=2" : "-DFIN=4"})).func, (uint32_t)((cb.C + 255) / 256), 1, 256, params), "hipModuleLaunchKernel(bn chunk total)");
+  last_launch.kernel = "bodahip_bn_sum"; last_launch.cfg = tile_cfg_t(); last_launch.grid = grid; last_launch.block = 256; last_launch.flops = 0;
+  last_launch.algo_bytes = 4.0 * (double)cb.elems * (mode == 2 ? 2 : 1);
+}
+// the cross-chunk step over the totals of `live` non-empty chunks, in chunk order: fin 3 -> mean (chans[0]); 1 -> mean, inv_std and the running pair (chans[0 .. 3]); 2 ->
+// the raw pair (chans[2], chans[3])
+void native_kernels_t::bnc_cross(bn_op_t const &b, int fin, float *tots, int live, float *const *chans) {
+  bn_args_t a = bn_args_of(b);
+  a.N = (int)b.n_glob(); a.ws = tots; a.nslabs = live;
+  if (fin == 2) { a.w0 = chans[2]; a.w1 = chans[3]; } else { a.w0 = chans[0]; a.w1 = chans[1]; a.w2 = chans[2]; a.w3 = chans[3]; }
+  void *params[] = {&a};
+  hip_err_chk(host->nh_launch(get_kernel(impl, host, bn_kernel_plan(2, "bodahip_bn_fin", {"-DFIN=" + std::to_string(fin), "-DXCH=1"})).func, (uint32_t)((b.C + 255) / 256), 1, 256, params), "hipModuleLaunchKernel(bn cross-chunk)");
+}
+void native_kernels_t::bnc_call(bn_op_t const &b, float *const *tens, float *const *chans) {
+  float *tots = nullptr;
+  float *const part = bnc_ws(b, tens[0], chans[2], &tots);
+  string const fn = b.kind == 1 ? "hip_bnc_stats" : "hip_bnc_bck_sums";
+  std::vector<bn_op_t> cbs; std::vector<long> offs;   // the non-empty chunks, ascending: their ops and their first element in the tensors
+  for (uint32_t i = 0; i < b.chunks; ++i) { bn_op_t const cb = bnc_chunk_op(fn, b, i); if (cb.B) { cbs.push_back(cb); offs.push_back(bnc_chunk_begin(b.B, b.chunks, i) * b.C * b.HW); } }
+  int const live = (int)cbs.size();
+  auto chunks_of = [&](int mode) { for (int k = 0; k < live; ++k) bnc_chunk(cbs[(size_t)k], mode, tens[0] + offs[(size_t)k], mode == 2 ? tens[1] + offs[(size_t)k] : nullptr, mode ? chans[0] : nullptr, mode == 2 ? chans[1] : nullptr, part, tots + (long)k * 2 * b.C); };
+  if (b.kind == 1) { chunks_of(0); bnc_cross(b, 3, tots, live, chans); chunks_of(3); bnc_cross(b, 1, tots, live, chans); }
+  else { chunks_of(2); bnc_cross(b, 2, tots, live, chans); }
+  last_launch.algo_bytes = plan_bn(b).algo_bytes;
 }
 void native_kernels_t::shard_sum(float const *slabs, float *out, int nslabs, long stride, long n) {
   bck_plan_t const bp = plan_shard_sum(nslabs, stride, n);

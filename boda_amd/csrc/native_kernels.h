@@ -142,6 +142,12 @@ struct native_kernels_t {
   void shard_sum(float const *slabs, float *out, int nslabs, long stride, long n);
   // hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out on raw device pointers (kernels/bn_f32.hip): tens / chans in bn_op_t's arg order
   void bn_call(bn_op_t const &b, float *const *tens, float *const *chans);
+  // hip_bnc_stats / hip_bnc_bck_sums with more than one chunk, the chunked chain: the whole call on one device, and its pieces -- the call's workspace (slab partials of
+  // one chunk; *tots: the totals [chunk][2][C] behind them), one chunk's totals, the cross-chunk step -- which a multi-device backend runs per device (csrc/hip_multi.cc)
+  void bnc_call(bn_op_t const &b, float *const *tens, float *const *chans);
+  float *bnc_ws(bn_op_t const &b, void const *key_in, void const *key_chan, float **tots);
+  void bnc_chunk(bn_op_t const &cb, int mode, float const *in, float const *dy, float const *c0, float const *c1, float *part, float *tot);
+  void bnc_cross(bn_op_t const &b, int fin, float *tots, int live, float *const *chans);
   void conv_winograd(float const *filts, float const *biases, float const *in, float *out, conv_geom_t const &g, int out_ctot, int out_coff);
 
   // tuning overrides ("" clears): key "sgemm_tile" / "conv_tile" -> "BIxBJxBKxWIxWJ[xMINW[xSPLITK[xMT]]]"; key "k1_stream" -> "off" | "WIxWJxOCBxCB[xMINW]";

@@ -1425,14 +1425,25 @@ sgd_plan_t plan_sgd_update(std::vector<long> const &elems) {
 
 // ---- the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip): the kernels of one call in launch order.  The slab plan itself is bn_slab_plan's
 // (rtc_types.h), shared with be=cpu; nothing here depends on the device.  algo_bytes counts every tensor of the call once
+plan_t bn_kernel_plan(int op, char const *kname, vect_string const &defs) {
+  plan_t p; p.bn = true; p.kname = kname; p.defs = {"-DOP=" + std::to_string(op)};
+  for (string const &d : defs) p.defs.push_back(d);
+  return p;
+}
 bn_plan_t plan_bn(bn_op_t const &b) {
   bn_plan_t r;
-  auto add = [&](int op, char const *kname, vect_string const &defs) {
-    bn_launch_t l; l.op = op; l.p.bn = true; l.p.kname = kname; l.p.defs = {"-DOP=" + std::to_string(op)};
-    for (string const &d : defs) l.p.defs.push_back(d);
-    r.ls.push_back(l);
-  };
+  auto add = [&](int op, char const *kname, vect_string const &defs) { bn_launch_t l; l.op = op; l.p = bn_kernel_plan(op, kname, defs); r.ls.push_back(l); };
   double const T = 4.0 * (double)b.elems, Cb = 4.0 * (double)b.C;
+  if (b.bnc && b.chunks > 1) {   // the chunked chain (one chunk: the twin's own launches below).  The kernels in the order a chunk and then the call needs them
+    if (b.kind == 1) {
+      add(1, "bodahip_bn_sum", {"-DMODE=0"}); add(2, "bodahip_bn_fin", {"-DFIN=4"}); add(2, "bodahip_bn_fin", {"-DFIN=3", "-DXCH=1"});
+      add(1, "bodahip_bn_sum", {"-DMODE=3"}); add(2, "bodahip_bn_fin", {"-DFIN=1", "-DXCH=1"}); r.algo_bytes = T + 4 * Cb;
+    } else { add(1, "bodahip_bn_sum", {"-DMODE=2"}); add(2, "bodahip_bn_fin", {"-DFIN=2"}); add(2, "bodahip_bn_fin", {"-DFIN=2", "-DXCH=1"}); r.algo_bytes = 2 * T + 4 * Cb; }
+    long ms = 1;
+    for (uint32_t i = 0; i < b.chunks; ++i) ms = std::max(ms, bnc_chunk_op("hip_bnc", b, i).nslabs);
+    r.ws_part = (size_t)(2 * b.C * ms); r.ws_bytes = (r.ws_part + (size_t)(2 * b.C) * b.chunks) * sizeof(float);   // the slab partials of one chunk at a time, then the totals [chunk][2][C]
+    return r;
+  }
   switch (b.kind) {
   case 1: add(1, "bodahip_bn_sum", {"-DMODE=0"}); add(1, "bodahip_bn_sum", {"-DMODE=1"}); add(2, "bodahip_bn_fin", {"-DFIN=1"}); r.algo_bytes = T + 4 * Cb; break;
   case 2: add(3, "bodahip_bn_fwd", {"-DRELU=" + std::to_string(b.relu)}); r.algo_bytes = 2 * T + 4 * Cb; break;
@@ -1446,13 +1457,20 @@ bn_plan_t plan_bn(bn_op_t const &b) {
 }
 string bn_plan_desc(bn_op_t const &b, bn_plan_t const &bp) {
   string s;
+  bool const chunked = b.bnc && b.chunks > 1;
   for (bn_launch_t const &l : bp.ls) {
-    long const grid = l.op == 1 ? b.C * b.nslabs : l.op == 2 ? (b.C + 255) / 256 : 0;
+    long const grid = l.op == 1 ? (chunked ? 0 : b.C * b.nslabs) : l.op == 2 ? (b.C + 255) / 256 : 0;   // (a chunk's sum has its own grid: C x the chunk's slabs)
     s += (s.empty() ? "" : " | ") + l.p.kname;
     if (grid) s += " grid=" + std::to_string(grid) + " block=256";
     for (size_t i = 1; i < l.p.defs.size(); ++i) s += " " + l.p.defs[i];
   }
-  if (b.kind == 1 || b.kind == 3) s += " | slab=" + std::to_string(b.slab) + " slabs=" + std::to_string(b.nslabs);
+  if (b.bnc && b.chunks) {
+    s += " | chunks=" + std::to_string(b.chunks);
+    for (uint32_t i = 0; i < b.chunks; ++i) {
+      bn_op_t const cb = bnc_chunk_op("hip_bnc", b, i);
+      s += " | chunk " + std::to_string(i) + ": " + (cb.B ? "imgs=" + std::to_string(cb.B) + " slab=" + std::to_string(cb.slab) + " slabs=" + std::to_string(cb.nslabs) : string("empty"));
+    }
+  } else if (b.kind == 1 || b.kind == 3) s += " | slab=" + std::to_string(b.slab) + " slabs=" + std::to_string(b.nslabs);
   return s;
 }
 

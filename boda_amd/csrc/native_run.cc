@@ -261,7 +261,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     sgd_plan_t const sp = plan_sgd_update(sgd_op_of_op(op).elems);
     if (plan_out) *plan_out = sp.p.kname + " grid=" + std::to_string(sp.grid) + " block=" + std::to_string(sp.block) + " tens=" + std::to_string(sp.blk0.size()) + " chunk=" + std::to_string(kSgdChunk);
     return arch.empty() ? 0 : compile_plan(sp.p, arch, &log).size();
-  } else if (fam == kFamBn) {   // (kernels/bn_f32.hip: every launch of the call, and the slab plan)
+  } else if (fam == kFamBn || fam == kFamBnc) {   // (kernels/bn_f32.hip: every launch of the call, and the slab plan)
     bn_op_t const b = bn_op_of_op(op);
     bn_plan_t const bp = plan_bn(b);
     if (plan_out) *plan_out = bn_plan_desc(b, bp);
@@ -698,6 +698,10 @@ struct native_kernels_t::call_t {
   void run_bn() {
     // every var must have exactly the dims the op gives its arg (the sums run over the whole batch: no img shards), and no two args may be one var except where
     // kernels/bn_f32.hip allows in-place use
+    // The hip_bnc_* functions (kFamBnc) leave the image count of their tensor vars free, as every function that runs on img shards does: fN stays the op's.  A whole
+    // hip_bnc_stats / hip_bnc_bck_sums call still needs the op's batch; a multi-device backend runs them in pieces, named by two by-value uint32 args it adds to the
+    // call (csrc/hip_multi.cc): bnc_stage = 1 S1 | 2 S2 | 3 the pair: the totals of THIS device's shard, one chunk, into slot bnc_slot of the call's totals here;
+    // 4 mean | 5 statistics | 6 the raw pair: the cross-chunk step over the first bnc_slot slots
     bn_op_t const b = bn_op_of_op(fi.op);
     vect_string vars; std::vector<float *> tens, chans;
     auto var_ptr = [&](string const &an) -> float * {
@@ -709,7 +713,27 @@ struct native_kernels_t::call_t {
     for (string const &an : b.chans) chans.push_back(var_ptr(an));
     bn_check_aliases(fn, b, vars);
     while (chans.size() < 5) chans.push_back(nullptr);
-    nk.bn_call(b, tens.data(), chans.data());
+    if (!b.bnc) { nk.bn_call(b, tens.data(), chans.data()); return; }
+    auto by_val = [&](char const *an) -> long {
+      auto it = am.find(an);
+      if (it == am.end()) return -1;
+      if (!it->second.is_valid() || it->second.is_var() || !it->second.v->rp_elems() || it->second.v->dims.tn != "uint32_t" || it->second.v->dims.sz() != 0) rt_err(fn + ": '" + an + "' must be a by-value uint32_t scalar of the call");
+      return (long)*(uint32_t const *)it->second.v->rp_elems();
+    };
+    long const stage = by_val("bnc_stage"), slot = by_val("bnc_slot");
+    if (b.kind == 2 || b.kind == 4) { nk.bn_call(bn_op_on_imgs(b, n_img), tens.data(), chans.data()); return; }
+    if (stage < 0) {
+      if (n_img != b.B) rt_err(fn + ": the call's vars hold " + std::to_string(n_img) + " images, the op says " + std::to_string(b.B) + ": the sums run over the whole batch (a multi-device backend runs them per shard)");
+      nk.bn_call(b, tens.data(), chans.data());
+      return;
+    }
+    bool const st_ok = b.kind == 1 ? (stage == 1 || stage == 2 || stage == 4 || stage == 5) : (stage == 3 || stage == 6);
+    if (!st_ok || b.chunks < 2 || slot < 0 || slot > (long)b.chunks || (stage <= 3 && slot == (long)b.chunks)) rt_err(fn + ": bnc_stage=" + std::to_string(stage) + " bnc_slot=" + std::to_string(slot) + ": not a piece of this call");
+    float *tots = nullptr;
+    float *const part = nk.bnc_ws(b, chans[0], chans[2], &tots);   // (keyed by per-channel vars: a device without images has no tensor pointer to tell calls apart)
+    if (stage <= 3) {
+      nk.bnc_chunk(bnc_op_of_imgs(fn, b, n_img), stage == 1 ? 0 : stage == 2 ? 3 : 2, tens[0], stage == 3 ? tens[1] : nullptr, stage == 1 ? nullptr : chans[0], stage == 3 ? chans[1] : nullptr, part, tots + slot * 2 * b.C);
+    } else nk.bnc_cross(b, stage == 4 ? 3 : stage == 5 ? 1 : 2, tots, (int)slot, chans.data());
   }
   void run_bck_op() {
     // every var must have the dims the op gives its arg -- except the number of images, which only has to agree between the vars (a multi-device backend runs these
@@ -792,7 +816,7 @@ void native_kernels_t::run(native_func_t const &f, rtc_func_info_t const &fi, ma
   case kFamBconv: c.run_bconv(); break;
   case kFamBckOp: c.run_bck_op(); break;
   case kFamSgd: c.run_sgd(); break;
-  case kFamBn: c.run_bn(); break;
+  case kFamBn: case kFamBnc: c.run_bn(); break;
   }
 }
 

@@ -129,7 +129,7 @@ struct op_base_t {
 };
 typedef std::shared_ptr<op_base_t> p_op_base_t;
 // ---- the op flags of a native function.  Which function takes which flag is a column of the one table, native_funcs.h (included at the end of this file), which defines:
-enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn };   // selects the handler
+enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc };   // selects the handler
 enum : unsigned { kFlagZinp = 1, kFlagSeedVar = 2, kFlagImgShards = 4, kFlagNhwcResidual = 8 };
 struct op_flag_name_t { char const *name; unsigned flag; };
 constexpr op_flag_name_t kOpFlagNames[] = {{"img_shards", kFlagImgShards}, {"seed_from_var", kFlagSeedVar}, {"zero_if_in_non_pos", kFlagZinp}, {"nhwc_residual", kFlagNhwcResidual}};
@@ -230,9 +230,14 @@ constexpr long kBnMinSlab = 4096;      // ... and never shorter than this: a sho
 constexpr long kBnTargetWgs = 512;     // two workgroups per CU on a fixed 256 CUs (not the device's count: the plan must not depend on the device)
 constexpr long kBnMaxSlabs = 4096;     // per channel (only a forced slab length can ask for more)
 constexpr int kFanOutMax = 8;
+constexpr uint32_t kBncMaxChunks = 64;  // of a hip_bnc_stats / hip_bnc_bck_sums call
 struct bn_op_t {
   int kind = 0;                  // 1 stats, 2 fwd, 3 bck_sums, 4 bck_in, 5 fan_out
+  bool bnc = false;              // a hip_bnc_* function (kFamBnc): the sums in the chunked chain, the image count of the call's vars free where the function is per image
+  uint32_t chunks = 0, forced = 0;   // bnc, kinds 1, 3: img chunks of the batch; the forced slab length every chunk's plan gets (0: the planner's)
   long B = 0, C = 0, HW = 0, N = 0;   // N = B * HW: the elements of one channel
+  long Nglob = 0;                // > 0: the WHOLE batch's N where B / N are a chunk's or a shard's (fN, unb and the N == 1 case are global)
+  long n_glob() const { return Nglob ? Nglob : N; }
   long elems = 0;                // of the whole tensor
   long slab = 0, nslabs = 0;     // kinds 1, 3: elements of a slab of a channel's flat (img, pel) range, slabs per channel
   float eps = 0.f, maf = 0.f; uint32_t relu = 0; int nout = 0;
@@ -251,12 +256,24 @@ inline void bn_slab_plan(string const &fn, long C, long N, uint32_t forced, long
   nslabs = std::max<long>(1, (N + slab - 1) / slab);
   if (nslabs > kBnMaxSlabs) unsup_err(fn + ": slab=" + std::to_string(slab) + " cuts a channel of " + std::to_string(N) + " elements into " + std::to_string(nslabs) + " slabs, more than " + std::to_string(kBnMaxSlabs));
 }
+// chunk i of `chunks` of a batch of T images holds images [T * i / chunks, T * (i + 1) / chunks), as csrc/hip_multi.cc cuts a batch over its devices
+inline long bnc_chunk_begin(long T, uint32_t chunks, uint32_t i) { return (long)((uint64_t)T * i / chunks); }
+// the op of a call whose vars hold n_img images of the op's batch (an img shard): the whole batch's N stays beside it
+inline bn_op_t bn_op_on_imgs(bn_op_t const &b, long n_img) { bn_op_t c = b; c.Nglob = b.n_glob(); c.B = n_img; c.N = n_img * b.HW; c.elems = c.N * b.C; return c; }
+// the op of ONE chunk of n_img images of a chunked call b: its own slab plan under the call's forced length, the whole batch's N beside it.  No images: no plan
+inline bn_op_t bnc_op_of_imgs(string const &fn, bn_op_t const &b, long n_img) {
+  bn_op_t c = bn_op_on_imgs(b, n_img); c.chunks = 1; c.slab = c.nslabs = 0;
+  if (c.B) bn_slab_plan(fn, b.C, c.N, b.forced, c.slab, c.nslabs);
+  return c;
+}
+inline bn_op_t bnc_chunk_op(string const &fn, bn_op_t const &b, uint32_t i) { return bnc_op_of_imgs(fn, b, bnc_chunk_begin(b.B, b.chunks, i + 1) - bnc_chunk_begin(b.B, b.chunks, i)); }
 inline bn_op_t bn_op_of_op(op_base_t const &op) {
   string const fn = op.has_func_name() ? op.get_func_name() : string();
   bn_op_t r;
   r.kind = native_func_member(fn, kFamBn);
+  if (!r.kind) { r.kind = native_func_member(fn, kFamBnc); r.bnc = r.kind != 0; }
   if (!r.kind) rt_err("'" + fn + "' is none of " + native_family_names(kFamBn));
-  string const type = native_func_type(kFamBn, r.kind);
+  string const type = native_func_type(r.bnc ? kFamBnc : kFamBn, r.kind);
   if (!op.has_type() || op.get_type() != type) rt_err(fn + ": a function of op type " + type + ", not " + (op.has_type() ? op.get_type() : string("?")));
   refuse_flags_not_taken(op, fn, "the function");
   auto f32 = [&](string const &an) { if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'"); p_nda_t const &v = op.get(an); if (v->dims.tn != "float" || v->dims.sz() != 0 || !v->rp) rt_err(fn + ": '" + an + "' is not a float scalar"); return *static_cast<float const *>(v->rp); };
@@ -289,7 +306,12 @@ inline bn_op_t bn_op_of_op(op_base_t const &op) {
   }
   if (r.kind == 1) { r.eps = f32("eps"); r.maf = f32("maf"); if (!(r.eps >= 0.0f)) rt_err(fn + ": eps must not be negative"); }
   if (r.kind == 2) { r.relu = u32("relu"); if (r.relu > 1) rt_err(fn + ": relu must be 0 | 1"); }
-  if (r.kind == 1 || r.kind == 3) bn_slab_plan(fn, r.C, r.N, u32("slab"), r.slab, r.nslabs);
+  if (r.bnc && (r.kind == 1 || r.kind == 3)) {   // the chunked chain: every non-empty chunk gets the plan of its own dims, under the same forced length
+    r.chunks = u32("chunks"); r.forced = u32("slab");
+    if (r.chunks < 1 || r.chunks > kBncMaxChunks) unsup_err(fn + ": chunks=" + std::to_string(r.chunks) + ": 1 to " + std::to_string(kBncMaxChunks) + " img chunks");
+    for (uint32_t i = 0; i < r.chunks; ++i) (void)bnc_chunk_op(fn, r, i);   // (refuses a forced slab that cuts a chunk's channel into too many)
+    if (r.chunks == 1) { bn_op_t const cb = bnc_chunk_op(fn, r, 0); r.slab = cb.slab; r.nslabs = cb.nslabs; }   // (one chunk: the twin's chain and launches)
+  } else if (r.kind == 1 || r.kind == 3) bn_slab_plan(fn, r.C, r.N, u32("slab"), r.slab, r.nslabs);
   return r;
 }
 // the var-level refusals of a call, the same text on both backends: `vars` = the var bound to every tensor arg followed by every per-channel arg (bn_op_t's order)

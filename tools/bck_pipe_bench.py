@@ -10,6 +10,7 @@ and the share of the step each native function takes (sums of the backend's per-
     python tools/bck_pipe_bench.py --sgd [--repeats 3] [--out profiles/r13_sgd_update.txt]
     python tools/bck_pipe_bench.py --nets resnet50 --batch 32 [--limit 900] [--out profiles/r14_resnet50_step.txt]
     python tools/bck_pipe_bench.py --grad-operands bf16 --nets resnet50 --batch 32 [--repeats 3] [--limit 900] [--out profiles/r16_step_bf16.txt]
+    python tools/bck_pipe_bench.py --img-chunks 2 --nets resnet50 --batch 32 [--devices 0:0] [--repeats 3] [--limit 900] [--out profiles/r17_resnet50_chunks.txt]
 
 --fuse-relu-grad: the same step both ways in ONE process -- ConvPipeBck() and ConvPipeBck(fuse_relu_grad=True), each on a backend instance of its own with the same
 params and inputs -- after the usual warm-up, in --repeats alternating blocks of --runs steps.  Per net two JSON lines ("way": "unfused" / "fused": step ms as the median
@@ -40,6 +41,14 @@ tensors_per_call is sgd_packed against sgd_per_tensor in the same run; no figure
 --devices d0:d1:...: the plain step on the multi-device backend `(be=hip,devices=...)`: the batch sharded on img, the five functions that are not independent per image
 run with img_shards=1.  Step ms is the longest of the devices' times; a call's share counts the time its device-side launches took, not the
 cross-device copies behind them.  No figure for more than one physical GPU is recorded yet.
+
+--img-chunks N: ConvPipeBck(img_chunks=...), the training BatchNorm's sums in the chunked chain and the Eltwise gradients as hip_split copies.
+Legs, ONE PROCESS EACH (a multi-device backend and a one-device backend do not share a process here), in --repeats alternating blocks -- every block starts every leg's
+process anew, runs --warmup steps and times --runs: "default" (the step as it is), "chunks1" (img_chunks=1: the same kernels and bits; expected inside the blocks'
+spread), "chunksN" (img_chunks=N on one device) and, with --devices d0:d1:... (N must be the device count), "devices" (the step on `(be=hip,devices=...)`).  Per leg one
+JSON line (step ms as the median over all blocks, the block medians, images/s, the call count, the loss, the per-function share) and one with the quotients against
+"default" of the same run.  No figure is required.  Devices that are shards of ONE physical GPU (0:0) run the exchange and say NOTHING about scaling: the shards
+share the GPU, and step ms is the longest of the shards' times.  On several devices a chunked call's share counts its first device-side piece only.
 
 --nets resnet50: the fourth net, with its 53 BatchNorm + Scale runs as training BatchNorms (hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in) and its 16 Eltwise
 gradients as hip_fan_out.  The step must end with a finite loss (the child fails otherwise).  Its first step compiles some 150 specialisations: give it --limit 900.
@@ -250,7 +259,7 @@ def sgd_ab(net, batch, runs, warmup, repeats):
         w["drv"].release(); w["rtc"].close()
 
 
-def one_net(net, batch, runs, warmup, devices=""):
+def one_net(net, batch, runs, warmup, devices="", img_chunks=0, raw=False):
     import numpy as np
     from boda_amd import conv_pipe
     from boda_amd.bck_pipe import ConvPipeBck, add_bck_ops
@@ -259,7 +268,7 @@ def one_net(net, batch, runs, warmup, devices=""):
     bp = add_bck_ops(cp)
     rtc = make_rtc(f"(be=hip,devices={devices})" if devices else "(be=hip)", 0)   # (several devices: the driver flags the five functions that are not independent per image)
     rtc.init()
-    drv = ConvPipeBck(rtc)
+    drv = ConvPipeBck(rtc, img_chunks=img_chunks)
     drv.init(bp)
     rng = np.random.default_rng(0)
     rtc.copy_nda_to_var("data", rng.uniform(-1, 1, cp.nodes["data"].sizes).astype(np.float32))
@@ -277,9 +286,43 @@ def one_net(net, batch, runs, warmup, devices=""):
         raise SystemExit(f"{net}: the step ended with the loss {loss}")
     tot = sum(share.values())
     step = statistics.median(ms)
+    if raw:   # one block of one leg of --img-chunks: the parent puts the blocks together
+        print(json.dumps({"ms": ms, "share_ms": share, "calls": len(drv.calls()), "loss": loss}), flush=True)
+        drv.release(); rtc.close()
+        return
     print(json.dumps({"net": net, "batch": batch, **({"devices": devices} if devices else {}), "calls": len(drv.calls()), "step_ms": round(step, 3), "imgs_per_s": round(batch / (step * 1e-3), 1), "loss": round(loss, 4),
                       "share": {k: round(v / tot, 4) for k, v in sorted(share.items(), key=lambda kv: -kv[1])}}), flush=True)
     drv.release(); rtc.close()
+
+
+def chunks_ab(a, net):
+    """The legs of --img-chunks, one process per leg and block, alternating -> the JSON lines (None after a failure: nothing more is started on the GPU)."""
+    legs = [("default", 0, ""), ("chunks1", 1, ""), (f"chunks{a.img_chunks}", a.img_chunks, "")] + ([("devices", a.img_chunks, a.devices)] if a.devices else [])
+    acc = {name: {"ms": [], "blocks": [], "share": {}, "calls": 0, "loss": None} for name, _, _ in legs}
+    for rep in range(a.repeats):
+        for name, n, devs in legs:
+            cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", net, "--batch", str(a.batch), "--runs", str(a.runs), "--warmup", str(a.warmup),
+                   "--img-chunks", str(n), "--raw"] + (["--devices", devs] if devs else [])
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                print(f"{net} {name}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
+                return None
+            rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+            w = acc[name]
+            w["ms"] += rec["ms"]; w["blocks"].append(round(statistics.median(rec["ms"]), 3)); w["calls"] = rec["calls"]; w["loss"] = rec["loss"]
+            print(f"{net} block {rep} {name}: {w['blocks'][-1]} ms", file=sys.stderr, flush=True)
+            for k, v in rec["share_ms"].items():
+                w["share"][k] = w["share"].get(k, 0.0) + v
+    lines = []
+    for name, n, devs in legs:
+        w = acc[name]; tot = sum(w["share"].values()); step = statistics.median(w["ms"])
+        lines.append(json.dumps({"net": net, "batch": a.batch, "leg": name, "img_chunks": n, **({"devices": devs} if devs else {}), "calls": w["calls"], "step_ms": round(step, 3),
+                                 "block_medians_ms": w["blocks"], "imgs_per_s": round(a.batch / (step * 1e-3), 1), "loss": round(w["loss"], 4),
+                                 "share": {k: round(v / tot, 4) for k, v in sorted(w["share"].items(), key=lambda kv: -kv[1])}}))
+    base = statistics.median(acc["default"]["ms"])
+    lines.append(json.dumps(dict({"net": net}, **{f"{name}_over_default": round(statistics.median(acc[name]["ms"]) / base, 4) for name, _, _ in legs[1:]},
+                                 note="shards of one physical GPU say nothing about scaling" if a.devices and len(set(a.devices.split(":"))) == 1 else "")))
+    return lines
 
 
 def main(argv=None):
@@ -297,13 +340,19 @@ def main(argv=None):
     ap.add_argument("--grad-operands", default="", choices=["", "bf16"], help="A/B: the fp32 step, the fp32 step with the fused filter + bias call, and the step with bf16 gradient operands, in one process")
     ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad / --graph / --sgd: alternating blocks of --runs steps per way")
     ap.add_argument("--devices", default="", help="e.g. 0:1:2:3: the plain step on the multi-device backend (be=hip,devices=...), batch sharded on img")
+    ap.add_argument("--img-chunks", type=int, default=0, help="A/B, one process per leg: the default step, img_chunks=1, img_chunks=N on one device and, with --devices, on the multi-device backend")
+    ap.add_argument("--raw", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--child", default="")
     a = ap.parse_args(argv)
+    if a.img_chunks and not a.child and (a.graph or a.fuse_relu_grad or a.sgd or a.fuse_filts_biases or a.grad_operands):
+        ap.error("--img-chunks is a comparison of its own: run it without the other A/Bs")
+    if a.img_chunks and a.devices and a.img_chunks != len(a.devices.split(":")):
+        ap.error("--img-chunks with --devices: chunk i is device i's shard, so N must be the device count")
     if a.devices and (a.graph or a.fuse_relu_grad or a.sgd or a.fuse_filts_biases or a.grad_operands):
         ap.error("--devices times the plain step: graph capture is not provided on several devices, and the fused and the solver A/B run on one")
     if a.graph + a.fuse_relu_grad + a.sgd + a.fuse_filts_biases + bool(a.grad_operands) > 1:
         ap.error("--graph, --fuse-relu-grad, --fuse-filts-biases, --grad-operands and --sgd are five comparisons: run them one at a time")
-    a.out = a.out or os.path.join(ROOT, "profiles", "r16_step_bf16.txt" if a.grad_operands else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r17_resnet50_chunks.txt" if a.img_chunks else "r16_step_bf16.txt" if a.grad_operands else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
     if a.child:
         if a.grad_operands:
             return operands_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, a.grad_operands)
@@ -313,9 +362,16 @@ def main(argv=None):
             return graph_ab(a.child, a.batch, a.runs, a.warmup, a.repeats)
         if a.fuse_filts_biases:
             return fuse_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, "fuse_filts_biases")
-        return fuse_ab(a.child, a.batch, a.runs, a.warmup, a.repeats) if a.fuse_relu_grad else one_net(a.child, a.batch, a.runs, a.warmup, a.devices)
+        return fuse_ab(a.child, a.batch, a.runs, a.warmup, a.repeats) if a.fuse_relu_grad else one_net(a.child, a.batch, a.runs, a.warmup, a.devices, a.img_chunks, a.raw)
     lines = []
     for net in a.nets.split(","):
+        if a.img_chunks:
+            got = chunks_ab(a, net)
+            if got is None:
+                return 1
+            lines += got
+            print("\n".join(got), flush=True)
+            continue
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", net, "--batch", str(a.batch), "--runs", str(a.runs), "--warmup", str(a.warmup)]
         cmd += ["--fuse-relu-grad", "--repeats", str(a.repeats)] if a.fuse_relu_grad else []
         cmd += ["--fuse-filts-biases", "--repeats", str(a.repeats)] if a.fuse_filts_biases else []
@@ -330,7 +386,7 @@ def main(argv=None):
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
         print("\n".join(lines[-4:] if (a.graph or a.sgd or a.grad_operands) else lines[-3:] if (a.fuse_relu_grad or a.fuse_filts_biases) else lines[-1:]), flush=True)
     with open(a.out, "w") as f:
-        extra = f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
+        extra = f" --img-chunks {a.img_chunks}{' --devices ' + a.devices if a.devices else ''} --repeats {a.repeats}" if a.img_chunks else f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
         f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 
