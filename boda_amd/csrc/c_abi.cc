@@ -21,7 +21,6 @@ void hip_compute_compile_code_object(rtc_compute_t *rtc, void const *code, size_
 p_rtc_compute_t make_hip_multi_compute(std::vector<int> const &device_ordinals);
 rtc_compute_t *hip_multi_sub(rtc_compute_t *rtc, uint32_t i);
 uint32_t hip_multi_num_devices(rtc_compute_t *rtc);
-extern char const *const k_src_gemm_conv_f32_ptr;
 }
 
 struct bodahip_ctx { p_rtc_compute_t rtc; };
@@ -190,7 +189,7 @@ int bodahip_compile_offline(const char *src_or_opts, const char *native_template
   if (native_template && native_template[0]) {
     if (string(native_template) != "gemm_conv_f32") rt_err(string("unknown native kernel template '") + native_template + "'");
     vect_string opts; std::istringstream is(S(src_or_opts, "opts")); string tok; while (is >> tok) opts.push_back(tok);
-    code = hiprtc_compile(k_src_gemm_conv_f32_ptr, "offline_native", S(arch, "arch"), opts, &log, use_cache != 0);
+    code = hiprtc_compile(find_kernel_source(native_template)->text, "offline_native", S(arch, "arch"), opts, &log, use_cache != 0, kernel_headers());
   } else {
     string src = (add_prelude ? cucl_prelude() : string()) + S(src_or_opts, "src");
     code = hiprtc_compile(src, "offline_cucl", S(arch, "arch"), {"-ffast-math"}, &log, use_cache != 0);

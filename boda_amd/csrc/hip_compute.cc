@@ -85,9 +85,11 @@ string default_cache_dir() {
 
 // compile `src` for `arch` with `opts`; returns the code object.  Uses (and fills) an on-disk cache of code objects so
 // that run-time specialisation costs one hiprtc call per (source, options, arch) per machine, not per process.
-std::vector<char> hiprtc_compile(string const &src, string const &name, string const &arch, vect_string const &opts, string *log_out, bool use_cache) {
+std::vector<char> hiprtc_compile(string const &src, string const &name, string const &arch, vect_string const &opts, string *log_out, bool use_cache,
+                                 std::vector<kernel_text_t> const &headers) {
   string key = src + "\n//" + arch;
   for (auto const &o : opts) key += " " + o;
+  for (auto const &h : headers) key += string("\n//#include ") + h.name + "\n" + h.text;   // (a header edit misses the cache as a source edit does)
   int rtc_major = 0, rtc_minor = 0; hiprtcVersion(&rtc_major, &rtc_minor);
   key += " hiprtc" + std::to_string(rtc_major) + "." + std::to_string(rtc_minor);
   char hbuf[40]; snprintf(hbuf, sizeof(hbuf), "%016llx", (unsigned long long)fnv1a(key));
@@ -109,7 +111,8 @@ std::vector<char> hiprtc_compile(string const &src, string const &name, string c
       fprintf(lf, "compiled %.0f ms: %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what.c_str()); fclose(lf); } } } } miss_log;
   miss_log.what = name + " [" + arch + "]"; for (auto const &o : opts) miss_log.what += " " + o;
   hiprtcProgram prog;
-  hiprtc_err_chk(hiprtcCreateProgram(&prog, src.c_str(), (name + ".hip").c_str(), 0, nullptr, nullptr), "hiprtcCreateProgram");
+  std::vector<char const *> htexts, hnames; for (auto const &h : headers) { htexts.push_back(h.text); hnames.push_back(h.name); }
+  hiprtc_err_chk(hiprtcCreateProgram(&prog, src.c_str(), (name + ".hip").c_str(), (int)headers.size(), htexts.data(), hnames.data()), "hiprtcCreateProgram");
   vect_string all = {"--offload-arch=" + arch, "-O3", "-std=c++17"};
   all.insert(all.end(), opts.begin(), opts.end());
   std::vector<char const *> copts; for (auto const &o : all) copts.push_back(o.c_str());

@@ -80,16 +80,8 @@
 #define SEEDVAR 0
 #endif
 
-struct bck_ops_args_t {   // must match native_internal.h
-  float const *p0; float const *p1; float const *p2; float const *p3;   // inputs, in the function's arg order
-  float *o0; float *o1;                                                 // outputs, in the function's arg order
-  long n;                                                               // threads that have work
-  int B, C, HW, n4;                                                     // images, channels, pels of a plane; OP 5: float4 quads
-  float f0, f1, f2, f3;                                                 // LRN: alpha / local_size, beta, k, ((2 * -beta) * alpha) / local_size; OP 10: f0 = scale
-  float const *p4; float const *p5; float const *p6; float const *p7;   // OP 9: inputs 4 .. 7; OP 10 with SEEDVAR: p4 = the uint32 word added to seed
-  unsigned seed, thresh;                                                // OP 10
-  int run, wide, off;                                                   // OP 11, 12: floats of one image's channel range, of one image of the wider tensor, offset of the range; OP 14: wide = the slab stride, B = the slabs
-};
+#include "kernel_args.h"      // bck_ops_args_t
+#include "device_prelude.h"
 
 constexpr float kFltMax = 3.402823466e+38f, kFltMin = 1.175494351e-38f;
 
@@ -242,7 +234,6 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
 }
 
 #elif OP == 5
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) {
   long const id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= p.n) return;
@@ -303,7 +294,6 @@ extern "C" __global__ __launch_bounds__(64) void KNAME(bck_ops_args_t const p) {
 }
 
 #elif OP == 9
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define RED_INS(T, ix) \
   T v = (T)0.0f + ((T const *)p.p0)[ix]; v = v + ((T const *)p.p1)[ix]; \
   if (NIN > 2) v = v + ((T const *)p.p2)[ix]; if (NIN > 3) v = v + ((T const *)p.p3)[ix]; if (NIN > 4) v = v + ((T const *)p.p4)[ix]; \
@@ -322,7 +312,6 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
 }
 
 #elif OP == 10
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float drop1(float x, unsigned ix, unsigned seed, bck_ops_args_t const &p) {
   unsigned h = ix + seed;
   h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
@@ -348,7 +337,6 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
 }
 
 #elif OP == 11 || OP == 12
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) {
   long const id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= p.n) return;
@@ -363,7 +351,6 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
 }
 
 #elif OP == 13
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float affine1(float x, float a, float b) {
   float v = x * a;
   v = v + b;
@@ -392,7 +379,6 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
 }
 
 #elif OP == 14
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define SUM_SLABS(T, ix) \
   T v = ((T const *)p.p0)[ix]; \
   for (int d = 1; d < p.B; ++d) v = v + ((T const *)(p.p0 + (long)d * p.wide))[ix];

@@ -37,22 +37,10 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
+#include "kernel_args.h"      // bconv_fb_args_t
+#include "device_prelude.h"
 
-struct bconv_fb_args_t {   // must match native_internal.h
-  float const *g; float const *x; float *df; float *db;   // out_grad_loss, in, filts_grad_loss, biases_grad_loss
-  float *ws; long slab_elems;                             // SLICED: ksl slabs of slab_elems = OC*NJ + OC floats
-  int B, C, H, W, OC, OH, OW;
-  int tiles_i, tiles_j, ksl, kt_per;
-  unsigned g_bytes, x_bytes;
-};
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 constexpr int kOOB = (int)0x80000000;   // byte offset beyond any num_records (tensors are < 2^31 bytes): the hardware returns 0
-__device__ __forceinline__ rsrc_t make_rsrc(void const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ float bload1(rsrc_t r, int byte_off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0)); }
 
 constexpr int kNT = WI * WJ * 64;
 constexpr int kTI = BI / (WI * 32), kTJ = BJ / (WJ * 32);

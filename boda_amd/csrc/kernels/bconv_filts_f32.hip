@@ -22,23 +22,10 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
+#include "kernel_args.h"      // bconv_args_t
+#include "device_prelude.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 constexpr int kOOB = (int)0x80000000;   // byte offset beyond any num_records (tensors are < 2^31 bytes): the hardware returns 0
-__device__ __forceinline__ rsrc_t make_rsrc(void const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ float bload1(rsrc_t r, int byte_off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0)); }
-
-struct bconv_args_t {   // must match native_internal.h
-  float const *a; float const *b; float *d;   // filts gradient: a = out_grad_loss, b = in, d = filts_grad_loss; bias gradient: a = out_grad_loss, d = biases_grad_loss
-  float *ws; long ws_slab;                    // K slices: tile tickets first, the slabs from ws + ws_slab on
-  int B, C, H, W, OC, OH, OW;
-  int tiles_i, tiles_j, ksl, kt_per;
-  unsigned a_bytes, b_bytes, d_bytes;
-  float const *zin;                           // (the data gradient's: kernels/bconv_in_f32.hip -DZINP=1)
-};
 
 #if BIAS_ONLY
 extern "C" __global__ __launch_bounds__(256) void KNAME(bconv_args_t const p) {

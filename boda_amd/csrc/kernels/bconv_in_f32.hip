@@ -28,20 +28,10 @@
 #define ZINP 0
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-constexpr int kOOB = (int)0x80000000;   // byte offset beyond any num_records (tensors are < 2^31 bytes): the hardware returns 0
-__device__ __forceinline__ rsrc_t make_rsrc(float const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ float bload1(rsrc_t r, int byte_off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0)); }
+#include "kernel_args.h"      // bconv_args_t
+#include "device_prelude.h"
 
-struct bconv_args_t {   // must match native_internal.h
-  float const *a; float const *b; float *d;   // bconv_in: a = filts, b = out_grad_loss, d = in_grad_loss
-  float *ws; long ws_slab;
-  int B, C, H, W, OC, OH, OW;
-  int tiles_i, tiles_j, ksl, kt_per;
-  unsigned a_bytes, b_bytes, d_bytes;
-  float const *zin;   // ZINP: the forward input (in_grad_loss's dims)
-};
+constexpr int kOOB = (int)0x80000000;   // byte offset beyond any num_records (tensors are < 2^31 bytes): the hardware returns 0
 
 constexpr int kTY = (KH + SY - 1) / SY, kTX = (KW + SX - 1) / SX, kTT = kTY * kTX;
 constexpr int kNT = WI * WJ * 64;

@@ -51,22 +51,8 @@
 
 #pragma clang fp contract(off) reassociate(off)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct bn_args_t {   // must match native_internal.h
-  float const *in; float const *dy;                                   // the tensors read
-  float const *c0; float const *c1; float const *c2; float const *c3; float const *c4;   // per-channel values read, in the function's arg order
-  float *out;                                                         // the tensor written (OP 3: out, OP 4: in_grad_loss)
-  float *w0; float *w1; float *w2; float *w3;                         // per-channel values written, in the function's arg order
-  float *ws;                                                          // slab partials: [2][C][nslabs]
-  float *outs[8];                                                     // OP 5
-  long n;                                                             // OP 3 .. 5: threads that have work
-  int B, C, HW, N;                                                    // images, channels, pels of a plane, B * HW
-  int slab, nslabs;                                                   // OP 1, 2
-  int quads;                                                          // OP 1: 1 = 16-byte loads; OP 3 .. 5: float4 quads of one plane (OP 5: of the tensor), 0 = none
-  int step_img, step_pel;                                             // OP 1: 1024 / HW, 1024 % HW -- from one quad of a chain to its next
-  float fN, eps, maf, omm, unb;
-};
+#include "kernel_args.h"      // bn_args_t
+#include "device_prelude.h"
 
 #if OP == 1
 #if MODE == 2

@@ -35,15 +35,8 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x3 __attribute__((ext_vector_type(3)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_args.h"      // gemm_args_t: I = filts (Mi x K), J = in (NCHW), D = out (NCHW)
+#include "device_prelude.h"
 #ifndef GROUP_I
 #define GROUP_I 8
 #endif
@@ -94,21 +87,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #ifndef ABLATE
 #define ABLATE 0 // experiment hook: 1 no output stores | 2 no pel loads | 4 no LDS stores in the staging waves | 8 no filter loads | 16 (with 2 | 8) pseudo-random values made in registers instead
 #endif
-
-struct gemm_args_t { // same layout as gemm_conv_f32.hip (one host-side struct serves all fp32 kernels)
-  float const *I; float const *J; float *D; float const *bias;   // I = filts (Mi x K), J = in (NCHW), D = out (NCHW)
-  int Mi, Nj, K;
-  int ldI, ldJ, ldD;
-  int C, H, W, OH, OW;
-  int tiles_i, tiles_j;
-  int splitk, kt_per;
-  float *ws; long ws_slab;
-  unsigned I_bytes, J_bytes;
-  unsigned D_bytes;
-  int out_ctot, out_coff;
-  int const *ktab; int ktab_n;
-  long bsI, bsJ, bsD;
-};
 
 #ifndef XPOSE_ONLY
 namespace {
@@ -189,11 +167,6 @@ constexpr int kRPT = BKS / kRG;               // k rows per thread and step
 constexpr int kNJ = kCPT * kRPT;
 static_assert(J_MODE == 7 || (TBJ % kCPT == 0 && kTW % 64 == 0 && kRG >= 1 && BKS % kRG == 0 && (J_MODE == 5 || kRPT % 4 == 0)), "pel staging: whole waves per k row, whole table quads per thread");
 static_assert(J_MODE == 2 || J_MODE == 5 || J_MODE == 7, "J_MODE: 2 | 5 | 7");
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(void const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ float bload1(rsrc_t r, int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0)); }
-__device__ __forceinline__ f32x2 bload2(rsrc_t r, int voff, int soff) { return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0)); }
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, int voff, int soff) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0)); }
 constexpr int colI(int x) { return (x / kTI) * kTIp + x % kTI; }   // LDS column of tile row x (out_chan) ...
 __device__ __forceinline__ int colJ(int x) { return PERMJ ? (x / kTJ) * kTJp + x % kTJ : x; }   // ... and of tile column x (pel; natural column blocks: itself)
 } // namespace

@@ -34,13 +34,8 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#include "kernel_args.h"      // gemm_args_t: I = filts, J = in; grp_args_t
+#include "device_prelude.h"
 
 #ifndef GROUP_I
 #define GROUP_I 8
@@ -108,27 +103,6 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #else
 #define BODAHIP_BID blockIdx.x
 #endif
-#ifndef BODAHIP_ARGS_DEFINED
-struct gemm_args_t { // identical to gemm_conv_f32.hip (one host-side struct); I = filts, J = in
-  float const *I; float const *J; float *D; float const *bias;
-  int Mi, Nj, K;
-  int ldI, ldJ, ldD;
-  int C, H, W, OH, OW;
-  int tiles_i, tiles_j;
-  int splitk, kt_per;
-  float *ws; long ws_slab;
-  unsigned I_bytes, J_bytes;
-  unsigned D_bytes;
-  int out_ctot, out_coff;
-  int const *ktab; int ktab_n;
-  long bsI, bsJ, bsD;
-};
-
-struct grp_args_t { // GROUPS: member m owns fused out_chans [oc0[m], oc0[m] + noc[m]) (oc0[m] multiples of the pad granularity; rows up to oc0[m+1] are zero padding)
-  int n; int oc0[4]; int noc[4];
-  void *D[4]; unsigned D_bytes[4]; int ctot[4]; int coff[4];
-};
-#endif // BODAHIP_ARGS_DEFINED
 
 #ifdef REDUCE_ONLY
 // out[pel][out_coff + oc] = cvt( relu( bias[oc] + sum_s ws[s][pel][oc] ) );  args: ws, ws_slab (floats per slab), splitk, D, Mi = OC, Nj = pels, out_ctot / out_coff.
@@ -196,9 +170,6 @@ constexpr int kEPitch = BI * 2 + 16;                               // epilogue t
 constexpr int kStage = NBUF * (kIImg + kJImg), kEpi = (OUT_F32 || SPLITK) ? 0 : BJ * kEPitch;
 constexpr int kSmem = kStage > kEpi ? kStage : kEpi;
 constexpr int kOOB = (int)0x80000000;
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef __attribute__((address_space(3))) void *lds_t;
-__device__ __forceinline__ rsrc_t make_rsrc(void const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
 __device__ __forceinline__ constexpr int swz(int row) { return (row / kRP) & (kCPR - 1); }
 } // namespace
 

@@ -23,12 +23,8 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_args.h"      // multi_prob_t, multi_tile_t, multi_args_t
+#include "device_prelude.h"
 
 #ifndef OUT_F32
 #define OUT_F32 0
@@ -36,18 +32,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #ifndef NBUF
 #define NBUF 3
 #endif
-
-struct prob_t {   // one member convolution (128 bytes; host mirror: native_kernels.cc)
-  void const *I; void const *J; void *D; float const *bias;     // filts, in, out, biases
-  unsigned I_bytes, J_bytes, D_bytes; int Mi;                    // buffer extents; out_chans
-  int Nj, CIN, KH, KW;                                           // output positions (img * oy * ox); stored in_chans (% 8 == 0); window
-  int SY, SX, PY, PX;
-  int CH, CW, COH, COW;                                          // input plane, output plane
-  int kCG, kKC, nK, relu;                                        // chunks per tap (CIN / 8), chunks along k (taps * kCG), K steps, ReLU
-  int out_ctot, out_coff, tiles_i, tiles_j;
-};
-struct tile_t { int prob, tile_i, tile_j, pad; };
-struct multi_args_t { prob_t const *probs; tile_t const *tiles; int n_tiles; int n_probs; };
 
 namespace {
 constexpr int kNW = WI * WJ, kNT = kNW * 64;
@@ -69,9 +53,6 @@ constexpr int kEPitch = BI * 2 + 16;                               // epilogue t
 constexpr int kStage = NBUF * (kIImg + kJImg), kEpi = OUT_F32 ? 0 : BJ * kEPitch;
 constexpr int kSmem = kStage > kEpi ? kStage : kEpi;
 constexpr int kOOB = (int)0x80000000;
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef __attribute__((address_space(3))) void *lds_t;
-__device__ __forceinline__ rsrc_t make_rsrc(void const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
 __device__ __forceinline__ constexpr int swz(int row) { return (row / kRP) & (kCPR - 1); }
 } // namespace
 
@@ -81,9 +62,9 @@ extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(multi_arg
   int const wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int const wi = wave / WJ, wj = wave % WJ;
 
-  tile_t const *__restrict__ const tp = a.tiles + blockIdx.x;     // workgroup-uniform: scalar loads
+  multi_tile_t const *__restrict__ const tp = a.tiles + blockIdx.x;     // workgroup-uniform: scalar loads
   int const t_prob = __builtin_amdgcn_readfirstlane(tp->prob), t_i = __builtin_amdgcn_readfirstlane(tp->tile_i), t_j = __builtin_amdgcn_readfirstlane(tp->tile_j);
-  prob_t const &q = *(prob_t const *__restrict__)(a.probs + t_prob);
+  multi_prob_t const &q = *(multi_prob_t const *__restrict__)(a.probs + t_prob);
 #define U(x) __builtin_amdgcn_readfirstlane(x)
   int const Mi = U(q.Mi), Nj = U(q.Nj), CIN = U(q.CIN), KW = U(q.KW), KH = U(q.KH), SY = U(q.SY), SX = U(q.SX), PY = U(q.PY), PX = U(q.PX), CH = U(q.CH), CW = U(q.CW),
             COH = U(q.COH), COW = U(q.COW);

@@ -23,12 +23,8 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_args.h"      // gemm_args_t: I = F', J = in
+#include "device_prelude.h"
 
 #ifndef GROUP_I
 #define GROUP_I 8
@@ -77,22 +73,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #else
 #define BODAHIP_BID blockIdx.x
 #endif
-#ifndef BODAHIP_ARGS_DEFINED
-struct gemm_args_t { // identical to gemm_conv_f32.hip (one host-side struct); I = F', J = in
-  float const *I; float const *J; float *D; float const *bias;
-  int Mi, Nj, K;
-  int ldI, ldJ, ldD;
-  int C, H, W, OH, OW;
-  int tiles_i, tiles_j;
-  int splitk, kt_per;
-  float *ws; long ws_slab;
-  unsigned I_bytes, J_bytes;
-  unsigned D_bytes;
-  int out_ctot, out_coff;
-  int const *ktab; int ktab_n;
-  long bsI, bsJ, bsD;
-};
-#endif // BODAHIP_ARGS_DEFINED
 
 namespace {
 constexpr int kNT = WI * WJ * 64;
@@ -133,12 +113,8 @@ constexpr int kImgC = kAImg + CG * kCSp;                            // chunks of
 constexpr int kOpB = 16 * kImgC * ((DBUF || ADIRECT) ? 2 : 1), kEpiB = OUT_F32 ? 0 : BJ * kEPitch;
 constexpr int kSmem = kOpB > kEpiB ? kOpB : kEpiB;
 constexpr int kOOB = (int)0x80000000;
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(void const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ u32x4 bload4(rsrc_t r, int voff) { return __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0); }
 // chunk offset of k-slot q = (g, ky, kx) inside the patch, relative to a lane's output position
 constexpr int slot_off(int q) { return (q >= kNPr) ? 0 : (POOL ? q * kCSp : ((q / kTaps) * kCSp + ((q % kTaps) / KW) * kWp + (q % KW))); } // (the pad slot reads tap 0: its filter row is zero)
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 // the B fragment of one output position and k-slot: the patch chunk at `at` -- or, POOL, the maximum over the window whose tap (0, 0) is at `at`
 __device__ __forceinline__ bf16x8 frag_b(u32x4 const *Js, int at) {
 #if POOL
@@ -218,14 +194,14 @@ extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(gemm_args
     for (int e = 0; e < kPE; ++e) {
       int const el = tid + e * kNT, g = el % CG;
       bool const ok = (pgoff[e] != kOOB) && (kNCG % CG == 0 || cg0 + g < kNCG);
-      rp[e] = bload4(rJ, ok ? (pgoff[e] + cg0 * 16) : kOOB);
+      rp[e] = bload4u(rJ, ok ? (pgoff[e] + cg0 * 16) : kOOB);
     }
 #pragma unroll
     for (int e = 0; e < kIE; ++e) {
       int const el = tid + e * kNT, q = el / BI, i = el - q * BI;             // k-slot q = (g, tap) of this step, out_chan i0 + i
       int const g = q / kTaps, tap = q - g * kTaps, cg = cg0 + g;
       bool const ok = (el < kNP * BI) && (q < kNPr) && (cg < kNCG) && (i0 + i < p.Mi);
-      rf[e] = bload4(rI, ok ? (int)((((unsigned)cg * kTaps + tap) * (unsigned)p.Mi + (unsigned)(i0 + i)) * 16u) : kOOB);
+      rf[e] = bload4u(rI, ok ? (int)((((unsigned)cg * kTaps + tap) * (unsigned)p.Mi + (unsigned)(i0 + i)) * 16u) : kOOB);
     }
   };
   auto store_step = [&](int buf) {
@@ -251,7 +227,7 @@ extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(gemm_args
 #pragma unroll
       for (int t = 0; t < kTI; ++t) {
         int const vo = ((kNPr & 1) && s == kN - 1 && hi) ? kOOB : aoff[t];   // (the zero pad slot of an odd step)
-        dst[t] = (ABLATE == 1) ? u32x4{0u, 0u, 0u, 0u} : bload4(rI, vo + ro);
+        dst[t] = (ABLATE == 1) ? u32x4{0u, 0u, 0u, 0u} : bload4u(rI, vo + ro);
       }
     };
     auto load_patch = [&](int kt) {
@@ -260,7 +236,7 @@ extern "C" __global__ __launch_bounds__(WI * WJ * 64, MINW) void KNAME(gemm_args
       for (int e = 0; e < kPE; ++e) {
         int const el = tid + e * kNT, g = el % CG;
         bool const ok = (pgoff[e] != kOOB) && (kNCG % CG == 0 || cg0 + g < kNCG);
-        rp[e] = (ABLATE == 1) ? u32x4{0u, 0u, 0u, 0u} : bload4(rJ, ok ? (pgoff[e] + cg0 * 16) : kOOB);
+        rp[e] = (ABLATE == 1) ? u32x4{0u, 0u, 0u, 0u} : bload4u(rJ, ok ? (pgoff[e] + cg0 * 16) : kOOB);
       }
     };
     auto store_patch = [&](int buf) {

@@ -24,13 +24,8 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
+#include "kernel_args.h"      // rows_args_t
+#include "device_prelude.h"
 
 #ifndef RELU
 #define RELU 0
@@ -48,15 +43,6 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 #ifndef LRN_N
 #define LRN_N 0    // > 0 (odd): across-channel LRN of that local size behind the pooling
 #endif
-
-struct rows_args_t {       // (host: native_kernels.cc conv_nhwc_rows)
-  void const *filts; void const *in; void *out; float const *bias;
-  int n_img, oc;           // images; out_chans (<= 64)
-  unsigned filts_bytes, in_bytes, out_bytes;
-  int out_ctot, out_coff;  // channels of the output tensor's rows, first channel this convolution writes
-  int n_chunks, rows_per_chunk;   // workgroups per image; output rows (pooled rows if PKH) each of them owns
-  float lrn_alpha, lrn_beta, lrn_k;
-};
 
 namespace {
 constexpr int BI = 64, BJ = 256;
@@ -85,9 +71,6 @@ constexpr int kPatchB = 2 * 16 * kPatchC, kRingB = kNR * kERow, kPoolB = (PKH > 
 constexpr int kSmem = kPatchB + kRingB + kPoolB + kBiasB;
 static_assert(kSmem <= 160 * 1024, "LDS");
 constexpr int kOOB = (int)0x80000000;
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(void const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ u32x4 bload4(rsrc_t r, int voff) { return __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0); }
 // chunk offset of k-slot q of K step kt inside a patch image, relative to a lane's output position: group (kt CG + g), tap (ky, kx)
 constexpr int slot_off(int kt, int q) {
   return (q >= kNPr || kt * CG + q / kTaps >= kNCG) ? 0 : ((kt * CG + q / kTaps) * kCSp + ((q % kTaps) / KW) * kWp + (q % KW));   // (pad slots read tap 0: their filter rows are zero)
@@ -138,7 +121,7 @@ extern "C" __global__ __launch_bounds__(WJ * 64, 1) void KNAME(rows_args_t const
       for (int t = 0; t < kTI; ++t) {
         int const oc = t * 32 + (lane & 31), row = kt * kNPr + 2 * s + h;
         bool const ok = (oc < p.oc) && !((kNPr & 1) && s == kN - 1 && h);
-        a[kt * kN + s][t] = bload4(rI, ok ? (row * p.oc + oc) * 16 : kOOB);
+        a[kt * kN + s][t] = bload4u(rI, ok ? (row * p.oc + oc) * 16 : kOOB);
       }
 
   // ---- this thread's patch chunks: element el = (position, channel group), position-major (kNCG consecutive lanes read kNCG x 16 contiguous bytes); slot s = input row
@@ -155,7 +138,7 @@ extern "C" __global__ __launch_bounds__(WJ * 64, 1) void KNAME(rows_args_t const
   u32x4 rp[kPE];
   auto load_patch = [&](int r0) {
 #pragma unroll
-    for (int e = 0; e < kPE; ++e) rp[e] = bload4(rJ, ((unsigned)(prow[e] + r0) < (unsigned)CH) ? (pgoff[e] + r0 * (CW * CIN * 2)) : kOOB);
+    for (int e = 0; e < kPE; ++e) rp[e] = bload4u(rJ, ((unsigned)(prow[e] + r0) < (unsigned)CH) ? (pgoff[e] + r0 * (CW * CIN * 2)) : kOOB);
   };
   auto store_patch = [&](int buf) {
     u32x4 *const Js = Js0 + buf * kPatchC;

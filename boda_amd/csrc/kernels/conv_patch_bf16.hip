@@ -21,10 +21,8 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "kernel_args.h"      // gemm_args_t: I = F' (re-laid-out bf16 filters), J = in; s2d_args_t
+#include "device_prelude.h"
 
 #ifndef GROUP_I
 #define GROUP_I 8
@@ -36,35 +34,12 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define SWAPST ((BJ / (WJ * 32)) % 2 == 0)
 #endif
 
-struct gemm_args_t { // identical to gemm_conv_f32.hip (one host-side struct); I = F' (re-laid-out bf16 filters), J = in
-  float const *I; float const *J; float *D; float const *bias;
-  int Mi, Nj, K;
-  int ldI, ldJ, ldD;
-  int C, H, W, OH, OW;
-  int tiles_i, tiles_j;
-  int splitk, kt_per;
-  float *ws; long ws_slab;
-  unsigned I_bytes, J_bytes;
-  unsigned D_bytes;
-  int out_ctot, out_coff;
-  int const *ktab; int ktab_n;
-  long bsI, bsJ, bsD;
-};
-
 #ifdef S2D_ONLY
 // Space-to-depth front end for strided convolutions on few input channels (the conv1 layers: 11x11/4 or 7x7/2 on 3 channels), which
 // the patch kernel cannot take directly (stride 1 in x, channels in groups of 8): an s x s block of input pixels becomes s*s channels,
 //   in2[b][c*s*s + dy*s + dx][Y][X] = in[b][c][s*Y + dy - Pry][s*X + dx - Prx]       (zero outside; Pr = pad rounded up to a multiple of s)
 //   f2 [oc][c*s*s + dy*s + dx][a][b] = filts[oc][c][s*a + dy - (Pry - PY)][s*b + dx - (Prx - PX)]   (zero outside)
 // and the layer is the stride-1, unpadded ceil((K + Pr - P)/s)-square convolution of in2 with f2 -- same outputs, term for term.
-struct s2d_args_t {
-  float const *src; float *dst;
-  int B, C, H, W, OC, KH, KW;       // source tensor geometry (filters: OC, C, KH, KW)
-  int S, C2, H2, W2;                // block size; channels (padded to a multiple of 8), rows, cols of the result (filters: rows = KHb, cols = KWb)
-  int oy, ox;                       // input: Pr (rounded-up pad) per axis; filters: Pr - P per axis
-  int filt;                         // 0: input tensor, 1: filters
-  int mode, c2_lo;                  // mode 0: one thread per result element with channel >= c2_lo (filters; the zero pad channels of the input)
-};                                  // mode 1: one thread per (b, c, Y, dy, X): S consecutive source pixels -> S channel planes (reads and writes coalesced)
 extern "C" __global__ __launch_bounds__(256) void KNAME(s2d_args_t const p) {
   long const idx = (long)blockIdx.x * 256 + threadIdx.x;
   int const SH = p.filt ? p.KH : p.H, SW = p.filt ? p.KW : p.W, ss = p.S * p.S;
@@ -126,10 +101,6 @@ constexpr int kCS = kSlots * kWp;                                  // input posi
 constexpr int kPE = (kCS * CG + kNT - 1) / kNT;                    // patch chunks per thread per K step
 constexpr int kIE = (kNP * BI + kNT - 1) / kNT;                    // filter chunks per thread per K step
 constexpr int kOOB = (int)0x80000000;
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(void const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ float bload1(rsrc_t r, int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0)); }
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, int voff) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0)); }
 // chunk offset of k-slot q = (g, ky, kx) inside the patch, relative to a lane's output position
 constexpr int slot_off(int q) { return (q >= kNPr) ? 0 : ((q / kTaps) * kCS + ((q % kTaps) / KW) * kWp + (q % KW)); } // (the pad slot reads tap 0: its filter row is zero)
 } // namespace

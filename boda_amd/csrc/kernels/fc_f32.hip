@@ -28,8 +28,8 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_args.h"      // gemm_args_t: I = filts [Mi][K], J = in [Nj][K]; tiles_i out_chan tiles (TN each), tiles_j image tiles (TM each)
+#include "device_prelude.h"
 #ifndef TM
 #define TM 64
 #endif
@@ -39,21 +39,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #ifndef RA
 #define RA 2 // operand quads read ahead of the MFMAs (measured: 2 best, 1 / 3 / 5 slower)
 #endif
-
-struct gemm_args_t { // same layout as gemm_conv_f32.hip (one host-side struct serves all fp32 kernels)
-  float const *I; float const *J; float *D; float const *bias;   // I = filts [Mi][K], J = in [Nj][K]
-  int Mi, Nj, K;
-  int ldI, ldJ, ldD;
-  int C, H, W, OH, OW;
-  int tiles_i, tiles_j;       // out_chan tiles (TN each) | image tiles (TM each)
-  int splitk, kt_per;
-  float *ws; long ws_slab;
-  unsigned I_bytes, J_bytes;
-  unsigned D_bytes;
-  int out_ctot, out_coff;
-  int const *ktab; int ktab_n;
-  long bsI, bsJ, bsD;
-};
 
 namespace {
 constexpr int kLDK = BKF + 4;                 // floats per LDS row (16-byte aligned rows: a staged float4 is one ds_write_b128)
@@ -65,10 +50,6 @@ constexpr int kU = 3 * PF;                    // steps per unrolled round (stage
 constexpr int kOOB = (int)0x80000000;
 static_assert((TM == 32 || TM == 64) && (TN == 32 || TN == 64) && (BKF == 32 || BKF == 64) && (PF == 2 || PF == 4), "TM, TN: 32 | 64; BKF: 32 | 64; PF: 2 | 4");
 static_assert(kNLA >= 1 && kNLB >= 1 && RA >= 1 && RA < kQ, "staging units per thread, read-ahead");
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(float const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, int voff, int soff) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0)); }
-__device__ __forceinline__ float bload1(rsrc_t r, int voff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0)); }
 } // namespace
 
 #ifndef STGPRIO

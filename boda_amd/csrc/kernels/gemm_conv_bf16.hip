@@ -26,10 +26,8 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "kernel_args.h"      // gemm_args_t (D_bytes, bsI / bsJ / bsD: not read here)
+#include "device_prelude.h"
 
 #ifndef KNAME
 #define KNAME bodahip_gemm_bf16
@@ -56,22 +54,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #endif           // of p.ws; bodahip_splitk_reduce (gemm_conv_f32.hip) sums the slabs and applies the epilogue.  Chosen by the host for
                  // tile-starved shapes with a long K (fully-connected layers): this path is not order-exact anyway.
 
-struct gemm_args_t { // identical to gemm_conv_f32.hip (one host-side struct)
-  float const *I; float const *J; float *D; float const *bias;
-  int Mi, Nj, K;
-  int ldI, ldJ, ldD;
-  int C, H, W, OH, OW;
-  int tiles_i, tiles_j;
-  int splitk, kt_per;
-  float *ws; long ws_slab;
-  unsigned I_bytes, J_bytes;
-  unsigned D_bytes;             // (used by the f32 kernel's epilogue; kept for a common argument block)
-  int out_ctot, out_coff;      // EPI 1: channels of the output tensor and first channel written (== Mi, 0 unless the conv writes a slice
-                               // of a wider tensor: Concat elimination)
-  int const *ktab; int ktab_n;
-  long bsI, bsJ, bsD; // (batched sgemm launches of gemm_conv_f32.hip only)
-};
-
 namespace {
 constexpr int kNT = WI * WJ * 64;
 constexpr int kTI = BI / (WI * 32);
@@ -85,12 +67,8 @@ static_assert(BI % (WI * 32) == 0 && BJ % (WJ * 32) == 0, "tile must be a multip
 static_assert((BI * BK / 8) % kNT == 0 && (BJ * BK / 8) % kNT == 0, "chunks must split evenly over the threads");
 static_assert(BJ % 64 == 0 || (J_MODE != 2 && J_MODE != 5), "gather: BJ must be a multiple of 64 (wave-uniform k chunk)");
 
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 constexpr int kOOB = (int)0x80000000;
 constexpr int kKTail = 0x7ffffff0;
-__device__ __forceinline__ rsrc_t make_rsrc(float const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, int off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0)); }
-__device__ __forceinline__ float bload1(rsrc_t r, int off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0)); }
 
 // one chunk = column x (tile-relative xr), k = k0 + 8*kc .. +7.  chunk index c = tid + p*kNT: xr = c % BX, kc = c / BX.
 template <int MODE, int BX, int NCH>

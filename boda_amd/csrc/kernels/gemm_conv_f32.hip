@@ -50,13 +50,12 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h> // offline (hipcc) builds only; hiprtc provides the device runtime implicitly
 #endif
+#include "kernel_args.h"      // gemm_args_t
+#include "device_prelude.h"
 
 #ifndef ST_AUX
 #define ST_AUX 0   // cache policy of the paired output stores (experiments: bit 0 sc0, bit 1 nt, bit 4 sc1)
 #endif
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef KNAME
 #define KNAME bodahip_gemm_f32
@@ -121,23 +120,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #ifndef MT
 #define MT 32 // MFMA tile: 32 -> v_mfma_f32_32x32x2_f32 (default), 16 -> v_mfma_f32_16x16x4_f32 (4x more, smaller wave tiles for
 #endif        // shapes with too few 32x32 tiles to give every SIMD a wave; same fp32 rate, same ascending-k fma chain)
-
-struct gemm_args_t {
-  float const *I; float const *J; float *D; float const *bias;
-  int Mi, Nj, K;          // extents of i, j, k
-  int ldI, ldJ, ldD;      // row pitches (elements) of I, J (k-major: per k row; i/j-major: per i/j row) and of D per i
-  int C, H, W, OH, OW;    // convolution geometry (J_MODE 2 / EPI 1)
-  int tiles_i, tiles_j;
-  int splitk, kt_per;     // SPLITK: number of K slices, K-tiles per slice
-  float *ws; long ws_slab; // SPLITK: partial-sum slabs, ws_slab elements apart
-  unsigned I_bytes, J_bytes; // sizes of the I / J tensors (buffer-descriptor num_records; host guarantees <= 2^31)
-  unsigned D_bytes;             // size of the output tensor (host guarantees < 2^32: 32-bit store offsets)
-  int out_ctot, out_coff;      // EPI 1: channels of the output tensor and first channel written (== Mi, 0 unless the conv writes a slice
-                               // of a wider tensor: Concat elimination)
-  int const *ktab; int ktab_n; // J_MODE 2: per-k gather tables, three arrays of ktab_n ints: element offset of (in_chan,ky,kx)
-                               // inside one image | ky | kx ; rows k >= K carry ky = 2^30 (fail the row-range test)
-  long bsI, bsJ, bsD;          // batched launches (gridDim.y problems of one shape, e.g. the 16 Winograd-domain sgemms): element strides of I / J / D per blockIdx.y
-};
 
 #ifndef REDUCE_ONLY
 namespace {
@@ -213,19 +195,9 @@ constexpr int kJTile = BK * kLDJ;
 // ---------------------------------------------------------------------------------------------------------------
 // global -> registers.  MODE 0/1: k-major rows of BX floats (x contiguous); MODE 2/3: x-major rows, k contiguous.
 // ---------------------------------------------------------------------------------------------------------------
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 constexpr int kOOB = (int)0x80000000; // byte offset beyond any num_records (tensors are <= 2^31 bytes): hardware returns 0
-__device__ __forceinline__ rsrc_t make_rsrc(float const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, int byte_off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0)); }
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x3 __attribute__((ext_vector_type(3)));
-// (whole-vector bit_casts: element-wise bit_casts of the b64/b96 results get mis-shrunk to a 1-dword load by this compiler)
-__device__ __forceinline__ f32x2 bload2(rsrc_t r, int byte_off) { return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, 0)); }
-__device__ __forceinline__ f32x3 bload3(rsrc_t r, int byte_off) { return __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(r, byte_off, 0, 0)); }
-__device__ __forceinline__ float bload1(rsrc_t r, int byte_off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0)); }
 
 #if HALF
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 static_assert((I_MODE == 0 || I_MODE == 1) && (J_MODE == 0 || J_MODE == 1) && EPI == 0 && !SPLITK, "half storage: plain k-major sgemm operands only");
 #endif
 template <int MODE, int BX, int NR>

@@ -26,27 +26,11 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "kernel_args.h"      // gemm_args_t: tiles_i out_chan tiles, tiles_j pel super-blocks (WJ*CB*32 pels each), kt_per workgroups per out_chan tile == a workgroup's super-block stride
+#include "device_prelude.h"
 #ifndef ABLATE
 #define ABLATE 0 // experiment hook (BODAHIP_EXTRA_DEFS): 1 no stores | 2 no input loads | 4 no MFMAs
 #endif
-
-struct gemm_args_t { // same layout as gemm_conv_f32.hip (one host-side struct serves both)
-  float const *I; float const *J; float *D; float const *bias;
-  int Mi, Nj, K;
-  int ldI, ldJ, ldD;
-  int C, H, W, OH, OW;
-  int tiles_i, tiles_j;       // out_chan tiles | pel super-blocks (WJ*CB*32 pels each)
-  int splitk, kt_per;         // kt_per: workgroups per out_chan tile == the super-block stride of a workgroup
-  float *ws; long ws_slab;
-  unsigned I_bytes, J_bytes;
-  unsigned D_bytes;
-  int out_ctot, out_coff;
-  int const *ktab; int ktab_n;
-  long bsI, bsJ, bsD; // (batched sgemm launches of gemm_conv_f32.hip only)
-};
 
 namespace {
 constexpr int kNT = WI * WJ * 64;
@@ -59,10 +43,6 @@ constexpr int kOOB = (int)0x80000000;
 #ifndef EDGE_OC
 #define EDGE_OC 1 // 0: out_chan is a multiple of the workgroup's out_chan tile (no per-row range test in the stores)
 #endif
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(float const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ float bload1(rsrc_t r, int voff, int soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0)); }
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, int voff, int soff) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0)); }
 // Resident filter image Fs[k][oc] = filts[row0 + oc][k] (ROWS x KCC, k-major with pitch LD; rows past the tensor and the pad row of an odd KCC are zero).  The filter
 // block is one contiguous run of floats: every thread issues ALL its 16-byte loads first, branch-free, and transposes into LDS afterwards -- one memory round trip for
 // the whole image.  (The first form -- one dword load, wait, one LDS store per element -- was a serial chain of 36-72 round trips per thread: 25-50 us at the head of

@@ -29,20 +29,8 @@
 
 #pragma clang fp contract(off) reassociate(off)
 
-#define SGD_MAX_TENS 32
+#include "kernel_args.h"      // sgd_tensor_t, sgd_update_args_t, kSgdMaxTens
 #define SGD_CHUNK 4096
-
-struct sgd_tensor_t {   // must match native_internal.h
-  float *w; float const *g; float *h;
-  unsigned n, blk0;                      // elements; index of the tensor's first workgroup
-  float lr_mult, decay_mult;
-  unsigned quads, pad;                   // 1: w, g and h are 16-byte aligned
-};
-struct sgd_update_args_t {   // must match native_internal.h
-  float const *hyper;                    // lr, momentum, weight_decay, unused
-  unsigned tens_num, pad;
-  sgd_tensor_t t[SGD_MAX_TENS];
-};
 
 struct sgd_coef_t { float lr, wd, mom; };
 
@@ -59,7 +47,7 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(sgd_update_args_t const 
   unsigned const b = blockIdx.x;
   int ti = 0;
 #pragma unroll
-  for (int i = 1; i < SGD_MAX_TENS; ++i) if (i < (int)p.tens_num && b >= p.t[i].blk0) ti = i;
+  for (int i = 1; i < kSgdMaxTens; ++i) if (i < (int)p.tens_num && b >= p.t[i].blk0) ti = i;
   ti = __builtin_amdgcn_readfirstlane(ti);
   sgd_tensor_t const t = p.t[ti];
   unsigned const base = (b - t.blk0) * SGD_CHUNK;

@@ -27,10 +27,8 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#include "kernel_args.h"      // gemm_args_t: I = a (K x Mi), J = b (K x Nj), D = c (Mi x Nj)
+#include "device_prelude.h"
 #ifndef GROUP_I
 #define GROUP_I 8
 #endif
@@ -68,21 +66,6 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #define NSTG 4 // LDS stages: tile t lives in stage t % NSTG and is written during step t - (NSTG - 1).  4: a tile is complete one barrier before its step, so the
 #endif         // multiplying waves fetch its first operands BEFORE the barrier that ends the previous step (nothing but the barrier itself between two steps)
 
-struct gemm_args_t { // same layout as gemm_conv_f32.hip (one host-side struct serves all fp32 kernels)
-  float const *I; float const *J; float *D; float const *bias;   // I = a (K x Mi), J = b (K x Nj), D = c (Mi x Nj)
-  int Mi, Nj, K;
-  int ldI, ldJ, ldD;
-  int C, H, W, OH, OW;
-  int tiles_i, tiles_j;
-  int splitk, kt_per;
-  float *ws; long ws_slab;
-  unsigned I_bytes, J_bytes;
-  unsigned D_bytes;
-  int out_ctot, out_coff;
-  int const *ktab; int ktab_n;
-  long bsI, bsJ, bsD;
-};
-
 namespace {
 constexpr int kNMW = WI * WJ;                 // multiplying waves
 static_assert(kNMW == 12 || kNMW == 8 || kNMW == 4, "twelve, eight or four multiplying waves");
@@ -98,9 +81,6 @@ constexpr int kD = NSTG - 1;                  // a tile is written kD steps ahea
 static_assert(NSTG == 3 || NSTG == 4, "NSTG: 3 | 4");
 constexpr int kOOB = (int)0x80000000;
 static_assert(BKS % 4 == 0 && (PF == 2 || PF == 4), "BKS % 4 == 0, PF: 2 | 4");
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(float const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, int voff, int soff) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0)); }
 template <bool B> struct bool_c { static constexpr bool value = B; };
 } // namespace
 

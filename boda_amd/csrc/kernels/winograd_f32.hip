@@ -18,16 +18,8 @@
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #endif
-
-struct wino_args_t {
-  float const *in; float const *filts; float const *bias; float *out;
-  float *U; float *V; float *M;
-  int B0, Bc;                 // first image and number of images of this chunk
-  int C, H, W, OC, OH, OW;
-  int TH, TW, Tc;             // tiles per image (rows, cols), tiles in the chunk = Bc*TH*TW
-  int PY, PX, relu;
-  int out_ctot, out_coff;     // channels of the output tensor, first channel written
-};
+#include "kernel_args.h"      // wino_args_t
+#include "device_prelude.h"
 
 // U[(xn*C + c)*OC + oc]; one thread per (c, oc), oc fastest (coalesced stores; the 9 filter taps are strided reads of a small tensor)
 extern "C" __global__ __launch_bounds__(256) void bodahip_wino_filt(wino_args_t const p) {
@@ -110,7 +102,6 @@ extern "C" __global__ __launch_bounds__(256) void bodahip_wino_out(wino_args_t c
 
 // U in the layout of the fused kernel: Ut[(c*OC + oc)*16 + xn] -- the 16 transform positions of one (in_chan, out_chan) are one 64-byte
 // record (four coalesced 16-byte stores per thread here, four 16-byte loads per record there).  Same expressions as bodahip_wino_filt.
-typedef float wf32x4 __attribute__((ext_vector_type(4)));
 extern "C" __global__ __launch_bounds__(256) void bodahip_wino_filt_t(wino_args_t const p) {
   long const idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long)p.C * p.OC) return;
@@ -122,11 +113,11 @@ extern "C" __global__ __launch_bounds__(256) void bodahip_wino_filt_t(wino_args_
     float const g0 = g[j], g1 = g[3 + j], g2 = g[6 + j];
     r[0][j] = g0; r[1][j] = 0.5f * (g0 + g1 + g2); r[2][j] = 0.5f * (g0 - g1 + g2); r[3][j] = g2;
   }
-  wf32x4 *u = reinterpret_cast<wf32x4 *>(p.U + idx * 16);
+  f32x4 *u = reinterpret_cast<f32x4 *>(p.U + idx * 16);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     float const a = r[i][0], b = r[i][1], d = r[i][2];
-    u[i] = wf32x4{a, 0.5f * (a + b + d), 0.5f * (a - b + d), d};
+    u[i] = f32x4{a, 0.5f * (a + b + d), 0.5f * (a - b + d), d};
   }
 }
 
@@ -152,14 +143,11 @@ extern "C" __global__ __launch_bounds__(256) void bodahip_wino_filt_t(wino_args_
 #ifndef WABLATE
 #define WABLATE 0   // measurement only (wrong results): 1 no input loads | 2 no U loads | 4 no MFMAs | 8 no operand reads after k-step 0 | 16 no transform / LDS writes
 #endif
-typedef float wf32x16 __attribute__((ext_vector_type(16)));
-typedef __amdgpu_buffer_rsrc_t wrsrc_t;
 namespace {
 constexpr int kWBK = 8;                    // input channels per stage
 constexpr int kWImg = kWBK * 64 * 16;      // floats of one operand image of a stage
 constexpr int kWOOB = (int)0x80000000;
 constexpr int kWFar = 0x40000000;
-__device__ __forceinline__ wrsrc_t wmake_rsrc(float const *p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes, 0x00020000); }
 } // namespace
 
 extern "C" __global__ __launch_bounds__(512, 1) void bodahip_wino_fused(wino_args_t const p) {
@@ -173,7 +161,7 @@ extern "C" __global__ __launch_bounds__(512, 1) void bodahip_wino_fused(wino_arg
   int const tpi = p.TH * p.TW;
 
   // ---- U staging: 4 x 16-byte loads per thread and stage: chunk tid & 3 of the record of out_chan (tid >> 2) & 63, channels (tid >> 8) + 2 i
-  wrsrc_t const rU = wmake_rsrc(p.U, (unsigned)((long)16 * p.C * p.OC * 4));
+  rsrc_t const rU = make_rsrc(p.U, (unsigned)((long)16 * p.C * p.OC * 4));
   int const u_j = tid & 3, u_oc = (tid >> 2) & 63, u_k0 = tid >> 8;
   int const u_off = (oc0 + u_oc < p.OC) ? (((oc0 + u_oc) * 16 + 4 * u_j) * 4) : kWOOB;
   int const u_lds = u_oc * 16 + 4 * (u_j ^ ((u_oc >> 1) & 3));
@@ -182,7 +170,7 @@ extern "C" __global__ __launch_bounds__(512, 1) void bodahip_wino_fused(wino_arg
   // Patch element (a, b) of channel c is read at byte offset cbase(c) + poff[4a + b]; elements outside the image (zero padding), tiles past
   // the end and channels past in_chan get kWFar added once or twice: the sum stays >= 2^30 as an unsigned offset, beyond the (< 2^30 byte)
   // tensor, so the hardware range check returns 0 -- no branch, no select per load.
-  wrsrc_t const rIn = wmake_rsrc(p.in, (unsigned)((long)p.Bc * p.C * p.H * p.W * 4));
+  rsrc_t const rIn = make_rsrc(p.in, (unsigned)((long)p.Bc * p.C * p.H * p.W * 4));
   int const tl = tid & 63, v_kc = tid >> 6;
   int v_base, poff[16];
   {
@@ -204,7 +192,7 @@ extern "C" __global__ __launch_bounds__(512, 1) void bodahip_wino_fused(wino_arg
   //   every fourth MFMA of k-steps 0..2 is preceded by two ds_read_b128: the operands of four transform positions of the next k-step.
   // Past the last stage the loads fall outside the tensors (zeros) and the writes go to the buffer nobody reads: no branch, the whole stage
   // is one basic block and every wait the compiler inserts counts exactly the loads it has to.
-  wf32x4 ureg[4]; float dreg[16];
+  f32x4 ureg[4]; float dreg[16];
   int cbase = 0;
   auto load_one = [&](int c0, int l) {   // l = 0..19
     if (l == 0) { int const c = c0 + v_kc; cbase = (c < p.C) ? (v_base + c * (p.H * p.W * 4)) : kWFar; }
@@ -218,9 +206,9 @@ extern "C" __global__ __launch_bounds__(512, 1) void bodahip_wino_fused(wino_arg
       int const i = l - 16, c = c0 + u_k0 + 2 * i;
       int const uo = (c < p.C) ? (u_off + c * (p.OC * 64)) : kWOOB;
 #if WABLATE & 2
-      ureg[i] = wf32x4{(float)uo, 1.f, 2.f, (float)i};
+      ureg[i] = f32x4{(float)uo, 1.f, 2.f, (float)i};
 #else
-      ureg[i] = __builtin_bit_cast(wf32x4, __builtin_amdgcn_raw_buffer_load_b128(rU, uo, 0, 0));
+      ureg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rU, uo, 0, 0));
 #endif
     }
   };
@@ -234,20 +222,20 @@ extern "C" __global__ __launch_bounds__(512, 1) void bodahip_wino_fused(wino_arg
       }
     } else if (k < 12 && k % 3 == 1) {
       int const xi = k / 3;
-      wf32x4 v;
+      f32x4 v;
 #pragma unroll
       for (int nu = 0; nu < 4; ++nu) {
         float const q0 = dreg[nu], q1 = dreg[4 + nu], q2 = dreg[8 + nu], q3 = dreg[12 + nu];
         v[nu] = (xi == 0) ? (q0 - q2) : (xi == 1) ? (q1 + q2) : (xi == 2) ? (q2 - q1) : (q1 - q3);
       }
-      *reinterpret_cast<wf32x4 *>(Vs + v_lds + 4 * (xi ^ v_sw)) = v;
+      *reinterpret_cast<f32x4 *>(Vs + v_lds + 4 * (xi ^ v_sw)) = v;
     } else if (k < 12 && k % 3 == 2) {
       int const i = k / 3;
-      *reinterpret_cast<wf32x4 *>(Us + (u_k0 + 2 * i) * 1024 + u_lds) = ureg[i];
+      *reinterpret_cast<f32x4 *>(Us + (u_k0 + 2 * i) * 1024 + u_lds) = ureg[i];
     }
   };
 
-  wf32x16 acc[8];
+  f32x16 acc[8];
 #pragma unroll
   for (int xn = 0; xn < 8; ++xn)
 #pragma unroll
@@ -268,9 +256,9 @@ extern "C" __global__ __launch_bounds__(512, 1) void bodahip_wino_fused(wino_arg
   }
   for (int st = 0; st < nst; ++st) {
     float const *const Us = smem + (st & 1) * (2 * kWImg), *const Vs = Us + kWImg;
-    wf32x4 fa[2][2], fb[2][2];
+    f32x4 fa[2][2], fb[2][2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) { fa[0][j] = *reinterpret_cast<wf32x4 const *>(Us + a_off[j]); fb[0][j] = *reinterpret_cast<wf32x4 const *>(Vs + b_off[j]); }
+    for (int j = 0; j < 2; ++j) { fa[0][j] = *reinterpret_cast<f32x4 const *>(Us + a_off[j]); fb[0][j] = *reinterpret_cast<f32x4 const *>(Vs + b_off[j]); }
 #pragma unroll
     for (int s = 0; s < kWBK / 2; ++s) {
 #pragma unroll
@@ -282,8 +270,8 @@ extern "C" __global__ __launch_bounds__(512, 1) void bodahip_wino_fused(wino_arg
         int const fs = s & 1;
         if (s + 1 < kWBK / 2 && (xn & 3) == 0) {
           int const j = xn >> 2;
-          fa[(s + 1) & 1][j] = *reinterpret_cast<wf32x4 const *>(Us + (s + 1) * 2048 + a_off[j]);
-          fb[(s + 1) & 1][j] = *reinterpret_cast<wf32x4 const *>(Vs + (s + 1) * 2048 + b_off[j]);
+          fa[(s + 1) & 1][j] = *reinterpret_cast<f32x4 const *>(Us + (s + 1) * 2048 + a_off[j]);
+          fb[(s + 1) & 1][j] = *reinterpret_cast<f32x4 const *>(Vs + (s + 1) * 2048 + b_off[j]);
         }
 #endif
 #if WABLATE & 4

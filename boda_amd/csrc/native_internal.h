@@ -9,27 +9,14 @@
 
 namespace bodahip {
 
-struct gemm_args_t { // must match kernels/gemm_conv_f32.hip
-  float const *I; float const *J; float *D; float const *bias;
-  int Mi, Nj, K;
-  int ldI, ldJ, ldD;
-  int C, H, W, OH, OW;
-  int tiles_i, tiles_j;
-  int splitk, kt_per;
-  float *ws; long ws_slab;
-  unsigned I_bytes, J_bytes;
-  unsigned D_bytes;
-  int out_ctot, out_coff;
-  void const *ktab; int ktab_n;
-  long bsI, bsJ, bsD;
-};
-// kernels/k1_quad_f32.hip -DCHAIN=1: gemm_args_t followed by the second convolution of a 1x1 chain.  (A struct of its own: gemm_args_t is also the element type of the member
-// tables of hip_conv_nhwc_set, whose device-side declaration must keep the size.)
-struct chain_args_t : gemm_args_t {
-  float const *I2; float const *bias2; float *Dmid;
-  int M2; unsigned I2_bytes, Dmid_bytes;
-};
-static_assert(sizeof(gemm_args_t) == 176, "gemm_args_t is declared with this size by every kernel source (and by set_kernel_source's text)");
+// The structs passed by value to a kernel or copied into a device-side table: declared once, for the host and the device compiler, with their layout assertions.
+// (chain_args_t, the arguments of kernels/k1_quad_f32.hip -DCHAIN=1, is a struct of its own derived from gemm_args_t, not a longer gemm_args_t: gemm_args_t is also the
+// element type of the member tables of hip_conv_nhwc_set and the argument of every other contraction kernel, so its size must not move with the chain's fields.)
+#include "kernels/kernel_args.h"
+static_assert(kSgdMaxTens == kSgdUpdateMaxTens, "hip_sgd_update: the op's limit is the size of the argument table");
+// enum kernel_src_t: one value kSrc_<name> per embedded kernels/<name>.hip, in the order of build.py's KERNELS (kernels_embed.inc; the texts are native_kernels.cc's)
+#include "kernels_embed.inc"
+kernel_text_t const &kernel_source(kernel_src_t s);
 
 struct kernel_t { hipModule_t mod = nullptr; hipFunction_t func = nullptr; int occ = 0; };   // occ: resident workgroups per CU (queried on first use by the persistent forms)
 
@@ -47,74 +34,19 @@ struct native_kernels_t::impl_t {
 };
 
 
-struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, big = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, nhwc_multi = false, nhwc_rows = false, ksl = false, bconv_in = false, bconv_filts = false, bconv_fb = false, bck_ops = false, sgd = false, bn = false; int rows = 0, cg = 0; };
+struct plan_t { tile_cfg_t cfg; vect_string defs; string kname; long split_pels = 0; tile_cfg_t tail_cfg; vect_string tail_defs;   /* split_pels > 0 (staging-wave convolution, round 6): two-level tiling along the pels -- this plan's tiles over the first split_pels pels (whole rounds of the CUs), tail_cfg's over the rest */ kernel_src_t src = kSrc_gemm_conv_f32;   /* the kernels/<name>.hip this plan specialises: set where kname is set.  The flags below: what launch code branches on */ bool ipconv = false, k1 = false, bf16 = false, patch = false, stream = false, quad = false, fc = false, cbig = false, rdec = false, patch16 = false, nhwc = false, nhwc_patch = false, ksl = false, bconv_in = false; int rows = 0, cg = 0; };
 
-struct bconv_args_t { // must match kernels/bconv_in_f32.hip, kernels/bconv_filts_f32.hip
-  float const *a; float const *b; float *d;
-  float *ws; long ws_slab;
-  int B, C, H, W, OC, OH, OW;
-  int tiles_i, tiles_j, ksl, kt_per;
-  unsigned a_bytes, b_bytes, d_bytes;
-  float const *zin;   // bconv_in -DZINP=1: the forward input, the condition of the select on the store
-};
-
-struct bconv_fb_args_t { // must match kernels/bconv_fb_f32.hip
-  float const *g; float const *x; float *df; float *db;
-  float *ws; long slab_elems;
-  int B, C, H, W, OC, OH, OW;
-  int tiles_i, tiles_j, ksl, kt_per;
-  unsigned g_bytes, x_bytes;
-};
-
-struct bck_ops_args_t { // must match kernels/bck_ops_f32.hip
-  float const *p0; float const *p1; float const *p2; float const *p3;
-  float *o0; float *o1;
-  long n;
-  int B, C, HW, n4;
-  float f0, f1, f2, f3;
-  float const *p4; float const *p5; float const *p6; float const *p7;
-  unsigned seed, thresh;
-  int run, wide, off;
-};
 // (the functions of the gradient pipe's non-conv ops, their kernels and their args: the kFamBckOp rows of native_funcs.h)
 struct bck_plan_t { plan_t p; long threads = 0; uint32_t grid = 0, block = 256; int CB = 0; double algo_bytes = 0; };
 bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus);
 bck_plan_t plan_shard_sum(int nslabs, long stride, long n);   // OP 14 of the same file: no function of its own, the multi-device backend's sum of per-shard partials
 
-// hip_sgd_update (kernels/sgd_update_f32.hip): the table of up to 32 tensors rides by value in the kernel arguments
-constexpr int kSgdMaxTens = kSgdUpdateMaxTens;
+// hip_sgd_update (kernels/sgd_update_f32.hip): the table of up to kSgdMaxTens tensors rides by value in the kernel arguments (sgd_update_args_t)
 constexpr long kSgdChunk = 4096;   // floats of one tensor a workgroup owns
-struct sgd_tensor_t { // must match kernels/sgd_update_f32.hip
-  float *w; float const *g; float *h;
-  unsigned n, blk0;
-  float lr_mult, decay_mult;
-  unsigned quads, pad;
-};
-struct sgd_update_args_t { // must match kernels/sgd_update_f32.hip
-  float const *hyper;
-  unsigned tens_num, pad;
-  sgd_tensor_t t[kSgdMaxTens];
-};
-static_assert(sizeof(sgd_tensor_t) == 48 && sizeof(sgd_update_args_t) == 16 + 48 * kSgdMaxTens, "sgd_update_args_t is declared with this layout by kernels/sgd_update_f32.hip");
 struct sgd_plan_t { plan_t p; uint32_t grid = 0, block = 256; std::vector<uint32_t> blk0; double algo_bytes = 0; };
 sgd_plan_t plan_sgd_update(std::vector<long> const &elems);
 
-// the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip)
-struct bn_args_t { // must match kernels/bn_f32.hip
-  float const *in; float const *dy;
-  float const *c0; float const *c1; float const *c2; float const *c3; float const *c4;
-  float *out;
-  float *w0; float *w1; float *w2; float *w3;
-  float *ws;
-  float *outs[8];
-  long n;
-  int B, C, HW, N;
-  int slab, nslabs;
-  int quads;
-  int step_img, step_pel;
-  float fN, eps, maf, omm, unb;
-};
-static_assert(sizeof(bn_args_t) == 13 * 8 + 8 * 8 + 8 + 9 * 4 + 5 * 4, "bn_args_t is declared with this layout by kernels/bn_f32.hip");
+// the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip, bn_args_t)
 // the kernels of one call in launch order: op 1 (a sum over slabs; mode 0 S1, 1 S2, 2 the bck_sums pair), 2 (the finalising step; fin 1 stats, 2 bck_sums), 3 fwd, 4 bck_in, 5 fan_out
 struct bn_launch_t { plan_t p; int op = 0; };
 struct bn_plan_t { std::vector<bn_launch_t> ls; double algo_bytes = 0; size_t ws_bytes = 0, ws_part = 0; };   // ws_part (the chunked chain): floats of slab partials in front of the totals
@@ -122,19 +54,12 @@ bn_plan_t plan_bn(bn_op_t const &b);
 plan_t bn_kernel_plan(int op, char const *kname, vect_string const &defs);   // one specialisation of kernels/bn_f32.hip (plan_bn's entries are these)
 string bn_plan_desc(bn_op_t const &b, bn_plan_t const &bp);
 
-struct rows_args_t { // must match kernels/conv_nhwc_rows_bf16.hip
-  void const *filts; void const *in; void *out; float const *bias;
-  int n_img, oc; unsigned filts_bytes, in_bytes, out_bytes; int out_ctot, out_coff; int n_chunks, rows_per_chunk; float lrn_alpha, lrn_beta, lrn_k;
-};
-
 struct sgemm_split_t { uint32_t m_main = 0; string tail_tile; double t_single = 0, t_split = 0; };
 static char const *const kBigTile = "256x256x16x2x4x1x1x32x2";
 struct sgemm_part_t { uint32_t m0 = 0, rows = 0, n0 = 0, cols = 0; string tile; };
 struct set_member_in_t { conv_geom_t g; bool patch_filts, pool; int grp_pad; };
 struct set_layout_t { std::vector<int> in_set, alone, variant_of; std::vector<plan_t const *> variants; std::vector<string> vkeys; int minw = 8; string skey; };
 
-// embedded kernel sources (kernels_embed.inc, included by native_kernels.cc)
-extern char const *const k_src_conv_nhwc_bf16_ptr, *const k_src_conv_nhwc_patch_bf16_ptr, *const k_src_winograd_f32_ptr;
 bool parse_tile(string const &s, tile_cfg_t &c);
 void launch(native_host_t *host, kernel_t &k, gemm_args_t &a, tile_cfg_t const &c);
 plan_t plan_sgemm(uint32_t M, uint32_t N, uint32_t K, int num_cus, string const &tile, bool bf16 = false, int batch = 1, bool allow_big = true);

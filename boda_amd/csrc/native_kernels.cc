@@ -5,8 +5,13 @@
 
 namespace bodahip {
 
-// kernel template sources, embedded at build time from kernels/*.hip (see build.py: kernels_embed.inc)
+// kernel template sources and their two headers, embedded at build time from kernels/ (see build.py: kernels_embed.inc): k_kernel_srcs[kernel_src_t], k_kernel_hdrs
+#define BODAHIP_KERNEL_TEXTS 1
 #include "kernels_embed.inc"
+static_assert(sizeof(k_kernel_srcs) / sizeof(k_kernel_srcs[0]) == kNumKernelSrcs, "one text per kernel_src_t value");
+kernel_text_t const &kernel_source(kernel_src_t s) { return k_kernel_srcs[s]; }
+kernel_text_t const *find_kernel_source(string const &name) { for (kernel_text_t const &k : k_kernel_srcs) if (name == k.name) return &k; return nullptr; }
+std::vector<kernel_text_t> const &kernel_headers() { static std::vector<kernel_text_t> const h(std::begin(k_kernel_hdrs), std::end(k_kernel_hdrs)); return h; }
 
 native_kernels_t::native_kernels_t(native_host_t *host_) : impl(new impl_t), host(host_) {
   if (char const *e = getenv("BODAHIP_SGEMM_TILE")) impl->tune["sgemm_tile"] = e;
@@ -93,7 +98,7 @@ void launch(native_host_t *host, kernel_t &k, gemm_args_t &a, tile_cfg_t const &
 
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log) {
   vect_string opts = p.defs; opts.push_back("-DKNAME=" + p.kname);
-  return hiprtc_compile(p.bn ? k_src_bn_f32 : p.sgd ? k_src_sgd_update_f32 : p.bck_ops ? k_src_bck_ops_f32 : p.bconv_in ? (p.bf16 ? k_src_bconv_in_bf16 : k_src_bconv_in_f32) : p.bconv_filts ? k_src_bconv_filts_f32 : p.bconv_fb ? (p.bf16 ? k_src_bconv_fb_bf16 : k_src_bconv_fb_f32) : p.nhwc_rows ? k_src_conv_nhwc_rows_bf16 : p.nhwc_multi ? k_src_conv_nhwc_multi_bf16 : p.nhwc_patch ? k_src_conv_nhwc_patch_bf16 : p.nhwc ? k_src_conv_nhwc_bf16 : p.patch16 ? k_src_conv_patch_bf16 : (p.cbig ? k_src_conv_big_f32 : p.big ? k_src_sgemm_big_f32 : p.fc ? k_src_fc_f32 : p.stream ? (p.quad ? k_src_k1_quad_f32 : k_src_k1_stream_f32) : (p.bf16 ? k_src_gemm_conv_bf16 : k_src_gemm_conv_f32)), p.kname, arch, opts, log, true);
+  return hiprtc_compile(kernel_source(p.src).text, p.kname, arch, opts, log, true, kernel_headers());
 }
 
 // grow-only scratch shared by the split-K slabs and the Winograd-domain tensors (like the reference's cudnn scratch var)
@@ -348,7 +353,7 @@ static void launch_patch16(native_kernels_t::impl_t *impl, native_host_t *host, 
   size_t const fbytes = (size_t)ncg * taps * g.OC * 16;
   if (fbytes >= 0x7ffffff0ull) unsup_err("hip_conv_bf16: re-laid-out filters of 2 GiB or more");
   ensure_ws(impl, host, ws_off + fbytes);
-  plan_t fp; fp.patch16 = true; fp.bf16 = true; fp.kname = "bodahip_filt_bf16"; fp.defs = {"-DFILT_ONLY=1"};
+  plan_t fp; fp.src = kSrc_conv_patch_bf16; fp.patch16 = true; fp.bf16 = true; fp.kname = "bodahip_filt_bf16"; fp.defs = {"-DFILT_ONLY=1"};
   kernel_t &fk = get_kernel(impl, host, fp);
   gemm_args_t fa; memset(&fa, 0, sizeof(fa));
   fa.I = filts; fa.D = (float *)((char *)impl->ws + ws_off); fa.Mi = g.OC; fa.C = g.C; fa.K = taps;
@@ -361,7 +366,6 @@ static void launch_patch16(native_kernels_t::impl_t *impl, native_host_t *host, 
 }
 
 // bf16 conv1-type layers (stride s in both axes, few input channels): space-to-depth front end + the patch kernel (kernels/conv_patch_bf16.hip)
-struct s2d_args_t { float const *src; float *dst; int B, C, H, W, OC, KH, KW; int S, C2, H2, W2; int oy, ox; int filt; int mode, c2_lo; };
 bool s2d_geom(conv_geom_t const &g, conv_geom_t &g2, int &pry, int &prx) {
   if (getenv("BODAHIP_NO_S2D")) return false;
   int const s = g.SY;
@@ -375,15 +379,6 @@ bool s2d_geom(conv_geom_t const &g, conv_geom_t &g2, int &pry, int &prx) {
 }
 
 // ---- F(2x2,3x3) Winograd path (kernels/winograd_f32.hip): opt-in, tune key conv_algo = "winograd" -----------------------------------
-struct wino_args_t { // must match kernels/winograd_f32.hip
-  float const *in; float const *filts; float const *bias; float *out;
-  float *U; float *V; float *M;
-  int B0, Bc;
-  int C, H, W, OC, OH, OW;
-  int TH, TW, Tc;
-  int PY, PX, relu;
-  int out_ctot, out_coff;
-};
 // conv_algo = "winograd_all": every 3x3 / stride-1 convolution; "winograd": only where it measured ahead of the direct kernel -- with
 // fewer than 96 input channels the transform-domain sgemms are too short (K = in_chan) and the streaming transforms dominate
 // (ResNet res2 64->64 @56x56: 228 vs 179 us direct; res3 128->128 @28x28: 145 vs 172; res4 256->256 @14x14: 108 vs 185)
@@ -405,7 +400,7 @@ void native_kernels_t::conv_winograd(float const *filts, float const *biases, fl
     if (host->nh_capturing()) rt_err("graph capture: Winograd transform kernels are not compiled yet -- run the call list once before capturing it");
     string log;
     vect_string wdefs; if (char const *e = getenv("BODAHIP_EXTRA_DEFS")) { std::istringstream is(e); string tok; while (is >> tok) wdefs.push_back(tok); } // (experiments)
-    std::vector<char> code = hiprtc_compile(k_src_winograd_f32, "bodahip_winograd", host->nh_arch(), wdefs, &log, true);
+    std::vector<char> code = hiprtc_compile(kernel_source(kSrc_winograd_f32).text, "bodahip_winograd", host->nh_arch(), wdefs, &log, true, kernel_headers());
     hip_err_chk(hipModuleLoadData(&impl->wino_mod, code.data()), "hipModuleLoadData(winograd)");
     hip_err_chk(hipModuleGetFunction(&impl->wino_filt, impl->wino_mod, "bodahip_wino_filt"), "hipModuleGetFunction(wino_filt)");
     hip_err_chk(hipModuleGetFunction(&impl->wino_in, impl->wino_mod, "bodahip_wino_in"), "hipModuleGetFunction(wino_in)");
@@ -508,7 +503,7 @@ void native_kernels_t::conv(float const *filts, float const *biases, float const
       size_t const off_in2 = 0, off_f2 = (in2 * 4 + 255) & ~size_t(255), off_fp = (off_f2 + f2 * 4 + 255) & ~size_t(255);
       size_t const fpb = (size_t)(g2.C / 8) * g2.KH * g2.KW * g.OC * 16;
       ensure_ws(impl, host, off_fp + fpb);
-      plan_t sp; sp.patch16 = true; sp.bf16 = true; sp.kname = "bodahip_s2d"; sp.defs = {"-DS2D_ONLY=1"};
+      plan_t sp; sp.src = kSrc_conv_patch_bf16; sp.patch16 = true; sp.bf16 = true; sp.kname = "bodahip_s2d"; sp.defs = {"-DS2D_ONLY=1"};
       kernel_t &sk = get_kernel(impl, host, sp);
       s2d_args_t sa; memset(&sa, 0, sizeof(sa));
       sa.B = g.B; sa.C = g.C; sa.H = g.H; sa.W = g.W; sa.OC = g.OC; sa.KH = g.KH; sa.KW = g.KW; sa.S = g.SY; sa.C2 = g2.C;
@@ -571,8 +566,8 @@ void native_kernels_t::conv(float const *filts, float const *biases, float const
   ga.out_ctot = out_ctot; ga.out_coff = out_coff;
   if (out_bytes >= 0x7ffffff0ull) unsup_err("hip_conv: out of 2 GiB or more is not supported (32-bit store offsets, masked lanes use offset 2^31)");
   ga.D_bytes = (unsigned)out_bytes;
-  if (p.rows) { ktab_t const kt = get_rtab(impl, host, g); ga.ktab = kt.d; ga.ktab_n = kt.n; }
-  else if (!p.ipconv && !p.k1 && !p.patch && !p.stream && !p.patch16) { ktab_t const kt = get_ktab(impl, host, g); ga.ktab = kt.d; ga.ktab_n = kt.n; }
+  if (p.rows) { ktab_t const kt = get_rtab(impl, host, g); ga.ktab = (int const *)kt.d; ga.ktab_n = kt.n; }
+  else if (!p.ipconv && !p.k1 && !p.patch && !p.stream && !p.patch16) { ktab_t const kt = get_ktab(impl, host, g); ga.ktab = (int const *)kt.d; ga.ktab_n = kt.n; }
   ga.tiles_i = (g.OC + cfg.BI - 1) / cfg.BI; ga.tiles_j = (int)((Nj + cfg.BJ - 1) / cfg.BJ);
   if (p.patch16) { launch_patch16(impl, host, p, k, ga, filts, g, 0); 
     last_launch.kernel = p.kname; last_launch.cfg = cfg; last_launch.grid = (uint32_t)(ga.tiles_i * ga.tiles_j); last_launch.block = cfg.threads();
@@ -618,7 +613,7 @@ void native_kernels_t::conv(float const *filts, float const *biases, float const
       } else {
       ts_off = (xb + 255) & ~size_t(255);
       ensure_ws(impl, host, ts_off + (getenv("BODAHIP_CBIG_TSTAMP") ? (size_t)ga.tiles_i * ga.tiles_j * 128 : 0));
-      plan_t xp; xp.cbig = true; xp.kname = "bodahip_conv_big_xpose"; xp.defs = {"-DXPOSE_ONLY=1"};
+      plan_t xp; xp.src = kSrc_conv_big_f32; xp.cbig = true; xp.kname = "bodahip_conv_big_xpose"; xp.defs = {"-DXPOSE_ONLY=1"};
       kernel_t &xk = get_kernel(impl, host, xp);
       float const *src = filts; float *dst = (float *)impl->ws; int Mi = g.OC, Mi4 = (int)mi4, Kk = (int)Kt, Kp = (int)kp;
       void *xparams[] = {&src, &dst, &Mi, &Mi4, &Kk, &Kp};
@@ -634,7 +629,7 @@ void native_kernels_t::conv(float const *filts, float const *biases, float const
     if (p.cbig && p.split_pels > 0) {   // two-level tiling along the pels: this plan's tiles over the first split_pels pels, the tail plan's over the rest
       ga.tiles_j = (int)(p.split_pels / cfg.BJ);
       launch(host, k, ga, cfg);
-      plan_t tp; tp.cbig = true; tp.kname = p.kname; tp.cfg = p.tail_cfg; tp.defs = p.tail_defs; tp.patch = p.patch; tp.k1 = p.k1; tp.rdec = p.rdec;
+      plan_t tp; tp.src = p.src; tp.cbig = true; tp.kname = p.kname; tp.cfg = p.tail_cfg; tp.defs = p.tail_defs; tp.patch = p.patch; tp.k1 = p.k1; tp.rdec = p.rdec;
       kernel_t &k2 = get_kernel(impl, host, tp);
       gemm_args_t g2 = ga; g2.tiles_i = (g.OC + tp.cfg.BI - 1) / tp.cfg.BI; g2.tiles_j = (int)((Nj - p.split_pels + tp.cfg.BJ - 1) / tp.cfg.BJ); g2.bsJ = p.split_pels; g2.ws = tstamp ? (float *)((char *)ga.ws + ts_main) : nullptr;
       launch(host, k2, g2, tp.cfg);
@@ -670,7 +665,7 @@ bool plan_k1_chain(conv_geom_t const &g, int oc2, bool relu2, plan_t &p) {
   long const lds = 4 * (kp * ((OCB * 32) | 1) + OCB * 32 + kp2 * ((OCB2 * 32) | 1) + OCB2 * 32);
   if (lds > 160 * 1024) return false;
   int RING = 8; while (ksteps % RING) --RING;
-  p = plan_t(); p.stream = true; p.quad = true; p.kname = "bodahip_k1_chain_f32";
+  p = plan_t(); p.src = kSrc_k1_quad_f32; p.stream = true; p.quad = true; p.kname = "bodahip_k1_chain_f32";
   p.cfg.BI = OCB * 32; p.cfg.BJ = 4 * 128; p.cfg.BK = g.C; p.cfg.WI = 1; p.cfg.WJ = 4; p.cfg.MINW = 1; p.cfg.SPLITK = 1; p.cfg.MT = 32; p.cfg.PF = RING;
   p.defs = {"-DKC=" + std::to_string(g.C), "-DHW=" + std::to_string(g.OH * g.OW), "-DWJ=4", "-DOCB=" + std::to_string(OCB), "-DRING=" + std::to_string(RING), "-DMINW=1",
             string("-DRELU=") + (g.relu ? "1" : "0"), "-DEDGE_OC=1", "-DCHAIN=1", "-DMID=" + std::to_string(g.OC), "-DOCB2=" + std::to_string(OCB2),
@@ -710,7 +705,7 @@ void native_kernels_t::conv_k1_chain(float const *filts, float const *biases, fl
 
 
 kernel_t &get_kernel(native_kernels_t::impl_t *impl, native_host_t *host, plan_t const &p) {
-  string key = p.kname; for (auto const &d : p.defs) key += " " + d;
+  string key = string(kernel_source(p.src).name) + ":" + p.kname; for (auto const &d : p.defs) key += " " + d;
   auto it = impl->kernels.find(key);
   if (it != impl->kernels.end()) return it->second;
   if (host->nh_capturing()) rt_err("graph capture: native kernel '" + key + "' is not specialised yet -- run the call list once before capturing it");

@@ -38,7 +38,12 @@
 namespace bodahip {
 
 void hip_err_chk(hipError_t e, char const *what);
-std::vector<char> hiprtc_compile(string const &src, string const &name, string const &arch, vect_string const &opts, string *log_out, bool use_cache);
+struct kernel_text_t { char const *name; char const *text; };   // an embedded kernels/<name>.hip or kernels/<name> header (kernels_embed.inc)
+// `headers`: what `src` may #include by name (in-memory; their texts are part of the cache key like src itself)
+std::vector<char> hiprtc_compile(string const &src, string const &name, string const &arch, vect_string const &opts, string *log_out, bool use_cache,
+                                 std::vector<kernel_text_t> const &headers = std::vector<kernel_text_t>());
+kernel_text_t const *find_kernel_source(string const &name);    // by its name in build.py's KERNELS; nullptr: none
+std::vector<kernel_text_t> const &kernel_headers();             // what every kernels/*.hip includes: kernels/kernel_args.h, kernels/device_prelude.h
 void hiprtc_compile_stats(uint64_t *hits, uint64_t *misses, double *compile_ms);   // process-wide: code objects from the on-disk cache / compiled, time spent compiling
 string cucl_prelude();
 string default_cache_dir();

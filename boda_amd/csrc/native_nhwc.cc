@@ -31,24 +31,7 @@ void native_kernels_t::conv_nhwc_rows(void const *filts, float const *biases, vo
 }
 
 
-struct grp_args_t { // must match kernels/conv_nhwc_bf16.hip
-  int n; int oc0[4]; int noc[4];
-  void *D[4]; unsigned D_bytes[4]; int ctot[4]; int coff[4];
-};
-// ---- hip_conv_nhwc_multi: several INDEPENDENT channels-last convolutions as one launch (kernels/conv_nhwc_multi_bf16.hip) ------------------------------------
-struct multi_prob_t { // must match prob_t of kernels/conv_nhwc_multi_bf16.hip (128 bytes)
-  void const *I; void const *J; void *D; float const *bias;
-  unsigned I_bytes, J_bytes, D_bytes; int Mi;
-  int Nj, CIN, KH, KW;
-  int SY, SX, PY, PX;
-  int CH, CW, COH, COW;
-  int kCG, kKC, nK, relu;
-  int out_ctot, out_coff, tiles_i, tiles_j;
-};
-static_assert(sizeof(multi_prob_t) == 128, "multi_prob_t must stay 128 bytes (kernel-side prob_t)");
-struct multi_tile_t { int prob, tile_i, tile_j, pad; };
-struct multi_args_t { multi_prob_t const *probs; multi_tile_t const *tiles; int n_tiles; int n_probs; };
-
+// ---- hip_conv_nhwc_multi: several INDEPENDENT channels-last convolutions as one launch (kernels/conv_nhwc_multi_bf16.hip; multi_prob_t, multi_tile_t, multi_args_t) -------
 // One tile shape for the whole launch (the kernel is specialised on it, not on any member's geometry).  tile: "BIxBJxBKxWIxWJ[xMINW[x1[x32[xNBUF]]]]" or "".
 // Default 64 x 128 x 64, 2 x 2 waves, a ring of TWO (48 KB of LDS: three workgroups, i.e. three waves per SIMD, per CU) -- the members are small (that is why they
 // are here), mostly narrow in out_chan (16-256) and short in K (3-13 steps), so what hides their latency is co-resident workgroups, not a deeper ring.  Measured on
@@ -56,7 +39,7 @@ struct multi_args_t { multi_prob_t const *probs; multi_tile_t const *tiles; int 
 // 64x256x32 ring 3 224 | 64x64x64 266 | 128x128x64 ring 3 326 (the members one by one: 533, of which 260 are launch floors).
 plan_t plan_conv_nhwc_multi(std::vector<conv_geom_t> const &gs, string const &tile, bool out_f32) {
   (void)gs;
-  plan_t p; p.nhwc = true; p.nhwc_multi = true; p.bf16 = true; p.kname = "bodahip_conv_nhwc_multi_bf16";
+  plan_t p; p.src = kSrc_conv_nhwc_multi_bf16; p.nhwc = true; p.bf16 = true; p.kname = "bodahip_conv_nhwc_multi_bf16";
   tile_cfg_t c; c.MT = 32; c.SPLITK = 1; c.PF = 2; c.BI = 64; c.BJ = 128; c.BK = 64; c.WI = 2; c.WJ = 2; c.MINW = 3;
   if (!tile.empty()) {
     int nbuf = 3;
@@ -146,10 +129,8 @@ static char const *const k_set_macros[] = {"BI", "BJ", "BK", "WI", "WJ", "MINW",
 string set_kernel_source(std::vector<plan_t const *> const &variants, int threads, int minw) {
   std::ostringstream o;
   o << "// generated by native_kernels.cc (conv_nhwc_set): " << variants.size() << " member specialisations in one kernel\n";
-  o << "#define BODAHIP_AS_MEMBER 1\n#define BODAHIP_ARGS_DEFINED 1\n";
-  o << "struct gemm_args_t { float const *I; float const *J; float *D; float const *bias; int Mi, Nj, K; int ldI, ldJ, ldD; int C, H, W, OH, OW; int tiles_i, tiles_j; int splitk, kt_per;\n"
-       "  float *ws; long ws_slab; unsigned I_bytes, J_bytes; unsigned D_bytes; int out_ctot, out_coff; int const *ktab; int ktab_n; long bsI, bsJ, bsD; };\n"
-       "struct grp_args_t { int n; int oc0[4]; int noc[4]; void *D[4]; unsigned D_bytes[4]; int ctot[4]; int coff[4]; };\n";
+  // the two headers once at global scope: their include guards make the members' own includes (inside the member namespaces) empty
+  o << "#define BODAHIP_AS_MEMBER 1\n#include \"kernel_args.h\"\n#include \"device_prelude.h\"\n";
   for (size_t v = 0; v < variants.size(); ++v) {
     plan_t const &p = *variants[v];
     for (string const &d : p.defs) {   // "-DNAME=value"
@@ -157,10 +138,9 @@ string set_kernel_source(std::vector<plan_t const *> const &variants, int thread
       if (d.compare(0, 2, "-D") != 0 || eq == string::npos) rt_err("conv_nhwc_set: unexpected kernel option '" + d + "'");
       o << "#define " << d.substr(2, eq - 2) << " " << d.substr(eq + 1) << "\n";
     }
-    o << "#define KNAME run\nnamespace member_v" << v << " {\n" << (p.nhwc_patch ? k_src_conv_nhwc_patch_bf16_ptr : k_src_conv_nhwc_bf16_ptr) << "\n}\n";
+    o << "#define KNAME run\nnamespace member_v" << v << " {\n" << kernel_source(p.src).text << "\n}\n";
     for (char const *m : k_set_macros) o << "#undef " << m << "\n";
   }
-  o << "struct set_args_t { gemm_args_t const *m; int const *ends; int const *variant; grp_args_t const *g; int n; };\n";
   // the largest LDS need of the members, as a constant expression
   o << "namespace { constexpr int set_max(int a, int b) { return a > b ? a : b; }\nconstexpr int kSmemAll = ";
   for (size_t v = 0; v < variants.size(); ++v) o << "set_max(member_v" << v << "::member_smem_bytes, ";
@@ -279,7 +259,7 @@ void native_kernels_t::conv_nhwc_set(int n, multi_member_t const *ms, bool const
     if (kit == impl->kernels.end()) {
       if (host->nh_capturing()) rt_err("graph capture: this hip_conv_nhwc_set kernel is not compiled yet -- run the call list once before capturing it");
       string log;
-      std::vector<char> code = hiprtc_compile(set_kernel_source(L.variants, 256, std::max(1, L.minw)), "bodahip_conv_nhwc_set", host->nh_arch(), vect_string(), &log, true);
+      std::vector<char> code = hiprtc_compile(set_kernel_source(L.variants, 256, std::max(1, L.minw)), "bodahip_conv_nhwc_set", host->nh_arch(), vect_string(), &log, true, kernel_headers());
       kernel_t k;
       hip_err_chk(hipModuleLoadData(&k.mod, code.data()), "hipModuleLoadData(conv_nhwc_set)");
       hip_err_chk(hipModuleGetFunction(&k.func, k.mod, "bodahip_conv_nhwc_set"), "hipModuleGetFunction(conv_nhwc_set)");
@@ -306,7 +286,7 @@ void native_kernels_t::conv_nhwc_set(int n, multi_member_t const *ms, bool const
       hip_err_chk(hipStreamSynchronize(host->nh_stream()), "hipStreamSynchronize(set table)");
       it = impl->ktabs.emplace(tkey, dev).first;
     }
-    struct { gemm_args_t const *m; int const *ends; int const *variant; grp_args_t const *g; int n; } sa;
+    set_args_t sa;
     sa.m = (gemm_args_t const *)it->second; sa.ends = (int const *)((char *)it->second + eo); sa.variant = (int const *)((char *)it->second + vo);
     sa.g = (grp_args_t const *)((char *)it->second + go); sa.n = (int)ns;
     void *params[] = {&sa};
@@ -390,7 +370,7 @@ void native_kernels_t::conv_nhwc(void const *filts, float const *biases, void co
   void *params[] = {&ga, &res};   // (the plain kernel declares one argument and reads only that)
   hip_err_chk(host->nh_launch(k.func, (uint32_t)(ga.tiles_i * ga.tiles_j * ga.splitk), 1, (uint32_t)cfg.threads(), params), "hipModuleLaunchKernel(conv_nhwc_bf16)");
   if (cfg.SPLITK > 1 && !p.ksl) {
-    plan_t rp; rp.nhwc = true; rp.bf16 = true; rp.kname = "bodahip_nhwc_splitk_reduce";
+    plan_t rp; rp.src = kSrc_conv_nhwc_bf16; rp.nhwc = true; rp.bf16 = true; rp.kname = "bodahip_nhwc_splitk_reduce";
     rp.defs = {"-DREDUCE_ONLY=1", string("-DRELU=") + (g.relu ? "1" : "0"), string("-DOUT_F32=") + (out_f32 ? "1" : "0")};
     kernel_t &rk = get_kernel(impl, host, rp);
     bool const v4 = (g.OC % 4 == 0) && (((out_ctot | out_coff) & 3) == 0);

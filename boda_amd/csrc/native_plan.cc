@@ -136,7 +136,7 @@ static bool plan_k1_stream(conv_geom_t const &g, int num_cus, string const &spec
     if (QWJ) {
       if (!QMINW) QMINW = (QOCB == 3) ? 2 : ((QOCB == 2) ? 3 : 4);   // registers: OCB*64 accumulators + 4*RING operands + ~30
       QMINW = (int)std::max(1l, std::min((long)QMINW, std::max(1l, (160l * 1024) / lds(1, QOCB)) * ((QWJ + 3) / 4)));
-      p.stream = true; p.quad = true; p.kname = "bodahip_k1_quad_f32";
+      p.src = kSrc_k1_quad_f32; p.stream = true; p.quad = true; p.kname = "bodahip_k1_quad_f32";
       p.cfg.BI = QOCB * 32; p.cfg.BJ = QWJ * 128; p.cfg.BK = g.C; p.cfg.WI = 1; p.cfg.WJ = QWJ; p.cfg.MINW = QMINW; p.cfg.SPLITK = 1; p.cfg.MT = 32; p.cfg.PF = QRING;
       p.defs = {"-DKC=" + std::to_string(g.C), "-DHW=" + std::to_string(g.OH * g.OW), "-DWJ=" + std::to_string(QWJ), "-DOCB=" + std::to_string(QOCB),
                 "-DRING=" + std::to_string(QRING), "-DMINW=" + std::to_string(QMINW), string("-DRELU=") + (g.relu ? "1" : "0"), string("-DEDGE_OC=") + ((g.OC % (QOCB * 32)) ? "1" : "0")};
@@ -163,7 +163,7 @@ static bool plan_k1_stream(conv_geom_t const &g, int num_cus, string const &spec
   }
   if (!MINW) { int const r = regs(OCB, CB); MINW = std::max(1, std::min(8, 512 / r)); int const wpw = (WI * WJ + 3) / 4; // waves per SIMD of one workgroup
                long const by_lds = std::max(1l, (160l * 1024) / lds(WI, OCB)); MINW = (int)std::max(1l, std::min((long)MINW, by_lds * wpw)); }
-  p.stream = true; p.kname = "bodahip_k1_stream_f32";
+  p.src = kSrc_k1_stream_f32; p.stream = true; p.kname = "bodahip_k1_stream_f32";
   p.cfg.BI = WI * OCB * 32; p.cfg.BJ = WJ * CB * 32; p.cfg.BK = g.C; p.cfg.WI = WI; p.cfg.WJ = WJ; p.cfg.MINW = MINW; p.cfg.SPLITK = 1; p.cfg.MT = 32; p.cfg.PF = 1;
   p.defs = {"-DKC=" + std::to_string(g.C), "-DHW=" + std::to_string(g.OH * g.OW), "-DWI=" + std::to_string(WI), "-DWJ=" + std::to_string(WJ),
             "-DOCB=" + std::to_string(OCB), "-DCB=" + std::to_string(CB), "-DMINW=" + std::to_string(MINW), string("-DRELU=") + (g.relu ? "1" : "0"),
@@ -202,7 +202,7 @@ static void bf16_cfg(tile_cfg_t &c, bool gather, long Mi = 0, long Nj = 0, long 
 
 static char const *const kStg64 = "64x64x16x2x2x4x1x32x2x3";   // the staging-wave kernel's 64 x 64 form (tile field 10 == 3: multiplying waves spelled out)
 plan_t plan_sgemm(uint32_t M, uint32_t N, uint32_t K, int num_cus, string const &tile, bool bf16, int batch, bool allow_big) {
-  plan_t p; p.kname = bf16 ? "bodahip_sgemm_bf16" : "bodahip_sgemm_f32"; p.bf16 = bf16;
+  plan_t p; p.src = bf16 ? kSrc_gemm_conv_bf16 : kSrc_gemm_conv_f32; p.kname = bf16 ? "bodahip_sgemm_bf16" : "bodahip_sgemm_f32"; p.bf16 = bf16;
   p.cfg = choose_cfg((int)M, (int)std::min<uint64_t>((uint64_t)N * batch, 0x7fffffffull), (int)K, num_cus, false, bf16); // (a batch deals batch x the tiles)
   if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) rt_err("bad sgemm_tile '" + tile + "'"); }
   if (bf16) {
@@ -223,7 +223,7 @@ plan_t plan_sgemm(uint32_t M, uint32_t N, uint32_t K, int num_cus, string const 
     bool const ok = (nmw == 8 || nmw == 4 || w12) && (ti == 4 || ti == 2 || ti == 1) && (tj == 2 || tj == 1) && c.BK >= 4 && c.BK <= 32 && c.BK % 4 == 0 && (c.BK * (c.BI / 4)) % 256 == 0 &&
                     (c.BK * (c.BJ / 4)) % 256 == 0 && (c.PF == 2 || c.PF == 4) && c.MT == 32 && c.SPLITK == 1 && c.MINW >= 1 && c.MINW <= 8 && (nstg == 3 || nstg == 4) && 4l * nstg * c.BK * (c.BI + c.BJ + 8) <= 160 * 1024;
     if (!ok || batch != 1 || M % 4 || N % 4 || !allow_big) unsup_err("hip_sgemm: unsupported staging-wave tile " + c.str() + " (8 | 4 multiplying waves of 4 | 2 | 1 x 2 | 1 blocks or 4 x 3 | 3 x 4 of 2 x 2, whole float4 units per staging thread, M and N multiples of 4)");
-    p.big = true; p.kname = "bodahip_sgemm_big_f32";
+    p.src = kSrc_sgemm_big_f32; p.kname = "bodahip_sgemm_big_f32";
     p.defs = {"-DBKS=" + std::to_string(c.BK), "-DPF=" + std::to_string(c.PF), "-DTBI=" + std::to_string(c.BI), "-DTBJ=" + std::to_string(c.BJ), "-DWI=" + std::to_string(c.WI),
               "-DWJ=" + std::to_string(c.WJ), "-DMINW=" + std::to_string(c.MINW)};
     if (c.KHO) p.defs.push_back("-DNSTG=" + std::to_string(nstg));
@@ -241,7 +241,7 @@ plan_t plan_sgemm(uint32_t M, uint32_t N, uint32_t K, int num_cus, string const 
       if (e && *e) { if (sscanf(e, "%dx%d", &bks, &pf) != 2 || bks < 4 || bks > 32 || bks % 4 || (pf != 2 && pf != 4)) rt_err(string("bad BODAHIP_SGEMM_BIG '") + e + "' (off | BKSxPF)"); }
       if (bks * (p.cfg.BI / 4) % 256 || bks * (p.cfg.BJ / 4) % 256) bks = 8;   // (whole float4 units per staging thread: BKS x TB / 4 a multiple of 256)
       int const minw = (p.cfg.BI == 128 && p.cfg.BJ == 128) ? ((!tile.empty() && p.cfg.MINW >= 1) ? std::min(p.cfg.MINW, 2) : 2) : 1;
-      p.big = true; p.kname = "bodahip_sgemm_big_f32"; p.cfg.BK = bks; p.cfg.PF = pf; p.cfg.WI = 3; p.cfg.WJ = 4; p.cfg.MINW = minw;
+      p.src = kSrc_sgemm_big_f32; p.kname = "bodahip_sgemm_big_f32"; p.cfg.BK = bks; p.cfg.PF = pf; p.cfg.WI = 3; p.cfg.WJ = 4; p.cfg.MINW = minw;
       p.defs = {"-DBKS=" + std::to_string(bks), "-DPF=" + std::to_string(pf)};
       if (!(p.cfg.BI == 256 && p.cfg.BJ == 256)) {   // (the 256 x 256 form keeps its option string: its code objects stay the cached ones)
         bool const tall = (p.cfg.BI == 256 && p.cfg.BJ == 128);    // 256 x 128: 4 x 2 multiplying waves of 64 x 64; the others 2 x 4 (128 x 128: 64 x 32; 128 x 256: 64 x 64)
@@ -302,7 +302,7 @@ bool plan_patch_bf16(conv_geom_t const &g, int num_cus, plan_t &p) {
   }
   if (pick < 0) return false;
   cand_t const &c = cands[pick];
-  p.patch16 = true; p.bf16 = true; p.cg = cg; p.kname = "bodahip_conv_patch_bf16";
+  p.src = kSrc_conv_patch_bf16; p.patch16 = true; p.bf16 = true; p.cg = cg; p.kname = "bodahip_conv_patch_bf16";
   p.cfg.BI = c.bi; p.cfg.BJ = c.bj; p.cfg.BK = cg * 8 * taps; p.cfg.WI = c.wi; p.cfg.WJ = c.wj; p.cfg.MINW = 2; p.cfg.SPLITK = 1; p.cfg.MT = 32; p.cfg.PF = 1;
   p.defs = {"-DBI=" + std::to_string(c.bi), "-DBJ=" + std::to_string(c.bj), "-DWI=" + std::to_string(c.wi), "-DWJ=" + std::to_string(c.wj), "-DMINW=2",
             "-DCG=" + std::to_string(cg), "-DKH=" + std::to_string(g.KH), "-DKW=" + std::to_string(g.KW), "-DSY=" + std::to_string(g.SY),
@@ -329,7 +329,7 @@ plan_t plan_conv_nhwc(conv_geom_t const &g, int num_cus, string const &tile, boo
   if (g.H >= 32768 || g.W >= 32768) unsup_err("hip_conv_nhwc: planes of 32768 rows / columns or more are not supported");
   long const Nj = (long)g.B * g.OH * g.OW;
   int const cg = g.C / 8, kc = cg * g.KH * g.KW;
-  plan_t p; p.nhwc = true; p.bf16 = true; p.kname = "bodahip_conv_nhwc_bf16";
+  plan_t p; p.src = kSrc_conv_nhwc_bf16; p.nhwc = true; p.bf16 = true; p.kname = "bodahip_conv_nhwc_bf16";
   tile_cfg_t c; c.MT = 32; c.SPLITK = 1; c.PF = 1;
   // K step: 64 (8 chunks) when a tap's chunks divide into it -- or when K is long anyway; 32 otherwise
   // Round 5 (tools/ksl_sweep.py, every 1x1 layer of GoogLeNet at 64 images under ten tiles): on SMALL maps (14 x 14 and 7 x 7 at 64 images: 3-12 k pels, 100-600
@@ -469,7 +469,7 @@ plan_t plan_conv_nhwc_patch(conv_geom_t const &g, int num_cus, string const &til
   static cand_t const cands_direct[] = {{128, 128, 4, 1, 2, 0}, {64, 256, 2, 2, 2, 0}, {64, 128, 2, 2, 2, 0}, {128, 64, 4, 1, 2, 0}, {32, 128, 1, 4, 2, 0}, {128, 256, 2, 2, 2, 4}, {256, 128, 4, 1, 2, 4}};
   cand_t const *const cands = adirect ? cands_direct : cands_staged;
   int const n_cands = adirect ? (int)(sizeof(cands_direct) / sizeof(cand_t)) : (int)(sizeof(cands_staged) / sizeof(cand_t));
-  plan_t p; p.nhwc = true; p.nhwc_patch = true; p.bf16 = true; p.kname = "bodahip_conv_nhwc_patch_bf16";
+  plan_t p; p.src = kSrc_conv_nhwc_patch_bf16; p.nhwc = true; p.nhwc_patch = true; p.bf16 = true; p.kname = "bodahip_conv_nhwc_patch_bf16";
   tile_cfg_t c; c.MT = 32; c.SPLITK = 1; c.PF = 1;
   int pick_pf = 0;
   if (!tile.empty()) {
@@ -582,7 +582,7 @@ bool plan_conv_nhwc_rows(conv_geom_t const &g, post_ops_t const &post, int num_c
   };
   while (tr > 1 && lds(tr) > 160 * 1024) --tr;
   if (lds(tr) > 160 * 1024) return no("the input rows of one output row do not fit the LDS");
-  p = plan_t(); p.nhwc = true; p.nhwc_rows = true; p.bf16 = true; p.kname = "bodahip_conv_nhwc_rows_bf16"; p.cg = cg; p.rows = tr;
+  p = plan_t(); p.src = kSrc_conv_nhwc_rows_bf16; p.nhwc = true; p.bf16 = true; p.kname = "bodahip_conv_nhwc_rows_bf16"; p.cg = cg; p.rows = tr;
   tile_cfg_t c; c.MT = 32; c.SPLITK = 1; c.PF = 1; c.BI = 64; c.BJ = 256; c.BK = g.C * taps; c.WI = 1; c.WJ = wj; c.MINW = 1;
   p.cfg = c;
   p.defs = {"-DCIN=" + std::to_string(g.C), "-DCG=" + std::to_string(cg), "-DKH=" + std::to_string(g.KH), "-DKW=" + std::to_string(g.KW), "-DPY=" + std::to_string(g.PY), "-DPX=" + std::to_string(g.PX),
@@ -646,7 +646,7 @@ bool plan_ipconv_dma(conv_geom_t const &g, int num_cus, plan_t &p) {
   if (tiles * 4 < num_cus * 3 && string(getenv("BODAHIP_IPCONV_DMA")) != "force") return false;   // fewer workgroups than 3/4 of the CUs: finer (16x16-MFMA) tiles of the gather kernel do better
   tile_cfg_t c; c.BI = 64; c.BJ = 64; c.BK = 32; c.WI = 2; c.WJ = 2; c.MINW = 1; c.SPLITK = 1; c.MT = 32; c.PF = 8;
   if (char const *e = getenv("BODAHIP_IPCONV_DMA_NBUF")) c.PF = std::max(2, std::min(8, atoi(e)));
-  p = plan_t(); p.nhwc = true; p.kname = "bodahip_conv_nhwc_f32"; p.cfg = c;
+  p = plan_t(); p.src = kSrc_conv_nhwc_bf16; p.nhwc = true; p.kname = "bodahip_conv_nhwc_f32"; p.cfg = c;
   p.defs = {"-DBI=64", "-DBJ=64", "-DBK=32", "-DWI=2", "-DWJ=2", "-DMINW=1", "-DCIN=" + std::to_string(Kt), "-DKH=1", "-DKW=1", "-DSY=1", "-DSX=1", "-DPY=0", "-DPX=0",
             "-DCH=1", "-DCW=1", "-DCOH=1", "-DCOW=1", string("-DRELU=") + (g.relu ? "1" : "0"), "-DOUT_F32=1", "-DIN_F32=1", "-DNBUF=" + std::to_string(c.PF)};
   if (char const *e = getenv("BODAHIP_EXTRA_DEFS")) { std::istringstream is(e); string tok; while (is >> tok) p.defs.push_back(tok); }
@@ -710,7 +710,7 @@ static bool plan_rdec(conv_geom_t const &g, int num_cus, plan_t &p) {
   }
   if (best < 0) return false;
   check_cfg(best_c, false, true);
-  p = plan_t(); p.kname = "bodahip_conv_f32"; p.patch = true; p.rdec = true; p.cfg = best_c;
+  p = plan_t(); p.src = kSrc_gemm_conv_f32; p.kname = "bodahip_conv_f32"; p.patch = true; p.rdec = true; p.cfg = best_c;
   p.defs = cfg_defs(p.cfg);
   p.defs.push_back(string("-DI_MODE=") + ((Kt % 4 == 0 && bk % 4 == 0) ? "2" : ((Kt % 2 == 0) ? "4" : "3")));
   for (string const &d : {string("-DJ_MODE=7"), string("-DRDEC=1"), "-DC0=" + std::to_string(g.C), "-DH0=" + std::to_string(g.H), "-DKH0=" + std::to_string(g.KH), "-DSY0=" + std::to_string(g.SY),
@@ -765,7 +765,7 @@ static bool conv_big_form(conv_geom_t const &g, tile_cfg_t const &c, conv_big_fo
 static plan_t plan_conv_big(conv_geom_t const &g0, tile_cfg_t const &c) {
   string why; conv_big_form_t f;
   if (!conv_big_form(g0, c, f, &why)) unsup_err("native kernel: unsupported staging-wave tile " + c.str() + " (" + why + ")");
-  plan_t p; p.cbig = true; p.k1 = (f.jmode == 5); p.patch = (f.jmode == 7); p.rdec = f.rdec; p.kname = "bodahip_conv_big_f32"; p.cfg = c; p.cfg.BK = f.bks;
+  plan_t p; p.src = kSrc_conv_big_f32; p.cbig = true; p.k1 = (f.jmode == 5); p.patch = (f.jmode == 7); p.rdec = f.rdec; p.kname = "bodahip_conv_big_f32"; p.cfg = c; p.cfg.BK = f.bks;
   conv_geom_t g = g0; if (f.rdec) { g.KH = 1; g.SY = 1; g.H = g0.OH; }   // (the decimated presentation: 1 x KW kernels, stride 1 in y, OH rows)
   p.defs = {"-DTBI=" + std::to_string(c.BI), "-DTBJ=" + std::to_string(c.BJ), "-DWI=" + std::to_string(c.WI), "-DWJ=" + std::to_string(c.WJ), "-DBKS=" + std::to_string(f.bks),
             "-DPF=" + std::to_string(c.PF), "-DNSTG=" + std::to_string(f.nstg), "-DMINW=" + std::to_string(c.MINW), "-DI_VW=" + std::to_string(f.ivw), "-DJ_MODE=" + std::to_string(f.jmode),
@@ -792,7 +792,8 @@ static plan_t plan_conv_tiled(conv_geom_t const &g, int num_cus, string const &t
   if (!bf16 && tile.empty() && plan_ipconv_dma(g, num_cus, p)) return p;
   if (!bf16 && tile.empty() && plan_k1_stream(g, num_cus, k1s, p)) return p;
   if (!bf16 && tile.empty() && !g.pooled() && plan_rdec(g, num_cus, p)) return p;
-  if (bf16 && tile.empty() && plan_patch_bf16(g, num_cus, p)) return p; p.kname = bf16 ? "bodahip_conv_bf16" : "bodahip_conv_f32"; p.bf16 = bf16;
+  if (bf16 && tile.empty() && plan_patch_bf16(g, num_cus, p)) return p;
+  p.src = bf16 ? kSrc_gemm_conv_bf16 : kSrc_gemm_conv_f32; p.kname = bf16 ? "bodahip_conv_bf16" : "bodahip_conv_f32"; p.bf16 = bf16;
   // output 1x1, no padding, kernel == whole input ("ipconv" case): the im2col row of image j is the contiguous image
   p.ipconv = (g.OH == 1 && g.OW == 1 && g.PY == 0 && g.PX == 0 && g.KH == g.H && g.KW == g.W);
   p.cfg = choose_cfg(g.OC, (int)Nj, (int)Kt, num_cus, !p.ipconv, bf16);
@@ -886,7 +887,7 @@ static plan_t plan_conv_tiled(conv_geom_t const &g, int num_cus, string const &t
       auto tiles = [&](int m, int n) { return (long)((Nj + m - 1) / m) * ((g.OC + n - 1) / n); };
       if (tiles(64, 64) * 4 < (long)num_cus * 3) { tn = 32; if (tiles(64, 32) * 4 < (long)num_cus * 3) tm = 32; }
     }
-    p.fc = true; p.kname = "bodahip_fc_f32"; p.cfg.BI = tn; p.cfg.BJ = tm; p.cfg.MT = 16; p.cfg.BK = bkf; p.cfg.PF = pf; p.cfg.MINW = 1; p.cfg.WI = 2; p.cfg.WJ = 4;   // (eight waves)
+    p.src = kSrc_fc_f32; p.fc = true; p.kname = "bodahip_fc_f32"; p.cfg.BI = tn; p.cfg.BJ = tm; p.cfg.MT = 16; p.cfg.BK = bkf; p.cfg.PF = pf; p.cfg.MINW = 1; p.cfg.WI = 2; p.cfg.WJ = 4;   // (eight waves)
     p.defs = {"-DTM=" + std::to_string(tm), "-DTN=" + std::to_string(tn), "-DBKF=" + std::to_string(bkf), "-DPF=" + std::to_string(pf), string("-DRELU=") + (g.relu ? "1" : "0")};
     if (char const *x = getenv("BODAHIP_EXTRA_DEFS")) { std::istringstream is(x); string tok; while (is >> tok) p.defs.push_back(tok); }
     return p;
@@ -1192,7 +1193,7 @@ long bconv_in_tiles(conv_geom_t const &g, int BJ) {
 }
 plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile, bool zinp) {
   bconv_check_geom(g, "hip_bconv_in");
-  plan_t p; p.bconv_in = true; p.kname = "bodahip_bconv_in";
+  plan_t p; p.src = kSrc_bconv_in_f32; p.bconv_in = true; p.kname = "bodahip_bconv_in";
   if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_in: bad tile '" + tile + "'"); }
   else {
     p.cfg = bconv_default_cfg(g.C, 16);
@@ -1206,7 +1207,7 @@ plan_t plan_bconv_in(conv_geom_t const &g, int num_cus, string const &tile, bool
 }
 plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile) {
   bconv_check_geom(g, "hip_bconv_filts");
-  plan_t p; p.bconv_filts = true; p.kname = "bodahip_bconv_filts";
+  plan_t p; p.src = kSrc_bconv_filts_f32; p.kname = "bodahip_bconv_filts";
   bool ksl_given = false;
   if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_filts: bad tile '" + tile + "'"); ksl_given = std::count(tile.begin(), tile.end(), 'x') >= 6; }
   else p.cfg = bconv_default_cfg(g.OC, 32);
@@ -1221,7 +1222,7 @@ plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile) {
   p.defs = bconv_geom_defs(g, p.cfg); p.defs.push_back("-DKSL=" + std::to_string(p.cfg.SPLITK));
   return p;
 }
-plan_t plan_bconv_biases() { plan_t p; p.bconv_filts = true; p.kname = "bodahip_bconv_biases"; p.defs = {"-DBIAS_ONLY=1"}; return p; }
+plan_t plan_bconv_biases() { plan_t p; p.src = kSrc_bconv_filts_f32; p.kname = "bodahip_bconv_biases"; p.defs = {"-DBIAS_ONLY=1"}; return p; }
 
 // hip_bconv_filts_biases (kernels/bconv_fb_f32.hip): the same tile strings; both operands are staged k-major, so every thread owns one k offset (threads % BK == 0) and
 // whole rows AND columns ((threads / BK) divides BI and BJ); the LDS images are transposed with pitch BK + 1; K slices go to slabs summed by a second launch: 1..1024
@@ -1236,7 +1237,7 @@ static void check_bconv_fb_cfg(tile_cfg_t const &c) {
 }
 plan_t plan_bconv_filts_biases(conv_geom_t const &g, int num_cus, string const &tile) {
   bconv_check_geom(g, "hip_bconv_filts_biases");
-  plan_t p; p.bconv_fb = true; p.kname = "bodahip_bconv_filts_biases";
+  plan_t p; p.src = kSrc_bconv_fb_f32; p.kname = "bodahip_bconv_filts_biases";
   bool ksl_given = false;
   if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_filts_biases: bad tile '" + tile + "'"); ksl_given = std::count(tile.begin(), tile.end(), 'x') >= 6; }
   else p.cfg = bconv_default_cfg(g.OC, 32);
@@ -1251,7 +1252,7 @@ plan_t plan_bconv_filts_biases(conv_geom_t const &g, int num_cus, string const &
   p.defs = bconv_geom_defs(g, p.cfg); p.defs.push_back(string("-DSLICED=") + (p.cfg.SPLITK > 1 ? "1" : "0"));
   return p;
 }
-plan_t plan_bconv_slab_sum() { plan_t p; p.bconv_fb = true; p.kname = "bodahip_bconv_slab_sum"; p.defs = {"-DSLAB_SUM=1"}; return p; }
+plan_t plan_bconv_slab_sum() { plan_t p; p.src = kSrc_bconv_fb_f32; p.kname = "bodahip_bconv_slab_sum"; p.defs = {"-DSLAB_SUM=1"}; return p; }
 
 // ---- hip_operands=bf16 (kernels/bconv_in_bf16.hip, kernels/bconv_fb_bf16.hip): the fp32 functions' tile strings, 16-deep MFMA steps (BK % 16 == 0), LDS images of
 // [row][BK + 8] bf16, double-buffered.  The static_asserts of the two kernels, checked on the host
@@ -1269,7 +1270,7 @@ static void check_bconv_in_bf16_cfg(tile_cfg_t const &c) {
 }
 plan_t plan_bconv_in_bf16(conv_geom_t const &g, int num_cus, string const &tile, bool zinp) {
   bconv_check_geom(g, "hip_bconv_in");
-  plan_t p; p.bconv_in = true; p.bf16 = true; p.kname = "bodahip_bconv_in_bf16";
+  plan_t p; p.src = kSrc_bconv_in_bf16; p.bconv_in = true; p.bf16 = true; p.kname = "bodahip_bconv_in_bf16";
   if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_in: bad tile '" + tile + "'"); }
   else {
     p.cfg = bconv_default_cfg(g.C, 32);
@@ -1295,7 +1296,7 @@ static void check_bconv_fb_bf16_cfg(tile_cfg_t const &c) {
 }
 plan_t plan_bconv_fb_bf16(conv_geom_t const &g, int num_cus, string const &tile) {
   bconv_check_geom(g, "hip_bconv_filts_biases");
-  plan_t p; p.bconv_fb = true; p.bf16 = true; p.kname = "bodahip_bconv_filts_biases_bf16";
+  plan_t p; p.src = kSrc_bconv_fb_bf16; p.bf16 = true; p.kname = "bodahip_bconv_filts_biases_bf16";
   bool ksl_given = false;
   if (!tile.empty()) { if (!parse_tile(tile, p.cfg)) unsup_err("hip_bconv_filts_biases: bad tile '" + tile + "'"); ksl_given = std::count(tile.begin(), tile.end(), 'x') >= 6; }
   else p.cfg = bconv_default_cfg(g.OC, 32);
@@ -1319,7 +1320,7 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
   native_func_t const *d = find_native_func(kFamBckOp, g.op);
   if (!d) rt_err("plan_bck_op: unknown op " + std::to_string(g.op));
   string const what = d->name;
-  bck_plan_t r; r.p.bck_ops = true; r.p.kname = d->kname; r.p.defs = {"-DOP=" + std::to_string(g.op)};
+  bck_plan_t r; r.p.src = kSrc_bck_ops_f32; r.p.kname = d->kname; r.p.defs = {"-DOP=" + std::to_string(g.op)};
   auto D = [&](char const *n, long v) { r.p.defs.push_back(string("-D") + n + "=" + std::to_string(v)); };
   auto lim = [&](double elems) { if (4.0 * elems >= 2147483648.0) unsup_err(what + ": tensors of 2 GiB or more (32-bit element offsets)"); };
   if (g.B < 0 || g.C < 0) rt_err(what + ": negative dims");
@@ -1399,7 +1400,7 @@ bck_plan_t plan_shard_sum(int nslabs, long stride, long n) {
   string const what = "bodahip_shard_sum";
   if (nslabs < 1 || n < 0 || stride < n) rt_err(what + ": " + std::to_string(nslabs) + " slabs of " + std::to_string(n) + " floats at a stride of " + std::to_string(stride));
   if (4.0 * (double)stride * nslabs >= 2147483648.0) unsup_err(what + ": slabs of 2 GiB or more (32-bit strides)");
-  bck_plan_t r; r.p.bck_ops = true; r.p.kname = what; r.p.defs = {"-DOP=14"};
+  bck_plan_t r; r.p.src = kSrc_bck_ops_f32; r.p.kname = what; r.p.defs = {"-DOP=14"};
   r.threads = n; r.algo_bytes = 4.0 * (nslabs + 1) * (double)n;
   r.grid = (uint32_t)((n + r.block - 1) / r.block);
   return r;
@@ -1410,7 +1411,7 @@ bck_plan_t plan_shard_sum(int nslabs, long stride, long n) {
 sgd_plan_t plan_sgd_update(std::vector<long> const &elems) {
   string const what = "hip_sgd_update";
   if (elems.empty() || (int)elems.size() > kSgdMaxTens) rt_err(what + ": tens_num=" + std::to_string(elems.size()) + ": 1 to " + std::to_string(kSgdMaxTens) + " tensors");
-  sgd_plan_t r; r.p.sgd = true; r.p.kname = "bodahip_sgd_update";
+  sgd_plan_t r; r.p.src = kSrc_sgd_update_f32; r.p.kname = "bodahip_sgd_update";
   uint64_t blocks = 0; double tot = 0;
   for (long n : elems) {
     if (n < 0) rt_err(what + ": negative size");
@@ -1426,7 +1427,7 @@ sgd_plan_t plan_sgd_update(std::vector<long> const &elems) {
 // ---- the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip): the kernels of one call in launch order.  The slab plan itself is bn_slab_plan's
 // (rtc_types.h), shared with be=cpu; nothing here depends on the device.  algo_bytes counts every tensor of the call once
 plan_t bn_kernel_plan(int op, char const *kname, vect_string const &defs) {
-  plan_t p; p.bn = true; p.kname = kname; p.defs = {"-DOP=" + std::to_string(op)};
+  plan_t p; p.src = kSrc_bn_f32; p.kname = kname; p.defs = {"-DOP=" + std::to_string(op)};
   for (string const &d : defs) p.defs.push_back(d);
   return p;
 }

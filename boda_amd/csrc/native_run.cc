@@ -175,7 +175,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
       for (plan_t const *q : L.variants) desc += " " + q->kname + ":" + q->cfg.str();
       if (plan_out) *plan_out = "bodahip_conv_nhwc_set variants=" + std::to_string(L.variants.size()) + desc;
       if (arch.empty()) return 0;
-      if (L.variants.size() >= 1) bytes += hiprtc_compile(set_kernel_source(L.variants, 256, std::max(1, L.minw)), "bodahip_conv_nhwc_set", arch, vect_string(), &log, true).size();
+      if (L.variants.size() >= 1) bytes += hiprtc_compile(set_kernel_source(L.variants, 256, std::max(1, L.minw)), "bodahip_conv_nhwc_set", arch, vect_string(), &log, true, kernel_headers()).size();
       return bytes;
     }
     conv_geom_t g; memset(&g, 0, sizeof(g));
@@ -216,7 +216,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     else if (fam == kFamNhwcGrp) { dims_t const &grp = op.get_dims("grp"); p = plan_conv_nhwc(g, num_cus, tile, op.get_dims("out_0").tn == "float", (int)grp.dims(grp.sz() - 1)); }
     else if (bf16 && tile.empty() && s2d_geom(g, g2, pry, prx) && plan_patch_bf16(g2, num_cus, p)) { // conv1-type layers: space-to-depth front end (see conv())
       s2d = "s2d(" + std::to_string(g2.C) + "x" + std::to_string(g2.H) + "x" + std::to_string(g2.W) + ",k" + std::to_string(g2.KH) + "x" + std::to_string(g2.KW) + ")+";
-      if (!arch.empty()) { plan_t sp; sp.patch16 = true; sp.bf16 = true; sp.kname = "bodahip_s2d"; sp.defs = {"-DS2D_ONLY=1"}; compile_plan(sp, arch, &log); }
+      if (!arch.empty()) { plan_t sp; sp.src = kSrc_conv_patch_bf16; sp.kname = "bodahip_s2d"; sp.defs = {"-DS2D_ONLY=1"}; compile_plan(sp, arch, &log); }
     } else {
       auto xe = op.str_vals.find("hip_exact"); bool const exact = !(xe != op.str_vals.end() && xe->second == "0");
       // the same resolution as conv(): in tolerance mode (and with no conv_algo / tile given) the 3x3 / stride-1 layers take the F(2x2,3x3) pipeline -- what is
@@ -224,7 +224,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
       if (!bf16 && !exact && tile.empty() && winograd_applies(g, "winograd")) {
         int const tpi = ((g.OH + 1) / 2) * ((g.OW + 1) / 2); long const Bc = wino_chunk_imgs(g);
         s2d = "winograd(F2x2,3x3)+";
-        if (!arch.empty()) hiprtc_compile(k_src_winograd_f32_ptr, "bodahip_winograd", arch, vect_string(), &log, true);
+        if (!arch.empty()) hiprtc_compile(kernel_source(kSrc_winograd_f32).text, "bodahip_winograd", arch, vect_string(), &log, true, kernel_headers());
         long const rem = g.B % Bc;
         if (rem) { plan_t const rp = plan_sgemm((uint32_t)g.OC, (uint32_t)(rem * tpi), (uint32_t)g.C, num_cus, string(), false, 16); if (!arch.empty()) compile_plan(rp, arch, &log); }
         p = plan_sgemm((uint32_t)g.OC, (uint32_t)(std::min<long>(Bc, g.B) * tpi), (uint32_t)g.C, num_cus, string(), false, 16);
@@ -286,12 +286,12 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     if (p.split_pels > 0) *plan_out += " pels<" + std::to_string(p.split_pels) + "+rest:" + p.tail_cfg.str(); }
   if (arch.empty()) return 0;
   size_t const n = compile_plan(p, arch, &log).size();
-  if (p.cbig && p.split_pels > 0) { plan_t tp; tp.cbig = true; tp.kname = p.kname; tp.cfg = p.tail_cfg; tp.defs = p.tail_defs; compile_plan(tp, arch, &log); }
-  if (p.cbig) { plan_t xp; xp.cbig = true; xp.kname = "bodahip_conv_big_xpose"; xp.defs = {"-DXPOSE_ONLY=1"}; compile_plan(xp, arch, &log); }   // (the filter transposition that runs in front of it)
-  if (p.patch16) { plan_t fp; fp.patch16 = true; fp.bf16 = true; fp.kname = "bodahip_filt_bf16"; fp.defs = {"-DFILT_ONLY=1"}; compile_plan(fp, arch, &log); }
+  if (p.cbig && p.split_pels > 0) { plan_t tp; tp.src = p.src; tp.kname = p.kname; tp.cfg = p.tail_cfg; tp.defs = p.tail_defs; compile_plan(tp, arch, &log); }
+  if (p.cbig) { plan_t xp; xp.src = kSrc_conv_big_f32; xp.kname = "bodahip_conv_big_xpose"; xp.defs = {"-DXPOSE_ONLY=1"}; compile_plan(xp, arch, &log); }   // (the filter transposition that runs in front of it)
+  if (p.patch16) { plan_t fp; fp.src = kSrc_conv_patch_bf16; fp.kname = "bodahip_filt_bf16"; fp.defs = {"-DFILT_ONLY=1"}; compile_plan(fp, arch, &log); }
   if (p.ksl) {   // (K slices reduced inside the launch: no second kernel)
   } else if (p.cfg.SPLITK > 1 && p.nhwc) {
-    plan_t rp; rp.nhwc = true; rp.bf16 = true; rp.kname = "bodahip_nhwc_splitk_reduce";
+    plan_t rp; rp.src = kSrc_conv_nhwc_bf16; rp.kname = "bodahip_nhwc_splitk_reduce";
     bool const relu = op.has("conv_has_relu") ? (op.get_u32("conv_has_relu") != 0) : true;
     rp.defs = {"-DREDUCE_ONLY=1", string("-DRELU=") + (relu ? "1" : "0"), string("-DOUT_F32=") + ((op.get_dims("out").tn == "float") ? "1" : "0")};
     compile_plan(rp, arch, &log);
@@ -787,7 +787,7 @@ struct native_kernels_t::call_t {
     long const OC = f.dims(0), Ktot = (long)f.dims(1) * f.dims(2) * f.dims(3), mi4 = (OC + 3) / 4 * 4, kp = Ktot + 128;
     if (kd.sz() != 2 || (long)kd.dims(0) != kp || (long)kd.dims(1) != mi4) rt_err("hip_conv_filts_kmajor: filts_km must be [K + 128][out_chan padded to a multiple of 4] floats");
     if ((uint64_t)kp * mi4 * 4 >= 0x7ffffff0ull) unsup_err("hip_conv_filts_kmajor: filts of 2 GiB or more");
-    plan_t xp; xp.cbig = true; xp.kname = "bodahip_conv_big_xpose"; xp.defs = {"-DXPOSE_ONLY=1"};
+    plan_t xp; xp.src = kSrc_conv_big_f32; xp.kname = "bodahip_conv_big_xpose"; xp.defs = {"-DXPOSE_ONLY=1"};
     kernel_t &xk = get_kernel(impl, host, xp);
     float const *src = (float const *)host->nh_var_ptr(fnm); float *dst = (float *)host->nh_var_ptr(knm); int Mi = (int)OC, Mi4 = (int)mi4, Kk = (int)Ktot, Kp = (int)kp;
     void *xparams[] = {&src, &dst, &Mi, &Mi4, &Kk, &Kp};
