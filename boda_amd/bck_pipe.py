@@ -23,10 +23,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, bnc_bck_in_func_op, bnc_bck_sums_func_op, bnc_fwd_func_op, bnc_stats_func_op, BNC_MAX_CHUNKS, fan_out_func_op, sgd_update_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
+from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, bnc_bck_in_func_op, bnc_bck_sums_func_op, bnc_fwd_func_op, bnc_stats_func_op, BNC_MAX_CHUNKS, fan_out_func_op, sgd_update_func_op, solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
                      pipe_func_args, seed_from_var, SEED_VAR_ARG, bf16_operands)
 from .conv_pipe import ConvPipe, PipeOp
-from .op import Dims, Nda, Op, RtErr, UnsupErr
+from .op import Dims, Nda, Op, RtErr, SOLVER_CHUNK, UnsupErr
 from .rtc import RtcArg, RtcFuncCall, RtcFuncInfo
 
 IN_PLACE_TYPES = ("ReLU", "Dropout", "BckDropout")   # and a ZeroIfNonPos whose out is its in (src/conv_util.cc:273-279)
@@ -64,6 +64,93 @@ class SgdSolver:
 
     def hyper(self) -> np.ndarray:
         return np.array([self.lr, self.momentum, self.weight_decay, 0.0], np.float32)
+
+
+SOLVER_HYPER_VAR = "solver_hyper"    # ConvPipeBck(solver=Solver(...)): float v=8 = [lr, momentum, weight_decay, momentum2, delta, corr, clip_gradients, unused]
+SOLVER_STATE_VAR = "solver_state"    # float v=4 = [coef, norm, sumsq, 0]: what hip_grad_norm leaves and the clipping update reads
+SOLVER_PARTS_VAR = "solver_gnorm_partials"   # one partial sum of squares per chunk of 4096 floats of every updated param
+SGD_HIST2_SFX = "_sgd_hist2"         # <param>_sgd_hist2: adam's second-moment history
+
+
+@dataclass
+class LrPolicy:
+    """Caffe's seven learning-rate policies, evaluated on the host in float64 (Python floats) from the written formulas; lr_at(base_lr, it) is what the driver rounds to
+    fp32 and uploads for step `it` (0-based):
+        fixed      base_lr
+        step       base_lr * gamma ^ floor(it / stepsize)
+        exp        base_lr * gamma ^ it
+        inv        base_lr * (1 + gamma * it) ^ (-power)
+        multistep  base_lr * gamma ^ (number of stepvalues <= it)
+        poly       base_lr * (1 - it / max_iter) ^ power
+        sigmoid    base_lr * (1 / (1 + exp(-gamma * (it - stepsize))))"""
+    policy: str = "fixed"
+    gamma: float = 0.1
+    power: float = 1.0
+    stepsize: int = 1
+    stepvalues: Sequence[int] = ()
+    max_iter: int = 1
+
+    POLICIES = ("fixed", "step", "exp", "inv", "multistep", "poly", "sigmoid")
+
+    def __post_init__(self):
+        if self.policy not in self.POLICIES:
+            raise RtErr(f"LrPolicy: policy must be one of {' | '.join(self.POLICIES)}, got {self.policy!r}")
+        if self.policy in ("step", "sigmoid") and int(self.stepsize) < 1:
+            raise RtErr(f"LrPolicy: {self.policy} needs stepsize >= 1, got {self.stepsize!r}")
+        if self.policy == "poly" and int(self.max_iter) < 1:
+            raise RtErr(f"LrPolicy: poly needs max_iter >= 1, got {self.max_iter!r}")
+
+    def lr_at(self, base_lr: float, it: int) -> float:
+        import math
+        b, g, p, it = float(base_lr), float(self.gamma), float(self.power), int(it)
+        if self.policy == "fixed":
+            return b
+        if self.policy == "step":
+            return b * g ** (it // int(self.stepsize))
+        if self.policy == "exp":
+            return b * g ** it
+        if self.policy == "inv":
+            return b * (1.0 + g * it) ** (-p)
+        if self.policy == "multistep":
+            return b * g ** sum(1 for s in self.stepvalues if int(s) <= it)
+        if self.policy == "poly":
+            return b * (1.0 - it / float(self.max_iter)) ** p
+        return b * (1.0 / (1.0 + math.exp(-g * (it - int(self.stepsize)))))
+
+
+@dataclass
+class Solver:
+    """SGD, Nesterov or Adam for ConvPipeBck(solver=...), with optional global-norm gradient clipping and a learning-rate policy (hip_solver_update, hip_grad_sumsq,
+    hip_grad_norm; DESIGN.md section 3.18 states the chains, every operation one fp32 rounding).  type: "sgd" | "nesterov" | "adam".  momentum is adam's beta1, momentum2 its
+    beta2, delta its epsilon; decoupled_wd (adam only) applies the decay to the param (AdamW) instead of adding it to the gradient.  clip_gradients > 0: every gradient is
+    scaled by coef = norm > clip ? clip / norm : 1, norm the l2 norm over ALL updated params' gradients; <param>_grad_loss keeps the unclipped gradient.  lr_policy: an
+    LrPolicy; the driver then uploads lr = lr_policy.lr_at(lr, iter) before every step.  lr_mult / decay_mult / tensors_per_call: as SgdSolver's."""
+    type: str
+    lr: float
+    momentum: float = 0.9
+    momentum2: float = 0.999
+    delta: float = 1e-8
+    weight_decay: float = 5e-4
+    decoupled_wd: bool = False
+    clip_gradients: float = 0.0
+    lr_policy: Optional[LrPolicy] = None
+    lr_mult: Optional[Dict[str, float]] = None
+    decay_mult: Optional[Dict[str, float]] = None
+    tensors_per_call: int = 32
+
+    mult_of = SgdSolver.mult_of
+
+    @staticmethod
+    def corr(momentum: float, momentum2: float, t: int) -> float:
+        """adam's bias correction sqrt(1 - momentum2^t) / (1 - momentum^t) in float64 from the fp32 values of the two momenta (a momentum of 0: the factor is 1)."""
+        m1, m2 = float(np.float32(momentum)), float(np.float32(momentum2))
+        return float(np.sqrt(1.0 - m2 ** t) / (1.0 - m1 ** t))
+
+    def hyper(self, it: int = 0) -> np.ndarray:
+        """The eight floats of solver_hyper for step `it`."""
+        lr = self.lr_policy.lr_at(self.lr, it) if self.lr_policy is not None else self.lr
+        return np.array([lr, self.momentum, self.weight_decay, self.momentum2, self.delta, self.corr(self.momentum, self.momentum2, it + 1) if self.type == "adam" else 1.0,
+                         self.clip_gradients, 0.0], np.float32)
 
 
 @dataclass
@@ -399,6 +486,11 @@ class ConvPipeBck:
     set_sgd_hyper uploads 16 bytes and touches no call (valid between graph replays: a learning-rate schedule needs no new capture); zero_sgd_history clears the
     history.  capture_graph captures the update calls with the rest and leaves params and history as they were.  On a multi-device backend the update runs on every
     device's replicas, which hold the same summed gradients and so stay equal.
+    solver=Solver(...) (an SgdSolver goes down the path above untouched): SGD, Nesterov or Adam with optional global-norm clipping and a
+    learning-rate policy.  init creates solver_hyper (float v=8), solver_state (float v=4), <param>_sgd_hist, for adam <param>_sgd_hist2 and, when clipping,
+    solver_gnorm_partials, and appends behind every gradient op: when clipping the hip_grad_sumsq calls (grad_sumsq_k) and one grad_norm, then the hip_solver_update calls
+    (solver_update_k); n_sgd_calls counts all of them.  `iter` starts at 0; before every step that runs those calls -- eager or a replay -- the 32 bytes of solver_hyper are
+    uploaded for step `iter` (lr from the policy, adam's bias correction for t = iter + 1), and `iter` advances behind it.  <param>_grad_loss keeps the unclipped gradient.
     fuse_filts_biases=True (opt-in; False leaves the calls, their names and every bit as they are): every BckConv emits hip_bconv_in followed by ONE
     hip_bconv_filts_biases in place of the hip_bconv_biases + hip_bconv_filts pair.  Every other node holds the same bits; the filter and
     bias gradients follow that function's written chains (on be=cpu: the single chains, the same bits as the pair).  Not on a multi-device backend: init raises UnsupErr.
@@ -421,7 +513,7 @@ class ConvPipeBck:
     the one-device step with the same n.  fuse_relu_grad, seed_in_var, solver= and, on one device, capture_graph work as before; fuse_filts_biases and grad_operands
     stay refused on a multi-device backend."""
 
-    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[SgdSolver] = None, bn_maf: float = 0.999, fuse_filts_biases: bool = False,
+    def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[object] = None, bn_maf: float = 0.999, fuse_filts_biases: bool = False,
                  grad_operands: str = "", img_chunks: int = 0):
         self.rtc = rtc
         if not isinstance(img_chunks, int) or isinstance(img_chunks, bool) or not 0 <= img_chunks <= BNC_MAX_CHUNKS:
@@ -434,7 +526,9 @@ class ConvPipeBck:
         self.solver = solver
         self.bn_maf = float(bn_maf)   # a training BatchNorm's moving-average fraction: run' = maf * run + (1 - maf) * batch
         self.sgd_params: List[str] = []   # the params the solver updates: all of them but the BatchNorm running statistics
-        self.n_sgd_calls = 0       # the update calls, the last n_sgd_calls of bck_calls
+        self.n_sgd_calls = 0       # the solver's calls (a Solver's clipping calls included), the last n_sgd_calls of bck_calls
+        self.iter = 0              # a Solver's step count: what its lr_policy and adam's bias correction are evaluated at
+        self._base_lr = float(solver.lr) if solver is not None else 0.0
         self.op_tune = op_tune or OpTune()
         self.fuse_relu_grad = bool(fuse_relu_grad)
         self.seed_in_var = bool(seed_in_var)
@@ -483,7 +577,22 @@ class ConvPipeBck:
         if self.solver is not None:   # (refused before anything is created)
             if not 1 <= int(self.solver.tensors_per_call) <= SGD_MAX_TENS:
                 raise RtErr(f"ConvPipeBck.init: SgdSolver.tensors_per_call={self.solver.tensors_per_call}: 1 to {SGD_MAX_TENS}")
-            for vn in [pn + SGD_HIST_SFX for pn in self.sgd_params] + [SGD_HYPER_VAR]:
+            gen = isinstance(self.solver, Solver)
+            if not gen and not isinstance(self.solver, SgdSolver):
+                raise RtErr(f"ConvPipeBck.init: solver must be an SgdSolver or a Solver, got {type(self.solver).__name__}")
+            if gen:
+                sv = self.solver
+                if sv.type not in ("sgd", "nesterov", "adam"):
+                    raise RtErr(f"ConvPipeBck.init: Solver.type must be sgd | nesterov | adam, got {sv.type!r}")
+                if sv.decoupled_wd and sv.type != "adam":
+                    raise RtErr(f"ConvPipeBck.init: Solver.decoupled_wd is adam's, not {sv.type}'s")
+                if not float(sv.clip_gradients) >= 0.0:
+                    raise RtErr(f"ConvPipeBck.init: Solver.clip_gradients={sv.clip_gradients!r}: 0 (off) or a positive norm")
+                if sv.lr_policy is not None and not isinstance(sv.lr_policy, LrPolicy):
+                    raise RtErr("ConvPipeBck.init: Solver.lr_policy must be an LrPolicy or None")
+            names = [SGD_HYPER_VAR] if not gen else [SOLVER_HYPER_VAR, SOLVER_STATE_VAR] + ([SOLVER_PARTS_VAR] if self.solver.clip_gradients > 0 else []) + \
+                ([pn + SGD_HIST2_SFX for pn in self.sgd_params] if self.solver.type == "adam" else [])
+            for vn in [pn + SGD_HIST_SFX for pn in self.sgd_params] + names:
                 if vn in bp.nodes:
                     raise RtErr(f"ConvPipeBck.init: the solver needs the var name {vn!r}, which is a node of the pipe")
             for pn in self.sgd_params:
@@ -628,7 +737,39 @@ class ConvPipeBck:
             for fop, args in calls:
                 emit(o.tag, fop, args)
         self.n_sgd_calls = 0
-        if self.solver is not None:   # the update calls, behind every gradient op
+        if isinstance(self.solver, Solver):   # sum of squares per chunk, the norm, then the update calls: all behind every gradient op, all counted in n_sgd_calls
+            sv = self.solver
+            pnames = list(self.sgd_params)
+            adam, clip = sv.type == "adam", sv.clip_gradients > 0
+            for pn in pnames:
+                self._var(pn + SGD_HIST_SFX, bp.cp.params[pn])
+                if adam:
+                    self._var(pn + SGD_HIST2_SFX, bp.cp.params[pn])
+            self._var(SOLVER_HYPER_VAR, Dims(("v",), (8,), "float"))
+            self._var(SOLVER_STATE_VAR, Dims(("v",), (4,), "float"))
+            per = int(sv.tensors_per_call)
+            groups = [pnames[k:k + per] for k in range(0, len(pnames), per)]
+            if clip:
+                parts = sum(-(-bp.cp.params[pn].dims_prod() // SOLVER_CHUNK) for pn in pnames)
+                self._var(SOLVER_PARTS_VAR, Dims(("v",), (parts,), "float"))
+                part0 = 0
+                for k, grp in enumerate(groups):
+                    fop = grad_sumsq_func_op([bp.cp.params[pn] for pn in grp], part0, parts)
+                    emit(f"grad_sumsq_{k}", fop, dict({f"g_{i}": pn + "_grad_loss" for i, pn in enumerate(grp)}, partials=SOLVER_PARTS_VAR))
+                    part0 += fop.solver_geom()["chunks"]; self.n_sgd_calls += 1
+                emit("grad_norm", grad_norm_func_op(parts), {"partials": SOLVER_PARTS_VAR, "hyper": SOLVER_HYPER_VAR, "state": SOLVER_STATE_VAR})
+                self.n_sgd_calls += 1
+            for k, grp in enumerate(groups):
+                fop = solver_update_func_op([bp.cp.params[pn] for pn in grp], sv.type, [sv.mult_of(sv.lr_mult, pn) for pn in grp], [sv.mult_of(sv.decay_mult, pn) for pn in grp],
+                                            clip=clip, decoupled_wd=sv.decoupled_wd)
+                args = {"hyper": SOLVER_HYPER_VAR, "state": SOLVER_STATE_VAR}
+                for i, pn in enumerate(grp):
+                    args.update({f"w_{i}": pn, f"g_{i}": pn + "_grad_loss", f"h_{i}": pn + SGD_HIST_SFX})
+                    if adam:
+                        args[f"h2_{i}"] = pn + SGD_HIST2_SFX
+                emit(f"solver_update_{k}", fop, args)
+                self.n_sgd_calls += 1
+        elif self.solver is not None:   # the update calls, behind every gradient op
             sv = self.solver
             pnames = list(self.sgd_params)
             for pn in pnames:
@@ -656,6 +797,8 @@ class ConvPipeBck:
         if self.solver is not None:
             self._sgd_hyper = self.solver.hyper()
             self.zero_sgd_history()
+            if isinstance(self.solver, Solver):
+                self.rtc.copy_nda_to_var(SOLVER_STATE_VAR, np.array([1.0, 0.0, 0.0, 0.0], np.float32))
             self.set_sgd_hyper()
 
     @staticmethod
@@ -678,21 +821,56 @@ class ConvPipeBck:
             runs[x] = (ips[0], ips[1], ips[2] if len(ips) > 2 else None)
         return runs
 
-    def set_sgd_hyper(self, lr: Optional[float] = None, momentum: Optional[float] = None, weight_decay: Optional[float] = None) -> None:
-        """Upload the 16 bytes of sgd_hyper with the values given replaced (None: kept).  Touches no call: the next step -- eager or a graph replay -- reads them."""
+    def set_sgd_hyper(self, lr: Optional[float] = None, momentum: Optional[float] = None, weight_decay: Optional[float] = None, momentum2: Optional[float] = None,
+                      delta: Optional[float] = None, clip_gradients: Optional[float] = None) -> None:
+        """Upload the 16 bytes of sgd_hyper (a Solver: the 32 bytes of solver_hyper, for step `iter`) with the values given replaced (None: kept).  Touches no call: the
+        next step -- eager or a graph replay -- reads them.  momentum2 / delta / clip_gradients are a Solver's; with a Solver that has an lr_policy the policy owns lr, and
+        setting it is an RtErr.  clip_gradients can be changed, not switched on or off: the calls were made for one or the other."""
         if self.solver is None:
             raise RtErr("ConvPipeBck.set_sgd_hyper: the driver was built without a solver")
-        for i, v in enumerate((lr, momentum, weight_decay)):
+        gen = isinstance(self.solver, Solver)
+        if not gen and any(v is not None for v in (momentum2, delta, clip_gradients)):
+            raise RtErr("ConvPipeBck.set_sgd_hyper: momentum2 / delta / clip_gradients are a Solver's; the driver was built with an SgdSolver")
+        if gen and lr is not None and self.solver.lr_policy is not None:
+            raise RtErr(f"ConvPipeBck.set_sgd_hyper: lr is set by the solver's lr_policy ({self.solver.lr_policy.policy}); build the Solver without one to set it by hand")
+        if gen and clip_gradients is not None and (float(clip_gradients) > 0) != (self.solver.clip_gradients > 0):
+            raise RtErr("ConvPipeBck.set_sgd_hyper: clip_gradients cannot be switched on or off after init (the clipping calls exist or they do not); build the Solver with it")
+        for i, v in ((0, lr), (1, momentum), (2, weight_decay)) + (((3, momentum2), (4, delta), (6, clip_gradients)) if gen else ()):
             if v is not None:
                 self._sgd_hyper[i] = np.float32(v)
-        self.rtc.copy_nda_to_var(SGD_HYPER_VAR, self._sgd_hyper)
+        if gen:
+            if lr is not None:
+                self._base_lr = float(lr)
+            self._upload_solver_hyper()
+        else:
+            self.rtc.copy_nda_to_var(SGD_HYPER_VAR, self._sgd_hyper)
+
+    def _upload_solver_hyper(self) -> None:
+        """The 32 bytes of solver_hyper for step self.iter: lr from the policy (where there is one), adam's corr for t = iter + 1 from the fp32 momenta."""
+        sv, h = self.solver, self._sgd_hyper
+        if sv.lr_policy is not None:
+            h[0] = np.float32(sv.lr_policy.lr_at(self._base_lr, self.iter))
+        h[5] = np.float32(Solver.corr(h[1], h[3], self.iter + 1)) if sv.type == "adam" else np.float32(1.0)
+        self.rtc.copy_nda_to_var(SOLVER_HYPER_VAR, h)
+
+    def _before_update_step(self) -> None:
+        if isinstance(self.solver, Solver):
+            self._upload_solver_hyper()
+
+    def _after_update_step(self) -> None:
+        if isinstance(self.solver, Solver):
+            self.iter += 1
 
     def zero_sgd_history(self) -> None:
-        """Clear every <param>_sgd_hist."""
+        """Clear every <param>_sgd_hist (and, for adam, <param>_sgd_hist2), and start a Solver's step count `iter` again at 0."""
         if self.solver is None:
             raise RtErr("ConvPipeBck.zero_sgd_history: the driver was built without a solver")
+        adam = isinstance(self.solver, Solver) and self.solver.type == "adam"
         for pn in self.sgd_params:
             self.rtc.copy_nda_to_var(pn + SGD_HIST_SFX, np.zeros(self.bp.cp.params[pn].sizes, np.float32))
+            if adam:
+                self.rtc.copy_nda_to_var(pn + SGD_HIST2_SFX, np.zeros(self.bp.cp.params[pn].sizes, np.float32))
+        self.iter = 0
 
     def _dropout_calls(self) -> List[Tuple[BckCall, int]]:
         """The dropout calls of the step with their layer's index among the pipe's Dropout ops (a layer's forward and backward call share it)."""
@@ -740,9 +918,13 @@ class ConvPipeBck:
         skip_sgd: leave the solver's update calls out (what capture_graph's preparing step does: params and history stay as they are)."""
         rtc = self.rtc
         todo = self.bck_calls[:len(self.bck_calls) - self.n_sgd_calls] if skip_sgd else self.bck_calls
+        if not skip_sgd:
+            self._before_update_step()
         for c in todo:
             c.call_id = rtc.run(c.rfc)
         rtc.finish_and_sync()
+        if not skip_sgd:
+            self._after_update_step()
         ids = [c.call_id for c in todo]
         self.compute_dur_ms = rtc.get_dur(ids[0], ids[-1]) if ids else 0.0
         self.per_call_ms = [(c.tag, c.fop.get_func_name(), rtc.get_dur(i, i)) for c, i in zip(todo, ids)]
@@ -817,8 +999,10 @@ class ConvPipeBck:
         rtc = self.rtc
         if self._graph is None:
             raise RtErr("ConvPipeBck.run_graph: no captured graph -- call capture_graph() first")
+        self._before_update_step()
         cid = rtc.graph_launch(self._graph)
         rtc.finish_and_sync()
+        self._after_update_step()
         self.compute_dur_ms = rtc.get_dur(cid, cid)
         self.per_call_ms = []
         rtc.release_per_call_id_data()

@@ -336,6 +336,67 @@ def sgd_update_func_op(dims_list, lr_mults=None, decay_mults=None) -> Op:
     return a
 
 
+SOLVER_UPDATE_FUNC, GRAD_SUMSQ_FUNC, GRAD_NORM_FUNC = "hip_solver_update", "hip_grad_sumsq", "hip_grad_norm"
+SOLVER_TYPES = ("sgd", "nesterov", "adam")
+# the solvers beyond plain SGD and global-norm clipping, in a table of their own (SGD_OP_FUNCS is pinned): ConvPipeBck appends their calls behind the gradient ops
+SOLVER_OP_FUNCS: Dict[str, tuple] = {"SolverUpdate": (SOLVER_UPDATE_FUNC,), "GradSumsq": (GRAD_SUMSQ_FUNC,), "GradNorm": (GRAD_NORM_FUNC,)}
+
+
+def _solver_vec(n: int) -> Nda:
+    from .op import Dims
+    return Nda(dims=Dims(("v",), (int(n),), "float"), tn="float")
+
+
+def solver_update_func_op(dims_list, solver_type, lr_mults=None, decay_mults=None, clip=False, decoupled_wd=False) -> Op:
+    """-> the annotated function op of hip_solver_update over the float tensors `dims_list` (1 to 32, any dims): per tensor i the var args w_i (param), g_i (gradient),
+    h_i (first history) and, for solver_type "adam", h2_i (second history), all of dims_list[i], and the floats lr_mult_i / decay_mult_i (default 1); then the var args
+    hyper, float v=8 = [lr, momentum, weight_decay, momentum2, delta, corr, clip_gradients, unused], and state, float v=4 = [coef, norm, sumsq, 0], which is read only with
+    clip=1 (g0 = coef * g).  solver_type "sgd" | "nesterov" | "adam" rides as a str_val, clip and (adam) decoupled_wd as uint32s.  csrc/kernels/solver_update_f32.hip and
+    DESIGN.md section 3.18 state the chains, every operation one fp32 rounding.  w_i, h_i, h2_i are rewritten in place; g_i, hyper and state only read."""
+    dims_list = list(dims_list)
+    n = len(dims_list)
+    lr_mults = [1.0] * n if lr_mults is None else list(lr_mults)
+    decay_mults = [1.0] * n if decay_mults is None else list(decay_mults)
+    if len(lr_mults) != n or len(decay_mults) != n:
+        raise RtErr(f"solver_update_func_op: {n} tensors, {len(lr_mults)} lr_mults, {len(decay_mults)} decay_mults")
+    v = {"tens_num": Nda(None, "uint32_t", (n,)), "hyper": _solver_vec(8), "state": _solver_vec(4), "clip": Nda(None, "uint32_t", (1 if clip else 0,))}
+    if solver_type == "adam":
+        v["decoupled_wd"] = Nda(None, "uint32_t", (1 if decoupled_wd else 0,))
+    elif decoupled_wd:
+        raise RtErr(f"solver_update_func_op: decoupled_wd is adam's, not {solver_type}'s")
+    for i, d in enumerate(dims_list):
+        for b in ("w", "g", "h") + (("h2",) if solver_type == "adam" else ()):
+            v[f"{b}_{i}"] = Nda(dims=d, tn=d.tn)
+        v[f"lr_mult_{i}"] = Nda(None, "float", (float(lr_mults[i]),))
+        v[f"decay_mult_{i}"] = Nda(None, "float", (float(decay_mults[i]),))
+    a = Op({"type": "SolverUpdate", "solver_type": str(solver_type)}, v)
+    a.solver_geom()
+    a.set_func_name(SOLVER_UPDATE_FUNC)
+    return a
+
+
+def grad_sumsq_func_op(dims_list, part0, parts_total) -> Op:
+    """-> the annotated function op of hip_grad_sumsq over the float tensors `dims_list` (1 to 32): var args g_i, then partials (float v=parts_total, INOUT: the call
+    writes only its own slots).  The chunk k of the call -- chunks of 4096 floats numbered over the call's tensors -- leaves its sum of squares in partials[part0 + k]."""
+    dims_list = list(dims_list)
+    v = {"tens_num": Nda(None, "uint32_t", (len(dims_list),)), "part0": Nda(None, "uint32_t", (int(part0),)), "partials": _solver_vec(parts_total)}
+    for i, d in enumerate(dims_list):
+        v[f"g_{i}"] = Nda(dims=d, tn=d.tn)
+    a = Op({"type": "GradSumsq"}, v)
+    a.solver_geom()
+    a.set_func_name(GRAD_SUMSQ_FUNC)
+    return a
+
+
+def grad_norm_func_op(parts_total) -> Op:
+    """-> the annotated function op of hip_grad_norm: partials (float v=parts_total) and hyper (float v=8) read, state (float v=4) written:
+    sumsq = the partials through the written chain; norm = sqrtf(sumsq); coef = norm > clip_gradients ? clip_gradients / norm : 1."""
+    a = Op({"type": "GradNorm"}, {"partials": _solver_vec(parts_total), "hyper": _solver_vec(8), "state": _solver_vec(4)})
+    a.solver_geom()
+    a.set_func_name(GRAD_NORM_FUNC)
+    return a
+
+
 # the training BatchNorm of the gradient pipe and the Eltwise-SUM gradient, in a table of their own (PIPE_OP_FUNCS is pinned): what bck_pipe.ConvPipeBck runs for a
 # BatchNorm + Scale (+ ReLU) run and its gradient, and for a BckEltwise.  This backend's own arithmetic: csrc/kernels/bn_f32.hip and DESIGN.md section 3.15 state it
 BN_OP_FUNCS: Dict[str, tuple] = {
@@ -557,6 +618,10 @@ def pipe_func_args(fop: Op) -> tuple:
     if fn == SGD_UPDATE_FUNC:
         per = tuple(x for i in range(fop.get_u32("tens_num")) for x in ((f"w_{i}", "INOUT"), (f"g_{i}", "IN"), (f"h_{i}", "INOUT")))
         return per + NATIVE_ARGS[fn]
+    if fn in (SOLVER_UPDATE_FUNC, GRAD_SUMSQ_FUNC) and fop.has("tens_num"):   # (an op without tens_num: the fixed args alone)
+        adam = fop.str_vals.get("solver_type") == "adam"
+        one = lambda i: ((f"w_{i}", "INOUT"), (f"g_{i}", "IN"), (f"h_{i}", "INOUT")) + (((f"h2_{i}", "INOUT"),) if adam else ()) if fn == SOLVER_UPDATE_FUNC else ((f"g_{i}", "IN"),)
+        return tuple(x for i in range(fop.get_u32("tens_num")) for x in one(i)) + NATIVE_ARGS[fn]
     if fn == "hip_fan_out":
         return NATIVE_ARGS[fn] + tuple((an, "OUT") for an in fop.multi_names("outs"))
     if fn == "hip_dropout" and has_seed_var_flag(fop):
@@ -608,6 +673,11 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_chan_affine": (("in", "IN"), ("a", "IN"), ("b", "IN"), ("out", "OUT")),
     # the solver's update (this backend's own).  The list depends on the op: w_i (INOUT) g_i (IN) h_i (INOUT) per tensor in front of hyper (pipe_func_args)
     "hip_sgd_update": (("hyper", "IN"),),
+    # the solvers beyond plain SGD and global-norm clipping (this backend's own).  In front of these (pipe_func_args): w_i (INOUT) g_i (IN) h_i (INOUT) and, for adam,
+    # h2_i (INOUT) per tensor | g_i (IN) per tensor.  partials is INOUT for hip_grad_sumsq: a call writes its own slots and leaves the others
+    "hip_solver_update": (("hyper", "IN"), ("state", "IN")),
+    "hip_grad_sumsq": (("partials", "INOUT"),),
+    "hip_grad_norm": (("partials", "IN"), ("hyper", "IN"), ("state", "OUT")),
     # the training BatchNorm and the Eltwise-SUM gradient (this backend's own; eps / maf / slab / relu ride in the op).  hip_fan_out's list depends on the op: in,
     # then outs_0 .. outs_{n-1} (pipe_func_args)
     "hip_bn_stats": (("in", "IN"), ("mean", "OUT"), ("inv_std", "OUT"), ("run_mean", "INOUT"), ("run_var", "INOUT")),

@@ -263,6 +263,56 @@ void sgd_update(float *w, float const *g, float *h, long n, float lr_i, float wd
     w[e] = w[e] - h2;
   }
 }
+// ---- the solver family (kernels/solver_update_f32.hip states the chains and the tree): the same operations in the same order, every one its own fp32 rounding
+struct solver_coef_c { float lr, wd, mom, mom2, delta, coef, c, o1, o2, s, lrwd; };
+void solver_update(int type, bool clip, bool dwd, float *w, float const *g, float *h, float *v, long n, solver_coef_c const k) {
+#pragma omp parallel for schedule(static)
+  for (long e = 0; e < n; ++e) {
+    float const g0 = clip ? k.coef * g[e] : g[e];
+    if (type == kSolverAdam) {
+      float g1 = g0;
+      if (!dwd) { float const reg = k.wd * w[e]; g1 = g0 + reg; }
+      float const ma = k.mom * h[e];
+      float const mb = k.o1 * g1;
+      float const m = ma + mb;
+      float const q = g1 * g1;
+      float const va = k.mom2 * v[e];
+      float const vb = k.o2 * q;
+      float const vn = va + vb;
+      float const sq = sqrtf(vn);
+      float const d = sq + k.delta;
+      float const r = m / d;
+      float u = k.s * r;
+      if (dwd) { float const dw = k.lrwd * w[e]; u = u + dw; }
+      h[e] = m; v[e] = vn; w[e] = w[e] - u;
+    } else {
+      float const reg = k.wd * w[e];
+      float const g1 = g0 + reg;
+      float const a = k.mom * h[e];
+      float const b = k.lr * g1;
+      float const hn = a + b;
+      h[e] = hn;
+      if (type == kSolverNesterov) { float u = k.c * hn; u = u - a; w[e] = w[e] - u; }
+      else w[e] = w[e] - hn;
+    }
+  }
+}
+// the tree over 256 lane sums: for h = 128 .. 1: a[t] = a[t] + a[t + h], t < h
+inline float solver_tree(float *a) { for (int h = 128; h > 0; h >>= 1) for (int t = 0; t < h; ++t) a[t] = a[t] + a[t + h]; return a[0]; }
+// one chunk's partial: lane t adds x * x for the elements t, t + 256, ... from +0
+float solver_chunk_sumsq(float const *g, long cnt) {
+  float a[256];
+  for (int t = 0; t < 256; ++t) { float acc = 0.0f; for (long e = t; e < cnt; e += 256) { float const q = g[e] * g[e]; acc = acc + q; } a[t] = acc; }
+  return solver_tree(a);
+}
+void solver_grad_norm(float const *partials, long n, float clip, float *state) {
+  float a[256];
+  for (int t = 0; t < 256; ++t) { float acc = 0.0f; for (long e = t; e < n; e += 256) acc = acc + partials[e]; a[t] = acc; }
+  float const sumsq = solver_tree(a);
+  float const norm = sqrtf(sumsq);
+  float const coef = (norm > clip) ? clip / norm : 1.0f;
+  state[0] = coef; state[1] = norm; state[2] = sumsq; state[3] = 0.0f;
+}
 // ---- the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip states the formulas and the chain of the sums): the same operations in the same order.
 // One slab of one channel: 256 chains, chain t owning the elements with (r / 4) mod 256 == t in ascending r, then the fixed tree.  term(e, acc0, acc1) adds element e's terms
 template <typename TermF> void bn_slab_sums(long e0, long len, TermF term, float &P0, float &P1) {
@@ -435,6 +485,7 @@ struct cpu_compute_t : public rtc_compute_t {
       (void)op_bf16_operands(fi.op);   // (str_val hip_operands: refused where the function has no bf16-operand form)
       if (f->family == kFamSgd) (void)sgd_op_of_op(fi.op);   // (the op must be whole)
       if (f->family == kFamBn || f->family == kFamBnc) (void)bn_op_of_op(fi.op);   // (likewise)
+      if (f->family == kFamSolver) (void)solver_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamBckOp) {
         if (!f->of_type(fi.op.get_type())) rt_err(fn + ": a function of op type " + f->types[0] + ", not " + fi.op.get_type());
         bck_op_args_t const a = bck_op_args(*f, fi.op);
@@ -747,6 +798,47 @@ struct cpu_compute_t : public rtc_compute_t {
     }
   }
 
+  // the solver family: the checks of be=hip (csrc/native_run.cc), then the twins above with the per-tensor scalars formed once
+  void run_solver(op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = op.get_func_name();
+    solver_op_t const so = solver_op_of_op(op);
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    auto var_ptr = [&](string const &an) -> float * {
+      string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn);
+      if (vd.tn != "float") rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ": the solver is fp32 only");
+      if (!(vd == op.get_dims(an))) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + op.get_dims(an).pretty_str());
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      return (float *)must_find(vis, vn).buf.get();
+    };
+    size_t const n = so.elems.size();
+    if (so.kind == 1) {
+      std::vector<float *> w(n), h(n), v(n, nullptr); std::vector<float const *> g(n);
+      for (size_t i = 0; i < n; ++i) {
+        string const sx = "_" + std::to_string(i);
+        w[i] = var_ptr("w" + sx); g[i] = var_ptr("g" + sx); h[i] = var_ptr("h" + sx); if (so.type == kSolverAdam) v[i] = var_ptr("h2" + sx);
+      }
+      float const *hy = var_ptr("hyper"); float const *st = var_ptr("state");
+      for (size_t i = 0; i < n; ++i) {
+        solver_coef_c k;
+        k.lr = hy[0] * so.lr_mult[i]; k.wd = hy[2] * so.decay_mult[i]; k.mom = hy[1]; k.mom2 = hy[3]; k.delta = hy[4];
+        k.coef = so.clip ? st[0] : 1.0f;
+        k.c = 1.0f + k.mom; k.o1 = 1.0f - k.mom; k.o2 = 1.0f - k.mom2; k.s = k.lr * hy[5]; k.lrwd = k.lr * k.wd;
+        solver_update(so.type, so.clip, so.decoupled_wd, w[i], g[i], h[i], v[i], so.elems[i], k);
+      }
+    } else if (so.kind == 2) {
+      std::vector<float const *> g(n);
+      for (size_t i = 0; i < n; ++i) g[i] = var_ptr("g_" + std::to_string(i));
+      float *const partials = var_ptr("partials");
+      long k = so.part0;
+      for (size_t i = 0; i < n; ++i)
+        for (long e0 = 0; e0 < so.elems[i]; e0 += kSolverChunk, ++k) partials[k] = solver_chunk_sumsq(g[i] + e0, std::min(kSolverChunk, so.elems[i] - e0));
+    } else {
+      float const *partials = var_ptr("partials"); float const *hy = var_ptr("hyper");
+      solver_grad_norm(partials, so.parts, hy[6], var_ptr("state"));
+    }
+  }
+
   // the training BatchNorm functions and hip_fan_out: the checks of be=hip (csrc/native_run.cc), then the twins above
   void run_bn(op_base_t const &op, map_str_rtc_arg_t const &am) {
     string const fn = op.get_func_name();
@@ -792,6 +884,7 @@ struct cpu_compute_t : public rtc_compute_t {
     double const tb = now_ms();
     if (f.family == kFamSgd) run_sgd_update(fi.op, am);
     else if (f.family == kFamBn || f.family == kFamBnc) run_bn(fi.op, am);
+    else if (f.family == kFamSolver) run_solver(fi.op, am);
     else if (f.family == kFamBckOp) run_bck_op(f, fi.op, am);
     else if (f.family == kFamBconv) run_bck(f, fi.op, am);
     else if (f.family == kFamSgemm) {

@@ -180,6 +180,36 @@ struct sgd_update_args_t {
 static_assert(sizeof(sgd_tensor_t) == 48 && sizeof(sgd_update_args_t) == 16 + 48 * kSgdMaxTens && __builtin_offsetof(sgd_tensor_t, n) == 24 && __builtin_offsetof(sgd_tensor_t, lr_mult) == 32 &&
               __builtin_offsetof(sgd_tensor_t, quads) == 40 && __builtin_offsetof(sgd_update_args_t, tens_num) == 8 && __builtin_offsetof(sgd_update_args_t, t) == 16, "sgd_tensor_t / sgd_update_args_t layout");
 
+// kernels/solver_update_f32.hip: the tables of up to kSgdMaxTens tensors ride by value in the kernel arguments
+struct solver_tensor_t {
+  float *w; float const *g; float *h; float *h2;   // h2: adam's second history (null otherwise)
+  unsigned n, blk0;                      // elements; index of the tensor's first workgroup
+  float lr_mult, decay_mult;
+  unsigned quads, pad;                   // 1: w, g, h (and h2) are 16-byte aligned
+};
+struct solver_update_args_t {
+  float const *hyper;                    // lr, momentum, weight_decay, momentum2, delta, corr, clip_gradients, unused
+  float const *state;                    // coef, norm, sumsq, 0: read with CLIP=1 only
+  unsigned tens_num, pad;
+  solver_tensor_t t[kSgdMaxTens];
+};
+static_assert(sizeof(solver_tensor_t) == 56 && sizeof(solver_update_args_t) == 24 + 56 * kSgdMaxTens && __builtin_offsetof(solver_tensor_t, h2) == 24 && __builtin_offsetof(solver_tensor_t, n) == 32 &&
+              __builtin_offsetof(solver_tensor_t, lr_mult) == 40 && __builtin_offsetof(solver_tensor_t, quads) == 48 && __builtin_offsetof(solver_update_args_t, state) == 8 &&
+              __builtin_offsetof(solver_update_args_t, tens_num) == 16 && __builtin_offsetof(solver_update_args_t, t) == 24, "solver_tensor_t / solver_update_args_t layout");
+struct sumsq_tensor_t { float const *g; unsigned n, blk0; };
+struct grad_sumsq_args_t {
+  float *partials;                       // the workgroup of chunk k writes partials[part0 + k]
+  unsigned tens_num, part0;
+  sumsq_tensor_t t[kSgdMaxTens];
+};
+static_assert(sizeof(sumsq_tensor_t) == 16 && sizeof(grad_sumsq_args_t) == 16 + 16 * kSgdMaxTens && __builtin_offsetof(sumsq_tensor_t, n) == 8 && __builtin_offsetof(grad_sumsq_args_t, tens_num) == 8 &&
+              __builtin_offsetof(grad_sumsq_args_t, part0) == 12 && __builtin_offsetof(grad_sumsq_args_t, t) == 16, "sumsq_tensor_t / grad_sumsq_args_t layout");
+struct grad_norm_args_t {
+  float const *partials; float const *hyper; float *state;
+  unsigned n_parts, pad;
+};
+static_assert(sizeof(grad_norm_args_t) == 32 && __builtin_offsetof(grad_norm_args_t, state) == 16 && __builtin_offsetof(grad_norm_args_t, n_parts) == 24, "grad_norm_args_t layout");
+
 // kernels/bn_f32.hip: the training BatchNorm functions and hip_fan_out
 struct bn_args_t {
   float const *in; float const *dy;                                   // the tensors read

@@ -45,6 +45,11 @@ bck_plan_t plan_shard_sum(int nslabs, long stride, long n);   // OP 14 of the sa
 constexpr long kSgdChunk = 4096;   // floats of one tensor a workgroup owns
 struct sgd_plan_t { plan_t p; uint32_t grid = 0, block = 256; std::vector<uint32_t> blk0; double algo_bytes = 0; };
 sgd_plan_t plan_sgd_update(std::vector<long> const &elems);
+// the solver family (kernels/solver_update_f32.hip; solver_update_args_t, grad_sumsq_args_t, grad_norm_args_t): the same chunking, so the same plan record.  hip_grad_norm:
+// one workgroup, blk0 empty
+static_assert(kSolverChunk == kSgdChunk, "the solver family cuts tensors into hip_sgd_update's chunks");
+sgd_plan_t plan_solver(solver_op_t const &so);
+string solver_plan_desc(solver_op_t const &so, sgd_plan_t const &sp);
 
 // the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip, bn_args_t)
 // the kernels of one call in launch order: op 1 (a sum over slabs; mode 0 S1, 1 S2, 2 the bck_sums pair), 2 (the finalising step; fin 1 stats, 2 bck_sums), 3 fwd, 4 bck_in, 5 fan_out

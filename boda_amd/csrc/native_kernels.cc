@@ -63,6 +63,9 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
     sgd_op_t const so = sgd_op_of_op(fi.op);
     (void)get_kernel(impl, host, plan_sgd_update(so.elems).p);
   } break;
+  case kFamSolver:   // likewise: the op whole, the code object built now
+    (void)get_kernel(impl, host, plan_solver(solver_op_of_op(fi.op)).p);
+    break;
   case kFamBn: case kFamBnc:   // the op must be whole; the code objects of all the call's launches are built NOW, so that a first run inside a graph capture finds them
     for (bn_launch_t const &l : plan_bn(bn_op_of_op(fi.op)).ls) (void)get_kernel(impl, host, l.p);
     break;
@@ -879,6 +882,49 @@ void native_kernels_t::sgd_update(int n, sgd_member_t const *m, float const *hyp
   for (int i = n; i < kSgdMaxTens; ++i) a.t[i].blk0 = 0xffffffffu;   // (never reached: the kernel's scan stops at tens_num)
   void *params[] = {&a};
   if (sp.grid) hip_err_chk(host->nh_launch(k.func, sp.grid, 1, sp.block, params), "hipModuleLaunchKernel(sgd_update)");
+  last_launch.kernel = sp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = sp.grid; last_launch.block = sp.block;
+  last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
+}
+// ---- the solver family (kernels/solver_update_f32.hip): one launch per call, the tables by value in the kernel arguments
+void native_kernels_t::solver_update(solver_op_t const &so, solver_member_t const *m, float const *hyper, float const *state) {
+  sgd_plan_t const sp = plan_solver(so);
+  kernel_t &k = get_kernel(impl, host, sp.p);
+  int const n = (int)so.elems.size();
+  solver_update_args_t a; memset(&a, 0, sizeof(a));
+  a.hyper = hyper; a.state = state; a.tens_num = (unsigned)n;
+  for (int i = 0; i < n; ++i) {
+    solver_tensor_t &t = a.t[i];
+    t.w = m[i].w; t.g = m[i].g; t.h = m[i].h; t.h2 = so.type == kSolverAdam ? m[i].h2 : nullptr;
+    t.n = (unsigned)so.elems[(size_t)i]; t.blk0 = sp.blk0[(size_t)i]; t.lr_mult = so.lr_mult[(size_t)i]; t.decay_mult = so.decay_mult[(size_t)i];
+    t.quads = ((((uintptr_t)t.w | (uintptr_t)t.g | (uintptr_t)t.h | (uintptr_t)t.h2) & 15) == 0) ? 1u : 0u;   // float4 where all of them are 16-byte aligned (a chunk starts on a quad)
+  }
+  for (int i = n; i < kSgdMaxTens; ++i) a.t[i].blk0 = 0xffffffffu;   // (never reached: the kernel's scan stops at tens_num)
+  void *params[] = {&a};
+  if (sp.grid) hip_err_chk(host->nh_launch(k.func, sp.grid, 1, sp.block, params), "hipModuleLaunchKernel(solver_update)");
+  last_launch.kernel = sp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = sp.grid; last_launch.block = sp.block;
+  last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
+}
+void native_kernels_t::grad_sumsq(solver_op_t const &so, float const *const *g, float *partials) {
+  sgd_plan_t const sp = plan_solver(so);
+  if ((long)so.part0 + (long)sp.grid > so.parts) rt_err("hip_grad_sumsq: part0 + chunks exceed the partials");   // (solver_op_of_op has refused it: the kernel's only store is partials[part0 + k])
+  kernel_t &k = get_kernel(impl, host, sp.p);
+  int const n = (int)so.elems.size();
+  grad_sumsq_args_t a; memset(&a, 0, sizeof(a));
+  a.partials = partials; a.tens_num = (unsigned)n; a.part0 = so.part0;
+  for (int i = 0; i < n; ++i) { a.t[i].g = g[i]; a.t[i].n = (unsigned)so.elems[(size_t)i]; a.t[i].blk0 = sp.blk0[(size_t)i]; }
+  for (int i = n; i < kSgdMaxTens; ++i) a.t[i].blk0 = 0xffffffffu;
+  void *params[] = {&a};
+  if (sp.grid) hip_err_chk(host->nh_launch(k.func, sp.grid, 1, sp.block, params), "hipModuleLaunchKernel(grad_sumsq)");
+  last_launch.kernel = sp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = sp.grid; last_launch.block = sp.block;
+  last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
+}
+void native_kernels_t::grad_norm(solver_op_t const &so, float const *partials, float const *hyper, float *state) {
+  sgd_plan_t const sp = plan_solver(so);
+  kernel_t &k = get_kernel(impl, host, sp.p);
+  grad_norm_args_t a; memset(&a, 0, sizeof(a));
+  a.partials = partials; a.hyper = hyper; a.state = state; a.n_parts = (unsigned)so.parts;
+  void *params[] = {&a};
+  hip_err_chk(host->nh_launch(k.func, sp.grid, 1, sp.block, params), "hipModuleLaunchKernel(grad_norm)");
   last_launch.kernel = sp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = sp.grid; last_launch.block = sp.block;
   last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
 }

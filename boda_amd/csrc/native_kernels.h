@@ -26,6 +26,9 @@
 //     hip_sgd_update                    this backend's own (the reference has no solver): n = tens_num and the floats lr_mult_i / decay_mult_i in the op; hyper is float v=4: lr,
 //                                       momentum, weight_decay, unused.  g1 = g + (wd * decay_mult_i) * w; h' = momentum * h + (lr * lr_mult_i) * g1; w' = w - h', every
 //                                       operation one fp32 rounding.  One launch for all tensors (kernels/sgd_update_f32.hip); the code object is built when the function is compiled
+//     hip_solver_update / hip_grad_sumsq / hip_grad_norm    this backend's own: SGD, Nesterov and Adam over up to 32 tensors per launch (str_val solver_type; hyper float v=8),
+//                                       and global-norm clipping as a sum of squares per chunk, one finishing launch and the coefficient in `state` (float v=4), which the
+//                                       update reads with clip=1.  kernels/solver_update_f32.hip states the chains and the tree; code objects built when the function is compiled
 //     hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out    this backend's own: the training BatchNorm of the gradient pipe (batch statistics, running
 //                                       pair, normalise + scale + bias + ReLU, the two gradients) and the gradient of an Eltwise SUM.  kernels/bn_f32.hip states the arithmetic and
 //                                       the order of the per-channel sums
@@ -144,6 +147,12 @@ struct native_kernels_t {
   // hip_sgd_update on raw device pointers: n (1 .. 32) tensors of m[i].n floats, hyper = {lr, momentum, weight_decay, unused} in device memory
   struct sgd_member_t { float *w; float const *g; float *h; long n; float lr_mult, decay_mult; };
   void sgd_update(int n, sgd_member_t const *m, float const *hyper);
+  // the solver family on raw device pointers (so says which kernel: solver_op_of_op).  solver_update: so.elems.size() tensors, h2 non-null for adam; hyper float[8], state
+  // float[4].  grad_sumsq: chunk k of the call writes partials[so.part0 + k].  grad_norm: so.parts partials -> state
+  struct solver_member_t { float *w; float const *g; float *h; float *h2; };
+  void solver_update(solver_op_t const &so, solver_member_t const *m, float const *hyper, float const *state);
+  void grad_sumsq(solver_op_t const &so, float const *const *g, float *partials);
+  void grad_norm(solver_op_t const &so, float const *partials, float const *hyper, float *state);
   void shard_sum(float const *slabs, float *out, int nslabs, long stride, long n);
   // hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out on raw device pointers (kernels/bn_f32.hip): tens / chans in bn_op_t's arg order
   void bn_call(bn_op_t const &b, float *const *tens, float *const *chans);

@@ -1424,6 +1424,40 @@ sgd_plan_t plan_sgd_update(std::vector<long> const &elems) {
   return r;
 }
 
+// ---- the solver family (kernels/solver_update_f32.hip).  hip_solver_update / hip_grad_sumsq: hip_sgd_update's chunking.  Bytes per element: sgd and nesterov 20 (w, g, h
+// read, h and w written), adam 28 (h2 read and written too), the sum of squares 4; hip_grad_norm reads the partials and writes four words
+sgd_plan_t plan_solver(solver_op_t const &so) {
+  static char const *const fns[] = {"", "hip_solver_update", "hip_grad_sumsq", "hip_grad_norm"};
+  string const what = fns[so.kind];
+  sgd_plan_t r; r.p.src = kSrc_solver_update_f32;
+  r.p.defs = {"-DOP=" + std::to_string(so.kind)};
+  if (so.kind == 3) { r.p.kname = "bodahip_grad_norm"; r.grid = 1; r.algo_bytes = 4.0 * (double)so.parts + 16.0; return r; }
+  if (so.kind == 1) {
+    r.p.kname = string("bodahip_solver_update_") + kSolverTypeNames[so.type];
+    r.p.defs.push_back("-DSOLVER=" + std::to_string(so.type)); r.p.defs.push_back(string("-DCLIP=") + (so.clip ? "1" : "0")); r.p.defs.push_back(string("-DDWD=") + (so.decoupled_wd ? "1" : "0"));
+  } else r.p.kname = "bodahip_grad_sumsq";
+  if (so.elems.empty() || (int)so.elems.size() > kSgdMaxTens) rt_err(what + ": tens_num=" + std::to_string(so.elems.size()) + ": 1 to " + std::to_string(kSgdMaxTens) + " tensors");
+  uint64_t blocks = 0; double tot = 0;
+  for (long n : so.elems) {
+    if (n < 0) rt_err(what + ": negative size");
+    if (4.0 * (double)n >= 2147483648.0) unsup_err(what + ": tensors of 2 GiB or more (32-bit element offsets)");
+    r.blk0.push_back((uint32_t)blocks);
+    blocks += (uint64_t)((n + kSgdChunk - 1) / kSgdChunk); tot += (double)n;
+  }
+  if (blocks >= (1ull << 31)) unsup_err(what + ": too many workgroups");
+  r.grid = (uint32_t)blocks;
+  r.algo_bytes = so.kind == 2 ? 4.0 * tot + 4.0 * (double)blocks : (so.type == kSolverAdam ? 28.0 : 20.0) * tot;
+  return r;
+}
+string solver_plan_desc(solver_op_t const &so, sgd_plan_t const &sp) {
+  string d = sp.p.kname + " grid=" + std::to_string(sp.grid) + " block=" + std::to_string(sp.block);
+  if (so.kind == 3) return d + " parts=" + std::to_string(so.parts);
+  d += " tens=" + std::to_string(sp.blk0.size()) + " chunk=" + std::to_string(kSgdChunk);
+  if (so.kind == 1) d += string(" clip=") + (so.clip ? "1" : "0") + (so.type == kSolverAdam ? string(" decoupled_wd=") + (so.decoupled_wd ? "1" : "0") : string());
+  else d += " part0=" + std::to_string(so.part0);
+  return d;
+}
+
 // ---- the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip): the kernels of one call in launch order.  The slab plan itself is bn_slab_plan's
 // (rtc_types.h), shared with be=cpu; nothing here depends on the device.  algo_bytes counts every tensor of the call once
 plan_t bn_kernel_plan(int op, char const *kname, vect_string const &defs) {

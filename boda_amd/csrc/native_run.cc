@@ -261,6 +261,12 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     sgd_plan_t const sp = plan_sgd_update(sgd_op_of_op(op).elems);
     if (plan_out) *plan_out = sp.p.kname + " grid=" + std::to_string(sp.grid) + " block=" + std::to_string(sp.block) + " tens=" + std::to_string(sp.blk0.size()) + " chunk=" + std::to_string(kSgdChunk);
     return arch.empty() ? 0 : compile_plan(sp.p, arch, &log).size();
+  } else if (fam == kFamSolver) {   // (kernels/solver_update_f32.hip: one kernel per function; the update specialised by solver_type, clip and decoupled_wd, never by shape)
+    if (!f) rt_err("prebuild: a bare " + t + " op: the solver's ops are function ops (cnn_op.solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op)");
+    solver_op_t const so = solver_op_of_op(op);
+    sgd_plan_t const sp = plan_solver(so);
+    if (plan_out) *plan_out = solver_plan_desc(so, sp);
+    return arch.empty() ? 0 : compile_plan(sp.p, arch, &log).size();
   } else if (fam == kFamBn || fam == kFamBnc) {   // (kernels/bn_f32.hip: every launch of the call, and the slab plan)
     bn_op_t const b = bn_op_of_op(op);
     bn_plan_t const bp = plan_bn(b);
@@ -695,6 +701,34 @@ struct native_kernels_t::call_t {
     float const *hyper = (float const *)var_ptr("hyper");
     nk.sgd_update(n, ms.data(), hyper);
   }
+  void run_solver() {
+    // as run_sgd: every var has exactly the dims the op gives its arg, and all the call's vars are different ones
+    solver_op_t const so = solver_op_of_op(fi.op);
+    size_t const n = so.elems.size();
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    auto var_ptr = [&](string const &an) -> float * {
+      string const vn = var_of_op_dims(an, "the solver is fp32 only");
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      return (float *)host->nh_var_ptr(vn);
+    };
+    if (so.kind == 1) {
+      std::vector<solver_member_t> ms(n);
+      for (size_t i = 0; i < n; ++i) {
+        string const sx = "_" + std::to_string(i);
+        ms[i].w = var_ptr("w" + sx); ms[i].g = var_ptr("g" + sx); ms[i].h = var_ptr("h" + sx); ms[i].h2 = so.type == kSolverAdam ? var_ptr("h2" + sx) : nullptr;
+      }
+      float const *hyper = var_ptr("hyper"); float const *state = var_ptr("state");
+      nk.solver_update(so, ms.data(), hyper, state);
+    } else if (so.kind == 2) {
+      std::vector<float const *> gs(n);
+      for (size_t i = 0; i < n; ++i) gs[i] = var_ptr("g_" + std::to_string(i));
+      nk.grad_sumsq(so, gs.data(), var_ptr("partials"));
+    } else {
+      float const *partials = var_ptr("partials"); float const *hyper = var_ptr("hyper");
+      nk.grad_norm(so, partials, hyper, var_ptr("state"));
+    }
+  }
   void run_bn() {
     // every var must have exactly the dims the op gives its arg (the sums run over the whole batch: no img shards), and no two args may be one var except where
     // kernels/bn_f32.hip allows in-place use
@@ -817,6 +851,7 @@ void native_kernels_t::run(native_func_t const &f, rtc_func_info_t const &fi, ma
   case kFamBckOp: c.run_bck_op(); break;
   case kFamSgd: c.run_sgd(); break;
   case kFamBn: case kFamBnc: c.run_bn(); break;
+  case kFamSolver: c.run_solver(); break;
   }
 }
 

@@ -129,7 +129,7 @@ struct op_base_t {
 };
 typedef std::shared_ptr<op_base_t> p_op_base_t;
 // ---- the op flags of a native function.  Which function takes which flag is a column of the one table, native_funcs.h (included at the end of this file), which defines:
-enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc };   // selects the handler
+enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver };   // selects the handler
 enum : unsigned { kFlagZinp = 1, kFlagSeedVar = 2, kFlagImgShards = 4, kFlagNhwcResidual = 8 };
 struct op_flag_name_t { char const *name; unsigned flag; };
 constexpr op_flag_name_t kOpFlagNames[] = {{"img_shards", kFlagImgShards}, {"seed_from_var", kFlagSeedVar}, {"zero_if_in_non_pos", kFlagZinp}, {"nhwc_residual", kFlagNhwcResidual}};
@@ -219,6 +219,70 @@ inline sgd_op_t sgd_op_of_op(op_base_t const &op) {
     }
     r.elems.push_back((long)w.dims_prod()); r.lr_mult.push_back(f32("lr_mult" + sx)); r.decay_mult.push_back(f32("decay_mult" + sx));
   }
+  return r;
+}
+
+// ---- the solver family (this backend's own; kernels/solver_update_f32.hip states the chains): hip_solver_update (op type SolverUpdate, member 1), hip_grad_sumsq (GradSumsq,
+// member 2), hip_grad_norm (GradNorm, member 3).  What both backends read from the function's op, and every refusal that needs the op alone
+constexpr long kSolverChunk = 4096;   // floats of one tensor a workgroup owns; one partial sum of squares per chunk
+enum { kSolverSgd = 0, kSolverNesterov = 1, kSolverAdam = 2 };
+inline constexpr char const *kSolverTypeNames[] = {"sgd", "nesterov", "adam"};
+struct solver_op_t {
+  int kind = 0;                          // the member: 1 update, 2 sumsq, 3 norm
+  int type = kSolverSgd; bool clip = false, decoupled_wd = false;   // kind 1
+  std::vector<long> elems; std::vector<float> lr_mult, decay_mult;  // kinds 1, 2: per tensor (the multipliers: kind 1)
+  uint32_t part0 = 0; long parts = 0;    // kind 2: the first partial this call writes; kinds 2, 3: the size of the partials var
+  long chunks() const { long c = 0; for (long n : elems) c += (n + kSolverChunk - 1) / kSolverChunk; return c; }
+};
+inline solver_op_t solver_op_of_op(op_base_t const &op) {
+  string const fn = op.get_func_name();
+  solver_op_t r;
+  r.kind = native_func_member(fn, kFamSolver);
+  if (!r.kind) rt_err("'" + fn + "' is none of " + native_family_names(kFamSolver));
+  string const type = native_func_type(kFamSolver, r.kind);
+  if (op.get_type() != type) rt_err(fn + ": a function of op type " + type + ", not " + op.get_type());
+  refuse_flags_not_taken(op, fn, "the solver");
+  auto need = [&](string const &an) { if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'"); };
+  auto vec = [&](string const &an, uint32_t v, char const *what) -> long {   // float v=<v> (v == 0: any length of at least 1)
+    need(an); dims_t const &d = op.get_dims(an);
+    if (d.tn != "float" || d.sz() != 1 || d.names(0) != "v" || (v ? d.dims(0) != v : d.dims(0) < 1)) rt_err(fn + ": " + an + " must be float v=" + (v ? std::to_string(v) : string("<partials>")) + " (" + what + "), got " + d.tn + " " + d.pretty_str());
+    return (long)d.dims(0); };
+  auto flag = [&](char const *an) { if (!op.has(an)) return false; uint32_t const v = op.get_u32(an); if (v > 1) rt_err(fn + ": " + an + " must be 0 | 1"); return v == 1; };
+  auto f32 = [&](string const &an) { p_nda_t const &v = op.get(an); if (v->dims.tn != "float" || v->dims.sz() != 0 || !v->rp) rt_err(fn + ": '" + an + "' is not a float scalar"); return *static_cast<float const *>(v->rp); };
+  if (r.kind == 3) {
+    r.parts = vec("partials", 0, "one partial per chunk"); vec("hyper", 8, "lr, momentum, weight_decay, momentum2, delta, corr, clip_gradients, unused"); vec("state", 4, "coef, norm, sumsq, 0");
+    if (4.0 * (double)r.parts >= 2147483648.0) unsup_err(fn + ": partials of 2 GiB or more");
+    return r;
+  }
+  if (r.kind == 1) {
+    auto st = op.str_vals.find("solver_type");
+    if (st == op.str_vals.end()) rt_err(fn + ": the op has no str_val 'solver_type' (sgd | nesterov | adam)");
+    r.type = -1; for (int i = 0; i < 3; ++i) if (st->second == kSolverTypeNames[i]) r.type = i;
+    if (r.type < 0) rt_err(fn + ": solver_type must be sgd | nesterov | adam, got '" + st->second + "'");
+    r.clip = flag("clip"); r.decoupled_wd = flag("decoupled_wd");
+    if (r.decoupled_wd && r.type != kSolverAdam) rt_err(fn + ": decoupled_wd=1 is adam's, not " + st->second + "'s");
+  }
+  if (!op.has("tens_num")) rt_err(fn + ": the op has no 'tens_num'");
+  uint32_t const n = op.get_u32("tens_num");
+  if (n < 1 || n > (uint32_t)kSgdUpdateMaxTens) rt_err(fn + ": tens_num=" + std::to_string(n) + ": 1 to " + std::to_string(kSgdUpdateMaxTens) + " tensors");
+  if (r.kind == 1) { vec("hyper", 8, "lr, momentum, weight_decay, momentum2, delta, corr, clip_gradients, unused"); vec("state", 4, "coef, norm, sumsq, 0"); }
+  else { r.parts = vec("partials", 0, "one partial per chunk"); need("part0"); r.part0 = op.get_u32("part0"); }
+  for (uint32_t i = 0; i < n; ++i) {
+    string const sx = "_" + std::to_string(i);
+    std::vector<string> bases = r.kind == 1 ? std::vector<string>{"w", "g", "h"} : std::vector<string>{"g"};
+    if (r.kind == 1 && r.type == kSolverAdam) bases.push_back("h2");
+    for (string const &b : bases) need(b + sx);
+    dims_t const &w = op.get_dims(bases[0] + sx);
+    for (string const &b : bases) {
+      dims_t const &d = op.get_dims(b + sx);
+      if (d.tn != "float") rt_err(fn + ": " + b + sx + " has type " + d.tn + ": the solver is fp32 only");
+      if (!(d == w)) rt_err(fn + ": " + b + sx + " dims " + d.pretty_str() + " differ from " + bases[0] + sx + "'s " + w.pretty_str());
+    }
+    r.elems.push_back((long)w.dims_prod());
+    if (r.kind == 1) { need("lr_mult" + sx); need("decay_mult" + sx); r.lr_mult.push_back(f32("lr_mult" + sx)); r.decay_mult.push_back(f32("decay_mult" + sx)); }
+  }
+  if (r.kind == 2 && (long)r.part0 + r.chunks() > r.parts)
+    rt_err(fn + ": part0=" + std::to_string(r.part0) + " + " + std::to_string(r.chunks()) + " chunks exceed the " + std::to_string(r.parts) + " partials");
   return r;
 }
 

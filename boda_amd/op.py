@@ -271,6 +271,12 @@ OP_INFO = {
     # this backend's own (the reference has no solver): the SGD update of up to 32 tensors.  The multi args w / g / h ride flattened as w_0 .. w_{tens_num-1} etc., with the
     # floats lr_mult_i / decay_mult_i beside them; w and h are read and written, g and hyper (float v=4: lr, momentum, weight_decay, unused) read
     "SgdUpdate": (("hyper",), (), ("tens_num",)),
+    # this backend's own: the solvers beyond plain SGD and global-norm clipping (csrc/kernels/solver_update_f32.hip states the chains).  SolverUpdate: the multi args w / g / h
+    # (and h2 for solver_type=adam) flattened as for SgdUpdate; hyper float v=8 (lr, momentum, weight_decay, momentum2, delta, corr, clip_gradients, unused), state float v=4
+    # (coef, norm, sumsq, 0).  GradSumsq: the multi arg g, one partial per chunk of 4096 elements into partials[part0 ..].  GradNorm: partials -> state
+    "SolverUpdate": (("hyper", "state"), (), ("tens_num",)),
+    "GradSumsq": ((), ("partials",), ("tens_num", "part0")),
+    "GradNorm": (("partials", "hyper"), ("state",), ()),
     # this backend's own: the training BatchNorm of the gradient pipe and the gradient of an Eltwise SUM (csrc/kernels/bn_f32.hip states the arithmetic).  The per-channel
     # args are float chan=C; run_mean / run_var are read and written; slab (0: the planner's) forces the slab length of the per-channel sums; FanOut writes the multi arg outs
     "BnStats": (("in",), ("mean", "inv_std", "run_mean", "run_var"), ("eps", "maf", "slab")),
@@ -280,9 +286,11 @@ OP_INFO = {
     "FanOut": (("in",), (), ("outs_num",)),
 }
 BN_TYPES = ("BnStats", "BnFwd", "BnBckSums", "BnBckIn", "FanOut")
+SOLVER_TYPES = ("SolverUpdate", "GradSumsq", "GradNorm")
+SOLVER_CHUNK = 4096   # floats of one tensor a workgroup owns; one partial sum of squares per chunk
 
 
-_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES
+_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + SOLVER_TYPES
 
 
 @dataclass
@@ -533,6 +541,55 @@ class Op:
             elems.append(w.dims_prod())
         return dict(n=n, elems=elems)
 
+    def solver_geom(self) -> dict:
+        """SolverUpdate / GradSumsq / GradNorm, with sgd_geom's checks: 1 to 32 tensors of identical float dims per tensor (w_i g_i h_i, h2_i for adam | g_i), hyper float
+        v=8, state float v=4, partials float v=P with part0 + the call's chunks <= P.  -> n, elems, chunks (GradNorm: parts)."""
+        t = self.get_type()
+
+        def vec(an, v, what):
+            d = self.get_dims(an)
+            if d.names != ("v",) or d.tn != "float" or (d.sizes != (v,) if v else d.sizes[0] < 1):
+                raise RtErr(f"{t}: {an} must be float v={v or '<partials>'} ({what}), got {d.tn} {d.pretty()}")
+            return d.sizes[0]
+        hyper = "lr, momentum, weight_decay, momentum2, delta, corr, clip_gradients, unused"
+        if t == "GradNorm":
+            parts = vec("partials", 0, "one partial per chunk"); vec("hyper", 8, hyper); vec("state", 4, "coef, norm, sumsq, 0")
+            return dict(parts=parts)
+        bases = ("g",)
+        if t == "SolverUpdate":
+            st = self.str_vals.get("solver_type")
+            if st not in ("sgd", "nesterov", "adam"):
+                raise RtErr(f"SolverUpdate: solver_type must be sgd | nesterov | adam, got {st!r}")
+            for fl in ("clip", "decoupled_wd"):
+                if self.has(fl) and self.get_u32(fl) not in (0, 1):
+                    raise RtErr(f"SolverUpdate: {fl} must be 0 | 1")
+            if self.has("decoupled_wd") and self.get_u32("decoupled_wd") and st != "adam":
+                raise RtErr(f"SolverUpdate: decoupled_wd=1 is adam's, not {st}'s")
+            bases = ("w", "g", "h") + (("h2",) if st == "adam" else ())
+        n = self.get_u32("tens_num")
+        if n < 1 or n > 32:
+            raise RtErr(f"{t}: tens_num={n}: 1 to 32 tensors")
+        if t == "SolverUpdate":
+            vec("hyper", 8, hyper); vec("state", 4, "coef, norm, sumsq, 0")
+        elems = []
+        for i in range(n):
+            w = self.get_dims(f"{bases[0]}_{i}")
+            for b in bases:
+                d = self.get_dims(f"{b}_{i}")
+                if d.tn != "float":
+                    raise RtErr(f"{t}: {b}_{i} has type {d.tn}: the solver is fp32 only")
+                if d != w:
+                    raise RtErr(f"{t}: {b}_{i} dims {d.pretty()} differ from {bases[0]}_{i}'s {w.pretty()}")
+            if t == "SolverUpdate":
+                self.get_f32(f"lr_mult_{i}"); self.get_f32(f"decay_mult_{i}")
+            elems.append(w.dims_prod())
+        chunks = sum(-(-e // SOLVER_CHUNK) for e in elems)
+        if t == "GradSumsq":
+            parts = vec("partials", 0, "one partial per chunk")
+            if self.get_u32("part0") + chunks > parts:
+                raise RtErr(f"GradSumsq: part0={self.get_u32('part0')} + {chunks} chunks exceed the {parts} partials")
+        return dict(n=n, elems=elems, chunks=chunks)
+
     def bn_geom(self) -> dict:
         """BnStats / BnFwd / BnBckSums / BnBckIn: float img:chan:y:x tensors of equal dims, the per-channel args float chan=C; FanOut: in and 2 to 8 outs of equal float dims."""
         t = self.get_type()
@@ -606,6 +663,13 @@ class Op:
         """4*(in+out+filts+biases) resp. 4*(a+b+c) (src/latex-util.H:119,133)."""
         if self.get_type() == "SgdUpdate":   # w, g, h read, h and w written
             return 20 * sum(self.sgd_geom()["elems"])
+        if self.get_type() == "SolverUpdate":   # adam reads and writes h2 as well
+            return (28 if self.str_vals.get("solver_type") == "adam" else 20) * sum(self.solver_geom()["elems"])
+        if self.get_type() == "GradSumsq":   # every gradient read once, one partial written per chunk
+            g = self.solver_geom()
+            return 4 * sum(g["elems"]) + 4 * g["chunks"]
+        if self.get_type() == "GradNorm":   # the partials read, four words written
+            return 4 * self.solver_geom()["parts"] + 16
         ins, outs, _ = OP_INFO[self.get_type()]
         multi = {"Reduce": ("ins",), "Concat": ("ins",), "Split": ("outs",), "FanOut": ("outs",)}.get(self.get_type(), ())
         return sum(self.get_dims(a).bytes_sz() for a in ins + outs + tuple(n for m in multi for n in self.multi_names(m)))
@@ -668,6 +732,8 @@ def parse_op(line: str) -> Op:
             op.sgd_geom()
         elif t in BN_TYPES:
             op.bn_geom()
+        elif t in SOLVER_TYPES:
+            op.solver_geom()
         else:
             op.sgemm_geom()
     return op

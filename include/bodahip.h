@@ -157,7 +157,7 @@ int bodahip_prebuild(const char *op_lexp, const char *arch, int num_cus, const c
  * (variant / blocking selection is host logic: the counterpart of add_codegen_annotations' choice, src/cnn_op.cc:16-378) */
 int bodahip_explain_plan(const char *op_lexp, int num_cus, const char *tile, char *plan_buf, size_t plan_buf_sz);
 /* the table of native functions (csrc/native_funcs.h), one line per function name:
- *   "<name> family=<family> member=<n> types=<T[,T]> flags=<flag[,flag] | -> be=<hip[,cpu]> multi_dev=<on_shards | replicated_only | needs_flag | refused> opt=<arg:KIND | -> why=<sentence>"
+ *   "<name> family=<family> member=<n> types=<T[,T]> flags=<flag[,flag] | -> be=<hip[,cpu]> multi_dev=<on_shards | replicated_only | needs_flag | refused | replicated_vars> opt=<arg:KIND | -> why=<sentence>"
  * (why: what a multi-device backend answers an unflagged / any call of a needs_flag / refused function; it runs to the end of the line).  Host-only, no context. */
 int bodahip_native_funcs(char *buf, size_t buf_sz);
 /* the args of an annotated function op in call order, "arg:KIND arg:KIND ..." with KIND one of IN OUT INOUT REF VAL: the table's fixed args with the part that depends
