@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, bnc_bck_in_func_op, bnc_bck_sums_func_op, bnc_fwd_func_op, bnc_stats_func_op, BNC_MAX_CHUNKS, fan_out_func_op, sgd_update_func_op, solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
+from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, bnc_bck_in_func_op, bnc_bck_sums_func_op, bnc_fwd_func_op, bnc_stats_func_op, BNC_MAX_CHUNKS, fan_out_func_op, sgd_update_func_op, solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op, grad_accum_func_op, solver_update_acc_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
                      pipe_func_args, seed_from_var, SEED_VAR_ARG, bf16_operands)
 from .conv_pipe import ConvPipe, PipeOp
 from .op import Dims, Nda, Op, RtErr, SOLVER_CHUNK, UnsupErr
@@ -70,6 +70,8 @@ SOLVER_HYPER_VAR = "solver_hyper"    # ConvPipeBck(solver=Solver(...)): float v=
 SOLVER_STATE_VAR = "solver_state"    # float v=4 = [coef, norm, sumsq, 0]: what hip_grad_norm leaves and the clipping update reads
 SOLVER_PARTS_VAR = "solver_gnorm_partials"   # one partial sum of squares per chunk of 4096 floats of every updated param
 SGD_HIST2_SFX = "_sgd_hist2"         # <param>_sgd_hist2: adam's second-moment history
+SOLVER_ACCUM_VAR = "solver_accum"    # ConvPipeBck(iter_size=n > 1): float v=4 = [first, apply, scale, micro], uploaded before every micro-step
+GRAD_ACC_SFX = "_grad_acc"           # <param>_grad_acc: the sum of the param's gradients over the micro-steps since the last update
 
 
 @dataclass
@@ -491,6 +493,14 @@ class ConvPipeBck:
     solver_gnorm_partials, and appends behind every gradient op: when clipping the hip_grad_sumsq calls (grad_sumsq_k) and one grad_norm, then the hip_solver_update calls
     (solver_update_k); n_sgd_calls counts all of them.  `iter` starts at 0; before every step that runs those calls -- eager or a replay -- the 32 bytes of solver_hyper are
     uploaded for step `iter` (lr from the policy, adam's bias correction for t = iter + 1), and `iter` advances behind it.  <param>_grad_loss keeps the unclipped gradient.
+    iter_size=n > 1 (1, the default, leaves the calls, the vars and every bit as they are; needs a Solver): Caffe's gradient accumulation.  A
+    step is a MICRO-step: its gradients are added into <param>_grad_acc (hip_grad_accum; the first micro-step of n overwrites, so nothing is ever cleared), and only the
+    n-th applies the update (hip_solver_update_acc) on 1 / n times the sum -- clipped, when clipping, by the norm of the SUM.  init creates <param>_grad_acc per updated
+    param and solver_accum (float v=4), and appends behind the gradient ops: the grad_accum_k calls, when clipping the grad_sumsq_k calls bound to the accumulators and
+    grad_norm, then the solver_update_k calls; n_sgd_calls counts all of them.  All of them run on every micro-step; before each the 16 bytes [micro == 0, micro == n - 1,
+    fp32(1 / n), micro] are uploaded into solver_accum, which the launches read from device memory: one captured graph serves every micro-step.  `micro` advances modulo
+    n, `iter` only behind the applying micro-step (a learning-rate policy and adam's bias correction count updates).  <param>_grad_loss, the loss and a BatchNorm's
+    statistics are the micro-batch's; the running pair moves on every pass.
     fuse_filts_biases=True (opt-in; False leaves the calls, their names and every bit as they are): every BckConv emits hip_bconv_in followed by ONE
     hip_bconv_filts_biases in place of the hip_bconv_biases + hip_bconv_filts pair.  Every other node holds the same bits; the filter and
     bias gradients follow that function's written chains (on be=cpu: the single chains, the same bits as the pair).  Not on a multi-device backend: init raises UnsupErr.
@@ -514,8 +524,15 @@ class ConvPipeBck:
     stay refused on a multi-device backend."""
 
     def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[object] = None, bn_maf: float = 0.999, fuse_filts_biases: bool = False,
-                 grad_operands: str = "", img_chunks: int = 0):
+                 grad_operands: str = "", img_chunks: int = 0, iter_size: int = 1):
         self.rtc = rtc
+        if not isinstance(iter_size, int) or isinstance(iter_size, bool) or iter_size < 1:
+            raise RtErr(f"ConvPipeBck: iter_size must be an int >= 1, got {iter_size!r}")
+        if iter_size > 1 and not isinstance(solver, Solver):
+            raise RtErr(f"ConvPipeBck: iter_size={iter_size} accumulates gradients for a Solver's update; build the driver with solver=Solver(type=\"sgd\", ...) "
+                        f"(got {'no solver' if solver is None else type(solver).__name__})")
+        self.iter_size = iter_size   # > 1: a step is a micro-step; the update applies on every iter_size-th
+        self.micro = 0               # the next micro-step's index in 0 .. iter_size - 1
         if not isinstance(img_chunks, int) or isinstance(img_chunks, bool) or not 0 <= img_chunks <= BNC_MAX_CHUNKS:
             raise RtErr(f"ConvPipeBck: img_chunks must be an int, 0 (off) or 1 to {BNC_MAX_CHUNKS}, got {img_chunks!r}")
         self.img_chunks = img_chunks   # > 0: the training BatchNorm's sums in the chunked chain over this many img chunks, an Eltwise gradient as hip_split copies
@@ -592,6 +609,8 @@ class ConvPipeBck:
                     raise RtErr("ConvPipeBck.init: Solver.lr_policy must be an LrPolicy or None")
             names = [SGD_HYPER_VAR] if not gen else [SOLVER_HYPER_VAR, SOLVER_STATE_VAR] + ([SOLVER_PARTS_VAR] if self.solver.clip_gradients > 0 else []) + \
                 ([pn + SGD_HIST2_SFX for pn in self.sgd_params] if self.solver.type == "adam" else [])
+            if self.iter_size > 1:
+                names += [SOLVER_ACCUM_VAR] + [pn + GRAD_ACC_SFX for pn in self.sgd_params]
             for vn in [pn + SGD_HIST_SFX for pn in self.sgd_params] + names:
                 if vn in bp.nodes:
                     raise RtErr(f"ConvPipeBck.init: the solver needs the var name {vn!r}, which is a node of the pipe")
@@ -749,22 +768,36 @@ class ConvPipeBck:
             self._var(SOLVER_STATE_VAR, Dims(("v",), (4,), "float"))
             per = int(sv.tensors_per_call)
             groups = [pnames[k:k + per] for k in range(0, len(pnames), per)]
+            acc = self.iter_size > 1
+            gsfx = GRAD_ACC_SFX if acc else "_grad_loss"   # what the norm and the update read: the accumulators, or the step's own gradients
+            if acc:   # the accumulate calls in front of the norm and the update, which then read the accumulators
+                for pn in pnames:
+                    self._var(pn + GRAD_ACC_SFX, bp.cp.params[pn])
+                self._var(SOLVER_ACCUM_VAR, Dims(("v",), (4,), "float"))
+                for k, grp in enumerate(groups):
+                    args = {"accum": SOLVER_ACCUM_VAR}
+                    for i, pn in enumerate(grp):
+                        args.update({f"g_{i}": pn + "_grad_loss", f"a_{i}": pn + GRAD_ACC_SFX})
+                    emit(f"grad_accum_{k}", grad_accum_func_op([bp.cp.params[pn] for pn in grp]), args)
+                    self.n_sgd_calls += 1
             if clip:
                 parts = sum(-(-bp.cp.params[pn].dims_prod() // SOLVER_CHUNK) for pn in pnames)
                 self._var(SOLVER_PARTS_VAR, Dims(("v",), (parts,), "float"))
                 part0 = 0
                 for k, grp in enumerate(groups):
                     fop = grad_sumsq_func_op([bp.cp.params[pn] for pn in grp], part0, parts)
-                    emit(f"grad_sumsq_{k}", fop, dict({f"g_{i}": pn + "_grad_loss" for i, pn in enumerate(grp)}, partials=SOLVER_PARTS_VAR))
+                    emit(f"grad_sumsq_{k}", fop, dict({f"g_{i}": pn + gsfx for i, pn in enumerate(grp)}, partials=SOLVER_PARTS_VAR))
                     part0 += fop.solver_geom()["chunks"]; self.n_sgd_calls += 1
                 emit("grad_norm", grad_norm_func_op(parts), {"partials": SOLVER_PARTS_VAR, "hyper": SOLVER_HYPER_VAR, "state": SOLVER_STATE_VAR})
                 self.n_sgd_calls += 1
             for k, grp in enumerate(groups):
-                fop = solver_update_func_op([bp.cp.params[pn] for pn in grp], sv.type, [sv.mult_of(sv.lr_mult, pn) for pn in grp], [sv.mult_of(sv.decay_mult, pn) for pn in grp],
-                                            clip=clip, decoupled_wd=sv.decoupled_wd)
+                fop = (solver_update_acc_func_op if acc else solver_update_func_op)([bp.cp.params[pn] for pn in grp], sv.type, [sv.mult_of(sv.lr_mult, pn) for pn in grp],
+                                                                                    [sv.mult_of(sv.decay_mult, pn) for pn in grp], clip=clip, decoupled_wd=sv.decoupled_wd)
                 args = {"hyper": SOLVER_HYPER_VAR, "state": SOLVER_STATE_VAR}
+                if acc:
+                    args["accum"] = SOLVER_ACCUM_VAR
                 for i, pn in enumerate(grp):
-                    args.update({f"w_{i}": pn, f"g_{i}": pn + "_grad_loss", f"h_{i}": pn + SGD_HIST_SFX})
+                    args.update({f"w_{i}": pn, f"g_{i}": pn + gsfx, f"h_{i}": pn + SGD_HIST_SFX})
                     if adam:
                         args[f"h2_{i}"] = pn + SGD_HIST2_SFX
                 emit(f"solver_update_{k}", fop, args)
@@ -799,6 +832,8 @@ class ConvPipeBck:
             self.zero_sgd_history()
             if isinstance(self.solver, Solver):
                 self.rtc.copy_nda_to_var(SOLVER_STATE_VAR, np.array([1.0, 0.0, 0.0, 0.0], np.float32))
+                if self.iter_size > 1:
+                    self.rtc.copy_nda_to_var(SOLVER_ACCUM_VAR, self.accum_words())
             self.set_sgd_hyper()
 
     @staticmethod
@@ -853,16 +888,29 @@ class ConvPipeBck:
         h[5] = np.float32(Solver.corr(h[1], h[3], self.iter + 1)) if sv.type == "adam" else np.float32(1.0)
         self.rtc.copy_nda_to_var(SOLVER_HYPER_VAR, h)
 
+    def accum_words(self) -> np.ndarray:
+        """The 16 bytes of solver_accum for the next micro-step: [micro == 0, micro == iter_size - 1, fp32(1 / iter_size), micro]."""
+        n, m = self.iter_size, self.micro
+        return np.array([1.0 if m == 0 else 0.0, 1.0 if m == n - 1 else 0.0, np.float32(1.0 / n), m], np.float32)
+
     def _before_update_step(self) -> None:
         if isinstance(self.solver, Solver):
             self._upload_solver_hyper()
+            if self.iter_size > 1:
+                self.rtc.copy_nda_to_var(SOLVER_ACCUM_VAR, self.accum_words())
 
     def _after_update_step(self) -> None:
         if isinstance(self.solver, Solver):
+            if self.iter_size > 1:   # `iter` counts updates: it advances behind the applying micro-step only
+                applied = self.micro == self.iter_size - 1
+                self.micro = (self.micro + 1) % self.iter_size
+                if not applied:
+                    return
             self.iter += 1
 
     def zero_sgd_history(self) -> None:
-        """Clear every <param>_sgd_hist (and, for adam, <param>_sgd_hist2), and start a Solver's step count `iter` again at 0."""
+        """Clear every <param>_sgd_hist (and, for adam, <param>_sgd_hist2), and start a Solver's step count `iter` -- and, with iter_size > 1, `micro` -- again at 0
+        (the accumulators need no clearing: the first micro-step overwrites them)."""
         if self.solver is None:
             raise RtErr("ConvPipeBck.zero_sgd_history: the driver was built without a solver")
         adam = isinstance(self.solver, Solver) and self.solver.type == "adam"
@@ -871,6 +919,7 @@ class ConvPipeBck:
             if adam:
                 self.rtc.copy_nda_to_var(pn + SGD_HIST2_SFX, np.zeros(self.bp.cp.params[pn].sizes, np.float32))
         self.iter = 0
+        self.micro = 0
 
     def _dropout_calls(self) -> List[Tuple[BckCall, int]]:
         """The dropout calls of the step with their layer's index among the pipe's Dropout ops (a layer's forward and backward call share it)."""

@@ -397,6 +397,36 @@ def grad_norm_func_op(parts_total) -> Op:
     return a
 
 
+GRAD_ACCUM_FUNC, SOLVER_UPDATE_ACC_FUNC = "hip_grad_accum", "hip_solver_update_acc"
+# gradient accumulation over iter_size micro-steps, in a table of its own (SOLVER_OP_FUNCS is pinned): ConvPipeBck(iter_size=n > 1) appends their calls behind the gradient ops
+ACCUM_OP_FUNCS: Dict[str, tuple] = {"GradAccum": (GRAD_ACCUM_FUNC,), "SolverUpdateAcc": (SOLVER_UPDATE_ACC_FUNC,)}
+
+
+def grad_accum_func_op(dims_list) -> Op:
+    """-> the annotated function op of hip_grad_accum over the float tensors `dims_list` (1 to 32): per tensor i the var args g_i (the micro-step's gradient, read) and a_i
+    (the accumulator, rewritten), then accum, float v=4 = [first, apply, scale, micro], read from device memory.  Per element: first != 0: a' = g (a is not read); else
+    a' = a + g, one fp32 add."""
+    dims_list = list(dims_list)
+    v = {"tens_num": Nda(None, "uint32_t", (len(dims_list),)), "accum": _solver_vec(4)}
+    for i, d in enumerate(dims_list):
+        v[f"g_{i}"] = Nda(dims=d, tn=d.tn)
+        v[f"a_{i}"] = Nda(dims=d, tn=d.tn)
+    a = Op({"type": "GradAccum"}, v)
+    a.solver_geom()
+    a.set_func_name(GRAD_ACCUM_FUNC)
+    return a
+
+
+def solver_update_acc_func_op(dims_list, solver_type, lr_mults=None, decay_mults=None, clip=False, decoupled_wd=False) -> Op:
+    """-> the annotated function op of hip_solver_update_acc: solver_update_func_op's op and args (g_i bound to the accumulators) plus the var arg accum, float v=4 =
+    [first, apply, scale, micro].  apply == 0: the launch writes nothing.  Otherwise hip_solver_update's chain on gs = scale * g0 (one rounding), g0 = clip ? coef * g : g:
+    clip on the summed gradient, then normalise, then regularise (Caffe's order).  With scale == 1 the bits are hip_solver_update's."""
+    a = solver_update_func_op(dims_list, solver_type, lr_mults, decay_mults, clip=clip, decoupled_wd=decoupled_wd)
+    a = Op(dict(a.str_vals, type="SolverUpdateAcc", func_name=SOLVER_UPDATE_ACC_FUNC), dict(a.nda_vals, accum=_solver_vec(4)))
+    a.solver_geom()
+    return a
+
+
 # the training BatchNorm of the gradient pipe and the Eltwise-SUM gradient, in a table of their own (PIPE_OP_FUNCS is pinned): what bck_pipe.ConvPipeBck runs for a
 # BatchNorm + Scale (+ ReLU) run and its gradient, and for a BckEltwise.  This backend's own arithmetic: csrc/kernels/bn_f32.hip and DESIGN.md section 3.15 state it
 BN_OP_FUNCS: Dict[str, tuple] = {
@@ -618,9 +648,10 @@ def pipe_func_args(fop: Op) -> tuple:
     if fn == SGD_UPDATE_FUNC:
         per = tuple(x for i in range(fop.get_u32("tens_num")) for x in ((f"w_{i}", "INOUT"), (f"g_{i}", "IN"), (f"h_{i}", "INOUT")))
         return per + NATIVE_ARGS[fn]
-    if fn in (SOLVER_UPDATE_FUNC, GRAD_SUMSQ_FUNC) and fop.has("tens_num"):   # (an op without tens_num: the fixed args alone)
+    if fn in (SOLVER_UPDATE_FUNC, GRAD_SUMSQ_FUNC, GRAD_ACCUM_FUNC, SOLVER_UPDATE_ACC_FUNC) and fop.has("tens_num"):   # (an op without tens_num: the fixed args alone)
         adam = fop.str_vals.get("solver_type") == "adam"
-        one = lambda i: ((f"w_{i}", "INOUT"), (f"g_{i}", "IN"), (f"h_{i}", "INOUT")) + (((f"h2_{i}", "INOUT"),) if adam else ()) if fn == SOLVER_UPDATE_FUNC else ((f"g_{i}", "IN"),)
+        one = lambda i: ((f"w_{i}", "INOUT"), (f"g_{i}", "IN"), (f"h_{i}", "INOUT")) + (((f"h2_{i}", "INOUT"),) if adam else ()) if fn in (SOLVER_UPDATE_FUNC, SOLVER_UPDATE_ACC_FUNC) else \
+            ((f"g_{i}", "IN"), (f"a_{i}", "INOUT")) if fn == GRAD_ACCUM_FUNC else ((f"g_{i}", "IN"),)
         return tuple(x for i in range(fop.get_u32("tens_num")) for x in one(i)) + NATIVE_ARGS[fn]
     if fn == "hip_fan_out":
         return NATIVE_ARGS[fn] + tuple((an, "OUT") for an in fop.multi_names("outs"))
@@ -678,6 +709,9 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_solver_update": (("hyper", "IN"), ("state", "IN")),
     "hip_grad_sumsq": (("partials", "INOUT"),),
     "hip_grad_norm": (("partials", "IN"), ("hyper", "IN"), ("state", "OUT")),
+    # gradient accumulation (this backend's own).  In front of these (pipe_func_args): g_i (IN) a_i (INOUT) per tensor | hip_solver_update's w_i g_i h_i [h2_i]
+    "hip_grad_accum": (("accum", "IN"),),
+    "hip_solver_update_acc": (("hyper", "IN"), ("state", "IN"), ("accum", "IN")),
     # the training BatchNorm and the Eltwise-SUM gradient (this backend's own; eps / maf / slab / relu ride in the op).  hip_fan_out's list depends on the op: in,
     # then outs_0 .. outs_{n-1} (pipe_func_args)
     "hip_bn_stats": (("in", "IN"), ("mean", "OUT"), ("inv_std", "OUT"), ("run_mean", "INOUT"), ("run_var", "INOUT")),

@@ -264,11 +264,13 @@ void sgd_update(float *w, float const *g, float *h, long n, float lr_i, float wd
   }
 }
 // ---- the solver family (kernels/solver_update_f32.hip states the chains and the tree): the same operations in the same order, every one its own fp32 rounding
-struct solver_coef_c { float lr, wd, mom, mom2, delta, coef, c, o1, o2, s, lrwd; };
-void solver_update(int type, bool clip, bool dwd, float *w, float const *g, float *h, float *v, long n, solver_coef_c const k) {
+struct solver_coef_c { float lr, wd, mom, mom2, delta, coef, c, o1, o2, s, lrwd, scale; };
+// acc (hip_solver_update_acc): gs = scale * g0, one rounding, in g0's place
+void solver_update(int type, bool clip, bool dwd, bool acc, float *w, float const *g, float *h, float *v, long n, solver_coef_c const k) {
 #pragma omp parallel for schedule(static)
   for (long e = 0; e < n; ++e) {
-    float const g0 = clip ? k.coef * g[e] : g[e];
+    float const gc = clip ? k.coef * g[e] : g[e];
+    float const g0 = acc ? k.scale * gc : gc;
     if (type == kSolverAdam) {
       float g1 = g0;
       if (!dwd) { float const reg = k.wd * w[e]; g1 = g0 + reg; }
@@ -296,6 +298,12 @@ void solver_update(int type, bool clip, bool dwd, float *w, float const *g, floa
       else w[e] = w[e] - hn;
     }
   }
+}
+// hip_grad_accum: first: a' = g, a not read; else a' = a + g, one fp32 add
+void grad_accum(bool first, float const *g, float *a, long n) {
+  if (first) { memcpy(a, g, sizeof(float) * (size_t)n); return; }
+#pragma omp parallel for schedule(static)
+  for (long e = 0; e < n; ++e) a[e] = a[e] + g[e];
 }
 // the tree over 256 lane sums: for h = 128 .. 1: a[t] = a[t] + a[t + h], t < h
 inline float solver_tree(float *a) { for (int h = 128; h > 0; h >>= 1) for (int t = 0; t < h; ++t) a[t] = a[t] + a[t + h]; return a[0]; }
@@ -812,20 +820,28 @@ struct cpu_compute_t : public rtc_compute_t {
       return (float *)must_find(vis, vn).buf.get();
     };
     size_t const n = so.elems.size();
-    if (so.kind == 1) {
+    if (so.update()) {
       std::vector<float *> w(n), h(n), v(n, nullptr); std::vector<float const *> g(n);
       for (size_t i = 0; i < n; ++i) {
         string const sx = "_" + std::to_string(i);
         w[i] = var_ptr("w" + sx); g[i] = var_ptr("g" + sx); h[i] = var_ptr("h" + sx); if (so.type == kSolverAdam) v[i] = var_ptr("h2" + sx);
       }
       float const *hy = var_ptr("hyper"); float const *st = var_ptr("state");
+      float const *ac = so.kind == 5 ? var_ptr("accum") : nullptr;
+      if (ac && ac[1] == 0.0f) return;   // (not the applying micro-step: nothing is written)
       for (size_t i = 0; i < n; ++i) {
         solver_coef_c k;
         k.lr = hy[0] * so.lr_mult[i]; k.wd = hy[2] * so.decay_mult[i]; k.mom = hy[1]; k.mom2 = hy[3]; k.delta = hy[4];
         k.coef = so.clip ? st[0] : 1.0f;
         k.c = 1.0f + k.mom; k.o1 = 1.0f - k.mom; k.o2 = 1.0f - k.mom2; k.s = k.lr * hy[5]; k.lrwd = k.lr * k.wd;
-        solver_update(so.type, so.clip, so.decoupled_wd, w[i], g[i], h[i], v[i], so.elems[i], k);
+        k.scale = ac ? ac[2] : 1.0f;
+        solver_update(so.type, so.clip, so.decoupled_wd, ac != nullptr, w[i], g[i], h[i], v[i], so.elems[i], k);
       }
+    } else if (so.kind == 4) {
+      std::vector<float const *> g(n); std::vector<float *> a(n);
+      for (size_t i = 0; i < n; ++i) { string const sx = "_" + std::to_string(i); g[i] = var_ptr("g" + sx); a[i] = var_ptr("a" + sx); }
+      float const *ac = var_ptr("accum");
+      for (size_t i = 0; i < n; ++i) grad_accum(ac[0] != 0.0f, g[i], a[i], so.elems[i]);
     } else if (so.kind == 2) {
       std::vector<float const *> g(n);
       for (size_t i = 0; i < n; ++i) g[i] = var_ptr("g_" + std::to_string(i));

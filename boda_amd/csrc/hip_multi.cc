@@ -390,7 +390,8 @@ struct hip_multi_compute_t : public rtc_compute_t {
     // hip_sgd_update: params, gradients and momentum history are REPLICATED vars, and an unflagged native call on replicated vars runs on every device (below).  The
     // replicas stay equal by construction: every device holds the same summed gradient after run_on_img_shards' fan-out, the same hyper, the same history, and runs the
     // same kernel -- no cross-device work of its own.  A sharded var (a leading img / M dim) would give every device another piece: refused.  The solver family
-    // (hip_solver_update, hip_grad_sumsq, hip_grad_norm; mode replicated_vars) has the same policy: equal gradients give equal partials, norm, coef and updates
+    // (hip_solver_update, hip_grad_sumsq, hip_grad_norm; mode replicated_vars) has the same policy: equal gradients give equal partials, norm, coef and updates -- and,
+    // with hip_grad_accum and hip_solver_update_acc, equal accumulators: solver_accum is uploaded to every replica
     native_func_t const *row = fit->second ? must_find(func_row, rfc.rtc_func_name) : nullptr;
     if (row && (row->multi_dev.mode == multi_dev_t::replicated_only || row->multi_dev.mode == multi_dev_t::replicated_vars))
       for (auto const &kv : rfc.arg_map) if (kv.second.is_valid() && kv.second.is_var() && must_find(vis, kv.second.n).shard_dim >= 0)

@@ -209,6 +209,28 @@ struct grad_norm_args_t {
   unsigned n_parts, pad;
 };
 static_assert(sizeof(grad_norm_args_t) == 32 && __builtin_offsetof(grad_norm_args_t, state) == 16 && __builtin_offsetof(grad_norm_args_t, n_parts) == 24, "grad_norm_args_t layout");
+// gradient accumulation (OP 4 and the -DACCUM=1 form of OP 1): accum = [first, apply, scale, micro] in device memory
+struct accum_tensor_t {
+  float const *g; float *a;              // the micro-step's gradient (read), the accumulator (written; read unless accum[0] != 0)
+  unsigned n, blk0;                      // elements; index of the tensor's first workgroup
+  unsigned quads, pad;                   // 1: g and a are 16-byte aligned
+};
+struct grad_accum_args_t {
+  float const *accum;
+  unsigned tens_num, pad;
+  accum_tensor_t t[kSgdMaxTens];
+};
+static_assert(sizeof(accum_tensor_t) == 32 && sizeof(grad_accum_args_t) == 16 + 32 * kSgdMaxTens && __builtin_offsetof(accum_tensor_t, a) == 8 && __builtin_offsetof(accum_tensor_t, n) == 16 &&
+              __builtin_offsetof(accum_tensor_t, quads) == 24 && __builtin_offsetof(grad_accum_args_t, tens_num) == 8 && __builtin_offsetof(grad_accum_args_t, t) == 16, "accum_tensor_t / grad_accum_args_t layout");
+struct solver_update_acc_args_t {
+  float const *hyper;                    // as solver_update_args_t's
+  float const *state;
+  float const *accum;                    // accum[1] == 0: the launch writes nothing; accum[2]: the factor on the (clipped) summed gradient
+  unsigned tens_num, pad;
+  solver_tensor_t t[kSgdMaxTens];        // g: the accumulator
+};
+static_assert(sizeof(solver_update_acc_args_t) == 32 + 56 * kSgdMaxTens && __builtin_offsetof(solver_update_acc_args_t, state) == 8 && __builtin_offsetof(solver_update_acc_args_t, accum) == 16 &&
+              __builtin_offsetof(solver_update_acc_args_t, tens_num) == 24 && __builtin_offsetof(solver_update_acc_args_t, t) == 32, "solver_update_acc_args_t layout");
 
 // kernels/bn_f32.hip: the training BatchNorm functions and hip_fan_out
 struct bn_args_t {

@@ -1,4 +1,4 @@
-// solver_update_f32.hip -- the solvers of the gradient pipe beyond plain SGD (family `solver`), fp32, for gfx950; specialised by hiprtc.  Three functions:
+// solver_update_f32.hip -- the solvers of the gradient pipe beyond plain SGD (family `solver`), fp32, for gfx950; specialised by hiprtc.  Three functions, and the two of gradient accumulation (OP 4 and OP 1 with ACCUM=1, below):
 //     OP 1  hip_solver_update (op type SolverUpdate): SGD, Nesterov or Adam over up to 32 tensors in one launch, optionally with the gradient scaled by the clip coefficient
 //     OP 2  hip_grad_sumsq    (op type GradSumsq):    one partial sum of squares per chunk of 4096 gradient elements
 //     OP 3  hip_grad_norm     (op type GradNorm):     the partials summed, the global norm and the clip coefficient
@@ -35,8 +35,20 @@
 //     an infinite norm (an Inf gradient, or a sum of squares that overflows) ->  coef = clip / inf = +0
 //     norm == clip  ->  coef = 1;   all-zero gradients  ->  norm = 0, coef = 1 (for clip >= 0)
 //
-// -D parameters: KNAME, OP; OP 1: SOLVER (0 | 1 | 2), CLIP (0 | 1), DWD (0 | 1, adam only).  Host side: plan_solver (native_plan.cc), native_kernels_t::solver_update /
-// grad_sumsq / grad_norm (native_kernels.cc), the argument checks in native_run.cc.
+// Gradient accumulation over iter_size micro-steps.  accum = [first, apply, scale, micro] lives in device memory and is read with ordinary loads,
+// like hyper and state: one captured launch serves every micro-step.
+//
+// OP 4  hip_grad_accum (op type GradAccum).  Per element of every tensor, g the micro-step's gradient and a the accumulator:
+//     accum[0] != 0:  a' = g  (the bits of g; a is NOT read, so the accumulators never need clearing)        else:  a' = a + g  (one fp32 add, denormals kept)
+//   g is only read; nothing outside the a_i is written.  Quads where g and a are both 16-byte aligned, as OP 1: all of a thread's loads before its first store.
+//
+// OP 1 with ACCUM=1  hip_solver_update_acc (op type SolverUpdateAcc): OP 1 with g the accumulator, and
+//     accum[1] == 0:  every workgroup returns before its first store: the launch writes nothing
+//     otherwise:      g0 = CLIP ? coef * g : g;   gs = accum[2] * g0 (one rounding);   the chain of the SOLVER above with gs where it has g0
+//   Caffe's order: clip on the SUMMED gradient, then normalise by 1 / iter_size, then regularise.  With accum[2] == 1 the bits are hip_solver_update's.
+//
+// -D parameters: KNAME, OP; OP 1: SOLVER (0 | 1 | 2), CLIP (0 | 1), DWD (0 | 1, adam only), ACCUM (0 | 1).  Host side: plan_solver (native_plan.cc),
+// native_kernels_t::solver_update / grad_sumsq / grad_norm / grad_accum (native_kernels.cc), the argument checks in native_run.cc.
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -44,7 +56,7 @@
 
 #pragma clang fp contract(off) reassociate(off)
 
-#include "kernel_args.h"      // solver_tensor_t, solver_update_args_t, sumsq_tensor_t, grad_sumsq_args_t, grad_norm_args_t, kSgdMaxTens
+#include "kernel_args.h"      // solver_tensor_t, solver_update_args_t, sumsq_tensor_t, grad_sumsq_args_t, grad_norm_args_t, accum_tensor_t, grad_accum_args_t, solver_update_acc_args_t, kSgdMaxTens
 #define SOLVER_CHUNK 4096
 
 #ifndef SOLVER
@@ -55,6 +67,9 @@
 #endif
 #ifndef DWD
 #define DWD 0
+#endif
+#ifndef ACCUM
+#define ACCUM 0
 #endif
 
 #if OP == 2 || OP == 3
@@ -72,14 +87,19 @@ static __device__ __forceinline__ float solver_tree(float *a, float mine, unsign
 #endif
 
 #if OP == 1
-struct solver_coef_t { float lr, wd, mom, mom2, delta, coef, c, o1, o2, s, lrwd; };
+struct solver_coef_t { float lr, wd, mom, mom2, delta, coef, c, o1, o2, s, lrwd, scale; };
 
 // one element: -> w', h' (and v' for adam)
 static __device__ __forceinline__ void solver_one(float w, float g, float h, float v, solver_coef_t const k, float &w2, float &h2, float &v2) {
 #if CLIP
-  float const g0 = k.coef * g;
+  float const gc = k.coef * g;
 #else
-  float const g0 = g;
+  float const gc = g;
+#endif
+#if ACCUM
+  float const g0 = k.scale * gc;
+#else
+  float const g0 = gc;
 #endif
 #if SOLVER == 2
 #if DWD
@@ -121,7 +141,12 @@ static __device__ __forceinline__ void solver_one(float w, float g, float h, flo
 #endif
 }
 
+#if ACCUM
+extern "C" __global__ __launch_bounds__(256) void KNAME(solver_update_acc_args_t const p) {
+  if (p.accum[1] == 0.0f) return;   // (not the applying micro-step: nothing is written)
+#else
 extern "C" __global__ __launch_bounds__(256) void KNAME(solver_update_args_t const p) {
+#endif
   unsigned const b = blockIdx.x;
   int ti = 0;
 #pragma unroll
@@ -135,6 +160,11 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(solver_update_args_t con
   k.lr = p.hyper[0] * t.lr_mult; k.wd = p.hyper[2] * t.decay_mult; k.mom = p.hyper[1]; k.mom2 = p.hyper[3]; k.delta = p.hyper[4];
   k.coef = CLIP ? p.state[0] : 1.0f;
   k.c = 1.0f + k.mom; k.o1 = 1.0f - k.mom; k.o2 = 1.0f - k.mom2; k.s = k.lr * p.hyper[5]; k.lrwd = k.lr * k.wd;
+#if ACCUM
+  k.scale = p.accum[2];
+#else
+  k.scale = 1.0f;
+#endif
   float *const w = t.w + base; float const *const g = t.g + base; float *const h = t.h + base;
 #if SOLVER == 2
   float *const v = t.h2 + base;
@@ -235,5 +265,50 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(grad_norm_args_t const p
   float const clip = p.hyper[6];
   float const coef = (norm > clip) ? clip / norm : 1.0f;
   if (tid < 4) p.state[tid] = (tid == 0) ? coef : (tid == 1) ? norm : (tid == 2) ? sumsq : 0.0f;
+}
+#endif
+
+#if OP == 4
+extern "C" __global__ __launch_bounds__(256) void KNAME(grad_accum_args_t const p) {
+  unsigned const b = blockIdx.x;
+  int ti = 0;
+#pragma unroll
+  for (int i = 1; i < kSgdMaxTens; ++i) if (i < (int)p.tens_num && b >= p.t[i].blk0) ti = i;
+  ti = __builtin_amdgcn_readfirstlane(ti);
+  accum_tensor_t const t = p.t[ti];
+  unsigned const base = (b - t.blk0) * SOLVER_CHUNK;
+  if (base >= t.n) return;   // (never: the grid is the sum of the chunks)
+  unsigned const cnt = (t.n - base < SOLVER_CHUNK) ? (t.n - base) : SOLVER_CHUNK;
+  bool const first = p.accum[0] != 0.0f;   // (the same word for every lane of the launch)
+  float const *const g = t.g + base; float *const a = t.a + base;
+  unsigned const tid = threadIdx.x;
+  unsigned done = 0;   // elements of the chunk covered by quads
+  if (t.quads) {
+    unsigned const nq = cnt / 4;
+    float4 G[4], A[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      unsigned const q = tid + 256u * j;
+      if (q < nq) {
+        G[j] = ((float4 const *)g)[q];
+        if (!first) A[j] = ((float4 const *)a)[q];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      unsigned const q = tid + 256u * j;
+      if (q < nq) {
+        float4 r = G[j];
+        if (!first) { r.x = A[j].x + G[j].x; r.y = A[j].y + G[j].y; r.z = A[j].z + G[j].z; r.w = A[j].w + G[j].w; }
+        ((float4 *)a)[q] = r;
+      }
+    }
+    done = nq * 4;
+  }
+  for (unsigned e = done + tid; e < cnt; e += 256) {
+    float r = g[e];
+    if (!first) r = a[e] + r;
+    a[e] = r;
+  }
 }
 #endif

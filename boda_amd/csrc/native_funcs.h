@@ -11,7 +11,7 @@ namespace bodahip {
 
 // the family (func_family_t of rtc_types.h) selects the handler (native_run.cc, native_kernels.cc: check_compile_time); handlers switch on the member, never on the name
 inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver"};
-// members.  kFamSolver: 1 update | 2 sumsq | 3 norm (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc: the kind of bn_op_t
+// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc: the kind of bn_op_t
 enum { kConvF32 = 0, kConvAlias = 1, kConvBf16 = 2, kConvWinograd = 3 };            // (the alias: hip_conv's contract without its fused pooling and filts_km)
 enum { kBconvIn = 1, kBconvBiases = 2, kBconvFilts = 3, kBconvFiltsBiases = 4 };   // (4 is opt-in: never one of the bare op's three calls)
 enum { kOpPoolYx = 1, kOpSpreading = 2, kOpLrnSb = 3, kOpBckLrn = 4, kOpZeroIfNonPos = 5, kOpSoftmax = 6, kOpSmGradAndLoss = 7, kOpSumLossOverImgs = 8, kOpReduce = 9,
@@ -22,9 +22,9 @@ inline constexpr char const *kArgKindNames[] = {"IN", "OUT", "INOUT", "REF", "VA
 struct func_arg_t { char const *name; arg_kind_t kind; };
 // the part of the arg list that depends on the op, as a rule: ins_0 .. ins_{ins_num-1} (IN, 2 to 8) in front of the last fixed arg | outs_0 .. outs_{outs_num-1} (OUT, 2 to 8)
 // behind the fixed args | w_i (INOUT) g_i (IN) h_i (INOUT), i < tens_num (1 to 32), in front of the fixed args | member lists, which their handlers describe |
-// w_i g_i h_i and, for solver_type=adam, h2_i (INOUT) in front | g_i (IN) in front.  The last two answer the fixed args alone for an op WITHOUT tens_num (the arg-list
-// query of a bare op; compiling such an op stays an error)
-enum var_args_t { kVarNone, kVarInsBeforeLast, kVarOutsBehind, kVarWghInFront, kVarMembers, kVarWghH2InFront, kVarGInFront };
+// w_i g_i h_i and, for solver_type=adam, h2_i (INOUT) in front | g_i (IN) in front | g_i (IN) a_i (INOUT) in front.  The last three answer the fixed args alone for an op
+// WITHOUT tens_num (the arg-list query of a bare op; compiling such an op stays an error)
+enum var_args_t { kVarNone, kVarInsBeforeLast, kVarOutsBehind, kVarWghInFront, kVarMembers, kVarWghH2InFront, kVarGInFront, kVarGaInFront };
 // a flag that adds a var arg (IN): which flag, the arg, and where -- at >= 0: in front of fixed arg `at`; at < 0: in front of the last fixed arg.  flag 0: none
 struct flag_arg_t { unsigned flag; char const *name; int at; };
 enum : unsigned { kBeHip = 1, kBeCpu = 2 };
@@ -112,6 +112,9 @@ inline constexpr native_func_t kNativeFuncs[] = {
   {"hip_solver_update", kFamSolver, 1, nullptr, {"SolverUpdate"}, {{"hyper", kIn}, {"state", kIn}}, {}, kVarWghH2InFront, 0, {}, kBeHip | kBeCpu, kReplicatedVars},
   {"hip_grad_sumsq", kFamSolver, 2, nullptr, {"GradSumsq"}, {{"partials", kInOut}}, {}, kVarGInFront, 0, {}, kBeHip | kBeCpu, kReplicatedVars},
   {"hip_grad_norm", kFamSolver, 3, nullptr, {"GradNorm"}, {{"partials", kIn}, {"hyper", kIn}, {"state", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kReplicatedVars},
+  // gradient accumulation over iter_size micro-steps (the same file): accum = [first, apply, scale, micro] says whether a_i is overwritten or added to, and whether the update applies
+  {"hip_grad_accum", kFamSolver, 4, nullptr, {"GradAccum"}, {{"accum", kIn}}, {}, kVarGaInFront, 0, {}, kBeHip | kBeCpu, kReplicatedVars},
+  {"hip_solver_update_acc", kFamSolver, 5, nullptr, {"SolverUpdateAcc"}, {{"hyper", kIn}, {"state", kIn}, {"accum", kIn}}, {}, kVarWghH2InFront, 0, {}, kBeHip | kBeCpu, kReplicatedVars},
   // the training BatchNorm and the Eltwise-SUM gradient (this backend's own; kernels/bn_f32.hip).  hip_bn_fwd and hip_fan_out are independent per image, but their calls
   // demand vars of exactly the op's dims, which an img shard does not have: refused with a message of their own, not left to fail on dims
   {"hip_bn_stats", kFamBn, 1, nullptr, {"BnStats"}, {{"in", kIn}, {"mean", kOut}, {"inv_std", kOut}, {"run_mean", kInOut}, {"run_var", kInOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, refused_on_devices(kWhyBnSums)},
@@ -188,14 +191,14 @@ inline vect_func_arg_t native_func_args(native_func_t const &f, op_base_t const 
     for (uint32_t i = 0; i < n; ++i) { string const sx = "_" + std::to_string(i); per.emplace_back("w" + sx, kInOut); per.emplace_back("g" + sx, kIn); per.emplace_back("h" + sx, kInOut); }
     r.insert(r.begin(), per.begin(), per.end());
   }
-  if ((f.var == kVarWghH2InFront || f.var == kVarGInFront) && op.has("tens_num")) {
+  if ((f.var == kVarWghH2InFront || f.var == kVarGInFront || f.var == kVarGaInFront) && op.has("tens_num")) {
     uint32_t const n = count("tens_num", 1, kSgdUpdateMaxTens, "tensors"); vect_func_arg_t per;
     auto const st = op.str_vals.find("solver_type");
     bool const adam = f.var == kVarWghH2InFront && st != op.str_vals.end() && st->second == "adam";
     for (uint32_t i = 0; i < n; ++i) {
       string const sx = "_" + std::to_string(i);
       if (f.var == kVarWghH2InFront) { per.emplace_back("w" + sx, kInOut); per.emplace_back("g" + sx, kIn); per.emplace_back("h" + sx, kInOut); if (adam) per.emplace_back("h2" + sx, kInOut); }
-      else per.emplace_back("g" + sx, kIn);
+      else { per.emplace_back("g" + sx, kIn); if (f.var == kVarGaInFront) per.emplace_back("a" + sx, kInOut); }
     }
     r.insert(r.begin(), per.begin(), per.end());
   }

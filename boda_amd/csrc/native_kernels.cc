@@ -886,12 +886,13 @@ void native_kernels_t::sgd_update(int n, sgd_member_t const *m, float const *hyp
   last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
 }
 // ---- the solver family (kernels/solver_update_f32.hip): one launch per call, the tables by value in the kernel arguments
-void native_kernels_t::solver_update(solver_op_t const &so, solver_member_t const *m, float const *hyper, float const *state) {
+void native_kernels_t::solver_update(solver_op_t const &so, solver_member_t const *m, float const *hyper, float const *state, float const *accum) {
   sgd_plan_t const sp = plan_solver(so);
   kernel_t &k = get_kernel(impl, host, sp.p);
   int const n = (int)so.elems.size();
-  solver_update_args_t a; memset(&a, 0, sizeof(a));
-  a.hyper = hyper; a.state = state; a.tens_num = (unsigned)n;
+  if ((so.kind == 5) != (accum != nullptr)) rt_err("solver_update: accum goes with hip_solver_update_acc, and only with it");
+  solver_update_acc_args_t a; memset(&a, 0, sizeof(a));   // (hip_solver_update's solver_update_args_t is this one without accum: filled below from the same table)
+  a.hyper = hyper; a.state = state; a.accum = accum; a.tens_num = (unsigned)n;
   for (int i = 0; i < n; ++i) {
     solver_tensor_t &t = a.t[i];
     t.w = m[i].w; t.g = m[i].g; t.h = m[i].h; t.h2 = so.type == kSolverAdam ? m[i].h2 : nullptr;
@@ -899,7 +900,9 @@ void native_kernels_t::solver_update(solver_op_t const &so, solver_member_t cons
     t.quads = ((((uintptr_t)t.w | (uintptr_t)t.g | (uintptr_t)t.h | (uintptr_t)t.h2) & 15) == 0) ? 1u : 0u;   // float4 where all of them are 16-byte aligned (a chunk starts on a quad)
   }
   for (int i = n; i < kSgdMaxTens; ++i) a.t[i].blk0 = 0xffffffffu;   // (never reached: the kernel's scan stops at tens_num)
-  void *params[] = {&a};
+  solver_update_args_t a1; memset(&a1, 0, sizeof(a1));
+  a1.hyper = hyper; a1.state = state; a1.tens_num = (unsigned)n; memcpy(a1.t, a.t, sizeof(a1.t));
+  void *params[] = {so.kind == 5 ? (void *)&a : (void *)&a1};
   if (sp.grid) hip_err_chk(host->nh_launch(k.func, sp.grid, 1, sp.block, params), "hipModuleLaunchKernel(solver_update)");
   last_launch.kernel = sp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = sp.grid; last_launch.block = sp.block;
   last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
@@ -915,6 +918,23 @@ void native_kernels_t::grad_sumsq(solver_op_t const &so, float const *const *g, 
   for (int i = n; i < kSgdMaxTens; ++i) a.t[i].blk0 = 0xffffffffu;
   void *params[] = {&a};
   if (sp.grid) hip_err_chk(host->nh_launch(k.func, sp.grid, 1, sp.block, params), "hipModuleLaunchKernel(grad_sumsq)");
+  last_launch.kernel = sp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = sp.grid; last_launch.block = sp.block;
+  last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
+}
+void native_kernels_t::grad_accum(solver_op_t const &so, float const *const *g, float *const *acc, float const *accum) {
+  sgd_plan_t const sp = plan_solver(so);
+  kernel_t &k = get_kernel(impl, host, sp.p);
+  int const n = (int)so.elems.size();
+  grad_accum_args_t a; memset(&a, 0, sizeof(a));
+  a.accum = accum; a.tens_num = (unsigned)n;
+  for (int i = 0; i < n; ++i) {
+    accum_tensor_t &t = a.t[i];
+    t.g = g[i]; t.a = acc[i]; t.n = (unsigned)so.elems[(size_t)i]; t.blk0 = sp.blk0[(size_t)i];
+    t.quads = ((((uintptr_t)t.g | (uintptr_t)t.a) & 15) == 0) ? 1u : 0u;   // float4 where both are 16-byte aligned (a chunk starts on a quad)
+  }
+  for (int i = n; i < kSgdMaxTens; ++i) a.t[i].blk0 = 0xffffffffu;   // (never reached: the kernel's scan stops at tens_num)
+  void *params[] = {&a};
+  if (sp.grid) hip_err_chk(host->nh_launch(k.func, sp.grid, 1, sp.block, params), "hipModuleLaunchKernel(grad_accum)");
   last_launch.kernel = sp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = sp.grid; last_launch.block = sp.block;
   last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
 }

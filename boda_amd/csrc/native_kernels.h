@@ -29,6 +29,8 @@
 //     hip_solver_update / hip_grad_sumsq / hip_grad_norm    this backend's own: SGD, Nesterov and Adam over up to 32 tensors per launch (str_val solver_type; hyper float v=8),
 //                                       and global-norm clipping as a sum of squares per chunk, one finishing launch and the coefficient in `state` (float v=4), which the
 //                                       update reads with clip=1.  kernels/solver_update_f32.hip states the chains and the tree; code objects built when the function is compiled
+//     hip_grad_accum / hip_solver_update_acc    this backend's own: gradient accumulation over iter_size micro-steps.  accum (float v=4 = first, apply, scale, micro) is read
+//                                       from device memory: a_i = first ? g_i : a_i + g_i; the update applies only where apply != 0, on scale * the (clipped) summed gradient
 //     hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out    this backend's own: the training BatchNorm of the gradient pipe (batch statistics, running
 //                                       pair, normalise + scale + bias + ReLU, the two gradients) and the gradient of an Eltwise SUM.  kernels/bn_f32.hip states the arithmetic and
 //                                       the order of the per-channel sums
@@ -150,9 +152,11 @@ struct native_kernels_t {
   // the solver family on raw device pointers (so says which kernel: solver_op_of_op).  solver_update: so.elems.size() tensors, h2 non-null for adam; hyper float[8], state
   // float[4].  grad_sumsq: chunk k of the call writes partials[so.part0 + k].  grad_norm: so.parts partials -> state
   struct solver_member_t { float *w; float const *g; float *h; float *h2; };
-  void solver_update(solver_op_t const &so, solver_member_t const *m, float const *hyper, float const *state);
+  void solver_update(solver_op_t const &so, solver_member_t const *m, float const *hyper, float const *state, float const *accum = nullptr);
   void grad_sumsq(solver_op_t const &so, float const *const *g, float *partials);
   void grad_norm(solver_op_t const &so, float const *partials, float const *hyper, float *state);
+  // gradient accumulation: grad_accum: a_i = accum[0] != 0 ? g_i : a_i + g_i; solver_update with so.kind == 5 takes accum (float[4]) as well
+  void grad_accum(solver_op_t const &so, float const *const *g, float *const *a, float const *accum);
   void shard_sum(float const *slabs, float *out, int nslabs, long stride, long n);
   // hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out on raw device pointers (kernels/bn_f32.hip): tens / chans in bn_op_t's arg order
   void bn_call(bn_op_t const &b, float *const *tens, float *const *chans);

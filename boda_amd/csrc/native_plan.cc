@@ -1425,17 +1425,19 @@ sgd_plan_t plan_sgd_update(std::vector<long> const &elems) {
 }
 
 // ---- the solver family (kernels/solver_update_f32.hip).  hip_solver_update / hip_grad_sumsq: hip_sgd_update's chunking.  Bytes per element: sgd and nesterov 20 (w, g, h
-// read, h and w written), adam 28 (h2 read and written too), the sum of squares 4; hip_grad_norm reads the partials and writes four words
+// read, h and w written), adam 28 (h2 read and written too), the sum of squares 4; hip_grad_norm reads the partials and writes four words.  hip_grad_accum: 12 (g and a
+// read, a written; the first micro-step moves 8).  hip_solver_update_acc: the update's kernel with -DACCUM=1, the update's bytes (a launch that does not apply moves none)
 sgd_plan_t plan_solver(solver_op_t const &so) {
-  static char const *const fns[] = {"", "hip_solver_update", "hip_grad_sumsq", "hip_grad_norm"};
+  static char const *const fns[] = {"", "hip_solver_update", "hip_grad_sumsq", "hip_grad_norm", "hip_grad_accum", "hip_solver_update_acc"};
   string const what = fns[so.kind];
   sgd_plan_t r; r.p.src = kSrc_solver_update_f32;
-  r.p.defs = {"-DOP=" + std::to_string(so.kind)};
+  r.p.defs = {"-DOP=" + std::to_string(so.update() ? 1 : so.kind)};
   if (so.kind == 3) { r.p.kname = "bodahip_grad_norm"; r.grid = 1; r.algo_bytes = 4.0 * (double)so.parts + 16.0; return r; }
-  if (so.kind == 1) {
+  if (so.update()) {
     r.p.kname = string("bodahip_solver_update_") + kSolverTypeNames[so.type];
     r.p.defs.push_back("-DSOLVER=" + std::to_string(so.type)); r.p.defs.push_back(string("-DCLIP=") + (so.clip ? "1" : "0")); r.p.defs.push_back(string("-DDWD=") + (so.decoupled_wd ? "1" : "0"));
-  } else r.p.kname = "bodahip_grad_sumsq";
+    if (so.kind == 5) r.p.defs.push_back("-DACCUM=1");   // (hip_solver_update's own option string stays as it was)
+  } else r.p.kname = so.kind == 4 ? "bodahip_grad_accum" : "bodahip_grad_sumsq";
   if (so.elems.empty() || (int)so.elems.size() > kSgdMaxTens) rt_err(what + ": tens_num=" + std::to_string(so.elems.size()) + ": 1 to " + std::to_string(kSgdMaxTens) + " tensors");
   uint64_t blocks = 0; double tot = 0;
   for (long n : so.elems) {
@@ -1446,15 +1448,15 @@ sgd_plan_t plan_solver(solver_op_t const &so) {
   }
   if (blocks >= (1ull << 31)) unsup_err(what + ": too many workgroups");
   r.grid = (uint32_t)blocks;
-  r.algo_bytes = so.kind == 2 ? 4.0 * tot + 4.0 * (double)blocks : (so.type == kSolverAdam ? 28.0 : 20.0) * tot;
+  r.algo_bytes = so.kind == 2 ? 4.0 * tot + 4.0 * (double)blocks : so.kind == 4 ? 12.0 * tot : (so.type == kSolverAdam ? 28.0 : 20.0) * tot;
   return r;
 }
 string solver_plan_desc(solver_op_t const &so, sgd_plan_t const &sp) {
   string d = sp.p.kname + " grid=" + std::to_string(sp.grid) + " block=" + std::to_string(sp.block);
   if (so.kind == 3) return d + " parts=" + std::to_string(so.parts);
   d += " tens=" + std::to_string(sp.blk0.size()) + " chunk=" + std::to_string(kSgdChunk);
-  if (so.kind == 1) d += string(" clip=") + (so.clip ? "1" : "0") + (so.type == kSolverAdam ? string(" decoupled_wd=") + (so.decoupled_wd ? "1" : "0") : string());
-  else d += " part0=" + std::to_string(so.part0);
+  if (so.update()) d += string(" clip=") + (so.clip ? "1" : "0") + (so.type == kSolverAdam ? string(" decoupled_wd=") + (so.decoupled_wd ? "1" : "0") : string()) + (so.kind == 5 ? " accum=1" : "");
+  else if (so.kind == 2) d += " part0=" + std::to_string(so.part0);
   return d;
 }
 

@@ -262,7 +262,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     if (plan_out) *plan_out = sp.p.kname + " grid=" + std::to_string(sp.grid) + " block=" + std::to_string(sp.block) + " tens=" + std::to_string(sp.blk0.size()) + " chunk=" + std::to_string(kSgdChunk);
     return arch.empty() ? 0 : compile_plan(sp.p, arch, &log).size();
   } else if (fam == kFamSolver) {   // (kernels/solver_update_f32.hip: one kernel per function; the update specialised by solver_type, clip and decoupled_wd, never by shape)
-    if (!f) rt_err("prebuild: a bare " + t + " op: the solver's ops are function ops (cnn_op.solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op)");
+    if (!f) rt_err("prebuild: a bare " + t + " op: the solver's ops are function ops (cnn_op.solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op, grad_accum_func_op, solver_update_acc_func_op)");
     solver_op_t const so = solver_op_of_op(op);
     sgd_plan_t const sp = plan_solver(so);
     if (plan_out) *plan_out = solver_plan_desc(so, sp);
@@ -712,14 +712,18 @@ struct native_kernels_t::call_t {
       if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
       return (float *)host->nh_var_ptr(vn);
     };
-    if (so.kind == 1) {
+    if (so.update()) {
       std::vector<solver_member_t> ms(n);
       for (size_t i = 0; i < n; ++i) {
         string const sx = "_" + std::to_string(i);
         ms[i].w = var_ptr("w" + sx); ms[i].g = var_ptr("g" + sx); ms[i].h = var_ptr("h" + sx); ms[i].h2 = so.type == kSolverAdam ? var_ptr("h2" + sx) : nullptr;
       }
       float const *hyper = var_ptr("hyper"); float const *state = var_ptr("state");
-      nk.solver_update(so, ms.data(), hyper, state);
+      nk.solver_update(so, ms.data(), hyper, state, so.kind == 5 ? var_ptr("accum") : nullptr);
+    } else if (so.kind == 4) {
+      std::vector<float const *> gs(n); std::vector<float *> as(n);
+      for (size_t i = 0; i < n; ++i) { string const sx = "_" + std::to_string(i); gs[i] = var_ptr("g" + sx); as[i] = var_ptr("a" + sx); }
+      nk.grad_accum(so, gs.data(), as.data(), var_ptr("accum"));
     } else if (so.kind == 2) {
       std::vector<float const *> gs(n);
       for (size_t i = 0; i < n; ++i) gs[i] = var_ptr("g_" + std::to_string(i));

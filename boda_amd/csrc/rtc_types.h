@@ -223,14 +223,17 @@ inline sgd_op_t sgd_op_of_op(op_base_t const &op) {
 }
 
 // ---- the solver family (this backend's own; kernels/solver_update_f32.hip states the chains): hip_solver_update (op type SolverUpdate, member 1), hip_grad_sumsq (GradSumsq,
-// member 2), hip_grad_norm (GradNorm, member 3).  What both backends read from the function's op, and every refusal that needs the op alone
+// member 2), hip_grad_norm (GradNorm, member 3), and the two of gradient accumulation: hip_grad_accum (GradAccum, member 4: g_i read, a_i rewritten, accum float v=4 =
+// [first, apply, scale, micro]) and hip_solver_update_acc (SolverUpdateAcc, member 5: the update's op plus accum).  What both backends read from the function's op, and
+// every refusal that needs the op alone
 constexpr long kSolverChunk = 4096;   // floats of one tensor a workgroup owns; one partial sum of squares per chunk
 enum { kSolverSgd = 0, kSolverNesterov = 1, kSolverAdam = 2 };
 inline constexpr char const *kSolverTypeNames[] = {"sgd", "nesterov", "adam"};
 struct solver_op_t {
-  int kind = 0;                          // the member: 1 update, 2 sumsq, 3 norm
-  int type = kSolverSgd; bool clip = false, decoupled_wd = false;   // kind 1
-  std::vector<long> elems; std::vector<float> lr_mult, decay_mult;  // kinds 1, 2: per tensor (the multipliers: kind 1)
+  int kind = 0;                          // the member: 1 update, 2 sumsq, 3 norm, 4 accum, 5 update_acc
+  int type = kSolverSgd; bool clip = false, decoupled_wd = false;   // kinds 1, 5
+  bool update() const { return kind == 1 || kind == 5; }
+  std::vector<long> elems; std::vector<float> lr_mult, decay_mult;  // kinds 1, 2, 4, 5: per tensor (the multipliers: kinds 1, 5)
   uint32_t part0 = 0; long parts = 0;    // kind 2: the first partial this call writes; kinds 2, 3: the size of the partials var
   long chunks() const { long c = 0; for (long n : elems) c += (n + kSolverChunk - 1) / kSolverChunk; return c; }
 };
@@ -254,7 +257,7 @@ inline solver_op_t solver_op_of_op(op_base_t const &op) {
     if (4.0 * (double)r.parts >= 2147483648.0) unsup_err(fn + ": partials of 2 GiB or more");
     return r;
   }
-  if (r.kind == 1) {
+  if (r.update()) {
     auto st = op.str_vals.find("solver_type");
     if (st == op.str_vals.end()) rt_err(fn + ": the op has no str_val 'solver_type' (sgd | nesterov | adam)");
     r.type = -1; for (int i = 0; i < 3; ++i) if (st->second == kSolverTypeNames[i]) r.type = i;
@@ -265,12 +268,13 @@ inline solver_op_t solver_op_of_op(op_base_t const &op) {
   if (!op.has("tens_num")) rt_err(fn + ": the op has no 'tens_num'");
   uint32_t const n = op.get_u32("tens_num");
   if (n < 1 || n > (uint32_t)kSgdUpdateMaxTens) rt_err(fn + ": tens_num=" + std::to_string(n) + ": 1 to " + std::to_string(kSgdUpdateMaxTens) + " tensors");
-  if (r.kind == 1) { vec("hyper", 8, "lr, momentum, weight_decay, momentum2, delta, corr, clip_gradients, unused"); vec("state", 4, "coef, norm, sumsq, 0"); }
-  else { r.parts = vec("partials", 0, "one partial per chunk"); need("part0"); r.part0 = op.get_u32("part0"); }
+  if (r.update()) { vec("hyper", 8, "lr, momentum, weight_decay, momentum2, delta, corr, clip_gradients, unused"); vec("state", 4, "coef, norm, sumsq, 0"); }
+  if (r.kind >= 4) vec("accum", 4, "first, apply, scale, micro");
+  if (r.kind == 2) { r.parts = vec("partials", 0, "one partial per chunk"); need("part0"); r.part0 = op.get_u32("part0"); }
   for (uint32_t i = 0; i < n; ++i) {
     string const sx = "_" + std::to_string(i);
-    std::vector<string> bases = r.kind == 1 ? std::vector<string>{"w", "g", "h"} : std::vector<string>{"g"};
-    if (r.kind == 1 && r.type == kSolverAdam) bases.push_back("h2");
+    std::vector<string> bases = r.update() ? std::vector<string>{"w", "g", "h"} : r.kind == 4 ? std::vector<string>{"g", "a"} : std::vector<string>{"g"};
+    if (r.update() && r.type == kSolverAdam) bases.push_back("h2");
     for (string const &b : bases) need(b + sx);
     dims_t const &w = op.get_dims(bases[0] + sx);
     for (string const &b : bases) {
@@ -279,7 +283,7 @@ inline solver_op_t solver_op_of_op(op_base_t const &op) {
       if (!(d == w)) rt_err(fn + ": " + b + sx + " dims " + d.pretty_str() + " differ from " + bases[0] + sx + "'s " + w.pretty_str());
     }
     r.elems.push_back((long)w.dims_prod());
-    if (r.kind == 1) { need("lr_mult" + sx); need("decay_mult" + sx); r.lr_mult.push_back(f32("lr_mult" + sx)); r.decay_mult.push_back(f32("decay_mult" + sx)); }
+    if (r.update()) { need("lr_mult" + sx); need("decay_mult" + sx); r.lr_mult.push_back(f32("lr_mult" + sx)); r.decay_mult.push_back(f32("decay_mult" + sx)); }
   }
   if (r.kind == 2 && (long)r.part0 + r.chunks() > r.parts)
     rt_err(fn + ": part0=" + std::to_string(r.part0) + " + " + std::to_string(r.chunks()) + " chunks exceed the " + std::to_string(r.parts) + " partials");

@@ -277,6 +277,10 @@ OP_INFO = {
     "SolverUpdate": (("hyper", "state"), (), ("tens_num",)),
     "GradSumsq": ((), ("partials",), ("tens_num", "part0")),
     "GradNorm": (("partials", "hyper"), ("state",), ()),
+    # this backend's own: gradient accumulation over iter_size micro-steps.  accum float v=4 (first, apply, scale, micro).  GradAccum: the multi args g (read) and a (the
+    # accumulators, rewritten).  SolverUpdateAcc: a SolverUpdate that also reads accum, its g the accumulators
+    "GradAccum": (("accum",), (), ("tens_num",)),
+    "SolverUpdateAcc": (("hyper", "state", "accum"), (), ("tens_num",)),
     # this backend's own: the training BatchNorm of the gradient pipe and the gradient of an Eltwise SUM (csrc/kernels/bn_f32.hip states the arithmetic).  The per-channel
     # args are float chan=C; run_mean / run_var are read and written; slab (0: the planner's) forces the slab length of the per-channel sums; FanOut writes the multi arg outs
     "BnStats": (("in",), ("mean", "inv_std", "run_mean", "run_var"), ("eps", "maf", "slab")),
@@ -286,7 +290,7 @@ OP_INFO = {
     "FanOut": (("in",), (), ("outs_num",)),
 }
 BN_TYPES = ("BnStats", "BnFwd", "BnBckSums", "BnBckIn", "FanOut")
-SOLVER_TYPES = ("SolverUpdate", "GradSumsq", "GradNorm")
+SOLVER_TYPES = ("SolverUpdate", "GradSumsq", "GradNorm", "GradAccum", "SolverUpdateAcc")
 SOLVER_CHUNK = 4096   # floats of one tensor a workgroup owns; one partial sum of squares per chunk
 
 
@@ -543,7 +547,8 @@ class Op:
 
     def solver_geom(self) -> dict:
         """SolverUpdate / GradSumsq / GradNorm, with sgd_geom's checks: 1 to 32 tensors of identical float dims per tensor (w_i g_i h_i, h2_i for adam | g_i), hyper float
-        v=8, state float v=4, partials float v=P with part0 + the call's chunks <= P.  -> n, elems, chunks (GradNorm: parts)."""
+        v=8, state float v=4, partials float v=P with part0 + the call's chunks <= P.  GradAccum (g_i a_i) and SolverUpdateAcc (a SolverUpdate's op) also carry accum
+        float v=4.  -> n, elems, chunks (GradNorm: parts)."""
         t = self.get_type()
 
         def vec(an, v, what):
@@ -555,22 +560,25 @@ class Op:
         if t == "GradNorm":
             parts = vec("partials", 0, "one partial per chunk"); vec("hyper", 8, hyper); vec("state", 4, "coef, norm, sumsq, 0")
             return dict(parts=parts)
-        bases = ("g",)
-        if t == "SolverUpdate":
+        bases = ("g", "a") if t == "GradAccum" else ("g",)
+        update = t in ("SolverUpdate", "SolverUpdateAcc")
+        if update:
             st = self.str_vals.get("solver_type")
             if st not in ("sgd", "nesterov", "adam"):
-                raise RtErr(f"SolverUpdate: solver_type must be sgd | nesterov | adam, got {st!r}")
+                raise RtErr(f"{t}: solver_type must be sgd | nesterov | adam, got {st!r}")
             for fl in ("clip", "decoupled_wd"):
                 if self.has(fl) and self.get_u32(fl) not in (0, 1):
-                    raise RtErr(f"SolverUpdate: {fl} must be 0 | 1")
+                    raise RtErr(f"{t}: {fl} must be 0 | 1")
             if self.has("decoupled_wd") and self.get_u32("decoupled_wd") and st != "adam":
-                raise RtErr(f"SolverUpdate: decoupled_wd=1 is adam's, not {st}'s")
+                raise RtErr(f"{t}: decoupled_wd=1 is adam's, not {st}'s")
             bases = ("w", "g", "h") + (("h2",) if st == "adam" else ())
         n = self.get_u32("tens_num")
         if n < 1 or n > 32:
             raise RtErr(f"{t}: tens_num={n}: 1 to 32 tensors")
-        if t == "SolverUpdate":
+        if update:
             vec("hyper", 8, hyper); vec("state", 4, "coef, norm, sumsq, 0")
+        if t in ("GradAccum", "SolverUpdateAcc"):
+            vec("accum", 4, "first, apply, scale, micro")
         elems = []
         for i in range(n):
             w = self.get_dims(f"{bases[0]}_{i}")
@@ -580,7 +588,7 @@ class Op:
                     raise RtErr(f"{t}: {b}_{i} has type {d.tn}: the solver is fp32 only")
                 if d != w:
                     raise RtErr(f"{t}: {b}_{i} dims {d.pretty()} differ from {bases[0]}_{i}'s {w.pretty()}")
-            if t == "SolverUpdate":
+            if update:
                 self.get_f32(f"lr_mult_{i}"); self.get_f32(f"decay_mult_{i}")
             elems.append(w.dims_prod())
         chunks = sum(-(-e // SOLVER_CHUNK) for e in elems)
@@ -663,7 +671,9 @@ class Op:
         """4*(in+out+filts+biases) resp. 4*(a+b+c) (src/latex-util.H:119,133)."""
         if self.get_type() == "SgdUpdate":   # w, g, h read, h and w written
             return 20 * sum(self.sgd_geom()["elems"])
-        if self.get_type() == "SolverUpdate":   # adam reads and writes h2 as well
+        if self.get_type() == "GradAccum":   # g and a read, a written
+            return 12 * sum(self.solver_geom()["elems"])
+        if self.get_type() in ("SolverUpdate", "SolverUpdateAcc"):   # adam reads and writes h2 as well
             return (28 if self.str_vals.get("solver_type") == "adam" else 20) * sum(self.solver_geom()["elems"])
         if self.get_type() == "GradSumsq":   # every gradient read once, one partial written per chunk
             g = self.solver_geom()

@@ -175,3 +175,68 @@ def pipe_spec(text: str, in_chw: Tuple[int, int, int] = (3, 224, 224)) -> List[s
         c, h, w = (dims[1], dims[2], dims[3]) if len(dims) == 4 else in_chw
         out.insert(0, f"input {_one(root, 'input')} {c} {h} {w}")
     return out
+
+
+# ---- Caffe's SolverParameter (solver.prototxt) -> bck_pipe.Solver
+_SOLVER_TYPES = {"SGD": "sgd", "Nesterov": "nesterov", "Adam": "adam"}                 # type: "<name>"
+_SOLVER_ENUMS = {"SGD": "sgd", "NESTEROV": "nesterov", "ADAM": "adam"}                 # the legacy solver_type: <ENUM>
+_SOLVER_UNSUP = ("AdaGrad", "RMSProp", "AdaDelta", "ADAGRAD", "RMSPROP", "ADADELTA")   # Caffe's other three: no kernel here
+_SOLVER_KEYS = ("type", "solver_type", "base_lr", "lr_policy", "gamma", "power", "stepsize", "stepvalue", "max_iter", "momentum", "momentum2", "delta", "weight_decay",
+                "clip_gradients", "iter_size", "regularization_type")
+
+
+def solver_spec(text: str):
+    """Caffe's SolverParameter text form -> (bck_pipe.Solver, iter_size, ignored): what ConvPipeBck(rtc, solver=..., iter_size=...) takes.
+    Read: type "SGD" | "Nesterov" | "Adam" (or the legacy solver_type SGD | NESTEROV | ADAM) -> type; base_lr -> lr; lr_policy with gamma / power / stepsize / the repeated
+    stepvalue / max_iter -> an LrPolicy holding the keys the file gives (no lr_policy key: None, a fixed rate); momentum, momentum2, delta, weight_decay, clip_gradients;
+    iter_size.  Absent keys get CAFFE's defaults, not the dataclass's: momentum 0, weight_decay 0, momentum2 0.999, delta 1e-8, clip_gradients -1 (off: 0.0 here),
+    iter_size 1, type SGD.  AdaGrad / RMSProp / AdaDelta and regularization_type "L1" are an UnsupErr that names the value.  Every other key (net, test_iter, display,
+    snapshot*, solver_mode, random_seed, ...) comes back in `ignored`, key -> the list of its values."""
+    from .bck_pipe import LrPolicy, Solver
+    from .op import UnsupErr
+    d = parse(text)
+    for k in _SOLVER_KEYS:
+        if k != "stepvalue" and len(d.get(k, [])) > 1:
+            raise RtErr(f"solver prototxt: {k!r} is given {len(d[k])} times")
+        if any(isinstance(v, dict) for v in d.get(k, [])):
+            raise RtErr(f"solver prototxt: {k!r} must be a value, not a block")
+
+    def num(k, default, conv=float):
+        v = _one(d, k)
+        if v is None:
+            return default
+        try:
+            return conv(v)
+        except ValueError:
+            raise RtErr(f"solver prototxt: {k}: {v!r} is not a number")
+    if "type" in d and "solver_type" in d:
+        raise RtErr("solver prototxt: both 'type' and the legacy 'solver_type' are given")
+    name, table = (_one(d, "type"), _SOLVER_TYPES) if "type" in d else (_one(d, "solver_type", "SGD"), _SOLVER_ENUMS)
+    if name in _SOLVER_UNSUP:
+        raise UnsupErr(f"solver prototxt: solver type {name!r}: only SGD, Nesterov and Adam have an update kernel (AdaGrad, RMSProp and AdaDelta are not built)")
+    if name not in table:
+        raise RtErr(f"solver prototxt: solver type {name!r}: one of {' | '.join(table)}")
+    reg = _one(d, "regularization_type", "L2")
+    if reg != "L2":
+        if reg == "L1":
+            raise UnsupErr("solver prototxt: regularization_type 'L1': the update kernels regularise with weight_decay * w (L2) only")
+        raise RtErr(f"solver prototxt: regularization_type {reg!r}: L2 | L1")
+    if "base_lr" not in d:
+        raise RtErr("solver prototxt: no base_lr")
+    policy = None
+    if "lr_policy" in d:
+        kw = {k: num(k, None) for k in ("gamma", "power") if k in d}
+        kw.update({k: num(k, None, int) for k in ("stepsize", "max_iter") if k in d})
+        if "stepvalue" in d:
+            try:
+                kw["stepvalues"] = tuple(int(v) for v in d["stepvalue"])
+            except (ValueError, TypeError):
+                raise RtErr(f"solver prototxt: stepvalue: {d['stepvalue']!r} are not all integers")
+        policy = LrPolicy(_one(d, "lr_policy"), **kw)
+    clip = num("clip_gradients", -1.0)
+    iter_size = num("iter_size", 1, int)
+    if iter_size < 1:
+        raise RtErr(f"solver prototxt: iter_size={iter_size}: at least 1")
+    sv = Solver(type=table[name], lr=num("base_lr", None), momentum=num("momentum", 0.0), momentum2=num("momentum2", 0.999), delta=num("delta", 1e-8),
+                weight_decay=num("weight_decay", 0.0), clip_gradients=clip if clip > 0 else 0.0, lr_policy=policy)
+    return sv, iter_size, {k: v for k, v in d.items() if k not in _SOLVER_KEYS}

@@ -43,6 +43,9 @@ hip_grad_sumsq calls and hip_grad_norm) against the step with hip_sgd_update, in
 per update function, the median us of its calls per step, the bytes they move (20 B per element for sgd / nesterov, 28 for adam, 4 for the sum of squares) and GB/s.
 --swap builds and runs the Solver leg first (which of the process's two backends allocates first is then the other one); --solver sgd runs hip_sgd_update's chain in the new
 kernel.  Several invocations go to one file by hand (profiles/r18_solver.txt); no figure is required.
+--iter-size N (with --solver): the two legs are the Solver's step with iter_size=1 and with iter_size=N of the same build: every pass then runs
+hip_grad_accum (12 B per element) and, when clipping, the norm over the accumulators; hip_solver_update_acc's us and GB/s are those of the passes that apply
+(us_not_applying: the others).  --runs should be a multiple of N.  Written to profiles/r19_grad_accum.txt.
 
 --devices d0:d1:...: the plain step on the multi-device backend `(be=hip,devices=...)`: the batch sharded on img, the five functions that are not independent per image
 run with img_shards=1.  Step ms is the longest of the devices' times; a call's share counts the time its device-side launches took, not the
@@ -265,9 +268,11 @@ def sgd_ab(net, batch, runs, warmup, repeats):
         w["drv"].release(); w["rtc"].close()
 
 
-def solver_ab(net, batch, runs, warmup, repeats, solver_type, clip, swap=False):
+def solver_ab(net, batch, runs, warmup, repeats, solver_type, clip, swap=False, iter_size=1):
     """--solver: the step with hip_sgd_update (SgdSolver, the rate every other figure is held against) and with Solver(type=solver_type, clip_gradients=clip), in
-    alternating blocks in one process: per way one JSON line with, per update function, the median us of its calls per step, the bytes they move and GB/s."""
+    alternating blocks in one process: per way one JSON line with, per update function, the median us of its calls per step, the bytes they move and GB/s.
+    iter_size > 1 (--iter-size): the two legs are the Solver's step with iter_size=1 and with iter_size=n (hip_grad_accum on every pass, hip_solver_update_acc; DESIGN.md
+    section 3.19) of the same build; hip_solver_update_acc's us and GB/s are those of the passes that apply, "us_not_applying" those of the others."""
     import numpy as np
     from boda_amd.bck_pipe import ConvPipeBck, SgdSolver, Solver, add_bck_ops, bn_stat_params, host_params
     from boda_amd.rtc import make_rtc
@@ -280,14 +285,17 @@ def solver_ab(net, batch, runs, warmup, repeats, solver_type, clip, swap=False):
     kw = dict(lr=1e-5, momentum=0.9, weight_decay=5e-4, lr_mult={"biases": 2.0}, decay_mult={"biases": 0.0})   # (a rate at which random labels keep every value finite)
     way2 = "solver_" + solver_type + ("_clip" if clip > 0 else "")   # ("solver_sgd": the same chain as the "sgd" leg, in the new kernel)
     ways = {}
-    legs = [("sgd", SgdSolver(**kw)), (way2, Solver(type=solver_type, clip_gradients=clip, **kw))]
-    for way, solver in (legs[::-1] if swap else legs):   # (swap: the Solver leg is built and run first -- which backend allocates first is then the other one)
+    legs = [("sgd", SgdSolver(**kw), 1), (way2, Solver(type=solver_type, clip_gradients=clip, **kw), 1)]
+    if iter_size > 1:
+        base, way2 = way2, way2 + f"_iter{iter_size}"
+        legs = [(base, Solver(type=solver_type, clip_gradients=clip, **kw), 1), (way2, Solver(type=solver_type, clip_gradients=clip, **kw), iter_size)]
+    for way, solver, n_it in (legs[::-1] if swap else legs):   # (swap: the Solver leg is built and run first -- which backend allocates first is then the other one)
         rtc = make_rtc("(be=hip)", 0)
         rtc.init()
-        drv = ConvPipeBck(rtc, solver=solver)
+        drv = ConvPipeBck(rtc, solver=solver, iter_size=n_it)
         drv.init(bp, params)
         rtc.copy_nda_to_var("data", data); rtc.copy_nda_to_var("label", label)
-        ways[way] = {"rtc": rtc, "drv": drv, "blocks": [], "ms": [], "fn_ms": {}}
+        ways[way] = {"rtc": rtc, "drv": drv, "blocks": [], "ms": [], "fn_ms": {}, "idle_ms": {}}
     for w in ways.values():
         for i in range(warmup):
             w["drv"].set_det_drop_seed(i); w["drv"].run_device_only()
@@ -296,10 +304,11 @@ def solver_ab(net, batch, runs, warmup, repeats, solver_type, clip, swap=False):
             ms = []
             for i in range(runs):
                 w["drv"].set_det_drop_seed(warmup + rep * runs + i)
+                applies = w["drv"].micro == w["drv"].iter_size - 1
                 ms.append(w["drv"].run_device_only())
                 tail = w["drv"].per_call_ms[len(w["drv"].per_call_ms) - w["drv"].n_sgd_calls:]
                 for fn in {fn for _, fn, _ in tail}:
-                    w["fn_ms"].setdefault(fn, []).append(sum(d for _, f, d in tail if f == fn))
+                    (w["fn_ms"] if applies or fn != "hip_solver_update_acc" else w["idle_ms"]).setdefault(fn, []).append(sum(d for _, f, d in tail if f == fn))
             w["ms"] += ms; w["blocks"].append(round(statistics.median(ms), 3))
     for way, w in ways.items():
         step = statistics.median(w["ms"])
@@ -308,10 +317,13 @@ def solver_ab(net, batch, runs, warmup, repeats, solver_type, clip, swap=False):
             us = statistics.median(ds) * 1e3
             nbytes = sum(f.algo_bytes() for _, f, _ in w["drv"].calls() if f.get_func_name() == fn)
             fns[fn] = {"calls": sum(1 for _, f, _ in w["drv"].calls() if f.get_func_name() == fn), "us": round(us, 1), "algo_bytes": nbytes, "GBps": round(nbytes / (us * 1e-6) / 1e9, 1)}
+            if fn in w["idle_ms"]:
+                fns[fn]["us_not_applying"] = round(statistics.median(w["idle_ms"][fn]) * 1e3, 1)
         print(json.dumps({"net": net, "batch": batch, "way": way, "calls": len(w["drv"].calls()), "step_ms": round(step, 3), "block_medians_ms": w["blocks"],
                           "imgs_per_s": round(batch / (step * 1e-3), 1), "loss": round(float(w["rtc"].copy_var_to_nda("loss").item()), 4),
                           "param_tensors": len(w["drv"].sgd_params), "update_functions": fns, "copy_rate_GBps_recorded": 6290.0}), flush=True)
-    print(json.dumps({"net": net, way2 + "_over_sgd_step": round(statistics.median(ways[way2]["ms"]) / statistics.median(ways["sgd"]["ms"]), 4)}), flush=True)
+    first = legs[0][0]
+    print(json.dumps({"net": net, f"{way2}_over_{first}_step": round(statistics.median(ways[way2]["ms"]) / statistics.median(ways[first]["ms"]), 4)}), flush=True)
     for w in ways.values():
         w["drv"].release(); w["rtc"].close()
 
@@ -397,6 +409,7 @@ def main(argv=None):
     ap.add_argument("--solver", default="", choices=["", "sgd", "nesterov", "adam"], help="A/B: the step with hip_sgd_update and with Solver(type=...) (hip_solver_update), in alternating blocks in one process; per update function us and GB/s")
     ap.add_argument("--swap", action="store_true", help="with --solver: build and run the Solver leg before the hip_sgd_update leg")
     ap.add_argument("--clip", type=float, default=0.0, help="with --solver: clip_gradients (0: off); adds the hip_grad_sumsq calls and hip_grad_norm")
+    ap.add_argument("--iter-size", type=int, default=1, help="with --solver: the legs are the Solver's step with iter_size=1 and with iter_size=N (hip_grad_accum, hip_solver_update_acc)")
     ap.add_argument("--grad-operands", default="", choices=["", "bf16"], help="A/B: the fp32 step, the fp32 step with the fused filter + bias call, and the step with bf16 gradient operands, in one process")
     ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad / --graph / --sgd: alternating blocks of --runs steps per way")
     ap.add_argument("--devices", default="", help="e.g. 0:1:2:3: the plain step on the multi-device backend (be=hip,devices=...), batch sharded on img")
@@ -416,12 +429,14 @@ def main(argv=None):
         ap.error("--solver is a comparison of its own on one device")
     if a.clip and not a.solver:
         ap.error("--clip goes with --solver")
-    a.out = a.out or os.path.join(ROOT, "profiles", "r17_resnet50_chunks.txt" if a.img_chunks else "r16_step_bf16.txt" if a.grad_operands else "r18_solver.txt" if a.solver else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
+    if a.iter_size != 1 and (not a.solver or a.iter_size < 1):
+        ap.error("--iter-size goes with --solver and is at least 1")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r17_resnet50_chunks.txt" if a.img_chunks else "r16_step_bf16.txt" if a.grad_operands else "r19_grad_accum.txt" if a.solver and a.iter_size > 1 else "r18_solver.txt" if a.solver else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
     if a.child:
         if a.grad_operands:
             return operands_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, a.grad_operands)
         if a.solver:
-            return solver_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, a.solver, a.clip, a.swap)
+            return solver_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, a.solver, a.clip, a.swap, a.iter_size)
         if a.sgd:
             return sgd_ab(a.child, a.batch, a.runs, a.warmup, a.repeats)
         if a.graph:
@@ -444,7 +459,7 @@ def main(argv=None):
         cmd += ["--grad-operands", a.grad_operands, "--repeats", str(a.repeats)] if a.grad_operands else []
         cmd += ["--graph", "--repeats", str(a.repeats)] if a.graph else []
         cmd += ["--sgd", "--repeats", str(a.repeats)] if a.sgd else []
-        cmd += ["--solver", a.solver, "--clip", str(a.clip), "--repeats", str(a.repeats)] + (["--swap"] if a.swap else []) if a.solver else []
+        cmd += ["--solver", a.solver, "--clip", str(a.clip), "--repeats", str(a.repeats)] + (["--swap"] if a.swap else []) + (["--iter-size", str(a.iter_size)] if a.iter_size > 1 else []) if a.solver else []
         cmd += ["--devices", a.devices] if a.devices else []
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:   # nothing more is started on the GPU after a failure
@@ -453,7 +468,7 @@ def main(argv=None):
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
         print("\n".join(lines[-4:] if (a.graph or a.sgd or a.grad_operands) else lines[-3:] if (a.fuse_relu_grad or a.fuse_filts_biases or a.solver) else lines[-1:]), flush=True)
     with open(a.out, "w") as f:
-        extra = f" --img-chunks {a.img_chunks}{' --devices ' + a.devices if a.devices else ''} --repeats {a.repeats}" if a.img_chunks else f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --solver {a.solver} --clip {a.clip}{' --swap' if a.swap else ''} --repeats {a.repeats}" if a.solver else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
+        extra = f" --img-chunks {a.img_chunks}{' --devices ' + a.devices if a.devices else ''} --repeats {a.repeats}" if a.img_chunks else f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --solver {a.solver} --clip {a.clip}{' --swap' if a.swap else ''}{f' --iter-size {a.iter_size}' if a.iter_size > 1 else ''} --repeats {a.repeats}" if a.solver else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
         f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 
