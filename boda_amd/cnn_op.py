@@ -427,6 +427,54 @@ def solver_update_acc_func_op(dims_list, solver_type, lr_mults=None, decay_mults
     return a
 
 
+ACCURACY_FUNC, EVAL_ACCUM_FUNC, BN_FOLD_FUNC = "hip_accuracy", "hip_eval_accum", "hip_bn_fold"
+# the evaluation pass of the gradient pipe, in a table of its own (the pinned ones stay as they are): what eval_pipe.EvalPipe adds to a driver's forward calls.  This
+# backend's own: csrc/kernels/eval_f32.hip states the rules
+EVAL_OP_FUNCS: Dict[str, tuple] = {"Accuracy": (ACCURACY_FUNC,), "EvalAccum": (EVAL_ACCUM_FUNC,), "BnFold": (BN_FOLD_FUNC,)}
+
+
+def accuracy_func_op(in_dims) -> Op:
+    """-> the annotated function op of hip_accuracy on the logits `in_dims` (float img:chan:1:1): args in, label (float img:1:1, the loss's own var) read, rank (uint32_t
+    img) written.  Per image: the label lf is valid iff lf >= 0 and lf < chan (a NaN is not), L = int(lf); invalid: rank = 0xFFFFFFFF; valid: rank = the number of
+    classes c != L with not (in[c] < in[L]) -- ties, and a NaN on either side, count against the true class.  A top-k hit is rank < k."""
+    from .op import Dims
+    if in_dims.names != ("img", "chan", "y", "x") or in_dims.tn != "float":
+        raise RtErr(f"accuracy_func_op: in must be float img:chan:y:x, got {in_dims.tn} {in_dims.pretty()}")
+    b = in_dims.dsz("img")
+    a = Op({"type": "Accuracy"}, {"in": Nda(dims=in_dims, tn="float"), "label": Nda(dims=Dims(("img", "y", "x"), (b, 1, 1), "float"), tn="float"),
+                                  "rank": Nda(dims=Dims(("img",), (b,), "uint32_t"), tn="uint32_t")})
+    a.eval_geom()
+    a.set_func_name(ACCURACY_FUNC)
+    return a
+
+
+def eval_accum_func_op(img: int, top_k: int) -> Op:
+    """-> the annotated function op of hip_eval_accum over `img` images: rank (uint32_t img), loss (float y=1:x=1) and ctl (uint32_t v=4 = [first, 0, 0, 0]) read; counts
+    (uint32_t v=4 = [images, hits_top1, hits_topk, batches]) and loss_sum (float v=1) rewritten.  first != 0: counts' = [img, h1, hk, 1], loss_sum' = loss, neither read;
+    else counts' = counts + [img, h1, hk, 1] and loss_sum' = loss_sum + loss (one fp32 add).  h1 counts rank < 1, hk rank < top_k (>= 1, rides in the op)."""
+    from .op import Dims
+    u4 = Dims(("v",), (4,), "uint32_t")
+    a = Op({"type": "EvalAccum"}, {"rank": Nda(dims=Dims(("img",), (int(img),), "uint32_t"), tn="uint32_t"), "loss": Nda(dims=Dims(("y", "x"), (1, 1), "float"), tn="float"),
+                                   "ctl": Nda(dims=u4, tn="uint32_t"), "counts": Nda(dims=u4, tn="uint32_t"), "loss_sum": Nda(dims=Dims(("v",), (1,), "float"), tn="float"),
+                                   "top_k": Nda(None, "uint32_t", (int(top_k),))})
+    a.eval_geom()
+    a.set_func_name(EVAL_ACCUM_FUNC)
+    return a
+
+
+def bn_fold_func_op(chan: int, eps: float) -> Op:
+    """-> the annotated function op of hip_bn_fold over `chan` channels: run_mean, run_var, scale, bias (float chan) read, a, b written -- the bits of
+    conv_pipe.fold_affine([("BatchNorm", run_mean, run_var, eps), ("Scale", scale, bias)]), what hip_chan_affine takes.  eps (>= 0) rides in the op."""
+    from .op import Dims
+    ch = Dims(("chan",), (int(chan),), "float")
+    v = {an: Nda(dims=ch, tn="float") for an in ("run_mean", "run_var", "scale", "bias", "a", "b")}
+    v["eps"] = Nda(None, "float", (_as_f32(eps),))
+    a = Op({"type": "BnFold"}, v)
+    a.eval_geom()
+    a.set_func_name(BN_FOLD_FUNC)
+    return a
+
+
 # the training BatchNorm of the gradient pipe and the Eltwise-SUM gradient, in a table of their own (PIPE_OP_FUNCS is pinned): what bck_pipe.ConvPipeBck runs for a
 # BatchNorm + Scale (+ ReLU) run and its gradient, and for a BckEltwise.  This backend's own arithmetic: csrc/kernels/bn_f32.hip and DESIGN.md section 3.15 state it
 BN_OP_FUNCS: Dict[str, tuple] = {
@@ -712,6 +760,10 @@ NATIVE_ARGS: Dict[str, tuple] = {
     # gradient accumulation (this backend's own).  In front of these (pipe_func_args): g_i (IN) a_i (INOUT) per tensor | hip_solver_update's w_i g_i h_i [h2_i]
     "hip_grad_accum": (("accum", "IN"),),
     "hip_solver_update_acc": (("hyper", "IN"), ("state", "IN"), ("accum", "IN")),
+    # the evaluation pass (this backend's own; top_k / eps ride in the op).  counts and loss_sum are read unless ctl[0] != 0, and rewritten
+    "hip_accuracy": (("in", "IN"), ("label", "IN"), ("rank", "OUT")),
+    "hip_eval_accum": (("rank", "IN"), ("loss", "IN"), ("ctl", "IN"), ("counts", "INOUT"), ("loss_sum", "INOUT")),
+    "hip_bn_fold": (("run_mean", "IN"), ("run_var", "IN"), ("scale", "IN"), ("bias", "IN"), ("a", "OUT"), ("b", "OUT")),
     # the training BatchNorm and the Eltwise-SUM gradient (this backend's own; eps / maf / slab / relu ride in the op).  hip_fan_out's list depends on the op: in,
     # then outs_0 .. outs_{n-1} (pipe_func_args)
     "hip_bn_stats": (("in", "IN"), ("mean", "OUT"), ("inv_std", "OUT"), ("run_mean", "INOUT"), ("run_var", "INOUT")),

@@ -419,6 +419,48 @@ void bn_bck_in(bn_op_t const &b, float const *in, float const *dy, float *dx, fl
     }
   }
 }
+// ---- the eval family (kernels/eval_f32.hip states the rules): the same tests and the same fp32 chain, one rounding per line
+void accuracy(float const *in, float const *label, uint32_t *rank, long B, long C) {
+#pragma omp parallel for schedule(static)
+  for (long img = 0; img < B; ++img) {
+    float const lf = label[img];
+    bool const valid = lf >= 0.0f && lf < (float)C;
+    if (!valid) { rank[img] = 0xFFFFFFFFu; continue; }
+    long const L = (long)(int)lf;
+    float const *const x = in + img * C;
+    float const t = x[L];
+    uint32_t cnt = 0;
+    for (long c = 0; c < C; ++c) cnt += (c != L && !(x[c] < t)) ? 1u : 0u;
+    rank[img] = cnt;
+  }
+}
+void eval_accum(uint32_t const *rank, float const *loss, uint32_t const *ctl, uint32_t *counts, float *loss_sum, long B, uint32_t top_k) {
+  uint32_t h1 = 0, hk = 0;
+  for (long i = 0; i < B; ++i) { h1 += rank[i] < 1u ? 1u : 0u; hk += rank[i] < top_k ? 1u : 0u; }
+  if (ctl[0] != 0u) {
+    counts[0] = (uint32_t)B; counts[1] = h1; counts[2] = hk; counts[3] = 1u;
+    memcpy(loss_sum, loss, sizeof(float));   // the loss's bits
+  } else {
+    counts[0] += (uint32_t)B; counts[1] += h1; counts[2] += hk; counts[3] += 1u;
+    loss_sum[0] = loss_sum[0] + loss[0];
+  }
+}
+void bn_fold(float const *run_mean, float const *run_var, float const *scale, float const *bias, float *a, float *b, long C, float eps) {
+  for (long c = 0; c < C; ++c) {
+    float const mean = run_mean[c], var = run_var[c], sc = scale[c], bi = bias[c];
+    float const ve = var + eps;
+    float const sd = sqrtf(ve);
+    float const a2 = 1.0f / sd;
+    float const mp = mean * a2;
+    float const b2 = -mp;
+    float const a1 = a2 * 1.0f;
+    float const z = a2 * 0.0f;
+    float const b1 = z + b2;
+    float const av = sc * a1;
+    float const sb = sc * b1;
+    a[c] = av; b[c] = sb + bi;
+  }
+}
 #pragma GCC pop_options
 } // namespace
 
@@ -494,6 +536,7 @@ struct cpu_compute_t : public rtc_compute_t {
       if (f->family == kFamSgd) (void)sgd_op_of_op(fi.op);   // (the op must be whole)
       if (f->family == kFamBn || f->family == kFamBnc) (void)bn_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamSolver) (void)solver_op_of_op(fi.op);   // (likewise)
+      if (f->family == kFamEval) (void)eval_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamBckOp) {
         if (!f->of_type(fi.op.get_type())) rt_err(fn + ": a function of op type " + f->types[0] + ", not " + fi.op.get_type());
         bck_op_args_t const a = bck_op_args(*f, fi.op);
@@ -888,6 +931,31 @@ struct cpu_compute_t : public rtc_compute_t {
     }
   }
 
+  // the eval family: the checks of be=hip (csrc/native_run.cc), then the twins above
+  void run_eval(op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = op.get_func_name();
+    eval_op_t e = eval_op_of_op(op);
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    std::vector<void *> P; long n_img = -1;
+    for (string const &an : e.args) {
+      string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn);
+      dims_t want = op.get_dims(an);
+      if (vd.tn != want.tn) rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ", the op says " + want.tn);
+      if (e.kind == 1 && vd.sz() == want.sz() && vd.sz() >= 1) {
+        if (n_img < 0) n_img = vd.dims(0);
+        if ((long)vd.dims(0) != n_img) rt_err(fn + ": arg '" + an + "' has " + std::to_string(vd.dims(0)) + " images, another arg " + std::to_string(n_img));
+        want[0].sz = vd.dims(0); want.calc_strides();
+      }
+      if (!(vd == want)) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + op.get_dims(an).pretty_str());
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      P.push_back(must_find(vis, vn).buf.get());
+    }
+    if (e.kind == 1) accuracy((float const *)P[0], (float const *)P[1], (uint32_t *)P[2], n_img, e.C);
+    else if (e.kind == 2) eval_accum((uint32_t const *)P[0], (float const *)P[1], (uint32_t const *)P[2], (uint32_t *)P[3], (float *)P[4], e.B, e.top_k);
+    else bn_fold((float const *)P[0], (float const *)P[1], (float const *)P[2], (float const *)P[3], (float *)P[4], (float *)P[5], e.C, e.eps);
+  }
+
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
     auto fit = funcs.find(rfc.rtc_func_name);
@@ -901,6 +969,7 @@ struct cpu_compute_t : public rtc_compute_t {
     if (f.family == kFamSgd) run_sgd_update(fi.op, am);
     else if (f.family == kFamBn || f.family == kFamBnc) run_bn(fi.op, am);
     else if (f.family == kFamSolver) run_solver(fi.op, am);
+    else if (f.family == kFamEval) run_eval(fi.op, am);
     else if (f.family == kFamBckOp) run_bck_op(f, fi.op, am);
     else if (f.family == kFamBconv) run_bck(f, fi.op, am);
     else if (f.family == kFamSgemm) {

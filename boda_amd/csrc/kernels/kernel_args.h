@@ -250,6 +250,27 @@ struct bn_args_t {
 static_assert(sizeof(bn_args_t) == 13 * 8 + 8 * 8 + 8 + 9 * 4 + 5 * 4 && __builtin_offsetof(bn_args_t, outs) == 104 && __builtin_offsetof(bn_args_t, n) == 168 && __builtin_offsetof(bn_args_t, B) == 176 &&
               __builtin_offsetof(bn_args_t, fN) == 212, "bn_args_t layout");
 
+// kernels/eval_f32.hip: the evaluation pass of the gradient pipe
+struct accuracy_args_t {
+  float const *in; float const *label;   // logits img:chan:1:1, labels img:1:1
+  unsigned *rank;                        // one word per image
+  int B, C;
+};
+static_assert(sizeof(accuracy_args_t) == 32 && __builtin_offsetof(accuracy_args_t, rank) == 16 && __builtin_offsetof(accuracy_args_t, B) == 24, "accuracy_args_t layout");
+struct eval_accum_args_t {
+  unsigned const *rank; float const *loss;
+  unsigned const *ctl;                   // ctl[0] != 0: counts and loss_sum are overwritten and not read
+  unsigned *counts; float *loss_sum;     // images, hits_top1, hits_topk, batches; the sum of the batches' losses
+  int B; unsigned top_k;
+};
+static_assert(sizeof(eval_accum_args_t) == 48 && __builtin_offsetof(eval_accum_args_t, counts) == 24 && __builtin_offsetof(eval_accum_args_t, B) == 40, "eval_accum_args_t layout");
+struct bn_fold_args_t {
+  float const *run_mean; float const *run_var; float const *scale; float const *bias;
+  float *a; float *b;
+  int C; float eps;
+};
+static_assert(sizeof(bn_fold_args_t) == 56 && __builtin_offsetof(bn_fold_args_t, a) == 32 && __builtin_offsetof(bn_fold_args_t, C) == 48, "bn_fold_args_t layout");
+
 #pragma pop_macro("CH")
 #pragma pop_macro("CIN")
 #pragma pop_macro("COH")

@@ -59,6 +59,10 @@ bn_plan_t plan_bn(bn_op_t const &b);
 plan_t bn_kernel_plan(int op, char const *kname, vect_string const &defs);   // one specialisation of kernels/bn_f32.hip (plan_bn's entries are these)
 string bn_plan_desc(bn_op_t const &b, bn_plan_t const &bp);
 
+// the eval family (kernels/eval_f32.hip; accuracy_args_t, eval_accum_args_t, bn_fold_args_t): one launch per call, nothing to choose but the grid
+bck_plan_t plan_eval_op(eval_op_t const &e);
+string eval_plan_desc(eval_op_t const &e, bck_plan_t const &bp);
+
 struct sgemm_split_t { uint32_t m_main = 0; string tail_tile; double t_single = 0, t_split = 0; };
 static char const *const kBigTile = "256x256x16x2x4x1x1x32x2";
 struct sgemm_part_t { uint32_t m0 = 0, rows = 0, n0 = 0, cols = 0; string tile; };

@@ -69,6 +69,9 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
   case kFamBn: case kFamBnc:   // the op must be whole; the code objects of all the call's launches are built NOW, so that a first run inside a graph capture finds them
     for (bn_launch_t const &l : plan_bn(bn_op_of_op(fi.op)).ls) (void)get_kernel(impl, host, l.p);
     break;
+  case kFamEval:   // likewise: the op whole, the code object built now (an eval pass may first run inside a graph capture)
+    (void)get_kernel(impl, host, plan_eval_op(eval_op_of_op(fi.op)).p);
+    break;
   case kFamBconv:   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     (void)op_bf16_operands(fi.op);   // (str_val hip_operands: refused at compile where the function has no bf16-operand form)
@@ -947,6 +950,24 @@ void native_kernels_t::grad_norm(solver_op_t const &so, float const *partials, f
   hip_err_chk(host->nh_launch(k.func, sp.grid, 1, sp.block, params), "hipModuleLaunchKernel(grad_norm)");
   last_launch.kernel = sp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = sp.grid; last_launch.block = sp.block;
   last_launch.flops = 0; last_launch.algo_bytes = sp.algo_bytes;
+}
+// ---- the eval family (kernels/eval_f32.hip): one launch per call
+void native_kernels_t::eval_call(eval_op_t const &e, void *const *ptrs) {
+  bck_plan_t const bp = plan_eval_op(e);
+  kernel_t &k = get_kernel(impl, host, bp.p);
+  accuracy_args_t a1; eval_accum_args_t a2; bn_fold_args_t a3; void *params[1] = {nullptr};
+  if (e.kind == 1) {
+    memset(&a1, 0, sizeof(a1)); a1.in = (float const *)ptrs[0]; a1.label = (float const *)ptrs[1]; a1.rank = (unsigned *)ptrs[2]; a1.B = (int)e.B; a1.C = (int)e.C; params[0] = &a1;
+  } else if (e.kind == 2) {
+    memset(&a2, 0, sizeof(a2)); a2.rank = (unsigned const *)ptrs[0]; a2.loss = (float const *)ptrs[1]; a2.ctl = (unsigned const *)ptrs[2]; a2.counts = (unsigned *)ptrs[3]; a2.loss_sum = (float *)ptrs[4];
+    a2.B = (int)e.B; a2.top_k = e.top_k; params[0] = &a2;
+  } else {
+    memset(&a3, 0, sizeof(a3)); a3.run_mean = (float const *)ptrs[0]; a3.run_var = (float const *)ptrs[1]; a3.scale = (float const *)ptrs[2]; a3.bias = (float const *)ptrs[3];
+    a3.a = (float *)ptrs[4]; a3.b = (float *)ptrs[5]; a3.C = (int)e.C; a3.eps = e.eps; params[0] = &a3;
+  }
+  if (bp.grid) hip_err_chk(host->nh_launch(k.func, bp.grid, 1, bp.block, params), "hipModuleLaunchKernel(eval)");
+  last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = bp.grid; last_launch.block = bp.block;
+  last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
 }
 // ---- the training BatchNorm functions and hip_fan_out (kernels/bn_f32.hip): one to three launches per call, in plan_bn's order.  The slab partials of the two
 // reducing functions live in a workspace of the CALL (keyed by its pointers, like the K-slice workspaces: calls of a parallel graph run at the same time), allocated on

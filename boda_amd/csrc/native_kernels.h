@@ -31,6 +31,9 @@
 //                                       update reads with clip=1.  kernels/solver_update_f32.hip states the chains and the tree; code objects built when the function is compiled
 //     hip_grad_accum / hip_solver_update_acc    this backend's own: gradient accumulation over iter_size micro-steps.  accum (float v=4 = first, apply, scale, micro) is read
 //                                       from device memory: a_i = first ? g_i : a_i + g_i; the update applies only where apply != 0, on scale * the (clipped) summed gradient
+//     hip_accuracy / hip_eval_accum / hip_bn_fold    this backend's own: the evaluation pass of the gradient pipe.  The rank of the true class per image (uint32; the logits, not
+//                                       prob), the batch's image / hit / batch counts and loss added into counts (uint32 v=4) and loss_sum under ctl = [first, 0, 0, 0] read
+//                                       from device memory, and a [BatchNorm, Scale] run's running statistics folded into (a, b) for hip_chan_affine.  kernels/eval_f32.hip
 //     hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out    this backend's own: the training BatchNorm of the gradient pipe (batch statistics, running
 //                                       pair, normalise + scale + bias + ReLU, the two gradients) and the gradient of an Eltwise SUM.  kernels/bn_f32.hip states the arithmetic and
 //                                       the order of the per-channel sums
@@ -157,6 +160,8 @@ struct native_kernels_t {
   void grad_norm(solver_op_t const &so, float const *partials, float const *hyper, float *state);
   // gradient accumulation: grad_accum: a_i = accum[0] != 0 ? g_i : a_i + g_i; solver_update with so.kind == 5 takes accum (float[4]) as well
   void grad_accum(solver_op_t const &so, float const *const *g, float *const *a, float const *accum);
+  // the eval family on raw device pointers (kernels/eval_f32.hip): ptrs in eval_op_t::args' order; e.B of hip_accuracy is the call's image count
+  void eval_call(eval_op_t const &e, void *const *ptrs);
   void shard_sum(float const *slabs, float *out, int nslabs, long stride, long n);
   // hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out on raw device pointers (kernels/bn_f32.hip): tens / chans in bn_op_t's arg order
   void bn_call(bn_op_t const &b, float *const *tens, float *const *chans);

@@ -1406,6 +1406,40 @@ bck_plan_t plan_shard_sum(int nslabs, long stride, long n) {
   return r;
 }
 
+// ---- the eval family (kernels/eval_f32.hip), beside plan_bck_op: no tile and no geometry in the code (B, C, top_k and eps are kernel arguments), only the grid.
+// hip_accuracy: one wave per image, four per workgroup (bodahip_softmax's layout); hip_eval_accum: one workgroup; hip_bn_fold: one thread per channel
+bck_plan_t plan_eval_op(eval_op_t const &e) {
+  static char const *const knames[] = {"", "bodahip_accuracy", "bodahip_eval_accum", "bodahip_bn_fold"};
+  if (e.kind < 1 || e.kind > 3) rt_err("plan_eval_op: unknown kind " + std::to_string(e.kind));
+  string const what = find_native_func(kFamEval, e.kind)->name;
+  bck_plan_t r; r.p.src = kSrc_eval_f32; r.p.kname = knames[e.kind]; r.p.defs = {"-DOP=" + std::to_string(e.kind)};
+  if (e.B < 0 || e.C < 0) rt_err(what + ": negative dims");
+  if (e.kind == 1) {
+    if (e.C < 1) rt_err(what + ": no channels");
+    if (4.0 * (double)e.B * (double)e.C >= 2147483648.0) unsup_err(what + ": tensors of 2 GiB or more (32-bit element offsets)");
+    r.threads = e.B * 64; r.algo_bytes = 4.0 * ((double)e.B * e.C + 2.0 * e.B);
+  } else if (e.kind == 2) {
+    if (e.B >= (1L << 31)) unsup_err(what + ": 2^31 images or more");
+    if (e.top_k < 1) rt_err(what + ": top_k=0: top_k must be at least 1");
+    r.threads = 256; r.algo_bytes = 4.0 * e.B + 4.0 + 16.0 + 2 * 20.0;
+  } else {
+    if (e.C < 1) rt_err(what + ": no channels");
+    if (e.C >= (1L << 31)) unsup_err(what + ": 2^31 channels or more");
+    r.threads = e.C; r.algo_bytes = 24.0 * e.C;
+  }
+  long const blocks = (r.threads + r.block - 1) / r.block;
+  if (blocks >= (1L << 31)) unsup_err(what + ": too many workgroups");
+  r.grid = (uint32_t)blocks;
+  return r;
+}
+string eval_plan_desc(eval_op_t const &e, bck_plan_t const &bp) {
+  string d = bp.p.kname + " grid=" + std::to_string(bp.grid) + " block=" + std::to_string(bp.block);
+  if (e.kind == 1) d += " imgs=" + std::to_string(e.B) + " chans=" + std::to_string(e.C);
+  else if (e.kind == 2) d += " imgs=" + std::to_string(e.B) + " top_k=" + std::to_string(e.top_k);
+  else d += " chans=" + std::to_string(e.C);
+  return d;
+}
+
 // ---- hip_sgd_update (kernels/sgd_update_f32.hip): one workgroup per chunk of kSgdChunk floats of one tensor; the grid is the sum of the tensors' chunks, blk0 its
 // prefix sums.  20 bytes move per element: w, g, h read, h and w written.
 sgd_plan_t plan_sgd_update(std::vector<long> const &elems) {

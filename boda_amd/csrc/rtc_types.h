@@ -129,7 +129,7 @@ struct op_base_t {
 };
 typedef std::shared_ptr<op_base_t> p_op_base_t;
 // ---- the op flags of a native function.  Which function takes which flag is a column of the one table, native_funcs.h (included at the end of this file), which defines:
-enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver };   // selects the handler
+enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver, kFamEval };   // selects the handler
 enum : unsigned { kFlagZinp = 1, kFlagSeedVar = 2, kFlagImgShards = 4, kFlagNhwcResidual = 8 };
 struct op_flag_name_t { char const *name; unsigned flag; };
 constexpr op_flag_name_t kOpFlagNames[] = {{"img_shards", kFlagImgShards}, {"seed_from_var", kFlagSeedVar}, {"zero_if_in_non_pos", kFlagZinp}, {"nhwc_residual", kFlagNhwcResidual}};
@@ -394,6 +394,60 @@ inline void bn_check_aliases(string const &fn, bn_op_t const &b, vect_string con
     if (b.kind == 4 && i == 1 && j == 2) ok = true;                       // hip_bn_bck_in: in_grad_loss may be out_grad_loss's var
     if (!ok) rt_err(fn + ": args '" + args[i] + "' and '" + args[j] + "' are the same var '" + vars[i] + "'");
   }
+}
+
+// ---- the eval family (this backend's own; kernels/eval_f32.hip states the rules): hip_accuracy (op type Accuracy, member 1: in float img:chan:1:1, label float img:1:1 read,
+// rank uint32_t img written), hip_eval_accum (EvalAccum, member 2: rank uint32_t img, loss float y=1:x=1, ctl uint32_t v=4 read; counts uint32_t v=4, loss_sum float v=1
+// rewritten; the uint32 top_k >= 1) and hip_bn_fold (BnFold, member 3: run_mean, run_var, scale, bias float chan=C read, a, b written; the float eps).  What both backends
+// read from the function's op, and every refusal that needs the op alone
+struct eval_op_t {
+  int kind = 0;                  // the member: 1 accuracy, 2 accum, 3 bn_fold
+  long B = 0, C = 0;             // kinds 1, 2: images; kinds 1, 3: channels
+  uint32_t top_k = 0; float eps = 0.f;
+  vect_string args;              // the var args in the function's arg order
+};
+inline eval_op_t eval_op_of_op(op_base_t const &op) {
+  string const fn = op.has_func_name() ? op.get_func_name() : string();
+  eval_op_t r;
+  r.kind = native_func_member(fn, kFamEval);
+  if (!r.kind) rt_err("'" + fn + "' is none of " + native_family_names(kFamEval));
+  string const type = native_func_type(kFamEval, r.kind);
+  if (!op.has_type() || op.get_type() != type) rt_err(fn + ": a function of op type " + type + ", not " + (op.has_type() ? op.get_type() : string("?")));
+  refuse_flags_not_taken(op, fn, "the function");
+  if (r.kind == 1) r.args = {"in", "label", "rank"}; else if (r.kind == 2) r.args = {"rank", "loss", "ctl", "counts", "loss_sum"}; else r.args = {"run_mean", "run_var", "scale", "bias", "a", "b"};
+  for (string const &an : r.args) if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'");
+  auto vec = [&](string const &an, char const *tn, char const *dn, long n, char const *what) {   // <tn> <dn>=<n> (n == 0: any length of at least 1)
+    dims_t const &d = op.get_dims(an);
+    if (d.tn != tn || d.sz() != 1 || d.names(0) != dn || (n ? (long)d.dims(0) != n : d.dims(0) < 1))
+      rt_err(fn + ": " + an + " must be " + tn + " " + dn + "=" + (n ? std::to_string(n) : string("<n>")) + " (" + what + "), got " + d.tn + " " + d.pretty_str());
+    return (long)d.dims(0); };
+  if (r.kind == 1) {
+    dims_t const &in = op.get_dims("in"), &lab = op.get_dims("label");
+    if (in.tn != "float" || !(in.sz() == 4 && in.names(0) == "img" && in.names(1) == "chan" && in.names(2) == "y" && in.names(3) == "x")) rt_err(fn + ": in must be float img:chan:y:x, got " + in.tn + " " + in.pretty_str());
+    if (in.dims(2) != 1 || in.dims(3) != 1 || lab.sz() != 3 || lab.names(0) != "img" || lab.dims(1) != 1 || lab.dims(2) != 1 || lab.dims(0) != in.dims(0))
+      unsup_err(fn + ": only 1 x 1 planes (in img:chan:1:1, label img:1:1): the reference reads label by image");
+    if (lab.tn != "float") rt_err(fn + ": label has type " + lab.tn + ": the loss's own var is float");
+    r.B = in.dims(0); r.C = in.dims(1);
+    if (r.B < 1 || r.C < 1) rt_err(fn + ": empty in");
+    if (4.0 * (double)r.B * (double)r.C >= 2147483648.0) unsup_err(fn + ": tensors of 2 GiB or more (32-bit element offsets)");
+    vec("rank", "uint32_t", "img", r.B, "one word per image");
+  } else if (r.kind == 2) {
+    r.B = vec("rank", "uint32_t", "img", 0, "one word per image");
+    dims_t const &lo = op.get_dims("loss");
+    if (lo.tn != "float" || lo.sz() != 2 || lo.names(0) != "y" || lo.names(1) != "x" || lo.dims(0) != 1 || lo.dims(1) != 1) rt_err(fn + ": loss must be float y=1:x=1 (the pipe's loss node), got " + lo.tn + " " + lo.pretty_str());
+    vec("ctl", "uint32_t", "v", 4, "first, 0, 0, 0"); vec("counts", "uint32_t", "v", 4, "images, hits_top1, hits_topk, batches"); vec("loss_sum", "float", "v", 1, "the sum of the batches' losses");
+    if (!op.has("top_k")) rt_err(fn + ": the op has no 'top_k'");
+    r.top_k = op.get_u32("top_k");
+    if (r.top_k < 1) rt_err(fn + ": top_k=0: top_k must be at least 1");
+  } else {
+    r.C = vec("run_mean", "float", "chan", 0, "one float per channel");
+    for (string const &an : r.args) vec(an, "float", "chan", r.C, "one float per channel");
+    if (!op.has("eps")) rt_err(fn + ": the op has no 'eps'");
+    p_nda_t const &v = op.get("eps"); if (v->dims.tn != "float" || v->dims.sz() != 0 || !v->rp) rt_err(fn + ": 'eps' is not a float scalar");
+    r.eps = *static_cast<float const *>(v->rp);
+    if (!(r.eps >= 0.0f)) rt_err(fn + ": eps must not be negative");
+  }
+  return r;
 }
 
 // ---- rtc layer ----------------------------------------------------------------------------------------------------

@@ -288,13 +288,20 @@ OP_INFO = {
     "BnBckSums": (("in", "mean", "inv_std", "out_grad_loss"), ("scale_grad_loss", "bias_grad_loss"), ("slab",)),
     "BnBckIn": (("in", "mean", "inv_std", "scale", "scale_grad_loss", "bias_grad_loss", "out_grad_loss"), ("in_grad_loss",), ()),
     "FanOut": (("in",), (), ("outs_num",)),
+    # this backend's own: the evaluation pass of the gradient pipe (csrc/kernels/eval_f32.hip states the rules).  Accuracy: the rank of the true class per image from the
+    # logits and the loss's label var.  EvalAccum: the batch's counts and loss into counts (uint32 v=4) / loss_sum (float v=1), which it reads and rewrites, under ctl (uint32
+    # v=4 = first, 0, 0, 0).  BnFold: a [BatchNorm, Scale] run's running statistics and scale / bias as the pair (a, b) of conv_pipe.fold_affine
+    "Accuracy": (("in", "label"), ("rank",), ()),
+    "EvalAccum": (("rank", "loss", "ctl"), ("counts", "loss_sum"), ("top_k",)),
+    "BnFold": (("run_mean", "run_var", "scale", "bias"), ("a", "b"), ("eps",)),
 }
 BN_TYPES = ("BnStats", "BnFwd", "BnBckSums", "BnBckIn", "FanOut")
 SOLVER_TYPES = ("SolverUpdate", "GradSumsq", "GradNorm", "GradAccum", "SolverUpdateAcc")
+EVAL_TYPES = ("Accuracy", "EvalAccum", "BnFold")
 SOLVER_CHUNK = 4096   # floats of one tensor a workgroup owns; one partial sum of squares per chunk
 
 
-_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + SOLVER_TYPES
+_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + SOLVER_TYPES + EVAL_TYPES
 
 
 @dataclass
@@ -598,6 +605,46 @@ class Op:
                 raise RtErr(f"GradSumsq: part0={self.get_u32('part0')} + {chunks} chunks exceed the {parts} partials")
         return dict(n=n, elems=elems, chunks=chunks)
 
+    def eval_geom(self) -> dict:
+        """Accuracy: in float img:chan:1:1, label float img:1:1, rank uint32_t img.  EvalAccum: rank uint32_t img, loss float y=1:x=1, ctl and counts uint32_t v=4, loss_sum
+        float v=1, top_k >= 1.  BnFold: six float chan=C vectors, eps >= 0."""
+        t = self.get_type()
+        ins, outs, req = OP_INFO[t]
+        for an in ins + outs + req:
+            if not self.has(an):
+                raise RtErr(f"{t}: the op has no {an!r}")
+
+        def vec(an, tn, dn, n):
+            d = self.get_dims(an)
+            if d.tn != tn or d.names != (dn,) or (d.sizes[0] != n if n else d.sizes[0] < 1):
+                raise RtErr(f"{t}: {an} must be {tn} {dn}={n or '<n>'}, got {d.tn} {d.pretty()}")
+            return d.sizes[0]
+        if t == "Accuracy":
+            i, lab = self.get_dims("in"), self.get_dims("label")
+            if i.names != ("img", "chan", "y", "x") or i.tn != "float":
+                raise RtErr(f"Accuracy: in must be float img:chan:y:x, got {i.tn} {i.pretty()}")
+            if (i.dsz("y"), i.dsz("x")) != (1, 1) or lab.names != ("img", "y", "x") or lab.sizes != (i.dsz("img"), 1, 1):
+                raise UnsupErr("Accuracy: only 1 x 1 planes (in img:chan:1:1, label img:1:1): the reference reads label by image")
+            if lab.tn != "float":
+                raise RtErr(f"Accuracy: label has type {lab.tn}: the loss's own var is float")
+            vec("rank", "uint32_t", "img", i.dsz("img"))
+            return dict(B=i.dsz("img"), C=i.dsz("chan"))
+        if t == "EvalAccum":
+            B = vec("rank", "uint32_t", "img", 0)
+            lo = self.get_dims("loss")
+            if lo.tn != "float" or lo.names != ("y", "x") or lo.sizes != (1, 1):
+                raise RtErr(f"EvalAccum: loss must be float y=1:x=1, got {lo.tn} {lo.pretty()}")
+            vec("ctl", "uint32_t", "v", 4); vec("counts", "uint32_t", "v", 4); vec("loss_sum", "float", "v", 1)
+            if self.get_u32("top_k") < 1:
+                raise RtErr("EvalAccum: top_k=0: top_k must be at least 1")
+            return dict(B=B, top_k=self.get_u32("top_k"))
+        C = vec("run_mean", "float", "chan", 0)
+        for an in ins + outs:
+            vec(an, "float", "chan", C)
+        if not self.get("eps").v[0] >= 0.0:
+            raise RtErr("BnFold: eps must not be negative")
+        return dict(C=C)
+
     def bn_geom(self) -> dict:
         """BnStats / BnFwd / BnBckSums / BnBckIn: float img:chan:y:x tensors of equal dims, the per-channel args float chan=C; FanOut: in and 2 to 8 outs of equal float dims."""
         t = self.get_type()
@@ -744,6 +791,8 @@ def parse_op(line: str) -> Op:
             op.bn_geom()
         elif t in SOLVER_TYPES:
             op.solver_geom()
+        elif t in EVAL_TYPES:
+            op.eval_geom()
         else:
             op.sgemm_geom()
     return op

@@ -3,7 +3,7 @@
 Restates what the reference's net reader needs for this path (src/caffepb.cc:166-326, src/conv_util.cc:405-529):
 TEST-phase layers only; Convolution out = (in + 2*pad - k)/stride + 1 (floor); Pooling uses ceil and `global_pooling`;
 Concat sums channels; ReLU / LRN / Dropout / BatchNorm / Scale / Eltwise keep the shape; InnerProduct is a convolution
-whose kernel is the whole input; Accuracy / Softmax* / loss layers are ignored.  Every Convolution gets a bias input
+whose kernel is the whole input; Accuracy / Softmax* / loss layers are ignored (accuracy_layers lists the Accuracy ones).  Every Convolution gets a bias input
 (the reference always attaches `<name>_biases`, src/caffepb.cc:227-228, even when the prototxt says bias_term: false).
 Only the subset of the text format that net definitions use is parsed: `key: value` and `key { ... }`.
 """
@@ -240,3 +240,56 @@ def solver_spec(text: str):
     sv = Solver(type=table[name], lr=num("base_lr", None), momentum=num("momentum", 0.0), momentum2=num("momentum2", 0.999), delta=num("delta", 1e-8),
                 weight_decay=num("weight_decay", 0.0), clip_gradients=clip if clip > 0 else 0.0, lr_policy=policy)
     return sv, iter_size, {k: v for k, v in d.items() if k not in _SOLVER_KEYS}
+
+
+def test_spec(text: str) -> dict:
+    """The test keys of a Caffe solver.prototxt -> {"test_iter", "test_interval", "test_initialization"}: how many batches an evaluation runs (EvalPipe.evaluate's
+    n_batches), every how many updates, and whether one runs before the first update.  Absent keys get Caffe's defaults: no test_iter -> 0 (test_iter is repeated, one
+    per test net: the first is taken), test_interval 0, test_initialization true.  solver_spec keeps handing these keys back in `ignored`; the caller's loop drives the
+    interval."""
+    d = parse(text)
+    for k in ("test_iter", "test_interval", "test_initialization"):
+        if any(isinstance(v, dict) for v in d.get(k, [])):
+            raise RtErr(f"solver prototxt: {k!r} must be a value, not a block")
+    for k in ("test_interval", "test_initialization"):
+        if len(d.get(k, [])) > 1:
+            raise RtErr(f"solver prototxt: {k!r} is given {len(d[k])} times")
+
+    def count(k):
+        v = _one(d, k, "0")
+        try:
+            n = int(v)
+        except ValueError:
+            raise RtErr(f"solver prototxt: {k}: {v!r} is not an integer")
+        if n < 0:
+            raise RtErr(f"solver prototxt: {k}={n}: not negative")
+        return n
+    ti = str(_one(d, "test_initialization", "true")).lower()
+    if ti not in ("true", "false"):
+        raise RtErr(f"solver prototxt: test_initialization: {ti!r} is neither true nor false")
+    return {"test_iter": count("test_iter"), "test_interval": count("test_interval"), "test_initialization": ti == "true"}
+
+
+def accuracy_layers(text: str) -> List[Tuple[str, str, str, int]]:
+    """-> [(name, bottom, label, top_k)] of a net definition's Accuracy layers, in definition order (a TRAIN-phase-only layer is left out): what to score (the blob an
+    EvalPipe's loss reads) and under which k.  top_k defaults to 1 (AccuracyParameter, src/ext/caffe.proto).  ignore_label and an axis other than 1 are an UnsupErr
+    that names the key.  The shape-inference readers above keep ignoring these layers."""
+    from .op import UnsupErr
+    root = parse(text)
+    out: List[Tuple[str, str, str, int]] = []
+    for L in root.get("layer", []) or root.get("layers", []):
+        if not _is_test_phase(L) or str(_one(L, "type")).upper().replace("_", "") != "ACCURACY":
+            continue
+        name, bots = str(_one(L, "name")), L.get("bottom", [])
+        if len(bots) != 2:
+            raise RtErr(f"prototxt: Accuracy layer {name!r} has {len(bots)} bottoms: the scores and the label")
+        ap = _one(L, "accuracy_param", {})
+        if "ignore_label" in ap:
+            raise UnsupErr(f"prototxt: Accuracy layer {name!r}: ignore_label is not provided (hip_accuracy counts every image; a label outside [0, chan) is a miss)")
+        if int(_one(ap, "axis", 1)) != 1:
+            raise UnsupErr(f"prototxt: Accuracy layer {name!r}: axis={_one(ap, 'axis')}: only axis 1, the channels, is provided")
+        k = int(_one(ap, "top_k", 1))
+        if k < 1:
+            raise RtErr(f"prototxt: Accuracy layer {name!r}: top_k={k}: at least 1")
+        out.append((name, str(bots[0]), str(bots[1]), k))
+    return out

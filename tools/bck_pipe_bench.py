@@ -10,6 +10,7 @@ and the share of the step each native function takes (sums of the backend's per-
     python tools/bck_pipe_bench.py --sgd [--repeats 3] [--out profiles/r13_sgd_update.txt]
     python tools/bck_pipe_bench.py --nets resnet50 --batch 32 [--limit 900] [--out profiles/r14_resnet50_step.txt]
     python tools/bck_pipe_bench.py --grad-operands bf16 --nets resnet50 --batch 32 [--repeats 3] [--limit 900] [--out profiles/r16_step_bf16.txt]
+    python tools/bck_pipe_bench.py --eval 8 [--nets nin,alexnet] [--repeats 3] [--out profiles/r20_eval.txt]
     python tools/bck_pipe_bench.py --img-chunks 2 --nets resnet50 --batch 32 [--devices 0:0] [--repeats 3] [--limit 900] [--out profiles/r17_resnet50_chunks.txt]
 
 --fuse-relu-grad: the same step both ways in ONE process -- ConvPipeBck() and ConvPipeBck(fuse_relu_grad=True), each on a backend instance of its own with the same
@@ -46,6 +47,11 @@ kernel.  Several invocations go to one file by hand (profiles/r18_solver.txt); n
 --iter-size N (with --solver): the two legs are the Solver's step with iter_size=1 and with iter_size=N of the same build: every pass then runs
 hip_grad_accum (12 B per element) and, when clipping, the norm over the accumulators; hip_solver_update_acc's us and GB/s are those of the passes that apply
 (us_not_applying: the others).  --runs should be a multiple of N.  Written to profiles/r19_grad_accum.txt.
+
+--eval N: the training step (hip_sgd_update) and the evaluation pass of eval_pipe.EvalPipe(top_k=5) over the SAME vars, in ONE process: --repeats
+alternating blocks of --runs training steps and N eval batches, all eager.  Per net one JSON line: ms per training step and ms per eval batch (medians over all blocks,
+and the block medians), their quotient, the call counts, the us per batch of hip_accuracy, hip_eval_accum and (summed over its calls) hip_bn_fold, and the last block's
+result().  Written to profiles/r20_eval.txt.  No figure is required.
 
 --devices d0:d1:...: the plain step on the multi-device backend `(be=hip,devices=...)`: the batch sharded on img, the five functions that are not independent per image
 run with img_shards=1.  Step ms is the longest of the devices' times; a call's share counts the time its device-side launches took, not the
@@ -328,6 +334,56 @@ def solver_ab(net, batch, runs, warmup, repeats, solver_type, clip, swap=False, 
         w["drv"].release(); w["rtc"].close()
 
 
+def eval_ab(net, batch, runs, warmup, repeats, n_eval):
+    """--eval: alternating blocks of `runs` training steps and `n_eval` evaluation batches of an EvalPipe over the same driver, one process."""
+    import numpy as np
+    from boda_amd.bck_pipe import ConvPipeBck, SgdSolver, add_bck_ops, host_params
+    from boda_amd.eval_pipe import EvalPipe
+    from boda_amd.rtc import make_rtc
+    cp = _pipe(net, batch)
+    bp = add_bck_ops(cp)
+    rng = np.random.default_rng(0)
+    data = rng.uniform(-1, 1, cp.nodes["data"].sizes).astype(np.float32)
+    label = rng.integers(0, 1000, (batch, 1, 1)).astype(np.float32)
+    rtc = make_rtc("(be=hip)", 0)
+    rtc.init()
+    drv = ConvPipeBck(rtc, solver=SgdSolver(lr=1e-5, momentum=0.9, weight_decay=5e-4, lr_mult={"biases": 2.0}, decay_mult={"biases": 0.0}))   # (a rate at which random labels keep every value finite)
+    drv.init(bp, host_params(bp, 5))
+    ev = EvalPipe(drv, top_k=5)
+    rtc.copy_nda_to_var("data", data); rtc.copy_nda_to_var("label", label)
+    for i in range(warmup):
+        drv.set_det_drop_seed(i); drv.run_device_only()
+        ev.run_device_only()
+    step_ms, eval_ms, step_blocks, eval_blocks, fn_us = [], [], [], [], {}
+    for rep in range(repeats):
+        ms = []
+        for i in range(runs):
+            drv.set_det_drop_seed(warmup + rep * runs + i)
+            ms.append(drv.run_device_only())
+        step_ms += ms; step_blocks.append(round(statistics.median(ms), 3))
+        ev.reset()
+        ms = []
+        for i in range(n_eval):
+            ms.append(ev.run_device_only())
+            for fn in ("hip_accuracy", "hip_eval_accum", "hip_bn_fold", "hip_chan_affine"):
+                ds = [d for _, f, d in ev.per_call_ms if f == fn]
+                if ds:
+                    fn_us.setdefault(fn, []).append(sum(ds) * 1e3)
+        eval_ms += ms; eval_blocks.append(round(statistics.median(ms), 3))
+    res = ev.result()
+    loss = float(rtc.copy_var_to_nda("loss").item())
+    if not np.isfinite(loss) or res["batches"] != n_eval or res["images"] != n_eval * batch:
+        raise SystemExit(f"{net}: loss {loss}, result {res}")
+    st, et = statistics.median(step_ms), statistics.median(eval_ms)
+    n_of = lambda fn: sum(1 for _, f, _ in ev.calls() if f.get_func_name() == fn)
+    print(json.dumps({"net": net, "batch": batch, "eval_batches_per_block": n_eval, "step_calls": len(drv.calls()), "eval_calls": len(ev.calls()), "step_ms": round(st, 3),
+                      "eval_batch_ms": round(et, 3), "eval_over_step": round(et / st, 4), "step_block_medians_ms": step_blocks, "eval_block_medians_ms": eval_blocks,
+                      "imgs_per_s_training": round(batch / (st * 1e-3), 1), "imgs_per_s_eval": round(batch / (et * 1e-3), 1),
+                      "eval_functions": {fn: {"calls": n_of(fn), "us_per_batch": round(statistics.median(v), 1)} for fn, v in fn_us.items()},
+                      "result": {k: (round(v, 6) if isinstance(v, float) else v) for k, v in res.items()}}), flush=True)
+    ev.release(); drv.release(); rtc.close()
+
+
 def one_net(net, batch, runs, warmup, devices="", img_chunks=0, raw=False):
     import numpy as np
     from boda_amd import conv_pipe
@@ -414,6 +470,7 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=3, help="with --fuse-relu-grad / --graph / --sgd: alternating blocks of --runs steps per way")
     ap.add_argument("--devices", default="", help="e.g. 0:1:2:3: the plain step on the multi-device backend (be=hip,devices=...), batch sharded on img")
     ap.add_argument("--img-chunks", type=int, default=0, help="A/B, one process per leg: the default step, img_chunks=1, img_chunks=N on one device and, with --devices, on the multi-device backend")
+    ap.add_argument("--eval", type=int, default=0, dest="n_eval", help="alternating blocks of --runs training steps and N evaluation batches (eval_pipe.EvalPipe) in one process: ms per eval batch beside ms per step")
     ap.add_argument("--raw", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--child", default="")
     a = ap.parse_args(argv)
@@ -427,12 +484,18 @@ def main(argv=None):
         ap.error("--graph, --fuse-relu-grad, --fuse-filts-biases, --grad-operands, --sgd and --solver are six comparisons: run them one at a time")
     if a.solver and (a.devices or a.img_chunks):
         ap.error("--solver is a comparison of its own on one device")
+    if a.n_eval and (a.graph or a.fuse_relu_grad or a.sgd or a.fuse_filts_biases or a.grad_operands or a.solver or a.devices or a.img_chunks):
+        ap.error("--eval is a comparison of its own on one device")
+    if a.n_eval < 0:
+        ap.error("--eval N: at least 1 batch")
     if a.clip and not a.solver:
         ap.error("--clip goes with --solver")
     if a.iter_size != 1 and (not a.solver or a.iter_size < 1):
         ap.error("--iter-size goes with --solver and is at least 1")
-    a.out = a.out or os.path.join(ROOT, "profiles", "r17_resnet50_chunks.txt" if a.img_chunks else "r16_step_bf16.txt" if a.grad_operands else "r19_grad_accum.txt" if a.solver and a.iter_size > 1 else "r18_solver.txt" if a.solver else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r20_eval.txt" if a.n_eval else "r17_resnet50_chunks.txt" if a.img_chunks else "r16_step_bf16.txt" if a.grad_operands else "r19_grad_accum.txt" if a.solver and a.iter_size > 1 else "r18_solver.txt" if a.solver else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
     if a.child:
+        if a.n_eval:
+            return eval_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, a.n_eval)
         if a.grad_operands:
             return operands_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, a.grad_operands)
         if a.solver:
@@ -461,6 +524,7 @@ def main(argv=None):
         cmd += ["--sgd", "--repeats", str(a.repeats)] if a.sgd else []
         cmd += ["--solver", a.solver, "--clip", str(a.clip), "--repeats", str(a.repeats)] + (["--swap"] if a.swap else []) + (["--iter-size", str(a.iter_size)] if a.iter_size > 1 else []) if a.solver else []
         cmd += ["--devices", a.devices] if a.devices else []
+        cmd += ["--eval", str(a.n_eval), "--repeats", str(a.repeats)] if a.n_eval else []
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:   # nothing more is started on the GPU after a failure
             print(f"{net}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
@@ -468,7 +532,7 @@ def main(argv=None):
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
         print("\n".join(lines[-4:] if (a.graph or a.sgd or a.grad_operands) else lines[-3:] if (a.fuse_relu_grad or a.fuse_filts_biases or a.solver) else lines[-1:]), flush=True)
     with open(a.out, "w") as f:
-        extra = f" --img-chunks {a.img_chunks}{' --devices ' + a.devices if a.devices else ''} --repeats {a.repeats}" if a.img_chunks else f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --solver {a.solver} --clip {a.clip}{' --swap' if a.swap else ''}{f' --iter-size {a.iter_size}' if a.iter_size > 1 else ''} --repeats {a.repeats}" if a.solver else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
+        extra = f" --eval {a.n_eval} --repeats {a.repeats}" if a.n_eval else f" --img-chunks {a.img_chunks}{' --devices ' + a.devices if a.devices else ''} --repeats {a.repeats}" if a.img_chunks else f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --solver {a.solver} --clip {a.clip}{' --swap' if a.swap else ''}{f' --iter-size {a.iter_size}' if a.iter_size > 1 else ''} --repeats {a.repeats}" if a.solver else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
         f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 
