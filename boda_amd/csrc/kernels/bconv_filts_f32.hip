@@ -10,7 +10,8 @@
 // tile's last ticket resets it and sums the KSL slabs in slice order.  No float atomics, no workgroup waits on another: run-to-run deterministic, and the
 // same bits for every tile shape that cuts K at the same places -- the same slice count AND the same slice length kt_per * BK, with nkt = ceil(K / BK) and
 // kt_per = ceil(nkt / KSL) (K = 300, KSL = 3: slices of 128 at BK = 32, of 112 at BK = 16 -- different bits; BI, BJ and the waves never matter).  KSL = 1 is the
-// reference template's single sequential chain bit for bit (the skipped border terms are fma(g, 0, acc) on finite data); KSL > 1 is a different association:
+// reference template's single sequential chain bit for bit (the skipped border terms are fma(g, 0, acc) on finite data; a NaN / Inf in out_grad_loss makes them
+// NaNs inside that out_chan's filter row, and a -0 accumulator becomes +0 under them and under the K tail's fma(0, 0, acc): DESIGN.md section 3.11a); KSL > 1 is a different association:
 // result = slab[0] + slab[1] + ... + slab[KSL-1], slab s = the chain from +0 over slice s, an empty slice (kt0 == kt1) a slab of +0.  Both are held to the CPU
 // emulation of exactly this (oracle/bck_chain.py) by tests/test_gpu_bck_chain.py.
 //

@@ -11,8 +11,13 @@
 //
 // Numerics: v_mfma_f32_32x32x2_f32 is an exact fp32 fma chain in ascending k, so every output is ONE fma chain in exactly the order of the reference's
 // template (test/rtc/BckConv_in_grad_loss.cucl: out_chan, then out_x, then out_y; the filter taps run descending) -- bit-identical to it.  The extra terms
-// (borders, taps outside the kernel) are fma(0, w, acc) or fma(g, 0, acc), which equal acc for FINITE data: the accumulator starts at +0 and never becomes -0.
-// An inf / nan in filts or out_grad_loss would poison padded terms the reference never forms (the same caveat as the forward kernels' K tail).
+// (borders, taps outside the kernel, the K tail past OC * TY * TX) are fma(0, w, acc), fma(g, 0, acc) or fma(0, 0, acc), which equal acc for FINITE data up to the
+// sign of a zero.  The accumulator starts at +0 but does become -0: a negative product that underflows gives fma(g, w, +0) = -0, and it stays -0 through further
+// such terms.  A padded term fma(+0, w, -0) with w > 0, or any K-tail term, then gives +0 where the reference, which skips the term, keeps -0 -- equal by value,
+// not by bits (oracle/bck_chain.in_grad_chain forms the same terms; the directed case of tests/test_gpu_bck_special.py shows both signs).
+// An inf / nan in out_grad_loss poisons the padded terms the reference never forms: every pel of the element's PHASE WINDOW y + PY - oy*SY in [0, SY*TY) (likewise x)
+// comes back as a NaN, not only the pels of its kernel window [0, KH) -- measured: all of them, on every strided form whose stride does not divide the kernel size;
+// outside the phase window nothing changes.  An inf / nan in filts is contained in its in_chan.
 //
 // -DZINP=1 (the function op's zero_if_in_non_pos): the ReLU gradient that follows this launch in a gradient pipe, folded into the store --
 //   in_grad_loss[e] = in[e] > 0 ? g[e] : +0,   g[e] the value above, `in` (p.zin) the convolution's forward input, which has in_grad_loss's dims:

@@ -4,8 +4,11 @@ numpy index arithmetic + the oracle's sgemm (an ascending-k fmaf chain from +0 p
 association WRITTEN DOWN in a kernel's header (boda_amd/csrc/kernels/bconv_filts_f32.hip, bconv_in_f32.hip) and asks nothing of the code under test: tile depth
 and slice count are inputs.  `geom` is Op.bck_conv_geom(): B C H W OC KH KW SY SX PY PX OH OW (the forward convolution's geometry).
 
-The operands are plain gathers with +0.0 where the kernels read out of bounds; a zero term is fma(a, 0, acc) = acc for finite data (the accumulators start at +0
-and never become -0), so the zero-padded chains carry the bits of the chains without those terms.
+The operands are plain gathers with +0.0 where the kernels read out of bounds; a zero term is fma(a, 0, acc) = acc for finite data as long as acc is not -0, so the
+zero-padded chains carry the bits of the chains without those terms -- up to the sign of a zero: an accumulator becomes -0 when a negative product underflows
+(fma(a, b, +0) rounds to -0), and a padded term fma(+0, w, -0) with w > 0 makes it +0 again.  The K tail does the same: a kernel runs whole K steps of BK terms, and
+the terms past K are fma(+0, +0, acc), which turn a -0 into +0 and change nothing else.  filts_sliced_chain forms them where a slice ends in a partial K step;
+in_grad_chain forms them when it is given the K step `bk` of the launch.
 """
 from __future__ import annotations
 import numpy as np
@@ -50,7 +53,10 @@ def filts_sliced_chain(I, J, BK, KSL, dims=None):
     acc = None
     for k0, k1 in filts_slices(K, BK, KSL):
         slab = bo.sgemm(I[k0:k1], J[k0:k1]) if k1 > k0 else np.zeros((OC, J.shape[1]), f32)
-        acc = slab if acc is None else (acc + slab).astype(f32, copy=False)
+        if (k1 - k0) % BK:   # the slice ends in the K tail: fma(+0, +0, acc) terms (a -0 becomes +0, a NaN stays)
+            slab = slab + f32(0.0)
+        with np.errstate(invalid="ignore", over="ignore"):   # (slabs that overflow, slabs of +Inf and -Inf: the Inf and the NaN are the kernel's too)
+            acc = slab if acc is None else (acc + slab).astype(f32, copy=False)
     return acc.reshape(dims) if dims is not None else acc
 
 
@@ -78,11 +84,12 @@ def biases_chain(g):
     return red[:, 0].copy()
 
 
-def in_grad_chain(w, g, geom):
+def in_grad_chain(w, g, geom, bk=0):
     """The data gradient as ONE chain per output in the reference template's order: k = (out_chan, out_x, out_y) ascending, the filter taps descending with them.
     Per phase (ry, rx) = ((y + PY) % SY, (x + PX) % SX) every pel meets the same TY x TX window of taps: out position (qy - (TY-1) + ty, qx - (TX-1) + tx) with
     q = (pel + pad) / stride, tap (ry + SY*(TY-1-ty), rx + SX*(TX-1-tx)).  Explicit operands with +0.0 where the out position or the tap does not exist, one
-    oracle sgemm per phase and image.  w = filts[OC, C, KH, KW], g = out_grad_loss[B, OC, OH, OW] -> in_grad_loss[B, C, H, W]."""
+    oracle sgemm per phase and image.  bk: the K step of the launch; where OC * TY * TX is no multiple of it the chain ends in K-tail terms fma(+0, +0, acc).
+    w = filts[OC, C, KH, KW], g = out_grad_loss[B, OC, OH, OW] -> in_grad_loss[B, C, H, W]."""
     B, C, H, W, OC, KH, KW, SY, SX, PY, PX, OH, OW = (geom[k] for k in ("B", "C", "H", "W", "OC", "KH", "KW", "SY", "SX", "PY", "PX", "OH", "OW"))
     w = np.asarray(w, f32).reshape(OC, C, KH, KW); g = np.asarray(g, f32).reshape(B, OC, OH, OW)
     TY, TX = -(-KH // SY), -(-KW // SX)
@@ -105,5 +112,7 @@ def in_grad_chain(w, g, geom):
             for img in range(B):
                 gp = gz[img][:, oy[None, :, :, None], ox[:, None, None, :]]    # (OC, TX, TY, ny, nx)
                 r = bo.sgemm(a, np.ascontiguousarray(gp).reshape(OC * TX * TY, len(ys) * len(xs)))
+                if bk and (OC * TX * TY) % bk:
+                    r = r + f32(0.0)
                 out[img][:, ys[:, None], xs[None, :]] = r.reshape(C, len(ys), len(xs))
     return out
