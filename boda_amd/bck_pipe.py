@@ -25,7 +25,9 @@ import numpy as np
 
 from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, bnc_bck_in_func_op, bnc_bck_sums_func_op, bnc_fwd_func_op, bnc_stats_func_op, BNC_MAX_CHUNKS, fan_out_func_op, sgd_update_func_op, solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op, grad_accum_func_op, solver_update_acc_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
                      pipe_func_args, seed_from_var, SEED_VAR_ARG, bf16_operands)
+from .cnn_op import data_transform_func_op
 from .conv_pipe import ConvPipe, PipeOp
+from .input_pipe import DATA_RAW_VAR, DATA_XF_MEAN_VAR, DATA_XF_PLAN_VAR, DATA_XF_TAG, InputTransform
 from .op import Dims, Nda, Op, RtErr, SOLVER_CHUNK, UnsupErr
 from .rtc import RtcArg, RtcFuncCall, RtcFuncInfo
 
@@ -521,11 +523,23 @@ class ConvPipeBck:
     are unchanged.  On one device and on be=cpu any n is allowed, and n=1 leaves today's bits in every node; on `(be=hip,devices=...)` n must be the device count (RtErr
     before anything is created) and the pipe then runs there: every node but the convolutions' filter / bias gradients (summed per shard, section 3.13) holds the bits of
     the one-device step with the same n.  fuse_relu_grad, seed_in_var, solver= and, on one device, capture_graph work as before; fuse_filts_biases and grad_operands
-    stay refused on a multi-device backend."""
+    stay refused on a multi-device backend.
+    input_transform=InputTransform(...) (opt-in; None leaves the vars, calls() and every bit as they are): the step takes its input as uint8
+    images and crops, mirrors, subtracts the mean and scales on the device.  init creates data_raw (uint8, the batch at the source size in the transform's layout),
+    data_xf_plan (uint32 img:v=4) and data_xf_mean (uploaded once; set_input_mean uploads it again) and puts ONE call in front of the step's first, tagged data_xf:
+    hip_data_transform from data_raw into the pipe's input node.  run_bck(["data_raw", "label"], ...) uploads bytes.  Before every pass -- a micro-step of iter_size
+    included, eager or a replay -- the B x 16 bytes of the plan are uploaded: input_transform.plan("train", xf_images, B), or the plan set_input_plan gave for this one
+    pass, checked by check_plan; behind the pass xf_images advances by B.  The plan lives in a var, so one captured graph serves every pass.  Feeding the input node
+    itself is an RtErr: the call would overwrite it.  On a multi-device backend the call runs on the img shards of data_raw, data_xf_plan and the input node."""
 
     def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[object] = None, bn_maf: float = 0.999, fuse_filts_biases: bool = False,
-                 grad_operands: str = "", img_chunks: int = 0, iter_size: int = 1):
+                 grad_operands: str = "", img_chunks: int = 0, iter_size: int = 1, input_transform: Optional[InputTransform] = None):
         self.rtc = rtc
+        if input_transform is not None and not isinstance(input_transform, InputTransform):
+            raise RtErr(f"ConvPipeBck: input_transform must be an input_pipe.InputTransform or None, got {type(input_transform).__name__}")
+        self.input_transform = input_transform
+        self.xf_images = 0           # the global index of the next pass's first image: what the train plan is made for
+        self._input_plan: Optional[np.ndarray] = None   # set_input_plan's, for one pass
         if not isinstance(iter_size, int) or isinstance(iter_size, bool) or iter_size < 1:
             raise RtErr(f"ConvPipeBck: iter_size must be an int >= 1, got {iter_size!r}")
         if iter_size > 1 and not isinstance(solver, Solver):
@@ -621,8 +635,21 @@ class ConvPipeBck:
             for vn in (x + BN_IN_SFX, bn.tag + BN_MEAN_SFX, bn.tag + BN_ISTD_SFX):
                 if vn in bp.nodes:
                     raise RtErr(f"ConvPipeBck.init: the BatchNorm on {x} needs the var name {vn!r}, which is a node of the pipe")
+        xf = self.input_transform
+        if xf is not None:   # (refused before anything is created)
+            dn = bp.cp.in_node; dd = bp.nodes[dn]
+            if dd.tn != "float" or dd.names != ("img", "chan", "y", "x") or (dd.dsz("y"), dd.dsz("x")) != (xf.ch, xf.cw):
+                raise RtErr(f"ConvPipeBck.init: input_transform crops to {xf.ch} x {xf.cw}: the pipe's input node {dn!r} must be float img:chan:y={xf.ch}:x={xf.cw}, got {dd.tn} {dd.pretty()}")
+            for vn in (DATA_RAW_VAR, DATA_XF_PLAN_VAR, DATA_XF_MEAN_VAR):
+                if vn in bp.nodes:
+                    raise RtErr(f"ConvPipeBck.init: input_transform needs the var name {vn!r}, which is a node of the pipe")
+            xf_mean = xf.mean_array(dd.dsz("chan"))
         for n, d in bp.nodes.items():
             self._var(n, d)
+        if xf is not None:
+            self._var(DATA_RAW_VAR, xf.src_dims(dd.dsz("img"), dd.dsz("chan")))
+            self._var(DATA_XF_PLAN_VAR, Dims(("img", "v"), (dd.dsz("img"), 4), "uint32_t"))
+            self._var(DATA_XF_MEAN_VAR, xf.mean_dims(dd.dsz("chan")))
         for x, (bn, sc, _) in bn_runs.items():
             self._var(x + BN_IN_SFX, bp.nodes[x])
             for sfx in (BN_MEAN_SFX, BN_ISTD_SFX):
@@ -665,6 +692,9 @@ class ConvPipeBck:
             self.bck_calls.append(BckCall(tag, fop, dict(args), RtcFuncCall(fname, am)))
             self.funcs.append(fname)
 
+        if xf is not None:   # in front of the step's first call: the input node from the bytes
+            emit(DATA_XF_TAG, data_transform_func_op(xf.src_dims(dd.dsz("img"), dd.dsz("chan")), (xf.ch, xf.cw), xf.mean_dims(dd.dsz("chan")), xf.scale),
+                 {"src": DATA_RAW_VAR, "plan": DATA_XF_PLAN_VAR, "mean": DATA_XF_MEAN_VAR, "out": dn})
         for o in ops:
             if o.tag in fused or o.tag in folds:
                 continue
@@ -823,6 +853,10 @@ class ConvPipeBck:
             if n not in params:
                 raise RtErr(f"ConvPipeBck.init: no value for param {n!r}")
             rtc.copy_nda_to_var(n, np.ascontiguousarray(params[n], np.float32).reshape(d.sizes))
+        if xf is not None:   # the mean once; a valid plan, so that a pass capture_graph runs on its own reads inside data_raw
+            rtc.copy_nda_to_var(DATA_XF_MEAN_VAR, xf_mean)
+            self.xf_images = 0; self._input_plan = None
+            rtc.copy_nda_to_var(DATA_XF_PLAN_VAR, xf.plan("train", 0, dd.dsz("img")))
         if self.seed_in_var:   # each layer's fixed offset, by value, once: from here on a new seed is four bytes into the var
             for c, k in self._dropout_calls():
                 c.rfc.arg_map["det_drop_seed"] = RtcArg.scalar((k * DROP_LAYER_STEP) & 0xFFFFFFFF, "uint32_t")
@@ -893,13 +927,48 @@ class ConvPipeBck:
         n, m = self.iter_size, self.micro
         return np.array([1.0 if m == 0 else 0.0, 1.0 if m == n - 1 else 0.0, np.float32(1.0 / n), m], np.float32)
 
+    # -- the input transform
+    def _xf_batch(self) -> int:
+        return self.bp.nodes[self.bp.cp.in_node].dsz("img")
+
+    def set_input_mean(self, mean) -> None:
+        """Upload data_xf_mean again: an array of the var's dims (chan, or chan:y:x at the source size, as the driver was built)."""
+        if self.input_transform is None:
+            raise RtErr("ConvPipeBck.set_input_mean: the driver was built without an input_transform")
+        d = self.input_transform.mean_dims(self.bp.nodes[self.bp.cp.in_node].dsz("chan"))
+        a = np.ascontiguousarray(mean, np.float32)
+        if a.shape != d.sizes:
+            raise RtErr(f"ConvPipeBck.set_input_mean: {DATA_XF_MEAN_VAR} is float {d.pretty()}, got shape {a.shape}")
+        self.rtc.copy_nda_to_var(DATA_XF_MEAN_VAR, a)
+
+    def set_input_plan(self, plan) -> None:
+        """The next pass -- one pass -- runs under this plan (uint32 (B, 4) = y_off, x_off, mirror, unused per image) instead of the train plan; checked here and
+        again before the upload.  xf_images advances behind that pass all the same."""
+        if self.input_transform is None:
+            raise RtErr("ConvPipeBck.set_input_plan: the driver was built without an input_transform")
+        self._input_plan = self.input_transform.check_plan(plan, self._xf_batch())
+
+    def _before_pass(self) -> None:
+        xf = self.input_transform
+        if xf is not None:
+            B = self._xf_batch()
+            plan = self._input_plan if self._input_plan is not None else xf.plan("train", self.xf_images, B)
+            self.rtc.copy_nda_to_var(DATA_XF_PLAN_VAR, xf.check_plan(plan, B))
+
+    def _after_pass(self) -> None:
+        if self.input_transform is not None:
+            self.xf_images += self._xf_batch()
+            self._input_plan = None
+
     def _before_update_step(self) -> None:
+        self._before_pass()
         if isinstance(self.solver, Solver):
             self._upload_solver_hyper()
             if self.iter_size > 1:
                 self.rtc.copy_nda_to_var(SOLVER_ACCUM_VAR, self.accum_words())
 
     def _after_update_step(self) -> None:
+        self._after_pass()
         if isinstance(self.solver, Solver):
             if self.iter_size > 1:   # `iter` counts updates: it advances behind the applying micro-step only
                 applied = self.micro == self.iter_size - 1
@@ -952,6 +1021,9 @@ class ConvPipeBck:
         rtc = self.rtc
         if graph and self._graph is None:
             raise RtErr("ConvPipeBck.run_bck(graph=True): no captured graph -- call capture_graph() first")
+        if self.input_transform is not None and self.bp.cp.in_node in to_set_vns:
+            raise RtErr(f"ConvPipeBck.run_bck: the driver was built with an input_transform: its {DATA_XF_TAG} call writes {self.bp.cp.in_node!r} from {DATA_RAW_VAR!r} on every "
+                        f"pass and would overwrite what is fed; feed {DATA_RAW_VAR!r} (uint8), or build the driver without input_transform")
         for v in to_set_vns:
             rtc.copy_nda_to_var(v, fwd[v])
         rtc.finish_and_sync()

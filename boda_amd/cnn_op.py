@@ -475,6 +475,30 @@ def bn_fold_func_op(chan: int, eps: float) -> Op:
     return a
 
 
+DATA_TRANSFORM_FUNC = "hip_data_transform"
+# the input transform of the gradient pipe, in a table of its own again: what a ConvPipeBck built with input_transform= puts in front of its step.  This backend's
+# own: csrc/kernels/data_f32.hip states the rule
+DATA_OP_FUNCS: Dict[str, tuple] = {"DataTransform": (DATA_TRANSFORM_FUNC,)}
+
+
+def data_transform_func_op(src_dims, crop_yx, mean_dims, scale: float) -> Op:
+    """-> the annotated function op of hip_data_transform: src (uint8_t img:y:x:chan or img:chan:y:x, `src_dims`), plan (uint32_t img:v=4 = y_off, x_off, mirror,
+    unused) and mean (`mean_dims`: float chan, or chan:y:x at the source size) read, out (float img:chan:y:x at the crop size `crop_yx`) written.  Per output element
+    (i, c, y, x): yo = min(plan[i][0], H - ch), xo = min(plan[i][1], W - cw), sy = yo + y, sx = xo + (plan[i][2] != 0 ? cw - 1 - x : x), out = ((float)src[i, sy, sx, c] -
+    mean[c] or mean[c, sy, sx]) * scale, two fp32 roundings.  scale rides in the op."""
+    from .op import Dims
+    if src_dims.tn != "uint8_t" or src_dims.names not in (("img", "y", "x", "chan"), ("img", "chan", "y", "x")):
+        raise RtErr(f"data_transform_func_op: src must be uint8_t img:y:x:chan or img:chan:y:x, got {src_dims.tn} {src_dims.pretty()}")
+    b, c = src_dims.dsz("img"), src_dims.dsz("chan")
+    a = Op({"type": "DataTransform"}, {"src": Nda(dims=src_dims, tn="uint8_t"), "plan": Nda(dims=Dims(("img", "v"), (b, 4), "uint32_t"), tn="uint32_t"),
+                                       "mean": Nda(dims=mean_dims, tn=mean_dims.tn),
+                                       "out": Nda(dims=Dims(("img", "chan", "y", "x"), (b, c, int(crop_yx[0]), int(crop_yx[1])), "float"), tn="float"),
+                                       "scale": Nda(None, "float", (_as_f32(scale),))})
+    a.data_geom()
+    a.set_func_name(DATA_TRANSFORM_FUNC)
+    return a
+
+
 # the training BatchNorm of the gradient pipe and the Eltwise-SUM gradient, in a table of their own (PIPE_OP_FUNCS is pinned): what bck_pipe.ConvPipeBck runs for a
 # BatchNorm + Scale (+ ReLU) run and its gradient, and for a BckEltwise.  This backend's own arithmetic: csrc/kernels/bn_f32.hip and DESIGN.md section 3.15 state it
 BN_OP_FUNCS: Dict[str, tuple] = {
@@ -764,6 +788,8 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_accuracy": (("in", "IN"), ("label", "IN"), ("rank", "OUT")),
     "hip_eval_accum": (("rank", "IN"), ("loss", "IN"), ("ctl", "IN"), ("counts", "INOUT"), ("loss_sum", "INOUT")),
     "hip_bn_fold": (("run_mean", "IN"), ("run_var", "IN"), ("scale", "IN"), ("bias", "IN"), ("a", "OUT"), ("b", "OUT")),
+    # the input transform (this backend's own; scale rides in the op)
+    "hip_data_transform": (("src", "IN"), ("plan", "IN"), ("mean", "IN"), ("out", "OUT")),
     # the training BatchNorm and the Eltwise-SUM gradient (this backend's own; eps / maf / slab / relu ride in the op).  hip_fan_out's list depends on the op: in,
     # then outs_0 .. outs_{n-1} (pipe_func_args)
     "hip_bn_stats": (("in", "IN"), ("mean", "OUT"), ("inv_std", "OUT"), ("run_mean", "INOUT"), ("run_var", "INOUT")),

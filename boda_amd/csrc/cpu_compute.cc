@@ -461,6 +461,26 @@ void bn_fold(float const *run_mean, float const *run_var, float const *scale, fl
     a[c] = av; b[c] = sb + bi;
   }
 }
+// ---- the data family (kernels/data_f32.hip states the rule): the same clamps, the same two fp32 roundings; OpenMP over images
+void data_transform(data_op_t const &d, unsigned char const *src, uint32_t const *plan, float const *mean, float *out) {
+  long const B = d.B, C = d.C, H = d.H, W = d.W, ch = d.ch, cw = d.cw;
+  float const scale = d.scale;
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < B; ++i) {
+    uint32_t const *const pl = plan + i * 4;
+    uint32_t const ymax = (uint32_t)(H - ch), xmax = (uint32_t)(W - cw);
+    long const yo = pl[0] < ymax ? pl[0] : ymax, xo = pl[1] < xmax ? pl[1] : xmax;
+    bool const m = pl[2] != 0u;
+    for (long c = 0; c < C; ++c) for (long y = 0; y < ch; ++y) for (long x = 0; x < cw; ++x) {
+      long const sy = yo + y, sx = xo + (m ? cw - 1 - x : x);
+      long const si = d.chw ? ((i * C + c) * H + sy) * W + sx : ((i * H + sy) * W + sx) * C + c;
+      float const mu = d.mean_pel ? mean[(c * H + sy) * W + sx] : mean[c];
+      float const v = (float)src[si];
+      float const dv = v - mu;
+      out[((i * C + c) * ch + y) * cw + x] = dv * scale;
+    }
+  }
+}
 #pragma GCC pop_options
 } // namespace
 
@@ -537,6 +557,7 @@ struct cpu_compute_t : public rtc_compute_t {
       if (f->family == kFamBn || f->family == kFamBnc) (void)bn_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamSolver) (void)solver_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamEval) (void)eval_op_of_op(fi.op);   // (likewise)
+      if (f->family == kFamData) (void)data_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamBckOp) {
         if (!f->of_type(fi.op.get_type())) rt_err(fn + ": a function of op type " + f->types[0] + ", not " + fi.op.get_type());
         bck_op_args_t const a = bck_op_args(*f, fi.op);
@@ -956,6 +977,32 @@ struct cpu_compute_t : public rtc_compute_t {
     else bn_fold((float const *)P[0], (float const *)P[1], (float const *)P[2], (float const *)P[3], (float *)P[4], (float *)P[5], e.C, e.eps);
   }
 
+  // the data family: the checks of be=hip (csrc/native_run.cc), then the twin above
+  void run_data(op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = op.get_func_name();
+    data_op_t d = data_op_of_op(op);
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    std::vector<void *> P; long n_img = -1;
+    for (string const &an : d.args) {
+      string const vn = var_of(am, an);
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      dims_t const vd = get_var_dims(vn);
+      dims_t want = op.get_dims(an);
+      if (vd.tn != want.tn) rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ", the op says " + want.tn);
+      if (an != "mean" && vd.sz() == want.sz() && vd.sz() >= 1) {
+        if (n_img < 0) n_img = vd.dims(0);
+        if ((long)vd.dims(0) != n_img) rt_err(fn + ": arg '" + an + "' has " + std::to_string(vd.dims(0)) + " images, another arg " + std::to_string(n_img));
+        want[0].sz = vd.dims(0); want.calc_strides();
+      }
+      if (!(vd == want)) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + op.get_dims(an).pretty_str());
+      P.push_back(must_find(vis, vn).buf.get());
+    }
+    d.B = n_img;
+    if (4.0 * (double)d.out_elems() >= 2147483648.0 || (double)d.B * d.C * d.H * d.W >= 2147483648.0) unsup_err(fn + ": tensors of 2 GiB or more");
+    data_transform(d, (unsigned char const *)P[0], (uint32_t const *)P[1], (float const *)P[2], (float *)P[3]);
+  }
+
   uint32_t run(rtc_func_call_t const &rfc) override {
     assert_st(init_done);
     auto fit = funcs.find(rfc.rtc_func_name);
@@ -970,6 +1017,7 @@ struct cpu_compute_t : public rtc_compute_t {
     else if (f.family == kFamBn || f.family == kFamBnc) run_bn(fi.op, am);
     else if (f.family == kFamSolver) run_solver(fi.op, am);
     else if (f.family == kFamEval) run_eval(fi.op, am);
+    else if (f.family == kFamData) run_data(fi.op, am);
     else if (f.family == kFamBckOp) run_bck_op(f, fi.op, am);
     else if (f.family == kFamBconv) run_bck(f, fi.op, am);
     else if (f.family == kFamSgemm) {

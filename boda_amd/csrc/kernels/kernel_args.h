@@ -271,6 +271,19 @@ struct bn_fold_args_t {
 };
 static_assert(sizeof(bn_fold_args_t) == 56 && __builtin_offsetof(bn_fold_args_t, a) == 32 && __builtin_offsetof(bn_fold_args_t, C) == 48, "bn_fold_args_t layout");
 
+// kernels/data_f32.hip: the input transform of the gradient pipe
+struct data_transform_args_t {
+  unsigned char const *src;              // img:y:x:chan or img:chan:y:x (-DCHW) at the source size H x W
+  unsigned const *plan;                  // img:v=4 = y_off, x_off, mirror, unused
+  float const *mean;                     // chan, or chan:y:x at the source size (-DMEAN_PEL)
+  float *out;                            // img:chan:y:x at the crop size ch x cw
+  long n;                                // out's elements, B * C * ch * cw
+  int C, H, W, ch, cw;
+  float scale;
+};
+static_assert(sizeof(data_transform_args_t) == 64 && __builtin_offsetof(data_transform_args_t, out) == 24 && __builtin_offsetof(data_transform_args_t, n) == 32 &&
+              __builtin_offsetof(data_transform_args_t, C) == 40 && __builtin_offsetof(data_transform_args_t, scale) == 60, "data_transform_args_t layout");
+
 #pragma pop_macro("CH")
 #pragma pop_macro("CIN")
 #pragma pop_macro("COH")

@@ -10,8 +10,8 @@
 namespace bodahip {
 
 // the family (func_family_t of rtc_types.h) selects the handler (native_run.cc, native_kernels.cc: check_compile_time); handlers switch on the member, never on the name
-inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval"};
-// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind)
+inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data"};
+// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform
 enum { kConvF32 = 0, kConvAlias = 1, kConvBf16 = 2, kConvWinograd = 3 };            // (the alias: hip_conv's contract without its fused pooling and filts_km)
 enum { kBconvIn = 1, kBconvBiases = 2, kBconvFilts = 3, kBconvFiltsBiases = 4 };   // (4 is opt-in: never one of the bare op's three calls)
 enum { kOpPoolYx = 1, kOpSpreading = 2, kOpLrnSb = 3, kOpBckLrn = 4, kOpZeroIfNonPos = 5, kOpSoftmax = 6, kOpSmGradAndLoss = 7, kOpSumLossOverImgs = 8, kOpReduce = 9,
@@ -132,6 +132,9 @@ inline constexpr native_func_t kNativeFuncs[] = {
   {"hip_bnc_fwd", kFamBnc, 2, nullptr, {"BncFwd"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"scale", kIn}, {"bias", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
   {"hip_bnc_bck_sums", kFamBnc, 3, nullptr, {"BncBckSums"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"out_grad_loss", kIn}, {"scale_grad_loss", kOut}, {"bias_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
   {"hip_bnc_bck_in", kFamBnc, 4, nullptr, {"BncBckIn"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"scale", kIn}, {"scale_grad_loss", kIn}, {"bias_grad_loss", kIn}, {"out_grad_loss", kIn}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  // the input transform of the gradient pipe (this backend's own; kernels/data_f32.hip): crop, mirror, mean and scale from uint8 images under a per-image plan var
+  // (independent per image: src, plan and out are img shards, mean is whole on every device).  In front of the eval rows, which stay the table's last three
+  {"hip_data_transform", kFamData, 1, nullptr, {"DataTransform"}, {{"src", kIn}, {"plan", kIn}, {"mean", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
   // the evaluation pass of the gradient pipe (this backend's own; kernels/eval_f32.hip): the rank of the true class per image (independent per image), the batch's counts
   // and loss added into two accumulators under ctl = [first, 0, 0, 0] (hip_grad_accum's protocol), and a BatchNorm + Scale run's running statistics folded into (a, b)
   {"hip_accuracy", kFamEval, 1, nullptr, {"Accuracy"}, {{"in", kIn}, {"label", kIn}, {"rank", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},

@@ -63,6 +63,10 @@ string bn_plan_desc(bn_op_t const &b, bn_plan_t const &bp);
 bck_plan_t plan_eval_op(eval_op_t const &e);
 string eval_plan_desc(eval_op_t const &e, bck_plan_t const &bp);
 
+// the data family (kernels/data_f32.hip; data_transform_args_t): one launch per call; d.B is the call's image count
+bck_plan_t plan_data_op(data_op_t const &d);
+string data_plan_desc(data_op_t const &d, bck_plan_t const &bp);
+
 struct sgemm_split_t { uint32_t m_main = 0; string tail_tile; double t_single = 0, t_split = 0; };
 static char const *const kBigTile = "256x256x16x2x4x1x1x32x2";
 struct sgemm_part_t { uint32_t m0 = 0, rows = 0, n0 = 0, cols = 0; string tile; };

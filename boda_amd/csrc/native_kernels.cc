@@ -72,6 +72,9 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
   case kFamEval:   // likewise: the op whole, the code object built now (an eval pass may first run inside a graph capture)
     (void)get_kernel(impl, host, plan_eval_op(eval_op_of_op(fi.op)).p);
     break;
+  case kFamData:   // likewise
+    (void)get_kernel(impl, host, plan_data_op(data_op_of_op(fi.op)).p);
+    break;
   case kFamBconv:   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     (void)op_bf16_operands(fi.op);   // (str_val hip_operands: refused at compile where the function has no bf16-operand form)
@@ -966,6 +969,18 @@ void native_kernels_t::eval_call(eval_op_t const &e, void *const *ptrs) {
     a3.a = (float *)ptrs[4]; a3.b = (float *)ptrs[5]; a3.C = (int)e.C; a3.eps = e.eps; params[0] = &a3;
   }
   if (bp.grid) hip_err_chk(host->nh_launch(k.func, bp.grid, 1, bp.block, params), "hipModuleLaunchKernel(eval)");
+  last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = bp.grid; last_launch.block = bp.block;
+  last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
+}
+// ---- the data family (kernels/data_f32.hip): one launch per call
+void native_kernels_t::data_call(data_op_t const &d, void *const *ptrs) {
+  bck_plan_t const bp = plan_data_op(d);
+  kernel_t &k = get_kernel(impl, host, bp.p);
+  data_transform_args_t a; memset(&a, 0, sizeof(a));
+  a.src = (unsigned char const *)ptrs[0]; a.plan = (unsigned const *)ptrs[1]; a.mean = (float const *)ptrs[2]; a.out = (float *)ptrs[3];
+  a.n = d.out_elems(); a.C = (int)d.C; a.H = (int)d.H; a.W = (int)d.W; a.ch = (int)d.ch; a.cw = (int)d.cw; a.scale = d.scale;
+  void *params[1] = {&a};
+  if (bp.grid) hip_err_chk(host->nh_launch(k.func, bp.grid, 1, bp.block, params), "hipModuleLaunchKernel(data)");
   last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = bp.grid; last_launch.block = bp.block;
   last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
 }

@@ -34,6 +34,9 @@
 //     hip_accuracy / hip_eval_accum / hip_bn_fold    this backend's own: the evaluation pass of the gradient pipe.  The rank of the true class per image (uint32; the logits, not
 //                                       prob), the batch's image / hit / batch counts and loss added into counts (uint32 v=4) and loss_sum under ctl = [first, 0, 0, 0] read
 //                                       from device memory, and a [BatchNorm, Scale] run's running statistics folded into (a, b) for hip_chan_affine.  kernels/eval_f32.hip
+//     hip_data_transform               this backend's own: the input transform of the gradient pipe.  uint8 images (interleaved or planar) cropped and mirrored under a
+//                                       per-image plan var (uint32 img:v=4 = y_off, x_off, mirror, unused; offsets clamped), mean (per channel or per source pel)
+//                                       subtracted, scaled: out = ((float)src - mean) * scale, two fp32 roundings.  kernels/data_f32.hip
 //     hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out    this backend's own: the training BatchNorm of the gradient pipe (batch statistics, running
 //                                       pair, normalise + scale + bias + ReLU, the two gradients) and the gradient of an Eltwise SUM.  kernels/bn_f32.hip states the arithmetic and
 //                                       the order of the per-channel sums
@@ -162,6 +165,8 @@ struct native_kernels_t {
   void grad_accum(solver_op_t const &so, float const *const *g, float *const *a, float const *accum);
   // the eval family on raw device pointers (kernels/eval_f32.hip): ptrs in eval_op_t::args' order; e.B of hip_accuracy is the call's image count
   void eval_call(eval_op_t const &e, void *const *ptrs);
+  // hip_data_transform on raw device pointers (kernels/data_f32.hip): ptrs = src, plan, mean, out; d.B is the call's image count
+  void data_call(data_op_t const &d, void *const *ptrs);
   void shard_sum(float const *slabs, float *out, int nslabs, long stride, long n);
   // hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out on raw device pointers (kernels/bn_f32.hip): tens / chans in bn_op_t's arg order
   void bn_call(bn_op_t const &b, float *const *tens, float *const *chans);

@@ -1440,6 +1440,25 @@ string eval_plan_desc(eval_op_t const &e, bck_plan_t const &bp) {
   return d;
 }
 
+// ---- the data family (kernels/data_f32.hip): the layout of src and the form of mean are in the code, every size is a kernel argument.  One thread per four flat
+// elements of out, workgroups of 256.  Algorithmic bytes: one source byte read and one float written per output element, the plan, and the mean -- one float per output
+// element where it is per pel (chan:y:x), the C values once where it is per channel
+bck_plan_t plan_data_op(data_op_t const &d) {
+  string const what = find_native_func(kFamData, 1)->name;
+  bck_plan_t r; r.p.src = kSrc_data_f32; r.p.kname = "bodahip_data_transform";
+  r.p.defs = {"-DCHW=" + std::to_string(d.chw), "-DMEAN_PEL=" + std::to_string(d.mean_pel)};
+  if (d.B < 0 || d.C < 1 || d.ch < 1 || d.cw < 1 || d.ch > d.H || d.cw > d.W) rt_err(what + ": bad dims");
+  long const n = d.out_elems();
+  if (4.0 * (double)n >= 2147483648.0 || (double)d.B * d.C * d.H * d.W >= 2147483648.0) unsup_err(what + ": tensors of 2 GiB or more");
+  r.threads = (n + 3) / 4; r.algo_bytes = (d.mean_pel ? 9.0 : 5.0) * (double)n + 16.0 * d.B + (d.mean_pel ? 0.0 : 4.0 * d.C);
+  r.grid = (uint32_t)((r.threads + r.block - 1) / r.block);
+  return r;
+}
+string data_plan_desc(data_op_t const &d, bck_plan_t const &bp) {
+  return bp.p.kname + " grid=" + std::to_string(bp.grid) + " block=" + std::to_string(bp.block) + " src=" + (d.chw ? "chw" : "hwc") + " mean=" + (d.mean_pel ? "chan:y:x" : "chan") +
+         " imgs=" + std::to_string(d.B) + " chans=" + std::to_string(d.C) + " " + std::to_string(d.H) + "x" + std::to_string(d.W) + "->" + std::to_string(d.ch) + "x" + std::to_string(d.cw);
+}
+
 // ---- hip_sgd_update (kernels/sgd_update_f32.hip): one workgroup per chunk of kSgdChunk floats of one tensor; the grid is the sum of the tensors' chunks, blk0 its
 // prefix sums.  20 bytes move per element: w, g, h read, h and w written.
 sgd_plan_t plan_sgd_update(std::vector<long> const &elems) {

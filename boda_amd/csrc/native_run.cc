@@ -280,6 +280,12 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     bck_plan_t const bp = plan_eval_op(e);
     if (plan_out) *plan_out = eval_plan_desc(e, bp);
     return arch.empty() ? 0 : compile_plan(bp.p, arch, &log).size();
+  } else if (fam == kFamData) {   // (kernels/data_f32.hip: specialised by src's layout and mean's form only)
+    if (!f) rt_err("prebuild: a bare " + t + " op: the input transform's op is a function op (cnn_op.data_transform_func_op)");
+    data_op_t const d = data_op_of_op(op);
+    bck_plan_t const bp = plan_data_op(d);
+    if (plan_out) *plan_out = data_plan_desc(d, bp);
+    return arch.empty() ? 0 : compile_plan(bp.p, arch, &log).size();
   } else {   // kFamBckOp, a non-conv op of the gradient pipe: its annotated function, or (the bare op) all its functions in call order
     if (op.has_func_name() && !f) rt_err("prebuild: " + t + " function '" + op.get_func_name() + "' has no native kernel");
     std::vector<native_func_t const *> const ds = f ? std::vector<native_func_t const *>{f} : of_t;
@@ -762,6 +768,30 @@ struct native_kernels_t::call_t {
     if (e.kind == 1) e.B = n_img;
     nk.eval_call(e, ptrs.data());
   }
+  void run_data() {
+    // every var has the type and the dims the op gives its arg -- except the number of images of src, plan and out (the function is independent per image), which only
+    // has to agree between them -- and all the call's vars are different ones
+    data_op_t d = data_op_of_op(fi.op);
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    std::vector<void *> ptrs;
+    for (string const &an : d.args) {
+      string const vn = var_of(am, an);
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      dims_t const vd = host->nh_var_dims(vn);
+      dims_t want = fi.op.get_dims(an);
+      if (vd.tn != want.tn) rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ", the op says " + want.tn);
+      if (an != "mean" && vd.sz() == want.sz() && vd.sz() >= 1) {
+        if (n_img < 0) n_img = vd.dims(0);
+        if ((long)vd.dims(0) != n_img) rt_err(fn + ": arg '" + an + "' has " + std::to_string(vd.dims(0)) + " images, another arg " + std::to_string(n_img));
+        want[0].sz = vd.dims(0); want.calc_strides();
+      }
+      if (!(vd == want)) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + fi.op.get_dims(an).pretty_str());
+      ptrs.push_back(host->nh_var_ptr(vn));
+    }
+    d.B = n_img;
+    nk.data_call(d, ptrs.data());
+  }
   void run_bn() {
     // every var must have exactly the dims the op gives its arg (the sums run over the whole batch: no img shards), and no two args may be one var except where
     // kernels/bn_f32.hip allows in-place use
@@ -886,6 +916,7 @@ void native_kernels_t::run(native_func_t const &f, rtc_func_info_t const &fi, ma
   case kFamBn: case kFamBnc: c.run_bn(); break;
   case kFamSolver: c.run_solver(); break;
   case kFamEval: c.run_eval(); break;
+  case kFamData: c.run_data(); break;
   }
 }
 

@@ -129,7 +129,7 @@ struct op_base_t {
 };
 typedef std::shared_ptr<op_base_t> p_op_base_t;
 // ---- the op flags of a native function.  Which function takes which flag is a column of the one table, native_funcs.h (included at the end of this file), which defines:
-enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver, kFamEval };   // selects the handler
+enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver, kFamEval, kFamData };   // selects the handler
 enum : unsigned { kFlagZinp = 1, kFlagSeedVar = 2, kFlagImgShards = 4, kFlagNhwcResidual = 8 };
 struct op_flag_name_t { char const *name; unsigned flag; };
 constexpr op_flag_name_t kOpFlagNames[] = {{"img_shards", kFlagImgShards}, {"seed_from_var", kFlagSeedVar}, {"zero_if_in_non_pos", kFlagZinp}, {"nhwc_residual", kFlagNhwcResidual}};
@@ -447,6 +447,54 @@ inline eval_op_t eval_op_of_op(op_base_t const &op) {
     r.eps = *static_cast<float const *>(v->rp);
     if (!(r.eps >= 0.0f)) rt_err(fn + ": eps must not be negative");
   }
+  return r;
+}
+
+// ---- the data family (this backend's own; kernels/data_f32.hip states the rule): hip_data_transform (op type DataTransform, member 1): src uint8_t img:y:x:chan
+// (interleaved) or img:chan:y:x (planar) at the source size H x W, plan uint32_t img:v=4 = [y_off, x_off, mirror, unused] per image and mean float chan or chan:y:x (at
+// the SOURCE size) read; out float img:chan:y:x at the crop size written; the float scale.  What both backends read from the function's op, and every refusal that needs
+// the op alone
+struct data_op_t {
+  long B = 0, C = 0, H = 0, W = 0, ch = 0, cw = 0;   // images, channels, the source size, the crop size
+  int chw = 0;                   // src's layout: 0 img:y:x:chan, 1 img:chan:y:x
+  int mean_pel = 0;              // mean's form: 0 chan, 1 chan:y:x
+  float scale = 0.f;
+  vect_string args;              // the var args in the function's arg order
+  long out_elems() const { return B * C * ch * cw; }
+};
+inline data_op_t data_op_of_op(op_base_t const &op) {
+  string const fn = op.has_func_name() ? op.get_func_name() : string();
+  data_op_t r;
+  if (native_func_member(fn, kFamData) != 1) rt_err("'" + fn + "' is none of " + native_family_names(kFamData));
+  string const type = native_func_type(kFamData, 1);
+  if (!op.has_type() || op.get_type() != type) rt_err(fn + ": a function of op type " + type + ", not " + (op.has_type() ? op.get_type() : string("?")));
+  refuse_flags_not_taken(op, fn, "the function");
+  r.args = {"src", "plan", "mean", "out"};
+  for (string const &an : r.args) if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'");
+  auto named = [](dims_t const &d, std::initializer_list<char const *> ns) { if (d.sz() != ns.size()) return false; uint32_t i = 0; for (char const *n : ns) if (d.names(i++) != n) return false; return true; };
+  dims_t const &src = op.get_dims("src"), &plan = op.get_dims("plan"), &mean = op.get_dims("mean"), &out = op.get_dims("out");
+  bool const hwc = named(src, {"img", "y", "x", "chan"}), chw = named(src, {"img", "chan", "y", "x"});
+  if (src.tn != "uint8_t" || !(hwc || chw)) rt_err(fn + ": src must be uint8_t img:y:x:chan or img:chan:y:x, got " + src.tn + " " + src.pretty_str());
+  if (out.tn != "float" || !named(out, {"img", "chan", "y", "x"})) rt_err(fn + ": out must be float img:chan:y:x, got " + out.tn + " " + out.pretty_str());
+  r.chw = chw ? 1 : 0;
+  r.B = src.dims(0); r.C = chw ? src.dims(1) : src.dims(3); r.H = chw ? src.dims(2) : src.dims(1); r.W = chw ? src.dims(3) : src.dims(2);
+  r.ch = out.dims(2); r.cw = out.dims(3);
+  if ((long)out.dims(0) != r.B) rt_err(fn + ": out has " + std::to_string(out.dims(0)) + " images, src " + std::to_string(r.B));
+  if ((long)out.dims(1) != r.C) rt_err(fn + ": out has chan=" + std::to_string(out.dims(1)) + ", src chan=" + std::to_string(r.C) + ": the transform keeps the channels");
+  if (r.B < 1 || r.C < 1 || r.ch < 1 || r.cw < 1) rt_err(fn + ": empty out");
+  if (r.ch > r.H || r.cw > r.W) rt_err(fn + ": the crop " + std::to_string(r.ch) + " x " + std::to_string(r.cw) + " is larger than the source " + std::to_string(r.H) + " x " + std::to_string(r.W));
+  bool const m_chan = named(mean, {"chan"}) && (long)mean.dims(0) == r.C;
+  bool const m_pel = named(mean, {"chan", "y", "x"}) && (long)mean.dims(0) == r.C && (long)mean.dims(1) == r.H && (long)mean.dims(2) == r.W;
+  if (mean.tn != "float" || !(m_chan || m_pel))
+    rt_err(fn + ": mean must be float chan=" + std::to_string(r.C) + " or chan=" + std::to_string(r.C) + ":y=" + std::to_string(r.H) + ":x=" + std::to_string(r.W) + " (the SOURCE size), got " + mean.tn + " " + mean.pretty_str());
+  r.mean_pel = m_pel ? 1 : 0;
+  if (plan.tn != "uint32_t" || !named(plan, {"img", "v"}) || (long)plan.dims(0) != r.B || plan.dims(1) != 4)
+    rt_err(fn + ": plan must be uint32_t img=" + std::to_string(r.B) + ":v=4 (y_off, x_off, mirror, unused), got " + plan.tn + " " + plan.pretty_str());
+  if ((double)r.B * r.C * r.H * r.W >= 2147483648.0 || 4.0 * (double)r.out_elems() >= 2147483648.0 || 4.0 * (double)r.C * r.H * r.W >= 2147483648.0)
+    unsup_err(fn + ": tensors of 2 GiB or more");
+  if (!op.has("scale")) rt_err(fn + ": the op has no 'scale'");
+  p_nda_t const &v = op.get("scale"); if (v->dims.tn != "float" || v->dims.sz() != 0 || !v->rp) rt_err(fn + ": 'scale' is not a float scalar");
+  r.scale = *static_cast<float const *>(v->rp);
   return r;
 }
 

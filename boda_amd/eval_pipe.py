@@ -10,6 +10,7 @@ import numpy as np
 
 from .bck_pipe import BN_IN_SFX, BckCall, ConvPipeBck
 from .cnn_op import accuracy_func_op, bn_fold_func_op, chan_affine_func_op, eval_accum_func_op, pipe_func_args
+from .input_pipe import DATA_RAW_VAR, DATA_XF_PLAN_VAR, DATA_XF_TAG
 from .op import Dims, Op, RtErr, UnsupErr
 from .rtc import RtcArg, RtcFuncCall, RtcFuncInfo
 
@@ -33,13 +34,15 @@ class EvalPipe:
         has no meaning in the test phase.
       * the selected SoftmaxWithLoss: the driver's three calls, then hip_accuracy on the loss's `in` node (the logits) and `label` into eval_rank, then hip_eval_accum
         into eval_counts / eval_loss_sum.  The loss calls of other heads are left out.
+      * the data_xf call of a driver built with input_transform: the driver's own call, first; run_batch({"data_raw": bytes, "label": y}).
       * everything else: the driver's own call.
     Before every batch, eager or replay, the 16 bytes of eval_ctl are uploaded: [1, 0, 0, 0] on the first batch after reset(), [0, 0, 0, 0] afterwards.  hip_eval_accum
     reads the word from device memory, so nobody clears an accumulator and one captured graph serves every batch.  capture_graph() captures the list serially into a
     graph of its own, beside the driver's; capturing either one does not destroy the other.
 
     WHAT A PASS MAY WRITE.  A pass writes the activation nodes and their side vars (<X>_bn_in, <out>_in_yx, <out>_scale_base, <loss>_prob, <loss>_per_pel, the loss node
-    and the logits' _grad_loss, which the loss function writes) and the vars named above (eval_ctl, eval_rank, eval_counts, eval_loss_sum, <bn>_eval_a / _eval_b).  A pass
+    and the logits' _grad_loss, which the loss function writes) and the vars named above (eval_ctl, eval_rank, eval_counts, eval_loss_sum, <bn>_eval_a / _eval_b) and, on a driver built
+    with input_transform, data_xf_plan (the TEST plan, uploaded beside eval_ctl; the driver uploads its own again before its next pass) and the fed data_raw.  A pass
     NEVER writes a param, a BatchNorm's running or batch statistics, a history, a _grad_acc, any other gradient, a solver var, det_drop_seed, drv.iter or drv.micro: a
     training run with evaluations in between leaves the bits of the same run without them.
 
@@ -60,7 +63,11 @@ class EvalPipe:
         self.drv, self.rtc, self.top_k, self.loss = drv, rtc, top_k, loss
         fwd_ops = {o.tag: o for o in bp.fwd_ops()}
         fwd_calls = []
-        for c in drv.bck_calls:   # the calls in front of the first gradient op
+        self.xf_call: Optional[BckCall] = None
+        for c in drv.bck_calls:   # the calls in front of the first gradient op -- behind the input transform's call, where the driver has one: reused as it is
+            if c.tag == DATA_XF_TAG and drv.input_transform is not None and not fwd_calls and self.xf_call is None:
+                self.xf_call = c
+                continue
             if c.tag not in fwd_ops:
                 break
             fwd_calls.append(c)
@@ -95,6 +102,9 @@ class EvalPipe:
             self.eval_calls.append(BckCall(tag, fop, dict(args), RtcFuncCall(fname, {an: RtcArg.var(args[an]) for an, _ in spec})))
             self.funcs.append(fname)
 
+        if self.xf_call is not None:
+            c = self.xf_call
+            self.eval_calls.append(BckCall(c.tag, c.fop, dict(c.args), c.rfc))
         for c in fwd_calls:
             o = fwd_ops[c.tag]
             if o.type == "Dropout":
@@ -135,6 +145,14 @@ class EvalPipe:
     def _ctl_words(self) -> np.ndarray:
         return np.array([1 if self._first else 0, 0, 0, 0], np.uint32)
 
+    def _upload_ctl(self) -> None:
+        """What is uploaded before every batch: eval_ctl and, on a driver with an input transform, the TEST plan (the centre crop, no mirror) into data_xf_plan --
+        which the driver uploads again before its next pass.  drv.xf_images is not advanced."""
+        self.rtc.copy_nda_to_var(EVAL_CTL_VAR, self._ctl_words())
+        xf = self.drv.input_transform
+        if xf is not None:
+            self.rtc.copy_nda_to_var(DATA_XF_PLAN_VAR, xf.plan("test", 0, self.drv._xf_batch()))
+
     def calls(self) -> List[Tuple[str, Op, Dict[str, RtcArg]]]:
         """The ordered (tag, function op, arg map) list of one evaluation batch."""
         return [(c.tag, c.fop, dict(c.rfc.arg_map)) for c in self.eval_calls]
@@ -155,7 +173,7 @@ class EvalPipe:
         rtc = self.rtc
         if graph and self._graph is None:
             raise RtErr("EvalPipe.run_batch(graph=True): no captured graph -- call capture_graph() first")
-        rtc.copy_nda_to_var(EVAL_CTL_VAR, self._ctl_words())
+        self._upload_ctl()
         if graph:
             cid = rtc.graph_launch(self._graph)
             rtc.finish_and_sync()
@@ -173,6 +191,8 @@ class EvalPipe:
         the graph capture_graph made."""
         if graph and self._graph is None:
             raise RtErr("EvalPipe.run_batch(graph=True): no captured graph -- call capture_graph() first")
+        if self.xf_call is not None and self.drv.bp.cp.in_node in feed:
+            raise RtErr(f"EvalPipe.run_batch: the driver was built with an input_transform: its {DATA_XF_TAG} call would overwrite {self.drv.bp.cp.in_node!r}; feed {DATA_RAW_VAR!r} (uint8)")
         for vn, a in feed.items():
             self.rtc.copy_nda_to_var(vn, a)
         self.rtc.finish_and_sync()
@@ -206,7 +226,7 @@ class EvalPipe:
             rtc.graph_destroy(self._graph); self._graph = None
         if not self._stepped:
             keep = {vn: rtc.copy_var_to_nda(vn) for vn in (EVAL_COUNTS_VAR, EVAL_LOSS_SUM_VAR)}
-            rtc.copy_nda_to_var(EVAL_CTL_VAR, self._ctl_words())
+            self._upload_ctl()
             self._run_calls()
             for vn, a in keep.items():
                 rtc.copy_nda_to_var(vn, a)

@@ -294,14 +294,18 @@ OP_INFO = {
     "Accuracy": (("in", "label"), ("rank",), ()),
     "EvalAccum": (("rank", "loss", "ctl"), ("counts", "loss_sum"), ("top_k",)),
     "BnFold": (("run_mean", "run_var", "scale", "bias"), ("a", "b"), ("eps",)),
+    # this backend's own: the input transform of the gradient pipe (csrc/kernels/data_f32.hip states the rule).  src uint8_t img:y:x:chan or img:chan:y:x, plan uint32_t
+    # img:v=4 = (y_off, x_off, mirror, unused), mean float chan or chan:y:x at the source size; out float img:chan:y:x at the crop size = ((float)src - mean) * scale
+    "DataTransform": (("src", "plan", "mean"), ("out",), ("scale",)),
 }
 BN_TYPES = ("BnStats", "BnFwd", "BnBckSums", "BnBckIn", "FanOut")
 SOLVER_TYPES = ("SolverUpdate", "GradSumsq", "GradNorm", "GradAccum", "SolverUpdateAcc")
 EVAL_TYPES = ("Accuracy", "EvalAccum", "BnFold")
+DATA_TYPES = ("DataTransform",)
 SOLVER_CHUNK = 4096   # floats of one tensor a workgroup owns; one partial sum of squares per chunk
 
 
-_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + SOLVER_TYPES + EVAL_TYPES
+_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + SOLVER_TYPES + EVAL_TYPES + DATA_TYPES
 
 
 @dataclass
@@ -645,6 +649,40 @@ class Op:
             raise RtErr("BnFold: eps must not be negative")
         return dict(C=C)
 
+    def data_geom(self) -> dict:
+        """DataTransform: src uint8_t img:y:x:chan ("hwc") or img:chan:y:x ("chw") at the source size H x W; out float img:chan:y:x with src's img and chan and the crop
+        size ch <= H, cw <= W; mean float chan=C or chan=C:y=H:x=W; plan uint32_t img=B:v=4; the float scale."""
+        fn = "DataTransform"
+        for an in ("src", "plan", "mean", "out"):
+            if not self.has(an):
+                raise RtErr(f"{fn}: the op has no {an!r}")
+        src, plan, mean, out = (self.get_dims(an) for an in ("src", "plan", "mean", "out"))
+        layout = {("img", "y", "x", "chan"): "hwc", ("img", "chan", "y", "x"): "chw"}.get(src.names)
+        if src.tn != "uint8_t" or layout is None:
+            raise RtErr(f"{fn}: src must be uint8_t img:y:x:chan or img:chan:y:x, got {src.tn} {src.pretty()}")
+        if out.tn != "float" or out.names != ("img", "chan", "y", "x"):
+            raise RtErr(f"{fn}: out must be float img:chan:y:x, got {out.tn} {out.pretty()}")
+        B, C, H, W = (src.dsz(n) for n in ("img", "chan", "y", "x"))
+        ch, cw = out.dsz("y"), out.dsz("x")
+        if out.dsz("img") != B:
+            raise RtErr(f"{fn}: out has {out.dsz('img')} images, src {B}")
+        if out.dsz("chan") != C:
+            raise RtErr(f"{fn}: out has chan={out.dsz('chan')}, src chan={C}: the transform keeps the channels")
+        if min(B, C, ch, cw) < 1:
+            raise RtErr(f"{fn}: empty out")
+        if ch > H or cw > W:
+            raise RtErr(f"{fn}: the crop {ch} x {cw} is larger than the source {H} x {W}")
+        forms = {(("chan",), (C,)): "chan", (("chan", "y", "x"), (C, H, W)): "chan:y:x"}
+        if mean.tn != "float" or (mean.names, mean.sizes) not in forms:
+            raise RtErr(f"{fn}: mean must be float chan={C} or chan={C}:y={H}:x={W} (the SOURCE size), got {mean.tn} {mean.pretty()}")
+        if plan.tn != "uint32_t" or plan.names != ("img", "v") or plan.sizes != (B, 4):
+            raise RtErr(f"{fn}: plan must be uint32_t img={B}:v=4 (y_off, x_off, mirror, unused), got {plan.tn} {plan.pretty()}")
+        if B * C * H * W >= 2 ** 31 or 4 * B * C * ch * cw >= 2 ** 31 or 4 * C * H * W >= 2 ** 31:
+            raise UnsupErr(f"{fn}: tensors of 2 GiB or more")
+        if not self.has("scale"):
+            raise RtErr(f"{fn}: the op has no 'scale'")
+        return dict(B=B, C=C, H=H, W=W, ch=ch, cw=cw, layout=layout, mean_form=forms[(mean.names, mean.sizes)], scale=self.get("scale").v[0])
+
     def bn_geom(self) -> dict:
         """BnStats / BnFwd / BnBckSums / BnBckIn: float img:chan:y:x tensors of equal dims, the per-channel args float chan=C; FanOut: in and 2 to 8 outs of equal float dims."""
         t = self.get_type()
@@ -793,6 +831,8 @@ def parse_op(line: str) -> Op:
             op.solver_geom()
         elif t in EVAL_TYPES:
             op.eval_geom()
+        elif t in DATA_TYPES:
+            op.data_geom()
         else:
             op.sgemm_geom()
     return op

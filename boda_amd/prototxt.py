@@ -293,3 +293,44 @@ def accuracy_layers(text: str) -> List[Tuple[str, str, str, int]]:
             raise RtErr(f"prototxt: Accuracy layer {name!r}: top_k={k}: at least 1")
         out.append((name, str(bots[0]), str(bots[1]), k))
     return out
+
+
+def transform_spec(text: str, phase: str) -> dict:
+    """The transform_param of a net definition's Data layer of `phase` ("train" | "test") -> {"crop_size", "mirror", "scale", "mean_value", "mean_file"}: what
+    input_pipe.InputTransform takes (the caller reads mean_file into an array).  A layer without an include block belongs to both phases.  Absent keys get Caffe's
+    defaults: crop_size 0 (the whole source), mirror false, scale 1, mean_value [], mean_file "".  mean_file and mean_value together are an RtErr, as in Caffe; force_color
+    / force_gray set are an UnsupErr that names the key.  conv_ops and pipe_spec keep reading crop_size alone."""
+    from .op import UnsupErr
+    if phase not in ("train", "test"):
+        raise RtErr(f"prototxt: transform_spec: phase must be 'train' | 'test', got {phase!r}")
+    root = parse(text)
+    for L in root.get("layer", []) or root.get("layers", []):
+        if str(_one(L, "type")).upper().replace("_", "") != "DATA":
+            continue
+        incs = [str(_one(inc, "phase", "")).upper() for inc in L.get("include", [])]
+        if incs and phase.upper() not in incs:
+            continue
+        name = _one(L, "name")
+        tp = _one(L, "transform_param", {})
+        if not isinstance(tp, dict):
+            raise RtErr(f"prototxt: Data layer {name!r}: transform_param must be a block")
+        for k in ("force_color", "force_gray"):
+            if str(_one(tp, k, "false")).lower() == "true":
+                raise UnsupErr(f"prototxt: Data layer {name!r}: {k} is not provided (hip_data_transform keeps the source's channels)")
+        for k in ("crop_size", "mirror", "scale", "mean_file"):
+            if len(tp.get(k, [])) > 1:
+                raise RtErr(f"prototxt: Data layer {name!r}: {k!r} is given {len(tp[k])} times")
+        try:
+            crop, scale, mv = int(_one(tp, "crop_size", 0)), float(_one(tp, "scale", 1.0)), [float(v) for v in tp.get("mean_value", [])]
+        except (ValueError, TypeError):
+            raise RtErr(f"prototxt: Data layer {name!r}: crop_size, scale and mean_value must be numbers")
+        mirror = str(_one(tp, "mirror", "false")).lower()
+        if mirror not in ("true", "false"):
+            raise RtErr(f"prototxt: Data layer {name!r}: mirror: {mirror!r} is neither true nor false")
+        mf = str(_one(tp, "mean_file", ""))
+        if mf and mv:
+            raise RtErr(f"prototxt: Data layer {name!r}: both mean_file and mean_value are given; Caffe takes one of them")
+        if crop < 0:
+            raise RtErr(f"prototxt: Data layer {name!r}: crop_size={crop}: not negative")
+        return {"crop_size": crop, "mirror": mirror == "true", "scale": scale, "mean_value": mv, "mean_file": mf}
+    raise RtErr(f"prototxt: transform_spec: no Data layer of the {phase} phase")
