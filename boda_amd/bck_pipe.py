@@ -25,7 +25,7 @@ import numpy as np
 
 from .cnn_op import (NATIVE_ARGS, OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, bnc_bck_in_func_op, bnc_bck_sums_func_op, bnc_fwd_func_op, bnc_stats_func_op, BNC_MAX_CHUNKS, fan_out_func_op, sgd_update_func_op, solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op, grad_accum_func_op, solver_update_acc_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos, IMG_SHARDS_FUNCS, on_img_shards,
                      pipe_func_args, seed_from_var, SEED_VAR_ARG, bf16_operands)
-from .cnn_op import data_transform_func_op
+from .cnn_op import bnf_bck_func_op, bnf_bck_in_func_op, bnf_prep_func_op, data_transform_func_op
 from .conv_pipe import ConvPipe, PipeOp
 from .input_pipe import DATA_RAW_VAR, DATA_XF_MEAN_VAR, DATA_XF_PLAN_VAR, DATA_XF_TAG, InputTransform
 from .op import Dims, Nda, Op, RtErr, SOLVER_CHUNK, UnsupErr
@@ -155,6 +155,32 @@ class Solver:
         lr = self.lr_policy.lr_at(self.lr, it) if self.lr_policy is not None else self.lr
         return np.array([lr, self.momentum, self.weight_decay, self.momentum2, self.delta, self.corr(self.momentum, self.momentum2, it + 1) if self.type == "adam" else 1.0,
                          self.clip_gradients, 0.0], np.float32)
+
+
+@dataclass
+class Freeze:
+    """Fine-tuning for ConvPipeBck(freeze=...): which params stay fixed, which BatchNorms run on their running pair, and the pruned backward walk.
+    params: param names (`res2a_branch2a_filts`), op tags (`conv1`: all of that op's params) or a suffix (`filts` | `biases` | `scale` | `bias`, as lr_mult keys are
+    written); a name that matches nothing is an RtErr that names it.  A frozen param has no history, second history or accumulator var, takes no part in the clipping norm
+    and is in no update call: its bits never change.
+    bn_global_stats: True (every BatchNorm), False, or a list of BatchNorm op tags.  A listed [BatchNorm, Scale (, ReLU)] run normalises by its running pair, which is then
+    only read (hip_bnf_prep in place of hip_bn_stats; backward hip_bnf_bck / hip_bnf_bck_in, dx = (scale * inv_std) * dy).
+    keep_grads: node names whose gradient is wanted although nothing trainable lies below them, e.g. ("data",) for a saliency map.
+    THE PRUNING RULE is Caffe's need_backward, applied by init to the pipe add_bck_ops returned.  Walking the forward ops in order, a node needs a gradient if its producer
+    has a trainable param, or if any of the producer's inputs needs one, or if it is in keep_grads; the input node and `label` never need one unless listed.  A gradient op
+    keeps a param-gradient output only if that param is trainable -- an op whose two params are not both frozen keeps both -- and its in_grad_loss output only if that
+    bottom node needs a gradient; a gradient op with no output left emits no call, and the vars of dropped gradients are not created.  (A training BatchNorm's data
+    gradient reads the two sums: where it is kept, they are computed even for a frozen Scale.)
+    Freeze() with nothing in it therefore drops only what feeds <input>_grad_loss: the data gradient of every layer below the first that reads a trainable layer's output
+    -- in a plain net the first convolution's hip_bconv_in."""
+    params: Sequence[str] = ()
+    bn_global_stats: object = False
+    keep_grads: Sequence[str] = ()
+
+
+PARAM_SFXS = ("filts", "biases", "scale", "bias")   # what an lr_mult / Freeze.params key may name besides a param or an op tag
+WHY_DROPPED = ("Freeze's pruning rule computes a node's gradient only if the node's producer has a trainable param, or an input of the producer needs a gradient, or the "
+               "node is in Freeze.keep_grads; a param's gradient only if the param (or the other param of its op) is trainable")
 
 
 @dataclass
@@ -530,11 +556,25 @@ class ConvPipeBck:
     hip_data_transform from data_raw into the pipe's input node.  run_bck(["data_raw", "label"], ...) uploads bytes.  Before every pass -- a micro-step of iter_size
     included, eager or a replay -- the B x 16 bytes of the plan are uploaded: input_transform.plan("train", xf_images, B), or the plan set_input_plan gave for this one
     pass, checked by check_plan; behind the pass xf_images advances by B.  The plan lives in a var, so one captured graph serves every pass.  Feeding the input node
-    itself is an RtErr: the call would overwrite it.  On a multi-device backend the call runs on the img shards of data_raw, data_xf_plan and the input node."""
+    itself is an RtErr: the call would overwrite it.  On a multi-device backend the call runs on the img shards of data_raw, data_xf_plan and the input node.
+    freeze=Freeze(...) (opt-in; None leaves the vars, calls(), _call_deps() and every bit of a step as they are): fine-tuning.  The params it names
+    stay fixed (not in sgd_params, no solver var, in no update or norm call), the BatchNorms it lists run on their running pair, which is then only read, and the backward
+    walk is pruned by Caffe's need_backward rule (Freeze's docstring): a gradient op emits only the calls whose outputs are still wanted, the vars of dropped gradients
+    are not created and asking run_bck for one is an RtErr.  `frozen` says what init did: {"params": the frozen params, "dropped_calls": the tags of the gradient ops
+    that emit no call, "bn_global": the BatchNorm tags on their running pair}.  A listed [BatchNorm, Scale (, ReLU)] run emits hip_bnf_prep (-> <bn-tag>_batch_mean /
+    _batch_inv_std from the running pair) and hip_bn_fwd as it is; backward ONE call: hip_bnf_bck (BckScale: both sums and dx = (scale * inv_std) * dy in one pass, in
+    place on X_grad_loss), hip_bn_bck_sums where nothing below needs a gradient, or hip_bnf_bck_in (BckBatchNorm) where both Scale params are frozen.  The one output
+    Freeze leaves of an Eltwise gradient is a hip_split copy.  Composes with every option above; on a multi-device backend param freezing alone works, bn_global_stats is
+    refused there and together with img_chunks before anything is created.  A pipe in which nothing is trainable is an RtErr.  A Freeze cannot be changed after init."""
 
     def __init__(self, rtc, op_tune: Optional[OpTune] = None, fuse_relu_grad: bool = False, seed_in_var: bool = False, solver: Optional[object] = None, bn_maf: float = 0.999, fuse_filts_biases: bool = False,
-                 grad_operands: str = "", img_chunks: int = 0, iter_size: int = 1, input_transform: Optional[InputTransform] = None):
+                 grad_operands: str = "", img_chunks: int = 0, iter_size: int = 1, input_transform: Optional[InputTransform] = None, freeze: Optional[Freeze] = None):
         self.rtc = rtc
+        if freeze is not None and not isinstance(freeze, Freeze):
+            raise RtErr(f"ConvPipeBck: freeze must be a bck_pipe.Freeze or None, got {type(freeze).__name__}")
+        self.freeze = freeze
+        self.frozen: Dict[str, object] = {"params": [], "dropped_calls": [], "bn_global": []}   # what init did with `freeze`
+        self._dropped_vars: set = set()   # the gradient vars the pruning rule left out
         if input_transform is not None and not isinstance(input_transform, InputTransform):
             raise RtErr(f"ConvPipeBck: input_transform must be an input_pipe.InputTransform or None, got {type(input_transform).__name__}")
         self.input_transform = input_transform
@@ -605,6 +645,7 @@ class ConvPipeBck:
                            "multi-device backend (devices=...)")
         stats = set(bn_stat_params(bp.cp))
         self.sgd_params = [pn for pn in bp.cp.params if pn not in stats]
+        keep, bn_global = self._plan_freeze(bp, bn_runs, multi_dev)   # (None, empty without freeze=; refuses before anything is created)
         if self.solver is not None:   # (refused before anything is created)
             if not 1 <= int(self.solver.tensors_per_call) <= SGD_MAX_TENS:
                 raise RtErr(f"ConvPipeBck.init: SgdSolver.tensors_per_call={self.solver.tensors_per_call}: 1 to {SGD_MAX_TENS}")
@@ -645,7 +686,8 @@ class ConvPipeBck:
                     raise RtErr(f"ConvPipeBck.init: input_transform needs the var name {vn!r}, which is a node of the pipe")
             xf_mean = xf.mean_array(dd.dsz("chan"))
         for n, d in bp.nodes.items():
-            self._var(n, d)
+            if n not in self._dropped_vars:
+                self._var(n, d)
         if xf is not None:
             self._var(DATA_RAW_VAR, xf.src_dims(dd.dsz("img"), dd.dsz("chan")))
             self._var(DATA_XF_PLAN_VAR, Dims(("img", "v"), (dd.dsz("img"), 4), "uint32_t"))
@@ -669,6 +711,7 @@ class ConvPipeBck:
             if relu is not None:
                 fused.add(relu.tag)
         bn_of_tag = {q.tag: (x, run) for x, run in bn_runs.items() for q in run[:2]}
+        by_tag_bck = {o.tag: o for o in bp.bck_ops()}
         folds, why = plan_relu_grad_folds(bp) if self.fuse_relu_grad else ({}, {o.tag: "fuse_relu_grad is off" for o in bp.bck_ops() if o.type == "ZeroIfNonPos"})
         self.fused_relu_grads = {"folded": list(folds), "unfolded": why}
         takes_relu = set(folds.values())   # the gradient ops that apply the mask of the ZeroIfNonPos behind them
@@ -695,8 +738,11 @@ class ConvPipeBck:
         if xf is not None:   # in front of the step's first call: the input node from the bytes
             emit(DATA_XF_TAG, data_transform_func_op(xf.src_dims(dd.dsz("img"), dd.dsz("chan")), (xf.ch, xf.cw), xf.mean_dims(dd.dsz("chan")), xf.scale),
                  {"src": DATA_RAW_VAR, "plan": DATA_XF_PLAN_VAR, "mean": DATA_XF_MEAN_VAR, "out": dn})
+        kept = lambda o, i: keep is None or o.tag not in keep or keep[o.tag][i]   # does gradient op o still write its i-th top?
         for o in ops:
             if o.tag in fused or o.tag in folds:
+                continue
+            if keep is not None and o.tag in keep and not any(keep[o.tag]):
                 continue
             t = o.type
             calls: List[Tuple[Op, Dict[str, str]]] = []
@@ -711,25 +757,40 @@ class ConvPipeBck:
                 fwd_op = bnc_fwd_func_op if nc else bn_fwd_func_op
                 sums_op = (lambda d: bnc_bck_sums_func_op(d, nc)) if nc else bn_bck_sums_func_op
                 in_op = bnc_bck_in_func_op if nc else bn_bck_in_func_op
-                if t == "BatchNorm":
+                if bn.tag in bn_global:   # on the running pair: hip_bnf_prep, hip_bn_fwd as it is, and ONE backward call -- which one, the pruning rule says
+                    in_need, sc_train = kept(o, 0), kept(o, 1) if t == "BckScale" else kept(by_tag_bck[sc.tag + "_bck"], 1)
+                    gl = {"out_grad_loss": o.bots[0], "in_grad_loss": o.tops[0]}
+                    if t == "BatchNorm":
+                        calls.append((bnf_prep_func_op(xd, bn.eps), {"run_mean": bn.tag + "_mean", "run_var": bn.tag + "_var", "mean": common["mean"], "inv_std": common["inv_std"]}))
+                    elif t == "Scale":
+                        calls.append((fwd_op(xd, 1 if relu is not None else 0), dict(common, scale=sc.tag + "_scale", bias=sc.tag + "_bias", out=x)))
+                    elif t == "BckScale" and sc_train and in_need:      # the sums and dx in one pass, in place on X_grad_loss
+                        calls.append((bnf_bck_func_op(xd), dict(common, scale=sc.tag + "_scale", scale_grad_loss=o.tops[1], bias_grad_loss=o.tops[2], **gl)))
+                    elif t == "BckScale" and sc_train:     # nothing below needs a gradient: the sums alone
+                        calls.append((sums_op(xd), dict(common, out_grad_loss=o.bots[0], scale_grad_loss=o.tops[1], bias_grad_loss=o.tops[2])))
+                    elif t == "BckBatchNorm" and not sc_train:   # behind a frozen Scale (with a trainable one hip_bnf_bck has written dx already)
+                        calls.append((bnf_bck_in_func_op(xd), dict(inv_std=common["inv_std"], scale=sc.tag + "_scale", **gl)))
+                elif t == "BatchNorm":
                     calls.append((stats_op(xd, bn.eps, self.bn_maf), dict(common, run_mean=bn.tag + "_mean", run_var=bn.tag + "_var")))
                 elif t == "Scale":
                     calls.append((fwd_op(xd, 1 if relu is not None else 0), dict(common, scale=sc.tag + "_scale", bias=sc.tag + "_bias", out=x)))
                 elif t == "BckScale":
                     calls.append((sums_op(xd), dict(common, out_grad_loss=o.bots[0], scale_grad_loss=o.tops[1], bias_grad_loss=o.tops[2])))
-                else:
+                elif kept(o, 0):
                     calls.append((in_op(xd), dict(common, scale=sc.tag + "_scale", scale_grad_loss=sc.tag + "_scale_grad_loss", bias_grad_loss=sc.tag + "_bias_grad_loss",
                                                               out_grad_loss=o.bots[0], in_grad_loss=o.tops[0])))
                 for fop, args in calls:
                     emit(o.tag, fop, args)
                 continue
-            if t == "BckEltwise" and self.img_chunks:   # one copy per output by a function that runs on img shards: hip_split of ALL of in's channels
-                d = bp.nodes[o.bots[0]]
-                for tp in o.tops:
+            n_kept = sum(1 for i in range(len(o.tops)) if kept(o, i))
+            if t == "BckEltwise" and (self.img_chunks or n_kept == 1):   # one copy per output by a function that runs on img shards: hip_split of ALL of in's channels
+                d = bp.nodes[o.bots[0]]    # (also the one output Freeze leaves of a fan-out: hip_fan_out writes two or more)
+                for tp in [tp for i, tp in enumerate(o.tops) if kept(o, i)]:
                     emit(o.tag, add_pipe_op_annotations(Op({"type": "Split"}, {"in": Nda(d), "outs_0": Nda(d), "outs_num": _u32(1)}), tune)[0], {"in": o.bots[0], "out": tp})
                 continue
             if t == "BckEltwise":
-                emit(o.tag, fan_out_func_op(bp.nodes[o.bots[0]], len(o.tops)), dict({f"outs_{i}": tp for i, tp in enumerate(o.tops)}, **{"in": o.bots[0]}))
+                tps = [tp for i, tp in enumerate(o.tops) if kept(o, i)]
+                emit(o.tag, fan_out_func_op(bp.nodes[o.bots[0]], len(tps)), dict({f"outs_{i}": tp for i, tp in enumerate(tps)}, **{"in": o.bots[0]}))
                 continue
             op = grad_op_to_op(bp, o)
             if t == "Convolution":
@@ -743,10 +804,11 @@ class ConvPipeBck:
             elif t == "BckConv":
                 fi, fb, ff = add_bck_conv_annotations(op, tune)
                 b16 = bf16_operands if self.grad_operands else (lambda f: f)
-                calls.append((b16(zinp(o, fi)), dict({"filts": o.bots[1], "out_grad_loss": o.bots[3], "in_grad_loss": o.tops[0]}, **({"in": o.bots[0]} if o.tag in takes_relu else {}))))
-                if self.fuse_filts_biases:   # one call writes both gradients
+                if kept(o, 0):
+                    calls.append((b16(zinp(o, fi)), dict({"filts": o.bots[1], "out_grad_loss": o.bots[3], "in_grad_loss": o.tops[0]}, **({"in": o.bots[0]} if o.tag in takes_relu else {}))))
+                if kept(o, 1) and self.fuse_filts_biases:   # one call writes both gradients  (not kept: both params frozen, the data gradient alone)
                     calls.append((b16(bconv_filts_biases_func_op(op, tune)), {"in": o.bots[0], "out_grad_loss": o.bots[3], "filts_grad_loss": o.tops[1], "biases_grad_loss": o.tops[2]}))
-                else:
+                elif kept(o, 1):
                     calls.append((fb, {"out_grad_loss": o.bots[3], "biases_grad_loss": o.tops[2]}))
                     calls.append((ff, {"in": o.bots[0], "out_grad_loss": o.bots[3], "filts_grad_loss": o.tops[1]}))
             elif t == "Pooling":
@@ -779,8 +841,9 @@ class ConvPipeBck:
                 for f, b in zip(add_pipe_op_annotations(op, tune), o.bots):
                     calls.append((f, {"in": b, "out": o.tops[0]}))
             elif t == "Split":
-                for f, tp in zip(add_pipe_op_annotations(op, tune), o.tops):
-                    calls.append((f, {"in": o.bots[0], "out": tp}))
+                for i, (f, tp) in enumerate(zip(add_pipe_op_annotations(op, tune), o.tops)):
+                    if kept(o, i):
+                        calls.append((f, {"in": o.bots[0], "out": tp}))
             else:
                 raise UnsupErr(f"ConvPipeBck: op type {t!r} (op {o.tag}) has no native function")
             for fop, args in calls:
@@ -869,6 +932,86 @@ class ConvPipeBck:
                 if self.iter_size > 1:
                     self.rtc.copy_nda_to_var(SOLVER_ACCUM_VAR, self.accum_words())
             self.set_sgd_hyper()
+
+    def _plan_freeze(self, bp: BckPipe, bn_runs: Dict[str, tuple], multi_dev: bool):
+        """Freeze's rule on the pipe -> ({gradient op tag: [is its i-th top still written]}, the set of BatchNorm tags on their running pair); (None, empty set) without
+        freeze=.  Sets sgd_params (the trainable params), frozen and _dropped_vars; every refusal comes before anything is created."""
+        fz = self.freeze
+        self.frozen = {"params": [], "dropped_calls": [], "bn_global": []}
+        self._dropped_vars = set()
+        if fz is None:
+            return None, set()
+        cp = bp.cp
+        fwd = [o for o in bp.fwd_ops() if o.type != "SoftmaxWithLoss"]
+        bn_tags = [o.tag for o in fwd if o.type == "BatchNorm"]
+        g = fz.bn_global_stats
+        if g is True or g is False or g is None:
+            bn_global = list(bn_tags) if g is True else []
+        elif isinstance(g, (str, bytes)):
+            raise RtErr(f"Freeze: bn_global_stats must be True, False or a list of BatchNorm op tags, got {g!r}")
+        else:
+            bn_global = list(g)
+            for tg in bn_global:
+                if tg not in bn_tags:
+                    raise RtErr(f"Freeze: bn_global_stats names {tg!r}, which is no BatchNorm op of the pipe")
+        if bn_global and multi_dev:
+            raise UnsupErr("ConvPipeBck.init: Freeze(bn_global_stats=...): a BatchNorm on its running pair runs as hip_bnf_prep / hip_bnf_bck / hip_bnf_bck_in, which take vars of "
+                           "exactly their op's dims and sum over the whole batch: not provided on a multi-device backend (devices=...); freeze params alone there")
+        if bn_global and self.img_chunks:
+            raise UnsupErr(f"ConvPipeBck.init: Freeze(bn_global_stats=...) together with img_chunks={self.img_chunks}: the hip_bnf_* functions have no chunked chain; a "
+                           "BatchNorm on its running pair runs on one device with img_chunks=0")
+        cand = list(self.sgd_params)   # every param but the BatchNorm running statistics, in the pipe's order
+        params_of = {o.tag: [b for b in o.bots[1:] if b in cand] for o in fwd}
+        frozen = set()
+        for e in fz.params:
+            hit = [e] if e in cand else params_of.get(e) or ([pn for pn in cand if pn.rsplit("_", 1)[-1] == e] if e in PARAM_SFXS else [])
+            if not hit:
+                raise RtErr(f"Freeze: params names {e!r}, which is no param of the pipe, no tag of an op with params and none of the suffixes {' | '.join(PARAM_SFXS)} of a param "
+                            "(a BatchNorm's running statistics are never solver params: see bn_global_stats)")
+            frozen.update(hit)
+        trainable = [pn for pn in cand if pn not in frozen]
+        if not trainable:
+            raise RtErr("ConvPipeBck.init: Freeze leaves nothing trainable: every param of the pipe is frozen, so a step would compute no gradient")
+        for nn in fz.keep_grads:
+            if nn not in cp.nodes:
+                raise RtErr(f"Freeze: keep_grads names {nn!r}, which is no node of the pipe (`{bp.label_node}` has no gradient)")
+        # the forward walk: need[node] = does the node's CURRENT value need a gradient (an in-place op rewrites the node it reads)
+        need = {cp.in_node: cp.in_node in fz.keep_grads}
+        in_need: Dict[str, List[bool]] = {}
+        op_train: Dict[str, bool] = {}
+        for o in fwd:
+            data_bots = [b for b in o.bots if b in cp.nodes]
+            in_need[o.tag] = [need.get(b, False) for b in data_bots]
+            op_train[o.tag] = any(pn not in frozen for pn in params_of[o.tag])
+            need[o.tops[0]] = op_train[o.tag] or any(in_need[o.tag]) or (not o.in_place and o.tops[0] in fz.keep_grads)
+        glob_x = {x for x, (bn, _, _) in bn_runs.items() if bn.tag in bn_global}
+        keep: Dict[str, List[bool]] = {}
+        for b in bp.bck_ops():
+            if b.type == "Reduce":
+                continue
+            f = b.tag[:-4]   # <forward tag>_bck
+            if b.type in ("BckConv", "BckScale"):
+                k = [in_need[f][0], op_train[f], op_train[f]]
+                if b.type == "BckScale" and b.bots[1] not in glob_x and in_need[f][0]:
+                    k[1] = k[2] = True   # a training BatchNorm's data gradient reads the two sums
+            else:
+                k = list(in_need[f])
+            keep[b.tag] = k
+        written = {tp for b in bp.bck_ops() if b.type != "Reduce" for i, tp in enumerate(b.tops) if keep[b.tag][i]}
+        written.update(tp for o in bp.fwd_ops() for tp in o.tops)
+        for b in bp.bck_ops():   # a Reduce at a fan-out is kept or dropped whole: every reader of a node that needs a gradient produces its partial
+            if b.type == "Reduce":
+                have = [i in written for i in b.bots]
+                if any(have) != all(have):
+                    raise RtErr(f"ConvPipeBck.init: Freeze: {b.tag} would sum {sum(have)} of its {len(have)} partial gradients")
+                keep[b.tag] = [all(have)]
+                if all(have):
+                    written.add(b.tops[0])
+        self._dropped_vars = {tp for b in bp.bck_ops() for tp in b.tops} - written
+        self.sgd_params = trainable
+        self.frozen = {"params": [pn for pn in cand if pn in frozen], "dropped_calls": [b.tag for b in bp.bck_ops() if not any(keep[b.tag])],
+                       "bn_global": [tg for tg in bn_tags if tg in bn_global]}
+        return keep, set(bn_global)
 
     @staticmethod
     def _plan_bn_runs(bp: BckPipe) -> Dict[str, tuple]:
@@ -1021,6 +1164,9 @@ class ConvPipeBck:
         rtc = self.rtc
         if graph and self._graph is None:
             raise RtErr("ConvPipeBck.run_bck(graph=True): no captured graph -- call capture_graph() first")
+        for v in to_get_vns:
+            if v in self._dropped_vars:
+                raise RtErr(f"ConvPipeBck.run_bck: {v!r} is not computed by this driver: {WHY_DROPPED}")
         if self.input_transform is not None and self.bp.cp.in_node in to_set_vns:
             raise RtErr(f"ConvPipeBck.run_bck: the driver was built with an input_transform: its {DATA_XF_TAG} call writes {self.bp.cp.in_node!r} from {DATA_RAW_VAR!r} on every "
                         f"pass and would overwrite what is fed; feed {DATA_RAW_VAR!r} (uint8), or build the driver without input_transform")

@@ -508,7 +508,15 @@ BN_OP_FUNCS: Dict[str, tuple] = {
     "BnBckIn": ("hip_bn_bck_in",),
     "FanOut": ("hip_fan_out",),
 }
-BN_FUNCS = tuple(v[0] for v in BN_OP_FUNCS.values())
+# BatchNorm on its running pair (fine-tuning with frozen statistics), a table of its own again (BN_OP_FUNCS is pinned): what ConvPipeBck runs for a
+# [BatchNorm, Scale (, ReLU)] run that Freeze(bn_global_stats=...) lists
+BNF_OP_FUNCS: Dict[str, tuple] = {
+    "BnfPrep": ("hip_bnf_prep",),
+    "BnfBck": ("hip_bnf_bck",),
+    "BnfBckIn": ("hip_bnf_bck_in",),
+}
+BNF_FUNCS = tuple(v[0] for v in BNF_OP_FUNCS.values())
+BN_FUNCS = tuple(v[0] for v in BN_OP_FUNCS.values()) + BNF_FUNCS
 
 
 def _as_f32(v: float) -> float:
@@ -528,7 +536,7 @@ def _bn_func_op(t: str, dims, tens, chans, **scalars) -> Op:
         v[k] = Nda(None, tn, (_as_f32(val) if tn == "float" else val,))
     a = Op({"type": t}, v)
     a.bn_geom()
-    a.set_func_name(BN_OP_FUNCS[t][0])
+    a.set_func_name((BN_OP_FUNCS[t] if t in BN_OP_FUNCS else BNF_OP_FUNCS[t])[0])
     return a
 
 
@@ -555,6 +563,25 @@ def bn_bck_in_func_op(dims) -> Op:
     """-> hip_bn_bck_in: dx = (scale * inv_std) * ((dy - bias_grad_loss / N) - xh * (scale_grad_loss / N)).  Args in, mean, inv_std, scale, scale_grad_loss,
     bias_grad_loss, out_grad_loss (IN), in_grad_loss (OUT, may be out_grad_loss's var)."""
     return _bn_func_op("BnBckIn", dims, ("in", "out_grad_loss", "in_grad_loss"), ("mean", "inv_std", "scale", "scale_grad_loss", "bias_grad_loss"))
+
+
+def bnf_prep_func_op(dims, eps: float) -> Op:
+    """-> hip_bnf_prep, a BatchNorm on its running pair: args run_mean, run_var (IN, only read), mean, inv_std (OUT), float chan=C of the tensor `dims` (which the op
+    carries as `in`; no var is bound to it).  mean = run_mean (the bits), inv_std = 1 / sqrtf(run_var + eps): what hip_bn_fwd and hip_bnf_bck then take."""
+    return _bn_func_op("BnfPrep", dims, ("in",), ("run_mean", "run_var", "mean", "inv_std"), eps=("float", float(eps)))
+
+
+def bnf_bck_func_op(dims, slab: int = 0) -> Op:
+    """-> hip_bnf_bck, the whole backward pass of a [BatchNorm on its running pair, Scale] run in ONE pass over in and out_grad_loss: scale_grad_loss = SUM dy * xh,
+    bias_grad_loss = SUM dy in hip_bn_bck_sums' chain (the same bits), dx = (scale * inv_std) * dy.  Args in, mean, inv_std, scale, out_grad_loss (IN), in_grad_loss (OUT,
+    may be out_grad_loss's var), scale_grad_loss, bias_grad_loss (OUT)."""
+    return _bn_func_op("BnfBck", dims, ("in", "out_grad_loss", "in_grad_loss"), ("mean", "inv_std", "scale", "scale_grad_loss", "bias_grad_loss"), slab=("uint32_t", int(slab)))
+
+
+def bnf_bck_in_func_op(dims) -> Op:
+    """-> hip_bnf_bck_in, the data gradient alone (both Scale params frozen): dx = (scale * inv_std) * dy.  Args inv_std, scale, out_grad_loss (IN), in_grad_loss (OUT,
+    may be out_grad_loss's var); the op carries `in` for the dims, no var is bound to it."""
+    return _bn_func_op("BnfBckIn", dims, ("in", "out_grad_loss", "in_grad_loss"), ("inv_std", "scale"))
 
 
 def fan_out_func_op(dims, n: int) -> Op:
@@ -797,6 +824,10 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_bn_bck_sums": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("out_grad_loss", "IN"), ("scale_grad_loss", "OUT"), ("bias_grad_loss", "OUT")),
     "hip_bn_bck_in": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("scale", "IN"), ("scale_grad_loss", "IN"), ("bias_grad_loss", "IN"), ("out_grad_loss", "IN"), ("in_grad_loss", "OUT")),
     "hip_fan_out": (("in", "IN"),),
+    # BatchNorm on its running pair (this backend's own; eps / slab ride in the op)
+    "hip_bnf_prep": (("run_mean", "IN"), ("run_var", "IN"), ("mean", "OUT"), ("inv_std", "OUT")),
+    "hip_bnf_bck": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("scale", "IN"), ("out_grad_loss", "IN"), ("in_grad_loss", "OUT"), ("scale_grad_loss", "OUT"), ("bias_grad_loss", "OUT")),
+    "hip_bnf_bck_in": (("inv_std", "IN"), ("scale", "IN"), ("out_grad_loss", "IN"), ("in_grad_loss", "OUT")),
     # the training BatchNorm over img chunks: the args of their hip_bn_* twins (chunks rides in the op)
     "hip_bnc_stats": (("in", "IN"), ("mean", "OUT"), ("inv_std", "OUT"), ("run_mean", "INOUT"), ("run_var", "INOUT")),
     "hip_bnc_fwd": (("in", "IN"), ("mean", "IN"), ("inv_std", "IN"), ("scale", "IN"), ("bias", "IN"), ("out", "OUT")),

@@ -212,7 +212,7 @@ int bodahip_explain_plan(const char *op_lexp, int num_cus, const char *tile, cha
   ABI_CATCH }
 int bodahip_native_funcs(char *buf, size_t buf_sz) {
   ABI_TRY
-  static char const *const modes[] = {"on_shards", "replicated_only", "needs_flag", "refused", "replicated_vars"};
+  static char const *const modes[] = {"on_shards", "replicated_only", "needs_flag", "refused", "replicated_vars", "one_device"};
   string s;
   for (native_func_t const &f : kNativeFuncs) {
     string flags; for (auto const &fl : kOpFlagNames) if (f.flags & fl.flag) flags += string(flags.empty() ? "" : ",") + fl.name;

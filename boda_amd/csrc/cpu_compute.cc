@@ -419,6 +419,27 @@ void bn_bck_in(bn_op_t const &b, float const *in, float const *dy, float *dx, fl
     }
   }
 }
+// BatchNorm on its running pair (hip_bnf_prep / hip_bnf_bck / hip_bnf_bck_in): the statistics are constants, dx = (scale * inv_std) * dy
+void bnf_prep(bn_op_t const &b, float const *run_mean, float const *run_var, float *mean, float *inv_std) {
+  for (long c = 0; c < b.C; ++c) {
+    float const ve = run_var[c] + b.eps;
+    float const sd = sqrtf(ve);
+    memcpy(mean + c, run_mean + c, sizeof(float));   // the bits
+    inv_std[c] = 1.0f / sd;
+  }
+}
+void bnf_bck_in(bn_op_t const &b, float const *dy, float *dx, float const *inv_std, float const *scale) {
+#pragma omp parallel for schedule(static)
+  for (long pl = 0; pl < b.B * b.C; ++pl) {
+    float const k = scale[pl % b.C] * inv_std[pl % b.C];
+    for (long e = pl * b.HW; e < (pl + 1) * b.HW; ++e) dx[e] = k * dy[e];
+  }
+}
+// (the sums first, over the unwritten dy: dx may be dy's buffer)
+void bnf_bck(bn_op_t const &b, float const *in, float const *dy, float *dx, float const *mean, float const *inv_std, float const *scale, float *sg, float *bg) {
+  bn_bck_sums(b, in, dy, mean, inv_std, sg, bg);
+  bnf_bck_in(b, dy, dx, inv_std, scale);
+}
 // ---- the eval family (kernels/eval_f32.hip states the rules): the same tests and the same fp32 chain, one rounding per line
 void accuracy(float const *in, float const *label, uint32_t *rank, long B, long C) {
 #pragma omp parallel for schedule(static)
@@ -554,7 +575,7 @@ struct cpu_compute_t : public rtc_compute_t {
       (void)op_img_shards_flag(fi.op);   // (likewise; here there is one shard: a flagged call is the unflagged one)
       (void)op_bf16_operands(fi.op);   // (str_val hip_operands: refused where the function has no bf16-operand form)
       if (f->family == kFamSgd) (void)sgd_op_of_op(fi.op);   // (the op must be whole)
-      if (f->family == kFamBn || f->family == kFamBnc) (void)bn_op_of_op(fi.op);   // (likewise)
+      if (f->family == kFamBn || f->family == kFamBnc || f->family == kFamBnf) (void)bn_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamSolver) (void)solver_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamEval) (void)eval_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamData) (void)data_op_of_op(fi.op);   // (likewise)
@@ -948,6 +969,9 @@ struct cpu_compute_t : public rtc_compute_t {
     case 2: bn_fwd(b, T[0], T[1], Cv[0], Cv[1], Cv[2], Cv[3]); break;
     case 3: bn_bck_sums(b, T[0], T[1], Cv[0], Cv[1], Cv[2], Cv[3]); break;
     case 4: bn_bck_in(b, T[0], T[1], T[2], Cv[0], Cv[1], Cv[2], Cv[3], Cv[4]); break;
+    case 6: bnf_prep(b, Cv[0], Cv[1], Cv[2], Cv[3]); break;
+    case 7: bnf_bck(b, T[0], T[1], T[2], Cv[0], Cv[1], Cv[2], Cv[3], Cv[4]); break;
+    case 8: bnf_bck_in(b, T[0], T[1], Cv[0], Cv[1]); break;
     default: for (int i = 0; i < b.nout; ++i) memcpy(T[(size_t)(1 + i)], T[0], sizeof(float) * (size_t)b.elems);
     }
   }
@@ -1014,7 +1038,7 @@ struct cpu_compute_t : public rtc_compute_t {
     (void)op_img_shards_flag(fi.op);   // (likewise)
     double const tb = now_ms();
     if (f.family == kFamSgd) run_sgd_update(fi.op, am);
-    else if (f.family == kFamBn || f.family == kFamBnc) run_bn(fi.op, am);
+    else if (f.family == kFamBn || f.family == kFamBnc || f.family == kFamBnf) run_bn(fi.op, am);
     else if (f.family == kFamSolver) run_solver(fi.op, am);
     else if (f.family == kFamEval) run_eval(fi.op, am);
     else if (f.family == kFamData) run_data(fi.op, am);

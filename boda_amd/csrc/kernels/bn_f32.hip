@@ -18,6 +18,14 @@
 //   hip_bn_bck_in    in, mean, inv_std, scale, scale_grad_loss, bias_grad_loss, out_grad_loss -> in_grad_loss (may be out_grad_loss's buffer)
 //       k = scale[c] * inv_std[c];  mb = bias_grad_loss[c] / fN;  mg = scale_grad_loss[c] / fN;  dx = k * ((dy - mb) - xh * mg)
 //   hip_fan_out      in -> outs_0 .. outs_{n-1}, 2 <= n <= 8: every outs_i = in bit for bit, in read once
+// BatchNorm ON THE RUNNING PAIR (fine-tuning with frozen statistics): the statistics are constants of the step, so the data gradient loses its
+// two mean terms and the running pair is only read.  hip_bn_fwd is the forward pass as it is, on hip_bnf_prep's outputs
+//   hip_bnf_prep     run_mean, run_var -> mean, inv_std.  eps rides in the op
+//       mean = run_mean (the bits);  ve = run_var + eps;  sd = sqrtf(ve);  inv_std = 1 / sd          (the arithmetic of the finalising step of hip_bn_stats)
+//   hip_bnf_bck      in, mean, inv_std, scale, out_grad_loss -> in_grad_loss (may be out_grad_loss's buffer), scale_grad_loss, bias_grad_loss
+//       scale_grad_loss = SUM dy * xh,  bias_grad_loss = SUM dy: the chain of hip_bn_bck_sums, term for term -- the same bits on the same mean / inv_std
+//       k = scale[c] * inv_std[c];  dx = k * dy, stored by the thread that owns the element in that chain: ONE pass over in and out_grad_loss
+//   hip_bnf_bck_in   inv_std, scale, out_grad_loss -> in_grad_loss (may be out_grad_loss's buffer):  k = scale[c] * inv_std[c];  dx = k * dy.  Reads no `in`
 //
 // THE ORDER OF THE THREE SUMS (S1, S2, and the pair of hip_bn_bck_sums) is this chain, the same on every backend, run to run, whatever the dispatch order:
 //   * a channel's elements are numbered e = img * HW + pel, 0 <= e < N.  Slab s holds e in [s * slab, min(N, (s + 1) * slab)); slab (a multiple of 4) and the slab
@@ -42,7 +50,7 @@
 // added in chunk order, then FIN=3 (mean = S1 / fN alone), FIN=1 (the finalising arithmetic below, verbatim) or FIN=2 (the raw pair).  On several devices chunk i is
 // device i's shard; the totals are copied between the launches, no kernel reads another device's memory.
 //
-// -D parameters: KNAME OP, then  1: MODE (0 S1, 1 S2, 2 the bck_sums pair, 3 S2 with mean from memory) | 2: FIN (1 stats, 2 bck_sums, 3 mean alone, 4 one raw sum), XCH | 3: RELU | 5: NOUT.
+// -D parameters: KNAME OP, then  1: MODE (0 S1, 1 S2, 2 the bck_sums pair, 3 S2 with mean from memory), DX (MODE 2 only: 1 = hip_bnf_bck, the owner also stores dx) | 2: FIN (1 stats, 2 bck_sums, 3 mean alone, 4 one raw sum), XCH | 3: RELU | 5: NOUT.
 // Host side: bn_slab_plan / bn_op_of_op (rtc_types.h), plan_bn (native_plan.cc), native_kernels_t::bn_call (native_kernels.cc), the argument checks in native_run.cc.
 
 #ifndef __HIPCC_RTC__
@@ -55,6 +63,12 @@
 #include "device_prelude.h"
 
 #if OP == 1
+#ifndef DX
+#define DX 0
+#endif
+#if DX && MODE != 2
+#error "bn_f32.hip: DX=1 is a form of MODE=2"
+#endif
 #if MODE == 2
 #define NSUM 2
 #else
@@ -82,6 +96,9 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
   float const mean = S1 / p.fN;
 #elif MODE == 2
   float const mean = p.c0[c], istd = p.c1[c];
+#if DX
+  float const kk = p.c2[c] * istd;
+#endif
 #elif MODE == 3
   float const mean = p.c0[c];
 #endif
@@ -97,6 +114,9 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
 #if MODE == 2
       f32x4 D[4];
 #endif
+#if DX
+      long O[4];
+#endif
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if (q + 256 * k < nq) {
@@ -104,6 +124,9 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
           X[k] = *(f32x4 const *)(p.in + off);
 #if MODE == 2
           D[k] = *(f32x4 const *)(p.dy + off);
+#endif
+#if DX
+          O[k] = off;
 #endif
         }
         pel += p.step_pel; img += p.step_img;
@@ -114,6 +137,13 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
         if (q + 256 * k < nq) {
 #if MODE == 2
           TERM(X[k].x, D[k].x) TERM(X[k].y, D[k].y) TERM(X[k].z, D[k].z) TERM(X[k].w, D[k].w)
+#if DX
+          // THE IN-PLACE STORE (out may be dy's buffer).  Element e of channel c belongs to exactly one (channel, slab) workgroup and there to exactly one chain, this
+          // thread: nobody else loads or stores it, in this launch or in the FIN launch behind it.  All of this round's loads of this thread (the loop above) are issued
+          // before this store, and a later round touches other elements: the store can neither race with a load of dy[e] nor be read back
+          f32x4 v; v.x = kk * D[k].x; v.y = kk * D[k].y; v.z = kk * D[k].z; v.w = kk * D[k].w;
+          *(f32x4 *)(p.out + O[k]) = v;
+#endif
 #else
           TERM(X[k].x, 0) TERM(X[k].y, 0) TERM(X[k].z, 0) TERM(X[k].w, 0)
 #endif
@@ -126,6 +156,9 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
 #if MODE == 2
       float D[4];
 #endif
+#if DX
+      long O[4];
+#endif
       int const r = 4 * q;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -137,6 +170,9 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
 #if MODE == 2
           D[j] = p.dy[off];
 #endif
+#if DX
+          O[j] = off;
+#endif
         }
       }
 #pragma unroll
@@ -144,6 +180,9 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
         if (r + j < len) {
 #if MODE == 2
           TERM(X[j], D[j])
+#if DX
+          p.out[O[j]] = kk * D[j];   // (the same ownership: element r + j of the slab is this chain's alone, and its four loads of the round came first)
+#endif
 #else
           TERM(X[j], 0)
 #endif
@@ -311,6 +350,38 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
   }
 }
 
+#elif OP == 6
+extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
+  int const c = (int)(blockIdx.x * 256 + threadIdx.x);   // one owner per channel; c0 / c1 = the running pair, only read
+  if (c >= p.C) return;
+  float const rm = p.c0[c], rv = p.c1[c];
+  float const ve = rv + p.eps;
+  float const sd = sqrtf(ve);
+  p.w0[c] = rm; p.w1[c] = 1.0f / sd;
+}
+
+#elif OP == 7
+extern "C" __global__ __launch_bounds__(256) void KNAME(bn_args_t const p) {
+  long const id = (long)blockIdx.x * 256 + threadIdx.x;   // (plane, unit of the plane) as for OP 3 / 4; c0 = inv_std, c1 = scale
+  if (id >= p.n) return;
+  int const units = p.quads + (p.HW - 4 * p.quads);
+  long const plane = id / units;
+  int const u = (int)(id - plane * units);
+  int const c = (int)(plane % p.C);
+  float const kk = p.c1[c] * p.c0[c];
+  long const base = plane * p.HW;
+  if (u < p.quads) {   // (out may be dy's buffer: this thread alone loads and stores this quad, the load first)
+    f32x4 const d = ((f32x4 const *)(p.dy + base))[u];
+    f32x4 v;
+    v.x = kk * d.x; v.y = kk * d.y; v.z = kk * d.z; v.w = kk * d.w;
+    ((f32x4 *)(p.out + base))[u] = v;
+  } else {
+    long const e = base + 4L * p.quads + (u - p.quads);
+    float const d = p.dy[e];
+    p.out[e] = kk * d;
+  }
+}
+
 #else
-#error "bn_f32.hip: -DOP=1..5"
+#error "bn_f32.hip: -DOP=1..7"
 #endif

@@ -66,7 +66,7 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
   case kFamSolver:   // likewise: the op whole, the code object built now
     (void)get_kernel(impl, host, plan_solver(solver_op_of_op(fi.op)).p);
     break;
-  case kFamBn: case kFamBnc:   // the op must be whole; the code objects of all the call's launches are built NOW, so that a first run inside a graph capture finds them
+  case kFamBn: case kFamBnc: case kFamBnf:   // the op must be whole; the code objects of all the call's launches are built NOW, so that a first run inside a graph capture finds them
     for (bn_launch_t const &l : plan_bn(bn_op_of_op(fi.op)).ls) (void)get_kernel(impl, host, l.p);
     break;
   case kFamEval:   // likewise: the op whole, the code object built now (an eval pass may first run inside a graph capture)
@@ -1007,6 +1007,9 @@ void native_kernels_t::bn_call(bn_op_t const &b, float *const *tens, float *cons
   case 2: a.in = tens[0]; a.out = tens[1]; a.c0 = chans[0]; a.c1 = chans[1]; a.c2 = chans[2]; a.c3 = chans[3]; break;
   case 3: a.in = tens[0]; a.dy = tens[1]; a.c0 = chans[0]; a.c1 = chans[1]; a.w0 = chans[2]; a.w1 = chans[3]; break;
   case 4: a.in = tens[0]; a.dy = tens[1]; a.out = tens[2]; a.c0 = chans[0]; a.c1 = chans[1]; a.c2 = chans[2]; a.c3 = chans[3]; a.c4 = chans[4]; break;
+  case 6: a.c0 = chans[0]; a.c1 = chans[1]; a.w0 = chans[2]; a.w1 = chans[3]; break;
+  case 7: a.in = tens[0]; a.dy = tens[1]; a.out = tens[2]; a.c0 = chans[0]; a.c1 = chans[1]; a.c2 = chans[2]; a.w0 = chans[3]; a.w1 = chans[4]; break;
+  case 8: a.dy = tens[0]; a.out = tens[1]; a.c0 = chans[0]; a.c1 = chans[1]; break;
   default: a.in = tens[0]; for (int i = 0; i < b.nout; ++i) a.outs[i] = tens[1 + i];
   }
   if (bp.ws_bytes) {
@@ -1029,9 +1032,9 @@ void native_kernels_t::bn_call(bn_op_t const &b, float *const *tens, float *cons
       a.quads = (aligned && (b.HW & 3) == 0) ? 1 : 0;
       a.step_img = (int)(kBnSlabUnit / b.HW); a.step_pel = (int)(kBnSlabUnit % b.HW);
       grid = (uint32_t)(b.C * b.nslabs);
-    } else if (l.op == 2) {
+    } else if (l.op == 2 || l.op == 6) {
       grid = (uint32_t)((b.C + 255) / 256);
-    } else if (l.op == 3 || l.op == 4) {   // quads of a plane: every tensor 16-byte aligned and planes of whole quads, so that every plane starts on a quad
+    } else if (l.op == 3 || l.op == 4 || l.op == 7) {   // quads of a plane: every tensor 16-byte aligned and planes of whole quads, so that every plane starts on a quad
       a.quads = (aligned && (b.HW & 3) == 0) ? (int)(b.HW / 4) : 0;
       a.n = b.B * b.C * (a.quads + (b.HW - 4L * a.quads));
       grid = (uint32_t)((a.n + 255) / 256);

@@ -168,7 +168,8 @@ struct native_kernels_t {
   // hip_data_transform on raw device pointers (kernels/data_f32.hip): ptrs = src, plan, mean, out; d.B is the call's image count
   void data_call(data_op_t const &d, void *const *ptrs);
   void shard_sum(float const *slabs, float *out, int nslabs, long stride, long n);
-  // hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out on raw device pointers (kernels/bn_f32.hip): tens / chans in bn_op_t's arg order
+  // hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out -- and hip_bnf_prep / hip_bnf_bck / hip_bnf_bck_in, the BatchNorm on its running pair (kFamBnf)
+  // -- on raw device pointers (kernels/bn_f32.hip): tens / chans in bn_op_t's arg order
   void bn_call(bn_op_t const &b, float *const *tens, float *const *chans);
   // hip_bnc_stats / hip_bnc_bck_sums with more than one chunk, the chunked chain: the whole call on one device, and its pieces -- the call's workspace (slab partials of
   // one chunk; *tots: the totals [chunk][2][C] behind them), one chunk's totals, the cross-chunk step -- which a multi-device backend runs per device (csrc/hip_multi.cc)

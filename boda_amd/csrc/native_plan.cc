@@ -1540,16 +1540,19 @@ bn_plan_t plan_bn(bn_op_t const &b) {
   case 3: add(1, "bodahip_bn_sum", {"-DMODE=2"}); add(2, "bodahip_bn_fin", {"-DFIN=2"}); r.algo_bytes = 2 * T + 4 * Cb; break;
   case 4: add(4, "bodahip_bn_bck_in", {}); r.algo_bytes = 3 * T + 5 * Cb; break;
   case 5: add(5, "bodahip_fan_out", {"-DNOUT=" + std::to_string(b.nout)}); r.algo_bytes = (1.0 + b.nout) * T; break;
+  case 6: add(6, "bodahip_bnf_prep", {}); r.algo_bytes = 4 * Cb; break;
+  case 7: add(1, "bodahip_bn_sum", {"-DMODE=2", "-DDX=1"}); add(2, "bodahip_bn_fin", {"-DFIN=2"}); r.algo_bytes = 3 * T + 5 * Cb; break;   // in, dy read and dx written ONCE each
+  case 8: add(7, "bodahip_bnf_bck_in", {}); r.algo_bytes = 2 * T + 2 * Cb; break;
   default: rt_err("plan_bn: unknown kind");
   }
-  if (b.kind == 1 || b.kind == 3) r.ws_bytes = (size_t)(2 * b.C * b.nslabs) * sizeof(float);
+  if (b.kind == 1 || b.kind == 3 || b.kind == 7) r.ws_bytes = (size_t)(2 * b.C * b.nslabs) * sizeof(float);
   return r;
 }
 string bn_plan_desc(bn_op_t const &b, bn_plan_t const &bp) {
   string s;
   bool const chunked = b.bnc && b.chunks > 1;
   for (bn_launch_t const &l : bp.ls) {
-    long const grid = l.op == 1 ? (chunked ? 0 : b.C * b.nslabs) : l.op == 2 ? (b.C + 255) / 256 : 0;   // (a chunk's sum has its own grid: C x the chunk's slabs)
+    long const grid = l.op == 1 ? (chunked ? 0 : b.C * b.nslabs) : (l.op == 2 || l.op == 6) ? (b.C + 255) / 256 : 0;   // (a chunk's sum has its own grid: C x the chunk's slabs)
     s += (s.empty() ? "" : " | ") + l.p.kname;
     if (grid) s += " grid=" + std::to_string(grid) + " block=256";
     for (size_t i = 1; i < l.p.defs.size(); ++i) s += " " + l.p.defs[i];
@@ -1560,7 +1563,7 @@ string bn_plan_desc(bn_op_t const &b, bn_plan_t const &bp) {
       bn_op_t const cb = bnc_chunk_op("hip_bnc", b, i);
       s += " | chunk " + std::to_string(i) + ": " + (cb.B ? "imgs=" + std::to_string(cb.B) + " slab=" + std::to_string(cb.slab) + " slabs=" + std::to_string(cb.nslabs) : string("empty"));
     }
-  } else if (b.kind == 1 || b.kind == 3) s += " | slab=" + std::to_string(b.slab) + " slabs=" + std::to_string(b.nslabs);
+  } else if (b.kind == 1 || b.kind == 3 || b.kind == 7) s += " | slab="+ std::to_string(b.slab) + " slabs=" + std::to_string(b.nslabs);
   return s;
 }
 

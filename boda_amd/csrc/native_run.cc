@@ -267,7 +267,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     sgd_plan_t const sp = plan_solver(so);
     if (plan_out) *plan_out = solver_plan_desc(so, sp);
     return arch.empty() ? 0 : compile_plan(sp.p, arch, &log).size();
-  } else if (fam == kFamBn || fam == kFamBnc) {   // (kernels/bn_f32.hip: every launch of the call, and the slab plan)
+  } else if (fam == kFamBn || fam == kFamBnc || fam == kFamBnf) {   // (kernels/bn_f32.hip: every launch of the call, and the slab plan)
     bn_op_t const b = bn_op_of_op(op);
     bn_plan_t const bp = plan_bn(b);
     if (plan_out) *plan_out = bn_plan_desc(b, bp);
@@ -913,7 +913,7 @@ void native_kernels_t::run(native_func_t const &f, rtc_func_info_t const &fi, ma
   case kFamBconv: c.run_bconv(); break;
   case kFamBckOp: c.run_bck_op(); break;
   case kFamSgd: c.run_sgd(); break;
-  case kFamBn: case kFamBnc: c.run_bn(); break;
+  case kFamBn: case kFamBnc: case kFamBnf: c.run_bn(); break;
   case kFamSolver: c.run_solver(); break;
   case kFamEval: c.run_eval(); break;
   case kFamData: c.run_data(); break;

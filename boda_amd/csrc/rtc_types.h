@@ -129,7 +129,7 @@ struct op_base_t {
 };
 typedef std::shared_ptr<op_base_t> p_op_base_t;
 // ---- the op flags of a native function.  Which function takes which flag is a column of the one table, native_funcs.h (included at the end of this file), which defines:
-enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver, kFamEval, kFamData };   // selects the handler
+enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver, kFamEval, kFamData, kFamBnf };   // selects the handler
 enum : unsigned { kFlagZinp = 1, kFlagSeedVar = 2, kFlagImgShards = 4, kFlagNhwcResidual = 8 };
 struct op_flag_name_t { char const *name; unsigned flag; };
 constexpr op_flag_name_t kOpFlagNames[] = {{"img_shards", kFlagImgShards}, {"seed_from_var", kFlagSeedVar}, {"zero_if_in_non_pos", kFlagZinp}, {"nhwc_residual", kFlagNhwcResidual}};
@@ -300,14 +300,14 @@ constexpr long kBnMaxSlabs = 4096;     // per channel (only a forced slab length
 constexpr int kFanOutMax = 8;
 constexpr uint32_t kBncMaxChunks = 64;  // of a hip_bnc_stats / hip_bnc_bck_sums call
 struct bn_op_t {
-  int kind = 0;                  // 1 stats, 2 fwd, 3 bck_sums, 4 bck_in, 5 fan_out
+  int kind = 0;                  // 1 stats, 2 fwd, 3 bck_sums, 4 bck_in, 5 fan_out; the BatchNorm on its running pair (kFamBnf): 6 bnf_prep, 7 bnf_bck, 8 bnf_bck_in
   bool bnc = false;              // a hip_bnc_* function (kFamBnc): the sums in the chunked chain, the image count of the call's vars free where the function is per image
   uint32_t chunks = 0, forced = 0;   // bnc, kinds 1, 3: img chunks of the batch; the forced slab length every chunk's plan gets (0: the planner's)
   long B = 0, C = 0, HW = 0, N = 0;   // N = B * HW: the elements of one channel
   long Nglob = 0;                // > 0: the WHOLE batch's N where B / N are a chunk's or a shard's (fN, unb and the N == 1 case are global)
   long n_glob() const { return Nglob ? Nglob : N; }
   long elems = 0;                // of the whole tensor
-  long slab = 0, nslabs = 0;     // kinds 1, 3: elements of a slab of a channel's flat (img, pel) range, slabs per channel
+  long slab = 0, nslabs = 0;     // kinds 1, 3, 7: elements of a slab of a channel's flat (img, pel) range, slabs per channel
   float eps = 0.f, maf = 0.f; uint32_t relu = 0; int nout = 0;
   vect_string tens, chans;       // the tensor args (dims of `in`) and the per-channel args (float chan=C), in the function's arg order
 };
@@ -340,8 +340,10 @@ inline bn_op_t bn_op_of_op(op_base_t const &op) {
   bn_op_t r;
   r.kind = native_func_member(fn, kFamBn);
   if (!r.kind) { r.kind = native_func_member(fn, kFamBnc); r.bnc = r.kind != 0; }
+  bool bnf = false;
+  if (!r.kind) { r.kind = native_func_member(fn, kFamBnf); bnf = r.kind != 0; }
   if (!r.kind) rt_err("'" + fn + "' is none of " + native_family_names(kFamBn));
-  string const type = native_func_type(r.bnc ? kFamBnc : kFamBn, r.kind);
+  string const type = native_func_type(r.bnc ? kFamBnc : bnf ? kFamBnf : kFamBn, r.kind);
   if (!op.has_type() || op.get_type() != type) rt_err(fn + ": a function of op type " + type + ", not " + (op.has_type() ? op.get_type() : string("?")));
   refuse_flags_not_taken(op, fn, "the function");
   auto f32 = [&](string const &an) { if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'"); p_nda_t const &v = op.get(an); if (v->dims.tn != "float" || v->dims.sz() != 0 || !v->rp) rt_err(fn + ": '" + an + "' is not a float scalar"); return *static_cast<float const *>(v->rp); };
@@ -351,6 +353,10 @@ inline bn_op_t bn_op_of_op(op_base_t const &op) {
   case 2: r.tens = {"in", "out"}; r.chans = {"mean", "inv_std", "scale", "bias"}; break;
   case 3: r.tens = {"in", "out_grad_loss"}; r.chans = {"mean", "inv_std", "scale_grad_loss", "bias_grad_loss"}; break;
   case 4: r.tens = {"in", "out_grad_loss", "in_grad_loss"}; r.chans = {"mean", "inv_std", "scale", "scale_grad_loss", "bias_grad_loss"}; break;
+  // (kinds 6 and 8 bind no var to `in`: their op carries it for the dims alone, as every function op of this file does)
+  case 6: r.chans = {"run_mean", "run_var", "mean", "inv_std"}; break;
+  case 7: r.tens = {"in", "out_grad_loss", "in_grad_loss"}; r.chans = {"mean", "inv_std", "scale", "scale_grad_loss", "bias_grad_loss"}; break;
+  case 8: r.tens = {"out_grad_loss", "in_grad_loss"}; r.chans = {"inv_std", "scale"}; break;
   default: {
     uint32_t const n = u32("outs_num");
     if (n < 2 || n > (uint32_t)kFanOutMax) unsup_err(fn + ": outs_num=" + std::to_string(n) + ": 2 to " + std::to_string(kFanOutMax) + " outputs");
@@ -359,6 +365,7 @@ inline bn_op_t bn_op_of_op(op_base_t const &op) {
   } }
   for (string const &an : r.tens) if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'");
   for (string const &an : r.chans) if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'");
+  if (!op.has("in")) rt_err(fn + ": the op has no 'in'");
   dims_t const &in = op.get_dims("in");
   if (in.tn != "float") rt_err(fn + ": in has type " + in.tn + ": fp32 only");
   if (r.kind != 5 && !(in.sz() == 4 && in.names(0) == "img" && in.names(1) == "chan" && in.names(2) == "y" && in.names(3) == "x")) rt_err(fn + ": in must be img:chan:y:x, got " + in.pretty_str());
@@ -372,6 +379,7 @@ inline bn_op_t bn_op_of_op(op_base_t const &op) {
     dims_t const &d = op.get_dims(an);
     if (d.tn != "float" || d.sz() != 1 || d.names(0) != "chan" || (long)d.dims(0) != r.C) rt_err(fn + ": " + an + " dims " + d.tn + " " + d.pretty_str() + ": one float per channel of in " + in.pretty_str());
   }
+  if (r.kind == 6) { r.eps = f32("eps"); if (!(r.eps >= 0.0f)) rt_err(fn + ": eps must not be negative"); }
   if (r.kind == 1) { r.eps = f32("eps"); r.maf = f32("maf"); if (!(r.eps >= 0.0f)) rt_err(fn + ": eps must not be negative"); }
   if (r.kind == 2) { r.relu = u32("relu"); if (r.relu > 1) rt_err(fn + ": relu must be 0 | 1"); }
   if (r.bnc && (r.kind == 1 || r.kind == 3)) {   // the chunked chain: every non-empty chunk gets the plan of its own dims, under the same forced length
@@ -379,7 +387,7 @@ inline bn_op_t bn_op_of_op(op_base_t const &op) {
     if (r.chunks < 1 || r.chunks > kBncMaxChunks) unsup_err(fn + ": chunks=" + std::to_string(r.chunks) + ": 1 to " + std::to_string(kBncMaxChunks) + " img chunks");
     for (uint32_t i = 0; i < r.chunks; ++i) (void)bnc_chunk_op(fn, r, i);   // (refuses a forced slab that cuts a chunk's channel into too many)
     if (r.chunks == 1) { bn_op_t const cb = bnc_chunk_op(fn, r, 0); r.slab = cb.slab; r.nslabs = cb.nslabs; }   // (one chunk: the twin's chain and launches)
-  } else if (r.kind == 1 || r.kind == 3) bn_slab_plan(fn, r.C, r.N, u32("slab"), r.slab, r.nslabs);
+  } else if (r.kind == 1 || r.kind == 3 || r.kind == 7) bn_slab_plan(fn, r.C, r.N, u32("slab"), r.slab, r.nslabs);
   return r;
 }
 // the var-level refusals of a call, the same text on both backends: `vars` = the var bound to every tensor arg followed by every per-channel arg (bn_op_t's order)
@@ -392,6 +400,8 @@ inline void bn_check_aliases(string const &fn, bn_op_t const &b, vect_string con
     bool ok = false;
     if (b.kind == 2 && i == 0 && j == 1) ok = true;                       // hip_bn_fwd: in and out may be one var
     if (b.kind == 4 && i == 1 && j == 2) ok = true;                       // hip_bn_bck_in: in_grad_loss may be out_grad_loss's var
+    if (b.kind == 7 && i == 1 && j == 2) ok = true;                       // hip_bnf_bck likewise (the owning chain loads an element before it stores it)
+    if (b.kind == 8 && i == 0 && j == 1) ok = true;                       // hip_bnf_bck_in likewise
     if (!ok) rt_err(fn + ": args '" + args[i] + "' and '" + args[j] + "' are the same var '" + vars[i] + "'");
   }
 }

@@ -288,6 +288,11 @@ OP_INFO = {
     "BnBckSums": (("in", "mean", "inv_std", "out_grad_loss"), ("scale_grad_loss", "bias_grad_loss"), ("slab",)),
     "BnBckIn": (("in", "mean", "inv_std", "scale", "scale_grad_loss", "bias_grad_loss", "out_grad_loss"), ("in_grad_loss",), ()),
     "FanOut": (("in",), (), ("outs_num",)),
+    # this backend's own: BatchNorm on its running pair (fine-tuning with frozen statistics; csrc/kernels/bn_f32.hip).  BnfPrep and BnfBckIn bind no var to `in`: their op
+    # carries it for the dims alone.  in_grad_loss may be out_grad_loss's var
+    "BnfPrep": (("run_mean", "run_var"), ("mean", "inv_std"), ("eps",)),
+    "BnfBck": (("in", "mean", "inv_std", "scale", "out_grad_loss"), ("in_grad_loss", "scale_grad_loss", "bias_grad_loss"), ("slab",)),
+    "BnfBckIn": (("inv_std", "scale", "out_grad_loss"), ("in_grad_loss",), ()),
     # this backend's own: the evaluation pass of the gradient pipe (csrc/kernels/eval_f32.hip states the rules).  Accuracy: the rank of the true class per image from the
     # logits and the loss's label var.  EvalAccum: the batch's counts and loss into counts (uint32 v=4) / loss_sum (float v=1), which it reads and rewrites, under ctl (uint32
     # v=4 = first, 0, 0, 0).  BnFold: a [BatchNorm, Scale] run's running statistics and scale / bias as the pair (a, b) of conv_pipe.fold_affine
@@ -299,13 +304,14 @@ OP_INFO = {
     "DataTransform": (("src", "plan", "mean"), ("out",), ("scale",)),
 }
 BN_TYPES = ("BnStats", "BnFwd", "BnBckSums", "BnBckIn", "FanOut")
+BNF_TYPES = ("BnfPrep", "BnfBck", "BnfBckIn")
 SOLVER_TYPES = ("SolverUpdate", "GradSumsq", "GradNorm", "GradAccum", "SolverUpdateAcc")
 EVAL_TYPES = ("Accuracy", "EvalAccum", "BnFold")
 DATA_TYPES = ("DataTransform",)
 SOLVER_CHUNK = 4096   # floats of one tensor a workgroup owns; one partial sum of squares per chunk
 
 
-_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + SOLVER_TYPES + EVAL_TYPES + DATA_TYPES
+_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + BNF_TYPES + SOLVER_TYPES + EVAL_TYPES + DATA_TYPES
 
 
 @dataclass
@@ -684,7 +690,7 @@ class Op:
         return dict(B=B, C=C, H=H, W=W, ch=ch, cw=cw, layout=layout, mean_form=forms[(mean.names, mean.sizes)], scale=self.get("scale").v[0])
 
     def bn_geom(self) -> dict:
-        """BnStats / BnFwd / BnBckSums / BnBckIn: float img:chan:y:x tensors of equal dims, the per-channel args float chan=C; FanOut: in and 2 to 8 outs of equal float dims."""
+        """BnStats / BnFwd / BnBckSums / BnBckIn and BnfPrep / BnfBck / BnfBckIn (`in` gives the dims even where no var is bound to it): float img:chan:y:x tensors of equal dims, the per-channel args float chan=C; FanOut: in and 2 to 8 outs of equal float dims."""
         t = self.get_type()
         i = self.get_dims("in")
         if i.tn != "float":
@@ -709,7 +715,9 @@ class Op:
                 raise RtErr(f"{t}: {an} dims {d.pretty()}: one float per channel of in {i.pretty()}")
         if t == "BnStats":
             self.get_f32("eps"); self.get_f32("maf")
-        if t in ("BnStats", "BnBckSums") and self.get_u32("slab") % 4:
+        if t == "BnfPrep" and not self.get_f32("eps") >= 0.0:
+            raise RtErr("BnfPrep: eps must not be negative")
+        if t in ("BnStats", "BnBckSums", "BnfBck") and self.get_u32("slab") % 4:
             raise RtErr(f"{t}: slab={self.get_u32('slab')}: a forced slab length is a multiple of 4")
         if t == "BnFwd" and self.get_u32("relu") not in (0, 1):
             raise RtErr("BnFwd: relu must be 0 | 1")
@@ -825,7 +833,7 @@ def parse_op(line: str) -> Op:
             op.chan_affine_geom()
         elif t == "SgdUpdate":
             op.sgd_geom()
-        elif t in BN_TYPES:
+        elif t in BN_TYPES or t in BNF_TYPES:
             op.bn_geom()
         elif t in SOLVER_TYPES:
             op.solver_geom()

@@ -334,3 +334,42 @@ def transform_spec(text: str, phase: str) -> dict:
             raise RtErr(f"prototxt: Data layer {name!r}: crop_size={crop}: not negative")
         return {"crop_size": crop, "mirror": mirror == "true", "scale": scale, "mean_value": mv, "mean_file": mf}
     raise RtErr(f"prototxt: transform_spec: no Data layer of the {phase} phase")
+
+
+def freeze_spec(text: str, cp=None):
+    """What a net definition says about fine-tuning -> bck_pipe.Freeze.  A Convolution / InnerProduct / Scale layer all of whose
+    `param { lr_mult }` entries are 0 (at least one entry; an entry without lr_mult has Caffe's default 1) becomes a frozen op tag in `params`; a BatchNorm layer with
+    `batch_norm_param { use_global_stats: true }` becomes a `bn_global_stats` entry (none: False).  A BatchNorm layer's own three `lr_mult: 0` blobs are ignored: its
+    statistics are never solver params here.  Layers of every phase are read, each name once.  use_global_stats on a layer that is no BatchNorm is an RtErr.  cp (a
+    ConvPipe, optional): every layer named must then be an op of that pipe, and a name that is not is an RtErr that names it."""
+    from .bck_pipe import Freeze
+    root = parse(text)
+    params: List[str] = []
+    bn_global: List[str] = []
+    seen = set()
+    for L in root.get("layer", []) or root.get("layers", []):
+        name, t = str(_one(L, "name")), str(_one(L, "type")).upper().replace("_", "")
+        if name in seen:
+            continue
+        seen.add(name)
+        bnp = _one(L, "batch_norm_param", {})
+        if isinstance(bnp, dict) and "use_global_stats" in bnp and t != "BATCHNORM":
+            raise RtErr(f"prototxt: freeze_spec: layer {name!r} is a {_one(L, 'type')}, not a BatchNorm: use_global_stats is a BatchNorm layer's")
+        if t == "BATCHNORM":
+            if isinstance(bnp, dict) and str(_one(bnp, "use_global_stats", "false")).lower() == "true":
+                bn_global.append(name)
+            continue
+        if t not in ("CONVOLUTION", "INNERPRODUCT", "SCALE"):
+            continue
+        try:
+            mults = [float(_one(p, "lr_mult", 1.0)) for p in L.get("param", []) if isinstance(p, dict)]
+        except (ValueError, TypeError):
+            raise RtErr(f"prototxt: freeze_spec: layer {name!r}: lr_mult must be a number")
+        if mults and all(m == 0.0 for m in mults):
+            params.append(name)
+    if cp is not None:
+        tags = {o.tag for o in cp.ops}
+        for name in params + bn_global:
+            if name not in tags:
+                raise RtErr(f"prototxt: freeze_spec: layer {name!r} is no op of the pipe {cp.name!r}")
+    return Freeze(params=tuple(params), bn_global_stats=list(bn_global) if bn_global else False)

@@ -57,6 +57,10 @@ result().  Written to profiles/r20_eval.txt.  No figure is required.
 run with img_shards=1.  Step ms is the longest of the devices' times; a call's share counts the time its device-side launches took, not the
 cross-device copies behind them.  No figure for more than one physical GPU is recorded yet.
 
+--freeze SPEC / --bn-global: the full step beside the step under ConvPipeBck(freeze=Freeze(...)), in ONE process in alternating blocks.  SPEC: a
+comma list of param names / op tags / suffixes, or all-but:TAG[,TAG] (a linear probe: --freeze all-but:fc1000).  --bn-global: a leg with every BatchNorm on its running
+pair; with both, a third leg with both.  Per leg the step's median ms, its ratio to the full step's, the calls, and ms per function.  Appended to profiles/r22_freeze.txt.
+    python tools/bck_pipe_bench.py --nets resnet50 --batch 32 --freeze all-but:fc1000 --bn-global
 --img-chunks N: ConvPipeBck(img_chunks=...), the training BatchNorm's sums in the chunked chain and the Eltwise gradients as hip_split copies.
 Legs, ONE PROCESS EACH (a multi-device backend and a one-device backend do not share a process here), in --repeats alternating blocks -- every block starts every leg's
 process anew, runs --warmup steps and times --runs: "default" (the step as it is), "chunks1" (img_chunks=1: the same kernels and bits; expected inside the blocks'
@@ -129,6 +133,63 @@ def fuse_ab(net, batch, runs, warmup, repeats, option="fuse_relu_grad"):
     print(json.dumps({"net": net, "launches_removed": len(u["drv"].calls()) - len(f["drv"].calls()), "folded": f["drv"].fused_relu_grads["folded"],
                       "unfolded": sorted(f["drv"].fused_relu_grads["unfolded"]), "fused_over_unfused": round(statistics.median(f["ms"]) / statistics.median(u["ms"]), 4),
                       "same_loss_bits": loss["unfused"] == loss["fused"]}), flush=True)
+    for w in ways.values():
+        w["drv"].release(); w["rtc"].close()
+
+
+def freeze_of(cp, spec, bn_global):
+    """--freeze SPEC -> Freeze: SPEC a comma list of param names / op tags / suffixes, or all-but:TAG[,TAG...] (every param but those of the ops named)."""
+    from boda_amd.bck_pipe import Freeze, bn_stat_params
+    params = ()
+    if spec.startswith("all-but:"):
+        keep = spec[len("all-but:"):].split(",")
+        stats = set(bn_stat_params(cp))
+        params = tuple(p for p in cp.params if p not in stats and p.rsplit("_", 1)[0] not in keep)
+    elif spec:
+        params = tuple(spec.split(","))
+    return Freeze(params=params, bn_global_stats=bool(bn_global))
+
+
+def freeze_ab(net, batch, runs, warmup, repeats, spec, bn_global):
+    """The full step, (--bn-global) the step with every BatchNorm on its running pair, and (--freeze SPEC) the step under that Freeze, in ONE process in alternating
+    blocks, each leg a ConvPipeBck on a backend instance of its own with the same params and inputs."""
+    import numpy as np
+    from boda_amd.bck_pipe import ConvPipeBck, Freeze, add_bck_ops, host_params
+    from boda_amd.rtc import make_rtc
+    cp = _pipe(net, batch)
+    bp = add_bck_ops(cp)
+    params = host_params(bp, 5)
+    rng = np.random.default_rng(0)
+    data = rng.uniform(-1, 1, cp.nodes["data"].sizes).astype(np.float32)
+    label = rng.integers(0, 1000, (batch, 1, 1)).astype(np.float32)
+    legs = [("full", None)] + ([("bn_global", Freeze(bn_global_stats=True))] if bn_global else []) + ([("freeze", freeze_of(cp, spec, bn_global))] if spec else [])
+    ways = {}
+    for way, fz in legs:
+        rtc = make_rtc("(be=hip)", 0)
+        rtc.init()
+        drv = ConvPipeBck(rtc, freeze=fz)
+        drv.init(add_bck_ops(cp), params)
+        rtc.copy_nda_to_var("data", data); rtc.copy_nda_to_var("label", label)
+        ways[way] = {"rtc": rtc, "drv": drv, "blocks": [], "ms": [], "share": {}}
+    for w in ways.values():
+        for i in range(warmup):
+            w["drv"].set_det_drop_seed(i); w["drv"].run_device_only()
+    for rep_ in range(repeats):
+        for w in ways.values():
+            ms = []
+            for i in range(runs):
+                w["drv"].set_det_drop_seed(warmup + rep_ * runs + i)
+                ms.append(w["drv"].run_device_only())
+                for _, fn, d in w["drv"].per_call_ms:
+                    w["share"][fn] = w["share"].get(fn, 0.0) + d
+            w["ms"] += ms; w["blocks"].append(round(statistics.median(ms), 3))
+    full = statistics.median(ways["full"]["ms"])
+    for way, w in ways.items():
+        step = statistics.median(w["ms"]); fr = w["drv"].frozen
+        print(json.dumps({"net": net, "batch": batch, "way": way, "calls": len(w["drv"].calls()), "step_ms": round(step, 3), "block_medians_ms": w["blocks"], "over_full": round(step / full, 4),
+                          "imgs_per_s": round(batch / (step * 1e-3), 1), "loss": round(float(w["rtc"].copy_var_to_nda("loss").item()), 4),
+                          "frozen_params": len(fr["params"]), "dropped_gradient_ops": len(fr["dropped_calls"]), "bn_global": len(fr["bn_global"]),
+                          "ms_per_step": {k: round(v / len(w["ms"]), 3) for k, v in sorted(w["share"].items(), key=lambda kv: -kv[1])}}), flush=True)
     for w in ways.values():
         w["drv"].release(); w["rtc"].close()
 
@@ -471,6 +532,8 @@ def main(argv=None):
     ap.add_argument("--devices", default="", help="e.g. 0:1:2:3: the plain step on the multi-device backend (be=hip,devices=...), batch sharded on img")
     ap.add_argument("--img-chunks", type=int, default=0, help="A/B, one process per leg: the default step, img_chunks=1, img_chunks=N on one device and, with --devices, on the multi-device backend")
     ap.add_argument("--eval", type=int, default=0, dest="n_eval", help="alternating blocks of --runs training steps and N evaluation batches (eval_pipe.EvalPipe) in one process: ms per eval batch beside ms per step")
+    ap.add_argument("--freeze", default="", help="A/B in one process: the full step beside the step under Freeze(params=SPEC): a comma list of param names / op tags / suffixes, or all-but:TAG[,TAG]")
+    ap.add_argument("--bn-global", action="store_true", help="A/B in one process: the full step beside the step with every BatchNorm on its running pair; with --freeze the third leg has both")
     ap.add_argument("--raw", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--child", default="")
     a = ap.parse_args(argv)
@@ -486,14 +549,18 @@ def main(argv=None):
         ap.error("--solver is a comparison of its own on one device")
     if a.n_eval and (a.graph or a.fuse_relu_grad or a.sgd or a.fuse_filts_biases or a.grad_operands or a.solver or a.devices or a.img_chunks):
         ap.error("--eval is a comparison of its own on one device")
+    if (a.freeze or a.bn_global) and (a.graph or a.fuse_relu_grad or a.sgd or a.fuse_filts_biases or a.grad_operands or a.solver or a.devices or a.img_chunks or a.n_eval):
+        ap.error("--freeze / --bn-global are a comparison of their own on one device")
     if a.n_eval < 0:
         ap.error("--eval N: at least 1 batch")
     if a.clip and not a.solver:
         ap.error("--clip goes with --solver")
     if a.iter_size != 1 and (not a.solver or a.iter_size < 1):
         ap.error("--iter-size goes with --solver and is at least 1")
-    a.out = a.out or os.path.join(ROOT, "profiles", "r20_eval.txt" if a.n_eval else "r17_resnet50_chunks.txt" if a.img_chunks else "r16_step_bf16.txt" if a.grad_operands else "r19_grad_accum.txt" if a.solver and a.iter_size > 1 else "r18_solver.txt" if a.solver else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r22_freeze.txt" if (a.freeze or a.bn_global) else "r20_eval.txt" if a.n_eval else "r17_resnet50_chunks.txt" if a.img_chunks else "r16_step_bf16.txt" if a.grad_operands else "r19_grad_accum.txt" if a.solver and a.iter_size > 1 else "r18_solver.txt" if a.solver else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
     if a.child:
+        if a.freeze or a.bn_global:
+            return freeze_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, a.freeze, a.bn_global)
         if a.n_eval:
             return eval_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, a.n_eval)
         if a.grad_operands:
@@ -524,15 +591,16 @@ def main(argv=None):
         cmd += ["--sgd", "--repeats", str(a.repeats)] if a.sgd else []
         cmd += ["--solver", a.solver, "--clip", str(a.clip), "--repeats", str(a.repeats)] + (["--swap"] if a.swap else []) + (["--iter-size", str(a.iter_size)] if a.iter_size > 1 else []) if a.solver else []
         cmd += ["--devices", a.devices] if a.devices else []
+        cmd += (["--freeze", a.freeze] if a.freeze else []) + (["--bn-global"] if a.bn_global else []) + (["--repeats", str(a.repeats)] if (a.freeze or a.bn_global) else [])
         cmd += ["--eval", str(a.n_eval), "--repeats", str(a.repeats)] if a.n_eval else []
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:   # nothing more is started on the GPU after a failure
             print(f"{net}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
             return r.returncode
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
-        print("\n".join(lines[-4:] if (a.graph or a.sgd or a.grad_operands) else lines[-3:] if (a.fuse_relu_grad or a.fuse_filts_biases or a.solver) else lines[-1:]), flush=True)
-    with open(a.out, "w") as f:
-        extra = f" --eval {a.n_eval} --repeats {a.repeats}" if a.n_eval else f" --img-chunks {a.img_chunks}{' --devices ' + a.devices if a.devices else ''} --repeats {a.repeats}" if a.img_chunks else f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --solver {a.solver} --clip {a.clip}{' --swap' if a.swap else ''}{f' --iter-size {a.iter_size}' if a.iter_size > 1 else ''} --repeats {a.repeats}" if a.solver else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
+        print("\n".join(lines[-3:] if (a.freeze or a.bn_global) else lines[-4:] if (a.graph or a.sgd or a.grad_operands) else lines[-3:] if (a.fuse_relu_grad or a.fuse_filts_biases or a.solver) else lines[-1:]), flush=True)
+    with open(a.out, "a" if (a.freeze or a.bn_global) else "w") as f:     # (profiles/r22_freeze.txt also holds tools/bn_bench.py --frozen's record)
+        extra = f"{' --freeze ' + a.freeze if a.freeze else ''}{' --bn-global' if a.bn_global else ''} --repeats {a.repeats}" if (a.freeze or a.bn_global) else f" --eval {a.n_eval} --repeats {a.repeats}" if a.n_eval else f" --img-chunks {a.img_chunks}{' --devices ' + a.devices if a.devices else ''} --repeats {a.repeats}" if a.img_chunks else f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --solver {a.solver} --clip {a.clip}{' --swap' if a.swap else ''}{f' --iter-size {a.iter_size}' if a.iter_size > 1 else ''} --repeats {a.repeats}" if a.solver else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
         f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 

@@ -13,6 +13,11 @@ still holds the wait for the host: such a figure is a dispatch time, not a kerne
 
     python tools/bn_bench.py [--batch 64] [--runs 20] [--warmup 5] [--repeats 3] [--out profiles/r14_bn_train.txt]
 
+--frozen: instead, the backward pass of a BatchNorm on its running pair -- hip_bnf_bck, ONE pass over in and out_grad_loss that leaves both sums
+and dx (3 tensor passes) -- beside the training BatchNorm's hip_bn_bck_sums + hip_bn_bck_in (5) on the same vars, per shape in microseconds and GB/s beside the recorded
+copy rate, in the same alternating blocks; no torch side.  The records are APPENDED to --out (default profiles/r22_freeze.txt) under a comment line with the command.
+    python tools/bn_bench.py --frozen [--batch 32]
+
 A measurement path that finds no GPU fails.  Run it under a time limit (timeout -k 10 600 python tools/bn_bench.py)."""
 import argparse
 import json
@@ -24,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 COPY_RATE_GBPS = 6290.0
-PASSES = {"hip_bn_stats": 1, "hip_bn_fwd": 2, "hip_bn_bck_sums": 2, "hip_bn_bck_in": 3}
+PASSES = {"hip_bn_stats": 1, "hip_bn_fwd": 2, "hip_bn_bck_sums": 2, "hip_bn_bck_in": 3, "hip_bnf_bck": 3}
 
 
 def bn_shapes(batch):
@@ -40,14 +45,89 @@ def bn_shapes(batch):
     return out
 
 
+def frozen_main(a):
+    """--frozen: hip_bnf_bck beside hip_bn_bck_sums + hip_bn_bck_in, one process, alternating blocks."""
+    import numpy as np
+    import torch   # (before the package, as in main; only asked whether there is a GPU)
+    if not torch.cuda.is_available():
+        raise SystemExit("bn_bench: no GPU")
+    from boda_amd.cnn_op import bn_bck_in_func_op, bn_bck_sums_func_op, bnf_bck_func_op, bnf_prep_func_op, pipe_func_args
+    from boda_amd.op import Dims
+    from boda_amd.rtc import RtcArg, RtcFuncCall, RtcFuncInfo, make_rtc
+    rtc = make_rtc("(be=hip)", 0)
+    rtc.init()
+    lines = []
+    for shape in bn_shapes(a.batch):
+        B, C, H, W = shape
+        d = Dims.make("float", img=B, chan=C, y=H, x=W)
+        ch = Dims(("chan",), (C,), "float")
+        rng = np.random.default_rng([B, C, H, W])
+        vals = {"bb_x": rng.standard_normal(shape, dtype=np.float32) * 1.5 + 0.4, "bb_dy": rng.standard_normal(shape, dtype=np.float32), "bb_dx": None, "bb_dxf": None}
+        chans = {"bb_rm": rng.uniform(-1, 1, C).astype(np.float32), "bb_rv": rng.uniform(0.5, 2, C).astype(np.float32), "bb_mean": None, "bb_istd": None,
+                 "bb_scale": rng.uniform(0.5, 1.5, C).astype(np.float32), "bb_sg": None, "bb_bg": None, "bb_sgf": None, "bb_bgf": None}
+        for vs, dd in ((vals, d), (chans, ch)):
+            for vn, v in vs.items():
+                rtc.create_var_with_dims(vn, dd)
+                if v is not None:
+                    rtc.copy_nda_to_var(vn, v)
+        common = {"in": "bb_x", "mean": "bb_mean", "inv_std": "bb_istd"}
+        funcs = [(bnf_prep_func_op(d, 1e-5), {"run_mean": "bb_rm", "run_var": "bb_rv", "mean": "bb_mean", "inv_std": "bb_istd"}),
+                 (bn_bck_sums_func_op(d), dict(common, out_grad_loss="bb_dy", scale_grad_loss="bb_sg", bias_grad_loss="bb_bg")),
+                 (bn_bck_in_func_op(d), dict(common, scale="bb_scale", scale_grad_loss="bb_sg", bias_grad_loss="bb_bg", out_grad_loss="bb_dy", in_grad_loss="bb_dx")),
+                 (bnf_bck_func_op(d), dict(common, scale="bb_scale", out_grad_loss="bb_dy", in_grad_loss="bb_dxf", scale_grad_loss="bb_sgf", bias_grad_loss="bb_bgf"))]
+        calls = []
+        for i, (f, args) in enumerate(funcs):
+            spec = pipe_func_args(f)
+            rtc.compile([RtcFuncInfo(f"bb_f{i}", "", [an for an, _ in spec], f)])
+            calls.append((f.get_func_name(), RtcFuncCall(f"bb_f{i}", {an: RtcArg.var(args[an]) for an, _ in spec})))
+        rtc.run(calls[0][1]); rtc.finish_and_sync(); rtc.release_per_call_id_data()     # mean / inv_std from the running pair, once
+
+        def block(n, keep):
+            for fn, call in calls[1:]:
+                ids = [rtc.run(call) for _ in range(n)]
+                rtc.finish_and_sync()
+                if keep is not None:
+                    keep.setdefault(fn, []).append([1e3 * rtc.get_dur(i, i) for i in ids])
+                rtc.release_per_call_id_data()
+        block(a.warmup, None)
+        keep = {}
+        for _ in range(a.repeats):
+            block(a.runs, keep)
+        T = 4.0 * B * C * H * W
+        rec = {"shape": list(shape), "tensor_MB": round(T / 1e6, 2), "copy_rate_GBps_recorded": COPY_RATE_GBPS}
+        med = {}
+        for fn, blocks in keep.items():
+            med[fn] = statistics.median([v for b in blocks for v in b])
+            rec[fn] = {"us": round(med[fn], 1), "GBps": round(PASSES[fn] * T / (med[fn] * 1e-6) / 1e9, 1), "block_medians_us": [round(statistics.median(b), 1) for b in blocks]}
+        rec["frozen_over_training_bwd"] = round(med["hip_bnf_bck"] / (med["hip_bn_bck_sums"] + med["hip_bn_bck_in"]), 3)
+        # the same sums bit for bit (one chain on the same mean / inv_std)
+        rec["sums_equal_bits"] = bool(np.array_equal(rtc.copy_var_to_nda("bb_sg").view(np.uint32), rtc.copy_var_to_nda("bb_sgf").view(np.uint32)) and
+                                      np.array_equal(rtc.copy_var_to_nda("bb_bg").view(np.uint32), rtc.copy_var_to_nda("bb_bgf").view(np.uint32)))
+        print(json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+        for i in range(len(funcs)):
+            rtc.release_func(f"bb_f{i}")
+        for vn in list(vals) + list(chans):
+            rtc.release_var(vn)
+    rtc.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write(f"# python tools/bn_bench.py --frozen --batch {a.batch} --runs {a.runs} --warmup {a.warmup} --repeats {a.repeats}\n" + "\n".join(lines) + "\n")
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r14_bn_train.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--frozen", action="store_true", help="time hip_bnf_bck beside hip_bn_bck_sums + hip_bn_bck_in instead")
     a = ap.parse_args(argv)
+    a.out = a.out or os.path.join(ROOT, "profiles", "r22_freeze.txt" if a.frozen else "r14_bn_train.txt")
+    if a.frozen:
+        return frozen_main(a)
     import numpy as np
     import torch   # (before the package: see __graft_entry__._recompile_with_the_wheels_hiprtc)
     import torch.nn.functional as F
