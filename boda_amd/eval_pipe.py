@@ -9,10 +9,11 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 
 from .bck_pipe import BN_IN_SFX, BckCall, ConvPipeBck
-from .cnn_op import accuracy_func_op, bn_fold_func_op, chan_affine_func_op, eval_accum_func_op, pipe_func_args
+from .call_list import CallList
+from .cnn_op import accuracy_func_op, bn_fold_func_op, chan_affine_func_op, eval_accum_func_op
 from .input_pipe import DATA_RAW_VAR, DATA_XF_PLAN_VAR, DATA_XF_TAG
 from .op import Dims, Op, RtErr, UnsupErr
-from .rtc import RtcArg, RtcFuncCall, RtcFuncInfo
+from .rtc import RtcArg
 
 EVAL_CTL_VAR = "eval_ctl"            # uint32 v=4 = [first, 0, 0, 0], uploaded before every batch
 EVAL_COUNTS_VAR = "eval_counts"      # uint32 v=4 = [images, hits_top1, hits_topk, batches]
@@ -71,7 +72,7 @@ class EvalPipe:
             if c.tag not in fwd_ops:
                 break
             fwd_calls.append(c)
-        bn_runs = drv._plan_bn_runs(bp)
+        bn_runs = drv.bn_runs   # (as the driver's init planned them)
         bn_of_tag = {q.tag: (x, run) for x, run in bn_runs.items() for q in run[:2]}
         lop = fwd_ops[loss]
         logits, label = lop.bots
@@ -85,26 +86,15 @@ class EvalPipe:
             if vn in bp.nodes or vn in drv.vars:
                 raise RtErr(f"EvalPipe: the evaluation pass needs the var name {vn!r}, which is a {'node of the pipe' if vn in bp.nodes else 'var of the driver'}")
         self.vars: List[str] = []
-        self.funcs: List[str] = []
-        self.eval_calls: List[BckCall] = []
-        self._graph: Optional[int] = None
+        self._calls = CallList(rtc, "eval")   # the batch's calls, the functions made for it and its own graph
         self._stepped = False
         self._first = True
         self._batches = 0   # since reset()
         self.per_call_ms: List[Tuple[str, str, float]] = []
         self.compute_dur_ms = 0.0
-        infos: List[RtcFuncInfo] = []
-
-        def emit(tag: str, fop: Op, args: Dict[str, str]) -> None:
-            fname = f"eval_{len(self.eval_calls)}_{fop.get_func_name()}"
-            spec = pipe_func_args(fop)
-            infos.append(RtcFuncInfo(fname, "", [an for an, _ in spec], fop))
-            self.eval_calls.append(BckCall(tag, fop, dict(args), RtcFuncCall(fname, {an: RtcArg.var(args[an]) for an, _ in spec})))
-            self.funcs.append(fname)
-
+        emit = self._calls.emit
         if self.xf_call is not None:
-            c = self.xf_call
-            self.eval_calls.append(BckCall(c.tag, c.fop, dict(c.args), c.rfc))
+            self._calls.reuse(self.xf_call)
         for c in fwd_calls:
             o = fwd_ops[c.tag]
             if o.type == "Dropout":
@@ -120,7 +110,7 @@ class EvalPipe:
                 continue
             if o.type == "SoftmaxWithLoss" and o.tag != loss:
                 continue
-            self.eval_calls.append(BckCall(c.tag, c.fop, dict(c.args), c.rfc))   # the driver's own function and bindings
+            self._calls.reuse(c)   # the driver's own function and bindings
             if o.type == "SoftmaxWithLoss" and c.fop.get_func_name() == "hip_sum_loss_over_imgs":
                 emit(o.tag, accuracy_func_op(bp.nodes[logits]), {"in": logits, "label": label, "rank": EVAL_RANK_VAR})
                 emit(o.tag, eval_accum_func_op(n_img, top_k), {"rank": EVAL_RANK_VAR, "loss": loss, "ctl": EVAL_CTL_VAR, "counts": EVAL_COUNTS_VAR, "loss_sum": EVAL_LOSS_SUM_VAR})
@@ -129,7 +119,7 @@ class EvalPipe:
         for vn, d in new_vars.items():
             rtc.create_var_with_dims(vn, d); self.vars.append(vn)
         try:
-            rtc.compile(infos)
+            self._calls.compile()
         except Exception:
             for vn in self.vars:
                 rtc.release_var(vn)
@@ -153,35 +143,24 @@ class EvalPipe:
         if xf is not None:
             self.rtc.copy_nda_to_var(DATA_XF_PLAN_VAR, xf.plan("test", 0, self.drv._xf_batch()))
 
+    eval_calls = property(lambda self: self._calls.calls)   # the batch's BckCalls in run order
+    funcs = property(lambda self: self._calls.funcs)
+    _graph = property(lambda self: self._calls.graph)
+
     def calls(self) -> List[Tuple[str, Op, Dict[str, RtcArg]]]:
         """The ordered (tag, function op, arg map) list of one evaluation batch."""
         return [(c.tag, c.fop, dict(c.rfc.arg_map)) for c in self.eval_calls]
 
-    def _run_calls(self) -> None:
-        rtc = self.rtc
-        for c in self.eval_calls:
-            c.call_id = rtc.run(c.rfc)
-        rtc.finish_and_sync()
-        ids = [c.call_id for c in self.eval_calls]
-        self.compute_dur_ms = rtc.get_dur(ids[0], ids[-1])
-        self.per_call_ms = [(c.tag, c.fop.get_func_name(), rtc.get_dur(i, i)) for c, i in zip(self.eval_calls, ids)]
-        rtc.release_per_call_id_data()
-        self._stepped = True
-
     def run_device_only(self, graph: bool = False) -> float:
         """One evaluation batch on the inputs already resident; -> ms of the pass.  per_call_ms: (tag, function, ms) per call of an eager batch, [] for a replay."""
-        rtc = self.rtc
         if graph and self._graph is None:
             raise RtErr("EvalPipe.run_batch(graph=True): no captured graph -- call capture_graph() first")
         self._upload_ctl()
         if graph:
-            cid = rtc.graph_launch(self._graph)
-            rtc.finish_and_sync()
-            self.compute_dur_ms = rtc.get_dur(cid, cid)
-            self.per_call_ms = []
-            rtc.release_per_call_id_data()
+            self.compute_dur_ms, self.per_call_ms = self._calls.replay(), []
         else:
-            self._run_calls()
+            self.compute_dur_ms, self.per_call_ms = self._calls.run()
+            self._stepped = True
         self._first = False
         self._batches += 1
         return self.compute_dur_ms
@@ -222,28 +201,20 @@ class EvalPipe:
         whatever the vars hold (workspaces and lazily built kernels must exist before a capture); the accumulators are put back behind it.  A second capture destroys
         the first; the driver's graph is not touched."""
         rtc = self.rtc
-        if self._graph is not None:
-            rtc.graph_destroy(self._graph); self._graph = None
+        self._calls.destroy_graph()
         if not self._stepped:
             keep = {vn: rtc.copy_var_to_nda(vn) for vn in (EVAL_COUNTS_VAR, EVAL_LOSS_SUM_VAR)}
             self._upload_ctl()
-            self._run_calls()
+            self.compute_dur_ms, self.per_call_ms = self._calls.run()
+            self._stepped = True
             for vn, a in keep.items():
                 rtc.copy_nda_to_var(vn, a)
-        rtc.finish_and_sync()
-        rtc.graph_begin()
-        for c in self.eval_calls:   # (a call that raises inside a capture: the backend drops the capture before it rethrows)
-            rtc.run(c.rfc)
-        self._graph, n = rtc.graph_end()
-        return n
+        return self._calls.capture()
 
     def release(self) -> None:
         """Destroy the graph, release the functions and vars this object made.  The driver, its functions, vars and graph stay as they are."""
-        if self._graph is not None:
-            self.rtc.graph_destroy(self._graph); self._graph = None
-        for f in self.funcs:
-            self.rtc.release_func(f)
+        self._calls.release()
         for v in self.vars:
             self.rtc.release_var(v)
-        self.funcs, self.vars, self.eval_calls = [], [], []
+        self.vars = []
         self._stepped = False

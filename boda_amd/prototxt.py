@@ -12,6 +12,7 @@ import re
 from typing import Dict, List, Tuple, Union
 
 from .op import Op, RtErr, parse_op
+from .solver_cfg import Freeze, LrPolicy, Solver
 
 Node = Dict[str, list]
 
@@ -177,7 +178,7 @@ def pipe_spec(text: str, in_chw: Tuple[int, int, int] = (3, 224, 224)) -> List[s
     return out
 
 
-# ---- Caffe's SolverParameter (solver.prototxt) -> bck_pipe.Solver
+# ---- Caffe's SolverParameter (solver.prototxt) -> solver_cfg.Solver
 _SOLVER_TYPES = {"SGD": "sgd", "Nesterov": "nesterov", "Adam": "adam"}                 # type: "<name>"
 _SOLVER_ENUMS = {"SGD": "sgd", "NESTEROV": "nesterov", "ADAM": "adam"}                 # the legacy solver_type: <ENUM>
 _SOLVER_UNSUP = ("AdaGrad", "RMSProp", "AdaDelta", "ADAGRAD", "RMSPROP", "ADADELTA")   # Caffe's other three: no kernel here
@@ -192,7 +193,6 @@ def solver_spec(text: str):
     iter_size.  Absent keys get CAFFE's defaults, not the dataclass's: momentum 0, weight_decay 0, momentum2 0.999, delta 1e-8, clip_gradients -1 (off: 0.0 here),
     iter_size 1, type SGD.  AdaGrad / RMSProp / AdaDelta and regularization_type "L1" are an UnsupErr that names the value.  Every other key (net, test_iter, display,
     snapshot*, solver_mode, random_seed, ...) comes back in `ignored`, key -> the list of its values."""
-    from .bck_pipe import LrPolicy, Solver
     from .op import UnsupErr
     d = parse(text)
     for k in _SOLVER_KEYS:
@@ -342,7 +342,6 @@ def freeze_spec(text: str, cp=None):
     `batch_norm_param { use_global_stats: true }` becomes a `bn_global_stats` entry (none: False).  A BatchNorm layer's own three `lr_mult: 0` blobs are ignored: its
     statistics are never solver params here.  Layers of every phase are read, each name once.  use_global_stats on a layer that is no BatchNorm is an RtErr.  cp (a
     ConvPipe, optional): every layer named must then be an op of that pipe, and a name that is not is an RtErr that names it."""
-    from .bck_pipe import Freeze
     root = parse(text)
     params: List[str] = []
     bn_global: List[str] = []
