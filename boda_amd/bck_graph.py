@@ -18,21 +18,46 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .conv_pipe import ConvPipe, PipeOp
-from .op import Dims, Nda, Op, RtErr, UnsupErr
+from .op import LOSS_NORMALIZATIONS, Dims, Nda, Op, RtErr, UnsupErr
 
 IN_PLACE_TYPES = ("ReLU", "Dropout", "BckDropout")   # and a ZeroIfNonPos whose out is its in (src/conv_util.cc:273-279)
 AFFINE_IN_PLACE_TYPES = ("BatchNorm", "Scale")       # ResNet's: in place on the node a convolution wrote, like a ReLU; their gradient ops must run in TRUE reverse order
 DROPOUT_RATIO = 0.5   # Dropout_coi's default (src/conv_util.cc:39); the ConvPipe records carry no ratio
 
 
+@dataclass(frozen=True)
+class LossSpec:
+    """A SoftmaxWithLoss as Caffe defines it (SoftmaxWithLossLayer, LossParameter), restated.  weight: loss_weight, which scales the head's gradient and not the loss
+    node (Caffe's top blob is unweighted too).  ignore_label: an integer; a pel whose label equals it adds nothing to the loss, gets a +0 gradient and is not counted by
+    the normaliser (None: no label is ignored; a value inside [0, chan) ignores that class).  normalization: what the summed loss and the gradient are divided by --
+    "valid": max(1, the pels that are not ignored), "full": img * y * x, "batch_size": img, "none": 1.  A label outside [0, chan) that is not ignored (a NaN included)
+    is INVALID: it matches no channel, costs -logf(FLT_MIN) and counts towards the normaliser.  The defaults are Caffe's."""
+    weight: float = 1.0
+    ignore_label: Optional[int] = None
+    normalization: str = "valid"
+
+    def check(self) -> "LossSpec":
+        if self.normalization not in LOSS_NORMALIZATIONS:
+            raise RtErr(f"LossSpec: normalization must be {' | '.join(LOSS_NORMALIZATIONS)}, got {self.normalization!r}")
+        w = self.weight
+        if isinstance(w, bool) or not isinstance(w, (int, float, np.floating, np.integer)) or not np.isfinite(w):
+            raise RtErr(f"LossSpec: weight must be a finite number, got {w!r}")
+        ig = self.ignore_label
+        if ig is not None and (isinstance(ig, bool) or not isinstance(ig, (int, np.integer))):
+            raise RtErr(f"LossSpec: ignore_label must be an integer or None, got {ig!r}")
+        return self
+
+
 @dataclass
 class GradOp:
-    """One op of the pipe with gradient ops: the reference's conv_op_t reduced to tag / type / bots / tops.  `src` is the forward PipeOp whose parameters it carries."""
+    """One op of the pipe with gradient ops: the reference's conv_op_t reduced to tag / type / bots / tops.  `src` is the forward PipeOp whose parameters it carries;
+    `spec` the LossSpec of a SoftmaxWithLoss that runs as the full loss (None: the reference's three calls)."""
     tag: str
     type: str
     bots: List[str]
     tops: List[str]
     src: Optional[PipeOp] = None
+    spec: Optional[LossSpec] = None
 
     @property
     def in_place(self) -> bool:
@@ -154,10 +179,38 @@ def _append_reversed(cp: ConvPipe, nodes: Dict[str, Dims], fwd: List[GradOp], wa
     return out
 
 
-def add_bck_ops(cp: ConvPipe, label_node: str = "label", loss_tops: Optional[Sequence[str]] = None) -> BckPipe:
+def _specs_of(loss_tops: List[str], loss_specs) -> List[Optional[LossSpec]]:
+    """loss_specs as add_bck_ops takes it -> one LossSpec or None per loss top, each checked."""
+    if loss_specs is None:
+        specs: List[Optional[LossSpec]] = [None] * len(loss_tops)
+    elif isinstance(loss_specs, LossSpec):
+        specs = [loss_specs] * len(loss_tops)
+    elif isinstance(loss_specs, dict):
+        for t in loss_specs:
+            if t not in loss_tops:
+                raise RtErr(f"add_bck_ops: loss_specs names {t!r}, which is no loss top ({', '.join(loss_tops)})")
+        specs = [loss_specs.get(t) for t in loss_tops]
+    elif isinstance(loss_specs, (list, tuple)):
+        if len(loss_specs) != len(loss_tops):
+            raise RtErr(f"add_bck_ops: {len(loss_specs)} loss_specs for {len(loss_tops)} loss tops")
+        specs = list(loss_specs)
+    else:
+        raise RtErr(f"add_bck_ops: loss_specs must be None, a LossSpec, a dict top -> LossSpec or a sequence aligned with loss_tops, got {type(loss_specs).__name__}")
+    for s in specs:
+        if s is not None and not isinstance(s, LossSpec):
+            raise RtErr(f"add_bck_ops: loss_specs holds a {type(s).__name__}, not a LossSpec")
+    return [s.check() if s is not None else None for s in specs]
+
+
+def add_bck_ops(cp: ConvPipe, label_node: str = "label", loss_tops: Optional[Sequence[str]] = None, loss_specs=None) -> BckPipe:
     """The pipe of `cp` with gradient ops.  `loss_tops`: the forward nodes to cap with a SoftmaxWithLoss (default: the pipe's out node; GoogLeNet's auxiliary heads are
-    named here).  One cap is tagged `loss` and writes the node `loss`; several are tagged loss1, loss2, ... in the order given.  All of them read `label_node`."""
+    named here).  One cap is tagged `loss` and writes the node `loss`; several are tagged loss1, loss2, ... in the order given.  All of them read `label_node`, whose
+    dims are img:y:x of the heads' plane (heads that share it must share the plane).
+    `loss_specs`: None, one LossSpec for every head, a dict top -> LossSpec, or a sequence aligned with loss_tops.  A head without a spec on a 1 x 1 plane is the
+    reference's gradient-test loss (three calls, divided by the image count); a head with a spec, and any head on a larger plane (as if given LossSpec()), is the full
+    SoftmaxWithLoss: GradOp.spec carries it."""
     loss_tops = list(loss_tops) if loss_tops else [cp.out_node()]
+    specs = _specs_of(loss_tops, loss_specs)
     fwd = [_fwd_grad_op(cp, o) for o in cp.ops]
     nodes: Dict[str, Dims] = dict(cp.nodes); nodes.update(cp.params)
     if label_node in nodes:
@@ -169,10 +222,19 @@ def add_bck_ops(cp: ConvPipe, label_node: str = "label", loss_tops: Optional[Seq
         tag = "loss" if len(loss_tops) == 1 else f"loss{i + 1}"
         if tag in nodes or t + "_grad_loss" in nodes:
             raise RtErr(f"add_bck_ops: node {tag!r} / {t + '_grad_loss'!r} already exists")
-        fwd.append(GradOp(tag, "SoftmaxWithLoss", [t, label_node], [t + "_grad_loss", tag]))
+        td = cp.nodes[t]
+        plane = (td.dsz("img"), td.dsz("y"), td.dsz("x")) if td.names == ("img", "chan", "y", "x") else (td.dsz("img"), 1, 1)
+        spec = specs[i] if specs[i] is not None or plane[1:] == (1, 1) else LossSpec()
+        if spec is not None and plane[0] * plane[1] * plane[2] >= 2 ** 24:
+            raise RtErr(f"add_bck_ops: loss top {t!r}: img * y * x = {plane[0] * plane[1] * plane[2]} pels: 2^24 or more, and the pel count must be exact as a float")
+        label_dims = Dims.make("float", img=plane[0], y=plane[1], x=plane[2])
+        if label_node in nodes and nodes[label_node] != label_dims:
+            raise RtErr(f"add_bck_ops: loss top {t!r} has the plane {label_dims.pretty()}, an earlier head {nodes[label_node].pretty()}: heads that share the label node "
+                        f"{label_node!r} must share its plane")
+        fwd.append(GradOp(tag, "SoftmaxWithLoss", [t, label_node], [t + "_grad_loss", tag], spec=spec))
         nodes[t + "_grad_loss"] = cp.nodes[t]
         nodes[tag] = Dims.make("float", y=1, x=1)
-        nodes[label_node] = Dims.make("float", img=cp.nodes[t].dsz("img"), y=1, x=1)
+        nodes[label_node] = label_dims
         loss_nodes.append(tag)
 
     g, by_tag = _reader_graph(fwd)

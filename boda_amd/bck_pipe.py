@@ -14,12 +14,12 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .bck_graph import (AFFINE_IN_PLACE_TYPES, DROPOUT_RATIO, IN_PLACE_TYPES, RELU_GRAD_PRODUCERS, BckPipe, GradOp, _u32, add_bck_ops, grad_op_to_op,
+from .bck_graph import (AFFINE_IN_PLACE_TYPES, DROPOUT_RATIO, IN_PLACE_TYPES, RELU_GRAD_PRODUCERS, BckPipe, GradOp, LossSpec, _u32, add_bck_ops, grad_op_to_op,
                         plan_relu_grad_folds)
 from .call_list import BckCall, CallList
 from .cnn_op import (OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, bnc_bck_in_func_op, bnc_bck_sums_func_op, bnc_fwd_func_op, bnc_stats_func_op, BNC_MAX_CHUNKS, fan_out_func_op, sgd_update_func_op, solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op, grad_accum_func_op, solver_update_acc_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos,
                      seed_from_var, SEED_VAR_ARG, bf16_operands)
-from .cnn_op import bnf_bck_func_op, bnf_bck_in_func_op, bnf_prep_func_op, data_transform_func_op
+from .cnn_op import bnf_bck_func_op, bnf_bck_in_func_op, bnf_prep_func_op, data_transform_func_op, loss_norm_func_op, softmax_loss_bck_func_op, softmax_loss_fwd_func_op
 from .conv_pipe import ConvPipe, PipeOp
 from .input_pipe import DATA_RAW_VAR, DATA_XF_MEAN_VAR, DATA_XF_PLAN_VAR, DATA_XF_TAG, InputTransform
 from .op import Dims, Nda, Op, RtErr, SOLVER_CHUNK, UnsupErr
@@ -30,6 +30,7 @@ from .solver_cfg import (GRAD_ACC_SFX, PARAM_SFXS, SGD_HIST2_SFX, SGD_HIST_SFX, 
 BN_IN_SFX = "_bn_in"                # <X>_bn_in: what the convolution in front of a BatchNorm wrote (X itself holds the normalised, scaled, rectified values)
 BN_MEAN_SFX, BN_ISTD_SFX = "_batch_mean", "_batch_inv_std"   # <bn-tag>_batch_mean / _batch_inv_std: the statistics of the step's batch
 BN_STAT_SFXS = ("_mean", "_var")    # a BatchNorm's params: running statistics, rewritten by the forward pass and never by a solver
+LOSS_STATE_SFX = "_state"           # <loss>_state: float v=4 = (Z, s, count, sum) of a head with a LossSpec; hip_softmax_loss_bck reads s from it
 SEED_VAR = "det_drop_seed"   # ConvPipeBck(seed_in_var=True): the one-word uint32 var every dropout call reads its seed from
 DROP_LAYER_STEP = 0x9E3779B1   # the k-th Dropout layer of a pipe hashes with seed + k * this (mod 2^32)
 
@@ -157,6 +158,12 @@ class _Lower:
 
     def loss(self, o):
         prob, lpp = o.tag + "_prob", o.tops[1] + "_per_pel"
+        if o.spec is not None:   # the full SoftmaxWithLoss (kernels/loss_f32.hip): the normaliser and s = weight / Z live in <loss>_state, on the device
+            d, st = self.bp.nodes[o.bots[0]], o.tops[1] + LOSS_STATE_SFX
+            return ([(softmax_loss_fwd_func_op(d, o.spec), {"in": o.bots[0], "label": o.bots[1], "prob": prob, "loss_per_pel": lpp}),
+                     (loss_norm_func_op(d, o.spec), {"label": o.bots[1], "loss_per_pel": lpp, "loss": o.tops[1], "loss_state": st}),
+                     (softmax_loss_bck_func_op(d, o.spec), {"prob": prob, "label": o.bots[1], "loss_state": st, "in_grad_loss": o.tops[0]})],
+                    [(prob, d), (lpp, self.bp.nodes[o.bots[1]]), (st, Dims(("v",), (4,), "float"))])
         fs, fg, fl = add_bck_op_annotations(grad_op_to_op(self.bp, o), self.tune)
         return ([(fs, {"in": o.bots[0], "prob": prob}), (fg, {"prob": prob, "label": o.bots[1], "in_grad_loss": o.tops[0], "loss_per_pel": lpp}),
                  (fl, {"loss_per_pel": lpp, "loss": o.tops[1]})], [(prob, self.bp.nodes[o.bots[0]]), (lpp, self.bp.nodes[o.bots[1]])])
@@ -371,6 +378,15 @@ class ConvPipeBck:
         if self.img_chunks and multi_dev and self.img_chunks != len(self.rtc.devices):
             raise RtErr(f"ConvPipeBck.init: img_chunks={self.img_chunks} on {len(self.rtc.devices)} devices: chunk i of a BatchNorm's sums is device i's img shard, so img_chunks must "
                         "be the device count")
+        spec_heads = [o for o in bp.fwd_ops() if o.type == "SoftmaxWithLoss" and o.spec is not None]
+        if spec_heads and multi_dev:
+            raise UnsupErr(f"ConvPipeBck.init: the loss {spec_heads[0].tag!r} has a LossSpec: the full softmax loss (hip_softmax_loss_fwd, hip_loss_norm, hip_softmax_loss_bck) "
+                           "counts the pels that are not ignored and sums over the WHOLE batch, which would need a cross-device reduction: not provided on a multi-device "
+                           "backend (devices=...); leave loss_specs off there")
+        for o in spec_heads:
+            for vn in (o.tag + "_prob", o.tops[1] + "_per_pel", o.tops[1] + LOSS_STATE_SFX):
+                if vn in bp.nodes:
+                    raise RtErr(f"ConvPipeBck.init: the loss {o.tag!r} needs the var name {vn!r}, which is a node of the pipe")
         bn_runs = self._plan_bn_runs(bp)   # node X -> (BatchNorm op, Scale op, the ReLU behind them or None); every other shape of BatchNorm / Scale is refused here
         if bn_runs and multi_dev and not self.img_chunks:
             raise UnsupErr("ConvPipeBck.init: the pipe has a BatchNorm, whose batch statistics sum over the images of the WHOLE batch: not provided on a multi-device backend "

@@ -11,6 +11,7 @@ as unsupported here, the way ops-prof records any annotation failure (src/rtc_pr
 """
 from __future__ import annotations
 from dataclasses import dataclass, fields
+from numbers import Integral
 from typing import Dict
 
 from .op import Nda, Op, RtErr, UnsupErr, parse_lexp
@@ -499,6 +500,60 @@ def data_transform_func_op(src_dims, crop_yx, mean_dims, scale: float) -> Op:
     return a
 
 
+SOFTMAX_LOSS_FWD_FUNC, LOSS_NORM_FUNC, SOFTMAX_LOSS_BCK_FUNC = "hip_softmax_loss_fwd", "hip_loss_norm", "hip_softmax_loss_bck"
+# the full SoftmaxWithLoss, in a table of its own: what a head with a bck_graph.LossSpec lowers to (loss_weight, ignore_label, planes, the four normalisers).  This
+# backend's own: csrc/kernels/loss_f32.hip states the rules
+LOSS_OP_FUNCS: Dict[str, tuple] = {"SoftmaxLossFwd": (SOFTMAX_LOSS_FWD_FUNC,), "LossNorm": (LOSS_NORM_FUNC,), "SoftmaxLossBck": (SOFTMAX_LOSS_BCK_FUNC,)}
+LOSS_FUNCS = tuple(v[0] for v in LOSS_OP_FUNCS.values())
+
+
+def _loss_func_op(t: str, in_dims, spec, args) -> Op:
+    """One of the three, over the logits `in_dims` (float img:chan:y:x); spec: anything with weight / ignore_label / normalization (bck_graph.LossSpec, whose check()
+    runs first).  Every op of the family carries the whole spec; the kernels take from it what they need."""
+    from .op import Dims
+    if in_dims.names != ("img", "chan", "y", "x") or in_dims.tn != "float":
+        raise RtErr(f"{t}: in must be float img:chan:y:x, got {in_dims.tn} {in_dims.pretty()}")
+    if hasattr(spec, "check"):
+        spec.check()
+    ig = spec.ignore_label
+    if ig is not None and (isinstance(ig, bool) or not isinstance(ig, Integral)):
+        raise RtErr(f"{t}: ignore_label must be an integer or None, got {ig!r}")
+    try:
+        w = float(spec.weight)
+    except (TypeError, ValueError):
+        raise RtErr(f"{t}: weight must be a finite number, got {spec.weight!r}")
+    plane = Dims(("img", "y", "x"), (in_dims.dsz("img"), in_dims.dsz("y"), in_dims.dsz("x")), "float")
+    dims = {"in": in_dims, "prob": in_dims, "in_grad_loss": in_dims, "label": plane, "loss_per_pel": plane, "loss": Dims(("y", "x"), (1, 1), "float"), "loss_state": Dims(("v",), (4,), "float")}
+    v = {an: Nda(dims=dims[an], tn="float") for an in args}
+    v.update({"weight": Nda(None, "float", (_as_f32(w) if w == w and abs(w) != float("inf") else w,)), "has_ignore": Nda(None, "uint32_t", (0 if ig is None else 1,)),
+              "ignore_label": Nda(None, "float", (_as_f32(0 if ig is None else int(ig)),))})
+    a = Op({"type": t, "normalization": str(spec.normalization)}, v)
+    a.loss_geom()
+    a.set_func_name(LOSS_OP_FUNCS[t][0])
+    return a
+
+
+def softmax_loss_fwd_func_op(in_dims, spec) -> Op:
+    """-> hip_softmax_loss_fwd over the logits `in_dims`: in, label (float img:y:x of in's plane) read; prob (in's dims) and loss_per_pel (label's dims) written.  Per
+    pel: prob = exp(in - m) / sum under the TRUE channel maximum m; a label equal to spec.ignore_label is ignored (loss_per_pel +0), one in [0, chan) is valid
+    (-logf(max(prob[L], FLT_MIN))), any other, a NaN included, is invalid (-logf(FLT_MIN)) and reads no memory.  Planes of 64 pels or more take the pel form (one thread
+    per pel), smaller ones the wave form (one wave per pel)."""
+    return _loss_func_op("SoftmaxLossFwd", in_dims, spec, ("in", "label", "prob", "loss_per_pel"))
+
+
+def loss_norm_func_op(in_dims, spec) -> Op:
+    """-> hip_loss_norm for the head on `in_dims`: label, loss_per_pel read; loss (float y=1:x=1) and loss_state (float v=4 = Z, s, count, sum) written.  count: the pels
+    that are not ignored; Z = valid: max(1, count) | full: img * y * x | batch_size: img | none: 1; s = weight / Z (one fp32 divide); loss = sum / Z, unweighted.  The
+    sum is one written chain (csrc/kernels/loss_f32.hip)."""
+    return _loss_func_op("LossNorm", in_dims, spec, ("label", "loss_per_pel", "loss", "loss_state"))
+
+
+def softmax_loss_bck_func_op(in_dims, spec) -> Op:
+    """-> hip_softmax_loss_bck for the head on `in_dims`: prob, label, loss_state read; in_grad_loss = ignored ? +0 : (prob - [c == L]) * s written, two fp32 roundings,
+    s = loss_state[1] read on the device (never passed by value: one captured graph serves every count of ignored pels)."""
+    return _loss_func_op("SoftmaxLossBck", in_dims, spec, ("prob", "label", "loss_state", "in_grad_loss"))
+
+
 # the training BatchNorm of the gradient pipe and the Eltwise-SUM gradient, in a table of their own (PIPE_OP_FUNCS is pinned): what bck_pipe.ConvPipeBck runs for a
 # BatchNorm + Scale (+ ReLU) run and its gradient, and for a BckEltwise.  This backend's own arithmetic: csrc/kernels/bn_f32.hip and DESIGN.md section 3.15 state it
 BN_OP_FUNCS: Dict[str, tuple] = {
@@ -815,6 +870,10 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_accuracy": (("in", "IN"), ("label", "IN"), ("rank", "OUT")),
     "hip_eval_accum": (("rank", "IN"), ("loss", "IN"), ("ctl", "IN"), ("counts", "INOUT"), ("loss_sum", "INOUT")),
     "hip_bn_fold": (("run_mean", "IN"), ("run_var", "IN"), ("scale", "IN"), ("bias", "IN"), ("a", "OUT"), ("b", "OUT")),
+    # the full SoftmaxWithLoss of a head with a LossSpec (this backend's own; weight / normalization / has_ignore / ignore_label ride in the op)
+    "hip_softmax_loss_fwd": (("in", "IN"), ("label", "IN"), ("prob", "OUT"), ("loss_per_pel", "OUT")),
+    "hip_loss_norm": (("label", "IN"), ("loss_per_pel", "IN"), ("loss", "OUT"), ("loss_state", "OUT")),
+    "hip_softmax_loss_bck": (("prob", "IN"), ("label", "IN"), ("loss_state", "IN"), ("in_grad_loss", "OUT")),
     # the input transform (this backend's own; scale rides in the op)
     "hip_data_transform": (("src", "IN"), ("plan", "IN"), ("mean", "IN"), ("out", "OUT")),
     # the training BatchNorm and the Eltwise-SUM gradient (this backend's own; eps / maf / slab / relu ride in the op).  hip_fan_out's list depends on the op: in,

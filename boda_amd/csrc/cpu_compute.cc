@@ -502,6 +502,75 @@ void data_transform(data_op_t const &d, unsigned char const *src, uint32_t const
     }
   }
 }
+// ---- the loss family (kernels/loss_f32.hip states the rules): the same tests, the same fp32 operations in the same order; expf and logf are this platform's
+constexpr float kLossFltMin = 1.175494351e-38f, kInvalidLoss = 0x1.5d58a0p+6f;   // (126 ln 2 rounded to fp32, the kernel's constant)
+static inline float loss_exp_diff(float a, float m) {   // exp(a - m) with the difference held exactly as the pair (d, r): the kernel's exp_diff
+  float const d = a - m;
+  float const bb = d - a;
+  float const r = (a - (d - bb)) - (m + bb);
+  float const e = expf(d);
+  float const er = e * r;
+  return e + er;
+}
+void softmax_loss_fwd(loss_op_t const &l, float const *in, float const *label, float *prob, float *lpp) {
+  long const C = l.C, HW = l.HW; bool const wave = HW < 64;
+#pragma omp parallel for schedule(static)
+  for (long id = 0; id < l.B * HW; ++id) {
+    long const img = id / HW, pel = id - img * HW;
+    float const *const x = in + img * C * HW + pel; float *const pr = prob + img * C * HW + pel;
+    float m, S;
+    if (!wave) {   // the pel form: one sequential chain over the channels
+      m = x[0]; for (long c = 1; c < C; ++c) { float const v = x[c * HW]; m = v > m ? v : m; }
+      S = 0.0f; for (long c = 0; c < C; ++c) S = S + loss_exp_diff(x[c * HW], m);
+    } else {       // the wave form: 64 lane chains over channels l, l + 64, ..., then the xor butterfly (lane l's partner at step k is l ^ k: pairwise, both get a + b)
+      float lm[64], ls[64];
+      for (int ln = 0; ln < 64; ++ln) { float v = -__builtin_inff(); for (long c = ln; c < C; c += 64) { float const w = x[c * HW]; v = w > v ? w : v; } lm[ln] = v; }
+      for (int k = 32; k > 0; k >>= 1) for (int ln = 0; ln < 64; ++ln) if (!(ln & k)) { float const a = lm[ln], b = lm[ln ^ k]; float const r = b > a ? b : a, r2 = a > b ? a : b; lm[ln] = r; lm[ln ^ k] = r2; }
+      m = lm[0];
+      for (int ln = 0; ln < 64; ++ln) { float a = 0.0f; for (long c = ln; c < C; c += 64) a = a + loss_exp_diff(x[c * HW], m); ls[ln] = a; }
+      for (int k = 32; k > 0; k >>= 1) for (int ln = 0; ln < 64; ++ln) if (!(ln & k)) { float const r = ls[ln] + ls[ln ^ k]; ls[ln] = r; ls[ln ^ k] = r; }
+      S = ls[0];
+    }
+    for (long c = 0; c < C; ++c) pr[c * HW] = loss_exp_diff(x[c * HW], m) / S;
+    float const lf = label[id];
+    float v;
+    if (l.has_ignore && lf == l.ignore) v = 0.0f;
+    else if (!(lf >= 0.0f && lf < (float)C)) v = kInvalidLoss;
+    else { float const pl = pr[(long)(int)lf * HW]; v = -logf(pl > kLossFltMin ? pl : kLossFltMin); }
+    lpp[id] = v;
+  }
+}
+void loss_norm(loss_op_t const &l, float const *label, float const *lpp, float *loss, float *state) {
+  long const N = l.pels();
+  float sa[256]; uint32_t sc[256];
+  for (long t = 0; t < 256; ++t) {
+    float a = 0.0f; uint32_t cnt = 0;
+    for (long i = t; i < N; i += 256) { a = a + lpp[i]; cnt += (l.has_ignore && label[i] == l.ignore) ? 0u : 1u; }
+    sa[t] = a; sc[t] = cnt;
+  }
+  for (long h = 128; h > 0; h >>= 1) for (long t = 0; t < h; ++t) { sa[t] = sa[t] + sa[t + h]; sc[t] += sc[t + h]; }
+  float const sum = sa[0]; uint32_t const count = sc[0];
+  float Z = 1.0f;
+  if (l.norm == 0) Z = (float)(count > 1u ? count : 1u); else if (l.norm == 1) Z = (float)N; else if (l.norm == 2) Z = (float)l.B;
+  float const s = l.weight / Z;
+  loss[0] = sum / Z;
+  state[0] = Z; state[1] = s; state[2] = (float)count; state[3] = sum;
+}
+void softmax_loss_bck(loss_op_t const &l, float const *prob, float const *label, float const *state, float *grad) {
+  long const C = l.C, HW = l.HW;
+  float const s = state[1];
+#pragma omp parallel for schedule(static)
+  for (long q = 0; q < l.B * C; ++q) {
+    long const img = q / C, c = q - img * C;
+    for (long pel = 0; pel < HW; ++pel) {
+      float const lf = label[img * HW + pel]; float const p = prob[q * HW + pel];
+      float g;
+      if (l.has_ignore && lf == l.ignore) g = 0.0f;
+      else { bool const valid = lf >= 0.0f && lf < (float)C; float const d = (valid && (long)(int)lf == c) ? p - 1.0f : p; g = d * s; }
+      grad[q * HW + pel] = g;
+    }
+  }
+}
 #pragma GCC pop_options
 } // namespace
 
@@ -579,6 +648,7 @@ struct cpu_compute_t : public rtc_compute_t {
       if (f->family == kFamSolver) (void)solver_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamEval) (void)eval_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamData) (void)data_op_of_op(fi.op);   // (likewise)
+      if (f->family == kFamLoss) (void)loss_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamBckOp) {
         if (!f->of_type(fi.op.get_type())) rt_err(fn + ": a function of op type " + f->types[0] + ", not " + fi.op.get_type());
         bck_op_args_t const a = bck_op_args(*f, fi.op);
@@ -1001,6 +1071,26 @@ struct cpu_compute_t : public rtc_compute_t {
     else bn_fold((float const *)P[0], (float const *)P[1], (float const *)P[2], (float const *)P[3], (float *)P[4], (float *)P[5], e.C, e.eps);
   }
 
+  // the loss family: the checks of be=hip (csrc/native_run.cc), then the twins above
+  void run_loss(op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = op.get_func_name();
+    loss_op_t const l = loss_op_of_op(op);
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    std::vector<float *> P;
+    for (string const &an : l.args) {
+      string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn);
+      dims_t const &want = op.get_dims(an);
+      if (vd.tn != want.tn) rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ", the op says " + want.tn);
+      if (!(vd == want)) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + want.pretty_str());
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      P.push_back((float *)must_find(vis, vn).buf.get());
+    }
+    if (l.kind == 1) softmax_loss_fwd(l, P[0], P[1], P[2], P[3]);
+    else if (l.kind == 2) loss_norm(l, P[0], P[1], P[2], P[3]);
+    else softmax_loss_bck(l, P[0], P[1], P[2], P[3]);
+  }
+
   // the data family: the checks of be=hip (csrc/native_run.cc), then the twin above
   void run_data(op_base_t const &op, map_str_rtc_arg_t const &am) {
     string const fn = op.get_func_name();
@@ -1042,6 +1132,7 @@ struct cpu_compute_t : public rtc_compute_t {
     else if (f.family == kFamSolver) run_solver(fi.op, am);
     else if (f.family == kFamEval) run_eval(fi.op, am);
     else if (f.family == kFamData) run_data(fi.op, am);
+    else if (f.family == kFamLoss) run_loss(fi.op, am);
     else if (f.family == kFamBckOp) run_bck_op(f, fi.op, am);
     else if (f.family == kFamBconv) run_bck(f, fi.op, am);
     else if (f.family == kFamSgemm) {

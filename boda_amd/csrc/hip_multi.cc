@@ -374,7 +374,7 @@ struct hip_multi_compute_t : public rtc_compute_t {
       // what a call on img shards does is the row's multi-device policy (native_funcs.h), where every function has to state one.  A function that is not independent per
       // image is refused with the row's sentence; one that sums over the images only without img_shards=1, which has taken the `continue` above
       if (row && n() > 1 && (row->multi_dev.mode == multi_dev_t::needs_flag || row->multi_dev.mode == multi_dev_t::refused)) func_img_sum[fi.func_name] = row->multi_dev.why;
-      if (row && n() > 1 && row->multi_dev.mode == multi_dev_t::one_device) func_img_sum[fi.func_name] = kWhyBnfOneDevice;   // (the hip_bnf_* family: one sentence for all its rows)
+      if (row && n() > 1 && row->multi_dev.mode == multi_dev_t::one_device) func_img_sum[fi.func_name] = why_one_device(row->family);   // (the hip_bnf_* and the loss families: one sentence for all the rows of a family)
       if (!nat) func_gen[fi.func_name] = scan_gen_func(all_src, fi.func_name);
     }
   }

@@ -284,6 +284,35 @@ struct data_transform_args_t {
 static_assert(sizeof(data_transform_args_t) == 64 && __builtin_offsetof(data_transform_args_t, out) == 24 && __builtin_offsetof(data_transform_args_t, n) == 32 &&
               __builtin_offsetof(data_transform_args_t, C) == 40 && __builtin_offsetof(data_transform_args_t, scale) == 60, "data_transform_args_t layout");
 
+// kernels/loss_f32.hip: the full SoftmaxWithLoss of the gradient pipe (loss_weight, ignore_label, planes, the four normalisers)
+struct softmax_loss_fwd_args_t {
+  float const *in; float const *label;   // logits img:chan:y:x, labels img:y:x
+  float *prob; float *loss_per_pel;      // img:chan:y:x, img:y:x
+  int B, C, HW;                          // images, channels, pels of a plane
+  int has_ignore; float ignore;          // a label equal to `ignore` is ignored (has_ignore != 0)
+  int pad_;
+};
+static_assert(sizeof(softmax_loss_fwd_args_t) == 56 && __builtin_offsetof(softmax_loss_fwd_args_t, prob) == 16 && __builtin_offsetof(softmax_loss_fwd_args_t, B) == 32 &&
+              __builtin_offsetof(softmax_loss_fwd_args_t, ignore) == 48, "softmax_loss_fwd_args_t layout");
+struct loss_norm_args_t {
+  float const *label; float const *loss_per_pel;   // img:y:x both
+  float *loss; float *state;             // y=1:x=1; v=4 = Z, s, count, the sum of loss_per_pel
+  int N, B;                              // pels of the batch (B * HW, below 2^24), images
+  int has_ignore; float ignore;
+  float weight; int norm;                // norm: 0 valid | 1 full | 2 batch_size | 3 none
+};
+static_assert(sizeof(loss_norm_args_t) == 56 && __builtin_offsetof(loss_norm_args_t, loss) == 16 && __builtin_offsetof(loss_norm_args_t, N) == 32 &&
+              __builtin_offsetof(loss_norm_args_t, weight) == 48, "loss_norm_args_t layout");
+struct softmax_loss_bck_args_t {
+  float const *prob; float const *label; float const *state;   // state[1] = s is read on the device
+  float *grad;                           // in_grad_loss img:chan:y:x
+  long n;                                // grad's elements, B * C * HW
+  int C, HW;
+  int has_ignore; float ignore;
+};
+static_assert(sizeof(softmax_loss_bck_args_t) == 56 && __builtin_offsetof(softmax_loss_bck_args_t, grad) == 24 && __builtin_offsetof(softmax_loss_bck_args_t, n) == 32 &&
+              __builtin_offsetof(softmax_loss_bck_args_t, C) == 40 && __builtin_offsetof(softmax_loss_bck_args_t, ignore) == 52, "softmax_loss_bck_args_t layout");
+
 #pragma pop_macro("CH")
 #pragma pop_macro("CIN")
 #pragma pop_macro("COH")

@@ -10,8 +10,8 @@
 namespace bodahip {
 
 // the family (func_family_t of rtc_types.h) selects the handler (native_run.cc, native_kernels.cc: check_compile_time); handlers switch on the member, never on the name
-inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf"};
-// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform
+inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf", "loss"};
+// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform.  kFamLoss: 1 fwd | 2 norm | 3 bck (loss_op_t::kind)
 enum { kConvF32 = 0, kConvAlias = 1, kConvBf16 = 2, kConvWinograd = 3 };            // (the alias: hip_conv's contract without its fused pooling and filts_km)
 enum { kBconvIn = 1, kBconvBiases = 2, kBconvFilts = 3, kBconvFiltsBiases = 4 };   // (4 is opt-in: never one of the bare op's three calls)
 enum { kOpPoolYx = 1, kOpSpreading = 2, kOpLrnSb = 3, kOpBckLrn = 4, kOpZeroIfNonPos = 5, kOpSoftmax = 6, kOpSmGradAndLoss = 7, kOpSumLossOverImgs = 8, kOpReduce = 9,
@@ -36,7 +36,7 @@ struct multi_dev_t {
                 needs_flag,        // not independent per image: refused (`why`) unless the op carries img_shards=1
                 refused,           // refused (`why`) on several devices
                 replicated_vars,   // replicated_only's policy: the call runs on every device's replicas, a sharded var is refused
-                one_device };      // refused on several devices like `refused`, with the sentence of its FAMILY (kWhyBnfOneDevice), which the row does not repeat
+                one_device };      // refused on several devices like `refused`, with the sentence of its FAMILY (why_one_device), which the row does not repeat
   mode_t mode; char const *why;
   constexpr multi_dev_t(mode_t mode_, char const *why_) : mode(mode_), why(why_) {}
 };
@@ -66,6 +66,8 @@ struct native_func_t {
 inline constexpr char kWhyBconvSum[] = "(a BckConv filter / bias gradient) sums over the images, which would need a cross-device reduction; only the data gradient (hip_bconv_in) runs on img shards";
 inline constexpr char kWhyBnSums[] = "(a training BatchNorm's per-channel sums) sums over the images of the WHOLE batch, which would need a cross-device reduction; statistics summed across img shards are out of scope";
 inline constexpr char kWhyBnfOneDevice[] = "(a BatchNorm on its running pair, the hip_bnf_* family) takes vars of exactly its op's dims, not img shards, and hip_bnf_bck sums over the images of the WHOLE batch, which would need a cross-device reduction; frozen statistics on several devices are out of scope";
+inline constexpr char kWhyLossOneDevice[] = "(the full softmax loss, the hip_softmax_loss_* / hip_loss_norm family) counts the pels that are not ignored and sums loss_per_pel over the WHOLE batch, which would need a cross-device reduction, and takes vars of exactly its op's dims, not img shards; a loss with a LossSpec on several devices is out of scope";
+inline constexpr char const *why_one_device(func_family_t family) { return family == kFamLoss ? kWhyLossOneDevice : kWhyBnfOneDevice; }
 inline constexpr native_func_t kNativeFuncs[] = {
   // sgemm, a:K:M b:K:N c:M:N (test/rtc/cublas_sgemm.cucl:1-4); Convolution in reference layout (test/rtc/cudnn_conv.cucl:1-7)
   {"hip_sgemm", kFamSgemm, 0, nullptr, {"sgemm"}, {{"a", kIn}, {"b", kIn}, {"c", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
@@ -140,6 +142,12 @@ inline constexpr native_func_t kNativeFuncs[] = {
   {"hip_bnf_prep", kFamBnf, 6, nullptr, {"BnfPrep"}, {{"run_mean", kIn}, {"run_var", kIn}, {"mean", kOut}, {"inv_std", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   {"hip_bnf_bck", kFamBnf, 7, nullptr, {"BnfBck"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"scale", kIn}, {"out_grad_loss", kIn}, {"in_grad_loss", kOut}, {"scale_grad_loss", kOut}, {"bias_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   {"hip_bnf_bck_in", kFamBnf, 8, nullptr, {"BnfBckIn"}, {{"inv_std", kIn}, {"scale", kIn}, {"out_grad_loss", kIn}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  // the full SoftmaxWithLoss (this backend's own; kernels/loss_f32.hip): what a head with a LossSpec lowers to -- loss_weight, ignore_label, planes, the four
+  // normalisers.  hip_softmax_loss_bck reads s = weight / Z from loss_state on the device.  One device only (why_one_device).  In front of the data and eval rows,
+  // which stay the table's last four
+  {"hip_softmax_loss_fwd", kFamLoss, 1, nullptr, {"SoftmaxLossFwd"}, {{"in", kIn}, {"label", kIn}, {"prob", kOut}, {"loss_per_pel", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  {"hip_loss_norm", kFamLoss, 2, nullptr, {"LossNorm"}, {{"label", kIn}, {"loss_per_pel", kIn}, {"loss", kOut}, {"loss_state", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  {"hip_softmax_loss_bck", kFamLoss, 3, nullptr, {"SoftmaxLossBck"}, {{"prob", kIn}, {"label", kIn}, {"loss_state", kIn}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   // the input transform of the gradient pipe (this backend's own; kernels/data_f32.hip): crop, mirror, mean and scale from uint8 images under a per-image plan var
   // (independent per image: src, plan and out are img shards, mean is whole on every device).  In front of the eval rows, which stay the table's last three
   {"hip_data_transform", kFamData, 1, nullptr, {"DataTransform"}, {{"src", kIn}, {"plan", kIn}, {"mean", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},

@@ -67,6 +67,10 @@ string eval_plan_desc(eval_op_t const &e, bck_plan_t const &bp);
 bck_plan_t plan_data_op(data_op_t const &d);
 string data_plan_desc(data_op_t const &d, bck_plan_t const &bp);
 
+// the loss family (kernels/loss_f32.hip; softmax_loss_fwd_args_t, loss_norm_args_t, softmax_loss_bck_args_t): one launch per call
+bck_plan_t plan_loss_op(loss_op_t const &l);
+string loss_plan_desc(loss_op_t const &l, bck_plan_t const &bp);
+
 struct sgemm_split_t { uint32_t m_main = 0; string tail_tile; double t_single = 0, t_split = 0; };
 static char const *const kBigTile = "256x256x16x2x4x1x1x32x2";
 struct sgemm_part_t { uint32_t m0 = 0, rows = 0, n0 = 0, cols = 0; string tile; };

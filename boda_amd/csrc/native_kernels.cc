@@ -75,6 +75,9 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
   case kFamData:   // likewise
     (void)get_kernel(impl, host, plan_data_op(data_op_of_op(fi.op)).p);
     break;
+  case kFamLoss:   // likewise
+    (void)get_kernel(impl, host, plan_loss_op(loss_op_of_op(fi.op)).p);
+    break;
   case kFamBconv:   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     (void)op_bf16_operands(fi.op);   // (str_val hip_operands: refused at compile where the function has no bf16-operand form)
@@ -981,6 +984,25 @@ void native_kernels_t::data_call(data_op_t const &d, void *const *ptrs) {
   a.n = d.out_elems(); a.C = (int)d.C; a.H = (int)d.H; a.W = (int)d.W; a.ch = (int)d.ch; a.cw = (int)d.cw; a.scale = d.scale;
   void *params[1] = {&a};
   if (bp.grid) hip_err_chk(host->nh_launch(k.func, bp.grid, 1, bp.block, params), "hipModuleLaunchKernel(data)");
+  last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = bp.grid; last_launch.block = bp.block;
+  last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
+}
+// ---- the loss family (kernels/loss_f32.hip): one launch per call
+void native_kernels_t::loss_call(loss_op_t const &l, void *const *ptrs) {
+  bck_plan_t const bp = plan_loss_op(l);
+  kernel_t &k = get_kernel(impl, host, bp.p);
+  softmax_loss_fwd_args_t a1; loss_norm_args_t a2; softmax_loss_bck_args_t a3; void *params[1] = {nullptr};
+  if (l.kind == 1) {
+    memset(&a1, 0, sizeof(a1)); a1.in = (float const *)ptrs[0]; a1.label = (float const *)ptrs[1]; a1.prob = (float *)ptrs[2]; a1.loss_per_pel = (float *)ptrs[3];
+    a1.B = (int)l.B; a1.C = (int)l.C; a1.HW = (int)l.HW; a1.has_ignore = l.has_ignore; a1.ignore = l.ignore; params[0] = &a1;
+  } else if (l.kind == 2) {
+    memset(&a2, 0, sizeof(a2)); a2.label = (float const *)ptrs[0]; a2.loss_per_pel = (float const *)ptrs[1]; a2.loss = (float *)ptrs[2]; a2.state = (float *)ptrs[3];
+    a2.N = (int)l.pels(); a2.B = (int)l.B; a2.has_ignore = l.has_ignore; a2.ignore = l.ignore; a2.weight = l.weight; a2.norm = l.norm; params[0] = &a2;
+  } else {
+    memset(&a3, 0, sizeof(a3)); a3.prob = (float const *)ptrs[0]; a3.label = (float const *)ptrs[1]; a3.state = (float const *)ptrs[2]; a3.grad = (float *)ptrs[3];
+    a3.n = l.pels() * l.C; a3.C = (int)l.C; a3.HW = (int)l.HW; a3.has_ignore = l.has_ignore; a3.ignore = l.ignore; params[0] = &a3;
+  }
+  hip_err_chk(host->nh_launch(k.func, bp.grid, 1, bp.block, params), "hipModuleLaunchKernel(loss)");
   last_launch.kernel = bp.p.kname; last_launch.cfg = tile_cfg_t(); last_launch.grid = bp.grid; last_launch.block = bp.block;
   last_launch.flops = 0; last_launch.algo_bytes = bp.algo_bytes;
 }

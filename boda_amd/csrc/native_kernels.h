@@ -37,6 +37,9 @@
 //     hip_data_transform               this backend's own: the input transform of the gradient pipe.  uint8 images (interleaved or planar) cropped and mirrored under a
 //                                       per-image plan var (uint32 img:v=4 = y_off, x_off, mirror, unused; offsets clamped), mean (per channel or per source pel)
 //                                       subtracted, scaled: out = ((float)src - mean) * scale, two fp32 roundings.  kernels/data_f32.hip
+//     hip_softmax_loss_fwd / hip_loss_norm / hip_softmax_loss_bck    this backend's own: the full SoftmaxWithLoss of a head with a LossSpec (loss_weight, ignore_label,
+//                                       planes, the four normalisers).  prob under the true maximum and loss_per_pel; the count of the pels that are not ignored, the
+//                                       normaliser Z, s = weight / Z and the loss into loss / loss_state; the gradient under s read from loss_state.  kernels/loss_f32.hip
 //     hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out    this backend's own: the training BatchNorm of the gradient pipe (batch statistics, running
 //                                       pair, normalise + scale + bias + ReLU, the two gradients) and the gradient of an Eltwise SUM.  kernels/bn_f32.hip states the arithmetic and
 //                                       the order of the per-channel sums
@@ -167,6 +170,8 @@ struct native_kernels_t {
   void eval_call(eval_op_t const &e, void *const *ptrs);
   // hip_data_transform on raw device pointers (kernels/data_f32.hip): ptrs = src, plan, mean, out; d.B is the call's image count
   void data_call(data_op_t const &d, void *const *ptrs);
+  // the loss family on raw device pointers (kernels/loss_f32.hip): ptrs in loss_op_t::args' order
+  void loss_call(loss_op_t const &l, void *const *ptrs);
   void shard_sum(float const *slabs, float *out, int nslabs, long stride, long n);
   // hip_bn_stats / hip_bn_fwd / hip_bn_bck_sums / hip_bn_bck_in / hip_fan_out -- and hip_bnf_prep / hip_bnf_bck / hip_bnf_bck_in, the BatchNorm on its running pair (kFamBnf)
   // -- on raw device pointers (kernels/bn_f32.hip): tens / chans in bn_op_t's arg order

@@ -1459,6 +1459,42 @@ string data_plan_desc(data_op_t const &d, bck_plan_t const &bp) {
          " imgs=" + std::to_string(d.B) + " chans=" + std::to_string(d.C) + " " + std::to_string(d.H) + "x" + std::to_string(d.W) + "->" + std::to_string(d.ch) + "x" + std::to_string(d.cw);
 }
 
+// ---- the loss family (kernels/loss_f32.hip).  hip_softmax_loss_fwd: the form is picked from the op alone -- the pel form (one thread per pel, -DFORM=0) where a plane
+// has a wave's worth of pels (y * x >= 64), the channels in registers up to kLossCreg of them (-DCREG=C, else 0); the wave form (one wave per pel, four per workgroup,
+// -DFORM=1) below that.  hip_loss_norm: one workgroup.  hip_softmax_loss_bck: one thread per four flat elements.  Every size is a kernel argument
+static long const kLossCreg = 32;
+bck_plan_t plan_loss_op(loss_op_t const &l) {
+  static char const *const knames[] = {"", "bodahip_softmax_loss_fwd", "bodahip_loss_norm", "bodahip_softmax_loss_bck"};
+  if (l.kind < 1 || l.kind > 3) rt_err("plan_loss_op: unknown kind " + std::to_string(l.kind));
+  string const what = find_native_func(kFamLoss, l.kind)->name;
+  bck_plan_t r; r.p.src = kSrc_loss_f32; r.p.kname = knames[l.kind]; r.p.defs = {"-DOP=" + std::to_string(l.kind)};
+  if (l.B < 1 || l.HW < 1 || (l.kind != 2 && l.C < 1)) rt_err(what + ": bad dims");
+  double const N = (double)l.B * (double)l.HW, E = N * (double)l.C;
+  if (N >= 16777216.0) rt_err(what + ": 2^24 pels or more");
+  if (l.kind != 2 && 4.0 * E >= 2147483648.0) unsup_err(what + ": tensors of 2 GiB or more");
+  if (l.kind == 1) {
+    bool const pel = l.HW >= 64;
+    r.p.defs.push_back(pel ? "-DFORM=0" : "-DFORM=1");
+    r.p.defs.push_back("-DCREG=" + std::to_string(pel && l.C <= kLossCreg ? l.C : 0));
+    r.threads = pel ? l.pels() : l.pels() * 64; r.algo_bytes = 4.0 * (2.0 * E + 2.0 * N);
+  } else if (l.kind == 2) {
+    r.threads = 256; r.algo_bytes = 4.0 * (2.0 * N + 5.0);
+  } else {
+    r.threads = (l.pels() * l.C + 3) / 4; r.algo_bytes = 4.0 * (2.0 * E + N + 1.0);
+  }
+  long const blocks = (r.threads + r.block - 1) / r.block;
+  if (blocks >= (1L << 31)) unsup_err(what + ": too many workgroups");
+  r.grid = (uint32_t)blocks;
+  return r;
+}
+string loss_plan_desc(loss_op_t const &l, bck_plan_t const &bp) {
+  string d = bp.p.kname + " grid=" + std::to_string(bp.grid) + " block=" + std::to_string(bp.block);
+  if (l.kind == 1) d += string(" form=") + (l.HW >= 64 ? "pel" : "wave") + " " + bp.p.defs.back();
+  d += " imgs=" + std::to_string(l.B) + (l.kind != 2 ? " chans=" + std::to_string(l.C) : string()) + " pels=" + std::to_string(l.HW);
+  if (l.kind == 2) d += string(" normalization=") + kLossNormNames[l.norm];
+  return d;
+}
+
 // ---- hip_sgd_update (kernels/sgd_update_f32.hip): one workgroup per chunk of kSgdChunk floats of one tensor; the grid is the sum of the tensors' chunks, blk0 its
 // prefix sums.  20 bytes move per element: w, g, h read, h and w written.
 sgd_plan_t plan_sgd_update(std::vector<long> const &elems) {

@@ -286,6 +286,12 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     bck_plan_t const bp = plan_data_op(d);
     if (plan_out) *plan_out = data_plan_desc(d, bp);
     return arch.empty() ? 0 : compile_plan(bp.p, arch, &log).size();
+  } else if (fam == kFamLoss) {   // (kernels/loss_f32.hip: the forward function specialised by its form and a small channel count, the others not at all)
+    if (!f) rt_err("prebuild: a bare " + t + " op: the full softmax loss's ops are function ops (cnn_op.softmax_loss_fwd_func_op, loss_norm_func_op, softmax_loss_bck_func_op)");
+    loss_op_t const l = loss_op_of_op(op);
+    bck_plan_t const bp = plan_loss_op(l);
+    if (plan_out) *plan_out = loss_plan_desc(l, bp);
+    return arch.empty() ? 0 : compile_plan(bp.p, arch, &log).size();
   } else {   // kFamBckOp, a non-conv op of the gradient pipe: its annotated function, or (the bare op) all its functions in call order
     if (op.has_func_name() && !f) rt_err("prebuild: " + t + " function '" + op.get_func_name() + "' has no native kernel");
     std::vector<native_func_t const *> const ds = f ? std::vector<native_func_t const *>{f} : of_t;
@@ -768,6 +774,23 @@ struct native_kernels_t::call_t {
     if (e.kind == 1) e.B = n_img;
     nk.eval_call(e, ptrs.data());
   }
+  void run_loss() {
+    // every var has the type and exactly the dims the op gives its arg (the count and the sum run over the whole batch: no img shards), and all the call's vars are
+    // different ones
+    loss_op_t const l = loss_op_of_op(fi.op);
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    std::vector<void *> ptrs;
+    for (string const &an : l.args) {
+      string const vn = var_of(am, an); dims_t const vd = host->nh_var_dims(vn);
+      dims_t const &want = fi.op.get_dims(an);
+      if (vd.tn != want.tn) rt_err(fn + ": arg '" + an + "' (var '" + vn + "') has type " + vd.tn + ", the op says " + want.tn);
+      if (!(vd == want)) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + want.pretty_str());
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      ptrs.push_back(host->nh_var_ptr(vn));
+    }
+    nk.loss_call(l, ptrs.data());
+  }
   void run_data() {
     // every var has the type and the dims the op gives its arg -- except the number of images of src, plan and out (the function is independent per image), which only
     // has to agree between them -- and all the call's vars are different ones
@@ -917,6 +940,7 @@ void native_kernels_t::run(native_func_t const &f, rtc_func_info_t const &fi, ma
   case kFamSolver: c.run_solver(); break;
   case kFamEval: c.run_eval(); break;
   case kFamData: c.run_data(); break;
+  case kFamLoss: c.run_loss(); break;
   }
 }
 

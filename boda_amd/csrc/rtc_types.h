@@ -129,7 +129,7 @@ struct op_base_t {
 };
 typedef std::shared_ptr<op_base_t> p_op_base_t;
 // ---- the op flags of a native function.  Which function takes which flag is a column of the one table, native_funcs.h (included at the end of this file), which defines:
-enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver, kFamEval, kFamData, kFamBnf };   // selects the handler
+enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver, kFamEval, kFamData, kFamBnf, kFamLoss };   // selects the handler
 enum : unsigned { kFlagZinp = 1, kFlagSeedVar = 2, kFlagImgShards = 4, kFlagNhwcResidual = 8 };
 struct op_flag_name_t { char const *name; unsigned flag; };
 constexpr op_flag_name_t kOpFlagNames[] = {{"img_shards", kFlagImgShards}, {"seed_from_var", kFlagSeedVar}, {"zero_if_in_non_pos", kFlagZinp}, {"nhwc_residual", kFlagNhwcResidual}};
@@ -505,6 +505,67 @@ inline data_op_t data_op_of_op(op_base_t const &op) {
   if (!op.has("scale")) rt_err(fn + ": the op has no 'scale'");
   p_nda_t const &v = op.get("scale"); if (v->dims.tn != "float" || v->dims.sz() != 0 || !v->rp) rt_err(fn + ": 'scale' is not a float scalar");
   r.scale = *static_cast<float const *>(v->rp);
+  return r;
+}
+
+// ---- the loss family (this backend's own; kernels/loss_f32.hip states the rules): the full SoftmaxWithLoss a head with a LossSpec lowers to.  hip_softmax_loss_fwd
+// (op type SoftmaxLossFwd, member 1: in float img:chan:y:x, label float img:y:x read; prob, loss_per_pel written), hip_loss_norm (LossNorm, member 2: label, loss_per_pel
+// read; loss float y=1:x=1, loss_state float v=4 written) and hip_softmax_loss_bck (SoftmaxLossBck, member 3: prob, label, loss_state read; in_grad_loss written).  The
+// spec rides in the op: the float weight, the str_val normalization (valid | full | batch_size | none), the uint32 has_ignore and the float ignore_label (the integer
+// as a float, which is what a label is compared with).  What both backends read from the function's op, and every refusal that needs the op alone
+struct loss_op_t {
+  int kind = 0;                  // the member: 1 fwd, 2 norm, 3 bck
+  long B = 0, C = 0, HW = 0;     // images, channels (kinds 1, 3), pels of a plane
+  int has_ignore = 0; float ignore = 0.f;
+  float weight = 1.f; int norm = 0;   // 0 valid | 1 full | 2 batch_size | 3 none
+  vect_string args;              // the var args in the function's arg order
+  long pels() const { return B * HW; }
+};
+inline constexpr char const *kLossNormNames[] = {"valid", "full", "batch_size", "none"};
+inline loss_op_t loss_op_of_op(op_base_t const &op) {
+  string const fn = op.has_func_name() ? op.get_func_name() : string();
+  loss_op_t r;
+  r.kind = native_func_member(fn, kFamLoss);
+  if (!r.kind) rt_err("'" + fn + "' is none of " + native_family_names(kFamLoss));
+  string const type = native_func_type(kFamLoss, r.kind);
+  if (!op.has_type() || op.get_type() != type) rt_err(fn + ": a function of op type " + type + ", not " + (op.has_type() ? op.get_type() : string("?")));
+  refuse_flags_not_taken(op, fn, "the function");
+  if (r.kind == 1) r.args = {"in", "label", "prob", "loss_per_pel"}; else if (r.kind == 2) r.args = {"label", "loss_per_pel", "loss", "loss_state"}; else r.args = {"prob", "label", "loss_state", "in_grad_loss"};
+  for (string const &an : r.args) if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'");
+  auto named = [](dims_t const &d, std::initializer_list<char const *> ns) { if (d.sz() != ns.size()) return false; uint32_t i = 0; for (char const *n : ns) if (d.names(i++) != n) return false; return true; };
+  dims_t const &lab = op.get_dims("label");
+  if (lab.tn != "float" || !named(lab, {"img", "y", "x"})) rt_err(fn + ": label must be float img:y:x, got " + lab.tn + " " + lab.pretty_str());
+  r.B = lab.dims(0); r.HW = (long)lab.dims(1) * lab.dims(2);
+  if (r.B < 1 || r.HW < 1) rt_err(fn + ": empty label");
+  if ((double)r.B * (double)r.HW >= 16777216.0) rt_err(fn + ": img * y * x = " + std::to_string(r.B * r.HW) + " pels: 2^24 or more, and the pel count must be exact as a float");
+  auto tensor = [&](char const *an) {   // float img:chan:y:x over label's images and plane
+    dims_t const &d = op.get_dims(an);
+    if (d.tn != "float" || !named(d, {"img", "chan", "y", "x"})) rt_err(fn + ": " + an + " must be float img:chan:y:x, got " + d.tn + " " + d.pretty_str());
+    if (d.dims(0) != lab.dims(0) || d.dims(2) != lab.dims(1) || d.dims(3) != lab.dims(2)) rt_err(fn + ": " + an + " " + d.pretty_str() + " and label " + lab.pretty_str() + " differ in img, y or x");
+    if (d.dims(1) < 1) rt_err(fn + ": " + string(an) + " has no channels");
+    if (4.0 * (double)d.dims_prod() >= 2147483648.0) unsup_err(fn + ": tensors of 2 GiB or more");
+    return (long)d.dims(1); };
+  auto same = [&](char const *an, dims_t const &want, char const *what) { dims_t const &d = op.get_dims(an); if (!(d == want)) rt_err(fn + ": " + an + " must be " + what + ", got " + d.tn + " " + d.pretty_str()); };
+  auto state = [&]() { dims_t const &d = op.get_dims("loss_state"); if (d.tn != "float" || !named(d, {"v"}) || d.dims(0) != 4) rt_err(fn + ": loss_state must be float v=4 (Z, s, count, sum), got " + d.tn + " " + d.pretty_str()); };
+  if (r.kind == 1) { r.C = tensor("in"); same("prob", op.get_dims("in"), "of in's dims"); same("loss_per_pel", lab, "of label's dims"); }
+  else if (r.kind == 2) {
+    same("loss_per_pel", lab, "of label's dims"); state();
+    dims_t const &lo = op.get_dims("loss");
+    if (lo.tn != "float" || !named(lo, {"y", "x"}) || lo.dims(0) != 1 || lo.dims(1) != 1) rt_err(fn + ": loss must be float y=1:x=1 (the pipe's loss node), got " + lo.tn + " " + lo.pretty_str());
+  } else { r.C = tensor("prob"); same("in_grad_loss", op.get_dims("prob"), "of prob's dims"); state(); }
+  auto f32 = [&](char const *an) { if (!op.has(an)) rt_err(fn + ": the op has no '" + an + "'"); p_nda_t const &v = op.get(an); if (v->dims.tn != "float" || v->dims.sz() != 0 || !v->rp) rt_err(fn + ": '" + an + "' is not a float scalar"); return *static_cast<float const *>(v->rp); };
+  if (!op.has("has_ignore")) rt_err(fn + ": the op has no 'has_ignore'");
+  r.has_ignore = op.get_u32("has_ignore") ? 1 : 0;
+  r.ignore = f32("ignore_label");
+  if (r.has_ignore && !(r.ignore == (float)(long)r.ignore)) rt_err(fn + ": ignore_label must be an integer");
+  if (r.kind == 2) {
+    r.weight = f32("weight");
+    if (!(r.weight - r.weight == 0.0f)) rt_err(fn + ": weight must be finite");
+    auto const it = op.str_vals.find("normalization");
+    if (it == op.str_vals.end()) rt_err(fn + ": the op has no 'normalization'");
+    r.norm = -1; for (int i = 0; i < 4; ++i) if (it->second == kLossNormNames[i]) r.norm = i;
+    if (r.norm < 0) rt_err(fn + ": normalization must be valid | full | batch_size | none, got '" + it->second + "'");
+  }
   return r;
 }
 

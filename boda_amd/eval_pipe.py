@@ -33,6 +33,8 @@ class EvalPipe:
       * BatchNorm of a [BatchNorm, Scale (, ReLU)] run on X: hip_bn_fold of the RUNNING pair <bn>_mean / <bn>_var and <scale>_scale / _bias into <bn>_eval_a / _eval_b
         (the bits of conv_pipe.fold_affine); the Scale is then hip_chan_affine from <X>_bn_in to X, ReLU included.  The same for a driver built with img_chunks, which
         has no meaning in the test phase.
+      * the selected SoftmaxWithLoss with a LossSpec (1 x 1 plane, no ignore_label; anything else is an UnsupErr here): hip_softmax_loss_fwd and hip_loss_norm, then
+        hip_accuracy and hip_eval_accum as below; its gradient call is left out.
       * the selected SoftmaxWithLoss: the driver's three calls, then hip_accuracy on the loss's `in` node (the logits) and `label` into eval_rank, then hip_eval_accum
         into eval_counts / eval_loss_sum.  The loss calls of other heads are left out.
       * the data_xf call of a driver built with input_transform: the driver's own call, first; run_batch({"data_raw": bytes, "label": y}).
@@ -76,6 +78,9 @@ class EvalPipe:
         bn_of_tag = {q.tag: (x, run) for x, run in bn_runs.items() for q in run[:2]}
         lop = fwd_ops[loss]
         logits, label = lop.bots
+        if lop.spec is not None and (bp.nodes[label].sizes[1:] != (1, 1) or lop.spec.ignore_label is not None):
+            raise UnsupErr(f"EvalPipe: the loss {loss!r} " + ("has a plane larger than 1 x 1" if bp.nodes[label].sizes[1:] != (1, 1) else f"has ignore_label={lop.spec.ignore_label}") +
+                           ": accuracy over a plane or with an ignore_label is not built (hip_accuracy ranks one label per image and counts every image)")
         n_img = bp.nodes[logits].dsz("img")
         new_vars: Dict[str, Dims] = {EVAL_CTL_VAR: Dims(("v",), (4,), "uint32_t"), EVAL_COUNTS_VAR: Dims(("v",), (4,), "uint32_t"),
                                      EVAL_LOSS_SUM_VAR: Dims(("v",), (1,), "float"), EVAL_RANK_VAR: Dims(("img",), (n_img,), "uint32_t")}
@@ -110,8 +115,10 @@ class EvalPipe:
                 continue
             if o.type == "SoftmaxWithLoss" and o.tag != loss:
                 continue
+            if o.type == "SoftmaxWithLoss" and c.fop.get_func_name() == "hip_softmax_loss_bck":
+                continue   # (a head with a LossSpec: the gradient call of the full loss is behind the loss node's; an evaluation pass needs no gradient)
             self._calls.reuse(c)   # the driver's own function and bindings
-            if o.type == "SoftmaxWithLoss" and c.fop.get_func_name() == "hip_sum_loss_over_imgs":
+            if o.type == "SoftmaxWithLoss" and c.fop.get_func_name() in ("hip_sum_loss_over_imgs", "hip_loss_norm"):
                 emit(o.tag, accuracy_func_op(bp.nodes[logits]), {"in": logits, "label": label, "rank": EVAL_RANK_VAR})
                 emit(o.tag, eval_accum_func_op(n_img, top_k), {"rank": EVAL_RANK_VAR, "loss": loss, "ctl": EVAL_CTL_VAR, "counts": EVAL_COUNTS_VAR, "loss_sum": EVAL_LOSS_SUM_VAR})
         if not self.funcs or self.eval_calls[-1].fop.get_func_name() != "hip_eval_accum":

@@ -302,16 +302,24 @@ OP_INFO = {
     # this backend's own: the input transform of the gradient pipe (csrc/kernels/data_f32.hip states the rule).  src uint8_t img:y:x:chan or img:chan:y:x, plan uint32_t
     # img:v=4 = (y_off, x_off, mirror, unused), mean float chan or chan:y:x at the source size; out float img:chan:y:x at the crop size = ((float)src - mean) * scale
     "DataTransform": (("src", "plan", "mean"), ("out",), ("scale",)),
+    # this backend's own: the full SoftmaxWithLoss of a head with a LossSpec (csrc/kernels/loss_f32.hip states the rules): loss_weight, ignore_label, planes larger than
+    # 1 x 1 and Caffe's four normalisers.  in / prob / in_grad_loss float img:chan:y:x, label / loss_per_pel float img:y:x, loss float y=1:x=1, loss_state float v=4 =
+    # (Z, s, count, sum).  The spec rides in every one of them: the float weight, the str_val normalization, the uint32 has_ignore and the float ignore_label
+    "SoftmaxLossFwd": (("in", "label"), ("prob", "loss_per_pel"), ("weight", "has_ignore", "ignore_label")),
+    "LossNorm": (("label", "loss_per_pel"), ("loss", "loss_state"), ("weight", "has_ignore", "ignore_label")),
+    "SoftmaxLossBck": (("prob", "label", "loss_state"), ("in_grad_loss",), ("weight", "has_ignore", "ignore_label")),
 }
 BN_TYPES = ("BnStats", "BnFwd", "BnBckSums", "BnBckIn", "FanOut")
 BNF_TYPES = ("BnfPrep", "BnfBck", "BnfBckIn")
 SOLVER_TYPES = ("SolverUpdate", "GradSumsq", "GradNorm", "GradAccum", "SolverUpdateAcc")
 EVAL_TYPES = ("Accuracy", "EvalAccum", "BnFold")
 DATA_TYPES = ("DataTransform",)
+LOSS_TYPES = ("SoftmaxLossFwd", "LossNorm", "SoftmaxLossBck")
+LOSS_NORMALIZATIONS = ("valid", "full", "batch_size", "none")
 SOLVER_CHUNK = 4096   # floats of one tensor a workgroup owns; one partial sum of squares per chunk
 
 
-_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + BNF_TYPES + SOLVER_TYPES + EVAL_TYPES + DATA_TYPES
+_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + BNF_TYPES + SOLVER_TYPES + EVAL_TYPES + DATA_TYPES + LOSS_TYPES
 
 
 @dataclass
@@ -482,7 +490,7 @@ class Op:
 
     def softmax_geom(self) -> dict:
         """SoftmaxWithLoss: in / in_grad_loss img:chan:1:1, label img:1:1, loss 1:1.  Larger planes are refused on purpose: the reference template reads `label` by image only
-        (test/rtc/sm_grad_and_loss.cucl), which is wrong for them, and every net here ends in a 1 x 1 plane."""
+        (test/rtc/sm_grad_and_loss.cucl), which is wrong for them.  A head on a larger plane runs as the full loss (loss_geom; bck_graph.LossSpec)."""
         i, l = self.get_dims("in"), self.get_dims("label")
         if i.names != ("img", "chan", "y", "x") or l.names != ("img", "y", "x") or i.tn != "float" or l.tn != "float":
             raise UnsupErr("SoftmaxWithLoss: in must be float img:chan:y:x and label float img:y:x")
@@ -654,6 +662,50 @@ class Op:
         if not self.get("eps").v[0] >= 0.0:
             raise RtErr("BnFold: eps must not be negative")
         return dict(C=C)
+
+    def loss_geom(self) -> dict:
+        """SoftmaxLossFwd / LossNorm / SoftmaxLossBck: label and loss_per_pel float img:y:x, the tensors float img:chan:y:x over the same images and plane, loss float
+        y=1:x=1, loss_state float v=4; a finite weight, a normalization of the four, has_ignore and an integer ignore_label; fewer than 2^24 pels."""
+        import math
+        t = self.get_type()
+        ins, outs, req = OP_INFO[t]
+        for an in ins + outs + req:
+            if not self.has(an):
+                raise RtErr(f"{t}: the op has no {an!r}")
+        lab = self.get_dims("label")
+        if lab.tn != "float" or lab.names != ("img", "y", "x"):
+            raise RtErr(f"{t}: label must be float img:y:x, got {lab.tn} {lab.pretty()}")
+        B, HW = lab.dsz("img"), lab.dsz("y") * lab.dsz("x")
+        if B < 1 or HW < 1:
+            raise RtErr(f"{t}: empty label")
+        if B * HW >= 2 ** 24:
+            raise RtErr(f"{t}: img * y * x = {B * HW} pels: 2^24 or more, and the pel count must be exact as a float")
+        C = 0
+        for an in ins + outs:
+            d = self.get_dims(an)
+            if an in ("in", "prob", "in_grad_loss"):
+                if d.tn != "float" or d.names != ("img", "chan", "y", "x"):
+                    raise RtErr(f"{t}: {an} must be float img:chan:y:x, got {d.tn} {d.pretty()}")
+                if (d.dsz("img"), d.dsz("y"), d.dsz("x")) != lab.sizes or d.dsz("chan") < 1 or (C and d.dsz("chan") != C):
+                    raise RtErr(f"{t}: {an} {d.pretty()} does not fit label {lab.pretty()}" + (f" and chan={C}" if C else ""))
+                C = d.dsz("chan")
+                if 4 * d.dims_prod() >= 2 ** 31:
+                    raise UnsupErr(f"{t}: tensors of 2 GiB or more")
+            elif an == "loss_per_pel" and d != lab:
+                raise RtErr(f"{t}: loss_per_pel must have label's dims, got {d.tn} {d.pretty()}")
+            elif an == "loss" and (d.tn != "float" or d.names != ("y", "x") or d.sizes != (1, 1)):
+                raise RtErr(f"{t}: loss must be float y=1:x=1, got {d.tn} {d.pretty()}")
+            elif an == "loss_state" and (d.tn != "float" or d.names != ("v",) or d.sizes != (4,)):
+                raise RtErr(f"{t}: loss_state must be float v=4 (Z, s, count, sum), got {d.tn} {d.pretty()}")
+        w, ig = self.get("weight").v[0], self.get("ignore_label").v[0]
+        if not math.isfinite(w):
+            raise RtErr(f"{t}: weight must be finite, got {w!r}")
+        norm = self.str_vals.get("normalization")
+        if norm not in LOSS_NORMALIZATIONS:
+            raise RtErr(f"{t}: normalization must be {' | '.join(LOSS_NORMALIZATIONS)}, got {norm!r}")
+        if self.get_u32("has_ignore") and not (math.isfinite(ig) and ig == int(ig)):
+            raise RtErr(f"{t}: ignore_label must be an integer, got {ig!r}")
+        return dict(B=B, C=C, HW=HW, form="pel" if HW >= 64 else "wave", weight=w, normalization=norm, ignore_label=int(ig) if self.get_u32("has_ignore") else None)
 
     def data_geom(self) -> dict:
         """DataTransform: src uint8_t img:y:x:chan ("hwc") or img:chan:y:x ("chw") at the source size H x W; out float img:chan:y:x with src's img and chan and the crop
@@ -841,6 +893,8 @@ def parse_op(line: str) -> Op:
             op.eval_geom()
         elif t in DATA_TYPES:
             op.data_geom()
+        elif t in LOSS_TYPES:
+            op.loss_geom()
         else:
             op.sgemm_geom()
     return op

@@ -372,3 +372,64 @@ def freeze_spec(text: str, cp=None):
             if name not in tags:
                 raise RtErr(f"prototxt: freeze_spec: layer {name!r} is no op of the pipe {cp.name!r}")
     return Freeze(params=tuple(params), bn_global_stats=list(bn_global) if bn_global else False)
+
+
+_LOSS_NORMS = {"FULL": "full", "VALID": "valid", "BATCH_SIZE": "batch_size", "NONE": "none"}
+
+
+def loss_spec(text: str, phase: str = "TRAIN"):
+    """-> [(name, bottom, label, bck_graph.LossSpec)] of a net definition's SoftmaxWithLoss layers of `phase` ("TRAIN" | "TEST"), in definition order: what add_bck_ops
+    takes as loss_tops and loss_specs.  A layer without an include block belongs to both phases; one of the other phase alone is left out.
+    Read: loss_weight (the first one: the loss top's) -> weight; loss_param { ignore_label, normalization: FULL | VALID | BATCH_SIZE | NONE } and the legacy
+    `normalize:` key, which counts only where normalization is absent (true -> valid, false -> batch_size), as in Caffe.  Absent keys get Caffe's defaults: weight 1,
+    no ignore_label, VALID.  Any other layer whose type ends in Loss is an UnsupErr that names the type: only the softmax loss has kernels here."""
+    from .bck_graph import LossSpec
+    from .op import UnsupErr
+    phase = str(phase).upper()
+    if phase not in ("TRAIN", "TEST"):
+        raise RtErr(f"prototxt: loss_spec: phase must be 'TRAIN' | 'TEST', got {phase!r}")
+    root = parse(text)
+    out = []
+    for L in root.get("layer", []) or root.get("layers", []):
+        tname = str(_one(L, "type"))
+        t = tname.upper().replace("_", "")
+        if not t.endswith("LOSS"):
+            continue
+        incs = [str(_one(inc, "phase", "")).upper() for inc in L.get("include", []) if isinstance(inc, dict)]
+        if incs and phase not in incs:
+            continue
+        name, bots = str(_one(L, "name")), L.get("bottom", [])
+        if t not in ("SOFTMAXWITHLOSS", "SOFTMAXLOSS"):
+            raise UnsupErr(f"prototxt: loss_spec: layer {name!r} is a {tname}: only SoftmaxWithLoss has kernels here (other loss layers are not built)")
+        if len(bots) != 2:
+            raise RtErr(f"prototxt: SoftmaxWithLoss layer {name!r} has {len(bots)} bottoms: the scores and the label")
+        lp = _one(L, "loss_param", {})
+        if not isinstance(lp, dict):
+            raise RtErr(f"prototxt: SoftmaxWithLoss layer {name!r}: loss_param must be a block")
+        for k in ("ignore_label", "normalization", "normalize"):
+            if len(lp.get(k, [])) > 1:
+                raise RtErr(f"prototxt: SoftmaxWithLoss layer {name!r}: {k!r} is given {len(lp[k])} times")
+        try:
+            weight = float(_one(L, "loss_weight", 1.0))
+        except (ValueError, TypeError):
+            raise RtErr(f"prototxt: SoftmaxWithLoss layer {name!r}: loss_weight must be a number")
+        ig = _one(lp, "ignore_label")
+        if ig is not None:
+            try:
+                ig = int(ig)
+            except (ValueError, TypeError):
+                raise RtErr(f"prototxt: SoftmaxWithLoss layer {name!r}: ignore_label: {ig!r} is not an integer")
+        if "normalization" in lp:
+            nz = str(_one(lp, "normalization")).upper()
+            if nz not in _LOSS_NORMS:
+                raise RtErr(f"prototxt: SoftmaxWithLoss layer {name!r}: normalization: {nz!r} is none of {' | '.join(_LOSS_NORMS)}")
+            norm = _LOSS_NORMS[nz]
+        elif "normalize" in lp:
+            nb = str(_one(lp, "normalize")).lower()
+            if nb not in ("true", "false"):
+                raise RtErr(f"prototxt: SoftmaxWithLoss layer {name!r}: normalize: {nb!r} is neither true nor false")
+            norm = "valid" if nb == "true" else "batch_size"
+        else:
+            norm = "valid"
+        out.append((name, str(bots[0]), str(bots[1]), LossSpec(weight=weight, ignore_label=ig, normalization=norm).check()))
+    return out

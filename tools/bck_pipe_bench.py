@@ -137,6 +137,58 @@ def fuse_ab(net, batch, runs, warmup, repeats, option="fuse_relu_grad"):
         w["drv"].release(); w["rtc"].close()
 
 
+GOOGLENET_TOPS = ["cls3_fc", "cls1_fc2", "cls2_fc2"]   # the main head first, then the two auxiliary ones: add_bck_ops tags them loss1, loss2, loss3
+
+
+def loss_ab(batch, runs, warmup, repeats, weights):
+    """--loss-weights W1,W2,W3: GoogLeNet's step with its three heads capped by the reference's unweighted losses, beside the step with
+    LossSpec(weight=W) per head IN THE ORDER OF THE NET'S LOSS LAYERS (loss1 and loss2 the auxiliary heads, loss3 the main one: Caffe's 0.3,0.3,1), in ONE process in
+    alternating blocks; per way the step, the calls, the three losses and the us per step of the loss functions."""
+    import numpy as np
+    from boda_amd import conv_pipe
+    from boda_amd.bck_pipe import ConvPipeBck, LossSpec, add_bck_ops, host_params
+    from boda_amd.rtc import make_rtc
+    cp = conv_pipe.googlenet_conv(batch)
+    w1, w2, w3 = weights
+    specs = {"cls1_fc2": LossSpec(w1), "cls2_fc2": LossSpec(w2), "cls3_fc": LossSpec(w3)}
+    rng = np.random.default_rng(0)
+    data = rng.uniform(-1, 1, cp.nodes["data"].sizes).astype(np.float32)
+    label = rng.integers(0, 1000, (batch, 1, 1)).astype(np.float32)
+    ways = {}
+    for way, sp in (("unweighted", None), ("weighted", specs)):
+        bp = add_bck_ops(cp, loss_tops=GOOGLENET_TOPS, loss_specs=sp)
+        rtc = make_rtc("(be=hip)", 0)
+        rtc.init()
+        drv = ConvPipeBck(rtc)
+        drv.init(bp, host_params(bp, 5))
+        rtc.copy_nda_to_var("data", data); rtc.copy_nda_to_var("label", label)
+        ways[way] = {"rtc": rtc, "drv": drv, "bp": bp, "blocks": [], "ms": [], "share": {}}
+    for w in ways.values():
+        for i in range(warmup):
+            w["drv"].set_det_drop_seed(i); w["drv"].run_device_only()
+    for rep in range(repeats):
+        for w in ways.values():
+            ms = []
+            for i in range(runs):
+                w["drv"].set_det_drop_seed(warmup + rep * runs + i)
+                ms.append(w["drv"].run_device_only())
+                for _, fn, d in w["drv"].per_call_ms:
+                    w["share"][fn] = w["share"].get(fn, 0.0) + d
+            w["ms"] += ms; w["blocks"].append(round(statistics.median(ms), 3))
+    loss_fns = ("hip_softmax", "hip_sm_grad_and_loss", "hip_sum_loss_over_imgs", "hip_softmax_loss_fwd", "hip_loss_norm", "hip_softmax_loss_bck")
+    for way, w in ways.items():
+        step = statistics.median(w["ms"])
+        losses = {n: round(float(w["rtc"].copy_var_to_nda(n).item()), 4) for n in w["bp"].loss_nodes}
+        if not all(np.isfinite(v) for v in losses.values()):
+            raise SystemExit(f"googlenet {way}: a loss is not finite: {losses}")
+        print(json.dumps({"net": "googlenet", "batch": batch, "way": way, "loss_weights": list(weights) if way == "weighted" else None, "calls": len(w["drv"].calls()),
+                          "step_ms": round(step, 3), "block_medians_ms": w["blocks"], "imgs_per_s": round(batch / (step * 1e-3), 1), "losses": losses,
+                          "loss_calls_us_per_step": {fn: round(1e3 * w["share"][fn] / len(w["ms"]), 1) for fn in loss_fns if fn in w["share"]}}), flush=True)
+    print(json.dumps({"net": "googlenet", "weighted_over_unweighted": round(statistics.median(ways["weighted"]["ms"]) / statistics.median(ways["unweighted"]["ms"]), 4)}), flush=True)
+    for w in ways.values():
+        w["drv"].release(); w["rtc"].close()
+
+
 def freeze_of(cp, spec, bn_global):
     """--freeze SPEC -> Freeze: SPEC a comma list of param names / op tags / suffixes, or all-but:TAG[,TAG...] (every param but those of the ops named)."""
     from boda_amd.bck_pipe import Freeze, bn_stat_params
@@ -534,6 +586,7 @@ def main(argv=None):
     ap.add_argument("--eval", type=int, default=0, dest="n_eval", help="alternating blocks of --runs training steps and N evaluation batches (eval_pipe.EvalPipe) in one process: ms per eval batch beside ms per step")
     ap.add_argument("--freeze", default="", help="A/B in one process: the full step beside the step under Freeze(params=SPEC): a comma list of param names / op tags / suffixes, or all-but:TAG[,TAG]")
     ap.add_argument("--bn-global", action="store_true", help="A/B in one process: the full step beside the step with every BatchNorm on its running pair; with --freeze the third leg has both")
+    ap.add_argument("--loss-weights", default="", help="e.g. 0.3,0.3,1: A/B in one process on GoogLeNet (whatever --nets says): its three heads under the reference's unweighted losses beside LossSpec(weight=W) per loss layer")
     ap.add_argument("--raw", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--child", default="")
     a = ap.parse_args(argv)
@@ -551,14 +604,26 @@ def main(argv=None):
         ap.error("--eval is a comparison of its own on one device")
     if (a.freeze or a.bn_global) and (a.graph or a.fuse_relu_grad or a.sgd or a.fuse_filts_biases or a.grad_operands or a.solver or a.devices or a.img_chunks or a.n_eval):
         ap.error("--freeze / --bn-global are a comparison of their own on one device")
+    if a.loss_weights:
+        if a.graph or a.fuse_relu_grad or a.sgd or a.fuse_filts_biases or a.grad_operands or a.solver or a.devices or a.img_chunks or a.n_eval or a.freeze or a.bn_global:
+            ap.error("--loss-weights is a comparison of its own on one device")
+        try:
+            a.weights = tuple(float(v) for v in a.loss_weights.split(","))
+        except ValueError:
+            a.weights = ()
+        if len(a.weights) != 3:
+            ap.error("--loss-weights takes three numbers, one per loss layer of GoogLeNet: 0.3,0.3,1")
+        a.nets = "googlenet"
     if a.n_eval < 0:
         ap.error("--eval N: at least 1 batch")
     if a.clip and not a.solver:
         ap.error("--clip goes with --solver")
     if a.iter_size != 1 and (not a.solver or a.iter_size < 1):
         ap.error("--iter-size goes with --solver and is at least 1")
-    a.out = a.out or os.path.join(ROOT, "profiles", "r22_freeze.txt" if (a.freeze or a.bn_global) else "r20_eval.txt" if a.n_eval else "r17_resnet50_chunks.txt" if a.img_chunks else "r16_step_bf16.txt" if a.grad_operands else "r19_grad_accum.txt" if a.solver and a.iter_size > 1 else "r18_solver.txt" if a.solver else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r23_loss_googlenet.txt" if a.loss_weights else "r22_freeze.txt" if (a.freeze or a.bn_global) else "r20_eval.txt" if a.n_eval else "r17_resnet50_chunks.txt" if a.img_chunks else "r16_step_bf16.txt" if a.grad_operands else "r19_grad_accum.txt" if a.solver and a.iter_size > 1 else "r18_solver.txt" if a.solver else "r13_sgd_update.txt" if a.sgd else "r10_bck_graph_ab.txt" if a.graph else "r09_bck_fuse_ab.txt" if a.fuse_relu_grad else "r15_resnet50_step_fb.txt" if a.fuse_filts_biases else "bck_pipe_devices.txt" if a.devices else "r14_resnet50_step.txt" if a.nets == "resnet50" else "r09_bck_pipe_bench.txt")
     if a.child:
+        if a.loss_weights:
+            return loss_ab(a.batch, a.runs, a.warmup, a.repeats, a.weights)
         if a.freeze or a.bn_global:
             return freeze_ab(a.child, a.batch, a.runs, a.warmup, a.repeats, a.freeze, a.bn_global)
         if a.n_eval:
@@ -593,14 +658,15 @@ def main(argv=None):
         cmd += ["--devices", a.devices] if a.devices else []
         cmd += (["--freeze", a.freeze] if a.freeze else []) + (["--bn-global"] if a.bn_global else []) + (["--repeats", str(a.repeats)] if (a.freeze or a.bn_global) else [])
         cmd += ["--eval", str(a.n_eval), "--repeats", str(a.repeats)] if a.n_eval else []
+        cmd += ["--loss-weights", a.loss_weights, "--repeats", str(a.repeats)] if a.loss_weights else []
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:   # nothing more is started on the GPU after a failure
             print(f"{net}: exit status {r.returncode}\n{r.stderr[-2000:]}", file=sys.stderr)
             return r.returncode
         lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
-        print("\n".join(lines[-3:] if (a.freeze or a.bn_global) else lines[-4:] if (a.graph or a.sgd or a.grad_operands) else lines[-3:] if (a.fuse_relu_grad or a.fuse_filts_biases or a.solver) else lines[-1:]), flush=True)
+        print("\n".join(lines[-3:] if (a.freeze or a.bn_global or a.loss_weights) else lines[-4:] if (a.graph or a.sgd or a.grad_operands) else lines[-3:] if (a.fuse_relu_grad or a.fuse_filts_biases or a.solver) else lines[-1:]), flush=True)
     with open(a.out, "a" if (a.freeze or a.bn_global) else "w") as f:     # (profiles/r22_freeze.txt also holds tools/bn_bench.py --frozen's record)
-        extra = f"{' --freeze ' + a.freeze if a.freeze else ''}{' --bn-global' if a.bn_global else ''} --repeats {a.repeats}" if (a.freeze or a.bn_global) else f" --eval {a.n_eval} --repeats {a.repeats}" if a.n_eval else f" --img-chunks {a.img_chunks}{' --devices ' + a.devices if a.devices else ''} --repeats {a.repeats}" if a.img_chunks else f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --solver {a.solver} --clip {a.clip}{' --swap' if a.swap else ''}{f' --iter-size {a.iter_size}' if a.iter_size > 1 else ''} --repeats {a.repeats}" if a.solver else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
+        extra = f" --loss-weights {a.loss_weights} --repeats {a.repeats}" if a.loss_weights else f"{' --freeze ' + a.freeze if a.freeze else ''}{' --bn-global' if a.bn_global else ''} --repeats {a.repeats}" if (a.freeze or a.bn_global) else f" --eval {a.n_eval} --repeats {a.repeats}" if a.n_eval else f" --img-chunks {a.img_chunks}{' --devices ' + a.devices if a.devices else ''} --repeats {a.repeats}" if a.img_chunks else f" --grad-operands {a.grad_operands} --repeats {a.repeats}" if a.grad_operands else f" --devices {a.devices}" if a.devices else f" --solver {a.solver} --clip {a.clip}{' --swap' if a.swap else ''}{f' --iter-size {a.iter_size}' if a.iter_size > 1 else ''} --repeats {a.repeats}" if a.solver else f" --sgd --repeats {a.repeats}" if a.sgd else f" --graph --repeats {a.repeats}" if a.graph else f" --fuse-relu-grad --repeats {a.repeats}" if a.fuse_relu_grad else f" --fuse-filts-biases --repeats {a.repeats}" if a.fuse_filts_biases else ""
         f.write(f"# python tools/bck_pipe_bench.py --nets {a.nets} --batch {a.batch} --runs {a.runs} --warmup {a.warmup}{extra}\n" + "\n".join(lines) + "\n")
     return 0
 
