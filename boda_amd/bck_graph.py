@@ -300,6 +300,8 @@ def grad_op_to_op(bp: BckPipe, o: GradOp) -> Op:
     if t in ("Convolution", "BckConv"):
         v = {"in": nd(o.bots[0]), "filts": nd(o.bots[1]), "biases": nd(o.bots[2]), "kern_sz": _none(*s.kern_sz), "stride": _none(*s.stride), "in_pad": _none(*s.in_pad),
              "out_chans": _u32(s.out_chans)}
+        if getattr(s, "group", 1) > 1:   # (an ungrouped layer's op is what it has always been)
+            v["group"] = _u32(s.group)
         if t == "Convolution":
             v["out"] = nd(o.tops[0])
         else:
@@ -365,6 +367,8 @@ def plan_relu_grad_folds(bp: BckPipe) -> Tuple[Dict[str, str], Dict[str, str]]:
         elif prev.type not in RELU_GRAD_PRODUCERS:
             why[o.tag] = f"the op before it is {prev.tag}, a {prev.type}" + (f": {gl} sums the partial gradients of {x}'s readers" if prev.type == "Reduce" else
                                                                              f" between {gl}'s producer and the ReLU gradient" if prev.type == "BckDropout" else "")
+        elif prev.type == "BckConv" and getattr(prev.src, "group", 1) > 1:
+            why[o.tag] = f"the op before it, {prev.tag}, is a grouped convolution's gradient (group={prev.src.group}): hip_bconv_in_grp takes no zero_if_in_non_pos"
         elif prev.tops[0] != gl:
             why[o.tag] = f"the op before it, {prev.tag}, writes {prev.tops[0]}, not {gl}"
         elif prev.bots[RELU_GRAD_PRODUCERS[prev.type]] != x:

@@ -18,7 +18,7 @@ from .bck_graph import (AFFINE_IN_PLACE_TYPES, DROPOUT_RATIO, IN_PLACE_TYPES, RE
                         plan_relu_grad_folds)
 from .call_list import BckCall, CallList
 from .cnn_op import (OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, bnc_bck_in_func_op, bnc_bck_sums_func_op, bnc_fwd_func_op, bnc_stats_func_op, BNC_MAX_CHUNKS, fan_out_func_op, sgd_update_func_op, solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op, grad_accum_func_op, solver_update_acc_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos,
-                     seed_from_var, SEED_VAR_ARG, bf16_operands)
+                     seed_from_var, SEED_VAR_ARG, bf16_operands, is_grouped)
 from .cnn_op import bnf_bck_func_op, bnf_bck_in_func_op, bnf_prep_func_op, data_transform_func_op, loss_norm_func_op, softmax_loss_bck_func_op, softmax_loss_fwd_func_op
 from .conv_pipe import ConvPipe, PipeOp
 from .input_pipe import DATA_RAW_VAR, DATA_XF_MEAN_VAR, DATA_XF_PLAN_VAR, DATA_XF_TAG, InputTransform
@@ -131,7 +131,7 @@ class _Lower:
         if self.kept(o, 0):
             takes = o.tag in self.takes_relu
             calls.append((b16(fuse_zero_if_in_non_pos(fi) if takes else fi), dict({"filts": o.bots[1], "out_grad_loss": o.bots[3], "in_grad_loss": o.tops[0]}, **({"in": o.bots[0]} if takes else {}))))
-        if self.kept(o, 1) and self.d.fuse_filts_biases:   # one call writes both gradients  (not kept: both params frozen, the data gradient alone)
+        if self.kept(o, 1) and self.d.fuse_filts_biases and not is_grouped(op):   # one call writes both gradients  (not kept: both params frozen, the data gradient alone; a grouped layer stays on its two calls)
             calls.append((b16(bconv_filts_biases_func_op(op, self.tune)), {"in": o.bots[0], "out_grad_loss": o.bots[3], "filts_grad_loss": o.tops[1], "biases_grad_loss": o.tops[2]}))
         elif self.kept(o, 1):
             calls.append((fb, {"out_grad_loss": o.bots[3], "biases_grad_loss": o.tops[2]}))
@@ -378,6 +378,13 @@ class ConvPipeBck:
         if self.img_chunks and multi_dev and self.img_chunks != len(self.rtc.devices):
             raise RtErr(f"ConvPipeBck.init: img_chunks={self.img_chunks} on {len(self.rtc.devices)} devices: chunk i of a BatchNorm's sums is device i's img shard, so img_chunks must "
                         "be the device count")
+        grouped = [o for o in bp.fwd_ops() if o.type == "Convolution" and getattr(o.src, "group", 1) > 1]
+        if grouped and self.grad_operands:
+            raise UnsupErr(f"ConvPipeBck.init: grad_operands='bf16': the convolution {grouped[0].tag!r} has group={grouped[0].src.group}, and a grouped convolution's gradients "
+                           "(hip_bconv_in_grp, hip_bconv_filts_grp) are fp32 only; leave the option off for a pipe with grouped layers")
+        if grouped and multi_dev:
+            raise UnsupErr(f"ConvPipeBck.init: the convolution {grouped[0].tag!r} has group={grouped[0].src.group}: the grouped functions take vars of exactly their op's dims, "
+                           "not img shards, and are not provided on a multi-device backend (devices=...); grouped layers on several devices are out of scope")
         spec_heads = [o for o in bp.fwd_ops() if o.type == "SoftmaxWithLoss" and o.spec is not None]
         if spec_heads and multi_dev:
             raise UnsupErr(f"ConvPipeBck.init: the loss {spec_heads[0].tag!r} has a LossSpec: the full softmax loss (hip_softmax_loss_fwd, hip_loss_norm, hip_softmax_loss_bck) "

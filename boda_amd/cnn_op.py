@@ -128,9 +128,12 @@ def add_codegen_annotations(op: Op, tune: OpTune, tile_wisdom=None) -> Op:
     t = a.get_type()
     native = (tune.use_be in ("", "hip"))
     if t == "Convolution":
-        a.conv_geom()
+        grouped = "G" in a.conv_geom()
         a.set_u32("conv_has_relu", 1)  # every Convolution under ops-prof (src/cnn_op.cc:337)
-        if tune.use_culibs:
+        if grouped:   # group > 1: the grouped family's forward function and nothing else (fp32, reference layouts)
+            refuse_grouped(a, tune)
+            a.set_func_name(CONV_GRP_FUNC)
+        elif tune.use_culibs:
             a.set_func_name("cudnn_conv")
         elif native and not (tune.k1conv or tune.tconv or tune.ipconv) and tune.hip_dtype == "bf16" and tune.hip_layout == "nhwc":
             from . import nhwc
@@ -152,12 +155,75 @@ def add_codegen_annotations(op: Op, tune: OpTune, tile_wisdom=None) -> Op:
         raise UnsupErr(f"op type {t!r} is not on the conv_fwd / sgemm hot path")
     if not tune.hip_exact and native and not tune.use_culibs and tune.hip_dtype != "bf16":
         a.str_vals["hip_exact"] = "0"   # travels with the function, like hip_tile
-    if tune.hip_tile and native and not tune.use_culibs:
-        a.str_vals["hip_tile"] = tune.hip_tile   # travels with the function: the backend applies it to this function's calls only
+    if tune.hip_tile and native and not tune.use_culibs and (a.get_func_name() != CONV_GRP_FUNC or is_grp_tile(tune.hip_tile)):
+        a.str_vals["hip_tile"] = tune.hip_tile   # travels with the function: the backend applies it to this function's calls only (a grouped op: its own seven-field form only)
     return a
 
 
 BCONV_FUNCS = ("hip_bconv_in", "hip_bconv_biases", "hip_bconv_filts")   # the order of the reference's three calls (src/rtc_fwd.cc:398-400)
+
+# a Convolution / BckConv with group = g > 1 (Caffe's `group`; the reference has none): for every group the ungrouped function on the op sliced to that group
+# (kernels/conv_grp_f32.hip).  The bias gradient knows no groups: it stays hip_bconv_biases
+CONV_GRP_FUNC = "hip_conv_grp"
+BCONV_GRP_FUNCS = ("hip_bconv_in_grp", "hip_bconv_biases", "hip_bconv_filts_grp")   # the same call order
+
+
+def op_group(op: Op) -> int:
+    """Caffe's `group` of a Convolution / BckConv op: uint32 group, the form of out_chans; absent means 1."""
+    return op.get_u32("group") if op.has("group") else 1
+
+
+def is_grp_tile(tile: str) -> bool:
+    """Is `tile` the grouped family's own form, seven fields BIxBJxBKxWIxWJxMINWxKSL?  A pipe-wide tile written for hip_conv / hip_bconv_* (five or six fields, or
+    more than seven) is not: it passes a grouped layer by, and the planner chooses for it."""
+    return bool(tile) and tile.count("x") == 6
+
+
+def is_grouped(op: Op) -> bool:
+    return op.get_type() in ("Convolution", "BckConv") and op_group(op) > 1
+
+
+def refuse_grouped(op: Op, tune: OpTune = None, what: str = "") -> None:
+    """UnsupErr that names `group` where a grouped op meets a function or an option that has no grouped form: everything but fp32 in reference layouts on the
+    grouped family's own three functions."""
+    g = op_group(op)
+    if g <= 1:
+        return
+    if what:
+        raise UnsupErr(f"{what}: the op carries group={g}: a grouped convolution runs as {CONV_GRP_FUNC} / {BCONV_GRP_FUNCS[0]} / {BCONV_GRP_FUNCS[2]} "
+                       f"(fp32, reference layouts) only")
+    if tune is None:
+        return
+    bad = [n for n, v in (("use_culibs", tune.use_culibs), ("k1conv", tune.k1conv), ("tconv", tune.tconv), ("ipconv", tune.ipconv), ("hip_algo", tune.hip_algo),
+                          ("hip_layout", tune.hip_layout), ("hip_out", tune.hip_out)) if v]
+    if tune.hip_dtype not in ("", "f32"):
+        bad.append("hip_dtype")
+    if tune.use_be not in ("", "hip"):
+        bad.append("use_be")
+    if not tune.hip_exact:
+        bad.append("hip_exact=0")
+    if bad:
+        raise UnsupErr(f"group={g}: a grouped convolution has no form under op_tune {', '.join(bad)} ({tune.to_str()}): fp32 in reference layouts only "
+                       f"({CONV_GRP_FUNC} / {BCONV_GRP_FUNCS[0]} / {BCONV_GRP_FUNCS[2]})")
+
+
+def add_bck_conv_grp_annotations(op: Op, tune: OpTune) -> tuple:
+    """-> (in_op, biases_op, filts_op) of a BckConv with group > 1, in the reference's call order: hip_bconv_in_grp, hip_bconv_biases (the ungrouped function as it is:
+    the bias gradient does not depend on groups), hip_bconv_filts_grp.  A seven-field tile in the tune travels with the two grouped functions; any other tile (a
+    pipe-wide one written for the ungrouped functions) passes them by."""
+    if op.get_type() != "BckConv":
+        raise RtErr(f"add_bck_conv_grp_annotations: op type {op.get_type()!r} is not BckConv")
+    if "G" not in op.bck_conv_geom():
+        raise RtErr("add_bck_conv_grp_annotations: the op carries no group > 1 (add_bck_conv_annotations is the annotator of an ungrouped BckConv)")
+    refuse_grouped(op, tune)
+    outs = []
+    for fn in BCONV_GRP_FUNCS:
+        a = op.copy()
+        a.set_func_name(fn)
+        if is_grp_tile(tune.hip_tile) and fn != "hip_bconv_biases":
+            a.str_vals["hip_tile"] = tune.hip_tile
+        outs.append(a)
+    return tuple(outs)
 
 
 def add_bck_conv_annotations(op: Op, tune: OpTune) -> tuple:
@@ -166,7 +232,8 @@ def add_bck_conv_annotations(op: Op, tune: OpTune) -> tuple:
     are not provided); a tile in the tune travels with the data and filter gradient functions."""
     if op.get_type() != "BckConv":
         raise RtErr(f"add_bck_conv_annotations: op type {op.get_type()!r} is not BckConv")
-    op.bck_conv_geom()
+    if "G" in op.bck_conv_geom():   # group > 1: the grouped family's annotator
+        return add_bck_conv_grp_annotations(op, tune)
     if tune.use_be not in ("", "hip") or tune.use_culibs or tune.k1conv or tune.tconv or tune.ipconv:
         raise UnsupErr(f"BckConv variants of op_tune={tune.to_str()} are generated by the reference's CUCL code generator; be=hip provides hip_bconv_*")
     if tune.hip_dtype not in ("", "f32") or tune.hip_layout or tune.hip_algo or tune.hip_out:
@@ -191,6 +258,7 @@ def bconv_filts_biases_func_op(op: Op, tune: OpTune) -> Op:
     with the function."""
     if op.get_type() != "BckConv":
         raise RtErr(f"bconv_filts_biases_func_op: op type {op.get_type()!r} is not BckConv")
+    refuse_grouped(op, what=BCONV_FB_FUNC)
     op.bck_conv_geom()
     if tune.use_be not in ("", "hip") or tune.use_culibs or tune.k1conv or tune.tconv or tune.ipconv:
         raise UnsupErr(f"BckConv variants of op_tune={tune.to_str()} are generated by the reference's CUCL code generator; be=hip provides hip_bconv_*")
@@ -714,6 +782,8 @@ def fuse_zero_if_in_non_pos(fop: Op) -> Op:
     in_grad_loss[e] = in[e] > 0 ? g[e] : +0, g being what the unflagged function writes and `in` the op's forward input -- the ReLU gradient (hip_zero_if_non_pos
     with cond = in) folded into the store.  hip_bconv_in and hip_spreading take `in` as one more var arg (pipe_func_args); hip_bck_lrn reads it already."""
     fn = fop.get_func_name() if fop.has_func_name() else ""
+    if is_grouped(fop):
+        refuse_grouped(fop, what=f"fuse_zero_if_in_non_pos ({fn or fop.get_type()})")
     if fn not in ZINP_FUNCS:
         raise RtErr(f"fuse_zero_if_in_non_pos: {fn or fop.get_type()!r} is none of {', '.join(ZINP_FUNCS)} (the functions whose in_grad_loss has the dims of their forward input)")
     if fop.get_dims("in") != fop.get_dims("in_grad_loss"):
@@ -738,6 +808,8 @@ def bf16_operands(fop: Op) -> Op:
     chain; zero_if_in_non_pos=1 composes (the condition is read unrounded).  The data and filter gradients are held to a bound, not to bits.
     hip_bconv_filts and hip_bconv_biases have no bf16 form of their own: UnsupErr, as on the backends."""
     fn = fop.get_func_name() if fop.has_func_name() else ""
+    if is_grouped(fop):
+        refuse_grouped(fop, what=f"bf16_operands ({fn or fop.get_type()})")
     if fn in ("hip_bconv_filts", "hip_bconv_biases"):
         raise UnsupErr(f"{fn}: hip_operands=bf16: the filter and bias gradients have their bf16-operand form as ONE call, {BCONV_FB_FUNC} "
                        f"(cnn_op.bconv_filts_biases_func_op); hip_bconv_filts and hip_bconv_biases are fp32 only")
@@ -837,6 +909,10 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_bconv_in": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),
     "hip_bconv_filts": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT")),
     "hip_bconv_filts_biases": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT"), ("biases_grad_loss", "OUT")),
+    # a Convolution / BckConv with group > 1: the lists of hip_conv, hip_bconv_in and hip_bconv_filts without their optional args
+    "hip_conv_grp": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),
+    "hip_bconv_in_grp": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),
+    "hip_bconv_filts_grp": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT")),
     "hip_bconv_biases": (("out_grad_loss", "IN"), ("biases_grad_loss", "OUT")),   # filts as [K + 128][out_chan padded to 4]: what hip_conv's optional filts_km arg takes
     # the non-conv backward ops, in their reference templates' arg order (test/rtc/pool.cucl, lrn.cucl, spreading.cucl, bck_lrn.cucl, ZeroIfNonPos.cucl, softmax.cucl,
     # sm_grad_and_loss.cucl, sum_loss_over_imgs.cucl); the by-value scalars of those templates (avg_pool, alpha, ...) ride in the op
@@ -899,9 +975,18 @@ K1_CHAIN_FUNC = "hip_conv_k1_chain"
 FILTS_KMAJOR_FUNC = "hip_conv_filts_kmajor"
 
 
+def filts_kmajor_func_op(conv: Op) -> Op:
+    """-> the hip_conv_filts_kmajor function op of an annotated hip_conv function: filts -> their k-major copy, [K + 128][out_chan padded to 4].  A grouped op is
+    refused by name: hip_conv_grp reads its filters as they are."""
+    refuse_grouped(conv, what=FILTS_KMAJOR_FUNC)
+    return Op({"type": "Convolution", "func_name": FILTS_KMAJOR_FUNC}, {})
+
+
 def k1_chain_applies(a: Op, b: Op) -> bool:
     """Can the fp32 convolutions a -> b (b reads a's output) run as one hip_conv_k1_chain launch?  Mirrors plan_k1_chain (csrc/native_kernels.cc): both 1x1 /
     stride 1 / unpadded, at most 96 intermediate channels, at most 128 out_chans, both filter images (k-major, odd pitch) within the LDS."""
+    if is_grouped(a) or is_grouped(b):   # (a grouped convolution passes the chain by)
+        return False
     ga, gb = a.conv_geom(), b.conv_geom()
     for g in (ga, gb):
         if (g["KH"], g["KW"], g["SY"], g["SX"], g["PY"], g["PX"]) != (1, 1, 1, 1, 0, 0):
@@ -918,6 +1003,8 @@ def k1_chain_applies(a: Op, b: Op) -> bool:
 def annotate_k1_chain(a: Op, b: Op, relu_a: int, relu_b: int) -> Op:
     """The function op of hip_conv_k1_chain for the annotated hip_conv ops a -> b: a's in / filts / biases / stride / in_pad, b's filts / biases as filts2 /
     biases2, b's out; conv_has_relu / conv_has_relu2 the two fused ReLUs."""
+    for x in (a, b):
+        refuse_grouped(x, what=K1_CHAIN_FUNC)
     if not k1_chain_applies(a, b):
         raise UnsupErr("hip_conv_k1_chain: two chained 1x1 / stride-1 / unpadded convolutions with <= 96 intermediate channels and <= 128 out_chans")
     c = a.copy()
@@ -951,6 +1038,7 @@ def fuse_f32_pool(conv: Op, pool_in, kern, stride) -> None:
     with the function: uint32 hip_pool, dims pool_sz / pool_stride.  The reference runs two functions (test/rtc/pool.cucl, then the conv: src/rtc_fwd.cc:545-549); here a
     patch element of the convolution's LDS input patch is the window maximum, formed while the patch is staged (kernels/gemm_conv_f32.hip, PKH).  Bit-identical."""
     from .op import Dims, Nda
+    refuse_grouped(conv, what="fuse_f32_pool (a pooling fused in front of hip_conv)")
     none = lambda y, x: Nda(Dims(("y", "x"), (y, x), "none"), "none")
     conv.nda_vals["in"] = Nda(dims=pool_in, tn=pool_in.tn)
     conv.set_u32("hip_pool", 1)

@@ -85,7 +85,7 @@ class OpInfoToLatex:
             g = op.conv_geom()
             self.din, self.dout = op.get_dims("in"), op.get_dims("out")
             self.B = g["B"]
-            self.M, self.K, self.N = g["B"] * g["OH"] * g["OW"], g["C"] * g["KH"] * g["KW"], g["OC"]
+            self.M, self.K, self.N = g["B"] * g["OH"] * g["OW"], g.get("CG", g["C"]) * g["KH"] * g["KW"], g["OC"]   # (K of a grouped op: its group's C/g channels)
         elif t == "sgemm":
             g = op.sgemm_geom()
             self.B, self.M, self.K, self.N = 1, g["M"], g["K"], g["N"]

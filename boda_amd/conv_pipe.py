@@ -25,7 +25,7 @@ import os
 import numpy as np
 
 from . import gen_data as gd
-from .cnn_op import CHAN_AFFINE_FUNC, FILTS_KMAJOR_FUNC, K1_CHAIN_FUNC, NATIVE_ARGS, OpTune, chan_affine_func_op, pipe_func_args, add_codegen_annotations, annotate_k1_chain, f32_pool_fusable, fuse_f32_pool, k1_chain_applies
+from .cnn_op import CHAN_AFFINE_FUNC, FILTS_KMAJOR_FUNC, K1_CHAIN_FUNC, NATIVE_ARGS, OpTune, chan_affine_func_op, pipe_func_args, add_codegen_annotations, annotate_k1_chain, f32_pool_fusable, filts_kmajor_func_op, fuse_f32_pool, k1_chain_applies
 from .cucl_template import instantiate, parse_template
 from .op import Dims, Nda, Op, RtErr, UnsupErr
 from .rtc import HipCompute, RtcArg, RtcCompileOpts, RtcFuncCall, RtcFuncInfo
@@ -48,6 +48,7 @@ class PipeOp:
     lrn: Tuple[int, float, float, float] = (5, 1.0, 0.75, 1.0)  # local_size, alpha, beta, k (src/conv_util.cc:42-48)
     bots: Tuple[str, ...] = ()     # Concat: all inputs in channel order (bot == bots[0]); Eltwise: the 2 to 8 nodes that are summed, in that order
     eps: float = 1e-5              # BatchNorm: added to the variance
+    group: int = 1                 # Convolution: Caffe's `group` -- out_chans j*OC/g .. read channels j*C/g .. only; filts are out_chan : in_chan=C/g : y : x
 
     @property
     def in_place(self) -> bool:
@@ -75,8 +76,10 @@ class ConvPipe:
             oh = (H + 2 * op.in_pad[0] - kh) // op.stride[0] + 1; ow = (W + 2 * op.in_pad[1] - kw) // op.stride[1] + 1
             if oh < 1 or ow < 1:
                 raise RtErr(f"pipe: conv {op.tag}: padded input too small")
+            if op.group < 1 or C % op.group or op.out_chans % op.group:
+                raise RtErr(f"pipe: conv {op.tag}: group={op.group} must divide its {C} input channels and its out_chans={op.out_chans}")
             out = Dims.make("float", img=B, chan=op.out_chans, y=oh, x=ow)
-            self.params[op.tag + "_filts"] = Dims.make("float", out_chan=op.out_chans, in_chan=C, y=kh, x=kw)
+            self.params[op.tag + "_filts"] = Dims.make("float", out_chan=op.out_chans, in_chan=C // op.group, y=kh, x=kw)
             self.params[op.tag + "_biases"] = Dims.make("float", out_chan=op.out_chans)
         elif op.type == "Pooling":
             if op.kern_sz is None:   # global pooling
@@ -131,10 +134,13 @@ class ConvPipe:
         """The op_base_t line of a Convolution of this pipe (same text form as the ops-prof op lists)."""
         i, o = self.nodes[op.bot], self.nodes[op.top]
         none = lambda y, x: Nda(Dims(("y", "x"), (y, x), "none"), "none")
-        return Op({"type": "Convolution"}, {"in": Nda(i), "out": Nda(o), "filts": Nda(self.params[op.tag + "_filts"]),
-                                            "biases": Nda(self.params[op.tag + "_biases"]), "kern_sz": none(*op.kern_sz),
-                                            "stride": none(*op.stride), "in_pad": none(*op.in_pad),
-                                            "out_chans": Nda(None, "uint32_t", (op.out_chans,))})
+        r = Op({"type": "Convolution"}, {"in": Nda(i), "out": Nda(o), "filts": Nda(self.params[op.tag + "_filts"]),
+                                         "biases": Nda(self.params[op.tag + "_biases"]), "kern_sz": none(*op.kern_sz),
+                                         "stride": none(*op.stride), "in_pad": none(*op.in_pad),
+                                         "out_chans": Nda(None, "uint32_t", (op.out_chans,))})
+        if op.group > 1:   # (an ungrouped layer's op is what it has always been)
+            r.nda_vals["group"] = Nda(None, "uint32_t", (op.group,))
+        return r
 
     def conv_flops(self) -> int:
         return sum(self.conv_op(o).flops() for o in self.ops if o.type == "Convolution")
@@ -252,8 +258,8 @@ def sibling_runs(ops: List[PipeOp], members: List[PipeOp], fused=frozenset()) ->
     return runs
 
 
-def _conv(p, tag, bot, oc, k, s=1, pad=0):
-    p.add(PipeOp(tag, "Convolution", bot, tag, out_chans=oc, kern_sz=(k, k), stride=(s, s), in_pad=(pad, pad)))
+def _conv(p, tag, bot, oc, k, s=1, pad=0, group=1):
+    p.add(PipeOp(tag, "Convolution", bot, tag, out_chans=oc, kern_sz=(k, k), stride=(s, s), in_pad=(pad, pad), group=group))
     p.add(PipeOp("relu_" + tag, "ReLU", tag, tag))
     return tag
 
@@ -288,6 +294,35 @@ def alexnet_ng_conv(batch: int, in_hw: int = 227) -> ConvPipe:
     n = _conv(p, "fc6", "pool5", 4096, 6); p.add(PipeOp("drop6", "Dropout", n, n))
     n = _conv(p, "fc7", n, 4096, 1); p.add(PipeOp("drop7", "Dropout", n, n))
     p.add(PipeOp("fc8", "Convolution", n, "fc8", out_chans=1000, kern_sz=(1, 1)))
+    return p
+
+
+def alexnet(batch: int, in_hw: int = 227) -> ConvPipe:
+    """The published AlexNet / CaffeNet layer geometry (bvlc_alexnet deploy: group: 2 on conv2, conv4 and conv5, so conv2's filters are 256 x 48 x 5 x 5), the fc
+    layers as convolutions: alexnet_ng_conv with the groups put back."""
+    p = ConvPipe("alexnet", "data", Dims.make("float", img=batch, chan=3, y=in_hw, x=in_hw))
+    lrn = (5, 1e-4, 0.75, 1.0)
+    n = _conv(p, "conv1", "data", 96, 11, 4)
+    p.add(PipeOp("norm1", "LRN", n, "norm1", lrn=lrn)); p.add(PipeOp("pool1", "Pooling", "norm1", "pool1", kern_sz=(3, 3), stride=(2, 2)))
+    n = _conv(p, "conv2", "pool1", 256, 5, 1, 2, group=2)
+    p.add(PipeOp("norm2", "LRN", n, "norm2", lrn=lrn)); p.add(PipeOp("pool2", "Pooling", "norm2", "pool2", kern_sz=(3, 3), stride=(2, 2)))
+    n = _conv(p, "conv3", "pool2", 384, 3, 1, 1); n = _conv(p, "conv4", n, 384, 3, 1, 1, group=2); n = _conv(p, "conv5", n, 256, 3, 1, 1, group=2)
+    p.add(PipeOp("pool5", "Pooling", n, "pool5", kern_sz=(3, 3), stride=(2, 2)))
+    n = _conv(p, "fc6", "pool5", 4096, 6); p.add(PipeOp("drop6", "Dropout", n, n))
+    n = _conv(p, "fc7", n, 4096, 1); p.add(PipeOp("drop7", "Dropout", n, n))
+    p.add(PipeOp("fc8", "Convolution", n, "fc8", out_chans=1000, kern_sz=(1, 1)))
+    return p
+
+
+def dw_sep_tiny(batch: int, in_hw: int = 12, classes: int = 10) -> ConvPipe:
+    """A small depthwise-separable net for the tests: a 3x3 stem, two depthwise 3x3 + pointwise 1x1 pairs (the second depthwise at stride 2), every convolution with
+    its ReLU, global average pooling and an fc layer."""
+    p = ConvPipe("dw_sep_tiny", "data", Dims.make("float", img=batch, chan=3, y=in_hw, x=in_hw))
+    n = _conv(p, "stem", "data", 8, 3, 1, 1)
+    n = _conv(p, "dw1", n, 8, 3, 1, 1, group=8); n = _conv(p, "pw1", n, 12, 1)
+    n = _conv(p, "dw2", n, 12, 3, 2, 1, group=12); n = _conv(p, "pw2", n, 16, 1)
+    p.add(PipeOp("pool", "Pooling", n, "pool", kern_sz=None, avg_pool=1))
+    p.add(PipeOp("fc", "Convolution", "pool", "fc", out_chans=classes, kern_sz=(0, 0)))
     return p
 
 
@@ -336,7 +371,8 @@ def pipe_from_spec(name: str, lines: Sequence[str], batch: int) -> ConvPipe:
         k = f[0]
         if k == "conv":
             oc, kh, kw, sy, sx, py, px = (int(x) for x in f[4:11])
-            p.add(PipeOp(f[1], "Convolution", f[2], f[3], out_chans=oc, kern_sz=(kh, kw), stride=(sy, sx), in_pad=(py, px)))
+            grp = int(f[11]) if len(f) > 11 else 1   # (an optional twelfth field: the group)
+            p.add(PipeOp(f[1], "Convolution", f[2], f[3], out_chans=oc, kern_sz=(kh, kw), stride=(sy, sx), in_pad=(py, px), group=grp))
         elif k == "pool":
             kh, kw, sy, sx, py, px, avg, glob = (int(x) for x in f[4:12])
             p.add(PipeOp(f[1], "Pooling", f[2], f[3], kern_sz=None if glob else (kh, kw), stride=(sy, sx), in_pad=(py, px), avg_pool=avg))
@@ -584,6 +620,14 @@ class ConvPipeFwd:
     def init(self, cp: ConvPipe, op_params: Optional[Dict[str, np.ndarray]] = None, gen_mode: int = 5) -> None:
         rtc = self.rtc
         self.cp = cp
+        # grouped convolutions (PipeOp.group > 1) run as hip_conv_grp: fp32 in reference layouts only -- refused by the first such layer's name, before anything is created
+        for o in cp.ops:
+            if o.type == "Convolution" and o.group > 1:
+                try:
+                    add_codegen_annotations(cp.conv_op(o), self.op_tune)
+                except UnsupErr as e:
+                    raise UnsupErr(f"pipe {cp.name}: convolution {o.tag}: {e}") from None
+                break
         try:    # the device's CU count for the planner questions asked below (a recording backend has none: the MI355X's 256)
             info = rtc.get_device_info()
             self._num_cus = int(info["num_cus"]) if isinstance(info, dict) and info.get("num_cus") else 256
@@ -648,7 +692,7 @@ class ConvPipeFwd:
                 if not o.in_place:
                     for b in (o.bots or (o.bot,)):
                         readers[b] = readers.get(b, 0) + 1
-            conv_tops = {o.top for o in cp.ops if o.type == "Convolution"}
+            conv_tops = {o.top for o in cp.ops if o.type == "Convolution" and o.group == 1}   # (hip_conv_grp writes whole tensors: a grouped convolution keeps its node)
             # a top that an un-fused in-place op (a ReLU that is not the conv's immediate successor, an in-place LRN) still works on
             # must exist as a var of its own: it is not eliminated
             inplace_targets = {o.top for o in cp.ops if o.in_place and o.tag not in fused and o.type != "Dropout"}
@@ -1014,7 +1058,7 @@ class ConvPipeFwd:
                     kmd = Dims(("k", "out_chan"), (fd.dsz("in_chan") * fd.dsz("y") * fd.dsz("x") + 128, (fd.dsz("out_chan") + 3) // 4 * 4), "float")
                     rtc.create_var_with_dims(kmv, kmd); self._vars.append(kmv)
                     xfn = f"{FILTS_KMAJOR_FUNC}__{cp.name}_{op.tag}"
-                    rtc.compile([RtcFuncInfo(xfn, "", [a for a, _ in NATIVE_ARGS[FILTS_KMAJOR_FUNC]], Op({"type": "Convolution", "func_name": FILTS_KMAJOR_FUNC}, {}))]); self._funcs.append(xfn)
+                    rtc.compile([RtcFuncInfo(xfn, "", [a for a, _ in NATIVE_ARGS[FILTS_KMAJOR_FUNC]], filts_kmajor_func_op(anno))]); self._funcs.append(xfn)
                     self._km_params.append(RtcFuncCall(xfn, {"filts": am["filts"], "filts_km": RtcArg.var(kmv)}))
                     am["filts_km"] = RtcArg.var(kmv)
                 self.fwd_calls.append(FwdCall(op.tag, RtcFuncCall(gen_fn, am), fn, cop.flops()))

@@ -82,7 +82,10 @@ void tiled_contract(micro_t micro, float const *at, long lda, long Mi, long Nj, 
   }
 }
 
-struct conv_geom_c { long B, C, H, W, OC, KH, KW, SY, SX, PY, PX, OH, OW; bool relu; };
+// CT / OCT (a grouped convolution run per group on offset pointers: C and OC are then ONE group's channels): the channels of the whole in / out tensors, which the image
+// strides follow; 0: C / OC
+struct conv_geom_c { long B, C, H, W, OC, KH, KW, SY, SX, PY, PX, OH, OW; bool relu; long CT, OCT;
+  long in_chans() const { return CT ? CT : C; } long out_chans() const { return OCT ? OCT : OC; } };
 
 // ---- the non-conv ops of the gradient pipe: plain loops in exactly the reference templates' order (test/rtc/pool.cucl, spreading.cucl, lrn.cucl, bck_lrn.cucl,
 // ZeroIfNonPos.cucl, softmax.cucl, sm_grad_and_loss.cucl, sum_loss_over_imgs.cucl), parallel over outputs.  They are the bit-exact checker of the HIP kernels
@@ -649,6 +652,7 @@ struct cpu_compute_t : public rtc_compute_t {
       if (f->family == kFamEval) (void)eval_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamData) (void)data_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamLoss) (void)loss_op_of_op(fi.op);   // (likewise)
+      if (f->family == kFamConvGrp) (void)conv_grp_geom_of_op(fi.op, f->member);   // (likewise: the group count and the geometry it needs)
       if (f->family == kFamBckOp) {
         if (!f->of_type(fi.op.get_type())) rt_err(fn + ": a function of op type " + f->types[0] + ", not " + fi.op.get_type());
         bck_op_args_t const a = bck_op_args(*f, fi.op);
@@ -689,7 +693,7 @@ struct cpu_compute_t : public rtc_compute_t {
         for (long n = 0; n < nb; ++n) {
           long const j = j0 + n, img = j / OHW, pel = j - img * OHW, oy = pel / g.OW, ox = pel - oy * g.OW;
           iy0[n] = (int)(oy * g.SY - g.PY); ix0[n] = (int)(ox * g.SX - g.PX);
-          base[n] = (img * g.C * g.H + iy0[n]) * g.W + ix0[n];
+          base[n] = (img * g.in_chans() * g.H + iy0[n]) * g.W + ix0[n];
         }
         for (int kk = 0; kk < kc; ++kk) {
           long const k = k0 + kk, c = k / (g.KH * g.KW), r = k - c * (g.KH * g.KW), ky = r / g.KW, kx = r - ky * g.KW;
@@ -708,7 +712,7 @@ struct cpu_compute_t : public rtc_compute_t {
             long const j = j0 + n, img = j / OHW, pel = j - img * OHW;
             float v = ct[m * kNB + n] + bias;
             if (g.relu) v = (v > 0.f) ? v : 0.f;
-            out[(img * g.OC + i0 + m) * OHW + pel] = v;
+            out[(img * g.out_chans() + i0 + m) * OHW + pel] = v;
           }
         } });
   }
@@ -729,10 +733,10 @@ struct cpu_compute_t : public rtc_compute_t {
               for (long ox = oxb; ox < oxe; ++ox, fx -= g.SX) {
                 long fy = y + g.PY - oyb * g.SY;
                 for (long oy = oyb; oy < oye; ++oy, fy -= g.SY)
-                  v = fmaf(ogl[((img * g.OC + oc) * g.OH + oy) * g.OW + ox], filts[((oc * g.C + c) * g.KH + fy) * g.KW + fx], v);
+                  v = fmaf(ogl[((img * g.out_chans() + oc) * g.OH + oy) * g.OW + ox], filts[((oc * g.C + c) * g.KH + fy) * g.KW + fx], v);
               }
             }
-            long const ix = ((img * g.C + c) * g.H + y) * g.W + x;
+            long const ix = ((img * g.in_chans() + c) * g.H + y) * g.W + x;
             igl[ix] = (zin && !(zin[ix] > 0.0f)) ? 0.0f : v;
           }
   }
@@ -746,7 +750,7 @@ struct cpu_compute_t : public rtc_compute_t {
             long oxb = 0, ixb = fx - g.PX; while (ixb < 0) { ixb += g.SX; ++oxb; }
             float v = 0.f;
             for (long img = 0; img < g.B; ++img) {
-              float const *ip = in + (img * g.C + c) * g.H * g.W, *op = ogl + (img * g.OC + oc) * g.OH * g.OW;
+              float const *ip = in + (img * g.in_chans() + c) * g.H * g.W, *op = ogl + (img * g.out_chans() + oc) * g.OH * g.OW;
               long oy = oyb;
               for (long iy = iyb; iy < g.H && oy < g.OH; iy += g.SY, ++oy) {
                 long ox = oxb;
@@ -832,6 +836,38 @@ struct cpu_compute_t : public rtc_compute_t {
     }
     if (din) bconv_in((float const *)must_find(vis, fnm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, inm).buf.get(), g, zin);
     else bconv_filts((float const *)must_find(vis, inm).buf.get(), (float const *)must_find(vis, ognm).buf.get(), (float *)must_find(vis, fnm).buf.get(), g);
+  }
+
+  // the grouped family (hip_conv_grp, hip_bconv_in_grp, hip_bconv_filts_grp): for every group the ungrouped function's own loops above, on pointers offset by the
+  // group's channels / filter rows, the image strides those of the whole tensors (conv_geom_c::CT / OCT).  Every var has exactly the dims the op gives its arg
+  void run_conv_grp(native_func_t const &f, op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = f.name;
+    conv_grp_geom_t const cg = conv_grp_geom_of_op(op, f.member);
+    auto si = am.find("stride"), pi = am.find("in_pad");
+    if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
+    if (!(si->second.get_dims(*this) == op.get_dims("stride")) || !(pi->second.get_dims(*this) == op.get_dims("in_pad"))) rt_err(fn + ": stride / in_pad args disagree with the op");
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    auto var_ptr = [&](char const *an) -> float * {
+      string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn); need_float(vd, an);
+      if (!(vd == op.get_dims(an))) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + op.get_dims(an).pretty_str());
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      return (float *)must_find(vis, vn).buf.get();
+    };
+    conv_geom_c g; memset(&g, 0, sizeof(g));
+    g.B = cg.B; g.C = cg.CG; g.H = cg.H; g.W = cg.W; g.OC = cg.OCG; g.KH = cg.KH; g.KW = cg.KW; g.SY = cg.SY; g.SX = cg.SX; g.PY = cg.PY; g.PX = cg.PX; g.OH = cg.OH; g.OW = cg.OW;
+    g.relu = cg.relu; g.CT = cg.C; g.OCT = cg.OC;
+    long const f_grp = (long)cg.OCG * cg.CG * cg.KH * cg.KW, in_grp = (long)cg.CG * cg.H * cg.W, out_grp = (long)cg.OCG * cg.OH * cg.OW;
+    if (f.member == kConvGrpFwd) {
+      float const *filts = var_ptr("filts"), *biases = var_ptr("biases"), *in = var_ptr("in"); float *out = var_ptr("out");
+      for (long j = 0; j < cg.G; ++j) conv(filts + j * f_grp, biases + j * cg.OCG, in + j * in_grp, out + j * out_grp, g);
+    } else if (f.member == kConvGrpBckIn) {
+      float const *filts = var_ptr("filts"), *ogl = var_ptr("out_grad_loss"); float *igl = var_ptr("in_grad_loss");
+      for (long j = 0; j < cg.G; ++j) bconv_in(filts + j * f_grp, ogl + j * out_grp, igl + j * in_grp, g);
+    } else {
+      float const *in = var_ptr("in"), *ogl = var_ptr("out_grad_loss"); float *fgl = var_ptr("filts_grad_loss");
+      for (long j = 0; j < cg.G; ++j) bconv_filts(in + j * in_grp, ogl + j * out_grp, fgl + j * f_grp, g);
+    }
   }
 
   static float op_f32(op_base_t const &op, string const &an) {
@@ -1135,6 +1171,7 @@ struct cpu_compute_t : public rtc_compute_t {
     else if (f.family == kFamLoss) run_loss(fi.op, am);
     else if (f.family == kFamBckOp) run_bck_op(f, fi.op, am);
     else if (f.family == kFamBconv) run_bck(f, fi.op, am);
+    else if (f.family == kFamConvGrp) run_conv_grp(f, fi.op, am);
     else if (f.family == kFamSgemm) {
       string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");
       dims_t const a = get_var_dims(an), b = get_var_dims(bn), c = get_var_dims(cn);
@@ -1152,7 +1189,7 @@ struct cpu_compute_t : public rtc_compute_t {
       if (si == am.end() || pi == am.end()) rt_err("hip_conv: 'stride' and 'in_pad' REF args are required");
       dims_t const stride = si->second.get_dims(*this), in_pad = pi->second.get_dims(*this);
       assert_st(f.sz() == 4 && in.sz() == 4 && out.sz() == 4 && bi.sz() == 1 && stride.sz() == 2 && in_pad.sz() == 2);
-      conv_geom_c g;
+      conv_geom_c g; memset(&g, 0, sizeof(g));
       g.B = in.dsz("img"); g.C = in.dsz("chan"); g.H = in.dsz("y"); g.W = in.dsz("x"); g.OC = f.dsz("out_chan"); g.KH = f.dsz("y"); g.KW = f.dsz("x");
       g.SY = stride.dsz("y"); g.SX = stride.dsz("x"); g.PY = in_pad.dsz("y"); g.PX = in_pad.dsz("x"); g.OH = out.dsz("y"); g.OW = out.dsz("x");
       g.relu = fi.op.get_u32("conv_has_relu") != 0;

@@ -313,6 +313,19 @@ struct softmax_loss_bck_args_t {
 static_assert(sizeof(softmax_loss_bck_args_t) == 56 && __builtin_offsetof(softmax_loss_bck_args_t, grad) == 24 && __builtin_offsetof(softmax_loss_bck_args_t, n) == 32 &&
               __builtin_offsetof(softmax_loss_bck_args_t, C) == 40 && __builtin_offsetof(softmax_loss_bck_args_t, ignore) == 52, "softmax_loss_bck_args_t layout");
 
+// kernels/conv_grp_f32.hip: a grouped convolution and its data / filter gradients (hip_conv_grp, hip_bconv_in_grp, hip_bconv_filts_grp)
+struct conv_grp_args_t {
+  float const *a; float const *b; float const *bias; float *d;   // forward: a = filts, b = in, bias = biases, d = out; data gradient: a = filts, b = out_grad_loss,
+                                                                 // d = in_grad_loss; filter gradient: a = out_grad_loss, b = in, d = filts_grad_loss
+  int B, C, H, W, OC, OH, OW;   // the WHOLE tensors' channels: the image strides; a group's share is the kernel's -DCG / -DOCG
+  int kt_per;                   // filter gradient: K steps per slice
+  long n;                       // threads that have work
+  unsigned a_bytes, b_bytes, d_bytes, ksl;   // ksl: the direct filter gradient's slab sum: slabs to add
+  float *ws;                    // the direct filter gradient with K slices: the call's slabs, [slice][filts_grad_loss's elements]
+};
+static_assert(sizeof(conv_grp_args_t) == 96 && __builtin_offsetof(conv_grp_args_t, B) == 32 && __builtin_offsetof(conv_grp_args_t, n) == 64 &&
+              __builtin_offsetof(conv_grp_args_t, a_bytes) == 72 && __builtin_offsetof(conv_grp_args_t, ws) == 88, "conv_grp_args_t layout");
+
 #pragma pop_macro("CH")
 #pragma pop_macro("CIN")
 #pragma pop_macro("COH")

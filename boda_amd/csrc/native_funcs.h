@@ -10,10 +10,11 @@
 namespace bodahip {
 
 // the family (func_family_t of rtc_types.h) selects the handler (native_run.cc, native_kernels.cc: check_compile_time); handlers switch on the member, never on the name
-inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf", "loss"};
-// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform.  kFamLoss: 1 fwd | 2 norm | 3 bck (loss_op_t::kind)
+inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf", "loss", "conv_grp"};
+// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform.  kFamLoss: 1 fwd | 2 norm | 3 bck (loss_op_t::kind).  kFamConvGrp: 1 fwd | 2 bck_in | 3 bck_filts
 enum { kConvF32 = 0, kConvAlias = 1, kConvBf16 = 2, kConvWinograd = 3 };            // (the alias: hip_conv's contract without its fused pooling and filts_km)
 enum { kBconvIn = 1, kBconvBiases = 2, kBconvFilts = 3, kBconvFiltsBiases = 4 };   // (4 is opt-in: never one of the bare op's three calls)
+enum { kConvGrpFwd = 1, kConvGrpBckIn = 2, kConvGrpBckFilts = 3 };                  // (a grouped convolution and its data / filter gradients; the bias gradient knows no groups)
 enum { kOpPoolYx = 1, kOpSpreading = 2, kOpLrnSb = 3, kOpBckLrn = 4, kOpZeroIfNonPos = 5, kOpSoftmax = 6, kOpSmGradAndLoss = 7, kOpSumLossOverImgs = 8, kOpReduce = 9,
        kOpDropout = 10, kOpConcat = 11, kOpSplit = 12, kOpChanAffine = 13 };
 
@@ -67,7 +68,8 @@ inline constexpr char kWhyBconvSum[] = "(a BckConv filter / bias gradient) sums 
 inline constexpr char kWhyBnSums[] = "(a training BatchNorm's per-channel sums) sums over the images of the WHOLE batch, which would need a cross-device reduction; statistics summed across img shards are out of scope";
 inline constexpr char kWhyBnfOneDevice[] = "(a BatchNorm on its running pair, the hip_bnf_* family) takes vars of exactly its op's dims, not img shards, and hip_bnf_bck sums over the images of the WHOLE batch, which would need a cross-device reduction; frozen statistics on several devices are out of scope";
 inline constexpr char kWhyLossOneDevice[] = "(the full softmax loss, the hip_softmax_loss_* / hip_loss_norm family) counts the pels that are not ignored and sums loss_per_pel over the WHOLE batch, which would need a cross-device reduction, and takes vars of exactly its op's dims, not img shards; a loss with a LossSpec on several devices is out of scope";
-inline constexpr char const *why_one_device(func_family_t family) { return family == kFamLoss ? kWhyLossOneDevice : kWhyBnfOneDevice; }
+inline constexpr char kWhyConvGrpOneDevice[] = "(a grouped convolution, the hip_conv_grp / hip_bconv_in_grp / hip_bconv_filts_grp family) takes vars of exactly its op's dims, not img shards, and hip_bconv_filts_grp sums over the images of the WHOLE batch, which would need a cross-device reduction; grouped layers on several devices are out of scope";
+inline constexpr char const *why_one_device(func_family_t family) { return family == kFamLoss ? kWhyLossOneDevice : family == kFamConvGrp ? kWhyConvGrpOneDevice : kWhyBnfOneDevice; }
 inline constexpr native_func_t kNativeFuncs[] = {
   // sgemm, a:K:M b:K:N c:M:N (test/rtc/cublas_sgemm.cucl:1-4); Convolution in reference layout (test/rtc/cudnn_conv.cucl:1-7)
   {"hip_sgemm", kFamSgemm, 0, nullptr, {"sgemm"}, {{"a", kIn}, {"b", kIn}, {"c", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
@@ -142,6 +144,12 @@ inline constexpr native_func_t kNativeFuncs[] = {
   {"hip_bnf_prep", kFamBnf, 6, nullptr, {"BnfPrep"}, {{"run_mean", kIn}, {"run_var", kIn}, {"mean", kOut}, {"inv_std", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   {"hip_bnf_bck", kFamBnf, 7, nullptr, {"BnfBck"}, {{"in", kIn}, {"mean", kIn}, {"inv_std", kIn}, {"scale", kIn}, {"out_grad_loss", kIn}, {"in_grad_loss", kOut}, {"scale_grad_loss", kOut}, {"bias_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   {"hip_bnf_bck_in", kFamBnf, 8, nullptr, {"BnfBckIn"}, {{"inv_std", kIn}, {"scale", kIn}, {"out_grad_loss", kIn}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  // a Convolution / BckConv with group > 1 (this backend's own: the reference has no grouped convolution; kernels/conv_grp_f32.hip): for every group the ungrouped
+  // function on the op sliced to that group.  The arg lists of hip_conv, hip_bconv_in and hip_bconv_filts without their optional args; no flag; one device only
+  // (why_one_device).  A family of its own: the rows of kFamConv and kFamBconv are pinned.  In front of the loss rows, which stay in front of the table's last four
+  {"hip_conv_grp", kFamConvGrp, kConvGrpFwd, nullptr, {"Convolution"}, {BODAHIP_CONV_ARGS}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  {"hip_bconv_in_grp", kFamConvGrp, kConvGrpBckIn, nullptr, {"BckConv"}, {{"filts", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  {"hip_bconv_filts_grp", kFamConvGrp, kConvGrpBckFilts, nullptr, {"BckConv"}, {{"in", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"filts_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   // the full SoftmaxWithLoss (this backend's own; kernels/loss_f32.hip): what a head with a LossSpec lowers to -- loss_weight, ignore_label, planes, the four
   // normalisers.  hip_softmax_loss_bck reads s = weight / Z from loss_state on the device.  One device only (why_one_device).  In front of the data and eval rows,
   // which stay the table's last four
@@ -161,10 +169,10 @@ inline constexpr native_func_t kNativeFuncs[] = {
 
 inline native_func_t const *find_native_func(string const &fn) { for (auto const &f : kNativeFuncs) if (fn == f.name) return &f; return nullptr; }
 inline native_func_t const *find_native_func(func_family_t family, int member) { for (auto const &f : kNativeFuncs) if (f.family == family && f.member == member) return &f; return nullptr; }
-// the functions of a bare op of type t, in call order (empty: no such op).  kBconvFiltsBiases is nobody's default call
+// the functions of a bare op of type t, in call order (empty: no such op).  kBconvFiltsBiases is nobody's default call, and the grouped functions belong to annotated ops
 inline std::vector<native_func_t const *> native_funcs_of_type(string const &t, unsigned backend = kBeHip) {
   std::vector<native_func_t const *> r;
-  for (auto const &f : kNativeFuncs) if (f.of_type(t) && (f.backends & backend) && !(f.family == kFamBconv && f.member == kBconvFiltsBiases)) r.push_back(&f);
+  for (auto const &f : kNativeFuncs) if (f.of_type(t) && (f.backends & backend) && !(f.family == kFamBconv && f.member == kBconvFiltsBiases) && f.family != kFamConvGrp) r.push_back(&f);
   std::stable_sort(r.begin(), r.end(), [](native_func_t const *a, native_func_t const *b) { return a->member < b->member; });
   return r;
 }
@@ -195,6 +203,39 @@ inline bool op_bf16_operands(op_base_t const &op) {
   if (it->second != "bf16") rt_err(string(f->name) + ": hip_operands must be f32 | bf16, got '" + it->second + "'");
   if (f->member != kBconvIn && f->member != kBconvFiltsBiases) unsup_err(string(f->name) + ": " + kWhyNoBf16Pair);
   return true;
+}
+
+// the grouped family (kFamConvGrp): what both backends read from the function's op, and every refusal that needs the op alone.  The op is a Convolution (member
+// kConvGrpFwd: in, filts, biases, out, conv_has_relu) or a BckConv (in, filts, out_grad_loss in the place of out) that carries group = g > 1: C and OC multiples of g,
+// filts = out_chan=OC : in_chan=C/g : y : x.  Group j reads channels [j*CG, (j+1)*CG) of in and filter rows / writes out_chans [j*OCG, (j+1)*OCG)
+struct conv_grp_geom_t { int B, C, H, W, OC, KH, KW, SY, SX, PY, PX, OH, OW, G, CG, OCG; bool relu; };
+inline uint32_t op_group(op_base_t const &op) { return op.has("group") ? op.get_u32("group") : 1u; }
+inline conv_grp_geom_t conv_grp_geom_of_op(op_base_t const &op, int member) {
+  native_func_t const *row = find_native_func(kFamConvGrp, member);
+  string const fn = row ? row->name : "hip_conv_grp";
+  if (row && !row->of_type(op.get_type())) rt_err(fn + ": a function of op type " + row->types[0] + ", not " + op.get_type());
+  bool const fwd = member == kConvGrpFwd;
+  dims_t const &f = op.get_dims("filts"), &in = op.get_dims("in"), &out = op.get_dims(fwd ? "out" : "out_grad_loss"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
+  if (f.sz() != 4 || in.sz() != 4 || out.sz() != 4 || st.sz() != 2 || pad.sz() != 2 || f.tn != "float" || in.tn != "float" || out.tn != "float")
+    rt_err(fn + ": float filts out_chan:in_chan:y:x, in / out img:chan:y:x, stride / in_pad y:x");
+  conv_grp_geom_t g;
+  g.B = (int)in.dsz("img"); g.C = (int)in.dsz("chan"); g.H = (int)in.dsz("y"); g.W = (int)in.dsz("x"); g.OC = (int)f.dsz("out_chan"); g.KH = (int)f.dsz("y"); g.KW = (int)f.dsz("x");
+  g.SY = (int)st.dsz("y"); g.SX = (int)st.dsz("x"); g.PY = (int)pad.dsz("y"); g.PX = (int)pad.dsz("x"); g.OH = (int)out.dsz("y"); g.OW = (int)out.dsz("x");
+  g.relu = fwd && op.get_u32("conv_has_relu") != 0;
+  uint32_t const grp = op_group(op);
+  if (grp < 2) rt_err(fn + ": the op carries no group > 1: an ungrouped convolution belongs to hip_conv / hip_bconv_in / hip_bconv_filts");
+  if (g.C % grp || g.OC % grp || f.dsz("in_chan") * grp != (uint32_t)g.C)
+    rt_err(fn + ": group=" + std::to_string(grp) + " needs in.chan=" + std::to_string(g.C) + " and filts.out_chan=" + std::to_string(g.OC) + " to be multiples of it and filts.in_chan=" + std::to_string(f.dsz("in_chan")) + " to be in.chan/group");
+  g.G = (int)grp; g.CG = g.C / g.G; g.OCG = g.OC / g.G;
+  if (g.B < 1 || g.H < 1 || g.W < 1 || g.KH < 1 || g.KW < 1 || g.SY < 1 || g.SX < 1 || g.PY < 0 || g.PX < 0 || g.OH < 1 || g.OW < 1 || g.SY > 16 || g.SX > 16 || g.KH > 64 || g.KW > 64) unsup_err(fn + ": unsupported geometry");
+  if (out.dsz("img") != (uint32_t)g.B || out.dsz("chan") != (uint32_t)g.OC || (g.H + 2 * g.PY - g.KH) / g.SY + 1 != g.OH || (g.W + 2 * g.PX - g.KW) / g.SX + 1 != g.OW)
+    rt_err(fn + ": " + (fwd ? "out" : "out_grad_loss") + " dims do not match in / filts / stride / in_pad");
+  if (fwd && op.get_dims("biases").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases must hold out_chan values");
+  if (member == kConvGrpBckIn && !(op.get_dims("in_grad_loss") == in)) rt_err(fn + ": in_grad_loss must have the dims of in");
+  if (member == kConvGrpBckFilts && !(op.get_dims("filts_grad_loss") == f)) rt_err(fn + ": filts_grad_loss must have the dims of filts");
+  uint64_t const in_b = 4ull * g.B * g.C * g.H * g.W, out_b = 4ull * g.B * g.OC * g.OH * g.OW, f_b = 4ull * g.OC * g.CG * g.KH * g.KW;
+  if (in_b >= 0x7ffffff0ull || out_b >= 0x7ffffff0ull || f_b >= 0x7ffffff0ull) unsup_err(fn + ": tensors of 2 GiB or more (32-bit offsets)");
+  return g;
 }
 
 // the (arg, kind) list of an annotated function op: the fixed args with the variable part and the flag's arg applied (what boda_amd/cnn_op.py calls pipe_func_args)

@@ -95,6 +95,10 @@ plan_t plan_bconv_in_bf16(conv_geom_t const &g, int num_cus, string const &tile,
 plan_t plan_bconv_fb_bf16(conv_geom_t const &g, int num_cus, string const &tile);                     // hip_operands=bf16: kernels/bconv_fb_bf16.hip; its second launch is plan_bconv_slab_sum's
 plan_t plan_bconv_slab_sum();                                                        // its second launch: the slabs added in slice order (kernels/bconv_fb_f32.hip -DSLAB_SUM)
 plan_t plan_bconv_biases();                                                          // BckConv bias gradient (kernels/bconv_filts_f32.hip -DBIAS_ONLY)
+plan_t plan_conv_grp(conv_grp_geom_t const &g, int member, int num_cus, string const &tile);   // the grouped family (kernels/conv_grp_f32.hip); member: kConvGrpFwd | kConvGrpBckIn | kConvGrpBckFilts
+plan_t plan_conv_grp_slab_sum(plan_t const &main);   // the second launch of a sliced direct filter gradient
+bool conv_grp_has_slab_sum(plan_t const &p);
+long conv_grp_threads(conv_grp_geom_t const &g, int member, tile_cfg_t const &c, uint32_t *grid, uint32_t *block);   // -> the kernel's p.n; *grid workgroups of *block threads
 long bconv_in_tiles(conv_geom_t const &g, int BJ);                                   // pel tiles over all SY x SX phases (the kernel's walk)
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log);
 void ensure_ws(native_kernels_t::impl_t *impl, native_host_t *host, size_t need);

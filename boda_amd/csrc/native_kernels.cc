@@ -78,6 +78,13 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
   case kFamLoss:   // likewise
     (void)get_kernel(impl, host, plan_loss_op(loss_op_of_op(fi.op)).p);
     break;
+  case kFamConvGrp:   // the op must be whole (group, geometry), and the tile one the family has; the code object is built NOW: a first run inside a graph capture finds it
+    { conv_grp_geom_t const cg = conv_grp_geom_of_op(fi.op, f->member);
+      auto const ht = fi.op.str_vals.find("hip_tile");
+      plan_t const gp = plan_conv_grp(cg, f->member, host->nh_num_cus(), (ht != fi.op.str_vals.end() && !ht->second.empty()) ? ht->second : tune_of(impl, "conv_tile"));
+      (void)get_kernel(impl, host, gp);
+      if (conv_grp_has_slab_sum(gp)) (void)get_kernel(impl, host, plan_conv_grp_slab_sum(gp)); }
+    break;
   case kFamBconv:   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     (void)op_bf16_operands(fi.op);   // (str_val hip_operands: refused at compile where the function has no bf16-operand form)
@@ -786,6 +793,42 @@ void native_kernels_t::bconv_filts(float const *in, float const *out_grad, float
   last_launch.kernel = p.kname; last_launch.cfg = p.cfg; last_launch.grid = grid; last_launch.block = p.cfg.threads();
   last_launch.flops = 2.0 * g.OC * (double)NJ * K;
   last_launch.algo_bytes = (double)a.a_bytes + a.b_bytes + a.d_bytes;
+}
+void native_kernels_t::conv_grp(int member, conv_grp_geom_t const &g, float const *a, float const *b, float const *bias, float *d) {
+  plan_t const p = plan_conv_grp(g, member, host->nh_num_cus(), tune_of(impl, "conv_tile"));
+  kernel_t &k = get_kernel(impl, host, p);
+  conv_grp_args_t ga; memset(&ga, 0, sizeof(ga));
+  ga.a = a; ga.b = b; ga.bias = bias; ga.d = d;
+  ga.B = g.B; ga.C = g.C; ga.H = g.H; ga.W = g.W; ga.OC = g.OC; ga.OH = g.OH; ga.OW = g.OW;
+  unsigned const f_b = (unsigned)(4ull * g.OC * g.CG * g.KH * g.KW), in_b = (unsigned)(4ull * g.B * g.C * g.H * g.W), out_b = (unsigned)(4ull * g.B * g.OC * g.OH * g.OW);
+  ga.a_bytes = member == kConvGrpBckFilts ? out_b : f_b; ga.b_bytes = member == kConvGrpBckIn ? out_b : in_b; ga.d_bytes = member == kConvGrpFwd ? out_b : member == kConvGrpBckIn ? in_b : f_b;
+  long const K = (long)g.B * g.OH * g.OW, nkt = (K + p.cfg.BK - 1) / p.cfg.BK;
+  ga.kt_per = (int)((nkt + p.cfg.SPLITK - 1) / p.cfg.SPLITK);
+  uint32_t grid = 0, block = 256;
+  ga.n = conv_grp_threads(g, member, p.cfg, &grid, &block);
+  kernel_t *ks = nullptr;
+  if (conv_grp_has_slab_sum(p)) {   // the call's slab workspace, as hip_bconv_filts_biases keeps one: [slice][filts_grad_loss's elements], nothing to zero
+    ks = &get_kernel(impl, host, plan_conv_grp_slab_sum(p));
+    size_t const total = (size_t)p.cfg.SPLITK * f_b;
+    if (total >= (size_t(1) << 32)) unsup_err("hip_bconv_filts_grp: K-slice workspace too large");
+    string const key = "ksl:conv_grp:" + std::to_string((uintptr_t)a) + ":" + std::to_string((uintptr_t)b) + ":" + std::to_string((uintptr_t)d) + ":" + std::to_string(total);
+    auto it = impl->ktabs.find(key);
+    if (it == impl->ktabs.end()) {
+      if (host->nh_capturing()) rt_err("graph capture: the K-slice workspace of this call is not allocated yet -- run the call list once before capturing it");
+      void *dev = nullptr;
+      call_ws_make_room(impl, host, total);
+      hip_err_chk(hipMalloc(&dev, total), "hipMalloc(K-slice workspace)"); impl->call_ws_bytes += total;
+      it = impl->ktabs.emplace(key, dev).first;
+    }
+    ga.ws = (float *)it->second; ga.ksl = (unsigned)p.cfg.SPLITK;
+  }
+  void *params[] = {&ga};
+  if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, block, params), "hipModuleLaunchKernel(conv_grp)");
+  if (ks) hip_err_chk(host->nh_launch(ks->func, (uint32_t)((f_b / 4 + 255) / 256), 1, 256, params), "hipModuleLaunchKernel(conv_grp_slab_sum)");
+  last_launch.kernel = p.kname; last_launch.cfg = p.cfg; last_launch.grid = grid; last_launch.block = block;
+  int const TY = (g.KH + g.SY - 1) / g.SY, TX = (g.KW + g.SX - 1) / g.SX;
+  last_launch.flops = member == kConvGrpBckIn ? 2.0 * g.B * g.H * g.W * g.C * ((double)g.OCG * TY * TX) : 2.0 * K * g.OC * ((double)g.CG * g.KH * g.KW);
+  last_launch.algo_bytes = (double)f_b + in_b + out_b + (member == kConvGrpFwd ? 4.0 * g.OC : 0.0);
 }
 void native_kernels_t::bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g) {
   kernel_t &k = get_kernel(impl, host, plan_bconv_biases());

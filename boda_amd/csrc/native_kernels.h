@@ -150,6 +150,9 @@ struct native_kernels_t {
   void bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g);
   // both at once, k-major staging, up to 1024 K slices in slabs summed by a second launch (kernels/bconv_fb_f32.hip); opt-in: ConvPipeBck(fuse_filts_biases=True)
   void bconv_filts_biases(float const *in, float const *out_grad, float *filts_grad, float *biases_grad, conv_geom_t const &g, bool bf16 = false);   // bf16: kernels/bconv_fb_bf16.hip, the same slabs and slab sum
+  // the grouped family (kernels/conv_grp_f32.hip) on raw device pointers.  member kConvGrpFwd: a = filts, b = in, bias = biases, d = out; kConvGrpBckIn: a = filts,
+  // b = out_grad_loss, d = in_grad_loss; kConvGrpBckFilts: a = out_grad_loss, b = in, d = filts_grad_loss.  One launch, no workspace
+  void conv_grp(int member, conv_grp_geom_t const &g, float const *a, float const *b, float const *bias, float *d);
   // the non-conv ops of the gradient pipe: ins / outs in the function's arg order (up to eight / two raw device pointers)
   // seed_word (dropout with g.seedvar): the device word added to g.seed
   void bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs, uint32_t const *seed_word = nullptr);

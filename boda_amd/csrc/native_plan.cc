@@ -1224,6 +1224,120 @@ plan_t plan_bconv_filts(conv_geom_t const &g, int num_cus, string const &tile) {
 }
 plan_t plan_bconv_biases() { plan_t p; p.src = kSrc_bconv_filts_f32; p.kname = "bodahip_bconv_biases"; p.defs = {"-DBIAS_ONLY=1"}; return p; }
 
+// ---- the grouped family (kernels/conv_grp_f32.hip): two forms of each function.  The MATRIX form is per group the ungrouped kernels' implicit GEMM on MFMA blocks
+// of 32 x 32 x 2 or -- a group's row extent below 32 -- 16 x 16 x 4; the DIRECT form is one explicit fmaf chain per output, for small per-group reductions.  The planner
+// chooses from the op alone: the matrix form where a group's row extent (OCG; the data gradient: CG) is at least 8 AND its reduction resp. column extent (forward
+// CG x KH x KW, data gradient OCG x ceil(KH/SY) x ceil(KW/SX), filter gradient CG x KH x KW) at least 16, the direct form below that (depthwise layers, channel
+// multipliers, groups of four channels).  Tile strings as for hip_bconv_filts, seven fields "BIxBJxBKxWIxWJxMINWxKSL", force the form:
+//   BI = 1: direct.  BJ = the adjacent outputs of a thread (forward: 1 | 2 | 4; data gradient: 1, or 4 at stride 1 in x), WI x WJ = 4 waves, BK / KSL the filter gradient's K step and slice count (1..1024; kernels of at most 49 taps;
+//           with slices the slabs go to the call's workspace and a second launch adds them in slice order)
+//   BI > 1: matrix.  Forward / data gradient: WI x WJ waves, each a (BI / WI) x (BJ / WJ) tile; filter gradient: WI = WJ = 1, the tile BI x BJ is one wave's and the
+//           workgroup's KSL (1..16) waves are its K slices.  The block is 16 x 16 x 4 where a wave's rows (BI / WI) are 16, else 32 x 32 x 2; BK a multiple of its k step
+// The launch reports the form in the kernel's name (_mfma | _direct), the block in the configuration string (_m16) and BK / KSL as BIxBJxBK_wWIxWJ[_sKSL]
+static bool conv_grp_matrix_default(conv_grp_geom_t const &g, int member) {
+  int const TY = (g.KH + g.SY - 1) / g.SY, TX = (g.KW + g.SX - 1) / g.SX;
+  int const rows = member == kConvGrpBckIn ? g.CG : g.OCG, other = member == kConvGrpBckIn ? g.OCG * TY * TX : g.CG * g.KH * g.KW;
+  return rows >= 8 && other >= 16;
+}
+plan_t plan_conv_grp(conv_grp_geom_t const &g, int member, int num_cus, string const &tile) {
+  native_func_t const *row = find_native_func(kFamConvGrp, member);
+  if (!row) rt_err("plan_conv_grp: no such member");
+  string const fn = row->name;
+  bool const filts = member == kConvGrpBckFilts;
+  plan_t p; p.src = kSrc_conv_grp_f32;
+  tile_cfg_t &c = p.cfg;
+  c = tile_cfg_t(); c.BI = 1; c.BJ = 1; c.BK = 1; c.WI = 2; c.WJ = 2; c.MINW = 1; c.SPLITK = 1;
+  long const K = (long)g.B * g.OH * g.OW;
+  bool matrix = conv_grp_matrix_default(g, member) || (filts && g.KH * g.KW > 49);   // (the direct filter gradient holds a kernel's taps in registers: at most 49)
+  int const rows = member == kConvGrpBckIn ? g.CG : g.OCG, ncol = g.CG * g.KH * g.KW;
+  bool const own_tile = std::count(tile.begin(), tile.end(), 'x') == 6;   // (any other tile -- a backend-wide or pipe-wide one written for hip_conv -- is not this family's: the planner decides)
+  if (own_tile) {
+    tile_cfg_t t;
+    if (!parse_tile(tile, t)) unsup_err(fn + ": bad tile '" + tile + "' (seven fields BIxBJxBKxWIxWJxMINWxKSL)");
+    matrix = t.BI > 1;
+    if (!matrix) {
+      if (filts && (g.KH * g.KW > 49 || t.SPLITK < 1 || t.SPLITK > 1024))
+        unsup_err(fn + ": tile " + t.str() + ": the direct filter gradient takes kernels of at most 49 taps and 1..1024 K slices");
+      if (t.BI != 1 || t.WI * t.WJ != 4 || t.MINW != 1 || t.BK < 1 || t.BK > 4096 || t.SPLITK < 1 || (!filts && (t.BK != 1 || t.SPLITK != 1)) ||
+          (member == kConvGrpFwd ? (t.BJ != 1 && t.BJ != 2 && t.BJ != 4) : member == kConvGrpBckIn ? (t.BJ != 1 && !(t.BJ == 4 && g.SX == 1)) : t.BJ != 1)) unsup_err(fn + ": unsupported tile configuration " + t.str() + " (direct form)");
+      c.BJ = t.BJ; c.BK = t.BK; c.WI = t.WI; c.WJ = t.WJ; c.SPLITK = t.SPLITK;
+    } else {
+      bool ok = t.WI >= 1 && t.WJ >= 1 && t.BI % t.WI == 0 && t.BJ >= 1 && t.BJ % t.WJ == 0 && t.MINW == 1 && t.WI * t.WJ <= 16;
+      int const wti = ok ? t.BI / t.WI : 0, wtj = ok ? t.BJ / t.WJ : 0, mt = wti == 16 ? 16 : 32;
+      ok = ok && wti % mt == 0 && wtj % mt == 0 && (wti / mt) * (wtj / mt) * (mt == 32 ? 16 : 4) <= 128 && t.BK >= 1 && t.BK <= 4096 && t.BK % (mt == 32 ? 2 : 4) == 0;
+      ok = ok && (filts ? (t.WI == 1 && t.WJ == 1 && t.SPLITK >= 1 && t.SPLITK <= 16 && (long)t.SPLITK * t.BI * t.BJ * 4 <= 65536) : t.SPLITK == 1);
+      if (!ok) unsup_err(fn + ": unsupported tile configuration " + t.str() + " (matrix form)");
+      c = t; c.MT = mt; c.PF = 1; c.SW = 0; c.KHO = 0;
+    }
+  } else if (matrix) {   // 32-row blocks where the group has them, two where it has 64 rows; four waves side by side along the columns (the filter gradient: one wave's tile, its waves are slices)
+    c.MT = rows < 32 ? 16 : 32; c.BI = (c.MT == 32 && rows >= 64) ? 64 : c.MT; c.WI = 1; c.BK = 32;
+    if (!filts) { c.WJ = 4; c.BJ = 4 * 2 * c.MT; }
+    else {
+      c.WJ = 1; c.BJ = (ncol > c.MT ? 2 : 1) * c.MT;
+      long const tiles = (long)g.G * ((rows + c.BI - 1) / c.BI) * ((ncol + c.BJ - 1) / c.BJ), nkt = (K + c.BK - 1) / c.BK;
+      long const want = std::min<long>(std::max<long>(1, (8L * num_cus) / tiles), std::max<long>(1, nkt / 8));   // about eight waves a CU, every slice at least 8 K steps long
+      c.SPLITK = (int)std::min<long>(want, std::min<long>(16, 65536 / ((long)c.BI * c.BJ * 4)));
+    }
+  } else if (member == kConvGrpFwd) c.BJ = g.OW >= 3 ? 4 : g.OW;
+  // (the direct data gradient keeps one output a thread: four adjacent x, a forced tile's BJ = 4, measured level on large maps and slower on small ones: DESIGN.md section 3.24)
+  else if (filts) {   // a thread is one (out_chan, in_chan) pair x one slice: slices until pairs x slices give the CUs about 2048 threads each, every slice at least 2 K steps long; a power of two
+    c.BK = 32;
+    long const pairs = (long)g.OC * g.CG, nkt = (K + c.BK - 1) / c.BK;
+    long want = std::min<long>(std::max<long>(1, (2048L * num_cus) / pairs), std::max<long>(1, nkt / 2));
+    int ksl = 1; while (ksl * 2 <= want && ksl < 1024) ksl *= 2;
+    c.SPLITK = ksl;
+  }
+  string const base = member == kConvGrpFwd ? "bodahip_conv_grp" : member == kConvGrpBckIn ? "bodahip_bconv_in_grp" : "bodahip_bconv_filts_grp";
+  p.kname = base + (matrix ? "_mfma" : "_direct");
+  p.defs = {"-DFUNC=" + std::to_string(member), string("-DFORM=") + (matrix ? "1" : "0"), "-DCG=" + std::to_string(g.CG), "-DOCG=" + std::to_string(g.OCG), "-DKH=" + std::to_string(g.KH),
+            "-DKW=" + std::to_string(g.KW), "-DSY=" + std::to_string(g.SY), "-DSX=" + std::to_string(g.SX), "-DPY=" + std::to_string(g.PY), "-DPX=" + std::to_string(g.PX)};
+  if (member == kConvGrpFwd) p.defs.push_back(string("-DRELU=") + (g.relu ? "1" : "0"));
+  if (matrix) for (auto const &d : {std::make_pair("MT", c.MT), std::make_pair("BI", c.BI), std::make_pair("BJ", c.BJ), std::make_pair("BK", c.BK), std::make_pair("WI", c.WI),
+                                     std::make_pair("WJ", c.WJ), std::make_pair("KSL", c.SPLITK)}) p.defs.push_back(string("-D") + d.first + "=" + std::to_string(d.second));
+  else {
+    if (!filts) p.defs.push_back("-DVX=" + std::to_string(c.BJ));
+    if (filts) { p.defs.push_back("-DBK=" + std::to_string(c.BK)); p.defs.push_back("-DKSL=" + std::to_string(c.SPLITK)); p.defs.push_back("-DSLAB_SUM=0"); }
+  }
+  return p;
+}
+// the second launch of a sliced direct filter gradient: the slabs of the call's workspace added in slice order (the same specialisation but -DSLAB_SUM=1)
+plan_t plan_conv_grp_slab_sum(plan_t const &main) {
+  plan_t p = main; p.kname = "bodahip_bconv_filts_grp_slab_sum"; p.defs.back() = "-DSLAB_SUM=1";
+  return p;
+}
+bool conv_grp_has_slab_sum(plan_t const &p) { return p.kname == "bodahip_bconv_filts_grp_direct" && p.cfg.SPLITK > 1; }
+// -> what the kernel reads as p.n (direct: threads resp. outputs that have work; matrix data gradient: pel tiles over all phases); *grid workgroups of *block threads
+long conv_grp_threads(conv_grp_geom_t const &g, int member, tile_cfg_t const &c, uint32_t *grid, uint32_t *block) {
+  long n = 0, wgs;
+  if (c.BI > 1) {   // the matrix form: (group, row tile, column tile); the kernels walk blockIdx the same way
+    int const rows = member == kConvGrpBckIn ? g.CG : g.OCG;
+    long const ti = (rows + c.BI - 1) / c.BI;
+    long tj;
+    if (member == kConvGrpFwd) tj = ((long)g.B * g.OH * g.OW + c.BJ - 1) / c.BJ;
+    else if (member == kConvGrpBckFilts) tj = ((long)g.CG * g.KH * g.KW + c.BJ - 1) / c.BJ;
+    else {
+      tj = 0;
+      for (int ry = 0; ry < g.SY; ++ry)
+        for (int rx = 0; rx < g.SX; ++rx) {
+          int const y0 = ((ry - g.PY) % g.SY + g.SY) % g.SY, x0 = ((rx - g.PX) % g.SX + g.SX) % g.SX;
+          long const ny = y0 < g.H ? (g.H - y0 + g.SY - 1) / g.SY : 0, nx = x0 < g.W ? (g.W - x0 + g.SX - 1) / g.SX : 0;
+          tj += ((long)g.B * ny * nx + c.BJ - 1) / c.BJ;
+        }
+      n = tj;
+    }
+    wgs = (long)g.G * ti * tj;
+    *block = member == kConvGrpBckFilts ? 64u * (uint32_t)c.SPLITK : 64u * (uint32_t)(c.WI * c.WJ);
+  } else {
+    *block = 256;
+    if (member == kConvGrpFwd) { n = (long)g.B * g.OC * g.OH * ((g.OW + c.BJ - 1) / c.BJ); wgs = (n + 255) / 256; }
+    else if (member == kConvGrpBckIn) { n = (long)g.B * g.C * g.H * ((g.W + c.BJ - 1) / c.BJ); wgs = (n + 255) / 256; }
+    else { n = (long)g.OC * g.CG; wgs = (n * c.SPLITK + 255) / 256; }   // (out_chan, in_chan) pairs; a thread per pair and slice
+  }
+  if (wgs >= (1L << 31)) unsup_err("the grouped family: more than 2^31 workgroups");
+  *grid = (uint32_t)wgs;
+  return n;
+}
+
 // hip_bconv_filts_biases (kernels/bconv_fb_f32.hip): the same tile strings; both operands are staged k-major, so every thread owns one k offset (threads % BK == 0) and
 // whole rows AND columns ((threads / BK) divides BI and BJ); the LDS images are transposed with pitch BK + 1; K slices go to slabs summed by a second launch: 1..1024
 static void check_bconv_fb_cfg(tile_cfg_t const &c) {

@@ -38,9 +38,14 @@ static bool apply_f32_pool(op_base_t const &op, conv_geom_t &g, char const *what
 // AOT: compile (into the on-disk code-object cache) the specialisation that run() would pick for `op`.  No device needed.
 // With arch == "" nothing is compiled and *plan_out receives "<kernel> <tile> <-D options>": the planner's decision (host-logic tests).
 // BckConv: the forward convolution's geometry from the op's in / filts / out_grad_loss / stride / in_pad (OP_INFO["BckConv"], boda_amd/op.py)
-static conv_geom_t bck_geom_of_op(op_base_t const &op) {
+static void refuse_group(op_base_t const &op, string const &what) {   // every convolution function but the grouped family's three takes ungrouped ops only
+  if (op_group(op) > 1) unsup_err(what + ": the op carries group=" + std::to_string(op_group(op)) + ": a grouped convolution runs as hip_conv_grp / hip_bconv_in_grp / hip_bconv_filts_grp (fp32, reference layouts) only");
+}
+// (any_group: the bias gradient, which knows no groups -- a grouped BckConv's hip_bconv_biases is the ungrouped function as it is)
+static conv_geom_t bck_geom_of_op(op_base_t const &op, bool any_group = false) {
+  if (!any_group) refuse_group(op, op.has_func_name() ? op.get_func_name() : op.get_type());
   conv_geom_t g = geom_from_dims(op.get_dims("filts"), op.get_dims("in"), op.get_dims("out_grad_loss"), op.get_dims("stride"), op.get_dims("in_pad"), false);
-  if (op.get_dims("filts").dsz("in_chan") != (uint32_t)g.C || op.get_dims("out_grad_loss").dsz("chan") != (uint32_t)g.OC || op.get_dims("out_grad_loss").dsz("img") != (uint32_t)g.B)
+  if (op.get_dims("filts").dsz("in_chan") * op_group(op) != (uint32_t)g.C || op.get_dims("out_grad_loss").dsz("chan") != (uint32_t)g.OC || op.get_dims("out_grad_loss").dsz("img") != (uint32_t)g.B)
     rt_err("BckConv: in / filts / out_grad_loss dims are inconsistent");
   return g;
 }
@@ -151,6 +156,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     if (a.tn == "half") { s2d.clear(); p = plan_sgemm(a.dsz("M"), b.dsz("N"), a.dsz("K"), num_cus, tile, false, 1, false); p.kname = "bodahip_sgemm_f16s"; p.defs.push_back("-DHALF=1"); }
   }
   else if (fam <= kFamFiltsKmajor) {   // op type Convolution
+    refuse_group(op, f ? string(f->name) : t);
     bool const relu = op.has("conv_has_relu") ? (op.get_u32("conv_has_relu") != 0) : true;
     bool const multi = fam == kFamNhwcMulti && member == 0;
     if (fam == kFamNhwcMulti && member == 1) {   // the wrapper kernel of the members' specialisations (and the kernels of members that stay alone)
@@ -231,7 +237,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
       } else { char const *k1e = getenv("BODAHIP_K1_STREAM"); p = plan_conv(g, num_cus, tile, bf16, k1e ? string(k1e) : string(), true, exact); }   // (the env var a backend instance reads its k1_stream tune from)
     }
   } else if (fam == kFamBconv) {   // the three gradient functions (or, for the bare op, all three: the calls of src/rtc_fwd.cc:398-400)
-    conv_geom_t const g = bck_geom_of_op(op);
+    conv_geom_t const g = bck_geom_of_op(op, member == kBconvBiases);
     string const fn = op.has_func_name() ? op.get_func_name() : string();
     if (!fn.empty() && !f) rt_err("prebuild: BckConv function '" + fn + "' has no native kernel");
     std::vector<plan_t> ps;
@@ -256,6 +262,16 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
       if (!arch.empty()) bytes += compile_plan(sp.p, arch, &log).size();
     }
     if (plan_out) *plan_out = desc;
+    return bytes;
+  } else if (fam == kFamConvGrp) {   // (kernels/conv_grp_f32.hip: one launch per call, specialised by the group's geometry)
+    conv_grp_geom_t const cg = conv_grp_geom_of_op(op, member);
+    plan_t const q = plan_conv_grp(cg, member, num_cus, tile);
+    uint32_t grid = 0, block = 0; (void)conv_grp_threads(cg, member, q.cfg, &grid, &block);
+    if (plan_out) { *plan_out = q.kname + " " + q.cfg.str() + " grid=" + std::to_string(grid); for (auto const &d : q.defs) *plan_out += " " + d; }
+    if (conv_grp_has_slab_sum(q) && plan_out) *plan_out += " | bodahip_bconv_filts_grp_slab_sum";
+    if (arch.empty()) return 0;
+    size_t bytes = compile_plan(q, arch, &log).size();
+    if (conv_grp_has_slab_sum(q)) bytes += compile_plan(plan_conv_grp_slab_sum(q), arch, &log).size();
     return bytes;
   } else if (fam == kFamSgd) {   // (hip_sgd_update: one kernel, no specialisation by shape; the grid is the sum of the tensors' chunks)
     sgd_plan_t const sp = plan_sgd_update(sgd_op_of_op(op).elems);
@@ -620,6 +636,7 @@ struct native_kernels_t::call_t {
   }
   void run_conv() {
     bool const bf16 = row.member == kConvBf16;
+    refuse_group(fi.op, fn);
     string const fnm = var_of(am, "filts"), bnm = var_of(am, "biases"), inm = var_of(am, "in"), onm = var_of(am, "out");
     dims_t const f = host->nh_var_dims(fnm), bi = host->nh_var_dims(bnm), in = host->nh_var_dims(inm), out = host->nh_var_dims(onm);
     need_float(f, "filts"); need_float(bi, "biases"); need_float(in, "in"); need_float(out, "out");
@@ -660,7 +677,7 @@ struct native_kernels_t::call_t {
          (row.member == kConvWinograd) ? "winograd_all" : nullptr, km); // hip_conv_winograd: the F(2x2,3x3) path for this function (3x3 / stride 1; others: direct)
   }
   void run_bconv() {
-    conv_geom_t g = bck_geom_of_op(fi.op);
+    conv_geom_t g = bck_geom_of_op(fi.op, row.member == kBconvBiases);
     if (row.member != kBconvBiases) {
       auto si = am.find("stride"), pi = am.find("in_pad");
       if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
@@ -697,6 +714,23 @@ struct native_kernels_t::call_t {
       if (fi.op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
       nk.bconv_biases((float const *)host->nh_var_ptr(ogl), (float *)host->nh_var_ptr(bgl), g);
     }
+  }
+  void run_conv_grp() {   // every var has exactly the dims the op gives its arg (one device: no img shards), and the call's vars are different ones
+    conv_grp_geom_t const g = conv_grp_geom_of_op(fi.op, row.member);
+    auto si = am.find("stride"), pi = am.find("in_pad");
+    if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
+    if (!(si->second.get_dims(host->nh_rtc()) == fi.op.get_dims("stride")) || !(pi->second.get_dims(host->nh_rtc()) == fi.op.get_dims("in_pad"))) rt_err(fn + ": stride / in_pad args disagree with the op");
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    auto var_ptr = [&](char const *an) -> float * {
+      string const vn = var_of_op_dims(an);
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      return (float *)host->nh_var_ptr(vn);
+    };
+    tile_override_t const tov(impl, "conv_tile", fi.op);
+    if (row.member == kConvGrpFwd) { float *a = var_ptr("filts"), *bias = var_ptr("biases"), *b = var_ptr("in"); nk.conv_grp(row.member, g, a, b, bias, var_ptr("out")); }
+    else if (row.member == kConvGrpBckIn) { float *a = var_ptr("filts"), *b = var_ptr("out_grad_loss"); nk.conv_grp(row.member, g, a, b, nullptr, var_ptr("in_grad_loss")); }
+    else { float *b = var_ptr("in"), *a = var_ptr("out_grad_loss"); nk.conv_grp(row.member, g, a, b, nullptr, var_ptr("filts_grad_loss")); }
   }
   void run_sgd() {
     // every var must have exactly the dims the op gives its arg (params are no img shards), and the 3n + 1 vars must all be different: w_i and h_i are rewritten in place
@@ -941,6 +975,7 @@ void native_kernels_t::run(native_func_t const &f, rtc_func_info_t const &fi, ma
   case kFamEval: c.run_eval(); break;
   case kFamData: c.run_data(); break;
   case kFamLoss: c.run_loss(); break;
+  case kFamConvGrp: c.run_conv_grp(); break;
   }
 }
 

@@ -408,7 +408,14 @@ class Op:
             g.update(UH=g["H"], UW=g["W"], PKH=ks.dsz("y"), PKW=ks.dsz("x"), PSY=ps.dsz("y"), PSX=ps.dsz("x"))
             g["H"] = (g["UH"] - g["PKH"]) // g["PSY"] + 1; g["W"] = (g["UW"] - g["PKW"]) // g["PSX"] + 1
         f_in = f.dsz("in_grp") * f.dsz("in_chan8") if f.has("in_grp") else f.dsz("in_chan")   # (filts in the input-patch kernel's in_grp:y:x:out_chan:in_chan8 form, boda_amd/nhwc.py)
-        if f_in != g["C"]:
+        grp = self.get_u32("group") if self.has("group") else 1   # Caffe's `group`, the form of out_chans; absent or 1: the ungrouped op
+        if grp > 1:   # filts = out_chan=OC : in_chan=C/g : y : x; group j reads channels j*CG .. and writes out_chans j*OCG ..
+            if f.has("in_grp") or g["C"] % grp or g["OC"] % grp or f_in * grp != g["C"]:
+                raise RtErr(f"conv: group={grp} needs in.chan={g['C']} and filts.out_chan={g['OC']} to be multiples of it and filts.in_chan={f_in} to be in.chan/group")
+            g.update(G=grp, CG=g["C"] // grp, OCG=g["OC"] // grp)
+        elif grp < 1:
+            raise RtErr(f"conv: group={grp} with in.chan={g['C']}, filts.out_chan={g['OC']}: group must be at least 1")
+        elif f_in != g["C"]:
             raise RtErr("conv: filts.in_chan != in.chan (groups are not on this path)")
         if o.dsz("img") != g["B"] or o.dsz("chan") != g["OC"]:
             raise RtErr("conv: out dims inconsistent with in/filts")
@@ -808,9 +815,9 @@ class Op:
             return 0
         if self.get_type() == "BckConv":   # two GEMMs of the forward size: the data and the filter gradient
             g = self.bck_conv_geom()
-            return 4 * (g["B"] * g["OH"] * g["OW"]) * g["OC"] * (g["C"] * g["KH"] * g["KW"])
-        g = self.conv_geom()
-        return 2 * (g["B"] * g["OH"] * g["OW"]) * g["OC"] * (g["C"] * g["KH"] * g["KW"])
+            return 4 * (g["B"] * g["OH"] * g["OW"]) * g["OC"] * (g.get("CG", g["C"]) * g["KH"] * g["KW"])
+        g = self.conv_geom()   # (group > 1: every out_chan reduces over its group's CG = C/g channels only)
+        return 2 * (g["B"] * g["OH"] * g["OW"]) * g["OC"] * (g.get("CG", g["C"]) * g["KH"] * g["KW"])
 
     def algo_bytes(self) -> int:
         """4*(in+out+filts+biases) resp. 4*(a+b+c) (src/latex-util.H:119,133)."""

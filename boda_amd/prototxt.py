@@ -84,14 +84,16 @@ def conv_ops(text: str, batch: int, in_chw: Tuple[int, int, int] = (3, 224, 224)
             if t == "CONVOLUTION":
                 cp = _one(L, "convolution_param", {})
                 oc = int(_one(cp, "num_output")); k = int(_one(cp, "kernel_size", 1)); s = int(_one(cp, "stride", 1)); p = int(_one(cp, "pad", 0))
-                if int(_one(cp, "group", 1)) != 1:
-                    raise RtErr(f"prototxt: grouped convolution {name!r} is not on this path")
+                grp = int(_one(cp, "group", 1))
+                if grp < 1 or C % grp or oc % grp:
+                    raise RtErr(f"prototxt: convolution {name!r}: group={grp} must divide its {C} input channels and its num_output={oc}")
                 kh = kw = k
             else:
-                oc = int(_one(_one(L, "inner_product_param", {}), "num_output")); kh, kw, s, p = H, W, 1, 0
+                oc = int(_one(_one(L, "inner_product_param", {}), "num_output")); kh, kw, s, p, grp = H, W, 1, 0, 1
             oh = (H + 2 * p - kh) // s + 1; ow = (W + 2 * p - kw) // s + 1
             out.append((name, parse_op(
-                f"(str_vals=(type=Convolution),nda_vals=(biases=(dims=(out_chan={oc})),filts=(dims=(out_chan={oc},in_chan={C},y={kh},x={kw})),"
+                f"(str_vals=(type=Convolution),nda_vals=(biases=(dims=(out_chan={oc})),filts=(dims=(out_chan={oc},in_chan={C // grp},y={kh},x={kw})),"
+                + (f"group=(tn=uint32_t,v={grp})," if grp > 1 else "") +
                 f"in=(dims=(img={batch},chan={C},y={H},x={W})),in_pad=(tn=none,dims=(y={p},x={p})),kern_sz=(tn=none,dims=(y={kh},x={kw})),"
                 f"out=(dims=(img={batch},chan={oc},y={oh},x={ow})),out_chans=(tn=uint32_t,v={oc}),stride=(tn=none,dims=(y={s},x={s}))))")))
             shapes[tops[0]] = (oc, oh, ow)
@@ -130,7 +132,7 @@ def conv_bottoms(text: str) -> List[Tuple[str, str]]:
 def pipe_spec(text: str, in_chw: Tuple[int, int, int] = (3, 224, 224)) -> List[str]:
     """-> the TEST-phase forward ops of a net definition as compact one-line records (boda_amd.conv_pipe.pipe_from_spec reads
     them back): what the reference's reader keeps of each layer for conv_pipe_t (src/caffepb.cc:166-326).
-      input C H W | conv tag bot top oc kh kw sy sx py px | pool tag bot top kh kw sy sx py px avg global
+      input C H W | conv tag bot top oc kh kw sy sx py px [group] | pool tag bot top kh kw sy sx py px avg global
       lrn tag bot top local_size alpha beta k | relu tag bot top | drop tag bot top | concat tag top bot1,bot2,..."""
     root = parse(text)
     layers = root.get("layer", []) or root.get("layers", [])
@@ -148,10 +150,11 @@ def pipe_spec(text: str, in_chw: Tuple[int, int, int] = (3, 224, 224)) -> List[s
             continue
         elif t == "CONVOLUTION":
             cp = _one(L, "convolution_param", {})
-            if int(_one(cp, "group", 1)) != 1:
-                raise RtErr(f"prototxt: grouped convolution {name!r} is not on this path")
+            grp = int(_one(cp, "group", 1))
+            if grp < 1:
+                raise RtErr(f"prototxt: convolution {name!r}: group={grp}: at least 1")
             k, s_, p_ = int(_one(cp, "kernel_size", 1)), int(_one(cp, "stride", 1)), int(_one(cp, "pad", 0))
-            out.append(f"conv {name} {bots[0]} {tops[0]} {int(_one(cp, 'num_output'))} {k} {k} {s_} {s_} {p_} {p_}")
+            out.append(f"conv {name} {bots[0]} {tops[0]} {int(_one(cp, 'num_output'))} {k} {k} {s_} {s_} {p_} {p_}" + (f" {grp}" if grp > 1 else ""))
         elif t == "INNERPRODUCT":
             out.append(f"conv {name} {bots[0]} {tops[0]} {int(_one(_one(L, 'inner_product_param', {}), 'num_output'))} 0 0 1 1 0 0")  # kernel = whole input
         elif t == "POOLING":
