@@ -89,8 +89,10 @@ class BckPipe:
 
 
 def _fwd_grad_op(cp: ConvPipe, o: PipeOp) -> GradOp:
-    if o.type == "Convolution":
+    if o.type in ("Convolution", "Deconvolution"):
         return GradOp(o.tag, o.type, [o.bot, o.tag + "_filts", o.tag + "_biases"], [o.top], o)
+    if o.type == "Crop":   # (reads bots[0] alone: the second bottom gives only the size, and gets no gradient from a Crop)
+        return GradOp(o.tag, o.type, [o.bot], [o.top], o)
     if o.type in ("Concat", "Eltwise"):
         return GradOp(o.tag, o.type, list(o.bots), [o.top], o)
     if o.type == "BatchNorm":   # in place; the running statistics are params it reads AND rewrites
@@ -132,6 +134,10 @@ def _bck_of(cop: GradOp, grad_loss_onn) -> Optional[GradOp]:
         return GradOp(tag, "BckDropout", [cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, cop.bots[0])], cop.src)
     if t == "Convolution":   # { in, filts, biases, out_grad_loss } -> the three gradients
         return GradOp(tag, "BckConv", cop.bots + [cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, b) for b in cop.bots], cop.src)
+    if t == "Deconvolution":   # BckConv's shape: { in, filts, biases, out_grad_loss } -> the three gradients
+        return GradOp(tag, "BckDeconv", cop.bots + [cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, b) for b in cop.bots], cop.src)
+    if t == "Crop":            # { out_grad_loss } -> a_grad_loss: out_grad_loss inside the window, +0 outside it
+        return GradOp(tag, "BckCrop", [cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, cop.bots[0])], cop.src)
     if t == "Concat":
         return GradOp(tag, "Split", [cop.tops[0] + "_grad_loss"], [grad_loss_onn(cop, b) for b in cop.bots], cop.src)
     if t == "LRN":        # { in, out, out_grad_loss } -> in_grad_loss
@@ -156,7 +162,7 @@ def _append_reversed(cp: ConvPipe, nodes: Dict[str, Dims], fwd: List[GradOp], wa
         for i in b.bots:
             if i not in nodes:
                 raise RtErr(f"add_bck_ops: gradient op {b.tag} reads {i!r}, which no earlier op writes")
-        if b.type == "BckConv":
+        if b.type in ("BckConv", "BckDeconv"):
             for t, s in zip(b.tops, b.bots[:3]):
                 nodes[t] = nodes[s]
         elif b.type in ("Split", "BckEltwise"):
@@ -167,7 +173,7 @@ def _append_reversed(cp: ConvPipe, nodes: Dict[str, Dims], fwd: List[GradOp], wa
         elif b.type == "BckScale":
             nodes[b.tops[0]] = nodes[b.bots[0]]
             nodes[b.tops[1]] = cp.params[b.src.tag + "_scale"]; nodes[b.tops[2]] = cp.params[b.src.tag + "_bias"]
-        elif b.type in ("Spreading", "BckLRN"):
+        elif b.type in ("Spreading", "BckLRN", "BckCrop"):
             nodes[b.tops[0]] = nodes[b.src.bot]
         elif b.type == "Reduce":
             if not 2 <= len(b.bots) <= 8:
@@ -307,6 +313,18 @@ def grad_op_to_op(bp: BckPipe, o: GradOp) -> Op:
         else:
             v.update({"out_grad_loss": nd(o.bots[3]), "in_grad_loss": Nda(bp.nodes[o.bots[0]]), "filts_grad_loss": nd(o.tops[1]), "biases_grad_loss": nd(o.tops[2])})
         return Op({"type": t}, v)
+    if t in ("Deconvolution", "BckDeconv"):
+        v = {"in": nd(o.bots[0]), "filts": nd(o.bots[1]), "biases": nd(o.bots[2]), "kern_sz": _none(*s.kern_sz), "stride": _none(*s.stride), "in_pad": _none(*s.in_pad),
+             "out_chans": _u32(s.out_chans)}
+        if t == "Deconvolution":
+            v["out"] = nd(o.tops[0])
+        else:
+            v.update({"out_grad_loss": nd(o.bots[3]), "in_grad_loss": Nda(bp.nodes[o.bots[0]]), "filts_grad_loss": nd(o.tops[1]), "biases_grad_loss": nd(o.tops[2])})
+        return Op({"type": t}, v)
+    if t == "Crop":
+        return Op({"type": t}, {"in": nd(o.bots[0]), "out": nd(o.tops[0]), "offset": _none(*s.offset)})
+    if t == "BckCrop":
+        return Op({"type": t}, {"out_grad_loss": nd(o.bots[0]), "in_grad_loss": Nda(bp.nodes[s.bot]), "offset": _none(*s.offset)})
     if t in ("Pooling", "Spreading"):
         v = {"kern_sz": _none(*s.kern_sz), "stride": _none(*s.stride), "in_pad": _none(*s.in_pad), "avg_pool": _u32(s.avg_pool), "emit_out_in_yx": _u32(0 if s.avg_pool else 1)}
         if t == "Pooling":

@@ -19,7 +19,7 @@ from .bck_graph import (AFFINE_IN_PLACE_TYPES, DROPOUT_RATIO, IN_PLACE_TYPES, RE
 from .call_list import BckCall, CallList
 from .cnn_op import (OpTune, SGD_MAX_TENS, bn_bck_in_func_op, bn_bck_sums_func_op, bn_fwd_func_op, bn_stats_func_op, bnc_bck_in_func_op, bnc_bck_sums_func_op, bnc_fwd_func_op, bnc_stats_func_op, BNC_MAX_CHUNKS, fan_out_func_op, sgd_update_func_op, solver_update_func_op, grad_sumsq_func_op, grad_norm_func_op, grad_accum_func_op, solver_update_acc_func_op, add_bck_conv_annotations, bconv_filts_biases_func_op, add_bck_op_annotations, add_codegen_annotations, add_pipe_op_annotations, fuse_zero_if_in_non_pos,
                      seed_from_var, SEED_VAR_ARG, bf16_operands, is_grouped)
-from .cnn_op import bnf_bck_func_op, bnf_bck_in_func_op, bnf_prep_func_op, data_transform_func_op, loss_norm_func_op, softmax_loss_bck_func_op, softmax_loss_fwd_func_op
+from .cnn_op import bck_deconv_calls, deconv_calls, deconv_role_dims, bnf_bck_func_op, bnf_bck_in_func_op, bnf_prep_func_op, data_transform_func_op, loss_norm_func_op, softmax_loss_bck_func_op, softmax_loss_fwd_func_op
 from .conv_pipe import ConvPipe, PipeOp
 from .input_pipe import DATA_RAW_VAR, DATA_XF_MEAN_VAR, DATA_XF_PLAN_VAR, DATA_XF_TAG, InputTransform
 from .op import Dims, Nda, Op, RtErr, SOLVER_CHUNK, UnsupErr
@@ -74,6 +74,14 @@ class BckPlan:
     dropped_vars: set
     bn_runs: Dict[str, tuple]                        # node X -> (BatchNorm op, Scale op, the ReLU behind them or None); EvalPipe reads them from the driver
     xf_mean: Optional[np.ndarray] = None             # what data_xf_mean is uploaded with
+
+
+@dataclass
+class SideVar:
+    """A var of a plan that is more than its dims: a reshaped view of another var (the same memory under other dim names), or a constant filled once at init."""
+    dims: Dims
+    view_of: Optional[str] = None
+    fill: Optional[float] = None
 
 
 class _Lower:
@@ -137,6 +145,42 @@ class _Lower:
             calls.append((fb, {"out_grad_loss": o.bots[3], "biases_grad_loss": o.tops[2]}))
             calls.append((ff, {"in": o.bots[0], "out_grad_loss": o.bots[3], "filts_grad_loss": o.tops[1]}))
         return calls, []
+
+    def _deconv_bound(self, o, op, calls, roles):
+        """The calls of cnn_op.deconv_calls / bck_deconv_calls with their roles bound: the layer's own vars from `roles`; on the matrix path the views of the layer's
+        vars under the exchanged dims (<tag>_filts_x, <tag>_filts_grad_loss_x, <tag>_biases_x) and the constants <tag>_ones / <tag>_zeros as side vars."""
+        tag, out, side = o.src.tag, [], []
+        view_of = {"filts_x": "filts", "filts_grad_loss_x": "filts_grad_loss", "biases_x": "biases"}
+        fill = {"ones": 1.0, "zeros": 0.0}
+        for fop, binds in calls:
+            args = {}
+            for an, role in binds.items():
+                if role in roles:
+                    args[an] = roles[role]; continue
+                vn = f"{tag}_{role}"
+                sv = SideVar(deconv_role_dims(op, role), view_of=roles[view_of[role]]) if role in view_of else SideVar(deconv_role_dims(op, role), fill=fill[role])
+                if vn in self.bp.nodes:
+                    raise RtErr(f"ConvPipeBck.init: the Deconvolution {tag!r} needs the var name {vn!r}, which is a node of the pipe")
+                side.append((vn, sv)); args[an] = vn
+            out.append((fop, args))
+        return out, side
+
+    def deconv(self, o):   # hip_deconv, or the matrix path's hip_bconv_in + hip_chan_affine; a ReLU behind it is `relu` above, as behind any op that is no Convolution
+        op = grad_op_to_op(self.bp, o)
+        return self._deconv_bound(o, op, deconv_calls(op, self.tune), {"filts": o.bots[1], "biases": o.bots[2], "in": o.bots[0], "out": o.tops[0]})
+
+    def bck_deconv(self, o):   # BckConv's three calls in its order; Freeze drops the data gradient or the filter / bias pair as for a BckConv
+        op = grad_op_to_op(self.bp, o)
+        ci, cb, cf = bck_deconv_calls(op, self.tune)
+        calls = ([ci] if self.kept(o, 0) else []) + ([cb, cf] if self.kept(o, 1) else [])
+        return self._deconv_bound(o, op, calls, {"in": o.bots[0], "filts": o.bots[1], "biases": o.bots[2], "out_grad_loss": o.bots[3], "in_grad_loss": o.tops[0],
+                                                 "filts_grad_loss": o.tops[1], "biases_grad_loss": o.tops[2]})
+
+    def crop(self, o):
+        return [(self._bck_ann(o), {"in": o.bots[0], "out": o.tops[0]})], []
+
+    def bck_crop(self, o):
+        return [(self._bck_ann(o), {"out_grad_loss": o.bots[0], "in_grad_loss": o.tops[0]})], []
 
     def pool(self, o):
         yx = o.tops[0] + "_in_yx"
@@ -220,7 +264,8 @@ class _Lower:
 
     BY_TYPE = {"Convolution": conv, "ReLU": relu, "BckConv": bck_conv, "Pooling": pool, "Spreading": spreading, "LRN": lrn, "BckLRN": bck_lrn,
                "ZeroIfNonPos": zero_if_non_pos, "SoftmaxWithLoss": loss, "Dropout": dropout, "BckDropout": dropout, "Reduce": reduce, "Eltwise": reduce, "Concat": concat,
-               "Split": split, "BckEltwise": bck_eltwise, "BatchNorm": bn_run, "Scale": bn_run, "BckScale": bn_run, "BckBatchNorm": bn_run}
+               "Split": split, "BckEltwise": bck_eltwise, "BatchNorm": bn_run, "Scale": bn_run, "BckScale": bn_run, "BckBatchNorm": bn_run,
+               "Deconvolution": deconv, "BckDeconv": bck_deconv, "Crop": crop, "BckCrop": bck_crop}
 
 
 class ConvPipeBck:
@@ -339,9 +384,17 @@ class ConvPipeBck:
         self.per_call_ms: List[Tuple[str, str, float]] = []
         self.compute_dur_ms = 0.0
 
-    def _var(self, vn: str, dims: Dims) -> None:
-        if vn not in self.vars:
-            self.rtc.create_var_with_dims(vn, dims); self.vars.append(vn)
+    def _var(self, vn: str, dims) -> None:
+        if vn in self.vars:
+            return
+        if isinstance(dims, SideVar):   # a view of another var (its calls are ordered as calls on that var), or a constant
+            if dims.view_of is not None:
+                self.rtc.create_var_with_dims_as_reshaped_view_of_var(vn, dims.dims, dims.view_of); self._calls.alias[vn] = dims.view_of
+            else:
+                self.rtc.create_var_with_dims(vn, dims.dims); self.rtc.copy_nda_to_var(vn, np.full(dims.dims.sizes, dims.fill, np.float32))
+        else:
+            self.rtc.create_var_with_dims(vn, dims)
+        self.vars.append(vn)
 
     bck_calls = property(lambda self: self._calls.calls)    # the step's BckCalls in run order
     funcs = property(lambda self: self._calls.funcs)
@@ -385,6 +438,10 @@ class ConvPipeBck:
         if grouped and multi_dev:
             raise UnsupErr(f"ConvPipeBck.init: the convolution {grouped[0].tag!r} has group={grouped[0].src.group}: the grouped functions take vars of exactly their op's dims, "
                            "not img shards, and are not provided on a multi-device backend (devices=...); grouped layers on several devices are out of scope")
+        deconvs = [o for o in bp.fwd_ops() if o.type == "Deconvolution"]
+        if deconvs and multi_dev:
+            raise UnsupErr(f"ConvPipeBck.init: the layer {deconvs[0].tag!r} is a Deconvolution: its functions take vars of exactly their op's dims, not img shards, and are "
+                           "not provided on a multi-device backend (devices=...); Deconvolution layers on several devices are out of scope")
         spec_heads = [o for o in bp.fwd_ops() if o.type == "SoftmaxWithLoss" and o.spec is not None]
         if spec_heads and multi_dev:
             raise UnsupErr(f"ConvPipeBck.init: the loss {spec_heads[0].tag!r} has a LossSpec: the full softmax loss (hip_softmax_loss_fwd, hip_loss_norm, hip_softmax_loss_bck) "
@@ -588,7 +645,7 @@ class ConvPipeBck:
             if b.type == "Reduce":
                 continue
             f = b.tag[:-4]   # <forward tag>_bck
-            if b.type in ("BckConv", "BckScale"):
+            if b.type in ("BckConv", "BckDeconv", "BckScale"):
                 k = [in_need[f][0], op_train[f], op_train[f]]
                 if b.type == "BckScale" and b.bots[1] not in glob_x and in_need[f][0]:
                     k[1] = k[2] = True   # a training BatchNorm's data gradient reads the two sums
@@ -822,7 +879,7 @@ class ConvPipeBck:
 
     def release(self) -> None:
         self._calls.release()
-        for v in self.vars:
+        for v in reversed(self.vars):   # (a view goes before the var it is a view of)
             self.rtc.release_var(v)
         self.vars = []
         self.n_sgd_calls = 0

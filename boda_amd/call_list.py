@@ -28,6 +28,7 @@ class CallList:
         self.calls: List[BckCall] = []
         self.funcs: List[str] = []
         self.graph: Optional[int] = None
+        self.alias: Dict[str, str] = {}          # a var that is a view of another var -> that var: deps() orders a call on the view as a call on the var
         self._infos: List[RtcFuncInfo] = []      # of the functions emitted since the last compile
         self._multi_dev = isinstance(getattr(rtc, "devices", None), list) and len(rtc.devices) > 1
 
@@ -87,9 +88,9 @@ class CallList:
             rd, wr = set(), set()
             for an, io in pipe_func_args(c.fop):
                 if io in ("IN", "INOUT") or an == "inout":
-                    rd.add(am[an].n)
+                    rd.add(self.alias.get(am[an].n, am[an].n))
                 if io in ("OUT", "INOUT"):
-                    wr.add(am[an].n)
+                    wr.add(self.alias.get(am[an].n, am[an].n))
             d = {writer[v] for v in rd | wr if v in writer}
             for v in wr:
                 d.update(readers.get(v, ()))

@@ -226,6 +226,155 @@ def add_bck_conv_grp_annotations(op: Op, tune: OpTune) -> tuple:
     return tuple(outs)
 
 
+# a Deconvolution / BckDeconv (this backend's own; kernels/deconv_f32.hip): each function is an existing one with the operands' roles exchanged
+DECONV_FUNC = "hip_deconv"
+BCK_DECONV_FUNCS = ("hip_deconv_bck_in", "hip_deconv_bck_biases", "hip_deconv_bck_filts")   # BckConv's call order
+
+
+def refuse_deconv_tune(op: Op, tune: OpTune) -> None:
+    """UnsupErr that names the layer type where a Deconvolution meets an option it has no form under: fp32 in reference layouts on the family's own functions only."""
+    bad = [n for n, v in (("use_culibs", tune.use_culibs), ("k1conv", tune.k1conv), ("tconv", tune.tconv), ("ipconv", tune.ipconv), ("hip_algo", tune.hip_algo),
+                          ("hip_layout", tune.hip_layout), ("hip_out", tune.hip_out)) if v]
+    if tune.hip_dtype not in ("", "f32"):
+        bad.append("hip_dtype")
+    if tune.use_be not in ("", "hip"):
+        bad.append("use_be")
+    if bad:
+        raise UnsupErr(f"{op.get_type()}: a Deconvolution has no form under op_tune {', '.join(bad)} ({tune.to_str()}): fp32 in reference layouts only "
+                       f"({DECONV_FUNC} / {' / '.join(BCK_DECONV_FUNCS)})")
+
+
+DECONV_MATRIX_MIN_CHANS = 32   # the planner's threshold: the matrix path where min(C, OC) reaches it (DESIGN.md section 3.25 says where it sits and why) ...
+DECONV_MATRIX_MIN_TERMS = 1024 # ... or where a gradient's chain, max(C, OC) x KH x KW terms, reaches this: moved here on the record (FCN's 16/8 head, 5376 terms: 6 - 11x)
+DECONV_MATRIX_MAX_STRIDE = 16  # hip_bconv_in / hip_bconv_filts: strides of at most 16 (kernels of at most 64 x 64 hold for the whole family)
+
+
+def deconv_matrix_can(op: Op) -> bool:
+    """Is the exchanged geometry inside the existing functions' limits (hip_bconv_in, hip_conv, hip_bconv_filts)?"""
+    g = op.deconv_geom()
+    return max(g["SY"], g["SX"]) <= DECONV_MATRIX_MAX_STRIDE and max(g["KH"], g["KW"]) <= 64
+
+
+def deconv_form(op: Op, tune: OpTune) -> str:
+    """-> "direct" | "matrix": which path a Deconvolution / BckDeconv takes.  The rule reads the op alone: the direct forms (kernels/deconv_f32.hip) where
+    min(C, OC) < DECONV_MATRIX_MIN_CHANS and max(C, OC) x KH x KW < DECONV_MATRIX_MIN_TERMS, or the exchanged geometry is outside an existing function's limits,
+    else the existing matrix functions on the exchanged roles.  A tile string forces either: a seven-field tile whose BI is 1 the direct forms, any tile whose BI is larger the matrix path (UnsupErr where the
+    geometry is outside the limits); the tile then travels with that path's conv functions."""
+    g = op.deconv_geom()
+    tile = tune.hip_tile
+    if tile:
+        bi = tile.split("x")[0]
+        if is_grp_tile(tile) and bi == "1":
+            return "direct"
+        if bi.isdigit() and int(bi) > 1:
+            if not deconv_matrix_can(op):
+                raise UnsupErr(f"{op.get_type()}: tile {tile} asks for the matrix path, but stride {g['SY']} x {g['SX']} is outside hip_bconv_in's / hip_bconv_filts' limits "
+                               f"(at most {DECONV_MATRIX_MAX_STRIDE}): the direct forms only")
+            return "matrix"
+    wide = min(g["C"], g["OC"]) >= DECONV_MATRIX_MIN_CHANS or max(g["C"], g["OC"]) * g["KH"] * g["KW"] >= DECONV_MATRIX_MIN_TERMS
+    return "matrix" if wide and deconv_matrix_can(op) else "direct"
+
+
+def deconv_exchanged_ops(op: Op) -> tuple:
+    """-> (Convolution op, BckConv op) of the exchanged roles of a Deconvolution / BckDeconv: the convolution OC -> C whose input plane is the layer's out and whose
+    output plane is the layer's in; its filts are the layer's blob read as out_chan=C : in_chan=OC."""
+    from .op import Dims
+    g = op.deconv_geom()
+    f = Dims(("out_chan", "in_chan", "y", "x"), (g["C"], g["OC"], g["KH"], g["KW"]), "float")
+    big = Dims(("img", "chan", "y", "x"), (g["B"], g["OC"], g["OH"], g["OW"]), "float")
+    small, b = op.get_dims("in"), Dims(("out_chan",), (g["C"],), "float")
+    common = {"filts": Nda(dims=f, tn="float"), "biases": Nda(dims=b, tn="float"), "in": Nda(dims=big, tn="float"), "kern_sz": op.get("kern_sz"), "stride": op.get("stride"),
+              "in_pad": op.get("in_pad"), "out_chans": Nda(None, "uint32_t", (g["C"],))}
+    conv = Op({"type": "Convolution"}, dict(common, out=Nda(dims=small, tn="float")))
+    bck = Op({"type": "BckConv"}, dict(common, out_grad_loss=Nda(dims=small, tn="float"), in_grad_loss=Nda(dims=big, tn="float"), filts_grad_loss=Nda(dims=f, tn="float"),
+                                       biases_grad_loss=Nda(dims=b, tn="float")))
+    conv.conv_geom(); bck.bck_conv_geom()
+    return conv, bck
+
+
+# the vars of a matrix-path call, by ROLE: the layer's own ("in", "out", "biases", "out_grad_loss", "in_grad_loss", "biases_grad_loss"), views of the layer's vars under
+# the exchanged dims ("filts_x" / "filts_grad_loss_x": the blob as out_chan=C : in_chan=OC; "biases_x": biases as chan=OC) and the two constants the driver creates
+# ("ones": chan=OC values of 1; "zeros": out_chan=C values of +0).  deconv_role_dims gives a role's dims
+def deconv_role_dims(op: Op, role: str):
+    from .op import Dims
+    g = op.deconv_geom()
+    if role in ("filts_x", "filts_grad_loss_x"):
+        return Dims(("out_chan", "in_chan", "y", "x"), (g["C"], g["OC"], g["KH"], g["KW"]), "float")
+    if role in ("biases_x", "ones"):
+        return Dims(("chan",), (g["OC"],), "float")
+    if role == "zeros":
+        return Dims(("out_chan",), (g["C"],), "float")
+    raise RtErr(f"deconv_role_dims: {role!r} is no view or constant of the matrix path")
+
+
+def _matrix_tune(tune: OpTune) -> OpTune:
+    """The tune the exchanged functions are annotated under: the caller's, without a tile that is this family's own (seven fields, BI = 1)."""
+    from dataclasses import replace
+    return replace(tune, hip_tile="") if is_grp_tile(tune.hip_tile) and tune.hip_tile.split("x")[0] == "1" else tune
+
+
+def deconv_calls(op: Op, tune: OpTune, form: str = "") -> list:
+    """-> [(function op, {arg: role})] of a Deconvolution in call order.  Direct: [hip_deconv].  Matrix: hip_bconv_in on (filts := filts_x, out_grad_loss := in) into
+    out, then hip_chan_affine in place on out with a := ones, b := biases_x -- fma(x, 1, b) is the one add.  `form` forces the path ("" = deconv_form)."""
+    if op.get_type() != "Deconvolution":
+        raise RtErr(f"deconv_calls: op type {op.get_type()!r} is not Deconvolution")
+    op.deconv_geom()
+    refuse_deconv_tune(op, tune)
+    if (form or deconv_form(op, tune)) == "direct":
+        a = op.copy()
+        a.set_func_name(DECONV_FUNC)
+        return [(a, {"filts": "filts", "biases": "biases", "in": "in", "out": "out"})]
+    if not deconv_matrix_can(op):
+        raise UnsupErr(f"{op.get_type()}: the matrix path: the exchanged geometry is outside hip_bconv_in's limits (strides of at most {DECONV_MATRIX_MAX_STRIDE})")
+    fi = add_bck_conv_annotations(deconv_exchanged_ops(op)[1], _matrix_tune(tune))[0]
+    aff = chan_affine_func_op(op.get_dims("out"), 0)
+    return [(fi, {"filts": "filts_x", "out_grad_loss": "in", "in_grad_loss": "out"}), (aff, {"in": "out", "a": "ones", "b": "biases_x", "out": "out"})]
+
+
+def bck_deconv_calls(op: Op, tune: OpTune, form: str = "") -> list:
+    """-> [(function op, {arg: role})] of a BckDeconv in BckConv's call order: data, bias and filter gradient.  Direct: hip_deconv_bck_in, hip_deconv_bck_biases,
+    hip_deconv_bck_filts (a seven-field tile travels with the filter gradient: its BK / KSL).  Matrix: hip_conv without ReLU on (filts := filts_x, biases := zeros,
+    in := out_grad_loss) into in_grad_loss; hip_deconv_bck_biases as it is; hip_bconv_filts on (in := out_grad_loss, out_grad_loss := in) into filts_grad_loss_x."""
+    if op.get_type() != "BckDeconv":
+        raise RtErr(f"bck_deconv_calls: op type {op.get_type()!r} is not BckDeconv")
+    op.deconv_geom()
+    refuse_deconv_tune(op, tune)
+    fb = op.copy(); fb.set_func_name("hip_deconv_bck_biases")
+    bias_call = (fb, {"out_grad_loss": "out_grad_loss", "biases_grad_loss": "biases_grad_loss"})
+    if (form or deconv_form(op, tune)) == "direct":
+        fi = op.copy(); fi.set_func_name("hip_deconv_bck_in")
+        ff = op.copy(); ff.set_func_name("hip_deconv_bck_filts")
+        if is_grp_tile(tune.hip_tile):
+            ff.str_vals["hip_tile"] = tune.hip_tile
+        return [(fi, {"filts": "filts", "out_grad_loss": "out_grad_loss", "in_grad_loss": "in_grad_loss"}), bias_call,
+                (ff, {"in": "in", "out_grad_loss": "out_grad_loss", "filts_grad_loss": "filts_grad_loss"})]
+    if not deconv_matrix_can(op):
+        raise UnsupErr(f"{op.get_type()}: the matrix path: the exchanged geometry is outside hip_bconv_filts' limits (strides of at most {DECONV_MATRIX_MAX_STRIDE})")
+    xc, xb = deconv_exchanged_ops(op)
+    mt = _matrix_tune(tune)
+    fc = add_codegen_annotations(xc, mt)
+    fc.nda_vals["conv_has_relu"] = Nda(None, "uint32_t", (0,))
+    ff = add_bck_conv_annotations(xb, mt)[2]
+    return [(fc, {"filts": "filts_x", "biases": "zeros", "in": "out_grad_loss", "out": "in_grad_loss"}), bias_call,
+            (ff, {"in": "out_grad_loss", "out_grad_loss": "in", "filts_grad_loss": "filts_grad_loss_x"})]
+
+
+def add_deconv_annotations(op: Op, tune: OpTune, form: str = ""):
+    """-> the function op(s) of a Deconvolution under the planner's rule (deconv_form), a forcing tile or `form`: hip_deconv, the direct form, as ONE Op; or the tuple
+    (hip_bconv_in, hip_chan_affine) of the matrix path, built on the exchanged dims.  deconv_calls gives the same functions with their arg bindings."""
+    calls = deconv_calls(op, tune, form)
+    return calls[0][0] if len(calls) == 1 else tuple(f for f, _ in calls)
+
+
+def add_bck_deconv_annotations(op: Op, tune: OpTune, form: str = "") -> tuple:
+    """-> (in_op, biases_op, filts_op) of a BckDeconv in BckConv's call order under the planner's rule (deconv_form), a forcing tile or `form`: the direct
+    hip_deconv_bck_in, hip_deconv_bck_biases (hip_bconv_biases' sum on out_grad_loss), hip_deconv_bck_filts -- a seven-field tile (BK and KSL) travels with the filter
+    gradient --, or the matrix path's hip_conv (zero biases, no ReLU), hip_deconv_bck_biases, hip_bconv_filts on the exchanged dims (bck_deconv_calls: the bindings)."""
+    if op.get_type() != "BckDeconv":
+        raise RtErr(f"add_bck_deconv_annotations: op type {op.get_type()!r} is not BckDeconv")
+    return tuple(f for f, _ in bck_deconv_calls(op, tune, form))
+
+
 def add_bck_conv_annotations(op: Op, tune: OpTune) -> tuple:
     """-> (in_op, biases_op, filts_op): the three annotated function ops of a BckConv, in the order src/rtc_fwd.cc:398-400 calls them -- the data gradient
     (hip_bconv_in), the bias gradient (hip_bconv_biases), the filter gradient (hip_bconv_filts).  fp32 and reference layouts only (bf16 / channels-last gradients
@@ -280,6 +429,8 @@ BCK_OP_FUNCS: Dict[str, tuple] = {
     "SoftmaxWithLoss": ("hip_softmax", "hip_sm_grad_and_loss", "hip_sum_loss_over_imgs"),
     "Pooling": ("hip_pool_yx",),
     "LRN": ("hip_lrn_sb",),
+    "Crop": ("hip_crop",),         # Caffe's Crop at axis 2 and its gradient (this backend's own; OP 15 / 16 of kernels/bck_ops_f32.hip): the offsets ride in the op
+    "BckCrop": ("hip_crop_bck",),
 }
 
 
@@ -309,6 +460,8 @@ def add_bck_op_annotations(op: Op, tune: OpTune) -> tuple:
         a.nda_vals["out_scale_base"] = Nda(dims=a.get_dims("out"), tn="float")
     elif t == "ZeroIfNonPos":
         a.zinp_geom()
+    elif t in ("Crop", "BckCrop"):
+        a.crop_geom()
     else:
         a.softmax_geom()
         a.nda_vals["prob"] = Nda(dims=a.get_dims("in"), tn="float")
@@ -913,6 +1066,13 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_conv_grp": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),
     "hip_bconv_in_grp": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),
     "hip_bconv_filts_grp": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT")),
+    # a Deconvolution / BckDeconv: the lists of hip_conv and of BckConv's three gradients without their optional args; Caffe's Crop and its gradient
+    "hip_deconv": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),
+    "hip_deconv_bck_in": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),
+    "hip_deconv_bck_filts": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT")),
+    "hip_deconv_bck_biases": (("out_grad_loss", "IN"), ("biases_grad_loss", "OUT")),
+    "hip_crop": (("in", "IN"), ("out", "OUT")),
+    "hip_crop_bck": (("out_grad_loss", "IN"), ("in_grad_loss", "OUT")),
     "hip_bconv_biases": (("out_grad_loss", "IN"), ("biases_grad_loss", "OUT")),   # filts as [K + 128][out_chan padded to 4]: what hip_conv's optional filts_km arg takes
     # the non-conv backward ops, in their reference templates' arg order (test/rtc/pool.cucl, lrn.cucl, spreading.cucl, bck_lrn.cucl, ZeroIfNonPos.cucl, softmax.cucl,
     # sm_grad_and_loss.cucl, sum_loss_over_imgs.cucl); the by-value scalars of those templates (avg_pool, alpha, ...) ride in the op

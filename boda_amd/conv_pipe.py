@@ -25,7 +25,7 @@ import os
 import numpy as np
 
 from . import gen_data as gd
-from .cnn_op import CHAN_AFFINE_FUNC, FILTS_KMAJOR_FUNC, K1_CHAIN_FUNC, NATIVE_ARGS, OpTune, chan_affine_func_op, pipe_func_args, add_codegen_annotations, annotate_k1_chain, f32_pool_fusable, filts_kmajor_func_op, fuse_f32_pool, k1_chain_applies
+from .cnn_op import add_bck_op_annotations, deconv_calls, deconv_role_dims, CHAN_AFFINE_FUNC, FILTS_KMAJOR_FUNC, K1_CHAIN_FUNC, NATIVE_ARGS, OpTune, chan_affine_func_op, pipe_func_args, add_codegen_annotations, annotate_k1_chain, f32_pool_fusable, filts_kmajor_func_op, fuse_f32_pool, k1_chain_applies
 from .cucl_template import instantiate, parse_template
 from .op import Dims, Nda, Op, RtErr, UnsupErr
 from .rtc import HipCompute, RtcArg, RtcCompileOpts, RtcFuncCall, RtcFuncInfo
@@ -37,7 +37,7 @@ from .rtc import HipCompute, RtcArg, RtcCompileOpts, RtcFuncCall, RtcFuncInfo
 @dataclass
 class PipeOp:
     tag: str
-    type: str                      # Convolution | Pooling | ReLU | LRN | Dropout | Concat | BatchNorm | Scale | Eltwise
+    type: str                      # Convolution | Pooling | ReLU | LRN | Dropout | Concat | BatchNorm | Scale | Eltwise | Deconvolution | Crop
     bot: str
     top: str
     out_chans: int = 0
@@ -49,6 +49,7 @@ class PipeOp:
     bots: Tuple[str, ...] = ()     # Concat: all inputs in channel order (bot == bots[0]); Eltwise: the 2 to 8 nodes that are summed, in that order
     eps: float = 1e-5              # BatchNorm: added to the variance
     group: int = 1                 # Convolution: Caffe's `group` -- out_chans j*OC/g .. read channels j*C/g .. only; filts are out_chan : in_chan=C/g : y : x
+    offset: Tuple[int, int] = (0, 0)   # Crop (Caffe's, axis 2): bots = (a, ref); top = the window of a at (y, x) = offset with ref's y / x; ref gives only the size
 
     @property
     def in_place(self) -> bool:
@@ -81,6 +82,28 @@ class ConvPipe:
             out = Dims.make("float", img=B, chan=op.out_chans, y=oh, x=ow)
             self.params[op.tag + "_filts"] = Dims.make("float", out_chan=op.out_chans, in_chan=C // op.group, y=kh, x=kw)
             self.params[op.tag + "_biases"] = Dims.make("float", out_chan=op.out_chans)
+        elif op.type == "Deconvolution":   # out = (in - 1) * stride + kern - 2 * pad, the inverse of the convolution's rule; filts are Caffe's blob in_chan : out_chan : y : x
+            if op.group != 1:
+                raise UnsupErr(f"pipe: deconvolution {op.tag}: group={op.group}: a Deconvolution with group > 1 is out of scope")
+            kh, kw = op.kern_sz
+            oh = (H - 1) * op.stride[0] + kh - 2 * op.in_pad[0]; ow = (W - 1) * op.stride[1] + kw - 2 * op.in_pad[1]
+            if oh < 1 or ow < 1 or min(kh, kw, op.stride[0], op.stride[1], op.out_chans) < 1:
+                raise RtErr(f"pipe: deconvolution {op.tag}: the padding leaves no output ({oh} x {ow})")
+            out = Dims.make("float", img=B, chan=op.out_chans, y=oh, x=ow)
+            self.params[op.tag + "_filts"] = Dims.make("float", in_chan=C, out_chan=op.out_chans, y=kh, x=kw)
+            self.params[op.tag + "_biases"] = Dims.make("float", out_chan=op.out_chans)
+        elif op.type == "Crop":            # Caffe's Crop at axis 2: the window of bots[0] at `offset` with bots[1]'s y / x
+            if len(op.bots) != 2 or op.bot != op.bots[0]:
+                raise RtErr(f"pipe: crop {op.tag}: bots must be (a, ref) with bot == a")
+            if op.bots[1] not in self.nodes:
+                raise RtErr(f"pipe: crop {op.tag} reads unknown node {op.bots[1]!r}")
+            r = self.nodes[op.bots[1]]
+            (oy, ox), rh, rw = op.offset, r.dsz("y"), r.dsz("x")
+            if oy < 0 or ox < 0 or oy + rh > H or ox + rw > W:
+                raise RtErr(f"pipe: crop {op.tag}: offset ({oy}, {ox}) + {op.bots[1]}'s plane ({rh}, {rw}) exceeds {op.bot}'s plane ({H}, {W})")
+            if op.in_place or op.top in op.bots:
+                raise RtErr(f"pipe: crop {op.tag} must write a new node")
+            out = Dims.make("float", img=B, chan=C, y=rh, x=rw)
         elif op.type == "Pooling":
             if op.kern_sz is None:   # global pooling
                 op.kern_sz, op.stride, op.in_pad = (H, W), (1, 1), (0, 0)
@@ -131,10 +154,10 @@ class ConvPipe:
         return self
 
     def conv_op(self, op: PipeOp) -> Op:
-        """The op_base_t line of a Convolution of this pipe (same text form as the ops-prof op lists)."""
+        """The op_base_t line of a Convolution or a Deconvolution of this pipe (same text form as the ops-prof op lists)."""
         i, o = self.nodes[op.bot], self.nodes[op.top]
         none = lambda y, x: Nda(Dims(("y", "x"), (y, x), "none"), "none")
-        r = Op({"type": "Convolution"}, {"in": Nda(i), "out": Nda(o), "filts": Nda(self.params[op.tag + "_filts"]),
+        r = Op({"type": op.type if op.type == "Deconvolution" else "Convolution"}, {"in": Nda(i), "out": Nda(o), "filts": Nda(self.params[op.tag + "_filts"]),
                                          "biases": Nda(self.params[op.tag + "_biases"]), "kern_sz": none(*op.kern_sz),
                                          "stride": none(*op.stride), "in_pad": none(*op.in_pad),
                                          "out_chans": Nda(None, "uint32_t", (op.out_chans,))})
@@ -142,8 +165,12 @@ class ConvPipe:
             r.nda_vals["group"] = Nda(None, "uint32_t", (op.group,))
         return r
 
+    def crop_op(self, op: PipeOp) -> Op:
+        """The op_base_t line of a Crop of this pipe."""
+        return Op({"type": "Crop"}, {"in": Nda(self.nodes[op.bot]), "out": Nda(self.nodes[op.top]), "offset": Nda(Dims(("y", "x"), tuple(op.offset), "none"), "none")})
+
     def conv_flops(self) -> int:
-        return sum(self.conv_op(o).flops() for o in self.ops if o.type == "Convolution")
+        return sum(self.conv_op(o).flops() for o in self.ops if o.type in ("Convolution", "Deconvolution"))
 
     def out_node(self) -> str:
         return self.ops[-1].top
@@ -326,6 +353,38 @@ def dw_sep_tiny(batch: int, in_hw: int = 12, classes: int = 10) -> ConvPipe:
     return p
 
 
+def bilinear_filts(C: int, OC: int, k: int) -> np.ndarray:
+    """Caffe's bilinear filler on the diagonal c == oc of a Deconvolution's filts[C][OC][k][k], +0 elsewhere: with f = ceil(k / 2) and c0 = (2f - 1 - f % 2) / (2f),
+    w[y][x] = (1 - |y / f - c0|) * (1 - |x / f - c0|), every operation in fp32."""
+    f32 = np.float32
+    f = f32(-(-k // 2))
+    c0 = f32(2 * f - 1 - f % 2) / f32(2 * f)
+    t = f32(1) - np.abs(np.arange(k, dtype=f32) / f - c0, dtype=f32)
+    w = np.zeros((C, OC, k, k), f32)
+    for c in range(min(C, OC)):
+        w[c, c] = t[:, None] * t[None, :]
+    return w
+
+
+def fcn_tiny(batch: int, in_hw: int = 16, classes: int = 5) -> ConvPipe:
+    """An FCN-16s in miniature: conv 3x3 / pool / conv 3x3 / pool, a 1x1 score at a quarter of the input, a Deconvolution 4/2 (to 10 x 10 at in_hw = 16), cropped at
+    offset 1 to the plane of a 1x1 score on pool1 and summed with it, a Deconvolution 4/2 of the sum (18 x 18), cropped at offset 1 to data's plane: the head of a
+    plane loss (add_bck_ops caps it with the full SoftmaxWithLoss)."""
+    p = ConvPipe("fcn_tiny", "data", Dims.make("float", img=batch, chan=3, y=in_hw, x=in_hw))
+    n = _conv(p, "conv1", "data", 8, 3, 1, 1)
+    p.add(PipeOp("pool1", "Pooling", n, "pool1", kern_sz=(2, 2), stride=(2, 2)))
+    n = _conv(p, "conv2", "pool1", 12, 3, 1, 1)
+    p.add(PipeOp("pool2", "Pooling", n, "pool2", kern_sz=(2, 2), stride=(2, 2)))
+    p.add(PipeOp("score2", "Convolution", "pool2", "score2", out_chans=classes, kern_sz=(1, 1)))
+    p.add(PipeOp("up2", "Deconvolution", "score2", "up2", out_chans=classes, kern_sz=(4, 4), stride=(2, 2)))
+    p.add(PipeOp("score1", "Convolution", "pool1", "score1", out_chans=classes, kern_sz=(1, 1)))
+    p.add(PipeOp("up2c", "Crop", "up2", "up2c", bots=("up2", "score1"), offset=(1, 1)))
+    p.add(PipeOp("fuse1", "Eltwise", "up2c", "fuse1", bots=("up2c", "score1")))
+    p.add(PipeOp("up1", "Deconvolution", "fuse1", "up1", out_chans=classes, kern_sz=(4, 4), stride=(2, 2)))
+    p.add(PipeOp("score", "Crop", "up1", "score", bots=("up1", "data"), offset=(1, 1)))
+    return p
+
+
 def resnet50(batch: int, in_hw: int = 224) -> ConvPipe:
     """nets/resnet-50/train_val.prototxt (TEST phase), Caffe's node and layer names: conv1 7x7/2 (+ bn_conv1, scale_conv1, ReLU), pool1 max 3x3/2, stages 2 .. 5 of
     [3, 4, 6, 3] bottleneck blocks, pool5 (global average), fc1000.  A block: branch2a 1x1 -> branch2b 3x3 -> branch2c 1x1 (x4 channels), every convolution followed
@@ -373,6 +432,11 @@ def pipe_from_spec(name: str, lines: Sequence[str], batch: int) -> ConvPipe:
             oc, kh, kw, sy, sx, py, px = (int(x) for x in f[4:11])
             grp = int(f[11]) if len(f) > 11 else 1   # (an optional twelfth field: the group)
             p.add(PipeOp(f[1], "Convolution", f[2], f[3], out_chans=oc, kern_sz=(kh, kw), stride=(sy, sx), in_pad=(py, px), group=grp))
+        elif k == "deconv":   # deconv tag bot top oc kh kw sy sx py px
+            oc, kh, kw, sy, sx, py, px = (int(x) for x in f[4:11])
+            p.add(PipeOp(f[1], "Deconvolution", f[2], f[3], out_chans=oc, kern_sz=(kh, kw), stride=(sy, sx), in_pad=(py, px)))
+        elif k == "crop":     # crop tag bot ref top oy ox
+            p.add(PipeOp(f[1], "Crop", f[2], f[4], bots=(f[2], f[3]), offset=(int(f[5]), int(f[6]))))
         elif k == "pool":
             kh, kw, sy, sx, py, px, avg, glob = (int(x) for x in f[4:12])
             p.add(PipeOp(f[1], "Pooling", f[2], f[3], kern_sz=None if glob else (kh, kw), stride=(sy, sx), in_pad=(py, px), avg_pool=avg))
@@ -607,6 +671,7 @@ class ConvPipeFwd:
         self.cp: Optional[ConvPipe] = None
         self.compute_dur_ms = float("nan")
         self._vars: List[str] = []
+        self._views: List[str] = []   # vars that are views of a param under other dim names (a Deconvolution's matrix path): released before the vars
         self._funcs: List[str] = []
         self.concat_elim = True      # convs write straight into their channel range of a Concat output where legal
         # op_tune (hip_dtype=bf16, hip_layout=nhwc): EVERY node lives as a channels-last bf16 tensor (channels padded to a multiple of 8), convs
@@ -628,6 +693,11 @@ class ConvPipeFwd:
                 except UnsupErr as e:
                     raise UnsupErr(f"pipe {cp.name}: convolution {o.tag}: {e}") from None
                 break
+        # Deconvolution and Crop layers run as hip_deconv / hip_crop: fp32 in reference layouts only -- refused by the first such layer's name, before anything is created
+        for o in cp.ops:
+            if o.type in ("Deconvolution", "Crop") and (self.nhwc or self.op_tune.hip_dtype not in ("", "f32")):
+                raise UnsupErr(f"pipe {cp.name}: {o.type} {o.tag}: a {o.type} layer has no bf16 or channels-last form (op_tune {self.op_tune.to_str()}): fp32 in reference "
+                               f"layouts only")
         try:    # the device's CU count for the planner questions asked below (a recording backend has none: the MI355X's 256)
             info = rtc.get_device_info()
             self._num_cus = int(info["num_cus"]) if isinstance(info, dict) and info.get("num_cus") else 256
@@ -1062,6 +1132,34 @@ class ConvPipeFwd:
                     self._km_params.append(RtcFuncCall(xfn, {"filts": am["filts"], "filts_km": RtcArg.var(kmv)}))
                     am["filts_km"] = RtcArg.var(kmv)
                 self.fwd_calls.append(FwdCall(op.tag, RtcFuncCall(gen_fn, am), fn, cop.flops()))
+            elif op.type == "Deconvolution":   # hip_deconv, the direct form; a ReLU behind it runs as a ReLU behind any op that is no Convolution
+                dop = cp.conv_op(op)
+                roles = {"filts": op.tag + "_filts", "biases": op.tag + "_biases", "in": vn(op.bot), "out": op.top}
+                view_of = {"filts_x": "filts", "biases_x": "biases"}
+                for ci, (fop, binds) in enumerate(deconv_calls(dop, self.op_tune)):   # hip_deconv, or the matrix path's hip_bconv_in + hip_chan_affine (cnn_op.deconv_form)
+                    fn = fop.get_func_name(); gen_fn = f"{fn}__{cp.name}_{op.tag}"
+                    annos[op.tag if ci == 0 else f"{op.tag}.{ci}"] = fop
+                    rtc.compile([RtcFuncInfo(gen_fn, "", [a for a, _ in NATIVE_ARGS[fn]], fop)]); self._funcs.append(gen_fn)
+                    am = {}
+                    for an, io in NATIVE_ARGS[fn]:
+                        if io == "REF":
+                            am[an] = RtcArg.ref(fop.get_dims(an)); continue
+                        role = binds[an]
+                        if role not in roles:   # a view of the layer's params under the exchanged dims, or the constant ones (the matrix path's)
+                            v = f"{op.tag}_{role}"
+                            if role in view_of:
+                                rtc.create_var_with_dims_as_reshaped_view_of_var(v, deconv_role_dims(dop, role), roles[view_of[role]]); self._views.append(v)
+                            else:
+                                rtc.create_var_with_dims(v, deconv_role_dims(dop, role)); self._vars.append(v)
+                                rtc.copy_nda_to_var(v, np.full(deconv_role_dims(dop, role).sizes, 1.0 if role == "ones" else 0.0, np.float32))
+                            roles[role] = v
+                        am[an] = RtcArg.var(roles[role])
+                    self.fwd_calls.append(FwdCall(op.tag if ci == 0 else f"{op.tag}.{ci}", RtcFuncCall(gen_fn, am), fn, dop.flops() if ci == 0 else 0))
+            elif op.type == "Crop":            # hip_crop: the window of bots[0]; bots[1] gives only the size
+                fop = add_bck_op_annotations(cp.crop_op(op), self.op_tune)[0]
+                gen_fn = f"hip_crop__{cp.name}_{op.tag}"
+                rtc.compile([RtcFuncInfo(gen_fn, "", [a for a, _ in NATIVE_ARGS["hip_crop"]], fop)]); self._funcs.append(gen_fn)
+                self.fwd_calls.append(FwdCall(op.tag, RtcFuncCall(gen_fn, {"in": RtcArg.var(vn(op.bot)), "out": RtcArg.var(op.top)}), "hip_crop"))
             elif op.type in AFFINE_TYPES:      # the first op of a BatchNorm / Scale run: the whole run (and the ReLU behind it) as one native call, in place
                 r = run_of[op.tag]
                 fop = chan_affine_func_op(cp.nodes[op.top], int(r["relu"] is not None))
@@ -1465,8 +1563,9 @@ class ConvPipeFwd:
             rtc.graph_destroy(self._graph); self._graph = None
         for f in self._funcs:
             rtc.release_func(f)
-        for v in self._vars:
+        for v in self._views + self._vars:
             rtc.release_var(v)
+        self._views = []
         self._funcs, self._vars, self.fwd_calls, self._grp_params, self.groups = [], [], [], [], []
         self._km_params, self._affine_params, self._conv_folds, self._res_nodes = [], [], [], {}
         self.fused_residuals = {"folded": [], "unfolded": {}}

@@ -653,6 +653,7 @@ struct cpu_compute_t : public rtc_compute_t {
       if (f->family == kFamData) (void)data_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamLoss) (void)loss_op_of_op(fi.op);   // (likewise)
       if (f->family == kFamConvGrp) (void)conv_grp_geom_of_op(fi.op, f->member);   // (likewise: the group count and the geometry it needs)
+      if (f->family == kFamDeconv) (void)deconv_geom_of_op(fi.op, f->member);   // (likewise: no group, no fused ReLU, the geometry)
       if (f->family == kFamBckOp) {
         if (!f->of_type(fi.op.get_type())) rt_err(fn + ": a function of op type " + f->types[0] + ", not " + fi.op.get_type());
         bck_op_args_t const a = bck_op_args(*f, fi.op);
@@ -870,6 +871,47 @@ struct cpu_compute_t : public rtc_compute_t {
     }
   }
 
+  // the Deconvolution family (hip_deconv, hip_deconv_bck_in, hip_deconv_bck_biases, hip_deconv_bck_filts): the functions ARE the ungrouped loops above with the
+  // operands' roles exchanged (native_funcs.h: deconv_geom_of_op) -- no second set of loops.  x is the geometry of the convolution OC -> C whose input plane is the
+  // layer's out and whose output plane is the layer's in.  Every var has exactly the dims the op gives its arg
+  void run_deconv(native_func_t const &f, op_base_t const &op, map_str_rtc_arg_t const &am) {
+    string const fn = f.name;
+    deconv_geom_t const dg = deconv_geom_of_op(op, f.member);
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    auto var_ptr = [&](char const *an) -> float * {
+      string const vn = var_of(am, an); dims_t const vd = get_var_dims(vn); need_float(vd, an);
+      if (!(vd == op.get_dims(an))) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + ", the op says " + op.get_dims(an).pretty_str());
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      return (float *)must_find(vis, vn).buf.get();
+    };
+    conv_geom_c x; memset(&x, 0, sizeof(x));
+    x.B = dg.B; x.C = dg.OC; x.H = dg.OH; x.W = dg.OW; x.OC = dg.C; x.KH = dg.KH; x.KW = dg.KW; x.SY = dg.SY; x.SX = dg.SX; x.PY = dg.PY; x.PX = dg.PX; x.OH = dg.H; x.OW = dg.W; x.relu = false;
+    if (f.member == kDeconvBckBiases) {   // hip_bconv_biases on out_grad_loss, unchanged: its loop reads the image count, the channels and the plane of out_grad_loss
+      conv_geom_c b; memset(&b, 0, sizeof(b)); b.B = dg.B; b.OC = dg.OC; b.OH = dg.OH; b.OW = dg.OW;
+      float const *ogl = var_ptr("out_grad_loss");
+      bconv_biases(ogl, var_ptr("biases_grad_loss"), b);
+      return;
+    }
+    auto si = am.find("stride"), pi = am.find("in_pad");
+    if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
+    if (!(si->second.get_dims(*this) == op.get_dims("stride")) || !(pi->second.get_dims(*this) == op.get_dims("in_pad"))) rt_err(fn + ": stride / in_pad args disagree with the op");
+    if (f.member == kDeconvFwd) {   // hip_bconv_in on (filts := filts, out_grad_loss := in) -> acc; out = acc + biases[oc], one fp32 add
+      float const *filts = var_ptr("filts"), *biases = var_ptr("biases"), *in = var_ptr("in"); float *out = var_ptr("out");
+      bconv_in(filts, in, out, x);
+      long const OHW = (long)dg.OH * dg.OW;
+#pragma omp parallel for schedule(static)
+      for (long pl = 0; pl < (long)dg.B * dg.OC; ++pl) { float const b = biases[pl % dg.OC]; float *o = out + pl * OHW; for (long e = 0; e < OHW; ++e) o[e] = o[e] + b; }
+    } else if (f.member == kDeconvBckIn) {   // hip_conv on (filts read as out_chan=C:in_chan=OC, C biases of +0, in := out_grad_loss), no ReLU
+      float const *filts = var_ptr("filts"), *ogl = var_ptr("out_grad_loss"); float *igl = var_ptr("in_grad_loss");
+      std::vector<float> const zeros((size_t)dg.C, 0.f);
+      conv(filts, zeros.data(), ogl, igl, x);
+    } else {   // hip_bconv_filts on (in := out_grad_loss, out_grad_loss := in)
+      float const *in = var_ptr("in"), *ogl = var_ptr("out_grad_loss"); float *fgl = var_ptr("filts_grad_loss");
+      bconv_filts(ogl, in, fgl, x);
+    }
+  }
+
   static float op_f32(op_base_t const &op, string const &an) {
     p_nda_t const &n = op.get(an);
     if (n->dims.tn != "float" || n->dims.sz() != 0 || !n->rp) rt_err("op: '" + an + "' is not a float scalar");
@@ -954,6 +996,22 @@ struct cpu_compute_t : public rtc_compute_t {
       uint32_t const relu = op.get_u32("relu");
       if (relu > 1) rt_err(fn + ": relu must be 0 | 1");
       chan_affine(in[0], in[1], in[2], out[0], n_img, (long)i4.dsz("chan"), (long)i4.dsz("y") * i4.dsz("x"), relu != 0);
+    } else if (f.member == kOpCrop || f.member == kOpCropBck) {   // the window of the op's offset; the gradient writes +0 outside it
+      bool const fwd = f.member == kOpCrop;
+      dims_t const &big = op.get_dims(fwd ? "in" : "in_grad_loss"), &win = op.get_dims(fwd ? "out" : "out_grad_loss"), &off = op.get_dims("offset");
+      if (big.sz() != 4 || win.sz() != 4 || off.sz() != 2 || big.dims(0) != win.dims(0) || big.dims(1) != win.dims(1)) rt_err(fn + ": plane and window must be img:chan:y:x tensors of equal img / chan, offset y:x");
+      long const H = big.dims(2), W = big.dims(3), OH = win.dims(2), OW = win.dims(3), oy = off.dsz("y"), ox = off.dsz("x");
+      if (oy + OH > H || ox + OW > W)
+        rt_err(fn + ": offset (" + std::to_string(oy) + ", " + std::to_string(ox) + ") + window (" + std::to_string(OH) + ", " + std::to_string(OW) + ") exceeds the plane (" + std::to_string(H) + ", " + std::to_string(W) + ")");
+      long const planes = n_img * (long)big.dims(1);
+#pragma omp parallel for schedule(static)
+      for (long pl = 0; pl < planes; ++pl) {
+        if (fwd) { for (long y = 0; y < OH; ++y) for (long x = 0; x < OW; ++x) out[0][(pl * OH + y) * OW + x] = in[0][(pl * H + y + oy) * W + x + ox]; }
+        else for (long y = 0; y < H; ++y) for (long x = 0; x < W; ++x) {
+          bool const inside = y >= oy && y < oy + OH && x >= ox && x < ox + OW;
+          out[0][(pl * H + y) * W + x] = inside ? in[0][(pl * OH + y - oy) * OW + x - ox] : 0.0f;
+        }
+      }
     } else if (f.member == kOpConcat || f.member == kOpSplit) {
       bool const cat = f.member == kOpConcat;
       dims_t const &i4 = op.get_dims("in"), &o4 = op.get_dims("out");
@@ -1172,6 +1230,7 @@ struct cpu_compute_t : public rtc_compute_t {
     else if (f.family == kFamBckOp) run_bck_op(f, fi.op, am);
     else if (f.family == kFamBconv) run_bck(f, fi.op, am);
     else if (f.family == kFamConvGrp) run_conv_grp(f, fi.op, am);
+    else if (f.family == kFamDeconv) run_deconv(f, fi.op, am);
     else if (f.family == kFamSgemm) {
       string const an = var_of(am, "a"), bn = var_of(am, "b"), cn = var_of(am, "c");
       dims_t const a = get_var_dims(an), b = get_var_dims(bn), c = get_var_dims(cn);

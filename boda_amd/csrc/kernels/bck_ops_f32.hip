@@ -63,10 +63,13 @@
 //     START FROM slab 0's value -- no +0 in front, so one slab is a copy and keeps a -0
 //   * the slab count is a loop bound: one specialisation for every device count.  A thread owns one quad or one tail element, reads it from every slab and then
 //     stores: out may be slab 0.  n4 = 0 unless p0, out and the stride are all 16-byte aligned
+// OP 15 bodahip_crop / OP 16 bodahip_crop_bck  (this backend's own: Caffe's Crop at axis 2 and its gradient)   in -> out  /  out_grad_loss -> in_grad_loss
+//   * out[i,c,y,x] = in[i,c,y + PY,x + PX]: the OH x OW window at offset (PY, PX) of the H x W plane; one thread per window element
+//   * in_grad_loss[i,c,y,x] = out_grad_loss[i,c,y - PY,x - PX] inside the window and +0 outside it: one thread per plane element, every element written
 // OP 9 .. 12 take float4 over the first n4 quads and scalars over the tail, like OP 5; the host sets n4 = 0 unless every pointer (11, 12: every per-image run) is
 // 16-byte aligned.  Quads never straddle a run: 11 / 12 use them only when run, wide and off are multiples of 4.
 //
-// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN | 2, 4: [ZINP] | 10: [SEEDVAR] | 13: RELU | 14: none.  Host side: plan_bck_op / plan_shard_sum (native_plan.cc), native_kernels.cc.
+// -D parameters: KNAME OP, then  1, 2: H W OH OW KH KW SY SX PY PX AVG | 3, 4: LS CB | 9: NIN | 2, 4: [ZINP] | 10: [SEEDVAR] | 13: RELU | 14: none | 15, 16: H W OH OW PY PX.  Host side: plan_bck_op / plan_shard_sum (native_plan.cc), native_kernels.cc.
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -395,6 +398,27 @@ extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) 
   }
 }
 
+#elif OP == 15
+extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) {
+  long const id = (long)blockIdx.x * 256 + threadIdx.x;   // one element of the window
+  if (id >= p.n) return;
+  int const x = (int)(id % OW), y = (int)((id / OW) % OH);
+  long const plane = id / (OW * OH);
+  p.o0[id] = p.p0[(plane * H + (y + PY)) * W + (x + PX)];
+}
+
+#elif OP == 16
+extern "C" __global__ __launch_bounds__(256) void KNAME(bck_ops_args_t const p) {
+  long const id = (long)blockIdx.x * 256 + threadIdx.x;   // one element of the plane
+  if (id >= p.n) return;
+  int const x = (int)(id % W) - PX, y = (int)((id / W) % H) - PY;
+  long const plane = id / (W * H);
+  bool const inside = (unsigned)x < (unsigned)OW && (unsigned)y < (unsigned)OH;
+  float v = 0.0f;
+  if (inside) v = p.p0[(plane * OH + y) * OW + x];
+  p.o0[id] = v;
+}
+
 #else
-#error "bck_ops_f32.hip: -DOP=1..14"
+#error "bck_ops_f32.hip: -DOP=1..16"
 #endif

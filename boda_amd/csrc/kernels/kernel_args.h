@@ -326,6 +326,20 @@ struct conv_grp_args_t {
 static_assert(sizeof(conv_grp_args_t) == 96 && __builtin_offsetof(conv_grp_args_t, B) == 32 && __builtin_offsetof(conv_grp_args_t, n) == 64 &&
               __builtin_offsetof(conv_grp_args_t, a_bytes) == 72 && __builtin_offsetof(conv_grp_args_t, ws) == 88, "conv_grp_args_t layout");
 
+// kernels/deconv_f32.hip: a Deconvolution and its data / filter gradients (hip_deconv, hip_deconv_bck_in, hip_deconv_bck_filts); channels and kernel are -D constants
+struct deconv_args_t {
+  float const *a; float const *b; float const *bias; float *d;   // forward: a = filts, b = in, bias = biases, d = out; data gradient: a = filts, b = out_grad_loss,
+                                                                 // d = in_grad_loss; filter gradient: a = out_grad_loss, b = in, d = filts_grad_loss
+  int B, H, W, OH, OW;          // images, the small map, the large map
+  int kt_per;                   // filter gradient: K steps per slice
+  int zs, per;                  // forward: chunks of a row phase's work, items (img, row, quad of x) per chunk
+  long n;                       // data gradient: outputs; filter gradient and its slab sum: elements of filts_grad_loss
+  unsigned a_bytes, b_bytes, d_bytes, ksl;   // ksl: the slab sum: slabs to add
+  float *ws;                    // the filter gradient with K slices: the call's slabs, [slice][filts_grad_loss's elements]
+};
+static_assert(sizeof(deconv_args_t) == 96 && __builtin_offsetof(deconv_args_t, B) == 32 && __builtin_offsetof(deconv_args_t, n) == 64 &&
+              __builtin_offsetof(deconv_args_t, a_bytes) == 72 && __builtin_offsetof(deconv_args_t, ws) == 88, "deconv_args_t layout");
+
 #pragma pop_macro("CH")
 #pragma pop_macro("CIN")
 #pragma pop_macro("COH")

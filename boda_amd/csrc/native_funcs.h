@@ -10,13 +10,14 @@
 namespace bodahip {
 
 // the family (func_family_t of rtc_types.h) selects the handler (native_run.cc, native_kernels.cc: check_compile_time); handlers switch on the member, never on the name
-inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf", "loss", "conv_grp"};
-// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform.  kFamLoss: 1 fwd | 2 norm | 3 bck (loss_op_t::kind).  kFamConvGrp: 1 fwd | 2 bck_in | 3 bck_filts
+inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf", "loss", "conv_grp", "deconv"};
+// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform.  kFamLoss: 1 fwd | 2 norm | 3 bck (loss_op_t::kind).  kFamConvGrp: 1 fwd | 2 bck_in | 3 bck_filts.  kFamDeconv: 1 fwd | 2 bck_in | 3 bck_biases | 4 bck_filts
 enum { kConvF32 = 0, kConvAlias = 1, kConvBf16 = 2, kConvWinograd = 3 };            // (the alias: hip_conv's contract without its fused pooling and filts_km)
 enum { kBconvIn = 1, kBconvBiases = 2, kBconvFilts = 3, kBconvFiltsBiases = 4 };   // (4 is opt-in: never one of the bare op's three calls)
 enum { kConvGrpFwd = 1, kConvGrpBckIn = 2, kConvGrpBckFilts = 3 };                  // (a grouped convolution and its data / filter gradients; the bias gradient knows no groups)
+enum { kDeconvFwd = 1, kDeconvBckIn = 2, kDeconvBckBiases = 3, kDeconvBckFilts = 4 };   // (a Deconvolution and its three gradients in BckConv's call order; the bias gradient is hip_bconv_biases' sum under this family's op type)
 enum { kOpPoolYx = 1, kOpSpreading = 2, kOpLrnSb = 3, kOpBckLrn = 4, kOpZeroIfNonPos = 5, kOpSoftmax = 6, kOpSmGradAndLoss = 7, kOpSumLossOverImgs = 8, kOpReduce = 9,
-       kOpDropout = 10, kOpConcat = 11, kOpSplit = 12, kOpChanAffine = 13 };
+       kOpDropout = 10, kOpConcat = 11, kOpSplit = 12, kOpChanAffine = 13, kOpCrop = 15, kOpCropBck = 16 };   // (14 is bodahip_shard_sum, which no function names)
 
 enum arg_kind_t { kIn, kOut, kInOut, kRef, kVal };   // kVal: a by-value scalar of the CALL
 inline constexpr char const *kArgKindNames[] = {"IN", "OUT", "INOUT", "REF", "VAL"};
@@ -69,7 +70,8 @@ inline constexpr char kWhyBnSums[] = "(a training BatchNorm's per-channel sums) 
 inline constexpr char kWhyBnfOneDevice[] = "(a BatchNorm on its running pair, the hip_bnf_* family) takes vars of exactly its op's dims, not img shards, and hip_bnf_bck sums over the images of the WHOLE batch, which would need a cross-device reduction; frozen statistics on several devices are out of scope";
 inline constexpr char kWhyLossOneDevice[] = "(the full softmax loss, the hip_softmax_loss_* / hip_loss_norm family) counts the pels that are not ignored and sums loss_per_pel over the WHOLE batch, which would need a cross-device reduction, and takes vars of exactly its op's dims, not img shards; a loss with a LossSpec on several devices is out of scope";
 inline constexpr char kWhyConvGrpOneDevice[] = "(a grouped convolution, the hip_conv_grp / hip_bconv_in_grp / hip_bconv_filts_grp family) takes vars of exactly its op's dims, not img shards, and hip_bconv_filts_grp sums over the images of the WHOLE batch, which would need a cross-device reduction; grouped layers on several devices are out of scope";
-inline constexpr char const *why_one_device(func_family_t family) { return family == kFamLoss ? kWhyLossOneDevice : family == kFamConvGrp ? kWhyConvGrpOneDevice : kWhyBnfOneDevice; }
+inline constexpr char kWhyDeconvOneDevice[] = "(a Deconvolution, the hip_deconv / hip_deconv_bck_in / hip_deconv_bck_filts / hip_deconv_bck_biases family) takes vars of exactly its op's dims, not img shards, and its filter and bias gradients sum over the images of the WHOLE batch, which would need a cross-device reduction; Deconvolution layers on several devices are out of scope";
+inline constexpr char const *why_one_device(func_family_t family) { return family == kFamLoss ? kWhyLossOneDevice : family == kFamConvGrp ? kWhyConvGrpOneDevice : family == kFamDeconv ? kWhyDeconvOneDevice : kWhyBnfOneDevice; }
 inline constexpr native_func_t kNativeFuncs[] = {
   // sgemm, a:K:M b:K:N c:M:N (test/rtc/cublas_sgemm.cucl:1-4); Convolution in reference layout (test/rtc/cudnn_conv.cucl:1-7)
   {"hip_sgemm", kFamSgemm, 0, nullptr, {"sgemm"}, {{"a", kIn}, {"b", kIn}, {"c", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
@@ -113,6 +115,10 @@ inline constexpr native_func_t kNativeFuncs[] = {
   {"hip_concat", kFamBckOp, kOpConcat, "bodahip_concat", {"Concat"}, {{"in", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
   {"hip_split", kFamBckOp, kOpSplit, "bodahip_split", {"Split"}, {{"in", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
   {"hip_chan_affine", kFamBckOp, kOpChanAffine, "bodahip_chan_affine", {"ChanAffine"}, {{"in", kIn}, {"a", kIn}, {"b", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},   // (a and b, one value per channel, are whole on every device)
+  // Caffe's Crop at axis 2 and its gradient (this backend's own): out = the op's offset window of in; in_grad_loss = out_grad_loss inside the window and +0 outside it,
+  // every element written.  The offsets ride in the op (`offset`, dims y:x).  Independent per image
+  {"hip_crop", kFamBckOp, kOpCrop, "bodahip_crop", {"Crop"}, {{"in", kIn}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
+  {"hip_crop_bck", kFamBckOp, kOpCropBck, "bodahip_crop_bck", {"BckCrop"}, {{"out_grad_loss", kIn}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
   // the solver's update (this backend's own): params, gradients and momentum history are replicated vars
   {"hip_sgd_update", kFamSgd, 0, nullptr, {"SgdUpdate"}, {{"hyper", kIn}}, {}, kVarWghInFront, 0, {}, kBeHip | kBeCpu, kReplicatedOnly},
   // the solvers beyond plain SGD, global-norm clipping (this backend's own; kernels/solver_update_f32.hip): replicated vars throughout
@@ -150,6 +156,13 @@ inline constexpr native_func_t kNativeFuncs[] = {
   {"hip_conv_grp", kFamConvGrp, kConvGrpFwd, nullptr, {"Convolution"}, {BODAHIP_CONV_ARGS}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   {"hip_bconv_in_grp", kFamConvGrp, kConvGrpBckIn, nullptr, {"BckConv"}, {{"filts", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   {"hip_bconv_filts_grp", kFamConvGrp, kConvGrpBckFilts, nullptr, {"BckConv"}, {{"in", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"filts_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  // a Deconvolution / BckDeconv (this backend's own: the reference knows the op type and its shapes but has no function for it; kernels/deconv_f32.hip).  in is
+  // img:chan=C:y:x, filts in_chan=C:out_chan=OC:y:x (Caffe's blob), out img:OC:(H-1)*SY+KH-2*PY:(W-1)*SX+KW-2*PX.  Each function is an existing one with the operands'
+  // roles exchanged (deconv_geom_of_op below); no group, no fused ReLU, no flag; one device only (why_one_device).  In front of the loss rows, like the grouped rows
+  {"hip_deconv", kFamDeconv, kDeconvFwd, nullptr, {"Deconvolution"}, {BODAHIP_CONV_ARGS}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  {"hip_deconv_bck_in", kFamDeconv, kDeconvBckIn, nullptr, {"BckDeconv"}, {{"filts", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  {"hip_deconv_bck_filts", kFamDeconv, kDeconvBckFilts, nullptr, {"BckDeconv"}, {{"in", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"filts_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  {"hip_deconv_bck_biases", kFamDeconv, kDeconvBckBiases, nullptr, {"BckDeconv"}, {{"out_grad_loss", kIn}, {"biases_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   // the full SoftmaxWithLoss (this backend's own; kernels/loss_f32.hip): what a head with a LossSpec lowers to -- loss_weight, ignore_label, planes, the four
   // normalisers.  hip_softmax_loss_bck reads s = weight / Z from loss_state on the device.  One device only (why_one_device).  In front of the data and eval rows,
   // which stay the table's last four
@@ -234,6 +247,41 @@ inline conv_grp_geom_t conv_grp_geom_of_op(op_base_t const &op, int member) {
   if (member == kConvGrpBckIn && !(op.get_dims("in_grad_loss") == in)) rt_err(fn + ": in_grad_loss must have the dims of in");
   if (member == kConvGrpBckFilts && !(op.get_dims("filts_grad_loss") == f)) rt_err(fn + ": filts_grad_loss must have the dims of filts");
   uint64_t const in_b = 4ull * g.B * g.C * g.H * g.W, out_b = 4ull * g.B * g.OC * g.OH * g.OW, f_b = 4ull * g.OC * g.CG * g.KH * g.KW;
+  if (in_b >= 0x7ffffff0ull || out_b >= 0x7ffffff0ull || f_b >= 0x7ffffff0ull) unsup_err(fn + ": tensors of 2 GiB or more (32-bit offsets)");
+  return g;
+}
+
+// the Deconvolution family (kFamDeconv): what both backends read from the function's op, and every refusal that needs the op alone.  The geometry is the LAYER's:
+// in B x C x H x W (the small map), filts C x OC x KH x KW, out / out_grad_loss B x OC x OH x OW with OH = (H-1)*SY + KH - 2*PY.  The functions are, term for term,
+//   forward          hip_bconv_in     on (filts := filts, out_grad_loss := in) -> acc; out = acc + biases[oc], one fp32 add
+//   data gradient    hip_conv         on (filts := filts read as out_chan=C:in_chan=OC, biases := C values of +0, in := out_grad_loss), no ReLU
+//   filter gradient  hip_bconv_filts  on (in := out_grad_loss, out_grad_loss := in): K = B*H*W of the small map
+//   bias gradient    hip_bconv_biases on out_grad_loss
+// of the convolution OC -> C whose input plane is OH x OW and whose output plane is H x W
+struct deconv_geom_t { int B, C, H, W, OC, KH, KW, SY, SX, PY, PX, OH, OW; };
+inline deconv_geom_t deconv_geom_of_op(op_base_t const &op, int member) {
+  native_func_t const *row = find_native_func(kFamDeconv, member);
+  string const fn = row ? row->name : "hip_deconv";
+  if (row && !row->of_type(op.get_type())) rt_err(fn + ": a function of op type " + row->types[0] + ", not " + op.get_type());
+  bool const fwd = member == kDeconvFwd;
+  if (op.has("group") && op.get_u32("group") != 1) unsup_err(fn + ": the op carries group=" + std::to_string(op.get_u32("group")) + ": a Deconvolution with group > 1 is out of scope");
+  if (op.has("conv_has_relu") && op.get_u32("conv_has_relu") != 0) unsup_err(fn + ": the op carries conv_has_relu=1: a Deconvolution has no fused ReLU");
+  dims_t const &f = op.get_dims("filts"), &in = op.get_dims("in"), &out = op.get_dims(fwd ? "out" : "out_grad_loss"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
+  if (f.sz() != 4 || in.sz() != 4 || out.sz() != 4 || st.sz() != 2 || pad.sz() != 2 || f.tn != "float" || in.tn != "float" || out.tn != "float" || f.names(0) != "in_chan" || f.names(1) != "out_chan")
+    rt_err(fn + ": float filts in_chan:out_chan:y:x, in / out img:chan:y:x, stride / in_pad y:x");
+  deconv_geom_t g;
+  g.B = (int)in.dsz("img"); g.C = (int)in.dsz("chan"); g.H = (int)in.dsz("y"); g.W = (int)in.dsz("x"); g.OC = (int)f.dsz("out_chan"); g.KH = (int)f.dsz("y"); g.KW = (int)f.dsz("x");
+  g.SY = (int)st.dsz("y"); g.SX = (int)st.dsz("x"); g.PY = (int)pad.dsz("y"); g.PX = (int)pad.dsz("x"); g.OH = (int)out.dsz("y"); g.OW = (int)out.dsz("x");
+  if (f.dsz("in_chan") != (uint32_t)g.C) rt_err(fn + ": filts.in_chan=" + std::to_string(f.dsz("in_chan")) + " is not in.chan=" + std::to_string(g.C));
+  if (g.B < 1 || g.C < 1 || g.OC < 1 || g.H < 1 || g.W < 1 || g.KH < 1 || g.KW < 1 || g.SY < 1 || g.SX < 1 || g.PY < 0 || g.PX < 0 || g.OH < 1 || g.OW < 1 || g.SY > 32 || g.SX > 32 || g.KH > 64 || g.KW > 64)
+    unsup_err(fn + ": unsupported geometry (kernels of at most 64 x 64, strides of at most 32)");
+  if (out.dsz("img") != (uint32_t)g.B || out.dsz("chan") != (uint32_t)g.OC || (g.H - 1) * g.SY + g.KH - 2 * g.PY != g.OH || (g.W - 1) * g.SX + g.KW - 2 * g.PX != g.OW)
+    rt_err(fn + ": " + (fwd ? "out" : "out_grad_loss") + " dims " + out.pretty_str() + " are not img:out_chan:(y-1)*stride+kern-2*pad of in " + in.pretty_str());
+  if (fwd && op.get_dims("biases").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases must hold out_chan values");
+  if (member == kDeconvBckIn && !(op.get_dims("in_grad_loss") == in)) rt_err(fn + ": in_grad_loss must have the dims of in");
+  if (member == kDeconvBckFilts && !(op.get_dims("filts_grad_loss") == f)) rt_err(fn + ": filts_grad_loss must have the dims of filts");
+  if (member == kDeconvBckBiases && op.get_dims("biases_grad_loss").dims_prod() != (uint64_t)g.OC) rt_err(fn + ": biases_grad_loss must hold out_chan values");
+  uint64_t const in_b = 4ull * g.B * g.C * g.H * g.W, out_b = 4ull * g.B * g.OC * g.OH * g.OW, f_b = 4ull * g.OC * g.C * g.KH * g.KW;
   if (in_b >= 0x7ffffff0ull || out_b >= 0x7ffffff0ull || f_b >= 0x7ffffff0ull) unsup_err(fn + ": tensors of 2 GiB or more (32-bit offsets)");
   return g;
 }

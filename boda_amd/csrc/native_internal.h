@@ -99,7 +99,11 @@ plan_t plan_conv_grp(conv_grp_geom_t const &g, int member, int num_cus, string c
 plan_t plan_conv_grp_slab_sum(plan_t const &main);   // the second launch of a sliced direct filter gradient
 bool conv_grp_has_slab_sum(plan_t const &p);
 long conv_grp_threads(conv_grp_geom_t const &g, int member, tile_cfg_t const &c, uint32_t *grid, uint32_t *block);   // -> the kernel's p.n; *grid workgroups of *block threads
-long bconv_in_tiles(conv_geom_t const &g, int BJ);                                   // pel tiles over all SY x SX phases (the kernel's walk)
+plan_t plan_deconv(deconv_geom_t const &g, int member, int num_cus, string const &tile);   // the Deconvolution family (kernels/deconv_f32.hip); member: kDeconvFwd | kDeconvBckIn | kDeconvBckFilts
+plan_t plan_deconv_slab_sum(plan_t const &main);     // the second launch of a sliced filter gradient
+bool deconv_has_slab_sum(plan_t const &p);
+void deconv_grid(deconv_geom_t const &g, int member, tile_cfg_t const &c, int num_cus, uint32_t *grid, int *zs, int *per);   // *grid workgroups of 256 threads; forward: *zs chunks of *per items
+long bconv_in_tiles(conv_geom_t const &g, int BJ);                                  // pel tiles over all SY x SX phases (the kernel's walk)
 std::vector<char> compile_plan(plan_t const &p, string const &arch, string *log);
 void ensure_ws(native_kernels_t::impl_t *impl, native_host_t *host, size_t need);
 void call_ws_make_room(native_kernels_t::impl_t *impl, native_host_t *host, size_t need);

@@ -85,6 +85,14 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
       (void)get_kernel(impl, host, gp);
       if (conv_grp_has_slab_sum(gp)) (void)get_kernel(impl, host, plan_conv_grp_slab_sum(gp)); }
     break;
+  case kFamDeconv:   // likewise: the op must be whole, the tile one the family has, the code objects built now
+    { deconv_geom_t const dg = deconv_geom_of_op(fi.op, f->member);
+      if (f->member == kDeconvBckBiases) { (void)get_kernel(impl, host, plan_bconv_biases()); break; }
+      auto const ht = fi.op.str_vals.find("hip_tile");
+      plan_t const dp = plan_deconv(dg, f->member, host->nh_num_cus(), (ht != fi.op.str_vals.end() && !ht->second.empty()) ? ht->second : tune_of(impl, "conv_tile"));
+      (void)get_kernel(impl, host, dp);
+      if (deconv_has_slab_sum(dp)) (void)get_kernel(impl, host, plan_deconv_slab_sum(dp)); }
+    break;
   case kFamBconv:   // BckConv's gradients: the op must carry the geometry
     for (char const *an : {"in", "filts", "out_grad_loss", "stride", "in_pad"}) (void)fi.op.get_dims(an);
     (void)op_bf16_operands(fi.op);   // (str_val hip_operands: refused at compile where the function has no bf16-operand form)
@@ -96,6 +104,7 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
     if (f->member == kOpDropout) (void)fi.op.get("dropout_ratio");
     if (f->member == kOpConcat || f->member == kOpSplit) (void)fi.op.get_u32(f->member == kOpConcat ? "ocix" : "icix");
     if (f->member == kOpChanAffine) (void)fi.op.get_u32("relu");
+    if (f->member == kOpCrop || f->member == kOpCropBck) (void)fi.op.get_dims("offset");
     if (a.refs) for (char const *an : {"kern_sz", "stride", "in_pad"}) (void)fi.op.get_dims(an);
   } }
   return f;
@@ -829,6 +838,43 @@ void native_kernels_t::conv_grp(int member, conv_grp_geom_t const &g, float cons
   int const TY = (g.KH + g.SY - 1) / g.SY, TX = (g.KW + g.SX - 1) / g.SX;
   last_launch.flops = member == kConvGrpBckIn ? 2.0 * g.B * g.H * g.W * g.C * ((double)g.OCG * TY * TX) : 2.0 * K * g.OC * ((double)g.CG * g.KH * g.KW);
   last_launch.algo_bytes = (double)f_b + in_b + out_b + (member == kConvGrpFwd ? 4.0 * g.OC : 0.0);
+}
+void native_kernels_t::deconv(int member, deconv_geom_t const &g, float const *a, float const *b, float const *bias, float *d) {
+  plan_t const p = plan_deconv(g, member, host->nh_num_cus(), tune_of(impl, "conv_tile"));
+  kernel_t &k = get_kernel(impl, host, p);
+  deconv_args_t da; memset(&da, 0, sizeof(da));
+  da.a = a; da.b = b; da.bias = bias; da.d = d;
+  da.B = g.B; da.H = g.H; da.W = g.W; da.OH = g.OH; da.OW = g.OW;
+  unsigned const f_b = (unsigned)(4ull * g.C * g.OC * g.KH * g.KW), in_b = (unsigned)(4ull * g.B * g.C * g.H * g.W), out_b = (unsigned)(4ull * g.B * g.OC * g.OH * g.OW);
+  da.a_bytes = member == kDeconvBckFilts ? out_b : f_b; da.b_bytes = member == kDeconvBckIn ? out_b : in_b; da.d_bytes = member == kDeconvFwd ? out_b : member == kDeconvBckIn ? in_b : f_b;
+  long const K = (long)g.B * g.H * g.W, nkt = (K + p.cfg.BK - 1) / p.cfg.BK;
+  da.kt_per = (int)((nkt + p.cfg.SPLITK - 1) / p.cfg.SPLITK);
+  da.n = member == kDeconvBckIn ? (long)g.B * g.C * g.H * g.W : (long)g.C * g.OC * g.KH * g.KW;
+  uint32_t grid = 0;
+  deconv_grid(g, member, p.cfg, host->nh_num_cus(), &grid, &da.zs, &da.per);
+  kernel_t *ks = nullptr;
+  if (deconv_has_slab_sum(p)) {   // the call's slab workspace, as hip_bconv_filts_grp keeps one: [slice][filts_grad_loss's elements], nothing to zero
+    ks = &get_kernel(impl, host, plan_deconv_slab_sum(p));
+    size_t const total = (size_t)p.cfg.SPLITK * f_b;
+    if (total >= (size_t(1) << 32)) unsup_err("hip_deconv_bck_filts: K-slice workspace too large");
+    string const key = "ksl:deconv:" + std::to_string((uintptr_t)a) + ":" + std::to_string((uintptr_t)b) + ":" + std::to_string((uintptr_t)d) + ":" + std::to_string(total);
+    auto it = impl->ktabs.find(key);
+    if (it == impl->ktabs.end()) {
+      if (host->nh_capturing()) rt_err("graph capture: the K-slice workspace of this call is not allocated yet -- run the call list once before capturing it");
+      void *dev = nullptr;
+      call_ws_make_room(impl, host, total);
+      hip_err_chk(hipMalloc(&dev, total), "hipMalloc(K-slice workspace)"); impl->call_ws_bytes += total;
+      it = impl->ktabs.emplace(key, dev).first;
+    }
+    da.ws = (float *)it->second; da.ksl = (unsigned)p.cfg.SPLITK;
+  }
+  void *params[] = {&da};
+  if (grid) hip_err_chk(host->nh_launch(k.func, grid, 1, 256, params), "hipModuleLaunchKernel(deconv)");
+  if (ks) hip_err_chk(host->nh_launch(ks->func, (uint32_t)((da.n + 255) / 256), 1, 256, params), "hipModuleLaunchKernel(deconv_slab_sum)");
+  last_launch.kernel = p.kname; last_launch.cfg = p.cfg; last_launch.grid = grid; last_launch.block = 256;
+  int const TYk = (g.KH + g.SY - 1) / g.SY, TXk = (g.KW + g.SX - 1) / g.SX;
+  last_launch.flops = member == kDeconvFwd ? 2.0 * g.B * g.OC * g.OH * g.OW * ((double)g.C * TYk * TXk) : 2.0 * K * g.C * ((double)g.OC * g.KH * g.KW);
+  last_launch.algo_bytes = (double)f_b + in_b + out_b + (member == kDeconvFwd ? 4.0 * g.OC : 0.0);
 }
 void native_kernels_t::bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g) {
   kernel_t &k = get_kernel(impl, host, plan_bconv_biases());

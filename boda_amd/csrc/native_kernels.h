@@ -153,6 +153,9 @@ struct native_kernels_t {
   // the grouped family (kernels/conv_grp_f32.hip) on raw device pointers.  member kConvGrpFwd: a = filts, b = in, bias = biases, d = out; kConvGrpBckIn: a = filts,
   // b = out_grad_loss, d = in_grad_loss; kConvGrpBckFilts: a = out_grad_loss, b = in, d = filts_grad_loss.  One launch, no workspace
   void conv_grp(int member, conv_grp_geom_t const &g, float const *a, float const *b, float const *bias, float *d);
+  // the Deconvolution family (kernels/deconv_f32.hip) on raw device pointers.  member kDeconvFwd: a = filts, b = in, bias = biases, d = out; kDeconvBckIn: a = filts,
+  // b = out_grad_loss, d = in_grad_loss; kDeconvBckFilts: a = out_grad_loss, b = in, d = filts_grad_loss (with K slices: slabs in the call's workspace, a second launch)
+  void deconv(int member, deconv_geom_t const &g, float const *a, float const *b, float const *bias, float *d);
   // the non-conv ops of the gradient pipe: ins / outs in the function's arg order (up to eight / two raw device pointers)
   // seed_word (dropout with g.seedvar): the device word added to g.seed
   void bck_op(bck_op_geom_t const &g, float const *const *ins, float *const *outs, uint32_t const *seed_word = nullptr);

@@ -1338,6 +1338,61 @@ long conv_grp_threads(conv_grp_geom_t const &g, int member, tile_cfg_t const &c,
   return n;
 }
 
+// ---- the Deconvolution family (kernels/deconv_f32.hip): the direct forms, one fmaf chain per output.  Nothing to choose for the forward and the data gradient; the
+// filter gradient's K = B*H*W (the small map) goes in KSL slices of whole BK steps where the outputs are few and K is long: slices until outputs x slices give the CUs
+// about 1024 threads each, every slice at least 2 K steps long; a power of two.  A seven-field tile "1x4xBKx2x2x1xKSL" forces BK (1..4096) and KSL (1..1024); any other
+// tile (a backend-wide or pipe-wide one written for hip_conv) is not this family's.  The launch reports BK / KSL as BIxBJxBK_wWIxWJ[_sKSL]
+plan_t plan_deconv(deconv_geom_t const &g, int member, int num_cus, string const &tile) {
+  native_func_t const *row = find_native_func(kFamDeconv, member);
+  if (!row || member == kDeconvBckBiases) rt_err("plan_deconv: no such member");
+  string const fn = row->name;
+  bool const filts = member == kDeconvBckFilts;
+  plan_t p; p.src = kSrc_deconv_f32;
+  tile_cfg_t &c = p.cfg;
+  c = tile_cfg_t(); c.BI = 1; c.BJ = member == kDeconvFwd ? 4 : 1; c.BK = 1; c.WI = 2; c.WJ = 2; c.MINW = 1; c.SPLITK = 1;
+  long const K = (long)g.B * g.H * g.W;
+  if (filts) {
+    c.BK = 32;
+    long const outs = (long)g.C * g.OC * g.KH * g.KW, nkt = (K + c.BK - 1) / c.BK;
+    long const want = std::min<long>(std::max<long>(1, (1024L * num_cus) / outs), std::max<long>(1, nkt / 2));
+    int ksl = 1; while (ksl * 2 <= want && ksl < 1024) ksl *= 2;
+    c.SPLITK = ksl;
+  }
+  if (std::count(tile.begin(), tile.end(), 'x') == 6) {
+    tile_cfg_t t;
+    if (!parse_tile(tile, t)) unsup_err(fn + ": bad tile '" + tile + "' (seven fields BIxBJxBKxWIxWJxMINWxKSL)");
+    if (t.BI != 1 || t.BJ != c.BJ || t.WI * t.WJ != 4 || t.MINW != 1 || t.BK < 1 || t.BK > 4096 || t.SPLITK < 1 || t.SPLITK > 1024 || (!filts && (t.BK != 1 || t.SPLITK != 1)))
+      unsup_err(fn + ": unsupported tile configuration " + t.str() + " (the direct forms: BI = 1, BJ = " + std::to_string(c.BJ) + ", four waves; BK 1..4096 and KSL 1..1024 for the filter gradient, 1 and 1 otherwise)");
+    c.BK = t.BK; c.WI = t.WI; c.WJ = t.WJ; c.SPLITK = t.SPLITK;
+  }
+  p.kname = member == kDeconvFwd ? "bodahip_deconv_direct" : member == kDeconvBckIn ? "bodahip_deconv_bck_in_direct" : "bodahip_deconv_bck_filts_direct";
+  p.defs = {"-DFUNC=" + std::to_string(member == kDeconvFwd ? 1 : member == kDeconvBckIn ? 2 : 3), "-DNIC=" + std::to_string(g.C), "-DNOC=" + std::to_string(g.OC), "-DKH=" + std::to_string(g.KH),
+            "-DKW=" + std::to_string(g.KW), "-DSY=" + std::to_string(g.SY), "-DSX=" + std::to_string(g.SX), "-DPY=" + std::to_string(g.PY), "-DPX=" + std::to_string(g.PX)};
+  if (filts) { p.defs.push_back("-DBK=" + std::to_string(c.BK)); p.defs.push_back("-DKSL=" + std::to_string(c.SPLITK)); }
+  return p;
+}
+// the second launch of a sliced filter gradient: the slabs of the call's workspace added in slice order
+plan_t plan_deconv_slab_sum(plan_t const &main) {
+  plan_t p = main; p.kname = "bodahip_deconv_bck_filts_slab_sum"; p.defs[0] = "-DFUNC=5";
+  return p;
+}
+bool deconv_has_slab_sum(plan_t const &p) { return p.kname == "bodahip_deconv_bck_filts_direct" && p.cfg.SPLITK > 1; }
+// -> *grid workgroups of 256 threads.  Forward: (out_chan, row phase, chunk) with *zs chunks of *per items (img, row of the phase, quad of x) each -- chunks until
+// the launch has about eight workgroups a CU, none shorter than one pass of the workgroup; data gradient: a thread per output; filter gradient: per output and slice
+void deconv_grid(deconv_geom_t const &g, int member, tile_cfg_t const &c, int num_cus, uint32_t *grid, int *zs, int *per) {
+  long wgs; *zs = 1; *per = 0;
+  if (member == kDeconvFwd) {
+    long const items = (long)g.B * ((g.OH + g.SY - 1) / g.SY) * ((g.OW + 3) / 4);   // of the longest phase
+    long const want = std::max<long>(1, (8L * num_cus + (long)g.OC * g.SY - 1) / ((long)g.OC * g.SY));
+    *zs = (int)std::max<long>(1, std::min<long>(want, (items + 255) / 256));
+    *per = (int)((items + *zs - 1) / *zs);
+    wgs = (long)g.OC * g.SY * *zs;
+  } else if (member == kDeconvBckIn) wgs = ((long)g.B * g.C * g.H * g.W + 255) / 256;
+  else wgs = ((long)g.C * g.OC * g.KH * g.KW * c.SPLITK + 255) / 256;
+  if (wgs >= (1L << 31)) unsup_err("the Deconvolution family: more than 2^31 workgroups");
+  *grid = (uint32_t)wgs;
+}
+
 // hip_bconv_filts_biases (kernels/bconv_fb_f32.hip): the same tile strings; both operands are staged k-major, so every thread owns one k offset (threads % BK == 0) and
 // whole rows AND columns ((threads / BK) divides BI and BJ); the LDS images are transposed with pitch BK + 1; K slices go to slabs summed by a second launch: 1..1024
 static void check_bconv_fb_cfg(tile_cfg_t const &c) {
@@ -1495,6 +1550,13 @@ bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {
     lim(in_e);
     D("RELU", g.relu);
     r.threads = (long)in_e; r.algo_bytes = 8.0 * in_e + 8.0 * g.C;   // (one thread per element at most: the launch counts quads where it may use them)
+  } else if (g.op == kOpCrop || g.op == kOpCropBck) {   // H x W: the plane the window is cut from; OH x OW: the window at (PY, PX)
+    if (g.C < 1 || g.H < 1 || g.W < 1 || g.OH < 1 || g.OW < 1) rt_err(what + ": empty tensor");
+    if (g.PY < 0 || g.PX < 0 || g.PY + g.OH > g.H || g.PX + g.OW > g.W)
+      rt_err(what + ": the window offset (" + std::to_string(g.PY) + ", " + std::to_string(g.PX) + ") + size (" + std::to_string(g.OH) + ", " + std::to_string(g.OW) + ") does not fit the plane (" + std::to_string(g.H) + ", " + std::to_string(g.W) + ")");
+    lim(in_e);
+    D("H", g.H); D("W", g.W); D("OH", g.OH); D("OW", g.OW); D("PY", g.PY); D("PX", g.PX);
+    r.threads = (long)(g.op == kOpCrop ? out_e : in_e); r.algo_bytes = 4.0 * (g.op == kOpCrop ? 2.0 * out_e : in_e + out_e);
   } else if (g.op == 6 || g.op == 7) {
     if (g.C < 1) rt_err(what + ": no channels");
     lim((double)g.B * g.C);

@@ -93,6 +93,16 @@ static bck_op_geom_t bck_op_geom_of_op(op_base_t const &op, native_func_t const 
     }
     g.B = in.dims(0); g.C = (int)in.dims(1); g.H = (int)in.dims(2); g.W = (int)in.dims(3); g.relu = (int)op.get_u32("relu");
     if (g.relu != 0 && g.relu != 1) rt_err(fn + ": relu must be 0 | 1");
+  } else if (g.op == kOpCrop || g.op == kOpCropBck) {   // the plane is in's resp. in_grad_loss's, the window out's resp. out_grad_loss's, at the op's offset
+    bool const fwd = g.op == kOpCrop;
+    dims_t const &big = op.get_dims(fwd ? "in" : "in_grad_loss"), &win = op.get_dims(fwd ? "out" : "out_grad_loss"), &off = op.get_dims("offset");
+    need_nchw(big, fn + (fwd ? ": in" : ": in_grad_loss")); need_nchw(win, fn + (fwd ? ": out" : ": out_grad_loss"));
+    if (win.dims(0) != big.dims(0) || win.dims(1) != big.dims(1)) rt_err(fn + ": the window " + win.pretty_str() + " differs from the plane's tensor " + big.pretty_str() + " in img / chan");
+    if (off.sz() != 2) rt_err(fn + ": offset must be y:x");
+    g.B = big.dims(0); g.C = (int)big.dims(1); g.H = (int)big.dims(2); g.W = (int)big.dims(3); g.OH = (int)win.dims(2); g.OW = (int)win.dims(3);
+    g.PY = (int)off.dsz("y"); g.PX = (int)off.dsz("x");
+    if ((long)g.PY + g.OH > g.H || (long)g.PX + g.OW > g.W)
+      rt_err(fn + ": offset (" + std::to_string(g.PY) + ", " + std::to_string(g.PX) + ") + window (" + std::to_string(g.OH) + ", " + std::to_string(g.OW) + ") exceeds the plane (" + std::to_string(g.H) + ", " + std::to_string(g.W) + ")");
   } else if (g.op == 10) {
     g.ratio = op_f32(op, "dropout_ratio"); g.n = (long)op.get_dims(op.has("inout") ? "inout" : "in").dims_prod();   // (the bare op carries in / out, its function the in-place arg inout)
   } else if (g.op == 11 || g.op == 12) {
@@ -272,6 +282,27 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     if (arch.empty()) return 0;
     size_t bytes = compile_plan(q, arch, &log).size();
     if (conv_grp_has_slab_sum(q)) bytes += compile_plan(plan_conv_grp_slab_sum(q), arch, &log).size();
+    return bytes;
+  } else if (fam == kFamDeconv) {   // (kernels/deconv_f32.hip: the direct forms, specialised by the geometry; a bare op: every function of its type)
+    std::vector<int> members;
+    if (member) members.push_back(member); else for (native_func_t const *r : of_t) members.push_back(r->member);
+    size_t bytes = 0; string desc;
+    for (int m : members) {
+      deconv_geom_t const dg = deconv_geom_of_op(op, m);
+      std::vector<plan_t> ps;
+      string d1;
+      if (m == kDeconvBckBiases) { ps.push_back(plan_bconv_biases()); d1 = ps[0].kname; }
+      else {
+        plan_t const q = plan_deconv(dg, m, num_cus, tile);
+        uint32_t grid = 0; int zs = 1, per = 0; deconv_grid(dg, m, q.cfg, num_cus, &grid, &zs, &per);
+        d1 = q.kname + " " + q.cfg.str() + " grid=" + std::to_string(grid); for (auto const &d : q.defs) d1 += " " + d;
+        ps.push_back(q);
+        if (deconv_has_slab_sum(q)) { ps.push_back(plan_deconv_slab_sum(q)); d1 += " | bodahip_deconv_bck_filts_slab_sum"; }
+      }
+      desc += (desc.empty() ? "" : " ; ") + d1;
+      if (!arch.empty()) for (plan_t const &q : ps) bytes += compile_plan(q, arch, &log).size();
+    }
+    if (plan_out) *plan_out = desc;
     return bytes;
   } else if (fam == kFamSgd) {   // (hip_sgd_update: one kernel, no specialisation by shape; the grid is the sum of the tensors' chunks)
     sgd_plan_t const sp = plan_sgd_update(sgd_op_of_op(op).elems);
@@ -732,6 +763,29 @@ struct native_kernels_t::call_t {
     else if (row.member == kConvGrpBckIn) { float *a = var_ptr("filts"), *b = var_ptr("out_grad_loss"); nk.conv_grp(row.member, g, a, b, nullptr, var_ptr("in_grad_loss")); }
     else { float *b = var_ptr("in"), *a = var_ptr("out_grad_loss"); nk.conv_grp(row.member, g, a, b, nullptr, var_ptr("filts_grad_loss")); }
   }
+  void run_deconv() {   // every var has exactly the dims the op gives its arg (one device: no img shards), and the call's vars are different ones
+    deconv_geom_t const g = deconv_geom_of_op(fi.op, row.member);
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    auto var_ptr = [&](char const *an) -> float * {
+      string const vn = var_of_op_dims(an);
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      return (float *)host->nh_var_ptr(vn);
+    };
+    if (row.member == kDeconvBckBiases) {
+      conv_geom_t cg; memset(&cg, 0, sizeof(cg)); cg.B = g.B; cg.OC = g.OC; cg.OH = g.OH; cg.OW = g.OW;
+      float *ogl = var_ptr("out_grad_loss");
+      nk.bconv_biases(ogl, var_ptr("biases_grad_loss"), cg);
+      return;
+    }
+    auto si = am.find("stride"), pi = am.find("in_pad");
+    if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
+    if (!(si->second.get_dims(host->nh_rtc()) == fi.op.get_dims("stride")) || !(pi->second.get_dims(host->nh_rtc()) == fi.op.get_dims("in_pad"))) rt_err(fn + ": stride / in_pad args disagree with the op");
+    tile_override_t const tov(impl, "conv_tile", fi.op);
+    if (row.member == kDeconvFwd) { float *a = var_ptr("filts"), *bias = var_ptr("biases"), *b = var_ptr("in"); nk.deconv(row.member, g, a, b, bias, var_ptr("out")); }
+    else if (row.member == kDeconvBckIn) { float *a = var_ptr("filts"), *b = var_ptr("out_grad_loss"); nk.deconv(row.member, g, a, b, nullptr, var_ptr("in_grad_loss")); }
+    else { float *b = var_ptr("in"), *a = var_ptr("out_grad_loss"); nk.deconv(row.member, g, a, b, nullptr, var_ptr("filts_grad_loss")); }
+  }
   void run_sgd() {
     // every var must have exactly the dims the op gives its arg (params are no img shards), and the 3n + 1 vars must all be different: w_i and h_i are rewritten in place
     sgd_op_t const so = sgd_op_of_op(fi.op);
@@ -976,6 +1030,7 @@ void native_kernels_t::run(native_func_t const &f, rtc_func_info_t const &fi, ma
   case kFamData: c.run_data(); break;
   case kFamLoss: c.run_loss(); break;
   case kFamConvGrp: c.run_conv_grp(); break;
+  case kFamDeconv: c.run_deconv(); break;
   }
 }
 

@@ -129,7 +129,7 @@ struct op_base_t {
 };
 typedef std::shared_ptr<op_base_t> p_op_base_t;
 // ---- the op flags of a native function.  Which function takes which flag is a column of the one table, native_funcs.h (included at the end of this file), which defines:
-enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver, kFamEval, kFamData, kFamBnf, kFamLoss, kFamConvGrp };   // selects the handler
+enum func_family_t { kFamSgemm, kFamConv, kFamConvNhwc, kFamNhwcGrp, kFamNhwcMulti, kFamK1Chain, kFamFiltsKmajor, kFamBconv, kFamBckOp, kFamSgd, kFamBn, kFamBnc, kFamSolver, kFamEval, kFamData, kFamBnf, kFamLoss, kFamConvGrp, kFamDeconv };   // selects the handler
 enum : unsigned { kFlagZinp = 1, kFlagSeedVar = 2, kFlagImgShards = 4, kFlagNhwcResidual = 8 };
 struct op_flag_name_t { char const *name; unsigned flag; };
 constexpr op_flag_name_t kOpFlagNames[] = {{"img_shards", kFlagImgShards}, {"seed_from_var", kFlagSeedVar}, {"zero_if_in_non_pos", kFlagZinp}, {"nhwc_residual", kFlagNhwcResidual}};

@@ -251,6 +251,13 @@ OP_INFO = {
     "sgemm": (("a", "b"), ("c",), ()),
     # { in, filts, biases, out_grad_loss } -> { in_grad_loss, filts_grad_loss, biases_grad_loss }: each output has its matching input's dims (src/conv_util.cc:65-66,411-416)
     "BckConv": (("in", "filts", "biases", "out_grad_loss"), ("in_grad_loss", "filts_grad_loss", "biases_grad_loss"), ("kern_sz", "stride", "in_pad", "out_chans")),
+    # this backend's own (the reference knows the type and its shapes, src/conv_util.cc:35, but has no function for it): in img:chan=C:y:x, filts in_chan=C:out_chan=OC:y:x
+    # (Caffe's blob), out img:OC:(H-1)*SY+KH-2*PY:(W-1)*SX+KW-2*PX; no group, no fused ReLU.  BckDeconv: every gradient with its matching input's dims
+    "Deconvolution": (("in", "filts", "biases"), ("out",), ("kern_sz", "stride", "in_pad", "out_chans")),
+    "BckDeconv": (("in", "filts", "biases", "out_grad_loss"), ("in_grad_loss", "filts_grad_loss", "biases_grad_loss"), ("kern_sz", "stride", "in_pad", "out_chans")),
+    # this backend's own: Caffe's Crop at axis 2 -- out is the window of in at `offset` (dims y:x, tn none) -- and its gradient, +0 outside the window
+    "Crop": (("in",), ("out",), ("offset",)),
+    "BckCrop": (("out_grad_loss",), ("in_grad_loss",), ("offset",)),
     # the non-conv ops of the gradient pipe, with the reference's arg names (src/conv_util.cc:33-64).  Scalars (uint32 / float ndas) and kern_sz / stride / in_pad ride in the op.
     # Spreading is the pooling gradient and BckLRN the LRN gradient: each carries its forward op's parameters; ZeroIfNonPos is the ReLU gradient.
     "Pooling": (("in",), ("out",), _POOL_PARAMS),
@@ -319,7 +326,7 @@ LOSS_NORMALIZATIONS = ("valid", "full", "batch_size", "none")
 SOLVER_CHUNK = 4096   # floats of one tensor a workgroup owns; one partial sum of squares per chunk
 
 
-_NON_GEMM_TYPES = ("Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + BNF_TYPES + SOLVER_TYPES + EVAL_TYPES + DATA_TYPES + LOSS_TYPES
+_NON_GEMM_TYPES = ("Crop", "BckCrop", "Pooling", "LRN", "Spreading", "BckLRN", "ZeroIfNonPos", "SoftmaxWithLoss", "Reduce", "Concat", "Split", "Dropout", "BckDropout", "ChanAffine", "SgdUpdate") + BN_TYPES + BNF_TYPES + SOLVER_TYPES + EVAL_TYPES + DATA_TYPES + LOSS_TYPES
 
 
 @dataclass
@@ -435,6 +442,53 @@ class Op:
                 raise RtErr(f"BckConv: {dst} dims {self.get_dims(dst).pretty()} != {src} dims {self.get_dims(src).pretty()}")
         if self.get_dims("biases").dims_prod() != g["OC"]:
             raise RtErr("BckConv: biases must hold out_chan values")
+        return g
+
+    def deconv_geom(self) -> dict:
+        """Named geometry of a Deconvolution (or, with out_grad_loss in the place of out, a BckDeconv): B C H W the input (the SMALL map), OC KH KW from filts
+        in_chan:out_chan:y:x, OH = (H-1)*SY + KH - 2*PY and OW likewise (the inverse of conv_geom's rule: the reference's conv_out_sz_to_in_sz).  group > 1 and a
+        fused ReLU are refused by name."""
+        t = self.get_type()
+        bck = t == "BckDeconv"
+        i, f, o = self.get_dims("in"), self.get_dims("filts"), self.get_dims("out_grad_loss" if bck else "out")
+        st, pad = self.get_dims("stride"), self.get_dims("in_pad")
+        if self.has("group") and self.get_u32("group") != 1:
+            raise UnsupErr(f"{t}: group={self.get_u32('group')}: a Deconvolution with group > 1 is out of scope")
+        if self.has("conv_has_relu") and self.get_u32("conv_has_relu"):
+            raise UnsupErr(f"{t}: conv_has_relu=1: a Deconvolution has no fused ReLU")
+        if f.names != ("in_chan", "out_chan", "y", "x"):
+            raise RtErr(f"{t}: filts must be in_chan:out_chan:y:x (Caffe's blob), got {f.pretty()}")
+        g = dict(B=i.dsz("img"), C=i.dsz("chan"), H=i.dsz("y"), W=i.dsz("x"), OC=f.dsz("out_chan"), KH=f.dsz("y"), KW=f.dsz("x"),
+                 SY=st.dsz("y"), SX=st.dsz("x"), PY=pad.dsz("y"), PX=pad.dsz("x"), OH=o.dsz("y"), OW=o.dsz("x"))
+        if f.dsz("in_chan") != g["C"]:
+            raise RtErr(f"{t}: filts.in_chan={f.dsz('in_chan')} != in.chan={g['C']}")
+        if o.dsz("img") != g["B"] or o.dsz("chan") != g["OC"]:
+            raise RtErr(f"{t}: out dims inconsistent with in/filts")
+        if min(g["SY"], g["SX"]) < 1:
+            raise RtErr(f"{t}: zero stride")
+        for hw, k, s, p, oo in (("H", "KH", "SY", "PY", "OH"), ("W", "KW", "SX", "PX", "OW")):
+            if (g[hw] - 1) * g[s] + g[k] - 2 * g[p] != g[oo]:
+                raise RtErr(f"{t}: out {oo}={g[oo]} != ({hw}-1)*{s}+{k}-2*{p} = {(g[hw] - 1) * g[s] + g[k] - 2 * g[p]}")
+        if self.get_dims("biases").dims_prod() != g["OC"]:
+            raise RtErr(f"{t}: biases must hold out_chan values")
+        if bck:
+            for src, dst in (("in", "in_grad_loss"), ("filts", "filts_grad_loss"), ("biases", "biases_grad_loss")):
+                if self.get_dims(dst) != self.get_dims(src):
+                    raise RtErr(f"BckDeconv: {dst} dims {self.get_dims(dst).pretty()} != {src} dims {self.get_dims(src).pretty()}")
+        return g
+
+    def crop_geom(self) -> dict:
+        """A Crop (in -> out) or a BckCrop (out_grad_loss -> in_grad_loss): the window OH x OW at offset (oy, ox) of the plane H x W, img / chan equal."""
+        t = self.get_type()
+        big, win = (self.get_dims("in"), self.get_dims("out")) if t == "Crop" else (self.get_dims("in_grad_loss"), self.get_dims("out_grad_loss"))
+        off = self.get_dims("offset")
+        if big.names != ("img", "chan", "y", "x") or win.names != big.names or big.tn != "float" or win.tn != "float":
+            raise RtErr(f"{t}: plane and window must be float img:chan:y:x")
+        if win.dsz("img") != big.dsz("img") or win.dsz("chan") != big.dsz("chan"):
+            raise RtErr(f"{t}: the window {win.pretty()} differs from the plane's tensor {big.pretty()} in img / chan")
+        g = dict(B=big.dsz("img"), C=big.dsz("chan"), H=big.dsz("y"), W=big.dsz("x"), OH=win.dsz("y"), OW=win.dsz("x"), oy=off.dsz("y"), ox=off.dsz("x"))
+        if g["oy"] + g["OH"] > g["H"] or g["ox"] + g["OW"] > g["W"]:
+            raise RtErr(f"{t}: offset ({g['oy']}, {g['ox']}) + window ({g['OH']}, {g['OW']}) exceeds the plane ({g['H']}, {g['W']})")
         return g
 
     def get_f32(self, an: str) -> float:
@@ -813,6 +867,9 @@ class Op:
             return 2 * g["M"] * g["N"] * g["K"]
         if self.get_type() in _NON_GEMM_TYPES:   # bandwidth ops: no multiply-accumulate work is accounted
             return 0
+        if self.get_type() in ("Deconvolution", "BckDeconv"):   # every in element meets every tap of every out_chan: 2*B*C*H*W*OC*KH*KW; the gradients twice that
+            g = self.deconv_geom()
+            return (4 if self.get_type() == "BckDeconv" else 2) * g["B"] * g["C"] * g["H"] * g["W"] * g["OC"] * g["KH"] * g["KW"]
         if self.get_type() == "BckConv":   # two GEMMs of the forward size: the data and the filter gradient
             g = self.bck_conv_geom()
             return 4 * (g["B"] * g["OH"] * g["OW"]) * g["OC"] * (g.get("CG", g["C"]) * g["KH"] * g["KW"])
@@ -846,7 +903,7 @@ def parse_op(line: str) -> Op:
         if unknown:
             raise RtErr(f"op(legacy): unknown fields {sorted(unknown)}")
         op.str_vals["type"] = str(d["type"])
-        none_dims = {"kern_sz", "stride", "in_pad"}
+        none_dims = {"kern_sz", "stride", "in_pad", "offset"}
         for k, v in _kv(d.get("dims_vals", [])).items():
             tn = "none" if k in none_dims else "float"
             dims, tn = _parse_dims(v, tn)
@@ -874,6 +931,10 @@ def parse_op(line: str) -> Op:
             op.conv_geom()
         elif t == "BckConv":
             op.bck_conv_geom()
+        elif t in ("Deconvolution", "BckDeconv"):
+            op.deconv_geom()
+        elif t in ("Crop", "BckCrop"):
+            op.crop_geom()
         elif t in ("Pooling", "Spreading"):
             op.pool_geom()
         elif t in ("LRN", "BckLRN"):

@@ -11,7 +11,7 @@ from __future__ import annotations
 import re
 from typing import Dict, List, Tuple, Union
 
-from .op import Op, RtErr, parse_op
+from .op import Op, RtErr, UnsupErr, parse_op
 from .solver_cfg import Freeze, LrPolicy, Solver
 
 Node = Dict[str, list]
@@ -97,6 +97,22 @@ def conv_ops(text: str, batch: int, in_chw: Tuple[int, int, int] = (3, 224, 224)
                 f"in=(dims=(img={batch},chan={C},y={H},x={W})),in_pad=(tn=none,dims=(y={p},x={p})),kern_sz=(tn=none,dims=(y={kh},x={kw})),"
                 f"out=(dims=(img={batch},chan={oc},y={oh},x={ow})),out_chans=(tn=uint32_t,v={oc}),stride=(tn=none,dims=(y={s},x={s}))))")))
             shapes[tops[0]] = (oc, oh, ow)
+        elif t == "DECONVOLUTION":   # out = (in - 1) * stride + k - 2 * pad; filts are Caffe's blob in_chan : out_chan : y : x
+            oc, k, s, p = _deconv_param(L, name)
+            oh = (H - 1) * s + k - 2 * p; ow = (W - 1) * s + k - 2 * p
+            out.append((name, parse_op(
+                f"(str_vals=(type=Deconvolution),nda_vals=(biases=(dims=(out_chan={oc})),filts=(dims=(in_chan={C},out_chan={oc},y={k},x={k})),"
+                f"in=(dims=(img={batch},chan={C},y={H},x={W})),in_pad=(tn=none,dims=(y={p},x={p})),kern_sz=(tn=none,dims=(y={k},x={k})),"
+                f"out=(dims=(img={batch},chan={oc},y={oh},x={ow})),out_chans=(tn=uint32_t,v={oc}),stride=(tn=none,dims=(y={s},x={s}))))")))
+            shapes[tops[0]] = (oc, oh, ow)
+        elif t == "CROP":
+            oy, ox = _crop_param(L, name)
+            if len(bots) != 2 or bots[1] not in shapes:
+                raise RtErr(f"prototxt: crop {name!r} needs two known bottoms (a, ref)")
+            rh, rw = shapes[bots[1]][1:]
+            if oy + rh > H or ox + rw > W:
+                raise RtErr(f"prototxt: crop {name!r}: offset ({oy}, {ox}) + {bots[1]!r}'s plane ({rh}, {rw}) exceeds {bots[0]!r}'s plane ({H}, {W})")
+            shapes[tops[0]] = (C, rh, rw)
         elif t == "POOLING":
             pp = _one(L, "pooling_param", {})
             if str(_one(pp, "global_pooling", "false")).lower() == "true":
@@ -118,6 +134,27 @@ def conv_ops(text: str, batch: int, in_chw: Tuple[int, int, int] = (3, 224, 224)
     return out
 
 
+def _deconv_param(L: Node, name) -> Tuple[int, int, int, int]:
+    """-> (num_output, kernel_size, stride, pad) of a Deconvolution layer; group > 1 is refused by name."""
+    cp = _one(L, "convolution_param", {})
+    grp = int(_one(cp, "group", 1))
+    if grp != 1:
+        raise UnsupErr(f"prototxt: deconvolution {name!r}: group={grp}: a Deconvolution with group > 1 is out of scope")
+    return int(_one(cp, "num_output")), int(_one(cp, "kernel_size", 1)), int(_one(cp, "stride", 1)), int(_one(cp, "pad", 0))
+
+
+def _crop_param(L: Node, name) -> Tuple[int, int]:
+    """-> (oy, ox) of a Crop layer: crop_param { axis offset }, one offset for both axes or one per axis; axis other than 2 is refused by name."""
+    cp = _one(L, "crop_param", {})
+    axis = int(_one(cp, "axis", 2))
+    if axis != 2:
+        raise UnsupErr(f"prototxt: crop {name!r}: axis={axis}: only axis 2 (the plane: y and x) is supported")
+    offs = [int(x) for x in cp.get("offset", [])] if isinstance(cp, dict) else []
+    if len(offs) > 2:
+        raise RtErr(f"prototxt: crop {name!r}: {len(offs)} offsets for the two axes y, x")
+    return (0, 0) if not offs else (offs[0], offs[0]) if len(offs) == 1 else (offs[0], offs[1])
+
+
 def conv_bottoms(text: str) -> List[Tuple[str, str]]:
     """-> [(layer name, bottom blob)] of the TEST-phase Convolution / InnerProduct layers in definition order (the order of conv_ops): which convolutions read the
     same blob -- sibling convolutions that can run as one fused launch -- is a fact of the net graph, not of the layer shapes."""
@@ -133,7 +170,8 @@ def pipe_spec(text: str, in_chw: Tuple[int, int, int] = (3, 224, 224)) -> List[s
     """-> the TEST-phase forward ops of a net definition as compact one-line records (boda_amd.conv_pipe.pipe_from_spec reads
     them back): what the reference's reader keeps of each layer for conv_pipe_t (src/caffepb.cc:166-326).
       input C H W | conv tag bot top oc kh kw sy sx py px [group] | pool tag bot top kh kw sy sx py px avg global
-      lrn tag bot top local_size alpha beta k | relu tag bot top | drop tag bot top | concat tag top bot1,bot2,..."""
+      lrn tag bot top local_size alpha beta k | relu tag bot top | drop tag bot top | concat tag top bot1,bot2,...
+      deconv tag bot top oc kh kw sy sx py px | crop tag bot ref top oy ox"""
     root = parse(text)
     layers = root.get("layer", []) or root.get("layers", [])
     out: List[str] = []
@@ -157,6 +195,14 @@ def pipe_spec(text: str, in_chw: Tuple[int, int, int] = (3, 224, 224)) -> List[s
             out.append(f"conv {name} {bots[0]} {tops[0]} {int(_one(cp, 'num_output'))} {k} {k} {s_} {s_} {p_} {p_}" + (f" {grp}" if grp > 1 else ""))
         elif t == "INNERPRODUCT":
             out.append(f"conv {name} {bots[0]} {tops[0]} {int(_one(_one(L, 'inner_product_param', {}), 'num_output'))} 0 0 1 1 0 0")  # kernel = whole input
+        elif t == "DECONVOLUTION":
+            oc, k, s_, p_ = _deconv_param(L, name)
+            out.append(f"deconv {name} {bots[0]} {tops[0]} {oc} {k} {k} {s_} {s_} {p_} {p_}")
+        elif t == "CROP":
+            oy, ox = _crop_param(L, name)
+            if len(bots) != 2:
+                raise RtErr(f"prototxt: crop {name!r} needs two bottoms (a, ref)")
+            out.append(f"crop {name} {bots[0]} {bots[1]} {tops[0]} {oy} {ox}")
         elif t == "POOLING":
             pp = _one(L, "pooling_param", {})
             glob = int(str(_one(pp, "global_pooling", "false")).lower() == "true")
