@@ -1,13 +1,15 @@
 """Test infrastructure of the grouped convolution (hip_conv_grp, hip_bconv_in_grp, hip_bconv_filts_grp): the case list, grouped ops, the DEFINITION -- for every
 group the ungrouped function on the op sliced to that group, the results side by side -- run on a given backend, and an independent float64 twin.
 
-A case is (B, g, C, OC, H, W, k, stride, pad).  mrd = max|x - r| / max|r| over a tensor (r the float64 result)."""
+A case is (B, g, C, OC, H, W, k, stride, pad); k, stride and pad are each one number (both axes) or a (y, x) pair.  mrd = max|x - r| / max|r| over a tensor (r the
+float64 result).  run_func is tests/deconv_ref.py's: NaN-filled outputs, inputs that keep their bits and, with guards=True, a guard var in front of and behind every var."""
 import numpy as np
 import torch
 
-from boda_amd.cnn_op import NATIVE_ARGS, OpTune, add_bck_conv_annotations, add_codegen_annotations
+from boda_amd.cnn_op import OpTune, add_bck_conv_annotations, add_codegen_annotations
 from boda_amd.op import parse_op
-from boda_amd.rtc import RtcArg, RtcFuncCall, RtcFuncInfo
+
+from deconv_ref import run_func   # noqa: F401  (one implementation for both families; the tests import it from here)
 
 CASES = [
     (3, 2, 6, 10, 7, 6, 3, 1, 1),      # ragged CG = 3, OCG = 5, two groups inside one tile's reach
@@ -23,27 +25,38 @@ CASES = [
 CASE_IDS = ["x".join(str(v) for v in c) for c in CASES]
 
 
+def two(v):
+    """A kernel, stride or pad as its (y, x) pair."""
+    return tuple(int(i) for i in v) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
 def out_plane(H, W, k, s, p):
-    return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    (KH, KW), (SY, SX), (PY, PX) = two(k), two(s), two(p)
+    return (H + 2 * PY - KH) // SY + 1, (W + 2 * PX - KW) // SX + 1
+
+
+def _geom_fields(k, s, p):
+    (KH, KW), (SY, SX), (PY, PX) = two(k), two(s), two(p)
+    return f"in_pad=(tn=none,dims=(y={PY},x={PX})),kern_sz=(tn=none,dims=(y={KH},x={KW})),stride=(tn=none,dims=(y={SY},x={SX}))"
 
 
 def conv_op(B, g, C, OC, H, W, k, s, p, group_field=True):
-    """A Convolution with filts OC x C/g x k x k; group_field=False leaves `group` out (g must then be 1)."""
+    """A Convolution with filts OC x C/g x KH x KW; group_field=False leaves `group` out (g must then be 1)."""
     OH, OW = out_plane(H, W, k, s, p)
+    KH, KW = two(k)
     grp = f"group=(tn=uint32_t,v={g})," if group_field else ""
-    return parse_op(f"(str_vals=(type=Convolution),nda_vals=(biases=(dims=(out_chan={OC})),filts=(dims=(out_chan={OC},in_chan={C // g},y={k},x={k})),{grp}"
-                    f"in=(dims=(img={B},chan={C},y={H},x={W})),in_pad=(tn=none,dims=(y={p},x={p})),kern_sz=(tn=none,dims=(y={k},x={k})),"
-                    f"out=(dims=(img={B},chan={OC},y={OH},x={OW})),out_chans=(tn=uint32_t,v={OC}),stride=(tn=none,dims=(y={s},x={s}))))")
+    return parse_op(f"(str_vals=(type=Convolution),nda_vals=(biases=(dims=(out_chan={OC})),filts=(dims=(out_chan={OC},in_chan={C // g},y={KH},x={KW})),{grp}"
+                    f"in=(dims=(img={B},chan={C},y={H},x={W})),out=(dims=(img={B},chan={OC},y={OH},x={OW})),out_chans=(tn=uint32_t,v={OC}),{_geom_fields(k, s, p)}))")
 
 
 def bck_op(B, g, C, OC, H, W, k, s, p, group_field=True):
     OH, OW = out_plane(H, W, k, s, p)
+    KH, KW = two(k)
     grp = f"group=(tn=uint32_t,v={g})," if group_field else ""
-    f = f"dims=(out_chan={OC},in_chan={C // g},y={k},x={k})"
+    f = f"dims=(out_chan={OC},in_chan={C // g},y={KH},x={KW})"
     i = f"dims=(img={B},chan={C},y={H},x={W})"
     return parse_op(f"(str_vals=(type=BckConv),nda_vals=(biases=(dims=(out_chan={OC})),biases_grad_loss=(dims=(out_chan={OC})),filts=({f}),filts_grad_loss=({f}),{grp}"
-                    f"in=({i}),in_grad_loss=({i}),in_pad=(tn=none,dims=(y={p},x={p})),kern_sz=(tn=none,dims=(y={k},x={k})),"
-                    f"out_chans=(tn=uint32_t,v={OC}),out_grad_loss=(dims=(img={B},chan={OC},y={OH},x={OW})),stride=(tn=none,dims=(y={s},x={s}))))")
+                    f"in=({i}),in_grad_loss=({i}),out_chans=(tn=uint32_t,v={OC}),out_grad_loss=(dims=(img={B},chan={OC},y={OH},x={OW})),{_geom_fields(k, s, p)}))")
 
 
 def rand_ins(case, seed, lo=-5.0, hi=5.0):
@@ -52,35 +65,7 @@ def rand_ins(case, seed, lo=-5.0, hi=5.0):
     OH, OW = out_plane(H, W, k, s, p)
     rng = np.random.default_rng(seed)
     u = lambda *sh: rng.uniform(lo, hi, sh).astype(np.float32)
-    return {"in": u(B, C, H, W), "filts": u(OC, C // g, k, k), "biases": u(OC), "out_grad_loss": u(B, OC, OH, OW)}
-
-
-def run_func(rtc, fop, ins, tile="", runs=1):
-    """Run one annotated function op on `rtc` with host inputs; every OUT var is NaN-filled before the call, so an element the call does not write shows.
-    -> (the function's output array, the launch record of a be=hip backend or None)."""
-    fn = fop.get_func_name()
-    if tile:
-        fop = fop.copy(); fop.str_vals["hip_tile"] = tile
-    rtc.compile([RtcFuncInfo("f", "", [a for a, _ in NATIVE_ARGS[fn]], fop)])
-    am, made = {}, []
-    try:
-        for an, io in NATIVE_ARGS[fn]:
-            if io == "REF":
-                am[an] = RtcArg.ref(fop.get_dims(an)); continue
-            rtc.create_var_with_dims(an, fop.get_dims(an)); made.append(an); am[an] = RtcArg.var(an)
-            if io == "IN":
-                rtc.copy_nda_to_var(an, np.ascontiguousarray(ins[an], dtype=np.float32))
-            else:
-                rtc.copy_nda_to_var(an, np.full(fop.get_dims(an).sizes, np.nan, np.float32))
-        for _ in range(runs):
-            rtc.run(RtcFuncCall("f", am))
-        rtc.finish_and_sync()
-        launch = rtc.last_launch() if rtc.be == "hip" else None
-        return rtc.copy_var_to_nda([a for a, io in NATIVE_ARGS[fn] if io == "OUT"][0]), launch
-    finally:
-        for vn in made:
-            rtc.release_var(vn)
-        rtc.release_func("f"); rtc.release_per_call_id_data()
+    return {"in": u(B, C, H, W), "filts": u(OC, C // g, *two(k)), "biases": u(OC), "out_grad_loss": u(B, OC, OH, OW)}
 
 
 def grouped_funcs(case, tune=None):
@@ -123,7 +108,7 @@ def torch_twin(case, ins, relu=True):
     x = torch.from_numpy(ins["in"].astype(np.float64)).requires_grad_(True)
     w = torch.from_numpy(ins["filts"].astype(np.float64)).requires_grad_(True)
     b = torch.from_numpy(ins["biases"].astype(np.float64))
-    y = torch.nn.functional.conv2d(x, w, None, stride=s, padding=p, groups=g)
+    y = torch.nn.functional.conv2d(x, w, None, stride=two(s), padding=two(p), groups=g)
     out = y.detach() + b.view(1, -1, 1, 1)
     if relu:
         out = torch.clamp(out, min=0.0)

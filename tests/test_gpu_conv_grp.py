@@ -2,7 +2,8 @@
   * hip_conv_grp / hip_bconv_in_grp equal be=cpu's hip_conv / hip_bconv_in on the op sliced per group (tests/conv_grp_ref.py: sliced)
   * hip_bconv_filts_grp equals oracle/bck_chain.filts_chain on the slices with the (BK, KSL) of the launch; with KSL = 1 also be=cpu's hip_bconv_filts on the slices
   * containment: an Inf or NaN in group 0's operands changes no bit outside group 0's outputs
-Every output is NaN-filled before the call (conv_grp_ref.run_func).  Every case runs in BOTH forms, forced by tile -- the matrix form on 32 x 32 x 2 and on 16 x 16 x 4
+Every output is NaN-filled before the call, a guard var stands in front of and behind every var and must keep its bits, and inputs keep their bits
+(conv_grp_ref.run_func, guards=True).  Every case runs in BOTH forms, forced by tile -- the matrix form on 32 x 32 x 2 and on 16 x 16 x 4
 blocks, with one and with several blocks per wave; the direct form -- and under the planner's own choice; so does the containment test: in the matrix form the first
 case has both groups inside one tile's reach (rows 5..31 of a group's block are masked, never the neighbour's), the second one whole 32-row block per group."""
 import numpy as np
@@ -77,7 +78,7 @@ def test_forward_bits(hip, cpu, case):
     fc = grouped_funcs(case)[0]
     want = ref(cpu, case, "fwd")
     for tile in ("",) + MATRIX_TILES + DIRECT_FWD_TILES:
-        got, launch = run_func(hip, fc, ins, tile)
+        got, launch = run_func(hip, fc, ins, tile, guards=True)
         assert launch["kernel"].startswith("bodahip_conv_grp_") and want_form(tile, launch), launch
         assert bits_equal(got, want), (case, tile, launch)
 
@@ -88,7 +89,7 @@ def test_data_gradient_bits(hip, cpu, case):
     fi = grouped_funcs(case)[1]
     want = ref(cpu, case, "in")
     for tile in ("",) + MATRIX_TILES + ("1x1x1x2x2x1x1",) + (("1x4x1x2x2x1x1",) if case[7] == 1 else ()):   # direct: one output a thread; four adjacent x (stride 1)
-        got, launch = run_func(hip, fi, ins, tile)
+        got, launch = run_func(hip, fi, ins, tile, guards=True)
         assert launch["kernel"].startswith("bodahip_bconv_in_grp_") and want_form(tile, launch), launch
         assert bits_equal(got, want), (case, tile, launch)
         if case == CASES[4]:   # 1x1 at stride 2: the odd rows and columns meet no term and are +0 (and written: the output was NaN-filled)
@@ -101,23 +102,23 @@ def test_filter_gradient_chain(hip, cpu, case):
     ff = grouped_funcs(case)[3]
     B, g, C, OC, H, W, k, s, p = case
     K = B * ((H + 2 * p - k) // s + 1) * ((W + 2 * p - k) // s + 1)
-    got, launch = run_func(hip, ff, ins, runs=2)   # the planner's default, held to the chain with its launched (BK, KSL); two runs into the same var
+    got, launch = run_func(hip, ff, ins, runs=2, guards=True)   # the planner's default, held to the chain with its launched (BK, KSL); two runs into the same var
     form, BK, KSL = plan_of(launch)
     assert launch["kernel"] == "bodahip_bconv_filts_grp_" + form
     assert bits_equal(got, chain(case, ins, BK, KSL)), (case, launch)
-    again, _ = run_func(hip, ff, ins)
+    again, _ = run_func(hip, ff, ins, guards=True)
     assert bits_equal(got, again)   # the same bits on two runs
     bk_odd = next(b for b in (10, 14, 6, 22, 7) if K % b)   # a BK that does not divide B * OH * OW
     nkt = -(-K // 32)
     for bk, ksl in ((32, 1), (32, 2), (bk_odd, 3), (32, min(256, nkt + 1))):   # KSL 1, 2, 3 and one larger than the number of K steps (empty slices)
-        got, launch = run_func(hip, ff, ins, f"1x1x{bk}x2x2x1x{ksl}")
+        got, launch = run_func(hip, ff, ins, f"1x1x{bk}x2x2x1x{ksl}", guards=True)
         assert plan_of(launch) == ("direct", bk, ksl), launch
         assert bits_equal(got, chain(case, ins, bk, ksl)), (case, bk, ksl)
         if ksl == 1:   # one slice: be=cpu's single chain on the slices, for any BK
             assert bits_equal(got, ref(cpu, case, "filts")), (case, bk)
-    got, _ = run_func(hip, ff, ins, f"1x1x{bk_odd}x2x2x1x1")
+    got, _ = run_func(hip, ff, ins, f"1x1x{bk_odd}x2x2x1x1", guards=True)
     assert bits_equal(got, ref(cpu, case, "filts")), (case, bk_odd)
-    got, launch = run_func(hip, ff, ins, "1x1x4x2x2x1x300")   # 300 slices: slabs in the call's workspace, added by the second launch (the launch record is the main kernel's)
+    got, launch = run_func(hip, ff, ins, "1x1x4x2x2x1x300", guards=True)   # 300 slices: slabs in the call's workspace, added by the second launch (the launch record is the main kernel's)
     assert plan_of(launch) == ("direct", 4, 300), launch
     assert bits_equal(got, chain(case, ins, 4, 300)), case
     # the matrix form: the tile is one wave's, the workgroup's KSL (1..16) waves are its slices.  32- and 16-row blocks, two blocks per wave
@@ -126,7 +127,7 @@ def test_filter_gradient_chain(hip, cpu, case):
     few = -(-K // bk_few) + 1
     for bi, bj, plans in ((32, 32, ((32, 1), (32, 2), (bk4, 3), (bk4, 1), (bk_few, few))), (16, 32, ((bk4, 3), (32, 1))), (32, 64, ((32, 2),))):
         for bk, ksl in plans:
-            got, launch = run_func(hip, ff, ins, f"{bi}x{bj}x{bk}x1x1x1x{ksl}")
+            got, launch = run_func(hip, ff, ins, f"{bi}x{bj}x{bk}x1x1x1x{ksl}", guards=True)
             assert plan_of(launch) == ("mfma", bk, ksl) and launch["block"] == 64 * ksl, launch
             assert bits_equal(got, chain(case, ins, bk, ksl)), (case, bi, bj, bk, ksl)
             if ksl == 1:
