@@ -198,10 +198,10 @@ def run_func(rtc, fop, ins, repeat=1, keep=None, bind=None):
         rtc.release_func("bn_f"); rtc.release_per_call_id_data()
 
 
-def run_all_five(rtc, shape, forced=0, relu=1, seed=0, repeat=1):
-    """The five functions on one backend, each fed the BACKEND's own upstream results -> dict of everything."""
+def run_all_five(rtc, shape, forced=0, relu=1, seed=0, repeat=1, inputs=None):
+    """The five functions on one backend, each fed the BACKEND's own upstream results -> dict of everything.  inputs: make_inputs' dict, in place of make_inputs(shape, seed)."""
     d = dims_of(shape)
-    i = make_inputs(shape, seed)
+    i = inputs if inputs is not None else make_inputs(shape, seed)
     r = dict(i)
     keep = []
     sts = run_func(rtc, bn_stats_func_op(d, EPS, MAF, forced), {"in": i["x"], "run_mean": i["run_mean"], "run_var": i["run_var"]}, repeat=repeat, keep=keep)

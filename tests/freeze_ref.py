@@ -45,10 +45,11 @@ def special_dy(shape, seed=0):
     return dy
 
 
-def run_all_three(rtc, shape, forced=0, seed=0, repeat=2, dy=None):
-    """The three functions on one backend, each fed the BACKEND's own upstream results; hip_bnf_bck and hip_bnf_bck_in also in place -> dict of everything."""
+def run_all_three(rtc, shape, forced=0, seed=0, repeat=2, dy=None, inputs=None):
+    """The three functions on one backend, each fed the BACKEND's own upstream results; hip_bnf_bck and hip_bnf_bck_in also in place -> dict of everything.
+    inputs: bn_ref.make_inputs' dict, in place of make_inputs(shape, seed)."""
     d = R.dims_of(shape)
-    i = R.make_inputs(shape, seed)
+    i = dict(inputs) if inputs is not None else R.make_inputs(shape, seed)
     if dy is not None:
         i["dy"] = dy
     r = dict(i)

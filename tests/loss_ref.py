@@ -220,9 +220,9 @@ GUARD = np.array([0x5A5A0001, 0x5A5A0002, 0x5A5A0003, 0x5A5A0004], np.uint32).vi
 POISON = np.uint32(0x7FC0BEEF)   # a payload NaN
 
 
-def run_func(rtc, fop, ins, kernel=None, pfx="lt_"):
+def run_func(rtc, fop, ins, kernel=None, pfx="lt_", runs=1):
     """Compile and run one annotated function with host inputs -> {OUT arg: array}.  Every OUT var is filled with a payload NaN first; asserted: no guard word changed,
-    every IN var still holds its input's bits, and (kernel given: be=hip) the launch was that kernel."""
+    every IN var still holds its input's bits, and (kernel given: be=hip) the launch was that kernel.  runs > 1: launched that often on the same vars."""
     fn = fop.get_func_name()
     spec = NATIVE_ARGS[fn]
     rtc.compile([RtcFuncInfo(pfx + "f", "", [a for a, _ in spec], fop)])
@@ -237,8 +237,9 @@ def run_func(rtc, fop, ins, kernel=None, pfx="lt_"):
             for g in ("_g0", "_g1"):
                 rtc.copy_nda_to_var(pfx + an + g, GUARD)
             rtc.copy_nda_to_var(pfx + an, np.ascontiguousarray(ins[an], F).reshape(d.sizes) if io == "IN" else np.full(d.sizes, POISON, np.uint32).view(F))
-        rtc.run(RtcFuncCall(pfx + "f", {an: RtcArg.var(pfx + an) for an, _ in spec}))
-        rtc.finish_and_sync()
+        for _ in range(runs):
+            rtc.run(RtcFuncCall(pfx + "f", {an: RtcArg.var(pfx + an) for an, _ in spec}))
+            rtc.finish_and_sync()
         if kernel is not None:
             assert rtc.last_launch()["kernel"] == kernel, rtc.last_launch()
         outs = {}
