@@ -130,7 +130,10 @@ def add_codegen_annotations(op: Op, tune: OpTune, tile_wisdom=None) -> Op:
     if t == "Convolution":
         grouped = "G" in a.conv_geom()
         a.set_u32("conv_has_relu", 1)  # every Convolution under ops-prof (src/cnn_op.cc:337)
-        if grouped:   # group > 1: the grouped family's forward function and nothing else (fp32, reference layouts)
+        if grouped and native and dw_nhwc_tune(tune) and is_depthwise(a):   # a depthwise layer under the bf16 channels-last tune: its own kernel (boda_amd/nhwc.py: annotate_dw)
+            from . import nhwc
+            nhwc.annotate_dw(a, "float" if tune.hip_out == "f32" else "bfloat16")
+        elif grouped:   # group > 1: the grouped family's forward function and nothing else (fp32, reference layouts)
             refuse_grouped(a, tune)
             a.set_func_name(CONV_GRP_FUNC)
         elif tune.use_culibs:
@@ -155,8 +158,9 @@ def add_codegen_annotations(op: Op, tune: OpTune, tile_wisdom=None) -> Op:
         raise UnsupErr(f"op type {t!r} is not on the conv_fwd / sgemm hot path")
     if not tune.hip_exact and native and not tune.use_culibs and tune.hip_dtype != "bf16":
         a.str_vals["hip_exact"] = "0"   # travels with the function, like hip_tile
-    if tune.hip_tile and native and not tune.use_culibs and (a.get_func_name() != CONV_GRP_FUNC or is_grp_tile(tune.hip_tile)):
-        a.str_vals["hip_tile"] = tune.hip_tile   # travels with the function: the backend applies it to this function's calls only (a grouped op: its own seven-field form only)
+    own_tile = {CONV_GRP_FUNC: is_grp_tile, CONV_NHWC_DW_FUNC: is_dw_tile}.get(a.get_func_name(), lambda t: True)
+    if tune.hip_tile and native and not tune.use_culibs and own_tile(tune.hip_tile):
+        a.str_vals["hip_tile"] = tune.hip_tile   # travels with the function: the backend applies it to this function's calls only (a grouped or depthwise op: its own form only)
     return a
 
 
@@ -177,6 +181,30 @@ def is_grp_tile(tile: str) -> bool:
     """Is `tile` the grouped family's own form, seven fields BIxBJxBKxWIxWJxMINWxKSL?  A pipe-wide tile written for hip_conv / hip_bconv_* (five or six fields, or
     more than seven) is not: it passes a grouped layer by, and the planner chooses for it."""
     return bool(tile) and tile.count("x") == 6
+
+
+# a depthwise Convolution (group == in.chan == out_chans) under op_tune hip_dtype=bf16, hip_layout=nhwc [, hip_out=f32]: channels-last bf16 tensors, tap-major filters
+# (kernels/conv_nhwc_dw_bf16.hip; DESIGN.md section 3.26).  Every other grouped op under that tune stays refused (refuse_grouped)
+CONV_NHWC_DW_FUNC = "hip_conv_nhwc_dw"
+
+
+def is_dw_tile(tile: str) -> bool:
+    """Is `tile` hip_conv_nhwc_dw's own form, dw:TYxTXxCB (output rows, output columns, 8-channel chunks of a workgroup)?  Any other tile passes a depthwise layer by."""
+    return tile.startswith("dw:")
+
+
+def is_depthwise(op: Op) -> bool:
+    """A Convolution whose group is its input channel count and its out_chan count: channel multiplier 1."""
+    if op.get_type() != "Convolution" or op_group(op) <= 1:
+        return False
+    g = op_group(op)
+    return op.get_dims("in").dsz("chan") == g and op.get_dims("filts").dsz("out_chan") == g
+
+
+def dw_nhwc_tune(tune: OpTune) -> bool:
+    """The tune hip_conv_nhwc_dw exists under: bf16 channels-last and nothing that names another variant (those stay refused by name: refuse_grouped)."""
+    return (tune.hip_dtype == "bf16" and tune.hip_layout == "nhwc" and not (tune.use_culibs or tune.k1conv or tune.tconv or tune.ipconv or tune.hip_algo) and
+            tune.hip_out in ("", "f32"))
 
 
 def is_grouped(op: Op) -> bool:
@@ -1066,6 +1094,7 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_conv_grp": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),
     "hip_bconv_in_grp": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),
     "hip_bconv_filts_grp": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT")),
+    "hip_conv_nhwc_dw": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),   # a depthwise layer, channels-last bf16
     # a Deconvolution / BckDeconv: the lists of hip_conv and of BckConv's three gradients without their optional args; Caffe's Crop and its gradient
     "hip_deconv": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),
     "hip_deconv_bck_in": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),

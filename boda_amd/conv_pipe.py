@@ -353,6 +353,27 @@ def dw_sep_tiny(batch: int, in_hw: int = 12, classes: int = 10) -> ConvPipe:
     return p
 
 
+def mobilenet_v1(batch: int, in_hw: int = 224, width: float = 1.0, classes: int = 1000) -> ConvPipe:
+    """MobileNet-v1 (Howard et al. 2017, table 1) at width multiplier `width`: conv1 3x3 / 2, thirteen depthwise 3x3 (conv<N>_dw, pad 1, stride 2 at N = 2, 4, 6, 12)
+    + pointwise 1x1 (conv<N>_sep) pairs, every convolution followed by BatchNorm, Scale and ReLU, global average pooling, fc as a 1x1 convolution.  Every convolution
+    keeps a _biases param.  Channel counts are width x (32, 64, 128, 128, 256, 256, 512 x 6, 1024, 1024), which must come out as whole multiples of 8."""
+    ch = lambda c: int(round(c * width))
+    p = ConvPipe("mobilenet_v1", "data", Dims.make("float", img=batch, chan=3, y=in_hw, x=in_hw))
+    def cbr(tag, bot, oc, k, s, pad, group=1):
+        if oc % 8:
+            raise UnsupErr(f"mobilenet_v1: width={width} gives {tag} {oc} channels, no multiple of 8")
+        p.add(PipeOp(tag, "Convolution", bot, tag, out_chans=oc, kern_sz=(k, k), stride=(s, s), in_pad=(pad, pad), group=group))
+        p.add(PipeOp(tag + "_bn", "BatchNorm", tag, tag)); p.add(PipeOp(tag + "_scale", "Scale", tag, tag)); p.add(PipeOp(tag + "_relu", "ReLU", tag, tag))
+        return tag
+    n = cbr("conv1", "data", ch(32), 3, 2, 1); c = ch(32)
+    for i, (oc, s) in enumerate(((64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2), (512, 1), (512, 1), (512, 1), (512, 1), (512, 1), (1024, 2), (1024, 1)), 2):
+        n = cbr(f"conv{i}_dw", n, c, 3, s, 1, group=c)
+        n = cbr(f"conv{i}_sep", n, ch(oc), 1, 1, 0); c = ch(oc)
+    p.add(PipeOp("pool", "Pooling", n, "pool", kern_sz=None, avg_pool=1))
+    p.add(PipeOp("fc", "Convolution", "pool", "fc", out_chans=classes, kern_sz=(1, 1)))
+    return p
+
+
 def bilinear_filts(C: int, OC: int, k: int) -> np.ndarray:
     """Caffe's bilinear filler on the diagonal c == oc of a Deconvolution's filts[C][OC][k][k], +0 elsewhere: with f = ceil(k / 2) and c0 = (2f - 1 - f % 2) / (2f),
     w[y][x] = (1 - |y / f - c0|) * (1 - |x / f - c0|), every operation in fp32."""
@@ -685,14 +706,14 @@ class ConvPipeFwd:
     def init(self, cp: ConvPipe, op_params: Optional[Dict[str, np.ndarray]] = None, gen_mode: int = 5) -> None:
         rtc = self.rtc
         self.cp = cp
-        # grouped convolutions (PipeOp.group > 1) run as hip_conv_grp: fp32 in reference layouts only -- refused by the first such layer's name, before anything is created
+        # grouped convolutions (PipeOp.group > 1) run as hip_conv_grp: fp32 in reference layouts only -- but for the depthwise layers of a bf16 channels-last net, which
+        # run as hip_conv_nhwc_dw.  Whatever has no function is refused by the first such layer's name, before anything is created
         for o in cp.ops:
             if o.type == "Convolution" and o.group > 1:
                 try:
                     add_codegen_annotations(cp.conv_op(o), self.op_tune)
                 except UnsupErr as e:
                     raise UnsupErr(f"pipe {cp.name}: convolution {o.tag}: {e}") from None
-                break
         # Deconvolution and Crop layers run as hip_deconv / hip_crop: fp32 in reference layouts only -- refused by the first such layer's name, before anything is created
         for o in cp.ops:
             if o.type in ("Deconvolution", "Crop") and (self.nhwc or self.op_tune.hip_dtype not in ("", "f32")):
@@ -1001,7 +1022,7 @@ class ConvPipeFwd:
         if self.nhwc and self.fuse_siblings:
             by_key: Dict[tuple, List[PipeOp]] = {}
             for o in cp.ops:
-                if o.type == "Convolution" and not annos[o.tag].has("nhwc_s2d") and not annos[o.tag].get_dims("filts").has("in_grp") and o.tag not in res_fold:
+                if o.type == "Convolution" and o.group == 1 and not annos[o.tag].has("nhwc_s2d") and not annos[o.tag].get_dims("filts").has("in_grp") and o.tag not in res_fold:   # (a depthwise layer is a call of its own)
                     by_key.setdefault((o.bot, tuple(o.kern_sz), tuple(o.stride), tuple(o.in_pad), has_relu[o.tag]), []).append(o)
             for members0 in by_key.values():
                 for members in sibling_runs(cp.ops, members0, fused):

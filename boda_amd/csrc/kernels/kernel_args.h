@@ -340,6 +340,15 @@ struct deconv_args_t {
 static_assert(sizeof(deconv_args_t) == 96 && __builtin_offsetof(deconv_args_t, B) == 32 && __builtin_offsetof(deconv_args_t, n) == 64 &&
               __builtin_offsetof(deconv_args_t, a_bytes) == 72 && __builtin_offsetof(deconv_args_t, ws) == 88, "deconv_args_t layout");
 
+// kernels/conv_nhwc_dw_bf16.hip: a depthwise channels-last bf16 convolution (hip_conv_nhwc_dw); the geometry and the work split are -D constants
+struct conv_dw_args_t {
+  void const *in; void const *filts; float const *bias; void *out;   // in img:y:x:chan bf16, filts y:x:chan bf16, biases float, out img:y:x:chan bf16 | float
+  int n_ys, n_xs, n_cs;         // the workgroup walk per image: row strips, column segments, chunk blocks (the chunk block is the fastest coordinate of blockIdx.x)
+  unsigned in_bytes, f_bytes, out_bytes;
+  int pad0, pad1;
+};
+static_assert(sizeof(conv_dw_args_t) == 64 && __builtin_offsetof(conv_dw_args_t, n_ys) == 32 && __builtin_offsetof(conv_dw_args_t, in_bytes) == 44, "conv_dw_args_t layout");
+
 #pragma pop_macro("CH")
 #pragma pop_macro("CIN")
 #pragma pop_macro("COH")

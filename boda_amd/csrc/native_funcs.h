@@ -10,7 +10,7 @@
 namespace bodahip {
 
 // the family (func_family_t of rtc_types.h) selects the handler (native_run.cc, native_kernels.cc: check_compile_time); handlers switch on the member, never on the name
-inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf", "loss", "conv_grp", "deconv"};
+inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf", "loss", "conv_grp", "deconv", "conv_nhwc_dw"};
 // members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform.  kFamLoss: 1 fwd | 2 norm | 3 bck (loss_op_t::kind).  kFamConvGrp: 1 fwd | 2 bck_in | 3 bck_filts.  kFamDeconv: 1 fwd | 2 bck_in | 3 bck_biases | 4 bck_filts
 enum { kConvF32 = 0, kConvAlias = 1, kConvBf16 = 2, kConvWinograd = 3 };            // (the alias: hip_conv's contract without its fused pooling and filts_km)
 enum { kBconvIn = 1, kBconvBiases = 2, kBconvFilts = 3, kBconvFiltsBiases = 4 };   // (4 is opt-in: never one of the bare op's three calls)
@@ -71,7 +71,8 @@ inline constexpr char kWhyBnfOneDevice[] = "(a BatchNorm on its running pair, th
 inline constexpr char kWhyLossOneDevice[] = "(the full softmax loss, the hip_softmax_loss_* / hip_loss_norm family) counts the pels that are not ignored and sums loss_per_pel over the WHOLE batch, which would need a cross-device reduction, and takes vars of exactly its op's dims, not img shards; a loss with a LossSpec on several devices is out of scope";
 inline constexpr char kWhyConvGrpOneDevice[] = "(a grouped convolution, the hip_conv_grp / hip_bconv_in_grp / hip_bconv_filts_grp family) takes vars of exactly its op's dims, not img shards, and hip_bconv_filts_grp sums over the images of the WHOLE batch, which would need a cross-device reduction; grouped layers on several devices are out of scope";
 inline constexpr char kWhyDeconvOneDevice[] = "(a Deconvolution, the hip_deconv / hip_deconv_bck_in / hip_deconv_bck_filts / hip_deconv_bck_biases family) takes vars of exactly its op's dims, not img shards, and its filter and bias gradients sum over the images of the WHOLE batch, which would need a cross-device reduction; Deconvolution layers on several devices are out of scope";
-inline constexpr char const *why_one_device(func_family_t family) { return family == kFamLoss ? kWhyLossOneDevice : family == kFamConvGrp ? kWhyConvGrpOneDevice : family == kFamDeconv ? kWhyDeconvOneDevice : kWhyBnfOneDevice; }
+inline constexpr char kWhyConvNhwcDwOneDevice[] = "(a depthwise channels-last bf16 convolution, hip_conv_nhwc_dw) takes vars of exactly its op's dims, not img shards: the image count is a constant of its specialised kernel; depthwise layers on several devices are out of scope";
+inline constexpr char const *why_one_device(func_family_t family) { return family == kFamLoss ? kWhyLossOneDevice : family == kFamConvGrp ? kWhyConvGrpOneDevice : family == kFamDeconv ? kWhyDeconvOneDevice : family == kFamConvNhwcDw ? kWhyConvNhwcDwOneDevice : kWhyBnfOneDevice; }
 inline constexpr native_func_t kNativeFuncs[] = {
   // sgemm, a:K:M b:K:N c:M:N (test/rtc/cublas_sgemm.cucl:1-4); Convolution in reference layout (test/rtc/cudnn_conv.cucl:1-7)
   {"hip_sgemm", kFamSgemm, 0, nullptr, {"sgemm"}, {{"a", kIn}, {"b", kIn}, {"c", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
@@ -163,6 +164,10 @@ inline constexpr native_func_t kNativeFuncs[] = {
   {"hip_deconv_bck_in", kFamDeconv, kDeconvBckIn, nullptr, {"BckDeconv"}, {{"filts", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"in_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   {"hip_deconv_bck_filts", kFamDeconv, kDeconvBckFilts, nullptr, {"BckDeconv"}, {{"in", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"filts_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
   {"hip_deconv_bck_biases", kFamDeconv, kDeconvBckBiases, nullptr, {"BckDeconv"}, {{"out_grad_loss", kIn}, {"biases_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOneDevice},
+  // a depthwise Convolution (group == in.chan == out_chans) on channels-last bf16 tensors (this backend's own; kernels/conv_nhwc_dw_bf16.hip): in / out img:y:x:chan,
+  // filts tap-major y:x:chan.  hip_conv's arg list without its optional arg; no flag; one device only (why_one_device).  A family of its own: the rows of kFamConv and
+  // kFamConvNhwc are pinned.  In front of the loss rows, like the grouped rows
+  {"hip_conv_nhwc_dw", kFamConvNhwcDw, 0, nullptr, {"Convolution"}, {BODAHIP_CONV_ARGS}, {}, kVarNone, 0, {}, kBeHip, kOneDevice},
   // the full SoftmaxWithLoss (this backend's own; kernels/loss_f32.hip): what a head with a LossSpec lowers to -- loss_weight, ignore_label, planes, the four
   // normalisers.  hip_softmax_loss_bck reads s = weight / Z from loss_state on the device.  One device only (why_one_device).  In front of the data and eval rows,
   // which stay the table's last four
@@ -182,10 +187,10 @@ inline constexpr native_func_t kNativeFuncs[] = {
 
 inline native_func_t const *find_native_func(string const &fn) { for (auto const &f : kNativeFuncs) if (fn == f.name) return &f; return nullptr; }
 inline native_func_t const *find_native_func(func_family_t family, int member) { for (auto const &f : kNativeFuncs) if (f.family == family && f.member == member) return &f; return nullptr; }
-// the functions of a bare op of type t, in call order (empty: no such op).  kBconvFiltsBiases is nobody's default call, and the grouped functions belong to annotated ops
+// the functions of a bare op of type t, in call order (empty: no such op).  kBconvFiltsBiases is nobody's default call, and the grouped and the depthwise channels-last functions belong to annotated ops
 inline std::vector<native_func_t const *> native_funcs_of_type(string const &t, unsigned backend = kBeHip) {
   std::vector<native_func_t const *> r;
-  for (auto const &f : kNativeFuncs) if (f.of_type(t) && (f.backends & backend) && !(f.family == kFamBconv && f.member == kBconvFiltsBiases) && f.family != kFamConvGrp) r.push_back(&f);
+  for (auto const &f : kNativeFuncs) if (f.of_type(t) && (f.backends & backend) && !(f.family == kFamBconv && f.member == kBconvFiltsBiases) && f.family != kFamConvGrp && f.family != kFamConvNhwcDw) r.push_back(&f);
   std::stable_sort(r.begin(), r.end(), [](native_func_t const *a, native_func_t const *b) { return a->member < b->member; });
   return r;
 }
@@ -248,6 +253,37 @@ inline conv_grp_geom_t conv_grp_geom_of_op(op_base_t const &op, int member) {
   if (member == kConvGrpBckFilts && !(op.get_dims("filts_grad_loss") == f)) rt_err(fn + ": filts_grad_loss must have the dims of filts");
   uint64_t const in_b = 4ull * g.B * g.C * g.H * g.W, out_b = 4ull * g.B * g.OC * g.OH * g.OW, f_b = 4ull * g.OC * g.CG * g.KH * g.KW;
   if (in_b >= 0x7ffffff0ull || out_b >= 0x7ffffff0ull || f_b >= 0x7ffffff0ull) unsup_err(fn + ": tensors of 2 GiB or more (32-bit offsets)");
+  return g;
+}
+
+// hip_conv_nhwc_dw (kFamConvNhwcDw): what the planner, the ahead-of-time build and the call read from the function's op, and every refusal that needs the op alone.
+// The op is a Convolution with group == in.chan == biases.out_chan (channel multiplier 1), in / out img:y:x:chan (in bfloat16, out bfloat16 | float), filts y:x:chan
+// bfloat16.  An UnsupErr names the field it is about
+struct conv_dw_geom_t { int B, C, H, W, KH, KW, SY, SX, PY, PX, OH, OW; bool relu, out_f32; };
+inline conv_dw_geom_t conv_dw_geom_of_op(op_base_t const &op) {
+  string const fn = "hip_conv_nhwc_dw";
+  if (op.get_type() != "Convolution") rt_err(fn + ": a function of op type Convolution, not " + op.get_type());
+  dims_t const &f = op.get_dims("filts"), &in = op.get_dims("in"), &out = op.get_dims("out"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
+  auto nhwc = [](dims_t const &d) { return d.sz() == 4 && d.names(0) == "img" && d.names(1) == "y" && d.names(2) == "x" && d.names(3) == "chan"; };
+  if (!nhwc(in) || !nhwc(out) || f.sz() != 3 || f.names(0) != "y" || f.names(1) != "x" || f.names(2) != "chan" || st.sz() != 2 || pad.sz() != 2 || in.tn != "bfloat16" || f.tn != "bfloat16" ||
+      (out.tn != "bfloat16" && out.tn != "float")) rt_err(fn + ": bfloat16 in img:y:x:chan and filts y:x:chan, bfloat16 | float out img:y:x:chan, stride / in_pad y:x");
+  conv_dw_geom_t g;
+  g.B = (int)in.dsz("img"); g.C = (int)in.dsz("chan"); g.H = (int)in.dsz("y"); g.W = (int)in.dsz("x"); g.KH = (int)f.dsz("y"); g.KW = (int)f.dsz("x");
+  g.SY = (int)st.dsz("y"); g.SX = (int)st.dsz("x"); g.PY = (int)pad.dsz("y"); g.PX = (int)pad.dsz("x"); g.OH = (int)out.dsz("y"); g.OW = (int)out.dsz("x");
+  g.relu = op.get_u32("conv_has_relu") != 0; g.out_f32 = out.tn == "float";
+  uint32_t const grp = op_group(op);
+  uint64_t const oc = op.get_dims("biases").dims_prod();
+  if (grp != (uint32_t)g.C) unsup_err(fn + ": group=" + std::to_string(grp) + " is not in.chan=" + std::to_string(g.C) + ": depthwise layers only (a grouped layer with in.chan/group > 1 has no channels-last form)");
+  if (oc != (uint64_t)g.C || f.dsz("chan") != (uint32_t)g.C || out.dsz("chan") != (uint32_t)g.C) unsup_err(fn + ": out_chan=" + std::to_string(oc) + " on in.chan=" + std::to_string(g.C) + ": channel multiplier 1 only (out_chan == in.chan == group)");
+  if (g.C % 8) unsup_err(fn + ": in.chan=" + std::to_string(g.C) + " is no multiple of 8 (a lane owns a 16-byte chunk of 8 channels)");
+  if (g.KH < 1 || g.KH > 7 || g.KW < 1 || g.KW > 7) unsup_err(fn + ": kern_sz " + std::to_string(g.KH) + " x " + std::to_string(g.KW) + ": kernels of 1..7 rows and columns");
+  if ((g.SY != 1 && g.SY != 2) || (g.SX != 1 && g.SX != 2)) unsup_err(fn + ": stride " + std::to_string(g.SY) + " x " + std::to_string(g.SX) + ": strides of 1 | 2");
+  if (g.PY < 0 || g.PY >= g.KH || g.PX < 0 || g.PX >= g.KW) unsup_err(fn + ": in_pad " + std::to_string(g.PY) + " x " + std::to_string(g.PX) + ": padding below the kernel size");
+  if (g.B < 1 || g.H < 1 || g.W < 1 || g.OH < 1 || g.OW < 1) rt_err(fn + ": empty tensors");
+  if (out.dsz("img") != (uint32_t)g.B || (g.H + 2 * g.PY - g.KH) / g.SY + 1 != g.OH || (g.W + 2 * g.PX - g.KW) / g.SX + 1 != g.OW) rt_err(fn + ": out dims do not match in / filts / stride / in_pad");
+  uint64_t const in_b = 2ull * g.B * g.C * g.H * g.W, out_b = (g.out_f32 ? 4ull : 2ull) * g.B * g.C * g.OH * g.OW;
+  if (in_b >= 0x7ffffff0ull || out_b >= 0x7ffffff0ull) unsup_err(fn + ": tensors of 2 GiB or more (32-bit offsets)");
+  for (char const *k : {"nhwc_residual", "nhwc_pool", "nhwc_post_pool", "nhwc_s2d"}) if (op.has(k) && op.get_u32(k)) unsup_err(fn + ": " + k + "=1: the depthwise kernel has no such form");
   return g;
 }
 

@@ -99,6 +99,9 @@ plan_t plan_conv_grp(conv_grp_geom_t const &g, int member, int num_cus, string c
 plan_t plan_conv_grp_slab_sum(plan_t const &main);   // the second launch of a sliced direct filter gradient
 bool conv_grp_has_slab_sum(plan_t const &p);
 long conv_grp_threads(conv_grp_geom_t const &g, int member, tile_cfg_t const &c, uint32_t *grid, uint32_t *block);   // -> the kernel's p.n; *grid workgroups of *block threads
+plan_t plan_conv_nhwc_dw(conv_dw_geom_t const &g, int num_cus, string const &tile);   // hip_conv_nhwc_dw (kernels/conv_nhwc_dw_bf16.hip); cfg: TY x TX x CB as BI x BJ x BK
+struct dw_launch_t { int n_ys = 0, n_xs = 0, n_cs = 0; uint32_t grid = 0, block = 0; long lds = 0; };   // the workgroup walk per image, the launch, the ring's bytes of LDS
+dw_launch_t conv_nhwc_dw_launch(conv_dw_geom_t const &g, tile_cfg_t const &c);
 plan_t plan_deconv(deconv_geom_t const &g, int member, int num_cus, string const &tile);   // the Deconvolution family (kernels/deconv_f32.hip); member: kDeconvFwd | kDeconvBckIn | kDeconvBckFilts
 plan_t plan_deconv_slab_sum(plan_t const &main);     // the second launch of a sliced filter gradient
 bool deconv_has_slab_sum(plan_t const &p);

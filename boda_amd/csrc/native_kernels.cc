@@ -85,6 +85,11 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
       (void)get_kernel(impl, host, gp);
       if (conv_grp_has_slab_sum(gp)) (void)get_kernel(impl, host, plan_conv_grp_slab_sum(gp)); }
     break;
+  case kFamConvNhwcDw:   // likewise (a tile of another kernel's form passes by: plan_conv_nhwc_dw)
+    { (void)fi.op.get_u32("conv_has_relu");
+      auto const ht = fi.op.str_vals.find("hip_tile");
+      (void)get_kernel(impl, host, plan_conv_nhwc_dw(conv_dw_geom_of_op(fi.op), host->nh_num_cus(), (ht != fi.op.str_vals.end() && !ht->second.empty()) ? ht->second : tune_of(impl, "conv_tile"))); }
+    break;
   case kFamDeconv:   // likewise: the op must be whole, the tile one the family has, the code objects built now
     { deconv_geom_t const dg = deconv_geom_of_op(fi.op, f->member);
       if (f->member == kDeconvBckBiases) { (void)get_kernel(impl, host, plan_bconv_biases()); break; }
@@ -875,6 +880,19 @@ void native_kernels_t::deconv(int member, deconv_geom_t const &g, float const *a
   int const TYk = (g.KH + g.SY - 1) / g.SY, TXk = (g.KW + g.SX - 1) / g.SX;
   last_launch.flops = member == kDeconvFwd ? 2.0 * g.B * g.OC * g.OH * g.OW * ((double)g.C * TYk * TXk) : 2.0 * K * g.C * ((double)g.OC * g.KH * g.KW);
   last_launch.algo_bytes = (double)f_b + in_b + out_b + (member == kDeconvFwd ? 4.0 * g.OC : 0.0);
+}
+void native_kernels_t::conv_nhwc_dw(conv_dw_geom_t const &g, void const *filts, float const *biases, void const *in, void *out) {
+  plan_t const p = plan_conv_nhwc_dw(g, host->nh_num_cus(), tune_of(impl, "conv_tile"));
+  kernel_t &k = get_kernel(impl, host, p);
+  dw_launch_t const l = conv_nhwc_dw_launch(g, p.cfg);
+  conv_dw_args_t a; memset(&a, 0, sizeof(a));
+  a.in = in; a.filts = filts; a.bias = biases; a.out = out; a.n_ys = l.n_ys; a.n_xs = l.n_xs; a.n_cs = l.n_cs;
+  a.in_bytes = (unsigned)(2ull * g.B * g.C * g.H * g.W); a.f_bytes = (unsigned)(2ull * g.KH * g.KW * g.C); a.out_bytes = (unsigned)((g.out_f32 ? 4ull : 2ull) * g.B * g.C * g.OH * g.OW);
+  void *params[] = {&a};
+  hip_err_chk(host->nh_launch(k.func, l.grid, 1, l.block, params), "hipModuleLaunchKernel(conv_nhwc_dw_bf16)");
+  last_launch.kernel = p.kname; last_launch.cfg = p.cfg; last_launch.grid = l.grid; last_launch.block = l.block;
+  last_launch.flops = 2.0 * g.B * g.OH * g.OW * (double)g.C * g.KH * g.KW;
+  last_launch.algo_bytes = (double)a.in_bytes + a.f_bytes + a.out_bytes + 4.0 * g.C;
 }
 void native_kernels_t::bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g) {
   kernel_t &k = get_kernel(impl, host, plan_bconv_biases());

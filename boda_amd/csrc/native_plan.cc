@@ -553,6 +553,49 @@ plan_t plan_conv_nhwc_patch(conv_geom_t const &g, int num_cus, string const &til
   return p;
 }
 
+// hip_conv_nhwc_dw (kernels/conv_nhwc_dw_bf16.hip): a depthwise layer on channels-last bf16 tensors.  A workgroup owns one image, TY output rows, TX output columns
+// and CB 8-channel chunks; its threads are TX x CB (chunk fastest), its LDS the two ring rows of ((TX-1)*SX + KW) x CB chunks.  Chosen from the op and the CU count:
+//   CB = the whole pel where it has at most 32 chunks (C <= 256), else 32 chunks (512 contiguous bytes per pel);
+//   TX = OW cut into the fewest equal segments of at most 256 / CB columns (at most 256 threads), fewer columns while the ring exceeds kDwLdsBudget;
+//   TY = 16 rows (the rows a strip re-reads above and below it: (KH - SY) / (16 SY) of the input), halved while the launch has fewer than two workgroups per CU.
+// A tile "dw:TYxTXxCB" forces the three (TX x CB <= 1024 threads, the ring within the budget); any other tile string -- one written for hip_conv_nhwc -- passes by.
+// cfg reports TY x TX x CB as BI x BJ x BK
+constexpr long kDwLdsBudget = 32 * 1024;   // bytes of LDS per workgroup: several workgroups stay resident per CU
+static long dw_lds_bytes(conv_dw_geom_t const &g, int TX, int CB) { return 2L * ((TX - 1) * g.SX + g.KW) * CB * 16; }
+plan_t plan_conv_nhwc_dw(conv_dw_geom_t const &g, int num_cus, string const &tile) {
+  string const fn = "hip_conv_nhwc_dw";
+  int const C8 = g.C / 8;
+  int TY, TX, CB;
+  if (tile.compare(0, 3, "dw:") == 0) {
+    char tail = 0;
+    if (sscanf(tile.c_str(), "dw:%dx%dx%d%c", &TY, &TX, &CB, &tail) != 3) unsup_err(fn + ": bad tile '" + tile + "' (dw:TYxTXxCB)");
+    if (TY < 1 || TY > 4096 || TX < 1 || CB < 1 || CB > C8 || (long)TX * CB > 1024 || TX > g.OW + 63 || dw_lds_bytes(g, TX, CB) > kDwLdsBudget)
+      unsup_err(fn + ": unsupported tile configuration " + tile + " (TY >= 1, 1 <= CB <= in.chan/8, TX x CB <= 1024 threads, ring within " + std::to_string(kDwLdsBudget) + " bytes of LDS)");
+  } else {
+    CB = std::min(C8, 32);
+    int const tx_max = std::max(1, 256 / CB), nseg = (g.OW + tx_max - 1) / tx_max;
+    TX = (g.OW + nseg - 1) / nseg;
+    while (TX > 1 && dw_lds_bytes(g, TX, CB) > kDwLdsBudget) TX = (TX + 1) / 2;
+    TY = std::min(g.OH, 16);
+    auto wgs = [&](int ty) { return (long)g.B * ((g.OH + ty - 1) / ty) * ((g.OW + TX - 1) / TX) * ((C8 + CB - 1) / CB); };
+    while (TY > 1 && wgs(TY) < 2L * num_cus) TY = (TY + 1) / 2;
+  }
+  plan_t p; p.src = kSrc_conv_nhwc_dw_bf16; p.kname = "bodahip_conv_nhwc_dw_bf16"; p.nhwc = true; p.bf16 = true;
+  tile_cfg_t &c = p.cfg; c = tile_cfg_t(); c.BI = TY; c.BJ = TX; c.BK = CB; c.WI = 1; c.WJ = 1; c.MINW = 1;
+  for (auto const &d : {std::make_pair("C8", C8), std::make_pair("CH", g.H), std::make_pair("CW", g.W), std::make_pair("COH", g.OH), std::make_pair("COW", g.OW), std::make_pair("KH", g.KH),
+                        std::make_pair("KW", g.KW), std::make_pair("SY", g.SY), std::make_pair("SX", g.SX), std::make_pair("PY", g.PY), std::make_pair("PX", g.PX), std::make_pair("RELU", (int)g.relu),
+                        std::make_pair("OUT_F32", (int)g.out_f32), std::make_pair("TY", TY), std::make_pair("TX", TX), std::make_pair("CB", CB)}) p.defs.push_back(string("-D") + d.first + "=" + std::to_string(d.second));
+  return p;
+}
+dw_launch_t conv_nhwc_dw_launch(conv_dw_geom_t const &g, tile_cfg_t const &c) {
+  dw_launch_t l;
+  l.n_ys = (g.OH + c.BI - 1) / c.BI; l.n_xs = (g.OW + c.BJ - 1) / c.BJ; l.n_cs = (g.C / 8 + c.BK - 1) / c.BK;
+  long const wgs = (long)g.B * l.n_ys * l.n_xs * l.n_cs;
+  if (wgs >= (1L << 31)) unsup_err("hip_conv_nhwc_dw: more than 2^31 workgroups");
+  l.grid = (uint32_t)wgs; l.block = (uint32_t)(c.BJ * c.BK); l.lds = dw_lds_bytes(g, c.BJ, c.BK);
+  return l;
+}
+
 // Rolling-rows form of the channels-last bf16 convolution (kernels/conv_nhwc_rows_bf16.hip): short-K layers of at most 64 out_chans whose time is their output --
 // the 7x7/2 stems after space-to-depth.  A workgroup of eight waves walks down a run of output rows of one image with the filters in registers; the rows land in an LDS
 // ring from which they are stored -- or pooled (+ LRN'd) without ever reaching memory (post).  Same k-slot order as the patch kernel (patch_cg): with an even tap count

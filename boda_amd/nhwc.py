@@ -125,6 +125,43 @@ def annotate(a: Op, out_tn: str = "bfloat16", allow_s2d: bool = True, allow_patc
     a.set_func_name(FUNC)
 
 
+DW_FUNC = "hip_conv_nhwc_dw"
+
+
+def dw_filts_dims(f: Dims) -> Dims:
+    """out_chan=C:in_chan=1:y:x -> the tap-major form y:x:chan: F[ky][kx][c] = filts_ref[c][0][ky][kx] (one 16-byte load gives a lane its 8 channels' weights of a tap)."""
+    return Dims(("y", "x", "chan"), (f.dsz("y"), f.dsz("x"), f.dsz("out_chan")), "bfloat16")
+
+
+def annotate_dw(a: Op, out_tn: str = "bfloat16") -> None:
+    """In place: the `hip_conv_nhwc_dw` form of an annotated depthwise Convolution (group == in.chan == out_chans; kernels/conv_nhwc_dw_bf16.hip) -- in / out
+    img:y:x:chan, filts tap-major y:x:chan, the originals as <arg>_ref.  What the kernel does not cover is refused by the field's name."""
+    g = a.conv_geom()
+    grp = a.get_u32("group")
+    if g["OC"] != g["C"] or grp != g["C"]:
+        raise UnsupErr(f"{DW_FUNC}: out_chan={g['OC']} on in.chan={g['C']}, group={grp}: channel multiplier 1 only (out_chan == in.chan == group)")
+    if g["C"] % 8:
+        raise UnsupErr(f"{DW_FUNC}: in.chan={g['C']} is no multiple of 8 (a lane owns a 16-byte chunk of 8 channels)")
+    if not (1 <= g["KH"] <= 7 and 1 <= g["KW"] <= 7):
+        raise UnsupErr(f"{DW_FUNC}: kern_sz {g['KH']} x {g['KW']}: kernels of 1..7 rows and columns")
+    if g["SY"] not in (1, 2) or g["SX"] not in (1, 2):
+        raise UnsupErr(f"{DW_FUNC}: stride {g['SY']} x {g['SX']}: strides of 1 | 2")
+    if not (0 <= g["PY"] < g["KH"] and 0 <= g["PX"] < g["KW"]):
+        raise UnsupErr(f"{DW_FUNC}: in_pad {g['PY']} x {g['PX']}: padding below the kernel size")
+    for an in ("in", "filts", "out"):
+        ref = a.get_dims(an)
+        a.nda_vals[an + "_ref"] = Nda(dims=ref, tn=ref.tn)
+    a.nda_vals["in"] = Nda(dims=nhwc_dims(a.get_dims("in_ref")), tn="bfloat16")
+    a.nda_vals["filts"] = Nda(dims=dw_filts_dims(a.get_dims("filts_ref")), tn="bfloat16")
+    a.nda_vals["out"] = Nda(dims=nhwc_dims(a.get_dims("out_ref"), out_tn, pad=False), tn=out_tn)
+    a.set_func_name(DW_FUNC)
+
+
+def _refuse_dw(a: Op, what: str) -> None:
+    if a.has_func_name() and a.get_func_name() == DW_FUNC:
+        raise UnsupErr(f"{what}: {DW_FUNC} (a depthwise convolution) has no such form: the kernel has no pooling, no residual epilogue and writes whole tensors")
+
+
 def pool_fusable(g: dict, in_hw: Tuple[int, int], kern: Tuple[int, int], stride: Tuple[int, int], pad: Tuple[int, int], avg: bool, out_f32: bool = False) -> bool:
     """Can a pooling (window kern, stride, pad; on planes in_hw) be taken into the 1x1 convolution `g` that consumes it?  Max pooling with stride 1 in front of a
     1x1 / stride-1 / unpadded convolution whose input plane is the pooling's output, a window of 2..25 positions, and a plane narrow enough for the LDS patch.
@@ -143,6 +180,7 @@ def fuse_pool(a: Op, pool_in: Dims, kern: Tuple[int, int], pad: Tuple[int, int])
     """In place: an annotated 1x1 hip_conv_nhwc function takes the max pooling in front of it (pool_fusable).  Its `in` becomes the POOLING's input, its filters take
     the input-patch form (one k-slot per channel group), and the window travels with the function: uint32 nhwc_pool, dims pool_sz / pool_pad.  The reference
     runs the two as two functions (test/rtc/pool.cucl, then the conv; src/rtc_fwd.cc:545-549); here the window maximum is taken while the MFMA B fragment is formed."""
+    _refuse_dw(a, "fuse_pool")
     if a.get_func_name() != FUNC or a.has("nhwc_s2d") or a.get_dims("filts").has("in_grp"):
         raise UnsupErr("fuse_pool: needs a plain hip_conv_nhwc function")
     none = lambda y, x: Nda(Dims(("y", "x"), (y, x), "none"), "none")
@@ -176,6 +214,7 @@ def fuse_post(a: Op, pool_out: Dims, kern, stride, pad, lrn=None) -> None:
     `out` becomes the POOLED tensor; window and LRN constants travel with the function (uint32 nhwc_post_pool, dims post_pool_sz / post_pool_stride / post_pool_pad, uint32
     nhwc_post_lrn = local size, floats post_lrn_alpha / post_lrn_beta / post_lrn_k).  The reference runs conv, pool and lrn as three functions (src/rtc_fwd.cc:495-503,
     545-549, test/rtc/pool.cucl, lrn.cucl); here the convolution's rows are pooled out of an LDS ring and its own output tensor is never written."""
+    _refuse_dw(a, "fuse_post")
     none = lambda y, x: Nda(Dims(("y", "x"), (y, x), "none"), "none")
     a.nda_vals["out_ref"] = Nda(dims=pool_out, tn=pool_out.tn)
     a.nda_vals["out"] = Nda(dims=nhwc_dims(pool_out, "bfloat16", pad=False), tn="bfloat16")
@@ -202,6 +241,7 @@ def fuse_residual(a: Op) -> None:
     conv_has_relu applies to the sum (kernels/conv_nhwc_bf16.hip -DRES=1).  Only the implicit-GEMM kernel has that epilogue: the input-patch form of filts (which also
     binds the rolling-rows kernel), a pooling fused in front or behind are refused here, sibling groups / sets / multi-problem launches refuse a flagged member, the
     planner refuses the two-kernel form of the K slices, the call an output channel slice."""
+    _refuse_dw(a, "fuse_residual")
     if not a.has_func_name() or a.get_func_name() != FUNC:
         raise UnsupErr(f"fuse_residual: {a.get_func_name() if a.has_func_name() else a.get_type()!r} is not a plain {FUNC} function")
     if a.has("nhwc_pool"):
@@ -234,6 +274,8 @@ def annotate_group(annos: List[Op]) -> Op:
     stacked along out_chan (member m at rows [oc0_m, oc0_m + out_chans_m), oc0_m = the earlier members' out_chans each rounded up to grp.pad), outputs
     out_0 .. out_{n-1}.  The horizontal counterpart of what the reference does vertically when it fuses a ReLU into its conv (src/rtc_fwd.cc:486-493)."""
     a0 = annos[0]
+    for a in annos:
+        _refuse_dw(a, "hip_conv_nhwc_grp")
     if not (2 <= len(annos) <= 4):
         raise UnsupErr("hip_conv_nhwc_grp: 2..4 members")
     for a in annos:
@@ -278,6 +320,7 @@ def annotate_multi(annos: List[Op]) -> Op:
     nv = {"multi": Nda(dims=Dims(("n",), (len(annos),), "none"), tn="none")}
     relu = [a.get_u32("conv_has_relu") for a in annos]
     for m, a in enumerate(annos):
+        _refuse_dw(a, "hip_conv_nhwc_multi")
         if a.has_func_name() and a.get_func_name() == FUNC and has_residual(a):
             raise UnsupErr("hip_conv_nhwc_multi: a member with nhwc_residual=1 (the residual epilogue belongs to a plain call)")
         if not multi_eligible(a):
@@ -315,6 +358,7 @@ def annotate_set(annos: List[Op]) -> Op:
     relu = [a.get_u32("conv_has_relu") for a in annos]
     out_tn = lambda a: a.get_dims("out_0" if a.get_func_name() == GRP_FUNC else "out").tn
     for m, a in enumerate(annos):
+        _refuse_dw(a, "hip_conv_nhwc_set")
         if out_tn(a) != out_tn(annos[0]):
             raise UnsupErr("hip_conv_nhwc_set: members differ in output type")
         if a.get_func_name() == GRP_FUNC:     # a horizontally fused member (hip_conv_nhwc_grp): its args keep their names, plus the member's suffix
@@ -408,6 +452,16 @@ CUCL_GLOBAL_KERNEL void hip_conv_nhwc_xpose_filts_patch( GASQ float const * cons
   }
   filts[i] = r;
 }
+// filts_ref out_chan=C:in_chan=1:y:x float -> the depthwise kernel's tap-major filts y:x:chan bf16: one thread per 16-byte chunk (ky, kx, 8 channels); C % 8 == 0
+CUCL_GLOBAL_KERNEL void hip_conv_nhwc_xpose_filts_dw( GASQ float const * const filts_ref, GASQ xp_bf16x8_t * const filts, uint32_t const n, uint32_t const C8,
+                                                       uint32_t const KHW ) {
+  uint32_t const i = GLOB_ID_1D;
+  if( i >= n ) { return; }
+  uint32_t const q = i % C8, t = i / C8;
+  xp_bf16x8_t r;
+  for( uint32_t e = 0; e != 8; ++e ) { r[e] = (__bf16)filts_ref[( 8*q + e )*KHW + t]; }
+  filts[i] = r;
+}
 // out img:y:x:chan (bf16 / float) -> out_ref img:chan:y:x float
 CUCL_GLOBAL_KERNEL void hip_conv_nhwc_xpose_out_bf16( GASQ __bf16 const * const out, GASQ float * const out_ref, uint32_t const n, uint32_t const C, uint32_t const HW ) {
   // CUCL IX GLOB_ID_1D out_ref
@@ -428,6 +482,7 @@ XPOSE_FUNCS: Dict[str, List[str]] = {
     "hip_conv_nhwc_xpose_in": ["in_ref", "in", "n", "C", "H", "W", "C2", "C8", "H2", "W2", "S", "PRY", "PRX"],
     "hip_conv_nhwc_xpose_filts": ["filts_ref", "filts", "n", "C", "KH", "KW", "C2", "C8", "KH2", "KW2", "S", "OFY", "OFX"],
     "hip_conv_nhwc_xpose_filts_patch": ["filts_ref", "filts", "n", "C", "KH", "KW", "OC", "C2", "KH2", "KW2", "S", "OFY", "OFX"],
+    "hip_conv_nhwc_xpose_filts_dw": ["filts_ref", "filts", "n", "C8", "KHW"],
     "hip_conv_nhwc_xpose_out_bf16": ["out", "out_ref", "n", "C", "HW"],
     "hip_conv_nhwc_xpose_out_f32": ["out", "out_ref", "n", "C", "HW"],
 }
@@ -502,6 +557,10 @@ def xpose_call(arg: str, ref_vn: str, vn: str, ref_dims: Dims, dims: Dims, anno:
             _spec_compile(rtc, name, XPOSE_IN_SPEC_SRC, sub, ["in_ref", "in", "n"])
             return RtcFuncCall(name, {"in_ref": RtcArg.var(ref_vn), "in": RtcArg.var(vn), "n": _u32(n)}, tpb=_TPB, blks=(n + _TPB - 1) // _TPB)
         return RtcFuncCall("hip_conv_nhwc_xpose_in", am, tpb=_TPB, blks=(n + _TPB - 1) // _TPB)
+    if arg == "filts" and dims.names == ("y", "x", "chan"):     # the depthwise kernel's tap-major filters
+        n = dims.dims_prod() // 8
+        am = {"filts_ref": RtcArg.var(ref_vn), "filts": RtcArg.var(vn), "n": _u32(n), "C8": _u32(dims.dsz("chan") // 8), "KHW": _u32(dims.dsz("y") * dims.dsz("x"))}
+        return RtcFuncCall("hip_conv_nhwc_xpose_filts_dw", am, tpb=_TPB, blks=(n + _TPB - 1) // _TPB)
     if arg == "filts" and dims.has("in_grp"):     # F' for the input-patch kernel
         n = dims.dims_prod() // 8
         C = ref_dims.dsz("in_chan")
