@@ -158,9 +158,9 @@ def add_codegen_annotations(op: Op, tune: OpTune, tile_wisdom=None) -> Op:
         raise UnsupErr(f"op type {t!r} is not on the conv_fwd / sgemm hot path")
     if not tune.hip_exact and native and not tune.use_culibs and tune.hip_dtype != "bf16":
         a.str_vals["hip_exact"] = "0"   # travels with the function, like hip_tile
-    own_tile = {CONV_GRP_FUNC: is_grp_tile, CONV_NHWC_DW_FUNC: is_dw_tile}.get(a.get_func_name(), lambda t: True)
+    own_tile = {CONV_GRP_FUNC: is_grp_tile, CONV_NHWC_DW_FUNC: is_dw_tile, CONV_NHWC_DW_PW_FUNC: is_dwpw_tile}.get(a.get_func_name(), lambda t: not is_dwpw_tile(t))
     if tune.hip_tile and native and not tune.use_culibs and own_tile(tune.hip_tile):
-        a.str_vals["hip_tile"] = tune.hip_tile   # travels with the function: the backend applies it to this function's calls only (a grouped or depthwise op: its own form only)
+        a.str_vals["hip_tile"] = tune.hip_tile   # travels with the function: the backend applies it to this function's calls only (a grouped or depthwise op: its own form only; a dwpw: tile belongs to the fused pair alone, nhwc.annotate_dw_pw)
     return a
 
 
@@ -191,6 +191,15 @@ CONV_NHWC_DW_FUNC = "hip_conv_nhwc_dw"
 def is_dw_tile(tile: str) -> bool:
     """Is `tile` hip_conv_nhwc_dw's own form, dw:TYxTXxCB (output rows, output columns, 8-channel chunks of a workgroup)?  Any other tile passes a depthwise layer by."""
     return tile.startswith("dw:")
+
+
+# a depthwise layer and the 1x1 convolution that alone reads it as one launch (nhwc.annotate_dw_pw; kernels/conv_nhwc_dwpw_bf16.hip; DESIGN.md section 3.27)
+CONV_NHWC_DW_PW_FUNC = "hip_conv_nhwc_dw_pw"
+
+
+def is_dwpw_tile(tile: str) -> bool:
+    """Is `tile` hip_conv_nhwc_dw_pw's own form, dwpw:TYxTXxCB (output rows, output columns of a workgroup's pel tile, 8-channel chunks of a depthwise pass)?"""
+    return tile.startswith("dwpw:")
 
 
 def is_depthwise(op: Op) -> bool:
@@ -1095,6 +1104,7 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_bconv_in_grp": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),
     "hip_bconv_filts_grp": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT")),
     "hip_conv_nhwc_dw": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),   # a depthwise layer, channels-last bf16
+    "hip_conv_nhwc_dw_pw": (("filts", "IN"), ("biases", "IN"), ("filts2", "IN"), ("biases2", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),   # a depthwise layer + the 1x1 convolution behind it
     # a Deconvolution / BckDeconv: the lists of hip_conv and of BckConv's three gradients without their optional args; Caffe's Crop and its gradient
     "hip_deconv": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),
     "hip_deconv_bck_in": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),

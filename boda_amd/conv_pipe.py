@@ -639,8 +639,15 @@ class ConvPipeFwd:
 
     def __init__(self, rtc: HipCompute, op_tune: Optional[OpTune] = None, per_call_fn: str = "", enable_double_run: bool = False, fuse_siblings: bool = True, fuse_levels: bool = True, fuse_pools: bool = True, sets_take_groups: bool = True,
                  spec_fwd: bool = True, fuse_pool_lrn="pool_first", fuse_k1_chains: bool = True, fuse_f32_pools: Optional[bool] = None, fuse_post: bool = True, filts_kmajor_once: bool = True,
-                 fuse_residual: bool = True):
+                 fuse_residual: bool = True, fuse_dw_pw=False):
         self.rtc, self.op_tune = rtc, op_tune or OpTune()
+        # channels-last bf16 nets, opt-in: a depthwise convolution whose output (after its folded BatchNorm / Scale / ReLU run) is read by ONE op, a 1x1 / stride-1 /
+        # unpadded convolution, runs with it as one hip_conv_nhwc_dw_pw launch (kernels/conv_nhwc_dwpw_bf16.hip): the depthwise output stays in LDS, its write + read are
+        # gone, and so is its node -- asking for it is an RtErr.  "all": every pair the kernel covers; True: the pairs nhwc.dw_pw_pays picks;
+        # False (default): none
+        self.fuse_dw_pw = fuse_dw_pw
+        self.fused_dw_pw: List[Tuple[str, str]] = []     # (depthwise tag, pointwise tag) of each fused pair
+        self._dwpw_nodes: Dict[str, str] = {}            # node of a fused depthwise layer (never materialised) -> the fused call's tag
         # channels-last bf16 nets: an Eltwise of two nodes (a ResNet block's res = ReLU(shortcut + branch2c)) is taken into the epilogue of the convolution that writes its
         # later-defined bottom (nhwc.fuse_residual, kernels/conv_nhwc_bf16.hip -DRES=1): the shortcut is read once, the convolution's own output is never written or read
         # again, the Eltwise and its ReLU emit no call.  False: every Eltwise runs as nhwc_eltwise.  No net without an Eltwise is touched either way
@@ -991,6 +998,33 @@ class ConvPipeFwd:
                     if with_lrn is not None:
                         post_of[with_lrn.tag] = q.tag
                     break
+        # depthwise -> 1x1 pairs (channels-last bf16 nets; see fuse_dw_pw): decided behind the residual, pooling and post fusions, whose flags on the 1x1 convolution
+        # rule a pair out (nhwc.dw_pw_applies); the planner has the last word
+        dwpw_first: Dict[str, PipeOp] = {}     # tag of the 1x1 convolution -> the depthwise convolution
+        dwpw_lazy = set()                       # tags of the fused depthwise convolutions
+        if self.nhwc and self.fuse_dw_pw and self.op_tune.hip_dtype == "bf16":
+            from .rtc import explain_plan
+            from .cnn_op import is_dwpw_tile
+            rd_d: Dict[str, List[PipeOp]] = {}
+            for o in cp.ops:
+                if o.tag not in fused:
+                    for b in (o.bots or (o.bot,)):
+                        rd_d.setdefault(b, []).append(o)
+            busy_tops = {o.top for o in cp.ops if o.in_place and o.tag not in fused and o.type != "Dropout"}
+            for a_ in cp.ops:
+                rd = rd_d.get(a_.top, [])
+                if a_.type != "Convolution" or annos[a_.tag].get_func_name() != _nhwc.DW_FUNC or len(rd) != 1 or rd[0].type != "Convolution" or a_.top in busy_tops or a_.top == cp.out_node():
+                    continue
+                b_ = rd[0]
+                if b_.tag in res_fold or b_.top in self.slices or not _nhwc.dw_pw_applies(annos[a_.tag], annos[b_.tag]):
+                    continue
+                if self.fuse_dw_pw != "all" and not _nhwc.dw_pw_pays(annos[a_.tag], annos[b_.tag]):
+                    continue
+                try:
+                    explain_plan(_nhwc.annotate_dw_pw(annos[a_.tag], annos[b_.tag], self.op_tune.hip_tile if is_dwpw_tile(self.op_tune.hip_tile) else ""), getattr(self, "_num_cus", 256))
+                except (UnsupErr, RtErr):
+                    continue
+                dwpw_first[b_.tag] = a_; dwpw_lazy.add(a_.tag); self.fused_dw_pw.append((a_.tag, b_.tag)); self._dwpw_nodes[a_.top] = a_.tag + "+" + b_.tag
         # pooling <-> LRN pairs (channels-last nets, specialised kernels): see fuse_pool_lrn
         pl_second: Dict[str, str] = {}     # tag of the second op of a pair -> tag of the first
         if self.nhwc and self.spec_fwd and self.fuse_pool_lrn:
@@ -1022,7 +1056,7 @@ class ConvPipeFwd:
         if self.nhwc and self.fuse_siblings:
             by_key: Dict[tuple, List[PipeOp]] = {}
             for o in cp.ops:
-                if o.type == "Convolution" and o.group == 1 and not annos[o.tag].has("nhwc_s2d") and not annos[o.tag].get_dims("filts").has("in_grp") and o.tag not in res_fold:   # (a depthwise layer is a call of its own)
+                if o.type == "Convolution" and o.group == 1 and not annos[o.tag].has("nhwc_s2d") and not annos[o.tag].get_dims("filts").has("in_grp") and o.tag not in res_fold and o.tag not in dwpw_first:   # (a depthwise layer is a call of its own; so is a fused depthwise + 1x1 pair)
                     by_key.setdefault((o.bot, tuple(o.kern_sz), tuple(o.stride), tuple(o.in_pad), has_relu[o.tag]), []).append(o)
             for members0 in by_key.values():
                 for members in sibling_runs(cp.ops, members0, fused):
@@ -1065,8 +1099,21 @@ class ConvPipeFwd:
                 etop = res_fold[op.tag][0].top
                 if etop not in made:
                     rtc.create_var_with_dims(etop, vd(etop)); self._vars.append(etop); made.add(etop)
-            elif not op.in_place and op.top not in made and op.top not in self.slices:
+            elif not op.in_place and op.top not in made and op.top not in self.slices and op.tag not in dwpw_lazy:   # (a fused depthwise layer's node does not exist)
                 rtc.create_var_with_dims(op.top, vd(op.top)); self._vars.append(op.top); made.add(op.top)
+            if op.tag in dwpw_lazy:            # emitted with the 1x1 convolution that reads it
+                continue
+            if op.tag in dwpw_first:           # ONE call from the depthwise layer's input to this convolution's output, on both layers' (folded) params
+                first = dwpw_first[op.tag]; fa, pa = annos[first.tag], annos[op.tag]
+                fa.nda_vals["conv_has_relu"].v = (has_relu[first.tag],); pa.nda_vals["conv_has_relu"].v = (has_relu[op.tag],)
+                from .cnn_op import is_dwpw_tile
+                danno = _nhwc.annotate_dw_pw(fa, pa, self.op_tune.hip_tile if is_dwpw_tile(self.op_tune.hip_tile) else ""); ftag = first.tag + "+" + op.tag; annos[ftag] = danno
+                dfn = f"{_nhwc.DW_PW_FUNC}__{cp.name}_{first.tag}"
+                rtc.compile([RtcFuncInfo(dfn, "", [a for a, _ in NATIVE_ARGS[_nhwc.DW_PW_FUNC]], danno)]); self._funcs.append(dfn)
+                dam = {"filts": RtcArg.var(first.tag + "_filts"), "biases": RtcArg.var(first.tag + "_biases"), "filts2": RtcArg.var(op.tag + "_filts"), "biases2": RtcArg.var(op.tag + "_biases"),
+                       "in": RtcArg.var(vn(first.bot)), "stride": RtcArg.ref(danno.get_dims("stride")), "in_pad": RtcArg.ref(danno.get_dims("in_pad")), "out": RtcArg.var(op.top)}
+                self.fwd_calls.append(FwdCall(ftag, RtcFuncCall(dfn, dam), _nhwc.DW_PW_FUNC, cp.conv_op(first).flops() + cp.conv_op(op).flops()))
+                continue
             if op.type == "Convolution" and op.tag in group_of:
                 grp = group_of[op.tag]
                 if grp[0].tag in grp_done:
@@ -1450,6 +1497,8 @@ class ConvPipeFwd:
         for v in to_get_vns:
             if v in getattr(self, "_res_nodes", {}):
                 raise RtErr(f"node {v!r} is never written: its convolution adds the shortcut in its epilogue and writes {self._res_nodes[v]!r} (ConvPipeFwd(fuse_residual=False) keeps it)")
+            if v in self._dwpw_nodes:
+                raise RtErr(f"node {v!r} is never written: its depthwise convolution runs inside the call {self._dwpw_nodes[v]!r} and its output stays in LDS (ConvPipeFwd(fuse_dw_pw=False) keeps it)")
             if v in self._lazy:      # (a fused pooling's output: no call of the pass writes it)
                 self._materialise(v)
             if v in self.slices:     # a conv output that only exists as a channel range of its Concat output
@@ -1591,4 +1640,5 @@ class ConvPipeFwd:
         self._km_params, self._affine_params, self._conv_folds, self._res_nodes = [], [], [], {}
         self.fused_residuals = {"folded": [], "unfolded": {}}
         self.fused_post, self._lazy_pre = {}, {}
+        self.fused_dw_pw, self._dwpw_nodes = [], {}
         self.k1_chains, self._lazy, self.fused_pools, self.fused_pool_lrn, self.level_sets, self.lds_pool_lrn = [], {}, {}, {}, [], set()   # (a second init() starts from a clean slate)

@@ -349,6 +349,14 @@ struct conv_dw_args_t {
 };
 static_assert(sizeof(conv_dw_args_t) == 64 && __builtin_offsetof(conv_dw_args_t, n_ys) == 32 && __builtin_offsetof(conv_dw_args_t, in_bytes) == 44, "conv_dw_args_t layout");
 
+// kernels/conv_nhwc_dwpw_bf16.hip: a depthwise convolution and the 1x1 convolution behind it as one launch (hip_conv_nhwc_dw_pw); geometry and work split are -D constants
+struct conv_dwpw_args_t {
+  void const *in; void const *filts; float const *bias; void const *filts2; float const *bias2; void *out;   // in img:y:x:chan bf16, filts y:x:chan bf16, filts2 out_chan:1:1:in_chan bf16, biases float, out img:y:x:chan bf16 | float
+  int n_ys, n_xs;               // the workgroup walk per image: row strips, column segments (the segment is the fastest coordinate of blockIdx.x)
+  unsigned in_bytes, f_bytes, f2_bytes, out_bytes;
+};
+static_assert(sizeof(conv_dwpw_args_t) == 72 && __builtin_offsetof(conv_dwpw_args_t, n_ys) == 48 && __builtin_offsetof(conv_dwpw_args_t, in_bytes) == 56, "conv_dwpw_args_t layout");
+
 #pragma pop_macro("CH")
 #pragma pop_macro("CIN")
 #pragma pop_macro("COH")

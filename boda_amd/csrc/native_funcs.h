@@ -11,10 +11,11 @@ namespace bodahip {
 
 // the family (func_family_t of rtc_types.h) selects the handler (native_run.cc, native_kernels.cc: check_compile_time); handlers switch on the member, never on the name
 inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf", "loss", "conv_grp", "deconv", "conv_nhwc_dw"};
-// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform.  kFamLoss: 1 fwd | 2 norm | 3 bck (loss_op_t::kind).  kFamConvGrp: 1 fwd | 2 bck_in | 3 bck_filts.  kFamDeconv: 1 fwd | 2 bck_in | 3 bck_biases | 4 bck_filts
+// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform.  kFamLoss: 1 fwd | 2 norm | 3 bck (loss_op_t::kind).  kFamConvGrp: 1 fwd | 2 bck_in | 3 bck_filts.  kFamDeconv: 1 fwd | 2 bck_in | 3 bck_biases | 4 bck_filts.  kFamConvNhwcDw: 0 the depthwise layer | 1 the depthwise + pointwise pair
 enum { kConvF32 = 0, kConvAlias = 1, kConvBf16 = 2, kConvWinograd = 3 };            // (the alias: hip_conv's contract without its fused pooling and filts_km)
 enum { kBconvIn = 1, kBconvBiases = 2, kBconvFilts = 3, kBconvFiltsBiases = 4 };   // (4 is opt-in: never one of the bare op's three calls)
 enum { kConvGrpFwd = 1, kConvGrpBckIn = 2, kConvGrpBckFilts = 3 };                  // (a grouped convolution and its data / filter gradients; the bias gradient knows no groups)
+enum { kConvNhwcDw = 0, kConvNhwcDwPw = 1 };                                          // (a depthwise layer alone | with the 1x1 convolution that alone reads it, one launch)
 enum { kDeconvFwd = 1, kDeconvBckIn = 2, kDeconvBckBiases = 3, kDeconvBckFilts = 4 };   // (a Deconvolution and its three gradients in BckConv's call order; the bias gradient is hip_bconv_biases' sum under this family's op type)
 enum { kOpPoolYx = 1, kOpSpreading = 2, kOpLrnSb = 3, kOpBckLrn = 4, kOpZeroIfNonPos = 5, kOpSoftmax = 6, kOpSmGradAndLoss = 7, kOpSumLossOverImgs = 8, kOpReduce = 9,
        kOpDropout = 10, kOpConcat = 11, kOpSplit = 12, kOpChanAffine = 13, kOpCrop = 15, kOpCropBck = 16 };   // (14 is bodahip_shard_sum, which no function names)
@@ -71,7 +72,7 @@ inline constexpr char kWhyBnfOneDevice[] = "(a BatchNorm on its running pair, th
 inline constexpr char kWhyLossOneDevice[] = "(the full softmax loss, the hip_softmax_loss_* / hip_loss_norm family) counts the pels that are not ignored and sums loss_per_pel over the WHOLE batch, which would need a cross-device reduction, and takes vars of exactly its op's dims, not img shards; a loss with a LossSpec on several devices is out of scope";
 inline constexpr char kWhyConvGrpOneDevice[] = "(a grouped convolution, the hip_conv_grp / hip_bconv_in_grp / hip_bconv_filts_grp family) takes vars of exactly its op's dims, not img shards, and hip_bconv_filts_grp sums over the images of the WHOLE batch, which would need a cross-device reduction; grouped layers on several devices are out of scope";
 inline constexpr char kWhyDeconvOneDevice[] = "(a Deconvolution, the hip_deconv / hip_deconv_bck_in / hip_deconv_bck_filts / hip_deconv_bck_biases family) takes vars of exactly its op's dims, not img shards, and its filter and bias gradients sum over the images of the WHOLE batch, which would need a cross-device reduction; Deconvolution layers on several devices are out of scope";
-inline constexpr char kWhyConvNhwcDwOneDevice[] = "(a depthwise channels-last bf16 convolution, hip_conv_nhwc_dw) takes vars of exactly its op's dims, not img shards: the image count is a constant of its specialised kernel; depthwise layers on several devices are out of scope";
+inline constexpr char kWhyConvNhwcDwOneDevice[] = "(a depthwise channels-last bf16 convolution, hip_conv_nhwc_dw / hip_conv_nhwc_dw_pw) takes vars of exactly its op's dims, not img shards: the image count is a constant of its specialised kernel; depthwise layers on several devices are out of scope";
 inline constexpr char const *why_one_device(func_family_t family) { return family == kFamLoss ? kWhyLossOneDevice : family == kFamConvGrp ? kWhyConvGrpOneDevice : family == kFamDeconv ? kWhyDeconvOneDevice : family == kFamConvNhwcDw ? kWhyConvNhwcDwOneDevice : kWhyBnfOneDevice; }
 inline constexpr native_func_t kNativeFuncs[] = {
   // sgemm, a:K:M b:K:N c:M:N (test/rtc/cublas_sgemm.cucl:1-4); Convolution in reference layout (test/rtc/cudnn_conv.cucl:1-7)
@@ -168,6 +169,9 @@ inline constexpr native_func_t kNativeFuncs[] = {
   // filts tap-major y:x:chan.  hip_conv's arg list without its optional arg; no flag; one device only (why_one_device).  A family of its own: the rows of kFamConv and
   // kFamConvNhwc are pinned.  In front of the loss rows, like the grouped rows
   {"hip_conv_nhwc_dw", kFamConvNhwcDw, 0, nullptr, {"Convolution"}, {BODAHIP_CONV_ARGS}, {}, kVarNone, 0, {}, kBeHip, kOneDevice},
+  // the depthwise layer and the 1x1 convolution that alone reads it as one launch (kernels/conv_nhwc_dwpw_bf16.hip): hip_conv_k1_chain's arg list -- filts / biases
+  // the depthwise layer's, filts2 (out_chan:y:x:in_chan, 1x1) / biases2 the pointwise layer's; the two ReLUs ride in the op (conv_has_relu, conv2_has_relu)
+  {"hip_conv_nhwc_dw_pw", kFamConvNhwcDw, kConvNhwcDwPw, nullptr, {"Convolution"}, {{"filts", kIn}, {"biases", kIn}, {"filts2", kIn}, {"biases2", kIn}, {"in", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip, kOneDevice},
   // the full SoftmaxWithLoss (this backend's own; kernels/loss_f32.hip): what a head with a LossSpec lowers to -- loss_weight, ignore_label, planes, the four
   // normalisers.  hip_softmax_loss_bck reads s = weight / Z from loss_state on the device.  One device only (why_one_device).  In front of the data and eval rows,
   // which stay the table's last four
@@ -285,6 +289,40 @@ inline conv_dw_geom_t conv_dw_geom_of_op(op_base_t const &op) {
   if (in_b >= 0x7ffffff0ull || out_b >= 0x7ffffff0ull) unsup_err(fn + ": tensors of 2 GiB or more (32-bit offsets)");
   for (char const *k : {"nhwc_residual", "nhwc_pool", "nhwc_post_pool", "nhwc_s2d"}) if (op.has(k) && op.get_u32(k)) unsup_err(fn + ": " + k + "=1: the depthwise kernel has no such form");
   return g;
+}
+
+// hip_conv_nhwc_dw_pw (kFamConvNhwcDw, member kConvNhwcDwPw): likewise.  The op is the depthwise function's op with the pointwise layer's filts2 out_chan:y:x:in_chan
+// (1 x 1, in_chan == in.chan) / biases2 and that layer's out img:y:x:chan (out_chan channels); uint32 conv2_has_relu is the pointwise layer's ReLU.  The kernel's scope:
+// in.chan a multiple of 8 and at most 1024, out_chan a multiple of 8, depthwise kernels of 1..5 rows and columns, strides 1 | 2, padding below the kernel size
+struct conv_dwpw_geom_t { conv_dw_geom_t d; int OC; bool relu2; };   // (d.relu: the depthwise layer's; d.out_f32: the pair's out)
+inline conv_dwpw_geom_t conv_dwpw_geom_of_op(op_base_t const &op) {
+  string const fn = "hip_conv_nhwc_dw_pw";
+  if (op.get_type() != "Convolution") rt_err(fn + ": a function of op type Convolution, not " + op.get_type());
+  dims_t const &f = op.get_dims("filts"), &f2 = op.get_dims("filts2"), &in = op.get_dims("in"), &out = op.get_dims("out"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
+  auto nhwc = [](dims_t const &d) { return d.sz() == 4 && d.names(0) == "img" && d.names(1) == "y" && d.names(2) == "x" && d.names(3) == "chan"; };
+  if (!nhwc(in) || !nhwc(out) || f.sz() != 3 || f.names(0) != "y" || f.names(1) != "x" || f.names(2) != "chan" || st.sz() != 2 || pad.sz() != 2 || in.tn != "bfloat16" || f.tn != "bfloat16" ||
+      f2.sz() != 4 || f2.names(0) != "out_chan" || f2.names(1) != "y" || f2.names(2) != "x" || f2.names(3) != "in_chan" || f2.tn != "bfloat16" || (out.tn != "bfloat16" && out.tn != "float"))
+    rt_err(fn + ": bfloat16 in img:y:x:chan, filts y:x:chan and filts2 out_chan:y:x:in_chan, bfloat16 | float out img:y:x:chan, stride / in_pad y:x");
+  conv_dwpw_geom_t r; conv_dw_geom_t &g = r.d;
+  g.B = (int)in.dsz("img"); g.C = (int)in.dsz("chan"); g.H = (int)in.dsz("y"); g.W = (int)in.dsz("x"); g.KH = (int)f.dsz("y"); g.KW = (int)f.dsz("x");
+  g.SY = (int)st.dsz("y"); g.SX = (int)st.dsz("x"); g.PY = (int)pad.dsz("y"); g.PX = (int)pad.dsz("x"); g.OH = (int)out.dsz("y"); g.OW = (int)out.dsz("x");
+  g.relu = op.get_u32("conv_has_relu") != 0; r.relu2 = op.get_u32("conv2_has_relu") != 0; g.out_f32 = out.tn == "float"; r.OC = (int)f2.dsz("out_chan");
+  uint32_t const grp = op_group(op);
+  if (grp != (uint32_t)g.C || f.dsz("chan") != (uint32_t)g.C || op.get_dims("biases").dims_prod() != (uint64_t)g.C) unsup_err(fn + ": group=" + std::to_string(grp) + ", filts.chan=" + std::to_string(f.dsz("chan")) + " on in.chan=" + std::to_string(g.C) + ": a depthwise first layer with channel multiplier 1 only");
+  if (g.C % 8 || g.C > 1024) unsup_err(fn + ": in.chan=" + std::to_string(g.C) + ": a multiple of 8 of at most 1024 (the workgroup's tile of the intermediate holds every channel in LDS)");
+  if (f2.dsz("y") != 1 || f2.dsz("x") != 1) unsup_err(fn + ": filts2 kern_sz " + std::to_string(f2.dsz("y")) + " x " + std::to_string(f2.dsz("x")) + ": the second layer is a 1 x 1 / stride-1 / unpadded convolution");
+  if (f2.dsz("in_chan") != (uint32_t)g.C) rt_err(fn + ": filts2.in_chan=" + std::to_string(f2.dsz("in_chan")) + " is not in.chan=" + std::to_string(g.C));
+  if (r.OC < 8 || r.OC % 8) unsup_err(fn + ": filts2.out_chan=" + std::to_string(r.OC) + " is no multiple of 8 (a lane stores quads of out_chans)");
+  if (op.get_dims("biases2").dims_prod() != (uint64_t)r.OC || out.dsz("chan") != (uint32_t)r.OC) rt_err(fn + ": biases2 / out.chan disagree with filts2.out_chan=" + std::to_string(r.OC));
+  if (g.KH < 1 || g.KH > 5 || g.KW < 1 || g.KW > 5) unsup_err(fn + ": kern_sz " + std::to_string(g.KH) + " x " + std::to_string(g.KW) + ": depthwise kernels of 1..5 rows and columns");
+  if ((g.SY != 1 && g.SY != 2) || (g.SX != 1 && g.SX != 2)) unsup_err(fn + ": stride " + std::to_string(g.SY) + " x " + std::to_string(g.SX) + ": strides of 1 | 2");
+  if (g.PY < 0 || g.PY >= g.KH || g.PX < 0 || g.PX >= g.KW) unsup_err(fn + ": in_pad " + std::to_string(g.PY) + " x " + std::to_string(g.PX) + ": padding below the kernel size");
+  if (g.B < 1 || g.H < 1 || g.W < 1 || g.OH < 1 || g.OW < 1) rt_err(fn + ": empty tensors");
+  if (out.dsz("img") != (uint32_t)g.B || (g.H + 2 * g.PY - g.KH) / g.SY + 1 != g.OH || (g.W + 2 * g.PX - g.KW) / g.SX + 1 != g.OW) rt_err(fn + ": out dims do not match in / filts / stride / in_pad");
+  uint64_t const in_b = 2ull * g.B * g.C * g.H * g.W, out_b = (g.out_f32 ? 4ull : 2ull) * g.B * r.OC * g.OH * g.OW;
+  if (in_b >= 0x7ffffff0ull || out_b >= 0x7ffffff0ull) unsup_err(fn + ": tensors of 2 GiB or more (32-bit offsets)");
+  for (char const *k : {"nhwc_residual", "nhwc_pool", "nhwc_post_pool", "nhwc_s2d"}) if (op.has(k) && op.get_u32(k)) unsup_err(fn + ": " + k + "=1: the fused pair has no such form");
+  return r;
 }
 
 // the Deconvolution family (kFamDeconv): what both backends read from the function's op, and every refusal that needs the op alone.  The geometry is the LAYER's:

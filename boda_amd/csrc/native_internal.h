@@ -102,6 +102,8 @@ long conv_grp_threads(conv_grp_geom_t const &g, int member, tile_cfg_t const &c,
 plan_t plan_conv_nhwc_dw(conv_dw_geom_t const &g, int num_cus, string const &tile);   // hip_conv_nhwc_dw (kernels/conv_nhwc_dw_bf16.hip); cfg: TY x TX x CB as BI x BJ x BK
 struct dw_launch_t { int n_ys = 0, n_xs = 0, n_cs = 0; uint32_t grid = 0, block = 0; long lds = 0; };   // the workgroup walk per image, the launch, the ring's bytes of LDS
 dw_launch_t conv_nhwc_dw_launch(conv_dw_geom_t const &g, tile_cfg_t const &c);
+plan_t plan_conv_nhwc_dwpw(conv_dwpw_geom_t const &g, int num_cus, string const &tile);   // hip_conv_nhwc_dw_pw (kernels/conv_nhwc_dwpw_bf16.hip); cfg as above; a "dwpw:TYxTXxCB" tile forces it
+dw_launch_t conv_nhwc_dwpw_launch(conv_dwpw_geom_t const &g, tile_cfg_t const &c);   // (n_cs = 1: a workgroup visits every chunk block; lds: ring + the intermediate's tile)
 plan_t plan_deconv(deconv_geom_t const &g, int member, int num_cus, string const &tile);   // the Deconvolution family (kernels/deconv_f32.hip); member: kDeconvFwd | kDeconvBckIn | kDeconvBckFilts
 plan_t plan_deconv_slab_sum(plan_t const &main);     // the second launch of a sliced filter gradient
 bool deconv_has_slab_sum(plan_t const &p);

@@ -88,7 +88,9 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
   case kFamConvNhwcDw:   // likewise (a tile of another kernel's form passes by: plan_conv_nhwc_dw)
     { (void)fi.op.get_u32("conv_has_relu");
       auto const ht = fi.op.str_vals.find("hip_tile");
-      (void)get_kernel(impl, host, plan_conv_nhwc_dw(conv_dw_geom_of_op(fi.op), host->nh_num_cus(), (ht != fi.op.str_vals.end() && !ht->second.empty()) ? ht->second : tune_of(impl, "conv_tile"))); }
+      string const tile = (ht != fi.op.str_vals.end() && !ht->second.empty()) ? ht->second : tune_of(impl, "conv_tile");
+      if (f->member == kConvNhwcDwPw) { (void)fi.op.get_u32("conv2_has_relu"); (void)get_kernel(impl, host, plan_conv_nhwc_dwpw(conv_dwpw_geom_of_op(fi.op), host->nh_num_cus(), tile)); }
+      else (void)get_kernel(impl, host, plan_conv_nhwc_dw(conv_dw_geom_of_op(fi.op), host->nh_num_cus(), tile)); }
     break;
   case kFamDeconv:   // likewise: the op must be whole, the tile one the family has, the code objects built now
     { deconv_geom_t const dg = deconv_geom_of_op(fi.op, f->member);
@@ -893,6 +895,21 @@ void native_kernels_t::conv_nhwc_dw(conv_dw_geom_t const &g, void const *filts, 
   last_launch.kernel = p.kname; last_launch.cfg = p.cfg; last_launch.grid = l.grid; last_launch.block = l.block;
   last_launch.flops = 2.0 * g.B * g.OH * g.OW * (double)g.C * g.KH * g.KW;
   last_launch.algo_bytes = (double)a.in_bytes + a.f_bytes + a.out_bytes + 4.0 * g.C;
+}
+void native_kernels_t::conv_nhwc_dwpw(conv_dwpw_geom_t const &gg, void const *filts, float const *biases, void const *filts2, float const *biases2, void const *in, void *out) {
+  conv_dw_geom_t const &g = gg.d;
+  plan_t const p = plan_conv_nhwc_dwpw(gg, host->nh_num_cus(), tune_of(impl, "conv_tile"));
+  kernel_t &k = get_kernel(impl, host, p);
+  dw_launch_t const l = conv_nhwc_dwpw_launch(gg, p.cfg);
+  conv_dwpw_args_t a; memset(&a, 0, sizeof(a));
+  a.in = in; a.filts = filts; a.bias = biases; a.filts2 = filts2; a.bias2 = biases2; a.out = out; a.n_ys = l.n_ys; a.n_xs = l.n_xs;
+  a.in_bytes = (unsigned)(2ull * g.B * g.C * g.H * g.W); a.f_bytes = (unsigned)(2ull * g.KH * g.KW * g.C); a.f2_bytes = (unsigned)(2ull * gg.OC * g.C);
+  a.out_bytes = (unsigned)((g.out_f32 ? 4ull : 2ull) * g.B * gg.OC * g.OH * g.OW);
+  void *params[] = {&a};
+  hip_err_chk(host->nh_launch(k.func, l.grid, 1, l.block, params), "hipModuleLaunchKernel(conv_nhwc_dwpw_bf16)");
+  last_launch.kernel = p.kname; last_launch.cfg = p.cfg; last_launch.grid = l.grid; last_launch.block = l.block;
+  last_launch.flops = 2.0 * g.B * g.OH * g.OW * ((double)g.C * g.KH * g.KW + (double)g.C * gg.OC);   // both layers
+  last_launch.algo_bytes = (double)a.in_bytes + a.f_bytes + a.f2_bytes + a.out_bytes + 4.0 * g.C + 4.0 * gg.OC;   // (the intermediate is not among them: it never reaches memory)
 }
 void native_kernels_t::bconv_biases(float const *out_grad, float *biases_grad, conv_geom_t const &g) {
   kernel_t &k = get_kernel(impl, host, plan_bconv_biases());

@@ -596,6 +596,58 @@ dw_launch_t conv_nhwc_dw_launch(conv_dw_geom_t const &g, tile_cfg_t const &c) {
   return l;
 }
 
+// hip_conv_nhwc_dw_pw (kernels/conv_nhwc_dwpw_bf16.hip): a depthwise layer and the 1x1 convolution behind it as one launch.  A workgroup owns one image, TY output
+// rows x TX output columns (P = TY * TX pels, rounded up to whole tiles of 32) and ALL out_chans; its threads are TX x CB rounded up to whole waves, its LDS the
+// depthwise ring plus the tile T of the intermediate: P rounded up to 32 pels x (C/8 rounded up to even, + 1) chunks of 16 bytes.  Chosen from the op and the CU count:
+//   CB, TX as plan_conv_nhwc_dw chooses them (the whole pel or 32 chunks; OW in the fewest equal segments of at most 256 / CB columns);
+//   TY = the most rows that keep P within 256 pels (eight accumulator tiles) and ring + T within kDwpwLdsBudget -- half of the 160 KB, so that two workgroups fit a
+//        CU -- or, where not even one tile of 32 pels fits that (C near 1024 on a wide ring), within the whole kDwpwLdsCap;
+//   then TY is halved while the launch has fewer workgroups than CUs.
+// A tile "dwpw:TYxTXxCB" forces the three (at most 1024 threads, P <= 256, LDS within the cap); any other tile string passes by.  cfg: TY x TX x CB as BI x BJ x BK
+constexpr long kDwpwLdsBudget = 80 * 1024, kDwpwLdsCap = 160 * 1024;
+static long dwpw_lds_bytes(conv_dw_geom_t const &g, int TY, int TX, int CB) {
+  long const pp = ((long)TY * TX + 31) / 32 * 32, pitch = (g.C / 8 + 1) / 2 * 2 + 1;
+  return dw_lds_bytes(g, TX, CB) + pp * pitch * 16;
+}
+plan_t plan_conv_nhwc_dwpw(conv_dwpw_geom_t const &gg, int num_cus, string const &tile) {
+  string const fn = "hip_conv_nhwc_dw_pw";
+  conv_dw_geom_t const &g = gg.d;
+  int const C8 = g.C / 8;
+  int TY, TX, CB;
+  if (tile.compare(0, 5, "dwpw:") == 0) {
+    char tail = 0;
+    if (sscanf(tile.c_str(), "dwpw:%dx%dx%d%c", &TY, &TX, &CB, &tail) != 3) unsup_err(fn + ": bad tile '" + tile + "' (dwpw:TYxTXxCB)");
+    if (TY < 1 || TY > 256 || TX < 1 || TX > 256 || CB < 1 || CB > C8 || (long)TX * CB > 1024 || TX > g.OW + 63 || TY * TX > 256 || dwpw_lds_bytes(g, TY, TX, CB) > kDwpwLdsCap)
+      unsup_err(fn + ": unsupported tile configuration " + tile + " (TY, TX >= 1, TY x TX <= 256 pels, 1 <= CB <= in.chan/8, TX x CB <= 1024 threads, ring + tile within " + std::to_string(kDwpwLdsCap) + " bytes of LDS)");
+  } else {
+    CB = std::min(C8, 32);
+    int const tx_max = std::max(1, 256 / CB), nseg = (g.OW + tx_max - 1) / tx_max;
+    TX = (g.OW + nseg - 1) / nseg;
+    long const budget = dwpw_lds_bytes(g, 1, TX, CB) <= kDwpwLdsBudget ? kDwpwLdsBudget : kDwpwLdsCap;
+    while (TX > 1 && dwpw_lds_bytes(g, 1, TX, CB) > budget) TX = (TX + 1) / 2;
+    TY = std::max(1, std::min(g.OH, 256 / TX));
+    while (TY > 1 && dwpw_lds_bytes(g, TY, TX, CB) > budget) --TY;
+    auto wgs = [&](int ty) { return (long)g.B * ((g.OH + ty - 1) / ty) * ((g.OW + TX - 1) / TX); };
+    while (TY > 1 && wgs(TY) < (long)num_cus) TY = (TY + 1) / 2;
+  }
+  plan_t p; p.src = kSrc_conv_nhwc_dwpw_bf16; p.kname = "bodahip_conv_nhwc_dwpw_bf16"; p.nhwc = true; p.bf16 = true;
+  tile_cfg_t &c = p.cfg; c = tile_cfg_t(); c.BI = TY; c.BJ = TX; c.BK = CB; c.WI = 1; c.WJ = 1; c.MINW = 1;
+  for (auto const &d : {std::make_pair("C8", C8), std::make_pair("NOC", gg.OC), std::make_pair("CH", g.H), std::make_pair("CW", g.W), std::make_pair("COH", g.OH), std::make_pair("COW", g.OW),
+                        std::make_pair("KH", g.KH), std::make_pair("KW", g.KW), std::make_pair("SY", g.SY), std::make_pair("SX", g.SX), std::make_pair("PY", g.PY), std::make_pair("PX", g.PX),
+                        std::make_pair("RELU", (int)g.relu), std::make_pair("RELU2", (int)gg.relu2), std::make_pair("OUT_F32", (int)g.out_f32), std::make_pair("TY", TY), std::make_pair("TX", TX),
+                        std::make_pair("CB", CB)}) p.defs.push_back(string("-D") + d.first + "=" + std::to_string(d.second));
+  return p;
+}
+dw_launch_t conv_nhwc_dwpw_launch(conv_dwpw_geom_t const &gg, tile_cfg_t const &c) {
+  conv_dw_geom_t const &g = gg.d;
+  dw_launch_t l;
+  l.n_ys = (g.OH + c.BI - 1) / c.BI; l.n_xs = (g.OW + c.BJ - 1) / c.BJ; l.n_cs = 1;
+  long const wgs = (long)g.B * l.n_ys * l.n_xs;
+  if (wgs >= (1L << 31)) unsup_err("hip_conv_nhwc_dw_pw: more than 2^31 workgroups");
+  l.grid = (uint32_t)wgs; l.block = (uint32_t)((c.BJ * c.BK + 63) / 64 * 64); l.lds = dwpw_lds_bytes(g, c.BI, c.BJ, c.BK);
+  return l;
+}
+
 // Rolling-rows form of the channels-last bf16 convolution (kernels/conv_nhwc_rows_bf16.hip): short-K layers of at most 64 out_chans whose time is their output --
 // the 7x7/2 stems after space-to-depth.  A workgroup of eight waves walks down a run of output rows of one image with the filters in registers; the rows land in an LDS
 // ring from which they are stored -- or pooled (+ LRN'd) without ever reaching memory (post).  Same k-slot order as the patch kernel (patch_cg): with an even tap count

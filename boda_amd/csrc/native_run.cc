@@ -284,9 +284,9 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     if (conv_grp_has_slab_sum(q)) bytes += compile_plan(plan_conv_grp_slab_sum(q), arch, &log).size();
     return bytes;
   } else if (fam == kFamConvNhwcDw) {   // (kernels/conv_nhwc_dw_bf16.hip: one launch per call, specialised by the geometry and the work split)
-    conv_dw_geom_t const dg = conv_dw_geom_of_op(op);
-    plan_t const q = plan_conv_nhwc_dw(dg, num_cus, tile);
-    dw_launch_t const l = conv_nhwc_dw_launch(dg, q.cfg);
+    plan_t q; dw_launch_t l;
+    if (member == kConvNhwcDwPw) { conv_dwpw_geom_t const pg = conv_dwpw_geom_of_op(op); q = plan_conv_nhwc_dwpw(pg, num_cus, tile); l = conv_nhwc_dwpw_launch(pg, q.cfg); }
+    else { conv_dw_geom_t const dg = conv_dw_geom_of_op(op); q = plan_conv_nhwc_dw(dg, num_cus, tile); l = conv_nhwc_dw_launch(dg, q.cfg); }
     if (plan_out) { *plan_out = q.kname + " " + q.cfg.str() + " grid=" + std::to_string(l.grid) + " block=" + std::to_string(l.block) + " lds=" + std::to_string(l.lds); for (auto const &d : q.defs) *plan_out += " " + d; }
     return arch.empty() ? 0 : compile_plan(q, arch, &log).size();
   } else if (fam == kFamDeconv) {   // (kernels/deconv_f32.hip: the direct forms, specialised by the geometry; a bare op: every function of its type)
@@ -812,6 +812,26 @@ struct native_kernels_t::call_t {
     void *f = var_ptr("filts"), *b = var_ptr("biases"), *in = var_ptr("in");
     nk.conv_nhwc_dw(g, f, (float const *)b, in, var_ptr("out"));
   }
+  void run_conv_nhwc_dwpw() {   // likewise: exact dims and element types per arg, all vars distinct, no channel range of a wider out
+    conv_dwpw_geom_t const g = conv_dwpw_geom_of_op(fi.op);
+    auto si = am.find("stride"), pi = am.find("in_pad");
+    if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
+    if (!(si->second.get_dims(host->nh_rtc()) == fi.op.get_dims("stride")) || !(pi->second.get_dims(host->nh_rtc()) == fi.op.get_dims("in_pad"))) rt_err(fn + ": stride / in_pad args disagree with the op");
+    if (am.find("out_chan_off") != am.end()) unsup_err(fn + ": out_chan_off: the fused pair writes whole tensors, not a channel range of a wider one");
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    auto var_ptr = [&](char const *an) -> void * {
+      string const vn = var_of(am, an);
+      dims_t const vd = host->nh_var_dims(vn), &want = fi.op.get_dims(an);
+      if (!(vd == want) || vd.tn != want.tn) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + " (" + vd.tn + "), the op says " + want.pretty_str() + " (" + want.tn + ")");
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      return host->nh_var_ptr(vn);
+    };
+    need_float(host->nh_var_dims(var_of(am, "biases")), "biases"); need_float(host->nh_var_dims(var_of(am, "biases2")), "biases2");
+    tile_override_t const tov(impl, "conv_tile", fi.op);
+    void *f = var_ptr("filts"), *b = var_ptr("biases"), *f2 = var_ptr("filts2"), *b2 = var_ptr("biases2"), *in = var_ptr("in");
+    nk.conv_nhwc_dwpw(g, f, (float const *)b, f2, (float const *)b2, in, var_ptr("out"));
+  }
   void run_sgd() {
     // every var must have exactly the dims the op gives its arg (params are no img shards), and the 3n + 1 vars must all be different: w_i and h_i are rewritten in place
     sgd_op_t const so = sgd_op_of_op(fi.op);
@@ -1057,7 +1077,7 @@ void native_kernels_t::run(native_func_t const &f, rtc_func_info_t const &fi, ma
   case kFamLoss: c.run_loss(); break;
   case kFamConvGrp: c.run_conv_grp(); break;
   case kFamDeconv: c.run_deconv(); break;
-  case kFamConvNhwcDw: c.run_conv_nhwc_dw(); break;
+  case kFamConvNhwcDw: if (f.member == kConvNhwcDwPw) c.run_conv_nhwc_dwpw(); else c.run_conv_nhwc_dw(); break;
   }
 }
 

@@ -157,6 +157,80 @@ def annotate_dw(a: Op, out_tn: str = "bfloat16") -> None:
     a.set_func_name(DW_FUNC)
 
 
+DW_PW_FUNC = "hip_conv_nhwc_dw_pw"
+DW_PW_MAX_CHAN = 1024     # the workgroup's tile of the intermediate holds every channel in LDS (kernels/conv_nhwc_dwpw_bf16.hip)
+
+
+def _dw_pw_why_not(dw: Op, pw: Op) -> str:
+    """Why the annotated ops dw -> pw (pw reads dw's output) cannot run as one hip_conv_nhwc_dw_pw launch, naming the field; '' when they can.  Mirrors
+    conv_dwpw_geom_of_op (csrc/native_funcs.h)."""
+    if not (dw.has_func_name() and dw.get_func_name() == DW_FUNC):
+        return f"the first op is {dw.get_func_name() if dw.has_func_name() else dw.get_type()!r}, not a {DW_FUNC} function"
+    yx = lambda a, k: (a.get_dims(k).dsz("y"), a.get_dims(k).dsz("x"))
+    if not (pw.has_func_name() and pw.get_func_name() == FUNC):
+        return f"the second op is {pw.get_func_name() if pw.has_func_name() else pw.get_type()!r}, not a plain {FUNC} function"
+    f2 = pw.get_dims("filts")
+    if pw.has("kern_sz") and yx(pw, "kern_sz") != (1, 1):     # (a window above 1 x 1 may carry the input-patch form of filts: name the window first)
+        return f"the second op's kern_sz is {yx(pw, 'kern_sz')[0]} x {yx(pw, 'kern_sz')[1]}, not 1 x 1"
+    if f2.names != ("out_chan", "y", "x", "in_chan"):
+        return f"the second op's filts are {':'.join(f2.names)}, not out_chan:y:x:in_chan"
+    for k in ("nhwc_s2d", "nhwc_pool", "nhwc_post_pool", "nhwc_residual"):
+        if pw.has(k) and pw.get_u32(k):
+            return f"the second op carries {k}={pw.get_u32(k)}"
+    if "hip_tile" in pw.str_vals:
+        return f"the second op carries hip_tile={pw.str_vals['hip_tile']}"
+    g = dict(C=dw.get_dims("in").dsz("chan"), KH=dw.get_dims("filts").dsz("y"), KW=dw.get_dims("filts").dsz("x"))
+    g2 = dict(OC=f2.dsz("out_chan"), KH=f2.dsz("y"), KW=f2.dsz("x"), SY=yx(pw, "stride")[0], SX=yx(pw, "stride")[1], PY=yx(pw, "in_pad")[0], PX=yx(pw, "in_pad")[1])
+    if (g2["KH"], g2["KW"]) != (1, 1):
+        return f"the second op's kern_sz is {g2['KH']} x {g2['KW']}, not 1 x 1"
+    if (g2["SY"], g2["SX"]) != (1, 1):
+        return f"the second op's stride is {g2['SY']} x {g2['SX']}, not 1 x 1"
+    if (g2["PY"], g2["PX"]) != (0, 0):
+        return f"the second op's in_pad is {g2['PY']} x {g2['PX']}, not 0 x 0"
+    if pw.get_dims("in") != dw.get_dims("out"):
+        return f"the second op's in {pw.get_dims('in').pretty()} is not the first op's out {dw.get_dims('out').pretty()}"
+    if g["C"] > DW_PW_MAX_CHAN:
+        return f"in.chan={g['C']} is above {DW_PW_MAX_CHAN}"
+    if g2["OC"] % 8:
+        return f"out_chan={g2['OC']} of the second op is no multiple of 8"
+    if not (1 <= g["KH"] <= 5 and 1 <= g["KW"] <= 5):
+        return f"kern_sz {g['KH']} x {g['KW']}: depthwise kernels of 1..5 rows and columns"
+    return ""
+
+
+def dw_pw_applies(dw: Op, pw: Op) -> bool:
+    """Can the annotated ops dw (a hip_conv_nhwc_dw function) -> pw (a plain hip_conv_nhwc function that reads dw's output) run as one hip_conv_nhwc_dw_pw launch?"""
+    return not _dw_pw_why_not(dw, pw)
+
+
+def dw_pw_pays(dw: Op, pw: Op) -> bool:
+    """The rule behind ConvPipeFwd(fuse_dw_pw=True), a function of the ops alone, read off the table of profiles/r27_conv_nhwc_dwpw.txt: of
+    MobileNet-v1's nine pairs at 64 images only 56 x 56 x 128 -> 128 at stride 1 beat its two calls by more than the noise band.  The pairs that lose are the
+    strided ones (the intermediate is a quarter of the input: little to save), the thin one (32 channels: two out_chan blocks for four waves) and the small maps
+    (every workgroup re-reads a filter as large as the traffic saved).  So: stride 1, at least 56 x 56 output pels per image, at least 128 channels."""
+    st, o = dw.get_dims("stride"), dw.get_dims("out")
+    return st.dsz("y") == 1 and st.dsz("x") == 1 and o.dsz("y") * o.dsz("x") >= 56 * 56 and dw.get_dims("in").dsz("chan") >= 128
+
+
+def annotate_dw_pw(dw: Op, pw: Op, tile: str = "") -> Op:
+    """The function op of hip_conv_nhwc_dw_pw (kernels/conv_nhwc_dwpw_bf16.hip) for the annotated ops dw -> pw: dw's in / filts / biases / stride / in_pad / kern_sz / group,
+    pw's filts / biases as filts2 / biases2, pw's out; conv_has_relu / conv2_has_relu the two layers' ReLUs as the ops carry them.  `tile`: a dwpw:TYxTXxCB work split
+    that travels with the function.  What the kernel does not cover is refused by the field's name."""
+    why = _dw_pw_why_not(dw, pw)
+    if why:
+        raise UnsupErr(f"{DW_PW_FUNC}: {why}")
+    c = dw.copy()
+    c.nda_vals["filts2"] = pw.nda_vals["filts"]; c.nda_vals["biases2"] = pw.nda_vals["biases"]; c.nda_vals["out"] = pw.nda_vals["out"]
+    c.nda_vals["filts2_ref"] = pw.nda_vals["filts_ref"]; c.nda_vals["out_ref"] = pw.nda_vals["out_ref"]
+    c.nda_vals["out_chans"] = pw.nda_vals["out_chans"] if "out_chans" in pw.nda_vals else Nda(None, "uint32_t", (pw.get_dims("filts").dsz("out_chan"),))
+    c.nda_vals["conv2_has_relu"] = Nda(None, "uint32_t", (pw.get_u32("conv_has_relu"),))
+    c.str_vals["func_name"] = DW_PW_FUNC
+    c.str_vals.pop("hip_tile", None)
+    if tile:
+        c.str_vals["hip_tile"] = tile
+    return c
+
+
 def _refuse_dw(a: Op, what: str) -> None:
     if a.has_func_name() and a.get_func_name() == DW_FUNC:
         raise UnsupErr(f"{what}: {DW_FUNC} (a depthwise convolution) has no such form: the kernel has no pooling, no residual epilogue and writes whole tensors")
