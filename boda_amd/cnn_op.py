@@ -1105,6 +1105,7 @@ NATIVE_ARGS: Dict[str, tuple] = {
     "hip_bconv_filts_grp": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT")),
     "hip_conv_nhwc_dw": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),   # a depthwise layer, channels-last bf16
     "hip_conv_nhwc_dw_pw": (("filts", "IN"), ("biases", "IN"), ("filts2", "IN"), ("biases2", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),   # a depthwise layer + the 1x1 convolution behind it
+    "hip_bconv_fb_nhwc": (("in", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("filts_grad_loss", "OUT"), ("biases_grad_loss", "OUT")),   # the filter and bias gradient from channels-last bf16 tensors (nhwc.annotate_bconv_fb)
     # a Deconvolution / BckDeconv: the lists of hip_conv and of BckConv's three gradients without their optional args; Caffe's Crop and its gradient
     "hip_deconv": (("filts", "IN"), ("biases", "IN"), ("in", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("out", "OUT")),
     "hip_deconv_bck_in": (("filts", "IN"), ("out_grad_loss", "IN"), ("stride", "REF"), ("in_pad", "REF"), ("in_grad_loss", "OUT")),

@@ -357,6 +357,16 @@ struct conv_dwpw_args_t {
 };
 static_assert(sizeof(conv_dwpw_args_t) == 72 && __builtin_offsetof(conv_dwpw_args_t, n_ys) == 48 && __builtin_offsetof(conv_dwpw_args_t, in_bytes) == 56, "conv_dwpw_args_t layout");
 
+// kernels/bconv_fb_nhwc_bf16.hip: filter and bias gradient from channels-last bf16 tensors (hip_bconv_fb_nhwc); its slab sum takes a bconv_fb_args_t
+struct bconv_nhwc_args_t {
+  void const *g; void const *x; float *df; float *db;   // out_grad_loss img:y:x:chan bf16, in img:y:x:chan bf16, filts_grad_loss out_chan:y:x:in_chan float, biases_grad_loss
+  float *ws; long slab_elems;                           // SLICED: ksl slabs of slab_elems = OC*KH*KW*C + OC floats
+  int B, C, H, W, OC, OH, OW;
+  int tiles_i, tiles_j, n_tg, ksl, st_per;              // out_chan tiles, in_chan tiles, tap groups, K slices (the fastest coordinate of blockIdx.x), stages per slice
+  unsigned g_bytes, x_bytes;
+};
+static_assert(sizeof(bconv_nhwc_args_t) == 104 && __builtin_offsetof(bconv_nhwc_args_t, ws) == 32 && __builtin_offsetof(bconv_nhwc_args_t, B) == 48 && __builtin_offsetof(bconv_nhwc_args_t, g_bytes) == 96, "bconv_nhwc_args_t layout");
+
 #pragma pop_macro("CH")
 #pragma pop_macro("CIN")
 #pragma pop_macro("COH")

@@ -10,8 +10,8 @@
 namespace bodahip {
 
 // the family (func_family_t of rtc_types.h) selects the handler (native_run.cc, native_kernels.cc: check_compile_time); handlers switch on the member, never on the name
-inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf", "loss", "conv_grp", "deconv", "conv_nhwc_dw"};
-// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform.  kFamLoss: 1 fwd | 2 norm | 3 bck (loss_op_t::kind).  kFamConvGrp: 1 fwd | 2 bck_in | 3 bck_filts.  kFamDeconv: 1 fwd | 2 bck_in | 3 bck_biases | 4 bck_filts.  kFamConvNhwcDw: 0 the depthwise layer | 1 the depthwise + pointwise pair
+inline constexpr char const *kFamilyNames[] = {"sgemm", "conv", "conv_nhwc", "nhwc_grp", "nhwc_multi", "k1_chain", "filts_kmajor", "bconv", "bck_op", "sgd", "bn", "bnc", "solver", "eval", "data", "bnf", "loss", "conv_grp", "deconv", "conv_nhwc_dw", "bconv_nhwc"};
+// members.  kFamSolver: 1 update | 2 sumsq | 3 norm | 4 accum | 5 update_acc (solver_op_t::kind).  kFamSgemm: 0 fp32 | 1 bf16 operands.  kFamNhwcMulti: 0 multi | 1 set.  kFamBckOp: the OP number of kernels/bck_ops_f32.hip.  kFamBn, kFamBnc, kFamBnf: the kind of bn_op_t.  kFamEval: 1 accuracy | 2 accum | 3 bn_fold (eval_op_t::kind).  kFamData: 1 transform.  kFamLoss: 1 fwd | 2 norm | 3 bck (loss_op_t::kind).  kFamConvGrp: 1 fwd | 2 bck_in | 3 bck_filts.  kFamDeconv: 1 fwd | 2 bck_in | 3 bck_biases | 4 bck_filts.  kFamConvNhwcDw: 0 the depthwise layer | 1 the depthwise + pointwise pair.  kFamBconvNhwc: 0, its one function
 enum { kConvF32 = 0, kConvAlias = 1, kConvBf16 = 2, kConvWinograd = 3 };            // (the alias: hip_conv's contract without its fused pooling and filts_km)
 enum { kBconvIn = 1, kBconvBiases = 2, kBconvFilts = 3, kBconvFiltsBiases = 4 };   // (4 is opt-in: never one of the bare op's three calls)
 enum { kConvGrpFwd = 1, kConvGrpBckIn = 2, kConvGrpBckFilts = 3 };                  // (a grouped convolution and its data / filter gradients; the bias gradient knows no groups)
@@ -73,7 +73,8 @@ inline constexpr char kWhyLossOneDevice[] = "(the full softmax loss, the hip_sof
 inline constexpr char kWhyConvGrpOneDevice[] = "(a grouped convolution, the hip_conv_grp / hip_bconv_in_grp / hip_bconv_filts_grp family) takes vars of exactly its op's dims, not img shards, and hip_bconv_filts_grp sums over the images of the WHOLE batch, which would need a cross-device reduction; grouped layers on several devices are out of scope";
 inline constexpr char kWhyDeconvOneDevice[] = "(a Deconvolution, the hip_deconv / hip_deconv_bck_in / hip_deconv_bck_filts / hip_deconv_bck_biases family) takes vars of exactly its op's dims, not img shards, and its filter and bias gradients sum over the images of the WHOLE batch, which would need a cross-device reduction; Deconvolution layers on several devices are out of scope";
 inline constexpr char kWhyConvNhwcDwOneDevice[] = "(a depthwise channels-last bf16 convolution, hip_conv_nhwc_dw / hip_conv_nhwc_dw_pw) takes vars of exactly its op's dims, not img shards: the image count is a constant of its specialised kernel; depthwise layers on several devices are out of scope";
-inline constexpr char const *why_one_device(func_family_t family) { return family == kFamLoss ? kWhyLossOneDevice : family == kFamConvGrp ? kWhyConvGrpOneDevice : family == kFamDeconv ? kWhyDeconvOneDevice : family == kFamConvNhwcDw ? kWhyConvNhwcDwOneDevice : kWhyBnfOneDevice; }
+inline constexpr char kWhyBconvNhwcOneDevice[] = "(a filter and bias gradient from channels-last bf16 tensors, hip_bconv_fb_nhwc) sums over the images of the WHOLE batch, which would need a cross-device reduction, and takes vars of exactly its op's dims, not img shards; channels-last gradients on several devices are out of scope";
+inline constexpr char const *why_one_device(func_family_t family) { return family == kFamLoss ? kWhyLossOneDevice : family == kFamConvGrp ? kWhyConvGrpOneDevice : family == kFamDeconv ? kWhyDeconvOneDevice : family == kFamConvNhwcDw ? kWhyConvNhwcDwOneDevice : family == kFamBconvNhwc ? kWhyBconvNhwcOneDevice : kWhyBnfOneDevice; }
 inline constexpr native_func_t kNativeFuncs[] = {
   // sgemm, a:K:M b:K:N c:M:N (test/rtc/cublas_sgemm.cucl:1-4); Convolution in reference layout (test/rtc/cudnn_conv.cucl:1-7)
   {"hip_sgemm", kFamSgemm, 0, nullptr, {"sgemm"}, {{"a", kIn}, {"b", kIn}, {"c", kOut}}, {}, kVarNone, 0, {}, kBeHip | kBeCpu, kOnShards},
@@ -172,6 +173,10 @@ inline constexpr native_func_t kNativeFuncs[] = {
   // the depthwise layer and the 1x1 convolution that alone reads it as one launch (kernels/conv_nhwc_dwpw_bf16.hip): hip_conv_k1_chain's arg list -- filts / biases
   // the depthwise layer's, filts2 (out_chan:y:x:in_chan, 1x1) / biases2 the pointwise layer's; the two ReLUs ride in the op (conv_has_relu, conv2_has_relu)
   {"hip_conv_nhwc_dw_pw", kFamConvNhwcDw, kConvNhwcDwPw, nullptr, {"Convolution"}, {{"filts", kIn}, {"biases", kIn}, {"filts2", kIn}, {"biases2", kIn}, {"in", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"out", kOut}}, {}, kVarNone, 0, {}, kBeHip, kOneDevice},
+  // a BckConv's filter and bias gradient from channels-last bf16 tensors (this backend's own; kernels/bconv_fb_nhwc_bf16.hip): in / out_grad_loss img:y:x:chan bfloat16,
+  // filts_grad_loss out_chan:y:x:in_chan and biases_grad_loss float.  hip_bconv_filts_biases' arg list; no flag; one device only (why_one_device).  A family of its
+  // own: the rows of kFamBconv are pinned.  Reached through nhwc.annotate_bconv_fb alone, never one of a bare op's calls.  In front of the loss rows
+  {"hip_bconv_fb_nhwc", kFamBconvNhwc, 0, nullptr, {"BckConv"}, {{"in", kIn}, {"out_grad_loss", kIn}, {"stride", kRef}, {"in_pad", kRef}, {"filts_grad_loss", kOut}, {"biases_grad_loss", kOut}}, {}, kVarNone, 0, {}, kBeHip, kOneDevice},
   // the full SoftmaxWithLoss (this backend's own; kernels/loss_f32.hip): what a head with a LossSpec lowers to -- loss_weight, ignore_label, planes, the four
   // normalisers.  hip_softmax_loss_bck reads s = weight / Z from loss_state on the device.  One device only (why_one_device).  In front of the data and eval rows,
   // which stay the table's last four
@@ -191,10 +196,10 @@ inline constexpr native_func_t kNativeFuncs[] = {
 
 inline native_func_t const *find_native_func(string const &fn) { for (auto const &f : kNativeFuncs) if (fn == f.name) return &f; return nullptr; }
 inline native_func_t const *find_native_func(func_family_t family, int member) { for (auto const &f : kNativeFuncs) if (f.family == family && f.member == member) return &f; return nullptr; }
-// the functions of a bare op of type t, in call order (empty: no such op).  kBconvFiltsBiases is nobody's default call, and the grouped and the depthwise channels-last functions belong to annotated ops
+// the functions of a bare op of type t, in call order (empty: no such op).  kBconvFiltsBiases is nobody's default call, and the grouped and the channels-last depthwise / gradient functions belong to annotated ops
 inline std::vector<native_func_t const *> native_funcs_of_type(string const &t, unsigned backend = kBeHip) {
   std::vector<native_func_t const *> r;
-  for (auto const &f : kNativeFuncs) if (f.of_type(t) && (f.backends & backend) && !(f.family == kFamBconv && f.member == kBconvFiltsBiases) && f.family != kFamConvGrp && f.family != kFamConvNhwcDw) r.push_back(&f);
+  for (auto const &f : kNativeFuncs) if (f.of_type(t) && (f.backends & backend) && !(f.family == kFamBconv && f.member == kBconvFiltsBiases) && f.family != kFamConvGrp && f.family != kFamConvNhwcDw && f.family != kFamBconvNhwc) r.push_back(&f);
   std::stable_sort(r.begin(), r.end(), [](native_func_t const *a, native_func_t const *b) { return a->member < b->member; });
   return r;
 }
@@ -323,6 +328,36 @@ inline conv_dwpw_geom_t conv_dwpw_geom_of_op(op_base_t const &op) {
   if (in_b >= 0x7ffffff0ull || out_b >= 0x7ffffff0ull) unsup_err(fn + ": tensors of 2 GiB or more (32-bit offsets)");
   for (char const *k : {"nhwc_residual", "nhwc_pool", "nhwc_post_pool", "nhwc_s2d"}) if (op.has(k) && op.get_u32(k)) unsup_err(fn + ": " + k + "=1: the fused pair has no such form");
   return r;
+}
+
+// hip_bconv_fb_nhwc (kFamBconvNhwc): what the planner, the ahead-of-time build and the call read from the function's op, and every refusal that needs the op alone.
+// The op is a BckConv with in img:y:x:chan (C) and out_grad_loss img:y:x:chan (OC) bfloat16, filts_grad_loss out_chan:y:x:in_chan and biases_grad_loss out_chan float.
+// The kernel's scope: no groups, C and OC multiples of 8, kernels of 1..7 rows and columns, strides 1 | 2, padding below the kernel size.  An UnsupErr names its field
+struct bconv_nhwc_geom_t { int B, C, H, W, OC, KH, KW, SY, SX, PY, PX, OH, OW; };
+inline bconv_nhwc_geom_t bconv_nhwc_geom_of_op(op_base_t const &op) {
+  string const fn = "hip_bconv_fb_nhwc";
+  if (op.get_type() != "BckConv") rt_err(fn + ": a function of op type BckConv, not " + op.get_type());
+  dims_t const &in = op.get_dims("in"), &og = op.get_dims("out_grad_loss"), &fg = op.get_dims("filts_grad_loss"), &bg = op.get_dims("biases_grad_loss"), &st = op.get_dims("stride"), &pad = op.get_dims("in_pad");
+  auto nhwc = [](dims_t const &d) { return d.sz() == 4 && d.names(0) == "img" && d.names(1) == "y" && d.names(2) == "x" && d.names(3) == "chan"; };
+  if (!nhwc(in) || !nhwc(og) || fg.sz() != 4 || fg.names(0) != "out_chan" || fg.names(1) != "y" || fg.names(2) != "x" || fg.names(3) != "in_chan" || st.sz() != 2 || pad.sz() != 2 ||
+      in.tn != "bfloat16" || og.tn != "bfloat16" || fg.tn != "float" || bg.tn != "float")
+    rt_err(fn + ": bfloat16 in and out_grad_loss img:y:x:chan, float filts_grad_loss out_chan:y:x:in_chan and biases_grad_loss, stride / in_pad y:x");
+  bconv_nhwc_geom_t g;
+  g.B = (int)in.dsz("img"); g.C = (int)in.dsz("chan"); g.H = (int)in.dsz("y"); g.W = (int)in.dsz("x"); g.OC = (int)og.dsz("chan"); g.KH = (int)fg.dsz("y"); g.KW = (int)fg.dsz("x");
+  g.SY = (int)st.dsz("y"); g.SX = (int)st.dsz("x"); g.PY = (int)pad.dsz("y"); g.PX = (int)pad.dsz("x"); g.OH = (int)og.dsz("y"); g.OW = (int)og.dsz("x");
+  uint32_t const grp = op.has("group") ? op.get_u32("group") : 1u;
+  if (grp != 1) unsup_err(fn + ": group=" + std::to_string(grp) + ": ungrouped convolutions only");
+  if (g.C < 8 || g.C % 8) unsup_err(fn + ": in.chan=" + std::to_string(g.C) + " is no multiple of 8 (rows are staged in 16-byte chunks of 8 channels)");
+  if (g.OC < 8 || g.OC % 8) unsup_err(fn + ": out_grad_loss.chan=" + std::to_string(g.OC) + " is no multiple of 8 (rows are staged in 16-byte chunks of 8 channels)");
+  if (g.KH < 1 || g.KH > 7 || g.KW < 1 || g.KW > 7) unsup_err(fn + ": kern_sz " + std::to_string(g.KH) + " x " + std::to_string(g.KW) + ": kernels of 1..7 rows and columns");
+  if ((g.SY != 1 && g.SY != 2) || (g.SX != 1 && g.SX != 2)) unsup_err(fn + ": stride " + std::to_string(g.SY) + " x " + std::to_string(g.SX) + ": strides of 1 | 2");
+  if (g.PY < 0 || g.PY >= g.KH || g.PX < 0 || g.PX >= g.KW) unsup_err(fn + ": in_pad " + std::to_string(g.PY) + " x " + std::to_string(g.PX) + ": padding below the kernel size");
+  if (g.B < 1 || g.H < 1 || g.W < 1 || g.OH < 1 || g.OW < 1) rt_err(fn + ": empty tensors");
+  if (og.dsz("img") != (uint32_t)g.B || (g.H + 2 * g.PY - g.KH) / g.SY + 1 != g.OH || (g.W + 2 * g.PX - g.KW) / g.SX + 1 != g.OW) rt_err(fn + ": out_grad_loss dims do not match in / filts_grad_loss / stride / in_pad");
+  if (fg.dsz("out_chan") != (uint32_t)g.OC || fg.dsz("in_chan") != (uint32_t)g.C || bg.dims_prod() != (uint64_t)g.OC) rt_err(fn + ": filts_grad_loss / biases_grad_loss disagree with in.chan=" + std::to_string(g.C) + " / out_grad_loss.chan=" + std::to_string(g.OC));
+  uint64_t const in_b = 2ull * g.B * g.C * g.H * g.W, og_b = 2ull * g.B * g.OC * g.OH * g.OW, f_b = 4ull * g.OC * g.C * g.KH * g.KW;
+  if (in_b >= 0x7ffffff0ull || og_b >= 0x7ffffff0ull || f_b >= 0x7ffffff0ull) unsup_err(fn + ": tensors of 2 GiB or more (32-bit offsets)");
+  return g;
 }
 
 // the Deconvolution family (kFamDeconv): what both backends read from the function's op, and every refusal that needs the op alone.  The geometry is the LAYER's:

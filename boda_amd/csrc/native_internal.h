@@ -104,6 +104,11 @@ struct dw_launch_t { int n_ys = 0, n_xs = 0, n_cs = 0; uint32_t grid = 0, block 
 dw_launch_t conv_nhwc_dw_launch(conv_dw_geom_t const &g, tile_cfg_t const &c);
 plan_t plan_conv_nhwc_dwpw(conv_dwpw_geom_t const &g, int num_cus, string const &tile);   // hip_conv_nhwc_dw_pw (kernels/conv_nhwc_dwpw_bf16.hip); cfg as above; a "dwpw:TYxTXxCB" tile forces it
 dw_launch_t conv_nhwc_dwpw_launch(conv_dwpw_geom_t const &g, tile_cfg_t const &c);   // (n_cs = 1: a workgroup visits every chunk block; lds: ring + the intermediate's tile)
+// hip_bconv_fb_nhwc (kernels/bconv_fb_nhwc_bf16.hip); cfg: BI x BJ x BK, WI x WJ waves, SPLITK = KSL; a "fbn:BIxBJxBKxKSL[xXB]" tile forces it (XB: columns of a
+// stage's block of output pels, kernels above 1 x 1).  Its second launch is plan_bconv_slab_sum's
+struct fbn_plan_t { plan_t p; int XB = 0, TR = 0, tiles_i = 0, tiles_j = 0, n_tg = 0, ksl = 0, st_per = 0; long n_st = 0; uint32_t grid = 0, block = 0; long lds = 0; };   // the plan, the launch, the bytes of LDS
+fbn_plan_t plan_bconv_fb_nhwc(bconv_nhwc_geom_t const &g, int num_cus, string const &tile);
+inline bool is_fbn_tile(string const &tile) { return tile.compare(0, 4, "fbn:") == 0; }   // (every other function lets such a tile pass by: tune_of, prebuild)
 plan_t plan_deconv(deconv_geom_t const &g, int member, int num_cus, string const &tile);   // the Deconvolution family (kernels/deconv_f32.hip); member: kDeconvFwd | kDeconvBckIn | kDeconvBckFilts
 plan_t plan_deconv_slab_sum(plan_t const &main);     // the second launch of a sliced filter gradient
 bool deconv_has_slab_sum(plan_t const &p);
@@ -114,6 +119,7 @@ void ensure_ws(native_kernels_t::impl_t *impl, native_host_t *host, size_t need)
 void call_ws_make_room(native_kernels_t::impl_t *impl, native_host_t *host, size_t need);
 void setup_ksl(native_kernels_t::impl_t *impl, native_host_t *host, gemm_args_t &ga, tile_cfg_t const &cfg, long nk, void const *key_ptr, char const *what);
 string tune_of(native_kernels_t::impl_t *impl, char const *key);
+string fbn_tile_of(native_kernels_t::impl_t *impl);   // the conv_tile tune where it is hip_bconv_fb_nhwc's own form, else empty
 sgemm_split_t plan_sgemm_split(uint32_t M, uint32_t N, uint32_t K, int num_cus);
 string sgemm_wide_tile(uint32_t M, uint32_t N, uint32_t K, long cus);
 bool parse_parts_env(uint32_t M, uint32_t N, uint32_t K, std::vector<sgemm_part_t> &out);

@@ -92,6 +92,12 @@ native_func_t const *native_kernels_t::check_compile_time(rtc_func_info_t const 
       if (f->member == kConvNhwcDwPw) { (void)fi.op.get_u32("conv2_has_relu"); (void)get_kernel(impl, host, plan_conv_nhwc_dwpw(conv_dwpw_geom_of_op(fi.op), host->nh_num_cus(), tile)); }
       else (void)get_kernel(impl, host, plan_conv_nhwc_dw(conv_dw_geom_of_op(fi.op), host->nh_num_cus(), tile)); }
     break;
+  case kFamBconvNhwc:   // likewise: the op must be whole, the tile this function's own or none, the code objects built now
+    { auto const ht = fi.op.str_vals.find("hip_tile");
+      fbn_plan_t const bp = plan_bconv_fb_nhwc(bconv_nhwc_geom_of_op(fi.op), host->nh_num_cus(), (ht != fi.op.str_vals.end() && !ht->second.empty()) ? ht->second : fbn_tile_of(impl));
+      (void)get_kernel(impl, host, bp.p);
+      if (bp.ksl > 1) (void)get_kernel(impl, host, plan_bconv_slab_sum()); }
+    break;
   case kFamDeconv:   // likewise: the op must be whole, the tile one the family has, the code objects built now
     { deconv_geom_t const dg = deconv_geom_of_op(fi.op, f->member);
       if (f->member == kDeconvBckBiases) { (void)get_kernel(impl, host, plan_bconv_biases()); break; }
@@ -294,7 +300,9 @@ static ktab_t get_rtab(native_kernels_t::impl_t *impl, native_host_t *host, conv
   return ktab_t{d, (int)n};
 }
 
-string tune_of(native_kernels_t::impl_t *impl, char const *key) { auto t = impl->tune.find(key); return (t == impl->tune.end()) ? string() : t->second; }
+// (a "fbn:" conv_tile is hip_bconv_fb_nhwc's own: it reads it through fbn_tile_of, every other function sees no tile)
+string tune_of(native_kernels_t::impl_t *impl, char const *key) { auto t = impl->tune.find(key); return (t == impl->tune.end() || (t->first == "conv_tile" && is_fbn_tile(t->second))) ? string() : t->second; }
+string fbn_tile_of(native_kernels_t::impl_t *impl) { auto t = impl->tune.find("conv_tile"); return (t != impl->tune.end() && is_fbn_tile(t->second)) ? t->second : string(); }
 
 static void sgemm_parts(native_kernels_t *nk, native_kernels_t::impl_t *impl, native_host_t *host, float const *a, float const *b, float *c, uint32_t M, uint32_t N, uint32_t K, std::vector<sgemm_part_t> const &parts) {
   if ((uint64_t)K * M * 4 > 0x80000000ull || (uint64_t)K * N * 4 > 0x80000000ull || (uint64_t)M * N * 4 >= 0x7ffffff0ull) unsup_err("hip_sgemm: operands / c of 2 GiB or more are not supported (32-bit buffer offsets)");
@@ -961,6 +969,44 @@ void native_kernels_t::bconv_filts_biases(float const *in, float const *out_grad
   last_launch.algo_bytes = (double)a.g_bytes + a.x_bytes + 4.0 * ((double)g.OC * NJ + g.OC);
 }
 
+// hip_bconv_fb_nhwc: both gradients from channels-last bf16 tensors (kernels/bconv_fb_nhwc_bf16.hip).  With K slices the main launch fills the call's slabs -- keyed and
+// allocated like hip_bconv_filts_biases' (run once before a capture), the outputs' own element order, then OC bias partials -- and bodahip_bconv_slab_sum adds them
+void native_kernels_t::bconv_fb_nhwc(bconv_nhwc_geom_t const &g, void const *in, void const *out_grad, float *filts_grad, float *biases_grad) {
+  fbn_plan_t const bp = plan_bconv_fb_nhwc(g, host->nh_num_cus(), fbn_tile_of(impl));
+  kernel_t &k = get_kernel(impl, host, bp.p);
+  bconv_nhwc_args_t a; memset(&a, 0, sizeof(a));
+  a.g = out_grad; a.x = in; a.df = filts_grad; a.db = biases_grad;
+  a.B = g.B; a.C = g.C; a.H = g.H; a.W = g.W; a.OC = g.OC; a.OH = g.OH; a.OW = g.OW;
+  a.tiles_i = bp.tiles_i; a.tiles_j = bp.tiles_j; a.n_tg = bp.n_tg; a.ksl = bp.ksl; a.st_per = bp.st_per;
+  a.g_bytes = (unsigned)(2ull * g.B * g.OC * g.OH * g.OW); a.x_bytes = (unsigned)(2ull * g.B * g.C * g.H * g.W);
+  long const NF = (long)g.OC * g.KH * g.KW * g.C, K = (long)g.B * g.OH * g.OW;
+  a.slab_elems = NF + g.OC;
+  bconv_fb_args_t sa; memset(&sa, 0, sizeof(sa));   // the slab sum's view of the same call
+  kernel_t *ks = nullptr;
+  if (bp.ksl > 1) {
+    ks = &get_kernel(impl, host, plan_bconv_slab_sum());
+    size_t const total = (size_t)bp.ksl * (size_t)a.slab_elems * 4;
+    if (total >= (size_t(1) << 32)) unsup_err("hip_bconv_fb_nhwc: K-slice workspace too large");
+    string const key = "ksl:bconv_fbn:" + std::to_string((uintptr_t)in) + ":" + std::to_string((uintptr_t)out_grad) + ":" + std::to_string((uintptr_t)filts_grad) + ":" +
+                       std::to_string((uintptr_t)biases_grad) + ":" + std::to_string(total);
+    auto it = impl->ktabs.find(key);
+    if (it == impl->ktabs.end()) {
+      if (host->nh_capturing()) rt_err("graph capture: the K-slice workspace of this call is not allocated yet -- run the call list once before capturing it");
+      void *dev = nullptr;
+      call_ws_make_room(impl, host, total);
+      hip_err_chk(hipMalloc(&dev, total), "hipMalloc(K-slice workspace)"); impl->call_ws_bytes += total;
+      it = impl->ktabs.emplace(key, dev).first;
+    }
+    a.ws = (float *)it->second;
+    sa.df = filts_grad; sa.db = biases_grad; sa.ws = a.ws; sa.slab_elems = a.slab_elems; sa.OC = g.OC; sa.ksl = bp.ksl;
+  }
+  void *params[] = {&a}, *sum_params[] = {&sa};
+  hip_err_chk(host->nh_launch(k.func, bp.grid, 1, bp.block, params), "hipModuleLaunchKernel(bconv_fb_nhwc_bf16)");
+  if (ks) hip_err_chk(host->nh_launch(ks->func, (uint32_t)((a.slab_elems + 255) / 256), 1, 256, sum_params), "hipModuleLaunchKernel(bconv_slab_sum)");
+  last_launch.kernel = bp.p.kname; last_launch.cfg = bp.p.cfg; last_launch.grid = bp.grid; last_launch.block = bp.block;
+  last_launch.flops = 2.0 * K * g.OC * (double)g.C * g.KH * g.KW;
+  last_launch.algo_bytes = (double)a.g_bytes + a.x_bytes + 4.0 * ((double)NF + g.OC);   // the two bf16 operands once, the fp32 outputs
+}
 
 
 // ---- the non-conv ops of the gradient pipe (kernels/bck_ops_f32.hip): one launch, one thread per written element (softmax: one wave per image)

@@ -158,6 +158,9 @@ struct native_kernels_t {
   // hip_conv_nhwc_dw_pw (kernels/conv_nhwc_dwpw_bf16.hip) on raw device pointers: the depthwise layer's filts y:x:chan bf16 / biases, the 1x1 layer's filts2
   // out_chan:1:1:in_chan bf16 / biases2, in / out img:y:x:chan (out bf16, or float with g.d.out_f32).  One launch, no workspace
   void conv_nhwc_dwpw(conv_dwpw_geom_t const &g, void const *filts, float const *biases, void const *filts2, float const *biases2, void const *in, void *out);
+  // hip_bconv_fb_nhwc (kernels/bconv_fb_nhwc_bf16.hip) on raw device pointers: in / out_grad_loss img:y:x:chan bf16, filts_grad_loss out_chan:y:x:in_chan and
+  // biases_grad_loss float.  With K slices: slabs in the call's workspace and bodahip_bconv_slab_sum behind the main launch
+  void bconv_fb_nhwc(bconv_nhwc_geom_t const &g, void const *in, void const *out_grad, float *filts_grad, float *biases_grad);
   // the Deconvolution family (kernels/deconv_f32.hip) on raw device pointers.  member kDeconvFwd: a = filts, b = in, bias = biases, d = out; kDeconvBckIn: a = filts,
   // b = out_grad_loss, d = in_grad_loss; kDeconvBckFilts: a = out_grad_loss, b = in, d = filts_grad_loss (with K slices: slabs in the call's workspace, a second launch)
   void deconv(int member, deconv_geom_t const &g, float const *a, float const *b, float const *bias, float *d);

@@ -1578,6 +1578,73 @@ plan_t plan_bconv_fb_bf16(conv_geom_t const &g, int num_cus, string const &tile)
 
 
 
+// ---- hip_bconv_fb_nhwc (kernels/bconv_fb_nhwc_bf16.hip): the filter and bias gradient from channels-last bf16 tensors.  A workgroup owns a BI x BJ tile of
+// (out_chan, in_chan), one group of TR kernel rows (all KW columns: TR * KW accumulator tiles per wave, at most 16 blocks of 32 x 32 = 256 registers) and one K slice;
+// a stage is BK output pels -- consecutive pels (1 x 1 kernels) or a block of BK/XB rows x XB columns of one image with its input patch.  Chosen from the op and the
+// CU count:
+//   BI, BJ  32 where the channel count is at most 32, else 64; 128 for a 1 x 1 kernel on more than 64 channels (four blocks per wave: a fragment read feeds two MFMAs)
+//   TR      the most kernel rows whose taps fit nine accumulator tiles, spread evenly over the fewest tap groups (3 x 3: one group; 5 x 5, 7 x 7: a row per group)
+//   XB      the divisor of BK (>= 4) whose blocks waste the fewest pels of the OH x OW plane; ties go to the wider block (consecutive k in consecutive slots)
+//   BK      64, halved (to 16 at least) while the two stage buffers exceed kFbnLdsBudget -- half of the 160 KB, so that two workgroups fit a CU
+//   KSL     so that tiles x tap groups x slices is about four workgroups a CU, every slice at least four stages long; 1..1024
+// KSL -- chosen or forced -- is then clamped to the number of slices that are not empty: ceil(stages / ceil(stages / KSL)).  A tile "fbn:BIxBJxBKxKSL[xXB]" forces the
+// fields (BI, BJ 32 | 64 | 128; BK a multiple of 16 of at most 128; XB a divisor of BK; LDS within kFbnLdsCap); any other tile string passes by
+constexpr long kFbnLdsBudget = 80 * 1024, kFbnLdsCap = 160 * 1024;
+static long fbn_lds_bytes(bconv_nhwc_geom_t const &g, int BI, int BJ, int BK, int XB, int TR) {
+  auto pitch = [](int w) { return 2L * w + ((2 * w) % 128 == 64 ? 0 : 64); };
+  bool const flat = g.KH == 1 && g.KW == 1;
+  long const slots = flat ? BK : ((long)(BK / XB - 1) * g.SY + TR) * ((long)(XB - 1) * g.SX + g.KW);
+  return 2 * (BK * pitch(BI) + slots * pitch(BJ));
+}
+static int fbn_pick_xb(bconv_nhwc_geom_t const &g, int BK) {
+  int best = BK; long best_cost = -1;
+  for (int xb = BK; xb >= 4; xb /= 2) {
+    int const yb = BK / xb;
+    long const cost = (long)((g.OW + xb - 1) / xb) * xb * ((g.OH + yb - 1) / yb) * yb;
+    if (best_cost < 0 || cost < best_cost) { best = xb; best_cost = cost; }
+  }
+  return best;
+}
+fbn_plan_t plan_bconv_fb_nhwc(bconv_nhwc_geom_t const &g, int num_cus, string const &tile) {
+  string const fn = "hip_bconv_fb_nhwc";
+  bool const flat = g.KH == 1 && g.KW == 1;
+  fbn_plan_t r;
+  int const max_rows = std::max(1, std::min(g.KH, 9 / g.KW));
+  r.n_tg = (g.KH + max_rows - 1) / max_rows; r.TR = (g.KH + r.n_tg - 1) / r.n_tg;
+  int BI, BJ, BK, KSL = 0, XB = 0;
+  if (is_fbn_tile(tile)) {
+    char tail = 0;
+    int const n = sscanf(tile.c_str(), "fbn:%dx%dx%dx%dx%d%c", &BI, &BJ, &BK, &KSL, &XB, &tail);
+    if (n != 4 && n != 5) unsup_err(fn + ": bad tile '" + tile + "' (fbn:BIxBJxBKxKSL[xXB])");
+    if (flat || n == 4) XB = flat ? BK : fbn_pick_xb(g, BK);
+    auto side = [](int b) { return b == 32 || b == 64 || b == 128; };
+    if (!side(BI) || !side(BJ) || BK < 16 || BK > 128 || BK % 16 || KSL < 1 || KSL > 1024 || XB < 1 || BK % XB || r.TR * g.KW * (BI / 64 ? BI / 64 : 1) * (BJ / 64 ? BJ / 64 : 1) > 16 ||
+        fbn_lds_bytes(g, BI, BJ, BK, XB, r.TR) > kFbnLdsCap)
+      unsup_err(fn + ": unsupported tile configuration " + tile + " (BI, BJ 32 | 64 | 128, BK a multiple of 16 of at most 128, KSL 1..1024, XB a divisor of BK, at most 16 accumulator blocks a wave, LDS within " + std::to_string(kFbnLdsCap) + " bytes)");
+  } else {
+    auto side = [&](int chans) { return chans <= 32 ? 32 : (flat && chans > 64) ? 128 : 64; };
+    BI = side(g.OC); BJ = side(g.C); BK = 64; XB = flat ? BK : fbn_pick_xb(g, BK);
+    while (BK > 16 && fbn_lds_bytes(g, BI, BJ, BK, XB, r.TR) > kFbnLdsBudget) { BK /= 2; XB = flat ? BK : fbn_pick_xb(g, BK); }
+    if (fbn_lds_bytes(g, BI, BJ, BK, XB, r.TR) > kFbnLdsCap) unsup_err(fn + ": no stage of this geometry fits " + std::to_string(kFbnLdsCap) + " bytes of LDS");
+  }
+  int const YB = BK / XB;
+  r.XB = XB; r.tiles_i = (g.OC + BI - 1) / BI; r.tiles_j = (g.C + BJ - 1) / BJ;
+  long const K = (long)g.B * g.OH * g.OW;
+  r.n_st = flat ? (K + BK - 1) / BK : (long)g.B * ((g.OH + YB - 1) / YB) * ((g.OW + XB - 1) / XB);
+  long const wgs = (long)r.tiles_i * r.tiles_j * r.n_tg;
+  if (!KSL) KSL = (int)std::max<long>(1, std::min<long>(std::min<long>(1024, (4L * num_cus + wgs - 1) / wgs), r.n_st / 4));
+  r.st_per = (int)((r.n_st + KSL - 1) / KSL); r.ksl = (int)((r.n_st + r.st_per - 1) / r.st_per);
+  if (wgs * r.ksl >= (1L << 31) || r.n_st >= (1L << 31)) unsup_err(fn + ": more than 2^31 workgroups");
+  r.grid = (uint32_t)(wgs * r.ksl); r.lds = fbn_lds_bytes(g, BI, BJ, BK, XB, r.TR);
+  plan_t &p = r.p; p.src = kSrc_bconv_fb_nhwc_bf16; p.kname = "bodahip_bconv_fb_nhwc_bf16"; p.nhwc = true; p.bf16 = true;
+  tile_cfg_t &c = p.cfg; c = tile_cfg_t(); c.BI = BI; c.BJ = BJ; c.BK = BK; c.WI = BI >= 64 ? 2 : 1; c.WJ = BJ >= 64 ? 2 : 1; c.MINW = 1; c.SPLITK = r.ksl;
+  r.block = (uint32_t)c.threads();
+  for (auto const &d : {std::make_pair("BI", BI), std::make_pair("BJ", BJ), std::make_pair("BK", BK), std::make_pair("WI", c.WI), std::make_pair("WJ", c.WJ), std::make_pair("XB", XB),
+                        std::make_pair("TR", r.TR), std::make_pair("KH", g.KH), std::make_pair("KW", g.KW), std::make_pair("SY", g.SY), std::make_pair("SX", g.SX), std::make_pair("PY", g.PY),
+                        std::make_pair("PX", g.PX), std::make_pair("SLICED", r.ksl > 1 ? 1 : 0)}) p.defs.push_back(string("-D") + d.first + "=" + std::to_string(d.second));
+  return r;
+}
+
 // ---- the non-conv ops of the gradient pipe (kernels/bck_ops_f32.hip).  Bandwidth kernels: no tile to choose, only the geometry to fold into the code (pooling
 // window / planes; LRN window and channel block) and the grid.
 bck_plan_t plan_bck_op(bck_op_geom_t const &g, int num_cus) {

@@ -128,7 +128,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
   string const &t = op.get_type();
   // a tile that travels with the function (str_val hip_tile: per-op tuned tiles, see tile_override_t) is what run() would use
   auto const ht = op.str_vals.find("hip_tile");
-  string const tile = (tile_arg.empty() && ht != op.str_vals.end()) ? ht->second : tile_arg;
+  string tile = (tile_arg.empty() && ht != op.str_vals.end()) ? ht->second : tile_arg;
   plan_t p; string log, s2d;
   (void)op_zinp_flag(op);   // (refuses the flag on a function that cannot take it)
   (void)op_seed_var_flag(op);   // (likewise)
@@ -140,6 +140,7 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
   std::vector<native_func_t const *> const of_t = native_funcs_of_type(t);
   if (!f && of_t.empty()) rt_err("prebuild: op type '" + t + "' has no native kernel");
   func_family_t const fam = f ? f->family : of_t[0]->family;
+  if (fam != kFamBconvNhwc && is_fbn_tile(tile)) tile.clear();   // (hip_bconv_fb_nhwc's own tile form passes every other function by, as in run(): tune_of)
   int const member = f ? f->member : 0;   // (0: the bare op, or the family's plain form)
   bool const bf16 = (fam == kFamSgemm && member == 1) || (fam == kFamConv && member == kConvBf16);
   if (fam == kFamSgemm) {
@@ -289,6 +290,17 @@ size_t native_kernels_t::prebuild(op_base_t const &op, string const &arch, int n
     else { conv_dw_geom_t const dg = conv_dw_geom_of_op(op); q = plan_conv_nhwc_dw(dg, num_cus, tile); l = conv_nhwc_dw_launch(dg, q.cfg); }
     if (plan_out) { *plan_out = q.kname + " " + q.cfg.str() + " grid=" + std::to_string(l.grid) + " block=" + std::to_string(l.block) + " lds=" + std::to_string(l.lds); for (auto const &d : q.defs) *plan_out += " " + d; }
     return arch.empty() ? 0 : compile_plan(q, arch, &log).size();
+  } else if (fam == kFamBconvNhwc) {   // (kernels/bconv_fb_nhwc_bf16.hip: the main kernel and, with K slices, the slab sum behind it)
+    fbn_plan_t const bp = plan_bconv_fb_nhwc(bconv_nhwc_geom_of_op(op), num_cus, tile);
+    if (plan_out) {
+      *plan_out = bp.p.kname + " " + bp.p.cfg.str() + " grid=" + std::to_string(bp.grid) + " block=" + std::to_string(bp.block) + " lds=" + std::to_string(bp.lds) + " ksl=" + std::to_string(bp.ksl) +
+                  " taps=" + std::to_string(bp.n_tg) + "x" + std::to_string(bp.TR) + " xb=" + std::to_string(bp.XB);
+      if (bp.ksl > 1) *plan_out += " | bodahip_bconv_slab_sum";
+    }
+    if (arch.empty()) return 0;
+    size_t bytes = compile_plan(bp.p, arch, &log).size();
+    if (bp.ksl > 1) bytes += compile_plan(plan_bconv_slab_sum(), arch, &log).size();
+    return bytes;
   } else if (fam == kFamDeconv) {   // (kernels/deconv_f32.hip: the direct forms, specialised by the geometry; a bare op: every function of its type)
     std::vector<int> members;
     if (member) members.push_back(member); else for (native_func_t const *r : of_t) members.push_back(r->member);
@@ -832,6 +844,24 @@ struct native_kernels_t::call_t {
     void *f = var_ptr("filts"), *b = var_ptr("biases"), *f2 = var_ptr("filts2"), *b2 = var_ptr("biases2"), *in = var_ptr("in");
     nk.conv_nhwc_dwpw(g, f, (float const *)b, f2, (float const *)b2, in, var_ptr("out"));
   }
+  void run_bconv_fb_nhwc() {   // likewise: exact dims and element types per arg (one device: no img shards), all vars distinct
+    bconv_nhwc_geom_t const g = bconv_nhwc_geom_of_op(fi.op);
+    auto si = am.find("stride"), pi = am.find("in_pad");
+    if (si == am.end() || pi == am.end()) rt_err(fn + ": 'stride' and 'in_pad' REF args are required");
+    if (!(si->second.get_dims(host->nh_rtc()) == fi.op.get_dims("stride")) || !(pi->second.get_dims(host->nh_rtc()) == fi.op.get_dims("in_pad"))) rt_err(fn + ": stride / in_pad args disagree with the op");
+    std::map<string, string> seen;   // var -> the arg it is bound to
+    auto var_ptr = [&](char const *an) -> void * {
+      string const vn = var_of(am, an);
+      dims_t const vd = host->nh_var_dims(vn), &want = fi.op.get_dims(an);
+      if (!(vd == want) || vd.tn != want.tn) rt_err(fn + ": arg '" + an + "' has dims " + vd.pretty_str() + " (" + vd.tn + "), the op says " + want.pretty_str() + " (" + want.tn + ")");
+      auto ins = seen.emplace(vn, an);
+      if (!ins.second) rt_err(fn + ": args '" + ins.first->second + "' and '" + an + "' are the same var '" + vn + "'");
+      return host->nh_var_ptr(vn);
+    };
+    tile_override_t const tov(impl, "conv_tile", fi.op);
+    void *in = var_ptr("in"), *og = var_ptr("out_grad_loss"), *fg = var_ptr("filts_grad_loss");
+    nk.bconv_fb_nhwc(g, in, og, (float *)fg, (float *)var_ptr("biases_grad_loss"));
+  }
   void run_sgd() {
     // every var must have exactly the dims the op gives its arg (params are no img shards), and the 3n + 1 vars must all be different: w_i and h_i are rewritten in place
     sgd_op_t const so = sgd_op_of_op(fi.op);
@@ -1078,6 +1108,7 @@ void native_kernels_t::run(native_func_t const &f, rtc_func_info_t const &fi, ma
   case kFamConvGrp: c.run_conv_grp(); break;
   case kFamDeconv: c.run_deconv(); break;
   case kFamConvNhwcDw: if (f.member == kConvNhwcDwPw) c.run_conv_nhwc_dwpw(); else c.run_conv_nhwc_dw(); break;
+  case kFamBconvNhwc: c.run_bconv_fb_nhwc(); break;
   }
 }
 

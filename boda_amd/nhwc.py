@@ -231,6 +231,42 @@ def annotate_dw_pw(dw: Op, pw: Op, tile: str = "") -> Op:
     return c
 
 
+BCONV_FB_FUNC = "hip_bconv_fb_nhwc"
+
+
+def annotate_bconv_fb(bck_op: Op, tile: str = "") -> Op:
+    """The function op of hip_bconv_fb_nhwc (kernels/bconv_fb_nhwc_bf16.hip) for a bare BckConv op in the reference layouts: in and
+    out_grad_loss become img:y:x:chan bfloat16 -- the tensors the channels-last forward pass leaves, no channel padding --, filts_grad_loss out_chan:y:x:in_chan
+    float, biases_grad_loss stays float; the op's other tensors (filts, biases, in_grad_loss) are not this function's and go.  `tile`: a fbn:BIxBJxBKxKSL[xXB]
+    work split that travels with the function.  The refusals are bconv_nhwc_geom_of_op's (csrc/native_funcs.h), word for word."""
+    fn = BCONV_FB_FUNC
+    if bck_op.get_type() != "BckConv":
+        raise UnsupErr(f"{fn}: a function of op type BckConv, not {bck_op.get_type()}")
+    grp = bck_op.get_u32("group") if bck_op.has("group") else 1
+    if grp != 1:
+        raise UnsupErr(f"{fn}: group={grp}: ungrouped convolutions only")
+    g = bck_op.bck_conv_geom()
+    if g["C"] < 8 or g["C"] % 8:
+        raise UnsupErr(f"{fn}: in.chan={g['C']} is no multiple of 8 (rows are staged in 16-byte chunks of 8 channels)")
+    if g["OC"] < 8 or g["OC"] % 8:
+        raise UnsupErr(f"{fn}: out_grad_loss.chan={g['OC']} is no multiple of 8 (rows are staged in 16-byte chunks of 8 channels)")
+    if not (1 <= g["KH"] <= 7 and 1 <= g["KW"] <= 7):
+        raise UnsupErr(f"{fn}: kern_sz {g['KH']} x {g['KW']}: kernels of 1..7 rows and columns")
+    if g["SY"] not in (1, 2) or g["SX"] not in (1, 2):
+        raise UnsupErr(f"{fn}: stride {g['SY']} x {g['SX']}: strides of 1 | 2")
+    if g["PY"] >= g["KH"] or g["PX"] >= g["KW"]:
+        raise UnsupErr(f"{fn}: in_pad {g['PY']} x {g['PX']}: padding below the kernel size")
+    if max(2 * g["B"] * g["C"] * g["H"] * g["W"], 2 * g["B"] * g["OC"] * g["OH"] * g["OW"], 4 * g["OC"] * g["C"] * g["KH"] * g["KW"]) >= 0x7ffffff0:
+        raise UnsupErr(f"{fn}: tensors of 2 GiB or more (32-bit offsets)")
+    a = Op({"type": "BckConv", "func_name": fn}, {k: bck_op.nda_vals[k] for k in ("stride", "in_pad", "kern_sz", "out_chans", "biases_grad_loss") if k in bck_op.nda_vals})
+    a.nda_vals["in"] = Nda(dims=Dims(("img", "y", "x", "chan"), (g["B"], g["H"], g["W"], g["C"]), "bfloat16"), tn="bfloat16")
+    a.nda_vals["out_grad_loss"] = Nda(dims=Dims(("img", "y", "x", "chan"), (g["B"], g["OH"], g["OW"], g["OC"]), "bfloat16"), tn="bfloat16")
+    a.nda_vals["filts_grad_loss"] = Nda(dims=Dims(("out_chan", "y", "x", "in_chan"), (g["OC"], g["KH"], g["KW"], g["C"]), "float"), tn="float")
+    if tile:
+        a.str_vals["hip_tile"] = tile
+    return a
+
+
 def _refuse_dw(a: Op, what: str) -> None:
     if a.has_func_name() and a.get_func_name() == DW_FUNC:
         raise UnsupErr(f"{what}: {DW_FUNC} (a depthwise convolution) has no such form: the kernel has no pooling, no residual epilogue and writes whole tensors")
